@@ -20,17 +20,28 @@ value = passages all ranks scored / max-over-ranks time.
 `--mode shard` is the other multi-GPU mode north_star names: ONE query's candidate list (hits=100) is cut into contiguous
 shares over the ranks (13,13,13,13,12,12,12,12 at 8 GPUs), every rank scores its share and ONE engine-issued all_gather per
 query collects the scores; a step is then one QUERY, value = 100 x steps / time ("scaling": "strong" - the work per step is
-fixed as N grows), and after the timed region every rank re-scores the whole query locally and asserts that the gathered
-scores are bit-identical.  Latency-bound by design (M = 12-13 passages per GPU); the weak mode is the throughput mode.
+fixed as N grows), and with --full every rank re-scores the whole query locally after the timed region and asserts that the
+gathered scores are bit-identical.  Latency-bound by design (M = 12-13 passages per GPU); the weak mode is the throughput mode.
 
-The timed region is repeated `--regions` times (default 3, each exactly --steps steps between fences, max over ranks) and the
-MEDIAN region is reported; all of them are listed in config.timed_regions_ms.
+A plain run sets up, runs --warmup untimed steps, times exactly --steps steps between two fences (one timed region, max over
+ranks), writes the outputs if --dump-outputs is given and prints the JSON line; everything else needs `--full`.
 
-Extra objects on the JSON line: `roofline` (the dominant kernel — the FFN-in + GEGLU GEMM — MFMA-bound: algorithmic
-2MNK flops per launch / average launch duration measured with HIP events on the engine's stream in a second, serial,
-profiled pass; the whole tiled-GEMM family beside it), `cpu_baseline` (the reference's CPU path — HF transformers
-fp32 — timed on this box's host cores, rank 0, N=1 only, on a bounded sample of the same workload) and
-`config.per_query` (what the drop-in API delivers one query at a time).
+--dump-outputs DIR: after the timed steps, the scores of the timed path's last launch sequence (the one that holds the last
+step) are written as DIR/scores.npy, float32 [passages, 2] = the yes / no logits a caller of the path receives (rank 0: with
+more than one rank, the gathered scores of all ranks).  Inputs and weights are seeded, so the same arguments give the same inputs.
+
+--full adds what the headline number does not need:
+  * the timed region is repeated `--regions` times (default 3 under --full, each exactly --steps steps between fences) and the
+    MEDIAN region is reported; all of them are listed in config.timed_regions_ms;
+  * config.pipeline_check / config.gather_check: the pipelined scores re-computed by blocking calls (bit-exact);
+  * `roofline` (the dominant kernel — the FFN-in + GEGLU GEMM — MFMA-bound: algorithmic 2MNK flops per launch / average launch
+    duration measured with HIP events on the engine's stream in a second, serial, profiled pass; the whole tiled-GEMM family
+    beside it);
+  * `cpu_baseline` (the reference's CPU path — HF transformers fp32 — timed on this box's host cores, rank 0, N=1 only, on a
+    bounded sample of the same workload);
+  * `config.per_query` (what the drop-in API delivers one query at a time) and the side legs (ragged, shard share, setwise,
+    flan-t5-xl qlm, Llama-3-8B compare).
+The --no_* switches turn single legs of a --full run off.
 """
 import argparse
 import json
@@ -88,7 +99,12 @@ def parse_args():
     ap.add_argument("--mode", default="weak", choices=["weak", "shard"],
                     help="weak: every rank scores its own batches (throughput); shard: one query's hits=100 candidates cut over the ranks, one gather per query")
     ap.add_argument("--hits", type=int, default=100, help="shard mode: candidates per query")
-    ap.add_argument("--regions", type=int, default=3, help="timed regions of exactly --steps steps each; the median is reported")
+    ap.add_argument("--regions", type=int, default=0,
+                    help="timed regions of exactly --steps steps each; the median is reported (0 = 1, or 3 under --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the checks, the roofline pass, the CPU baseline, per-query numbers and the side legs (see the module doc)")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", default=None, metavar="DIR",
+                    help="write the scores of the last timed launch sequence as DIR/scores.npy (float32)")
     ap.add_argument("--no_extras", action="store_true", help="skip the legs after the timed region: ragged (S2), one rank's shard share, setwise (S3), flan-t5-xl qlm (configs[3]), Llama-3-8B compare (configs[4])")
     ap.add_argument("--cpu_batch", type=int, default=32, help="batch size of the cpu_baseline leg (BASELINE.md section 3: 32)")
     ap.add_argument("--dry_ranks", action="store_true",
@@ -431,6 +447,24 @@ def per_query_numbers(eng, dims, B, L):
     return out
 
 
+def dump_outputs(out_dir, eng, pipe, world, bounds=None):
+    """--dump-outputs: the scores of the timed path's last launch sequence as its caller receives them, DIR/scores.npy = float32
+    [passages, 2] yes / no logits; with more than one rank the gathered scores of all ranks in rank order (`bounds`: the
+    candidate shares of --mode shard)."""
+    import numpy as np
+    mine = eng.read_scores(pipe.last_slot)
+    if world == 1:
+        scores = mine
+    else:
+        got = eng.comm_read_gathered(pipe.last_slot)
+        if bounds is not None:
+            scores = np.concatenate([got[r_, :(b_ - a_) * 2] for r_, (a_, b_) in enumerate(bounds)])
+        else:
+            scores = got[:, :mine.size]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "scores.npy"), np.ascontiguousarray(scores, dtype=np.float32).reshape(-1, 2))
+
+
 def main():
     args = parse_args()
     self_spawn(args)
@@ -443,6 +477,10 @@ def main():
     import torch                        # first: its bundled HIP runtime must be the one in the process
     import torch.distributed as dist
     dry = args.dry_ranks
+    if args.regions <= 0:
+        args.regions = 3 if args.full else 1
+    if not args.full:                   # a plain run: the headline number only (module doc)
+        args.no_profile = args.no_per_query = args.no_cpu_baseline = args.no_extras = True
     if dry:
         args.no_profile = args.no_per_query = args.no_cpu_baseline = args.no_extras = True
     elif not torch.cuda.is_available():
@@ -491,10 +529,11 @@ def main():
         rt = T5Runtime.from_engine(eng, dims)
         rt.comm_init_from_process_group(max(G * B * 2, args.hits * 2))
         assert rt.comm_ready() and rt.comm_capacity >= G * B * 2
-    try:
-        rccl = eng.comm_library_info()                     # which librccl this process binds (path | ncclGetVersion code)
-    except Exception as exc:                               # never take a 1-GPU number down: RCCL is only needed for N > 1
-        rccl = f"unavailable: {exc}"
+    if world > 1 or args.full:
+        try:
+            rccl = eng.comm_library_info()                 # which librccl this process binds (path | ncclGetVersion code)
+        except Exception as exc:                           # never take a 1-GPU number down: RCCL is only needed for N > 1
+            rccl = f"unavailable: {exc}"
     if rank == 0:
         print(f"[bench] weights generated + engine finalized in {time.time() - t0:.1f}s; group = {G} batches; rccl = {rccl}", file=sys.stderr)
 
@@ -537,9 +576,12 @@ def main():
     order = sorted(range(len(regions)), key=lambda i: regions[i])
     mid = order[len(order) // 2]
     elapsed, ev_ms = regions[mid], ev_regions[mid]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, eng, pipe, world, bounds if shard else None)
     gather_check = None
     pipeline_check = None
-    if shard:
+    scores = None
+    if shard and args.full:
         # every rank re-scores the WHOLE last query itself: the gathered scores must be those bits (batch independence)
         q = queries[pipe.last_slot]
         if world > 1:
@@ -551,8 +593,8 @@ def main():
         assert np.array_equal(gathered, local_all), f"rank {rank}: gathered scores differ from the locally recomputed ones"
         gather_check = f"gathered == locally recomputed scores of all {args.hits} candidates on every rank (bit-exact)"
         scores = local_all[:B]
-    else:
-        if world > 1:
+    elif not shard:
+        if world > 1 and args.full:
             got = eng.comm_read_gathered(pipe.last_slot)       # [world, G*B*2]: every rank holds every rank's scores
             mine = eng.read_scores(pipe.last_slot).reshape(-1)
             assert got.shape[0] == world and np.array_equal(got[rank, :len(mine)], mine), f"rank {rank}: its own gathered row differs from its scores"
@@ -562,7 +604,7 @@ def main():
         # the pipelined launch sequences (two slots in flight, decoder graphs beside the next encoder) must give the bits of a
         # blocking call on the same batch: batch independence under the conditions of the timed region itself (round 4 found a
         # counted-wait race that only showed here)
-        if not dry:
+        if not dry and args.full:
             for s_ in range(n_slots):
                 piped = eng.read_scores(s_)
                 again = eng.score(pipe.slot_seqs[s_][:len(piped)], [0], [YES_ID, NO_ID])   # (a leftover group re-staged a prefix)

@@ -279,7 +279,11 @@ parser, commands = runmod.build_parser()
 args = runmod.parse_args(parser, commands, json.loads(sys.argv[3]))
 runmod.validate(args)
 runmod.main(args)
-print("CALLS " + json.dumps(engines[0].calls))
+print("CALLS " + json.dumps(engines[0].calls), flush=True)
+import torch.distributed as dist
+if dist.is_initialized():       # an orderly gloo shutdown: leaving the group to interpreter exit can abort a rank (SIGABRT)
+    dist.barrier()
+    dist.destroy_process_group()
 '''
 
 

@@ -10,11 +10,11 @@ if [ -z "$SKIP_TESTS" ]; then timeout 2400 python -m pytest tests -m gpu -q -p n
 bash tools/gpu_prof.sh > $OUT/prof_stdout.txt 2>&1; tail -22 $OUT/prof_stdout.txt | cut -c1-220
 cp gpurun_out/prof/bench_kernel_stats.csv $OUT/ 2>/dev/null; cp gpurun_out/prof/pmc_summary.json $OUT/ 2>/dev/null
 cp gpurun_out/prof/bench_kernel_stats.csv profiles/bench_kernel_stats_latest.csv 2>/dev/null; cp gpurun_out/prof/pmc_summary.json profiles/pmc_summary_latest.json 2>/dev/null
-timeout 1200 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver.json 2> $OUT/bench_driver.err; echo "bench rc=$?"; tail -c 1200 $OUT/bench_driver.json; tail -4 $OUT/bench_driver.err
+timeout 1200 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/bench_driver.json 2> $OUT/bench_driver.err; echo "bench rc=$?"; tail -c 1200 $OUT/bench_driver.json; tail -4 $OUT/bench_driver.err
 if [ -z "$SKIP_SIDE" ]; then
-timeout 600 python bench.py --steps 128 --warmup 16 --no_cpu_baseline --no_per_query --no_extras > $OUT/bench_128.json 2> $OUT/bench_128.err; python -c "
+timeout 600 python bench.py --steps 128 --warmup 16 --full --no_cpu_baseline --no_per_query --no_extras > $OUT/bench_128.json 2> $OUT/bench_128.err; python -c "
 import json; j=json.loads(open('$OUT/bench_128.json').read().strip().splitlines()[-1]); print('128 steps:', j['value'], j['config']['whole_path_frac_of_mfma_peak'], j['roofline']['frac'], j['roofline']['family']['frac'])"
-timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 --mode shard --no_cpu_baseline --no_per_query --no_extras > $OUT/bench_shard_n1.json 2> /dev/null; python -c "
+timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 --mode shard --full --no_cpu_baseline --no_per_query --no_extras > $OUT/bench_shard_n1.json 2> /dev/null; python -c "
 import json; j=json.loads(open('$OUT/bench_shard_n1.json').read().strip().splitlines()[-1]); print('shard mode, 1 rank:', j['value'], j['config']['gather_check'])"
 timeout 600 python bench.py --steps 20 --warmup 5 --group 1 --no_cpu_baseline --no_per_query --no_profile --no_extras > $OUT/bench_group1.json 2> /dev/null; python -c "
 import json; j=json.loads(open('$OUT/bench_group1.json').read().strip().splitlines()[-1]); print('group 1:', j['value'])"
