@@ -1000,7 +1000,7 @@ __device__ __forceinline__ void gemm_wait_vmcnt() {
 // and, if the other is already there, publishes nothing - adds the other slab to its registers (a + b == b + a: the same bits
 // whoever arrives last) and runs the epilogue.  Nobody spins.  (Three / four ways measured slower: every slab re-read.)  A split
 // sums K in another association than one workgroup would: results differ from the unsplit launch in the last fp32 bits; whether a
-// launch is split follows from (M, N, K) alone (host: choose_ksplit), so a call shape always gives the same bits.
+// launch is split follows from (M, N, K) and from whether its stream has a K-split workspace (host: plan_gemm; the slot streams do)
 template <int EPI, int KO = 0, bool RS = false, bool SPLIT = false>
 __global__ __launch_bounds__(512, 2) void gemm_pp2_kernel(GemmArgs p) {
   constexpr int HALF = 128 * 64;

@@ -163,6 +163,7 @@ int fail(rk_engine* e, int code, const char* fmt, ...) {
     hipError_t _s = (call);                                                                          \
     if (_s != hipSuccess) return fail((E), RK_ERR_HIP, "%s failed: %s", #call, hipGetErrorString(_s)); \
   } while (0)
+#define RC(x) do { rc = (x); if (rc) return rc; } while (0)   // (needs an int rc in scope)
 
 template <class T>
 int dalloc(rk_engine* e, T** p, size_t n) {
@@ -257,12 +258,8 @@ void launch_pp2(hipStream_t st, const GemmArgs& a, int max_wgs) {
 // K split of the ping-pong kernel (gemm.h: SPLIT): only the fp32 residual projections (O / FFN-out, Llama o / down), only TWO ways,
 // only when the launch has at most half as many 256 x 256 tiles as the chip has CUs and K >= 6 144 (96 K tiles).  Measured
 // (profiles/r06_gemm_ksplit.txt, M = 1 536, N = 4 096): K = 14 336 281.6 -> 212.0 us, K = 8 192 155.9 -> 123.6 us, K = 4 096
-// 76.9 -> 75.1 us (not worth a different rounding); three / four ways lose (every slab is published and re-read).  A function of
-// (M, N, K) alone.  flan-t5-large / -xl never qualify (K <= 5 120).
-const rk_engine::SkWs* ksplit_workspace(const rk_engine* e, hipStream_t st) {
-  for (const auto& w : e->sk_ws) if (w.st == st && w.slabs) return &w;
-  return nullptr;
-}
+// 76.9 -> 75.1 us (not worth a different rounding); three / four ways lose (every slab is published and re-read).  Needs the
+// workspace of the launch's stream (plan_gemm).  flan-t5-large / -xl never qualify (K <= 5 120).
 int choose_ksplit(const rk_engine* e, int epi, int M, int N, int K) {
   if (!e->opt.gemm_sk || !(epi == EPI_RESID_F32 || epi == EPI_STORE_F32) || K % 64) return 1;
   const long tiles = (long)((M + 255) / 256) * ((N + 255) / 256);
@@ -273,15 +270,15 @@ int choose_ksplit(const rk_engine* e, int epi, int M, int N, int K) {
   return 2;
 }
 
-int choose_variant(const rk_engine* e, int epi, int M, int N, int K, bool fold_producer = false, double* cost_out = nullptr) {
-  if (cost_out) *cost_out = 0;
+int choose_variant(const rk_engine* e, int epi, int M, int N, int K, bool fold_producer, double* cost_out) {
+  *cost_out = 0;
   if (e->opt.gemm_variant) return (e->opt.gemm_variant == 3 && (EPI_IS_GATED(epi) || fold_producer)) ? 2 : e->opt.gemm_variant;
   struct V { int id, bm, bn, slots; double round_us; };
   static const V vs[5] = {{5, 256, 256, 256, 25.5}, {2, 256, 256, 256, 29.8}, {3, 256, 192, 256, 24.7}, {4, 256, 128, 256, 19.0}, {1, 128, 128, 512, 17.3}};
   // 64x64 tiles (variant 6) win only while the larger tiles leave most of the chip idle (tools/gemm_bench.py, r02: O / FFN-out
   // of one or two setwise prompts, M = 1450 / 2900: 12.7 / 15.0 us against 15.7 / 17.4 us on 128x128 tiles; from M = 5888 on,
   // or for the wide QKV / FFN-in outputs, they lose): at most 192 tiles of 128x128
-  if ((long)((M + 127) / 128) * ((N + 127) / 128) <= 192 && K >= 64) { if (cost_out) *cost_out = 15.0; return 6; }
+  if ((long)((M + 127) / 128) * ((N + 127) / 128) <= 192 && K >= 64) { *cost_out = 15.0; return 6; }
   double best = 1e30; int bv = 1;
   for (const V& v : vs) {
     if (v.id == 3 && (EPI_IS_GATED(epi) || fold_producer)) continue;   // (the folded-norm producer needs 64-column wave tiles)
@@ -291,125 +288,178 @@ int choose_variant(const rk_engine* e, int epi, int M, int N, int K, bool fold_p
     if (v.id == 5 && e->opt.gemm_sk == 1 && choose_ksplit(e, epi, M, N, K) > 1) cost = 0.0;   // the K-split launch wins wherever it is eligible (measured)
     if (cost < best - 1e-9) { best = cost; bv = v.id; }
   }
-  if (cost_out) *cost_out = best;
+  *cost_out = best;
   return bv;
 }
 
-// Launch plan of one tiled GEMM: rows [0, m_pp2) on the persistent ping-pong kernel in WHOLE rounds over the CUs, the rest
-// (m_pp2 = 0: everything) on `variant`.  The ping-pong kernel pays a full round for a partial one: the 100 passages of one
-// query (M = 18 400: 72 row panels) are 288 tiles of the O / FFN-out projections = 1.1 rounds paid as 2, 864 of QKV = 3.4 as
-// 4.  All tile variants produce the same bits (K order, epilogue statistics: tests), so the rows beyond the last whole round
-// go to the cheapest fill-in variant as a second launch - same model as choose_variant.  The grouped bench launches (M = 58 880)
-// keep one launch: their last round is 60-98 % full and the model says so.
-struct GemmPlan { int m_pp2; int variant; };
-GemmPlan choose_plan(const rk_engine* e, int epi, int M, int N, int K, bool fold_producer) {
+// Folded RMSNorm hooks of one GEMM launch (GemmArgs): consumer side = rowscale or ssq_in / nb_in, producer side = xraw + ssq.
+#define RK_XRAW_SCALE 0.0625f   // the fp16 copy of the fp32 residual stream is stored x 2^-4: head-room for the outlier
+                                // channels of real T5 checkpoints (fp16 max 65504 -> 1.0e6), exact (power of two)
+struct GemmFold { const float* rowscale = nullptr; half_t* xraw = nullptr; float* ssq = nullptr; const float* ssq_in = nullptr; int nb_in = 0; };
+
+// Kernel family.  It follows from the CALLER's regime, never from M: a row's result must not depend on how many other rows share
+// the launch (the families sum K in different orders).  GEMV: the few-row decoder pass (gemv_rows.h; run_decoder decides from the
+// pass's rows / positions), one wave per output column over all CUs.  STREAM: weight-streaming (gemm_skinny_kernel) - the decoder,
+// per-head batches, the greedy head.  TILED: the MFMA tile kernels.
+enum GemmFamily { GEMM_NONE = -1, GEMM_TILED, GEMM_STREAM, GEMM_GEMV };
+constexpr bool gemv_has(int E) { return E == EPI_STORE_F16 || E == EPI_RESID_F32 || E == EPI_GEGLU_F16 || E == EPI_RELU_F16 || E == EPI_STORE_F32; }
+constexpr bool stream_has(int E) { return E != EPI_LSE_F32; }
+constexpr bool tiled_has(int E) { return E != EPI_ARGMAX_F32; }
+// the rows and K the GEMV kernel takes: all rows staged in LDS, K in 16-byte pieces, at most GEMV_MAX_PIECES per lane
+inline bool gemv_fits(int M, int K) { return M <= GEMV_MAX_ROWS && K % 8 == 0 && K <= 512 * GEMV_MAX_PIECES; }
+
+// One GEMM call, C = epilogue(A [M, K] x W [N, K]^T): the fields every call has in the constructor, the rare ones by name.
+struct Gemm {
+  int cls, epi; const half_t* A; int lda; const half_t* W; int ldw; void* C; int ldc, M, N, K;
+  int n_split = 0; long split_stride = 0;       // GemmArgs::n_split (the stacked cross-attention K / V projection)
+  int batch = 1; long bsA = 0, bsW = 0, bsC = 0;  // per-head GEMMs: `batch` blockIdx.y batches, element strides between them
+  GemmFamily family = GEMM_TILED;
+  GemmFold fold;
+  Gemm(int cls_, int epi_, const half_t* A_, int lda_, const half_t* W_, int ldw_, void* C_, int ldc_, int M_, int N_, int K_)
+      : cls(cls_), epi(epi_), A(A_), lda(lda_), W(W_), ldw(ldw_), C(C_), ldc(ldc_), M(M_), N(N_), K(K_) {}
+  Gemm& heads(int b, long sA, long sW, long sC) { batch = b; bsA = sA; bsW = sW; bsC = sC; return *this; }
+  Gemm& split(int n, long stride) { n_split = n; split_stride = stride; return *this; }
+  Gemm& on(GemmFamily f) { family = f; return *this; }
+  Gemm& with(const GemmFold& f) { fold = f; return *this; }
+};
+
+// Launch plan of one GEMM call: everything gemm() launches, decided here and nowhere else.
+struct GemmPlan {
+  GemmFamily family = GEMM_NONE;   // NONE: no kernel runs the call as described (gemm() fails)
+  int nb = 0;        // partial sums of squares per row the launch writes to fold.ssq: the nb_in of the GEMMs that read them
+  // TILED: rows [0, m_pp2) on the persistent ping-pong kernel in whole rounds over the CUs (K split ks_pp2), the rest on `variant`
+  // (1 = 128x128, 2..4 = 256-row v2 tiles, 5 = ping-pong, 6 = 64x64 with `stages` LDS stages; K split `ksplit` on variant 5)
+  int m_pp2 = 0, ks_pp2 = 1, variant = 0, ksplit = 1, stages = 0;
+  int wgs = 0;       // ping-pong grid: persistent workgroups (<= 0: one per tile)
+  int ko = 0;        // measurement builds: ping-pong knock-out mask (gemm_variant 80 + mask)
+  const rk_engine::SkWs* ks_ws = nullptr;   // the stream's K-split workspace
+  // rows on the persistent ping-pong kernel?  A folded-norm consumer there takes its row factors ready-made (rowscale_kernel in
+  // front of it); every other kernel forms them from the producer's block sums itself.
+  bool pp2() const { return family == GEMM_TILED && (m_pp2 > 0 || variant == 5); }
+};
+
+// Tiled family: the ping-pong kernel pays a full round for a partial one: the 100 passages of one query (M = 18 400: 72 row panels)
+// are 288 tiles of the O / FFN-out projections = 1.1 rounds paid as 2, 864 of QKV = 3.4 as 4.  All tile variants produce the same
+// bits (K order, epilogue statistics: tests), so the rows beyond the last whole round go to the cheapest fill-in variant as a second
+// launch - same model as choose_variant.  The grouped bench launches (M = 58 880) keep one launch: their last round is 60-98 % full
+// and the model says so.
+// A function of the call, the options and the CU count; its one stream-dependent input is the K split, which needs a workspace
+// of the launch's stream (rk_engine::sk_ws: the slot streams have one).
+GemmPlan plan_gemm(const rk_engine* e, const Gemm& c, hipStream_t st) {
+  GemmPlan p;
+  const int epi = c.epi, M = c.M, N = c.N, K = c.K;
+  if (c.family == GEMM_GEMV) {                   // marked few-row by the caller: this kernel or none
+    if (gemv_has(epi) && gemv_fits(M, K) && c.batch == 1 && c.n_split == 0) {
+      p.family = GEMM_GEMV;
+      p.nb = gemv_grid(N, e->n_cu);              // producer: one partial sum of squares per workgroup
+    }
+    return p;
+  }
+  if ((c.family == GEMM_STREAM || c.batch > 1) && c.n_split == 0 && (((e->opt.skinny >> epi) & 1) || c.batch > 1 || epi == EPI_ARGMAX_F32)) {
+    if (stream_has(epi)) { p.family = GEMM_STREAM; p.nb = (N + 31) / 32; }   // producer blocks of 32 columns
+    return p;
+  }
+  if (!tiled_has(epi)) return p;
+  p.family = GEMM_TILED;
+  p.nb = (N + 63) / 64;                          // producer blocks of 64 columns
+  p.wgs = e->opt.gemm_persistent == 1 ? (e->n_cu & ~7) : (e->opt.gemm_persistent & ~7);
+  for (const auto& w : e->sk_ws) if (!p.ks_ws && w.st == st && w.slabs) p.ks_ws = &w;
+  auto ksplit = [&](int rows) { return e->opt.gemm_persistent == 1 && p.ks_ws ? choose_ksplit(e, epi, rows, N, K) : 1; };
+  const bool fold_producer = c.fold.xraw != nullptr;
   double whole = 0;
-  GemmPlan plan{0, choose_variant(e, epi, M, N, K, fold_producer, &whole)};
-  if (!e->opt.gemm_split || e->opt.gemm_variant || K < 128 || e->opt.gemm_persistent != 1) return plan;
-  if (!(epi == EPI_STORE_F16 || epi == EPI_RESID_F32 || EPI_IS_GATED(epi) || epi == EPI_RELU_F16)) return plan;   // (the heads index rows from 0)
-  const int wgs = e->n_cu & ~7, tiles_n = (N + 255) / 256, tiles_m = (M + 255) / 256;
-  const long rounds = (long)tiles_m * tiles_n / wgs;
-  if (rounds < 1 || (long)tiles_m * tiles_n % wgs == 0) return plan;
-  const int panels = (int)(rounds * wgs / tiles_n);          // whole row panels inside the whole rounds
-  if (panels < 1 || panels >= tiles_m) return plan;
-  const long used = (long)panels * tiles_n;
-  double rest = 0;
-  const int v_rest = choose_variant(e, epi, M - panels * 256, N, K, fold_producer, &rest);
-  const double split = (double)((used + wgs - 1) / wgs) * 25.5 + rest + 1.5;   // + a kernel boundary
-  if (split < whole - 1e-9) { plan.m_pp2 = panels * 256; plan.variant = v_rest; }
-  return plan;
-}
-
-// does a folded-norm consumer GEMM of this shape run the persistent ping-pong kernel (row factors from rowscale_kernel)?
-bool consumer_uses_pp2(const rk_engine* e, int epi, int M, int N, int K) {
-  const GemmPlan pl = choose_plan(e, epi, M, N, K, false);
-  int v = pl.variant;
-  if (v > 6) v = 5;
-  return pl.m_pp2 > 0 || (v == 5 && K >= 128);
-}
-
-template <int EPI>
-void launch_gemm_epi(rk_engine* e, hipStream_t st, const GemmArgs& a_in, int force_variant = 0) {
-  GemmArgs a = a_in;
-  int variant = force_variant;
-  if (!variant) {
-    const GemmPlan pl = choose_plan(e, EPI, a.M, a.N, a.K, a.xraw != nullptr);
-    variant = pl.variant;
-    if (pl.m_pp2 > 0) {
-      // whole rounds on the ping-pong kernel, then the remaining rows on the fill-in variant (row-offset arguments)
-      GemmArgs head = a;
-      head.M = pl.m_pp2;
-      launch_gemm_epi<EPI>(e, st, head, 5);
-      const size_t r = (size_t)pl.m_pp2;
-      constexpr size_t celt = (EPI == EPI_RESID_F32 || EPI == EPI_STORE_F32) ? 4 : 2;
-      a.A += r * a.lda;
-      a.C = (char*)a.C + r * (size_t)a.ldc * celt;
-      if (a.rowscale) a.rowscale += r;
-      if (a.xraw) a.xraw += r * a.ldx;
-      if (a.ssq) a.ssq += r * a.nb;
-      if (a.ssq_in) a.ssq_in += r * a.nb_in;
-      a.M -= pl.m_pp2;
+  p.variant = choose_variant(e, epi, M, N, K, fold_producer, &whole);
+  if (e->opt.gemm_split && !e->opt.gemm_variant && K >= 128 && e->opt.gemm_persistent == 1 &&
+      (epi == EPI_STORE_F16 || epi == EPI_RESID_F32 || EPI_IS_GATED(epi) || epi == EPI_RELU_F16)) {   // (the heads index rows from 0)
+    const int tiles_n = (N + 255) / 256, tiles_m = (M + 255) / 256;
+    const long rounds = (long)tiles_m * tiles_n / p.wgs;
+    const int panels = (int)(rounds * p.wgs / tiles_n);          // whole row panels inside the whole rounds
+    if (rounds >= 1 && (long)tiles_m * tiles_n % p.wgs != 0 && panels >= 1 && panels < tiles_m) {
+      const long used = (long)panels * tiles_n;
+      double rest = 0;
+      const int v_rest = choose_variant(e, epi, M - panels * 256, N, K, fold_producer, &rest);
+      if ((double)((used + p.wgs - 1) / p.wgs) * 25.5 + rest + 1.5 < whole - 1e-9) {   // (+ 1.5: a kernel boundary)
+        p.m_pp2 = panels * 256; p.ks_pp2 = ksplit(p.m_pp2); p.variant = v_rest;
+      }
     }
   }
 #ifdef RK_MEASURE
-  if constexpr (EPI == EPI_STORE_F16) {                              // timing-only knock-outs (gemm_variant 80 + mask)
-    if (variant > 80 && variant <= 96 && a.K >= 128) {
-      switch (variant - 80) {
-        case 8: launch_pp2<EPI, 8>(st, a, (e->opt.gemm_persistent == 1 ? (e->n_cu & ~7) : (e->opt.gemm_persistent & ~7))); return;    // no W-panel DMA
-        case 16: launch_pp2<EPI, 16>(st, a, (e->opt.gemm_persistent == 1 ? (e->n_cu & ~7) : (e->opt.gemm_persistent & ~7))); return;  // no A-panel DMA
-        case 1: launch_pp2<EPI, 1>(st, a, (e->opt.gemm_persistent == 1 ? (e->n_cu & ~7) : (e->opt.gemm_persistent & ~7))); return;
-        case 2: launch_pp2<EPI, 2>(st, a, (e->opt.gemm_persistent == 1 ? (e->n_cu & ~7) : (e->opt.gemm_persistent & ~7))); return;
-        case 3: launch_pp2<EPI, 3>(st, a, (e->opt.gemm_persistent == 1 ? (e->n_cu & ~7) : (e->opt.gemm_persistent & ~7))); return;
-        case 4: launch_pp2<EPI, 4>(st, a, (e->opt.gemm_persistent == 1 ? (e->n_cu & ~7) : (e->opt.gemm_persistent & ~7))); return;
-        case 5: launch_pp2<EPI, 5>(st, a, (e->opt.gemm_persistent == 1 ? (e->n_cu & ~7) : (e->opt.gemm_persistent & ~7))); return;
-        default: launch_pp2<EPI, 6>(st, a, (e->opt.gemm_persistent == 1 ? (e->n_cu & ~7) : (e->opt.gemm_persistent & ~7))); return;
-      }
+  if (epi == EPI_STORE_F16 && p.variant > 80 && p.variant <= 96 && K >= 128) { p.ko = p.variant - 80; p.variant = 5; return p; }
+#endif
+  if (p.variant > 6) p.variant = 5;
+  if (p.variant == 5 && K < 128) p.variant = 2;                   // the ping-pong kernel needs two K tiles
+  if (p.variant == 5) p.ksplit = ksplit(M - p.m_pp2);
+  if (p.variant == 6) {
+    // stages: as many as keep every tile resident at once (4 -> 2 workgroups per CU, 3 -> 3, 2 -> 4)
+    const int tiles = ((M - p.m_pp2 + 63) / 64) * ((N + 63) / 64);
+    p.stages = e->opt.s64_stages;
+    if (p.stages < 2 || p.stages > 4) p.stages = tiles <= 2 * e->n_cu ? 4 : (tiles <= 3 * e->n_cu ? 3 : 2);
+  }
+  return p;
+}
+
+template <int EPI, int NST>
+void launch_s64(hipStream_t st, const GemmArgs& a) {
+  constexpr int smem = NST * 16384;
+  static std::atomic<uint64_t> attr_done{0};
+  ensure_dynamic_lds((const void*)gemm_s64_kernel<EPI, NST>, smem, attr_done);
+  hipLaunchKernelGGL((gemm_s64_kernel<EPI, NST>), dim3(((a.M + 63) / 64) * ((a.N + 63) / 64)), dim3(128), smem, st, a);
+}
+
+// one ping-pong launch of the plan with K split ks
+template <int EPI>
+void launch_pp2_plan(hipStream_t st, GemmArgs a, const GemmPlan& p, int ks) {
+#ifdef RK_MEASURE
+  if constexpr (EPI == EPI_STORE_F16) {                              // timing-only knock-outs
+    switch (p.ko) {
+      case 0: break;
+      case 8: launch_pp2<EPI, 8>(st, a, p.wgs); return;              // no W-panel DMA
+      case 16: launch_pp2<EPI, 16>(st, a, p.wgs); return;            // no A-panel DMA
+      case 1: launch_pp2<EPI, 1>(st, a, p.wgs); return;
+      case 2: launch_pp2<EPI, 2>(st, a, p.wgs); return;
+      case 3: launch_pp2<EPI, 3>(st, a, p.wgs); return;
+      case 4: launch_pp2<EPI, 4>(st, a, p.wgs); return;
+      case 5: launch_pp2<EPI, 5>(st, a, p.wgs); return;
+      default: launch_pp2<EPI, 6>(st, a, p.wgs); return;
     }
   }
 #endif
-  if (variant == 6) {
-    const int tiles = ((a.M + 63) / 64) * ((a.N + 63) / 64);
-    // stages: as many as keep every tile resident at once (4 -> 2 workgroups per CU, 3 -> 3, 2 -> 4)
-    int nst = e->opt.s64_stages;
-    if (nst < 2 || nst > 4) nst = tiles <= 2 * e->n_cu ? 4 : (tiles <= 3 * e->n_cu ? 3 : 2);
-    if (nst == 4) {
-      static std::atomic<uint64_t> attr_done{0};
-      ensure_dynamic_lds((const void*)gemm_s64_kernel<EPI, 4>, 65536, attr_done);
-      hipLaunchKernelGGL((gemm_s64_kernel<EPI, 4>), dim3(tiles), dim3(128), 65536, st, a);
-    } else if (nst == 3) {
-      static std::atomic<uint64_t> attr_done{0};
-      ensure_dynamic_lds((const void*)gemm_s64_kernel<EPI, 3>, 49152, attr_done);
-      hipLaunchKernelGGL((gemm_s64_kernel<EPI, 3>), dim3(tiles), dim3(128), 49152, st, a);
-    } else {
-      static std::atomic<uint64_t> attr_done{0};
-      ensure_dynamic_lds((const void*)gemm_s64_kernel<EPI, 2>, 32768, attr_done);
-      hipLaunchKernelGGL((gemm_s64_kernel<EPI, 2>), dim3(tiles), dim3(128), 32768, st, a);
-    }
-    return;
+  if constexpr (EPI == EPI_STORE_F16 || EPI_IS_GATED(EPI) || EPI == EPI_RELU_F16) {
+    if (a.rowscale) { launch_pp2<EPI, 0, true>(st, a, p.wgs); return; }   // consumer side of the folded RMSNorm
   }
-  if (variant > 6) variant = 5;
-  if (variant == 5 && a.K < 128) variant = 2;                       // the ping-pong kernel needs two K tiles
-  if (variant == 5) {
-    const int wgs = e->opt.gemm_persistent == 1 ? (e->n_cu & ~7) : (e->opt.gemm_persistent & ~7);
-    if constexpr (EPI == EPI_STORE_F16 || EPI_IS_GATED(EPI) || EPI == EPI_RELU_F16) {
-      if (a.rowscale) { launch_pp2<EPI, 0, true>(st, a, wgs); return; }   // consumer side of the folded RMSNorm
-    }
-    if constexpr (EPI == EPI_RESID_F32 || EPI == EPI_STORE_F32) {
-      const int ks = e->opt.gemm_persistent == 1 ? choose_ksplit(e, EPI, a.M, a.N, a.K) : 1;
-      const rk_engine::SkWs* w = ks > 1 ? ksplit_workspace(e, st) : nullptr;
-      if (w) {
-        GemmArgs b = a;
-        b.ksplit = ks; b.ks_slabs = w->slabs; b.ks_cnt = w->cnt;
-        launch_pp2<EPI, 0, false, true>(st, b, wgs);
-        return;
-      }
-    }
-    launch_pp2<EPI>(st, a, wgs);
-    return;
+  if constexpr (EPI == EPI_RESID_F32 || EPI == EPI_STORE_F32) {
+    if (ks > 1) { a.ksplit = ks; a.ks_slabs = p.ks_ws->slabs; a.ks_cnt = p.ks_ws->cnt; launch_pp2<EPI, 0, false, true>(st, a, p.wgs); return; }
   }
-  if (variant == 2) { launch_v2<EPI, 2, 4, 4, 2>(st, a); return; }
-  if constexpr (!EPI_IS_GATED(EPI)) { if (variant == 3) { launch_v2<EPI, 4, 2, 2, 3>(st, a); return; } }
-  if (variant == 4) { launch_v2<EPI, 4, 2, 2, 2>(st, a); return; }
+  launch_pp2<EPI>(st, a, p.wgs);
+}
+
+template <int EPI>
+void launch_tiled(const rk_engine* e, hipStream_t st, GemmArgs a, const GemmPlan& p) {
+  if (p.m_pp2 > 0) {
+    // whole rounds on the ping-pong kernel, then the remaining rows on the fill-in variant (row-offset arguments)
+    GemmArgs head = a;
+    head.M = p.m_pp2;
+    launch_pp2_plan<EPI>(st, head, p, p.ks_pp2);
+    const size_t r = (size_t)p.m_pp2;
+    constexpr size_t celt = (EPI == EPI_RESID_F32 || EPI == EPI_STORE_F32) ? 4 : 2;
+    a.A += r * a.lda;
+    a.C = (char*)a.C + r * (size_t)a.ldc * celt;
+    if (a.rowscale) a.rowscale += r;
+    if (a.xraw) a.xraw += r * a.ldx;
+    if (a.ssq) a.ssq += r * a.nb;
+    if (a.ssq_in) a.ssq_in += r * a.nb_in;
+    a.M -= p.m_pp2;
+  }
+  switch (p.variant) {
+    case 6:
+      if (p.stages == 4) launch_s64<EPI, 4>(st, a);
+      else if (p.stages == 3) launch_s64<EPI, 3>(st, a);
+      else launch_s64<EPI, 2>(st, a);
+      return;
+    case 5: launch_pp2_plan<EPI>(st, a, p, p.ksplit); return;
+    case 2: launch_v2<EPI, 2, 4, 4, 2>(st, a); return;
+    case 3: if constexpr (!EPI_IS_GATED(EPI)) { launch_v2<EPI, 4, 2, 2, 3>(st, a); return; } break;
+    case 4: launch_v2<EPI, 4, 2, 2, 2>(st, a); return;
+  }
   // (a 16-wave 256x256 form, launch_v2<EPI, 4, 4, 2, 2>, measured 3-9 % slower than the 8-wave one: not instantiated)
   const int tiles = ((a.M + GEMM_BM - 1) / GEMM_BM) * ((a.N + GEMM_BN - 1) / GEMM_BN);
   if (e->opt.glds)
@@ -418,87 +468,65 @@ void launch_gemm_epi(rk_engine* e, hipStream_t st, const GemmArgs& a_in, int for
     hipLaunchKernelGGL((gemm_f16_kernel<EPI, false>), dim3(tiles), dim3(256), GEMM_LDS_BYTES, st, a);
 }
 
-// Folded RMSNorm hooks of one GEMM launch (GemmArgs): consumer side = rowscale, producer side = xraw + ssq.
-#define RK_XRAW_SCALE 0.0625f   // the fp16 copy of the fp32 residual stream is stored x 2^-4: head-room for the outlier
-                                // channels of real T5 checkpoints (fp16 max 65504 -> 1.0e6), exact (power of two)
-struct GemmFold { const float* rowscale = nullptr; half_t* xraw = nullptr; float* ssq = nullptr; const float* ssq_in = nullptr; int nb_in = 0;
-                  bool few = false; };   // few: the few-row GEMV family (gemv_rows.h; run_decoder decides from the pass's rows / positions)
-
-GemmArgs make_gemm_args(const rk_engine* e, const half_t* A, int lda, const half_t* W, int ldw, void* C, int ldc, int M, int N, int K,
-                        int n_split, long split_stride, float scale, long bsA, long bsW, long bsC, const GemmFold& fold) {
-  GemmArgs a{A, W, C, lda, ldw, ldc, M, N, K, n_split, split_stride, scale, bsA, bsW, bsC};
-  a.rowscale = fold.rowscale; a.xraw = fold.xraw; a.ssq = fold.ssq; a.ldx = N; a.nb = (N + 63) / 64; a.xs = RK_XRAW_SCALE;
-  a.ssq_in = fold.ssq_in; a.nb_in = fold.nb_in ? fold.nb_in : (K + 63) / 64; a.eps_in = e->d.eps;       // (tiled producers: 64-column blocks)
-  a.group_n = GEMM_GROUP_N;
-  return a;
+template <int EPI, int MR>
+void launch_gemv(const rk_engine* e, hipStream_t st, const GemmArgs& a) {
+  const int smem = MR * a.K * 2 + (GEMV_MAX_ROWS + 4 * GEMV_MAX_ROWS) * 4;
+  static std::atomic<uint64_t> attr_done{0};
+  if (smem > 65536) ensure_dynamic_lds((const void*)gemv_rows_kernel<EPI, MR>, 160 * 1024, attr_done);
+  hipLaunchKernelGGL((gemv_rows_kernel<EPI, MR>), dim3(gemv_grid(EPI_IS_GATED(EPI) ? a.N / 2 : a.N, e->n_cu)), dim3(256), smem, st, a);
 }
 
-void gemm(rk_engine* e, hipStream_t st, int cls, int epi, const half_t* A, int lda, const half_t* W, int ldw, void* C,
-          int ldc, int M, int N, int K, int n_split = 0, long split_stride = 0, float scale = 1.f,
-          int batch = 1, long bsA = 0, long bsW = 0, long bsC = 0, bool weight_streaming = false, GemmFold fold = GemmFold()) {
-  if (M <= 0) return;
-  GemmArgs a = make_gemm_args(e, A, lda, W, ldw, C, ldc, M, N, K, n_split, split_stride, scale, bsA, bsW, bsC, fold);
-  const double flops = 2.0 * M * (double)N * K * batch;
-  const double out_elems = EPI_IS_GATED(epi) ? (double)M * N / 2 : (double)M * N;
-  const double bytes = 2.0 * ((double)M * K + (double)N * K) +
-                       out_elems * (epi == EPI_RESID_F32 ? 8.0 : (epi == EPI_STORE_F32 ? 4.0 : 2.0));
-  Bracket br(e, st, cls, flops, bytes);
-  // Few-row GEMV family (gemv_rows.h): the decoder pass of ONE setwise compare (run_decoder sets fold.few from the pass's row and
-  // position counts): one wave per output column over all CUs instead of 32-column MFMA tiles.
-  if (fold.few && weight_streaming && batch == 1 && n_split == 0 && M <= GEMV_MAX_ROWS && K % 8 == 0 && K <= 512 * GEMV_MAX_PIECES &&
-      (epi == EPI_STORE_F16 || epi == EPI_RESID_F32 || epi == EPI_GEGLU_F16 || epi == EPI_RELU_F16 || epi == EPI_STORE_F32)) {
-    const int n_out = EPI_IS_GATED(epi) ? N / 2 : N;
-    const int grid = gemv_grid(n_out, e->n_cu);
-    a.nb = gemv_grid(N, e->n_cu);                                   // producer: one partial sum of squares per workgroup
-    const int mr = M <= 2 ? 2 : (M <= 4 ? 4 : (M <= 8 ? 8 : 16));
-    const int smem = mr * K * 2 + (GEMV_MAX_ROWS + 4 * GEMV_MAX_ROWS) * 4;
-    auto go = [&](auto kern) {
-      static std::atomic<uint64_t> attr_done{0};
-      if (smem > 65536) ensure_dynamic_lds((const void*)kern, 160 * 1024, attr_done);
-      hipLaunchKernelGGL(kern, dim3(grid), dim3(256), smem, st, a);
-    };
-#define RK_GEMV_CASE(E)                                                                                                   \
-    case E: if (mr == 2) go(gemv_rows_kernel<E, 2>); else if (mr == 4) go(gemv_rows_kernel<E, 4>);                        \
-            else if (mr == 8) go(gemv_rows_kernel<E, 8>); else go(gemv_rows_kernel<E, 16>); break;
-    switch (epi) {
-      RK_GEMV_CASE(EPI_STORE_F16) RK_GEMV_CASE(EPI_RESID_F32) RK_GEMV_CASE(EPI_GEGLU_F16) RK_GEMV_CASE(EPI_STORE_F32)
-      default: if (mr == 2) go(gemv_rows_kernel<EPI_RELU_F16, 2>); else if (mr == 4) go(gemv_rows_kernel<EPI_RELU_F16, 4>);
-               else if (mr == 8) go(gemv_rows_kernel<EPI_RELU_F16, 8>); else go(gemv_rows_kernel<EPI_RELU_F16, 16>); break;
+template <int EPI>
+void launch_stream(hipStream_t st, const GemmArgs& a, int batch) {
+  // (a form where one workgroup takes up to 8 row slabs - 8x fewer, fatter workgroups - was bit-identical but made
+  // the step 6 % slower: what the decoder costs the concurrent encoder GEMMs is the serial LENGTH of its chain, every
+  // kernel delaying some tile of the GEMM in flight, not its CU-time; so: many short workgroups)
+  // (tried and dropped, round 3: a 1-D launch that runs all row slabs of a column block on ONE XCD, so that a weight row is
+  // fetched into one L2 only - dec_gemm 0.337 vs 0.328 ms per step at 320 rows: the slabs are not bound by weight traffic)
+  constexpr int NT = EPI_IS_GATED(EPI) ? 2 : 1;                    // gated: the gate and up blocks of 32 columns together
+  hipLaunchKernelGGL((gemm_skinny_kernel<EPI, NT>), dim3((a.N + 32 * NT - 1) / (32 * NT), batch, (a.M + 31) / 32), dim3(SKINNY_THREADS), 0, st, a);
+}
+
+// f(std::integral_constant<int, epi>): the one map from the runtime epilogue kind (0 .. EPI_LSE_F32) to the kernel templates
+template <int E = 0, class F>
+void with_epi(int epi, F&& f) {
+  if (epi == E) f(std::integral_constant<int, E>());
+  else if constexpr (E < EPI_LSE_F32) with_epi<E + 1>(epi, f);
+}
+
+// Runs plan_gemm's plan of the call.  *nb (optional): the plan's statistics layout, for the GEMMs that read what this one produced.
+int gemm(rk_engine* e, hipStream_t st, const Gemm& c, int* nb = nullptr) {
+  if (c.M <= 0) return RK_OK;
+  const GemmPlan p = plan_gemm(e, c, st);
+  if (p.family == GEMM_NONE)
+    return fail(e, RK_ERR_STATE, "no kernel of family %d takes the GEMM M=%d N=%d K=%d (epilogue %d, batch %d)", (int)c.family, c.M, c.N, c.K, c.epi, c.batch);
+  if (nb) *nb = p.nb;
+  GemmArgs a{c.A, c.W, c.C, c.lda, c.ldw, c.ldc, c.M, c.N, c.K, c.n_split, c.split_stride, 1.f, c.bsA, c.bsW, c.bsC};
+  a.rowscale = c.fold.rowscale; a.xraw = c.fold.xraw; a.ssq = c.fold.ssq; a.ldx = c.N; a.nb = p.nb; a.xs = RK_XRAW_SCALE;
+  a.ssq_in = c.fold.ssq_in; a.nb_in = c.fold.nb_in; a.eps_in = e->d.eps;
+  a.group_n = GEMM_GROUP_N;
+  if (c.epi == EPI_ARGMAX_F32) a.amax_idx = e->amax_idx;
+  if (c.epi == EPI_LSE_F32) { a.lse_labels = e->lse_labels; a.lse_npos = e->lse_npos; a.lse_xlab = e->lse_xlab; }
+  const double flops = 2.0 * c.M * (double)c.N * c.K * c.batch;
+  const double out_elems = EPI_IS_GATED(c.epi) ? (double)c.M * c.N / 2 : (double)c.M * c.N;
+  const double bytes = 2.0 * ((double)c.M * c.K + (double)c.N * c.K) +
+                       out_elems * (c.epi == EPI_RESID_F32 ? 8.0 : (c.epi == EPI_STORE_F32 ? 4.0 : 2.0));
+  Bracket br(e, st, c.cls, flops, bytes);
+  with_epi(c.epi, [&](auto E) {
+    constexpr int EPI = decltype(E)::value;
+    if constexpr (gemv_has(EPI)) {
+      if (p.family == GEMM_GEMV) {
+        if (a.M <= 2) launch_gemv<EPI, 2>(e, st, a);            // rows staged per workgroup
+        else if (a.M <= 4) launch_gemv<EPI, 4>(e, st, a);
+        else if (a.M <= 8) launch_gemv<EPI, 8>(e, st, a);
+        else launch_gemv<EPI, 16>(e, st, a);
+        return;
+      }
     }
-#undef RK_GEMV_CASE
-    return;
-  }
-  // Kernel family is chosen by the CALLER's regime, never by M: a row's result must not depend on how many other rows
-  // share the launch (the split-K weight-streaming kernel and the tiled kernels sum K in different orders).
-  if ((weight_streaming || batch > 1) && n_split == 0 && (((e->opt.skinny >> epi) & 1) || batch > 1 || epi == EPI_ARGMAX_F32)) {
-    // (a form where one workgroup takes up to 8 row slabs - 8x fewer, fatter workgroups - was bit-identical but made
-    // the step 6 % slower: what the decoder costs the concurrent encoder GEMMs is the serial LENGTH of its chain, every
-    // kernel delaying some tile of the GEMM in flight, not its CU-time; so: many short workgroups)
-    const dim3 b(SKINNY_THREADS);
-    const unsigned gy = (unsigned)batch, gz = (unsigned)((M + 31) / 32);
-    a.nb = (N + 31) / 32; a.nb_in = fold.nb_in ? fold.nb_in : (K + 31) / 32;   // this kernel's own producer blocks are 32 columns wide
-    // (tried and dropped, round 3: a 1-D launch that runs all row slabs of a column block on ONE XCD, so that a weight row is
-    // fetched into one L2 only - dec_gemm 0.337 vs 0.328 ms per step at 320 rows: the slabs are not bound by weight traffic)
-    switch (epi) {
-      case EPI_STORE_F16: hipLaunchKernelGGL((gemm_skinny_kernel<EPI_STORE_F16, 1>), dim3((N + 31) / 32, gy, gz), b, 0, st, a); break;
-      case EPI_RESID_F32: hipLaunchKernelGGL((gemm_skinny_kernel<EPI_RESID_F32, 1>), dim3((N + 31) / 32, gy, gz), b, 0, st, a); break;
-      case EPI_GEGLU_F16: hipLaunchKernelGGL((gemm_skinny_kernel<EPI_GEGLU_F16, 2>), dim3((N + 63) / 64, gy, gz), b, 0, st, a); break;
-      case EPI_SWIGLU_F16: hipLaunchKernelGGL((gemm_skinny_kernel<EPI_SWIGLU_F16, 2>), dim3((N + 63) / 64, gy, gz), b, 0, st, a); break;
-      case EPI_RELU_F16: hipLaunchKernelGGL((gemm_skinny_kernel<EPI_RELU_F16, 1>), dim3((N + 31) / 32, gy, gz), b, 0, st, a); break;
-      case EPI_ARGMAX_F32: a.amax_idx = e->amax_idx; hipLaunchKernelGGL((gemm_skinny_kernel<EPI_ARGMAX_F32, 1>), dim3((N + 31) / 32, gy, gz), b, 0, st, a); break;
-      default: hipLaunchKernelGGL((gemm_skinny_kernel<EPI_STORE_F32, 1>), dim3((N + 31) / 32, gy, gz), b, 0, st, a); break;
-    }
-    return;
-  }
-  switch (epi) {
-    case EPI_STORE_F16: launch_gemm_epi<EPI_STORE_F16>(e, st, a); break;
-    case EPI_RESID_F32: launch_gemm_epi<EPI_RESID_F32>(e, st, a); break;
-    case EPI_GEGLU_F16: launch_gemm_epi<EPI_GEGLU_F16>(e, st, a); break;
-    case EPI_SWIGLU_F16: launch_gemm_epi<EPI_SWIGLU_F16>(e, st, a); break;
-    case EPI_RELU_F16: launch_gemm_epi<EPI_RELU_F16>(e, st, a); break;
-    case EPI_LSE_F32: a.lse_labels = e->lse_labels; a.lse_npos = e->lse_npos; a.lse_xlab = e->lse_xlab; launch_gemm_epi<EPI_LSE_F32>(e, st, a); break;
-    default: launch_gemm_epi<EPI_STORE_F32>(e, st, a); break;
-  }
+    if constexpr (stream_has(EPI)) { if (p.family == GEMM_STREAM) { launch_stream<EPI>(st, a, c.batch); return; } }
+    if constexpr (tiled_has(EPI)) { if (p.family == GEMM_TILED) launch_tiled<EPI>(e, st, a, p); }
+  });
+  return RK_OK;
 }
 
 void rmsnorm(rk_engine* e, hipStream_t st, const float* x, const float* w, half_t* out, const int* row_map, int rows, float scale = 1.f) {
@@ -519,9 +547,8 @@ void embed(rk_engine* e, hipStream_t st, const int* ids, float* out, int rows, h
 }
 
 // folded RMSNorm: block sums of squares (left by the residual GEMM epilogue) -> row factors
-void rowscale(rk_engine* e, hipStream_t st, const float* ssq, float* out, int rows, int nb = 0) {   // nb: block sums per row (0: 64-column blocks)
+void rowscale(rk_engine* e, hipStream_t st, const float* ssq, float* out, int rows, int nb) {   // nb: block sums per row (the producer's plan)
   if (rows <= 0) return;
-  if (nb <= 0) nb = (e->d.d_model + 63) / 64;
   Bracket br(e, st, PC_NORM, 0, (double)rows * (nb + 1) * 4.0);
   hipLaunchKernelGGL(rowscale_kernel, dim3((rows + 255) / 256), dim3(256), 0, st, ssq, out, rows, nb, e->d.d_model, e->d.eps, RK_XRAW_SCALE);
 }
@@ -601,23 +628,26 @@ int run_encoder(rk_engine* e, Slot& sl, bool need_cross_kv) {
   // producer of the stream: embedding / residual epilogue), their weights carry the norm weight, and their epilogue
   // applies the row factor - the two norm kernels per layer (re-reading the fp32 stream) are gone.
   const bool fold = e->opt.fold_norm != 0;
-  GemmFold cons, cons_ssq, prod;
-  if (fold) { cons.rowscale = sl.rowscale; cons_ssq.ssq_in = sl.ssq; prod.xraw = sl.xraw; prod.ssq = sl.ssq; }
-  // The persistent ping-pong GEMM takes its row factors ready-made (loaded under its last MFMAs): a rowscale_kernel runs in
-  // front of it.  The fill-in tile variants of small launches (one setwise prompt) add the block sums themselves in their
-  // epilogue (gemm_row_factors, same rk_row_factor -> same bits): two 5-us launches per layer less where launches are what costs.
-  const bool qkv_pp2 = !e->opt.consumer_stats || consumer_uses_pp2(e, EPI_STORE_F16, T, 3 * I, dm);
-  const bool ffn_pp2 = !e->opt.consumer_stats || consumer_uses_pp2(e, d.gated_gelu ? EPI_GEGLU_F16 : EPI_RELU_F16, T, d.gated_gelu ? 2 * F : F, dm);
+  half_t* const xin = fold ? sl.xraw : sl.xn;   // what the GEMMs behind a norm read
+  GemmFold prod;                                // producer side: the residual GEMMs (but the last: the final norm reads the fp32 stream)
+  if (fold) { prod.xraw = sl.xraw; prod.ssq = sl.ssq; }
+  int nb = 0, rc = RK_OK;                       // block sums per row of the last residual GEMM (0: the embedding wrote the row factors)
+  // The GEMM c behind a norm.  Folded, the persistent ping-pong GEMM takes its row factors ready-made (loaded under its last
+  // MFMAs): a rowscale_kernel runs in front of it.  The fill-in tile variants of small launches (one setwise prompt) add the block
+  // sums themselves in their epilogue (gemm_row_factors, same rk_row_factor -> same bits): two 5-us launches per layer less where
+  // launches are what costs.
+  auto normed = [&](const float* ln, Gemm c) {
+    GemmFold f;
+    if (!fold) rmsnorm(e, st, sl.hidden, ln, sl.xn, nullptr, T);
+    else if (nb && e->opt.consumer_stats && !plan_gemm(e, c, st).pp2()) { f.ssq_in = sl.ssq; f.nb_in = nb; }
+    else { if (nb) rowscale(e, st, sl.ssq, sl.rowscale, T, nb); f.rowscale = sl.rowscale; }
+    return c.with(f);
+  };
   embed(e, st, sl.d_tokens, sl.hidden, T, fold ? sl.xraw : nullptr, fold ? sl.rowscale : nullptr);
   for (int l = 0; l < d.n_enc_layers; ++l) {
     const EncLayerW& w = e->enc[l];
-    if (fold) {
-      gemm(e, st, PC_ENC_GEMM_QKV, EPI_STORE_F16, sl.xraw, dm, w.qkv_f, dm, sl.qkv, 3 * I, T, 3 * I, dm, 0, 0, 1.f, 1, 0, 0, 0, false,
-           (l == 0 || qkv_pp2) ? cons : cons_ssq);            // layer 0: the embedding kernel wrote the row factors
-    } else {
-      rmsnorm(e, st, sl.hidden, w.ln0, sl.xn, nullptr, T);
-      gemm(e, st, PC_ENC_GEMM_QKV, EPI_STORE_F16, sl.xn, dm, w.qkv, dm, sl.qkv, 3 * I, T, 3 * I, dm);
-    }
+    const bool last = l + 1 == d.n_enc_layers;
+    RC(gemm(e, st, normed(w.ln0, Gemm(PC_ENC_GEMM_QKV, EPI_STORE_F16, xin, dm, fold ? w.qkv_f : w.qkv, dm, sl.qkv, 3 * I, T, 3 * I, dm))));
     {
       // Every sequence of the batch at most ATT_ROW_MAXL keys: the DMA kernel (attn_short = 5, the default: two six-wave groups
       // per 768-thread workgroup; 6: one group per workgroup); otherwise, or with attn_short = 0, the tiled kernel.  The two
@@ -671,31 +701,16 @@ int run_encoder(rk_engine* e, Slot& sl, bool need_cross_kv) {
       else   // option attn_long = 0: the tiled kernel for every length (the on-device cross-check of the two DMA kernels)
         hipLaunchKernelGGL(attn_enc_kernel, dim3((sl.maxL + 127) / 128, d.n_heads, sl.n_seq), dim3(256), 0, st, a);
     }
-    if (fold) {
-      gemm(e, st, PC_ENC_GEMM_O, EPI_RESID_F32, sl.ctx, I, w.o, I, sl.hidden, dm, T, dm, I, 0, 0, 1.f, 1, 0, 0, 0, false, prod);
-      if (ffn_pp2) rowscale(e, st, sl.ssq, sl.rowscale, T);
-      if (d.gated_gelu)
-        gemm(e, st, PC_ENC_GEMM_FFN_IN, EPI_GEGLU_F16, sl.xraw, dm, w.ffn_in_f, dm, sl.ffh, F, T, 2 * F, dm, 0, 0, 1.f, 1, 0, 0, 0, false, ffn_pp2 ? cons : cons_ssq);
-      else
-        gemm(e, st, PC_ENC_GEMM_FFN_IN, EPI_RELU_F16, sl.xraw, dm, w.ffn_in_f, dm, sl.ffh, F, T, F, dm, 0, 0, 1.f, 1, 0, 0, 0, false, ffn_pp2 ? cons : cons_ssq);
-      const bool last = l + 1 == d.n_enc_layers;   // the final norm reads the fp32 stream itself
-      gemm(e, st, PC_ENC_GEMM_FFN_OUT, EPI_RESID_F32, sl.ffh, F, w.ffn_out, F, sl.hidden, dm, T, dm, F, 0, 0, 1.f, 1, 0, 0, 0, false, last ? GemmFold() : prod);
-      if (!last && qkv_pp2) rowscale(e, st, sl.ssq, sl.rowscale, T);
-      continue;
-    }
-    gemm(e, st, PC_ENC_GEMM_O, EPI_RESID_F32, sl.ctx, I, w.o, I, sl.hidden, dm, T, dm, I);
-    rmsnorm(e, st, sl.hidden, w.ln1, sl.xn, nullptr, T);
-    if (d.gated_gelu)
-      gemm(e, st, PC_ENC_GEMM_FFN_IN, EPI_GEGLU_F16, sl.xn, dm, w.ffn_in, dm, sl.ffh, F, T, 2 * F, dm);
-    else
-      gemm(e, st, PC_ENC_GEMM_FFN_IN, EPI_RELU_F16, sl.xn, dm, w.ffn_in, dm, sl.ffh, F, T, F, dm);
-    gemm(e, st, PC_ENC_GEMM_FFN_OUT, EPI_RESID_F32, sl.ffh, F, w.ffn_out, F, sl.hidden, dm, T, dm, F);
+    RC(gemm(e, st, Gemm(PC_ENC_GEMM_O, EPI_RESID_F32, sl.ctx, I, w.o, I, sl.hidden, dm, T, dm, I).with(prod), &nb));
+    RC(gemm(e, st, normed(w.ln1, Gemm(PC_ENC_GEMM_FFN_IN, d.gated_gelu ? EPI_GEGLU_F16 : EPI_RELU_F16, xin, dm, fold ? w.ffn_in_f : w.ffn_in, dm,
+                                      sl.ffh, F, T, d.gated_gelu ? 2 * F : F, dm))));
+    RC(gemm(e, st, Gemm(PC_ENC_GEMM_FFN_OUT, EPI_RESID_F32, sl.ffh, F, w.ffn_out, F, sl.hidden, dm, T, dm, F).with(last ? GemmFold() : prod), &nb));
   }
   rmsnorm(e, st, sl.hidden, e->enc_final_ln, sl.enc_out, nullptr, T);
   // the stacked K/V projections are only materialised when the decoder has too many rows for the query-side form
   if (need_cross_kv)
-    gemm(e, st, PC_GEMM_CROSS_KV, EPI_STORE_F16, sl.enc_out, dm, e->cross_kv_w, dm, sl.cross_kv, 2 * I, T,
-         d.n_dec_layers * 2 * I, dm, 2 * I, (long)d.max_tokens * 2 * I);
+    RC(gemm(e, st, Gemm(PC_GEMM_CROSS_KV, EPI_STORE_F16, sl.enc_out, dm, e->cross_kv_w, dm, sl.cross_kv, 2 * I, T, d.n_dec_layers * 2 * I, dm)
+                       .split(2 * I, (long)d.max_tokens * 2 * I)));
   sl.have_cross_kv = need_cross_kv;
   HIPCHK(e, hipGetLastError());
   return RK_OK;
@@ -722,8 +737,6 @@ int run_decoder(rk_engine* e, Slot& sl, int Ld, const DecTree* tree = nullptr) {
   // those with the norm weight folded into its matrix and forms the row factor itself (gemm.h: GemmArgs::ssq_in) - three
   // launches per layer less.  A producer never writes the buffer a workgroup of the same launch may still read: two of each.
   const bool dfold = ws && e->opt.dec_fold_norm && (e->opt.skinny & 0x3F) == 0x3F;
-  int cur = 0; bool from_embed = true;
-  // (the producers of dssq are weight-streaming GEMMs: 32-column blocks, whichever kernel family consumes them)
   // Few-row GEMV family (round 6, gemv_rows.h): the pass of ONE setwise / pairwise prompt - a handful of rows at two or more
   // positions ("<pad> Passage": 2 rows; the second greedy step: 3) - runs its plain projections one wave per output column over all
   // CUs.  Decided from the PASS (rows, positions), so every row of a pass takes one family; a row scored alone and the same row in
@@ -734,37 +747,42 @@ int run_decoder(rk_engine* e, Slot& sl, int Ld, const DecTree* tree = nullptr) {
   // 12 rows 12.86 / 12.36, 16 rows 15.18 / 14.58 (profiles/r06_few_rows_ab.txt) - every workgroup stages ALL rows in LDS and the
   // per-column VALU work grows with the rows; rk_t5_greedy2's 13-row tree pass stays on the matrix cores.
   const bool fuse_any = (e->opt.dec_fuse == 2 || (e->opt.dec_fuse == 1 && Ld == 1));
-  const bool few = dfold && e->opt.dec_gemv && Ld >= 2 && M <= e->opt.dec_gemv_rows && !fuse_any && dm <= 512 * GEMV_MAX_PIECES && F <= 512 * GEMV_MAX_PIECES &&
-                   dm % 8 == 0 && F % 8 == 0 && I % 8 == 0;
-  const int nb_few = gemv_grid(dm, e->n_cu);
-  auto cons = [&]() {
-    GemmFold f; f.few = few;
-    if (from_embed) f.rowscale = sl.drowscale;
-    else if (few) { f.ssq_in = sl.dssq_few[cur]; f.nb_in = nb_few; }
-    else { f.ssq_in = sl.dssq[cur]; f.nb_in = (dm + 31) / 32; }
+  const bool few = dfold && e->opt.dec_gemv && Ld >= 2 && M <= e->opt.dec_gemv_rows && !fuse_any &&
+                   gemv_fits(M, dm) && gemv_fits(M, I) && gemv_fits(M, F);   // every K of the pass's projections
+  const GemmFamily fam = few ? GEMM_GEMV : (ws ? GEMM_STREAM : GEMM_TILED);
+  // folded: the stream is dxraw[cur] with nb block sums per row in ssq[cur] (nb: the plan of the GEMM that wrote them; 0: the
+  // embedding wrote the row factors)
+  float* const* ssq = few ? sl.dssq_few : sl.dssq;
+  int cur = 0, nb = 0, rc = RK_OK;
+  auto xin = [&]() { return dfold ? sl.dxraw[cur] : sl.dxn; };   // what the GEMMs behind a norm read
+  auto norm = [&](const float* ln) {                              // ... and their row factors
+    GemmFold f;
+    if (!dfold) rmsnorm(e, st, sl.dhidden, ln, sl.dxn, nullptr, M);
+    else if (!nb) f.rowscale = sl.drowscale;
+    else { f.ssq_in = ssq[cur]; f.nb_in = nb; }
     return f;
   };
-  auto with_prod = [&](GemmFold f) { f.few = few; f.xraw = sl.dxraw[cur ^ 1]; f.ssq = few ? sl.dssq_few[cur ^ 1] : sl.dssq[cur ^ 1]; return f; };
-  auto flip = [&]() { cur ^= 1; from_embed = false; };
+  // a residual GEMM (fp32 stream += c); folded and `stats` (all but the last: the head's norm reads the fp32 stream) it also leaves
+  // the next fp16 copy of the stream and its block sums
+  auto resid = [&](Gemm c, bool stats = true) {
+    if (!(dfold && stats)) return gemm(e, st, c.on(fam));
+    c.fold.xraw = sl.dxraw[cur ^ 1]; c.fold.ssq = ssq[cur ^ 1];
+    cur ^= 1;                                                     // the GEMMs from here on read what this one writes
+    return gemm(e, st, c.on(fam), &nb);
+  };
   embed(e, st, sl.d_dec_ids, sl.dhidden, M, dfold ? sl.dxraw[0] : nullptr, dfold ? sl.drowscale : nullptr);
   const size_t smem_self = (64 + 256 + 8 + (size_t)Ld) * sizeof(float);
   const size_t smem_cross = (64 + 256 + 8 + (size_t)sl.maxL) * sizeof(float);
   for (int l = 0; l < d.n_dec_layers; ++l) {
     const DecLayerW& w = e->dec[l];
-    if (!dfold) rmsnorm(e, st, sl.dhidden, w.ln0, sl.dxn, nullptr, M);
+    const GemmFold in0 = norm(w.ln0);
     if (Ld == 1) {
       // one decoder position: softmax over a single key is 1, so self-attention is exactly o(v(x)) — the q/k
       // projections, scores and bias are dead (hf: modeling_t5.py:448-509 at L_d = 1)
       // ... and o(v(x)) = (W_o W_v) x: one GEMM with the product matrix formed once at finalize
-      if (dfold) {
-        gemm(e, st, PC_DEC_GEMM, EPI_RESID_F32, sl.dxraw[cur], dm, w.ov_f, dm, sl.dhidden, dm, M, dm, dm, 0, 0, 1.f, 1, 0, 0, 0, ws, with_prod(cons()));
-        flip();
-      } else {
-        gemm(e, st, PC_DEC_GEMM, EPI_RESID_F32, sl.dxn, dm, w.ov, dm, sl.dhidden, dm, M, dm, dm, 0, 0, 1.f, 1, 0, 0, 0, ws);
-      }
+      RC(resid(Gemm(PC_DEC_GEMM, EPI_RESID_F32, xin(), dm, dfold ? w.ov_f : w.ov, dm, sl.dhidden, dm, M, dm, dm).with(in0)));
     } else {
-      if (dfold) gemm(e, st, PC_DEC_GEMM, EPI_STORE_F16, sl.dxraw[cur], dm, w.qkv_f, dm, sl.dqkv, 3 * I, M, 3 * I, dm, 0, 0, 1.f, 1, 0, 0, 0, ws, cons());
-      else gemm(e, st, PC_DEC_GEMM, EPI_STORE_F16, sl.dxn, dm, w.qkv, dm, sl.dqkv, 3 * I, M, 3 * I, dm, 0, 0, 1.f, 1, 0, 0, 0, ws);
+      RC(gemm(e, st, Gemm(PC_DEC_GEMM, EPI_STORE_F16, xin(), dm, dfold ? w.qkv_f : w.qkv, dm, sl.dqkv, 3 * I, M, 3 * I, dm).on(fam).with(in0)));
       AttnDecArgs a{sl.dqkv, 3 * I, sl.dqkv + I, sl.dqkv + 2 * I, 3 * I, nullptr, sl.dctx, I, e->lut_dec, Ld, 1, Ld};
       {
         Bracket br(e, st, PC_DEC_ATTN, 4.0 * M * Ld * I, 0);
@@ -781,8 +799,7 @@ int run_decoder(rk_engine* e, Slot& sl, int Ld, const DecTree* tree = nullptr) {
           hipLaunchKernelGGL(attn_dec_kernel, dim3(Ld, d.n_heads, B), dim3(256), smem_self, st, a);
         }
       }
-      gemm(e, st, PC_DEC_GEMM, EPI_RESID_F32, sl.dctx, I, w.o, I, sl.dhidden, dm, M, dm, I, 0, 0, 1.f, 1, 0, 0, 0, ws, dfold ? with_prod(GemmFold()) : GemmFold());
-      if (dfold) flip();
+      RC(resid(Gemm(PC_DEC_GEMM, EPI_RESID_F32, sl.dctx, I, w.o, I, sl.dhidden, dm, M, dm, I)));
     }
     // Query-side cross-attention with the projections around it fused per (head, row slab) - decoder_kernels.h: the q
     // projection + W_k^T q in one launch, the chunk merge + W_v in another (dec_fuse = 1, the default): 3 launches instead of 5
@@ -791,11 +808,8 @@ int run_decoder(rk_engine* e, Slot& sl, int Ld, const DecTree* tree = nullptr) {
     // the cold weights of a layer over 512 + 5120 workgroups).  The family follows from the CALL SHAPE, never from the batch
     // (the two round differently): fused for one decoder position, separate beyond (dec_fuse = 2 forces the fused form: tests)
     const bool fuse = (e->opt.dec_fuse == 2 || (e->opt.dec_fuse == 1 && Ld == 1)) && !sl.have_cross_kv && dm % 128 == 0;   // (eight K ranges of whole k16 steps per workgroup)
-    if (!dfold) rmsnorm(e, st, sl.dhidden, w.ln1, sl.dxn, nullptr, M);
-    if (!fuse) {
-      if (dfold) gemm(e, st, PC_DEC_GEMM, EPI_STORE_F16, sl.dxraw[cur], dm, w.cq_f, dm, sl.dq, I, M, I, dm, 0, 0, 1.f, 1, 0, 0, 0, ws, cons());
-      else gemm(e, st, PC_DEC_GEMM, EPI_STORE_F16, sl.dxn, dm, w.cq, dm, sl.dq, I, M, I, dm, 0, 0, 1.f, 1, 0, 0, 0, ws);
-    }
+    const GemmFold in1 = norm(w.ln1);
+    if (!fuse) RC(gemm(e, st, Gemm(PC_DEC_GEMM, EPI_STORE_F16, xin(), dm, dfold ? w.cq_f : w.cq, dm, sl.dq, I, M, I, dm).on(fam).with(in1)));
     if (!sl.have_cross_kv) {
       // query-side cross-attention: qk = W_k^T q per head; scores/softmax/weighted sum over the raw encoder states;
       // ctx = W_v (.) per head  (attention.h: XAttnArgs)
@@ -805,9 +819,8 @@ int run_decoder(rk_engine* e, Slot& sl, int Ld, const DecTree* tree = nullptr) {
       for (int r0 = 0; r0 < M; r0 += blk) {
         const int nr = std::min(blk, M - r0);
         if (fuse) {
-          const GemmFold cf = dfold ? cons() : GemmFold();
-          DecQKArgs qa{(dfold ? sl.dxraw[cur] : sl.dxn) + (size_t)r0 * dm, dm, dfold ? w.cq_f : w.cq, w.ckT, sl.xqk, nr, dm, H,
-                       cf.rowscale ? cf.rowscale + r0 : nullptr, cf.ssq_in ? cf.ssq_in + (size_t)r0 * cf.nb_in : nullptr, cf.nb_in, d.eps, RK_XRAW_SCALE, 32, 1};
+          DecQKArgs qa{xin() + (size_t)r0 * dm, dm, dfold ? w.cq_f : w.cq, w.ckT, sl.xqk, nr, dm, H,
+                       in1.rowscale ? in1.rowscale + r0 : nullptr, in1.ssq_in ? in1.ssq_in + (size_t)r0 * in1.nb_in : nullptr, in1.nb_in, d.eps, RK_XRAW_SCALE, 32, 1};
           if (e->opt.dec_fuse_rows > 0) qa.R = std::min(32, e->opt.dec_fuse_rows);
           else if (nr <= 16) qa.R = 16;   // (a setwise pass: 13 rows - half the MFMA columns, half the x rows; measured at 320 rows: 32 > 16 > 8)
           // few rows: several workgroups per (head, slab) share the output columns, each streaming 1 / CS of W_k^T (and all of W_q,h)
@@ -815,7 +828,7 @@ int run_decoder(rk_engine* e, Slot& sl, int Ld, const DecTree* tree = nullptr) {
           Bracket br(e, st, PC_DEC_GEMM, 2.0 * nr * (double)dm * I * 2, 2.0 * ((double)I * dm * 2 + (double)nr * H * dm));
           hipLaunchKernelGGL(dec_cross_qk_kernel, dim3(H, (nr + qa.R - 1) / qa.R, qa.CS), dim3(64 * DEC_NW), 0, st, qa);
         } else {
-          gemm(e, st, PC_DEC_GEMM, EPI_STORE_F16, sl.dq + (size_t)r0 * I, I, w.ckT, 64, sl.xqk, H * dm, nr, dm, 64, 0, 0, 1.f, H, 64, (long)dm * 64, dm);
+          RC(gemm(e, st, Gemm(PC_DEC_GEMM, EPI_STORE_F16, sl.dq + (size_t)r0 * I, I, w.ckT, 64, sl.xqk, H * dm, nr, dm, 64).heads(H, 64, (long)dm * 64, dm)));
         }
         XAttnArgs xa{sl.xqk, sl.enc_out, sl.d_seq_off, sl.xpart, sl.xstat, sl.xctx, Ld, H, dm, nch, r0, tree ? tree->seq : nullptr};
         const bool fuse_cv = fuse && nch <= DECV_MAXCH;
@@ -846,7 +859,7 @@ int run_decoder(rk_engine* e, Slot& sl, int Ld, const DecTree* tree = nullptr) {
           Bracket br(e, st, PC_DEC_GEMM, 2.0 * nr * (double)dm * I, 2.0 * (double)I * dm + 4.0 * (double)nr * nch * H * dm);
           hipLaunchKernelGGL(dec_cross_cv_kernel, dim3(H, (nr + R - 1) / R), dim3(64 * DEC_NW), lds, st, ca);
         } else {
-          gemm(e, st, PC_DEC_GEMM, EPI_STORE_F16, sl.xctx, H * dm, wv, dm, sl.dctx + (size_t)r0 * I, I, nr, 64, dm, 0, 0, 1.f, H, dm, (long)64 * dm, 64);
+          RC(gemm(e, st, Gemm(PC_DEC_GEMM, EPI_STORE_F16, sl.xctx, H * dm, wv, dm, sl.dctx + (size_t)r0 * I, I, nr, 64, dm).heads(H, dm, (long)64 * dm, 64)));
         }
       }
     } else {
@@ -865,42 +878,29 @@ int run_decoder(rk_engine* e, Slot& sl, int Ld, const DecTree* tree = nullptr) {
       else
         hipLaunchKernelGGL(attn_dec_kernel, dim3(Ld, d.n_heads, B), dim3(256), smem_cross, st, a);
     }
-    if (dfold) {
-      gemm(e, st, PC_DEC_GEMM, EPI_RESID_F32, sl.dctx, I, w.co, I, sl.dhidden, dm, M, dm, I, 0, 0, 1.f, 1, 0, 0, 0, ws, with_prod(GemmFold()));
-      flip();
-      {
-        // ONE decoder position (pointwise yes_no, MonoT5): FFN-in runs on the TILED kernels whatever the number of rows.  Its
-        // 5632 output columns are 176 column blocks x (rows / 32) workgroups for the weight-streaming kernel - 1760 at the
-        // bench's 320 rows, 29.9 us per layer - against 440 tiles of 64x64 on the matrix cores, 14.5 us (dec_gemm 0.32 ->
-        // 0.28 ms per step, +0.9 % passages/s).  The family follows from the call shape (L_d == 1), never from the batch, so a
-        // row's bits still do not depend on what shares its launch; the other projections of the layer (1024 columns: 80 tiles)
-        // measured the same on either family and stay where they were.
-        const bool tiled_in = e->opt.dec_ffn_tiled && Ld == 1;
-        const int epi_in = d.gated_gelu ? EPI_GEGLU_F16 : EPI_RELU_F16, n_in = d.gated_gelu ? 2 * F : F;
-        GemmFold cf = cons();
-        if (tiled_in && cf.ssq_in && consumer_uses_pp2(e, epi_in, M, n_in, dm)) {
-          // (many rows, or a forced tile shape: the persistent ping-pong kernel takes its row factors ready-made - same block
-          // sums, same rk_row_factor, same bits as the fill-in kernels form in their epilogue)
-          rowscale(e, st, cf.ssq_in, sl.drowscale, M, cf.nb_in);
-          cf = GemmFold(); cf.rowscale = sl.drowscale;
-        }
-        gemm(e, st, PC_DEC_GEMM, epi_in, sl.dxraw[cur], dm, w.ffn_in_f, dm, sl.dffh, F, M, n_in, dm, 0, 0, 1.f, 1, 0, 0, 0, tiled_in ? false : ws, cf);
+    RC(resid(Gemm(PC_DEC_GEMM, EPI_RESID_F32, sl.dctx, I, w.co, I, sl.dhidden, dm, M, dm, I)));
+    {
+      // ONE decoder position (pointwise yes_no, MonoT5), folded: FFN-in runs on the TILED kernels whatever the number of rows.  Its
+      // 5632 output columns are 176 column blocks x (rows / 32) workgroups for the weight-streaming kernel - 1760 at the
+      // bench's 320 rows, 29.9 us per layer - against 440 tiles of 64x64 on the matrix cores, 14.5 us (dec_gemm 0.32 ->
+      // 0.28 ms per step, +0.9 % passages/s).  The family follows from the call shape (L_d == 1), never from the batch, so a
+      // row's bits still do not depend on what shares its launch; the other projections of the layer (1024 columns: 80 tiles)
+      // measured the same on either family and stay where they were.
+      const bool tiled_in = dfold && e->opt.dec_ffn_tiled && Ld == 1;
+      Gemm in = Gemm(PC_DEC_GEMM, d.gated_gelu ? EPI_GEGLU_F16 : EPI_RELU_F16, xin(), dm, dfold ? w.ffn_in_f : w.ffn_in, dm, sl.dffh, F, M,
+                     d.gated_gelu ? 2 * F : F, dm).on(tiled_in ? GEMM_TILED : fam);
+      GemmFold f = norm(w.ln2);
+      if (f.ssq_in && plan_gemm(e, in, st).pp2()) {
+        // (many rows, or a forced tile shape: the persistent ping-pong kernel takes its row factors ready-made - same block
+        // sums, same rk_row_factor, same bits as the fill-in kernels form in their epilogue)
+        rowscale(e, st, f.ssq_in, sl.drowscale, M, f.nb_in);
+        f = GemmFold(); f.rowscale = sl.drowscale;
       }
-      const bool last = l + 1 == d.n_dec_layers;   // the final norm (head kernels) reads the fp32 stream itself
-      // (the same switch for FFN-out - 80 tiles of 64x64 with 44 K steps each - took 9 us per layer off the serial profile and
-      // nothing measurable off the pipeline: left on the weight-streaming kernel)
-      GemmFold plain; plain.few = few;
-      gemm(e, st, PC_DEC_GEMM, EPI_RESID_F32, sl.dffh, F, w.ffn_out, F, sl.dhidden, dm, M, dm, F, 0, 0, 1.f, 1, 0, 0, 0, ws, last ? plain : with_prod(GemmFold()));
-      if (!last) flip();
-      continue;
+      RC(gemm(e, st, in.with(f)));
     }
-    gemm(e, st, PC_DEC_GEMM, EPI_RESID_F32, sl.dctx, I, w.co, I, sl.dhidden, dm, M, dm, I, 0, 0, 1.f, 1, 0, 0, 0, ws);
-    rmsnorm(e, st, sl.dhidden, w.ln2, sl.dxn, nullptr, M);
-    if (d.gated_gelu)
-      gemm(e, st, PC_DEC_GEMM, EPI_GEGLU_F16, sl.dxn, dm, w.ffn_in, dm, sl.dffh, F, M, 2 * F, dm, 0, 0, 1.f, 1, 0, 0, 0, ws);
-    else
-      gemm(e, st, PC_DEC_GEMM, EPI_RELU_F16, sl.dxn, dm, w.ffn_in, dm, sl.dffh, F, M, F, dm, 0, 0, 1.f, 1, 0, 0, 0, ws);
-    gemm(e, st, PC_DEC_GEMM, EPI_RESID_F32, sl.dffh, F, w.ffn_out, F, sl.dhidden, dm, M, dm, F, 0, 0, 1.f, 1, 0, 0, 0, ws);
+    // (the tiled form for FFN-out - 80 tiles of 64x64 with 44 K steps each - took 9 us per layer off the serial profile and
+    // nothing measurable off the pipeline: left on the weight-streaming kernel)
+    RC(resid(Gemm(PC_DEC_GEMM, EPI_RESID_F32, sl.dffh, F, w.ffn_out, F, sl.dhidden, dm, M, dm, F), l + 1 < d.n_dec_layers));
   }
   HIPCHK(e, hipGetLastError());
   return RK_OK;
@@ -1368,7 +1368,6 @@ int rk_engine_finalize(rk_engine* e) {
     }
     return v;
   };
-#define RC(x) do { rc = (x); if (rc) return rc; } while (0)
   RC(up_h(&e->emb, H("shared.weight")));
   if (d.tied_head) e->lm_head = e->emb; else RC(up_h(&e->lm_head, H("lm_head.weight")));
   RC(up_f(&e->enc_final_ln, Fv("encoder.final_layer_norm.weight")));
@@ -1447,14 +1446,13 @@ int rk_engine_finalize(rk_engine* e) {
     RC(dalloc(e, &d_vT, (size_t)dm * I)); RC(dalloc(e, &d_ov32, (size_t)dm * dm));
     std::vector<half_t> vT((size_t)dm * I), ov16((size_t)dm * dm);
     std::vector<float> ov32((size_t)dm * dm);
-    const int saved_variant = e->opt.gemm_variant;
     for (int l = 0; l < d.n_dec_layers; ++l) {
       const std::string p = "decoder.block." + std::to_string(l) + ".layer.0.SelfAttention.";
       const auto& wv = H(p + "v.weight");
       for (int j = 0; j < I; ++j)
         for (int k = 0; k < dm; ++k) vT[(size_t)k * I + j] = wv[(size_t)j * dm + k];
       HIPCHK(e, hipMemcpy(d_vT, vT.data(), vT.size() * 2, hipMemcpyHostToDevice));
-      gemm(e, e->slots[0].se, PC_OTHER, EPI_STORE_F32, e->dec[l].o, I, d_vT, I, d_ov32, dm, dm, dm, I);
+      RC(gemm(e, e->slots[0].se, Gemm(PC_OTHER, EPI_STORE_F32, e->dec[l].o, I, d_vT, I, d_ov32, dm, dm, dm, I)));
       HIPCHK(e, hipStreamSynchronize(e->slots[0].se));
       HIPCHK(e, hipMemcpy(ov32.data(), d_ov32, ov32.size() * 4, hipMemcpyDeviceToHost));
       for (size_t i = 0; i < ov32.size(); ++i) ov16[i] = (half_t)ov32[i];
@@ -1463,7 +1461,6 @@ int rk_engine_finalize(rk_engine* e) {
       for (size_t i = 0; i < ov32.size(); ++i) ov16[i] = (half_t)(ov32[i] * ln0[i % dm]);
       RC(up_h(&e->dec[l].ov_f, ov16));
     }
-    e->opt.gemm_variant = saved_variant;
     HIPCHK(e, hipGetLastError());
   }
   e->host.clear();
@@ -1492,7 +1489,6 @@ int rk_engine_finalize(rk_engine* e) {
     HIPCHK(e, hipHostMalloc((void**)&sl.h_scores, e->scores_cap * sizeof(float), hipHostMallocDefault));
     HIPCHK(e, hipHostMalloc((void**)&sl.h_small, 4 * 8192 * sizeof(int), hipHostMallocDefault));
   }
-#undef RC
   // dynamic-LDS opt-in for the kernels that may exceed the 64 KiB default
   const int dec_smem_max = (int)((64 + 256 + 8 + (size_t)std::max(d.max_tokens, d.max_dec_len)) * sizeof(float));
   if (dec_smem_max > 160 * 1024) { /* checked per call against maxL */ }
@@ -1583,7 +1579,7 @@ int rk_t5_qlm(rk_engine* e, const int32_t* tokens, const int32_t* seq_offsets, i
   // head GEMM with the log-sum-exp fused into its epilogue: per row and 32-column block (max, sum exp) + the label's logit
   const int nblk = (e->d.vocab + 31) / 32;
   e->lse_labels = sl.d_labels; e->lse_npos = n_labels; e->lse_xlab = e->logits + (size_t)M * nblk * 2;
-  gemm(e, sd, PC_HEAD, EPI_LSE_F32, sl.dxn, e->d.d_model, e->lm_head, e->d.d_model, e->logits, nblk, M, e->d.vocab, e->d.d_model);
+  RC(gemm(e, sd, Gemm(PC_HEAD, EPI_LSE_F32, sl.dxn, e->d.d_model, e->lm_head, e->d.d_model, e->logits, nblk, M, e->d.vocab, e->d.d_model)));
   hipLaunchKernelGGL(qlm_lse_kernel, dim3(n_seq), dim3(256), 0, sd, (const float2*)e->logits, nblk, e->lse_xlab, n_labels, sl.d_scores);
   HIPCHK(e, hipMemcpyAsync(sl.h_scores, sl.d_scores, (size_t)n_seq * sizeof(float), hipMemcpyDeviceToHost, sd));
   if ((rc = mark_decoder_done(e, sl))) return rc;
@@ -1610,10 +1606,11 @@ static int ensure_amax(rk_engine* e, size_t rows, int vocab) {
   e->amax_rows = rows;
   return RK_OK;
 }
-static void head_argmax(rk_engine* e, hipStream_t st, const half_t* x, int rows, int d_model, int vocab, int* d_out) {
+static int head_argmax(rk_engine* e, hipStream_t st, const half_t* x, int rows, int d_model, int vocab, int* d_out) {
   const int nblk = (vocab + 31) / 32;
-  gemm(e, st, PC_HEAD, EPI_ARGMAX_F32, x, d_model, e->lm_head, d_model, e->amax_val, nblk, rows, vocab, d_model, 0, 0, 1.f, 1, 0, 0, 0, true);
-  hipLaunchKernelGGL(argmax_blocks_kernel, dim3(rows), dim3(256), 0, st, e->amax_val, e->amax_idx, nblk, d_out);
+  const int rc = gemm(e, st, Gemm(PC_HEAD, EPI_ARGMAX_F32, x, d_model, e->lm_head, d_model, e->amax_val, nblk, rows, vocab, d_model).on(GEMM_STREAM));
+  if (rc == RK_OK) hipLaunchKernelGGL(argmax_blocks_kernel, dim3(rows), dim3(256), 0, st, e->amax_val, e->amax_idx, nblk, d_out);
+  return rc;
 }
 
 // One greedy step over the staged batch (encoder done): decoder over rows[b] (Ld ids per sequence), final norm of the last
@@ -1631,8 +1628,7 @@ static int greedy_step(rk_engine* e, Slot& sl, const std::vector<std::vector<int
     int r = run_decoder(e, sl, Ld);
     if (r) return r;
     rmsnorm(e, sd, sl.dhidden, e->dec_final_ln, sl.dlast, sl.d_last_rows, n_seq, head_scale(e));
-    head_argmax(e, sd, sl.dlast, n_seq, e->d.d_model, e->d.vocab, sl.d_argmax);
-    return RK_OK;
+    return head_argmax(e, sd, sl.dlast, n_seq, e->d.d_model, e->d.vocab, sl.d_argmax);
   });
   if (rc) return rc;
   amax.resize(n_seq);
@@ -1746,8 +1742,7 @@ int rk_t5_greedy2(rk_engine* e, const int32_t* tokens, const int32_t* seq_offset
     int r = run_decoder(e, sl, Ld, &tree);
     if (r) return r;
     rmsnorm(e, sd, sl.dhidden, e->dec_final_ln, sl.dlast, sl.d_last_rows, (int)R, head_scale(e));
-    head_argmax(e, sd, sl.dlast, (int)R, e->d.d_model, e->d.vocab, sl.d_argmax);
-    return RK_OK;
+    return head_argmax(e, sd, sl.dlast, (int)R, e->d.d_model, e->d.vocab, sl.d_argmax);
   });
   if (rc) return rc;
   HIPCHK(e, hipMemcpyAsync(amax.data(), sl.d_argmax, (size_t)R * sizeof(int), hipMemcpyDeviceToHost, sd));
@@ -1823,7 +1818,6 @@ static int llama_finalize(rk_engine* e) {
   auto H = [&](const std::string& n) -> const std::vector<half_t>& { return e->host[n].h; };
   auto Fv = [&](const std::string& n) -> const std::vector<float>& { return e->host[n].f; };
   int rc = RK_OK;
-#define RC(x) do { rc = (x); if (rc) return rc; } while (0)
   RC(upload(e, &e->emb, H("model.embed_tokens.weight").data(), H("model.embed_tokens.weight").size()));
   if (l.tied_head) e->lm_head = e->emb; else RC(upload(e, &e->lm_head, H("lm_head.weight").data(), H("lm_head.weight").size()));
   RC(upload(e, &e->l_final_ln, Fv("model.norm.weight").data(), (size_t)dm));
@@ -1889,7 +1883,6 @@ static int llama_finalize(rk_engine* e) {
   RC(dalloc(e, &sl.d_scores, e->scores_cap));
   HIPCHK(e, hipHostMalloc((void**)&sl.h_scores, e->scores_cap * sizeof(float), hipHostMallocDefault));
   HIPCHK(e, hipHostMalloc((void**)&sl.h_small, 4 * 8192 * sizeof(int), hipHostMallocDefault));
-#undef RC
   HIPCHK(e, hipDeviceSynchronize());
   e->finalized = true;
   return RK_OK;
@@ -1917,11 +1910,12 @@ static int llama_prefill(rk_engine* e, const int32_t* tokens, const int32_t* off
   HIPCHK(e, hipMemcpy(sl.d_last_rows, last.data(), (size_t)n_seq * sizeof(int), hipMemcpyHostToDevice));
   GemmFold cons, prod;
   cons.rowscale = sl.rowscale; prod.xraw = sl.xraw; prod.ssq = sl.ssq;
+  int nb = 0;                                   // block sums per row of the last residual GEMM
   embed(e, st, sl.d_tokens, sl.hidden, T, sl.xraw, sl.rowscale);
   const float scale_log2e = (1.0f / std::sqrt(128.0f)) * 1.4426950408889634f;
   for (int i = 0; i < l.n_layers; ++i) {
     const LlamaLayerW& w = e->ll[i];
-    gemm(e, st, PC_ENC_GEMM_QKV, EPI_STORE_F16, sl.xraw, dm, w.qkv_f, dm, sl.qkv, ldq, T, ldq, dm, 0, 0, 1.f, 1, 0, 0, 0, false, cons);
+    RC(gemm(e, st, Gemm(PC_ENC_GEMM_QKV, EPI_STORE_F16, sl.xraw, dm, w.qkv_f, dm, sl.qkv, ldq, T, ldq, dm).with(cons)));
     {
       Bracket br(e, st, PC_OTHER, 0, (double)T * (Q + KV) * 4.0);
       hipLaunchKernelGGL(rope128_kernel, dim3(T), dim3(256), 0, st, sl.qkv, e->d_pos, e->rope_cos, e->rope_sin, ldq, l.n_heads + l.n_kv_heads);
@@ -1946,12 +1940,12 @@ static int llama_prefill(rk_engine* e, const int32_t* tokens, const int32_t* off
         hipLaunchKernelGGL(attn_causal128_kernel, dim3((sl.maxL + 127) / 128, l.n_heads, n_seq), dim3(256), 0, st, a);
       }
     }
-    gemm(e, st, PC_ENC_GEMM_O, EPI_RESID_F32, sl.ctx, Q, w.o, Q, sl.hidden, dm, T, dm, Q, 0, 0, 1.f, 1, 0, 0, 0, false, prod);
-    rowscale(e, st, sl.ssq, sl.rowscale, T);
-    gemm(e, st, PC_ENC_GEMM_FFN_IN, EPI_SWIGLU_F16, sl.xraw, dm, w.gu_f, dm, sl.ffh, F, T, 2 * F, dm, 0, 0, 1.f, 1, 0, 0, 0, false, cons);
+    RC(gemm(e, st, Gemm(PC_ENC_GEMM_O, EPI_RESID_F32, sl.ctx, Q, w.o, Q, sl.hidden, dm, T, dm, Q).with(prod), &nb));
+    rowscale(e, st, sl.ssq, sl.rowscale, T, nb);
+    RC(gemm(e, st, Gemm(PC_ENC_GEMM_FFN_IN, EPI_SWIGLU_F16, sl.xraw, dm, w.gu_f, dm, sl.ffh, F, T, 2 * F, dm).with(cons)));
     const bool lastl = i + 1 == l.n_layers;
-    gemm(e, st, PC_ENC_GEMM_FFN_OUT, EPI_RESID_F32, sl.ffh, F, w.down, F, sl.hidden, dm, T, dm, F, 0, 0, 1.f, 1, 0, 0, 0, false, lastl ? GemmFold() : prod);
-    if (!lastl) rowscale(e, st, sl.ssq, sl.rowscale, T);
+    RC(gemm(e, st, Gemm(PC_ENC_GEMM_FFN_OUT, EPI_RESID_F32, sl.ffh, F, w.down, F, sl.hidden, dm, T, dm, F).with(lastl ? GemmFold() : prod), &nb));
+    if (!lastl) rowscale(e, st, sl.ssq, sl.rowscale, T, nb);
   }
   rmsnorm(e, st, sl.hidden, e->l_final_ln, sl.dlast, sl.d_last_rows, n_seq);
   HIPCHK(e, hipGetLastError());
@@ -1995,7 +1989,7 @@ int rk_llama_greedy1(rk_engine* e, const int32_t* tokens, const int32_t* seq_off
   Slot& sl = e->slots[0];
   hipStream_t st = sl.se;
   // full-vocabulary head on the n_seq last rows: weight-streaming GEMM, then the first arg-max (torch.argmax tie rule)
-  head_argmax(e, st, sl.dlast, n_seq, e->ld.hidden, e->ld.vocab, sl.d_argmax);
+  if ((rc = head_argmax(e, st, sl.dlast, n_seq, e->ld.hidden, e->ld.vocab, sl.d_argmax))) return rc;
   std::vector<int> amax(n_seq);
   HIPCHK(e, hipMemcpyAsync(amax.data(), sl.d_argmax, n_seq * sizeof(int), hipMemcpyDeviceToHost, st));
   HIPCHK(e, hipStreamSynchronize(st));
@@ -2312,9 +2306,10 @@ int rk_debug_gemm(rk_engine* e, const uint16_t* A, const uint16_t* W, float* C, 
   HIPCHK(e, hipMemcpy(dW, W, (size_t)N * K * 2, hipMemcpyHostToDevice));
   const int saved = e->opt.glds;
   e->opt.glds = use_glds != 0;
-  GemmFold dbg_fold; dbg_fold.few = use_glds == 3;                 // 3: the few-row GEMV family (M <= 16)
-  gemm(e, e->slots[0].se, PC_OTHER, EPI_STORE_F32, dA, K, dW, K, dC, N, M, N, K, 0, 0, 1.f, 1, 0, 0, 0, /*weight_streaming=*/use_glds >= 2, dbg_fold);
+  // 2: the weight-streaming family, 3: the few-row GEMV family (M <= 16)
+  rc = gemm(e, e->slots[0].se, Gemm(PC_OTHER, EPI_STORE_F32, dA, K, dW, K, dC, N, M, N, K).on(use_glds == 3 ? GEMM_GEMV : (use_glds >= 2 ? GEMM_STREAM : GEMM_TILED)));
   e->opt.glds = saved;
+  if (rc) { hipFree(dA); hipFree(dW); hipFree(dC); return rc; }
   HIPCHK(e, hipStreamSynchronize(e->slots[0].se));
   HIPCHK(e, hipGetLastError());
   HIPCHK(e, hipMemcpy(C, dC, (size_t)M * N * 4, hipMemcpyDeviceToHost));
@@ -2353,9 +2348,10 @@ int rk_debug_gemm_bench(rk_engine* e, int M, int N, int K, int epi, int iters, f
     HIPCHK(e, hipMalloc((void**)&dX, nc * 2)); HIPCHK(e, hipMalloc((void**)&dS, (size_t)M * ((N + 31) / 32) * 4));
     fold.xraw = dX; fold.ssq = dS;
   }
-  for (int i = 0; i < 2; ++i) gemm(e, e->slots[0].se, PC_OTHER, epi, dA, ldk, dW, ldk, dC, ldc, M, N, K, 0, 0, 1.f, 1, 0, 0, 0, false, fold);
+  const Gemm c = Gemm(PC_OTHER, epi, dA, ldk, dW, ldk, dC, ldc, M, N, K).with(fold);
+  for (int i = 0; i < 2; ++i) RC(gemm(e, e->slots[0].se, c));
   HIPCHK(e, hipEventRecord(e->t0, e->slots[0].se));
-  for (int i = 0; i < iters; ++i) gemm(e, e->slots[0].se, PC_OTHER, epi, dA, ldk, dW, ldk, dC, ldc, M, N, K, 0, 0, 1.f, 1, 0, 0, 0, false, fold);
+  for (int i = 0; i < iters; ++i) RC(gemm(e, e->slots[0].se, c));
   HIPCHK(e, hipEventRecord(e->t1, e->slots[0].se));
   HIPCHK(e, hipEventSynchronize(e->t1));
   float ms = 0;

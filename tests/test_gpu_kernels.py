@@ -231,6 +231,28 @@ def test_few_row_decoder_family_vs_weight_streaming_family_and_oracle(toy):
         np.testing.assert_array_equal(tok2, tok[:, :2])                                   # tree pass == two steps (same family)
 
 
+def test_few_row_decoder_family_wide_attention_inner_dim():
+    """A 2-row, 2-position decoder pass of a model whose attention width I = n_heads * d_kv = 3328 exceeds what the GEMV kernel
+    takes as K (512 * GEMV_MAX_PIECES = 3072): the O / cross-O projections cannot run on it, so the whole pass must stay on the
+    weight-streaming family (one statistics layout for the folded norms) - default options, dec_gemv = 0 and the oracle agree."""
+    from llmrankers import _synth
+    from oracle.t5_numpy import T5Oracle
+    dims = _synth.T5Dims(vocab=256, d_model=256, n_heads=52, d_kv=64, d_ff=512, n_enc=1, n_dec=2)
+    state = _synth.synth_state_dict(dims, seed=71, gain=2.0)
+    eng = _engine(dims, state)
+    try:
+        seqs = _synth.synth_token_batch(1, 20, 120, dims.vocab, seed=72)
+        prefix, ids = [0, 17], [11, 12, 13, 14, 15]
+        got = eng.score(seqs, prefix, ids)
+        eng.set_option("dec_gemv", 0)
+        ref = eng.score(seqs, prefix, ids)
+    finally:
+        eng.close()
+    want = T5Oracle(dims, state).score_last(seqs, prefix, ids)
+    assert np.abs(got - want).max() < LOGIT_TOL and np.abs(ref - want).max() < LOGIT_TOL, (np.abs(got - want).max(), np.abs(ref - want).max())
+    assert np.abs(got - ref).max() < 2e-3, np.abs(got - ref).max()
+
+
 def test_encoder_stages_one_layer():
     """1-layer model: every intermediate buffer vs the oracle (localises a wrong kernel)."""
     from llmrankers import _synth
