@@ -207,16 +207,23 @@ hipStream_t enc_stream(rk_engine* e, Slot& sl) { return e->opt.overlap ? e->slot
 hipStream_t dec_stream(rk_engine* e, Slot& sl) { return e->opt.overlap ? sl.sd : e->slots[0].se; }
 
 // ---- kernel launch helpers ------------------------------------------------------------------------------
-// More than 64 KiB of dynamic LDS needs hipFuncSetAttribute, which applies per DEVICE: done once per (kernel, device),
-// whichever engine / thread launches it there first (engines on different GPUs may live in one process).
-inline void ensure_dynamic_lds(const void* fn, int bytes, std::atomic<uint64_t>& done) {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-  const uint64_t bit = 1ull << (dev & 63);
-  if (done.load(std::memory_order_acquire) & bit) return;
-  hipError_t rc = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-  if (rc != hipSuccess) fprintf(stderr, "[rk_engine] hipFuncSetAttribute(%d B LDS) failed: %s\n", bytes, hipGetErrorString(rc));
-  done.fetch_or(bit, std::memory_order_release);
+// Launches kernel K with `lds` bytes of dynamic LDS.  More than 64 KiB needs hipFuncSetAttribute (opt_in bytes; 0: none), which
+// applies per DEVICE: done once per (kernel, device), whichever engine / thread launches it there first (engines on different GPUs
+// may live in one process).
+template <auto K, class Args>
+void launch_lds(hipStream_t st, dim3 grid, dim3 block, int lds, int opt_in, const Args& a) {
+  static std::atomic<uint64_t> done{0};
+  if (opt_in > 0) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) dev = 0;
+    const uint64_t bit = 1ull << (dev & 63);
+    if (!(done.load(std::memory_order_acquire) & bit)) {
+      hipError_t rc = hipFuncSetAttribute((const void*)K, hipFuncAttributeMaxDynamicSharedMemorySize, opt_in);
+      if (rc != hipSuccess) fprintf(stderr, "[rk_engine] hipFuncSetAttribute(%d B LDS) failed: %s\n", opt_in, hipGetErrorString(rc));
+      done.fetch_or(bit, std::memory_order_release);
+    }
+  }
+  hipLaunchKernelGGL(K, grid, block, lds, st, a);
 }
 
 template <int EPI, int WM, int WN, int MI, int NI>
@@ -224,10 +231,8 @@ void launch_v2(hipStream_t st, const GemmArgs& a) {
   constexpr int BM = WM * MI * 32, BN = WN * NI * 32;
   constexpr int smem_stages = 2 * (BM + BN) * 64 * 2, smem_epi = WM * WN * 32 * (NI * 32 * 4 + 16);
   constexpr int smem = smem_stages > smem_epi ? smem_stages : smem_epi;
-  static std::atomic<uint64_t> attr_done{0};
-  ensure_dynamic_lds((const void*)gemm_v2_kernel<EPI, WM, WN, MI, NI>, smem, attr_done);
   const int tiles = ((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN);
-  hipLaunchKernelGGL((gemm_v2_kernel<EPI, WM, WN, MI, NI>), dim3(tiles), dim3(WM * WN * 64), smem, st, a);
+  launch_lds<gemm_v2_kernel<EPI, WM, WN, MI, NI>>(st, dim3(tiles), dim3(WM * WN * 64), smem, smem, a);
 }
 
 #define KSPLIT_MAX_SLABS 256      // partial tiles (256 x 256 fp32 = 256 KiB each) per stream: 64 MiB
@@ -235,8 +240,6 @@ void launch_v2(hipStream_t st, const GemmArgs& a) {
 template <int EPI, int KO = 0, bool RS = false, bool SPLIT = false>
 void launch_pp2(hipStream_t st, const GemmArgs& a, int max_wgs) {
   constexpr int smem = 2 * 4 * 128 * 64 * 2 + 32768;   // 8 half-tile buffers + 32 KiB epilogue staging = all 160 KiB
-  static std::atomic<uint64_t> attr_done{0};
-  ensure_dynamic_lds((const void*)gemm_pp2_kernel<EPI, KO, RS, SPLIT>, smem, attr_done);
   const int tiles = ((a.M + 255) / 256) * ((a.N + 255) / 256) * (SPLIT ? a.ksplit : 1);
   // persistent: one workgroup per CU walks the tiles (max_wgs = CUs rounded down to a multiple of 8 keeps the tile -> XCD
   // association); max_wgs <= 0: one workgroup per tile
@@ -247,7 +250,7 @@ void launch_pp2(hipStream_t st, const GemmArgs& a, int max_wgs) {
   // MFMA phases at no cost to the critical path: o 0.496 -> 0.484 ms per step in the serial profile, 7302-7340 against
   // 7338-7376 passages/s in the pipeline - the epilogue's cost is not a shared-HBM burst that de-phasing would spread)
   const int grid = max_wgs > 0 && tiles > max_wgs ? max_wgs : tiles;
-  hipLaunchKernelGGL((gemm_pp2_kernel<EPI, KO, RS, SPLIT>), dim3(grid), dim3(512), smem, st, a);
+  launch_lds<gemm_pp2_kernel<EPI, KO, RS, SPLIT>>(st, dim3(grid), dim3(512), smem, smem, a);
 }
 
 // Tile-shape choice.  variant: 0 = auto, 1 = 128x128 (v1, two workgroups per CU), 2 = 256x256, 3 = 256x192,
@@ -400,9 +403,7 @@ GemmPlan plan_gemm(const rk_engine* e, const Gemm& c, hipStream_t st) {
 template <int EPI, int NST>
 void launch_s64(hipStream_t st, const GemmArgs& a) {
   constexpr int smem = NST * 16384;
-  static std::atomic<uint64_t> attr_done{0};
-  ensure_dynamic_lds((const void*)gemm_s64_kernel<EPI, NST>, smem, attr_done);
-  hipLaunchKernelGGL((gemm_s64_kernel<EPI, NST>), dim3(((a.M + 63) / 64) * ((a.N + 63) / 64)), dim3(128), smem, st, a);
+  launch_lds<gemm_s64_kernel<EPI, NST>>(st, dim3(((a.M + 63) / 64) * ((a.N + 63) / 64)), dim3(128), smem, smem, a);
 }
 
 // one ping-pong launch of the plan with K split ks
@@ -471,9 +472,7 @@ void launch_tiled(const rk_engine* e, hipStream_t st, GemmArgs a, const GemmPlan
 template <int EPI, int MR>
 void launch_gemv(const rk_engine* e, hipStream_t st, const GemmArgs& a) {
   const int smem = MR * a.K * 2 + (GEMV_MAX_ROWS + 4 * GEMV_MAX_ROWS) * 4;
-  static std::atomic<uint64_t> attr_done{0};
-  if (smem > 65536) ensure_dynamic_lds((const void*)gemv_rows_kernel<EPI, MR>, 160 * 1024, attr_done);
-  hipLaunchKernelGGL((gemv_rows_kernel<EPI, MR>), dim3(gemv_grid(EPI_IS_GATED(EPI) ? a.N / 2 : a.N, e->n_cu)), dim3(256), smem, st, a);
+  launch_lds<gemv_rows_kernel<EPI, MR>>(st, dim3(gemv_grid(EPI_IS_GATED(EPI) ? a.N / 2 : a.N, e->n_cu)), dim3(256), smem, smem > 65536 ? 160 * 1024 : 0, a);
 }
 
 template <int EPI>
@@ -605,8 +604,6 @@ int upload_small(rk_engine* e, Slot& sl, hipStream_t st, std::vector<int>* cache
 }
 
 // ---- forward passes -----------------------------------------------------------------------------------------
-// hf: modeling_t5.py:663-750 (T5Stack.forward, encoder) over the slot's staged ragged batch, then the stacked
-// cross-attention K/V projections of all decoder layers (:325-326 with key_value_states = encoder output).
 #define XA_MAX_ROWS 512     // decoder rows (sequences x positions) per pass of the direct cross-attention path
 #define XA_MAX_CHUNKS 4096  // rows x 64-key chunks of partial-sum workspace per pass
 #define XA_MAX_LD 16        // decoder positions per sequence up to which the query-side form is used
@@ -620,6 +617,199 @@ bool use_xattn_direct(const rk_engine* e, const Slot&, int max_ld) {
   return e->opt.xattn_direct && max_ld <= XA_MAX_LD;
 }
 
+// ---- attention launch plans: like plan_gemm, each a function of the call shape, the options and the CU count (which kernels
+// run, in order, their template parameter, grid, block, dynamic LDS, derived arguments); one launcher per plan runs it ----------
+inline size_t attn_dec_lds(int keys) { return (64 + 256 + 8 + (size_t)keys) * sizeof(float); }   // attn_dec_kernel's dynamic LDS
+
+// Encoder self-attention of one run_encoder call (hf: modeling_t5.py:144-173)
+struct EncAttnPlan {
+  enum Kind { DMA, LONG, TILED } kind = TILED;
+  int ng = 0, heads_per_wg = 0;       // DMA: attn_enc_dma_kernel<ng> (wave groups per workgroup), (sequence, head) items per group
+  int nw = 0, nqb = 0, xcd_map = 0;   // LONG: attn_enc_long_kernel<nw> (waves per workgroup), query blocks of 32 nw, XCD grouping
+  bool skip_long = false;             // LONG: attn_enc_kernel first, for the batch's sequences of at most ATT_ROW_MAXL keys
+  dim3 grid, tiled_grid; int block = 0, lds = 0;   // DMA / long kernel; attn_enc_kernel's grid (256 threads, no dynamic LDS)
+};
+EncAttnPlan plan_enc_attn(const rk_engine* e, int n_seq, int maxL, int minL, int H) {
+  const auto& o = e->opt;
+  EncAttnPlan p;
+  if (maxL <= ATT_ROW_MAXL && o.attn_short) {
+    // Every sequence of the batch at most ATT_ROW_MAXL keys: the DMA kernel (attn_short = 5, the default: two six-wave groups
+    // per 768-thread workgroup; 6: one group per workgroup).  The two compute a sequence bit-identically (attention.h: ATT_ROW_MAXL).
+    // Persistent launch: at most one workgroup per CU, the (sequence, head) items dealt out evenly in contiguous runs per
+    // wave group (320 sequences x 16 heads on 256 CUs x 2 groups: 10 items each)
+    p.kind = EncAttnPlan::DMA; p.ng = o.attn_short == 6 ? 1 : 2;
+    const long total = (long)n_seq * H, groups = (long)e->n_cu * p.ng;
+    p.heads_per_wg = o.attn_heads_per_wg > 0 ? o.attn_heads_per_wg : (int)((total + groups - 1) / groups);
+    p.grid = dim3((unsigned)((total + (long)p.ng * p.heads_per_wg - 1) / ((long)p.ng * p.heads_per_wg)));
+    p.block = 384 * p.ng; p.lds = p.ng * ATTD_LDS_BYTES;
+  } else if (o.attn_long) {
+    // every sequence longer than ATT_ROW_MAXL keys: the chunked LDS-DMA kernel (round 5); the batch's short sequences (if any):
+    // the tiled kernel, which reproduces the short kernel's bits - a sequence's result depends on ITS length only
+    p.kind = EncAttnPlan::LONG; p.skip_long = minL <= ATT_ROW_MAXL; p.tiled_grid = dim3((ATT_ROW_MAXL + 127) / 128, H, n_seq);
+    // waves per workgroup (same bits for every choice): option attn_long_nw, default 4
+    // (measured, one to eight 1 560-token prompts: 4 waves = 128 queries per workgroup, two workgroups per CU, wins everywhere -
+    // 36.9 / 49.1 / 157.5 us per layer at 1 / 2 / 8 prompts against 60 / 60 / 180 at twelve waves, 48 / 85 / 212 at six (384-thread
+    // workgroups of this register size run one per CU) and 39.6 / 67.6 / 224.9 for the tiled kernel; profiles/r05_attn_long.jsonl)
+    p.nw = (o.attn_long_nw == 12 || o.attn_long_nw == 6 || o.attn_long_nw == 3) ? o.attn_long_nw : 4;
+    p.nqb = (maxL + 32 * p.nw - 1) / (32 * p.nw); p.grid = dim3(xcd_grid(n_seq * H, p.nqb)); p.block = 64 * p.nw; p.lds = ATTL_LDS_BYTES;
+    p.xcd_map = o.attn_long_xcd;
+  } else {   // option attn_long = 0: the tiled kernel for every length (the on-device cross-check of the two DMA kernels)
+    p.tiled_grid = dim3((maxL + 127) / 128, H, n_seq);
+  }
+  return p;
+}
+
+void launch_enc_attn(rk_engine* e, hipStream_t st, const Slot& sl, const EncAttnPlan& p) {
+  const int I = e->inner;
+  AttnEncArgs a{sl.qkv, sl.ctx, sl.d_seq_off, e->lut_enc, 3 * I, I, I, 1, e->opt.attn_ko};
+#ifdef RK_MEASURE
+  a.trace = e->attn_trace;
+#endif
+  Bracket br(e, st, PC_ENC_ATTN, 4.0 * (double)sl.maxL * sl.T * I, (double)sl.T * 4 * I * 2.0);   // flops: exact for uniform lengths, upper bound if ragged
+  if (p.kind == EncAttnPlan::TILED || p.skip_long) { a.skip_long = p.skip_long; hipLaunchKernelGGL(attn_enc_kernel, p.tiled_grid, dim3(256), 0, st, a); }
+  if (p.kind == EncAttnPlan::DMA) {
+    a.heads_per_wg = p.heads_per_wg; a.n_seq = sl.n_seq;
+    if (p.ng == 2) launch_lds<attn_enc_dma_kernel<2>>(st, p.grid, p.block, p.lds, p.lds, a);
+    else launch_lds<attn_enc_dma_kernel<1>>(st, p.grid, p.block, p.lds, p.lds, a);
+  } else if (p.kind == EncAttnPlan::LONG) {
+    a.n_seq = sl.n_seq; a.n_heads = e->d.n_heads; a.nqb = p.nqb; a.xcd_map = p.xcd_map;
+    if (p.nw == 12) launch_lds<attn_enc_long_kernel<12>>(st, p.grid, p.block, p.lds, p.lds, a);
+    else if (p.nw == 6) launch_lds<attn_enc_long_kernel<6>>(st, p.grid, p.block, p.lds, p.lds, a);
+    else if (p.nw == 4) launch_lds<attn_enc_long_kernel<4>>(st, p.grid, p.block, p.lds, p.lds, a);
+    else launch_lds<attn_enc_long_kernel<3>>(st, p.grid, p.block, p.lds, p.lds, a);
+  }
+}
+
+// Decoder attention of one run_decoder pass over decoder rows (self; tree: rk_t5_greedy2's shared prefixes) or over the
+// materialised encoder K / V (cross): the matrix-core kernel, then a staged kernel for the sequences it leaves.  The call's
+// position count decides whether the MFMA kernel runs at all, a sequence's own key count (<= ATTX_MAXK) whether it takes it.
+struct DecAttnPlan {
+  bool mfma = false;                            // attn_dec_cross_mfma_kernel, 128 threads, ATTX_LDS_BYTES
+  enum Staged { NONE, SEQ, ROW } staged = ROW;  // then attn_dec_seq_kernel (one workgroup per (head, sequence): K / V staged
+                                                // once) or attn_dec_kernel (same bits), 256 threads
+  dim3 mfma_grid, grid; size_t lds = 0;         // grid and dynamic LDS of the staged kernel
+};
+// keys: per sequence, Ld (self) or the longest (cross); tree_rows > 0: the tree form
+DecAttnPlan plan_dec_attn(const rk_engine* e, bool cross, int B, int Ld, int keys, int H, int tree_rows) {
+  DecAttnPlan p;
+  if (tree_rows) { p.grid = dim3(1, H, tree_rows); p.lds = attn_dec_lds(keys); return p; }
+  // cross-attention from two positions on; self-attention for long prefixes only (the materialised-K / V regime, qlm: round 6)
+  p.mfma = e->opt.dec_cross_mfma && Ld <= ATTX_MAXQ && (cross ? Ld >= 2 : Ld > XA_MAX_LD);
+  p.mfma_grid = dim3(H, B);
+  if (p.mfma && keys <= ATTX_MAXK) p.staged = DecAttnPlan::NONE;
+  else if (e->opt.dec_attn_seq && Ld >= 2 && attn_dec_seq_lds(keys) <= 160 * 1024) { p.staged = DecAttnPlan::SEQ; p.grid = dim3(H, B); p.lds = attn_dec_seq_lds(keys); }
+  else { p.grid = dim3(Ld, H, B); p.lds = attn_dec_lds(keys); }
+  return p;
+}
+
+void launch_dec_attn(rk_engine* e, hipStream_t st, const DecAttnPlan& p, AttnDecArgs a, double flops, double bytes) {
+  Bracket br(e, st, PC_DEC_ATTN, flops, bytes);
+  if (p.mfma) { hipLaunchKernelGGL(attn_dec_cross_mfma_kernel, p.mfma_grid, dim3(128), ATTX_LDS_BYTES, st, a); a.skip_short = 1; }
+  if (p.staged == DecAttnPlan::SEQ) hipLaunchKernelGGL(attn_dec_seq_kernel, p.grid, dim3(256), p.lds, st, a);
+  else if (p.staged == DecAttnPlan::ROW) hipLaunchKernelGGL(attn_dec_kernel, p.grid, dim3(256), p.lds, st, a);
+}
+
+// Query-side cross-attention of one block of nr decoder rows (attention.h: XAttnArgs): qk = W_k^T q per head; scores, softmax and
+// weighted sums over the raw encoder states in 64-key chunks; ctx = W_v (.) per head.  fuse (run_decoder): the projections around
+// it fused per (head, row slab) - decoder_kernels.h: the q projection + W_k^T q in one launch, the chunk merge + W_v in another.
+struct XAttnPlan {
+  int nr = 0, nch = 0;                                      // rows, 64-key chunks of the longest sequence
+  bool fuse_qk = false; int qk_R = 32, qk_CS = 1;           // dec_cross_qk_kernel (H, ceil(nr / R), CS); else the W_k^T GEMM per head
+  enum Part { MFMA_FEW, MFMA, VALU16, VALU4 } part = MFMA;  // xattn_part_mfma_kernel<true / false>, xattn_part_kernel<16 / 4>
+  dim3 part_grid;
+  bool fuse_cv = false; int cv_R = 16;   // dec_cross_cv_kernel (H, ceil(nr / R)); else xattn_combine_kernel + the W_v GEMM per head
+};
+XAttnPlan plan_xattn(const rk_engine* e, bool fuse, int nr, int maxL, int H, int dm) {
+  const auto& o = e->opt;
+  XAttnPlan p;
+  p.nr = nr; p.nch = (maxL + 63) / 64; p.fuse_qk = fuse;
+  if (fuse) {
+    if (o.dec_fuse_rows > 0) p.qk_R = std::min(32, o.dec_fuse_rows);
+    else if (nr <= 16) p.qk_R = 16;   // (a setwise pass: 13 rows - half the MFMA columns, half the x rows; measured at 320 rows: 32 > 16 > 8)
+    // few rows: several workgroups per (head, slab) share the output columns, each streaming 1 / CS of W_k^T (and all of W_q,h)
+    while (p.qk_CS < 8 && (dm / 64) % (2 * p.qk_CS) == 0 && (long)((nr + p.qk_R - 1) / p.qk_R) * H * p.qk_CS < e->n_cu / 2) p.qk_CS *= 2;
+  }
+  // MFMA form (weighted sums on the matrix cores, the chunk's encoder rows staged in LDS by a loader wave) whenever the model
+  // width allows its LDS image (every wave takes whole 64-column pieces of its quarter); the VALU form otherwise.  The choice
+  // depends on the MODEL only, never on the batch (the two round differently).  Few workgroups (a setwise compare): the
+  // latency-scheduled form, two pieces per wave (same bits; attention.h).
+  const long wgs16 = (long)p.nch * nr * ((H + 15) / 16);
+  if (o.xattn_mfma && dm % 256 == 0) p.part = wgs16 <= 2 * e->n_cu ? XAttnPlan::MFMA_FEW : XAttnPlan::MFMA;
+  else p.part = wgs16 >= 2 * e->n_cu ? XAttnPlan::VALU16 : XAttnPlan::VALU4;
+  p.part_grid = dim3(p.nch, nr, p.part == XAttnPlan::VALU4 ? (H + 3) / 4 : (H + 15) / 16);
+  // fused merge: rows per workgroup: the largest slab that still gives about half the chip a workgroup (results do not depend on
+  // it) (16 rows: 41 KiB of LDS at d = 1024, three workgroups per CU hide each other's load latency)
+  p.fuse_cv = fuse && p.nch <= DECV_MAXCH;
+  while (p.fuse_cv && p.cv_R > 2 && (long)((nr + p.cv_R - 1) / p.cv_R) * H < e->n_cu / 2) p.cv_R >>= 1;
+  return p;
+}
+
+// Rows [r0, r0 + p.nr) of decoder layer l.  Fused: x, wq and in1 are the q projection's input, weight and norm; else sl.dq holds
+// q.  row_seq: decoder row -> encoder sequence (tree form) or nullptr.
+int launch_xattn(rk_engine* e, hipStream_t st, Slot& sl, const XAttnPlan& p, int l, int Ld, int r0, const half_t* x,
+                 const half_t* wq, const GemmFold& in1, const int* row_seq) {
+  const rk_model_desc& d = e->d;
+  const int H = d.n_heads, dm = d.d_model, I = e->inner, nr = p.nr;
+  const half_t* wv = e->cross_kv_w + ((size_t)l * 2 * I + I) * dm;
+  int rc = RK_OK;
+  if (p.fuse_qk) {
+    DecQKArgs qa{x + (size_t)r0 * dm, dm, wq, e->dec[l].ckT, sl.xqk, nr, dm, H, in1.rowscale ? in1.rowscale + r0 : nullptr,
+                 in1.ssq_in ? in1.ssq_in + (size_t)r0 * in1.nb_in : nullptr, in1.nb_in, d.eps, RK_XRAW_SCALE, p.qk_R, p.qk_CS};
+    Bracket br(e, st, PC_DEC_GEMM, 2.0 * nr * (double)dm * I * 2, 2.0 * ((double)I * dm * 2 + (double)nr * H * dm));
+    hipLaunchKernelGGL(dec_cross_qk_kernel, dim3(H, (nr + p.qk_R - 1) / p.qk_R, p.qk_CS), dim3(64 * DEC_NW), 0, st, qa);
+  } else {
+    RC(gemm(e, st, Gemm(PC_DEC_GEMM, EPI_STORE_F16, sl.dq + (size_t)r0 * I, I, e->dec[l].ckT, 64, sl.xqk, H * dm, nr, dm, 64).heads(H, 64, (long)dm * 64, dm)));
+  }
+  XAttnArgs xa{sl.xqk, sl.enc_out, sl.d_seq_off, sl.xpart, sl.xstat, sl.xctx, Ld, H, dm, p.nch, r0, row_seq};
+  {
+    Bracket br(e, st, PC_DEC_ATTN, 4.0 * nr * (double)sl.maxL * H * dm, (double)sl.T * dm * 2.0 * 2);
+    if (p.part == XAttnPlan::MFMA_FEW) hipLaunchKernelGGL(xattn_part_mfma_kernel<true>, p.part_grid, dim3(256), 0, st, xa);
+    else if (p.part == XAttnPlan::MFMA) hipLaunchKernelGGL(xattn_part_mfma_kernel<false>, p.part_grid, dim3(256), 0, st, xa);
+    else if (p.part == XAttnPlan::VALU16) hipLaunchKernelGGL(xattn_part_kernel<16>, p.part_grid, dim3(256), 0, st, xa);
+    else hipLaunchKernelGGL(xattn_part_kernel<4>, p.part_grid, dim3(256), 0, st, xa);
+    if (!p.fuse_cv) hipLaunchKernelGGL(xattn_combine_kernel, dim3(H, nr), dim3(256), 0, st, xa);
+  }
+  if (!p.fuse_cv)
+    return gemm(e, st, Gemm(PC_DEC_GEMM, EPI_STORE_F16, sl.xctx, H * dm, wv, dm, sl.dctx + (size_t)r0 * I, I, nr, 64, dm).heads(H, dm, (long)64 * dm, 64));
+  DecCVArgs ca{sl.xpart, sl.xstat, sl.d_seq_off, row_seq, Ld, r0, wv, sl.dctx + (size_t)r0 * I, nr, dm, H, p.nch, I, p.cv_R};
+  Bracket br(e, st, PC_DEC_GEMM, 2.0 * nr * (double)dm * I, 2.0 * (double)I * dm + 4.0 * (double)nr * p.nch * H * dm);
+  launch_lds<dec_cross_cv_kernel>(st, dim3(H, (nr + p.cv_R - 1) / p.cv_R), dim3(64 * DEC_NW), (int)dec_cv_lds_bytes(dm, p.cv_R), 160 * 1024, ca);
+  return RK_OK;
+}
+
+// Causal attention of one llama_prefill call (hf: modeling_llama.py:130-214)
+struct CausalAttnPlan {
+  bool dma = false; int nw = 0, nqb = 0;   // attn_causal128_dma_kernel<nw>, query blocks of 32 nw; else attn_causal128_kernel
+  dim3 grid; int block = 256, lds = 0, lds_opt_in = 0;
+};
+CausalAttnPlan plan_llama_attn(const rk_engine* e, int n_seq, int maxL, int n_heads, int n_kv) {
+  CausalAttnPlan p;
+  p.dma = e->opt.llama_attn_dma;   // K / V chunks by LDS-DMA, V^T by transposing reads (round 5); chosen by the option alone: batch-independent
+  if (!p.dma) { p.grid = dim3((maxL + 127) / 128, n_heads, n_seq); return p; }
+  p.nw = e->opt.llama_attn_nw == 8 ? 8 : 4;   // same bits either way
+  p.nqb = (maxL + 32 * p.nw - 1) / (32 * p.nw); p.grid = dim3(xcd_grid(n_seq * n_kv, (n_heads / n_kv) * p.nqb));
+  p.block = 64 * p.nw; p.lds = p.lds_opt_in = ATCD_LDS_BYTES;
+#ifdef RK_MEASURE
+  p.lds_opt_in += 49152;
+  if (e->opt.attn_ko & 256) p.lds += 49152;   // residency probe: 112 KiB per workgroup = ONE per CU for certain
+#endif
+  return p;
+}
+
+void launch_llama_attn(rk_engine* e, hipStream_t st, const Slot& sl, const CausalAttnPlan& p) {
+  const rk_llama_desc& l = e->ld;
+  const int T = sl.T, Q = l.n_heads * 128, KV = l.n_kv_heads * 128;
+  const float scale_log2e = (1.0f / std::sqrt(128.0f)) * 1.4426950408889634f;   // head_dim**-0.5 * log2(e)
+  AttnCausalArgs a{sl.qkv, sl.ctx, sl.d_seq_off, Q + 2 * KV, Q, l.n_heads, l.n_kv_heads, scale_log2e, 0, 0, e->opt.attn_ko};
+  Bracket br(e, st, PC_ENC_ATTN, 2.0 * (double)sl.maxL * T * Q, (double)T * (2 * Q + 2 * KV) * 2.0);   // causal: half of 4 L T Q
+  if (!p.dma) { hipLaunchKernelGGL(attn_causal128_kernel, p.grid, dim3(p.block), 0, st, a); return; }
+  a.n_seq = sl.n_seq; a.nqb = p.nqb;
+  if (p.nw == 8) launch_lds<attn_causal128_dma_kernel<8>>(st, p.grid, p.block, p.lds, p.lds_opt_in, a);
+  else launch_lds<attn_causal128_dma_kernel<4>>(st, p.grid, p.block, p.lds, p.lds_opt_in, a);
+}
+
+// hf: modeling_t5.py:663-750 (T5Stack.forward, encoder) over the slot's staged ragged batch, then the stacked
+// cross-attention K/V projections of all decoder layers (:325-326 with key_value_states = encoder output).
 int run_encoder(rk_engine* e, Slot& sl, bool need_cross_kv) {
   const rk_model_desc& d = e->d;
   hipStream_t st = enc_stream(e, sl);
@@ -643,64 +833,13 @@ int run_encoder(rk_engine* e, Slot& sl, bool need_cross_kv) {
     else { if (nb) rowscale(e, st, sl.ssq, sl.rowscale, T, nb); f.rowscale = sl.rowscale; }
     return c.with(f);
   };
+  const EncAttnPlan ap = plan_enc_attn(e, sl.n_seq, sl.maxL, sl.minL, d.n_heads);
   embed(e, st, sl.d_tokens, sl.hidden, T, fold ? sl.xraw : nullptr, fold ? sl.rowscale : nullptr);
   for (int l = 0; l < d.n_enc_layers; ++l) {
     const EncLayerW& w = e->enc[l];
     const bool last = l + 1 == d.n_enc_layers;
     RC(gemm(e, st, normed(w.ln0, Gemm(PC_ENC_GEMM_QKV, EPI_STORE_F16, xin, dm, fold ? w.qkv_f : w.qkv, dm, sl.qkv, 3 * I, T, 3 * I, dm))));
-    {
-      // Every sequence of the batch at most ATT_ROW_MAXL keys: the DMA kernel (attn_short = 5, the default: two six-wave groups
-      // per 768-thread workgroup; 6: one group per workgroup); otherwise, or with attn_short = 0, the tiled kernel.  The two
-      // compute a sequence bit-identically (attention.h: ATT_ROW_MAXL).
-      AttnEncArgs a{sl.qkv, sl.ctx, sl.d_seq_off, e->lut_enc, 3 * I, I, I, 1, e->opt.attn_ko};
-#ifdef RK_MEASURE
-      a.trace = e->attn_trace;
-#endif
-      const double att_flops = 4.0 * (double)sl.maxL * T * I;   // exact for uniform lengths, upper bound if ragged
-      Bracket br(e, st, PC_ENC_ATTN, att_flops, (double)T * 4 * I * 2.0);
-      if (sl.maxL <= ATT_ROW_MAXL && e->opt.attn_short) {
-        const int ng = e->opt.attn_short == 6 ? 1 : 2;
-        // persistent launch: at most one workgroup per CU, the (sequence, head) items dealt out evenly in contiguous runs per
-        // wave group (320 sequences x 16 heads on 256 CUs x 2 groups: 10 items each)
-        const long total = (long)sl.n_seq * d.n_heads, groups = (long)e->n_cu * ng;
-        const int per = e->opt.attn_heads_per_wg > 0 ? e->opt.attn_heads_per_wg : (int)((total + groups - 1) / groups);
-        a.heads_per_wg = per;
-        a.n_seq = sl.n_seq;
-        const dim3 grid((unsigned)((total + (long)ng * per - 1) / ((long)ng * per)));
-        if (ng == 2) {
-          static std::atomic<uint64_t> attr_done{0};
-          ensure_dynamic_lds((const void*)attn_enc_dma_kernel<2>, 2 * ATTD_LDS_BYTES, attr_done);
-          hipLaunchKernelGGL(attn_enc_dma_kernel<2>, grid, dim3(768), 2 * ATTD_LDS_BYTES, st, a);
-        } else {
-          static std::atomic<uint64_t> attr_done{0};
-          ensure_dynamic_lds((const void*)attn_enc_dma_kernel<1>, ATTD_LDS_BYTES, attr_done);
-          hipLaunchKernelGGL(attn_enc_dma_kernel<1>, grid, dim3(384), ATTD_LDS_BYTES, st, a);
-        }
-      }
-      else if (e->opt.attn_long) {
-        // every sequence longer than ATT_ROW_MAXL keys: the chunked LDS-DMA kernel (round 5); the batch's short sequences (if any):
-        // the tiled kernel, which reproduces the short kernel's bits - a sequence's result depends on ITS length only
-        if (sl.minL <= ATT_ROW_MAXL) {
-          a.skip_long = 1;
-          hipLaunchKernelGGL(attn_enc_kernel, dim3((ATT_ROW_MAXL + 127) / 128, d.n_heads, sl.n_seq), dim3(256), 0, st, a);
-        }
-        // waves per workgroup (same bits for every choice): option attn_long_nw, or from the batch - enough workgroups for the chip
-        int nw = e->opt.attn_long_nw;
-        // (measured, one to eight 1 560-token prompts: 4 waves = 128 queries per workgroup, two workgroups per CU, wins everywhere -
-        // 36.9 / 49.1 / 157.5 us per layer at 1 / 2 / 8 prompts against 60 / 60 / 180 at twelve waves, 48 / 85 / 212 at six (384-thread
-        // workgroups of this register size run one per CU) and 39.6 / 67.6 / 224.9 for the tiled kernel; profiles/r05_attn_long.jsonl)
-        if (nw != 12 && nw != 6 && nw != 4 && nw != 3) nw = 4;
-        a.n_seq = sl.n_seq; a.n_heads = d.n_heads; a.nqb = (sl.maxL + 32 * nw - 1) / (32 * nw); a.xcd_map = e->opt.attn_long_xcd;
-        const dim3 grid(xcd_grid(sl.n_seq * d.n_heads, a.nqb));
-        static std::atomic<uint64_t> attr12{0}, attr6{0}, attr4{0}, attr3{0};
-        if (nw == 12) { ensure_dynamic_lds((const void*)attn_enc_long_kernel<12>, ATTL_LDS_BYTES, attr12); hipLaunchKernelGGL(attn_enc_long_kernel<12>, grid, dim3(768), ATTL_LDS_BYTES, st, a); }
-        else if (nw == 6) { ensure_dynamic_lds((const void*)attn_enc_long_kernel<6>, ATTL_LDS_BYTES, attr6); hipLaunchKernelGGL(attn_enc_long_kernel<6>, grid, dim3(384), ATTL_LDS_BYTES, st, a); }
-        else if (nw == 4) { ensure_dynamic_lds((const void*)attn_enc_long_kernel<4>, ATTL_LDS_BYTES, attr4); hipLaunchKernelGGL(attn_enc_long_kernel<4>, grid, dim3(256), ATTL_LDS_BYTES, st, a); }
-        else { ensure_dynamic_lds((const void*)attn_enc_long_kernel<3>, ATTL_LDS_BYTES, attr3); hipLaunchKernelGGL(attn_enc_long_kernel<3>, grid, dim3(192), ATTL_LDS_BYTES, st, a); }
-      }
-      else   // option attn_long = 0: the tiled kernel for every length (the on-device cross-check of the two DMA kernels)
-        hipLaunchKernelGGL(attn_enc_kernel, dim3((sl.maxL + 127) / 128, d.n_heads, sl.n_seq), dim3(256), 0, st, a);
-    }
+    launch_enc_attn(e, st, sl, ap);
     RC(gemm(e, st, Gemm(PC_ENC_GEMM_O, EPI_RESID_F32, sl.ctx, I, w.o, I, sl.hidden, dm, T, dm, I).with(prod), &nb));
     RC(gemm(e, st, normed(w.ln1, Gemm(PC_ENC_GEMM_FFN_IN, d.gated_gelu ? EPI_GEGLU_F16 : EPI_RELU_F16, xin, dm, fold ? w.ffn_in_f : w.ffn_in, dm,
                                       sl.ffh, F, T, d.gated_gelu ? 2 * F : F, dm))));
@@ -745,9 +884,16 @@ int run_decoder(rk_engine* e, Slot& sl, int Ld, const DecTree* tree = nullptr) {
   // Row limit (option dec_gemv_rows, default 4): measured cross-over at flan-t5-large dims and 1 450-token prompts, whole calls,
   // GEMV against weight-streaming MFMA family: 2 rows 4.87 / 5.20 ms, 4 rows 6.38 / 6.67, 6 rows 8.30 / 8.25, 8 rows 9.41 / 9.39,
   // 12 rows 12.86 / 12.36, 16 rows 15.18 / 14.58 (profiles/r06_few_rows_ab.txt) - every workgroup stages ALL rows in LDS and the
-  // per-column VALU work grows with the rows; rk_t5_greedy2's 13-row tree pass stays on the matrix cores.
-  const bool fuse_any = (e->opt.dec_fuse == 2 || (e->opt.dec_fuse == 1 && Ld == 1));
-  const bool few = dfold && e->opt.dec_gemv && Ld >= 2 && M <= e->opt.dec_gemv_rows && !fuse_any &&
+  // per-column VALU work grows with the rows; rk_t5_greedy2's 13-row tree pass stays on the matrix cores.  A pass that asked for
+  // the fused cross-attention projections (below) never takes it, whether or not they can run.
+  // Query-side cross-attention with the projections around it fused per (head, row slab) (dec_fuse = 1, the default): 3 launches
+  // instead of 5.  Measured (r04): at 100-320 rows (pointwise, one decoder position) the fused pair is 9 us per layer faster and the
+  // grouped pipeline gains 1.2 %; at the 13 rows x 23 chunks of a setwise compare it is 4 us per layer SLOWER (the separate GEMMs
+  // spread the cold weights of a layer over 512 + 5120 workgroups).  The family follows from the CALL SHAPE, never from the batch
+  // (the two round differently): fused for one decoder position, separate beyond (dec_fuse = 2 forces the fused form: tests)
+  const bool fuse_asked = e->opt.dec_fuse == 2 || (e->opt.dec_fuse == 1 && Ld == 1);
+  const bool fuse = fuse_asked && !sl.have_cross_kv && dm % 128 == 0;   // (eight K ranges of whole k16 steps per workgroup)
+  const bool few = dfold && e->opt.dec_gemv && Ld >= 2 && M <= e->opt.dec_gemv_rows && !fuse_asked &&
                    gemv_fits(M, dm) && gemv_fits(M, I) && gemv_fits(M, F);   // every K of the pass's projections
   const GemmFamily fam = few ? GEMM_GEMV : (ws ? GEMM_STREAM : GEMM_TILED);
   // folded: the stream is dxraw[cur] with nb block sums per row in ssq[cur] (nb: the plan of the GEMM that wrote them; 0: the
@@ -771,8 +917,8 @@ int run_decoder(rk_engine* e, Slot& sl, int Ld, const DecTree* tree = nullptr) {
     return gemm(e, st, c.on(fam), &nb);
   };
   embed(e, st, sl.d_dec_ids, sl.dhidden, M, dfold ? sl.dxraw[0] : nullptr, dfold ? sl.drowscale : nullptr);
-  const size_t smem_self = (64 + 256 + 8 + (size_t)Ld) * sizeof(float);
-  const size_t smem_cross = (64 + 256 + 8 + (size_t)sl.maxL) * sizeof(float);
+  const DecAttnPlan self_plan = plan_dec_attn(e, false, B, Ld, Ld, d.n_heads, tree ? tree->rows : 0);
+  const DecAttnPlan cross_plan = plan_dec_attn(e, true, B, Ld, sl.maxL, d.n_heads, 0);
   for (int l = 0; l < d.n_dec_layers; ++l) {
     const DecLayerW& w = e->dec[l];
     const GemmFold in0 = norm(w.ln0);
@@ -783,100 +929,23 @@ int run_decoder(rk_engine* e, Slot& sl, int Ld, const DecTree* tree = nullptr) {
       RC(resid(Gemm(PC_DEC_GEMM, EPI_RESID_F32, xin(), dm, dfold ? w.ov_f : w.ov, dm, sl.dhidden, dm, M, dm, dm).with(in0)));
     } else {
       RC(gemm(e, st, Gemm(PC_DEC_GEMM, EPI_STORE_F16, xin(), dm, dfold ? w.qkv_f : w.qkv, dm, sl.dqkv, 3 * I, M, 3 * I, dm).on(fam).with(in0)));
-      AttnDecArgs a{sl.dqkv, 3 * I, sl.dqkv + I, sl.dqkv + 2 * I, 3 * I, nullptr, sl.dctx, I, e->lut_dec, Ld, 1, Ld};
-      {
-        Bracket br(e, st, PC_DEC_ATTN, 4.0 * M * Ld * I, 0);
-        if (tree) {
-          a.tree_keys = tree->keys; a.tree_pos = tree->pos;
-          hipLaunchKernelGGL(attn_dec_kernel, dim3(1, d.n_heads, M), dim3(256), smem_self, st, a);
-        } else if (e->opt.dec_cross_mfma && Ld > XA_MAX_LD && Ld <= ATTX_MAXQ) {
-          // long prefixes (the materialised-K / V regime, qlm): causal self-attention on the matrix cores too (round 6); the choice
-          // follows from the call's position count alone, like the cross-attention's
-          hipLaunchKernelGGL(attn_dec_cross_mfma_kernel, dim3(d.n_heads, B), dim3(128), ATTX_LDS_BYTES, st, a);
-        } else if (e->opt.dec_attn_seq && attn_dec_seq_lds(Ld) <= 160 * 1024) {   // one workgroup per (head, sequence): K / V staged once (same bits)
-          hipLaunchKernelGGL(attn_dec_seq_kernel, dim3(d.n_heads, B), dim3(256), attn_dec_seq_lds(Ld), st, a);
-        } else {
-          hipLaunchKernelGGL(attn_dec_kernel, dim3(Ld, d.n_heads, B), dim3(256), smem_self, st, a);
-        }
-      }
+      launch_dec_attn(e, st, self_plan, AttnDecArgs{sl.dqkv, 3 * I, sl.dqkv + I, sl.dqkv + 2 * I, 3 * I, nullptr, sl.dctx, I, e->lut_dec, Ld, 1, Ld,
+                                                    tree ? tree->keys : nullptr, tree ? tree->pos : nullptr}, 4.0 * M * Ld * I, 0);
       RC(resid(Gemm(PC_DEC_GEMM, EPI_RESID_F32, sl.dctx, I, w.o, I, sl.dhidden, dm, M, dm, I)));
     }
-    // Query-side cross-attention with the projections around it fused per (head, row slab) - decoder_kernels.h: the q
-    // projection + W_k^T q in one launch, the chunk merge + W_v in another (dec_fuse = 1, the default): 3 launches instead of 5
-    // Measured (r04): at 100-320 rows (pointwise, one decoder position) the fused pair is 9 us per layer faster and the grouped
-    // pipeline gains 1.2 %; at the 13 rows x 23 chunks of a setwise compare it is 4 us per layer SLOWER (the separate GEMMs spread
-    // the cold weights of a layer over 512 + 5120 workgroups).  The family follows from the CALL SHAPE, never from the batch
-    // (the two round differently): fused for one decoder position, separate beyond (dec_fuse = 2 forces the fused form: tests)
-    const bool fuse = (e->opt.dec_fuse == 2 || (e->opt.dec_fuse == 1 && Ld == 1)) && !sl.have_cross_kv && dm % 128 == 0;   // (eight K ranges of whole k16 steps per workgroup)
     const GemmFold in1 = norm(w.ln1);
     if (!fuse) RC(gemm(e, st, Gemm(PC_DEC_GEMM, EPI_STORE_F16, xin(), dm, dfold ? w.cq_f : w.cq, dm, sl.dq, I, M, I, dm).on(fam).with(in1)));
     if (!sl.have_cross_kv) {
-      // query-side cross-attention: qk = W_k^T q per head; scores/softmax/weighted sum over the raw encoder states;
-      // ctx = W_v (.) per head  (attention.h: XAttnArgs)
-      const int H = d.n_heads, nch = (sl.maxL + 63) / 64;
-      const int blk = std::max(1, std::min(XA_MAX_ROWS, XA_MAX_CHUNKS / nch));
-      const half_t* wv = e->cross_kv_w + ((size_t)l * 2 * I + I) * dm;
+      // in blocks of rows that fit the workspace
+      const int blk = std::max(1, std::min(XA_MAX_ROWS, XA_MAX_CHUNKS / ((sl.maxL + 63) / 64)));
       for (int r0 = 0; r0 < M; r0 += blk) {
-        const int nr = std::min(blk, M - r0);
-        if (fuse) {
-          DecQKArgs qa{xin() + (size_t)r0 * dm, dm, dfold ? w.cq_f : w.cq, w.ckT, sl.xqk, nr, dm, H,
-                       in1.rowscale ? in1.rowscale + r0 : nullptr, in1.ssq_in ? in1.ssq_in + (size_t)r0 * in1.nb_in : nullptr, in1.nb_in, d.eps, RK_XRAW_SCALE, 32, 1};
-          if (e->opt.dec_fuse_rows > 0) qa.R = std::min(32, e->opt.dec_fuse_rows);
-          else if (nr <= 16) qa.R = 16;   // (a setwise pass: 13 rows - half the MFMA columns, half the x rows; measured at 320 rows: 32 > 16 > 8)
-          // few rows: several workgroups per (head, slab) share the output columns, each streaming 1 / CS of W_k^T (and all of W_q,h)
-          while (qa.CS < 8 && (dm / 64) % (2 * qa.CS) == 0 && (long)((nr + qa.R - 1) / qa.R) * H * qa.CS < e->n_cu / 2) qa.CS *= 2;
-          Bracket br(e, st, PC_DEC_GEMM, 2.0 * nr * (double)dm * I * 2, 2.0 * ((double)I * dm * 2 + (double)nr * H * dm));
-          hipLaunchKernelGGL(dec_cross_qk_kernel, dim3(H, (nr + qa.R - 1) / qa.R, qa.CS), dim3(64 * DEC_NW), 0, st, qa);
-        } else {
-          RC(gemm(e, st, Gemm(PC_DEC_GEMM, EPI_STORE_F16, sl.dq + (size_t)r0 * I, I, w.ckT, 64, sl.xqk, H * dm, nr, dm, 64).heads(H, 64, (long)dm * 64, dm)));
-        }
-        XAttnArgs xa{sl.xqk, sl.enc_out, sl.d_seq_off, sl.xpart, sl.xstat, sl.xctx, Ld, H, dm, nch, r0, tree ? tree->seq : nullptr};
-        const bool fuse_cv = fuse && nch <= DECV_MAXCH;
-        {
-          Bracket br(e, st, PC_DEC_ATTN, 4.0 * nr * (double)sl.maxL * H * dm, (double)sl.T * dm * 2.0 * 2);
-          // MFMA form (weighted sums on the matrix cores, the chunk's encoder rows staged in LDS by a loader wave) whenever
-          // the model width allows its LDS image; the VALU form otherwise.  The choice depends on the MODEL only, never on the
-          // batch (the two round differently).
-          if (e->opt.xattn_mfma && dm % 256 == 0) {             // (every wave takes whole 64-column pieces of its quarter)
-            // few workgroups (a setwise compare): the latency-scheduled form, two pieces per wave (same bits; attention.h)
-            if ((long)nch * nr * ((H + 15) / 16) <= 2 * e->n_cu) hipLaunchKernelGGL(xattn_part_mfma_kernel<true>, dim3(nch, nr, (H + 15) / 16), dim3(256), 0, st, xa);
-            else hipLaunchKernelGGL(xattn_part_mfma_kernel<false>, dim3(nch, nr, (H + 15) / 16), dim3(256), 0, st, xa);
-          } else if ((long)nch * nr * ((H + 15) / 16) >= 2 * e->n_cu)
-            hipLaunchKernelGGL(xattn_part_kernel<16>, dim3(nch, nr, (H + 15) / 16), dim3(256), 0, st, xa);
-          else
-            hipLaunchKernelGGL(xattn_part_kernel<4>, dim3(nch, nr, (H + 3) / 4), dim3(256), 0, st, xa);
-          if (!fuse_cv) hipLaunchKernelGGL(xattn_combine_kernel, dim3(H, nr), dim3(256), 0, st, xa);
-        }
-        if (fuse_cv) {
-          // rows per workgroup: the largest slab that still gives about half the chip a workgroup (results do not depend on it)
-          // (16 rows: 41 KiB of LDS at d = 1024, three workgroups per CU hide each other's load latency)
-          int R = 16;
-          while (R > 2 && (long)((nr + R - 1) / R) * H < e->n_cu / 2) R >>= 1;
-          DecCVArgs ca{sl.xpart, sl.xstat, sl.d_seq_off, tree ? tree->seq : nullptr, Ld, r0, wv, sl.dctx + (size_t)r0 * I, nr, dm, H, nch, I, R};
-          const size_t lds = dec_cv_lds_bytes(dm, R);
-          static std::atomic<uint64_t> attr_done{0};
-          ensure_dynamic_lds((const void*)dec_cross_cv_kernel, 160 * 1024, attr_done);
-          Bracket br(e, st, PC_DEC_GEMM, 2.0 * nr * (double)dm * I, 2.0 * (double)I * dm + 4.0 * (double)nr * nch * H * dm);
-          hipLaunchKernelGGL(dec_cross_cv_kernel, dim3(H, (nr + R - 1) / R), dim3(64 * DEC_NW), lds, st, ca);
-        } else {
-          RC(gemm(e, st, Gemm(PC_DEC_GEMM, EPI_STORE_F16, sl.xctx, H * dm, wv, dm, sl.dctx + (size_t)r0 * I, I, nr, 64, dm).heads(H, dm, (long)64 * dm, 64)));
-        }
+        const XAttnPlan xp = plan_xattn(e, fuse, std::min(blk, M - r0), sl.maxL, d.n_heads, dm);
+        RC(launch_xattn(e, st, sl, xp, l, Ld, r0, xin(), dfold ? w.cq_f : w.cq, in1, tree ? tree->seq : nullptr));
       }
     } else {
       const half_t* kv = sl.cross_kv + (size_t)l * d.max_tokens * 2 * I;
-      AttnDecArgs a{sl.dq, I, kv, kv + I, 2 * I, sl.d_seq_off, sl.dctx, I, nullptr, Ld, 0, sl.maxL};
-      Bracket br(e, st, PC_DEC_ATTN, 4.0 * Ld * (double)sl.T * I, (double)sl.T * 2 * I * 2.0);
-      // sequences of at most ATTX_MAXK keys (every pointwise prompt): the matrix-core kernel; longer ones: the staged kernels.  The
-      // call's position count decides whether the MFMA kernel runs at all, a sequence's own key count which kernel takes it.
-      const bool mfma = e->opt.dec_cross_mfma && Ld >= 2 && Ld <= ATTX_MAXQ;
-      if (mfma) hipLaunchKernelGGL(attn_dec_cross_mfma_kernel, dim3(d.n_heads, B), dim3(128), ATTX_LDS_BYTES, st, a);
-      a.skip_short = mfma ? 1 : 0;
-      if (mfma && sl.maxL <= ATTX_MAXK) {
-        // nothing left for the staged kernels
-      } else if (e->opt.dec_attn_seq && Ld >= 2 && attn_dec_seq_lds(sl.maxL) <= 160 * 1024)
-        hipLaunchKernelGGL(attn_dec_seq_kernel, dim3(d.n_heads, B), dim3(256), attn_dec_seq_lds(sl.maxL), st, a);
-      else
-        hipLaunchKernelGGL(attn_dec_kernel, dim3(Ld, d.n_heads, B), dim3(256), smem_cross, st, a);
+      launch_dec_attn(e, st, cross_plan, AttnDecArgs{sl.dq, I, kv, kv + I, 2 * I, sl.d_seq_off, sl.dctx, I, nullptr, Ld, 0, sl.maxL},
+                      4.0 * Ld * (double)sl.T * I, (double)sl.T * 2 * I * 2.0);
     }
     RC(resid(Gemm(PC_DEC_GEMM, EPI_RESID_F32, sl.dctx, I, w.co, I, sl.dhidden, dm, M, dm, I)));
     {
@@ -968,7 +1037,7 @@ int check_batch(rk_engine* e, Slot& sl, const int32_t* tokens, const int32_t* of
   if (T > e->d.max_tokens) return fail(e, RK_ERR_CAPACITY, "%d tokens > max_tokens %d", T, e->d.max_tokens);
   for (int t = 0; t < T; ++t)
     if (tokens[t] < 0 || tokens[t] >= e->d.vocab) return fail(e, RK_ERR_INVALID, "token id %d out of range at %d", tokens[t], t);
-  if ((64 + 256 + 8 + (size_t)maxL) * sizeof(float) > 160 * 1024 || maxL > 65536)
+  if (attn_dec_lds(maxL) > 160 * 1024 || maxL > 65536)
     return fail(e, RK_ERR_CAPACITY, "sequence of %d tokens exceeds the cross-attention LDS budget", maxL);
   sl.maxL = maxL; sl.minL = minL; sl.T = T; sl.n_seq = n_seq;
   return RK_OK;
@@ -1489,12 +1558,9 @@ int rk_engine_finalize(rk_engine* e) {
     HIPCHK(e, hipHostMalloc((void**)&sl.h_scores, e->scores_cap * sizeof(float), hipHostMallocDefault));
     HIPCHK(e, hipHostMalloc((void**)&sl.h_small, 4 * 8192 * sizeof(int), hipHostMallocDefault));
   }
-  // dynamic-LDS opt-in for the kernels that may exceed the 64 KiB default
-  const int dec_smem_max = (int)((64 + 256 + 8 + (size_t)std::max(d.max_tokens, d.max_dec_len)) * sizeof(float));
-  if (dec_smem_max > 160 * 1024) { /* checked per call against maxL */ }
-  // best effort: only kernels asking for more than the default dynamic-LDS window need the opt-in
-  (void)hipFuncSetAttribute((const void*)attn_dec_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            std::min(dec_smem_max, 160 * 1024));
+  // dynamic-LDS opt-in (best effort) for the kernels that may exceed the 64 KiB default (check_batch refuses longer calls)
+  const int dec_smem_max = (int)attn_dec_lds(std::max(d.max_tokens, d.max_dec_len));
+  (void)hipFuncSetAttribute((const void*)attn_dec_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, std::min(dec_smem_max, 160 * 1024));
   (void)hipFuncSetAttribute((const void*)attn_dec_seq_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
 #define GEMM_ATTR(EPI)                                                                                              \
   (void)hipFuncSetAttribute((const void*)gemm_f16_kernel<EPI, true>, hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_LDS_BYTES); \
@@ -1911,8 +1977,8 @@ static int llama_prefill(rk_engine* e, const int32_t* tokens, const int32_t* off
   GemmFold cons, prod;
   cons.rowscale = sl.rowscale; prod.xraw = sl.xraw; prod.ssq = sl.ssq;
   int nb = 0;                                   // block sums per row of the last residual GEMM
+  const CausalAttnPlan ap = plan_llama_attn(e, n_seq, sl.maxL, l.n_heads, l.n_kv_heads);
   embed(e, st, sl.d_tokens, sl.hidden, T, sl.xraw, sl.rowscale);
-  const float scale_log2e = (1.0f / std::sqrt(128.0f)) * 1.4426950408889634f;
   for (int i = 0; i < l.n_layers; ++i) {
     const LlamaLayerW& w = e->ll[i];
     RC(gemm(e, st, Gemm(PC_ENC_GEMM_QKV, EPI_STORE_F16, sl.xraw, dm, w.qkv_f, dm, sl.qkv, ldq, T, ldq, dm).with(cons)));
@@ -1920,26 +1986,7 @@ static int llama_prefill(rk_engine* e, const int32_t* tokens, const int32_t* off
       Bracket br(e, st, PC_OTHER, 0, (double)T * (Q + KV) * 4.0);
       hipLaunchKernelGGL(rope128_kernel, dim3(T), dim3(256), 0, st, sl.qkv, e->d_pos, e->rope_cos, e->rope_sin, ldq, l.n_heads + l.n_kv_heads);
     }
-    {
-      AttnCausalArgs a{sl.qkv, sl.ctx, sl.d_seq_off, ldq, Q, l.n_heads, l.n_kv_heads, scale_log2e, 0, 0, e->opt.attn_ko};
-      Bracket br(e, st, PC_ENC_ATTN, 2.0 * (double)sl.maxL * T * Q, (double)T * (2 * Q + 2 * KV) * 2.0);   // causal: half of 4 L T Q
-      if (e->opt.llama_attn_dma) {     // K / V chunks by LDS-DMA, V^T by transposing reads (round 5); chosen by the option alone: batch-independent
-        static std::atomic<uint64_t> attr_done{0};
-        static std::atomic<uint64_t> attr_done8{0};
-        int lds = ATCD_LDS_BYTES, lds_max = ATCD_LDS_BYTES;
-#ifdef RK_MEASURE
-        lds_max += 49152;
-        if (e->opt.attn_ko & 256) lds += 49152;          // residency probe: 112 KiB per workgroup = ONE per CU for certain
-#endif
-        const int nw = e->opt.llama_attn_nw == 8 ? 8 : 4;   // same bits either way
-        a.n_seq = n_seq; a.nqb = (sl.maxL + 32 * nw - 1) / (32 * nw);
-        const dim3 grid(xcd_grid(n_seq * l.n_kv_heads, (l.n_heads / l.n_kv_heads) * a.nqb));
-        if (nw == 8) { ensure_dynamic_lds((const void*)attn_causal128_dma_kernel<8>, lds_max, attr_done8); hipLaunchKernelGGL(attn_causal128_dma_kernel<8>, grid, dim3(512), lds, st, a); }
-        else { ensure_dynamic_lds((const void*)attn_causal128_dma_kernel<4>, lds_max, attr_done); hipLaunchKernelGGL(attn_causal128_dma_kernel<4>, grid, dim3(256), lds, st, a); }
-      } else {
-        hipLaunchKernelGGL(attn_causal128_kernel, dim3((sl.maxL + 127) / 128, l.n_heads, n_seq), dim3(256), 0, st, a);
-      }
-    }
+    launch_llama_attn(e, st, sl, ap);
     RC(gemm(e, st, Gemm(PC_ENC_GEMM_O, EPI_RESID_F32, sl.ctx, Q, w.o, Q, sl.hidden, dm, T, dm, Q).with(prod), &nb));
     rowscale(e, st, sl.ssq, sl.rowscale, T, nb);
     RC(gemm(e, st, Gemm(PC_ENC_GEMM_FFN_IN, EPI_SWIGLU_F16, sl.xraw, dm, w.gu_f, dm, sl.ffh, F, T, 2 * F, dm).with(cons)));
@@ -2236,7 +2283,7 @@ const OptionDesc kOptions[] = {
   {"gemm_variant", &rk_engine::Options::gemm_variant, 0, 120, nullptr, "tile variant: 0 auto, 1..6 see choose_variant; measurement builds: 80+ / 100+ knock-outs"},
   {"dec_fuse_rows", &rk_engine::Options::dec_fuse_rows, 0, 32, nullptr, "rows per workgroup of dec_cross_qk_kernel (0 = auto); same bits"},
   {"dec_fuse", &rk_engine::Options::dec_fuse, 0, 2, nullptr, "few-row decoder: projections around the query-side cross-attention fused at one position (1), always (2), never (0)"},
-  {"llama_attn_nw", &rk_engine::Options::llama_attn_nw, 0, 8, "0,4,8", "waves per workgroup of the Llama LDS-DMA attention kernel (0 = default 8); same bits"},
+  {"llama_attn_nw", &rk_engine::Options::llama_attn_nw, 0, 8, "0,4,8", "waves per workgroup of the Llama LDS-DMA attention kernel (0 = default 4); same bits"},
   {"llama_attn_dma", &rk_engine::Options::llama_attn_dma, 0, 1, nullptr, "Llama causal attention: LDS-DMA kernel (1) or the register-staged first kernel (0); differ within fp16 noise"},
   {"attn_long_xcd", &rk_engine::Options::attn_long_xcd, 0, 1, nullptr, "long-sequence attention: workgroups of a (sequence, head) pair on one XCD (1) or dealt over all eight (0); same bits"},
   {"attn_long_nw", &rk_engine::Options::attn_long_nw, 0, 12, "0,3,4,6,12", "waves per workgroup of the long-sequence attention kernel (0 = default 4); same bits"},
