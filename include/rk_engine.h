@@ -92,6 +92,15 @@ int rk_t5_greedy2(rk_engine* e, const int32_t* tokens, const int32_t* seq_offset
                   const int32_t* dec_prefix, int dec_len, const int32_t* cand_ids, int n_cand, int eos_id, int pad_id,
                   int32_t* out_tokens, int32_t* out_steps);
 
+/* rk_t5_greedy's arguments and contract (out_tokens[n_seq][max_new], pad_id after EOS, remaining columns pad_id once every row
+ * has finished, *out_steps = the decoder steps rk_t5_greedy would have executed, the same capacity errors), decoded
+ * incrementally: each step runs ONE new decoder row per sequence against a self-attention K / V cache, the arg-max is fed back on
+ * the device and the step is one replayed graph.  For long continuations (the listwise permutation, up to 20 tokens).
+ * replaces: self.llm.generate(input_ids)  (ref: llmrankers/listwise.py:248) */
+int rk_t5_generate(rk_engine* e, const int32_t* tokens, const int32_t* seq_offsets, int n_seq,
+                   const int32_t* dec_prefix, int dec_len, int max_new, int eos_id, int pad_id,
+                   int32_t* out_tokens, int32_t* out_steps);
+
 /* ---- staged / asynchronous form: inputs resident in HBM, used by bench.py and the multi-GPU driver ---- */
 int rk_t5_stage(rk_engine* e, const int32_t* tokens, const int32_t* seq_offsets, int n_seq);   /* H2D, synchronous */
 /* enqueue encoder + decoder + head on the engine stream for the staged batch; scores land in an engine-owned

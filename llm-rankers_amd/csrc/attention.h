@@ -1367,6 +1367,81 @@ __global__ __launch_bounds__(256) void attn_dec_kernel(AttnDecArgs p) {
   }
 }
 
+// Incremental decoder self-attention (rk_t5_generate): ONE new row per sequence at the position t that the device holds in *pos.
+// The row's k and v go into the sequence's cache at t, then the row attends to the cached keys 0 .. t (hf: modeling_t5.py:448-509
+// with past_key_value: no 1/sqrt(d) scaling, unidirectional bias at bucket(j - t)).  The arithmetic is attn_dec_kernel's for the
+// query row t - the same fma chains, reduction trees and key shares per wave - so its context row is BIT-IDENTICAL to that
+// kernel's row t over the same q / K / V rows (tests).  Key t is read from the new row itself, keys before it from the cache.
+// grid = (H, B), 256 threads, dynamic LDS = attn_dec_kernel's for P keys.
+struct AttnCachedArgs {
+  const half_t* qkv; int ldqkv;   // this step's rows, one per sequence: q | k | v at columns 0 | inner | 2 inner
+  half_t* cache;                  // this layer's cache [B][P][2 inner]: k | v per position
+  int P, inner;                   // positions per sequence in the cache, n_heads * 64
+  const int* pos;                 // device: the position t of this step's rows
+  half_t* ctx; int ldctx;         // out rows b
+  const float* bias_lut;          // [H][RK_LUT_N] (the decoder's table)
+};
+__global__ __launch_bounds__(256) void attn_dec_cached_kernel(AttnCachedArgs p) {
+  extern __shared__ __attribute__((aligned(16))) float dec_smem[];
+  float* sQ = dec_smem;            // [64]
+  float* sPart = sQ + 64;          // [4][64]
+  float* sRed = sPart + 256;       // [8]
+  float* sP = sRed + 8;            // [P]
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int h = blockIdx.x, b = blockIdx.y;
+  const int i = *p.pos;
+  if (i < 0 || i >= p.P) return;   // (never past the cache, whatever the host enqueued)
+  const int I2 = 2 * p.inner, nk = i + 1;
+  const half_t* qr = p.qkv + (size_t)b * p.ldqkv;
+  half_t* cb = p.cache + (size_t)b * p.P * I2;
+  if (tid < 64) {
+    cb[(size_t)i * I2 + h * 64 + tid] = qr[p.inner + h * 64 + tid];
+    cb[(size_t)i * I2 + p.inner + h * 64 + tid] = qr[2 * p.inner + h * 64 + tid];
+    sQ[tid] = (float)qr[h * 64 + tid];
+  }
+  __syncthreads();
+  auto krow = [&](int j) { return j < i ? cb + (size_t)j * I2 + h * 64 : qr + p.inner + h * 64; };
+  float mx = -1e30f;
+  for (int j = tid; j < nk; j += 256) {
+    float s = dec_qk_dot(sQ, krow(j));
+    s += dec_bias(p.bias_lut, h, j, i);
+    sP[j] = s;
+    mx = fmaxf(mx, s);
+  }
+  mx = dec_wave_max(mx);
+  if (lane == 0) sRed[wave] = mx;
+  __syncthreads();
+  mx = fmaxf(fmaxf(sRed[0], sRed[1]), fmaxf(sRed[2], sRed[3]));
+  float sum = 0.f;
+  for (int j = tid; j < nk; j += 256) {
+    const float e = __expf(sP[j] - mx);
+    sP[j] = e;
+    sum += e;
+  }
+  sum = dec_wave_sum(sum);
+  if (lane == 0) sRed[4 + wave] = sum;
+  __syncthreads();
+  sum = (sRed[4] + sRed[5]) + (sRed[6] + sRed[7]);
+  const half_t* vc = cb + p.inner + h * 64 + lane;
+  const half_t* vn = qr + 2 * p.inner + h * 64 + lane;
+  sPart[wave * 64 + lane] = dec_pv_part(sP, nk, wave, [&](int j) { return (float)(j < i ? vc[(size_t)j * I2] : *vn); });
+  __syncthreads();
+  if (wave == 0) {
+    const float acc = (sPart[lane] + sPart[64 + lane]) + (sPart[128 + lane] + sPart[192 + lane]);
+    p.ctx[(size_t)b * p.ldctx + h * 64 + lane] = f2h_sat(acc / sum);
+  }
+}
+// Option dec_cached_attn = 0 routes the cached pass through attn_dec_kernel's tree form instead (the on-device cross-check):
+// this kernel appends the step's k and v to the cache and publishes the position as the rows' tree position.  grid = (B).
+__global__ __launch_bounds__(256) void kv_append_kernel(AttnCachedArgs p, int* tree_pos) {
+  const int b = blockIdx.x, i = *p.pos, I2 = 2 * p.inner;
+  if (i < 0 || i >= p.P) return;
+  const half_t* qr = p.qkv + (size_t)b * p.ldqkv + p.inner;
+  half_t* dst = p.cache + ((size_t)b * p.P + i) * I2;
+  for (int c = threadIdx.x; c < I2; c += 256) dst[c] = qr[c];
+  if (threadIdx.x == 0) tree_pos[b] = i;
+}
+
 // The same attention with ONE workgroup per (head, sequence) for decoder passes of several positions (qlm: ~30 label
 // positions, ref: llmrankers/pointwise.py:41-82; greedy prefixes): the per-row kernel above is launched as L_d x H x B
 // workgroups that each re-read the head's K and V rows of their sequence (27 x 36 KB through L2 per (head, sequence) in a

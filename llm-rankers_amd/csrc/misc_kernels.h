@@ -136,6 +136,38 @@ __global__ __launch_bounds__(256) void argmax_blocks_kernel(const float* __restr
   }
 }
 
+// Token feedback of rk_t5_generate's step graph, after argmax_blocks_kernel: the decoder just ran input position t = st[0].
+// Prefix positions (t + 1 < dec_len) are forced: the next input is prefix[t + 1].  Otherwise column n = t + 1 - dec_len of the
+// output gets the row's arg-max, or pad once the row has finished (hf: generation/utils.py greedy: finished rows emit pad); EOS
+// finishes a row; the token is the row's next input.  st[1] (0 until then) becomes the number of columns the recompute loop of
+// rk_t5_greedy would have produced: n + 1 at the column where the last row finished, or max_new.  The position advances, held
+// at the cache's last row: a step enqueued after the end writes nothing but pads over pads.  One workgroup.
+// st = {t, finished step, eos, pad}
+__global__ __launch_bounds__(256) void greedy_advance_kernel(const int* __restrict__ argmax, int* st, const int* __restrict__ prefix,
+                                                             int* done, int* out, int* next_ids, int n_seq, int dec_len, int max_new) {
+  __shared__ int s_all;
+  const int tid = threadIdx.x, t = st[0], eos = st[2], pad = st[3], n = t + 1 - dec_len;
+  if (tid == 0) s_all = 1;
+  __syncthreads();
+  for (int b = tid; b < n_seq; b += 256) {
+    int next = pad;
+    if (n < 0) next = prefix[t + 1];
+    else if (n < max_new) {
+      const int tok = done[b] ? pad : argmax[b];
+      out[(size_t)b * max_new + n] = tok;
+      if (tok == eos) done[b] = 1;
+      next = tok;
+    }
+    next_ids[b] = next;
+    if (!done[b]) s_all = 0;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    if (n >= 0 && n < max_new && st[1] == 0 && (s_all || n == max_new - 1)) st[1] = n + 1;
+    st[0] = t + 1 < dec_len + max_new - 1 ? t + 1 : dec_len + max_new - 1;
+  }
+}
+
 // QLM score (ref: llmrankers/pointwise.py:77-79) from the fused head (gemm.h: EPI_LSE_F32): stats [rows, nblk] = (block max, sum exp(x - block max)), xlab [rows] =
 // the label's logit.  out[b] = -sum_t ( logsumexp_t - xlab[b, t] ), logsumexp_t = M + log(sum_blocks s * exp(m - M)).
 // One block per sequence; the blocks of a position are merged in a fixed order, the positions summed in order (deterministic).

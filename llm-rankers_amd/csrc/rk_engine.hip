@@ -107,6 +107,10 @@ struct rk_engine {
   float* logits = nullptr; size_t logits_cap = 0;              // qlm head: per-block (max, sum exp) pairs [rows, vocab/32] + label logits [rows]; slot 0 only
   const int* lse_labels = nullptr; int lse_npos = 0; float* lse_xlab = nullptr;   // arguments of the next EPI_LSE_F32 launch
   float* amax_val = nullptr; int* amax_idx = nullptr; size_t amax_rows = 0;   // greedy head: per-row block maxima / first columns
+  // rk_t5_generate: self-attention K / V cache [n_dec_layers][n_seq][P][2 inner] (grown like amax; kv_gen counts the moves), the
+  // per-call int block on the device (state, prefix, finished rows, output, tree arrays), pinned read-back of the finished step
+  half_t* kv_cache = nullptr; size_t kv_cap = 0; int kv_gen = 0;
+  int* gen_buf = nullptr; size_t gen_cap = 0; int* gen_pin = nullptr; hipEvent_t ev_gen[2] = {nullptr, nullptr};
   size_t scores_cap = 0;
   Slot slots[RK_SLOTS];
   // options / measurement
@@ -117,7 +121,8 @@ struct rk_engine {
     int glds = 1, skinny = 0x3F, overlap = 1, gemm_variant = 0, attn_short = 5, xattn_direct = 1, attn_heads_per_wg = 0, attn_ko = 0,
         gemm_persistent = 1, fold_norm = 1, s64_stages = 0, dec_fold_norm = 1, greedy_spec = 160, consumer_stats = 1, xattn_mfma = 1,
         dec_ffn_tiled = 1, gemm_split = 1, dec_fuse = 1, dec_fuse_rows = 0, dec_attn_seq = 1, attn_long = 1, attn_long_nw = 0,
-        llama_attn_dma = 1, attn_long_xcd = 1, llama_attn_nw = 0, dec_graph = 1, gemm_sk = 1, dec_cross_mfma = 1, dec_gemv = 1, dec_gemv_rows = 4;
+        llama_attn_dma = 1, attn_long_xcd = 1, llama_attn_nw = 0, dec_graph = 1, gemm_sk = 1, dec_cross_mfma = 1, dec_gemv = 1, dec_gemv_rows = 4,
+        dec_cached_attn = 1;
   } opt;
   float* attn_trace = nullptr;   // measurement builds only (option attn_trace)
   int n_cu = 256;
@@ -861,15 +866,22 @@ int run_encoder(rk_engine* e, Slot& sl, bool need_cross_kv) {
 // common prefix.  rows = row count, Ld = longest position count; device arrays: keys[r * Ld + j] = row at position j of
 // row r's sequence, pos[r] = position of row r, seq[r] = its encoder sequence.  Query-side cross-attention only.
 struct DecTree { int rows; const int* keys; const int* pos; const int* seq; };
+// cache (rk_t5_generate): the incremental pass - ONE new row per sequence (Ld = 1) at the position *pos on the device, layer l's
+// self-attention K / V cache at kv + l * B * P * 2I.  The layer is the one-position chain's (fused query-side cross-attention,
+// folded norms, tiled FFN-in: every family from the call shape, never from B) but for self-attention: the QKV projection of the
+// new row, then attn_dec_cached_kernel over the cache.  tree_keys / tree_pos: option dec_cached_attn = 0 (attn_dec_kernel's
+// tree form over the cache rows b * P + j).
+struct DecCache { half_t* kv; int P; const int* pos; const int* tree_keys; int* tree_pos; };
 // (Tried and dropped, round 3: the single-position pass of 320 rows as TWO or THREE chains of 32-row-aligned row ranges on
 // helper streams, fork / join by events (parallel branches of the decoder graph) - bit-identical, but 6.4-6.6k passages/s
 // against 7.3k: what the decoder costs the encoder running beside it is every one of its kernels delaying the persistent
 // GEMM it meets, so more, smaller decoder kernels cost more, not less.  The lever is fewer and shorter decoder kernels.)
-int run_decoder(rk_engine* e, Slot& sl, int Ld, const DecTree* tree = nullptr) {
+int run_decoder(rk_engine* e, Slot& sl, int Ld, const DecTree* tree = nullptr, const DecCache* cache = nullptr) {
   const rk_model_desc& d = e->d;
   hipStream_t st = dec_stream(e, sl);
   const int B = sl.n_seq, M = tree ? tree->rows : B * Ld, I = e->inner, dm = d.d_model, F = d.d_ff;
   if (tree && (sl.have_cross_kv || Ld < 2)) return fail(e, RK_ERR_STATE, "the tree form needs the query-side cross-attention and L_d >= 2");
+  if (cache && (tree || sl.have_cross_kv || Ld != 1)) return fail(e, RK_ERR_STATE, "the incremental pass needs the query-side cross-attention and one row per sequence");
   const bool ws = Ld <= 4;   // few decoder positions: weight-streaming GEMMs (any number of sequences); else tiled
   // Folded RMSNorm on the weight-streaming path (as in the encoder, minus the statistics kernel): the residual GEMMs leave
   // the new rows as fp16 (dxraw) with their sums of squares per 32-column block (dssq), the GEMM behind the norm reads
@@ -922,7 +934,22 @@ int run_decoder(rk_engine* e, Slot& sl, int Ld, const DecTree* tree = nullptr) {
   for (int l = 0; l < d.n_dec_layers; ++l) {
     const DecLayerW& w = e->dec[l];
     const GemmFold in0 = norm(w.ln0);
-    if (Ld == 1) {
+    if (cache) {
+      RC(gemm(e, st, Gemm(PC_DEC_GEMM, EPI_STORE_F16, xin(), dm, dfold ? w.qkv_f : w.qkv, dm, sl.dqkv, 3 * I, M, 3 * I, dm).on(fam).with(in0)));
+      const AttnCachedArgs ca{sl.dqkv, 3 * I, cache->kv + (size_t)l * B * cache->P * 2 * I, cache->P, I, cache->pos, sl.dctx, I, e->lut_dec};
+      {
+        Bracket br(e, st, PC_DEC_ATTN, 4.0 * B * (double)cache->P * I, (double)B * cache->P * 2 * I * 2.0);
+        if (e->opt.dec_cached_attn) {
+          hipLaunchKernelGGL(attn_dec_cached_kernel, dim3(d.n_heads, B), dim3(256), attn_dec_lds(cache->P), st, ca);
+        } else {
+          hipLaunchKernelGGL(kv_append_kernel, dim3(B), dim3(256), 0, st, ca, cache->tree_pos);
+          hipLaunchKernelGGL(attn_dec_kernel, dim3(1, d.n_heads, B), dim3(256), attn_dec_lds(cache->P), st,
+                             AttnDecArgs{sl.dqkv, 3 * I, ca.cache, ca.cache + I, 2 * I, nullptr, sl.dctx, I, e->lut_dec, cache->P, 1, cache->P,
+                                         cache->tree_keys, cache->tree_pos});
+        }
+      }
+      RC(resid(Gemm(PC_DEC_GEMM, EPI_RESID_F32, sl.dctx, I, w.o, I, sl.dhidden, dm, M, dm, I)));
+    } else if (Ld == 1) {
       // one decoder position: softmax over a single key is 1, so self-attention is exactly o(v(x)) — the q/k
       // projections, scores and bias are dead (hf: modeling_t5.py:448-509 at L_d = 1)
       // ... and o(v(x)) = (W_o W_v) x: one GEMM with the product matrix formed once at finalize
@@ -977,10 +1004,11 @@ int run_decoder(rk_engine* e, Slot& sl, int Ld, const DecTree* tree = nullptr) {
 
 // Encoder on s_enc, decoder on s_dec, ordered by events; the decoder of this slot's PREVIOUS batch must have
 // finished reading cross_kv before the encoder overwrites it.
-int encoder_then_handoff(rk_engine* e, Slot& sl, int max_ld) {
+// query_side: the caller's decoder takes the query-side cross-attention whatever its length (rk_t5_generate: one row per step).
+int encoder_then_handoff(rk_engine* e, Slot& sl, int max_ld, bool query_side = false) {
   hipStream_t se = enc_stream(e, sl), sd = dec_stream(e, sl);
   if (sl.dec_pending && sd != se) HIPCHK(e, hipStreamWaitEvent(se, sl.ev_dec, 0));
-  int rc = run_encoder(e, sl, !use_xattn_direct(e, sl, max_ld));
+  int rc = run_encoder(e, sl, !query_side && !use_xattn_direct(e, sl, max_ld));
   if (rc) return rc;
   if (sd != se) {
     HIPCHK(e, hipEventRecord(sl.ev_enc, se));
@@ -1324,6 +1352,10 @@ void rk_engine_destroy(rk_engine* e) {
   if (e->logits) hipFree(e->logits);
   if (e->amax_val) hipFree(e->amax_val);
   if (e->amax_idx) hipFree(e->amax_idx);
+  if (e->kv_cache) hipFree(e->kv_cache);
+  if (e->gen_buf) hipFree(e->gen_buf);
+  if (e->gen_pin) hipHostFree(e->gen_pin);
+  for (hipEvent_t ev : e->ev_gen) if (ev) hipEventDestroy(ev);
   for (auto& w : e->sk_ws) { if (w.slabs) hipFree(w.slabs); if (w.cnt) hipFree(w.cnt); }
   for (auto& sl : e->slots) {
     if (sl.h_scores) hipHostFree(sl.h_scores);
@@ -1740,6 +1772,103 @@ int rk_t5_greedy(rk_engine* e, const int32_t* tokens, const int32_t* seq_offsets
   if ((rc = sync_all(e))) return rc;
   sl.dec_pending = false;
   if (out_steps) *out_steps = steps;
+  return RK_OK;
+}
+
+// rk_t5_generate's device memory: the K / V cache for n_seq sequences of P positions (grown like ensure_amax, between calls only -
+// never inside a capture; a move changes kv_gen, which is part of the step graph's key), the per-call int block, the pinned
+// read-back words and their events.
+static int ensure_gen(rk_engine* e, int n_seq, int P) {
+  const size_t kv = (size_t)e->d.n_dec_layers * n_seq * P * 2 * e->inner;
+  if (kv > e->kv_cap) {
+    int rc = sync_all(e);
+    if (rc) return rc;
+    if (e->kv_cache) HIPCHK(e, hipFree(e->kv_cache));
+    e->kv_cache = nullptr; e->kv_cap = 0;
+    HIPCHK(e, hipMalloc((void**)&e->kv_cache, kv * sizeof(half_t)));
+    e->kv_cap = kv; ++e->kv_gen;
+  }
+  if (!e->gen_buf) {
+    // state, prefix, finished rows, tree positions, output [n_seq][max_new], tree keys [n_seq][P]: at most this many ints
+    const size_t L = (size_t)e->d.max_dec_len, S = (size_t)e->d.max_seqs;
+    e->gen_cap = 8 + L + 2 * S + S * L + S * (L + 1);
+    HIPCHK(e, hipMalloc((void**)&e->gen_buf, e->gen_cap * sizeof(int)));
+    HIPCHK(e, hipHostMalloc((void**)&e->gen_pin, 16 * sizeof(int), hipHostMallocDefault));
+    for (hipEvent_t& ev : e->ev_gen) HIPCHK(e, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+  }
+  return RK_OK;
+}
+
+// Greedy decoding with a self-attention K / V cache: one decoder row per sequence and step (run_decoder's incremental pass), the
+// arg-max fed back on the device (greedy_advance_kernel), the step replayed as ONE graph whose launch arguments never change within
+// the call - position, finished rows and next ids live in device memory.  Prefix positions run as forced steps through the same
+// graph.  The host reads back one word per step (the finished step) and keeps one step queued ahead of the one it waits for; a
+// step after the last changes nothing (greedy_advance_kernel).  Same contract as rk_t5_greedy, which recomputes the whole prefix
+// every step (hf: generation/utils.py:2868-2935 is this cached loop).
+int rk_t5_generate(rk_engine* e, const int32_t* tokens, const int32_t* seq_offsets, int n_seq, const int32_t* dec_prefix,
+                   int dec_len, int max_new, int eos_id, int pad_id, int32_t* out_tokens, int32_t* out_steps) {
+  int rc;
+  if ((rc = rk_t5_stage(e, tokens, seq_offsets, n_seq))) return rc;
+  Slot& sl = e->slots[0];
+  if (!dec_prefix || dec_len <= 0 || max_new <= 0 || dec_len + max_new - 1 > e->d.max_dec_len)
+    return fail(e, RK_ERR_CAPACITY, "dec_len %d + max_new %d exceeds max_dec_len %d", dec_len, max_new, e->d.max_dec_len);
+  if (!out_tokens) return fail(e, RK_ERR_INVALID, "null output");
+  if ((rc = check_ids(e, dec_prefix, dec_len, "decoder"))) return rc;
+  const int P = dec_len + max_new;                                       // cache positions per sequence (the last: a step past the end)
+  if ((rc = ensure_amax(e, (size_t)n_seq, e->d.vocab))) return rc;
+  if ((rc = ensure_gen(e, n_seq, P))) return rc;
+  if ((rc = encoder_then_handoff(e, sl, 1, true))) return rc;
+  hipStream_t sd = dec_stream(e, sl);
+  // the call's int block: {t, finished step, eos, pad} | prefix | done[n] | tree_pos[n] | out[n][max_new] | tree_keys[n][P]
+  const size_t o_pre = 8, o_done = o_pre + dec_len, o_tpos = o_done + n_seq, o_out = o_tpos + n_seq, o_keys = o_out + (size_t)n_seq * max_new;
+  const size_t n_ints = o_keys + (size_t)n_seq * P;
+  std::vector<int> init(n_ints, 0);
+  init[2] = eos_id; init[3] = pad_id;
+  memcpy(&init[o_pre], dec_prefix, dec_len * sizeof(int));
+  for (size_t k = 0; k < (size_t)n_seq * max_new; ++k) init[o_out + k] = pad_id;
+  for (int b = 0; b < n_seq; ++b)
+    for (int j = 0; j < P; ++j) init[o_keys + (size_t)b * P + j] = b * P + j;
+  std::vector<int> ids0(n_seq, dec_prefix[0]);
+  int* g = e->gen_buf;
+  HIPCHK(e, hipStreamSynchronize(sd));
+  HIPCHK(e, hipMemcpy(g, init.data(), n_ints * sizeof(int), hipMemcpyHostToDevice));
+  HIPCHK(e, hipMemcpy(sl.d_dec_ids, ids0.data(), n_seq * sizeof(int), hipMemcpyHostToDevice));
+  sl.cache_dec.clear(); ++sl.dec_epoch;
+  const DecCache kc{e->kv_cache, P, g, g + o_keys, g + o_tpos};
+  auto step = [&]() -> int {
+    int r = run_decoder(e, sl, 1, nullptr, &kc);
+    if (r) return r;
+    rmsnorm(e, sd, sl.dhidden, e->dec_final_ln, sl.dlast, nullptr, n_seq, head_scale(e));
+    if ((r = head_argmax(e, sd, sl.dlast, n_seq, e->d.d_model, e->d.vocab, sl.d_argmax))) return r;
+    Bracket br(e, sd, PC_OTHER, 0, 0);
+    hipLaunchKernelGGL(greedy_advance_kernel, dim3(1), dim3(256), 0, sd, sl.d_argmax, g, g + o_pre, g + o_done, g + o_out, sl.d_dec_ids,
+                       n_seq, dec_len, max_new);
+    return RK_OK;
+  };
+  const std::vector<int> key{3, 0, n_seq, (sl.maxL + 63) / 64, dec_len, max_new, (int)e->amax_rows, e->kv_gen};
+  const int total = dec_len - 1 + max_new;                               // forced prefix steps + one step per new column
+  int* pin = e->gen_pin;
+  bool stop = false;
+  for (int s = 0; s < total && !stop; ++s) {
+    if ((rc = run_graphed(e, sd, key, step))) return rc;
+    if (s >= dec_len - 1) {                                              // a column step: its finished-step word, read back
+      HIPCHK(e, hipMemcpyAsync(pin + (s & 1), g + 1, sizeof(int), hipMemcpyDeviceToHost, sd));
+      HIPCHK(e, hipEventRecord(e->ev_gen[s & 1], sd));
+    }
+    if (s - 1 >= dec_len - 1) {                                          // the previous step's word, while this step runs
+      HIPCHK(e, hipEventSynchronize(e->ev_gen[(s - 1) & 1]));
+      stop = pin[(s - 1) & 1] != 0;
+    }
+  }
+  std::vector<int> res((size_t)n_seq * max_new + 1);
+  HIPCHK(e, hipMemcpyAsync(res.data(), g + o_out, (size_t)n_seq * max_new * sizeof(int), hipMemcpyDeviceToHost, sd));
+  HIPCHK(e, hipMemcpyAsync(res.data() + (size_t)n_seq * max_new, g + 1, sizeof(int), hipMemcpyDeviceToHost, sd));
+  if ((rc = mark_decoder_done(e, sl))) return rc;
+  if ((rc = sync_all(e))) return rc;
+  sl.dec_pending = false;
+  HIPCHK(e, hipGetLastError());
+  memcpy(out_tokens, res.data(), (size_t)n_seq * max_new * sizeof(int));
+  if (out_steps) *out_steps = res[(size_t)n_seq * max_new];
   return RK_OK;
 }
 
@@ -2293,6 +2422,7 @@ const OptionDesc kOptions[] = {
   {"dec_cross_mfma", &rk_engine::Options::dec_cross_mfma, 0, 1, nullptr, "long decoder prefixes (qlm), cross-attention over the materialised K / V: matrix-core kernel for sequences <= 192 keys (1) or the staged fma-chain kernels (0); differ within fp16 noise"},
   {"dec_attn_seq", &rk_engine::Options::dec_attn_seq, 0, 1, nullptr, "decoder attention at several positions: one workgroup per (head, sequence) (1) or per query row (0); same bits"},
   {"gemm_sk", &rk_engine::Options::gemm_sk, 0, 2, nullptr, "ping-pong GEMM, fp32 residual projections with few tiles and a long K: K split over two workgroups (1: choose_ksplit), never (0), wherever it fits (2: tests)"},
+  {"dec_cached_attn", &rk_engine::Options::dec_cached_attn, 0, 1, nullptr, "rk_t5_generate's self-attention: attn_dec_cached_kernel (1) or the cache append + attn_dec_kernel's tree form (0); same bits"},
   {"gemm_split", &rk_engine::Options::gemm_split, 0, 1, nullptr, "rows beyond the ping-pong kernel's last whole round on a fill-in tile variant (1) or one launch (0); same bits"},
 #ifdef RK_MEASURE
   {"attn_ko", &rk_engine::Options::attn_ko, 0, 1 << 20, nullptr, "timing-only knock-outs of the attention kernels (measurement builds)"},

@@ -221,10 +221,14 @@ def default_queries_per_call(kind: str, hits: int) -> int:
     `likelihood`, 129 / 59.6 / 52.0 ms `generation`; round 6, profiles/r06_lockstep_sweep.txt: 16 / 24 / 32 / 48 queries = 46.8 /
     45.4 / 44.4 / 41.7 ms `likelihood`, 50.7 / 47.7 / 46.0 / 44.6 ms `generation` - the more prompts per sift-down step, the
     better the encoder GEMMs' rounds over the CUs are filled.  Thirty-two = two alternating groups of sixteen prompts, the most
-    that still fits ONE engine call of either runtime: 25k tokens of T5Runtime's 49k, the 16 sequences of LlamaRuntime); anything
-    else one query at a time."""
+    that still fits ONE engine call of either runtime: 25k tokens of T5Runtime's 49k, the 16 sequences of LlamaRuntime); listwise:
+    thirty-two sliding-window walks in lockstep (tools/bench_listwise.py, profiles/listwise_bench.jsonl: flan-t5-large dims,
+    100 passages of ~100 tokens, window 4 / step 2: 1 / 8 / 32 queries = 2 150 / 320 / 120 ms per query `generation`, 185 / 42.2 /
+    23.5 ms `likelihood`); anything else one query at a time."""
     if kind == "pointwise":
         return max(1, min(16, -(-1600 // max(1, int(hits)))))
     if kind == "setwise":
+        return 32
+    if kind == "listwise":
         return 32
     return 1

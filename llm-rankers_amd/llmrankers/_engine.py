@@ -49,6 +49,7 @@ ABI = {
     "rk_t5_qlm": (C.c_int, [C.c_void_p, _i32p, _i32p, C.c_int, _i32p, C.c_int, _f32p]),
     "rk_t5_greedy": (C.c_int, [C.c_void_p, _i32p, _i32p, C.c_int, _i32p, C.c_int, C.c_int, C.c_int, C.c_int, _i32p, _i32p]),
     "rk_t5_greedy2": (C.c_int, [C.c_void_p, _i32p, _i32p, C.c_int, _i32p, C.c_int, _i32p, C.c_int, C.c_int, C.c_int, _i32p, _i32p]),
+    "rk_t5_generate": (C.c_int, [C.c_void_p, _i32p, _i32p, C.c_int, _i32p, C.c_int, C.c_int, C.c_int, C.c_int, _i32p, _i32p]),
     "rk_t5_stage": (C.c_int, [C.c_void_p, _i32p, _i32p, C.c_int]),
     "rk_t5_score_staged": (C.c_int, [C.c_void_p, _i32p, C.c_int, _i32p, C.c_int]),
     "rk_engine_sync": (C.c_int, [C.c_void_p]),
@@ -227,6 +228,19 @@ class RkEngine:
         self._chk(self.lib.rk_t5_greedy(self.h, tok.ctypes.data_as(_i32p), off.ctypes.data_as(_i32p), len(seqs),
                                         dp.ctypes.data_as(_i32p), len(dp), max_new, eos_id, pad_id,
                                         out.ctypes.data_as(_i32p), C.byref(steps)))
+        return out, int(steps.value)
+
+    def generate(self, seqs: Sequence[Sequence[int]], dec_prefix: Sequence[int], max_new: int, eos_id: int = 1,
+                 pad_id: int = 0) -> Tuple[np.ndarray, int]:
+        """`greedy`'s result (tokens [B, max_new], decoder steps) from the KV-cached incremental decoder (rk_t5_generate): one
+        decoder row per sequence and step instead of the whole prefix - for long continuations (listwise permutations)."""
+        tok, off = pack_ragged(seqs)
+        dp = _i32(dec_prefix)
+        out = np.empty((len(seqs), max_new), dtype=np.int32)
+        steps = C.c_int32(0)
+        self._chk(self.lib.rk_t5_generate(self.h, tok.ctypes.data_as(_i32p), off.ctypes.data_as(_i32p), len(seqs),
+                                          dp.ctypes.data_as(_i32p), len(dp), max_new, eos_id, pad_id,
+                                          out.ctypes.data_as(_i32p), C.byref(steps)))
         return out, int(steps.value)
 
     # -- staged / async form (bench, multi-GPU) --------------------------------------------------------

@@ -337,6 +337,17 @@ class T5Runtime:
         return np.concatenate(parts, axis=0)
 
 
+    def generate(self, seqs, dec_prefix, max_new, eos_id=1, pad_id=0) -> np.ndarray:
+        """`greedy`'s result ([B, max_new], -1 after the step at which every row of an engine call had finished) from the
+        KV-cached incremental decoder (RkEngine.generate); chunked by capacity the same way."""
+        parts = []
+        for c in self._chunks(seqs):
+            toks, steps = self.engine.generate(c, dec_prefix, max_new, eos_id, pad_id)
+            toks = toks.copy()
+            toks[:, steps:] = -1
+            parts.append(toks)
+        return np.concatenate(parts, axis=0)
+
 class LlamaRuntime:
     """Decoder-only (Llama family) counterpart of T5Runtime: checkpoint directory -> rk_llama_* engine.  Replaces
     `AutoModelForCausalLM.from_pretrained(..., device_map='auto', torch_dtype=fp16)` of ref: llmrankers/setwise.py:65-69."""

@@ -1,0 +1,240 @@
+"""Listwise ranker on the MI355X engine: RankGPT-style sliding windows over a "rank these passages" call.
+
+Drop-in for ref: llmrankers/listwise.py:202-291 (ListwiseLlmRanker) on T5 checkpoints - same constructor, `compare()`
+contract, counters, window walk and permutation rules.  Each compare is one encoder pass over the window's prompt plus either
+a greedy continuation of up to 20 tokens read as a permutation (`scoring='generation'`, engine call rk_t5_generate: one decoder
+row per sequence and step against a K / V cache) or one label-row read at decoder position 1 ordering the passages by their
+label logits (`scoring='likelihood'`, rk_t5_score with the window's label ids).
+Llama checkpoints raise NotImplementedError: listwise generation on them needs an incremental Llama decoder.
+"""
+import copy
+from typing import List, Optional
+
+import numpy as np
+
+from ._batching import tokenize_prompts
+from .rankers import LlmRanker, SearchResult
+
+# the "complete" prompt of the reference (ref: listwise.py:85-104) - model input, byte for byte
+HEAD = ("This is RankGPT, an intelligent assistant that can rank passages based on their relevancy to the query.\n\n"
+        "The following are {num} passages, each indicated by number identifier []. "
+        "I can rank them based on their relevance to query: {query}\n\n")
+ENTRY = "[{rank}] {content}\n\n"
+TAIL = ("The search query is: {query}"
+        "I will rank the {num} passages above based on their relevance to the search query. The passages "
+        "will be listed in descending order using identifiers, and the most relevant passages should be listed "
+        "first, and the output format should be [] > [] > etc, e.g., [1] > [2] > etc.\n\n"
+        "The ranking results of the {num} passages (only identifiers) is:")
+MAX_WORDS = 300                                   # words kept per passage (ref: listwise.py:97)
+# the setwise-style prompt of `likelihood` scoring (ref: listwise.py:265-267)
+QUESTION = 'Given a query "{query}", which of the following passages is the most relevant one to the query?\n\n'
+INSTRUCTION = '\n\nOutput only the passage label of the most relevant passage:'
+
+LLAMA_MESSAGE = ("listwise on the engine needs an incremental (KV-cached) Llama decoder, which it does not have: the listwise "
+                 "ranker is T5-only for now")
+
+
+def resolve_max_new(model_dir: Optional[str] = None) -> int:
+    """New tokens of the reference's bare `llm.generate(input_ids)` (ref: listwise.py:248) for an encoder-decoder checkpoint: the
+    checkpoint's generation_config.json when it sets a length, otherwise the installed transformers' default (>= 5: 20 new
+    tokens; before: max_length 20 counting the decoder start token)."""
+    import json
+    import os
+    if model_dir and os.path.exists(os.path.join(model_dir, "generation_config.json")):
+        with open(os.path.join(model_dir, "generation_config.json")) as f:
+            gc = json.load(f)
+        if gc.get("max_new_tokens") is not None:
+            return int(gc["max_new_tokens"])
+        if gc.get("max_length") is not None:
+            return int(gc["max_length"]) - 1
+    try:
+        from transformers import GenerationConfig
+        ml = GenerationConfig().max_length
+    except Exception:                      # (no transformers: the current default)
+        ml = None
+    return 20 if ml is None else int(ml) - 1
+
+
+def permutation_order(response: str, n: int) -> List[int]:
+    """The window order a generated permutation asks for (ref: listwise.py:118-148): the digit runs of the text are 1-based ids;
+    repeats after the first and ids outside 1..n are dropped; ids never named follow in their current order."""
+    seen, order = set(), []
+    for word in "".join(c if c.isdigit() else " " for c in response).split():
+        k = int(word) - 1
+        if 0 <= k < n and k not in seen:
+            seen.add(k)
+            order.append(k)
+    return order + [k for k in range(n) if k not in seen]
+
+
+class ListwiseLlmRanker(LlmRanker):
+    # "Passage X" / "Passage Y" tokenize into 3 tokens with the T5 vocabulary, hence 23 labels (ref: listwise.py:203-205)
+    CHARACTERS = ["A", "B", "C", "D", "E", "F", "G", "H", "I", "J", "K", "L",
+                  "M", "N", "O", "P", "Q", "R", "S", "T", "U", "V", "W"]
+
+    def __init__(self, model_name_or_path, tokenizer_name_or_path, device, window_size, step_size,
+                 scoring='generation', num_repeat=1, cache_dir=None):
+        # ref: listwise.py:207-238: T5 by config.model_type; Llama is the reference's other family, not on this engine
+        from ._runtime import load_runtime, read_config, resolve_checkpoint
+        path = resolve_checkpoint(model_name_or_path, cache_dir)
+        if read_config(path).get("model_type") == "llama":
+            raise NotImplementedError(LLAMA_MESSAGE)
+        try:
+            runtime = load_runtime(path, device, cache_dir=cache_dir)
+        except NotImplementedError as exc:   # same message shape as ref: listwise.py:238
+            raise NotImplementedError(f"{exc} (listwise)") from None
+        from transformers import T5Tokenizer
+        tokenizer = T5Tokenizer.from_pretrained(
+            tokenizer_name_or_path if tokenizer_name_or_path is not None else model_name_or_path, cache_dir=cache_dir)
+        self._setup(runtime, tokenizer, device, window_size, step_size, scoring, num_repeat, resolve_max_new(path))
+
+    @classmethod
+    def from_runtime(cls, runtime, tokenizer, device="cuda", window_size=3, step_size=1, scoring='generation', num_repeat=1,
+                     max_new=None):
+        """Build the ranker around an existing runtime (a loaded engine, or a test double) and tokenizer.  max_new: new tokens
+        per `generation` compare (None: the installed transformers' default, resolve_max_new)."""
+        self = cls.__new__(cls)
+        self._setup(runtime, tokenizer, device, window_size, step_size, scoring, num_repeat,
+                    resolve_max_new() if max_new is None else int(max_new))
+        return self
+
+    def _setup(self, runtime, tokenizer, device, window_size, step_size, scoring, num_repeat, max_new):
+        if getattr(runtime, "model_type", "t5") == "llama":
+            raise NotImplementedError(LLAMA_MESSAGE)
+        self.device = device
+        self.window_size = window_size
+        self.step_size = step_size
+        self.num_repeat = num_repeat
+        self.scoring = scoring
+        self.llm = runtime
+        self.config = getattr(runtime, "config", None)
+        self.tokenizer = tokenizer
+        self.max_new = max_new
+        self.decoder_start = [int(getattr(runtime, "decoder_start_token_id", 0) or 0)]
+        # likelihood: decoder prompt "<pad> Passage" and the last token of "<pad> Passage {label}" (ref: listwise.py:225-231)
+        self.decoder_input_ids = self.tokenizer.encode("<pad> Passage", add_special_tokens=False)
+        self.target_token_ids = [self.tokenizer.encode(f"<pad> Passage {c}", add_special_tokens=False)[-1] for c in self.CHARACTERS]
+        self.total_compare = 0
+        self.total_prompt_tokens = 0
+        self.total_completion_tokens = 0
+
+    # ------------------------------------------------------------------------------------------------------
+    def _permutation_prompt(self, query: str, docs: List) -> str:
+        num = len(docs)
+        body = "".join(ENTRY.format(rank=r + 1, content=" ".join(d.text.replace('Title: Content: ', '').strip().split()[:MAX_WORDS]))
+                       for r, d in enumerate(docs))
+        return HEAD.format(num=num, query=query) + body + TAIL.format(num=num, query=query)
+
+    def _label_prompt(self, query: str, docs: List) -> str:
+        passages = "\n\n".join(f'Passage {self.CHARACTERS[i]}: "{doc.text}"' for i, doc in enumerate(docs))
+        return QUESTION.format(query=query) + passages + INSTRUCTION
+
+    def _truncated_ids(self, texts: List[str]) -> List[List[int]]:
+        """tokenizer(text, truncation=True).input_ids (ref: listwise.py:244): the memoised full tokenisation, and the tokenizer
+        itself for the prompts longer than model_max_length"""
+        ids = tokenize_prompts(self.tokenizer, texts)
+        limit = getattr(self.tokenizer, "model_max_length", None)
+        for i, row in enumerate(ids):
+            if limit is not None and len(row) > limit:
+                ids[i] = list(self.tokenizer(texts[i], truncation=True)["input_ids"])
+        return ids
+
+    def _compare_windows(self, queries: List[str], doc_lists: List[List]):
+        """ONE engine call for windows that may belong to different queries -> (outputs, prompt tokens per window, completion
+        tokens per window); touches no counter.  A window's result does not depend on what shares the call."""
+        if self.scoring == 'generation':
+            ids = self._truncated_ids([self._permutation_prompt(q, docs) for q, docs in zip(queries, doc_lists)])
+            eos, pad = self.tokenizer.eos_token_id, self.tokenizer.pad_token_id
+            new = np.asarray(self.llm.generate(ids, self.decoder_start, self.max_new, eos, pad))
+            outs, completion = [], []
+            for row in new:
+                toks = [int(t) for t in row if t >= 0]
+                if eos in toks:                                  # alone, this row would have stopped at its own EOS
+                    toks = toks[:toks.index(eos) + 1]
+                out_ids = self.decoder_start + toks              # what generate() returns: the start token + the new ones
+                completion.append(len(out_ids))
+                outs.append(self.tokenizer.decode(out_ids, skip_special_tokens=True).strip())
+            return outs, [len(i) for i in ids], completion
+        if self.scoring == 'likelihood':
+            ids = tokenize_prompts(self.tokenizer, [self._label_prompt(q, docs) for q, docs in zip(queries, doc_lists)])
+            nmax = max(len(docs) for docs in doc_lists)
+            lg = np.asarray(self.llm.score(ids, self.decoder_input_ids, self.target_token_ids[:nmax]))
+            outs = []
+            for r, docs in enumerate(doc_lists):
+                # softmax is monotone: descending label logits, ties in window order (the reference's stable sort, :270-271)
+                order = sorted(range(len(docs)), key=lambda i: -float(lg[r, i]))
+                outs.append('>'.join(f"[{i + 1}]" for i in order))
+            return outs, [len(i) for i in ids], [0] * len(ids)
+        raise UnboundLocalError("local variable 'output' referenced before assignment")   # what the reference does
+
+    def compare(self, query: str, docs: List):
+        # ref: listwise.py:240-283
+        self.total_compare += 1
+        (output,), (ptok,), (ctok,) = self._compare_windows([query], [docs])
+        self.total_prompt_tokens += ptok
+        self.total_completion_tokens += ctok
+        return output
+
+    # ---- the sliding-window walk ------------------------------------------------------------------------------
+    def _walk(self, ranking):
+        """The reference's walk (ref: listwise.py:180-199) as a generator: yields each window, is sent the compare's output, and
+        returns the final ranking.  Windows start at n - window_size and move down by step_size while the start is >= 0."""
+        for _ in range(self.num_repeat):
+            ranking = copy.deepcopy(ranking)
+            end, start = len(ranking), len(ranking) - self.window_size
+            while start >= 0:
+                window = ranking[start:end]
+                output = yield window
+                ranking[start:end] = [window[k] for k in permutation_order(output, len(window))]
+                end -= self.step_size
+                start -= self.step_size
+        for i, doc in enumerate(ranking):
+            doc.score = -i
+        return ranking
+
+    def rerank(self, query: str, ranking: List[SearchResult]) -> List[SearchResult]:
+        self.total_compare = 0
+        self.total_prompt_tokens = 0
+        self.total_completion_tokens = 0
+        walk = self._walk(ranking)
+        try:
+            window = next(walk)
+            while True:
+                window = walk.send(self.compare(query, window))
+        except StopIteration as stop:
+            return stop.value
+
+    def rerank_many(self, items):
+        """Several queries at once: `items` = [(query, ranking), ...] -> (results, counters); results[i] and counters[i] =
+        (total_compare, total_prompt_tokens, total_completion_tokens) are what `rerank(*items[i])` gives.  Each query's windows
+        are a dependency chain; the pending windows of all live chains go to the engine as ONE call per step."""
+        items = list(items)
+        counts = [[0, 0, 0] for _ in items]
+        results = [None] * len(items)
+        walks, pending = {}, {}
+        for q, (_, ranking) in enumerate(items):
+            walks[q] = self._walk(ranking)
+            try:
+                pending[q] = next(walks[q])
+            except StopIteration as stop:
+                results[q] = stop.value
+        while pending:
+            order = sorted(pending)
+            outs, ptok, ctok = self._compare_windows([items[q][0] for q in order], [pending[q] for q in order])
+            nxt = {}
+            for q, out, p, c in zip(order, outs, ptok, ctok):
+                counts[q][0] += 1
+                counts[q][1] += p
+                counts[q][2] += c
+                try:
+                    nxt[q] = walks[q].send(out)
+                except StopIteration as stop:
+                    results[q] = stop.value
+            pending = nxt
+        counters = [tuple(c) for c in counts]
+        if counters:
+            self.total_compare, self.total_prompt_tokens, self.total_completion_tokens = counters[-1]
+        return results, counters
+
+    def truncate(self, text, length):
+        return self.tokenizer.convert_tokens_to_string(self.tokenizer.tokenize(text)[:length])

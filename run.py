@@ -6,8 +6,8 @@
            pointwise --method yes_no --batch_size 32
 
 Same sub-commands (`run` + one of `pointwise` / `setwise`), flags, defaults, TREC run input/output and the four
-averages printed at the end (ref: run.py:198-201).  pairwise / listwise / OpenAI rankers are outside the hot
-path this build accelerates and are rejected with a clear message.  The data back-ends
+averages printed at the end (ref: run.py:198-201).  OpenAI rankers, duoT5 pairwise and listwise on Llama checkpoints are
+outside the hot path this build accelerates and are rejected with a clear message.  The data back-ends
 (ir_datasets / pyserini) are imported lazily; because neither exists offline, two plain-file sources are
 accepted as well:  --query_file (TSV `qid<TAB>text` or JSONL {"qid"|"query_id"|"_id", "text"|"query"}) and
 --doc_file (TSV `docid<TAB>text` or JSONL {"docid"|"doc_id"|"_id", "text"|"contents", ["title"]}).
@@ -253,7 +253,12 @@ def build_ranker(args):
                                  device=args.run.device, cache_dir=args.run.cache_dir, method=args.pairwise.method,
                                  batch_size=args.pairwise.batch_size, k=args.pairwise.k)
     if args.listwise:
-        raise NotImplementedError("listwise rankers are outside the path this engine accelerates (DESIGN.md); use the reference")
+        if args.run.openai_key:
+            raise NotImplementedError("OpenAI rankers are remote HTTP calls, not part of the MI355X hot path; use the reference")
+        from llmrankers.listwise import ListwiseLlmRanker
+        return ListwiseLlmRanker(model_name_or_path=args.run.model_name_or_path, tokenizer_name_or_path=args.run.tokenizer_name_or_path,
+                                 device=args.run.device, cache_dir=args.run.cache_dir, window_size=args.listwise.window_size,
+                                 step_size=args.listwise.step_size, scoring=args.run.scoring, num_repeat=args.listwise.num_repeat)
     raise ValueError("Must specify either --pointwise, --setwise, --pairwise or --listwise.")
 
 
@@ -371,7 +376,8 @@ def main(args):
     per_call = int(getattr(args.run, "queries_per_call", 0) or 0)
     if per_call <= 0:                                                # auto: the engine's grouped throughput by default
         from llmrankers._batching import default_queries_per_call
-        per_call = default_queries_per_call("pointwise" if args.pointwise else ("setwise" if args.setwise else "other"), args.run.hits)
+        kind = "pointwise" if args.pointwise else ("setwise" if args.setwise else ("listwise" if args.listwise else "other"))
+        per_call = default_queries_per_call(kind, args.run.hits)
     if per_call > 1 and not hasattr(ranker, "rerank_many"):
         per_call = 1
     if per_call > 1 and args.run.shuffle_ranking == "random" and getattr(ranker, "num_permutation", 1) > 1:
@@ -510,7 +516,7 @@ def build_parser():
                     help="pointwise under several ranks: 1 (default) shards every query's candidates and gathers the scores over "
                          "RCCL, 0 deals whole queries to the ranks")
     rp.add_argument("--queries_per_call", type=int, default=0,
-                    help="pointwise / setwise: queries handed to the engine together (same rankings and counters as one at a time); "
+                    help="pointwise / setwise / listwise: queries handed to the engine together (same rankings and counters as one at a time); "
                          "0 = auto (llmrankers._batching.default_queries_per_call): pointwise enough queries for >= 1600 passages "
                          f"per call, at most 16 ({_auto_per_call('pointwise', 100)} at hits=100), setwise {_auto_per_call('setwise', 100)} "
                          "heapsorts in lockstep; with --resume the run file is appended once per call, i.e. every that many queries; "

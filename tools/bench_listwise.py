@@ -1,0 +1,130 @@
+#!/usr/bin/env python
+"""Listwise ranking on the engine (flan-t5-large dims, seeded synthetic weights, the test tokenizer): one query of 100 passages
+of ~100 tokens (varied lengths), window 4, step 2, num_repeat 1 - ListwiseLlmRanker.rerank() wall time per query for
+`generation` and `likelihood`; for `generation` the same ranker on rk_t5_generate (KV-cached incremental decoder) against
+rk_t5_greedy (whole-prefix recompute), alternated in one process; lockstep (rerank_many) at 1 / 8 / 32 queries per call; and
+microseconds per decoder step of rk_t5_generate at 1 and 32 sequences ((t(20 new tokens) - t(1)) / 19 over the same prompts).
+One JSON object per line on stdout, and into the file --out names.
+
+--profile-call: only ONE lockstep call of 8 windows (for `rocprofv3 --kernel-trace --hip-runtime-trace --stats -- python
+tools/bench_listwise.py --profile-call`): every decoder step of it should be one hipGraphLaunch."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [os.path.join(REPO, "llm-rankers_amd"), REPO]
+from llmrankers import _synth                      # noqa: E402
+from llmrankers._engine import RkEngine            # noqa: E402
+from llmrankers._runtime import T5Runtime          # noqa: E402
+from llmrankers.listwise import ListwiseLlmRanker  # noqa: E402
+from llmrankers.rankers import SearchResult        # noqa: E402
+
+
+class BenchRuntime(T5Runtime):
+    """T5Runtime on an engine with synthetic weights.  Generated ids beyond the test tokenizer's 202 pieces read as <unk> (the
+    random model rarely says EOS: every compare decodes the full 20 tokens, the worst case).  recompute=True: `generate` runs
+    rk_t5_greedy instead (the A/B)."""
+    recompute = False
+    n_tok = 202
+
+    def generate(self, seqs, dec_prefix, max_new, eos_id=1, pad_id=0):
+        f = T5Runtime.greedy if self.recompute else T5Runtime.generate
+        out = np.asarray(f(self, seqs, dec_prefix, max_new, eos_id, pad_id))
+        return np.where(out >= self.n_tok, 2, out)
+
+
+def make_queries(tok, n_queries, n_passages=100, seed=5):
+    rs = np.random.RandomState(seed)
+    vocab = [w for w in tok.get_vocab() if w.startswith("▁") and w[1:].isalpha() and len(w) > 2]
+    words = [w[1:] for w in vocab]
+    out = []
+    for q in range(n_queries):
+        query = " ".join(rs.choice(words, size=4))
+        docs = [SearchResult(f"q{q}d{i}", None, " ".join(rs.choice(words, size=int(rs.randint(60, 110))))) for i in range(n_passages)]
+        out.append((query, docs))
+    return out
+
+
+def timed(fn):
+    t = time.perf_counter()
+    r = fn()
+    return (time.perf_counter() - t) * 1e3, r
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=None, help="also write the result lines to this file")
+    ap.add_argument("--rounds", type=int, default=2)
+    ap.add_argument("--profile-call", action="store_true")
+    args = ap.parse_args()
+    from transformers import T5Tokenizer
+    tok = T5Tokenizer.from_pretrained(os.path.join(REPO, "tests", "golden", "tok"))
+    dims = _synth.FLAN_T5_LARGE
+    eng = RkEngine(dims, device=0, max_tokens=49152, max_seqs=64, max_dec_len=24)
+    eng.load_state(_synth.synth_tensors(dims, seed=929, threads=16))
+    rt = BenchRuntime.from_engine(eng, dims)
+    rows = []
+
+    def emit(**kw):
+        print(json.dumps(kw), flush=True)
+        rows.append(kw)
+
+    rk = {s: ListwiseLlmRanker.from_runtime(rt, tok, window_size=4, step_size=2, scoring=s, num_repeat=1, max_new=20)
+          for s in ("generation", "likelihood")}
+    if args.profile_call:
+        qs = make_queries(tok, 8)
+        rk["generation"]._compare_windows([q for q, _ in qs], [d[96:] for _, d in qs])       # warm: first sighting, capture
+        eng.sync()
+        ms, _ = timed(lambda: rk["generation"]._compare_windows([q for q, _ in qs], [d[96:] for _, d in qs]))
+        emit(what="profile_call", windows=8, ms=ms)
+    else:
+        sweep(eng, rt, rk, tok, args, emit)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            for r in rows:
+                f.write(json.dumps(r) + "\n")
+
+
+def sweep(eng, rt, rk, tok, args, emit):
+    qs = make_queries(tok, 32)
+    rk["generation"].rerank(*qs[0])                                                         # warm-up (graphs, LDS opt-ins)
+    rk["likelihood"].rerank(*qs[0])
+    # whole query, one at a time: generation on the cached decoder vs on the recompute loop, alternated; likelihood
+    for r in range(args.rounds):
+        for mode in ("generate", "greedy"):
+            rt.recompute = mode == "greedy"
+            ms, _ = timed(lambda: rk["generation"].rerank(*qs[1 + r]))
+            emit(what="query", scoring="generation", engine_call=mode, queries_per_call=1, ms_per_query=ms,
+                 compares=rk["generation"].total_compare, completion_tokens=rk["generation"].total_completion_tokens)
+        rt.recompute = False
+        ms, _ = timed(lambda: rk["likelihood"].rerank(*qs[1 + r]))
+        emit(what="query", scoring="likelihood", queries_per_call=1, ms_per_query=ms, compares=rk["likelihood"].total_compare)
+    # lockstep sweep
+    for n in (8, 32):
+        for mode in ("generate", "greedy"):
+            rt.recompute = mode == "greedy"
+            ms, _ = timed(lambda: rk["generation"].rerank_many(qs[:n]))
+            emit(what="lockstep", scoring="generation", engine_call=mode, queries_per_call=n, ms_per_query=ms / n)
+        rt.recompute = False
+        ms, _ = timed(lambda: rk["likelihood"].rerank_many(qs[:n]))
+        emit(what="lockstep", scoring="likelihood", queries_per_call=n, ms_per_query=ms / n)
+    # microseconds per decoder step of rk_t5_generate: the same prompts with 20 and with 1 new token
+    for n in (1, 32):
+        ids = rk["generation"]._truncated_ids([rk["generation"]._permutation_prompt(q, d[96:]) for q, d in qs[:n]])
+        for max_new in (1, 20):
+            eng.generate(ids, [0], max_new, eos_id=-1)
+        t = {}
+        for max_new in (1, 20):
+            eng.sync()
+            t[max_new] = min(timed(lambda: eng.generate(ids, [0], max_new, eos_id=-1))[0] for _ in range(3))
+        emit(what="decoder_step", sequences=n, ms_1=t[1], ms_20=t[20], us_per_step=(t[20] - t[1]) / 19 * 1e3)
+
+
+if __name__ == "__main__":
+    main()
