@@ -120,7 +120,8 @@ int rk_t5_scores_device_ptr(rk_engine* e, void** out_ptr);
 
 /* ---- decoder-only Llama family: the model call of the reference's setwise ranker for `model_type == 'llama'`
  * (ref: llmrankers/setwise.py:60-69, 159-177): self.llm.generate(input_ids, do_sample=False, max_new_tokens=1) = prefill
- * of the prompt + arg-max of the last position's logits.  hf: models/llama/modeling_llama.py (RMSNorm, RoPE with
+ * of the prompt + arg-max of the last position's logits; and of its listwise ranker (ref: llmrankers/listwise.py:261-271):
+ * self.llm.generate(input_ids) = rk_llama_generate, the prefill once and then one KV-cached row per new token.  hf: models/llama/modeling_llama.py (RMSNorm, RoPE with
  * rope_theta, grouped-query causal attention with head_dim 128, SwiGLU).  Weights go through rk_engine_load_tensor with
  * the HF Llama names ("model.layers.0.self_attn.q_proj.weight", ...) and rk_engine_finalize; rk_engine_destroy frees. */
 typedef struct rk_llama_desc {
@@ -141,6 +142,17 @@ int rk_llama_greedy1(rk_engine* e, const int32_t* tokens, const int32_t* seq_off
 /* the same logits for a few vocabulary rows only -> out_logits[n_seq][n_out] fp32 (label scoring, tests) */
 int rk_llama_last_logits(rk_engine* e, const int32_t* tokens, const int32_t* seq_offsets, int n_seq,
                          const int32_t* out_token_ids, int n_out, float* out_logits);
+/* Greedy continuation of every prompt by up to max_new tokens -> out_tokens[n_seq][max_new].  A row finishes at the
+ * first token that is one of eos_ids[n_eos] (n_eos 0..8), or, when max_total > 0, once prompt_len + new == max_total;
+ * finished rows emit pad_id; the call stops when every row has finished, remaining columns = pad_id;
+ * *out_steps = columns produced.  Prefill once, then ONE new row per sequence and step against a K / V cache (the step is one
+ * replayed graph, the arg-max is fed back on the device).  RK_ERR_CAPACITY when the longest prompt + max_new exceeds max_tokens
+ * or the batch exceeds the prefill's capacities; RK_ERR_INVALID for max_new <= 0, n_eos outside 0..8, an id outside the
+ * vocabulary, a prompt that already reaches max_total; RK_ERR_STATE on a T5 engine.
+ * replaces: self.llm.generate(input_ids)  (ref: llmrankers/listwise.py:268) */
+int rk_llama_generate(rk_engine* e, const int32_t* tokens, const int32_t* seq_offsets, int n_seq,
+                      int max_new, int max_total, const int32_t* eos_ids, int n_eos, int pad_id,
+                      int32_t* out_tokens, int32_t* out_steps);
 
 /* ---- score collection across the GPUs of one node: one process per GPU, one engine per process.
  * The reference has no counterpart (its multi-GPU mode is accelerate's layer placement, ref: pointwise.py:21); this
@@ -206,7 +218,8 @@ int rk_debug_gemm(rk_engine* e, const uint16_t* A, const uint16_t* W, float* C, 
  * 2 GEGLU, 3 ReLU, 4 store f32), random operands, `iters` back-to-back launches timed with HIP events */
 int rk_debug_gemm_bench(rk_engine* e, int M, int N, int K, int epi, int iters, float* out_ms);
 /* debug: copy an internal activation buffer to the host as fp32. name: "enc_hidden" [T,d], "enc_out" [T,d],
- * "qkv" [T,3I], "ctx" [T,I], "dec_hidden" [B*Ld,d]. Returns number of floats written or a negative status. */
+ * "qkv" [T,3I], "ctx" [T,I], "dec_hidden" [B*Ld,d], "llama_last" [n_seq,hidden] (the final-normed last rows of the most recent
+ * Llama call: after rk_llama_generate, the rows the last step's head read). Returns number of floats written or a negative status. */
 int64_t rk_debug_read(rk_engine* e, const char* name, float* out, int64_t max_floats);
 
 #ifdef __cplusplus

@@ -464,3 +464,191 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_causal128_dma_kernel(AttnCaus
     }
   }
 }
+
+// =========================== incremental decoding: one new row per sequence against a K / V cache ===========================
+// rk_llama_generate keeps every layer's rotated keys and its values: per layer K [n_seq][n_kv][P][128] then V, fp16, the keys
+// of one kv head contiguous.  kv_cache_fill128_kernel copies the prompt's rows out of the prefill's fused QKV buffer (after
+// rope128_kernel); grid = (longest prompt, n_seq), a thread moves one 16-byte piece of K and of V.
+__global__ __launch_bounds__(256) void kv_cache_fill128_kernel(const half_t* __restrict__ qkv, const int* __restrict__ seq_off,
+                                                               half_t* __restrict__ kc, half_t* __restrict__ vc, int ld,
+                                                               int n_heads, int n_kv, int P) {
+  const int b = blockIdx.y, t = blockIdx.x;
+  const int tok0 = seq_off[b];
+  if (t >= seq_off[b + 1] - tok0 || t >= P) return;
+  const half_t* row = qkv + (size_t)(tok0 + t) * ld + (size_t)n_heads * 128;
+  for (int c = threadIdx.x; c < n_kv * 16; c += 256) {
+    const int h = c >> 4, piece = (c & 15) * 8;
+    const size_t dst = (((size_t)b * n_kv + h) * P + t) * 128 + piece;
+    *(half8*)(kc + dst) = *(const half8*)(row + h * 128 + piece);
+    *(half8*)(vc + dst) = *(const half8*)(row + (size_t)(n_kv + h) * 128 + piece);
+  }
+}
+
+struct AttnDecCached128Args {
+  const half_t* qkv;     // [n_seq, ld]: the step's fused q | k | v rows, NOT yet rotated
+  half_t* kc;            // this layer's key cache [n_seq][n_kv][P][128]; the new key is written at the row's position
+  half_t* vc;            // value cache, same shape
+  const int* pos;        // [n_seq] position of the new row (device: it advances inside the replayed step graph)
+  const float* cos_t;    // rotary tables [max_pos, 64]
+  const float* sin_t;
+  float* part;           // [n_seq][n_heads][nch][LDC_PSTR]: per key chunk 128 accumulators, running maximum, sum
+  half_t* ctx;           // [n_seq, n_heads * 128]
+  int ld, n_heads, n_kv, P, nch;
+  float scale_log2e;     // head_dim**-0.5 * log2(e)
+};
+#define LDC_CHUNK 128    // keys per workgroup: FIXED, so the chunk boundaries of a sequence follow from its own position alone
+#define LDC_PSTR 132     // floats per partial: 128 accumulators, maximum, sum, 2 unused (16-byte rows)
+
+// Single-token attention over the cache (hf: modeling_llama.py:130-214 at one query position: scaling head_dim**-0.5, fp32
+// softmax, repeat_kv), d = 128.  grid = (key chunks of the longest cache, n_heads / R, n_seq), 256 threads.  A workgroup takes
+// ONE chunk of LDC_CHUNK keys of one kv head and R query heads that share it: with R = n_heads / n_kv_heads (Llama-3-8B: 4)
+// every K / V byte is read once per kv head.  K / V go straight to registers (no LDS staging: each byte is used once): a lane
+// holds 8 of a key's 128 dims, 16 lanes a key, a wave 4 keys per load and 32 keys in all, every load issued before the first
+// use.  The new row is rotated here (rope128_kernel's arithmetic on the same table entries), its key and value are used from
+// registers and written to the cache by the workgroup that owns the position's chunk.  Each workgroup leaves one (maximum, sum,
+// accumulator) partial per head - its four waves merged in wave order - and attn_dec_combine128_kernel merges a row's chunks
+// in key order: nobody waits on another workgroup, and a row's context depends on its own position only, never on the batch.
+template <int R>
+__global__ __launch_bounds__(256) void attn_dec_cached128_kernel(AttnDecCached128Args p) {
+  __shared__ float s_m[4][R], s_l[4][R];
+  __shared__ __attribute__((aligned(16))) float s_acc[4][R][128];
+  const int ch = blockIdx.x, h0 = blockIdx.y * R, b = blockIdx.z;
+  int pos = p.pos[b];
+  pos = pos < 0 ? 0 : (pos < p.P - 1 ? pos : p.P - 1);   // (the host keeps it inside the cache; the clamp keeps a bad word from faulting)
+  const int key0 = ch * LDC_CHUNK;
+  if (key0 > pos) return;                                 // uniform: this chunk lies beyond the row's keys
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, kg = lane >> 4, c = lane & 15;
+  const int G = p.n_heads / p.n_kv, kvh = h0 / G;
+  const half_t* row = p.qkv + (size_t)b * p.ld;
+  const int i0 = (c & 7) * 8;
+  const bool hi = c >= 8;                                 // this lane's dims are in the second half of the head
+  float co[8], si[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) { co[j] = p.cos_t[(size_t)pos * 64 + i0 + j]; si[j] = p.sin_t[(size_t)pos * 64 + i0 + j]; }
+  auto rotated = [&](const half_t* head) {               // this lane's 8 dims of the rotated head, rounded as rope128_kernel does
+    const half8 a = *(const half8*)(head + i0), bb = *(const half8*)(head + 64 + i0);
+    half8 o;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const float x1 = (float)a[j], x2 = (float)bb[j];
+      const half_t oa = f2h_sat(x1 * co[j] - x2 * si[j]);
+      const half_t ob = f2h_sat(x2 * co[j] + x1 * si[j]);
+      o[j] = hi ? ob : oa;
+    }
+    return o;
+  };
+  const half8 knew = rotated(row + (size_t)(p.n_heads + kvh) * 128);
+  const half8 vnew = *(const half8*)(row + (size_t)(p.n_heads + p.n_kv + kvh) * 128 + c * 8);
+  half_t* kbase = p.kc + ((size_t)b * p.n_kv + kvh) * p.P * 128 + c * 8;
+  half_t* vbase = p.vc + ((size_t)b * p.n_kv + kvh) * p.P * 128 + c * 8;
+  if (pos - key0 < LDC_CHUNK && h0 % G == 0 && wave == 0 && kg == 0) {   // the position's chunk, once per kv head
+    *(half8*)(kbase + (size_t)pos * 128) = knew;
+    *(half8*)(vbase + (size_t)pos * 128) = vnew;
+  }
+  const int wkey0 = key0 + wave * 32;
+  float m_w[R], l_w[R], acc[R][8];
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    m_w[r] = -1e30f; l_w[r] = 0.f;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc[r][j] = 0.f;
+  }
+  if (wkey0 <= pos) {                                     // wave-uniform
+    half8 kf[8], vf[8];
+    const int last_old = pos > 0 ? pos - 1 : 0;           // keys before the new one come from the cache
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const int key = wkey0 + 4 * i + kg;
+      const int idx = key < last_old ? key : last_old;
+      kf[i] = *(const half8*)(kbase + (size_t)idx * 128);
+      vf[i] = *(const half8*)(vbase + (size_t)idx * 128);
+    }
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const bool is_new = wkey0 + 4 * i + kg >= pos;
+      kf[i] = is_new ? knew : kf[i];
+      vf[i] = is_new ? vnew : vf[i];
+    }
+    float s[R][8];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      const half8 q = rotated(row + (size_t)(h0 + r) * 128);
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        float d = 0.f;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) d = __builtin_fmaf((float)q[j], (float)kf[i][j], d);
+        d = row16_sum_f(d) * p.scale_log2e;
+        s[r][i] = wkey0 + 4 * i + kg <= pos ? d : -1e30f;
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      float mx = s[r][0];
+#pragma unroll
+      for (int i = 1; i < 8; ++i) mx = fmaxf(mx, s[r][i]);
+      mx = fmaxf(mx, __shfl_xor(mx, 16));
+      mx = fmaxf(mx, __shfl_xor(mx, 32));
+      float sum = 0.f;
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        const float pr = __builtin_amdgcn_exp2f(s[r][i] - mx);   // masked keys: exp2(-1e30) = 0
+        sum += pr;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) acc[r][j] = __builtin_fmaf(pr, (float)vf[i][j], acc[r][j]);
+      }
+      sum += __shfl_xor(sum, 16);
+      sum += __shfl_xor(sum, 32);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        acc[r][j] += __shfl_xor(acc[r][j], 16);
+        acc[r][j] += __shfl_xor(acc[r][j], 32);
+      }
+      m_w[r] = mx; l_w[r] = sum;
+    }
+  }
+  if (kg == 0) {
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      *(f32x4*)&s_acc[wave][r][c * 8] = f32x4{acc[r][0], acc[r][1], acc[r][2], acc[r][3]};
+      *(f32x4*)&s_acc[wave][r][c * 8 + 4] = f32x4{acc[r][4], acc[r][5], acc[r][6], acc[r][7]};
+      if (c == 0) { s_m[wave][r] = m_w[r]; s_l[wave][r] = l_w[r]; }
+    }
+  }
+  __syncthreads();
+  if (tid < 128) {                                        // the four waves' partials, merged in wave order
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      const float M = fmaxf(fmaxf(s_m[0][r], s_m[1][r]), fmaxf(s_m[2][r], s_m[3][r]));
+      float L = 0.f, A = 0.f;
+#pragma unroll
+      for (int w = 0; w < 4; ++w) {
+        const float f = __builtin_amdgcn_exp2f(s_m[w][r] - M);
+        L = __builtin_fmaf(s_l[w][r], f, L);
+        A = __builtin_fmaf(s_acc[w][r][tid], f, A);
+      }
+      float* dst = p.part + (((size_t)b * p.n_heads + h0 + r) * p.nch + ch) * LDC_PSTR;
+      dst[tid] = A;
+      if (tid == 0) { dst[128] = M; dst[129] = L; }
+    }
+  }
+}
+
+// Merges the chunk partials of one (sequence, head) in key order and writes the fp16 context.  grid = (n_heads, n_seq), 128
+// threads = the head's 128 dims.
+__global__ __launch_bounds__(128) void attn_dec_combine128_kernel(AttnDecCached128Args p) {
+  const int h = blockIdx.x, b = blockIdx.y, d = threadIdx.x;
+  int pos = p.pos[b];
+  pos = pos < 0 ? 0 : (pos < p.P - 1 ? pos : p.P - 1);
+  const int n = pos / LDC_CHUNK + 1;
+  const float* src = p.part + ((size_t)b * p.n_heads + h) * p.nch * LDC_PSTR;
+  float M = -1e30f;
+  for (int k = 0; k < n; ++k) M = fmaxf(M, src[(size_t)k * LDC_PSTR + 128]);
+  float L = 0.f, A = 0.f;
+  for (int k = 0; k < n; ++k) {
+    const float f = __builtin_amdgcn_exp2f(src[(size_t)k * LDC_PSTR + 128] - M);
+    L = __builtin_fmaf(src[(size_t)k * LDC_PSTR + 129], f, L);
+    A = __builtin_fmaf(src[(size_t)k * LDC_PSTR + d], f, A);
+  }
+  p.ctx[(size_t)b * p.n_heads * 128 + h * 128 + d] = f2h_sat(A / L);   // a row always sees its own key: L > 0
+}

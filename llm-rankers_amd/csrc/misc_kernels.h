@@ -168,6 +168,39 @@ __global__ __launch_bounds__(256) void greedy_advance_kernel(const int* __restri
   }
 }
 
+// Token feedback of rk_llama_generate, the sibling of greedy_advance_kernel for a decoder-only model: a SET of EOS ids and a limit
+// on a row's total length.  st = {n, finished step, pad, n_eos, max_new, max_total, P, 0, eos[8]}: column n of the output gets
+// the row's arg-max, or pad once the row has finished (hf: generation/utils.py greedy); a row finishes at one of the EOS ids or,
+// with max_total > 0, once prompt + new tokens == max_total (hf: MaxLengthCriteria).  The token is the row's next input at
+// position len[b] + n, held inside the cache.  st[1] (0 until then) becomes n + 1 at the column where the last row finished, or
+// max_new.  A step enqueued after that writes pads over pads (every row has finished) or nothing (n == max_new).  One workgroup.
+__global__ __launch_bounds__(256) void llama_advance_kernel(const int* __restrict__ argmax, int* st, const int* __restrict__ len,
+                                                            int* done, int* pos, int* out, int* next_ids, int n_seq) {
+  __shared__ int s_all;
+  const int tid = threadIdx.x, n = st[0], pad = st[2], n_eos = st[3], max_new = st[4], max_total = st[5], P = st[6];
+  if (n >= max_new) return;
+  if (tid == 0) s_all = 1;
+  __syncthreads();
+  for (int b = tid; b < n_seq; b += 256) {
+    const int tok = done[b] ? pad : argmax[b];
+    out[(size_t)b * max_new + n] = tok;
+    if (!done[b]) {
+      bool fin = max_total > 0 && len[b] + n + 1 >= max_total;
+      for (int k = 0; k < n_eos; ++k) fin = fin || tok == st[8 + k];
+      if (fin) done[b] = 1;
+    }
+    next_ids[b] = tok;
+    const int p = len[b] + n;
+    pos[b] = p < P - 1 ? p : P - 1;
+    if (!done[b]) s_all = 0;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    if (st[1] == 0 && (s_all || n == max_new - 1)) st[1] = n + 1;
+    st[0] = n + 1;
+  }
+}
+
 // QLM score (ref: llmrankers/pointwise.py:77-79) from the fused head (gemm.h: EPI_LSE_F32): stats [rows, nblk] = (block max, sum exp(x - block max)), xlab [rows] =
 // the label's logit.  out[b] = -sum_t ( logsumexp_t - xlab[b, t] ), logsumexp_t = M + log(sum_blocks s * exp(m - M)).
 // One block per sequence; the blocks of a position are merged in a fixed order, the positions summed in order (deterministic).

@@ -139,6 +139,11 @@ struct rk_engine {
   int family = 0; rk_llama_desc ld{};
   float rope_factor = 0.f, rope_low = 1.f, rope_high = 4.f; int rope_orig = 0;   // rope type llama3 when rope_factor > 0
   std::vector<LlamaLayerW> ll; float *l_final_ln = nullptr, *rope_cos = nullptr, *rope_sin = nullptr; int* d_pos = nullptr;
+  // rk_llama_generate: K / V cache [n_layers][2][n_seq][n_kv][P][128], the attention partials and the call's int block (grown
+  // between calls; lkv_gen counts the moves and is part of the step graph's key), and the step's activation rows (max_seqs each)
+  half_t* lkv = nullptr; size_t lkv_cap = 0; float* lpart = nullptr; size_t lpart_cap = 0; int* lints = nullptr; size_t lints_cap = 0;
+  int lkv_gen = 0;
+  struct LlamaStep { float* hidden = nullptr; half_t *xraw = nullptr, *qkv = nullptr, *ctx = nullptr, *ffh = nullptr; float *ssq = nullptr, *rowscale = nullptr; } lg;
   // decoder chains as HIP graphs: key = everything the launch parameters of a chain depend on
   struct GraphEntry { int seen = 0; bool failed = false; hipGraphExec_t exec = nullptr; };
   std::map<std::vector<int>, GraphEntry> graphs; int opt_epoch = 0;
@@ -813,6 +818,31 @@ void launch_llama_attn(rk_engine* e, hipStream_t st, const Slot& sl, const Causa
   else launch_lds<attn_causal128_dma_kernel<4>>(st, p.grid, p.block, p.lds, p.lds_opt_in, a);
 }
 
+// Single-token attention of one rk_llama_generate step over the K / V cache of P positions per sequence: the chunk kernel over
+// (key chunks of P, groups of R query heads, rows), then the merge per (head, row).  R = the largest of 8 / 4 / 2 / 1 that divides
+// the query heads per kv head (Llama-3-8B: 4): a model constant, so a row's bits never depend on the call.
+struct LlamaDecAttnPlan { int R = 1, nch = 1; dim3 grid, cgrid; };
+LlamaDecAttnPlan plan_llama_dec_attn(const rk_engine* e, int rows, int P, int n_heads, int n_kv) {
+  (void)e;                                                   // (no option and no CU count enters: fixed chunk length, model-constant R)
+  LlamaDecAttnPlan p;
+  const int G = n_heads / n_kv;
+  p.R = G % 8 == 0 ? 8 : (G % 4 == 0 ? 4 : (G % 2 == 0 ? 2 : 1));
+  p.nch = (P + LDC_CHUNK - 1) / LDC_CHUNK;
+  p.grid = dim3(p.nch, n_heads / p.R, rows);
+  p.cgrid = dim3(n_heads, rows);
+  return p;
+}
+
+void launch_llama_dec_attn(rk_engine* e, hipStream_t st, const LlamaDecAttnPlan& p, AttnDecCached128Args a, int rows) {
+  a.nch = p.nch;
+  Bracket br(e, st, PC_DEC_ATTN, 4.0 * rows * (double)a.P * a.n_heads * 128, 2.0 * rows * (double)a.P * a.n_kv * 128 * 2.0);
+  if (p.R == 8) hipLaunchKernelGGL(attn_dec_cached128_kernel<8>, p.grid, dim3(256), 0, st, a);
+  else if (p.R == 4) hipLaunchKernelGGL(attn_dec_cached128_kernel<4>, p.grid, dim3(256), 0, st, a);
+  else if (p.R == 2) hipLaunchKernelGGL(attn_dec_cached128_kernel<2>, p.grid, dim3(256), 0, st, a);
+  else hipLaunchKernelGGL(attn_dec_cached128_kernel<1>, p.grid, dim3(256), 0, st, a);
+  hipLaunchKernelGGL(attn_dec_combine128_kernel, p.cgrid, dim3(128), 0, st, a);
+}
+
 // hf: modeling_t5.py:663-750 (T5Stack.forward, encoder) over the slot's staged ragged batch, then the stacked
 // cross-attention K/V projections of all decoder layers (:325-326 with key_value_states = encoder output).
 int run_encoder(rk_engine* e, Slot& sl, bool need_cross_kv) {
@@ -1353,6 +1383,9 @@ void rk_engine_destroy(rk_engine* e) {
   if (e->amax_val) hipFree(e->amax_val);
   if (e->amax_idx) hipFree(e->amax_idx);
   if (e->kv_cache) hipFree(e->kv_cache);
+  if (e->lkv) hipFree(e->lkv);
+  if (e->lpart) hipFree(e->lpart);
+  if (e->lints) hipFree(e->lints);
   if (e->gen_buf) hipFree(e->gen_buf);
   if (e->gen_pin) hipHostFree(e->gen_pin);
   for (hipEvent_t ev : e->ev_gen) if (ev) hipEventDestroy(ev);
@@ -2084,7 +2117,9 @@ static int llama_finalize(rk_engine* e) {
 }
 
 // prefill of the ragged batch; leaves the final-normed LAST hidden state of every sequence in sl.dlast [n_seq, hidden]
-static int llama_prefill(rk_engine* e, const int32_t* tokens, const int32_t* off, int n_seq) {
+// keep (rk_llama_generate only): every layer's rotated K and its V are also copied to the cache, P positions per sequence
+struct LlamaKeep { half_t* kv; int P; };
+static int llama_prefill(rk_engine* e, const int32_t* tokens, const int32_t* off, int n_seq, const LlamaKeep* keep = nullptr) {
   if (!e || e->family != 1) return fail(e, RK_ERR_STATE, "not a Llama engine");
   int rc = set_device(e);
   if (rc) return rc;
@@ -2114,6 +2149,13 @@ static int llama_prefill(rk_engine* e, const int32_t* tokens, const int32_t* off
     {
       Bracket br(e, st, PC_OTHER, 0, (double)T * (Q + KV) * 4.0);
       hipLaunchKernelGGL(rope128_kernel, dim3(T), dim3(256), 0, st, sl.qkv, e->d_pos, e->rope_cos, e->rope_sin, ldq, l.n_heads + l.n_kv_heads);
+    }
+    if (keep) {
+      const size_t half_layer = (size_t)n_seq * l.n_kv_heads * keep->P * 128;
+      half_t* kc = keep->kv + (size_t)i * 2 * half_layer;
+      Bracket br(e, st, PC_OTHER, 0, (double)T * KV * 8.0);
+      hipLaunchKernelGGL(kv_cache_fill128_kernel, dim3(sl.maxL, n_seq), dim3(256), 0, st, sl.qkv, sl.d_seq_off, kc, kc + half_layer, ldq,
+                         l.n_heads, l.n_kv_heads, keep->P);
     }
     launch_llama_attn(e, st, sl, ap);
     RC(gemm(e, st, Gemm(PC_ENC_GEMM_O, EPI_RESID_F32, sl.ctx, Q, w.o, Q, sl.hidden, dm, T, dm, Q).with(prod), &nb));
@@ -2171,6 +2213,155 @@ int rk_llama_greedy1(rk_engine* e, const int32_t* tokens, const int32_t* seq_off
   HIPCHK(e, hipStreamSynchronize(st));
   HIPCHK(e, hipGetLastError());
   for (int b = 0; b < n_seq; ++b) out_tokens[b] = amax[b];
+  return RK_OK;
+}
+
+// rk_llama_generate's device memory, grown between calls only (never inside a capture; a move changes lkv_gen, which is part of
+// the step graph's key): the K / V cache, the attention partials, the call's int block; once: the step's activation rows, the
+// pinned read-back words and their events.
+static int ensure_llama_gen(rk_engine* e, int n_seq, int P, int max_new) {
+  const rk_llama_desc& l = e->ld;
+  const size_t S = (size_t)l.max_seqs, dm = l.hidden, Q = (size_t)l.n_heads * 128, KV = (size_t)l.n_kv_heads * 128, F = l.intermediate;
+  const size_t kv = (size_t)l.n_layers * 2 * n_seq * KV * P;
+  const size_t part = (size_t)n_seq * l.n_heads * ((P + LDC_CHUNK - 1) / LDC_CHUNK) * LDC_PSTR;
+  const size_t ints = 16 + 4 * S + (size_t)n_seq * max_new;
+  if (kv > e->lkv_cap || part > e->lpart_cap || ints > e->lints_cap) {
+    int rc = sync_all(e);
+    if (rc) return rc;
+    if (kv > e->lkv_cap) {
+      if (e->lkv) HIPCHK(e, hipFree(e->lkv));
+      e->lkv = nullptr; e->lkv_cap = 0;
+      HIPCHK(e, hipMalloc((void**)&e->lkv, kv * sizeof(half_t)));
+      e->lkv_cap = kv;
+    }
+    if (part > e->lpart_cap) {
+      if (e->lpart) HIPCHK(e, hipFree(e->lpart));
+      e->lpart = nullptr; e->lpart_cap = 0;
+      HIPCHK(e, hipMalloc((void**)&e->lpart, part * sizeof(float)));
+      e->lpart_cap = part;
+    }
+    if (ints > e->lints_cap) {
+      if (e->lints) HIPCHK(e, hipFree(e->lints));
+      e->lints = nullptr; e->lints_cap = 0;
+      HIPCHK(e, hipMalloc((void**)&e->lints, ints * sizeof(int)));
+      e->lints_cap = ints;
+    }
+    ++e->lkv_gen;
+  }
+  if (!e->lg.hidden) {
+    int rc = RK_OK;
+    RC(dalloc(e, &e->lg.hidden, S * dm)); RC(dalloc(e, &e->lg.xraw, S * dm)); RC(dalloc(e, &e->lg.qkv, S * (Q + 2 * KV)));
+    RC(dalloc(e, &e->lg.ctx, S * Q)); RC(dalloc(e, &e->lg.ffh, S * F)); RC(dalloc(e, &e->lg.ssq, S * ((dm + 31) / 32)));
+    RC(dalloc(e, &e->lg.rowscale, S));
+  }
+  if (!e->gen_pin) {
+    HIPCHK(e, hipHostMalloc((void**)&e->gen_pin, 16 * sizeof(int), hipHostMallocDefault));
+    for (hipEvent_t& ev : e->ev_gen) HIPCHK(e, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+  }
+  return RK_OK;
+}
+
+// Greedy continuation with a K / V cache (hf: generation/utils.py greedy loop over LlamaForCausalLM with use_cache): the prefill
+// once, keeping every layer's rotated K and its V; column 0 = the prefill's arg-max (rk_llama_greedy1's token); then ONE new row
+// per sequence and step: embedding of the fed-back token, per layer QKV (folded norm) -> attn_dec_cached128_kernel -> o + residual
+// -> gate|up + SwiGLU -> down + residual, final norm, arg-max head, llama_advance_kernel.  Every projection runs on the
+// weight-streaming family (the caller's regime, never the row count: a row's tokens do not depend on what shares the call).  The
+// step is one graph per (rows, P, cache generation), replayed; position, finished rows and next ids live on the device; the host
+// reads one word per step and keeps one step queued ahead (rk_t5_generate's loop).
+int rk_llama_generate(rk_engine* e, const int32_t* tokens, const int32_t* seq_offsets, int n_seq, int max_new, int max_total,
+                      const int32_t* eos_ids, int n_eos, int pad_id, int32_t* out_tokens, int32_t* out_steps) {
+  if (!e) return RK_ERR_INVALID;
+  if (e->family != 1) return fail(e, RK_ERR_STATE, "rk_llama_generate called on a T5 engine (use rk_t5_generate)");
+  if (!out_tokens) return fail(e, RK_ERR_INVALID, "null output");
+  if (max_new <= 0) return fail(e, RK_ERR_INVALID, "max_new must be positive (got %d)", max_new);
+  if (n_eos < 0 || n_eos > 8 || (n_eos > 0 && !eos_ids)) return fail(e, RK_ERR_INVALID, "n_eos must be in 0..8 (got %d)", n_eos);
+  int rc;
+  if ((rc = check_ids(e, eos_ids, n_eos, "eos")) || (rc = check_ids(e, &pad_id, 1, "pad"))) return rc;
+  if ((rc = set_device(e))) return rc;
+  Slot& sl = e->slots[0];
+  if ((rc = check_batch(e, sl, tokens, seq_offsets, n_seq))) return rc;
+  const rk_llama_desc& l = e->ld;
+  if ((long)sl.maxL + max_new > l.max_tokens)
+    return fail(e, RK_ERR_CAPACITY, "longest prompt %d + max_new %d exceeds max_tokens %d (the rotary tables end there)", sl.maxL, max_new, l.max_tokens);
+  for (int b = 0; b < n_seq; ++b)
+    if (max_total > 0 && seq_offsets[b + 1] - seq_offsets[b] >= max_total)
+      return fail(e, RK_ERR_INVALID, "prompt %d has %d tokens: it already reaches max_total %d", b, seq_offsets[b + 1] - seq_offsets[b], max_total);
+  const int P = sl.maxL + max_new, S = l.max_seqs;
+  if ((rc = ensure_amax(e, (size_t)n_seq, l.vocab))) return rc;
+  if ((rc = ensure_llama_gen(e, n_seq, P, max_new))) return rc;
+  hipStream_t st = sl.se;
+  // the call's int block: {n, finished step, pad, n_eos, max_new, max_total, P, 0, eos[8]} | len[S] | done[S] | pos[S] | next[S] | out[n][max_new]
+  int* g = e->lints;
+  int *d_len = g + 16, *d_done = d_len + S, *d_pos = d_done + S, *d_next = d_pos + S, *d_out = d_next + S;
+  std::vector<int> init(16 + 4 * (size_t)S + (size_t)n_seq * max_new, 0);
+  init[2] = pad_id; init[3] = n_eos; init[4] = max_new; init[5] = max_total; init[6] = P;
+  for (int k = 0; k < n_eos; ++k) init[8 + k] = eos_ids[k];
+  for (int b = 0; b < n_seq; ++b) init[16 + b] = seq_offsets[b + 1] - seq_offsets[b];
+  for (size_t k = 0; k < (size_t)n_seq * max_new; ++k) init[16 + 4 * (size_t)S + k] = pad_id;
+  HIPCHK(e, hipStreamSynchronize(st));
+  HIPCHK(e, hipMemcpy(g, init.data(), init.size() * sizeof(int), hipMemcpyHostToDevice));
+  const LlamaKeep keep{e->lkv, P};
+  if ((rc = llama_prefill(e, tokens, seq_offsets, n_seq, &keep))) return rc;
+  auto head_and_advance = [&]() -> int {
+    int r = head_argmax(e, st, sl.dlast, n_seq, l.hidden, l.vocab, sl.d_argmax);
+    if (r) return r;
+    Bracket br(e, st, PC_OTHER, 0, 0);
+    hipLaunchKernelGGL(llama_advance_kernel, dim3(1), dim3(256), 0, st, sl.d_argmax, g, d_len, d_done, d_pos, d_out, d_next, n_seq);
+    return RK_OK;
+  };
+  if ((rc = head_and_advance())) return rc;
+  const int dm = l.hidden, Q = l.n_heads * 128, KV = l.n_kv_heads * 128, F = l.intermediate, ldq = Q + 2 * KV;
+  const LlamaDecAttnPlan ap = plan_llama_dec_attn(e, n_seq, P, l.n_heads, l.n_kv_heads);
+  const size_t half_layer = (size_t)n_seq * KV * P;
+  const float scale_log2e = (1.0f / std::sqrt(128.0f)) * 1.4426950408889634f;
+  const auto& lg = e->lg;
+  auto step = [&]() -> int {
+    int r = RK_OK, nb = 0;
+    GemmFold prod;
+    prod.xraw = lg.xraw; prod.ssq = lg.ssq;
+    // the GEMM behind a norm: row factors from the embedding (nb == 0), from the producer's block sums in its own epilogue, or -
+    // more block sums than that path stages (hidden > 2 048) - from rowscale_kernel in front of it.  A function of the model only.
+    auto normed = [&]() {
+      GemmFold f;
+      if (!nb) f.rowscale = lg.rowscale;
+      else if (nb <= 64) { f.ssq_in = lg.ssq; f.nb_in = nb; }
+      else { rowscale(e, st, lg.ssq, lg.rowscale, n_seq, nb); f.rowscale = lg.rowscale; }
+      return f;
+    };
+    embed(e, st, d_next, lg.hidden, n_seq, lg.xraw, lg.rowscale);
+    for (int i = 0; i < l.n_layers; ++i) {
+      const LlamaLayerW& w = e->ll[i];
+      if ((r = gemm(e, st, Gemm(PC_DEC_GEMM, EPI_STORE_F16, lg.xraw, dm, w.qkv_f, dm, lg.qkv, ldq, n_seq, ldq, dm).on(GEMM_STREAM).with(normed())))) return r;
+      half_t* kc = e->lkv + (size_t)i * 2 * half_layer;
+      launch_llama_dec_attn(e, st, ap, AttnDecCached128Args{lg.qkv, kc, kc + half_layer, d_pos, e->rope_cos, e->rope_sin, e->lpart, lg.ctx,
+                                                            ldq, l.n_heads, l.n_kv_heads, P, ap.nch, scale_log2e}, n_seq);
+      if ((r = gemm(e, st, Gemm(PC_DEC_GEMM, EPI_RESID_F32, lg.ctx, Q, w.o, Q, lg.hidden, dm, n_seq, dm, Q).on(GEMM_STREAM).with(prod), &nb))) return r;
+      if ((r = gemm(e, st, Gemm(PC_DEC_GEMM, EPI_SWIGLU_F16, lg.xraw, dm, w.gu_f, dm, lg.ffh, F, n_seq, 2 * F, dm).on(GEMM_STREAM).with(normed())))) return r;
+      const bool lastl = i + 1 == l.n_layers;
+      if ((r = gemm(e, st, Gemm(PC_DEC_GEMM, EPI_RESID_F32, lg.ffh, F, w.down, F, lg.hidden, dm, n_seq, dm, F).on(GEMM_STREAM).with(lastl ? GemmFold() : prod), &nb))) return r;
+    }
+    rmsnorm(e, st, lg.hidden, e->l_final_ln, sl.dlast, nullptr, n_seq);
+    return head_and_advance();
+  };
+  const std::vector<int> key{4, 0, n_seq, P, (int)e->amax_rows, e->lkv_gen};
+  int* pin = e->gen_pin;
+  HIPCHK(e, hipMemcpyAsync(pin, g + 1, sizeof(int), hipMemcpyDeviceToHost, st));       // column 0's finished-step word
+  HIPCHK(e, hipEventRecord(e->ev_gen[0], st));
+  bool stop = false;
+  for (int s = 1; s < max_new && !stop; ++s) {                                         // step s produces column s
+    if ((rc = run_graphed(e, st, key, step))) return rc;
+    HIPCHK(e, hipMemcpyAsync(pin + (s & 1), g + 1, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(e, hipEventRecord(e->ev_gen[s & 1], st));
+    HIPCHK(e, hipEventSynchronize(e->ev_gen[(s - 1) & 1]));                            // the previous column's word, while this step runs
+    stop = pin[(s - 1) & 1] != 0;
+  }
+  std::vector<int> res((size_t)n_seq * max_new + 1);
+  HIPCHK(e, hipMemcpyAsync(res.data(), d_out, (size_t)n_seq * max_new * sizeof(int), hipMemcpyDeviceToHost, st));
+  HIPCHK(e, hipMemcpyAsync(res.data() + (size_t)n_seq * max_new, g + 1, sizeof(int), hipMemcpyDeviceToHost, st));
+  HIPCHK(e, hipStreamSynchronize(st));
+  HIPCHK(e, hipGetLastError());
+  memcpy(out_tokens, res.data(), (size_t)n_seq * max_new * sizeof(int));
+  if (out_steps) *out_steps = res[(size_t)n_seq * max_new];
   return RK_OK;
 }
 
@@ -2572,6 +2763,7 @@ int64_t rk_debug_read(rk_engine* e, const char* name, float* out, int64_t max_fl
   else if (n == "qkv") { src = sl.qkv; cnt = (int64_t)sl.T * 3 * I; }
   else if (n == "ctx") { src = sl.ctx; cnt = (int64_t)sl.T * I; }
   else if (n == "xn") { src = sl.xn; cnt = (int64_t)sl.T * dm; }
+  else if (n == "llama_last") { src = sl.dlast; cnt = (int64_t)sl.n_seq * dm; }   // final-normed last rows of the most recent Llama call
   else if (n == "dec_hidden") { src = sl.dhidden; cnt = (int64_t)sl.n_seq * e->d.max_dec_len * dm; is_half = false; }
   else return fail(e, RK_ERR_INVALID, "unknown buffer %s", name);
   cnt = std::min(cnt, max_floats);

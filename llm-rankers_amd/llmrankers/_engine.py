@@ -63,6 +63,7 @@ ABI = {
     "rk_llama_set_rope_scaling": (C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_int]),
     "rk_llama_greedy1": (C.c_int, [C.c_void_p, _i32p, _i32p, C.c_int, _i32p]),
     "rk_llama_last_logits": (C.c_int, [C.c_void_p, _i32p, _i32p, C.c_int, _i32p, C.c_int, _f32p]),
+    "rk_llama_generate": (C.c_int, [C.c_void_p, _i32p, _i32p, C.c_int, C.c_int, C.c_int, _i32p, C.c_int, C.c_int, _i32p, _i32p]),
     "rk_comm_unique_id": (C.c_int, [_P(C.c_uint8), C.c_int]),
     "rk_comm_init": (C.c_int, [C.c_void_p, _P(C.c_uint8), C.c_int, C.c_int, C.c_int, C.c_int]),
     "rk_comm_world": (C.c_int, [C.c_void_p, _i32p, _i32p]),
@@ -423,6 +424,20 @@ class RkLlamaEngine(RkEngine):
         self._chk(self.lib.rk_llama_last_logits(self.h, tok.ctypes.data_as(_i32p), off.ctypes.data_as(_i32p), len(seqs),
                                                 oi.ctypes.data_as(_i32p), len(oi), out.ctypes.data_as(_f32p)))
         return out
+
+    def generate(self, seqs: Sequence[Sequence[int]], max_new: int, eos_ids: Sequence[int], pad_id: int,
+                 max_total: int = 0) -> Tuple[np.ndarray, int]:
+        """Greedy continuation of every prompt (rk_llama_generate: the prefill once, then one KV-cached row per sequence and
+        step) -> (tokens [B, max_new], columns produced).  A row finishes at one of `eos_ids` (at most 8) or, with max_total >
+        0, at that total length; finished rows emit pad_id."""
+        tok, off = pack_ragged(seqs)
+        eos = _i32(list(eos_ids))
+        out = np.empty((len(seqs), max_new), dtype=np.int32)
+        steps = C.c_int32(0)
+        self._chk(self.lib.rk_llama_generate(self.h, tok.ctypes.data_as(_i32p), off.ctypes.data_as(_i32p), len(seqs), int(max_new),
+                                             int(max_total), eos.ctypes.data_as(_i32p), len(eos), int(pad_id),
+                                             out.ctypes.data_as(_i32p), C.byref(steps)))
+        return out, int(steps.value)
 
 
 def rel_bucket(rel: int, bidirectional: bool, num_buckets: int = 32, max_distance: int = 128) -> int:

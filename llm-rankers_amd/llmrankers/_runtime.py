@@ -348,6 +348,41 @@ class T5Runtime:
             parts.append(toks)
         return np.concatenate(parts, axis=0)
 
+def read_generation_settings(model_dir, cfg: dict) -> dict:
+    """What the reference's bare `self.llm.generate(input_ids)` (ref: llmrankers/listwise.py:268) takes from the checkpoint:
+    generation_config.json over config.json for eos_token_id (int or list -> list), pad_token_id (absent: the first EOS id, as
+    HF's generate does), max_new_tokens, max_length, do_sample."""
+    gc = {}
+    if model_dir and os.path.exists(os.path.join(model_dir, "generation_config.json")):
+        with open(os.path.join(model_dir, "generation_config.json")) as f:
+            gc = json.load(f)
+
+    def pick(key):
+        return gc[key] if gc.get(key) is not None else cfg.get(key)
+    eos = pick("eos_token_id")
+    eos = [] if eos is None else ([int(t) for t in eos] if isinstance(eos, (list, tuple)) else [int(eos)])
+    pad = pick("pad_token_id")
+    return {"eos_token_ids": eos, "pad_token_id": int(pad) if pad is not None else (eos[0] if eos else 0),
+            "max_new_tokens": gc.get("max_new_tokens"), "max_length": gc.get("max_length"), "do_sample": bool(gc.get("do_sample"))}
+
+
+def default_generation_length():
+    """(max_new_tokens, max_length) of a bare `generate(input_ids)` when the checkpoint sets no length - resolve_max_new's logic
+    (listwise.py) for a decoder-only prompt: transformers >= 5 has no default max_length and generates 20 new tokens; before,
+    max_length = 20 counted the prompt."""
+    try:
+        from transformers import GenerationConfig
+        ml = GenerationConfig().max_length
+    except Exception:                      # (no transformers: the current default)
+        ml = None
+    return (20, None) if ml is None else (None, int(ml))
+
+
+def hf_prompt_too_long_error():
+    """the exception type HF's generate raises for a prompt that already reaches max_length (ValueError in transformers 4 and 5)"""
+    return ValueError
+
+
 class LlamaRuntime:
     """Decoder-only (Llama family) counterpart of T5Runtime: checkpoint directory -> rk_llama_* engine.  Replaces
     `AutoModelForCausalLM.from_pretrained(..., device_map='auto', torch_dtype=fp16)` of ref: llmrankers/setwise.py:65-69."""
@@ -361,6 +396,7 @@ class LlamaRuntime:
         self.config = cfg
         self.dims = _synth.LlamaDims.from_hf_config(cfg)
         self.max_tokens, self.max_seqs = max_tokens, max_seqs
+        self.generation = read_generation_settings(model_name_or_path, cfg)
         self.engine = RkLlamaEngine(self.dims, parse_device(device), max_tokens, max_seqs)
         self.engine.load_state(iter_checkpoint_tensors(model_name_or_path))
 
@@ -369,11 +405,38 @@ class LlamaRuntime:
         self = cls.__new__(cls)
         self.dims = dims if dims is not None else engine.dims
         self.config, self.model_type = self.dims.to_hf_config(), "llama"
+        self.generation = read_generation_settings(None, self.config)
         self.max_tokens, self.max_seqs = int(engine.desc.max_tokens), int(engine.desc.max_seqs)
         self.engine = engine
         return self
 
     _chunks = T5Runtime._chunks
+    _warned_sampling = False
+
+    def generation_plan(self, prompt_lens) -> dict:
+        """The arguments of `generate` for prompts of these lengths, from the checkpoint's generation settings in HF's order:
+        max_new_tokens if set; else max_length (a limit on prompt + new tokens; a prompt that already reaches it raises what
+        HF's generate raises); else the installed transformers' default.  do_sample: the engine decodes greedily and says so
+        once."""
+        return generation_plan(self, prompt_lens)
+
+    def generate(self, seqs, max_new, eos_ids, pad_id, max_total=0) -> np.ndarray:
+        """[B, max_new] new tokens of every prompt (RkLlamaEngine.generate: prefill once, then one KV-cached row per token);
+        chunked by capacity like T5Runtime.generate, the columns after the step at which every row of an engine call had
+        finished hold -1.  A chunk leaves room for its continuations in the engine's token capacity."""
+        parts = []
+        for c in self._gen_chunks(seqs, max_new):
+            toks, steps = self.engine.generate(c, max_new, eos_ids, pad_id, max_total)
+            toks = toks.copy()
+            toks[:, steps:] = -1
+            parts.append(toks)
+        return np.concatenate(parts, axis=0)
+
+    def _gen_chunks(self, seqs, max_new):
+        for s in seqs:
+            if len(s) + max_new > self.max_tokens:
+                raise ValueError(f"a prompt of {len(s)} tokens + {max_new} new ones exceeds the engine capacity {self.max_tokens}")
+        return self._chunks(seqs)
 
     def greedy1(self, seqs) -> np.ndarray:
         """next token (first arg-max of the last position's logits) of every prompt"""
@@ -381,6 +444,31 @@ class LlamaRuntime:
 
     def last_logits(self, seqs, out_ids) -> np.ndarray:
         return np.concatenate([self.engine.last_logits(c, out_ids) for c in self._chunks(seqs)], axis=0)
+
+
+def generation_plan(runtime, prompt_lens) -> dict:
+    """LlamaRuntime.generation_plan for any runtime with a `generation` dict (the engine's, or a test double's)."""
+    import logging
+    g = runtime.generation
+    if g.get("do_sample") and not getattr(runtime, "_warned_sampling", False):
+        logging.getLogger("llmrankers").warning(
+            "the checkpoint's generation_config.json asks for sampling (do_sample: true); the MI355X engine decodes greedily "
+            "(documented deviation, DESIGN.md section 4)")
+        runtime._warned_sampling = True
+    longest = max(prompt_lens)
+    new, total = g.get("max_new_tokens"), g.get("max_length")
+    if new is None and total is None:
+        new, total = default_generation_length()
+    if new is not None:
+        max_new, max_total = int(new), 0
+    else:
+        max_total = int(total)
+        if longest >= max_total:
+            raise hf_prompt_too_long_error()(
+                f"Input length of input_ids is {longest}, but `max_length` is set to {max_total}. This can lead to unexpected "
+                "behavior. You should consider increasing `max_length` or, better yet, setting `max_new_tokens`.")
+        max_new = max_total - min(prompt_lens)
+    return {"max_new": max_new, "max_total": max_total, "eos_ids": list(g["eos_token_ids"]), "pad_id": int(g["pad_token_id"])}
 
 
 def load_runtime(model_name_or_path: str, device, cache_dir=None):

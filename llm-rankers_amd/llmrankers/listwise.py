@@ -1,11 +1,14 @@
 """Listwise ranker on the MI355X engine: RankGPT-style sliding windows over a "rank these passages" call.
 
-Drop-in for ref: llmrankers/listwise.py:202-291 (ListwiseLlmRanker) on T5 checkpoints - same constructor, `compare()`
+Drop-in for ref: llmrankers/listwise.py:202-291 (ListwiseLlmRanker) on T5 and Llama checkpoints - same constructor, `compare()`
 contract, counters, window walk and permutation rules.  Each compare is one encoder pass over the window's prompt plus either
 a greedy continuation of up to 20 tokens read as a permutation (`scoring='generation'`, engine call rk_t5_generate: one decoder
 row per sequence and step against a K / V cache) or one label-row read at decoder position 1 ordering the passages by their
 label logits (`scoring='likelihood'`, rk_t5_score with the window's label ids).
-Llama checkpoints raise NotImplementedError: listwise generation on them needs an incremental Llama decoder.
+On a Llama checkpoint (ref: listwise.py:235-245, 261-271) a compare is the chat-template prompt (system message, one user /
+assistant pair per passage, the closing instruction) continued greedily by rk_llama_generate - the prefill once, then one
+KV-cached decoder row per new token - with the length, EOS ids and pad id of the checkpoint's generation settings; `likelihood`
+fails there as it does in the reference.
 """
 import copy
 from typing import List, Optional
@@ -30,8 +33,14 @@ MAX_WORDS = 300                                   # words kept per passage (ref:
 QUESTION = 'Given a query "{query}", which of the following passages is the most relevant one to the query?\n\n'
 INSTRUCTION = '\n\nOutput only the passage label of the most relevant passage:'
 
-LLAMA_MESSAGE = ("listwise on the engine needs an incremental (KV-cached) Llama decoder, which it does not have: the listwise "
-                 "ranker is T5-only for now")
+LLAMA_MESSAGE = "listwise on a Llama checkpoint needs a runtime with the incremental (KV-cached) decoder: `generate` is missing"
+# the chat prompt of the Llama branch (ref: listwise.py:17-26, 63-88 with model_name=None: no length loop) - model input, as is
+CHAT_SYSTEM = "You are RankGPT, an intelligent assistant that can rank passages based on their relevancy to the query."
+CHAT_OPEN = "I will provide you with {num} passages, each indicated by number identifier []. \nRank the passages based on their relevance to query: {query}."
+CHAT_OPEN_REPLY = "Okay, please provide the passages."
+CHAT_POST = ("Search Query: {query}. \nRank the {num} passages above based on their relevance to the search query. The passages should be "
+             "listed in descending order using identifiers. The most relevant passages should be listed first. The output format should "
+             "be [] > [], e.g., [1] > [2]. Only response the ranking results, do not say any word or explain.")
 
 
 def resolve_max_new(model_dir: Optional[str] = None) -> int:
@@ -74,15 +83,22 @@ class ListwiseLlmRanker(LlmRanker):
 
     def __init__(self, model_name_or_path, tokenizer_name_or_path, device, window_size, step_size,
                  scoring='generation', num_repeat=1, cache_dir=None):
-        # ref: listwise.py:207-238: T5 by config.model_type; Llama is the reference's other family, not on this engine
-        from ._runtime import load_runtime, read_config, resolve_checkpoint
+        # ref: listwise.py:207-247: T5 or Llama by config.model_type, NotImplementedError otherwise
+        from ._runtime import load_runtime, resolve_checkpoint
         path = resolve_checkpoint(model_name_or_path, cache_dir)
-        if read_config(path).get("model_type") == "llama":
-            raise NotImplementedError(LLAMA_MESSAGE)
         try:
             runtime = load_runtime(path, device, cache_dir=cache_dir)
-        except NotImplementedError as exc:   # same message shape as ref: listwise.py:238
+        except NotImplementedError as exc:   # same message shape as ref: listwise.py:247
             raise NotImplementedError(f"{exc} (listwise)") from None
+        if runtime.model_type == "llama":
+            from transformers import AutoTokenizer
+            from .setwise import VICUNA_TEMPLATE
+            tokenizer = AutoTokenizer.from_pretrained(model_name_or_path, cache_dir=cache_dir)   # (the reference ignores tokenizer_name_or_path here)
+            tokenizer.use_default_system_prompt = False
+            if 'v1.5' in model_name_or_path:       # the reference's `'vicuna' and 'v1.5' in name` (ref :238)
+                tokenizer.chat_template = VICUNA_TEMPLATE
+            self._setup(runtime, tokenizer, device, window_size, step_size, scoring, num_repeat, None)
+            return
         from transformers import T5Tokenizer
         tokenizer = T5Tokenizer.from_pretrained(
             tokenizer_name_or_path if tokenizer_name_or_path is not None else model_name_or_path, cache_dir=cache_dir)
@@ -94,13 +110,17 @@ class ListwiseLlmRanker(LlmRanker):
         """Build the ranker around an existing runtime (a loaded engine, or a test double) and tokenizer.  max_new: new tokens
         per `generation` compare (None: the installed transformers' default, resolve_max_new)."""
         self = cls.__new__(cls)
-        self._setup(runtime, tokenizer, device, window_size, step_size, scoring, num_repeat,
-                    resolve_max_new() if max_new is None else int(max_new))
+        if getattr(runtime, "model_type", "t5") == "llama":        # the length comes from the runtime's generation settings
+            self._setup(runtime, tokenizer, device, window_size, step_size, scoring, num_repeat, max_new)
+        else:
+            self._setup(runtime, tokenizer, device, window_size, step_size, scoring, num_repeat,
+                        resolve_max_new() if max_new is None else int(max_new))
         return self
 
     def _setup(self, runtime, tokenizer, device, window_size, step_size, scoring, num_repeat, max_new):
-        if getattr(runtime, "model_type", "t5") == "llama":
-            raise NotImplementedError(LLAMA_MESSAGE)
+        self.model_type = getattr(runtime, "model_type", "t5")
+        if self.model_type == "llama" and not hasattr(runtime, "generate"):
+            raise NotImplementedError(f"{LLAMA_MESSAGE} (Llama runtime {type(runtime).__name__})")
         self.device = device
         self.window_size = window_size
         self.step_size = step_size
@@ -110,13 +130,15 @@ class ListwiseLlmRanker(LlmRanker):
         self.config = getattr(runtime, "config", None)
         self.tokenizer = tokenizer
         self.max_new = max_new
+        self.total_compare = 0
+        self.total_prompt_tokens = 0
+        self.total_completion_tokens = 0
+        if self.model_type == "llama":           # no decoder prompt / label ids: the reference's Llama branch sets none (ref :235-245)
+            return
         self.decoder_start = [int(getattr(runtime, "decoder_start_token_id", 0) or 0)]
         # likelihood: decoder prompt "<pad> Passage" and the last token of "<pad> Passage {label}" (ref: listwise.py:225-231)
         self.decoder_input_ids = self.tokenizer.encode("<pad> Passage", add_special_tokens=False)
         self.target_token_ids = [self.tokenizer.encode(f"<pad> Passage {c}", add_special_tokens=False)[-1] for c in self.CHARACTERS]
-        self.total_compare = 0
-        self.total_prompt_tokens = 0
-        self.total_completion_tokens = 0
 
     # ------------------------------------------------------------------------------------------------------
     def _permutation_prompt(self, query: str, docs: List) -> str:
@@ -124,6 +146,48 @@ class ListwiseLlmRanker(LlmRanker):
         body = "".join(ENTRY.format(rank=r + 1, content=" ".join(d.text.replace('Title: Content: ', '').strip().split()[:MAX_WORDS]))
                        for r, d in enumerate(docs))
         return HEAD.format(num=num, query=query) + body + TAIL.format(num=num, query=query)
+
+    def _chat_messages(self, query: str, docs: List) -> List[dict]:
+        """create_permutation_instruction_chat(query, docs, model_name=None) (ref: listwise.py:63-88)"""
+        num = len(docs)
+        messages = [{'role': 'system', 'content': CHAT_SYSTEM},
+                    {'role': 'user', 'content': CHAT_OPEN.format(num=num, query=query)},
+                    {'role': 'assistant', 'content': CHAT_OPEN_REPLY}]
+        for r, d in enumerate(docs):
+            content = " ".join(d.text.replace('Title: Content: ', '').strip().split()[:MAX_WORDS])
+            messages.append({'role': 'user', 'content': f"[{r + 1}] {content}"})
+            messages.append({'role': 'assistant', 'content': f'Received passage [{r + 1}].'})
+        messages.append({'role': 'user', 'content': CHAT_POST.format(num=num, query=query)})
+        return messages
+
+    def _chat_ids(self, query: str, docs: List) -> List[int]:
+        """tokenizer.apply_chat_template(messages, add_generation_prompt=True) with tokenisation on (ref: listwise.py:263-264)"""
+        ids = self.tokenizer.apply_chat_template(self._chat_messages(query, docs), add_generation_prompt=True, return_dict=False)
+        return [int(t) for t in ids]
+
+    def _compare_windows_llama(self, queries: List[str], doc_lists: List[List]):
+        if self.scoring == 'likelihood':
+            # ref: listwise.py:282 reads self.decoder_input_ids, which only the T5 branch sets
+            raise AttributeError("'ListwiseLlmRanker' object has no attribute 'decoder_input_ids'")
+        if self.scoring != 'generation':
+            raise UnboundLocalError("local variable 'output' referenced before assignment")
+        from ._runtime import generation_plan
+        ids = [self._chat_ids(q, docs) for q, docs in zip(queries, doc_lists)]
+        plan = generation_plan(self.llm, [len(i) for i in ids])
+        if self.max_new is not None:
+            plan["max_new"], plan["max_total"] = int(self.max_new), 0
+        new = np.asarray(self.llm.generate(ids, plan["max_new"], plan["eos_ids"], plan["pad_id"], plan["max_total"]))
+        outs, completion = [], []
+        for prompt, row in zip(ids, new):
+            toks = [int(t) for t in row if t >= 0]
+            if plan["max_total"]:                                # alone, this row would have stopped at its own length limit
+                toks = toks[:plan["max_total"] - len(prompt)]
+            stop = next((i for i, t in enumerate(toks) if t in plan["eos_ids"]), None)
+            if stop is not None:                                 # ... or at its own EOS
+                toks = toks[:stop + 1]
+            completion.append(len(prompt) + len(toks))           # the reference counts the prompt too (ref :269)
+            outs.append(self.tokenizer.decode(toks, skip_special_tokens=True).strip())
+        return outs, [len(i) for i in ids], completion
 
     def _label_prompt(self, query: str, docs: List) -> str:
         passages = "\n\n".join(f'Passage {self.CHARACTERS[i]}: "{doc.text}"' for i, doc in enumerate(docs))
@@ -142,6 +206,8 @@ class ListwiseLlmRanker(LlmRanker):
     def _compare_windows(self, queries: List[str], doc_lists: List[List]):
         """ONE engine call for windows that may belong to different queries -> (outputs, prompt tokens per window, completion
         tokens per window); touches no counter.  A window's result does not depend on what shares the call."""
+        if self.model_type == "llama":
+            return self._compare_windows_llama(queries, doc_lists)
         if self.scoring == 'generation':
             ids = self._truncated_ids([self._permutation_prompt(q, docs) for q, docs in zip(queries, doc_lists)])
             eos, pad = self.tokenizer.eos_token_id, self.tokenizer.pad_token_id

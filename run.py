@@ -6,8 +6,8 @@
            pointwise --method yes_no --batch_size 32
 
 Same sub-commands (`run` + one of `pointwise` / `setwise`), flags, defaults, TREC run input/output and the four
-averages printed at the end (ref: run.py:198-201).  OpenAI rankers, duoT5 pairwise and listwise on Llama checkpoints are
-outside the hot path this build accelerates and are rejected with a clear message.  The data back-ends
+averages printed at the end (ref: run.py:198-201).  Listwise runs on T5 and on Llama checkpoints (the latter on the KV-cached
+decoder rk_llama_generate).  OpenAI rankers and duoT5 pairwise are outside the hot path this build accelerates and are rejected with a clear message.  The data back-ends
 (ir_datasets / pyserini) are imported lazily; because neither exists offline, two plain-file sources are
 accepted as well:  --query_file (TSV `qid<TAB>text` or JSONL {"qid"|"query_id"|"_id", "text"|"query"}) and
 --doc_file (TSV `docid<TAB>text` or JSONL {"docid"|"doc_id"|"_id", "text"|"contents", ["title"]}).

@@ -6,6 +6,12 @@ rk_t5_greedy (whole-prefix recompute), alternated in one process; lockstep (rera
 microseconds per decoder step of rk_t5_generate at 1 and 32 sequences ((t(20 new tokens) - t(1)) / 19 over the same prompts).
 One JSON object per line on stdout, and into the file --out names.
 
+--llama: the Llama leg instead (Llama-3-8B dims, _synth's timing-only weights, window-4-sized prompts of 1 536 tokens, 20 new
+tokens, no EOS).  Per row count 1 / 8 / 32, median of three: rk_llama_generate's prefill (max_new = 1), ms per KV-cached step
+((t(20) - t(1)) / 19), and the same 20 tokens by a loop of rk_llama_greedy1 over the growing prompt (a full prefill per token) in
+the same process; plus the per-class split of one 20-token call (event-bracketed pass).  --llama --profile-call: ONE call of 8
+rows (for `rocprofv3 --kernel-trace --stats -- python tools/bench_listwise.py --llama --profile-call`).
+
 --profile-call: only ONE lockstep call of 8 windows (for `rocprofv3 --kernel-trace --hip-runtime-trace --stats -- python
 tools/bench_listwise.py --profile-call`): every decoder step of it should be one hipGraphLaunch."""
 import argparse
@@ -61,7 +67,10 @@ def main():
     ap.add_argument("--out", default=None, help="also write the result lines to this file")
     ap.add_argument("--rounds", type=int, default=2)
     ap.add_argument("--profile-call", action="store_true")
+    ap.add_argument("--llama", action="store_true")
     args = ap.parse_args()
+    if args.llama:
+        return llama_leg(args)
     from transformers import T5Tokenizer
     tok = T5Tokenizer.from_pretrained(os.path.join(REPO, "tests", "golden", "tok"))
     dims = _synth.FLAN_T5_LARGE
@@ -84,6 +93,65 @@ def main():
         emit(what="profile_call", windows=8, ms=ms)
     else:
         sweep(eng, rt, rk, tok, args, emit)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            for r in rows:
+                f.write(json.dumps(r) + "\n")
+
+
+def llama_leg(args):
+    from llmrankers._engine import RkLlamaEngine
+    dims = _synth.LLAMA_3_8B
+    L, NEW = 1536, 20
+    eng = RkLlamaEngine(dims, device=0, max_tokens=32 * (L + NEW) + 64, max_seqs=32)
+    eng.load_state(_synth.synth_tensors_pool(dims, seed=929))
+    rows = []
+
+    def emit(**kw):
+        print(json.dumps(kw), flush=True)
+        rows.append(kw)
+
+    rs = np.random.RandomState(11)
+    prompts = [rs.randint(3, dims.vocab - 28, size=L).astype(np.int32) for _ in range(32)]
+
+    def reprefill(seqs):
+        cur = [list(s) for s in seqs]
+        for _ in range(NEW):
+            nxt = eng.greedy1(cur)
+            for c, t in zip(cur, nxt):
+                c.append(int(t))
+        return cur
+
+    if args.profile_call:
+        eng.generate(prompts[:8], NEW, [], 0)
+        eng.generate(prompts[:8], NEW, [], 0)                                            # warm: first sighting, capture
+        ms, _ = timed(lambda: eng.generate(prompts[:8], NEW, [], 0))
+        emit(what="llama_profile_call", rows=8, prompt_tokens=L, new_tokens=NEW, ms=ms)
+    else:
+        w_bytes = 2.0 * (dims.n_layers * (dims.hidden * (dims.n_heads + 2 * dims.n_kv_heads) * 128 + dims.hidden * dims.n_heads * 128
+                                          + 3 * dims.hidden * dims.intermediate) + dims.vocab * dims.hidden)
+        for n in (1, 8, 32):
+            seqs = prompts[:n]
+            for max_new in (1, NEW, NEW):
+                eng.generate(seqs, max_new, [], 0)                                         # warm-up: allocation, eager step, capture
+            t1 = float(np.median([timed(lambda: eng.generate(seqs, 1, [], 0))[0] for _ in range(3)]))
+            t20 = float(np.median([timed(lambda: eng.generate(seqs, NEW, [], 0))[0] for _ in range(3)]))
+            eng.greedy1(seqs)
+            loop = float(np.median([timed(lambda: reprefill(seqs))[0] for _ in range(3)]))
+            step = (t20 - t1) / (NEW - 1)
+            kv_bytes = 2.0 * n * (L + NEW / 2) * dims.n_kv_heads * 128 * 2 * dims.n_layers
+            emit(what="llama_generate", rows=n, prompt_tokens=L, new_tokens=NEW, prefill_ms=t1, generate_ms=t20, ms_per_step=step,
+                 reprefill_loop_ms=loop, speedup=loop / t20, hbm_floor_ms_per_step=(w_bytes + kv_bytes) / 6e12 * 1e3,
+                 weight_bytes=w_bytes, kv_bytes=kv_bytes)
+        eng.profile(True)                                                                  # per-class split of one 8-row call (eager)
+        eng.profile_reset()
+        eng.generate(prompts[:8], NEW, [], 0)
+        rep = eng.profile_report()
+        eng.profile(False)
+        emit(what="llama_generate_classes", rows=8, new_tokens=NEW,
+             classes={k: {"ms": round(v["ms"], 3), "launches": v["launches"]} for k, v in rep.items() if v["launches"]})
+    eng.close()
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as f:
