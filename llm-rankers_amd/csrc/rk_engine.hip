@@ -63,6 +63,43 @@ struct LlamaLayerW { half_t *qkv_f = nullptr, *o = nullptr, *gu_f = nullptr, *do
 
 struct ProfRec { hipEvent_t a, b; int cls; };
 
+struct Gemm;
+
+// The residual stream of ONE chain (encoder, T5 decoder, Llama prefill, Llama step) and the protocol of its RMSNorms.
+// Folded (the default): the GEMMs that follow a norm read the un-normalised stream as fp16 (written by the producer of the
+// stream: embedding / residual epilogue), their weights carry the norm weight, and their epilogue applies the row factor - the
+// norm kernels (re-reading the fp32 stream) are gone.  Unfolded: rmsnorm writes xn in front of every consumer.
+// The buffers live as long as their owner (Slot, rk_engine::LlamaStep); a chain works on a copy, whose state begin() resets.
+struct NormStream {
+  float* hidden = nullptr;                 // the fp32 stream [rows, d_model]
+  half_t* xraw[2] = {nullptr, nullptr};    // its fp16 copy x RK_XRAW_SCALE.  Two that alternate where a producer reads the stream it
+                                           // replaces (T5 decoder: a producer never writes the buffer a workgroup of the same launch
+                                           // may still read); else one
+  float* ssq[2] = {nullptr, nullptr};      // block sums of squares per row left by the producer, one buffer per xraw
+  float* factors = nullptr;                // row factors: written by the embedding or by rowscale_kernel
+  half_t* xn = nullptr;                    // unfolded: the normed copy (chains that never run unfolded have none)
+  int rows = 0; bool fold = false;
+  int cur = 0, nb = 0;                     // the current xraw / ssq; block sums per row of the last producer (its plan; 0: the
+                                           // embedding wrote the row factors)
+  void begin(rk_engine* e, hipStream_t st, const int* ids, int rows_, bool fold_);   // the embedding launch
+  const half_t* x() const { return fold ? xraw[cur] : xn; }                          // what the GEMMs behind a norm read
+  Gemm consumer(rk_engine* e, hipStream_t st, const float* ln, Gemm c, bool own_factors) const;
+  int producer(rk_engine* e, hipStream_t st, Gemm c, bool stats = true);
+};
+
+// A device buffer that grows between calls (never inside a capture).  reserve: nothing if n elements fit; else everything in
+// flight is awaited, the buffer is replaced (contents lost) and *gen - part of the key of every graph that captured the
+// address - is bumped.  Freed with its owner.
+template <class T>
+struct Grown {
+  T* p = nullptr; size_t cap = 0;
+  Grown() = default;
+  Grown(const Grown&) = delete;
+  Grown& operator=(const Grown&) = delete;
+  ~Grown() { if (p) hipFree(p); }
+  int reserve(rk_engine* e, size_t n, int* gen = nullptr);
+};
+
 }  // namespace
 
 #define RK_SLOTS 2
@@ -73,15 +110,15 @@ struct ProfRec { hipEvent_t a, b; int cls; };
 // (1104 GEMM tiles on 512 resident slots is 3 rounds alone but 2.16 rounds of work).
 struct Slot {
   hipStream_t se = nullptr, sd = nullptr;   // this slot's encoder chain (MFMA-bound) | decoder chain (latency-bound)
-  float* hidden = nullptr; half_t *xn = nullptr, *qkv = nullptr, *ctx = nullptr, *ffh = nullptr, *enc_out = nullptr;
-  half_t* xraw = nullptr; float *ssq = nullptr, *rowscale = nullptr;   // folded RMSNorm: fp16 stream x RK_XRAW_SCALE, block sums of squares, row factors
+  NormStream enc;                                              // the encoder's residual stream (Llama: the prefill's)
+  half_t *qkv = nullptr, *ctx = nullptr, *ffh = nullptr, *enc_out = nullptr;
   int* d_tokens = nullptr; int* d_seq_off = nullptr;
   int n_seq = 0, T = 0, maxL = 0, minL = 0; bool staged = false; int last_n_out = 0;
   half_t* cross_kv = nullptr;                                  // [n_dec][max_tokens][2I] encoder -> decoder hand-off
   int *d_dec_ids = nullptr, *d_last_rows = nullptr, *d_out_ids = nullptr, *d_labels = nullptr, *d_argmax = nullptr, *d_row_seq = nullptr, *d_tree_keys = nullptr, *d_tree_pos = nullptr;
-  float* dhidden = nullptr; half_t *dxn = nullptr, *dqkv = nullptr, *dctx = nullptr, *dq = nullptr, *dffh = nullptr, *dlast = nullptr;
-  half_t* dxraw[2] = {nullptr, nullptr}; float* dssq[2] = {nullptr, nullptr}; float* drowscale = nullptr;   // folded decoder norms (run_decoder)
-  float* dssq_few[2] = {nullptr, nullptr};   // the same for the few-row GEMV family (gemv_rows.h): one partial per producing workgroup
+  NormStream dec;                                              // the decoder's (run_decoder); rk_t5_qlm's final norm writes dec.xn
+  half_t *dqkv = nullptr, *dctx = nullptr, *dq = nullptr, *dffh = nullptr, *dlast = nullptr;
+  float* dssq_few[2] = {nullptr, nullptr};   // dec.ssq for the few-row GEMV family (gemv_rows.h): one partial per producing workgroup
   half_t *xqk = nullptr, *xctx = nullptr;                      // direct cross-attention: [32][H*d] each
   float *xpart = nullptr, *xstat = nullptr; bool have_cross_kv = false;
   float* d_scores = nullptr; float* h_scores = nullptr;
@@ -104,13 +141,13 @@ struct rk_engine {
   std::vector<EncLayerW> enc;
   std::vector<DecLayerW> dec;
   float *enc_final_ln = nullptr, *dec_final_ln = nullptr, *lut_enc = nullptr, *lut_dec = nullptr;
-  float* logits = nullptr; size_t logits_cap = 0;              // qlm head: per-block (max, sum exp) pairs [rows, vocab/32] + label logits [rows]; slot 0 only
+  Grown<float> logits;                                         // qlm head: per-block (max, sum exp) pairs [rows, vocab/32] + label logits [rows]; slot 0 only
   const int* lse_labels = nullptr; int lse_npos = 0; float* lse_xlab = nullptr;   // arguments of the next EPI_LSE_F32 launch
-  float* amax_val = nullptr; int* amax_idx = nullptr; size_t amax_rows = 0;   // greedy head: per-row block maxima / first columns
-  // rk_t5_generate: self-attention K / V cache [n_dec_layers][n_seq][P][2 inner] (grown like amax; kv_gen counts the moves), the
-  // per-call int block on the device (state, prefix, finished rows, output, tree arrays), pinned read-back of the finished step
-  half_t* kv_cache = nullptr; size_t kv_cap = 0; int kv_gen = 0;
-  int* gen_buf = nullptr; size_t gen_cap = 0; int* gen_pin = nullptr; hipEvent_t ev_gen[2] = {nullptr, nullptr};
+  Grown<float> amax_val; Grown<int> amax_idx; int amax_gen = 0;   // greedy head: per-row block maxima / first columns
+  // rk_t5_generate: self-attention K / V cache [n_dec_layers][n_seq][P][2 inner] (kv_gen counts the moves) and the per-call int
+  // block on the device (state, prefix, finished rows, output, tree arrays); decode_cached: pinned read-back of the finished step
+  Grown<half_t> kv_cache; int kv_gen = 0;
+  Grown<int> gen_buf; int* gen_pin = nullptr; hipEvent_t ev_gen[2] = {nullptr, nullptr};
   size_t scores_cap = 0;
   Slot slots[RK_SLOTS];
   // options / measurement
@@ -141,9 +178,8 @@ struct rk_engine {
   std::vector<LlamaLayerW> ll; float *l_final_ln = nullptr, *rope_cos = nullptr, *rope_sin = nullptr; int* d_pos = nullptr;
   // rk_llama_generate: K / V cache [n_layers][2][n_seq][n_kv][P][128], the attention partials and the call's int block (grown
   // between calls; lkv_gen counts the moves and is part of the step graph's key), and the step's activation rows (max_seqs each)
-  half_t* lkv = nullptr; size_t lkv_cap = 0; float* lpart = nullptr; size_t lpart_cap = 0; int* lints = nullptr; size_t lints_cap = 0;
-  int lkv_gen = 0;
-  struct LlamaStep { float* hidden = nullptr; half_t *xraw = nullptr, *qkv = nullptr, *ctx = nullptr, *ffh = nullptr; float *ssq = nullptr, *rowscale = nullptr; } lg;
+  Grown<half_t> lkv; Grown<float> lpart; Grown<int> lints; int lkv_gen = 0;
+  struct LlamaStep { NormStream stream; half_t *qkv = nullptr, *ctx = nullptr, *ffh = nullptr; } lg;
   // decoder chains as HIP graphs: key = everything the launch parameters of a chain depend on
   struct GraphEntry { int seen = 0; bool failed = false; hipGraphExec_t exec = nullptr; };
   std::map<std::vector<int>, GraphEntry> graphs; int opt_epoch = 0;
@@ -514,7 +550,7 @@ int gemm(rk_engine* e, hipStream_t st, const Gemm& c, int* nb = nullptr) {
   a.rowscale = c.fold.rowscale; a.xraw = c.fold.xraw; a.ssq = c.fold.ssq; a.ldx = c.N; a.nb = p.nb; a.xs = RK_XRAW_SCALE;
   a.ssq_in = c.fold.ssq_in; a.nb_in = c.fold.nb_in; a.eps_in = e->d.eps;
   a.group_n = GEMM_GROUP_N;
-  if (c.epi == EPI_ARGMAX_F32) a.amax_idx = e->amax_idx;
+  if (c.epi == EPI_ARGMAX_F32) a.amax_idx = e->amax_idx.p;
   if (c.epi == EPI_LSE_F32) { a.lse_labels = e->lse_labels; a.lse_npos = e->lse_npos; a.lse_xlab = e->lse_xlab; }
   const double flops = 2.0 * c.M * (double)c.N * c.K * c.batch;
   const double out_elems = EPI_IS_GATED(c.epi) ? (double)c.M * c.N / 2 : (double)c.M * c.N;
@@ -560,6 +596,33 @@ void rowscale(rk_engine* e, hipStream_t st, const float* ssq, float* out, int ro
   if (rows <= 0) return;
   Bracket br(e, st, PC_NORM, 0, (double)rows * (nb + 1) * 4.0);
   hipLaunchKernelGGL(rowscale_kernel, dim3((rows + 255) / 256), dim3(256), 0, st, ssq, out, rows, nb, e->d.d_model, e->d.eps, RK_XRAW_SCALE);
+}
+
+void NormStream::begin(rk_engine* e, hipStream_t st, const int* ids, int rows_, bool fold_) {
+  rows = rows_; fold = fold_; cur = 0; nb = 0;
+  embed(e, st, ids, hidden, rows, fold ? xraw[0] : nullptr, fold ? factors : nullptr);
+}
+
+// The GEMM c behind the norm with weight ln (c reads x(); folded, its matrix carries ln).  Folded, it needs the row factors: the
+// embedding wrote them (nb == 0), or they come from the last producer's block sums.  The persistent ping-pong GEMM takes them
+// ready-made (loaded under its last MFMAs): rowscale_kernel runs in front of it.  Every other kernel can add the block sums itself
+// in its epilogue (gemm_row_factors, same rk_row_factor -> same bits, one launch less where launches are what costs) and does
+// where the chain allows it (own_factors - the whole of a site's policy); else rowscale_kernel again.
+Gemm NormStream::consumer(rk_engine* e, hipStream_t st, const float* ln, Gemm c, bool own_factors) const {
+  GemmFold f;
+  if (!fold) rmsnorm(e, st, hidden, ln, xn, nullptr, rows);
+  else if (nb && own_factors && !plan_gemm(e, c, st).pp2()) { f.ssq_in = ssq[cur]; f.nb_in = nb; }
+  else { if (nb) rowscale(e, st, ssq[cur], factors, rows, nb); f.rowscale = factors; }
+  return c.with(f);
+}
+
+// A residual GEMM (fp32 stream += c).  Folded and `stats` (all but the chain's last: the final norm reads the fp32 stream) it also
+// leaves the next fp16 copy of the stream and its block sums: the GEMMs from here on read what this one writes.
+int NormStream::producer(rk_engine* e, hipStream_t st, Gemm c, bool stats) {
+  if (!(fold && stats)) return gemm(e, st, c);
+  if (xraw[1]) cur ^= 1;
+  c.fold.xraw = xraw[cur]; c.fold.ssq = ssq[cur];
+  return gemm(e, st, c, &nb);
 }
 
 // ---- relative position bucket (hf: modeling_t5.py:216-262), float32 like torch ------------------------------
@@ -849,38 +912,24 @@ int run_encoder(rk_engine* e, Slot& sl, bool need_cross_kv) {
   const rk_model_desc& d = e->d;
   hipStream_t st = enc_stream(e, sl);
   const int T = sl.T, I = e->inner, dm = d.d_model, F = d.d_ff;
-  // Folded RMSNorm (default): the GEMMs that follow a norm read the un-normalised stream as fp16 (written by the
-  // producer of the stream: embedding / residual epilogue), their weights carry the norm weight, and their epilogue
-  // applies the row factor - the two norm kernels per layer (re-reading the fp32 stream) are gone.
-  const bool fold = e->opt.fold_norm != 0;
-  half_t* const xin = fold ? sl.xraw : sl.xn;   // what the GEMMs behind a norm read
-  GemmFold prod;                                // producer side: the residual GEMMs (but the last: the final norm reads the fp32 stream)
-  if (fold) { prod.xraw = sl.xraw; prod.ssq = sl.ssq; }
-  int nb = 0, rc = RK_OK;                       // block sums per row of the last residual GEMM (0: the embedding wrote the row factors)
-  // The GEMM c behind a norm.  Folded, the persistent ping-pong GEMM takes its row factors ready-made (loaded under its last
-  // MFMAs): a rowscale_kernel runs in front of it.  The fill-in tile variants of small launches (one setwise prompt) add the block
-  // sums themselves in their epilogue (gemm_row_factors, same rk_row_factor -> same bits): two 5-us launches per layer less where
-  // launches are what costs.
-  auto normed = [&](const float* ln, Gemm c) {
-    GemmFold f;
-    if (!fold) rmsnorm(e, st, sl.hidden, ln, sl.xn, nullptr, T);
-    else if (nb && e->opt.consumer_stats && !plan_gemm(e, c, st).pp2()) { f.ssq_in = sl.ssq; f.nb_in = nb; }
-    else { if (nb) rowscale(e, st, sl.ssq, sl.rowscale, T, nb); f.rowscale = sl.rowscale; }
-    return c.with(f);
-  };
+  // The fill-in tile variants of small launches (one setwise prompt) may form their row factors themselves (option consumer_stats):
+  // two 5-us launches per layer less where launches are what costs.
+  const bool own = e->opt.consumer_stats != 0;
+  int rc = RK_OK;
+  NormStream ns = sl.enc;
   const EncAttnPlan ap = plan_enc_attn(e, sl.n_seq, sl.maxL, sl.minL, d.n_heads);
-  embed(e, st, sl.d_tokens, sl.hidden, T, fold ? sl.xraw : nullptr, fold ? sl.rowscale : nullptr);
+  ns.begin(e, st, sl.d_tokens, T, e->opt.fold_norm != 0);
   for (int l = 0; l < d.n_enc_layers; ++l) {
     const EncLayerW& w = e->enc[l];
     const bool last = l + 1 == d.n_enc_layers;
-    RC(gemm(e, st, normed(w.ln0, Gemm(PC_ENC_GEMM_QKV, EPI_STORE_F16, xin, dm, fold ? w.qkv_f : w.qkv, dm, sl.qkv, 3 * I, T, 3 * I, dm))));
+    RC(gemm(e, st, ns.consumer(e, st, w.ln0, Gemm(PC_ENC_GEMM_QKV, EPI_STORE_F16, ns.x(), dm, ns.fold ? w.qkv_f : w.qkv, dm, sl.qkv, 3 * I, T, 3 * I, dm), own)));
     launch_enc_attn(e, st, sl, ap);
-    RC(gemm(e, st, Gemm(PC_ENC_GEMM_O, EPI_RESID_F32, sl.ctx, I, w.o, I, sl.hidden, dm, T, dm, I).with(prod), &nb));
-    RC(gemm(e, st, normed(w.ln1, Gemm(PC_ENC_GEMM_FFN_IN, d.gated_gelu ? EPI_GEGLU_F16 : EPI_RELU_F16, xin, dm, fold ? w.ffn_in_f : w.ffn_in, dm,
-                                      sl.ffh, F, T, d.gated_gelu ? 2 * F : F, dm))));
-    RC(gemm(e, st, Gemm(PC_ENC_GEMM_FFN_OUT, EPI_RESID_F32, sl.ffh, F, w.ffn_out, F, sl.hidden, dm, T, dm, F).with(last ? GemmFold() : prod), &nb));
+    RC(ns.producer(e, st, Gemm(PC_ENC_GEMM_O, EPI_RESID_F32, sl.ctx, I, w.o, I, ns.hidden, dm, T, dm, I)));
+    RC(gemm(e, st, ns.consumer(e, st, w.ln1, Gemm(PC_ENC_GEMM_FFN_IN, d.gated_gelu ? EPI_GEGLU_F16 : EPI_RELU_F16, ns.x(), dm, ns.fold ? w.ffn_in_f : w.ffn_in, dm,
+                                                 sl.ffh, F, T, d.gated_gelu ? 2 * F : F, dm), own)));
+    RC(ns.producer(e, st, Gemm(PC_ENC_GEMM_FFN_OUT, EPI_RESID_F32, sl.ffh, F, w.ffn_out, F, ns.hidden, dm, T, dm, F), !last));
   }
-  rmsnorm(e, st, sl.hidden, e->enc_final_ln, sl.enc_out, nullptr, T);
+  rmsnorm(e, st, ns.hidden, e->enc_final_ln, sl.enc_out, nullptr, T);
   // the stacked K/V projections are only materialised when the decoder has too many rows for the query-side form
   if (need_cross_kv)
     RC(gemm(e, st, Gemm(PC_GEMM_CROSS_KV, EPI_STORE_F16, sl.enc_out, dm, e->cross_kv_w, dm, sl.cross_kv, 2 * I, T, d.n_dec_layers * 2 * I, dm)
@@ -891,7 +940,7 @@ int run_encoder(rk_engine* e, Slot& sl, bool need_cross_kv) {
 }
 
 // hf: modeling_t5.py:663-750 (decoder stack) for Ld teacher-forced positions per sequence (ids already on the
-// device in sl.d_dec_ids, row = b*Ld + t).  Leaves the residual stream in sl.dhidden.
+// device in sl.d_dec_ids, row = b*Ld + t).  Leaves the residual stream in sl.dec.hidden.
 // tree (rk_t5_greedy2): the decoder rows are not Ld per sequence - several continuations of a prompt share the rows of their
 // common prefix.  rows = row count, Ld = longest position count; device arrays: keys[r * Ld + j] = row at position j of
 // row r's sequence, pos[r] = position of row r, seq[r] = its encoder sequence.  Query-side cross-attention only.
@@ -914,9 +963,8 @@ int run_decoder(rk_engine* e, Slot& sl, int Ld, const DecTree* tree = nullptr, c
   if (cache && (tree || sl.have_cross_kv || Ld != 1)) return fail(e, RK_ERR_STATE, "the incremental pass needs the query-side cross-attention and one row per sequence");
   const bool ws = Ld <= 4;   // few decoder positions: weight-streaming GEMMs (any number of sequences); else tiled
   // Folded RMSNorm on the weight-streaming path (as in the encoder, minus the statistics kernel): the residual GEMMs leave
-  // the new rows as fp16 (dxraw) with their sums of squares per 32-column block (dssq), the GEMM behind the norm reads
-  // those with the norm weight folded into its matrix and forms the row factor itself (gemm.h: GemmArgs::ssq_in) - three
-  // launches per layer less.  A producer never writes the buffer a workgroup of the same launch may still read: two of each.
+  // the new rows as fp16 with their sums of squares per 32-column block, the GEMM behind the norm reads those with the norm
+  // weight folded into its matrix and forms the row factor itself (gemm.h: GemmArgs::ssq_in) - three launches per layer less.
   const bool dfold = ws && e->opt.dec_fold_norm && (e->opt.skinny & 0x3F) == 0x3F;
   // Few-row GEMV family (round 6, gemv_rows.h): the pass of ONE setwise / pairwise prompt - a handful of rows at two or more
   // positions ("<pad> Passage": 2 rows; the second greedy step: 3) - runs its plain projections one wave per output column over all
@@ -938,36 +986,26 @@ int run_decoder(rk_engine* e, Slot& sl, int Ld, const DecTree* tree = nullptr, c
   const bool few = dfold && e->opt.dec_gemv && Ld >= 2 && M <= e->opt.dec_gemv_rows && !fuse_asked &&
                    gemv_fits(M, dm) && gemv_fits(M, I) && gemv_fits(M, F);   // every K of the pass's projections
   const GemmFamily fam = few ? GEMM_GEMV : (ws ? GEMM_STREAM : GEMM_TILED);
-  // folded: the stream is dxraw[cur] with nb block sums per row in ssq[cur] (nb: the plan of the GEMM that wrote them; 0: the
-  // embedding wrote the row factors)
-  float* const* ssq = few ? sl.dssq_few : sl.dssq;
-  int cur = 0, nb = 0, rc = RK_OK;
-  auto xin = [&]() { return dfold ? sl.dxraw[cur] : sl.dxn; };   // what the GEMMs behind a norm read
-  auto norm = [&](const float* ln) {                              // ... and their row factors
-    GemmFold f;
-    if (!dfold) rmsnorm(e, st, sl.dhidden, ln, sl.dxn, nullptr, M);
-    else if (!nb) f.rowscale = sl.drowscale;
-    else { f.ssq_in = ssq[cur]; f.nb_in = nb; }
-    return f;
-  };
-  // a residual GEMM (fp32 stream += c); folded and `stats` (all but the last: the head's norm reads the fp32 stream) it also leaves
-  // the next fp16 copy of the stream and its block sums
-  auto resid = [&](Gemm c, bool stats = true) {
-    if (!(dfold && stats)) return gemm(e, st, c.on(fam));
-    c.fold.xraw = sl.dxraw[cur ^ 1]; c.fold.ssq = ssq[cur ^ 1];
-    cur ^= 1;                                                     // the GEMMs from here on read what this one writes
-    return gemm(e, st, c.on(fam), &nb);
-  };
-  embed(e, st, sl.d_dec_ids, sl.dhidden, M, dfold ? sl.dxraw[0] : nullptr, dfold ? sl.drowscale : nullptr);
+  int rc = RK_OK;
+  NormStream ns = sl.dec;
+  if (few) { ns.ssq[0] = sl.dssq_few[0]; ns.ssq[1] = sl.dssq_few[1]; }
+  // the GEMM c of this pass's family behind the norm ln: every consumer here may form its row factors itself
+  auto normed = [&](const float* ln, Gemm c) { return ns.consumer(e, st, ln, c.on(fam), true); };
+  auto resid = [&](Gemm c, bool stats = true) { return ns.producer(e, st, c.on(fam), stats); };
+  ns.begin(e, st, sl.d_dec_ids, M, dfold);
   const DecAttnPlan self_plan = plan_dec_attn(e, false, B, Ld, Ld, d.n_heads, tree ? tree->rows : 0);
   const DecAttnPlan cross_plan = plan_dec_attn(e, true, B, Ld, sl.maxL, d.n_heads, 0);
   for (int l = 0; l < d.n_dec_layers; ++l) {
     const DecLayerW& w = e->dec[l];
-    const GemmFold in0 = norm(w.ln0);
-    if (cache) {
-      RC(gemm(e, st, Gemm(PC_DEC_GEMM, EPI_STORE_F16, xin(), dm, dfold ? w.qkv_f : w.qkv, dm, sl.dqkv, 3 * I, M, 3 * I, dm).on(fam).with(in0)));
-      const AttnCachedArgs ca{sl.dqkv, 3 * I, cache->kv + (size_t)l * B * cache->P * 2 * I, cache->P, I, cache->pos, sl.dctx, I, e->lut_dec};
-      {
+    if (!cache && Ld == 1) {
+      // one decoder position: softmax over a single key is 1, so self-attention is exactly o(v(x)) — the q/k
+      // projections, scores and bias are dead (hf: modeling_t5.py:448-509 at L_d = 1; SURVEY.md K7)
+      // ... and o(v(x)) = (W_o W_v) x: one GEMM with the product matrix formed once at finalize
+      RC(resid(normed(w.ln0, Gemm(PC_DEC_GEMM, EPI_RESID_F32, ns.x(), dm, dfold ? w.ov_f : w.ov, dm, ns.hidden, dm, M, dm, dm))));
+    } else {
+      RC(gemm(e, st, normed(w.ln0, Gemm(PC_DEC_GEMM, EPI_STORE_F16, ns.x(), dm, dfold ? w.qkv_f : w.qkv, dm, sl.dqkv, 3 * I, M, 3 * I, dm))));
+      if (cache) {
+        const AttnCachedArgs ca{sl.dqkv, 3 * I, cache->kv + (size_t)l * B * cache->P * 2 * I, cache->P, I, cache->pos, sl.dctx, I, e->lut_dec};
         Bracket br(e, st, PC_DEC_ATTN, 4.0 * B * (double)cache->P * I, (double)B * cache->P * 2 * I * 2.0);
         if (e->opt.dec_cached_attn) {
           hipLaunchKernelGGL(attn_dec_cached_kernel, dim3(d.n_heads, B), dim3(256), attn_dec_lds(cache->P), st, ca);
@@ -977,34 +1015,28 @@ int run_decoder(rk_engine* e, Slot& sl, int Ld, const DecTree* tree = nullptr, c
                              AttnDecArgs{sl.dqkv, 3 * I, ca.cache, ca.cache + I, 2 * I, nullptr, sl.dctx, I, e->lut_dec, cache->P, 1, cache->P,
                                          cache->tree_keys, cache->tree_pos});
         }
+      } else {
+        launch_dec_attn(e, st, self_plan, AttnDecArgs{sl.dqkv, 3 * I, sl.dqkv + I, sl.dqkv + 2 * I, 3 * I, nullptr, sl.dctx, I, e->lut_dec, Ld, 1, Ld,
+                                                      tree ? tree->keys : nullptr, tree ? tree->pos : nullptr}, 4.0 * M * Ld * I, 0);
       }
-      RC(resid(Gemm(PC_DEC_GEMM, EPI_RESID_F32, sl.dctx, I, w.o, I, sl.dhidden, dm, M, dm, I)));
-    } else if (Ld == 1) {
-      // one decoder position: softmax over a single key is 1, so self-attention is exactly o(v(x)) — the q/k
-      // projections, scores and bias are dead (hf: modeling_t5.py:448-509 at L_d = 1; SURVEY.md K7)
-      // ... and o(v(x)) = (W_o W_v) x: one GEMM with the product matrix formed once at finalize
-      RC(resid(Gemm(PC_DEC_GEMM, EPI_RESID_F32, xin(), dm, dfold ? w.ov_f : w.ov, dm, sl.dhidden, dm, M, dm, dm).with(in0)));
-    } else {
-      RC(gemm(e, st, Gemm(PC_DEC_GEMM, EPI_STORE_F16, xin(), dm, dfold ? w.qkv_f : w.qkv, dm, sl.dqkv, 3 * I, M, 3 * I, dm).on(fam).with(in0)));
-      launch_dec_attn(e, st, self_plan, AttnDecArgs{sl.dqkv, 3 * I, sl.dqkv + I, sl.dqkv + 2 * I, 3 * I, nullptr, sl.dctx, I, e->lut_dec, Ld, 1, Ld,
-                                                    tree ? tree->keys : nullptr, tree ? tree->pos : nullptr}, 4.0 * M * Ld * I, 0);
-      RC(resid(Gemm(PC_DEC_GEMM, EPI_RESID_F32, sl.dctx, I, w.o, I, sl.dhidden, dm, M, dm, I)));
+      RC(resid(Gemm(PC_DEC_GEMM, EPI_RESID_F32, sl.dctx, I, w.o, I, ns.hidden, dm, M, dm, I)));
     }
-    const GemmFold in1 = norm(w.ln1);
-    if (!fuse) RC(gemm(e, st, Gemm(PC_DEC_GEMM, EPI_STORE_F16, xin(), dm, dfold ? w.cq_f : w.cq, dm, sl.dq, I, M, I, dm).on(fam).with(in1)));
+    // the cross-attention q projection: a GEMM of its own, or fused into launch_xattn's first kernel, which takes the same norm hooks
+    const Gemm cq = normed(w.ln1, Gemm(PC_DEC_GEMM, EPI_STORE_F16, ns.x(), dm, dfold ? w.cq_f : w.cq, dm, sl.dq, I, M, I, dm));
+    if (!fuse) RC(gemm(e, st, cq));
     if (!sl.have_cross_kv) {
       // in blocks of rows that fit the workspace
       const int blk = std::max(1, std::min(XA_MAX_ROWS, XA_MAX_CHUNKS / ((sl.maxL + 63) / 64)));
       for (int r0 = 0; r0 < M; r0 += blk) {
         const XAttnPlan xp = plan_xattn(e, fuse, std::min(blk, M - r0), sl.maxL, d.n_heads, dm);
-        RC(launch_xattn(e, st, sl, xp, l, Ld, r0, xin(), dfold ? w.cq_f : w.cq, in1, tree ? tree->seq : nullptr));
+        RC(launch_xattn(e, st, sl, xp, l, Ld, r0, cq.A, cq.W, cq.fold, tree ? tree->seq : nullptr));
       }
     } else {
       const half_t* kv = sl.cross_kv + (size_t)l * d.max_tokens * 2 * I;
       launch_dec_attn(e, st, cross_plan, AttnDecArgs{sl.dq, I, kv, kv + I, 2 * I, sl.d_seq_off, sl.dctx, I, nullptr, Ld, 0, sl.maxL},
                       4.0 * Ld * (double)sl.T * I, (double)sl.T * 2 * I * 2.0);
     }
-    RC(resid(Gemm(PC_DEC_GEMM, EPI_RESID_F32, sl.dctx, I, w.co, I, sl.dhidden, dm, M, dm, I)));
+    RC(resid(Gemm(PC_DEC_GEMM, EPI_RESID_F32, sl.dctx, I, w.co, I, ns.hidden, dm, M, dm, I)));
     {
       // ONE decoder position (pointwise yes_no, MonoT5), folded: FFN-in runs on the TILED kernels whatever the number of rows.  Its
       // 5632 output columns are 176 column blocks x (rows / 32) workgroups for the weight-streaming kernel - 1760 at the
@@ -1012,21 +1044,15 @@ int run_decoder(rk_engine* e, Slot& sl, int Ld, const DecTree* tree = nullptr, c
       // 0.28 ms per step, +0.9 % passages/s).  The family follows from the call shape (L_d == 1), never from the batch, so a
       // row's bits still do not depend on what shares its launch; the other projections of the layer (1024 columns: 80 tiles)
       // measured the same on either family and stay where they were.
+      // (Many rows, or a forced tile shape: the persistent ping-pong kernel takes its row factors ready-made - same block sums,
+      // same rk_row_factor, same bits as the fill-in kernels form in their epilogue.)
       const bool tiled_in = dfold && e->opt.dec_ffn_tiled && Ld == 1;
-      Gemm in = Gemm(PC_DEC_GEMM, d.gated_gelu ? EPI_GEGLU_F16 : EPI_RELU_F16, xin(), dm, dfold ? w.ffn_in_f : w.ffn_in, dm, sl.dffh, F, M,
-                     d.gated_gelu ? 2 * F : F, dm).on(tiled_in ? GEMM_TILED : fam);
-      GemmFold f = norm(w.ln2);
-      if (f.ssq_in && plan_gemm(e, in, st).pp2()) {
-        // (many rows, or a forced tile shape: the persistent ping-pong kernel takes its row factors ready-made - same block
-        // sums, same rk_row_factor, same bits as the fill-in kernels form in their epilogue)
-        rowscale(e, st, f.ssq_in, sl.drowscale, M, f.nb_in);
-        f = GemmFold(); f.rowscale = sl.drowscale;
-      }
-      RC(gemm(e, st, in.with(f)));
+      RC(gemm(e, st, ns.consumer(e, st, w.ln2, Gemm(PC_DEC_GEMM, d.gated_gelu ? EPI_GEGLU_F16 : EPI_RELU_F16, ns.x(), dm, dfold ? w.ffn_in_f : w.ffn_in, dm,
+                                                   sl.dffh, F, M, d.gated_gelu ? 2 * F : F, dm).on(tiled_in ? GEMM_TILED : fam), true)));
     }
     // (the tiled form for FFN-out - 80 tiles of 64x64 with 44 K steps each - took 9 us per layer off the serial profile and
     // nothing measurable off the pipeline: left on the weight-streaming kernel)
-    RC(resid(Gemm(PC_DEC_GEMM, EPI_RESID_F32, sl.dffh, F, w.ffn_out, F, sl.dhidden, dm, M, dm, F), l + 1 < d.n_dec_layers));
+    RC(resid(Gemm(PC_DEC_GEMM, EPI_RESID_F32, sl.dffh, F, w.ffn_out, F, ns.hidden, dm, M, dm, F), l + 1 < d.n_dec_layers));
   }
   HIPCHK(e, hipGetLastError());
   return RK_OK;
@@ -1061,18 +1087,31 @@ int sync_all(rk_engine* e) {
   return RK_OK;
 }
 
+// The blocking T5 entry points end here: the slot's decoder event, every stream drained.
+int finish_blocking(rk_engine* e, Slot& sl) {
+  int rc = mark_decoder_done(e, sl);
+  if (rc || (rc = sync_all(e))) return rc;
+  sl.dec_pending = false;
+  return RK_OK;
+}
+
+template <class T>
+int Grown<T>::reserve(rk_engine* e, size_t n, int* gen) {
+  if (n <= cap) return RK_OK;
+  int rc = sync_all(e);
+  if (rc) return rc;
+  if (p) HIPCHK(e, hipFree(p));
+  p = nullptr; cap = 0;
+  HIPCHK(e, hipMalloc((void**)&p, n * sizeof(T)));
+  cap = n;
+  if (gen) ++*gen;
+  return RK_OK;
+}
+
 int ensure_logits(rk_engine* e, size_t rows) {
   // fused qlm head: rows x ceil(vocab / 32) float2 block statistics, then rows floats of label logits (the [rows, vocab]
   // fp32 logits this buffer used to hold are never materialised)
-  const size_t need_elems = rows * (2 * ((size_t)(e->d.vocab + 31) / 32) + 1);
-  if (need_elems <= e->logits_cap) return RK_OK;
-  int rc = sync_all(e);
-  if (rc) return rc;
-  if (e->logits) HIPCHK(e, hipFree(e->logits));
-  e->logits = nullptr; e->logits_cap = 0;
-  HIPCHK(e, hipMalloc((void**)&e->logits, need_elems * sizeof(float)));
-  e->logits_cap = need_elems;
-  return RK_OK;
+  return e->logits.reserve(e, rows * (2 * ((size_t)(e->d.vocab + 31) / 32) + 1));
 }
 
 float head_scale(const rk_engine* e) {   // hf: modeling_t5.py:1044-1045 (scale_decoder_outputs)
@@ -1169,6 +1208,49 @@ int run_graphed(rk_engine* e, hipStream_t st, std::vector<int> key, F&& body) {
   return RK_OK;
 }
 
+// The cached greedy loop of rk_t5_generate / rk_llama_generate.  `step` (one graph under `key`) decodes one position of every
+// sequence on st and leaves in *d_word the step at which the last sequence finished (0: none yet).  `forced` steps (a prefix) run
+// before the first step that yields an output column; columns below `first_col` were produced, and *d_word set, before the call
+// (the Llama prefill's).  The host reads back one word per column into a two-entry pinned ring and waits for the PREVIOUS column's
+// while the next step is queued: one step stays ahead, and a step after the last changes nothing (the advance kernels).  Returns
+// d_out's [n_seq][max_new] tokens and the final word.  Nothing is allocated here: the ring is the caller's to ensure
+// (ensure_decode_ring, with its other memory, before the chain starts).
+int ensure_decode_ring(rk_engine* e) {
+  if (e->gen_pin) return RK_OK;
+  HIPCHK(e, hipHostMalloc((void**)&e->gen_pin, 16 * sizeof(int), hipHostMallocDefault));
+  for (hipEvent_t& ev : e->ev_gen) HIPCHK(e, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+  return RK_OK;
+}
+template <class F>
+int decode_cached(rk_engine* e, hipStream_t st, const std::vector<int>& key, F&& step, int forced, int first_col, int n_seq, int max_new,
+                  const int* d_word, const int* d_out, int32_t* out_tokens, int32_t* out_steps) {
+  int* pin = e->gen_pin;
+  auto request = [&](int c) -> int {                                       // column c's finished-step word, read back
+    HIPCHK(e, hipMemcpyAsync(pin + (c & 1), d_word, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(e, hipEventRecord(e->ev_gen[c & 1], st));
+    return RK_OK;
+  };
+  int rc = RK_OK;
+  if (first_col > 0) RC(request(first_col - 1));
+  bool stop = false;
+  for (int c = first_col - forced; c < max_new && !stop; ++c) {            // this step's column (< 0: a forced step)
+    RC(run_graphed(e, st, key, step));
+    if (c >= 0) RC(request(c));
+    if (c >= 1) {                                                          // the previous column's word, while this step runs
+      HIPCHK(e, hipEventSynchronize(e->ev_gen[(c - 1) & 1]));
+      stop = pin[(c - 1) & 1] != 0;
+    }
+  }
+  std::vector<int> res((size_t)n_seq * max_new + 1);
+  HIPCHK(e, hipMemcpyAsync(res.data(), d_out, (size_t)n_seq * max_new * sizeof(int), hipMemcpyDeviceToHost, st));
+  HIPCHK(e, hipMemcpyAsync(res.data() + (size_t)n_seq * max_new, d_word, sizeof(int), hipMemcpyDeviceToHost, st));
+  HIPCHK(e, hipStreamSynchronize(st));
+  HIPCHK(e, hipGetLastError());
+  memcpy(out_tokens, res.data(), (size_t)n_seq * max_new * sizeof(int));
+  if (out_steps) *out_steps = res[(size_t)n_seq * max_new];
+  return RK_OK;
+}
+
 int score_slot(rk_engine* e, int slot, const int32_t* dec_prefix, int dec_len, const int32_t* out_token_ids, int n_out) {
   if (slot < 0 || slot >= RK_SLOTS) return fail(e, RK_ERR_INVALID, "slot %d out of range", slot);
   int rc = set_device(e);
@@ -1193,7 +1275,7 @@ int score_slot(rk_engine* e, int slot, const int32_t* dec_prefix, int dec_len, c
   rc = run_graphed(e, sd, {0, slot, sl.n_seq, dec_len, sl.have_cross_kv ? sl.maxL : (sl.maxL + 63) / 64, (int)sl.have_cross_kv, n_out, (int)skip_dec}, [&]() -> int {
     int r = RK_OK;
     if (!skip_dec && (r = run_decoder(e, sl, dec_len))) return r;
-    rmsnorm(e, sd, sl.dhidden, e->dec_final_ln, sl.dlast, sl.d_last_rows, sl.n_seq, head_scale(e));
+    rmsnorm(e, sd, sl.dec.hidden, e->dec_final_ln, sl.dlast, sl.d_last_rows, sl.n_seq, head_scale(e));
     Bracket br(e, sd, PC_HEAD, 2.0 * sl.n_seq * n_out * e->d.d_model, 0);
     hipLaunchKernelGGL(head_rows_kernel, dim3((sl.n_seq * n_out + 3) / 4), dim3(256), 0, sd, sl.dlast, e->lm_head,
                        sl.d_out_ids, sl.d_scores, sl.n_seq, n_out, e->d.d_model);
@@ -1379,14 +1461,6 @@ void rk_engine_destroy(rk_engine* e) {
   for (auto& kv : e->graphs) if (kv.second.exec) hipGraphExecDestroy(kv.second.exec);
   e->graphs.clear();
   for (void* p : e->allocs) hipFree(p);
-  if (e->logits) hipFree(e->logits);
-  if (e->amax_val) hipFree(e->amax_val);
-  if (e->amax_idx) hipFree(e->amax_idx);
-  if (e->kv_cache) hipFree(e->kv_cache);
-  if (e->lkv) hipFree(e->lkv);
-  if (e->lpart) hipFree(e->lpart);
-  if (e->lints) hipFree(e->lints);
-  if (e->gen_buf) hipFree(e->gen_buf);
   if (e->gen_pin) hipHostFree(e->gen_pin);
   for (hipEvent_t ev : e->ev_gen) if (ev) hipEventDestroy(ev);
   for (auto& w : e->sk_ws) { if (w.slabs) hipFree(w.slabs); if (w.cnt) hipFree(w.cnt); }
@@ -1404,7 +1478,7 @@ void rk_engine_destroy(rk_engine* e) {
     if (sl.se) hipStreamDestroy(sl.se);
     if (sl.sd) hipStreamDestroy(sl.sd);
   }
-  delete e;
+  delete e;   // (frees the Grown buffers)
 }
 
 int rk_engine_load_tensor(rk_engine* e, const char* hf_name, const void* data, int dtype, const int64_t* shape, int ndim) {
@@ -1502,6 +1576,14 @@ int rk_engine_finalize(rk_engine* e) {
     }
     return v;
   };
+  // folded RMSNorm: W'[n][k] = fp16(W[n][k] * ln[k])  (the norm weight multiplies the GEMM's input channels)
+  auto folded = [&](const std::vector<half_t>& wm, const std::vector<float>& ln) {
+    std::vector<half_t> v(wm.size());
+    const size_t rows = wm.size() / dm;
+    for (size_t r = 0; r < rows; ++r)
+      for (int k = 0; k < dm; ++k) v[r * dm + k] = (half_t)((float)wm[r * dm + k] * ln[k]);
+    return v;
+  };
   RC(up_h(&e->emb, H("shared.weight")));
   if (d.tied_head) e->lm_head = e->emb; else RC(up_h(&e->lm_head, H("lm_head.weight")));
   RC(up_f(&e->enc_final_ln, Fv("encoder.final_layer_norm.weight")));
@@ -1525,14 +1607,6 @@ int rk_engine_finalize(rk_engine* e) {
     RC(up_h(&w.ffn_out, H(p + ".1.DenseReluDense.wo.weight")));
     RC(up_f(&w.ln0, Fv(p + ".0.layer_norm.weight")));
     RC(up_f(&w.ln1, Fv(p + ".1.layer_norm.weight")));
-    // folded RMSNorm: W'[n][k] = fp16(W[n][k] * ln[k])  (the norm weight multiplies the GEMM's input channels)
-    auto folded = [&](const std::vector<half_t>& wm, const std::vector<float>& ln) {
-      std::vector<half_t> v(wm.size());
-      const size_t rows = wm.size() / dm;
-      for (size_t r = 0; r < rows; ++r)
-        for (int k = 0; k < dm; ++k) v[r * dm + k] = (half_t)((float)wm[r * dm + k] * ln[k]);
-      return v;
-    };
     RC(up_h(&w.qkv_f, folded(cat3(p + ".0.SelfAttention."), Fv(p + ".0.layer_norm.weight"))));
     RC(up_h(&w.ffn_in_f, folded(ffn_in(p + ".1.DenseReluDense"), Fv(p + ".1.layer_norm.weight"))));
   }
@@ -1559,18 +1633,9 @@ int rk_engine_finalize(rk_engine* e) {
     RC(up_f(&w.ln0, Fv(p + ".0.layer_norm.weight")));
     RC(up_f(&w.ln1, Fv(p + ".1.layer_norm.weight")));
     RC(up_f(&w.ln2, Fv(p + ".2.layer_norm.weight")));
-    {
-      auto folded = [&](const std::vector<half_t>& wm, const std::vector<float>& ln) {
-        std::vector<half_t> v(wm.size());
-        const size_t rows = wm.size() / dm;
-        for (size_t r = 0; r < rows; ++r)
-          for (int k = 0; k < dm; ++k) v[r * dm + k] = (half_t)((float)wm[r * dm + k] * ln[k]);
-        return v;
-      };
-      RC(up_h(&w.qkv_f, folded(cat3(p + ".0.SelfAttention."), Fv(p + ".0.layer_norm.weight"))));
-      RC(up_h(&w.cq_f, folded(H(p + ".1.EncDecAttention.q.weight"), Fv(p + ".1.layer_norm.weight"))));
-      RC(up_h(&w.ffn_in_f, folded(ffn_in(p + ".2.DenseReluDense"), Fv(p + ".2.layer_norm.weight"))));
-    }
+    RC(up_h(&w.qkv_f, folded(cat3(p + ".0.SelfAttention."), Fv(p + ".0.layer_norm.weight"))));
+    RC(up_h(&w.cq_f, folded(H(p + ".1.EncDecAttention.q.weight"), Fv(p + ".1.layer_norm.weight"))));
+    RC(up_h(&w.ffn_in_f, folded(ffn_in(p + ".2.DenseReluDense"), Fv(p + ".2.layer_norm.weight"))));
     for (const char* m : {"k", "v"}) { const auto& s = H(p + ".1.EncDecAttention." + m + ".weight"); ckv.insert(ckv.end(), s.begin(), s.end()); }
   }
   RC(up_h(&e->cross_kv_w, ckv));
@@ -1603,20 +1668,20 @@ int rk_engine_finalize(rk_engine* e) {
   const size_t Tc = d.max_tokens, Bc = d.max_seqs, Mc = (size_t)d.max_seqs * d.max_dec_len;
   e->scores_cap = Bc * 64;
   for (Slot& sl : e->slots) {
-    RC(dalloc(e, &sl.hidden, Tc * dm)); RC(dalloc(e, &sl.xn, Tc * dm)); RC(dalloc(e, &sl.qkv, Tc * 3 * I));
+    RC(dalloc(e, &sl.enc.hidden, Tc * dm)); RC(dalloc(e, &sl.enc.xn, Tc * dm)); RC(dalloc(e, &sl.qkv, Tc * 3 * I));
     RC(dalloc(e, &sl.ctx, Tc * I)); RC(dalloc(e, &sl.ffh, Tc * F)); RC(dalloc(e, &sl.enc_out, Tc * dm));
-    RC(dalloc(e, &sl.xraw, Tc * dm)); RC(dalloc(e, &sl.ssq, Tc * ((dm + 63) / 64))); RC(dalloc(e, &sl.rowscale, Tc + 512));   // padded: the ping-pong GEMM reads the row factors of a whole 256-row tile
-    HIPCHK(e, hipMemset(sl.rowscale, 0, (Tc + 512) * sizeof(float)));
+    RC(dalloc(e, &sl.enc.xraw[0], Tc * dm)); RC(dalloc(e, &sl.enc.ssq[0], Tc * ((dm + 63) / 64))); RC(dalloc(e, &sl.enc.factors, Tc + 512));   // padded: the ping-pong GEMM reads the row factors of a whole 256-row tile
+    HIPCHK(e, hipMemset(sl.enc.factors, 0, (Tc + 512) * sizeof(float)));
     RC(dalloc(e, &sl.d_tokens, Tc)); RC(dalloc(e, &sl.d_seq_off, Bc + 1));
     RC(dalloc(e, &sl.cross_kv, (size_t)d.n_dec_layers * Tc * 2 * I));
     RC(dalloc(e, &sl.d_dec_ids, Mc)); RC(dalloc(e, &sl.d_last_rows, Bc)); RC(dalloc(e, &sl.d_out_ids, 8192));
     RC(dalloc(e, &sl.d_labels, (size_t)d.max_dec_len)); RC(dalloc(e, &sl.d_argmax, Bc));
     RC(dalloc(e, &sl.d_row_seq, Mc)); RC(dalloc(e, &sl.d_tree_keys, Mc * (size_t)d.max_dec_len)); RC(dalloc(e, &sl.d_tree_pos, Mc));
-    RC(dalloc(e, &sl.dhidden, Mc * dm)); RC(dalloc(e, &sl.dxn, Mc * dm)); RC(dalloc(e, &sl.dqkv, Mc * 3 * I));
+    RC(dalloc(e, &sl.dec.hidden, Mc * dm)); RC(dalloc(e, &sl.dec.xn, Mc * dm)); RC(dalloc(e, &sl.dqkv, Mc * 3 * I));
     RC(dalloc(e, &sl.dctx, Mc * I)); RC(dalloc(e, &sl.dq, Mc * I)); RC(dalloc(e, &sl.dffh, Mc * F));
     RC(dalloc(e, &sl.dlast, Bc * dm));
-    for (int i = 0; i < 2; ++i) { RC(dalloc(e, &sl.dxraw[i], Mc * dm)); RC(dalloc(e, &sl.dssq[i], Mc * ((dm + 31) / 32))); RC(dalloc(e, &sl.dssq_few[i], (size_t)GEMV_MAX_ROWS * e->n_cu)); }
-    RC(dalloc(e, &sl.drowscale, Mc));
+    for (int i = 0; i < 2; ++i) { RC(dalloc(e, &sl.dec.xraw[i], Mc * dm)); RC(dalloc(e, &sl.dec.ssq[i], Mc * ((dm + 31) / 32))); RC(dalloc(e, &sl.dssq_few[i], (size_t)GEMV_MAX_ROWS * e->n_cu)); }
+    RC(dalloc(e, &sl.dec.factors, Mc));
     RC(dalloc(e, &sl.xqk, (size_t)XA_MAX_ROWS * d.n_heads * dm)); RC(dalloc(e, &sl.xctx, (size_t)XA_MAX_ROWS * d.n_heads * dm));
     RC(dalloc(e, &sl.xpart, (size_t)XA_MAX_CHUNKS * d.n_heads * dm)); RC(dalloc(e, &sl.xstat, (size_t)XA_MAX_CHUNKS * d.n_heads * 2));
     RC(dalloc(e, &sl.d_scores, e->scores_cap));
@@ -1706,16 +1771,14 @@ int rk_t5_qlm(rk_engine* e, const int32_t* tokens, const int32_t* seq_offsets, i
   if ((rc = ensure_logits(e, M))) return rc;
   if ((rc = encoder_then_handoff(e, sl, n_labels))) return rc;
   if ((rc = run_decoder(e, sl, n_labels))) return rc;
-  rmsnorm(e, sd, sl.dhidden, e->dec_final_ln, sl.dxn, nullptr, M, head_scale(e));
+  rmsnorm(e, sd, sl.dec.hidden, e->dec_final_ln, sl.dec.xn, nullptr, M, head_scale(e));
   // head GEMM with the log-sum-exp fused into its epilogue: per row and 32-column block (max, sum exp) + the label's logit
   const int nblk = (e->d.vocab + 31) / 32;
-  e->lse_labels = sl.d_labels; e->lse_npos = n_labels; e->lse_xlab = e->logits + (size_t)M * nblk * 2;
-  RC(gemm(e, sd, Gemm(PC_HEAD, EPI_LSE_F32, sl.dxn, e->d.d_model, e->lm_head, e->d.d_model, e->logits, nblk, M, e->d.vocab, e->d.d_model)));
-  hipLaunchKernelGGL(qlm_lse_kernel, dim3(n_seq), dim3(256), 0, sd, (const float2*)e->logits, nblk, e->lse_xlab, n_labels, sl.d_scores);
+  e->lse_labels = sl.d_labels; e->lse_npos = n_labels; e->lse_xlab = e->logits.p + (size_t)M * nblk * 2;
+  RC(gemm(e, sd, Gemm(PC_HEAD, EPI_LSE_F32, sl.dec.xn, e->d.d_model, e->lm_head, e->d.d_model, e->logits.p, nblk, M, e->d.vocab, e->d.d_model)));
+  hipLaunchKernelGGL(qlm_lse_kernel, dim3(n_seq), dim3(256), 0, sd, (const float2*)e->logits.p, nblk, e->lse_xlab, n_labels, sl.d_scores);
   HIPCHK(e, hipMemcpyAsync(sl.h_scores, sl.d_scores, (size_t)n_seq * sizeof(float), hipMemcpyDeviceToHost, sd));
-  if ((rc = mark_decoder_done(e, sl))) return rc;
-  if ((rc = sync_all(e))) return rc;
-  sl.dec_pending = false;
+  RC(finish_blocking(e, sl));
   HIPCHK(e, hipGetLastError());
   memcpy(out_scores, sl.h_scores, (size_t)n_seq * sizeof(float));
   return RK_OK;
@@ -1724,24 +1787,29 @@ int rk_t5_qlm(rk_engine* e, const int32_t* tokens, const int32_t* seq_offsets, i
 // Greedy head: full-vocabulary logits of `rows` final-normed rows (x: [rows, d_model] fp16) reduced to their first arg-max
 // WITHOUT writing the logits: the weight-streaming GEMM keeps per 32-column block the maximum and its first column
 // (gemm.h: EPI_ARGMAX_F32), argmax_blocks_kernel picks per row.  hf: modeling_t5.py:1044-1047 + torch.argmax.
-static int ensure_amax(rk_engine* e, size_t rows, int vocab) {
-  if (rows <= e->amax_rows) return RK_OK;
-  int rc = sync_all(e);
-  if (rc) return rc;
-  if (e->amax_val) HIPCHK(e, hipFree(e->amax_val));
-  if (e->amax_idx) HIPCHK(e, hipFree(e->amax_idx));
-  e->amax_val = nullptr; e->amax_idx = nullptr; e->amax_rows = 0;
-  const size_t nblk = (size_t)(vocab + 31) / 32;
-  HIPCHK(e, hipMalloc((void**)&e->amax_val, rows * nblk * sizeof(float)));
-  HIPCHK(e, hipMalloc((void**)&e->amax_idx, rows * nblk * sizeof(int)));
-  e->amax_rows = rows;
-  return RK_OK;
+// (amax_gen counts the moves of the two buffers: part of the key of every graph that holds a head)
+static int ensure_amax(rk_engine* e, size_t rows) {
+  const size_t n = rows * ((size_t)(e->d.vocab + 31) / 32);
+  const int rc = e->amax_val.reserve(e, n, &e->amax_gen);
+  return rc ? rc : e->amax_idx.reserve(e, n, &e->amax_gen);
 }
 static int head_argmax(rk_engine* e, hipStream_t st, const half_t* x, int rows, int d_model, int vocab, int* d_out) {
   const int nblk = (vocab + 31) / 32;
-  const int rc = gemm(e, st, Gemm(PC_HEAD, EPI_ARGMAX_F32, x, d_model, e->lm_head, d_model, e->amax_val, nblk, rows, vocab, d_model).on(GEMM_STREAM));
-  if (rc == RK_OK) hipLaunchKernelGGL(argmax_blocks_kernel, dim3(rows), dim3(256), 0, st, e->amax_val, e->amax_idx, nblk, d_out);
+  const int rc = gemm(e, st, Gemm(PC_HEAD, EPI_ARGMAX_F32, x, d_model, e->lm_head, d_model, e->amax_val.p, nblk, rows, vocab, d_model).on(GEMM_STREAM));
+  if (rc == RK_OK) hipLaunchKernelGGL(argmax_blocks_kernel, dim3(rows), dim3(256), 0, st, e->amax_val.p, e->amax_idx.p, nblk, d_out);
   return rc;
+}
+// T5: final norm of `rows` decoder rows (row_map, or the first rows) -> arg-max head -> sl.d_argmax
+static int final_argmax(rk_engine* e, hipStream_t st, Slot& sl, const int* row_map, int rows) {
+  rmsnorm(e, st, sl.dec.hidden, e->dec_final_ln, sl.dlast, row_map, rows, head_scale(e));
+  return head_argmax(e, st, sl.dlast, rows, e->d.d_model, e->d.vocab, sl.d_argmax);
+}
+// the first n arg-max ints of sl.d_argmax, read back on st (blocking)
+static int read_argmax(rk_engine* e, hipStream_t st, const Slot& sl, int* out, int n) {
+  HIPCHK(e, hipMemcpyAsync(out, sl.d_argmax, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, st));
+  HIPCHK(e, hipStreamSynchronize(st));
+  HIPCHK(e, hipGetLastError());
+  return RK_OK;
 }
 
 // One greedy step over the staged batch (encoder done): decoder over rows[b] (Ld ids per sequence), final norm of the last
@@ -1755,18 +1823,13 @@ static int greedy_step(rk_engine* e, Slot& sl, const std::vector<std::vector<int
   HIPCHK(e, hipMemcpy(sl.d_dec_ids, flat.data(), flat.size() * sizeof(int), hipMemcpyHostToDevice));
   HIPCHK(e, hipMemcpy(sl.d_last_rows, rowmap.data(), n_seq * sizeof(int), hipMemcpyHostToDevice));
   sl.cache_dec.clear(); sl.cache_rows.clear(); ++sl.dec_epoch;
-  int rc = run_graphed(e, sd, {1, 0, n_seq, Ld, sl.have_cross_kv ? sl.maxL : (sl.maxL + 63) / 64, (int)sl.have_cross_kv, (int)e->amax_rows}, [&]() -> int {
-    int r = run_decoder(e, sl, Ld);
-    if (r) return r;
-    rmsnorm(e, sd, sl.dhidden, e->dec_final_ln, sl.dlast, sl.d_last_rows, n_seq, head_scale(e));
-    return head_argmax(e, sd, sl.dlast, n_seq, e->d.d_model, e->d.vocab, sl.d_argmax);
+  int rc = run_graphed(e, sd, {1, 0, n_seq, Ld, sl.have_cross_kv ? sl.maxL : (sl.maxL + 63) / 64, (int)sl.have_cross_kv, e->amax_gen}, [&]() -> int {
+    const int r = run_decoder(e, sl, Ld);
+    return r ? r : final_argmax(e, sd, sl, sl.d_last_rows, n_seq);
   });
   if (rc) return rc;
   amax.resize(n_seq);
-  HIPCHK(e, hipMemcpyAsync(amax.data(), sl.d_argmax, n_seq * sizeof(int), hipMemcpyDeviceToHost, sd));
-  HIPCHK(e, hipStreamSynchronize(sd));
-  HIPCHK(e, hipGetLastError());
-  return RK_OK;
+  return read_argmax(e, sd, sl, amax.data(), n_seq);
 }
 
 int rk_t5_greedy(rk_engine* e, const int32_t* tokens, const int32_t* seq_offsets, int n_seq, const int32_t* dec_prefix,
@@ -1777,9 +1840,8 @@ int rk_t5_greedy(rk_engine* e, const int32_t* tokens, const int32_t* seq_offsets
   if (!dec_prefix || dec_len <= 0 || max_new <= 0 || dec_len + max_new - 1 > e->d.max_dec_len)
     return fail(e, RK_ERR_CAPACITY, "dec_len %d + max_new %d exceeds max_dec_len %d", dec_len, max_new, e->d.max_dec_len);
   if ((rc = check_ids(e, dec_prefix, dec_len, "decoder"))) return rc;
-  if ((rc = ensure_amax(e, (size_t)n_seq, e->d.vocab))) return rc;
+  if ((rc = ensure_amax(e, (size_t)n_seq))) return rc;
   if ((rc = encoder_then_handoff(e, sl, dec_len + max_new - 1))) return rc;
-  hipStream_t sd = dec_stream(e, sl);
   // Per-row decoder ids grow by one token per step; the tiny decoder is recomputed over the whole prefix each
   // step (cross K/V are reused), which equals HF's KV-cached greedy loop (hf: generation/utils.py:2868-2935).
   std::vector<std::vector<int>> rows(n_seq, std::vector<int>(dec_prefix, dec_prefix + dec_len));
@@ -1801,35 +1863,20 @@ int rk_t5_greedy(rk_engine* e, const int32_t* tokens, const int32_t* seq_offsets
     }
     if (all_done) break;
   }
-  if ((rc = mark_decoder_done(e, sl))) return rc;
-  if ((rc = sync_all(e))) return rc;
-  sl.dec_pending = false;
+  if ((rc = finish_blocking(e, sl))) return rc;
   if (out_steps) *out_steps = steps;
   return RK_OK;
 }
 
-// rk_t5_generate's device memory: the K / V cache for n_seq sequences of P positions (grown like ensure_amax, between calls only -
-// never inside a capture; a move changes kv_gen, which is part of the step graph's key), the per-call int block, the pinned
-// read-back words and their events.
+// rk_t5_generate's device memory, grown between calls only: the K / V cache for n_seq sequences of P positions (a move changes
+// kv_gen, which is part of the step graph's key) and the per-call int block.
 static int ensure_gen(rk_engine* e, int n_seq, int P) {
-  const size_t kv = (size_t)e->d.n_dec_layers * n_seq * P * 2 * e->inner;
-  if (kv > e->kv_cap) {
-    int rc = sync_all(e);
-    if (rc) return rc;
-    if (e->kv_cache) HIPCHK(e, hipFree(e->kv_cache));
-    e->kv_cache = nullptr; e->kv_cap = 0;
-    HIPCHK(e, hipMalloc((void**)&e->kv_cache, kv * sizeof(half_t)));
-    e->kv_cap = kv; ++e->kv_gen;
-  }
-  if (!e->gen_buf) {
-    // state, prefix, finished rows, tree positions, output [n_seq][max_new], tree keys [n_seq][P]: at most this many ints
-    const size_t L = (size_t)e->d.max_dec_len, S = (size_t)e->d.max_seqs;
-    e->gen_cap = 8 + L + 2 * S + S * L + S * (L + 1);
-    HIPCHK(e, hipMalloc((void**)&e->gen_buf, e->gen_cap * sizeof(int)));
-    HIPCHK(e, hipHostMalloc((void**)&e->gen_pin, 16 * sizeof(int), hipHostMallocDefault));
-    for (hipEvent_t& ev : e->ev_gen) HIPCHK(e, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-  }
-  return RK_OK;
+  // state, prefix, finished rows, tree positions, output [n_seq][max_new], tree keys [n_seq][P]: at most this many ints
+  const size_t L = (size_t)e->d.max_dec_len, S = (size_t)e->d.max_seqs;
+  int rc = RK_OK;
+  RC(e->kv_cache.reserve(e, (size_t)e->d.n_dec_layers * n_seq * P * 2 * e->inner, &e->kv_gen));
+  RC(e->gen_buf.reserve(e, 8 + L + 2 * S + S * L + S * (L + 1)));
+  return ensure_decode_ring(e);
 }
 
 // Greedy decoding with a self-attention K / V cache: one decoder row per sequence and step (run_decoder's incremental pass), the
@@ -1848,7 +1895,7 @@ int rk_t5_generate(rk_engine* e, const int32_t* tokens, const int32_t* seq_offse
   if (!out_tokens) return fail(e, RK_ERR_INVALID, "null output");
   if ((rc = check_ids(e, dec_prefix, dec_len, "decoder"))) return rc;
   const int P = dec_len + max_new;                                       // cache positions per sequence (the last: a step past the end)
-  if ((rc = ensure_amax(e, (size_t)n_seq, e->d.vocab))) return rc;
+  if ((rc = ensure_amax(e, (size_t)n_seq))) return rc;
   if ((rc = ensure_gen(e, n_seq, P))) return rc;
   if ((rc = encoder_then_handoff(e, sl, 1, true))) return rc;
   hipStream_t sd = dec_stream(e, sl);
@@ -1862,47 +1909,24 @@ int rk_t5_generate(rk_engine* e, const int32_t* tokens, const int32_t* seq_offse
   for (int b = 0; b < n_seq; ++b)
     for (int j = 0; j < P; ++j) init[o_keys + (size_t)b * P + j] = b * P + j;
   std::vector<int> ids0(n_seq, dec_prefix[0]);
-  int* g = e->gen_buf;
+  int* g = e->gen_buf.p;
   HIPCHK(e, hipStreamSynchronize(sd));
   HIPCHK(e, hipMemcpy(g, init.data(), n_ints * sizeof(int), hipMemcpyHostToDevice));
   HIPCHK(e, hipMemcpy(sl.d_dec_ids, ids0.data(), n_seq * sizeof(int), hipMemcpyHostToDevice));
   sl.cache_dec.clear(); ++sl.dec_epoch;
-  const DecCache kc{e->kv_cache, P, g, g + o_keys, g + o_tpos};
+  const DecCache kc{e->kv_cache.p, P, g, g + o_keys, g + o_tpos};
   auto step = [&]() -> int {
     int r = run_decoder(e, sl, 1, nullptr, &kc);
-    if (r) return r;
-    rmsnorm(e, sd, sl.dhidden, e->dec_final_ln, sl.dlast, nullptr, n_seq, head_scale(e));
-    if ((r = head_argmax(e, sd, sl.dlast, n_seq, e->d.d_model, e->d.vocab, sl.d_argmax))) return r;
+    if (r || (r = final_argmax(e, sd, sl, nullptr, n_seq))) return r;
     Bracket br(e, sd, PC_OTHER, 0, 0);
     hipLaunchKernelGGL(greedy_advance_kernel, dim3(1), dim3(256), 0, sd, sl.d_argmax, g, g + o_pre, g + o_done, g + o_out, sl.d_dec_ids,
                        n_seq, dec_len, max_new);
     return RK_OK;
   };
-  const std::vector<int> key{3, 0, n_seq, (sl.maxL + 63) / 64, dec_len, max_new, (int)e->amax_rows, e->kv_gen};
-  const int total = dec_len - 1 + max_new;                               // forced prefix steps + one step per new column
-  int* pin = e->gen_pin;
-  bool stop = false;
-  for (int s = 0; s < total && !stop; ++s) {
-    if ((rc = run_graphed(e, sd, key, step))) return rc;
-    if (s >= dec_len - 1) {                                              // a column step: its finished-step word, read back
-      HIPCHK(e, hipMemcpyAsync(pin + (s & 1), g + 1, sizeof(int), hipMemcpyDeviceToHost, sd));
-      HIPCHK(e, hipEventRecord(e->ev_gen[s & 1], sd));
-    }
-    if (s - 1 >= dec_len - 1) {                                          // the previous step's word, while this step runs
-      HIPCHK(e, hipEventSynchronize(e->ev_gen[(s - 1) & 1]));
-      stop = pin[(s - 1) & 1] != 0;
-    }
-  }
-  std::vector<int> res((size_t)n_seq * max_new + 1);
-  HIPCHK(e, hipMemcpyAsync(res.data(), g + o_out, (size_t)n_seq * max_new * sizeof(int), hipMemcpyDeviceToHost, sd));
-  HIPCHK(e, hipMemcpyAsync(res.data() + (size_t)n_seq * max_new, g + 1, sizeof(int), hipMemcpyDeviceToHost, sd));
-  if ((rc = mark_decoder_done(e, sl))) return rc;
-  if ((rc = sync_all(e))) return rc;
-  sl.dec_pending = false;
-  HIPCHK(e, hipGetLastError());
-  memcpy(out_tokens, res.data(), (size_t)n_seq * max_new * sizeof(int));
-  if (out_steps) *out_steps = res[(size_t)n_seq * max_new];
-  return RK_OK;
+  const std::vector<int> key{3, 0, n_seq, (sl.maxL + 63) / 64, dec_len, max_new, e->amax_gen, e->kv_gen};
+  // dec_len - 1 forced prefix steps, then one step per new column
+  if ((rc = decode_cached(e, sd, key, step, dec_len - 1, 0, n_seq, max_new, g + 1, g + o_out, out_tokens, out_steps))) return rc;
+  return finish_blocking(e, sl);
 }
 
 // Two greedy tokens in ONE decoder pass (the setwise `generation` compare: ref llmrankers/setwise.py:113-121 runs
@@ -1927,7 +1951,7 @@ int rk_t5_greedy2(rk_engine* e, const int32_t* tokens, const int32_t* seq_offset
   if ((rc = rk_t5_stage(e, tokens, seq_offsets, n_seq))) return rc;
   Slot& sl = e->slots[0];
   if ((rc = check_ids(e, dec_prefix, dec_len, "decoder"))) return rc;
-  if ((rc = ensure_amax(e, (size_t)R, e->d.vocab))) return rc;
+  if ((rc = ensure_amax(e, (size_t)R))) return rc;
   if ((rc = encoder_then_handoff(e, sl, Ld))) return rc;
   hipStream_t sd = dec_stream(e, sl);
   // row layout of prompt b: [prefix position 0 .. dec_len-1][candidate 0 .. n_cand-1 at position dec_len]
@@ -1966,16 +1990,11 @@ int rk_t5_greedy2(rk_engine* e, const int32_t* tokens, const int32_t* seq_offset
     sl.g2_epoch = ++sl.dec_epoch;
   }
   const DecTree tree{(int)M, sl.d_tree_keys, sl.d_tree_pos, sl.d_row_seq};
-  rc = run_graphed(e, sd, {2, 0, n_seq, Ld, (sl.maxL + 63) / 64, n_cand, (int)e->amax_rows}, [&]() -> int {
-    int r = run_decoder(e, sl, Ld, &tree);
-    if (r) return r;
-    rmsnorm(e, sd, sl.dhidden, e->dec_final_ln, sl.dlast, sl.d_last_rows, (int)R, head_scale(e));
-    return head_argmax(e, sd, sl.dlast, (int)R, e->d.d_model, e->d.vocab, sl.d_argmax);
+  rc = run_graphed(e, sd, {2, 0, n_seq, Ld, (sl.maxL + 63) / 64, n_cand, e->amax_gen}, [&]() -> int {
+    const int r = run_decoder(e, sl, Ld, &tree);
+    return r ? r : final_argmax(e, sd, sl, sl.d_last_rows, (int)R);
   });
-  if (rc) return rc;
-  HIPCHK(e, hipMemcpyAsync(amax.data(), sl.d_argmax, (size_t)R * sizeof(int), hipMemcpyDeviceToHost, sd));
-  HIPCHK(e, hipStreamSynchronize(sd));
-  HIPCHK(e, hipGetLastError());
+  if (rc || (rc = read_argmax(e, sd, sl, amax.data(), (int)R))) return rc;
   bool all_done = true, miss = false;
   for (int b = 0; b < n_seq; ++b) {
     const int t1 = amax[b];
@@ -1997,9 +2016,7 @@ int rk_t5_greedy2(rk_engine* e, const int32_t* tokens, const int32_t* seq_offset
     for (int b = 0; b < n_seq; ++b)
       if (out_tokens[b * 2] != eos_id) out_tokens[b * 2 + 1] = a2[b];
   }
-  if ((rc = mark_decoder_done(e, sl))) return rc;
-  if ((rc = sync_all(e))) return rc;
-  sl.dec_pending = false;
+  if ((rc = finish_blocking(e, sl))) return rc;
   if (out_steps) *out_steps = all_done ? 1 : 2;
   return RK_OK;
 }
@@ -2102,8 +2119,8 @@ static int llama_finalize(rk_engine* e) {
   }
   const size_t Tc = l.max_tokens, Bc = l.max_seqs;
   Slot& sl = e->slots[0];
-  RC(dalloc(e, &sl.hidden, Tc * dm)); RC(dalloc(e, &sl.xraw, Tc * dm)); RC(dalloc(e, &sl.ssq, Tc * ((dm + 63) / 64)));
-  RC(dalloc(e, &sl.rowscale, Tc + 512)); HIPCHK(e, hipMemset(sl.rowscale, 0, (Tc + 512) * sizeof(float)));
+  RC(dalloc(e, &sl.enc.hidden, Tc * dm)); RC(dalloc(e, &sl.enc.xraw[0], Tc * dm)); RC(dalloc(e, &sl.enc.ssq[0], Tc * ((dm + 63) / 64)));
+  RC(dalloc(e, &sl.enc.factors, Tc + 512)); HIPCHK(e, hipMemset(sl.enc.factors, 0, (Tc + 512) * sizeof(float)));
   RC(dalloc(e, &sl.qkv, Tc * (Q + 2 * KV))); RC(dalloc(e, &sl.ctx, Tc * Q)); RC(dalloc(e, &sl.ffh, Tc * F));
   RC(dalloc(e, &sl.d_tokens, Tc)); RC(dalloc(e, &e->d_pos, Tc)); RC(dalloc(e, &sl.d_seq_off, Bc + 1));
   RC(dalloc(e, &sl.d_last_rows, Bc)); RC(dalloc(e, &sl.d_out_ids, 8192)); RC(dalloc(e, &sl.d_argmax, Bc)); RC(dalloc(e, &sl.dlast, Bc * dm));
@@ -2138,14 +2155,14 @@ static int llama_prefill(rk_engine* e, const int32_t* tokens, const int32_t* off
   HIPCHK(e, hipMemcpy(e->d_pos, pos.data(), (size_t)T * sizeof(int), hipMemcpyHostToDevice));
   HIPCHK(e, hipMemcpy(sl.d_seq_off, off, (size_t)(n_seq + 1) * sizeof(int), hipMemcpyHostToDevice));
   HIPCHK(e, hipMemcpy(sl.d_last_rows, last.data(), (size_t)n_seq * sizeof(int), hipMemcpyHostToDevice));
-  GemmFold cons, prod;
-  cons.rowscale = sl.rowscale; prod.xraw = sl.xraw; prod.ssq = sl.ssq;
-  int nb = 0;                                   // block sums per row of the last residual GEMM
+  // every consumer takes its row factors from rowscale_kernel (own_factors = false), also where a fill-in tile variant could
+  // form them itself
+  NormStream ns = sl.enc;
   const CausalAttnPlan ap = plan_llama_attn(e, n_seq, sl.maxL, l.n_heads, l.n_kv_heads);
-  embed(e, st, sl.d_tokens, sl.hidden, T, sl.xraw, sl.rowscale);
+  ns.begin(e, st, sl.d_tokens, T, true);
   for (int i = 0; i < l.n_layers; ++i) {
     const LlamaLayerW& w = e->ll[i];
-    RC(gemm(e, st, Gemm(PC_ENC_GEMM_QKV, EPI_STORE_F16, sl.xraw, dm, w.qkv_f, dm, sl.qkv, ldq, T, ldq, dm).with(cons)));
+    RC(gemm(e, st, ns.consumer(e, st, nullptr, Gemm(PC_ENC_GEMM_QKV, EPI_STORE_F16, ns.x(), dm, w.qkv_f, dm, sl.qkv, ldq, T, ldq, dm), false)));
     {
       Bracket br(e, st, PC_OTHER, 0, (double)T * (Q + KV) * 4.0);
       hipLaunchKernelGGL(rope128_kernel, dim3(T), dim3(256), 0, st, sl.qkv, e->d_pos, e->rope_cos, e->rope_sin, ldq, l.n_heads + l.n_kv_heads);
@@ -2158,14 +2175,11 @@ static int llama_prefill(rk_engine* e, const int32_t* tokens, const int32_t* off
                          l.n_heads, l.n_kv_heads, keep->P);
     }
     launch_llama_attn(e, st, sl, ap);
-    RC(gemm(e, st, Gemm(PC_ENC_GEMM_O, EPI_RESID_F32, sl.ctx, Q, w.o, Q, sl.hidden, dm, T, dm, Q).with(prod), &nb));
-    rowscale(e, st, sl.ssq, sl.rowscale, T, nb);
-    RC(gemm(e, st, Gemm(PC_ENC_GEMM_FFN_IN, EPI_SWIGLU_F16, sl.xraw, dm, w.gu_f, dm, sl.ffh, F, T, 2 * F, dm).with(cons)));
-    const bool lastl = i + 1 == l.n_layers;
-    RC(gemm(e, st, Gemm(PC_ENC_GEMM_FFN_OUT, EPI_RESID_F32, sl.ffh, F, w.down, F, sl.hidden, dm, T, dm, F).with(lastl ? GemmFold() : prod), &nb));
-    if (!lastl) rowscale(e, st, sl.ssq, sl.rowscale, T, nb);
+    RC(ns.producer(e, st, Gemm(PC_ENC_GEMM_O, EPI_RESID_F32, sl.ctx, Q, w.o, Q, ns.hidden, dm, T, dm, Q)));
+    RC(gemm(e, st, ns.consumer(e, st, nullptr, Gemm(PC_ENC_GEMM_FFN_IN, EPI_SWIGLU_F16, ns.x(), dm, w.gu_f, dm, sl.ffh, F, T, 2 * F, dm), false)));
+    RC(ns.producer(e, st, Gemm(PC_ENC_GEMM_FFN_OUT, EPI_RESID_F32, sl.ffh, F, w.down, F, ns.hidden, dm, T, dm, F), i + 1 < l.n_layers));
   }
-  rmsnorm(e, st, sl.hidden, e->l_final_ln, sl.dlast, sl.d_last_rows, n_seq);
+  rmsnorm(e, st, ns.hidden, e->l_final_ln, sl.dlast, sl.d_last_rows, n_seq);
   HIPCHK(e, hipGetLastError());
   return RK_OK;
 }
@@ -2203,62 +2217,31 @@ int rk_llama_greedy1(rk_engine* e, const int32_t* tokens, const int32_t* seq_off
   if (!e || !out_tokens) return RK_ERR_INVALID;
   int rc = llama_prefill(e, tokens, seq_offsets, n_seq);
   if (rc) return rc;
-  if ((rc = ensure_amax(e, (size_t)n_seq, e->ld.vocab))) return rc;
+  if ((rc = ensure_amax(e, (size_t)n_seq))) return rc;
   Slot& sl = e->slots[0];
   hipStream_t st = sl.se;
   // full-vocabulary head on the n_seq last rows: weight-streaming GEMM, then the first arg-max (torch.argmax tie rule)
   if ((rc = head_argmax(e, st, sl.dlast, n_seq, e->ld.hidden, e->ld.vocab, sl.d_argmax))) return rc;
-  std::vector<int> amax(n_seq);
-  HIPCHK(e, hipMemcpyAsync(amax.data(), sl.d_argmax, n_seq * sizeof(int), hipMemcpyDeviceToHost, st));
-  HIPCHK(e, hipStreamSynchronize(st));
-  HIPCHK(e, hipGetLastError());
-  for (int b = 0; b < n_seq; ++b) out_tokens[b] = amax[b];
-  return RK_OK;
+  return read_argmax(e, st, sl, out_tokens, n_seq);
 }
 
-// rk_llama_generate's device memory, grown between calls only (never inside a capture; a move changes lkv_gen, which is part of
-// the step graph's key): the K / V cache, the attention partials, the call's int block; once: the step's activation rows, the
-// pinned read-back words and their events.
+// rk_llama_generate's device memory, grown between calls only (never inside a capture; a move of any of the three changes
+// lkv_gen, which is part of the step graph's key: the step holds all three addresses): the K / V cache, the attention partials,
+// the call's int block; once: the step's activation rows.
 static int ensure_llama_gen(rk_engine* e, int n_seq, int P, int max_new) {
   const rk_llama_desc& l = e->ld;
   const size_t S = (size_t)l.max_seqs, dm = l.hidden, Q = (size_t)l.n_heads * 128, KV = (size_t)l.n_kv_heads * 128, F = l.intermediate;
   const size_t kv = (size_t)l.n_layers * 2 * n_seq * KV * P;
   const size_t part = (size_t)n_seq * l.n_heads * ((P + LDC_CHUNK - 1) / LDC_CHUNK) * LDC_PSTR;
   const size_t ints = 16 + 4 * S + (size_t)n_seq * max_new;
-  if (kv > e->lkv_cap || part > e->lpart_cap || ints > e->lints_cap) {
-    int rc = sync_all(e);
-    if (rc) return rc;
-    if (kv > e->lkv_cap) {
-      if (e->lkv) HIPCHK(e, hipFree(e->lkv));
-      e->lkv = nullptr; e->lkv_cap = 0;
-      HIPCHK(e, hipMalloc((void**)&e->lkv, kv * sizeof(half_t)));
-      e->lkv_cap = kv;
-    }
-    if (part > e->lpart_cap) {
-      if (e->lpart) HIPCHK(e, hipFree(e->lpart));
-      e->lpart = nullptr; e->lpart_cap = 0;
-      HIPCHK(e, hipMalloc((void**)&e->lpart, part * sizeof(float)));
-      e->lpart_cap = part;
-    }
-    if (ints > e->lints_cap) {
-      if (e->lints) HIPCHK(e, hipFree(e->lints));
-      e->lints = nullptr; e->lints_cap = 0;
-      HIPCHK(e, hipMalloc((void**)&e->lints, ints * sizeof(int)));
-      e->lints_cap = ints;
-    }
-    ++e->lkv_gen;
+  int rc = RK_OK;
+  RC(e->lkv.reserve(e, kv, &e->lkv_gen)); RC(e->lpart.reserve(e, part, &e->lkv_gen)); RC(e->lints.reserve(e, ints, &e->lkv_gen));
+  if (!e->lg.stream.hidden) {
+    RC(dalloc(e, &e->lg.stream.hidden, S * dm)); RC(dalloc(e, &e->lg.stream.xraw[0], S * dm)); RC(dalloc(e, &e->lg.qkv, S * (Q + 2 * KV)));
+    RC(dalloc(e, &e->lg.ctx, S * Q)); RC(dalloc(e, &e->lg.ffh, S * F)); RC(dalloc(e, &e->lg.stream.ssq[0], S * ((dm + 31) / 32)));
+    RC(dalloc(e, &e->lg.stream.factors, S));
   }
-  if (!e->lg.hidden) {
-    int rc = RK_OK;
-    RC(dalloc(e, &e->lg.hidden, S * dm)); RC(dalloc(e, &e->lg.xraw, S * dm)); RC(dalloc(e, &e->lg.qkv, S * (Q + 2 * KV)));
-    RC(dalloc(e, &e->lg.ctx, S * Q)); RC(dalloc(e, &e->lg.ffh, S * F)); RC(dalloc(e, &e->lg.ssq, S * ((dm + 31) / 32)));
-    RC(dalloc(e, &e->lg.rowscale, S));
-  }
-  if (!e->gen_pin) {
-    HIPCHK(e, hipHostMalloc((void**)&e->gen_pin, 16 * sizeof(int), hipHostMallocDefault));
-    for (hipEvent_t& ev : e->ev_gen) HIPCHK(e, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-  }
-  return RK_OK;
+  return ensure_decode_ring(e);
 }
 
 // Greedy continuation with a K / V cache (hf: generation/utils.py greedy loop over LlamaForCausalLM with use_cache): the prefill
@@ -2287,11 +2270,11 @@ int rk_llama_generate(rk_engine* e, const int32_t* tokens, const int32_t* seq_of
     if (max_total > 0 && seq_offsets[b + 1] - seq_offsets[b] >= max_total)
       return fail(e, RK_ERR_INVALID, "prompt %d has %d tokens: it already reaches max_total %d", b, seq_offsets[b + 1] - seq_offsets[b], max_total);
   const int P = sl.maxL + max_new, S = l.max_seqs;
-  if ((rc = ensure_amax(e, (size_t)n_seq, l.vocab))) return rc;
+  if ((rc = ensure_amax(e, (size_t)n_seq))) return rc;
   if ((rc = ensure_llama_gen(e, n_seq, P, max_new))) return rc;
   hipStream_t st = sl.se;
   // the call's int block: {n, finished step, pad, n_eos, max_new, max_total, P, 0, eos[8]} | len[S] | done[S] | pos[S] | next[S] | out[n][max_new]
-  int* g = e->lints;
+  int* g = e->lints.p;
   int *d_len = g + 16, *d_done = d_len + S, *d_pos = d_done + S, *d_next = d_pos + S, *d_out = d_next + S;
   std::vector<int> init(16 + 4 * (size_t)S + (size_t)n_seq * max_new, 0);
   init[2] = pad_id; init[3] = n_eos; init[4] = max_new; init[5] = max_total; init[6] = P;
@@ -2300,7 +2283,7 @@ int rk_llama_generate(rk_engine* e, const int32_t* tokens, const int32_t* seq_of
   for (size_t k = 0; k < (size_t)n_seq * max_new; ++k) init[16 + 4 * (size_t)S + k] = pad_id;
   HIPCHK(e, hipStreamSynchronize(st));
   HIPCHK(e, hipMemcpy(g, init.data(), init.size() * sizeof(int), hipMemcpyHostToDevice));
-  const LlamaKeep keep{e->lkv, P};
+  const LlamaKeep keep{e->lkv.p, P};
   if ((rc = llama_prefill(e, tokens, seq_offsets, n_seq, &keep))) return rc;
   auto head_and_advance = [&]() -> int {
     int r = head_argmax(e, st, sl.dlast, n_seq, l.hidden, l.vocab, sl.d_argmax);
@@ -2316,53 +2299,28 @@ int rk_llama_generate(rk_engine* e, const int32_t* tokens, const int32_t* seq_of
   const float scale_log2e = (1.0f / std::sqrt(128.0f)) * 1.4426950408889634f;
   const auto& lg = e->lg;
   auto step = [&]() -> int {
-    int r = RK_OK, nb = 0;
-    GemmFold prod;
-    prod.xraw = lg.xraw; prod.ssq = lg.ssq;
-    // the GEMM behind a norm: row factors from the embedding (nb == 0), from the producer's block sums in its own epilogue, or -
-    // more block sums than that path stages (hidden > 2 048) - from rowscale_kernel in front of it.  A function of the model only.
-    auto normed = [&]() {
-      GemmFold f;
-      if (!nb) f.rowscale = lg.rowscale;
-      else if (nb <= 64) { f.ssq_in = lg.ssq; f.nb_in = nb; }
-      else { rowscale(e, st, lg.ssq, lg.rowscale, n_seq, nb); f.rowscale = lg.rowscale; }
-      return f;
-    };
-    embed(e, st, d_next, lg.hidden, n_seq, lg.xraw, lg.rowscale);
+    int rc = RK_OK;
+    NormStream ns = lg.stream;
+    // the GEMM behind a norm forms its row factors from the producer's block sums in its own epilogue, or - more block sums than
+    // that path stages by DMA (64: hidden > 2 048) - takes them from rowscale_kernel in front of it.  A function of the model only.
+    auto normed = [&](Gemm c) { return ns.consumer(e, st, nullptr, c.on(GEMM_STREAM), ns.nb <= 64); };
+    ns.begin(e, st, d_next, n_seq, true);
     for (int i = 0; i < l.n_layers; ++i) {
       const LlamaLayerW& w = e->ll[i];
-      if ((r = gemm(e, st, Gemm(PC_DEC_GEMM, EPI_STORE_F16, lg.xraw, dm, w.qkv_f, dm, lg.qkv, ldq, n_seq, ldq, dm).on(GEMM_STREAM).with(normed())))) return r;
-      half_t* kc = e->lkv + (size_t)i * 2 * half_layer;
-      launch_llama_dec_attn(e, st, ap, AttnDecCached128Args{lg.qkv, kc, kc + half_layer, d_pos, e->rope_cos, e->rope_sin, e->lpart, lg.ctx,
+      RC(gemm(e, st, normed(Gemm(PC_DEC_GEMM, EPI_STORE_F16, ns.x(), dm, w.qkv_f, dm, lg.qkv, ldq, n_seq, ldq, dm))));
+      half_t* kc = e->lkv.p + (size_t)i * 2 * half_layer;
+      launch_llama_dec_attn(e, st, ap, AttnDecCached128Args{lg.qkv, kc, kc + half_layer, d_pos, e->rope_cos, e->rope_sin, e->lpart.p, lg.ctx,
                                                             ldq, l.n_heads, l.n_kv_heads, P, ap.nch, scale_log2e}, n_seq);
-      if ((r = gemm(e, st, Gemm(PC_DEC_GEMM, EPI_RESID_F32, lg.ctx, Q, w.o, Q, lg.hidden, dm, n_seq, dm, Q).on(GEMM_STREAM).with(prod), &nb))) return r;
-      if ((r = gemm(e, st, Gemm(PC_DEC_GEMM, EPI_SWIGLU_F16, lg.xraw, dm, w.gu_f, dm, lg.ffh, F, n_seq, 2 * F, dm).on(GEMM_STREAM).with(normed())))) return r;
-      const bool lastl = i + 1 == l.n_layers;
-      if ((r = gemm(e, st, Gemm(PC_DEC_GEMM, EPI_RESID_F32, lg.ffh, F, w.down, F, lg.hidden, dm, n_seq, dm, F).on(GEMM_STREAM).with(lastl ? GemmFold() : prod), &nb))) return r;
+      RC(ns.producer(e, st, Gemm(PC_DEC_GEMM, EPI_RESID_F32, lg.ctx, Q, w.o, Q, ns.hidden, dm, n_seq, dm, Q).on(GEMM_STREAM)));
+      RC(gemm(e, st, normed(Gemm(PC_DEC_GEMM, EPI_SWIGLU_F16, ns.x(), dm, w.gu_f, dm, lg.ffh, F, n_seq, 2 * F, dm))));
+      RC(ns.producer(e, st, Gemm(PC_DEC_GEMM, EPI_RESID_F32, lg.ffh, F, w.down, F, ns.hidden, dm, n_seq, dm, F).on(GEMM_STREAM), i + 1 < l.n_layers));
     }
-    rmsnorm(e, st, lg.hidden, e->l_final_ln, sl.dlast, nullptr, n_seq);
+    rmsnorm(e, st, ns.hidden, e->l_final_ln, sl.dlast, nullptr, n_seq);
     return head_and_advance();
   };
-  const std::vector<int> key{4, 0, n_seq, P, (int)e->amax_rows, e->lkv_gen};
-  int* pin = e->gen_pin;
-  HIPCHK(e, hipMemcpyAsync(pin, g + 1, sizeof(int), hipMemcpyDeviceToHost, st));       // column 0's finished-step word
-  HIPCHK(e, hipEventRecord(e->ev_gen[0], st));
-  bool stop = false;
-  for (int s = 1; s < max_new && !stop; ++s) {                                         // step s produces column s
-    if ((rc = run_graphed(e, st, key, step))) return rc;
-    HIPCHK(e, hipMemcpyAsync(pin + (s & 1), g + 1, sizeof(int), hipMemcpyDeviceToHost, st));
-    HIPCHK(e, hipEventRecord(e->ev_gen[s & 1], st));
-    HIPCHK(e, hipEventSynchronize(e->ev_gen[(s - 1) & 1]));                            // the previous column's word, while this step runs
-    stop = pin[(s - 1) & 1] != 0;
-  }
-  std::vector<int> res((size_t)n_seq * max_new + 1);
-  HIPCHK(e, hipMemcpyAsync(res.data(), d_out, (size_t)n_seq * max_new * sizeof(int), hipMemcpyDeviceToHost, st));
-  HIPCHK(e, hipMemcpyAsync(res.data() + (size_t)n_seq * max_new, g + 1, sizeof(int), hipMemcpyDeviceToHost, st));
-  HIPCHK(e, hipStreamSynchronize(st));
-  HIPCHK(e, hipGetLastError());
-  memcpy(out_tokens, res.data(), (size_t)n_seq * max_new * sizeof(int));
-  if (out_steps) *out_steps = res[(size_t)n_seq * max_new];
-  return RK_OK;
+  const std::vector<int> key{4, 0, n_seq, P, e->amax_gen, e->lkv_gen};
+  // column 0 is the prefill's: the steps produce columns 1 .. max_new - 1
+  return decode_cached(e, st, key, step, 0, 1, n_seq, max_new, g + 1, d_out, out_tokens, out_steps);
 }
 
 // ---- K9: score collection across the GPUs of a node, RCCL over xGMI, straight from the slot's device score buffer --
@@ -2755,16 +2713,16 @@ int64_t rk_debug_read(rk_engine* e, const char* name, float* out, int64_t max_fl
   const std::string n(name);
   const int I = e->inner, dm = e->d.d_model;
   const void* src = nullptr; int64_t cnt = 0; bool is_half = true;
-  if (n == "enc_hidden") { src = sl.hidden; cnt = (int64_t)sl.T * dm; is_half = false; }
+  if (n == "enc_hidden") { src = sl.enc.hidden; cnt = (int64_t)sl.T * dm; is_half = false; }
 #ifdef RK_MEASURE
   else if (n == "attn_trace" && e->attn_trace) { src = e->attn_trace; cnt = 12 * 16 * 16; is_half = false; }
 #endif
   else if (n == "enc_out") { src = sl.enc_out; cnt = (int64_t)sl.T * dm; }
   else if (n == "qkv") { src = sl.qkv; cnt = (int64_t)sl.T * 3 * I; }
   else if (n == "ctx") { src = sl.ctx; cnt = (int64_t)sl.T * I; }
-  else if (n == "xn") { src = sl.xn; cnt = (int64_t)sl.T * dm; }
+  else if (n == "xn") { src = sl.enc.xn; cnt = (int64_t)sl.T * dm; }
   else if (n == "llama_last") { src = sl.dlast; cnt = (int64_t)sl.n_seq * dm; }   // final-normed last rows of the most recent Llama call
-  else if (n == "dec_hidden") { src = sl.dhidden; cnt = (int64_t)sl.n_seq * e->d.max_dec_len * dm; is_half = false; }
+  else if (n == "dec_hidden") { src = sl.dec.hidden; cnt = (int64_t)sl.n_seq * e->d.max_dec_len * dm; is_half = false; }
   else return fail(e, RK_ERR_INVALID, "unknown buffer %s", name);
   cnt = std::min(cnt, max_floats);
   if (is_half) {
