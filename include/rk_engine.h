@@ -76,6 +76,17 @@ int rk_t5_score(rk_engine* e, const int32_t* tokens, const int32_t* seq_offsets,
  * replaces: self.llm(input_ids, attention_mask, labels=...).logits + CrossEntropyLoss(reduction="none") (pointwise.py:73-79) */
 int rk_t5_qlm(rk_engine* e, const int32_t* tokens, const int32_t* seq_offsets, int n_seq,
               const int32_t* labels, int n_labels, float* out_scores);
+/* rk_t5_qlm for several queries in one call: sequence b scores ITS OWN labels, labels[label_offsets[b] .. label_offsets[b+1])
+ * (label_offsets[n_seq + 1], label_offsets[0] == 0): out_scores[b] = -sum_t CE(logits[b,t,:], labels[label_offsets[b] + t]) with
+ * decoder input = shift_right of those labels.  A sequence's score is BIT FOR BIT what rk_t5_qlm gives that sequence with those
+ * labels, whatever else shares the call and in whatever order (one encoder run over all sequences, one ragged decoder pass per
+ * class of label counts that share their arithmetic; DESIGN.md sections 3 and 4 - the one exception is rk_t5_qlm's own: a decoder
+ * pass of at most 4 rows at two or more positions).  Blocking; the scores stay in slot 0's device score buffer in sequence order,
+ * so rk_comm_append_scores_slot works behind it as behind rk_t5_qlm.  RK_ERR_CAPACITY for a sequence with 0 or more than
+ * max_dec_len labels, RK_ERR_INVALID for ids outside the vocabulary or offsets that do not start at 0 and grow.
+ * replaces: one self.llm(input_ids, attention_mask, labels=...) call per query (pointwise.py:73-79) for the queries of a group */
+int rk_t5_qlm_many(rk_engine* e, const int32_t* tokens, const int32_t* seq_offsets, int n_seq,
+                   const int32_t* labels, const int32_t* label_offsets, float* out_scores);
 /* Greedy continuation of dec_prefix by up to max_new tokens -> out_tokens[n_seq][max_new] (pad_id after EOS;
  * stops early when every row has finished, remaining columns = pad_id); *out_steps = decoder steps executed.
  * replaces: self.llm.generate(input_ids, decoder_input_ids=..., max_new_tokens=2)  (setwise.py:93-95, 128-130) */
@@ -175,7 +186,7 @@ int rk_comm_library_info(char* buf, int n_bytes);
 int rk_comm_all_gather_slot(rk_engine* e, int slot, int n_floats);
 int rk_comm_read_gathered_slot(rk_engine* e, int slot, float* out, int n_floats_total);
 /* Appended form for a rank whose share of the candidates takes several engine calls (more than max_seqs sequences or
- * max_tokens tokens): after each blocking call (rk_t5_score / rk_t5_qlm: scores in slot 0) or rk_t5_score_slot, copy that
+ * max_tokens tokens): after each blocking call (rk_t5_score / rk_t5_qlm / rk_t5_qlm_many: scores in slot 0) or rk_t5_score_slot, copy that
  * call's n_floats scores to offset dst_offset of the engine's send buffer (device to device, on the producing stream);
  * then ONE ncclAllGather of the first n_floats of the send buffer (every rank passes the same n_floats = the largest
  * share; capacity = rk_comm_init's max_floats_per_rank); rk_comm_read_appended waits and copies out[world][n_floats].

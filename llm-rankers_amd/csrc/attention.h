@@ -1258,7 +1258,17 @@ struct AttnDecArgs {
   // attn_dec_cross_mfma_kernel, the others by the staged kernels; which kernel computes a sequence follows from ITS key count
   // alone (its bits never depend on the batch): skip_short = 1 makes attn_dec_seq_kernel / attn_dec_kernel leave those to it
   int skip_short;
+  // ragged rows (rk_t5_qlm_many: sequences of one pass with different position counts), not for the tree form: the query /
+  // context rows of sequence b are row_off[b] .. row_off[b + 1] - 1 (in the self form those are also its keys) and ITS row count
+  // takes Lq's place everywhere - key tiles, masks, the waves that retire - so a sequence's bits never depend on the pass's
+  // longest member.  The grid and the LDS are sized for the longest; nullptr: Lq rows per sequence.
+  const int* row_off;
 };
+// first row and row count of sequence b
+__device__ __forceinline__ void dec_rows_of(const AttnDecArgs& p, int b, int& row0, int& Lq) {
+  if (p.row_off) { row0 = p.row_off[b]; Lq = p.row_off[b + 1] - row0; }
+  else { row0 = b * p.Lq; Lq = p.Lq; }
+}
 
 // The arithmetic of ONE query row of the decoder attention, shared by attn_dec_kernel (one workgroup per row: the tree form of
 // rk_t5_greedy2 and sequences with more keys than attn_dec_seq_kernel stages) and attn_dec_seq_kernel (one workgroup per
@@ -1326,13 +1336,15 @@ __global__ __launch_bounds__(256) void attn_dec_kernel(AttnDecArgs p) {
   const int b = blockIdx.z, h = blockIdx.y;
   const int* tkeys = p.tree_keys ? p.tree_keys + (size_t)b * p.Lq : nullptr;
   const int i = tkeys ? p.tree_pos[b] : (int)blockIdx.x;
-  int koff, Lk;
+  int koff, Lk, row0, Lq;
+  dec_rows_of(p, b, row0, Lq);
+  if (!tkeys && i >= Lq) return;                              // ragged rows: a sequence shorter than the grid (uniform for the workgroup)
   if (tkeys) { koff = 0; Lk = i + 1; }
   else if (p.key_off) { koff = p.key_off[b]; Lk = p.key_off[b + 1] - koff; }
-  else { koff = b * p.Lq; Lk = p.Lq; }
+  else { koff = row0; Lk = Lq; }
   if (p.skip_short && Lk <= ATTX_MAXK) return;                // attn_dec_cross_mfma_kernel's sequence (uniform for the workgroup)
   const int nk = p.causal ? (i + 1 < Lk ? i + 1 : Lk) : Lk;   // keys 0..nk-1 are visible
-  const size_t qrow = tkeys ? (size_t)b : (size_t)(b * p.Lq + i);
+  const size_t qrow = tkeys ? (size_t)b : (size_t)(row0 + i);
   auto krow = [&](int j) { return tkeys ? (size_t)tkeys[j] : (size_t)(koff + j); };
   if (tid < 64) sQ[tid] = (float)p.q[qrow * p.ldq + h * 64 + tid];
   __syncthreads();
@@ -1477,8 +1489,10 @@ __global__ __launch_bounds__(128) void attn_dec_cross_mfma_kernel(AttnDecArgs p)
   const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, hh = lane >> 5;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int h = blockIdx.x, b = blockIdx.y;
-  const int koff = p.key_off ? p.key_off[b] : b * p.Lq, Lk = p.key_off ? p.key_off[b + 1] - koff : p.Lq;
-  if (Lk > ATTX_MAXK || Lk <= 0) return;            // the staged kernel's sequence (uniform)
+  int row0, Lq;
+  dec_rows_of(p, b, row0, Lq);
+  const int koff = p.key_off ? p.key_off[b] : row0, Lk = p.key_off ? p.key_off[b + 1] - koff : Lq;
+  if (Lk > ATTX_MAXK || Lk <= 0 || Lq <= 0) return;   // the staged kernel's sequence (uniform)
   const int nt = (Lk + 31) >> 5;                    // key tiles
   if (p.bias_lut)
     for (int idx = tid; idx < RK_LUT_N; idx += 128) sLut[idx] = p.bias_lut[h * RK_LUT_N + idx];
@@ -1496,10 +1510,10 @@ __global__ __launch_bounds__(128) void attn_dec_cross_mfma_kernel(AttnDecArgs p)
     for (int j = 0; j < 8; ++j) sVt[(c * 8 + j) * ATTX_VSTR + r] = vv[j];
   }
   __syncthreads();
-  if (wave * 32 >= p.Lq) return;                    // a second wave without decoder positions
+  if (wave * 32 >= Lq) return;                      // a second wave without decoder positions
   // ---- Q fragments of this wave's 32 positions (B operand: k = 16 ks + 8 hh .. + 7 of query l31) ----
   const int qi = wave * 32 + l31;
-  const size_t qrow = (size_t)b * p.Lq + (qi < p.Lq ? qi : p.Lq - 1);
+  const size_t qrow = (size_t)row0 + (qi < Lq ? qi : Lq - 1);
   half8 qf[4];
 #pragma unroll
   for (int ks = 0; ks < 4; ++ks) qf[ks] = *(const half8*)(p.q + qrow * p.ldq + h * 64 + ks * 16 + 8 * hh);
@@ -1566,9 +1580,9 @@ __global__ __launch_bounds__(128) void attn_dec_cross_mfma_kernel(AttnDecArgs p)
     }
   }
   // ---- context row of query l31: d = 32 dt + (r & 3) + 8 (r >> 2) + 4 hh -> 8-byte pieces ----
-  if (qi < p.Lq) {
+  if (qi < Lq) {
     const float inv = 1.0f / sum;
-    half_t* dst = p.ctx + ((size_t)b * p.Lq + qi) * p.ldctx + h * 64;
+    half_t* dst = p.ctx + ((size_t)row0 + qi) * p.ldctx + h * 64;
 #pragma unroll
     for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
@@ -1589,9 +1603,10 @@ __global__ __launch_bounds__(256) void attn_dec_seq_kernel(AttnDecArgs p) {
   float* sLut = (float*)(sV + (size_t)kp * 64);    // [RK_LUT_N (+3)]  this head's bias by clamp(key - query)
   float* sQ = sLut + RK_LUT_N + 3 + (size_t)wave * (64 * 4 + kp * 4);   // [4][64]   (wave-private from here on)
   float* sP = sQ + 64 * 4;                         // [kp][4]: the probabilities of the wave's (up to) four rows, interleaved
-  int koff, Lk;
+  int koff, Lk, row0, Lq;
+  dec_rows_of(p, b, row0, Lq);
   if (p.key_off) { koff = p.key_off[b]; Lk = p.key_off[b + 1] - koff; }
-  else { koff = b * p.Lq; Lk = p.Lq; }
+  else { koff = row0; Lk = Lq; }
   if (p.skip_short && Lk <= ATTX_MAXK) return;     // attn_dec_cross_mfma_kernel's sequence (uniform for the workgroup)
   for (int idx = tid; idx < Lk * 8; idx += 256) {
     const int r = idx >> 3, c = idx & 7;
@@ -1610,9 +1625,9 @@ __global__ __launch_bounds__(256) void attn_dec_seq_kernel(AttnDecArgs p) {
   const half_t* vb = sV + lane;
   if (p.causal || p.bias_lut) {
     // ---- one row at a time (self-attention: nk = i + 1 keys) ----
-    for (int i = wave; i < p.Lq; i += 4) {
+    for (int i = wave; i < Lq; i += 4) {
       const int nk = p.causal ? (i + 1 < Lk ? i + 1 : Lk) : Lk;
-      const size_t qrow = (size_t)b * p.Lq + i;
+      const size_t qrow = (size_t)row0 + i;
       sQ[lane] = (float)p.q[qrow * p.ldq + h * 64 + lane];
       __builtin_amdgcn_wave_barrier();
       float mx = -1e30f;
@@ -1676,12 +1691,12 @@ __global__ __launch_bounds__(256) void attn_dec_seq_kernel(AttnDecArgs p) {
   }
   // ---- four rows at a time (no mask, no bias: every row of the block sees keys 0 .. Lk-1) ----
   const int nk = Lk;
-  for (int i0 = wave; i0 < p.Lq; i0 += 16) {
+  for (int i0 = wave; i0 < Lq; i0 += 16) {
     int rows[4];
 #pragma unroll
-    for (int r = 0; r < 4; ++r) { const int i = i0 + 4 * r; rows[r] = i < p.Lq ? i : i0; }   // (a missing row repeats the first: computed, not stored)
+    for (int r = 0; r < 4; ++r) { const int i = i0 + 4 * r; rows[r] = i < Lq ? i : i0; }   // (a missing row repeats the first: computed, not stored)
 #pragma unroll
-    for (int r = 0; r < 4; ++r) sQ[r * 64 + lane] = (float)p.q[((size_t)b * p.Lq + rows[r]) * p.ldq + h * 64 + lane];
+    for (int r = 0; r < 4; ++r) sQ[r * 64 + lane] = (float)p.q[((size_t)row0 + rows[r]) * p.ldq + h * 64 + lane];
     __builtin_amdgcn_wave_barrier();
     float mx[4] = {-1e30f, -1e30f, -1e30f, -1e30f};
     for (int j0 = lane; j0 < nk; j0 += 256) {
@@ -1788,13 +1803,13 @@ __global__ __launch_bounds__(256) void attn_dec_seq_kernel(AttnDecArgs p) {
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int i = i0 + 4 * r;
-      if (i < p.Lq) {
+      if (i < Lq) {
         const float sum = (ssum[r][0] + ssum[r][1]) + (ssum[r][2] + ssum[r][3]);
         float part[4];
 #pragma unroll
         for (int w = 0; w < 4; ++w) part[w] = (a[r][w][0] + a[r][w][1]) + (a[r][w][2] + a[r][w][3]);
         const float acc = (part[0] + part[1]) + (part[2] + part[3]);
-        p.ctx[((size_t)b * p.Lq + i) * p.ldctx + h * 64 + lane] = f2h_sat(acc / sum);
+        p.ctx[((size_t)row0 + i) * p.ldctx + h * 64 + lane] = f2h_sat(acc / sum);
       }
     }
     __builtin_amdgcn_wave_barrier();

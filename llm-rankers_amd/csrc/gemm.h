@@ -48,8 +48,9 @@ struct GemmArgs {
   // EPI_ARGMAX_F32 (greedy head): C = float [M, ldc] block maxima, amax_idx = int [M, ldc] their first column (ldc = blocks)
   int* amax_idx;
   // EPI_LSE_F32 (qlm head): C = float2 [M, ldc] (block max, sum of exp(x - block max)) per 32-column block (ldc = blocks);
-  // row m scores label lse_labels[m % lse_npos], whose logit goes to lse_xlab[m].  The logits never reach memory.
-  const int* lse_labels; int lse_npos; float* lse_xlab;
+  // row m scores label lse_labels[m] (one entry per row: the sequences of a pass may score different label sequences), whose
+  // logit goes to lse_xlab[m].  The logits never reach memory.
+  const int* lse_labels; float* lse_xlab;
   // ping-pong kernel: width (in tiles) of the column panels of the grouped tile order (gemm_tile_coords); host default GEMM_GROUP_N
   int group_n;
   // ping-pong kernel, K split over workgroups (SPLIT instantiations; gemm_pp2_kernel): ksplit >= 2 workgroups share an output tile,
@@ -244,7 +245,7 @@ __device__ __forceinline__ void gemm_epilogue_lse(const GemmArgs& p, f32x16 (&ac
   for (int mi = 0; mi < MI; ++mi) {
     const int m = mbase + mi * 32 + l31;
     const bool row_ok = m < p.M;
-    const int label = row_ok ? p.lse_labels[m % p.lse_npos] : -1;
+    const int label = row_ok ? p.lse_labels[m] : -1;
     const float sc = rsc[mi];
 #pragma unroll
     for (int ni = 0; ni < NI; ++ni) {

@@ -204,13 +204,18 @@ __global__ __launch_bounds__(256) void llama_advance_kernel(const int* __restric
 // QLM score (ref: llmrankers/pointwise.py:77-79) from the fused head (gemm.h: EPI_LSE_F32): stats [rows, nblk] = (block max, sum exp(x - block max)), xlab [rows] =
 // the label's logit.  out[b] = -sum_t ( logsumexp_t - xlab[b, t] ), logsumexp_t = M + log(sum_blocks s * exp(m - M)).
 // One block per sequence; the blocks of a position are merged in a fixed order, the positions summed in order (deterministic).
+// row_off (rk_t5_qlm_many): the rows of sequence b are row_off[b] .. row_off[b + 1] - 1 instead of n_pos per sequence; out_idx:
+// its score goes to out[out_idx[b]] (the caller's order of sequences that were sorted for the pass).
 __global__ __launch_bounds__(256) void qlm_lse_kernel(const float2* __restrict__ stats, int nblk, const float* __restrict__ xlab,
-                                                      int n_pos, float* __restrict__ out) {
+                                                      int n_pos, const int* __restrict__ row_off, const int* __restrict__ out_idx,
+                                                      float* __restrict__ out) {
   __shared__ float sred[4];
   const int b = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const size_t row0 = row_off ? (size_t)row_off[b] : (size_t)b * n_pos;
+  if (row_off) n_pos = row_off[b + 1] - row_off[b];
   float total = 0.f;
   for (int t = 0; t < n_pos; ++t) {
-    const size_t row = (size_t)b * n_pos + t;
+    const size_t row = row0 + t;
     const float2* src = stats + row * nblk;
     float mx = -INFINITY;
     for (int c = tid; c < nblk; c += 256) mx = fmaxf(mx, src[c].x);
@@ -228,5 +233,5 @@ __global__ __launch_bounds__(256) void qlm_lse_kernel(const float2* __restrict__
     __syncthreads();
     total += (mx + logf(se)) - xlab[row];
   }
-  if (tid == 0) out[b] = -total;
+  if (tid == 0) out[out_idx ? out_idx[b] : b] = -total;
 }

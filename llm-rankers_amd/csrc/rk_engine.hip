@@ -115,7 +115,7 @@ struct Slot {
   int* d_tokens = nullptr; int* d_seq_off = nullptr;
   int n_seq = 0, T = 0, maxL = 0, minL = 0; bool staged = false; int last_n_out = 0;
   half_t* cross_kv = nullptr;                                  // [n_dec][max_tokens][2I] encoder -> decoder hand-off
-  int *d_dec_ids = nullptr, *d_last_rows = nullptr, *d_out_ids = nullptr, *d_labels = nullptr, *d_argmax = nullptr, *d_row_seq = nullptr, *d_tree_keys = nullptr, *d_tree_pos = nullptr;
+  int *d_dec_ids = nullptr, *d_last_rows = nullptr, *d_out_ids = nullptr, *d_row_label = nullptr, *d_row_off = nullptr, *d_out_idx = nullptr, *d_argmax = nullptr, *d_row_seq = nullptr, *d_tree_keys = nullptr, *d_tree_pos = nullptr;
   NormStream dec;                                              // the decoder's (run_decoder); rk_t5_qlm's final norm writes dec.xn
   half_t *dqkv = nullptr, *dctx = nullptr, *dq = nullptr, *dffh = nullptr, *dlast = nullptr;
   float* dssq_few[2] = {nullptr, nullptr};   // dec.ssq for the few-row GEMV family (gemv_rows.h): one partial per producing workgroup
@@ -142,7 +142,7 @@ struct rk_engine {
   std::vector<DecLayerW> dec;
   float *enc_final_ln = nullptr, *dec_final_ln = nullptr, *lut_enc = nullptr, *lut_dec = nullptr;
   Grown<float> logits;                                         // qlm head: per-block (max, sum exp) pairs [rows, vocab/32] + label logits [rows]; slot 0 only
-  const int* lse_labels = nullptr; int lse_npos = 0; float* lse_xlab = nullptr;   // arguments of the next EPI_LSE_F32 launch
+  const int* lse_labels = nullptr; float* lse_xlab = nullptr;   // arguments of the next EPI_LSE_F32 launch
   Grown<float> amax_val; Grown<int> amax_idx; int amax_gen = 0;   // greedy head: per-row block maxima / first columns
   // rk_t5_generate: self-attention K / V cache [n_dec_layers][n_seq][P][2 inner] (kv_gen counts the moves) and the per-call int
   // block on the device (state, prefix, finished rows, output, tree arrays); decode_cached: pinned read-back of the finished step
@@ -551,7 +551,7 @@ int gemm(rk_engine* e, hipStream_t st, const Gemm& c, int* nb = nullptr) {
   a.ssq_in = c.fold.ssq_in; a.nb_in = c.fold.nb_in; a.eps_in = e->d.eps;
   a.group_n = GEMM_GROUP_N;
   if (c.epi == EPI_ARGMAX_F32) a.amax_idx = e->amax_idx.p;
-  if (c.epi == EPI_LSE_F32) { a.lse_labels = e->lse_labels; a.lse_npos = e->lse_npos; a.lse_xlab = e->lse_xlab; }
+  if (c.epi == EPI_LSE_F32) { a.lse_labels = e->lse_labels; a.lse_xlab = e->lse_xlab; }
   const double flops = 2.0 * c.M * (double)c.N * c.K * c.batch;
   const double out_elems = EPI_IS_GATED(c.epi) ? (double)c.M * c.N / 2 : (double)c.M * c.N;
   const double bytes = 2.0 * ((double)c.M * c.K + (double)c.N * c.K) +
@@ -681,13 +681,38 @@ int upload_small(rk_engine* e, Slot& sl, hipStream_t st, std::vector<int>* cache
 #define XA_MAX_CHUNKS 4096  // rows x 64-key chunks of partial-sum workspace per pass
 #define XA_MAX_LD 16        // decoder positions per sequence up to which the query-side form is used
 
+// Everything a decoder pass decides from the POSITION COUNT of its sequences and that rounds differently on either side of
+// the line: the ONE place these lines are drawn (run_decoder, use_xattn_direct and plan_dec_attn read them here).  Two
+// position counts with the same key() take the same arithmetic row for row, so sequences of different label counts may share
+// a ragged pass exactly when their keys agree (rk_t5_qlm_many); with the default options the classes are
+// {1}, {2..4}, {5..16}, {17..64} and {65..max_dec_len}.
+struct DecLenClass {
+  bool one = false;          // a single position: the W_o W_v product form, fused cross-attention projections, tiled FFN-in
+  bool stream = false;       // few positions: the weight-streaming GEMM family (and its folded norms), else the tiled one
+  bool direct = false;       // query-side cross-attention, else the materialised K / V
+  bool self_mfma = false, cross_mfma = false;   // attn_dec_cross_mfma_kernel for the self- / cross-attention, else the staged kernels
+  int key() const { return (int)one | (int)stream << 1 | (int)direct << 2 | (int)self_mfma << 3 | (int)cross_mfma << 4; }
+};
+DecLenClass dec_len_class(const rk_engine* e, int Ld) {
+  DecLenClass c;
+  c.one = Ld == 1;
+  c.stream = Ld <= 4;
+  c.direct = e->opt.xattn_direct && Ld <= XA_MAX_LD;
+  // the matrix-core kernel: cross-attention from two positions on; self-attention for long prefixes only (the materialised-K / V
+  // regime, qlm: round 6); at most ATTX_MAXQ positions (two 32-query tiles)
+  const bool mfma = e->opt.dec_cross_mfma && Ld <= ATTX_MAXQ;
+  c.self_mfma = mfma && Ld > XA_MAX_LD;
+  c.cross_mfma = mfma && Ld >= 2;
+  return c;
+}
+
 // Query-side cross-attention (attention.h) or materialised K/V: the two round at different points, so the choice must
 // not depend on what else shares the call (a row's logits have to be the same in any batch, on any rank): it is made
 // from the decoder LENGTH of the call alone (the query-side form costs L_d x L x H x d flops per sequence against
 // L x 2I x d for the projections: cheaper up to L_d ~ 64, and far fewer bytes below 16).  More rows than the workspace
 // holds are taken in passes (run_decoder).
 bool use_xattn_direct(const rk_engine* e, const Slot&, int max_ld) {
-  return e->opt.xattn_direct && max_ld <= XA_MAX_LD;
+  return dec_len_class(e, max_ld).direct;
 }
 
 // ---- attention launch plans: like plan_gemm, each a function of the call shape, the options and the CU count (which kernels
@@ -762,12 +787,13 @@ struct DecAttnPlan {
                                                 // once) or attn_dec_kernel (same bits), 256 threads
   dim3 mfma_grid, grid; size_t lds = 0;         // grid and dynamic LDS of the staged kernel
 };
-// keys: per sequence, Ld (self) or the longest (cross); tree_rows > 0: the tree form
+// keys: per sequence, Ld (self) or the longest (cross); tree_rows > 0: the tree form.  Ragged rows (AttnDecArgs::row_off): Ld =
+// the pass's longest sequence - grids and LDS are sized by it (work, not bits), the kernels take each sequence's own count
 DecAttnPlan plan_dec_attn(const rk_engine* e, bool cross, int B, int Ld, int keys, int H, int tree_rows) {
   DecAttnPlan p;
   if (tree_rows) { p.grid = dim3(1, H, tree_rows); p.lds = attn_dec_lds(keys); return p; }
-  // cross-attention from two positions on; self-attention for long prefixes only (the materialised-K / V regime, qlm: round 6)
-  p.mfma = e->opt.dec_cross_mfma && Ld <= ATTX_MAXQ && (cross ? Ld >= 2 : Ld > XA_MAX_LD);
+  const DecLenClass lc = dec_len_class(e, Ld);
+  p.mfma = cross ? lc.cross_mfma : lc.self_mfma;
   p.mfma_grid = dim3(H, B);
   if (p.mfma && keys <= ATTX_MAXK) p.staged = DecAttnPlan::NONE;
   else if (e->opt.dec_attn_seq && Ld >= 2 && attn_dec_seq_lds(keys) <= 160 * 1024) { p.staged = DecAttnPlan::SEQ; p.grid = dim3(H, B); p.lds = attn_dec_seq_lds(keys); }
@@ -944,7 +970,15 @@ int run_encoder(rk_engine* e, Slot& sl, bool need_cross_kv) {
 // tree (rk_t5_greedy2): the decoder rows are not Ld per sequence - several continuations of a prompt share the rows of their
 // common prefix.  rows = row count, Ld = longest position count; device arrays: keys[r * Ld + j] = row at position j of
 // row r's sequence, pos[r] = position of row r, seq[r] = its encoder sequence.  Query-side cross-attention only.
-struct DecTree { int rows; const int* keys; const int* pos; const int* seq; };
+// ragged (rk_t5_qlm_many): the pass covers the sequences seq0 .. seq0 + n_seq - 1 of the slot's batch, each with its OWN position
+// count (all of one DecLenClass; Ld = the longest): sequence seq0 + b owns the rows row_off[b] .. row_off[b + 1] - 1 at positions
+// 0, 1, ..; seq[r] = encoder sequence of row r (index into the slot's batch), ids = the pass's decoder ids; cross_kv: the pass
+// reads the materialised K / V (the encoder made them) - otherwise the query-side form, whatever the encoder left.
+struct DecRows {
+  int rows; const int* keys; const int* pos; const int* seq;
+  const int* row_off; int seq0, n_seq; bool cross_kv; const int* ids;
+  bool tree() const { return keys != nullptr; }
+};
 // cache (rk_t5_generate): the incremental pass - ONE new row per sequence (Ld = 1) at the position *pos on the device, layer l's
 // self-attention K / V cache at kv + l * B * P * 2I.  The layer is the one-position chain's (fused query-side cross-attention,
 // folded norms, tiled FFN-in: every family from the call shape, never from B) but for self-attention: the QKV projection of the
@@ -955,13 +989,18 @@ struct DecCache { half_t* kv; int P; const int* pos; const int* tree_keys; int* 
 // helper streams, fork / join by events (parallel branches of the decoder graph) - bit-identical, but 6.4-6.6k passages/s
 // against 7.3k: what the decoder costs the encoder running beside it is every one of its kernels delaying the persistent
 // GEMM it meets, so more, smaller decoder kernels cost more, not less.  The lever is fewer and shorter decoder kernels.)
-int run_decoder(rk_engine* e, Slot& sl, int Ld, const DecTree* tree = nullptr, const DecCache* cache = nullptr) {
+int run_decoder(rk_engine* e, Slot& sl, int Ld, const DecRows* rows = nullptr, const DecCache* cache = nullptr) {
   const rk_model_desc& d = e->d;
   hipStream_t st = dec_stream(e, sl);
-  const int B = sl.n_seq, M = tree ? tree->rows : B * Ld, I = e->inner, dm = d.d_model, F = d.d_ff;
-  if (tree && (sl.have_cross_kv || Ld < 2)) return fail(e, RK_ERR_STATE, "the tree form needs the query-side cross-attention and L_d >= 2");
-  if (cache && (tree || sl.have_cross_kv || Ld != 1)) return fail(e, RK_ERR_STATE, "the incremental pass needs the query-side cross-attention and one row per sequence");
-  const bool ws = Ld <= 4;   // few decoder positions: weight-streaming GEMMs (any number of sequences); else tiled
+  const bool tree = rows && rows->tree(), ragged = rows && !rows->tree();
+  const int B = ragged ? rows->n_seq : sl.n_seq, M = rows ? rows->rows : B * Ld, I = e->inner, dm = d.d_model, F = d.d_ff;
+  const bool have_kv = ragged ? rows->cross_kv : sl.have_cross_kv;
+  const int* seq_off = sl.d_seq_off + (ragged ? rows->seq0 : 0);
+  const DecLenClass lc = dec_len_class(e, Ld);
+  if (tree && (have_kv || lc.one)) return fail(e, RK_ERR_STATE, "the tree form needs the query-side cross-attention and L_d >= 2");
+  if (ragged && have_kv && !sl.have_cross_kv) return fail(e, RK_ERR_STATE, "the ragged pass needs the K / V the encoder did not materialise");
+  if (cache && (rows || have_kv || Ld != 1)) return fail(e, RK_ERR_STATE, "the incremental pass needs the query-side cross-attention and one row per sequence");
+  const bool ws = lc.stream;   // few decoder positions: weight-streaming GEMMs (any number of sequences); else tiled
   // Folded RMSNorm on the weight-streaming path (as in the encoder, minus the statistics kernel): the residual GEMMs leave
   // the new rows as fp16 with their sums of squares per 32-column block, the GEMM behind the norm reads those with the norm
   // weight folded into its matrix and forms the row factor itself (gemm.h: GemmArgs::ssq_in) - three launches per layer less.
@@ -981,9 +1020,9 @@ int run_decoder(rk_engine* e, Slot& sl, int Ld, const DecTree* tree = nullptr, c
   // grouped pipeline gains 1.2 %; at the 13 rows x 23 chunks of a setwise compare it is 4 us per layer SLOWER (the separate GEMMs
   // spread the cold weights of a layer over 512 + 5120 workgroups).  The family follows from the CALL SHAPE, never from the batch
   // (the two round differently): fused for one decoder position, separate beyond (dec_fuse = 2 forces the fused form: tests)
-  const bool fuse_asked = e->opt.dec_fuse == 2 || (e->opt.dec_fuse == 1 && Ld == 1);
-  const bool fuse = fuse_asked && !sl.have_cross_kv && dm % 128 == 0;   // (eight K ranges of whole k16 steps per workgroup)
-  const bool few = dfold && e->opt.dec_gemv && Ld >= 2 && M <= e->opt.dec_gemv_rows && !fuse_asked &&
+  const bool fuse_asked = e->opt.dec_fuse == 2 || (e->opt.dec_fuse == 1 && lc.one);
+  const bool fuse = fuse_asked && !have_kv && dm % 128 == 0;   // (eight K ranges of whole k16 steps per workgroup)
+  const bool few = dfold && e->opt.dec_gemv && !lc.one && M <= e->opt.dec_gemv_rows && !fuse_asked &&
                    gemv_fits(M, dm) && gemv_fits(M, I) && gemv_fits(M, F);   // every K of the pass's projections
   const GemmFamily fam = few ? GEMM_GEMV : (ws ? GEMM_STREAM : GEMM_TILED);
   int rc = RK_OK;
@@ -992,12 +1031,12 @@ int run_decoder(rk_engine* e, Slot& sl, int Ld, const DecTree* tree = nullptr, c
   // the GEMM c of this pass's family behind the norm ln: every consumer here may form its row factors itself
   auto normed = [&](const float* ln, Gemm c) { return ns.consumer(e, st, ln, c.on(fam), true); };
   auto resid = [&](Gemm c, bool stats = true) { return ns.producer(e, st, c.on(fam), stats); };
-  ns.begin(e, st, sl.d_dec_ids, M, dfold);
-  const DecAttnPlan self_plan = plan_dec_attn(e, false, B, Ld, Ld, d.n_heads, tree ? tree->rows : 0);
+  ns.begin(e, st, ragged && rows->ids ? rows->ids : sl.d_dec_ids, M, dfold);
+  const DecAttnPlan self_plan = plan_dec_attn(e, false, B, Ld, Ld, d.n_heads, tree ? rows->rows : 0);
   const DecAttnPlan cross_plan = plan_dec_attn(e, true, B, Ld, sl.maxL, d.n_heads, 0);
   for (int l = 0; l < d.n_dec_layers; ++l) {
     const DecLayerW& w = e->dec[l];
-    if (!cache && Ld == 1) {
+    if (!cache && lc.one) {
       // one decoder position: softmax over a single key is 1, so self-attention is exactly o(v(x)) — the q/k
       // projections, scores and bias are dead (hf: modeling_t5.py:448-509 at L_d = 1)
       // ... and o(v(x)) = (W_o W_v) x: one GEMM with the product matrix formed once at finalize
@@ -1017,23 +1056,25 @@ int run_decoder(rk_engine* e, Slot& sl, int Ld, const DecTree* tree = nullptr, c
         }
       } else {
         launch_dec_attn(e, st, self_plan, AttnDecArgs{sl.dqkv, 3 * I, sl.dqkv + I, sl.dqkv + 2 * I, 3 * I, nullptr, sl.dctx, I, e->lut_dec, Ld, 1, Ld,
-                                                      tree ? tree->keys : nullptr, tree ? tree->pos : nullptr}, 4.0 * M * Ld * I, 0);
+                                                      tree ? rows->keys : nullptr, tree ? rows->pos : nullptr, 0, ragged ? rows->row_off : nullptr},
+                        4.0 * M * Ld * I, 0);
       }
       RC(resid(Gemm(PC_DEC_GEMM, EPI_RESID_F32, sl.dctx, I, w.o, I, ns.hidden, dm, M, dm, I)));
     }
     // the cross-attention q projection: a GEMM of its own, or fused into launch_xattn's first kernel, which takes the same norm hooks
     const Gemm cq = normed(w.ln1, Gemm(PC_DEC_GEMM, EPI_STORE_F16, ns.x(), dm, dfold ? w.cq_f : w.cq, dm, sl.dq, I, M, I, dm));
     if (!fuse) RC(gemm(e, st, cq));
-    if (!sl.have_cross_kv) {
+    if (!have_kv) {
       // in blocks of rows that fit the workspace
       const int blk = std::max(1, std::min(XA_MAX_ROWS, XA_MAX_CHUNKS / ((sl.maxL + 63) / 64)));
       for (int r0 = 0; r0 < M; r0 += blk) {
         const XAttnPlan xp = plan_xattn(e, fuse, std::min(blk, M - r0), sl.maxL, d.n_heads, dm);
-        RC(launch_xattn(e, st, sl, xp, l, Ld, r0, cq.A, cq.W, cq.fold, tree ? tree->seq : nullptr));
+        RC(launch_xattn(e, st, sl, xp, l, Ld, r0, cq.A, cq.W, cq.fold, rows ? rows->seq : nullptr));
       }
     } else {
       const half_t* kv = sl.cross_kv + (size_t)l * d.max_tokens * 2 * I;
-      launch_dec_attn(e, st, cross_plan, AttnDecArgs{sl.dq, I, kv, kv + I, 2 * I, sl.d_seq_off, sl.dctx, I, nullptr, Ld, 0, sl.maxL},
+      launch_dec_attn(e, st, cross_plan, AttnDecArgs{sl.dq, I, kv, kv + I, 2 * I, seq_off, sl.dctx, I, nullptr, Ld, 0, sl.maxL, nullptr, nullptr, 0,
+                                                       ragged ? rows->row_off : nullptr},
                       4.0 * Ld * (double)sl.T * I, (double)sl.T * 2 * I * 2.0);
     }
     RC(resid(Gemm(PC_DEC_GEMM, EPI_RESID_F32, sl.dctx, I, w.co, I, ns.hidden, dm, M, dm, I)));
@@ -1046,7 +1087,7 @@ int run_decoder(rk_engine* e, Slot& sl, int Ld, const DecTree* tree = nullptr, c
       // measured the same on either family and stay where they were.
       // (Many rows, or a forced tile shape: the persistent ping-pong kernel takes its row factors ready-made - same block sums,
       // same rk_row_factor, same bits as the fill-in kernels form in their epilogue.)
-      const bool tiled_in = dfold && e->opt.dec_ffn_tiled && Ld == 1;
+      const bool tiled_in = dfold && e->opt.dec_ffn_tiled && lc.one;
       RC(gemm(e, st, ns.consumer(e, st, w.ln2, Gemm(PC_DEC_GEMM, d.gated_gelu ? EPI_GEGLU_F16 : EPI_RELU_F16, ns.x(), dm, dfold ? w.ffn_in_f : w.ffn_in, dm,
                                                    sl.dffh, F, M, d.gated_gelu ? 2 * F : F, dm).on(tiled_in ? GEMM_TILED : fam), true)));
     }
@@ -1061,16 +1102,21 @@ int run_decoder(rk_engine* e, Slot& sl, int Ld, const DecTree* tree = nullptr, c
 // Encoder on s_enc, decoder on s_dec, ordered by events; the decoder of this slot's PREVIOUS batch must have
 // finished reading cross_kv before the encoder overwrites it.
 // query_side: the caller's decoder takes the query-side cross-attention whatever its length (rk_t5_generate: one row per step).
-int encoder_then_handoff(rk_engine* e, Slot& sl, int max_ld, bool query_side = false) {
+// need_cross_kv: some decoder pass of the call reads the materialised K / V.
+int encoder_then_handoff_kv(rk_engine* e, Slot& sl, bool need_cross_kv) {
   hipStream_t se = enc_stream(e, sl), sd = dec_stream(e, sl);
   if (sl.dec_pending && sd != se) HIPCHK(e, hipStreamWaitEvent(se, sl.ev_dec, 0));
-  int rc = run_encoder(e, sl, !query_side && !use_xattn_direct(e, sl, max_ld));
+  int rc = run_encoder(e, sl, need_cross_kv);
   if (rc) return rc;
   if (sd != se) {
     HIPCHK(e, hipEventRecord(sl.ev_enc, se));
     HIPCHK(e, hipStreamWaitEvent(sd, sl.ev_enc, 0));
   }
   return RK_OK;
+}
+
+int encoder_then_handoff(rk_engine* e, Slot& sl, int max_ld, bool query_side = false) {
+  return encoder_then_handoff_kv(e, sl, !query_side && !use_xattn_direct(e, sl, max_ld));
 }
 
 int mark_decoder_done(rk_engine* e, Slot& sl) {
@@ -1675,7 +1721,7 @@ int rk_engine_finalize(rk_engine* e) {
     RC(dalloc(e, &sl.d_tokens, Tc)); RC(dalloc(e, &sl.d_seq_off, Bc + 1));
     RC(dalloc(e, &sl.cross_kv, (size_t)d.n_dec_layers * Tc * 2 * I));
     RC(dalloc(e, &sl.d_dec_ids, Mc)); RC(dalloc(e, &sl.d_last_rows, Bc)); RC(dalloc(e, &sl.d_out_ids, 8192));
-    RC(dalloc(e, &sl.d_labels, (size_t)d.max_dec_len)); RC(dalloc(e, &sl.d_argmax, Bc));
+    RC(dalloc(e, &sl.d_row_label, Mc)); RC(dalloc(e, &sl.d_row_off, 2 * Bc + 1)); RC(dalloc(e, &sl.d_out_idx, Bc)); RC(dalloc(e, &sl.d_argmax, Bc));
     RC(dalloc(e, &sl.d_row_seq, Mc)); RC(dalloc(e, &sl.d_tree_keys, Mc * (size_t)d.max_dec_len)); RC(dalloc(e, &sl.d_tree_pos, Mc));
     RC(dalloc(e, &sl.dec.hidden, Mc * dm)); RC(dalloc(e, &sl.dec.xn, Mc * dm)); RC(dalloc(e, &sl.dqkv, Mc * 3 * I));
     RC(dalloc(e, &sl.dctx, Mc * I)); RC(dalloc(e, &sl.dq, Mc * I)); RC(dalloc(e, &sl.dffh, Mc * F));
@@ -1765,18 +1811,114 @@ int rk_t5_qlm(rk_engine* e, const int32_t* tokens, const int32_t* seq_offsets, i
   for (int t = 1; t < n_labels; ++t) dec_in[t] = labels[t - 1];
   hipStream_t sd = dec_stream(e, sl);
   if ((rc = upload_dec_ids_shared(e, sl, dec_in.data(), n_labels))) return rc;
-  HIPCHK(e, hipStreamSynchronize(sd));
-  HIPCHK(e, hipMemcpy(sl.d_labels, labels, n_labels * sizeof(int), hipMemcpyHostToDevice));
   const int M = n_seq * n_labels;
+  std::vector<int> row_label((size_t)M);   // the head's label per ROW (the array rk_t5_qlm_many fills per sequence)
+  for (int b = 0; b < n_seq; ++b) memcpy(&row_label[(size_t)b * n_labels], labels, n_labels * sizeof(int));
+  HIPCHK(e, hipStreamSynchronize(sd));
+  HIPCHK(e, hipMemcpy(sl.d_row_label, row_label.data(), row_label.size() * sizeof(int), hipMemcpyHostToDevice));
   if ((rc = ensure_logits(e, M))) return rc;
   if ((rc = encoder_then_handoff(e, sl, n_labels))) return rc;
   if ((rc = run_decoder(e, sl, n_labels))) return rc;
   rmsnorm(e, sd, sl.dec.hidden, e->dec_final_ln, sl.dec.xn, nullptr, M, head_scale(e));
   // head GEMM with the log-sum-exp fused into its epilogue: per row and 32-column block (max, sum exp) + the label's logit
   const int nblk = (e->d.vocab + 31) / 32;
-  e->lse_labels = sl.d_labels; e->lse_npos = n_labels; e->lse_xlab = e->logits.p + (size_t)M * nblk * 2;
+  e->lse_labels = sl.d_row_label; e->lse_xlab = e->logits.p + (size_t)M * nblk * 2;
   RC(gemm(e, sd, Gemm(PC_HEAD, EPI_LSE_F32, sl.dec.xn, e->d.d_model, e->lm_head, e->d.d_model, e->logits.p, nblk, M, e->d.vocab, e->d.d_model)));
-  hipLaunchKernelGGL(qlm_lse_kernel, dim3(n_seq), dim3(256), 0, sd, (const float2*)e->logits.p, nblk, e->lse_xlab, n_labels, sl.d_scores);
+  hipLaunchKernelGGL(qlm_lse_kernel, dim3(n_seq), dim3(256), 0, sd, (const float2*)e->logits.p, nblk, e->lse_xlab, n_labels, nullptr, nullptr, sl.d_scores);
+  HIPCHK(e, hipMemcpyAsync(sl.h_scores, sl.d_scores, (size_t)n_seq * sizeof(float), hipMemcpyDeviceToHost, sd));
+  RC(finish_blocking(e, sl));
+  HIPCHK(e, hipGetLastError());
+  memcpy(out_scores, sl.h_scores, (size_t)n_seq * sizeof(float));
+  return RK_OK;
+}
+
+// rk_t5_qlm for sequences that each score their OWN label sequence.  A sequence's score is bit for bit what rk_t5_qlm gives it
+// with those labels, whatever shares the call: the sequences are ordered by the class of their label count (dec_len_class - the
+// encoder does not care about order), the encoder runs ONCE over all of them (cross K / V materialised iff some class reads
+// them), then every non-empty class is one ragged decoder pass + final norm + LSE head over its contiguous sequence range, and
+// qlm_lse_kernel writes each score at the sequence's place in the caller's order.  (A pass of at most dec_gemv_rows rows at two
+// or more positions takes the few-row GEMV family, as in rk_t5_qlm: DESIGN.md section 4.)
+int rk_t5_qlm_many(rk_engine* e, const int32_t* tokens, const int32_t* seq_offsets, int n_seq, const int32_t* labels,
+                   const int32_t* label_offsets, float* out_scores) {
+  if (!e) return RK_ERR_INVALID;
+  if (e->family != 0) return fail(e, RK_ERR_STATE, "T5 entry point called on a Llama engine (use rk_llama_*)");
+  if (!e->finalized) return fail(e, RK_ERR_STATE, "engine not finalized");
+  if (!tokens || !seq_offsets || n_seq <= 0 || !out_scores) return fail(e, RK_ERR_INVALID, "empty batch (n_seq=%d)", n_seq);
+  if (n_seq > e->d.max_seqs) return fail(e, RK_ERR_CAPACITY, "n_seq %d > max_seqs %d", n_seq, e->d.max_seqs);
+  if (!labels || !label_offsets) return fail(e, RK_ERR_INVALID, "labels missing");
+  if (seq_offsets[0] != 0 || label_offsets[0] != 0) return fail(e, RK_ERR_INVALID, "seq_offsets[0] and label_offsets[0] must be 0");
+  const int max_ld = e->d.max_dec_len;
+  for (int b = 0; b < n_seq; ++b) {
+    const int nb = label_offsets[b + 1] - label_offsets[b];
+    if (nb <= 0 || nb > max_ld) return fail(e, RK_ERR_CAPACITY, "sequence %d: n_labels %d out of range (max %d)", b, nb, max_ld);
+    if (seq_offsets[b + 1] <= seq_offsets[b]) return fail(e, RK_ERR_INVALID, "sequence %d is empty", b);
+  }
+  int rc;
+  if ((rc = check_ids(e, labels, label_offsets[n_seq], "label"))) return rc;
+  // class index of every label count, in order of first appearance as the count grows; the sequences in class order (stable)
+  std::vector<int> cls_of((size_t)max_ld + 1, 0), keys;
+  std::vector<DecLenClass> classes;
+  for (int n = 1; n <= max_ld; ++n) {
+    const DecLenClass c = dec_len_class(e, n);
+    size_t i = 0;
+    while (i < keys.size() && keys[i] != c.key()) ++i;
+    if (i == keys.size()) { keys.push_back(c.key()); classes.push_back(c); }
+    cls_of[n] = (int)i;
+  }
+  auto n_of = [&](int b) { return label_offsets[b + 1] - label_offsets[b]; };
+  std::vector<int> order((size_t)n_seq);
+  for (int b = 0; b < n_seq; ++b) order[b] = b;
+  std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return cls_of[n_of(x)] < cls_of[n_of(y)]; });
+  std::vector<int> ptok((size_t)seq_offsets[n_seq]), poff((size_t)n_seq + 1, 0);
+  for (int s = 0; s < n_seq; ++s) {
+    const int b = order[s], L = seq_offsets[b + 1] - seq_offsets[b];
+    memcpy(&ptok[poff[s]], tokens + seq_offsets[b], (size_t)L * sizeof(int));
+    poff[s + 1] = poff[s] + L;
+  }
+  if ((rc = rk_t5_stage(e, ptok.data(), poff.data(), n_seq))) return rc;
+  Slot& sl = e->slots[0];
+  hipStream_t sd = dec_stream(e, sl);
+  // per row, pass after pass: decoder id (shift_right of the sequence's labels; hf: modeling_t5.py:618-637), label, sequence;
+  // per pass: its sequences' row offsets (relative to the pass)
+  struct Pass { int s0, s1, r0, rows, ld, off0; DecLenClass c; };
+  std::vector<Pass> passes;
+  std::vector<int> ids, rlab, rseq, roff;
+  bool need_kv = false;
+  int max_rows = 0;
+  for (int s = 0; s < n_seq;) {
+    Pass p{s, s, (int)ids.size(), 0, 0, (int)roff.size(), classes[cls_of[n_of(order[s])]]};
+    while (p.s1 < n_seq && cls_of[n_of(order[p.s1])] == cls_of[n_of(order[s])]) {
+      const int b = order[p.s1], nb = n_of(b);
+      const int32_t* lab = labels + label_offsets[b];
+      roff.push_back(p.rows);
+      for (int t = 0; t < nb; ++t) { ids.push_back(t ? lab[t - 1] : 0); rlab.push_back(lab[t]); rseq.push_back(p.s1); }
+      p.rows += nb; p.ld = std::max(p.ld, nb); ++p.s1;
+    }
+    roff.push_back(p.rows);
+    need_kv = need_kv || !p.c.direct;
+    max_rows = std::max(max_rows, p.rows);
+    passes.push_back(p);
+    s = p.s1;
+  }
+  if ((rc = ensure_logits(e, (size_t)max_rows))) return rc;
+  HIPCHK(e, hipStreamSynchronize(sd));
+  HIPCHK(e, hipMemcpy(sl.d_dec_ids, ids.data(), ids.size() * sizeof(int), hipMemcpyHostToDevice));
+  HIPCHK(e, hipMemcpy(sl.d_row_label, rlab.data(), rlab.size() * sizeof(int), hipMemcpyHostToDevice));
+  HIPCHK(e, hipMemcpy(sl.d_row_seq, rseq.data(), rseq.size() * sizeof(int), hipMemcpyHostToDevice));
+  HIPCHK(e, hipMemcpy(sl.d_row_off, roff.data(), roff.size() * sizeof(int), hipMemcpyHostToDevice));
+  HIPCHK(e, hipMemcpy(sl.d_out_idx, order.data(), order.size() * sizeof(int), hipMemcpyHostToDevice));
+  sl.cache_dec.clear(); ++sl.dec_epoch;   // the shared decoder id / row buffers were written
+  if ((rc = encoder_then_handoff_kv(e, sl, need_kv))) return rc;
+  const int nblk = (e->d.vocab + 31) / 32;
+  for (const Pass& p : passes) {
+    const DecRows rows{p.rows, nullptr, nullptr, sl.d_row_seq + p.r0, sl.d_row_off + p.off0, p.s0, p.s1 - p.s0, !p.c.direct, sl.d_dec_ids + p.r0};
+    if ((rc = run_decoder(e, sl, p.ld, &rows))) return rc;
+    rmsnorm(e, sd, sl.dec.hidden, e->dec_final_ln, sl.dec.xn, nullptr, p.rows, head_scale(e));
+    e->lse_labels = sl.d_row_label + p.r0; e->lse_xlab = e->logits.p + (size_t)p.rows * nblk * 2;
+    RC(gemm(e, sd, Gemm(PC_HEAD, EPI_LSE_F32, sl.dec.xn, e->d.d_model, e->lm_head, e->d.d_model, e->logits.p, nblk, p.rows, e->d.vocab, e->d.d_model)));
+    hipLaunchKernelGGL(qlm_lse_kernel, dim3(p.s1 - p.s0), dim3(256), 0, sd, (const float2*)e->logits.p, nblk, e->lse_xlab, 0,
+                       sl.d_row_off + p.off0, sl.d_out_idx + p.s0, sl.d_scores);
+  }
   HIPCHK(e, hipMemcpyAsync(sl.h_scores, sl.d_scores, (size_t)n_seq * sizeof(float), hipMemcpyDeviceToHost, sd));
   RC(finish_blocking(e, sl));
   HIPCHK(e, hipGetLastError());
@@ -1989,7 +2131,7 @@ int rk_t5_greedy2(rk_engine* e, const int32_t* tokens, const int32_t* seq_offset
     sl.cache_g2.swap(sig);
     sl.g2_epoch = ++sl.dec_epoch;
   }
-  const DecTree tree{(int)M, sl.d_tree_keys, sl.d_tree_pos, sl.d_row_seq};
+  const DecRows tree{(int)M, sl.d_tree_keys, sl.d_tree_pos, sl.d_row_seq};
   rc = run_graphed(e, sd, {2, 0, n_seq, Ld, (sl.maxL + 63) / 64, n_cand, e->amax_gen}, [&]() -> int {
     const int r = run_decoder(e, sl, Ld, &tree);
     return r ? r : final_argmax(e, sd, sl, sl.d_last_rows, (int)R);

@@ -47,6 +47,7 @@ ABI = {
     "rk_engine_finalize": (C.c_int, [C.c_void_p]),
     "rk_t5_score": (C.c_int, [C.c_void_p, _i32p, _i32p, C.c_int, _i32p, C.c_int, _i32p, C.c_int, _f32p]),
     "rk_t5_qlm": (C.c_int, [C.c_void_p, _i32p, _i32p, C.c_int, _i32p, C.c_int, _f32p]),
+    "rk_t5_qlm_many": (C.c_int, [C.c_void_p, _i32p, _i32p, C.c_int, _i32p, _i32p, _f32p]),
     "rk_t5_greedy": (C.c_int, [C.c_void_p, _i32p, _i32p, C.c_int, _i32p, C.c_int, C.c_int, C.c_int, C.c_int, _i32p, _i32p]),
     "rk_t5_greedy2": (C.c_int, [C.c_void_p, _i32p, _i32p, C.c_int, _i32p, C.c_int, _i32p, C.c_int, C.c_int, C.c_int, _i32p, _i32p]),
     "rk_t5_generate": (C.c_int, [C.c_void_p, _i32p, _i32p, C.c_int, _i32p, C.c_int, C.c_int, C.c_int, C.c_int, _i32p, _i32p]),
@@ -210,6 +211,18 @@ class RkEngine:
         out = np.empty(len(seqs), dtype=np.float32)
         self._chk(self.lib.rk_t5_qlm(self.h, tok.ctypes.data_as(_i32p), off.ctypes.data_as(_i32p), len(seqs),
                                      lab.ctypes.data_as(_i32p), len(lab), out.ctypes.data_as(_f32p)))
+        return out
+
+    def qlm_many(self, seqs: Sequence[Sequence[int]], labels_per_seq: Sequence[Sequence[int]]) -> np.ndarray:
+        """qlm scores of sequences that each score their OWN label sequence, in one engine call (rk_t5_qlm_many): element b is
+        bit for bit qlm([seqs[b]], labels_per_seq[b])[0] in a batch that stays off the few-row family."""
+        if len(labels_per_seq) != len(seqs):
+            raise ValueError(f"{len(seqs)} sequences but {len(labels_per_seq)} label sequences")
+        tok, off = pack_ragged(seqs)
+        lab, loff = pack_ragged(labels_per_seq)
+        out = np.empty(len(seqs), dtype=np.float32)
+        self._chk(self.lib.rk_t5_qlm_many(self.h, tok.ctypes.data_as(_i32p), off.ctypes.data_as(_i32p), len(seqs),
+                                          lab.ctypes.data_as(_i32p), loff.ctypes.data_as(_i32p), out.ctypes.data_as(_f32p)))
         return out
 
     def greedy(self, seqs: Sequence[Sequence[int]], dec_prefix: Sequence[int], max_new: int, eos_id: int = 1,

@@ -205,9 +205,13 @@ class T5Runtime:
         k = len(out_ids) if kind == "score" else 1
         if tail is not None and len(tail):
             self.engine.comm_append_host(np.asarray(tail, dtype=np.float32), tail_offset)
-        parts, off = [], 0
+        parts, off, done = [], 0, 0
         for chunk in self._chunks(seqs):
-            part = self.engine.qlm(chunk, arg) if kind == "qlm" else self.engine.score(chunk, arg, out_ids)
+            if kind == "qlm_many":                               # arg = one label sequence per sequence (several queries' shares)
+                part = self.engine.qlm_many(chunk, arg[done:done + len(chunk)])
+            else:
+                part = self.engine.qlm(chunk, arg) if kind == "qlm" else self.engine.score(chunk, arg, out_ids)
+            done += len(chunk)
             n = len(chunk) * k
             self.engine.comm_append(n, off, slot=0)              # blocking calls leave their scores in slot 0
             parts.append(np.asarray(part, dtype=np.float32).reshape(-1))
@@ -310,6 +314,15 @@ class T5Runtime:
 
     def qlm(self, seqs, labels) -> np.ndarray:
         return np.concatenate([self.engine.qlm(c, labels) for c in self._chunks(seqs)], axis=0)
+
+    def qlm_many(self, seqs, labels_per_seq) -> np.ndarray:
+        """qlm scores of sequences with their OWN labels each (the passages of several queries): one engine call per capacity
+        chunk, whatever the number of queries in it.  Element b is bit for bit what qlm gives seqs[b] with labels_per_seq[b]."""
+        parts, done = [], 0
+        for c in self._chunks(seqs):
+            parts.append(self.engine.qlm_many(c, labels_per_seq[done:done + len(c)]))
+            done += len(c)
+        return np.concatenate(parts, axis=0) if parts else np.zeros(0, np.float32)
 
     def qlm_batches(self, batches, labels) -> List[np.ndarray]:
         """qlm scores of several batches of ONE query (same labels): the reference's batch_size only shapes its host loop and a

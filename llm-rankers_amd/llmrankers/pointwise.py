@@ -182,7 +182,10 @@ class PointwiseLlmRanker(LlmRanker):
         the raw outputs and the prompts' token counts of all of them.  A rank's row: its scores packed in query order
         [sum_q n_rq * k], then at offset W * k (W = sum_q of the widest share) the token counts [sum_q n_rq].  Rankings, scores
         and counters are those of `rerank` query by query (a passage's score does not depend on what shares its call).
-        Returns None when the queries cannot share a call (mixed call shapes, a row beyond the communicator's capacity)."""
+        qlm groups the same way when the runtime has `qlm_many`: every passage goes to the engine with its own query's labels
+        (rk_t5_qlm_many), k = 1, the counters from each query's own label count.
+        Returns None when the queries cannot share a call (mixed call shapes, a row beyond the communicator's capacity, qlm on
+        a runtime without `qlm_many`)."""
         from . import _dist
         rank, ws = _dist.world()
         if ws == 1 and getattr(self.llm, "comm_ready", lambda: False)():
@@ -192,22 +195,24 @@ class PointwiseLlmRanker(LlmRanker):
             bounds = _dist.shard_bounds(len(ranking), ws)
             s, e = bounds[rank]
             spec = self._spec(query, ranking[s:e])
-            if spec is None or spec[1] != "score" or (plans and (spec[2], spec[3]) != (plans[0][2][2], plans[0][2][3])):
+            if spec is None or not self._can_share(spec, plans[0][2] if plans else None):
                 return None
             plans.append((bounds, (s, e), spec))
             W += max(b - a for a, b in bounds)
         if not plans or W == 0:
             return None
-        arg, out_ids, dec_len = plans[0][2][2], plans[0][2][3], plans[0][2][4]
-        k = len(out_ids)
+        kind, arg, out_ids = plans[0][2][1], plans[0][2][2], plans[0][2][3]
+        k = len(out_ids) if kind == "score" else 1
         row = W * (k + 1)
         have_comm = getattr(self.llm, "ensure_comm", lambda: False)()
         if have_comm and row > self.llm.comm_capacity:
             return None
         flat = [q for _, _, spec in plans for q in tokenize_prompts(self.tokenizer, spec[0])]
         lens = np.asarray([len(q) for q in flat], dtype=np.float32)
+        if kind == "qlm":                                                 # one label sequence per passage: its query's
+            kind, arg = "qlm_many", [spec[2] for _, (s, e), spec in plans for _ in range(e - s)]
         if have_comm:
-            local, allv = self.llm.sharded_scores("score", flat, arg, out_ids, row, tail=lens, tail_offset=W * k)
+            local, allv = self.llm.sharded_scores(kind, flat, arg, out_ids, row, tail=lens, tail_offset=W * k)
             assert len(local) == len(flat) * k
             allv = np.asarray(allv, dtype=np.float32).reshape(ws, row)
         else:
@@ -216,7 +221,10 @@ class PointwiseLlmRanker(LlmRanker):
                 raise RuntimeError("candidate sharding needs a runtime with a communicator (T5Runtime) or a host_all_gather of its own")
             chunks = [flat[i:j] for i, j in batches(len(flat), self.batch_size)]
             local = np.zeros(row, np.float32)
-            local[:len(flat) * k] = self._raw(chunks, "score", arg, out_ids).reshape(-1)
+            if kind == "qlm_many":
+                local[:len(flat)] = np.asarray(self.llm.qlm_many(flat, arg), dtype=np.float32).reshape(-1) if flat else 0
+            else:
+                local[:len(flat) * k] = self._raw(chunks, "score", arg, out_ids).reshape(-1)
             local[W * k:W * k + len(flat)] = lens
             allv = gather(local, row)
         out, counters = [], []
@@ -227,12 +235,20 @@ class PointwiseLlmRanker(LlmRanker):
             for r, (a, b) in enumerate(bounds):
                 pos[r] += b - a
             self._reset()
-            self._count_from_lengths(np.rint(all_lens).astype(np.int64), dec_len)
+            self._count_from_lengths(np.rint(all_lens).astype(np.int64), spec[4])   # (qlm: the query's own label count)
             counters.append((self.total_compare, self.total_prompt_tokens, self.total_completion_tokens))
-            for doc, sc in zip(ranking, spec[5](raw.reshape(-1, k))):
+            for doc, sc in zip(ranking, spec[5](raw.reshape(-1, k) if spec[1] == "score" else raw)):
                 doc.score = float(sc)
             out.append(sorted(ranking, key=lambda x: x.score, reverse=True))
         return out, counters
+
+    def _can_share(self, spec, first) -> bool:
+        """May the query behind `spec` share an engine call with the group that `first` (its first spec, or None) opened?
+        'score' queries need the same decoder prefix and output ids; 'qlm' queries bring their own labels per passage and
+        need a runtime with `qlm_many` (test doubles without it keep the one-by-one path)."""
+        if spec[1] == "qlm":
+            return hasattr(self.llm, "qlm_many") and (first is None or first[1] == "qlm")
+        return spec[1] == "score" and (first is None or (first[1] == "score" and (spec[2], spec[3]) == (first[2], first[3])))
 
     def rerank(self, query: str, ranking: List[SearchResult]) -> List[SearchResult]:
         if self.shard_candidates:
@@ -257,8 +273,10 @@ class PointwiseLlmRanker(LlmRanker):
         query at a time (ref: run.py:183-201); a passage's score does not depend on what shares its engine call (ragged
         execution, bit-exact), so the batches of all the queries go to the engine together - its GEMMs then run on several
         hundred passages instead of a hundred and the decoder chain runs once (grouped launches).
-        Candidate-sharded runs group the same way (_rerank_sharded_many: every rank's share of every query in one launch
-        sequence, ONE all_gather); qlm (per-query labels) and unknown methods take the one-by-one path."""
+        qlm groups too: every passage travels with its own query's labels (T5Runtime.qlm_many -> rk_t5_qlm_many, whose score
+        for a passage is bit for bit rk_t5_qlm's); a query's labels are tokenised once.  Candidate-sharded runs group the
+        same way (_rerank_sharded_many: every rank's share of every query in one launch sequence, ONE all_gather).  Unknown
+        methods, and qlm on a runtime without `qlm_many` (test doubles), take the one-by-one path."""
         items = list(items)
         specs = []
         if self.shard_candidates and items:
@@ -271,7 +289,7 @@ class PointwiseLlmRanker(LlmRanker):
         for query, ranking in items:
             spec = self._spec(query, ranking) if grouped else None
             specs.append(spec)
-            if spec is None or spec[1] != "score" or (specs[0] is not None and (spec[2], spec[3]) != (specs[0][2], specs[0][3])):
+            if spec is None or specs[0] is None or not self._can_share(spec, specs[0] if len(specs) > 1 else None):
                 grouped = False
         if not grouped or not items:
             out, counters = [], []
@@ -292,7 +310,14 @@ class PointwiseLlmRanker(LlmRanker):
                 sizes.append(len(prompts))
                 yield chunks
 
-        if hasattr(self.llm, "score_stream"):
+        if specs[0][1] == "qlm":
+            flat, labels_per_seq = [], []
+            for chunks, spec in zip(tokenised_queries(), specs):
+                seqs = [s for c in chunks for s in c]
+                flat.extend(seqs)
+                labels_per_seq.extend([spec[2]] * len(seqs))
+            raw = np.asarray(self.llm.qlm_many(flat, labels_per_seq), dtype=np.float32).reshape(-1) if flat else np.zeros(0, np.float32)
+        elif hasattr(self.llm, "score_stream"):
             raw = self.llm.score_stream(([s for c in chunks for s in c] for chunks in tokenised_queries()), specs[0][2], specs[0][3])
         else:                                                        # a runtime without batch slots (test doubles): batch by batch
             raw = self._raw([c for chunks in tokenised_queries() for c in chunks], "score", specs[0][2], specs[0][3])
