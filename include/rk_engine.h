@@ -223,8 +223,51 @@ int rk_abi_version(void);
 int rk_rel_bucket(int relative_position, int bidirectional, int num_buckets, int max_distance);
 /* debug: run one GEMM through the engine's kernel on host data (A[M,K] fp16, W[N,K] fp16 -> C[M,N] fp32);
  * use_glds: 1 = tiled kernel with LDS-DMA staging, 0 = register staging, 2 = the weight-streaming (decoder) kernel,
- * 3 = the few-row GEMV kernel (M <= 16, K <= 3072; falls back to 2 otherwise) */
+ * 3 = the few-row GEMV kernel (M <= 16, K <= 3072; fails otherwise).  A thin call into rk_debug_gemm_ex. */
 int rk_debug_gemm(rk_engine* e, const uint16_t* A, const uint16_t* W, float* C, int M, int N, int K, int use_glds);
+/* debug: run ANY call of the engine's GEMM (csrc/rk_engine.hip: struct Gemm -> plan_gemm -> the launchers, nothing of its own)
+ * on host data, every output inside guard bands.  The call is described as the engine describes it:
+ *   epi     0 store f16, 1 residual f32 (C += acc), 2 GEGLU f16, 3 ReLU f16, 4 store f32, 5 SwiGLU f16 (2 / 5: W rows interleaved
+ *           gate / up in groups of 32, N / 2 output columns), 6 argmax blocks (C = float maxima, idx = int first columns, one per
+ *           32-column block, ldc = blocks per row), 7 log-sum-exp blocks (C = float2 (max, sum exp(x - max)) per 32-column block,
+ *           labels[M] in, xlab[M] out: the label's logit)
+ *   family  0 tiled MFMA kernels (engine options gemm_variant / gemm_glds / gemm_sk / gemm_s64_stages / gemm_split choose among
+ *           them as they do for the engine), 1 weight-streaming, 2 few-row GEMV
+ *   A, W    host fp16, a_elems / w_elems elements; the call reads A[b * bsA + m * lda + k], W[b * bsW + n * ldw + k]
+ *   C       host INTERIOR of the output, c_elems elements of the output type (2 bytes for the f16 epilogues, 4 for f32 and argmax,
+ *           8 for epi 7), copied to the device as it is (residual input; the caller pre-fills what the call must not touch, e.g.
+ *           pad columns of ldc > N); the call's C pointer is interior + c_off
+ *   C_out   host, band_rows * ldc + c_elems + band_rows * ldc elements: the WHOLE device allocation after the call - a band in
+ *           front and one behind the interior, each band_rows (>= 256, one tile panel) rows of ldc elements, filled with the
+ *           byte RK_DEBUG_SENTINEL before the call.  idx_out (epi 6): the same layout in ints.
+ *   optional (null / 0 when unused): rowscale[M] or ssq_in[M][nb_in] (folded-RMSNorm consumer; factors_kernel != 0: the engine's
+ *           rowscale_kernel turns ssq_in into the row factors in front of the call, as it does for the ping-pong kernel), xraw_out / ssq_out (producer:
+ *           fp16 [band | M x N | band] and float [band | M x nb | band] with bands of band_rows rows, sentinel-filled before the call;
+ *           ssq_cap = floats ssq_out holds; the plan's nb comes back in out_nb), n_split / split_stride, batch / bsA / bsW / bsC.
+ *   plan_only != 0: nothing is allocated or launched, only the out_* fields are filled.
+ * Every extent is checked against the sizes given before anything is launched.  A call outside the contract of its kernel family
+ * (plan_gemm; DESIGN.md "GEMM contract") fails with RK_ERR_STATE and launches nothing.  out_*: the plan (family, tile variant,
+ * rows on the ping-pong kernel, K split, statistics blocks) and what a test needs to predict it (CUs, eps, the xraw scale). */
+#define RK_DEBUG_SENTINEL 0xCD
+typedef struct rk_debug_gemm_call {
+  int epi, family;
+  int M, N, K, lda, ldw, ldc;
+  const uint16_t* A; int64_t a_elems;
+  const uint16_t* W; int64_t w_elems;
+  const void* C; int64_t c_elems, c_off;
+  void* C_out; int32_t* idx_out;
+  int band_rows;
+  const float* rowscale;
+  const float* ssq_in; int nb_in; int factors_kernel;
+  uint16_t* xraw_out; float* ssq_out; int64_t ssq_cap;
+  int n_split; int64_t split_stride;
+  int batch; int64_t bsA, bsW, bsC;
+  const int32_t* labels; float* xlab;
+  int plan_only;
+  int out_family, out_variant, out_m_pp2, out_ksplit, out_nb, out_n_cu;
+  float out_eps, out_xs;
+} rk_debug_gemm_call;
+int rk_debug_gemm_ex(rk_engine* e, rk_debug_gemm_call* call);
 /* measurement: average ms per launch of the engine's GEMM kernel at one shape (epi = 0 store f16, 1 residual f32,
  * 2 GEGLU, 3 ReLU, 4 store f32), random operands, `iters` back-to-back launches timed with HIP events */
 int rk_debug_gemm_bench(rk_engine* e, int M, int N, int K, int epi, int iters, float* out_ms);

@@ -375,6 +375,7 @@ struct Gemm {
 // Launch plan of one GEMM call: everything gemm() launches, decided here and nowhere else.
 struct GemmPlan {
   GemmFamily family = GEMM_NONE;   // NONE: no kernel runs the call as described (gemm() fails)
+  const char* why = "no kernel of the family has the epilogue";   // NONE: what the call breaks (gemm_contract)
   int nb = 0;        // partial sums of squares per row the launch writes to fold.ssq: the nb_in of the GEMMs that read them
   // TILED: rows [0, m_pp2) on the persistent ping-pong kernel in whole rounds over the CUs (K split ks_pp2), the rest on `variant`
   // (1 = 128x128, 2..4 = 256-row v2 tiles, 5 = ping-pong, 6 = 64x64 with `stages` LDS stages; K split `ksplit` on variant 5)
@@ -387,6 +388,57 @@ struct GemmPlan {
   bool pp2() const { return family == GEMM_TILED && (m_pp2 > 0 || variant == 5); }
 };
 
+// The CONTRACT of the kernel families (DESIGN.md "GEMM contract and how it is tested"): what the kernels require of a call, read off
+// their loads and stores - not what the engine's dimension checks happen to guarantee.  Returns nullptr when family `fam` runs the
+// call as described, else the reason; plan_gemm refuses (GEMM_NONE -> gemm() fails with RK_ERR_STATE) whatever breaks it, nothing
+// is launched.  tests/test_gpu_gemm_epilogues.py asserts both directions through rk_debug_gemm_ex.
+//   all       lda, ldw multiples of 8 halfs and >= K, A / W 16-byte aligned (16-byte operand pieces); ldc >= the output width
+//   TILED     K % 64 (whole K tiles).  gemm_epilogue_staged writes 16-byte pieces: fp16 outputs 8 columns (N % 8, ldc % 8, n_split
+//             % 8; N = 8j + 4 would put four halfs past column N - into the next row, or past C), fp32 outputs 4.  The folded-norm
+//             consumer exists for the fp16 epilogues only (the residual epilogues with prefetched old rows and the ping-pong kernel's
+//             fp32 / LSE instantiations never read the row factors); n_split not with the residual, gated or LSE epilogues (their
+//             old-row prefetch / block layout ignores it); producer statistics need 64-column wave tiles (never the 192-wide tile:
+//             choose_variant) and no n_split.  One launch: batch > 1 always goes to the weight-streaming kernel.
+//   STREAM    K % 16 (k16 steps), 4-column pieces (N % 4, ldc % 4) except argmax blocks; no n_split (plan_gemm sends such a call to
+//             the tiles); batches share neither fold buffers nor the argmax index buffer (not offset per batch)
+//   GEMV      M <= 16, K % 8, K <= 3072 (gemv_fits), scalar stores: any N, any ldc
+//   gated     N % 64 everywhere: gate / up rows interleaved in groups of 32, a 64-row weight tile = 32 output columns
+const char* gemm_contract(const Gemm& c, GemmFamily fam) {
+  const int epi = c.epi;
+  const bool gated = EPI_IS_GATED(epi), f16 = epi == EPI_STORE_F16 || epi == EPI_RELU_F16 || gated;
+  const bool blocks = epi == EPI_ARGMAX_F32 || epi == EPI_LSE_F32;
+  const bool consumer = c.fold.rowscale || c.fold.ssq_in, producer = c.fold.xraw || c.fold.ssq;
+  if (c.N <= 0 || c.K <= 0 || c.batch < 1 || c.n_split < 0) return "empty or negative shape";
+  if (c.lda < c.K || c.ldw < c.K || c.lda % 8 || c.ldw % 8 || c.bsA % 8 || c.bsW % 8 || ((uintptr_t)c.A | (uintptr_t)c.W) % 16)
+    return "A / W rows must be 16-byte aligned and at least K long";
+  if (gated && c.N % 64) return "gated epilogues pair gate / up rows in groups of 32: N % 64";
+  const int width = blocks ? (c.N + 31) / 32 : (c.n_split > 0 ? c.n_split : (gated ? c.N / 2 : c.N));
+  if (c.ldc < width) return "ldc smaller than the output width";
+  if (producer && (epi != EPI_RESID_F32 || !c.fold.xraw || !c.fold.ssq || c.n_split || c.batch > 1))
+    return "producer statistics: fp32 residual epilogue, one batch, no n_split, xraw and ssq together";
+  if (c.fold.ssq_in && c.fold.nb_in <= 0) return "ssq_in without nb_in";
+  if (consumer && c.batch > 1) return "folded-norm consumer: one batch";
+  if (fam == GEMM_GEMV) return nullptr;              // (gemv_fits, batch and n_split: plan_gemm)
+  const int piece = fam == GEMM_TILED && f16 ? 8 : 4;        // columns per store
+  const size_t cbytes = f16 ? 2 : 4;
+  if (!blocks) {
+    if (c.N % piece || c.ldc % piece || c.n_split % piece || c.split_stride % piece || c.bsC % piece || (uintptr_t)c.C % (piece * cbytes))
+      return fam == GEMM_TILED && f16 ? "tiled fp16 outputs are written in 8-column pieces: N, ldc, n_split % 8, C 16-byte aligned"
+                                      : "outputs are written in 4-column pieces: N, ldc, n_split % 4, C aligned to a piece";
+    if (c.n_split > 0 && c.N % c.n_split) return "n_split must divide N";
+  }
+  if (fam == GEMM_STREAM) {
+    if (c.K % 16) return "weight-streaming kernel: K % 16";
+    if (c.batch > 1 && epi == EPI_ARGMAX_F32) return "argmax blocks: one batch";
+    return nullptr;
+  }
+  if (c.batch > 1) return "tiled kernels: one batch (a batch with n_split has no kernel)";
+  if (c.K % 64) return "tiled kernels: K % 64";
+  if (consumer && !f16) return "tiled kernels: folded-norm consumer for the fp16 epilogues only";
+  if (c.n_split > 0 && (epi == EPI_RESID_F32 || gated || blocks)) return "tiled kernels: n_split for plain stores only";
+  return nullptr;
+}
+
 // Tiled family: the ping-pong kernel pays a full round for a partial one: the 100 passages of one query (M = 18 400: 72 row panels)
 // are 288 tiles of the O / FFN-out projections = 1.1 rounds paid as 2, 864 of QKV = 3.4 as 4.  All tile variants produce the same
 // bits (K order, epilogue statistics: tests), so the rows beyond the last whole round go to the cheapest fill-in variant as a second
@@ -398,17 +450,20 @@ GemmPlan plan_gemm(const rk_engine* e, const Gemm& c, hipStream_t st) {
   GemmPlan p;
   const int epi = c.epi, M = c.M, N = c.N, K = c.K;
   if (c.family == GEMM_GEMV) {                   // marked few-row by the caller: this kernel or none
-    if (gemv_has(epi) && gemv_fits(M, K) && c.batch == 1 && c.n_split == 0) {
+    if (!gemv_has(epi)) return p;
+    if (!(gemv_fits(M, K) && c.batch == 1 && c.n_split == 0)) { p.why = "few-row GEMV: M <= 16, K % 8, K <= 3072, one batch, no n_split"; return p; }
+    if ((p.why = gemm_contract(c, GEMM_GEMV)) == nullptr) {
       p.family = GEMM_GEMV;
       p.nb = gemv_grid(N, e->n_cu);              // producer: one partial sum of squares per workgroup
     }
     return p;
   }
   if ((c.family == GEMM_STREAM || c.batch > 1) && c.n_split == 0 && (((e->opt.skinny >> epi) & 1) || c.batch > 1 || epi == EPI_ARGMAX_F32)) {
-    if (stream_has(epi)) { p.family = GEMM_STREAM; p.nb = (N + 31) / 32; }   // producer blocks of 32 columns
+    if (stream_has(epi) && (p.why = gemm_contract(c, GEMM_STREAM)) == nullptr) { p.family = GEMM_STREAM; p.nb = (N + 31) / 32; }   // producer blocks of 32 columns
     return p;
   }
   if (!tiled_has(epi)) return p;
+  if ((p.why = gemm_contract(c, GEMM_TILED)) != nullptr) return p;
   p.family = GEMM_TILED;
   p.nb = (N + 63) / 64;                          // producer blocks of 64 columns
   p.wgs = e->opt.gemm_persistent == 1 ? (e->n_cu & ~7) : (e->opt.gemm_persistent & ~7);
@@ -442,6 +497,11 @@ GemmPlan plan_gemm(const rk_engine* e, const Gemm& c, hipStream_t st) {
     const int tiles = ((M - p.m_pp2 + 63) / 64) * ((N + 63) / 64);
     p.stages = e->opt.s64_stages;
     if (p.stages < 2 || p.stages > 4) p.stages = tiles <= 2 * e->n_cu ? 4 : (tiles <= 3 * e->n_cu ? 3 : 2);
+  }
+  if (p.pp2()) {
+    // the ping-pong kernel addresses its panels with 32-bit byte offsets and takes ready-made row factors only
+    if ((double)M * c.lda * 2 >= 4294967296.0 || (double)N * c.ldw * 2 >= 4294967296.0) { p.family = GEMM_NONE; p.why = "ping-pong kernel: an operand panel beyond 4 GiB"; }
+    else if (c.fold.ssq_in && !c.fold.rowscale) { p.family = GEMM_NONE; p.why = "ping-pong kernel: row factors ready-made (rowscale), not ssq_in"; }
   }
   return p;
 }
@@ -544,7 +604,7 @@ int gemm(rk_engine* e, hipStream_t st, const Gemm& c, int* nb = nullptr) {
   if (c.M <= 0) return RK_OK;
   const GemmPlan p = plan_gemm(e, c, st);
   if (p.family == GEMM_NONE)
-    return fail(e, RK_ERR_STATE, "no kernel of family %d takes the GEMM M=%d N=%d K=%d (epilogue %d, batch %d)", (int)c.family, c.M, c.N, c.K, c.epi, c.batch);
+    return fail(e, RK_ERR_STATE, "no kernel of family %d takes the GEMM M=%d N=%d K=%d (epilogue %d, batch %d): %s", (int)c.family, c.M, c.N, c.K, c.epi, c.batch, p.why ? p.why : "");
   if (nb) *nb = p.nb;
   GemmArgs a{c.A, c.W, c.C, c.lda, c.ldw, c.ldc, c.M, c.N, c.K, c.n_split, c.split_stride, 1.f, c.bsA, c.bsW, c.bsC};
   a.rowscale = c.fold.rowscale; a.xraw = c.fold.xraw; a.ssq = c.fold.ssq; a.ldx = c.N; a.nb = p.nb; a.xs = RK_XRAW_SCALE;
@@ -2762,26 +2822,127 @@ int rk_engine_set_option(rk_engine* e, const char* key, int value) {
   return fail(e, RK_ERR_INVALID, "unknown option %s", key);
 }
 
-int rk_debug_gemm(rk_engine* e, const uint16_t* A, const uint16_t* W, float* C, int M, int N, int K, int use_glds) {
-  if (!e || !A || !W || !C) return RK_ERR_INVALID;
+// debug: one Gemm call on host data, every output between sentinel bands (include/rk_engine.h).  No launch code of its own: it
+// builds the Gemm and calls gemm().
+int rk_debug_gemm_ex(rk_engine* e, rk_debug_gemm_call* q) {
+  if (!e || !q) return RK_ERR_INVALID;
   int rc = set_device(e);
   if (rc) return rc;
+  const int epi = q->epi, M = q->M, N = q->N, K = q->K, batch = q->batch > 0 ? q->batch : 1;
+  if (epi < 0 || epi > EPI_LSE_F32 || q->family < 0 || q->family > 2 || M <= 0 || N <= 0 || K <= 0 || q->lda <= 0 || q->ldw <= 0 || q->ldc <= 0 ||
+      q->n_split < 0 || q->split_stride < 0 || q->bsA < 0 || q->bsW < 0 || q->bsC < 0 || q->c_off < 0 || (long)M * batch > (1 << 22))
+    return fail(e, RK_ERR_INVALID, "debug gemm: bad shape");
+  const bool gated = EPI_IS_GATED(epi), blocks = epi == EPI_ARGMAX_F32 || epi == EPI_LSE_F32;
+  const bool f16 = epi == EPI_STORE_F16 || epi == EPI_RELU_F16 || gated;
+  const size_t celt = f16 ? 2 : (epi == EPI_LSE_F32 ? 8 : 4);
+  const GemmFamily fam = q->family == 2 ? GEMM_GEMV : (q->family == 1 ? GEMM_STREAM : GEMM_TILED);
+  const bool producer = q->xraw_out || q->ssq_out, planning = q->plan_only != 0;
+  // the plan first (pointers only count as aligned / present): a call outside the contract stops here, before any allocation
+  half_t* const dummy = (half_t*)(uintptr_t)256;
+  Gemm c(PC_OTHER, epi, dummy, q->lda, dummy, q->ldw, (char*)dummy + (size_t)q->c_off * celt, q->ldc, M, N, K);
+  c.on(fam).heads(batch, q->bsA, q->bsW, q->bsC).split(q->n_split, q->split_stride);
+  if (q->rowscale || (q->ssq_in && q->factors_kernel)) c.fold.rowscale = (const float*)dummy;
+  else if (q->ssq_in) { c.fold.ssq_in = (const float*)dummy; c.fold.nb_in = q->nb_in; }
+  if (q->ssq_in && q->nb_in <= 0) return fail(e, RK_ERR_INVALID, "debug gemm: ssq_in without nb_in");
+  if (producer) { c.fold.xraw = dummy; c.fold.ssq = (float*)dummy; }
+  hipStream_t st = e->slots[0].se;
+  const GemmPlan p = plan_gemm(e, c, st);
+  q->out_family = (int)p.family; q->out_variant = p.variant; q->out_m_pp2 = p.m_pp2; q->out_ksplit = p.m_pp2 > 0 ? p.ks_pp2 : p.ksplit;
+  q->out_nb = p.nb; q->out_n_cu = e->n_cu; q->out_eps = e->d.eps; q->out_xs = RK_XRAW_SCALE;
+  if (p.family == GEMM_NONE)
+    return fail(e, RK_ERR_STATE, "no kernel of family %d takes the GEMM M=%d N=%d K=%d (epilogue %d, batch %d): %s", (int)fam, M, N, K, epi, batch, p.why ? p.why : "");
+  if (planning) return RK_OK;
+  // extents, from the addressing of the call, against what the caller gave
+  if (!q->A || !q->W || !q->C || !q->C_out || q->band_rows < 256) return fail(e, RK_ERR_INVALID, "debug gemm: A, W, C, C_out and band_rows >= 256");
+  const long nsb = q->n_split > 0 ? (N + q->n_split - 1) / q->n_split : 1;
+  const long width = blocks ? (N + 31) / 32 : (q->n_split > 0 ? q->n_split : (gated ? N / 2 : N));
+  const long a_need = (long)(batch - 1) * q->bsA + (long)(M - 1) * q->lda + K, w_need = (long)(batch - 1) * q->bsW + (long)(N - 1) * q->ldw + K;
+  const long c_need = q->c_off + (long)(batch - 1) * q->bsC + (nsb - 1) * q->split_stride + (long)(M - 1) * q->ldc + width;
+  if (a_need > q->a_elems || w_need > q->w_elems || c_need > q->c_elems)
+    return fail(e, RK_ERR_INVALID, "debug gemm: the call reaches beyond A (%ld of %ld), W (%ld of %ld) or C (%ld of %ld)", a_need, (long)q->a_elems, w_need, (long)q->w_elems, c_need, (long)q->c_elems);
+  if (epi == EPI_ARGMAX_F32 && !q->idx_out) return fail(e, RK_ERR_INVALID, "debug gemm: argmax needs idx_out");
+  if (epi == EPI_LSE_F32 && (!q->labels || !q->xlab)) return fail(e, RK_ERR_INVALID, "debug gemm: LSE needs labels and xlab");
+  if (producer && (!q->xraw_out || !q->ssq_out || (long)(M + 2 * q->band_rows) * p.nb > q->ssq_cap))
+    return fail(e, RK_ERR_INVALID, "debug gemm: producer needs xraw_out and ssq_out of (M + 2 band_rows) x %d floats", p.nb);
+  const size_t band = (size_t)q->band_rows * q->ldc, c_all = 2 * band + (size_t)q->c_elems;
+  const size_t xband = (size_t)q->band_rows * N, x_all = 2 * xband + (size_t)M * N;
+  const size_t sband = (size_t)q->band_rows * p.nb, s_all = 2 * sband + (size_t)M * p.nb;
+  const size_t m_pad = ((size_t)M + 255) / 256 * 256 + 256;     // the ping-pong kernel reads the row factors of whole 256-row panels
+  std::vector<void*> dev;
+  auto alloc = [&](size_t bytes, int fill) -> void* {
+    void* ptr = nullptr;
+    if (hipMalloc(&ptr, bytes ? bytes : 16) != hipSuccess) return nullptr;
+    dev.push_back(ptr);
+    if (fill >= 0 && hipMemset(ptr, fill, bytes) != hipSuccess) return nullptr;
+    return ptr;
+  };
+  auto done = [&](int r) { for (void* ptr : dev) hipFree(ptr); return r; };
+#define DBG_HIP(x) do { if ((x) != hipSuccess) return done(fail(e, RK_ERR_HIP, "debug gemm: %s", #x)); } while (0)
+  half_t* dA = (half_t*)alloc((size_t)q->a_elems * 2, -1);
+  half_t* dW = (half_t*)alloc((size_t)q->w_elems * 2, -1);
+  char* dC = (char*)alloc(c_all * celt, RK_DEBUG_SENTINEL);
+  int* dI = epi == EPI_ARGMAX_F32 ? (int*)alloc(c_all * 4, RK_DEBUG_SENTINEL) : nullptr;
+  half_t* dX = producer ? (half_t*)alloc(x_all * 2, RK_DEBUG_SENTINEL) : nullptr;
+  float* dS = producer ? (float*)alloc(s_all * 4, RK_DEBUG_SENTINEL) : nullptr;
+  float* dR = (q->rowscale || q->ssq_in) ? (float*)alloc(m_pad * 4, 0) : nullptr;
+  float* dQ = q->ssq_in ? (float*)alloc((size_t)M * q->nb_in * 4, -1) : nullptr;
+  int* dL = epi == EPI_LSE_F32 ? (int*)alloc((size_t)M * 4, -1) : nullptr;
+  float* dXl = epi == EPI_LSE_F32 ? (float*)alloc((size_t)M * 4, -1) : nullptr;
+  if (!dA || !dW || !dC || (epi == EPI_ARGMAX_F32 && !dI) || (producer && (!dX || !dS)) || ((q->rowscale || q->ssq_in) && !dR) ||
+      (q->ssq_in && !dQ) || (epi == EPI_LSE_F32 && (!dL || !dXl)))
+    return done(fail(e, RK_ERR_HIP, "debug gemm: device allocation failed"));
+  DBG_HIP(hipMemcpy(dA, q->A, (size_t)q->a_elems * 2, hipMemcpyHostToDevice));
+  DBG_HIP(hipMemcpy(dW, q->W, (size_t)q->w_elems * 2, hipMemcpyHostToDevice));
+  DBG_HIP(hipMemcpy(dC + band * celt, q->C, (size_t)q->c_elems * celt, hipMemcpyHostToDevice));
+  if (q->rowscale) DBG_HIP(hipMemcpy(dR, q->rowscale, (size_t)M * 4, hipMemcpyHostToDevice));
+  if (q->ssq_in) DBG_HIP(hipMemcpy(dQ, q->ssq_in, (size_t)M * q->nb_in * 4, hipMemcpyHostToDevice));
+  if (dL) { DBG_HIP(hipMemcpy(dL, q->labels, (size_t)M * 4, hipMemcpyHostToDevice)); DBG_HIP(hipMemcpy(dXl, q->xlab, (size_t)M * 4, hipMemcpyHostToDevice)); }
+  DBG_HIP(hipDeviceSynchronize());
+  c.A = dA; c.W = dW; c.C = dC + (band + (size_t)q->c_off) * celt;
+  c.fold = GemmFold();
+  if (q->rowscale) c.fold.rowscale = dR;
+  else if (q->ssq_in && q->factors_kernel) {
+    hipLaunchKernelGGL(rowscale_kernel, dim3((M + 255) / 256), dim3(256), 0, st, dQ, dR, M, q->nb_in, K, e->d.eps, RK_XRAW_SCALE);
+    c.fold.rowscale = dR;
+  } else if (q->ssq_in) { c.fold.ssq_in = dQ; c.fold.nb_in = q->nb_in; }
+  if (producer) { c.fold.xraw = dX + xband; c.fold.ssq = dS + sband; }
+  // the buffers the block epilogues take from the engine, for the length of this call
+  int* const saved_idx = e->amax_idx.p; const int* const saved_lab = e->lse_labels; float* const saved_xlab = e->lse_xlab;
+  if (dI) e->amax_idx.p = dI + band + q->c_off;
+  if (dL) { e->lse_labels = dL; e->lse_xlab = dXl; }
+  int nb = 0;
+  rc = gemm(e, st, c, &nb);
+  e->amax_idx.p = saved_idx; e->lse_labels = saved_lab; e->lse_xlab = saved_xlab;
+  if (rc) return done(rc);
+  DBG_HIP(hipStreamSynchronize(st));
+  DBG_HIP(hipGetLastError());
+  q->out_nb = nb;
+  DBG_HIP(hipMemcpy(q->C_out, dC, c_all * celt, hipMemcpyDeviceToHost));
+  if (dI) DBG_HIP(hipMemcpy(q->idx_out, dI, c_all * 4, hipMemcpyDeviceToHost));
+  if (producer) { DBG_HIP(hipMemcpy(q->xraw_out, dX, x_all * 2, hipMemcpyDeviceToHost)); DBG_HIP(hipMemcpy(q->ssq_out, dS, s_all * 4, hipMemcpyDeviceToHost)); }
+  if (dXl) DBG_HIP(hipMemcpy(q->xlab, dXl, (size_t)M * 4, hipMemcpyDeviceToHost));
+#undef DBG_HIP
+  return done(RK_OK);
+}
+
+int rk_debug_gemm(rk_engine* e, const uint16_t* A, const uint16_t* W, float* C, int M, int N, int K, int use_glds) {
+  if (!e || !A || !W || !C) return RK_ERR_INVALID;
   if (K % 64 || N % 4) return fail(e, RK_ERR_INVALID, "debug gemm needs K%%64==0 and N%%4==0");
-  half_t *dA = nullptr, *dW = nullptr; float* dC = nullptr;
-  HIPCHK(e, hipMalloc((void**)&dA, (size_t)M * K * 2)); HIPCHK(e, hipMalloc((void**)&dW, (size_t)N * K * 2));
-  HIPCHK(e, hipMalloc((void**)&dC, (size_t)M * N * 4));
-  HIPCHK(e, hipMemcpy(dA, A, (size_t)M * K * 2, hipMemcpyHostToDevice));
-  HIPCHK(e, hipMemcpy(dW, W, (size_t)N * K * 2, hipMemcpyHostToDevice));
+  if (M <= 0) return RK_OK;
+  // 2: the weight-streaming family, 3: the few-row GEMV family (M <= 16)
+  rk_debug_gemm_call q{};
+  q.epi = EPI_STORE_F32; q.family = use_glds == 3 ? 2 : (use_glds >= 2 ? 1 : 0);
+  q.M = M; q.N = N; q.K = K; q.lda = q.ldw = K; q.ldc = N;
+  q.A = A; q.a_elems = (int64_t)M * K; q.W = W; q.w_elems = (int64_t)N * K;
+  q.C = C; q.c_elems = (int64_t)M * N; q.band_rows = 256; q.batch = 1;
+  std::vector<float> all((size_t)(M + 512) * N);
+  q.C_out = all.data();
   const int saved = e->opt.glds;
   e->opt.glds = use_glds != 0;
-  // 2: the weight-streaming family, 3: the few-row GEMV family (M <= 16)
-  rc = gemm(e, e->slots[0].se, Gemm(PC_OTHER, EPI_STORE_F32, dA, K, dW, K, dC, N, M, N, K).on(use_glds == 3 ? GEMM_GEMV : (use_glds >= 2 ? GEMM_STREAM : GEMM_TILED)));
+  const int rc = rk_debug_gemm_ex(e, &q);
   e->opt.glds = saved;
-  if (rc) { hipFree(dA); hipFree(dW); hipFree(dC); return rc; }
-  HIPCHK(e, hipStreamSynchronize(e->slots[0].se));
-  HIPCHK(e, hipGetLastError());
-  HIPCHK(e, hipMemcpy(C, dC, (size_t)M * N * 4, hipMemcpyDeviceToHost));
-  hipFree(dA); hipFree(dW); hipFree(dC);
+  if (rc) return rc;
+  memcpy(C, all.data() + (size_t)256 * N, (size_t)M * N * 4);
   return RK_OK;
 }
 

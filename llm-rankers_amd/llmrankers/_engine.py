@@ -36,6 +36,23 @@ class RkLlamaDesc(C.Structure):
                [(n, C.c_int32) for n in ("max_tokens", "max_seqs")]
 
 
+class RkDebugGemmCall(C.Structure):
+    """rk_debug_gemm_call of include/rk_engine.h, field for field."""
+    _fields_ = [(n, C.c_int) for n in ("epi", "family", "M", "N", "K", "lda", "ldw", "ldc")] + \
+               [("A", C.c_void_p), ("a_elems", C.c_int64), ("W", C.c_void_p), ("w_elems", C.c_int64),
+                ("C", C.c_void_p), ("c_elems", C.c_int64), ("c_off", C.c_int64), ("C_out", C.c_void_p), ("idx_out", C.c_void_p),
+                ("band_rows", C.c_int), ("rowscale", C.c_void_p), ("ssq_in", C.c_void_p), ("nb_in", C.c_int), ("factors_kernel", C.c_int),
+                ("xraw_out", C.c_void_p), ("ssq_out", C.c_void_p), ("ssq_cap", C.c_int64),
+                ("n_split", C.c_int), ("split_stride", C.c_int64), ("batch", C.c_int), ("bsA", C.c_int64), ("bsW", C.c_int64), ("bsC", C.c_int64),
+                ("labels", C.c_void_p), ("xlab", C.c_void_p), ("plan_only", C.c_int)] + \
+               [(n, C.c_int) for n in ("out_family", "out_variant", "out_m_pp2", "out_ksplit", "out_nb", "out_n_cu")] + \
+               [("out_eps", C.c_float), ("out_xs", C.c_float)]
+
+
+DEBUG_SENTINEL = 0xCD                      # RK_DEBUG_SENTINEL: the byte the guard bands of rk_debug_gemm_ex are filled with
+DEBUG_BAND_ROWS = 256
+GEMM_OUT_DTYPE = {0: np.float16, 1: np.float32, 2: np.float16, 3: np.float16, 4: np.float32, 5: np.float16, 6: np.float32, 7: np.float32}
+
 # name -> (restype, argtypes); this table is also what tests check against include/rk_engine.h
 _P = C.POINTER
 _i32p, _f32p = _P(C.c_int32), _P(C.c_float)
@@ -88,6 +105,7 @@ ABI = {
     "rk_abi_version": (C.c_int, []),
     "rk_rel_bucket": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "rk_debug_gemm": (C.c_int, [C.c_void_p, _P(C.c_uint16), _P(C.c_uint16), _f32p, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "rk_debug_gemm_ex": (C.c_int, [C.c_void_p, _P(RkDebugGemmCall)]),
     "rk_debug_gemm_bench": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _f32p]),
     "rk_debug_read": (C.c_int64, [C.c_void_p, C.c_char_p, _f32p, C.c_int64]),
 }
@@ -392,6 +410,68 @@ class RkEngine:
         ms = C.c_float(0)
         self._chk(self.lib.rk_debug_gemm_bench(self.h, m, n, k, epi, iters, C.byref(ms)))
         return float(ms.value)
+
+    def debug_gemm_ex(self, epi: int, family: int, a16: np.ndarray, w16: np.ndarray, M: int, N: int, K: int, *, lda=None, ldw=None,
+                      ldc=None, c_in: Optional[np.ndarray] = None, c_off=0, rowscale=None, ssq_in=None, factors_kernel=False,
+                      producer=False, n_split=0, split_stride=0, batch=1, bsA=0, bsW=0, bsC=0, labels=None, plan_only=False) -> dict:
+        """One call of the engine's GEMM through rk_debug_gemm_ex (include/rk_engine.h).  a16 / w16: flat or 2-D fp16 arrays holding
+        everything the call addresses; c_in: the flat INTERIOR of the output in the output type (epi 7: two floats per element),
+        default = all sentinel bytes.  Returns the plan fields and the WHOLE device allocations after the call, bands included:
+        "C" (flat, band | interior | band; "band" = elements per band), "idx", "xraw" [(2 band_rows + M), N], "ssq"
+        [(2 band_rows + M), nb], "xlab"."""
+        a16 = np.ascontiguousarray(a16, dtype=np.float16).reshape(-1)
+        w16 = np.ascontiguousarray(w16, dtype=np.float16).reshape(-1)
+        gated, blocks = epi in (2, 5), epi in (6, 7)
+        width = -(-N // 32) if blocks else (n_split if n_split else (N // 2 if gated else N))
+        lda, ldw, ldc = lda or K, ldw or K, ldc or width
+        dt, per = GEMM_OUT_DTYPE[epi], (2 if epi == 7 else 1)
+        if c_in is None:
+            nsb = -(-N // n_split) if n_split else 1
+            c_elems = c_off + (batch - 1) * bsC + (nsb - 1) * split_stride + M * ldc
+            c_in = np.frombuffer(bytes([DEBUG_SENTINEL]) * (c_elems * per * np.dtype(dt).itemsize), dtype=dt).copy()
+        c_in = np.ascontiguousarray(c_in, dtype=dt).reshape(-1)
+        c_elems = c_in.size // per
+        band = DEBUG_BAND_ROWS * ldc
+        q = RkDebugGemmCall()
+        q.epi, q.family, q.M, q.N, q.K, q.lda, q.ldw, q.ldc = epi, family, M, N, K, lda, ldw, ldc
+        q.A, q.a_elems, q.W, q.w_elems = a16.ctypes.data, a16.size, w16.ctypes.data, w16.size
+        q.C, q.c_elems, q.c_off, q.band_rows = c_in.ctypes.data, c_elems, c_off, DEBUG_BAND_ROWS
+        c_out = np.zeros((2 * band + c_elems) * per, dtype=dt)
+        q.C_out = c_out.ctypes.data
+        keep = [a16, w16, c_in, c_out]
+        idx = xraw = ssq = xlab = None
+        if epi == 6:
+            idx = np.zeros(2 * band + c_elems, dtype=np.int32)
+            q.idx_out = idx.ctypes.data
+        if rowscale is not None:
+            rowscale = np.ascontiguousarray(rowscale, dtype=np.float32)
+            assert rowscale.size == M
+            q.rowscale = rowscale.ctypes.data
+        if ssq_in is not None:
+            ssq_in = np.ascontiguousarray(ssq_in, dtype=np.float32)
+            assert ssq_in.ndim == 2 and ssq_in.shape[0] == M
+            q.ssq_in, q.nb_in, q.factors_kernel = ssq_in.ctypes.data, ssq_in.shape[1], int(factors_kernel)
+        rows_all = 2 * DEBUG_BAND_ROWS + M
+        if producer:
+            xraw = np.zeros((rows_all, N), dtype=np.float16)
+            ssq = np.zeros(rows_all * (-(-N // 4) + 1), dtype=np.float32)       # room for any family's block count
+            q.xraw_out, q.ssq_out, q.ssq_cap = xraw.ctypes.data, ssq.ctypes.data, ssq.size
+        q.n_split, q.split_stride, q.batch, q.bsA, q.bsW, q.bsC = n_split, split_stride, batch, bsA, bsW, bsC
+        if epi == 7:
+            labels = np.ascontiguousarray(labels, dtype=np.int32)
+            assert labels.size == M
+            xlab = np.frombuffer(bytes([DEBUG_SENTINEL]) * (4 * M), dtype=np.float32).copy()
+            q.labels, q.xlab = labels.ctypes.data, xlab.ctypes.data
+        q.plan_only = int(plan_only)
+        self._chk(self.lib.rk_debug_gemm_ex(self.h, C.byref(q)))
+        del keep
+        out = {k[4:]: getattr(q, k) for k, _ in RkDebugGemmCall._fields_ if k.startswith("out_")}
+        if plan_only:
+            return out
+        out.update(C=c_out, band=band, idx=idx, xlab=xlab, ldc=ldc, c_elems=c_elems)
+        if producer:
+            out.update(xraw=xraw, ssq=ssq[:rows_all * q.out_nb].reshape(rows_all, q.out_nb))
+        return out
 
     def debug_read(self, name: str, n_floats: int) -> np.ndarray:
         out = np.empty(n_floats, dtype=np.float32)
