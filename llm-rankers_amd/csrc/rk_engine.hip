@@ -100,6 +100,31 @@ struct Grown {
   int reserve(rk_engine* e, size_t n, int* gen = nullptr);
 };
 
+// The decoder-side index buffers of a slot and the ONLY host code that writes them.  Every T5 entry point leaves its ids, row
+// maps and labels here, and a later call may skip an upload because of what an earlier one left: so what the device holds is
+// recorded here, as a consequence of WHICH buffer a write went to, never by the caller.
+//   put     content-compared: nothing happens (no synchronisation, no copy) if the buffer holds exactly these ints, else one
+//           pinned asynchronous copy on st (buffers below IX_N_CACHED: a pinned staging slot each)
+//   write   plain synchronous copies (the big or always-changing arrays) after ONE synchronisation of st; what put knew of
+//           those buffers is forgotten
+//   tree    rk_t5_greedy2's five arrays: written only if `sig` differs from the last tree's or anything was written since
+// The Llama family has IX_LAST_ROWS and IX_OUT_IDS only: llama_prefill writes the former through write(), rk_llama_last_logits copies
+// the latter on its stream itself (its one writer, nothing is ever skipped there).  rk_t5_generate's greedy_advance_kernel
+// writes IX_DEC_IDS on the device, behind the write() that forgot its content.
+enum DecBuf { IX_DEC_IDS, IX_OUT_IDS, IX_LAST_ROWS, IX_N_CACHED, IX_ROW_LABEL = IX_N_CACHED, IX_ROW_OFF, IX_OUT_IDX, IX_ROW_SEQ, IX_TREE_KEYS, IX_TREE_POS, IX_COUNT };
+struct DecIndex {
+  struct Src { DecBuf b; const std::vector<int>& v; };
+  int* d[IX_COUNT] = {nullptr};
+  int* pin = nullptr;                                          // pinned staging: IX_N_CACHED slots of PIN_INTS
+  static constexpr int PIN_INTS = 8192;
+  int put(rk_engine* e, hipStream_t st, DecBuf b, const int* src, int n);
+  int write(rk_engine* e, hipStream_t st, std::initializer_list<Src> srcs);
+  int tree(rk_engine* e, hipStream_t st, std::vector<int>& sig, std::initializer_list<Src> srcs);
+ private:
+  std::vector<int> held[IX_N_CACHED], tree_sig;                // what put / tree left on the device (empty: unknown)
+  unsigned long epoch = 0, tree_epoch = ~0ul;                  // epoch counts the writes that reached the device
+};
+
 }  // namespace
 
 #define RK_SLOTS 2
@@ -115,16 +140,13 @@ struct Slot {
   int* d_tokens = nullptr; int* d_seq_off = nullptr;
   int n_seq = 0, T = 0, maxL = 0, minL = 0; bool staged = false; int last_n_out = 0;
   half_t* cross_kv = nullptr;                                  // [n_dec][max_tokens][2I] encoder -> decoder hand-off
-  int *d_dec_ids = nullptr, *d_last_rows = nullptr, *d_out_ids = nullptr, *d_row_label = nullptr, *d_row_off = nullptr, *d_out_idx = nullptr, *d_argmax = nullptr, *d_row_seq = nullptr, *d_tree_keys = nullptr, *d_tree_pos = nullptr;
+  DecIndex idx; int* d_argmax = nullptr;                       // decoder ids, row maps, labels (see DecIndex) | the greedy head's result
   NormStream dec;                                              // the decoder's (run_decoder); rk_t5_qlm's final norm writes dec.xn
   half_t *dqkv = nullptr, *dctx = nullptr, *dq = nullptr, *dffh = nullptr, *dlast = nullptr;
   float* dssq_few[2] = {nullptr, nullptr};   // dec.ssq for the few-row GEMV family (gemv_rows.h): one partial per producing workgroup
   half_t *xqk = nullptr, *xctx = nullptr;                      // direct cross-attention: [32][H*d] each
   float *xpart = nullptr, *xstat = nullptr; bool have_cross_kv = false;
   float* d_scores = nullptr; float* h_scores = nullptr;
-  int* h_small = nullptr;                                      // pinned staging for small int uploads
-  std::vector<int> cache_dec, cache_out, cache_rows;
-  std::vector<int> cache_g2; unsigned long dec_epoch = 0, g2_epoch = ~0ul;   // rk_t5_greedy2's five index arrays, valid while no other path wrote the decoder id / row buffers (dec_epoch)
   hipEvent_t ev_enc = nullptr, ev_dec = nullptr; bool dec_pending = false;
 };
 
@@ -142,7 +164,6 @@ struct rk_engine {
   std::vector<DecLayerW> dec;
   float *enc_final_ln = nullptr, *dec_final_ln = nullptr, *lut_enc = nullptr, *lut_dec = nullptr;
   Grown<float> logits;                                         // qlm head: per-block (max, sum exp) pairs [rows, vocab/32] + label logits [rows]; slot 0 only
-  const int* lse_labels = nullptr; float* lse_xlab = nullptr;   // arguments of the next EPI_LSE_F32 launch
   Grown<float> amax_val; Grown<int> amax_idx; int amax_gen = 0;   // greedy head: per-row block maxima / first columns
   // rk_t5_generate: self-attention K / V cache [n_dec_layers][n_seq][P][2 inner] (kv_gen counts the moves) and the per-call int
   // block on the device (state, prefix, finished rows, output, tree arrays); decode_cached: pinned read-back of the finished step
@@ -364,12 +385,16 @@ struct Gemm {
   int batch = 1; long bsA = 0, bsW = 0, bsC = 0;  // per-head GEMMs: `batch` blockIdx.y batches, element strides between them
   GemmFamily family = GEMM_TILED;
   GemmFold fold;
+  const int* lse_labels = nullptr; float* lse_xlab = nullptr;   // EPI_LSE_F32: the label of every row, where its logit goes
+  int* amax_idx = nullptr;                        // EPI_ARGMAX_F32: the first column of every block maximum, laid out like C
   Gemm(int cls_, int epi_, const half_t* A_, int lda_, const half_t* W_, int ldw_, void* C_, int ldc_, int M_, int N_, int K_)
       : cls(cls_), epi(epi_), A(A_), lda(lda_), W(W_), ldw(ldw_), C(C_), ldc(ldc_), M(M_), N(N_), K(K_) {}
   Gemm& heads(int b, long sA, long sW, long sC) { batch = b; bsA = sA; bsW = sW; bsC = sC; return *this; }
   Gemm& split(int n, long stride) { n_split = n; split_stride = stride; return *this; }
   Gemm& on(GemmFamily f) { family = f; return *this; }
   Gemm& with(const GemmFold& f) { fold = f; return *this; }
+  Gemm& lse(const int* labels, float* xlab) { lse_labels = labels; lse_xlab = xlab; return *this; }
+  Gemm& argmax(int* idx) { amax_idx = idx; return *this; }
 };
 
 // Launch plan of one GEMM call: everything gemm() launches, decided here and nowhere else.
@@ -414,6 +439,8 @@ const char* gemm_contract(const Gemm& c, GemmFamily fam) {
   if (gated && c.N % 64) return "gated epilogues pair gate / up rows in groups of 32: N % 64";
   const int width = blocks ? (c.N + 31) / 32 : (c.n_split > 0 ? c.n_split : (gated ? c.N / 2 : c.N));
   if (c.ldc < width) return "ldc smaller than the output width";
+  if (epi == EPI_LSE_F32 && !(c.lse_labels && c.lse_xlab)) return "LSE epilogue without row labels and label-logit buffer";
+  if (epi == EPI_ARGMAX_F32 && !c.amax_idx) return "argmax epilogue without index buffer";
   if (producer && (epi != EPI_RESID_F32 || !c.fold.xraw || !c.fold.ssq || c.n_split || c.batch > 1))
     return "producer statistics: fp32 residual epilogue, one batch, no n_split, xraw and ssq together";
   if (c.fold.ssq_in && c.fold.nb_in <= 0) return "ssq_in without nb_in";
@@ -610,8 +637,7 @@ int gemm(rk_engine* e, hipStream_t st, const Gemm& c, int* nb = nullptr) {
   a.rowscale = c.fold.rowscale; a.xraw = c.fold.xraw; a.ssq = c.fold.ssq; a.ldx = c.N; a.nb = p.nb; a.xs = RK_XRAW_SCALE;
   a.ssq_in = c.fold.ssq_in; a.nb_in = c.fold.nb_in; a.eps_in = e->d.eps;
   a.group_n = GEMM_GROUP_N;
-  if (c.epi == EPI_ARGMAX_F32) a.amax_idx = e->amax_idx.p;
-  if (c.epi == EPI_LSE_F32) { a.lse_labels = e->lse_labels; a.lse_xlab = e->lse_xlab; }
+  a.amax_idx = c.amax_idx; a.lse_labels = c.lse_labels; a.lse_xlab = c.lse_xlab;
   const double flops = 2.0 * c.M * (double)c.N * c.K * c.batch;
   const double out_elems = EPI_IS_GATED(c.epi) ? (double)c.M * c.N / 2 : (double)c.M * c.N;
   const double bytes = 2.0 * ((double)c.M * c.K + (double)c.N * c.K) +
@@ -719,20 +745,40 @@ int set_device(rk_engine* e) {
   return RK_OK;
 }
 
-// Upload a small int array through pinned memory unless it equals what is already on the device.
-int upload_small(rk_engine* e, Slot& sl, hipStream_t st, std::vector<int>* cache, int* dptr, int pin_slot, const int* src, int n) {
-  if ((int)cache->size() == n && (n == 0 || memcmp(cache->data(), src, n * sizeof(int)) == 0)) return RK_OK;
+int DecIndex::put(rk_engine* e, hipStream_t st, DecBuf b, const int* src, int n) {
+  if (b >= IX_N_CACHED) return fail(e, RK_ERR_STATE, "index buffer %d has no pinned slot: write() it", (int)b);
+  std::vector<int>& h = held[b];
+  if ((int)h.size() == n && (n == 0 || memcmp(h.data(), src, n * sizeof(int)) == 0)) return RK_OK;
   HIPCHK(e, hipStreamSynchronize(st));   // the pinned slot may still be in flight
-  ++sl.dec_epoch;
-  if (n > 8192) {                        // larger than a pinned slot: plain synchronous copy
-    HIPCHK(e, hipMemcpy(dptr, src, (size_t)n * sizeof(int), hipMemcpyHostToDevice));
-    cache->assign(src, src + n);
-    return RK_OK;
+  ++epoch;
+  h.clear();
+  int* slot = pin + b * PIN_INTS;
+  if (n > PIN_INTS) {                    // larger than a pinned slot: plain synchronous copy
+    HIPCHK(e, hipMemcpy(d[b], src, (size_t)n * sizeof(int), hipMemcpyHostToDevice));
+  } else {
+    memcpy(slot, src, n * sizeof(int));
+    HIPCHK(e, hipMemcpyAsync(d[b], slot, n * sizeof(int), hipMemcpyHostToDevice, st));
   }
-  int* pin = sl.h_small + pin_slot * 8192;
-  memcpy(pin, src, n * sizeof(int));
-  HIPCHK(e, hipMemcpyAsync(dptr, pin, n * sizeof(int), hipMemcpyHostToDevice, st));
-  cache->assign(src, src + n);
+  h.assign(src, src + n);
+  return RK_OK;
+}
+
+int DecIndex::write(rk_engine* e, hipStream_t st, std::initializer_list<Src> srcs) {
+  HIPCHK(e, hipStreamSynchronize(st));
+  ++epoch;
+  for (const Src& s : srcs) {
+    if (s.b < IX_N_CACHED) held[s.b].clear();
+    HIPCHK(e, hipMemcpy(d[s.b], s.v.data(), s.v.size() * sizeof(int), hipMemcpyHostToDevice));
+  }
+  return RK_OK;
+}
+
+int DecIndex::tree(rk_engine* e, hipStream_t st, std::vector<int>& sig, std::initializer_list<Src> srcs) {
+  if (tree_epoch == epoch && sig == tree_sig) return RK_OK;
+  const int rc = write(e, st, srcs);
+  if (rc) return rc;
+  tree_sig.swap(sig);
+  tree_epoch = epoch;
   return RK_OK;
 }
 
@@ -1026,7 +1072,7 @@ int run_encoder(rk_engine* e, Slot& sl, bool need_cross_kv) {
 }
 
 // hf: modeling_t5.py:663-750 (decoder stack) for Ld teacher-forced positions per sequence (ids already on the
-// device in sl.d_dec_ids, row = b*Ld + t).  Leaves the residual stream in sl.dec.hidden.
+// device in sl.idx.d[IX_DEC_IDS], row = b*Ld + t).  Leaves the residual stream in sl.dec.hidden.
 // tree (rk_t5_greedy2): the decoder rows are not Ld per sequence - several continuations of a prompt share the rows of their
 // common prefix.  rows = row count, Ld = longest position count; device arrays: keys[r * Ld + j] = row at position j of
 // row r's sequence, pos[r] = position of row r, seq[r] = its encoder sequence.  Query-side cross-attention only.
@@ -1091,7 +1137,7 @@ int run_decoder(rk_engine* e, Slot& sl, int Ld, const DecRows* rows = nullptr, c
   // the GEMM c of this pass's family behind the norm ln: every consumer here may form its row factors itself
   auto normed = [&](const float* ln, Gemm c) { return ns.consumer(e, st, ln, c.on(fam), true); };
   auto resid = [&](Gemm c, bool stats = true) { return ns.producer(e, st, c.on(fam), stats); };
-  ns.begin(e, st, ragged && rows->ids ? rows->ids : sl.d_dec_ids, M, dfold);
+  ns.begin(e, st, ragged && rows->ids ? rows->ids : sl.idx.d[IX_DEC_IDS], M, dfold);
   const DecAttnPlan self_plan = plan_dec_attn(e, false, B, Ld, Ld, d.n_heads, tree ? rows->rows : 0);
   const DecAttnPlan cross_plan = plan_dec_attn(e, true, B, Ld, sl.maxL, d.n_heads, 0);
   for (int l = 0; l < d.n_dec_layers; ++l) {
@@ -1224,7 +1270,8 @@ float head_scale(const rk_engine* e) {   // hf: modeling_t5.py:1044-1045 (scale_
   return e->d.tied_head ? 1.0f / std::sqrt((float)e->d.d_model) : 1.0f;
 }
 
-int check_batch(rk_engine* e, Slot& sl, const int32_t* tokens, const int32_t* off, int n_seq) {
+// The checks of a ragged batch; with a slot, its shape is recorded there (without: the caller stages another order of it).
+int check_batch(rk_engine* e, Slot* sl, const int32_t* tokens, const int32_t* off, int n_seq) {
   if (!e->finalized) return fail(e, RK_ERR_STATE, "engine not finalized");
   if (!tokens || !off || n_seq <= 0) return fail(e, RK_ERR_INVALID, "empty batch (n_seq=%d)", n_seq);
   if (n_seq > e->d.max_seqs) return fail(e, RK_ERR_CAPACITY, "n_seq %d > max_seqs %d", n_seq, e->d.max_seqs);
@@ -1242,7 +1289,7 @@ int check_batch(rk_engine* e, Slot& sl, const int32_t* tokens, const int32_t* of
     if (tokens[t] < 0 || tokens[t] >= e->d.vocab) return fail(e, RK_ERR_INVALID, "token id %d out of range at %d", tokens[t], t);
   if (attn_dec_lds(maxL) > 160 * 1024 || maxL > 65536)
     return fail(e, RK_ERR_CAPACITY, "sequence of %d tokens exceeds the cross-attention LDS budget", maxL);
-  sl.maxL = maxL; sl.minL = minL; sl.T = T; sl.n_seq = n_seq;
+  if (sl) { sl->maxL = maxL; sl->minL = minL; sl->T = T; sl->n_seq = n_seq; }
   return RK_OK;
 }
 
@@ -1252,17 +1299,34 @@ int check_ids(rk_engine* e, const int32_t* ids, int n, const char* what) {
   return RK_OK;
 }
 
-int upload_dec_ids_shared(rk_engine* e, Slot& sl, const int32_t* prefix, int Ld) {
+// the same Ld decoder ids for every sequence of the slot's batch
+int put_dec_ids_shared(rk_engine* e, Slot& sl, const int32_t* prefix, int Ld) {
   std::vector<int> ids((size_t)sl.n_seq * Ld);
   for (int b = 0; b < sl.n_seq; ++b) memcpy(&ids[(size_t)b * Ld], prefix, Ld * sizeof(int));
-  hipStream_t st = dec_stream(e, sl);
-  if (ids.size() > 8192) {   // larger than a pinned slot: plain synchronous copy
-    HIPCHK(e, hipStreamSynchronize(st));
-    HIPCHK(e, hipMemcpy(sl.d_dec_ids, ids.data(), ids.size() * sizeof(int), hipMemcpyHostToDevice));
-    sl.cache_dec.clear(); ++sl.dec_epoch;
-    return RK_OK;
-  }
-  return upload_small(e, sl, st, &sl.cache_dec, sl.d_dec_ids, 0, ids.data(), (int)ids.size());
+  return sl.idx.put(e, dec_stream(e, sl), IX_DEC_IDS, ids.data(), (int)ids.size());
+}
+
+// decoder input of teacher-forced labels = shift_right(labels): [decoder_start(0), labels[:-1]]  (hf: modeling_t5.py:618-637)
+void shift_right(const int32_t* labels, int n, std::vector<int>* out) {
+  for (int t = 0; t < n; ++t) out->push_back(t ? labels[t - 1] : 0);
+}
+
+// dec_prefix / dec_len / max_new of the greedy entry points
+int check_greedy_args(rk_engine* e, const int32_t* dec_prefix, int dec_len, int max_new) {
+  if (!dec_prefix || dec_len <= 0 || max_new <= 0 || dec_len + max_new - 1 > e->d.max_dec_len)
+    return fail(e, RK_ERR_CAPACITY, "dec_len %d + max_new %d exceeds max_dec_len %d", dec_len, max_new, e->d.max_dec_len);
+  return RK_OK;
+}
+
+// The end of a blocking call that returns floats: the slot's first n scores through its pinned buffer, the call's stream st
+// finished (T5, with its two streams per slot: finish_blocking).
+int read_scores_blocking(rk_engine* e, Slot& sl, hipStream_t st, size_t n, float* out) {
+  HIPCHK(e, hipMemcpyAsync(sl.h_scores, sl.d_scores, n * sizeof(float), hipMemcpyDeviceToHost, st));
+  if (e->family == 0) { const int rc = finish_blocking(e, sl); if (rc) return rc; }
+  else HIPCHK(e, hipStreamSynchronize(st));
+  HIPCHK(e, hipGetLastError());
+  memcpy(out, sl.h_scores, n * sizeof(float));
+  return RK_OK;
 }
 
 int stage_slot(rk_engine* e, int slot, const int32_t* tokens, const int32_t* seq_offsets, int n_seq) {
@@ -1272,7 +1336,7 @@ int stage_slot(rk_engine* e, int slot, const int32_t* tokens, const int32_t* seq
   if (rc) return rc;
   Slot& sl = e->slots[slot];
   sl.staged = false;
-  if ((rc = check_batch(e, sl, tokens, seq_offsets, n_seq))) return rc;
+  if ((rc = check_batch(e, &sl, tokens, seq_offsets, n_seq))) return rc;
   // the slot's previous batch (encoder reads tokens, decoder reads seq_off) must be done before overwriting
   if (sl.dec_pending) { HIPCHK(e, hipEventSynchronize(sl.ev_dec)); sl.dec_pending = false; }
   HIPCHK(e, hipStreamSynchronize(enc_stream(e, sl)));
@@ -1287,6 +1351,7 @@ int stage_slot(rk_engine* e, int slot, const int32_t* tokens, const int32_t* seq
 // dependent-kernel boundary (1-2 us).  `body` enqueues the chain on `st`; the second time a key is seen the chain is
 // captured, instantiated and cached, from then on it is replayed.  The key holds every value the launch parameters
 // depend on (shapes, options epoch); buffers are per-slot and never move.  Profiling runs stay eager (per-kernel events).
+enum GraphKind { GK_T5_SCORE, GK_T5_GREEDY_STEP, GK_T5_GREEDY2, GK_T5_GENERATE_STEP, GK_LLAMA_STEP };   // which chain: the key's first int
 template <class F>
 int run_graphed(rk_engine* e, hipStream_t st, std::vector<int> key, F&& body) {
   key.push_back(e->opt_epoch);
@@ -1367,24 +1432,24 @@ int score_slot(rk_engine* e, int slot, const int32_t* dec_prefix, int dec_len, c
   if (!out_token_ids || n_out <= 0 || n_out > 64) return fail(e, RK_ERR_INVALID, "n_out must be in 1..64 (got %d)", n_out);
   if ((rc = check_ids(e, dec_prefix, dec_len, "decoder")) || (rc = check_ids(e, out_token_ids, n_out, "output"))) return rc;
   hipStream_t sd = dec_stream(e, sl);
-  if ((rc = upload_dec_ids_shared(e, sl, dec_prefix, dec_len))) return rc;
-  if ((rc = upload_small(e, sl, sd, &sl.cache_out, sl.d_out_ids, 1, out_token_ids, n_out))) return rc;   // n_out <= 64 (checked)
+  if ((rc = put_dec_ids_shared(e, sl, dec_prefix, dec_len))) return rc;
+  if ((rc = sl.idx.put(e, sd, IX_OUT_IDS, out_token_ids, n_out))) return rc;
   std::vector<int> rows(sl.n_seq);
   for (int b = 0; b < sl.n_seq; ++b) rows[b] = b * dec_len + dec_len - 1;
-  if ((rc = upload_small(e, sl, sd, &sl.cache_rows, sl.d_last_rows, 2, rows.data(), sl.n_seq))) return rc;
+  if ((rc = sl.idx.put(e, sd, IX_LAST_ROWS, rows.data(), sl.n_seq))) return rc;
   if ((rc = encoder_then_handoff(e, sl, dec_len))) return rc;
 #ifdef RK_MEASURE   // measurement builds only (never what build() ships): encoder-chain floor, scores are garbage
   static const bool skip_dec = getenv("RK_DEBUG_SKIP_DECODER") != nullptr;
 #else
   constexpr bool skip_dec = false;
 #endif
-  rc = run_graphed(e, sd, {0, slot, sl.n_seq, dec_len, sl.have_cross_kv ? sl.maxL : (sl.maxL + 63) / 64, (int)sl.have_cross_kv, n_out, (int)skip_dec}, [&]() -> int {
+  rc = run_graphed(e, sd, {GK_T5_SCORE, slot, sl.n_seq, dec_len, sl.have_cross_kv ? sl.maxL : (sl.maxL + 63) / 64, (int)sl.have_cross_kv, n_out, (int)skip_dec}, [&]() -> int {
     int r = RK_OK;
     if (!skip_dec && (r = run_decoder(e, sl, dec_len))) return r;
-    rmsnorm(e, sd, sl.dec.hidden, e->dec_final_ln, sl.dlast, sl.d_last_rows, sl.n_seq, head_scale(e));
+    rmsnorm(e, sd, sl.dec.hidden, e->dec_final_ln, sl.dlast, sl.idx.d[IX_LAST_ROWS], sl.n_seq, head_scale(e));
     Bracket br(e, sd, PC_HEAD, 2.0 * sl.n_seq * n_out * e->d.d_model, 0);
     hipLaunchKernelGGL(head_rows_kernel, dim3((sl.n_seq * n_out + 3) / 4), dim3(256), 0, sd, sl.dlast, e->lm_head,
-                       sl.d_out_ids, sl.d_scores, sl.n_seq, n_out, e->d.d_model);
+                       sl.idx.d[IX_OUT_IDS], sl.d_scores, sl.n_seq, n_out, e->d.d_model);
     return RK_OK;
   });
   if (rc) return rc;
@@ -1572,7 +1637,7 @@ void rk_engine_destroy(rk_engine* e) {
   for (auto& w : e->sk_ws) { if (w.slabs) hipFree(w.slabs); if (w.cnt) hipFree(w.cnt); }
   for (auto& sl : e->slots) {
     if (sl.h_scores) hipHostFree(sl.h_scores);
-    if (sl.h_small) hipHostFree(sl.h_small);
+    if (sl.idx.pin) hipHostFree(sl.idx.pin);
     if (sl.ev_enc) hipEventDestroy(sl.ev_enc);
     if (sl.ev_dec) hipEventDestroy(sl.ev_dec);
   }
@@ -1780,9 +1845,9 @@ int rk_engine_finalize(rk_engine* e) {
     HIPCHK(e, hipMemset(sl.enc.factors, 0, (Tc + 512) * sizeof(float)));
     RC(dalloc(e, &sl.d_tokens, Tc)); RC(dalloc(e, &sl.d_seq_off, Bc + 1));
     RC(dalloc(e, &sl.cross_kv, (size_t)d.n_dec_layers * Tc * 2 * I));
-    RC(dalloc(e, &sl.d_dec_ids, Mc)); RC(dalloc(e, &sl.d_last_rows, Bc)); RC(dalloc(e, &sl.d_out_ids, 8192));
-    RC(dalloc(e, &sl.d_row_label, Mc)); RC(dalloc(e, &sl.d_row_off, 2 * Bc + 1)); RC(dalloc(e, &sl.d_out_idx, Bc)); RC(dalloc(e, &sl.d_argmax, Bc));
-    RC(dalloc(e, &sl.d_row_seq, Mc)); RC(dalloc(e, &sl.d_tree_keys, Mc * (size_t)d.max_dec_len)); RC(dalloc(e, &sl.d_tree_pos, Mc));
+    RC(dalloc(e, &sl.idx.d[IX_DEC_IDS], Mc)); RC(dalloc(e, &sl.idx.d[IX_LAST_ROWS], Bc)); RC(dalloc(e, &sl.idx.d[IX_OUT_IDS], 8192));
+    RC(dalloc(e, &sl.idx.d[IX_ROW_LABEL], Mc)); RC(dalloc(e, &sl.idx.d[IX_ROW_OFF], 2 * Bc + 1)); RC(dalloc(e, &sl.idx.d[IX_OUT_IDX], Bc)); RC(dalloc(e, &sl.d_argmax, Bc));
+    RC(dalloc(e, &sl.idx.d[IX_ROW_SEQ], Mc)); RC(dalloc(e, &sl.idx.d[IX_TREE_KEYS], Mc * (size_t)d.max_dec_len)); RC(dalloc(e, &sl.idx.d[IX_TREE_POS], Mc));
     RC(dalloc(e, &sl.dec.hidden, Mc * dm)); RC(dalloc(e, &sl.dec.xn, Mc * dm)); RC(dalloc(e, &sl.dqkv, Mc * 3 * I));
     RC(dalloc(e, &sl.dctx, Mc * I)); RC(dalloc(e, &sl.dq, Mc * I)); RC(dalloc(e, &sl.dffh, Mc * F));
     RC(dalloc(e, &sl.dlast, Bc * dm));
@@ -1792,7 +1857,7 @@ int rk_engine_finalize(rk_engine* e) {
     RC(dalloc(e, &sl.xpart, (size_t)XA_MAX_CHUNKS * d.n_heads * dm)); RC(dalloc(e, &sl.xstat, (size_t)XA_MAX_CHUNKS * d.n_heads * 2));
     RC(dalloc(e, &sl.d_scores, e->scores_cap));
     HIPCHK(e, hipHostMalloc((void**)&sl.h_scores, e->scores_cap * sizeof(float), hipHostMallocDefault));
-    HIPCHK(e, hipHostMalloc((void**)&sl.h_small, 4 * 8192 * sizeof(int), hipHostMallocDefault));
+    HIPCHK(e, hipHostMalloc((void**)&sl.idx.pin, IX_N_CACHED * DecIndex::PIN_INTS * sizeof(int), hipHostMallocDefault));
   }
   // dynamic-LDS opt-in (best effort) for the kernels that may exceed the 64 KiB default (check_batch refuses longer calls)
   const int dec_smem_max = (int)attn_dec_lds(std::max(d.max_tokens, d.max_dec_len));
@@ -1858,6 +1923,38 @@ int rk_t5_score(rk_engine* e, const int32_t* tokens, const int32_t* seq_offsets,
   return rk_t5_read_scores(e, out_logits, n_seq * n_out);
 }
 
+// One decoder pass of a qlm call over the sequences s0 .. s0 + n_seq - 1 of the staged batch: `rows` rows from row r0 of
+// IX_DEC_IDS / IX_ROW_LABEL (/ IX_ROW_SEQ), ld positions at most.  Uniform (off0 < 0; the whole batch, ld rows per sequence, scores
+// in batch order) or ragged (run_decoder: DecRows; the sequences' row offsets from IX_ROW_OFF + off0, their scores to the
+// places IX_OUT_IDX + s0 names).  cross_kv: the pass reads the materialised K / V.
+struct QlmPass { int s0, n_seq, r0, rows, ld, off0; bool cross_kv; };
+
+// The qlm computation of both entry points over the staged batch, its index buffers written: the encoder once, then per pass the
+// decoder, the final norm, the head GEMM with the log-sum-exp fused into its epilogue (per row and 32-column block (max, sum exp)
+// + the label's logit) and the merge into one score per sequence; the scores read back once.
+static int run_qlm(rk_engine* e, Slot& sl, const std::vector<QlmPass>& passes, float* out_scores) {
+  hipStream_t sd = dec_stream(e, sl);
+  int* const* ix = sl.idx.d;
+  int rc = RK_OK, max_rows = 0;
+  bool need_kv = false;
+  for (const QlmPass& p : passes) { max_rows = std::max(max_rows, p.rows); need_kv = need_kv || p.cross_kv; }
+  RC(ensure_logits(e, (size_t)max_rows));
+  RC(encoder_then_handoff_kv(e, sl, need_kv));
+  const int nblk = (e->d.vocab + 31) / 32, dm = e->d.d_model;
+  for (const QlmPass& p : passes) {
+    const bool ragged = p.off0 >= 0;
+    const int* off = ragged ? ix[IX_ROW_OFF] + p.off0 : nullptr;
+    const DecRows rows{p.rows, nullptr, nullptr, ix[IX_ROW_SEQ] + p.r0, off, p.s0, p.n_seq, p.cross_kv, ix[IX_DEC_IDS] + p.r0};
+    RC(run_decoder(e, sl, p.ld, ragged ? &rows : nullptr));
+    rmsnorm(e, sd, sl.dec.hidden, e->dec_final_ln, sl.dec.xn, nullptr, p.rows, head_scale(e));
+    float* xlab = e->logits.p + (size_t)p.rows * nblk * 2;
+    RC(gemm(e, sd, Gemm(PC_HEAD, EPI_LSE_F32, sl.dec.xn, dm, e->lm_head, dm, e->logits.p, nblk, p.rows, e->d.vocab, dm).lse(ix[IX_ROW_LABEL] + p.r0, xlab)));
+    hipLaunchKernelGGL(qlm_lse_kernel, dim3(p.n_seq), dim3(256), 0, sd, (const float2*)e->logits.p, nblk, xlab, ragged ? 0 : p.ld, off,
+                       ragged ? ix[IX_OUT_IDX] + p.s0 : nullptr, sl.d_scores);
+  }
+  return read_scores_blocking(e, sl, sd, (size_t)sl.n_seq, out_scores);
+}
+
 int rk_t5_qlm(rk_engine* e, const int32_t* tokens, const int32_t* seq_offsets, int n_seq, const int32_t* labels,
               int n_labels, float* out_scores) {
   int rc;
@@ -1865,55 +1962,32 @@ int rk_t5_qlm(rk_engine* e, const int32_t* tokens, const int32_t* seq_offsets, i
   Slot& sl = e->slots[0];
   if (!labels || n_labels <= 0 || n_labels > e->d.max_dec_len) return fail(e, RK_ERR_CAPACITY, "n_labels %d out of range (max %d)", n_labels, e->d.max_dec_len);
   if ((rc = check_ids(e, labels, n_labels, "label"))) return rc;
-  // decoder input = shift_right(labels): [decoder_start(0), labels[:-1]]  (hf: modeling_t5.py:618-637)
-  std::vector<int> dec_in(n_labels);
-  dec_in[0] = 0;
-  for (int t = 1; t < n_labels; ++t) dec_in[t] = labels[t - 1];
-  hipStream_t sd = dec_stream(e, sl);
-  if ((rc = upload_dec_ids_shared(e, sl, dec_in.data(), n_labels))) return rc;
-  const int M = n_seq * n_labels;
-  std::vector<int> row_label((size_t)M);   // the head's label per ROW (the array rk_t5_qlm_many fills per sequence)
-  for (int b = 0; b < n_seq; ++b) memcpy(&row_label[(size_t)b * n_labels], labels, n_labels * sizeof(int));
-  HIPCHK(e, hipStreamSynchronize(sd));
-  HIPCHK(e, hipMemcpy(sl.d_row_label, row_label.data(), row_label.size() * sizeof(int), hipMemcpyHostToDevice));
-  if ((rc = ensure_logits(e, M))) return rc;
-  if ((rc = encoder_then_handoff(e, sl, n_labels))) return rc;
-  if ((rc = run_decoder(e, sl, n_labels))) return rc;
-  rmsnorm(e, sd, sl.dec.hidden, e->dec_final_ln, sl.dec.xn, nullptr, M, head_scale(e));
-  // head GEMM with the log-sum-exp fused into its epilogue: per row and 32-column block (max, sum exp) + the label's logit
-  const int nblk = (e->d.vocab + 31) / 32;
-  e->lse_labels = sl.d_row_label; e->lse_xlab = e->logits.p + (size_t)M * nblk * 2;
-  RC(gemm(e, sd, Gemm(PC_HEAD, EPI_LSE_F32, sl.dec.xn, e->d.d_model, e->lm_head, e->d.d_model, e->logits.p, nblk, M, e->d.vocab, e->d.d_model)));
-  hipLaunchKernelGGL(qlm_lse_kernel, dim3(n_seq), dim3(256), 0, sd, (const float2*)e->logits.p, nblk, e->lse_xlab, n_labels, nullptr, nullptr, sl.d_scores);
-  HIPCHK(e, hipMemcpyAsync(sl.h_scores, sl.d_scores, (size_t)n_seq * sizeof(float), hipMemcpyDeviceToHost, sd));
-  RC(finish_blocking(e, sl));
-  HIPCHK(e, hipGetLastError());
-  memcpy(out_scores, sl.h_scores, (size_t)n_seq * sizeof(float));
-  return RK_OK;
+  std::vector<int> dec_in, row_label;   // the head's label per ROW (the array rk_t5_qlm_many fills per sequence)
+  shift_right(labels, n_labels, &dec_in);
+  for (int b = 0; b < n_seq; ++b) row_label.insert(row_label.end(), labels, labels + n_labels);
+  if ((rc = put_dec_ids_shared(e, sl, dec_in.data(), n_labels))) return rc;
+  if ((rc = sl.idx.write(e, dec_stream(e, sl), {{IX_ROW_LABEL, row_label}}))) return rc;
+  // ONE uniform pass: run_decoder's plain form, as rk_t5_score_slot runs it
+  return run_qlm(e, sl, {{0, n_seq, 0, n_seq * n_labels, n_labels, -1, !use_xattn_direct(e, sl, n_labels)}}, out_scores);
 }
 
 // rk_t5_qlm for sequences that each score their OWN label sequence.  A sequence's score is bit for bit what rk_t5_qlm gives it
 // with those labels, whatever shares the call: the sequences are ordered by the class of their label count (dec_len_class - the
 // encoder does not care about order), the encoder runs ONCE over all of them (cross K / V materialised iff some class reads
-// them), then every non-empty class is one ragged decoder pass + final norm + LSE head over its contiguous sequence range, and
-// qlm_lse_kernel writes each score at the sequence's place in the caller's order.  (A pass of at most dec_gemv_rows rows at two
-// or more positions takes the few-row GEMV family, as in rk_t5_qlm: DESIGN.md section 4.)
+// them), then every non-empty class is one ragged pass of run_qlm over its contiguous sequence range, and qlm_lse_kernel writes
+// each score at the sequence's place in the caller's order.  (A pass of at most dec_gemv_rows rows at two or more positions
+// takes the few-row GEMV family, as in rk_t5_qlm: DESIGN.md section 4.)
 int rk_t5_qlm_many(rk_engine* e, const int32_t* tokens, const int32_t* seq_offsets, int n_seq, const int32_t* labels,
                    const int32_t* label_offsets, float* out_scores) {
   if (!e) return RK_ERR_INVALID;
   if (e->family != 0) return fail(e, RK_ERR_STATE, "T5 entry point called on a Llama engine (use rk_llama_*)");
-  if (!e->finalized) return fail(e, RK_ERR_STATE, "engine not finalized");
-  if (!tokens || !seq_offsets || n_seq <= 0 || !out_scores) return fail(e, RK_ERR_INVALID, "empty batch (n_seq=%d)", n_seq);
-  if (n_seq > e->d.max_seqs) return fail(e, RK_ERR_CAPACITY, "n_seq %d > max_seqs %d", n_seq, e->d.max_seqs);
-  if (!labels || !label_offsets) return fail(e, RK_ERR_INVALID, "labels missing");
-  if (seq_offsets[0] != 0 || label_offsets[0] != 0) return fail(e, RK_ERR_INVALID, "seq_offsets[0] and label_offsets[0] must be 0");
-  const int max_ld = e->d.max_dec_len;
-  for (int b = 0; b < n_seq; ++b) {
-    const int nb = label_offsets[b + 1] - label_offsets[b];
-    if (nb <= 0 || nb > max_ld) return fail(e, RK_ERR_CAPACITY, "sequence %d: n_labels %d out of range (max %d)", b, nb, max_ld);
-    if (seq_offsets[b + 1] <= seq_offsets[b]) return fail(e, RK_ERR_INVALID, "sequence %d is empty", b);
-  }
   int rc;
+  if ((rc = check_batch(e, nullptr, tokens, seq_offsets, n_seq))) return rc;   // before the reorder reads the batch
+  if (!out_scores || !labels || !label_offsets || label_offsets[0] != 0) return fail(e, RK_ERR_INVALID, "labels, label_offsets (from 0) or output missing");
+  const int max_ld = e->d.max_dec_len;
+  auto n_of = [&](int b) { return label_offsets[b + 1] - label_offsets[b]; };
+  for (int b = 0; b < n_seq; ++b)
+    if (n_of(b) <= 0 || n_of(b) > max_ld) return fail(e, RK_ERR_CAPACITY, "sequence %d: n_labels %d out of range (max %d)", b, n_of(b), max_ld);
   if ((rc = check_ids(e, labels, label_offsets[n_seq], "label"))) return rc;
   // class index of every label count, in order of first appearance as the count grows; the sequences in class order (stable)
   std::vector<int> cls_of((size_t)max_ld + 1, 0), keys;
@@ -1925,7 +1999,6 @@ int rk_t5_qlm_many(rk_engine* e, const int32_t* tokens, const int32_t* seq_offse
     if (i == keys.size()) { keys.push_back(c.key()); classes.push_back(c); }
     cls_of[n] = (int)i;
   }
-  auto n_of = [&](int b) { return label_offsets[b + 1] - label_offsets[b]; };
   std::vector<int> order((size_t)n_seq);
   for (int b = 0; b < n_seq; ++b) order[b] = b;
   std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return cls_of[n_of(x)] < cls_of[n_of(y)]; });
@@ -1937,53 +2010,26 @@ int rk_t5_qlm_many(rk_engine* e, const int32_t* tokens, const int32_t* seq_offse
   }
   if ((rc = rk_t5_stage(e, ptok.data(), poff.data(), n_seq))) return rc;
   Slot& sl = e->slots[0];
-  hipStream_t sd = dec_stream(e, sl);
-  // per row, pass after pass: decoder id (shift_right of the sequence's labels; hf: modeling_t5.py:618-637), label, sequence;
-  // per pass: its sequences' row offsets (relative to the pass)
-  struct Pass { int s0, s1, r0, rows, ld, off0; DecLenClass c; };
-  std::vector<Pass> passes;
+  // per row, pass after pass: decoder id, label, sequence; per pass: its sequences' row offsets (relative to the pass)
+  std::vector<QlmPass> passes;
   std::vector<int> ids, rlab, rseq, roff;
-  bool need_kv = false;
-  int max_rows = 0;
   for (int s = 0; s < n_seq;) {
-    Pass p{s, s, (int)ids.size(), 0, 0, (int)roff.size(), classes[cls_of[n_of(order[s])]]};
-    while (p.s1 < n_seq && cls_of[n_of(order[p.s1])] == cls_of[n_of(order[s])]) {
-      const int b = order[p.s1], nb = n_of(b);
+    const int cls = cls_of[n_of(order[s])];
+    QlmPass p{s, 0, (int)ids.size(), 0, 0, (int)roff.size(), !classes[cls].direct};
+    for (; s < n_seq && cls_of[n_of(order[s])] == cls; ++s, ++p.n_seq) {
+      const int b = order[s], nb = n_of(b);
       const int32_t* lab = labels + label_offsets[b];
       roff.push_back(p.rows);
-      for (int t = 0; t < nb; ++t) { ids.push_back(t ? lab[t - 1] : 0); rlab.push_back(lab[t]); rseq.push_back(p.s1); }
-      p.rows += nb; p.ld = std::max(p.ld, nb); ++p.s1;
+      shift_right(lab, nb, &ids);
+      rlab.insert(rlab.end(), lab, lab + nb);
+      rseq.insert(rseq.end(), nb, s);
+      p.rows += nb; p.ld = std::max(p.ld, nb);
     }
     roff.push_back(p.rows);
-    need_kv = need_kv || !p.c.direct;
-    max_rows = std::max(max_rows, p.rows);
     passes.push_back(p);
-    s = p.s1;
   }
-  if ((rc = ensure_logits(e, (size_t)max_rows))) return rc;
-  HIPCHK(e, hipStreamSynchronize(sd));
-  HIPCHK(e, hipMemcpy(sl.d_dec_ids, ids.data(), ids.size() * sizeof(int), hipMemcpyHostToDevice));
-  HIPCHK(e, hipMemcpy(sl.d_row_label, rlab.data(), rlab.size() * sizeof(int), hipMemcpyHostToDevice));
-  HIPCHK(e, hipMemcpy(sl.d_row_seq, rseq.data(), rseq.size() * sizeof(int), hipMemcpyHostToDevice));
-  HIPCHK(e, hipMemcpy(sl.d_row_off, roff.data(), roff.size() * sizeof(int), hipMemcpyHostToDevice));
-  HIPCHK(e, hipMemcpy(sl.d_out_idx, order.data(), order.size() * sizeof(int), hipMemcpyHostToDevice));
-  sl.cache_dec.clear(); ++sl.dec_epoch;   // the shared decoder id / row buffers were written
-  if ((rc = encoder_then_handoff_kv(e, sl, need_kv))) return rc;
-  const int nblk = (e->d.vocab + 31) / 32;
-  for (const Pass& p : passes) {
-    const DecRows rows{p.rows, nullptr, nullptr, sl.d_row_seq + p.r0, sl.d_row_off + p.off0, p.s0, p.s1 - p.s0, !p.c.direct, sl.d_dec_ids + p.r0};
-    if ((rc = run_decoder(e, sl, p.ld, &rows))) return rc;
-    rmsnorm(e, sd, sl.dec.hidden, e->dec_final_ln, sl.dec.xn, nullptr, p.rows, head_scale(e));
-    e->lse_labels = sl.d_row_label + p.r0; e->lse_xlab = e->logits.p + (size_t)p.rows * nblk * 2;
-    RC(gemm(e, sd, Gemm(PC_HEAD, EPI_LSE_F32, sl.dec.xn, e->d.d_model, e->lm_head, e->d.d_model, e->logits.p, nblk, p.rows, e->d.vocab, e->d.d_model)));
-    hipLaunchKernelGGL(qlm_lse_kernel, dim3(p.s1 - p.s0), dim3(256), 0, sd, (const float2*)e->logits.p, nblk, e->lse_xlab, 0,
-                       sl.d_row_off + p.off0, sl.d_out_idx + p.s0, sl.d_scores);
-  }
-  HIPCHK(e, hipMemcpyAsync(sl.h_scores, sl.d_scores, (size_t)n_seq * sizeof(float), hipMemcpyDeviceToHost, sd));
-  RC(finish_blocking(e, sl));
-  HIPCHK(e, hipGetLastError());
-  memcpy(out_scores, sl.h_scores, (size_t)n_seq * sizeof(float));
-  return RK_OK;
+  if ((rc = sl.idx.write(e, dec_stream(e, sl), {{IX_DEC_IDS, ids}, {IX_ROW_LABEL, rlab}, {IX_ROW_SEQ, rseq}, {IX_ROW_OFF, roff}, {IX_OUT_IDX, order}}))) return rc;
+  return run_qlm(e, sl, passes, out_scores);
 }
 
 // Greedy head: full-vocabulary logits of `rows` final-normed rows (x: [rows, d_model] fp16) reduced to their first arg-max
@@ -1997,7 +2043,7 @@ static int ensure_amax(rk_engine* e, size_t rows) {
 }
 static int head_argmax(rk_engine* e, hipStream_t st, const half_t* x, int rows, int d_model, int vocab, int* d_out) {
   const int nblk = (vocab + 31) / 32;
-  const int rc = gemm(e, st, Gemm(PC_HEAD, EPI_ARGMAX_F32, x, d_model, e->lm_head, d_model, e->amax_val.p, nblk, rows, vocab, d_model).on(GEMM_STREAM));
+  const int rc = gemm(e, st, Gemm(PC_HEAD, EPI_ARGMAX_F32, x, d_model, e->lm_head, d_model, e->amax_val.p, nblk, rows, vocab, d_model).on(GEMM_STREAM).argmax(e->amax_idx.p));
   if (rc == RK_OK) hipLaunchKernelGGL(argmax_blocks_kernel, dim3(rows), dim3(256), 0, st, e->amax_val.p, e->amax_idx.p, nblk, d_out);
   return rc;
 }
@@ -2021,13 +2067,11 @@ static int greedy_step(rk_engine* e, Slot& sl, const std::vector<std::vector<int
   hipStream_t sd = dec_stream(e, sl);
   std::vector<int> flat((size_t)n_seq * Ld), rowmap(n_seq);
   for (int b = 0; b < n_seq; ++b) { memcpy(&flat[(size_t)b * Ld], rows[b].data(), Ld * sizeof(int)); rowmap[b] = b * Ld + Ld - 1; }
-  HIPCHK(e, hipStreamSynchronize(sd));
-  HIPCHK(e, hipMemcpy(sl.d_dec_ids, flat.data(), flat.size() * sizeof(int), hipMemcpyHostToDevice));
-  HIPCHK(e, hipMemcpy(sl.d_last_rows, rowmap.data(), n_seq * sizeof(int), hipMemcpyHostToDevice));
-  sl.cache_dec.clear(); sl.cache_rows.clear(); ++sl.dec_epoch;
-  int rc = run_graphed(e, sd, {1, 0, n_seq, Ld, sl.have_cross_kv ? sl.maxL : (sl.maxL + 63) / 64, (int)sl.have_cross_kv, e->amax_gen}, [&]() -> int {
+  int rc = sl.idx.write(e, sd, {{IX_DEC_IDS, flat}, {IX_LAST_ROWS, rowmap}});
+  if (rc) return rc;
+  rc = run_graphed(e, sd, {GK_T5_GREEDY_STEP, 0, n_seq, Ld, sl.have_cross_kv ? sl.maxL : (sl.maxL + 63) / 64, (int)sl.have_cross_kv, e->amax_gen}, [&]() -> int {
     const int r = run_decoder(e, sl, Ld);
-    return r ? r : final_argmax(e, sd, sl, sl.d_last_rows, n_seq);
+    return r ? r : final_argmax(e, sd, sl, sl.idx.d[IX_LAST_ROWS], n_seq);
   });
   if (rc) return rc;
   amax.resize(n_seq);
@@ -2039,8 +2083,7 @@ int rk_t5_greedy(rk_engine* e, const int32_t* tokens, const int32_t* seq_offsets
   int rc;
   if ((rc = rk_t5_stage(e, tokens, seq_offsets, n_seq))) return rc;
   Slot& sl = e->slots[0];
-  if (!dec_prefix || dec_len <= 0 || max_new <= 0 || dec_len + max_new - 1 > e->d.max_dec_len)
-    return fail(e, RK_ERR_CAPACITY, "dec_len %d + max_new %d exceeds max_dec_len %d", dec_len, max_new, e->d.max_dec_len);
+  if ((rc = check_greedy_args(e, dec_prefix, dec_len, max_new))) return rc;
   if ((rc = check_ids(e, dec_prefix, dec_len, "decoder"))) return rc;
   if ((rc = ensure_amax(e, (size_t)n_seq))) return rc;
   if ((rc = encoder_then_handoff(e, sl, dec_len + max_new - 1))) return rc;
@@ -2092,8 +2135,7 @@ int rk_t5_generate(rk_engine* e, const int32_t* tokens, const int32_t* seq_offse
   int rc;
   if ((rc = rk_t5_stage(e, tokens, seq_offsets, n_seq))) return rc;
   Slot& sl = e->slots[0];
-  if (!dec_prefix || dec_len <= 0 || max_new <= 0 || dec_len + max_new - 1 > e->d.max_dec_len)
-    return fail(e, RK_ERR_CAPACITY, "dec_len %d + max_new %d exceeds max_dec_len %d", dec_len, max_new, e->d.max_dec_len);
+  if ((rc = check_greedy_args(e, dec_prefix, dec_len, max_new))) return rc;
   if (!out_tokens) return fail(e, RK_ERR_INVALID, "null output");
   if ((rc = check_ids(e, dec_prefix, dec_len, "decoder"))) return rc;
   const int P = dec_len + max_new;                                       // cache positions per sequence (the last: a step past the end)
@@ -2112,20 +2154,18 @@ int rk_t5_generate(rk_engine* e, const int32_t* tokens, const int32_t* seq_offse
     for (int j = 0; j < P; ++j) init[o_keys + (size_t)b * P + j] = b * P + j;
   std::vector<int> ids0(n_seq, dec_prefix[0]);
   int* g = e->gen_buf.p;
-  HIPCHK(e, hipStreamSynchronize(sd));
+  if ((rc = sl.idx.write(e, sd, {{IX_DEC_IDS, ids0}}))) return rc;   // (leaves sd idle)
   HIPCHK(e, hipMemcpy(g, init.data(), n_ints * sizeof(int), hipMemcpyHostToDevice));
-  HIPCHK(e, hipMemcpy(sl.d_dec_ids, ids0.data(), n_seq * sizeof(int), hipMemcpyHostToDevice));
-  sl.cache_dec.clear(); ++sl.dec_epoch;
   const DecCache kc{e->kv_cache.p, P, g, g + o_keys, g + o_tpos};
   auto step = [&]() -> int {
     int r = run_decoder(e, sl, 1, nullptr, &kc);
     if (r || (r = final_argmax(e, sd, sl, nullptr, n_seq))) return r;
     Bracket br(e, sd, PC_OTHER, 0, 0);
-    hipLaunchKernelGGL(greedy_advance_kernel, dim3(1), dim3(256), 0, sd, sl.d_argmax, g, g + o_pre, g + o_done, g + o_out, sl.d_dec_ids,
+    hipLaunchKernelGGL(greedy_advance_kernel, dim3(1), dim3(256), 0, sd, sl.d_argmax, g, g + o_pre, g + o_done, g + o_out, sl.idx.d[IX_DEC_IDS],
                        n_seq, dec_len, max_new);
     return RK_OK;
   };
-  const std::vector<int> key{3, 0, n_seq, (sl.maxL + 63) / 64, dec_len, max_new, e->amax_gen, e->kv_gen};
+  const std::vector<int> key{GK_T5_GENERATE_STEP, 0, n_seq, (sl.maxL + 63) / 64, dec_len, max_new, e->amax_gen, e->kv_gen};
   // dec_len - 1 forced prefix steps, then one step per new column
   if ((rc = decode_cached(e, sd, key, step, dec_len - 1, 0, n_seq, max_new, g + 1, g + o_out, out_tokens, out_steps))) return rc;
   return finish_blocking(e, sl);
@@ -2175,26 +2215,16 @@ int rk_t5_greedy2(rk_engine* e, const int32_t* tokens, const int32_t* seq_offset
     }
   }
   // the five index arrays are the same for every compare of a query (same prefix, candidates and prompt count): uploaded
-  // only when they differ from what this path left on the device and nobody else wrote the shared id / row buffers since
+  // only when they differ from what this path left on the device or something else was written since (DecIndex::tree)
   std::vector<int> sig;
   sig.reserve(ids.size() + rows.size() + rseq.size() + rpos.size() + keys.size() + 2);
   sig.push_back(n_seq); sig.push_back(Ld);
   for (const std::vector<int>* v : {&ids, &rows, &rseq, &rpos, &keys}) sig.insert(sig.end(), v->begin(), v->end());
-  if (sl.g2_epoch != sl.dec_epoch || sig != sl.cache_g2) {
-    HIPCHK(e, hipStreamSynchronize(sd));
-    HIPCHK(e, hipMemcpy(sl.d_dec_ids, ids.data(), ids.size() * sizeof(int), hipMemcpyHostToDevice));
-    HIPCHK(e, hipMemcpy(sl.d_last_rows, rows.data(), rows.size() * sizeof(int), hipMemcpyHostToDevice));
-    HIPCHK(e, hipMemcpy(sl.d_row_seq, rseq.data(), rseq.size() * sizeof(int), hipMemcpyHostToDevice));
-    HIPCHK(e, hipMemcpy(sl.d_tree_pos, rpos.data(), rpos.size() * sizeof(int), hipMemcpyHostToDevice));
-    HIPCHK(e, hipMemcpy(sl.d_tree_keys, keys.data(), keys.size() * sizeof(int), hipMemcpyHostToDevice));
-    sl.cache_dec.clear(); sl.cache_rows.clear();
-    sl.cache_g2.swap(sig);
-    sl.g2_epoch = ++sl.dec_epoch;
-  }
-  const DecRows tree{(int)M, sl.d_tree_keys, sl.d_tree_pos, sl.d_row_seq};
-  rc = run_graphed(e, sd, {2, 0, n_seq, Ld, (sl.maxL + 63) / 64, n_cand, e->amax_gen}, [&]() -> int {
+  if ((rc = sl.idx.tree(e, sd, sig, {{IX_DEC_IDS, ids}, {IX_LAST_ROWS, rows}, {IX_ROW_SEQ, rseq}, {IX_TREE_POS, rpos}, {IX_TREE_KEYS, keys}}))) return rc;
+  const DecRows tree{(int)M, sl.idx.d[IX_TREE_KEYS], sl.idx.d[IX_TREE_POS], sl.idx.d[IX_ROW_SEQ]};
+  rc = run_graphed(e, sd, {GK_T5_GREEDY2, 0, n_seq, Ld, (sl.maxL + 63) / 64, n_cand, e->amax_gen}, [&]() -> int {
     const int r = run_decoder(e, sl, Ld, &tree);
-    return r ? r : final_argmax(e, sd, sl, sl.d_last_rows, (int)R);
+    return r ? r : final_argmax(e, sd, sl, sl.idx.d[IX_LAST_ROWS], (int)R);
   });
   if (rc || (rc = read_argmax(e, sd, sl, amax.data(), (int)R))) return rc;
   bool all_done = true, miss = false;
@@ -2325,11 +2355,11 @@ static int llama_finalize(rk_engine* e) {
   RC(dalloc(e, &sl.enc.factors, Tc + 512)); HIPCHK(e, hipMemset(sl.enc.factors, 0, (Tc + 512) * sizeof(float)));
   RC(dalloc(e, &sl.qkv, Tc * (Q + 2 * KV))); RC(dalloc(e, &sl.ctx, Tc * Q)); RC(dalloc(e, &sl.ffh, Tc * F));
   RC(dalloc(e, &sl.d_tokens, Tc)); RC(dalloc(e, &e->d_pos, Tc)); RC(dalloc(e, &sl.d_seq_off, Bc + 1));
-  RC(dalloc(e, &sl.d_last_rows, Bc)); RC(dalloc(e, &sl.d_out_ids, 8192)); RC(dalloc(e, &sl.d_argmax, Bc)); RC(dalloc(e, &sl.dlast, Bc * dm));
+  RC(dalloc(e, &sl.idx.d[IX_LAST_ROWS], Bc)); RC(dalloc(e, &sl.idx.d[IX_OUT_IDS], 8192)); RC(dalloc(e, &sl.d_argmax, Bc)); RC(dalloc(e, &sl.dlast, Bc * dm));
   e->scores_cap = Bc * 64;
   RC(dalloc(e, &sl.d_scores, e->scores_cap));
   HIPCHK(e, hipHostMalloc((void**)&sl.h_scores, e->scores_cap * sizeof(float), hipHostMallocDefault));
-  HIPCHK(e, hipHostMalloc((void**)&sl.h_small, 4 * 8192 * sizeof(int), hipHostMallocDefault));
+  HIPCHK(e, hipHostMalloc((void**)&sl.idx.pin, IX_N_CACHED * DecIndex::PIN_INTS * sizeof(int), hipHostMallocDefault));
   HIPCHK(e, hipDeviceSynchronize());
   e->finalized = true;
   return RK_OK;
@@ -2343,7 +2373,7 @@ static int llama_prefill(rk_engine* e, const int32_t* tokens, const int32_t* off
   int rc = set_device(e);
   if (rc) return rc;
   Slot& sl = e->slots[0];
-  if ((rc = check_batch(e, sl, tokens, off, n_seq))) return rc;
+  if ((rc = check_batch(e, &sl, tokens, off, n_seq))) return rc;
   const rk_llama_desc& l = e->ld;
   const int T = sl.T, dm = l.hidden, Q = l.n_heads * 128, KV = l.n_kv_heads * 128, F = l.intermediate, ldq = Q + 2 * KV;
   hipStream_t st = sl.se;
@@ -2356,7 +2386,7 @@ static int llama_prefill(rk_engine* e, const int32_t* tokens, const int32_t* off
   HIPCHK(e, hipMemcpy(sl.d_tokens, tokens, (size_t)T * sizeof(int), hipMemcpyHostToDevice));
   HIPCHK(e, hipMemcpy(e->d_pos, pos.data(), (size_t)T * sizeof(int), hipMemcpyHostToDevice));
   HIPCHK(e, hipMemcpy(sl.d_seq_off, off, (size_t)(n_seq + 1) * sizeof(int), hipMemcpyHostToDevice));
-  HIPCHK(e, hipMemcpy(sl.d_last_rows, last.data(), (size_t)n_seq * sizeof(int), hipMemcpyHostToDevice));
+  RC(sl.idx.write(e, st, {{IX_LAST_ROWS, last}}));
   // every consumer takes its row factors from rowscale_kernel (own_factors = false), also where a fill-in tile variant could
   // form them itself
   NormStream ns = sl.enc;
@@ -2381,7 +2411,7 @@ static int llama_prefill(rk_engine* e, const int32_t* tokens, const int32_t* off
     RC(gemm(e, st, ns.consumer(e, st, nullptr, Gemm(PC_ENC_GEMM_FFN_IN, EPI_SWIGLU_F16, ns.x(), dm, w.gu_f, dm, sl.ffh, F, T, 2 * F, dm), false)));
     RC(ns.producer(e, st, Gemm(PC_ENC_GEMM_FFN_OUT, EPI_RESID_F32, sl.ffh, F, w.down, F, ns.hidden, dm, T, dm, F), i + 1 < l.n_layers));
   }
-  rmsnorm(e, st, ns.hidden, e->l_final_ln, sl.dlast, sl.d_last_rows, n_seq);
+  rmsnorm(e, st, ns.hidden, e->l_final_ln, sl.dlast, sl.idx.d[IX_LAST_ROWS], n_seq);
   HIPCHK(e, hipGetLastError());
   return RK_OK;
 }
@@ -2395,14 +2425,10 @@ int rk_llama_last_logits(rk_engine* e, const int32_t* tokens, const int32_t* seq
   if ((rc = llama_prefill(e, tokens, seq_offsets, n_seq))) return rc;
   Slot& sl = e->slots[0];
   hipStream_t st = sl.se;
-  HIPCHK(e, hipMemcpyAsync(sl.d_out_ids, out_token_ids, n_out * sizeof(int), hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(head_rows_kernel, dim3((n_seq * n_out + 3) / 4), dim3(256), 0, st, sl.dlast, e->lm_head, sl.d_out_ids,
+  HIPCHK(e, hipMemcpyAsync(sl.idx.d[IX_OUT_IDS], out_token_ids, n_out * sizeof(int), hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(head_rows_kernel, dim3((n_seq * n_out + 3) / 4), dim3(256), 0, st, sl.dlast, e->lm_head, sl.idx.d[IX_OUT_IDS],
                      sl.d_scores, n_seq, n_out, e->ld.hidden);
-  HIPCHK(e, hipMemcpyAsync(sl.h_scores, sl.d_scores, (size_t)n_seq * n_out * sizeof(float), hipMemcpyDeviceToHost, st));
-  HIPCHK(e, hipStreamSynchronize(st));
-  HIPCHK(e, hipGetLastError());
-  memcpy(out_logits, sl.h_scores, (size_t)n_seq * n_out * sizeof(float));
-  return RK_OK;
+  return read_scores_blocking(e, sl, st, (size_t)n_seq * n_out, out_logits);
 }
 
 int rk_llama_set_rope_scaling(rk_engine* e, float factor, float low_freq_factor, float high_freq_factor, int original_max_pos) {
@@ -2464,7 +2490,7 @@ int rk_llama_generate(rk_engine* e, const int32_t* tokens, const int32_t* seq_of
   if ((rc = check_ids(e, eos_ids, n_eos, "eos")) || (rc = check_ids(e, &pad_id, 1, "pad"))) return rc;
   if ((rc = set_device(e))) return rc;
   Slot& sl = e->slots[0];
-  if ((rc = check_batch(e, sl, tokens, seq_offsets, n_seq))) return rc;
+  if ((rc = check_batch(e, &sl, tokens, seq_offsets, n_seq))) return rc;
   const rk_llama_desc& l = e->ld;
   if ((long)sl.maxL + max_new > l.max_tokens)
     return fail(e, RK_ERR_CAPACITY, "longest prompt %d + max_new %d exceeds max_tokens %d (the rotary tables end there)", sl.maxL, max_new, l.max_tokens);
@@ -2520,7 +2546,7 @@ int rk_llama_generate(rk_engine* e, const int32_t* tokens, const int32_t* seq_of
     rmsnorm(e, st, ns.hidden, e->l_final_ln, sl.dlast, nullptr, n_seq);
     return head_and_advance();
   };
-  const std::vector<int> key{4, 0, n_seq, P, e->amax_gen, e->lkv_gen};
+  const std::vector<int> key{GK_LLAMA_STEP, 0, n_seq, P, e->amax_gen, e->lkv_gen};
   // column 0 is the prefill's: the steps produce columns 1 .. max_new - 1
   return decode_cached(e, st, key, step, 0, 1, n_seq, max_new, g + 1, d_out, out_tokens, out_steps);
 }
@@ -2845,6 +2871,7 @@ int rk_debug_gemm_ex(rk_engine* e, rk_debug_gemm_call* q) {
   else if (q->ssq_in) { c.fold.ssq_in = (const float*)dummy; c.fold.nb_in = q->nb_in; }
   if (q->ssq_in && q->nb_in <= 0) return fail(e, RK_ERR_INVALID, "debug gemm: ssq_in without nb_in");
   if (producer) { c.fold.xraw = dummy; c.fold.ssq = (float*)dummy; }
+  c.lse((const int*)dummy, (float*)dummy).argmax((int*)dummy);
   hipStream_t st = e->slots[0].se;
   const GemmPlan p = plan_gemm(e, c, st);
   q->out_family = (int)p.family; q->out_variant = p.variant; q->out_m_pp2 = p.m_pp2; q->out_ksplit = p.m_pp2 > 0 ? p.ks_pp2 : p.ksplit;
@@ -2906,13 +2933,9 @@ int rk_debug_gemm_ex(rk_engine* e, rk_debug_gemm_call* q) {
     c.fold.rowscale = dR;
   } else if (q->ssq_in) { c.fold.ssq_in = dQ; c.fold.nb_in = q->nb_in; }
   if (producer) { c.fold.xraw = dX + xband; c.fold.ssq = dS + sband; }
-  // the buffers the block epilogues take from the engine, for the length of this call
-  int* const saved_idx = e->amax_idx.p; const int* const saved_lab = e->lse_labels; float* const saved_xlab = e->lse_xlab;
-  if (dI) e->amax_idx.p = dI + band + q->c_off;
-  if (dL) { e->lse_labels = dL; e->lse_xlab = dXl; }
+  c.lse(dL, dXl).argmax(dI ? dI + band + q->c_off : nullptr);
   int nb = 0;
   rc = gemm(e, st, c, &nb);
-  e->amax_idx.p = saved_idx; e->lse_labels = saved_lab; e->lse_xlab = saved_xlab;
   if (rc) return done(rc);
   DBG_HIP(hipStreamSynchronize(st));
   DBG_HIP(hipGetLastError());
