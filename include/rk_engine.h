@@ -148,6 +148,12 @@ int rk_llama_create(const rk_llama_desc* desc, int device_ordinal, rk_engine** o
  * interpolated.  Call between rk_llama_create and rk_engine_finalize (the rotary tables are built there); never calling
  * it = the default rope type. */
 int rk_llama_set_rope_scaling(rk_engine* e, float factor, float low_freq_factor, float high_freq_factor, int original_max_pos);
+/* Qwen2 family (hf: models/qwen2/modeling_qwen2.py; Qwen2.5-Instruct checkpoints, the Rank-R1 rerankers of ref:
+ * llmrankers/setwise.py:406-553): the q / k / v projections carry a bias.  on != 0: rk_engine_finalize requires
+ * model.layers.N.self_attn.{q,k,v}_proj.bias (shapes n_heads * 128, n_kv_heads * 128, n_kv_heads * 128) and the engine adds them
+ * in fp32 to the projections' output before the rotation.  Call between rk_llama_create and the first rk_engine_load_tensor;
+ * RK_ERR_STATE on a T5 engine or after finalize.  Never calling it (or on = 0): the bias names are ignored. */
+int rk_llama_set_qkv_bias(rk_engine* e, int on);
 /* next token of every prompt: first arg-max over the whole vocabulary of the logits at its last position */
 int rk_llama_greedy1(rk_engine* e, const int32_t* tokens, const int32_t* seq_offsets, int n_seq, int32_t* out_tokens);
 /* the same logits for a few vocabulary rows only -> out_logits[n_seq][n_out] fp32 (label scoring, tests) */

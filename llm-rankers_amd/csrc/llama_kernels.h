@@ -9,12 +9,47 @@
 #include "common.h"
 #include "xcd_map.h"
 
+// The q / k / v projection bias of the Qwen2 family (hf: models/qwen2/modeling_qwen2.py: Qwen2Attention, q_proj / k_proj / v_proj
+// with bias=True): fp32, added to the fp16 GEMM output.  It cannot be folded into the weights - the QKV GEMM multiplies its
+// output by the folded RMSNorm's row factor, the bias comes after that - so it is added where the row is touched next: here (prefill)
+// and in attn_dec_cached128_kernel's row load (decode step), by THESE helpers, so that both form the same bits.
+__device__ __forceinline__ void bias_add8(float (&x)[8], const half8 a, const float* __restrict__ b) {
+  const f32x4 b0 = *(const f32x4*)b, b1 = *(const f32x4*)(b + 4);
+#pragma unroll
+  for (int j = 0; j < 8; ++j) x[j] = (float)a[j] + (j < 4 ? b0[j & 3] : b1[j & 3]);
+}
+__device__ __forceinline__ half8 bias_v8(const half8 a, const float* __restrict__ b) {   // a value row's 8 dims: one rounding
+  float x[8];
+  bias_add8(x, a, b);
+  half8 o;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) o[j] = f2h_sat(x[j]);
+  return o;
+}
+
+// One rotated pair of the BIAS kernels, in a FIXED form (no contraction left to the compiler): `fused` = both results as one fma
+// over a rounded product, else two rounded products and an add.  EVERY caller - the prefill's q and k, the step's new key and its
+// queries - passes fused = (element 0 of the thread's eight), so a step rounds a row exactly as a prefill does: the cached key IS
+// the prefill's key by construction.  Why element 0: that is what the compiler in use makes of the bias-free rope128_kernel
+// (one v_fma_mix, seven packed multiplies + add), so a prefill with an all-zero bias gives the bias-free bits
+// (tests/test_gpu_rankr1.py).  That equality is tied to one compiler version, not a property of the code; the bias path's own
+// guarantees do not depend on it.
+__device__ __forceinline__ void rope_rot(float x1, float x2, float co, float si, bool fused, float& lo, float& hi) {
+#pragma clang fp contract(off)
+  if (fused) { lo = __builtin_fmaf(co, x1, -(si * x2)); hi = __builtin_fmaf(co, x2, si * x1); }
+  else { lo = co * x1 - si * x2; hi = co * x2 + si * x1; }
+}
+
 // In place on the fused QKV buffer [T, ld]: the first n_rot heads of a row (all query heads, then all key heads) are
 // rotated by the row's position.  cos / sin: [max_pos, 64] fp32 (the two halves of HF's table are equal).
 // One workgroup per token; a thread takes 8 consecutive pairs of one head: 16-byte accesses.
+// BIAS (Qwen2): bias [(n_rot + n_v) * 128] fp32 in q | k | v order is added to the fp16 GEMM output before the rotation - ONE
+// fp16 rounding for q and k, after bias and rotation - and to the n_v value heads behind them (touched only here).  BIAS = false
+// is the Llama kernel as it was: the same instructions, the same bits.
+template <bool BIAS>
 __global__ __launch_bounds__(256) void rope128_kernel(half_t* __restrict__ qkv, const int* __restrict__ pos,
                                                       const float* __restrict__ cos_t, const float* __restrict__ sin_t,
-                                                      int ld, int n_rot) {
+                                                      int ld, int n_rot, const float* __restrict__ bias, int n_v) {
   const int t = blockIdx.x;
   const int p = pos[t];
   half_t* row = qkv + (size_t)t * ld;
@@ -25,15 +60,34 @@ __global__ __launch_bounds__(256) void rope128_kernel(half_t* __restrict__ qkv, 
     half_t* x = row + head * 128 + i0;
     const half8 a = *(const half8*)x, b = *(const half8*)(x + 64);
     half8 oa, ob;
+    if constexpr (BIAS) {
+      float xa[8], xb[8];
+      bias_add8(xa, a, bias + head * 128 + i0);
+      bias_add8(xb, b, bias + head * 128 + 64 + i0);
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const float co = cr[i0 + j], si = sr[i0 + j];
-      const float x1 = (float)a[j], x2 = (float)b[j];
-      oa[j] = f2h_sat(x1 * co - x2 * si);          // q * cos + rotate_half(q) * sin, first half: -x2
-      ob[j] = f2h_sat(x2 * co + x1 * si);          // second half: +x1
+      for (int j = 0; j < 8; ++j) {
+        float lo, hi;
+        rope_rot(xa[j], xb[j], cr[i0 + j], sr[i0 + j], j == 0, lo, hi);
+        oa[j] = f2h_sat(lo);
+        ob[j] = f2h_sat(hi);
+      }
+    } else {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const float co = cr[i0 + j], si = sr[i0 + j];
+        const float x1 = (float)a[j], x2 = (float)b[j];
+        oa[j] = f2h_sat(x1 * co - x2 * si);          // q * cos + rotate_half(q) * sin, first half: -x2
+        ob[j] = f2h_sat(x2 * co + x1 * si);          // second half: +x1
+      }
     }
     *(half8*)x = oa;
     *(half8*)(x + 64) = ob;
+  }
+  if constexpr (BIAS) {
+    for (int c = threadIdx.x; c < n_v * 16; c += 256) {
+      const int off = (n_rot + (c >> 4)) * 128 + (c & 15) * 8;
+      *(half8*)(row + off) = bias_v8(*(const half8*)(row + off), bias + off);
+    }
   }
 }
 
@@ -495,6 +549,7 @@ struct AttnDecCached128Args {
   half_t* ctx;           // [n_seq, n_heads * 128]
   int ld, n_heads, n_kv, P, nch;
   float scale_log2e;     // head_dim**-0.5 * log2(e)
+  const float* bias;     // Qwen2: this layer's q | k | v projection bias [(n_heads + 2 n_kv) * 128] fp32, else null
 };
 #define LDC_CHUNK 128    // keys per workgroup: FIXED, so the chunk boundaries of a sequence follow from its own position alone
 #define LDC_PSTR 132     // floats per partial: 128 accumulators, maximum, sum, 2 unused (16-byte rows)
@@ -508,8 +563,11 @@ struct AttnDecCached128Args {
 // registers and written to the cache by the workgroup that owns the position's chunk.  Each workgroup leaves one (maximum, sum,
 // accumulator) partial per head - its four waves merged in wave order - and attn_dec_combine128_kernel merges a row's chunks
 // in key order: nobody waits on another workgroup, and a row's context depends on its own position only, never on the batch.
-template <int R>
-__global__ __launch_bounds__(256) void attn_dec_cached128_kernel(AttnDecCached128Args p) {
+// BIAS (Qwen2): the row's q / k / v get the projection bias where they are loaded - bias_add8 / bias_v8, rope128_kernel<true>'s
+// arithmetic and rounding - so the key a step writes to the cache is bit for bit the key a prefill writes for that token.
+// A head's arithmetic does not depend on R (every per-head array is indexed by r alone, the merge is per head).
+template <int R, bool BIAS>
+__device__ __forceinline__ void attn_dec_cached128_body(const AttnDecCached128Args& p) {
   __shared__ float s_m[4][R], s_l[4][R];
   __shared__ __attribute__((aligned(16))) float s_acc[4][R][128];
   const int ch = blockIdx.x, h0 = blockIdx.y * R, b = blockIdx.z;
@@ -525,20 +583,36 @@ __global__ __launch_bounds__(256) void attn_dec_cached128_kernel(AttnDecCached12
   float co[8], si[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) { co[j] = p.cos_t[(size_t)pos * 64 + i0 + j]; si[j] = p.sin_t[(size_t)pos * 64 + i0 + j]; }
-  auto rotated = [&](const half_t* head) {               // this lane's 8 dims of the rotated head, rounded as rope128_kernel does
+  // this lane's 8 dims of rotated head hd (of q | k), rounded as rope128_kernel does (BIAS: the same rope_rot calls)
+  auto rotated = [&](int hd) {
+    const half_t* head = row + (size_t)hd * 128;
     const half8 a = *(const half8*)(head + i0), bb = *(const half8*)(head + 64 + i0);
     half8 o;
+    if constexpr (BIAS) {
+      float xa[8], xb[8];
+      bias_add8(xa, a, p.bias + (size_t)hd * 128 + i0);
+      bias_add8(xb, bb, p.bias + (size_t)hd * 128 + 64 + i0);
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const float x1 = (float)a[j], x2 = (float)bb[j];
-      const half_t oa = f2h_sat(x1 * co[j] - x2 * si[j]);
-      const half_t ob = f2h_sat(x2 * co[j] + x1 * si[j]);
-      o[j] = hi ? ob : oa;
+      for (int j = 0; j < 8; ++j) {
+        float lo, up;
+        rope_rot(xa[j], xb[j], co[j], si[j], j == 0, lo, up);
+        o[j] = hi ? f2h_sat(up) : f2h_sat(lo);
+      }
+    } else {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const float x1 = (float)a[j], x2 = (float)bb[j];
+        const half_t oa = f2h_sat(x1 * co[j] - x2 * si[j]);
+        const half_t ob = f2h_sat(x2 * co[j] + x1 * si[j]);
+        o[j] = hi ? ob : oa;
+      }
     }
     return o;
   };
-  const half8 knew = rotated(row + (size_t)(p.n_heads + kvh) * 128);
-  const half8 vnew = *(const half8*)(row + (size_t)(p.n_heads + p.n_kv + kvh) * 128 + c * 8);
+  const half8 knew = rotated(p.n_heads + kvh);
+  const size_t voff = (size_t)(p.n_heads + p.n_kv + kvh) * 128 + c * 8;
+  half8 vnew = *(const half8*)(row + voff);
+  if constexpr (BIAS) vnew = bias_v8(vnew, p.bias + voff);
   half_t* kbase = p.kc + ((size_t)b * p.n_kv + kvh) * p.P * 128 + c * 8;
   half_t* vbase = p.vc + ((size_t)b * p.n_kv + kvh) * p.P * 128 + c * 8;
   if (pos - key0 < LDC_CHUNK && h0 % G == 0 && wave == 0 && kg == 0) {   // the position's chunk, once per kv head
@@ -572,7 +646,7 @@ __global__ __launch_bounds__(256) void attn_dec_cached128_kernel(AttnDecCached12
     float s[R][8];
 #pragma unroll
     for (int r = 0; r < R; ++r) {
-      const half8 q = rotated(row + (size_t)(h0 + r) * 128);
+      const half8 q = rotated(h0 + r);
 #pragma unroll
       for (int i = 0; i < 8; ++i) {
         float d = 0.f;
@@ -633,6 +707,12 @@ __global__ __launch_bounds__(256) void attn_dec_cached128_kernel(AttnDecCached12
     }
   }
 }
+
+// the two entry points of the body above: the bias-free kernel (Llama: the kernel as it always was) and the Qwen2 one
+template <int R>
+__global__ __launch_bounds__(256) void attn_dec_cached128_kernel(AttnDecCached128Args p) { attn_dec_cached128_body<R, false>(p); }
+template <int R>
+__global__ __launch_bounds__(256) void attn_dec_cached128_bias_kernel(AttnDecCached128Args p) { attn_dec_cached128_body<R, true>(p); }
 
 // Merges the chunk partials of one (sequence, head) in key order and writes the fp16 context.  grid = (n_heads, n_seq), 128
 // threads = the head's 128 dims.

@@ -59,7 +59,7 @@ struct DecLayerW {
 };
 
 // Llama-family decoder layer (hf: modeling_llama.py:291-330): fused q|k|v and interleaved gate|up carry the RMSNorm weights
-struct LlamaLayerW { half_t *qkv_f = nullptr, *o = nullptr, *gu_f = nullptr, *down = nullptr; };
+struct LlamaLayerW { half_t *qkv_f = nullptr, *o = nullptr, *gu_f = nullptr, *down = nullptr; float* qkv_bias = nullptr; };   // qkv_bias: Qwen2 only (rk_llama_set_qkv_bias), fp32 [Q + 2 KV], NOT scaled by the norm weight
 
 struct ProfRec { hipEvent_t a, b; int cls; };
 
@@ -180,7 +180,7 @@ struct rk_engine {
         gemm_persistent = 1, fold_norm = 1, s64_stages = 0, dec_fold_norm = 1, greedy_spec = 160, consumer_stats = 1, xattn_mfma = 1,
         dec_ffn_tiled = 1, gemm_split = 1, dec_fuse = 1, dec_fuse_rows = 0, dec_attn_seq = 1, attn_long = 1, attn_long_nw = 0,
         llama_attn_dma = 1, attn_long_xcd = 1, llama_attn_nw = 0, dec_graph = 1, gemm_sk = 1, dec_cross_mfma = 1, dec_gemv = 1, dec_gemv_rows = 4,
-        dec_cached_attn = 1;
+        dec_cached_attn = 1, llama_dec_r = 0;
   } opt;
   float* attn_trace = nullptr;   // measurement builds only (option attn_trace)
   int n_cu = 256;
@@ -196,6 +196,7 @@ struct rk_engine {
   // intermediate, eps, capacities) so that the helpers below serve both families
   int family = 0; rk_llama_desc ld{};
   float rope_factor = 0.f, rope_low = 1.f, rope_high = 4.f; int rope_orig = 0;   // rope type llama3 when rope_factor > 0
+  bool qkv_bias = false;                                                          // Qwen2 family: q / k / v projections carry a bias
   std::vector<LlamaLayerW> ll; float *l_final_ln = nullptr, *rope_cos = nullptr, *rope_sin = nullptr; int* d_pos = nullptr;
   // rk_llama_generate: K / V cache [n_layers][2][n_seq][n_kv][P][128], the attention partials and the call's int block (grown
   // between calls; lkv_gen counts the moves and is part of the step graph's key), and the step's activation rows (max_seqs each)
@@ -1015,13 +1016,19 @@ void launch_llama_attn(rk_engine* e, hipStream_t st, const Slot& sl, const Causa
 
 // Single-token attention of one rk_llama_generate step over the K / V cache of P positions per sequence: the chunk kernel over
 // (key chunks of P, groups of R query heads, rows), then the merge per (head, row).  R = the largest of 8 / 4 / 2 / 1 that divides
-// the query heads per kv head (Llama-3-8B: 4): a model constant, so a row's bits never depend on the call.
+// the query heads per kv head G (Llama-3-8B: 4): a model constant, so a row's bits never depend on the call.  Nor do they depend
+// on R: a head's arithmetic in attn_dec_cached128_kernel indexes every per-head array by r alone and the merge is per head.
+// R = G = 7 (Qwen2.5-7B: 28 heads on 4, R = 1 by the rule, every cached byte read 7 times) has an instantiation of its own behind
+// option llama_dec_r = 2 (measurement and tests only; G = 6 / 5 / 3 were not measured and have none), but is NOT the rule: measured at Qwen2.5-7B widths it lost at one row (6.19 against 5.95 ms
+// per token: 17 chunks x 4 kv heads = 68 workgroups on 256 CUs, where R = 1 has 476 and L2 serves the re-reads) and only tied
+// at eight rows (7.60 / 7.65; profiles/rankr1_bench.txt).  llama_dec_r = 1 forces R = 1.  Same bits whichever (tests).
 struct LlamaDecAttnPlan { int R = 1, nch = 1; dim3 grid, cgrid; };
 LlamaDecAttnPlan plan_llama_dec_attn(const rk_engine* e, int rows, int P, int n_heads, int n_kv) {
-  (void)e;                                                   // (no option and no CU count enters: fixed chunk length, model-constant R)
-  LlamaDecAttnPlan p;
+  LlamaDecAttnPlan p;                                        // (no CU count enters: fixed chunk length, model-constant R)
   const int G = n_heads / n_kv;
   p.R = G % 8 == 0 ? 8 : (G % 4 == 0 ? 4 : (G % 2 == 0 ? 2 : 1));
+  if (e->opt.llama_dec_r == 1) p.R = 1;
+  if (e->opt.llama_dec_r == 2 && G == 7) p.R = 7;
   p.nch = (P + LDC_CHUNK - 1) / LDC_CHUNK;
   p.grid = dim3(p.nch, n_heads / p.R, rows);
   p.cgrid = dim3(n_heads, rows);
@@ -1031,10 +1038,19 @@ LlamaDecAttnPlan plan_llama_dec_attn(const rk_engine* e, int rows, int P, int n_
 void launch_llama_dec_attn(rk_engine* e, hipStream_t st, const LlamaDecAttnPlan& p, AttnDecCached128Args a, int rows) {
   a.nch = p.nch;
   Bracket br(e, st, PC_DEC_ATTN, 4.0 * rows * (double)a.P * a.n_heads * 128, 2.0 * rows * (double)a.P * a.n_kv * 128 * 2.0);
-  if (p.R == 8) hipLaunchKernelGGL(attn_dec_cached128_kernel<8>, p.grid, dim3(256), 0, st, a);
-  else if (p.R == 4) hipLaunchKernelGGL(attn_dec_cached128_kernel<4>, p.grid, dim3(256), 0, st, a);
-  else if (p.R == 2) hipLaunchKernelGGL(attn_dec_cached128_kernel<2>, p.grid, dim3(256), 0, st, a);
-  else hipLaunchKernelGGL(attn_dec_cached128_kernel<1>, p.grid, dim3(256), 0, st, a);
+  auto go = [&](auto rc) {                                   // the bias-free instantiation is the Llama kernel as it was
+    constexpr int R = decltype(rc)::value;
+    if (a.bias) hipLaunchKernelGGL(attn_dec_cached128_bias_kernel<R>, p.grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(attn_dec_cached128_kernel<R>, p.grid, dim3(256), 0, st, a);
+  };
+  using std::integral_constant;
+  switch (p.R) {
+    case 8: go(integral_constant<int, 8>{}); break;
+    case 7: go(integral_constant<int, 7>{}); break;
+    case 4: go(integral_constant<int, 4>{}); break;
+    case 2: go(integral_constant<int, 2>{}); break;
+    default: go(integral_constant<int, 1>{}); break;
+  }
   hipLaunchKernelGGL(attn_dec_combine128_kernel, p.cgrid, dim3(128), 0, st, a);
 }
 
@@ -2290,6 +2306,7 @@ static int llama_finalize(rk_engine* e) {
     N2(p + ".self_attn.o_proj.weight", dm, Q);
     N2(p + ".mlp.gate_proj.weight", F, dm); N2(p + ".mlp.up_proj.weight", F, dm); N2(p + ".mlp.down_proj.weight", dm, F);
     N1(p + ".input_layernorm.weight", dm); N1(p + ".post_attention_layernorm.weight", dm);
+    if (e->qkv_bias) { N1(p + ".self_attn.q_proj.bias", Q); N1(p + ".self_attn.k_proj.bias", KV); N1(p + ".self_attn.v_proj.bias", KV); }
   }
   if (!missing.empty()) return fail(e, RK_ERR_MISSING, "missing or mis-shaped tensors: %s", missing.c_str());
   auto H = [&](const std::string& n) -> const std::vector<half_t>& { return e->host[n].h; };
@@ -2315,6 +2332,14 @@ static int llama_finalize(rk_engine* e) {
         r0 += rows;
       }
       RC(upload(e, &w.qkv_f, buf.data(), buf.size()));
+    }
+    if (e->qkv_bias) {   // q | k | v bias, fp32, as it is: it is added AFTER the folded norm's row factor, so no norm weight enters
+      std::vector<float> bias;
+      for (const char* m : {"q_proj", "k_proj", "v_proj"}) {
+        const auto& src = Fv(p + ".self_attn." + m + ".bias");
+        bias.insert(bias.end(), src.begin(), src.end());
+      }
+      RC(upload(e, &w.qkv_bias, bias.data(), bias.size()));
     }
     RC(upload(e, &w.o, H(p + ".self_attn.o_proj.weight").data(), (size_t)dm * Q));
     {   // gate | up interleaved in groups of 32 rows (the SwiGLU epilogue pairs them in one lane), post-attention norm folded
@@ -2397,7 +2422,12 @@ static int llama_prefill(rk_engine* e, const int32_t* tokens, const int32_t* off
     RC(gemm(e, st, ns.consumer(e, st, nullptr, Gemm(PC_ENC_GEMM_QKV, EPI_STORE_F16, ns.x(), dm, w.qkv_f, dm, sl.qkv, ldq, T, ldq, dm), false)));
     {
       Bracket br(e, st, PC_OTHER, 0, (double)T * (Q + KV) * 4.0);
-      hipLaunchKernelGGL(rope128_kernel, dim3(T), dim3(256), 0, st, sl.qkv, e->d_pos, e->rope_cos, e->rope_sin, ldq, l.n_heads + l.n_kv_heads);
+      if (w.qkv_bias)
+        hipLaunchKernelGGL(rope128_kernel<true>, dim3(T), dim3(256), 0, st, sl.qkv, e->d_pos, e->rope_cos, e->rope_sin, ldq, l.n_heads + l.n_kv_heads,
+                           w.qkv_bias, l.n_kv_heads);
+      else
+        hipLaunchKernelGGL(rope128_kernel<false>, dim3(T), dim3(256), 0, st, sl.qkv, e->d_pos, e->rope_cos, e->rope_sin, ldq, l.n_heads + l.n_kv_heads,
+                           (const float*)nullptr, 0);
     }
     if (keep) {
       const size_t half_layer = (size_t)n_seq * l.n_kv_heads * keep->P * 128;
@@ -2438,6 +2468,14 @@ int rk_llama_set_rope_scaling(rk_engine* e, float factor, float low_freq_factor,
   if (!(factor > 0.f) || !(high_freq_factor > low_freq_factor) || !(low_freq_factor > 0.f) || original_max_pos <= 0)
     return fail(e, RK_ERR_INVALID, "bad llama3 rope scaling (factor %g, low %g, high %g, original_max_position_embeddings %d)", factor, low_freq_factor, high_freq_factor, original_max_pos);
   e->rope_factor = factor; e->rope_low = low_freq_factor; e->rope_high = high_freq_factor; e->rope_orig = original_max_pos;
+  return RK_OK;
+}
+
+int rk_llama_set_qkv_bias(rk_engine* e, int on) {
+  if (!e) return RK_ERR_INVALID;
+  if (e->family != 1) return fail(e, RK_ERR_STATE, "q / k / v projection biases apply to Llama-family engines (rk_llama_create)");
+  if (e->finalized) return fail(e, RK_ERR_STATE, "rk_llama_set_qkv_bias must precede rk_engine_finalize (the bias vectors are uploaded there)");
+  e->qkv_bias = on != 0;
   return RK_OK;
 }
 
@@ -2538,7 +2576,7 @@ int rk_llama_generate(rk_engine* e, const int32_t* tokens, const int32_t* seq_of
       RC(gemm(e, st, normed(Gemm(PC_DEC_GEMM, EPI_STORE_F16, ns.x(), dm, w.qkv_f, dm, lg.qkv, ldq, n_seq, ldq, dm))));
       half_t* kc = e->lkv.p + (size_t)i * 2 * half_layer;
       launch_llama_dec_attn(e, st, ap, AttnDecCached128Args{lg.qkv, kc, kc + half_layer, d_pos, e->rope_cos, e->rope_sin, e->lpart.p, lg.ctx,
-                                                            ldq, l.n_heads, l.n_kv_heads, P, ap.nch, scale_log2e}, n_seq);
+                                                            ldq, l.n_heads, l.n_kv_heads, P, ap.nch, scale_log2e, w.qkv_bias}, n_seq);
       RC(ns.producer(e, st, Gemm(PC_DEC_GEMM, EPI_RESID_F32, lg.ctx, Q, w.o, Q, ns.hidden, dm, n_seq, dm, Q).on(GEMM_STREAM)));
       RC(gemm(e, st, normed(Gemm(PC_DEC_GEMM, EPI_SWIGLU_F16, ns.x(), dm, w.gu_f, dm, lg.ffh, F, n_seq, 2 * F, dm))));
       RC(ns.producer(e, st, Gemm(PC_DEC_GEMM, EPI_RESID_F32, lg.ffh, F, w.down, F, ns.hidden, dm, n_seq, dm, F).on(GEMM_STREAM), i + 1 < l.n_layers));
@@ -2800,6 +2838,7 @@ const OptionDesc kOptions[] = {
   {"dec_attn_seq", &rk_engine::Options::dec_attn_seq, 0, 1, nullptr, "decoder attention at several positions: one workgroup per (head, sequence) (1) or per query row (0); same bits"},
   {"gemm_sk", &rk_engine::Options::gemm_sk, 0, 2, nullptr, "ping-pong GEMM, fp32 residual projections with few tiles and a long K: K split over two workgroups (1: choose_ksplit), never (0), wherever it fits (2: tests)"},
   {"dec_cached_attn", &rk_engine::Options::dec_cached_attn, 0, 1, nullptr, "rk_t5_generate's self-attention: attn_dec_cached_kernel (1) or the cache append + attn_dec_kernel's tree form (0); same bits"},
+  {"llama_dec_r", &rk_engine::Options::llama_dec_r, 0, 2, nullptr, "rk_llama_generate's attention: query heads per workgroup by plan_llama_dec_attn's rule (0), one (1), or, where a kv head has 7, all seven (2: measurement and tests; every cached K / V byte read once per step); same bits"},
   {"gemm_split", &rk_engine::Options::gemm_split, 0, 1, nullptr, "rows beyond the ping-pong kernel's last whole round on a fill-in tile variant (1) or one launch (0); same bits"},
 #ifdef RK_MEASURE
   {"attn_ko", &rk_engine::Options::attn_ko, 0, 1 << 20, nullptr, "timing-only knock-outs of the attention kernels (measurement builds)"},

@@ -101,6 +101,82 @@ def iter_checkpoint_tensors(model_dir: str) -> Iterator[Tuple[str, np.ndarray]]:
                         yield k, t.float().numpy()
 
 
+LORA_PROJECTIONS = _synth.LORA_TARGETS      # the seven plain projections of a decoder layer
+
+
+def _read_adapter_tensors(adapter_dir: str) -> dict:
+    st = os.path.join(adapter_dir, "adapter_model.safetensors")
+    if os.path.exists(st):
+        from safetensors import safe_open
+        import torch
+        out = {}
+        with safe_open(st, framework="pt") as f:            # (through torch: adapters are often bf16, which numpy lacks)
+            for k in f.keys():
+                out[k] = f.get_tensor(k).float().numpy()
+        return out
+    pt = os.path.join(adapter_dir, "adapter_model.bin")
+    if os.path.exists(pt):
+        import torch
+        return {k: t.float().numpy() for k, t in torch.load(pt, map_location="cpu", weights_only=True).items()}
+    raise FileNotFoundError(f"no adapter_model.safetensors or adapter_model.bin in {adapter_dir}")
+
+
+def merge_lora(tensors, adapter_dir: str) -> Iterator[Tuple[str, np.ndarray]]:
+    """Wrap iter_checkpoint_tensors: every weight a PEFT LoRA adapter targets is yielded in fp32 as W + scale * B @ A (scale =
+    lora_alpha / r, with use_rslora lora_alpha / sqrt(r)), everything else untouched.  The merge happens once, on the host, before
+    rk_engine_load_tensor rounds to fp16 - the reference serves the adapter unmerged in half precision through vLLM (ref:
+    llmrankers/setwise.py:450-454, 491-498): a documented deviation ("Qwen2 family and Rank-R1").  Adapter keys are
+    base_model.model.<hf name minus .weight>.lora_A.weight [r, in] and .lora_B.weight [out, r]; a key that matches no
+    checkpoint tensor is an error, and so is anything but plain LoRA on the seven projections the engine holds."""
+    with open(os.path.join(adapter_dir, "adapter_config.json")) as f:
+        ac = json.load(f)
+    if ac.get("peft_type", "LORA") != "LORA":
+        raise NotImplementedError(f"adapter type {ac.get('peft_type')!r} is not supported by the MI355X engine (LoRA is)")
+    if ac.get("use_dora"):
+        raise NotImplementedError("DoRA adapters (use_dora) are not supported by the MI355X engine")
+    if ac.get("bias", "none") != "none":
+        raise NotImplementedError(f"LoRA adapters that train biases (bias={ac['bias']!r}) are not supported by the MI355X engine")
+    if ac.get("modules_to_save"):
+        raise NotImplementedError(f"LoRA adapters with modules_to_save ({ac['modules_to_save']}) are not supported by the MI355X engine")
+    targets = ac.get("target_modules")
+    if not isinstance(targets, (list, tuple)):
+        raise NotImplementedError(f"target_modules must be a list of module names (got {targets!r})")
+    bad = [m for m in targets if m.split(".")[-1] not in LORA_PROJECTIONS]
+    if bad:
+        raise NotImplementedError(f"LoRA on {bad} is not supported: the MI355X engine holds {LORA_PROJECTIONS} as plain projections")
+    r, alpha = int(ac["r"]), float(ac["lora_alpha"])
+    if ac.get("rank_pattern") or ac.get("alpha_pattern"):
+        raise NotImplementedError("per-module LoRA ranks / alphas (rank_pattern, alpha_pattern) are not supported by the MI355X engine")
+    scale = alpha / np.sqrt(r) if ac.get("use_rslora") else alpha / r
+    pairs = {}
+    for k, v in _read_adapter_tensors(adapter_dir).items():
+        for tag in (".lora_A.weight", ".lora_B.weight"):
+            if k.endswith(tag) and k.startswith("base_model.model."):
+                name = k[len("base_model.model."):-len(tag)]
+                if name.split(".")[-1] not in LORA_PROJECTIONS:
+                    raise NotImplementedError(f"adapter tensor {k}: not one of the projections the MI355X engine holds")
+                pairs.setdefault(name + ".weight", {})[tag[6]] = np.asarray(v, dtype=np.float32)
+                break
+        else:
+            raise NotImplementedError(f"adapter tensor {k} is not a plain LoRA A / B matrix")
+    for name, arr in tensors:
+        ab = pairs.pop(name, None)
+        if ab is None:
+            yield name, arr
+            continue
+        if set(ab) != {"A", "B"}:
+            raise ValueError(f"adapter for {name}: lora_A / lora_B incomplete")
+        if arr.dtype == np.uint16:                              # raw bf16 bits (iter_checkpoint_tensors)
+            arr = (arr.astype(np.uint32) << 16).view(np.float32)
+        w = np.asarray(arr, dtype=np.float32)
+        a, b = ab["A"], ab["B"]
+        if a.shape != (r, w.shape[1]) or b.shape != (w.shape[0], r):
+            raise ValueError(f"adapter for {name}: A {a.shape} / B {b.shape} do not fit the weight {w.shape} at rank {r}")
+        yield name, (w + np.float32(scale) * (b @ a)).astype(np.float32)
+    if pairs:
+        raise KeyError(f"adapter tensors match no checkpoint tensor: {sorted(pairs)[:4]}{' ...' if len(pairs) > 4 else ''}")
+
+
 def _iter_torch_bin(model_dir: str) -> Iterator[Tuple[str, np.ndarray]]:
     """pytorch_model.bin checkpoints (e.g. castorini/monot5-*): read with torch.load — loader plumbing only."""
     import torch
@@ -400,24 +476,33 @@ class LlamaRuntime:
     """Decoder-only (Llama family) counterpart of T5Runtime: checkpoint directory -> rk_llama_* engine.  Replaces
     `AutoModelForCausalLM.from_pretrained(..., device_map='auto', torch_dtype=fp16)` of ref: llmrankers/setwise.py:65-69."""
 
-    def __init__(self, model_name_or_path: str, device, max_tokens: int = 32768, max_seqs: int = 16, cache_dir=None):
+    def __init__(self, model_name_or_path: str, device, max_tokens: int = 32768, max_seqs: int = 16, cache_dir=None,
+                 accept_model_types=("llama",), adapter_dir=None):
+        """accept_model_types: the config.model_type values the caller serves - the reference's setwise / pairwise / listwise
+        rankers refuse Qwen (ref: setwise.py:71), its Rank-R1 ranker runs on it.  adapter_dir: a PEFT LoRA adapter merged into
+        the weights on the way in (merge_lora)."""
         model_name_or_path = resolve_checkpoint(model_name_or_path, cache_dir)
         cfg = read_config(model_name_or_path)
         self.model_type = cfg.get("model_type")
-        if self.model_type != "llama":
+        if self.model_type not in accept_model_types:
             raise NotImplementedError(f"Model type {self.model_type} is not supported yet by the MI355X engine")
         self.config = cfg
         self.dims = _synth.LlamaDims.from_hf_config(cfg)
         self.max_tokens, self.max_seqs = max_tokens, max_seqs
         self.generation = read_generation_settings(model_name_or_path, cfg)
+        if self.dims.head_dim != 128 or self.dims.hidden > 4096:
+            raise NotImplementedError(f"head_dim {self.dims.head_dim} / hidden {self.dims.hidden}: the MI355X engine serves head_dim 128 and "
+                                      "hidden <= 4096 (Llama-2/3 up to 8B, Qwen2.5-1.5B / 3B / 7B)")
         self.engine = RkLlamaEngine(self.dims, parse_device(device), max_tokens, max_seqs)
-        self.engine.load_state(iter_checkpoint_tensors(model_name_or_path))
+        tensors = iter_checkpoint_tensors(model_name_or_path)
+        self.engine.load_state(merge_lora(tensors, adapter_dir) if adapter_dir else tensors)
 
     @classmethod
     def from_engine(cls, engine: RkLlamaEngine, dims=None) -> "LlamaRuntime":
         self = cls.__new__(cls)
         self.dims = dims if dims is not None else engine.dims
-        self.config, self.model_type = self.dims.to_hf_config(), "llama"
+        self.config = self.dims.to_hf_config()
+        self.model_type = self.config["model_type"]
         self.generation = read_generation_settings(None, self.config)
         self.max_tokens, self.max_seqs = int(engine.desc.max_tokens), int(engine.desc.max_seqs)
         self.engine = engine

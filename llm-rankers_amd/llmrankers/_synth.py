@@ -114,8 +114,23 @@ class LlamaDims:
     # rope_type "llama3" (Llama-3.1 / 3.2 checkpoints; hf: modeling_rope_utils.py _compute_llama3_parameters):
     # (factor, low_freq_factor, high_freq_factor, original_max_position_embeddings), None = default rope type
     rope_scaling: Optional[Tuple[float, float, float, int]] = None
+    # Qwen2 family (hf: models/qwen2/modeling_qwen2.py): the same decoder with a bias on the q / k / v projections (not on o_proj)
+    qkv_bias: bool = False
 
     def to_hf_config(self) -> dict:
+        if self.qkv_bias:
+            if self.rope_scaling is not None:
+                raise NotImplementedError("rope scaling on a Qwen2 configuration is not supported by the MI355X engine")
+            return {
+                "architectures": ["Qwen2ForCausalLM"], "model_type": "qwen2", "vocab_size": self.vocab,
+                "hidden_size": self.hidden, "intermediate_size": self.intermediate, "num_hidden_layers": self.n_layers,
+                "num_attention_heads": self.n_heads, "num_key_value_heads": self.n_kv_heads, "head_dim": self.head_dim,
+                "hidden_act": "silu", "rms_norm_eps": self.eps, "rope_theta": self.rope_theta, "rope_scaling": None,
+                "max_position_embeddings": 32768, "use_sliding_window": False, "sliding_window": None,
+                "max_window_layers": self.n_layers, "attention_dropout": 0.0,
+                "tie_word_embeddings": bool(self.tied_head), "bos_token_id": self.bos_token_id, "eos_token_id": self.eos_token_id,
+                "use_cache": True,
+            }
         scaling = None
         if self.rope_scaling is not None:
             f, lo, hi, orig = self.rope_scaling
@@ -133,8 +148,12 @@ class LlamaDims:
 
     @staticmethod
     def from_hf_config(cfg: dict) -> "LlamaDims":
+        # (a Llama config's attention_bias also puts a bias on o_proj: refused; Qwen2's q / k / v biases are its architecture)
         if cfg.get("hidden_act", "silu") != "silu" or cfg.get("attention_bias") or cfg.get("mlp_bias"):
             raise NotImplementedError("only bias-free SwiGLU Llama configurations are supported by the MI355X engine")
+        qwen2 = cfg.get("model_type") == "qwen2"
+        if qwen2 and cfg.get("use_sliding_window"):
+            raise NotImplementedError("Qwen2 configurations with use_sliding_window are not supported by the MI355X engine")
         rope = cfg.get("rope_parameters") or {}
         scaling = cfg.get("rope_scaling") or ({k: v for k, v in rope.items() if k != "rope_theta"} if rope.get("rope_type", "default") != "default" else None)
         rs = None
@@ -152,17 +171,26 @@ class LlamaDims:
                          rope_theta=float(cfg.get("rope_theta") or rope.get("rope_theta") or 10000.0),
                          eps=cfg.get("rms_norm_eps", 1e-6), tied_head=bool(cfg.get("tie_word_embeddings", False)),
                          bos_token_id=cfg.get("bos_token_id", 1) or 1, eos_token_id=eos[0] if isinstance(eos, list) else eos,
-                         rope_scaling=rs)
+                         rope_scaling=rs, qkv_bias=qwen2)
 
 
 LLAMA_3_8B = LlamaDims(vocab=128256, hidden=4096, n_heads=32, n_kv_heads=8, head_dim=128, intermediate=14336, n_layers=32,
                        bos_token_id=128000, eos_token_id=128001)
+# Qwen2.5-7B-Instruct (the base of the Rank-R1 7B rerankers): 28 query heads on 4 kv heads; timing tools only
+QWEN25_7B = LlamaDims(vocab=152064, hidden=3584, n_heads=28, n_kv_heads=4, head_dim=128, intermediate=18944, n_layers=28,
+                      rope_theta=1000000.0, eps=1e-6, bos_token_id=151643, eos_token_id=151645, qkv_bias=True)
 # toy: kernel-friendly (head_dim 128 like every Llama-3), grouped-query (4 q heads on 2 kv heads), q width != hidden
 TOY_LLAMA = LlamaDims(vocab=256, hidden=256, n_heads=4, n_kv_heads=2, head_dim=128, intermediate=512, n_layers=2)
 # the same with Llama-3.1's rope type; a short original context and a small base so that most of the 64 frequencies fall in
 # the scaled and the interpolated bands at toy sequence lengths
 TOY_LLAMA3ROPE = LlamaDims(vocab=256, hidden=256, n_heads=4, n_kv_heads=2, head_dim=128, intermediate=512, n_layers=2,
                            rope_theta=10000.0, rope_scaling=(8.0, 1.0, 4.0, 32))
+
+
+# toy Qwen2: 7 query heads on ONE kv head (Qwen2.5-7B's group size: the decode attention takes all 7 in one pass over the cache),
+# tied head, q / k / v biases; ids 1 / 2 are tests/golden/tok_qwen's <|im_start|> / <|im_end|>
+TOY_QWEN2 = LlamaDims(vocab=512, hidden=256, n_heads=7, n_kv_heads=1, head_dim=128, intermediate=512, n_layers=2,
+                      rope_theta=1000000.0, eps=1e-6, tied_head=True, qkv_bias=True)
 
 
 def llama_tensor_specs(d: "LlamaDims") -> Iterator[Tuple[str, Tuple[int, ...], float, bool]]:
@@ -174,6 +202,10 @@ def llama_tensor_specs(d: "LlamaDims") -> Iterator[Tuple[str, Tuple[int, ...], f
         yield f"{p}.self_attn.k_proj.weight", (d.n_kv_heads * d.head_dim, d.hidden), d.hidden ** -0.5, False
         yield f"{p}.self_attn.v_proj.weight", (d.n_kv_heads * d.head_dim, d.hidden), d.hidden ** -0.5, False
         yield f"{p}.self_attn.o_proj.weight", (d.hidden, d.n_heads * d.head_dim), (d.n_heads * d.head_dim) ** -0.5, False
+        if d.qkv_bias:                                # (after the weights: the streams of a bias-free checkpoint do not move)
+            yield f"{p}.self_attn.q_proj.bias", (d.n_heads * d.head_dim,), 0.5, False
+            yield f"{p}.self_attn.k_proj.bias", (d.n_kv_heads * d.head_dim,), 0.5, False
+            yield f"{p}.self_attn.v_proj.bias", (d.n_kv_heads * d.head_dim,), 0.5, False
         yield f"{p}.input_layernorm.weight", (d.hidden,), 0.1, True
         yield f"{p}.mlp.gate_proj.weight", (d.intermediate, d.hidden), d.hidden ** -0.5, False
         yield f"{p}.mlp.up_proj.weight", (d.intermediate, d.hidden), d.hidden ** -0.5, False
@@ -188,6 +220,7 @@ NAMED_DIMS = {
     "flan-t5-small": FLAN_T5_SMALL, "flan-t5-base": FLAN_T5_BASE, "flan-t5-large": FLAN_T5_LARGE,
     "flan-t5-xl": FLAN_T5_XL, "toy-gated-untied": TOY_GATED_UNTIED, "toy-relu-tied": TOY_RELU_TIED, "toy-monot5": TOY_MONOT5,
     "llama-3-8b": LLAMA_3_8B, "toy-llama": TOY_LLAMA, "toy-llama3rope": TOY_LLAMA3ROPE,
+    "qwen2.5-7b": QWEN25_7B, "toy-qwen2": TOY_QWEN2,
 }
 
 _M64 = np.uint64(0xFFFFFFFFFFFFFFFF)
@@ -395,6 +428,47 @@ def checkpoint_sha256(path: str) -> str:
     import os
     from safetensors.numpy import load_file
     sd = load_file(os.path.join(path, "model.safetensors"))
+    h = hashlib.sha256()
+    for k in sorted(sd):
+        h.update(k.encode())
+        h.update(np.ascontiguousarray(sd[k]).tobytes())
+    return h.hexdigest()
+
+
+LORA_TARGETS = ("q_proj", "k_proj", "v_proj", "o_proj", "gate_proj", "up_proj", "down_proj")
+
+
+def synth_lora_tensors(d: "LlamaDims", spec: dict) -> Dict[str, np.ndarray]:
+    """A PEFT-layout LoRA adapter from a recipe {seed, r, std[, targets]}: lora_A [r, in] and lora_B [out, r] of every targeted
+    projection of every layer, N(0, std) entries from the counter generator (streams 100000 +), fp16-representable."""
+    out, stream = {}, 100000
+    targets = tuple(spec.get("targets", LORA_TARGETS))
+    for name, shape, _, _ in llama_tensor_specs(d):
+        mod = name.split(".")[-2]
+        if not name.endswith(".weight") or mod not in targets or mod not in LORA_TARGETS:
+            continue
+        base = "base_model.model." + name[:-len(".weight")]
+        for tag, shp in (("lora_A", (spec["r"], shape[1])), ("lora_B", (shape[0], spec["r"]))):
+            z = counter_normal(int(np.prod(shp)), stream, spec["seed"])
+            out[f"{base}.{tag}.weight"] = _fp16_round((spec["std"] * z).astype(np.float32).reshape(shp))
+            stream += 1
+    return out
+
+
+def write_lora_adapter(path: str, d: "LlamaDims", spec: dict) -> str:
+    """Materialise the adapter directory (adapter_config.json + adapter_model.safetensors) of a recipe {seed, r, lora_alpha, std[,
+    targets, use_rslora]} -> sha256 over names and bytes."""
+    import hashlib
+    import json
+    import os
+    from safetensors.numpy import save_file
+    os.makedirs(path, exist_ok=True)
+    sd = synth_lora_tensors(d, spec)
+    save_file({k: np.ascontiguousarray(v) for k, v in sd.items()}, os.path.join(path, "adapter_model.safetensors"))
+    with open(os.path.join(path, "adapter_config.json"), "w") as f:
+        json.dump({"peft_type": "LORA", "task_type": "CAUSAL_LM", "r": spec["r"], "lora_alpha": spec["lora_alpha"],
+                   "use_rslora": bool(spec.get("use_rslora", False)), "use_dora": False, "bias": "none", "modules_to_save": None,
+                   "lora_dropout": 0.0, "target_modules": list(spec.get("targets", LORA_TARGETS))}, f, indent=1)
     h = hashlib.sha256()
     for k in sorted(sd):
         h.update(k.encode())

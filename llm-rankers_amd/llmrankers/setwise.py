@@ -568,3 +568,163 @@ class SetwiseLlmRanker(LlmRanker):
 
     def truncate(self, text, length):
         return self.tokenizer.convert_tokens_to_string(self.tokenizer.tokenize(text)[:length])
+
+
+def load_prompt_file(prompt_file):
+    """The Rank-R1 prompt settings (prompt_system, prompt_user, pattern): a mapping as it is, or a TOML file (ref:
+    llmrankers/setwise.py:426-427 reads it with `toml`) through whichever TOML reader is installed."""
+    if isinstance(prompt_file, dict) or hasattr(prompt_file, "keys"):
+        prompt = dict(prompt_file)
+    else:
+        reader = None
+        for name in ("tomllib", "tomli", "toml"):
+            try:
+                reader = __import__(name)
+                break
+            except ImportError:
+                continue
+        if reader is None:
+            raise ImportError("reading a Rank-R1 prompt file needs a TOML reader (Python >= 3.11's tomllib, or the tomli or toml "
+                              "package); alternatively pass the parsed mapping as prompt_file")
+        if reader.__name__ == "toml":
+            prompt = dict(reader.load(prompt_file))
+        else:
+            with open(prompt_file, "rb") as f:
+                prompt = dict(reader.load(f))
+    missing = [k for k in ("prompt_system", "prompt_user", "pattern") if k not in prompt]
+    if missing:
+        raise KeyError(f"prompt file lacks {missing}")
+    return prompt
+
+
+class RankR1SetwiseLlmRanker(SetwiseLlmRanker):
+    """Rank-R1, the reasoning setwise reranker (ref: llmrankers/setwise.py:406-553; Qwen2.5-Instruct + a LoRA adapter served by
+    vLLM there): one compare = a chat prompt listing the passages as "[n] text", a generated chain of thought of up to
+    max_new_tokens tokens, and a regular expression that takes the answer's "[n]" label out of it.  Here the checkpoint (the
+    adapter merged on the host, _runtime.merge_lora) runs on the engine's KV-cached greedy decoder (rk_llama_generate).  Same
+    constructor, compare() contract, counters, vote and sort drivers as the reference; stand-ins for vLLM ("Qwen2 family and Rank-R1"):
+    the stop ids are the checkpoint's generation settings, the EOS that ended a row counts as a completion token, the completion
+    text is the new tokens decoded without special tokens."""
+    CHARACTERS = [f'[{i + 1}]' for i in range(20)]
+
+    def __init__(self, model_name_or_path, prompt_file, lora_name_or_path=None, tokenizer_name_or_path=None, num_child=19, k=10,
+                 scoring='generation', method="heapsort", num_permutation=1, cache_dir=None, verbose=False, device="cuda",
+                 max_new_tokens=2048):
+        if scoring != 'generation':
+            raise NotImplementedError(f"Scoring method {scoring} is not supported for RankR1SetwiseLlmRanker. RankR1SetwiseLlmRanker only supports 'generation' scoring.")
+        from transformers import AutoTokenizer
+        from ._runtime import LlamaRuntime, resolve_checkpoint
+        prompt = load_prompt_file(prompt_file)
+        lora_path = resolve_checkpoint(lora_name_or_path, cache_dir) if lora_name_or_path is not None else None
+        tokenizer = AutoTokenizer.from_pretrained(tokenizer_name_or_path if tokenizer_name_or_path is not None else model_name_or_path,
+                                                  cache_dir=cache_dir)
+        runtime = LlamaRuntime(model_name_or_path, device, cache_dir=cache_dir, accept_model_types=("qwen2", "llama"),
+                               adapter_dir=lora_path)
+        self._setup_r1(runtime, tokenizer, prompt, lora_path, device, num_child, k, method, num_permutation, verbose, max_new_tokens)
+
+    @classmethod
+    def from_runtime(cls, runtime, tokenizer, prompt_file, device="cuda", num_child=19, k=10, scoring='generation', method="heapsort",
+                     num_permutation=1, verbose=False, max_new_tokens=2048):
+        """Build the ranker around an existing runtime (a loaded engine - adapter already merged - or a test double)."""
+        if scoring != 'generation':
+            raise NotImplementedError(f"Scoring method {scoring} is not supported for RankR1SetwiseLlmRanker. RankR1SetwiseLlmRanker only supports 'generation' scoring.")
+        self = cls.__new__(cls)
+        self._setup_r1(runtime, tokenizer, load_prompt_file(prompt_file), None, device, num_child, k, method, num_permutation, verbose,
+                       max_new_tokens)
+        return self
+
+    def _setup_r1(self, runtime, tokenizer, prompt, lora_path, device, num_child, k, method, num_permutation, verbose, max_new_tokens):
+        self.verbose = verbose
+        self.prompt = prompt
+        self.lora_path = lora_path
+        self.device = device
+        self.num_child = num_child
+        self.num_permutation = num_permutation
+        self.k = k
+        self.max_new_tokens = int(max_new_tokens)          # the reference's SamplingParams(temperature=0.0, max_tokens=2048)
+        self.tokenizer = tokenizer
+        self.llm = runtime
+        self.config = getattr(runtime, "config", None)
+        self.model_type = getattr(runtime, "model_type", "qwen2")
+        self.scoring = 'generation'
+        self.method = method
+        self.batch_independent_compares = False           # compare() draws from `random`: the one-by-one order is the contract
+        self.total_compare = 0
+        self.total_completion_tokens = 0
+        self.total_prompt_tokens = 0
+
+    def compare(self, query: str, docs: List):
+        # ref: setwise.py:462-553
+        import re
+        self.total_compare += 1 if self.num_permutation == 1 else self.num_permutation
+        id_passage = [(i, p) for i, p in enumerate(docs)]
+        labels = [self.CHARACTERS[i] for i in range(len(docs))]
+        batch_ref, input_text = [], []
+        for _ in range(self.num_permutation):               # one draw per permutation (also for a single one); labels stay in order
+            shuffled = random.sample(id_passage, len(id_passage))
+            batch_ref.append(([p[0] for p in shuffled], list(labels)))
+            passages = "\n".join(f'{c} {p[1].text}' for p, c in zip(shuffled, labels))
+            input_text.append([{'role': "system", 'content': self.prompt["prompt_system"]},
+                               {'role': "user", 'content': self.prompt['prompt_user'].format(query=query, docs=passages)}])
+        ids = [self._chat_ids(messages) for messages in input_text]
+        gen = self.llm.generation
+        eos_ids = list(gen["eos_token_ids"])
+        rows = np.asarray(self.llm.generate(ids, self.max_new_tokens, eos_ids, int(gen["pad_token_id"])))   # ONE engine call
+        results = []
+        for prompt_ids, row, messages in zip(ids, rows, input_text):
+            new = [int(t) for t in row if t >= 0]
+            stop = next((i for i, t in enumerate(new) if t in eos_ids), None)
+            if stop is not None:                             # vLLM's token_ids keep the EOS that ended the row
+                new = new[:stop + 1]
+            self.total_completion_tokens += len(new)
+            self.total_prompt_tokens += len(prompt_ids)
+            completion = self.tokenizer.decode(new, skip_special_tokens=True)
+            if self.verbose:
+                print('--------------------------------------')
+                print(f'query: {query}')
+                print(f'input_text:\n{self.tokenizer.apply_chat_template(messages, tokenize=False)}')
+                print(f'completion:\n{completion}')
+                print('--------------------------------------')
+            match = re.search(rf'{self.prompt["pattern"]}', completion.lower(), re.DOTALL)
+            results.append(match.group(1).strip() if match else f'input_text:\n{messages}, completion:\n{completion}')
+        candidates = []
+        for (docids, characters), result in zip(batch_ref, results):
+            result = result.strip()
+            if result not in characters:
+                if self.verbose:
+                    print(f"Unexpected output: {result}")
+                continue
+            candidates.append(docids[characters.index(result)])
+        if len(candidates) == 0:
+            if self.verbose:
+                print(f"Unexpected voting: {results}")
+            output = "Unexpected voting."
+        else:
+            counts = Counter(candidates)
+            top = max(counts.values())
+            winners = [c for c, v in counts.items() if v == top]
+            output = self.CHARACTERS[winners[0] if len(winners) == 1 else random.choice(winners)]
+        if output not in self.CHARACTERS and self.verbose:
+            print(f"Unexpected output: {output}")
+        return output
+
+    def _chat_ids(self, messages) -> List[int]:
+        """what vLLM's LLM.chat feeds the model: the chat template with the generation prompt, tokenized"""
+        out = self.tokenizer.apply_chat_template(messages, add_generation_prompt=True, tokenize=True)
+        if hasattr(out, "keys"):                             # transformers >= 5 returns a BatchEncoding
+            out = out["input_ids"]
+        return [int(t) for t in out]
+
+    def rerank_many(self, items):
+        """One rerank per query: the lock-step paths of the parent assume draw-free compares and single-letter labels."""
+        out, counters = [], []
+        for query, ranking in items:
+            out.append(self.rerank(query, ranking))
+            counters.append((self.total_compare, self.total_prompt_tokens, self.total_completion_tokens))
+        return out, counters
+
+    def _compare_many(self, query, doc_lists):
+        return [self.compare(query, docs) for docs in doc_lists]
+
+    def _compare_windows(self, queries, doc_lists):
+        raise NotImplementedError("RankR1SetwiseLlmRanker compares one window at a time")
