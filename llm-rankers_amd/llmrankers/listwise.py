@@ -16,6 +16,7 @@ from typing import List, Optional
 import numpy as np
 
 from ._batching import tokenize_prompts
+from ._lockstep import Lockstep
 from .rankers import LlmRanker, SearchResult
 
 # the "complete" prompt of the reference (ref: listwise.py:85-104) - model input, byte for byte
@@ -243,14 +244,15 @@ class ListwiseLlmRanker(LlmRanker):
 
     # ---- the sliding-window walk ------------------------------------------------------------------------------
     def _walk(self, ranking):
-        """The reference's walk (ref: listwise.py:180-199) as a generator: yields each window, is sent the compare's output, and
-        returns the final ranking.  Windows start at n - window_size and move down by step_size while the start is >= 0."""
+        """The reference's walk (ref: listwise.py:180-199) as a chain of _lockstep: yields each window (a list of one), is sent
+        the compare's output, and returns the final ranking.  Windows start at n - window_size and move down by step_size while
+        the start is >= 0."""
         for _ in range(self.num_repeat):
             ranking = copy.deepcopy(ranking)
             end, start = len(ranking), len(ranking) - self.window_size
             while start >= 0:
                 window = ranking[start:end]
-                output = yield window
+                (output,) = yield [window]
                 ranking[start:end] = [window[k] for k in permutation_order(output, len(window))]
                 end -= self.step_size
                 start -= self.step_size
@@ -262,13 +264,10 @@ class ListwiseLlmRanker(LlmRanker):
         self.total_compare = 0
         self.total_prompt_tokens = 0
         self.total_completion_tokens = 0
-        walk = self._walk(ranking)
-        try:
-            window = next(walk)
-            while True:
-                window = walk.send(self.compare(query, window))
-        except StopIteration as stop:
-            return stop.value
+        walk = Lockstep({0: self._walk(ranking)})
+        while walk:
+            walk.advance([self.compare(query, window) for window in walk.pending()[1]])
+        return walk.returned[0]
 
     def rerank_many(self, items):
         """Several queries at once: `items` = [(query, ranking), ...] -> (results, counters); results[i] and counters[i] =
@@ -276,27 +275,16 @@ class ListwiseLlmRanker(LlmRanker):
         are a dependency chain; the pending windows of all live chains go to the engine as ONE call per step."""
         items = list(items)
         counts = [[0, 0, 0] for _ in items]
-        results = [None] * len(items)
-        walks, pending = {}, {}
-        for q, (_, ranking) in enumerate(items):
-            walks[q] = self._walk(ranking)
-            try:
-                pending[q] = next(walks[q])
-            except StopIteration as stop:
-                results[q] = stop.value
-        while pending:
-            order = sorted(pending)
-            outs, ptok, ctok = self._compare_windows([items[q][0] for q in order], [pending[q] for q in order])
-            nxt = {}
-            for q, out, p, c in zip(order, outs, ptok, ctok):
+        walks = Lockstep({q: self._walk(ranking) for q, (_, ranking) in enumerate(items)})
+        while walks:
+            keys, windows = walks.pending()
+            outs, ptok, ctok = self._compare_windows([items[q][0] for q in keys], windows)
+            for q, p, c in zip(keys, ptok, ctok):
                 counts[q][0] += 1
                 counts[q][1] += p
                 counts[q][2] += c
-                try:
-                    nxt[q] = walks[q].send(out)
-                except StopIteration as stop:
-                    results[q] = stop.value
-            pending = nxt
+            walks.advance(outs)
+        results = [walks.returned[q] for q in range(len(items))]
         counters = [tuple(c) for c in counts]
         if counters:
             self.total_compare, self.total_prompt_tokens, self.total_completion_tokens = counters[-1]

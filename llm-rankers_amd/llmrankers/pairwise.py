@@ -16,7 +16,7 @@ from typing import List
 import numpy as np
 
 from ._batching import batches, padded_token_count, tokenize_prompts
-from .rankers import LlmRanker, SearchResult
+from .rankers import LlmRanker, SearchResult, top_k_then_rest
 
 PROMPT = ('Given a query "{query}", which of the following two passages is more relevant to the query?\n\n'
           'Passage A: "{doc1}"\n\nPassage B: "{doc2}"\n\nOutput Passage A or Passage B:')
@@ -199,16 +199,7 @@ class PairwiseLlmRanker(LlmRanker):
                     cur -= 1
         else:
             raise NotImplementedError(f'Method {self.method} is not implemented.')
-        results, top, rank = [], set(), 1
-        for doc in ranking[:self.k]:
-            top.add(doc.docid)
-            results.append(SearchResult(docid=doc.docid, score=-rank, text=None))
-            rank += 1
-        for docid in original_docids:
-            if docid not in top:
-                results.append(SearchResult(docid=docid, score=-rank, text=None))
-                rank += 1
-        return results
+        return top_k_then_rest(ranking, original_docids, self.k)
 
     def truncate(self, text, length):
         return self.tokenizer.convert_tokens_to_string(self.tokenizer.tokenize(text)[:length])

@@ -15,6 +15,19 @@ class SearchResult:
     text: Optional[str]
 
 
+def top_k_then_rest(ordered, original_docids, k) -> List[SearchResult]:
+    """Result assembly of the sorting rankers (ref: setwise.py:299-313, pairwise.py:281-295): the first k of `ordered` with
+    score -rank, then every other docid in the caller's original order, ranks running on."""
+    results, top = [], set()
+    for doc in ordered[:k]:
+        top.add(doc.docid)
+        results.append(SearchResult(docid=doc.docid, score=-(len(results) + 1), text=None))
+    for docid in original_docids:
+        if docid not in top:
+            results.append(SearchResult(docid=docid, score=-(len(results) + 1), text=None))
+    return results
+
+
 class LlmRanker:
     """Interface every ranker implements: rerank a candidate list for a query; truncate text by tokens."""
 

@@ -14,7 +14,8 @@ from typing import List
 import numpy as np
 
 from ._batching import tokenize_prompts
-from .rankers import LlmRanker, SearchResult
+from ._lockstep import Lockstep
+from .rankers import LlmRanker, SearchResult, top_k_then_rest
 
 random.seed(929)   # same import-time seeding as the reference (ref: setwise.py:18): permutation voting depends on it
 
@@ -30,6 +31,24 @@ VICUNA_TEMPLATE = ("{% if messages[0]['role'] == 'system' %}{% set loop_messages
 
 QUESTION = 'Given a query "{query}", which of the following passages is the most relevant one to the query?\n\n'
 INSTRUCTION = '\n\nOutput only the passage label of the most relevant passage:'
+
+
+def vote(refs, answers, characters, say):
+    """The permutation vote (ref: setwise.py:132-150, 520-548): refs[p] = (docids, labels) of permutation p, answers[p] what
+    the model said to it.  Answers that name no label of their permutation are reported through `say` and dropped; the docid
+    named most often wins, a tie is broken by one `random.choice`; no usable answer at all -> "Unexpected voting."."""
+    candidates = []
+    for (docids, labels), answer in zip(refs, answers):
+        if answer not in labels:
+            say(f"Unexpected output: {answer}")
+            continue
+        candidates.append(docids[labels.index(answer)])
+    if len(candidates) == 0:
+        return "Unexpected voting."
+    counts = Counter(candidates)
+    top = max(counts.values())
+    winners = [c for c, v in counts.items() if v == top]
+    return characters[winners[0] if len(winners) == 1 else random.choice(winners)]
 
 
 class SetwiseLlmRanker(LlmRanker):
@@ -111,75 +130,34 @@ class SetwiseLlmRanker(LlmRanker):
     def compare(self, query: str, docs: List):
         # ref: setwise.py:79-198
         self.total_compare += 1 if self.num_permutation == 1 else self.num_permutation
-        n = len(docs)
-        if self.model_type == "llama":
-            # ref: setwise.py:159-177 — generation only; num_permutation is ignored (it only entered total_compare above)
-            if self.scoring != 'generation':
-                if self.scoring == 'likelihood':
-                    raise NotImplementedError
-                raise UnboundLocalError("local variable 'output' referenced before assignment")
-            ids = self._llama_prompt_ids(self._prompt(query, self.CHARACTERS[:n], [d.text for d in docs]))
-            self.total_prompt_tokens += len(ids)
-            tok = int(self.llm.greedy1([ids])[0])
-            self.total_completion_tokens += len(ids) + 1        # generate() returns prompt + new token for a decoder-only model
-            output = self.tokenizer.decode([tok], skip_special_tokens=True).strip().upper()
-            if not (len(output) == 1 and output in self.CHARACTERS):
-                print(f"Unexpected output: {output}")
-            return output
-        if self.scoring == 'generation':
-            if self.num_permutation == 1:
-                text = self._prompt(query, self.CHARACTERS[:n], [d.text for d in docs])
-                ids = tokenize_prompts(self.tokenizer, [text])
-                self.total_prompt_tokens += len(ids[0])
-                output_ids = self._generate(ids)[0]
-                self.total_completion_tokens += len(output_ids)
-                output = self.tokenizer.decode(output_ids, skip_special_tokens=True).strip()
-                output = output[-1]
-            else:
-                id_passage = [(i, p) for i, p in enumerate(docs)]
-                labels = [self.CHARACTERS[i] for i in range(n)]
-                perms = []
-                for _ in range(self.num_permutation):   # two draws per permutation, in this order (ref :107-109)
-                    perms.append([random.sample(id_passage, len(id_passage)), random.sample(labels, len(labels))])
-                refs, texts = [], []
-                for shuffled, chars in perms:
-                    refs.append(([p[0] for p in shuffled], list(chars)))
-                    texts.append(self._prompt(query, list(chars), [p[1].text for p in shuffled]))
-                ids = tokenize_prompts(self.tokenizer, texts)
-                # return_tensors="pt" without padding requires equal lengths; permuting passages keeps them equal
-                self.total_prompt_tokens += len(ids[0]) * len(ids)
-                rows = self._generate(ids)
-                plen = len(self.decoder_input_ids)
-                decoded = self.tokenizer.batch_decode([r[plen:] for r in rows], skip_special_tokens=True)
-                candidates = []
-                for (docids, chars), result in zip(refs, decoded):
-                    result = result.strip().upper()
-                    if len(result) != 1 or result not in chars:
-                        print(f"Unexpected output: {result}")
-                        continue
-                    candidates.append(docids[chars.index(result)])
-                if len(candidates) == 0:
-                    print(f"Unexpected voting: {decoded}")
-                    output = "Unexpected voting."
-                else:
-                    counts = Counter(candidates)
-                    top = max(counts.values())
-                    winners = [c for c, v in counts.items() if v == top]
-                    output = self.CHARACTERS[winners[0] if len(winners) == 1 else random.choice(winners)]
-        elif self.scoring == 'likelihood':
-            text = self._prompt(query, self.CHARACTERS[:n], [d.text for d in docs])
-            ids = tokenize_prompts(self.tokenizer, [text])
-            self.total_prompt_tokens += len(ids[0])
-            # softmax over the vocabulary is monotone, so the best label is the arg-max of the label logits;
-            # stable descending sort = first maximum wins (ref: setwise.py:184-188)
-            if n == 0:
-                raise IndexError("list index out of range")   # ranked[0] on an empty list in the reference (:188)
-            lg = self.llm.score(ids, self.decoder_input_ids, self.target_token_ids[:n])[0]
-            output = self.CHARACTERS[int(np.argmax(lg))]
-        else:
-            raise UnboundLocalError("local variable 'output' referenced before assignment")  # what the reference does
+        if self.model_type != "llama" and self.scoring == 'generation' and self.num_permutation > 1:
+            return self._compare_permuted(query, docs)
+        # one window of `_compare_windows` (a Llama model ignores num_permutation: it only entered total_compare above)
+        (output,), (ptok,), (ctok,) = self._compare_windows([query], [docs])
+        self.total_prompt_tokens += ptok
+        self.total_completion_tokens += ctok
+        return output
 
-        if not (len(output) == 1 and output in self.CHARACTERS):
+    def _compare_permuted(self, query: str, docs: List):
+        """T5 `generation` with num_permutation > 1 (ref: setwise.py:100-150): every permutation's prompt in one call, then the vote"""
+        id_passage = [(i, p) for i, p in enumerate(docs)]
+        labels = [self.CHARACTERS[i] for i in range(len(docs))]
+        perms = []
+        for _ in range(self.num_permutation):   # two draws per permutation, in this order (ref :107-109)
+            perms.append([random.sample(id_passage, len(id_passage)), random.sample(labels, len(labels))])
+        refs, texts = [], []
+        for shuffled, chars in perms:
+            refs.append(([p[0] for p in shuffled], list(chars)))
+            texts.append(self._prompt(query, list(chars), [p[1].text for p in shuffled]))
+        ids = tokenize_prompts(self.tokenizer, texts)
+        # return_tensors="pt" without padding requires equal lengths; permuting passages keeps them equal
+        self.total_prompt_tokens += len(ids[0]) * len(ids)
+        rows = self._generate(ids)
+        plen = len(self.decoder_input_ids)
+        decoded = self.tokenizer.batch_decode([r[plen:] for r in rows], skip_special_tokens=True)
+        output = vote(refs, [result.strip().upper() for result in decoded], self.CHARACTERS, print)
+        if output not in self.CHARACTERS:
+            print(f"Unexpected voting: {decoded}")
             print(f"Unexpected output: {output}")
         return output
 
@@ -199,40 +177,40 @@ class SetwiseLlmRanker(LlmRanker):
         return outs
 
     def _compare_windows(self, queries: List[str], doc_lists: List[List]):
-        """The engine call behind `_compare_many`, for windows that may belong to different queries (`rerank_many`):
-        -> (labels, prompt tokens per window, completion tokens per window); touches no counter."""
-        assert self.num_permutation == 1
+        """The engine call behind `compare` and `_compare_many`, for windows that may belong to different queries (`rerank_many`):
+        -> (labels, prompt tokens per window, completion tokens per window); touches no counter and draws no random number."""
+        if self.model_type == "llama" and self.scoring == 'likelihood':
+            raise NotImplementedError                           # ref: setwise.py:175-176, before any token is counted
+        if self.scoring not in ('generation', 'likelihood'):
+            raise UnboundLocalError("local variable 'output' referenced before assignment")  # what the reference does
         texts = [self._prompt(q, self.CHARACTERS[:len(docs)], [d.text for d in docs]) for q, docs in zip(queries, doc_lists)]
         if self.model_type == "llama":
-            if self.scoring != 'generation':
-                raise NotImplementedError
+            # ref: setwise.py:159-177 — prefill and one greedy token; generate() returns prompt + new token for a decoder-only model
             ids = [self._llama_prompt_ids(t) for t in texts]
             toks = self.llm.greedy1(ids)
             outs = [self.tokenizer.decode([int(tok)], skip_special_tokens=True).strip().upper() for tok in toks]
-            for output in outs:
-                if not (len(output) == 1 and output in self.CHARACTERS):
-                    print(f"Unexpected output: {output}")
-            return outs, [len(seq) for seq in ids], [len(seq) + 1 for seq in ids]
-        ids = tokenize_prompts(self.tokenizer, texts)
-        prompt_tokens = [len(i) for i in ids]
-        outs, completion_tokens = [], [0] * len(ids)
-        if self.scoring == 'generation':
-            eos = self.tokenizer.eos_token_id
-            for r, row in enumerate(self._generate(ids)):
+            prompt_tokens, completion_tokens = [len(seq) for seq in ids], [len(seq) + 1 for seq in ids]
+        elif self.scoring == 'generation':
+            ids = tokenize_prompts(self.tokenizer, texts)
+            prompt_tokens, completion_tokens = [len(i) for i in ids], []
+            outs, eos = [], self.tokenizer.eos_token_id
+            for row in self._generate(ids):
                 new = row[len(self.decoder_input_ids):]
                 if eos in new:                                  # alone, this row would have stopped at its own EOS
                     new = new[:new.index(eos) + 1]
                 row = list(self.decoder_input_ids) + new
-                completion_tokens[r] = len(row)
+                completion_tokens.append(len(row))
                 outs.append(self.tokenizer.decode(row, skip_special_tokens=True).strip()[-1])
-        elif self.scoring == 'likelihood':
+        else:
+            # softmax over the vocabulary is monotone, so the best label is the arg-max of the label logits;
+            # stable descending sort = first maximum wins (ref: setwise.py:184-188)
             if any(len(docs) == 0 for docs in doc_lists):
-                raise IndexError("list index out of range")
+                raise IndexError("list index out of range")     # ranked[0] on an empty list in the reference (:188)
+            ids = tokenize_prompts(self.tokenizer, texts)
+            prompt_tokens, completion_tokens = [len(i) for i in ids], [0] * len(ids)
             nmax = max(len(docs) for docs in doc_lists)
             lg = np.asarray(self.llm.score(ids, self.decoder_input_ids, self.target_token_ids[:nmax]))
             outs = [self.CHARACTERS[int(np.argmax(lg[r, :len(docs)]))] for r, docs in enumerate(doc_lists)]
-        else:
-            raise UnboundLocalError("local variable 'output' referenced before assignment")
         for output in outs:
             if not (len(output) == 1 and output in self.CHARACTERS):
                 print(f"Unexpected output: {output}")
@@ -270,72 +248,58 @@ class SetwiseLlmRanker(LlmRanker):
         return (getattr(self, "batch_independent_compares", False) and self.num_permutation == 1
                 and "compare" not in self.__dict__ and type(self).compare is SetwiseLlmRanker.compare)
 
-    def _build_heap_batched(self, arr, n, query):
-        """Build phase of the c-ary heapsort with the sift-downs of one tree level advanced together.  The reference
-        walks i = n//c .. 0 (ref: setwise.py:221-223), i.e. level by level from the deepest internal one; nodes of a
-        level root disjoint subtrees, so their sift-down chains touch disjoint array slots and commute: the array,
-        the set of compares and every counter end up identical, only the order of compares inside a level differs."""
-        c = self.num_child
-        levels = {}
-        for i in range(n // c, -1, -1):
-            if c * i + 1 < n:
-                depth, first = 0, 0
-                while i >= first + c ** depth:      # nodes of depth d occupy [first, first + c^d)
-                    first += c ** depth
-                    depth += 1
-                levels.setdefault(depth, []).append(i)
-        for depth in sorted(levels, reverse=True):
-            active = levels[depth]
-            while active:
-                windows = [[i] + list(range(c * i + 1, min(c * (i + 1) + 1, n))) for i in active]
-                outs = self._compare_many(query, [[arr[j] for j in inds] for inds in windows])
-                nxt = []
-                for i, inds, out in zip(active, windows, outs):
-                    best = self._pick(out)
-                    largest = inds[best] if best < len(inds) else i
-                    if largest != i:
-                        arr[i], arr[largest] = arr[largest], arr[i]
-                        if c * largest + 1 < n:
-                            nxt.append(largest)
-                active = nxt
-
-    # ---- sort drivers: pure index logic, must reproduce the reference's comparisons exactly ---------------
+    # ---- the sorts: pure index logic, must reproduce the reference's comparisons exactly -------------------------
+    # Each is a generator that yields a list of windows whose compares are independent of each other and is sent their labels.
     def _pick(self, output: str) -> int:
         try:
             return self.CHARACTERS.index(output)
         except ValueError:
             return 0                              # malformed output -> first document wins (ref :206-209)
 
-    def heapify(self, arr, n, i, query):
-        # ref: setwise.py:200-217, written as a loop instead of tail recursion
+    def _sift(self, arr, n, i):
+        """Sift node i of the c-ary max-heap arr[:n] down (ref: setwise.py:200-217, a loop instead of tail recursion): one
+        window, the parent and its children, per step."""
         c = self.num_child
-        while c * i + 1 < n:
-            hi = min(c * (i + 1) + 1, n)
-            inds = [i] + list(range(c * i + 1, hi))
-            best = self._pick(self.compare(query, [arr[j] for j in inds]))
+        while True:
+            first = c * i + 1                                  # node i's children are first .. first + c - 1
+            if first >= n:
+                return
+            inds = [i] + list(range(first, min(first + c, n)))
+            (label,) = yield [[arr[j] for j in inds]]
+            best = self._pick(label)
             largest = inds[best] if best < len(inds) else i   # label beyond the window keeps the parent (ref :210-213)
             if largest == i:
                 return
             arr[i], arr[largest] = arr[largest], arr[i]
             i = largest
 
-    def heapSort(self, arr, query, k):
-        # ref: setwise.py:219-232
-        n = len(arr)
-        if self._batched_ok():
-            self._build_heap_batched(arr, n, query)
+    def _heapsort_steps(self, arr, k, level_batched):
+        """ref: setwise.py:219-232.  The build phase sifts the nodes n//c .. 0.  Reference order: one after another.  Level
+        order: the reference's walk goes level by level from the deepest one, and the nodes of a level root disjoint subtrees,
+        so their sift-downs touch disjoint array slots and commute - they advance in lock step, one list of windows per step:
+        the array, the set of compares and every counter end up identical, only the order of compares inside a level differs."""
+        c, n = self.num_child, len(arr)
+        if level_batched:
+            levels, first, width = [], 0, 1                   # the nodes of depth d occupy [first, first + c^d)
+            while first <= n // c:
+                levels.append(range(min(first + width - 1, n // c), first - 1, -1))
+                first, width = first + width, width * c
+            for level in reversed(levels):
+                build = Lockstep({j: self._sift(arr, n, i) for j, i in enumerate(level)})
+                while build:
+                    build.advance((yield build.pending()[1]))
         else:
-            for i in range(n // self.num_child, -1, -1):
-                self.heapify(arr, n, i, query)
+            for i in range(n // c, -1, -1):
+                yield from self._sift(arr, n, i)
         ranked = 0
-        for i in range(n - 1, 0, -1):
-            arr[i], arr[0] = arr[0], arr[i]
+        for m in range(n - 1, 0, -1):
+            arr[m], arr[0] = arr[0], arr[m]
             ranked += 1
             if ranked == k:
                 break
-            self.heapify(arr, i, 0, query)
+            yield from self._sift(arr, m, 0)
 
-    def _bubblesort(self, ranking, query):
+    def _bubblesort_steps(self, ranking):
         # ref: setwise.py:243-273 — sliding window of num_child+1 bubbling the best document to position i,
         # with the reference's `last_start` shortcut that skips windows already known to be in order.
         c = self.num_child
@@ -348,7 +312,8 @@ class SetwiseLlmRanker(LlmRanker):
                 if start < i:
                     start = i
                 window = ranking[start:end]
-                best = self._pick(self.compare(query, window))
+                (label,) = yield [window]
+                best = self._pick(label)
                 if best != 0:
                     # no guard here in the reference either: an out-of-window label raises IndexError
                     ranking[start], ranking[start + best] = ranking[start + best], ranking[start]
@@ -363,102 +328,44 @@ class SetwiseLlmRanker(LlmRanker):
                 start -= c
                 end -= c
 
+    def _sort_steps(self, ranking, level_batched):
+        if self.method == "heapsort":
+            return self._heapsort_steps(ranking, self.k, level_batched)
+        if self.method == "bubblesort":
+            return self._bubblesort_steps(ranking)
+        raise NotImplementedError(f'Method {self.method} is not implemented.')
+
+    def _drive(self, query, steps, level_batched):
+        """Run a sort for one query.  Reference order: every window through `compare`, one at a time (looked up on the
+        instance: tests, golden generators and subclasses replace it); level order: every yielded list is one `_compare_many`."""
+        labels = None
+        while True:
+            try:
+                windows = steps.send(labels)
+            except StopIteration:
+                return
+            labels = self._compare_many(query, windows) if level_batched else [self.compare(query, w) for w in windows]
+
+    def heapify(self, arr, n, i, query):
+        # ref: setwise.py:200-217, always one compare at a time
+        self._drive(query, self._sift(arr, n, i), False)
+
+    def heapSort(self, arr, query, k):
+        # ref: setwise.py:219-232
+        level_batched = self._batched_ok()
+        self._drive(query, self._heapsort_steps(arr, k, level_batched), level_batched)
+
     def rerank(self, query: str, ranking: List[SearchResult]) -> List[SearchResult]:
         # ref: setwise.py:234-313.  NB: like the reference, the caller's list is re-ordered in place.
         original_docids = [doc.docid for doc in ranking]     # (the reference deep-copies the whole list: 3 ms for 100 passages; only the docid order is read)
         self.total_compare = 0
         self.total_completion_tokens = 0
         self.total_prompt_tokens = 0
-        if self.method == "heapsort":
-            self.heapSort(ranking, query, self.k)
-            ranking = list(reversed(ranking))
-        elif self.method == "bubblesort":
-            self._bubblesort(ranking, query)
-        else:
-            raise NotImplementedError(f'Method {self.method} is not implemented.')
-        results, top_doc_ids, rank = [], set(), 1
-        for doc in ranking[:self.k]:
-            top_doc_ids.add(doc.docid)
-            results.append(SearchResult(docid=doc.docid, score=-rank, text=None))
-            rank += 1
-        for docid in original_docids:
-            if docid not in top_doc_ids:
-                results.append(SearchResult(docid=docid, score=-rank, text=None))
-                rank += 1
-        return results
+        level_batched = self.method == "heapsort" and self._batched_ok()
+        self._drive(query, self._sort_steps(ranking, level_batched), level_batched)
+        return top_k_then_rest(list(reversed(ranking)) if self.method == "heapsort" else ranking, original_docids, self.k)
 
     # ---- several queries at once ---------------------------------------------------------------------------
-    def _heapsort_steps(self, arr, k):
-        """heapSort(arr, query, k) as a generator: yields lists of windows whose compares are independent of each other
-        (one tree level of the build phase, then one sift-down step at a time) and is sent their labels.  Same array
-        updates, compares and order as `_build_heap_batched` + `heapify` (the shipped single-query path)."""
-        c, n = self.num_child, len(arr)
-        levels = {}
-        for i in range(n // c, -1, -1):
-            if c * i + 1 < n:
-                depth, first = 0, 0
-                while i >= first + c ** depth:
-                    first += c ** depth
-                    depth += 1
-                levels.setdefault(depth, []).append(i)
-        for depth in sorted(levels, reverse=True):
-            active = levels[depth]
-            while active:
-                windows = [[i] + list(range(c * i + 1, min(c * (i + 1) + 1, n))) for i in active]
-                outs = yield [[arr[j] for j in inds] for inds in windows]
-                nxt = []
-                for i, inds, out in zip(active, windows, outs):
-                    best = self._pick(out)
-                    largest = inds[best] if best < len(inds) else i
-                    if largest != i:
-                        arr[i], arr[largest] = arr[largest], arr[i]
-                        if c * largest + 1 < n:
-                            nxt.append(largest)
-                active = nxt
-        ranked = 0
-        for m in range(n - 1, 0, -1):
-            arr[m], arr[0] = arr[0], arr[m]
-            ranked += 1
-            if ranked == k:
-                break
-            i = 0
-            while c * i + 1 < m:
-                inds = [i] + list(range(c * i + 1, min(c * (i + 1) + 1, m)))
-                (out,) = yield [[arr[j] for j in inds]]
-                best = self._pick(out)
-                largest = inds[best] if best < len(inds) else i
-                if largest == i:
-                    break
-                arr[i], arr[largest] = arr[largest], arr[i]
-                i = largest
-
-    def _bubblesort_steps(self, ranking):
-        """`_bubblesort` as a generator (one window per step; same windows, swaps and `last_start` shortcut)."""
-        c = self.num_child
-        full = len(ranking) - (c + 1)
-        last_start = full
-        for i in range(self.k):
-            start, end = last_start, last_start + (c + 1)
-            changed = False
-            while True:
-                if start < i:
-                    start = i
-                window = ranking[start:end]
-                (out,) = yield [window]
-                best = self._pick(out)
-                if best != 0:
-                    ranking[start], ranking[start + best] = ranking[start + best], ranking[start]
-                    if not changed:
-                        changed = True
-                        if last_start != full and best == len(window) - 1:
-                            last_start += len(window) - 1
-                if start == i:
-                    break
-                if not changed:
-                    last_start -= c
-                start -= c
-                end -= c
-
     def rerank_many(self, items):
         """Several queries at once: `items` = [(query, ranking), ...] -> (results, counters); results[i] and counters[i] =
         (total_compare, total_prompt_tokens, total_completion_tokens) are exactly what `rerank(*items[i])` gives, and the
@@ -466,7 +373,8 @@ class SetwiseLlmRanker(LlmRanker):
         needs the previous label), but the chains of different queries are independent: their pending compares go to the
         engine together, one call per step of all the chains - several ~900-token prompts per launch sequence instead of one
         (a compare's result does not depend on what shares its engine call: ragged execution, bit-exact).
-        heapsort and bubblesort with the draw-free default settings; anything else takes the one-by-one path."""
+        heapsort and bubblesort with the draw-free default settings; anything else (permutation voting, a compare() of a
+        subclass such as Rank-R1's) is one rerank per query."""
         items = list(items)
         if self.method not in ("heapsort", "bubblesort") or not self._batched_ok() or len(items) < 2:
             out, counters = [], []
@@ -476,51 +384,40 @@ class SetwiseLlmRanker(LlmRanker):
             return out, counters
         originals = [[doc.docid for doc in ranking] for _, ranking in items]
         counts = [[0, 0, 0] for _ in items]
-        heap = self.method == "heapsort"
-        gens = [self._heapsort_steps(ranking, self.k) if heap else self._bubblesort_steps(ranking) for _, ranking in items]
-        pending = {}
-        for q, gen in enumerate(gens):
-            try:
-                pending[q] = next(gen)
-            except StopIteration:
-                pass
+        chains = Lockstep({q: self._sort_steps(ranking, True) for q, (_, ranking) in enumerate(items)})
 
-        def windows_of(group):
-            order = sorted(group)
-            return order, [items[q][0] for q in order for _ in group[q]], [w for q in order for w in group[q]]
+        def queries_of(keys):
+            return [items[q][0] for q in keys]
 
-        def advance(group, order, outs, ptok, ctok):
-            """hand every chain of the group its labels -> the group's next pending windows"""
-            pos, nxt = 0, {}
-            for q in order:
-                n = len(group[q])
-                counts[q][0] += n
-                counts[q][1] += sum(ptok[pos:pos + n])
-                counts[q][2] += sum(ctok[pos:pos + n])
-                try:
-                    nxt[q] = gens[q].send(outs[pos:pos + n])
-                except StopIteration:
-                    pass
-                pos += n
-            return nxt
+        def counted(keys, labels, prompt_tokens, completion_tokens):
+            for q, p, c in zip(keys, prompt_tokens, completion_tokens):
+                counts[q][0] += 1
+                counts[q][1] += p
+                counts[q][2] += c
+            return labels
 
-        if len(pending) >= 4 and self._can_alternate():
+        if len(chains.live()) >= 4 and self._can_alternate():
             # Two groups of chains alternate over the engine's two batch slots: while one group's call is on the GPU the host
             # advances the other group's heaps, builds and tokenises its prompts and launches them - the launch-bound decoder
             # chain of one call runs under the encoder of the next, and the host part of a step is hidden.  A chain sees the
             # same labels as alone (batch independence), so rankings and counters do not change (tests).
-            groups = [{}, {}]
-            for i, q in enumerate(sorted(pending)):
-                groups[i % 2][q] = pending[q]
-            inflight = []                                            # [(group index, order, launched)] oldest first
+            groups = [Lockstep({}), Lockstep({})]
+            for i, q in enumerate(chains.live()):
+                groups[i % 2].absorb(chains, [q])
+            inflight = []                                            # [(group index, keys, launched)] oldest first
 
             def submit(g) -> bool:
-                order, queries, windows = windows_of(groups[g])
-                launched = self._launch_windows(queries, windows, slot=g)
+                keys, windows = groups[g].pending()
+                launched = self._launch_windows(queries_of(keys), windows, slot=g)
                 if launched is None:                                 # does not fit one engine call: back to the blocking loop below
                     return False
-                inflight.append((g, order, launched))
+                inflight.append((g, keys, launched))
                 return True
+
+            def collect() -> int:
+                g, keys, launched = inflight.pop(0)
+                groups[g].advance(counted(keys, *self._collect_windows(launched)))
+                return g
 
             ok = True
             try:
@@ -528,13 +425,11 @@ class SetwiseLlmRanker(LlmRanker):
                     if ok and groups[g]:
                         ok = submit(g)
                 while ok and inflight:
-                    g, order, launched = inflight.pop(0)
-                    groups[g] = advance(groups[g], order, *self._collect_windows(launched))
+                    g = collect()
                     if groups[g]:
                         ok = submit(g)
                 while inflight:                                      # (only after a call that did not fit)
-                    g, order, launched = inflight.pop(0)
-                    groups[g] = advance(groups[g], order, *self._collect_windows(launched))
+                    collect()
             finally:
                 # whatever raised above (a tokenizer error, a capacity error of the other group's launch): a call still queued on
                 # its slot is collected before the exception leaves - score_async's contract is that nothing else runs on the
@@ -544,26 +439,16 @@ class SetwiseLlmRanker(LlmRanker):
                         self._collect_windows(launched)
                     except Exception:
                         pass
-            pending = {**groups[0], **groups[1]}
-        while pending:
-            order, queries, windows = windows_of(pending)
-            pending = advance(pending, order, *self._compare_windows(queries, windows))
-        results = []
-        for (query, ranking), original in zip(items, originals):
-            ordered = list(reversed(ranking)) if heap else ranking
-            res, top, rank = [], set(), 1
-            for doc in ordered[:self.k]:
-                top.add(doc.docid)
-                res.append(SearchResult(docid=doc.docid, score=-rank, text=None))
-                rank += 1
-            for docid in original:
-                if docid not in top:
-                    res.append(SearchResult(docid=docid, score=-rank, text=None))
-                    rank += 1
-            results.append(res)
+            for group in groups:
+                chains.absorb(group)
+        while chains:
+            keys, windows = chains.pending()
+            chains.advance(counted(keys, *self._compare_windows(queries_of(keys), windows)))
+        heap = self.method == "heapsort"
+        results = [top_k_then_rest(list(reversed(ranking)) if heap else ranking, original, self.k)
+                   for (_, ranking), original in zip(items, originals)]
         counters = [tuple(c) for c in counts]
-        if counters:
-            self.total_compare, self.total_prompt_tokens, self.total_completion_tokens = counters[-1]
+        self.total_compare, self.total_prompt_tokens, self.total_completion_tokens = counters[-1]
         return results, counters
 
     def truncate(self, text, length):
@@ -687,25 +572,11 @@ class RankR1SetwiseLlmRanker(SetwiseLlmRanker):
                 print('--------------------------------------')
             match = re.search(rf'{self.prompt["pattern"]}', completion.lower(), re.DOTALL)
             results.append(match.group(1).strip() if match else f'input_text:\n{messages}, completion:\n{completion}')
-        candidates = []
-        for (docids, characters), result in zip(batch_ref, results):
-            result = result.strip()
-            if result not in characters:
-                if self.verbose:
-                    print(f"Unexpected output: {result}")
-                continue
-            candidates.append(docids[characters.index(result)])
-        if len(candidates) == 0:
-            if self.verbose:
-                print(f"Unexpected voting: {results}")
-            output = "Unexpected voting."
-        else:
-            counts = Counter(candidates)
-            top = max(counts.values())
-            winners = [c for c, v in counts.items() if v == top]
-            output = self.CHARACTERS[winners[0] if len(winners) == 1 else random.choice(winners)]
-        if output not in self.CHARACTERS and self.verbose:
-            print(f"Unexpected output: {output}")
+        say = print if self.verbose else (lambda *_: None)
+        output = vote(batch_ref, [result.strip() for result in results], self.CHARACTERS, say)
+        if output not in self.CHARACTERS:
+            say(f"Unexpected voting: {results}")
+            say(f"Unexpected output: {output}")
         return output
 
     def _chat_ids(self, messages) -> List[int]:
@@ -714,17 +585,6 @@ class RankR1SetwiseLlmRanker(SetwiseLlmRanker):
         if hasattr(out, "keys"):                             # transformers >= 5 returns a BatchEncoding
             out = out["input_ids"]
         return [int(t) for t in out]
-
-    def rerank_many(self, items):
-        """One rerank per query: the lock-step paths of the parent assume draw-free compares and single-letter labels."""
-        out, counters = [], []
-        for query, ranking in items:
-            out.append(self.rerank(query, ranking))
-            counters.append((self.total_compare, self.total_prompt_tokens, self.total_completion_tokens))
-        return out, counters
-
-    def _compare_many(self, query, doc_lists):
-        return [self.compare(query, docs) for docs in doc_lists]
 
     def _compare_windows(self, queries, doc_lists):
         raise NotImplementedError("RankR1SetwiseLlmRanker compares one window at a time")

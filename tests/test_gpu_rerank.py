@@ -115,7 +115,7 @@ def test_pairwise_cases(stack):
 @pytest.mark.parametrize("batched", [True, False])
 def test_setwise_cases(cases, stack, monkeypatch, batched):
     """batched=True is what ships: the build phase of the heapsort submits the independent sift-downs of a tree level
-    in one engine call (SetwiseLlmRanker._build_heap_batched / _compare_many, incl. the multi-row greedy EOS trimming).
+    in one engine call (SetwiseLlmRanker._heapsort_steps in level order / _compare_many, incl. the multi-row greedy EOS trimming).
     Compares are logged by wrapping the CLASS methods, so the ranker's own dispatch (_batched_ok) is untouched; the
     level-wise order differs from the reference's inside a level, so the compare log is checked as a multiset there
     and as an exact sequence with batching off."""
