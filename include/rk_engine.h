@@ -274,6 +274,56 @@ typedef struct rk_debug_gemm_call {
   float out_eps, out_xs;
 } rk_debug_gemm_call;
 int rk_debug_gemm_ex(rk_engine* e, rk_debug_gemm_call* call);
+/* debug: run ANY attention call of the engine (csrc/rk_engine.hip: plan_*attn -> the plan's launcher, no kernel and no dispatch of
+ * its own) on host data, every output inside guard bands.  kind selects the plan; heads have the kernels' own width (64 for the T5
+ * kinds, 128 for the Llama kinds); an engine of the other family gets RK_ERR_STATE.
+ *   1 T5 encoder         plan_enc_attn: q = packed qkv [T, ldq] (q | k | v at columns 0 | I | 2I, I = 64 H), seq_off[n_seq + 1], bias_lut
+ *                        [H][257] (entry rel + 128 for rel = key - query clamped to +-128; the table itself, not built from weights),
+ *                        out = ctx [T, ldctx].  Options attn_short, attn_heads_per_wg, attn_long, attn_long_nw, attn_long_xcd.
+ *   2 T5 decoder         plan_dec_attn.  cross = 0 (causal self-attention): q = fused rows [rows, ldq], keys / values in the same rows
+ *                        at columns k_col / v_col, bias_lut or null; rows = n_seq x Ld, or ragged row_off[n_seq + 1] (Ld = the longest),
+ *                        or the tree form: tree_rows query rows, row r at position tree_pos[r] sees rows tree_keys[r * Ld + j], j <=
+ *                        tree_pos[r].  cross = 1: q [rows, ldq], kv [Tk, ldkv] (k at k_col, v at v_col), seq_off = key offsets, no bias,
+ *                        no mask.  out = ctx [rows, ldctx].  Options dec_cross_mfma, dec_attn_seq, xattn_direct.
+ *   3 query-side cross   plan_xattn(fuse = false), the chunk kernel and xattn_combine_kernel only: q = qk [M, H, d] (ldq = H d), kv = enc
+ *                        [T, d] (ldkv = d), seq_off; query m belongs to sequence row_seq[row0 + m] (n_row_seq entries) or (row0 + m) / Ld;
+ *                        out [M, H, d] (ldctx = H d) = sum_t softmax_t(qk_h . enc_t) enc_t.  Option xattn_mfma.
+ *   4 Llama prefill      plan_llama_attn: q = rotated qkv [T, ldq] (H query heads, n_kv key heads, n_kv value heads of 128), seq_off,
+ *                        out = ctx [T, ldctx].  Options llama_attn_dma, llama_attn_nw.
+ *   5 Llama cached step  plan_llama_dec_attn: q = the step's rows [n_seq, ldq], NOT rotated; cache = K [n_seq][n_kv][P][128] then V, pos[n_seq]
+ *                        (< P, < max_pos), cos_t / sin_t [max_pos][64], qkv_bias [(H + 2 n_kv) 128] fp32 or null; out = ctx [n_seq, H 128]
+ *                        (ldctx = H 128); cache_all = the cache afterwards (the row's rotated key and its value appended at pos).  Option llama_dec_r.
+ * Inputs q / kv: host fp16, the WHOLE allocation: band_rows rows in front of and behind the q_rows / kv_rows interior rows, all of ldq /
+ * ldkv elements; the caller fills the bands (finite values: a kernel may load a masked row and give it weight 0); the call's pointer is
+ * the first interior row.  out: the interior, out_rows x ldctx elements, copied to the device as it is (the caller pre-fills what no
+ * kernel may touch); out_all: (out_rows + 2 band_rows) x ldctx elements, the whole device allocation after the call, the bands filled
+ * with the byte RK_DEBUG_SENTINEL before it.  cache / cache_all: the same with bands of band_rows x 128 elements.
+ * plan_only != 0: nothing is allocated or launched, only the out_* fields are filled: out_kind (1: DMA 0 / LONG 1 / TILED 2; 2: the
+ * staged kernel NONE 0 / SEQ 1 / ROW 2; 3: part MFMA_FEW 0 / MFMA 1 / VALU16 2 / VALU4 3; 4: dma 0 / 1), out_tparam (the kernel's template
+ * parameter: wave groups, waves, heads per workgroup or R), out_grid (the first kernel's), out_grid2 (the tiled / staged / merge
+ * kernel's), out_lds, out_staged, out_mfma, out_part, out_R, out_nch, out_skip_long, out_heads_per_wg, out_n_cu.
+ * Every extent is checked against the sizes given before anything is launched (RK_ERR_INVALID); a shape no kernel of the plan takes
+ * fails with RK_ERR_STATE and launches nothing. */
+typedef struct rk_debug_attn_call {
+  int kind;
+  int n_seq, H, n_kv, Ld, cross, M, row0, d, P;
+  int ldq, ldkv, ldctx, k_col, v_col, band_rows;
+  const uint16_t* q; int64_t q_rows;
+  const uint16_t* kv; int64_t kv_rows;
+  const int32_t* seq_off; const int32_t* row_off;
+  const int32_t* tree_keys; const int32_t* tree_pos; int tree_rows;
+  const int32_t* row_seq; int n_row_seq;
+  const int32_t* pos;
+  const float* bias_lut;
+  const float* cos_t; const float* sin_t; int max_pos;
+  const float* qkv_bias;
+  const uint16_t* out; int64_t out_rows; uint16_t* out_all;
+  const uint16_t* cache; uint16_t* cache_all;
+  int plan_only;
+  int out_kind, out_tparam, out_grid[3], out_grid2[3], out_lds, out_staged, out_mfma, out_part, out_R, out_nch, out_skip_long,
+      out_heads_per_wg, out_n_cu;
+} rk_debug_attn_call;
+int rk_debug_attn(rk_engine* e, rk_debug_attn_call* call);
 /* measurement: average ms per launch of the engine's GEMM kernel at one shape (epi = 0 store f16, 1 residual f32,
  * 2 GEGLU, 3 ReLU, 4 store f32), random operands, `iters` back-to-back launches timed with HIP events */
 int rk_debug_gemm_bench(rk_engine* e, int M, int N, int K, int epi, int iters, float* out_ms);

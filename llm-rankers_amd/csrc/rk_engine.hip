@@ -864,20 +864,22 @@ EncAttnPlan plan_enc_attn(const rk_engine* e, int n_seq, int maxL, int minL, int
   return p;
 }
 
-void launch_enc_attn(rk_engine* e, hipStream_t st, const Slot& sl, const EncAttnPlan& p) {
-  const int I = e->inner;
-  AttnEncArgs a{sl.qkv, sl.ctx, sl.d_seq_off, e->lut_enc, 3 * I, I, I, 1, e->opt.attn_ko};
+// what the launcher reads of a call: run_encoder fills it from its slot and the model, rk_debug_attn from host operands
+struct EncAttnCall { const half_t* qkv; half_t* ctx; const int* seq_off; const float* lut; int ld, ldctx, I, H, n_seq, maxL, T; };
+void launch_enc_attn(rk_engine* e, hipStream_t st, const EncAttnCall& c, const EncAttnPlan& p) {
+  const int I = c.I;
+  AttnEncArgs a{c.qkv, c.ctx, c.seq_off, c.lut, c.ld, c.ldctx, I, 1, e->opt.attn_ko};
 #ifdef RK_MEASURE
   a.trace = e->attn_trace;
 #endif
-  Bracket br(e, st, PC_ENC_ATTN, 4.0 * (double)sl.maxL * sl.T * I, (double)sl.T * 4 * I * 2.0);   // flops: exact for uniform lengths, upper bound if ragged
+  Bracket br(e, st, PC_ENC_ATTN, 4.0 * (double)c.maxL * c.T * I, (double)c.T * 4 * I * 2.0);   // flops: exact for uniform lengths, upper bound if ragged
   if (p.kind == EncAttnPlan::TILED || p.skip_long) { a.skip_long = p.skip_long; hipLaunchKernelGGL(attn_enc_kernel, p.tiled_grid, dim3(256), 0, st, a); }
   if (p.kind == EncAttnPlan::DMA) {
-    a.heads_per_wg = p.heads_per_wg; a.n_seq = sl.n_seq;
+    a.heads_per_wg = p.heads_per_wg; a.n_seq = c.n_seq;
     if (p.ng == 2) launch_lds<attn_enc_dma_kernel<2>>(st, p.grid, p.block, p.lds, p.lds, a);
     else launch_lds<attn_enc_dma_kernel<1>>(st, p.grid, p.block, p.lds, p.lds, a);
   } else if (p.kind == EncAttnPlan::LONG) {
-    a.n_seq = sl.n_seq; a.n_heads = e->d.n_heads; a.nqb = p.nqb; a.xcd_map = p.xcd_map;
+    a.n_seq = c.n_seq; a.n_heads = c.H; a.nqb = p.nqb; a.xcd_map = p.xcd_map;
     if (p.nw == 12) launch_lds<attn_enc_long_kernel<12>>(st, p.grid, p.block, p.lds, p.lds, a);
     else if (p.nw == 6) launch_lds<attn_enc_long_kernel<6>>(st, p.grid, p.block, p.lds, p.lds, a);
     else if (p.nw == 4) launch_lds<attn_enc_long_kernel<4>>(st, p.grid, p.block, p.lds, p.lds, a);
@@ -950,6 +952,17 @@ XAttnPlan plan_xattn(const rk_engine* e, bool fuse, int nr, int maxL, int H, int
   return p;
 }
 
+// The chunk kernel of the plan over xa's rows and, unless the merge is fused into the W_v product, xattn_combine_kernel (maxL, T:
+// the longest sequence and the token count, for the profile only)
+void launch_xattn_part(rk_engine* e, hipStream_t st, const XAttnPlan& p, const XAttnArgs& xa, int maxL, int T) {
+  Bracket br(e, st, PC_DEC_ATTN, 4.0 * p.nr * (double)maxL * xa.H * xa.d, (double)T * xa.d * 2.0 * 2);
+  if (p.part == XAttnPlan::MFMA_FEW) hipLaunchKernelGGL(xattn_part_mfma_kernel<true>, p.part_grid, dim3(256), 0, st, xa);
+  else if (p.part == XAttnPlan::MFMA) hipLaunchKernelGGL(xattn_part_mfma_kernel<false>, p.part_grid, dim3(256), 0, st, xa);
+  else if (p.part == XAttnPlan::VALU16) hipLaunchKernelGGL(xattn_part_kernel<16>, p.part_grid, dim3(256), 0, st, xa);
+  else hipLaunchKernelGGL(xattn_part_kernel<4>, p.part_grid, dim3(256), 0, st, xa);
+  if (!p.fuse_cv) hipLaunchKernelGGL(xattn_combine_kernel, dim3(xa.H, p.nr), dim3(256), 0, st, xa);
+}
+
 // Rows [r0, r0 + p.nr) of decoder layer l.  Fused: x, wq and in1 are the q projection's input, weight and norm; else sl.dq holds
 // q.  row_seq: decoder row -> encoder sequence (tree form) or nullptr.
 int launch_xattn(rk_engine* e, hipStream_t st, Slot& sl, const XAttnPlan& p, int l, int Ld, int r0, const half_t* x,
@@ -966,15 +979,7 @@ int launch_xattn(rk_engine* e, hipStream_t st, Slot& sl, const XAttnPlan& p, int
   } else {
     RC(gemm(e, st, Gemm(PC_DEC_GEMM, EPI_STORE_F16, sl.dq + (size_t)r0 * I, I, e->dec[l].ckT, 64, sl.xqk, H * dm, nr, dm, 64).heads(H, 64, (long)dm * 64, dm)));
   }
-  XAttnArgs xa{sl.xqk, sl.enc_out, sl.d_seq_off, sl.xpart, sl.xstat, sl.xctx, Ld, H, dm, p.nch, r0, row_seq};
-  {
-    Bracket br(e, st, PC_DEC_ATTN, 4.0 * nr * (double)sl.maxL * H * dm, (double)sl.T * dm * 2.0 * 2);
-    if (p.part == XAttnPlan::MFMA_FEW) hipLaunchKernelGGL(xattn_part_mfma_kernel<true>, p.part_grid, dim3(256), 0, st, xa);
-    else if (p.part == XAttnPlan::MFMA) hipLaunchKernelGGL(xattn_part_mfma_kernel<false>, p.part_grid, dim3(256), 0, st, xa);
-    else if (p.part == XAttnPlan::VALU16) hipLaunchKernelGGL(xattn_part_kernel<16>, p.part_grid, dim3(256), 0, st, xa);
-    else hipLaunchKernelGGL(xattn_part_kernel<4>, p.part_grid, dim3(256), 0, st, xa);
-    if (!p.fuse_cv) hipLaunchKernelGGL(xattn_combine_kernel, dim3(H, nr), dim3(256), 0, st, xa);
-  }
+  launch_xattn_part(e, st, p, XAttnArgs{sl.xqk, sl.enc_out, sl.d_seq_off, sl.xpart, sl.xstat, sl.xctx, Ld, H, dm, p.nch, r0, row_seq}, sl.maxL, sl.T);
   if (!p.fuse_cv)
     return gemm(e, st, Gemm(PC_DEC_GEMM, EPI_STORE_F16, sl.xctx, H * dm, wv, dm, sl.dctx + (size_t)r0 * I, I, nr, 64, dm).heads(H, dm, (long)64 * dm, 64));
   DecCVArgs ca{sl.xpart, sl.xstat, sl.d_seq_off, row_seq, Ld, r0, wv, sl.dctx + (size_t)r0 * I, nr, dm, H, p.nch, I, p.cv_R};
@@ -1002,14 +1007,15 @@ CausalAttnPlan plan_llama_attn(const rk_engine* e, int n_seq, int maxL, int n_he
   return p;
 }
 
-void launch_llama_attn(rk_engine* e, hipStream_t st, const Slot& sl, const CausalAttnPlan& p) {
-  const rk_llama_desc& l = e->ld;
-  const int T = sl.T, Q = l.n_heads * 128, KV = l.n_kv_heads * 128;
+// what the launcher reads of a call: llama_prefill fills it from its slot and the model, rk_debug_attn from host operands
+struct CausalAttnCall { const half_t* qkv; half_t* ctx; const int* seq_off; int ld, ldctx, n_heads, n_kv, n_seq, maxL, T; };
+void launch_llama_attn(rk_engine* e, hipStream_t st, const CausalAttnCall& c, const CausalAttnPlan& p) {
+  const int T = c.T, Q = c.n_heads * 128, KV = c.n_kv * 128;
   const float scale_log2e = (1.0f / std::sqrt(128.0f)) * 1.4426950408889634f;   // head_dim**-0.5 * log2(e)
-  AttnCausalArgs a{sl.qkv, sl.ctx, sl.d_seq_off, Q + 2 * KV, Q, l.n_heads, l.n_kv_heads, scale_log2e, 0, 0, e->opt.attn_ko};
-  Bracket br(e, st, PC_ENC_ATTN, 2.0 * (double)sl.maxL * T * Q, (double)T * (2 * Q + 2 * KV) * 2.0);   // causal: half of 4 L T Q
+  AttnCausalArgs a{c.qkv, c.ctx, c.seq_off, c.ld, c.ldctx, c.n_heads, c.n_kv, scale_log2e, 0, 0, e->opt.attn_ko};
+  Bracket br(e, st, PC_ENC_ATTN, 2.0 * (double)c.maxL * T * Q, (double)T * (2 * Q + 2 * KV) * 2.0);   // causal: half of 4 L T Q
   if (!p.dma) { hipLaunchKernelGGL(attn_causal128_kernel, p.grid, dim3(p.block), 0, st, a); return; }
-  a.n_seq = sl.n_seq; a.nqb = p.nqb;
+  a.n_seq = c.n_seq; a.nqb = p.nqb;
   if (p.nw == 8) launch_lds<attn_causal128_dma_kernel<8>>(st, p.grid, p.block, p.lds, p.lds_opt_in, a);
   else launch_lds<attn_causal128_dma_kernel<4>>(st, p.grid, p.block, p.lds, p.lds_opt_in, a);
 }
@@ -1071,7 +1077,7 @@ int run_encoder(rk_engine* e, Slot& sl, bool need_cross_kv) {
     const EncLayerW& w = e->enc[l];
     const bool last = l + 1 == d.n_enc_layers;
     RC(gemm(e, st, ns.consumer(e, st, w.ln0, Gemm(PC_ENC_GEMM_QKV, EPI_STORE_F16, ns.x(), dm, ns.fold ? w.qkv_f : w.qkv, dm, sl.qkv, 3 * I, T, 3 * I, dm), own)));
-    launch_enc_attn(e, st, sl, ap);
+    launch_enc_attn(e, st, EncAttnCall{sl.qkv, sl.ctx, sl.d_seq_off, e->lut_enc, 3 * I, I, I, d.n_heads, sl.n_seq, sl.maxL, sl.T}, ap);
     RC(ns.producer(e, st, Gemm(PC_ENC_GEMM_O, EPI_RESID_F32, sl.ctx, I, w.o, I, ns.hidden, dm, T, dm, I)));
     RC(gemm(e, st, ns.consumer(e, st, w.ln1, Gemm(PC_ENC_GEMM_FFN_IN, d.gated_gelu ? EPI_GEGLU_F16 : EPI_RELU_F16, ns.x(), dm, ns.fold ? w.ffn_in_f : w.ffn_in, dm,
                                                  sl.ffh, F, T, d.gated_gelu ? 2 * F : F, dm), own)));
@@ -2436,7 +2442,7 @@ static int llama_prefill(rk_engine* e, const int32_t* tokens, const int32_t* off
       hipLaunchKernelGGL(kv_cache_fill128_kernel, dim3(sl.maxL, n_seq), dim3(256), 0, st, sl.qkv, sl.d_seq_off, kc, kc + half_layer, ldq,
                          l.n_heads, l.n_kv_heads, keep->P);
     }
-    launch_llama_attn(e, st, sl, ap);
+    launch_llama_attn(e, st, CausalAttnCall{sl.qkv, sl.ctx, sl.d_seq_off, ldq, Q, l.n_heads, l.n_kv_heads, sl.n_seq, sl.maxL, T}, ap);
     RC(ns.producer(e, st, Gemm(PC_ENC_GEMM_O, EPI_RESID_F32, sl.ctx, Q, w.o, Q, ns.hidden, dm, T, dm, Q)));
     RC(gemm(e, st, ns.consumer(e, st, nullptr, Gemm(PC_ENC_GEMM_FFN_IN, EPI_SWIGLU_F16, ns.x(), dm, w.gu_f, dm, sl.ffh, F, T, 2 * F, dm), false)));
     RC(ns.producer(e, st, Gemm(PC_ENC_GEMM_FFN_OUT, EPI_RESID_F32, sl.ffh, F, w.down, F, ns.hidden, dm, T, dm, F), i + 1 < l.n_layers));
@@ -2983,6 +2989,212 @@ int rk_debug_gemm_ex(rk_engine* e, rk_debug_gemm_call* q) {
   if (dI) DBG_HIP(hipMemcpy(q->idx_out, dI, c_all * 4, hipMemcpyDeviceToHost));
   if (producer) { DBG_HIP(hipMemcpy(q->xraw_out, dX, x_all * 2, hipMemcpyDeviceToHost)); DBG_HIP(hipMemcpy(q->ssq_out, dS, s_all * 4, hipMemcpyDeviceToHost)); }
   if (dXl) DBG_HIP(hipMemcpy(q->xlab, dXl, (size_t)M * 4, hipMemcpyDeviceToHost));
+#undef DBG_HIP
+  return done(RK_OK);
+}
+
+// debug: one attention call on host data, every output between sentinel bands (include/rk_engine.h).  No kernel and no dispatch of
+// its own: it uploads the operands, asks the plan_*attn function of the kind and hands the plan to that plan's launcher.
+int rk_debug_attn(rk_engine* e, rk_debug_attn_call* q) {
+  if (!e || !q) return RK_ERR_INVALID;
+  int rc = set_device(e);
+  if (rc) return rc;
+  if (!e->finalized) return fail(e, RK_ERR_STATE, "debug attn: engine not finalized");
+  const int kind = q->kind, B = q->n_seq, H = q->H;
+  if (kind < 1 || kind > 5) return fail(e, RK_ERR_INVALID, "debug attn: kind 1..5");
+  if (e->family != (kind >= 4 ? 1 : 0)) return fail(e, RK_ERR_STATE, "debug attn: kind %d needs a %s engine", kind, kind >= 4 ? "Llama" : "T5");
+  if (B <= 0 || B > (1 << 16) || H <= 0 || H > 1024) return fail(e, RK_ERR_INVALID, "debug attn: n_seq and H");
+  const bool planning = q->plan_only != 0;
+  const int hd = kind >= 4 ? 128 : 64, band = q->band_rows;
+  if (!planning && (!q->q || !q->out || !q->out_all || band < 1)) return fail(e, RK_ERR_INVALID, "debug attn: q, out, out_all and band_rows >= 1");
+  // ---- the offsets: lengths, the longest and the shortest ----
+  int maxL = 0, minL = 1 << 30, T = 0;
+  const bool has_off = kind == 1 || kind == 3 || kind == 4 || (kind == 2 && q->cross);
+  if (has_off) {
+    if (!q->seq_off || q->seq_off[0] != 0) return fail(e, RK_ERR_INVALID, "debug attn: seq_off[n_seq + 1] starting at 0");
+    for (int b = 0; b < B; ++b) {
+      const int L = q->seq_off[b + 1] - q->seq_off[b];
+      if (L <= 0 || L > (1 << 20)) return fail(e, RK_ERR_INVALID, "debug attn: sequence %d has %d keys", b, L);
+      maxL = std::max(maxL, L); minL = std::min(minL, L);
+    }
+    T = q->seq_off[B];
+  }
+  long q_rows_need = 0, kv_rows_need = 0, out_rows_need = 0;   // interior rows the call addresses
+  long ldq_min = 0, ldkv_min = 0, ldctx_min = 0;
+  auto plan_out = [&](int k, int tp, dim3 g1, dim3 g2, int lds) {
+    q->out_kind = k; q->out_tparam = tp; q->out_lds = lds; q->out_n_cu = e->n_cu;
+    q->out_grid[0] = (int)g1.x; q->out_grid[1] = (int)g1.y; q->out_grid[2] = (int)g1.z;
+    q->out_grid2[0] = (int)g2.x; q->out_grid2[1] = (int)g2.y; q->out_grid2[2] = (int)g2.z;
+  };
+  q->out_staged = q->out_mfma = q->out_part = q->out_R = q->out_nch = q->out_skip_long = q->out_heads_per_wg = 0;
+  EncAttnPlan ep; DecAttnPlan dp; XAttnPlan xp; CausalAttnPlan cp; LlamaDecAttnPlan lp;
+  int dec_rows = 0, dec_keys = 0;
+  if (kind == 1) {
+    const int I = H * 64;
+    ldq_min = 3L * I; ldctx_min = I; q_rows_need = out_rows_need = T;
+    if (!planning && !q->bias_lut) return fail(e, RK_ERR_INVALID, "debug attn: the encoder needs bias_lut");
+    ep = plan_enc_attn(e, B, maxL, minL, H);
+    plan_out((int)ep.kind, ep.kind == EncAttnPlan::DMA ? ep.ng : ep.nw, ep.grid, ep.tiled_grid, ep.lds);
+    q->out_skip_long = ep.skip_long; q->out_heads_per_wg = ep.heads_per_wg;
+  } else if (kind == 2) {
+    const int Ld = q->Ld;
+    if (Ld <= 0 || Ld > (1 << 16) || q->k_col < 0 || q->v_col < 0) return fail(e, RK_ERR_INVALID, "debug attn: Ld, k_col, v_col");
+    const bool tree = q->tree_rows > 0;
+    if (tree && (q->cross || q->row_off || !q->tree_keys || !q->tree_pos)) return fail(e, RK_ERR_INVALID, "debug attn: the tree form is the self-attention's, with tree_keys and tree_pos, without row_off");
+    if (q->row_off) {
+      if (q->row_off[0] != 0) return fail(e, RK_ERR_INVALID, "debug attn: row_off starts at 0");
+      int longest = 0;
+      for (int b = 0; b < B; ++b) {
+        const int n = q->row_off[b + 1] - q->row_off[b];
+        if (n <= 0) return fail(e, RK_ERR_INVALID, "debug attn: sequence %d has %d rows", b, n);
+        longest = std::max(longest, n);
+      }
+      if (longest != Ld) return fail(e, RK_ERR_INVALID, "debug attn: Ld = %d is not the longest row count %d", Ld, longest);
+      dec_rows = q->row_off[B];
+    } else dec_rows = tree ? q->tree_rows : B * Ld;
+    dec_keys = q->cross ? maxL : Ld;
+    ldq_min = H * 64; ldctx_min = H * 64; out_rows_need = dec_rows;
+    q_rows_need = tree ? 0 : dec_rows;                       // (tree: the rows tree_keys names, checked below)
+    if (q->cross) { ldkv_min = std::max(q->k_col, q->v_col) + H * 64; kv_rows_need = T; }
+    else ldq_min = std::max<long>(ldq_min, std::max(q->k_col, q->v_col) + H * 64);
+    if (tree) {
+      q_rows_need = q->tree_rows;
+      for (int r = 0; r < q->tree_rows; ++r) {
+        if (q->tree_pos[r] < 0 || q->tree_pos[r] >= Ld) return fail(e, RK_ERR_INVALID, "debug attn: tree_pos[%d] outside 0..Ld-1", r);
+        for (int j = 0; j <= q->tree_pos[r]; ++j) {
+          const int k = q->tree_keys[(size_t)r * Ld + j];
+          if (k < 0) return fail(e, RK_ERR_INVALID, "debug attn: tree_keys[%d][%d] negative", r, j);
+          q_rows_need = std::max<long>(q_rows_need, k + 1L);
+        }
+      }
+    }
+    dp = plan_dec_attn(e, q->cross != 0, B, Ld, dec_keys, H, tree ? q->tree_rows : 0);
+    plan_out((int)dp.staged, 0, dp.mfma_grid, dp.grid, (int)dp.lds);
+    q->out_staged = (int)dp.staged; q->out_mfma = dp.mfma;
+    // the staged kernels' dynamic LDS is opted in at finalize for the engine's capacities (the MFMA kernel's is fixed)
+    const size_t lds_cap = dp.staged == DecAttnPlan::SEQ ? 160 * 1024 : std::min<size_t>(attn_dec_lds(std::max(e->d.max_tokens, e->d.max_dec_len)), 160 * 1024);
+    if (dp.staged != DecAttnPlan::NONE && dp.lds > lds_cap)
+      return fail(e, RK_ERR_STATE, "debug attn: %d keys need %zu bytes of LDS, the staged kernel of this engine has %zu", dec_keys, dp.lds, lds_cap);
+    if (dp.mfma && Ld > ATTX_MAXQ) return fail(e, RK_ERR_STATE, "debug attn: the matrix-core kernel takes at most %d positions", ATTX_MAXQ);
+  } else if (kind == 3) {
+    const int M = q->M, d = q->d, Ld = q->Ld;
+    if (M <= 0 || M > (1 << 16) || d <= 0 || d % 32 || d > 16384 || Ld <= 0 || q->row0 < 0) return fail(e, RK_ERR_INVALID, "debug attn: M, Ld, row0 and d (a multiple of 32)");
+    if (q->ldq != H * d || q->ldkv != d || q->ldctx != H * d) return fail(e, RK_ERR_INVALID, "debug attn: the query-side form is dense: ldq = ldctx = H d, ldkv = d");
+    if (maxL > 65536) return fail(e, RK_ERR_STATE, "debug attn: the chunk merge takes sequences of at most 65536 keys");
+    for (int m = 0; m < M; ++m) {
+      if (q->row_seq && q->row0 + m >= q->n_row_seq) return fail(e, RK_ERR_INVALID, "debug attn: row_seq has %d entries, row %d is read", q->n_row_seq, q->row0 + m);
+      const int b = q->row_seq ? q->row_seq[q->row0 + m] : (q->row0 + m) / Ld;
+      if (b < 0 || b >= B) return fail(e, RK_ERR_INVALID, "debug attn: row %d belongs to sequence %d of %d", q->row0 + m, b, B);
+    }
+    ldq_min = (long)H * d; ldkv_min = d; ldctx_min = (long)H * d; q_rows_need = out_rows_need = M; kv_rows_need = T;
+    xp = plan_xattn(e, false, M, maxL, H, d);
+    plan_out((int)xp.part, xp.part == XAttnPlan::VALU4 ? 4 : 16, xp.part_grid, dim3(H, M), 0);
+    q->out_part = (int)xp.part; q->out_nch = xp.nch; q->out_mfma = xp.part == XAttnPlan::MFMA_FEW || xp.part == XAttnPlan::MFMA;
+  } else if (kind == 4) {
+    const int n_kv = q->n_kv;
+    if (n_kv <= 0 || H % n_kv) return fail(e, RK_ERR_INVALID, "debug attn: n_kv must divide H");
+    ldq_min = (long)(H + 2 * n_kv) * 128; ldctx_min = (long)H * 128; q_rows_need = out_rows_need = T;
+    cp = plan_llama_attn(e, B, maxL, H, n_kv);
+    plan_out((int)cp.dma, cp.nw, cp.grid, dim3(0, 0, 0), cp.lds);
+  } else {
+    const int n_kv = q->n_kv, P = q->P;
+    if (n_kv <= 0 || H % n_kv || P <= 0 || P > (1 << 20)) return fail(e, RK_ERR_INVALID, "debug attn: n_kv must divide H, P > 0");
+    if (q->ldctx != H * 128) return fail(e, RK_ERR_INVALID, "debug attn: the step's ctx is dense: ldctx = 128 H");
+    ldq_min = (long)(H + 2 * n_kv) * 128; ldctx_min = (long)H * 128; q_rows_need = out_rows_need = B;
+    if (!planning) {
+      if (!q->pos || !q->cos_t || !q->sin_t || !q->cache || !q->cache_all) return fail(e, RK_ERR_INVALID, "debug attn: the step needs pos, cos_t, sin_t, cache and cache_all");
+      for (int b = 0; b < B; ++b)
+        if (q->pos[b] < 0 || q->pos[b] >= P || q->pos[b] >= q->max_pos) return fail(e, RK_ERR_INVALID, "debug attn: pos[%d] = %d outside the cache of %d / the tables of %d", b, q->pos[b], P, q->max_pos);
+    }
+    lp = plan_llama_dec_attn(e, B, P, H, n_kv);
+    plan_out(0, lp.R, lp.grid, lp.cgrid, 0);
+    q->out_R = lp.R; q->out_nch = lp.nch;
+    if (H % lp.R) return fail(e, RK_ERR_STATE, "debug attn: R = %d does not divide %d heads", lp.R, H);
+  }
+  if (planning) return RK_OK;
+  // ---- extents, from the addressing of the call, against what the caller gave ----
+  if (q->ldq < ldq_min || q->ldq % 8 || q->ldctx < ldctx_min || q->ldctx % 8 || (ldkv_min && (q->ldkv < ldkv_min || q->ldkv % 8)) || q->k_col % 8 || q->v_col % 8)
+    return fail(e, RK_ERR_INVALID, "debug attn: leading dimensions (ldq %d >= %ld, ldkv %d >= %ld, ldctx %d >= %ld; multiples of 8, as k_col and v_col)", q->ldq, ldq_min, q->ldkv, ldkv_min, q->ldctx, ldctx_min);
+  if (q_rows_need > q->q_rows || out_rows_need > q->out_rows || (kv_rows_need && (!q->kv || kv_rows_need > q->kv_rows)))
+    return fail(e, RK_ERR_INVALID, "debug attn: the call reaches beyond q (%ld of %ld rows), kv (%ld of %ld) or out (%ld of %ld)", q_rows_need, (long)q->q_rows, kv_rows_need, (long)q->kv_rows, out_rows_need, (long)q->out_rows);
+  if (((long)q->q_rows + 2L * band) * q->ldq >= (1L << 31) || ((long)q->kv_rows + 2L * band) * std::max(q->ldkv, 1) >= (1L << 31))
+    return fail(e, RK_ERR_INVALID, "debug attn: operands of 2^31 elements or more");   // (the DMA kernels address rows by 32-bit byte offsets)
+  std::vector<void*> dev;
+  auto alloc = [&](size_t bytes, int fill) -> void* {
+    void* ptr = nullptr;
+    if (hipMalloc(&ptr, bytes ? bytes : 16) != hipSuccess) return nullptr;
+    dev.push_back(ptr);
+    if (fill >= 0 && hipMemset(ptr, fill, bytes) != hipSuccess) return nullptr;
+    return ptr;
+  };
+  auto done = [&](int r) { for (void* ptr : dev) hipFree(ptr); return r; };
+#define DBG_HIP(x) do { if ((x) != hipSuccess) return done(fail(e, RK_ERR_HIP, "debug attn: %s", #x)); } while (0)
+  auto up = [&](const void* src, size_t bytes) -> void* {
+    void* ptr = alloc(bytes, -1);
+    if (ptr && hipMemcpy(ptr, src, bytes, hipMemcpyHostToDevice) != hipSuccess) return nullptr;
+    return ptr;
+  };
+  const size_t q_all = ((size_t)q->q_rows + 2 * (size_t)band) * q->ldq, kv_all = q->kv ? ((size_t)q->kv_rows + 2 * (size_t)band) * q->ldkv : 0;
+  const size_t o_band = (size_t)band * q->ldctx, o_in = (size_t)q->out_rows * q->ldctx, o_all = o_in + 2 * o_band;
+  half_t* dQ = (half_t*)up(q->q, q_all * 2);
+  half_t* dKV = q->kv ? (half_t*)up(q->kv, kv_all * 2) : nullptr;
+  half_t* dO = (half_t*)alloc(o_all * 2, RK_DEBUG_SENTINEL);
+  if (!dQ || (q->kv && !dKV) || !dO) return done(fail(e, RK_ERR_HIP, "debug attn: device allocation or upload failed"));
+  DBG_HIP(hipMemcpy(dO + o_band, q->out, o_in * 2, hipMemcpyHostToDevice));
+  half_t* const qi = dQ + (size_t)band * q->ldq;
+  half_t* const kvi = dKV ? dKV + (size_t)band * q->ldkv : nullptr;
+  half_t* const oi = dO + o_band;
+  int* dOff = has_off ? (int*)up(q->seq_off, (size_t)(B + 1) * 4) : nullptr;
+  if (has_off && !dOff) return done(fail(e, RK_ERR_HIP, "debug attn: upload failed"));
+  float* dLut = q->bias_lut && kind <= 2 ? (float*)up(q->bias_lut, (size_t)H * RK_LUT_N * 4) : nullptr;
+  if (q->bias_lut && kind <= 2 && !dLut) return done(fail(e, RK_ERR_HIP, "debug attn: upload failed"));
+  hipStream_t st = e->slots[0].se;
+  half_t* dC = nullptr; size_t c_all = 0;
+  if (kind == 1) {
+    DBG_HIP(hipDeviceSynchronize());
+    launch_enc_attn(e, st, EncAttnCall{qi, oi, dOff, dLut, q->ldq, q->ldctx, H * 64, H, B, maxL, T}, ep);
+  } else if (kind == 2) {
+    int *dRow = nullptr, *dTk = nullptr, *dTp = nullptr;
+    if (q->row_off && !(dRow = (int*)up(q->row_off, (size_t)(B + 1) * 4))) return done(fail(e, RK_ERR_HIP, "debug attn: upload failed"));
+    if (q->tree_rows > 0) {
+      dTk = (int*)up(q->tree_keys, (size_t)q->tree_rows * q->Ld * 4); dTp = (int*)up(q->tree_pos, (size_t)q->tree_rows * 4);
+      if (!dTk || !dTp) return done(fail(e, RK_ERR_HIP, "debug attn: upload failed"));
+    }
+    DBG_HIP(hipDeviceSynchronize());
+    const half_t* kb = q->cross ? kvi : qi;
+    launch_dec_attn(e, st, dp, AttnDecArgs{qi, q->ldq, kb + q->k_col, kb + q->v_col, q->cross ? q->ldkv : q->ldq, q->cross ? dOff : nullptr, oi, q->ldctx, dLut,
+                                           q->Ld, q->cross ? 0 : 1, dec_keys, dTk, dTp, 0, dRow}, 0, 0);
+  } else if (kind == 3) {
+    int* dRs = nullptr;
+    if (q->row_seq && !(dRs = (int*)up(q->row_seq, (size_t)q->n_row_seq * 4))) return done(fail(e, RK_ERR_HIP, "debug attn: upload failed"));
+    float* dPart = (float*)alloc((size_t)q->M * xp.nch * H * q->d * 4, RK_DEBUG_SENTINEL);
+    float* dStat = (float*)alloc((size_t)q->M * xp.nch * H * 2 * 4, RK_DEBUG_SENTINEL);
+    if (!dPart || !dStat) return done(fail(e, RK_ERR_HIP, "debug attn: device allocation failed"));
+    DBG_HIP(hipDeviceSynchronize());
+    launch_xattn_part(e, st, xp, XAttnArgs{qi, kvi, dOff, dPart, dStat, oi, q->Ld, H, q->d, xp.nch, q->row0, dRs}, maxL, T);
+  } else if (kind == 4) {
+    DBG_HIP(hipDeviceSynchronize());
+    launch_llama_attn(e, st, CausalAttnCall{qi, oi, dOff, q->ldq, q->ldctx, H, q->n_kv, B, maxL, T}, cp);
+  } else {
+    const size_t half_layer = (size_t)B * q->n_kv * q->P * 128, c_band = (size_t)band * 128;
+    c_all = 2 * half_layer + 2 * c_band;
+    dC = (half_t*)alloc(c_all * 2, RK_DEBUG_SENTINEL);
+    int* dPos = (int*)up(q->pos, (size_t)B * 4);
+    float* dCos = (float*)up(q->cos_t, (size_t)q->max_pos * 64 * 4);
+    float* dSin = (float*)up(q->sin_t, (size_t)q->max_pos * 64 * 4);
+    float* dBias = q->qkv_bias ? (float*)up(q->qkv_bias, (size_t)(H + 2 * q->n_kv) * 128 * 4) : nullptr;
+    float* dPart = (float*)alloc((size_t)B * H * lp.nch * LDC_PSTR * 4, RK_DEBUG_SENTINEL);
+    if (!dC || !dPos || !dCos || !dSin || (q->qkv_bias && !dBias) || !dPart) return done(fail(e, RK_ERR_HIP, "debug attn: device allocation or upload failed"));
+    DBG_HIP(hipMemcpy(dC + c_band, q->cache, 2 * half_layer * 2, hipMemcpyHostToDevice));
+    DBG_HIP(hipDeviceSynchronize());
+    const float scale_log2e = (1.0f / std::sqrt(128.0f)) * 1.4426950408889634f;
+    half_t* kc = dC + c_band;
+    launch_llama_dec_attn(e, st, lp, AttnDecCached128Args{qi, kc, kc + half_layer, dPos, dCos, dSin, dPart, oi, q->ldq, H, q->n_kv, q->P, lp.nch, scale_log2e, dBias}, B);
+  }
+  DBG_HIP(hipStreamSynchronize(st));
+  DBG_HIP(hipGetLastError());
+  DBG_HIP(hipMemcpy(q->out_all, dO, o_all * 2, hipMemcpyDeviceToHost));
+  if (dC) DBG_HIP(hipMemcpy(q->cache_all, dC, c_all * 2, hipMemcpyDeviceToHost));
 #undef DBG_HIP
   return done(RK_OK);
 }

@@ -49,6 +49,20 @@ class RkDebugGemmCall(C.Structure):
                [("out_eps", C.c_float), ("out_xs", C.c_float)]
 
 
+class RkDebugAttnCall(C.Structure):
+    """rk_debug_attn_call of include/rk_engine.h, field for field."""
+    _fields_ = [(n, C.c_int) for n in ("kind", "n_seq", "H", "n_kv", "Ld", "cross", "M", "row0", "d", "P",
+                                       "ldq", "ldkv", "ldctx", "k_col", "v_col", "band_rows")] + \
+               [("q", C.c_void_p), ("q_rows", C.c_int64), ("kv", C.c_void_p), ("kv_rows", C.c_int64),
+                ("seq_off", C.c_void_p), ("row_off", C.c_void_p), ("tree_keys", C.c_void_p), ("tree_pos", C.c_void_p), ("tree_rows", C.c_int),
+                ("row_seq", C.c_void_p), ("n_row_seq", C.c_int), ("pos", C.c_void_p), ("bias_lut", C.c_void_p),
+                ("cos_t", C.c_void_p), ("sin_t", C.c_void_p), ("max_pos", C.c_int), ("qkv_bias", C.c_void_p),
+                ("out", C.c_void_p), ("out_rows", C.c_int64), ("out_all", C.c_void_p), ("cache", C.c_void_p), ("cache_all", C.c_void_p),
+                ("plan_only", C.c_int), ("out_kind", C.c_int), ("out_tparam", C.c_int), ("out_grid", C.c_int * 3), ("out_grid2", C.c_int * 3)] + \
+               [(n, C.c_int) for n in ("out_lds", "out_staged", "out_mfma", "out_part", "out_R", "out_nch", "out_skip_long",
+                                       "out_heads_per_wg", "out_n_cu")]
+
+
 DEBUG_SENTINEL = 0xCD                      # RK_DEBUG_SENTINEL: the byte the guard bands of rk_debug_gemm_ex are filled with
 DEBUG_BAND_ROWS = 256
 GEMM_OUT_DTYPE = {0: np.float16, 1: np.float32, 2: np.float16, 3: np.float16, 4: np.float32, 5: np.float16, 6: np.float32, 7: np.float32}
@@ -107,6 +121,7 @@ ABI = {
     "rk_rel_bucket": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "rk_debug_gemm": (C.c_int, [C.c_void_p, _P(C.c_uint16), _P(C.c_uint16), _f32p, C.c_int, C.c_int, C.c_int, C.c_int]),
     "rk_debug_gemm_ex": (C.c_int, [C.c_void_p, _P(RkDebugGemmCall)]),
+    "rk_debug_attn": (C.c_int, [C.c_void_p, _P(RkDebugAttnCall)]),
     "rk_debug_gemm_bench": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _f32p]),
     "rk_debug_read": (C.c_int64, [C.c_void_p, C.c_char_p, _f32p, C.c_int64]),
 }
@@ -473,6 +488,72 @@ class RkEngine:
         if producer:
             out.update(xraw=xraw, ssq=ssq[:rows_all * q.out_nb].reshape(rows_all, q.out_nb))
         return out
+
+    def debug_attn(self, kind: int, *, n_seq: int, H: int, q=None, out=None, kv=None, band_rows=8, n_kv=0, Ld=0, cross=False, M=0, row0=0,
+                   d=0, P=0, ldq=0, ldkv=0, ldctx=0, k_col=0, v_col=0, seq_off=None, row_off=None, tree_keys=None, tree_pos=None,
+                   row_seq=None, pos=None, bias_lut=None, cos=None, sin=None, qkv_bias=None, cache=None, plan_only=False) -> dict:
+        """One attention call through rk_debug_attn (include/rk_engine.h).  q / kv: 2-D fp16 [band_rows + rows + band_rows, ld], the
+        WHOLE allocation with the caller's bands; out: 2-D fp16 [rows, ldctx], the pre-filled interior; cache (kind 5): flat fp16, K then
+        V.  Returns the plan fields and, unless plan_only, "out" [band_rows + rows + band_rows, ldctx] and "cache" (flat, with bands
+        of band_rows * 128 elements): the whole device allocations after the call."""
+        c = RkDebugAttnCall()
+        c.kind, c.n_seq, c.H, c.n_kv, c.Ld, c.cross, c.M, c.row0, c.d, c.P = kind, n_seq, H, n_kv, Ld, int(cross), M, row0, d, P
+        c.ldq, c.ldkv, c.ldctx, c.k_col, c.v_col, c.band_rows, c.plan_only = ldq, ldkv, ldctx, k_col, v_col, band_rows, int(plan_only)
+        keep = []
+
+        def put(field, a, dt):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dtype=dt)
+            keep.append(a)
+            setattr(c, field, a.ctypes.data)
+            return a
+
+        if q is not None:
+            q = put("q", q, np.float16)
+            assert q.ndim == 2 and q.shape[1] == ldq and q.shape[0] >= 2 * band_rows
+            c.q_rows = q.shape[0] - 2 * band_rows
+        if kv is not None:
+            kv = put("kv", kv, np.float16)
+            assert kv.ndim == 2 and kv.shape[1] == ldkv and kv.shape[0] >= 2 * band_rows
+            c.kv_rows = kv.shape[0] - 2 * band_rows
+        for name, a in (("seq_off", seq_off), ("row_off", row_off), ("tree_keys", tree_keys), ("tree_pos", tree_pos), ("row_seq", row_seq), ("pos", pos)):
+            a = put(name, a, np.int32)
+            if a is not None:
+                assert a.size >= {"seq_off": n_seq + 1, "row_off": n_seq + 1, "pos": n_seq}.get(name, 0)
+                if name == "tree_pos":
+                    c.tree_rows = a.size
+                    assert tree_keys is not None and np.asarray(tree_keys).size == a.size * Ld
+                if name == "row_seq":
+                    c.n_row_seq = a.size
+        if bias_lut is not None:
+            assert put("bias_lut", bias_lut, np.float32).shape == (H, 257)
+        if cos is not None:
+            cos, sin = put("cos_t", cos, np.float32), put("sin_t", sin, np.float32)
+            assert cos.ndim == 2 and cos.shape[1] == 64 and sin.shape == cos.shape
+            c.max_pos = cos.shape[0]
+        if qkv_bias is not None:
+            assert put("qkv_bias", qkv_bias, np.float32).size == (H + 2 * n_kv) * 128
+        out_all = cache_all = None
+        if out is not None:
+            out = put("out", out, np.float16)
+            assert out.ndim == 2 and out.shape[1] == ldctx
+            c.out_rows = out.shape[0]
+            out_all = put("out_all", np.zeros((out.shape[0] + 2 * band_rows, ldctx)), np.float16)
+        if cache is not None:
+            cache = put("cache", cache, np.float16).reshape(-1)
+            assert cache.size == 2 * n_seq * n_kv * P * 128
+            cache_all = put("cache_all", np.zeros(cache.size + 2 * band_rows * 128), np.float16)
+        self._chk(self.lib.rk_debug_attn(self.h, C.byref(c)))
+        del keep
+        res = {}
+        for k, _ in RkDebugAttnCall._fields_:
+            if k.startswith("out_") and k != "out_all" and k != "out_rows":
+                v = getattr(c, k)
+                res[k[4:]] = v if isinstance(v, int) else tuple(v)
+        if not plan_only:
+            res.update(out=out_all, cache=cache_all)
+        return res
 
     def debug_read(self, name: str, n_floats: int) -> np.ndarray:
         out = np.empty(n_floats, dtype=np.float32)
