@@ -112,6 +112,18 @@ int rk_t5_generate(rk_engine* e, const int32_t* tokens, const int32_t* seq_offse
                    const int32_t* dec_prefix, int dec_len, int max_new, int eos_id, int pad_id,
                    int32_t* out_tokens, int32_t* out_steps);
 
+/* The duoT5 compare (ref: llmrankers/pairwise.py:296-352): 2 * n_pairs sequences, pair p = sequences 2p (the A/B prompt) and
+ * 2p + 1 (the B/A prompt); one decoder position holding dec_start_id; the logits of false_id / true_id, the two-way softmax and
+ * the strict verdict P(true)[2p] > P(true)[2p + 1] are taken on the device (pair_verdict_kernel).  out_logits[2 n_pairs][2] =
+ * (false, true) are bit for bit rk_t5_score's with dec_prefix = {dec_start_id}, out_token_ids = {false_id, true_id}; out_p_true
+ * [2 n_pairs]; out_first_wins[n_pairs] = 1 / 0 (a tie is 0).  A pair's seven floats do not depend on what shares its call.
+ * RK_ERR_INVALID for n_pairs <= 0, an id outside the vocabulary or false_id == true_id; RK_ERR_STATE on a Llama engine; the
+ * capacity errors of rk_t5_score; nothing is launched after any of them.
+ * replaces: self.llm(input_ids, attention_mask, decoder_input_ids).logits[:, 0, [6136, 1176]] + softmax + compare (pairwise.py:330-343) */
+int rk_t5_compare(rk_engine* e, const int32_t* tokens, const int32_t* seq_offsets, int n_pairs,
+                  int dec_start_id, int false_id, int true_id,
+                  float* out_logits, float* out_p_true, int32_t* out_first_wins);
+
 /* ---- staged / asynchronous form: inputs resident in HBM, used by bench.py and the multi-GPU driver ---- */
 int rk_t5_stage(rk_engine* e, const int32_t* tokens, const int32_t* seq_offsets, int n_seq);   /* H2D, synchronous */
 /* enqueue encoder + decoder + head on the engine stream for the staged batch; scores land in an engine-owned
@@ -126,6 +138,12 @@ int rk_engine_num_slots(void);
 int rk_t5_stage_slot(rk_engine* e, int slot, const int32_t* tokens, const int32_t* seq_offsets, int n_seq);
 int rk_t5_score_slot(rk_engine* e, int slot, const int32_t* dec_prefix, int dec_len, const int32_t* out_token_ids, int n_out);
 int rk_t5_read_scores_slot(rk_engine* e, int slot, float* out_logits, int n_floats);
+/* rk_t5_score_slot's twin for the duoT5 compare: after rk_t5_stage_slot of 2 * n_pairs sequences (an odd count: RK_ERR_INVALID;
+ * no staged batch: RK_ERR_STATE).  The slot's score buffer then holds 7 * n_pairs floats, read whole by
+ * rk_t5_read_scores_slot(e, slot, out, 7 * n_pairs): [0, 4 n_pairs) the logits [n_seq][2] = (false, true) - rk_t5_score_slot's
+ * place and layout, so the rk_comm_* calls work behind it -, [4 n_pairs, 6 n_pairs) P(true) per sequence, [6 n_pairs, 7 n_pairs)
+ * the verdict per pair as 1.0f / 0.0f. */
+int rk_t5_compare_slot(rk_engine* e, int slot, int dec_start_id, int false_id, int true_id);
 /* device address of the fp32 score buffer [n_seq][n_out] of the last rk_t5_score_staged (for RCCL gathers) */
 int rk_t5_scores_device_ptr(rk_engine* e, void** out_ptr);
 

@@ -1,4 +1,4 @@
-// HBM-bound helper kernels (embedding gather, RMSNorm, head rows, argmax, cross-entropy) for gfx950.
+// HBM-bound helper kernels (embedding gather, RMSNorm, head rows, pair verdict, argmax, cross-entropy) for gfx950.
 // One wave (64 lanes) per row, 16-byte vector accesses, shuffle reductions.
 #pragma once
 #include "common.h"
@@ -83,6 +83,19 @@ __global__ __launch_bounds__(256) void rmsnorm_kernel(const float* __restrict__ 
   }
 }
 
+// dot(x row, head row) by one wave: 8 halves per lane and 512-column step, eight sequential fp32 adds per step, then the
+// wave's butterfly sum.  The one order of additions behind every label logit (head_rows_kernel, pair_verdict_kernel).
+__device__ __forceinline__ float head_row_dot(const half_t* __restrict__ xr, const half_t* __restrict__ hr, int d, int lane) {
+  float s = 0.f;
+  for (int c = lane * 8; c < d; c += 512) {
+    const half8 a = *(const half8*)(xr + c);
+    const half8 w = *(const half8*)(hr + c);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) s += (float)a[e] * (float)w[e];
+  }
+  return wave_sum(s);
+}
+
 // Final-token logit extraction for the label / yes-no rows only (hf: modeling_t5.py:1044-1047 lm_head, but
 // just the n_out vocabulary rows the rankers read: ref pointwise.py:120-121, setwise.py:186).
 // out[b][j] = dot(x[b], head[out_ids[j]]); one wave per (b, j).
@@ -93,17 +106,41 @@ __global__ __launch_bounds__(256) void head_rows_kernel(const half_t* __restrict
   const int lane = threadIdx.x & 63;
   if (idx >= n_seq * n_out) return;
   const int b = idx / n_out, j = idx % n_out;
-  const half_t* xr = x + (size_t)b * d;
-  const half_t* hr = head + (size_t)out_ids[j] * d;
-  float s = 0.f;
-  for (int c = lane * 8; c < d; c += 512) {
-    const half8 a = *(const half8*)(xr + c);
-    const half8 w = *(const half8*)(hr + c);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) s += (float)a[e] * (float)w[e];
-  }
-  s = wave_sum(s);
+  const float s = head_row_dot(x + (size_t)b * d, head + (size_t)out_ids[j] * d, d, lane);
   if (lane == 0) out[idx] = s;
+}
+
+// The tail of a duoT5 compare (ref: llmrankers/pairwise.py:330-343) on the device: pair p = sequences 2p (the A/B prompt) and
+// 2p + 1 (the B/A prompt).  One workgroup per pair; wave w computes the logit of sequence 2p + (w >> 1) for the id `false`
+// (w even) or `true` (w odd) with head_rows_kernel's own dot product, so the logits are the ones rk_t5_score gives bit for
+// bit.  The four sums meet in LDS and one thread takes, per ordering, the max-subtracted two-way softmax (torch's and
+// _softmax_first's form; expf and IEEE division, no fast-math intrinsic) and the strict verdict P(true)[0] > P(true)[1].
+// out: [0, 2 n_seq) logits [n_seq][2] = (false, true), rk_t5_score's place and layout for out ids {false, true};
+//      [2 n_seq, 3 n_seq) P(true) per sequence;  [3 n_seq, 3 n_seq + n_seq / 2) the verdict per pair as 1.0f / 0.0f.
+__global__ __launch_bounds__(256) void pair_verdict_kernel(const half_t* __restrict__ x, const half_t* __restrict__ head,
+                                                           int false_id, int true_id, float* __restrict__ out,
+                                                           int n_seq, int d) {
+  __shared__ float sums[4];   // (false, true) logits of sequence 2p, then of 2p + 1
+  const int p = blockIdx.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  if (2 * p + 1 >= n_seq) return;                      // (uniform per workgroup: no barrier is skipped by part of one)
+  const int b = 2 * p + (wave >> 1);
+  const float s = head_row_dot(x + (size_t)b * d, head + (size_t)((wave & 1) ? true_id : false_id) * d, d, lane);
+  if (lane == 0) sums[wave] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float pt[2];
+#pragma unroll
+    for (int o = 0; o < 2; ++o) {
+      const float f = sums[2 * o], t = sums[2 * o + 1];
+      const float m = fmaxf(f, t);
+      const float ef = expf(f - m), et = expf(t - m);
+      pt[o] = et / (ef + et);
+      out[(size_t)(2 * p + o) * 2] = f;
+      out[(size_t)(2 * p + o) * 2 + 1] = t;
+      out[(size_t)2 * n_seq + 2 * p + o] = pt[o];
+    }
+    out[(size_t)3 * n_seq + p] = pt[0] > pt[1] ? 1.0f : 0.0f;
+  }
 }
 
 // Greedy decoding step, second half of the fused head: the weight-streaming head GEMM (EPI_ARGMAX_F32) left, per 32-column

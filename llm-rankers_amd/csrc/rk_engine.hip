@@ -138,7 +138,7 @@ struct Slot {
   NormStream enc;                                              // the encoder's residual stream (Llama: the prefill's)
   half_t *qkv = nullptr, *ctx = nullptr, *ffh = nullptr, *enc_out = nullptr;
   int* d_tokens = nullptr; int* d_seq_off = nullptr;
-  int n_seq = 0, T = 0, maxL = 0, minL = 0; bool staged = false; int last_n_out = 0;
+  int n_seq = 0, T = 0, maxL = 0, minL = 0; bool staged = false; int last_floats = 0;   // what the slot's last score / compare call left in its score buffer
   half_t* cross_kv = nullptr;                                  // [n_dec][max_tokens][2I] encoder -> decoder hand-off
   DecIndex idx; int* d_argmax = nullptr;                       // decoder ids, row maps, labels (see DecIndex) | the greedy head's result
   NormStream dec;                                              // the decoder's (run_decoder); rk_t5_qlm's final norm writes dec.xn
@@ -1373,7 +1373,7 @@ int stage_slot(rk_engine* e, int slot, const int32_t* tokens, const int32_t* seq
 // dependent-kernel boundary (1-2 us).  `body` enqueues the chain on `st`; the second time a key is seen the chain is
 // captured, instantiated and cached, from then on it is replayed.  The key holds every value the launch parameters
 // depend on (shapes, options epoch); buffers are per-slot and never move.  Profiling runs stay eager (per-kernel events).
-enum GraphKind { GK_T5_SCORE, GK_T5_GREEDY_STEP, GK_T5_GREEDY2, GK_T5_GENERATE_STEP, GK_LLAMA_STEP };   // which chain: the key's first int
+enum GraphKind { GK_T5_SCORE, GK_T5_GREEDY_STEP, GK_T5_GREEDY2, GK_T5_GENERATE_STEP, GK_LLAMA_STEP, GK_T5_COMPARE };   // which chain: the key's first int
 template <class F>
 int run_graphed(rk_engine* e, hipStream_t st, std::vector<int> key, F&& body) {
   key.push_back(e->opt_epoch);
@@ -1477,7 +1477,43 @@ int score_slot(rk_engine* e, int slot, const int32_t* dec_prefix, int dec_len, c
   if (rc) return rc;
   HIPCHK(e, hipMemcpyAsync(sl.h_scores, sl.d_scores, (size_t)sl.n_seq * n_out * sizeof(float), hipMemcpyDeviceToHost, sd));
   HIPCHK(e, hipGetLastError());
-  sl.last_n_out = n_out;
+  sl.last_floats = sl.n_seq * n_out;
+  return mark_decoder_done(e, sl);
+}
+
+// score_slot's twin for the duoT5 compare: the staged batch is pairs of sequences (2p, 2p + 1), the decoder has one position,
+// and pair_verdict_kernel takes the place of head_rows_kernel: logits, P(true) and verdicts in the slot's score buffer.
+int compare_slot(rk_engine* e, int slot, int dec_start_id, int false_id, int true_id) {
+  if (slot < 0 || slot >= RK_SLOTS) return fail(e, RK_ERR_INVALID, "slot %d out of range", slot);
+  if (e->family != 0) return fail(e, RK_ERR_STATE, "T5 entry point called on a Llama engine (use rk_llama_*)");
+  int rc = set_device(e);
+  if (rc) return rc;
+  Slot& sl = e->slots[slot];
+  if (!sl.staged) return fail(e, RK_ERR_STATE, "no staged batch in slot %d", slot);
+  if (sl.n_seq % 2) return fail(e, RK_ERR_INVALID, "a compare needs pairs of sequences (staged n_seq = %d)", sl.n_seq);
+  const int32_t out_ids[2] = {false_id, true_id};
+  if ((rc = check_ids(e, &dec_start_id, 1, "decoder")) || (rc = check_ids(e, out_ids, 2, "output"))) return rc;
+  if (false_id == true_id) return fail(e, RK_ERR_INVALID, "false_id and true_id are the same id %d", false_id);
+  hipStream_t sd = dec_stream(e, sl);
+  if ((rc = put_dec_ids_shared(e, sl, &dec_start_id, 1))) return rc;
+  std::vector<int> rows(sl.n_seq);
+  for (int b = 0; b < sl.n_seq; ++b) rows[b] = b;
+  if ((rc = sl.idx.put(e, sd, IX_LAST_ROWS, rows.data(), sl.n_seq))) return rc;
+  if ((rc = encoder_then_handoff(e, sl, 1))) return rc;
+  rc = run_graphed(e, sd, {GK_T5_COMPARE, slot, sl.n_seq, sl.have_cross_kv ? sl.maxL : (sl.maxL + 63) / 64, (int)sl.have_cross_kv, false_id, true_id}, [&]() -> int {
+    int r = RK_OK;
+    if ((r = run_decoder(e, sl, 1))) return r;
+    rmsnorm(e, sd, sl.dec.hidden, e->dec_final_ln, sl.dlast, sl.idx.d[IX_LAST_ROWS], sl.n_seq, head_scale(e));
+    Bracket br(e, sd, PC_HEAD, 2.0 * sl.n_seq * 2 * e->d.d_model, 0);
+    hipLaunchKernelGGL(pair_verdict_kernel, dim3(sl.n_seq / 2), dim3(256), 0, sd, sl.dlast, e->lm_head, false_id, true_id,
+                       sl.d_scores, sl.n_seq, e->d.d_model);
+    return RK_OK;
+  });
+  if (rc) return rc;
+  const int n_floats = 3 * sl.n_seq + sl.n_seq / 2;
+  HIPCHK(e, hipMemcpyAsync(sl.h_scores, sl.d_scores, (size_t)n_floats * sizeof(float), hipMemcpyDeviceToHost, sd));
+  HIPCHK(e, hipGetLastError());
+  sl.last_floats = n_floats;
   return mark_decoder_done(e, sl);
 }
 
@@ -1859,7 +1895,8 @@ int rk_engine_finalize(rk_engine* e) {
 
   // workspaces, sized once for the 288 GB part: nothing is allocated on the hot path afterwards
   const size_t Tc = d.max_tokens, Bc = d.max_seqs, Mc = (size_t)d.max_seqs * d.max_dec_len;
-  e->scores_cap = Bc * 64;
+  e->scores_cap = Bc * 64;                                  // rk_t5_score: n_out <= 64 floats per sequence; rk_t5_compare: 3.5
+  if (2 * e->scores_cap < 7 * Bc) return fail(e, RK_ERR_CAPACITY, "score buffer of %zu floats cannot hold a compare of %zu sequences", e->scores_cap, Bc);
   for (Slot& sl : e->slots) {
     RC(dalloc(e, &sl.enc.hidden, Tc * dm)); RC(dalloc(e, &sl.enc.xn, Tc * dm)); RC(dalloc(e, &sl.qkv, Tc * 3 * I));
     RC(dalloc(e, &sl.ctx, Tc * I)); RC(dalloc(e, &sl.ffh, Tc * F)); RC(dalloc(e, &sl.enc_out, Tc * dm));
@@ -1922,7 +1959,7 @@ int rk_engine_sync(rk_engine* e) {
 int rk_t5_read_scores_slot(rk_engine* e, int slot, float* out_logits, int n_floats) {
   if (!e || !out_logits || slot < 0 || slot >= RK_SLOTS) return RK_ERR_INVALID;
   Slot& sl = e->slots[slot];
-  if (n_floats > sl.n_seq * sl.last_n_out) return fail(e, RK_ERR_INVALID, "asked for %d floats, have %d", n_floats, sl.n_seq * sl.last_n_out);
+  if (n_floats > sl.last_floats) return fail(e, RK_ERR_INVALID, "asked for %d floats, have %d", n_floats, sl.last_floats);
   if (sl.dec_pending) { HIPCHK(e, hipEventSynchronize(sl.ev_dec)); sl.dec_pending = false; }
   memcpy(out_logits, sl.h_scores, (size_t)n_floats * sizeof(float));
   return RK_OK;
@@ -1943,6 +1980,27 @@ int rk_t5_score(rk_engine* e, const int32_t* tokens, const int32_t* seq_offsets,
   if ((rc = rk_t5_stage(e, tokens, seq_offsets, n_seq))) return rc;
   if ((rc = rk_t5_score_staged(e, dec_prefix, dec_len, out_token_ids, n_out))) return rc;
   return rk_t5_read_scores(e, out_logits, n_seq * n_out);
+}
+
+int rk_t5_compare_slot(rk_engine* e, int slot, int dec_start_id, int false_id, int true_id) {
+  if (!e) return RK_ERR_INVALID;
+  return compare_slot(e, slot, dec_start_id, false_id, true_id);
+}
+
+int rk_t5_compare(rk_engine* e, const int32_t* tokens, const int32_t* seq_offsets, int n_pairs, int dec_start_id, int false_id,
+                  int true_id, float* out_logits, float* out_p_true, int32_t* out_first_wins) {
+  if (!e) return RK_ERR_INVALID;
+  if (n_pairs <= 0 || n_pairs > (1 << 28) || !out_logits || !out_p_true || !out_first_wins) return fail(e, RK_ERR_INVALID, "empty compare (n_pairs=%d)", n_pairs);
+  const int n_seq = 2 * n_pairs;
+  int rc;
+  if ((rc = rk_t5_stage(e, tokens, seq_offsets, n_seq))) return rc;
+  if ((rc = rk_t5_compare_slot(e, 0, dec_start_id, false_id, true_id))) return rc;
+  std::vector<float> res((size_t)7 * n_pairs);
+  if ((rc = rk_t5_read_scores(e, res.data(), 7 * n_pairs))) return rc;
+  memcpy(out_logits, res.data(), (size_t)2 * n_seq * sizeof(float));
+  memcpy(out_p_true, res.data() + (size_t)2 * n_seq, (size_t)n_seq * sizeof(float));
+  for (int p = 0; p < n_pairs; ++p) out_first_wins[p] = res[(size_t)3 * n_seq + p] != 0.f;
+  return RK_OK;
 }
 
 // One decoder pass of a qlm call over the sequences s0 .. s0 + n_seq - 1 of the staged batch: `rows` rows from row r0 of

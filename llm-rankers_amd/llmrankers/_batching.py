@@ -224,11 +224,18 @@ def default_queries_per_call(kind: str, hits: int) -> int:
     that still fits ONE engine call of either runtime: 25k tokens of T5Runtime's 49k, the 16 sequences of LlamaRuntime); listwise:
     thirty-two sliding-window walks in lockstep (tools/bench_listwise.py, profiles/listwise_bench.jsonl: flan-t5-large dims,
     100 passages of ~100 tokens, window 4 / step 2: 1 / 8 / 32 queries = 2 150 / 320 / 120 ms per query `generation`, 185 / 42.2 /
-    23.5 ms `likelihood`); anything else one query at a time."""
+    23.5 ms `likelihood`); duot5: thirty-two binary heapsorts in lockstep (tools/bench_duot5.py, profiles/duot5_bench.txt: duot5-base dims,
+    100 passages of ~100 tokens, k = 10, ~265-token prompts: one compare per score call 415 ms per query, rerank with the device
+    verdict and the level-batched build 205 ms, rerank_many at 4 / 8 / 16 / 32 queries = 75.7 / 54.4 / 48.7 / 44.3 ms per query - the
+    smallest count of the sweep within 3 % of its best is the largest one.  Thirty-two = two alternating groups of sixteen pairs
+    per sift-down step: 32 prompts, 16k tokens at 512-token prompts, inside ONE engine call of T5Runtime's 256 prompts / 49k
+    tokens); anything else, PRP pairwise included, one query at a time."""
     if kind == "pointwise":
         return max(1, min(16, -(-1600 // max(1, int(hits)))))
     if kind == "setwise":
         return 32
     if kind == "listwise":
+        return 32
+    if kind == "duot5":
         return 32
     return 1

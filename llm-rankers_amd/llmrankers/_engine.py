@@ -77,6 +77,7 @@ ABI = {
     "rk_engine_load_tensor": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int, _P(C.c_int64), C.c_int]),
     "rk_engine_finalize": (C.c_int, [C.c_void_p]),
     "rk_t5_score": (C.c_int, [C.c_void_p, _i32p, _i32p, C.c_int, _i32p, C.c_int, _i32p, C.c_int, _f32p]),
+    "rk_t5_compare": (C.c_int, [C.c_void_p, _i32p, _i32p, C.c_int, C.c_int, C.c_int, C.c_int, _f32p, _f32p, _i32p]),
     "rk_t5_qlm": (C.c_int, [C.c_void_p, _i32p, _i32p, C.c_int, _i32p, C.c_int, _f32p]),
     "rk_t5_qlm_many": (C.c_int, [C.c_void_p, _i32p, _i32p, C.c_int, _i32p, _i32p, _f32p]),
     "rk_t5_greedy": (C.c_int, [C.c_void_p, _i32p, _i32p, C.c_int, _i32p, C.c_int, C.c_int, C.c_int, C.c_int, _i32p, _i32p]),
@@ -88,6 +89,7 @@ ABI = {
     "rk_engine_num_slots": (C.c_int, []),
     "rk_t5_stage_slot": (C.c_int, [C.c_void_p, C.c_int, _i32p, _i32p, C.c_int]),
     "rk_t5_score_slot": (C.c_int, [C.c_void_p, C.c_int, _i32p, C.c_int, _i32p, C.c_int]),
+    "rk_t5_compare_slot": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]),
     "rk_t5_read_scores_slot": (C.c_int, [C.c_void_p, C.c_int, _f32p, C.c_int]),
     "rk_t5_read_scores": (C.c_int, [C.c_void_p, _f32p, C.c_int]),
     "rk_t5_scores_device_ptr": (C.c_int, [C.c_void_p, _P(C.c_void_p)]),
@@ -239,6 +241,19 @@ class RkEngine:
                                        out.ctypes.data_as(_f32p)))
         return out
 
+    def compare_pairs(self, seqs: Sequence[Sequence[int]], dec_start: int, false_id: int, true_id: int):
+        """The duoT5 compare (rk_t5_compare): seqs = 2n sequences, pair p = (seqs[2p], seqs[2p + 1]) = the A/B and the B/A prompt.
+        -> (logits [2n, 2] = (false, true), p_true [2n], first_wins [n] bool), softmax and verdict taken on the device."""
+        if len(seqs) % 2:
+            raise ValueError(f"a compare needs pairs of sequences (got {len(seqs)})")
+        tok, off = pack_ragged(seqs)
+        n = len(seqs) // 2
+        logits, p_true, wins = np.empty((2 * n, 2), np.float32), np.empty(2 * n, np.float32), np.empty(n, np.int32)
+        self._chk(self.lib.rk_t5_compare(self.h, tok.ctypes.data_as(_i32p), off.ctypes.data_as(_i32p), n, int(dec_start),
+                                         int(false_id), int(true_id), logits.ctypes.data_as(_f32p), p_true.ctypes.data_as(_f32p),
+                                         wins.ctypes.data_as(_i32p)))
+        return logits, p_true, wins != 0
+
     def qlm(self, seqs: Sequence[Sequence[int]], labels: Sequence[int]) -> np.ndarray:
         tok, off = pack_ragged(seqs)
         lab = _i32(labels)
@@ -308,11 +323,21 @@ class RkEngine:
         self._slot_shape[slot][1] = len(oi)
         self._chk(self.lib.rk_t5_score_slot(self.h, slot, dp.ctypes.data_as(_i32p), len(dp), oi.ctypes.data_as(_i32p), len(oi)))
 
+    def compare_staged(self, dec_start: int, false_id: int, true_id: int, slot: int = 0):
+        """score_staged's twin for the duoT5 compare (rk_t5_compare_slot) over the slot's staged pairs; `read_scores` then gives
+        compare_pairs' triple."""
+        self._slot_shape[slot][1] = None
+        self._chk(self.lib.rk_t5_compare_slot(self.h, slot, int(dec_start), int(false_id), int(true_id)))
+
     def sync(self):
         self._chk(self.lib.rk_engine_sync(self.h))
 
-    def read_scores(self, slot: int = 0) -> np.ndarray:
+    def read_scores(self, slot: int = 0):
         n, k = self._slot_shape[slot]
+        if k is None:                    # a compare: logits [n, 2], P(true) [n], verdicts [n / 2] in one buffer of 3.5 n floats
+            out = np.empty(3 * n + n // 2, dtype=np.float32)
+            self._chk(self.lib.rk_t5_read_scores_slot(self.h, slot, out.ctypes.data_as(_f32p), out.size))
+            return out[:2 * n].reshape(n, 2).copy(), out[2 * n:3 * n].copy(), out[3 * n:] != 0
         out = np.empty((n, k), dtype=np.float32)
         self._chk(self.lib.rk_t5_read_scores_slot(self.h, slot, out.ctypes.data_as(_f32p), out.size))
         return out

@@ -388,6 +388,49 @@ class T5Runtime:
         """[n, len(out_ids)] scores of the call score_async enqueued (waits for it)."""
         return self.engine.read_scores(handle)
 
+    # -- the duoT5 compare: pairs of sequences (the A/B and the B/A prompt), softmax and verdict on the device -----------------
+    supports_compare_pairs = True
+
+    def _pair_chunks(self, seqs) -> Iterator[List[Sequence[int]]]:
+        """`_chunks` with a PAIR as the unit: the same greedy cut by max_seqs / max_tokens, never between the two orderings."""
+        if len(seqs) % 2:
+            raise ValueError(f"a compare needs pairs of sequences (got {len(seqs)})")
+        if self.max_seqs < 2:
+            raise ValueError(f"a pair of prompts exceeds the engine capacity of {self.max_seqs} sequence")
+        cur, tok = [], 0
+        for p in range(0, len(seqs), 2):
+            n = len(seqs[p]) + len(seqs[p + 1])
+            if n > self.max_tokens:
+                raise ValueError(f"a pair of prompts of {n} tokens exceeds the engine capacity {self.max_tokens}")
+            if cur and (tok + n > self.max_tokens or len(cur) + 2 > self.max_seqs):
+                yield cur
+                cur, tok = [], 0
+            cur += [seqs[p], seqs[p + 1]]
+            tok += n
+        if cur:
+            yield cur
+
+    def compare_pairs(self, seqs, dec_start, false_id, true_id):
+        """(logits [2n, 2], p_true [2n], first_wins [n] bool) of the n pairs (seqs[2p], seqs[2p + 1]): RkEngine.compare_pairs, cut
+        into engine calls of whole pairs.  A pair's figures do not depend on what shares its call."""
+        parts = [self.engine.compare_pairs(c, dec_start, false_id, true_id) for c in self._pair_chunks(seqs)]
+        if not parts:
+            return np.zeros((0, 2), np.float32), np.zeros(0, np.float32), np.zeros(0, bool)
+        return tuple(np.concatenate([p[i] for p in parts], axis=0) for i in range(3))
+
+    def compare_async(self, seqs, dec_start, false_id, true_id, slot: int):
+        """score_async's twin: ONE compare call for the pairs in `seqs` enqueued on batch slot `slot` -> a handle for
+        compare_collect, or None when they do not fit one call (the caller then uses compare_pairs, which cuts them)."""
+        if not (0 < len(seqs) <= self.max_seqs and len(seqs) % 2 == 0 and sum(len(s) for s in seqs) <= self.max_tokens):
+            return None
+        self.engine.stage(seqs, slot=slot)
+        self.engine.compare_staged(dec_start, false_id, true_id, slot=slot)
+        return slot
+
+    def compare_collect(self, handle):
+        """compare_pairs' triple of the call compare_async enqueued (waits for it)."""
+        return self.engine.read_scores(handle)
+
     def qlm(self, seqs, labels) -> np.ndarray:
         return np.concatenate([self.engine.qlm(c, labels) for c in self._chunks(seqs)], axis=0)
 

@@ -9,6 +9,10 @@ once (the reference's batch_size only shapes its host loop and the padded-shape 
 Llama-family checkpoints (ref: pairwise.py:60-77, 104-129) take the decoder-only path of the setwise ranker: chat-template
 prompt + " Passage:", prefill and ONE greedy token per ordering (rk_llama_greedy1), outputs "Passage <token>"; `allpair`
 is T5-only there too (it reads `self.decoder_input_ids`, which the reference only sets for T5: AttributeError).
+
+DuoT5LlmRanker (ref: llmrankers/pairwise.py:296-352) is the monoT5-style pairwise ranker: both orderings of a pair through the
+model at one decoder position, softmax over the logits of `false` / `true`, the first passage wins iff its P(true) is strictly
+larger.  The whole tail of a compare runs on the device (rk_t5_compare), and heapsorts of several queries advance in lock step.
 """
 from itertools import combinations
 from typing import List
@@ -16,6 +20,8 @@ from typing import List
 import numpy as np
 
 from ._batching import batches, padded_token_count, tokenize_prompts
+from ._lockstep import Lockstep
+from .pointwise import _softmax_first
 from .rankers import LlmRanker, SearchResult, top_k_then_rest
 
 PROMPT = ('Given a query "{query}", which of the following two passages is more relevant to the query?\n\n'
@@ -203,3 +209,257 @@ class PairwiseLlmRanker(LlmRanker):
 
     def truncate(self, text, length):
         return self.tokenizer.convert_tokens_to_string(self.tokenizer.tokenize(text)[:length])
+
+
+DUO_PROMPT = 'Query: {query} Document0: {doc1} Document1: {doc2} Relevant:'
+HF_NO_LIMIT = int(1e20)      # transformers' LARGE_INTEGER: a model_max_length above it means "no limit", nothing is truncated
+
+
+class DuoT5LlmRanker(PairwiseLlmRanker):
+    """duoT5 (ref: llmrankers/pairwise.py:296-352): heapsort over "is document 0 more relevant than document 1" compares.  One
+    compare = the A/B and the B/A prompt at ONE decoder position (decoder_start_token_id), softmax over the logits of `false` /
+    `true` per ordering, verdict P(true)[A/B] > P(true)[B/A] - strict, a tie is False.  On the engine the logits, the softmax and
+    the verdict of every pair of a call come from the device (T5Runtime.compare_pairs, rk_t5_compare); a runtime without it gives
+    the four logits through `score` and the softmax runs on the host.  Same constructor, counters (completion tokens stay 0) and
+    result assembly as the reference; the caller's list is not reordered."""
+    FALSE_ID, TRUE_ID = 6136, 1176            # the ids of "false" / "true" in the T5 vocabulary (ref :314-315)
+    fp16_scores = False                       # True: the host verdict from the returned logits, rounded as the reference's fp16 model does
+
+    def _setup(self, runtime, tokenizer, device, method, batch_size, k):
+        super()._setup(runtime, tokenizer, device, method, batch_size, k)
+        if self.model_type != "t5":
+            raise NotImplementedError(f"Model type {self.model_type} is not supported yet for duoT5 :(")
+        # heapsort build phase: the independent sift-downs of a tree level share an engine call (same array, set of compares and
+        # counters as the reference's one-by-one order)
+        self.batch_independent_compares = True
+
+    # -- the model call ------------------------------------------------------------------------------------------
+    def _pair_ids(self, queries, pairs) -> List[List[int]]:
+        """Token ids of the two prompts of every (a_text, b_text) pair, A/B then B/A: tokenizer(inputs, truncation=True) - each
+        sequence cut to tokenizer.model_max_length with the EOS kept (ref :303; 512 for the published duoT5 tokenizers), nothing
+        cut when the tokenizer carries transformers' "no limit" value."""
+        texts = []
+        for q, (a, b) in zip(queries, pairs):
+            texts.append(DUO_PROMPT.format(query=q, doc1=a, doc2=b))
+            texts.append(DUO_PROMPT.format(query=q, doc1=b, doc2=a))
+        ids = tokenize_prompts(self.tokenizer, texts)
+        limit = getattr(self.tokenizer, "model_max_length", None)
+        if limit is not None and 0 < limit <= HF_NO_LIMIT:
+            limit = int(limit)
+            ids = [seq if len(seq) <= limit else seq[:limit - 1] + seq[-1:] for seq in ids]
+        return ids
+
+    def _decoder_start(self) -> int:
+        start = getattr(self.llm, "decoder_start_token_id", None)
+        if start is None:
+            start = (self.config or {}).get("decoder_start_token_id", 0)
+        return int(start)
+
+    def _verdicts(self, result) -> List[bool]:
+        """compare_pairs' triple (or bare logits [2n, 2] of a runtime without it) -> the n verdicts."""
+        if isinstance(result, tuple):
+            logits, _, wins = result
+            if not self.fp16_scores:
+                return [bool(w) for w in wins]
+        else:
+            logits = result
+        logits = np.asarray(logits, dtype=np.float32)
+        p_true = _softmax_first(logits[:, 1], logits[:, 0], self.fp16_scores)
+        return [bool(a > b) for a, b in zip(p_true[0::2], p_true[1::2])]
+
+    def _compare_pairs(self, queries, pairs):
+        """The engine call behind `compare`, for pairs that may belong to different queries -> (verdicts, prompt tokens per
+        compare); touches no counter."""
+        ids = self._pair_ids(queries, pairs)
+        prompt_tokens = [padded_token_count(ids[i:i + 2]) for i in range(0, len(ids), 2)]     # padding=True (ref :303, :308)
+        if getattr(self.llm, "supports_compare_pairs", False):
+            result = self.llm.compare_pairs(ids, self._decoder_start(), self.FALSE_ID, self.TRUE_ID)
+        else:
+            result = self.llm.score(ids, [self._decoder_start()], [self.FALSE_ID, self.TRUE_ID])
+        return self._verdicts(result), prompt_tokens
+
+    def compare(self, query: str, docs: List) -> bool:
+        # ref: pairwise.py:297-318 — docs = the two passage TEXTS
+        self.total_compare += 1
+        self.prompt = DUO_PROMPT
+        (verdict,), (prompt_tokens,) = self._compare_pairs([query], [(docs[0], docs[1])])
+        self.total_prompt_tokens += prompt_tokens
+        return verdict
+
+    # ---- the same compare, launched and collected separately (a runtime with batch slots) -------------------------
+    def _can_alternate(self) -> bool:
+        return (getattr(self, "alternate_groups", True) and hasattr(self.llm, "compare_async")
+                and getattr(getattr(self.llm, "engine", None), "num_slots", 1) >= 2)
+
+    def _launch_pairs(self, queries, pairs, slot: int):
+        """First half of `_compare_pairs`: ONE engine call enqueued on `slot`; None when the pairs do not fit one call."""
+        ids = self._pair_ids(queries, pairs)
+        handle = self.llm.compare_async(ids, self._decoder_start(), self.FALSE_ID, self.TRUE_ID, slot)
+        if handle is None:
+            return None
+        return handle, [padded_token_count(ids[i:i + 2]) for i in range(0, len(ids), 2)]
+
+    def _collect_pairs(self, launched):
+        handle, prompt_tokens = launched
+        return self._verdicts(self.llm.compare_collect(handle)), prompt_tokens
+
+    def _batched_ok(self) -> bool:
+        # sharing an engine call needs compare() to be ours (no subclass / instance override)
+        return (getattr(self, "batch_independent_compares", False) and "compare" not in self.__dict__
+                and type(self).compare is DuoT5LlmRanker.compare)
+
+    # ---- the sort: pure index logic, must reproduce the reference's comparisons exactly ----------------------------
+    # A generator that yields a list of ordered pairs (a, b) whose compares are independent and is sent their verdicts `a > b`.
+    def _sift(self, arr, n, i):
+        """Sift node i of the binary max-heap arr[:n] down (ref: pairwise.py:133-147, a loop instead of tail recursion): at most
+        two compares per level, (left, i) then (right, largest)."""
+        while True:
+            largest, left, right = i, 2 * i + 1, 2 * i + 2
+            if left < n:
+                (gt,) = yield [(arr[left], arr[i])]
+                if gt:
+                    largest = left
+            if right < n:
+                (gt,) = yield [(arr[right], arr[largest])]
+                if gt:
+                    largest = right
+            if largest == i:
+                return
+            arr[i], arr[largest] = arr[largest], arr[i]
+            i = largest
+
+    def _heapsort_steps(self, arr, k, level_batched):
+        """ref: pairwise.py:149-162.  The build phase sifts the nodes n//2 .. 0.  Reference order: one after another.  Level
+        order: that walk goes level by level from the deepest one, and the nodes of a level root disjoint subtrees, so their
+        sift-downs touch disjoint array slots and commute - they advance in lock step, one list of pairs per step: the array,
+        the set of compares and every counter end up identical, only the order of compares inside a level differs.  Extraction
+        is a chain: one compare at a time."""
+        n = len(arr)
+        if level_batched:
+            levels, first, width = [], 0, 1                   # the nodes of depth d occupy [first, first + 2^d)
+            while first <= n // 2:
+                levels.append(range(min(first + width - 1, n // 2), first - 1, -1))
+                first, width = first + width, width * 2
+            for level in reversed(levels):
+                build = Lockstep({j: self._sift(arr, n, i) for j, i in enumerate(level)})
+                while build:
+                    build.advance((yield build.pending()[1]))
+        else:
+            for i in range(n // 2, -1, -1):
+                yield from self._sift(arr, n, i)
+        ranked = 0
+        for m in range(n - 1, 0, -1):
+            arr[m], arr[0] = arr[0], arr[m]
+            ranked += 1
+            if ranked == k:
+                break
+            yield from self._sift(arr, m, 0)
+
+    def _compare_many(self, query, windows) -> List[bool]:
+        """Independent compares of one query in ONE engine call: same verdicts and counters as `compare()` on each in turn."""
+        verdicts, prompt_tokens = self._compare_pairs([query] * len(windows), [(a.text, b.text) for a, b in windows])
+        self.total_compare += len(windows)
+        self.total_prompt_tokens += sum(prompt_tokens)
+        return verdicts
+
+    def _drive(self, query, steps, level_batched):
+        """Run a sort for one query.  Reference order: every pair through `compare`, one at a time (looked up on the instance:
+        tests, golden generators and subclasses replace it); level order: every yielded list is one `_compare_many`."""
+        verdicts = None
+        while True:
+            try:
+                windows = steps.send(verdicts)
+            except StopIteration:
+                return
+            verdicts = (self._compare_many(query, windows) if level_batched
+                        else [self.compare(query, [a.text, b.text]) for a, b in windows])
+
+    def rerank(self, query: str, ranking: List[SearchResult]) -> List[SearchResult]:
+        # ref: pairwise.py:320-352.  The sort works on a new list: the caller's is left as it is.
+        original_docids = [doc.docid for doc in ranking]
+        self.total_compare = 0
+        self.total_completion_tokens = 0
+        self.total_prompt_tokens = 0
+        if self.method != "heapsort":
+            raise NotImplementedError(f'Method {self.method} is not implemented.')
+        arr = list(ranking)
+        level_batched = self._batched_ok()
+        self._drive(query, self._heapsort_steps(arr, self.k, level_batched), level_batched)
+        return top_k_then_rest(list(reversed(arr)), original_docids, self.k)
+
+    # ---- several queries at once ---------------------------------------------------------------------------
+    def rerank_many(self, items):
+        """Several queries at once: `items` = [(query, ranking), ...] -> (results, counters); results[i] and counters[i] =
+        (total_compare, total_prompt_tokens, total_completion_tokens) are exactly what `rerank(*items[i])` gives.  A query's
+        heapsort is several hundred DEPENDENT compares of two sequences each; the chains of different queries are independent, so
+        their pending compares share an engine call, one call per step of all the chains (a pair's verdict does not depend on
+        what shares its call: ragged execution, bit-exact).  With at least four live chains on a runtime with batch slots two
+        groups alternate over them, as in SetwiseLlmRanker.rerank_many; a round that does not fit one engine call takes the
+        blocking call for that round.  A replaced compare(), or fewer than two queries: one rerank per query."""
+        items = list(items)
+        if self.method != "heapsort" or not self._batched_ok() or len(items) < 2:
+            out, counters = [], []
+            for query, ranking in items:
+                out.append(self.rerank(query, ranking))
+                counters.append((self.total_compare, self.total_prompt_tokens, self.total_completion_tokens))
+            return out, counters
+        originals = [[doc.docid for doc in ranking] for _, ranking in items]
+        arrs = [list(ranking) for _, ranking in items]
+        counts = [[0, 0, 0] for _ in items]
+        chains = Lockstep({q: self._heapsort_steps(arr, self.k, True) for q, arr in enumerate(arrs)})
+
+        def call_args(keys, windows):
+            return [items[q][0] for q in keys], [(a.text, b.text) for a, b in windows]
+
+        def counted(keys, verdicts, prompt_tokens):
+            for q, p in zip(keys, prompt_tokens):
+                counts[q][0] += 1
+                counts[q][1] += p
+            return verdicts
+
+        if len(chains.live()) >= 4 and self._can_alternate():
+            # two groups of chains alternate over the engine's two batch slots: while one group's call is on the GPU the host
+            # advances the other group's heaps, tokenises its prompts and launches them
+            groups = [Lockstep({}), Lockstep({})]
+            for i, q in enumerate(chains.live()):
+                groups[i % 2].absorb(chains, [q])
+            inflight = []                                            # [(group index, keys, launched)] oldest first
+
+            def collect():
+                g, keys, launched = inflight.pop(0)
+                groups[g].advance(counted(keys, *self._collect_pairs(launched)))
+
+            try:
+                while groups[0] or groups[1]:
+                    for g in (0, 1):                                 # group g's turn: its own call is the oldest one in flight
+                        while any(entry[0] == g for entry in inflight):
+                            collect()
+                        if not groups[g]:
+                            continue
+                        keys, windows = groups[g].pending()
+                        launched = self._launch_pairs(*call_args(keys, windows), slot=g)
+                        if launched is not None:
+                            inflight.append((g, keys, launched))
+                            continue
+                        # this round does not fit one engine call (the build phase of many long heaps): the slots are drained
+                        # and it goes through the blocking call, which cuts it; the next round is launched as before
+                        while inflight:
+                            collect()
+                        groups[g].advance(counted(keys, *self._compare_pairs(*call_args(keys, windows))))
+            finally:
+                # whatever raised above: a call still queued on its slot is collected before the exception leaves -
+                # compare_async's contract is that nothing else runs on the engine until then
+                for _, _, launched in inflight:
+                    try:
+                        self._collect_pairs(launched)
+                    except Exception:
+                        pass
+            for group in groups:
+                chains.absorb(group)
+        while chains:
+            keys, windows = chains.pending()
+            chains.advance(counted(keys, *self._compare_pairs(*call_args(keys, windows))))
+        results = [top_k_then_rest(list(reversed(arr)), original, self.k) for arr, original in zip(arrs, originals)]
+        counters = [tuple(c) for c in counts]
+        self.total_compare, self.total_prompt_tokens, self.total_completion_tokens = counters[-1]
+        return results, counters

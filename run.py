@@ -7,7 +7,8 @@
 
 Same sub-commands (`run` + one of `pointwise` / `setwise`), flags, defaults, TREC run input/output and the four
 averages printed at the end (ref: run.py:198-201).  Listwise runs on T5 and on Llama checkpoints (the latter on the KV-cached
-decoder rk_llama_generate).  OpenAI rankers and duoT5 pairwise are outside the hot path this build accelerates and are rejected with a clear message.  The data back-ends
+decoder rk_llama_generate).  Pairwise runs PRP, and duoT5 for a model name
+containing `duot5` (heapsort; the compare's softmax and verdict on the device, rk_t5_compare).  OpenAI rankers are outside the hot path this build accelerates and are rejected with a clear message.  The data back-ends
 (ir_datasets / pyserini) are imported lazily; because neither exists offline, two plain-file sources are
 accepted as well:  --query_file (TSV `qid<TAB>text` or JSONL {"qid"|"query_id"|"_id", "text"|"query"}) and
 --doc_file (TSV `docid<TAB>text` or JSONL {"docid"|"doc_id"|"_id", "text"|"contents", ["title"]}).
@@ -246,10 +247,11 @@ def build_ranker(args):
         if args.pairwise.method != "allpair":                    # ref: run.py:88-90
             args.pairwise.batch_size = 2
             logger.info("Setting batch_size to 2.")
-        if args.run.openai_key or "duot5" in args.run.model_name_or_path:
-            raise NotImplementedError("OpenAI / duoT5 pairwise rankers are not part of this build; use the reference")
-        from llmrankers.pairwise import PairwiseLlmRanker
-        return PairwiseLlmRanker(model_name_or_path=args.run.model_name_or_path, tokenizer_name_or_path=args.run.tokenizer_name_or_path,
+        if args.run.openai_key:
+            raise NotImplementedError("OpenAI rankers are remote HTTP calls, not part of the MI355X hot path; use the reference")
+        from llmrankers.pairwise import DuoT5LlmRanker, PairwiseLlmRanker
+        cls = DuoT5LlmRanker if "duot5" in args.run.model_name_or_path else PairwiseLlmRanker        # ref: run.py:99-106
+        return cls(model_name_or_path=args.run.model_name_or_path, tokenizer_name_or_path=args.run.tokenizer_name_or_path,
                                  device=args.run.device, cache_dir=args.run.cache_dir, method=args.pairwise.method,
                                  batch_size=args.pairwise.batch_size, k=args.pairwise.k)
     if args.listwise:
@@ -371,12 +373,15 @@ def main(args):
 
     results, n_cmp, n_prompt, n_compl = [], 0, 0, 0
     # --queries_per_call N: N queries go to the engine together (PointwiseLlmRanker.rerank_many: all their batches in one launch
-    # sequence; SetwiseLlmRanker.rerank_many: their heapsorts advance in lockstep, one engine call per step of all the chains) -
+    # sequence; SetwiseLlmRanker / DuoT5LlmRanker.rerank_many: their heapsorts advance in lockstep, one engine call per step of all the chains) -
     # same rankings and counters as one query at a time, the engine's batched throughput instead of its per-query one
     per_call = int(getattr(args.run, "queries_per_call", 0) or 0)
     if per_call <= 0:                                                # auto: the engine's grouped throughput by default
         from llmrankers._batching import default_queries_per_call
         kind = "pointwise" if args.pointwise else ("setwise" if args.setwise else ("listwise" if args.listwise else "other"))
+        if args.pairwise:
+            from llmrankers.pairwise import DuoT5LlmRanker
+            kind = "duot5" if isinstance(ranker, DuoT5LlmRanker) else "pairwise"
         per_call = default_queries_per_call(kind, args.run.hits)
     if per_call > 1 and not hasattr(ranker, "rerank_many"):
         per_call = 1
@@ -516,10 +521,10 @@ def build_parser():
                     help="pointwise under several ranks: 1 (default) shards every query's candidates and gathers the scores over "
                          "RCCL, 0 deals whole queries to the ranks")
     rp.add_argument("--queries_per_call", type=int, default=0,
-                    help="pointwise / setwise / listwise: queries handed to the engine together (same rankings and counters as one at a time); "
+                    help="pointwise / setwise / listwise / duoT5 pairwise: queries handed to the engine together (same rankings and counters as one at a time); "
                          "0 = auto (llmrankers._batching.default_queries_per_call): pointwise enough queries for >= 1600 passages "
                          f"per call, at most 16 ({_auto_per_call('pointwise', 100)} at hits=100), setwise {_auto_per_call('setwise', 100)} "
-                         "heapsorts in lockstep; with --resume the run file is appended once per call, i.e. every that many queries; "
+                         f"heapsorts in lockstep, duoT5 {_auto_per_call('duot5', 100)}; with --resume the run file is appended once per call, i.e. every that many queries; "
                          "1 = the reference's one query at a time (and its per-query flush)")
     pw = commands.add_parser("pointwise")
     pw.add_argument("--method", type=str, default="yes_no", choices=["qlm", "yes_no"])
