@@ -189,6 +189,32 @@ int rk_llama_generate(rk_engine* e, const int32_t* tokens, const int32_t* seq_of
                       int max_new, int max_total, const int32_t* eos_ids, int n_eos, int pad_id,
                       int32_t* out_tokens, int32_t* out_steps);
 
+/* ---- decoding session: continuous batching for long greedy decodes (the Rank-R1 ranker; the reference serves it through
+ * vLLM, ref: llmrankers/setwise.py:406-553, which gives a finished row's place to the next request).  A session has a fixed
+ * number of cache slots of max_len positions each; prompts are admitted into free slots while the other slots keep their state;
+ * every step decodes one token for all slots through ONE replayed graph.  A prompt's tokens are bit for bit what
+ * rk_llama_generate returns for that prompt alone (max_total = 0), whatever shares the session.  One session per engine; while it
+ * is open rk_llama_generate, rk_llama_greedy1 and rk_llama_last_logits return RK_ERR_STATE and leave it intact.
+ * open: RK_ERR_CAPACITY for n_slots > max_seqs or max_len > max_tokens; RK_ERR_STATE when a session is open.  max_new_cap bounds
+ * every request's max_new; eos_ids / pad_id as in rk_llama_generate. */
+int rk_llama_session_open(rk_engine* e, int n_slots, int max_len, int max_new_cap, const int32_t* eos_ids, int n_eos, int pad_id);
+/* n prompts (ragged, as everywhere) into the free slots slots[n], prompt b to generate up to max_new[b] tokens: ONE prefill,
+ * every layer's keys and values to the slots' cache rows, column 0 of each slot = the prefill's arg-max (a slot can finish here:
+ * EOS, or max_new 1).  Refused without touching the session: RK_ERR_STATE for a busy slot, RK_ERR_INVALID for a slot out of range
+ * or named twice, RK_ERR_CAPACITY for len + max_new > max_len, max_new > max_new_cap or a batch beyond the prefill's capacities. */
+int rk_llama_session_admit(rk_engine* e, const int32_t* tokens, const int32_t* seq_offsets, const int32_t* slots,
+                           const int32_t* max_new, int n);
+/* Steps until at least one slot has newly finished, no slot is active, or max_steps steps were issued (one step stays queued
+ * ahead of the host's check, so a finish is seen one step late; that step changes nothing for the finished slot).
+ * out_finished[n_slots] receives the slots that finished since the last run (at admit included), *out_n_finished their number,
+ * *out_steps the steps issued (0 when a finish was already waiting or nothing is active). */
+int rk_llama_session_run(rk_engine* e, int max_steps, int32_t* out_finished, int32_t* out_n_finished, int32_t* out_steps);
+/* The finished slot's new tokens (the EOS that ended it included) -> out_tokens[*out_n], and the slot is free again.
+ * RK_ERR_STATE for a slot that is idle or still decoding, RK_ERR_CAPACITY when cap is too small. */
+int rk_llama_session_read(rk_engine* e, int slot, int32_t* out_tokens, int cap, int32_t* out_n);
+/* Drains the stream and ends the session (a no-op without one).  Cache and step graph stay for the next open of the same sizes. */
+int rk_llama_session_close(rk_engine* e);
+
 /* ---- score collection across the GPUs of one node: one process per GPU, one engine per process.
  * The reference has no counterpart (its multi-GPU mode is accelerate's layer placement, ref: pointwise.py:21); this
  * replaces the torch.distributed round trip of a data-parallel caller.  RCCL (librccl.so.1) is dlopen'ed on first use.
@@ -347,7 +373,7 @@ int rk_debug_attn(rk_engine* e, rk_debug_attn_call* call);
 int rk_debug_gemm_bench(rk_engine* e, int M, int N, int K, int epi, int iters, float* out_ms);
 /* debug: copy an internal activation buffer to the host as fp32. name: "enc_hidden" [T,d], "enc_out" [T,d],
  * "qkv" [T,3I], "ctx" [T,I], "dec_hidden" [B*Ld,d], "llama_last" [n_seq,hidden] (the final-normed last rows of the most recent
- * Llama call: after rk_llama_generate, the rows the last step's head read). Returns number of floats written or a negative status. */
+ * Llama call: after rk_llama_generate, the rows the last step's head read; after rk_llama_session_run, its n_slots rows). Returns number of floats written or a negative status. */
 int64_t rk_debug_read(rk_engine* e, const char* name, float* out, int64_t max_floats);
 
 #ifdef __cplusplus

@@ -538,6 +538,24 @@ __global__ __launch_bounds__(256) void kv_cache_fill128_kernel(const half_t* __r
   }
 }
 
+// The decoding session's fill (rk_llama_session_admit): the same copy, but sequence b of the call goes to cache row slots[b] of
+// a cache that holds other, running rows.  Two 16-byte stores per thread, addresses from the slot map alone.
+__global__ __launch_bounds__(256) void kv_cache_fill128_slots_kernel(const half_t* __restrict__ qkv, const int* __restrict__ seq_off,
+                                                                     const int* __restrict__ slots, int n_slots,
+                                                                     half_t* __restrict__ kc, half_t* __restrict__ vc, int ld,
+                                                                     int n_heads, int n_kv, int P) {
+  const int b = blockIdx.y, t = blockIdx.x;
+  const int tok0 = seq_off[b], slot = slots[b];
+  if (t >= seq_off[b + 1] - tok0 || t >= P || slot < 0 || slot >= n_slots) return;
+  const half_t* row = qkv + (size_t)(tok0 + t) * ld + (size_t)n_heads * 128;
+  for (int c = threadIdx.x; c < n_kv * 16; c += 256) {
+    const int h = c >> 4, piece = (c & 15) * 8;
+    const size_t dst = (((size_t)slot * n_kv + h) * P + t) * 128 + piece;
+    *(half8*)(kc + dst) = *(const half8*)(row + h * 128 + piece);
+    *(half8*)(vc + dst) = *(const half8*)(row + (size_t)(n_kv + h) * 128 + piece);
+  }
+}
+
 struct AttnDecCached128Args {
   const half_t* qkv;     // [n_seq, ld]: the step's fused q | k | v rows, NOT yet rotated
   half_t* kc;            // this layer's key cache [n_seq][n_kv][P][128]; the new key is written at the row's position

@@ -238,6 +238,45 @@ __global__ __launch_bounds__(256) void llama_advance_kernel(const int* __restric
   }
 }
 
+// Token feedback of a decoding session (rk_llama_session_*), the sibling of llama_advance_kernel for rows that start and end on
+// their own: every cache slot has its prompt length, its own column counter, its own max_new and a done flag (1: idle or
+// finished).  st = {finishes so far, pad, n_eos, max_len, max_new_cap, 0, 0, 0, eos[8]}.  An active slot's column col[b] gets its
+// arg-max; the slot finishes at one of the EOS ids or at its max_new-th token; the token is its next input at position
+// len[b] + col[b], held inside the cache.  A slot that is idle or done emits nothing, keeps its position, feeds pad and is not
+// counted again: the step queued behind a finish changes nothing for that slot.  st[0], the session word, is the running number
+// of finishes (the host compares it with what it has seen).
+// admit != null (rk_llama_session_admit, behind the prefill's head; admit = slot[n] | len[n] | max_new[n]): row r of argmax belongs
+// to slot admit[r], which starts here with that prompt length and max_new; only those slots are touched.  One workgroup.
+__global__ __launch_bounds__(256) void llama_session_advance_kernel(const int* __restrict__ argmax, int* st, int* len, int* col,
+                                                                    int* max_new, int* done, int* pos, int* out, int* next_ids,
+                                                                    int n_slots, const int* __restrict__ admit, int n_admit) {
+  __shared__ int s_fin;
+  const int tid = threadIdx.x, pad = st[1], n_eos = st[2], max_len = st[3], cap = st[4];
+  if (tid == 0) s_fin = 0;
+  __syncthreads();
+  const int rows = admit ? n_admit : n_slots;
+  for (int r = tid; r < rows; r += 256) {
+    int b = r;
+    if (admit) {
+      b = admit[r];
+      if (b < 0 || b >= n_slots) continue;
+      len[b] = admit[n_admit + r]; max_new[b] = admit[2 * n_admit + r]; col[b] = 0; done[b] = 0;
+    }
+    if (done[b]) { next_ids[b] = pad; continue; }
+    const int tok = argmax[r], c = col[b];
+    bool fin = c + 1 >= max_new[b] || c + 1 >= cap;
+    for (int k = 0; k < n_eos; ++k) fin = fin || tok == st[8 + k];
+    if (c < cap) out[(size_t)b * cap + c] = tok;
+    next_ids[b] = tok;
+    const int p = len[b] + c;
+    pos[b] = p < max_len - 1 ? p : max_len - 1;
+    col[b] = c + 1;
+    if (fin) { done[b] = 1; atomicAdd(&s_fin, 1); }
+  }
+  __syncthreads();
+  if (tid == 0 && s_fin) st[0] += s_fin;
+}
+
 // QLM score (ref: llmrankers/pointwise.py:77-79) from the fused head (gemm.h: EPI_LSE_F32): stats [rows, nblk] = (block max, sum exp(x - block max)), xlab [rows] =
 // the label's logit.  out[b] = -sum_t ( logsumexp_t - xlab[b, t] ), logsumexp_t = M + log(sum_blocks s * exp(m - M)).
 // One block per sequence; the blocks of a position are merged in a fixed order, the positions summed in order (deterministic).

@@ -202,6 +202,12 @@ struct rk_engine {
   // between calls; lkv_gen counts the moves and is part of the step graph's key), and the step's activation rows (max_seqs each)
   Grown<half_t> lkv; Grown<float> lpart; Grown<int> lints; int lkv_gen = 0;
   struct LlamaStep { NormStream stream; half_t *qkv = nullptr, *ctx = nullptr, *ffh = nullptr; } lg;
+  // rk_llama_session_*: the one open decoding session.  It lives in lkv / lpart / lints (rk_llama_generate is refused meanwhile)
+  // and mirrors on the host what the device's int block said at the last read-back: no step is ever in flight between two calls.
+  struct LlamaSession {
+    bool open = false; int n_slots = 0, max_len = 0, cap = 0, seen = 0;   // seen: the session word at the last read-back
+    std::vector<int> busy, told, len, max_new, col, done;                 // per slot; told: its finish was returned by a run
+  } ls;
   // decoder chains as HIP graphs: key = everything the launch parameters of a chain depend on
   struct GraphEntry { int seen = 0; bool failed = false; hipGraphExec_t exec = nullptr; };
   std::map<std::vector<int>, GraphEntry> graphs; int opt_epoch = 0;
@@ -1373,7 +1379,7 @@ int stage_slot(rk_engine* e, int slot, const int32_t* tokens, const int32_t* seq
 // dependent-kernel boundary (1-2 us).  `body` enqueues the chain on `st`; the second time a key is seen the chain is
 // captured, instantiated and cached, from then on it is replayed.  The key holds every value the launch parameters
 // depend on (shapes, options epoch); buffers are per-slot and never move.  Profiling runs stay eager (per-kernel events).
-enum GraphKind { GK_T5_SCORE, GK_T5_GREEDY_STEP, GK_T5_GREEDY2, GK_T5_GENERATE_STEP, GK_LLAMA_STEP, GK_T5_COMPARE };   // which chain: the key's first int
+enum GraphKind { GK_T5_SCORE, GK_T5_GREEDY_STEP, GK_T5_GREEDY2, GK_T5_GENERATE_STEP, GK_LLAMA_STEP, GK_T5_COMPARE, GK_LLAMA_SESSION_STEP };   // which chain: the key's first int
 template <class F>
 int run_graphed(rk_engine* e, hipStream_t st, std::vector<int> key, F&& body) {
   key.push_back(e->opt_epoch);
@@ -2456,7 +2462,8 @@ static int llama_finalize(rk_engine* e) {
 
 // prefill of the ragged batch; leaves the final-normed LAST hidden state of every sequence in sl.dlast [n_seq, hidden]
 // keep (rk_llama_generate only): every layer's rotated K and its V are also copied to the cache, P positions per sequence
-struct LlamaKeep { half_t* kv; int P; };
+// slots (rk_llama_session_admit): sequence b goes to cache row slots[b] (device ints) of a cache of `rows` rows
+struct LlamaKeep { half_t* kv; int P; const int* slots = nullptr; int rows = 0; };
 static int llama_prefill(rk_engine* e, const int32_t* tokens, const int32_t* off, int n_seq, const LlamaKeep* keep = nullptr) {
   if (!e || e->family != 1) return fail(e, RK_ERR_STATE, "not a Llama engine");
   int rc = set_device(e);
@@ -2494,11 +2501,15 @@ static int llama_prefill(rk_engine* e, const int32_t* tokens, const int32_t* off
                            (const float*)nullptr, 0);
     }
     if (keep) {
-      const size_t half_layer = (size_t)n_seq * l.n_kv_heads * keep->P * 128;
+      const size_t half_layer = (size_t)(keep->slots ? keep->rows : n_seq) * l.n_kv_heads * keep->P * 128;
       half_t* kc = keep->kv + (size_t)i * 2 * half_layer;
       Bracket br(e, st, PC_OTHER, 0, (double)T * KV * 8.0);
-      hipLaunchKernelGGL(kv_cache_fill128_kernel, dim3(sl.maxL, n_seq), dim3(256), 0, st, sl.qkv, sl.d_seq_off, kc, kc + half_layer, ldq,
-                         l.n_heads, l.n_kv_heads, keep->P);
+      if (keep->slots)
+        hipLaunchKernelGGL(kv_cache_fill128_slots_kernel, dim3(sl.maxL, n_seq), dim3(256), 0, st, sl.qkv, sl.d_seq_off, keep->slots, keep->rows,
+                           kc, kc + half_layer, ldq, l.n_heads, l.n_kv_heads, keep->P);
+      else
+        hipLaunchKernelGGL(kv_cache_fill128_kernel, dim3(sl.maxL, n_seq), dim3(256), 0, st, sl.qkv, sl.d_seq_off, kc, kc + half_layer, ldq,
+                           l.n_heads, l.n_kv_heads, keep->P);
     }
     launch_llama_attn(e, st, CausalAttnCall{sl.qkv, sl.ctx, sl.d_seq_off, ldq, Q, l.n_heads, l.n_kv_heads, sl.n_seq, sl.maxL, T}, ap);
     RC(ns.producer(e, st, Gemm(PC_ENC_GEMM_O, EPI_RESID_F32, sl.ctx, Q, w.o, Q, ns.hidden, dm, T, dm, Q)));
@@ -2513,6 +2524,7 @@ static int llama_prefill(rk_engine* e, const int32_t* tokens, const int32_t* off
 int rk_llama_last_logits(rk_engine* e, const int32_t* tokens, const int32_t* seq_offsets, int n_seq,
                          const int32_t* out_token_ids, int n_out, float* out_logits) {
   if (!e || !out_logits) return RK_ERR_INVALID;
+  if (e->ls.open) return fail(e, RK_ERR_STATE, "rk_llama_last_logits while a decoding session is open (it shares the prefill's buffers): rk_llama_session_close first");
   if (!out_token_ids || n_out <= 0 || n_out > 64) return fail(e, RK_ERR_INVALID, "n_out must be in 1..64 (got %d)", n_out);
   int rc = check_ids(e, out_token_ids, n_out, "output");
   if (rc) return rc;
@@ -2545,6 +2557,7 @@ int rk_llama_set_qkv_bias(rk_engine* e, int on) {
 
 int rk_llama_greedy1(rk_engine* e, const int32_t* tokens, const int32_t* seq_offsets, int n_seq, int32_t* out_tokens) {
   if (!e || !out_tokens) return RK_ERR_INVALID;
+  if (e->ls.open) return fail(e, RK_ERR_STATE, "rk_llama_greedy1 while a decoding session is open (it shares the prefill's buffers): rk_llama_session_close first");
   int rc = llama_prefill(e, tokens, seq_offsets, n_seq);
   if (rc) return rc;
   if ((rc = ensure_amax(e, (size_t)n_seq))) return rc;
@@ -2557,13 +2570,12 @@ int rk_llama_greedy1(rk_engine* e, const int32_t* tokens, const int32_t* seq_off
 
 // rk_llama_generate's device memory, grown between calls only (never inside a capture; a move of any of the three changes
 // lkv_gen, which is part of the step graph's key: the step holds all three addresses): the K / V cache, the attention partials,
-// the call's int block; once: the step's activation rows.
-static int ensure_llama_gen(rk_engine* e, int n_seq, int P, int max_new) {
+// the call's int block (`ints` of them); once: the step's activation rows.  A decoding session (below) holds the same three.
+static int ensure_llama_gen(rk_engine* e, int n_seq, int P, size_t ints) {
   const rk_llama_desc& l = e->ld;
   const size_t S = (size_t)l.max_seqs, dm = l.hidden, Q = (size_t)l.n_heads * 128, KV = (size_t)l.n_kv_heads * 128, F = l.intermediate;
   const size_t kv = (size_t)l.n_layers * 2 * n_seq * KV * P;
   const size_t part = (size_t)n_seq * l.n_heads * ((P + LDC_CHUNK - 1) / LDC_CHUNK) * LDC_PSTR;
-  const size_t ints = 16 + 4 * S + (size_t)n_seq * max_new;
   int rc = RK_OK;
   RC(e->lkv.reserve(e, kv, &e->lkv_gen)); RC(e->lpart.reserve(e, part, &e->lkv_gen)); RC(e->lints.reserve(e, ints, &e->lkv_gen));
   if (!e->lg.stream.hidden) {
@@ -2572,6 +2584,38 @@ static int ensure_llama_gen(rk_engine* e, int n_seq, int P, int max_new) {
     RC(dalloc(e, &e->lg.stream.factors, S));
   }
   return ensure_decode_ring(e);
+}
+
+// One decoding step over `rows` cache rows of P positions each (rk_llama_generate's rows, a session's slots), up to the final
+// norm: the embedding of next[rows], per layer QKV (folded norm) -> attn_dec_cached128_kernel at pos[rows] -> o + residual ->
+// gate|up + SwiGLU -> down + residual, then the final-normed rows in slots[0].dlast.  The cache, the partials and the activation
+// rows are the engine's (ensure_llama_gen).  Nothing here depends on which rows are live: a row's bits follow from its own
+// tokens and position.
+static int llama_step_rows(rk_engine* e, hipStream_t st, int rows, int P, const int* d_next, const int* d_pos) {
+  const rk_llama_desc& l = e->ld;
+  const int dm = l.hidden, Q = l.n_heads * 128, KV = l.n_kv_heads * 128, F = l.intermediate, ldq = Q + 2 * KV;
+  const LlamaDecAttnPlan ap = plan_llama_dec_attn(e, rows, P, l.n_heads, l.n_kv_heads);
+  const size_t half_layer = (size_t)rows * KV * P;
+  const float scale_log2e = (1.0f / std::sqrt(128.0f)) * 1.4426950408889634f;
+  const auto& lg = e->lg;
+  int rc = RK_OK;
+  NormStream ns = lg.stream;
+  // the GEMM behind a norm forms its row factors from the producer's block sums in its own epilogue, or - more block sums than
+  // that path stages by DMA (64: hidden > 2 048) - takes them from rowscale_kernel in front of it.  A function of the model only.
+  auto normed = [&](Gemm c) { return ns.consumer(e, st, nullptr, c.on(GEMM_STREAM), ns.nb <= 64); };
+  ns.begin(e, st, d_next, rows, true);
+  for (int i = 0; i < l.n_layers; ++i) {
+    const LlamaLayerW& w = e->ll[i];
+    RC(gemm(e, st, normed(Gemm(PC_DEC_GEMM, EPI_STORE_F16, ns.x(), dm, w.qkv_f, dm, lg.qkv, ldq, rows, ldq, dm))));
+    half_t* kc = e->lkv.p + (size_t)i * 2 * half_layer;
+    launch_llama_dec_attn(e, st, ap, AttnDecCached128Args{lg.qkv, kc, kc + half_layer, d_pos, e->rope_cos, e->rope_sin, e->lpart.p, lg.ctx,
+                                                          ldq, l.n_heads, l.n_kv_heads, P, ap.nch, scale_log2e, w.qkv_bias}, rows);
+    RC(ns.producer(e, st, Gemm(PC_DEC_GEMM, EPI_RESID_F32, lg.ctx, Q, w.o, Q, ns.hidden, dm, rows, dm, Q).on(GEMM_STREAM)));
+    RC(gemm(e, st, normed(Gemm(PC_DEC_GEMM, EPI_SWIGLU_F16, ns.x(), dm, w.gu_f, dm, lg.ffh, F, rows, 2 * F, dm))));
+    RC(ns.producer(e, st, Gemm(PC_DEC_GEMM, EPI_RESID_F32, lg.ffh, F, w.down, F, ns.hidden, dm, rows, dm, F).on(GEMM_STREAM), i + 1 < l.n_layers));
+  }
+  rmsnorm(e, st, ns.hidden, e->l_final_ln, e->slots[0].dlast, nullptr, rows);
+  return RK_OK;
 }
 
 // Greedy continuation with a K / V cache (hf: generation/utils.py greedy loop over LlamaForCausalLM with use_cache): the prefill
@@ -2585,6 +2629,7 @@ int rk_llama_generate(rk_engine* e, const int32_t* tokens, const int32_t* seq_of
                       const int32_t* eos_ids, int n_eos, int pad_id, int32_t* out_tokens, int32_t* out_steps) {
   if (!e) return RK_ERR_INVALID;
   if (e->family != 1) return fail(e, RK_ERR_STATE, "rk_llama_generate called on a T5 engine (use rk_t5_generate)");
+  if (e->ls.open) return fail(e, RK_ERR_STATE, "rk_llama_generate while a decoding session is open (it shares the cache and the step's rows): rk_llama_session_close first");
   if (!out_tokens) return fail(e, RK_ERR_INVALID, "null output");
   if (max_new <= 0) return fail(e, RK_ERR_INVALID, "max_new must be positive (got %d)", max_new);
   if (n_eos < 0 || n_eos > 8 || (n_eos > 0 && !eos_ids)) return fail(e, RK_ERR_INVALID, "n_eos must be in 0..8 (got %d)", n_eos);
@@ -2601,7 +2646,7 @@ int rk_llama_generate(rk_engine* e, const int32_t* tokens, const int32_t* seq_of
       return fail(e, RK_ERR_INVALID, "prompt %d has %d tokens: it already reaches max_total %d", b, seq_offsets[b + 1] - seq_offsets[b], max_total);
   const int P = sl.maxL + max_new, S = l.max_seqs;
   if ((rc = ensure_amax(e, (size_t)n_seq))) return rc;
-  if ((rc = ensure_llama_gen(e, n_seq, P, max_new))) return rc;
+  if ((rc = ensure_llama_gen(e, n_seq, P, 16 + 4 * (size_t)S + (size_t)n_seq * max_new))) return rc;
   hipStream_t st = sl.se;
   // the call's int block: {n, finished step, pad, n_eos, max_new, max_total, P, 0, eos[8]} | len[S] | done[S] | pos[S] | next[S] | out[n][max_new]
   int* g = e->lints.p;
@@ -2623,34 +2668,194 @@ int rk_llama_generate(rk_engine* e, const int32_t* tokens, const int32_t* seq_of
     return RK_OK;
   };
   if ((rc = head_and_advance())) return rc;
-  const int dm = l.hidden, Q = l.n_heads * 128, KV = l.n_kv_heads * 128, F = l.intermediate, ldq = Q + 2 * KV;
-  const LlamaDecAttnPlan ap = plan_llama_dec_attn(e, n_seq, P, l.n_heads, l.n_kv_heads);
-  const size_t half_layer = (size_t)n_seq * KV * P;
-  const float scale_log2e = (1.0f / std::sqrt(128.0f)) * 1.4426950408889634f;
-  const auto& lg = e->lg;
   auto step = [&]() -> int {
-    int rc = RK_OK;
-    NormStream ns = lg.stream;
-    // the GEMM behind a norm forms its row factors from the producer's block sums in its own epilogue, or - more block sums than
-    // that path stages by DMA (64: hidden > 2 048) - takes them from rowscale_kernel in front of it.  A function of the model only.
-    auto normed = [&](Gemm c) { return ns.consumer(e, st, nullptr, c.on(GEMM_STREAM), ns.nb <= 64); };
-    ns.begin(e, st, d_next, n_seq, true);
-    for (int i = 0; i < l.n_layers; ++i) {
-      const LlamaLayerW& w = e->ll[i];
-      RC(gemm(e, st, normed(Gemm(PC_DEC_GEMM, EPI_STORE_F16, ns.x(), dm, w.qkv_f, dm, lg.qkv, ldq, n_seq, ldq, dm))));
-      half_t* kc = e->lkv.p + (size_t)i * 2 * half_layer;
-      launch_llama_dec_attn(e, st, ap, AttnDecCached128Args{lg.qkv, kc, kc + half_layer, d_pos, e->rope_cos, e->rope_sin, e->lpart.p, lg.ctx,
-                                                            ldq, l.n_heads, l.n_kv_heads, P, ap.nch, scale_log2e, w.qkv_bias}, n_seq);
-      RC(ns.producer(e, st, Gemm(PC_DEC_GEMM, EPI_RESID_F32, lg.ctx, Q, w.o, Q, ns.hidden, dm, n_seq, dm, Q).on(GEMM_STREAM)));
-      RC(gemm(e, st, normed(Gemm(PC_DEC_GEMM, EPI_SWIGLU_F16, ns.x(), dm, w.gu_f, dm, lg.ffh, F, n_seq, 2 * F, dm))));
-      RC(ns.producer(e, st, Gemm(PC_DEC_GEMM, EPI_RESID_F32, lg.ffh, F, w.down, F, ns.hidden, dm, n_seq, dm, F).on(GEMM_STREAM), i + 1 < l.n_layers));
-    }
-    rmsnorm(e, st, ns.hidden, e->l_final_ln, sl.dlast, nullptr, n_seq);
-    return head_and_advance();
+    const int r = llama_step_rows(e, st, n_seq, P, d_next, d_pos);
+    return r ? r : head_and_advance();
   };
   const std::vector<int> key{GK_LLAMA_STEP, 0, n_seq, P, e->amax_gen, e->lkv_gen};
   // column 0 is the prefill's: the steps produce columns 1 .. max_new - 1
   return decode_cached(e, st, key, step, 0, 1, n_seq, max_new, g + 1, d_out, out_tokens, out_steps);
+}
+
+// ---- decoding session: fixed cache slots, prompts admitted while the other slots keep their state, ONE replayed step graph ----
+// What vLLM's continuous batching gives the reference's Rank-R1 ranker (ref: llmrankers/setwise.py:406-553): a finished row's place
+// goes to the next request.  The session's rows are rk_llama_generate's rows (llama_step_rows, the same launch sequence over all
+// n_slots rows, P = max_len), its prefill is llama_prefill with a slot map, and llama_session_advance_kernel keeps every slot's
+// own column counter: a prompt's tokens are bit for bit what rk_llama_generate gives for it alone.
+// int block: {finishes, pad, n_eos, max_len, cap, 0, 0, 0, eos[8]} | len[S] | col[S] | max_new[S] | done[S] | pos[S] | next[S] |
+// admit[3 S] | out[S][cap]
+namespace {
+struct SessionInts { int *st, *len, *col, *max_new, *done, *pos, *next, *admit, *out; };
+SessionInts session_ints(rk_engine* e) {
+  const int S = e->ls.n_slots;
+  int* g = e->lints.p;
+  return SessionInts{g, g + 16, g + 16 + S, g + 16 + 2 * S, g + 16 + 3 * S, g + 16 + 4 * S, g + 16 + 5 * S, g + 16 + 6 * S, g + 16 + 9 * S};
+}
+int session_check(rk_engine* e, const char* who) {
+  if (!e) return RK_ERR_INVALID;
+  if (e->family != 1) return fail(e, RK_ERR_STATE, "%s called on a T5 engine", who);
+  if (!e->ls.open) return fail(e, RK_ERR_STATE, "%s without an open session (rk_llama_session_open)", who);
+  return set_device(e);
+}
+// the session word, every slot's column counter and done flag -> the host mirror; the stream is idle afterwards
+int session_read_back(rk_engine* e, hipStream_t st) {
+  auto& ls = e->ls;
+  const SessionInts d = session_ints(e);
+  const int S = ls.n_slots;
+  std::vector<int> buf(16 + 4 * (size_t)S);
+  HIPCHK(e, hipMemcpyAsync(buf.data(), d.st, buf.size() * sizeof(int), hipMemcpyDeviceToHost, st));   // st | len | col | max_new | done
+  HIPCHK(e, hipStreamSynchronize(st));
+  HIPCHK(e, hipGetLastError());
+  ls.seen = buf[0];
+  for (int b = 0; b < S; ++b) { ls.col[b] = buf[16 + S + b]; ls.done[b] = buf[16 + 3 * S + b]; }
+  return RK_OK;
+}
+}  // namespace
+
+int rk_llama_session_open(rk_engine* e, int n_slots, int max_len, int max_new_cap, const int32_t* eos_ids, int n_eos, int pad_id) {
+  if (!e) return RK_ERR_INVALID;
+  if (e->family != 1) return fail(e, RK_ERR_STATE, "rk_llama_session_open called on a T5 engine");
+  if (!e->finalized) return fail(e, RK_ERR_STATE, "engine not finalized");
+  if (e->ls.open) return fail(e, RK_ERR_STATE, "a decoding session is already open on this engine (rk_llama_session_close first)");
+  const rk_llama_desc& l = e->ld;
+  if (n_slots <= 0 || max_len <= 1 || max_new_cap <= 0) return fail(e, RK_ERR_INVALID, "n_slots, max_new_cap must be positive and max_len > 1 (got %d, %d, %d)", n_slots, max_new_cap, max_len);
+  if (n_slots > l.max_seqs) return fail(e, RK_ERR_CAPACITY, "n_slots %d > max_seqs %d", n_slots, l.max_seqs);
+  if (max_len > l.max_tokens) return fail(e, RK_ERR_CAPACITY, "max_len %d > max_tokens %d (the rotary tables end there)", max_len, l.max_tokens);
+  if (n_eos < 0 || n_eos > 8 || (n_eos > 0 && !eos_ids)) return fail(e, RK_ERR_INVALID, "n_eos must be in 0..8 (got %d)", n_eos);
+  int rc;
+  if ((rc = check_ids(e, eos_ids, n_eos, "eos")) || (rc = check_ids(e, &pad_id, 1, "pad"))) return rc;
+  if ((rc = set_device(e))) return rc;
+  const size_t S = (size_t)n_slots, n_ints = 16 + 9 * S + S * (size_t)max_new_cap;
+  if ((rc = ensure_amax(e, S))) return rc;
+  if ((rc = ensure_llama_gen(e, n_slots, max_len, n_ints))) return rc;
+  auto& ls = e->ls;
+  ls.n_slots = n_slots; ls.max_len = max_len; ls.cap = max_new_cap; ls.seen = 0;
+  ls.busy.assign(S, 0); ls.told.assign(S, 0); ls.len.assign(S, 0); ls.max_new.assign(S, 0); ls.col.assign(S, 0); ls.done.assign(S, 1);
+  std::vector<int> init(n_ints, 0);                        // every slot idle: done, position 0, pad as its next id
+  init[1] = pad_id; init[2] = n_eos; init[3] = max_len; init[4] = max_new_cap;
+  for (int k = 0; k < n_eos; ++k) init[8 + k] = eos_ids[k];
+  for (size_t b = 0; b < S; ++b) { init[16 + 3 * S + b] = 1; init[16 + 5 * S + b] = pad_id; }
+  for (size_t k = 0; k < S * (size_t)max_new_cap; ++k) init[16 + 9 * S + k] = pad_id;
+  hipStream_t st = e->slots[0].se;
+  HIPCHK(e, hipStreamSynchronize(st));
+  HIPCHK(e, hipMemcpy(e->lints.p, init.data(), n_ints * sizeof(int), hipMemcpyHostToDevice));
+  ls.open = true;
+  return RK_OK;
+}
+
+int rk_llama_session_admit(rk_engine* e, const int32_t* tokens, const int32_t* seq_offsets, const int32_t* slots, const int32_t* max_new, int n) {
+  int rc = session_check(e, "rk_llama_session_admit");
+  if (rc) return rc;
+  auto& ls = e->ls;
+  if (!tokens || !seq_offsets || !slots || !max_new || n <= 0) return fail(e, RK_ERR_INVALID, "empty admit (n=%d)", n);
+  // every check before anything is touched: a refused admit leaves the session as it was
+  std::vector<char> taken(ls.n_slots, 0);
+  for (int b = 0; b < n; ++b) {
+    const int s = slots[b];
+    if (s < 0 || s >= ls.n_slots) return fail(e, RK_ERR_INVALID, "slot %d out of range (the session has %d)", s, ls.n_slots);
+    if (taken[s]) return fail(e, RK_ERR_INVALID, "slot %d named twice in one admit", s);
+    if (ls.busy[s]) return fail(e, RK_ERR_STATE, "slot %d is busy (rk_llama_session_read frees it)", s);
+    taken[s] = 1;
+  }
+  Slot& sl = e->slots[0];
+  if ((rc = check_batch(e, nullptr, tokens, seq_offsets, n))) return rc;
+  for (int b = 0; b < n; ++b) {
+    const int L = seq_offsets[b + 1] - seq_offsets[b];
+    if (max_new[b] <= 0) return fail(e, RK_ERR_INVALID, "max_new must be positive (prompt %d: %d)", b, max_new[b]);
+    if (max_new[b] > ls.cap) return fail(e, RK_ERR_CAPACITY, "prompt %d: max_new %d > the session's max_new_cap %d", b, max_new[b], ls.cap);
+    if ((long)L + max_new[b] > ls.max_len) return fail(e, RK_ERR_CAPACITY, "prompt %d: %d tokens + max_new %d exceed the session's max_len %d", b, L, max_new[b], ls.max_len);
+  }
+  const SessionInts d = session_ints(e);
+  hipStream_t st = sl.se;
+  std::vector<int> adm(3 * (size_t)n);                     // slot[n] | len[n] | max_new[n]: its head is the cache fill's slot map
+  for (int b = 0; b < n; ++b) { adm[b] = slots[b]; adm[n + b] = seq_offsets[b + 1] - seq_offsets[b]; adm[2 * n + b] = max_new[b]; }
+  HIPCHK(e, hipStreamSynchronize(st));                     // (nothing is in flight between two session calls)
+  HIPCHK(e, hipMemcpy(d.admit, adm.data(), adm.size() * sizeof(int), hipMemcpyHostToDevice));
+  const LlamaKeep keep{e->lkv.p, ls.max_len, d.admit, ls.n_slots};
+  if ((rc = llama_prefill(e, tokens, seq_offsets, n, &keep))) return rc;
+  if ((rc = head_argmax(e, st, sl.dlast, n, e->ld.hidden, e->ld.vocab, sl.d_argmax))) return rc;
+  {
+    Bracket br(e, st, PC_OTHER, 0, 0);
+    hipLaunchKernelGGL(llama_session_advance_kernel, dim3(1), dim3(256), 0, st, sl.d_argmax, d.st, d.len, d.col, d.max_new, d.done, d.pos, d.out,
+                       d.next, ls.n_slots, d.admit, n);
+  }
+  for (int b = 0; b < n; ++b) { const int s = slots[b]; ls.busy[s] = 1; ls.told[s] = 0; ls.len[s] = adm[n + b]; ls.max_new[s] = max_new[b]; }
+  return session_read_back(e, st);
+}
+
+int rk_llama_session_run(rk_engine* e, int max_steps, int32_t* out_finished, int32_t* out_n_finished, int32_t* out_steps) {
+  int rc = session_check(e, "rk_llama_session_run");
+  if (rc) return rc;
+  if (!out_finished || !out_n_finished) return fail(e, RK_ERR_INVALID, "null output");
+  auto& ls = e->ls;
+  Slot& sl = e->slots[0];
+  hipStream_t st = sl.se;
+  const SessionInts d = session_ints(e);
+  auto untold = [&]() { for (int b = 0; b < ls.n_slots; ++b) if (ls.busy[b] && ls.done[b] && !ls.told[b]) return true; return false; };
+  // the steps after which no slot can still be active: a bound on the loop whatever the device says
+  int live = 0;
+  for (int b = 0; b < ls.n_slots; ++b) if (ls.busy[b] && !ls.done[b]) live = std::max(live, ls.max_new[b] - ls.col[b]);
+  int steps = 0;
+  if (!untold() && live > 0 && max_steps > 0) {
+    auto step = [&]() -> int {
+      int r = llama_step_rows(e, st, ls.n_slots, ls.max_len, d.next, d.pos);
+      if (r || (r = head_argmax(e, st, sl.dlast, ls.n_slots, e->ld.hidden, e->ld.vocab, sl.d_argmax))) return r;
+      Bracket br(e, st, PC_OTHER, 0, 0);
+      hipLaunchKernelGGL(llama_session_advance_kernel, dim3(1), dim3(256), 0, st, sl.d_argmax, d.st, d.len, d.col, d.max_new, d.done, d.pos,
+                         d.out, d.next, ls.n_slots, (const int*)nullptr, 0);
+      return RK_OK;
+    };
+    const std::vector<int> key{GK_LLAMA_SESSION_STEP, 0, ls.n_slots, ls.max_len, ls.cap, e->amax_gen, e->lkv_gen};
+    int* pin = e->gen_pin;
+    const int limit = std::min(max_steps, live);
+    bool stop = false;
+    for (int c = 0; c < limit && !stop; ++c) {             // decode_cached's loop: one word per step, one step queued ahead
+      RC(run_graphed(e, st, key, step));
+      ++steps;
+      HIPCHK(e, hipMemcpyAsync(pin + (c & 1), d.st, sizeof(int), hipMemcpyDeviceToHost, st));
+      HIPCHK(e, hipEventRecord(e->ev_gen[c & 1], st));
+      if (c >= 1) {
+        HIPCHK(e, hipEventSynchronize(e->ev_gen[(c - 1) & 1]));
+        stop = pin[(c - 1) & 1] != ls.seen;
+      }
+    }
+    sl.n_seq = ls.n_slots;                                 // rk_debug_read("llama_last"): the step's final rows
+    RC(session_read_back(e, st));
+  }
+  int nf = 0;
+  for (int b = 0; b < ls.n_slots; ++b)
+    if (ls.busy[b] && ls.done[b] && !ls.told[b]) { out_finished[nf++] = b; ls.told[b] = 1; }
+  *out_n_finished = nf;
+  if (out_steps) *out_steps = steps;
+  return RK_OK;
+}
+
+int rk_llama_session_read(rk_engine* e, int slot, int32_t* out_tokens, int cap, int32_t* out_n) {
+  int rc = session_check(e, "rk_llama_session_read");
+  if (rc) return rc;
+  auto& ls = e->ls;
+  if (!out_tokens || !out_n) return fail(e, RK_ERR_INVALID, "null output");
+  if (slot < 0 || slot >= ls.n_slots) return fail(e, RK_ERR_INVALID, "slot %d out of range (the session has %d)", slot, ls.n_slots);
+  if (!ls.busy[slot] || !ls.done[slot]) return fail(e, RK_ERR_STATE, "slot %d %s", slot, ls.busy[slot] ? "has not finished" : "is idle");
+  const int n = ls.col[slot];
+  if (cap < n) return fail(e, RK_ERR_CAPACITY, "slot %d holds %d tokens, the caller's buffer %d", slot, n, cap);
+  const SessionInts d = session_ints(e);
+  HIPCHK(e, hipMemcpy(out_tokens, d.out + (size_t)slot * ls.cap, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
+  const int zero = 0;                                      // idle again: one key chunk of attention per step
+  HIPCHK(e, hipMemcpy(d.pos + slot, &zero, sizeof(int), hipMemcpyHostToDevice));
+  *out_n = n;
+  ls.busy[slot] = 0; ls.told[slot] = 0;
+  return RK_OK;
+}
+
+int rk_llama_session_close(rk_engine* e) {
+  if (!e) return RK_ERR_INVALID;
+  if (!e->ls.open) return RK_OK;
+  int rc = set_device(e);
+  if (rc) return rc;
+  e->ls.open = false;                                      // (the buffers and the step graph stay for the next open of these sizes)
+  HIPCHK(e, hipStreamSynchronize(e->slots[0].se));
+  return RK_OK;
 }
 
 // ---- K9: score collection across the GPUs of a node, RCCL over xGMI, straight from the slot's device score buffer --
@@ -3356,7 +3561,7 @@ int64_t rk_debug_read(rk_engine* e, const char* name, float* out, int64_t max_fl
   else if (n == "qkv") { src = sl.qkv; cnt = (int64_t)sl.T * 3 * I; }
   else if (n == "ctx") { src = sl.ctx; cnt = (int64_t)sl.T * I; }
   else if (n == "xn") { src = sl.enc.xn; cnt = (int64_t)sl.T * dm; }
-  else if (n == "llama_last") { src = sl.dlast; cnt = (int64_t)sl.n_seq * dm; }   // final-normed last rows of the most recent Llama call
+  else if (n == "llama_last") { src = sl.dlast; cnt = (int64_t)sl.n_seq * dm; }   // final-normed last rows of the most recent Llama call (a session's step: n_slots rows)
   else if (n == "dec_hidden") { src = sl.dec.hidden; cnt = (int64_t)sl.n_seq * e->d.max_dec_len * dm; is_half = false; }
   else return fail(e, RK_ERR_INVALID, "unknown buffer %s", name);
   cnt = std::min(cnt, max_floats);

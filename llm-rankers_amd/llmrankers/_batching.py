@@ -208,7 +208,7 @@ def padded_token_count(seqs: Sequence[Sequence[int]]) -> int:
     return len(seqs) * max(len(s) for s in seqs) if seqs else 0
 
 
-def default_queries_per_call(kind: str, hits: int) -> int:
+def default_queries_per_call(kind: str, hits: int, slots: int = 16) -> int:
     """How many queries run.py hands to a ranker's rerank_many at once when --queries_per_call is left at 0 (auto).
     Results, caller lists and counters are those of one query at a time (tests); what changes is what one engine launch
     sequence holds.  pointwise: enough queries for >= 1 600 passages, at most 16 - the runtime cuts them into launch sequences of
@@ -229,7 +229,9 @@ def default_queries_per_call(kind: str, hits: int) -> int:
     verdict and the level-batched build 205 ms, rerank_many at 4 / 8 / 16 / 32 queries = 75.7 / 54.4 / 48.7 / 44.3 ms per query - the
     smallest count of the sweep within 3 % of its best is the largest one.  Thirty-two = two alternating groups of sixteen pairs
     per sift-down step: 32 prompts, 16k tokens at 512-token prompts, inside ONE engine call of T5Runtime's 256 prompts / 49k
-    tokens); anything else, PRP pairwise included, one query at a time."""
+    tokens); rankr1: `slots`, the decoding slots of the runtime (LlamaRuntime.max_seqs) - every query is a chain that keeps
+    num_permutation rows of the pool busy, so one flush can fill it (tools/bench_rankr1.py --session measures the pool; not measured yet);
+    anything else, PRP pairwise included, one query at a time."""
     if kind == "pointwise":
         return max(1, min(16, -(-1600 // max(1, int(hits)))))
     if kind == "setwise":
@@ -238,4 +240,6 @@ def default_queries_per_call(kind: str, hits: int) -> int:
         return 32
     if kind == "duot5":
         return 32
+    if kind == "rankr1":
+        return max(1, int(slots))
     return 1

@@ -99,6 +99,11 @@ ABI = {
     "rk_llama_greedy1": (C.c_int, [C.c_void_p, _i32p, _i32p, C.c_int, _i32p]),
     "rk_llama_last_logits": (C.c_int, [C.c_void_p, _i32p, _i32p, C.c_int, _i32p, C.c_int, _f32p]),
     "rk_llama_generate": (C.c_int, [C.c_void_p, _i32p, _i32p, C.c_int, C.c_int, C.c_int, _i32p, C.c_int, C.c_int, _i32p, _i32p]),
+    "rk_llama_session_open": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, _i32p, C.c_int, C.c_int]),
+    "rk_llama_session_admit": (C.c_int, [C.c_void_p, _i32p, _i32p, _i32p, _i32p, C.c_int]),
+    "rk_llama_session_run": (C.c_int, [C.c_void_p, C.c_int, _i32p, _i32p, _i32p]),
+    "rk_llama_session_read": (C.c_int, [C.c_void_p, C.c_int, _i32p, C.c_int, _i32p]),
+    "rk_llama_session_close": (C.c_int, [C.c_void_p]),
     "rk_comm_unique_id": (C.c_int, [_P(C.c_uint8), C.c_int]),
     "rk_comm_init": (C.c_int, [C.c_void_p, _P(C.c_uint8), C.c_int, C.c_int, C.c_int, C.c_int]),
     "rk_comm_world": (C.c_int, [C.c_void_p, _i32p, _i32p]),
@@ -640,6 +645,68 @@ class RkLlamaEngine(RkEngine):
                                              int(max_total), eos.ctypes.data_as(_i32p), len(eos), int(pad_id),
                                              out.ctypes.data_as(_i32p), C.byref(steps)))
         return out, int(steps.value)
+
+    def session(self, n_slots: int, max_len: int, max_new_cap: int, eos_ids: Sequence[int], pad_id: int) -> "LlamaSession":
+        """A decoding session (rk_llama_session_*): `n_slots` cache slots of `max_len` positions, prompts admitted into free
+        slots while the others decode.  A context manager; one per engine, and generate / greedy1 / last_logits are refused
+        while it is open."""
+        return LlamaSession(self, n_slots, max_len, max_new_cap, eos_ids, pad_id)
+
+
+class LlamaSession:
+    """The five session calls of one RkLlamaEngine.  `busy` is the set of slots that hold a request (decoding, or finished and
+    not yet read)."""
+
+    def __init__(self, eng: RkLlamaEngine, n_slots: int, max_len: int, max_new_cap: int, eos_ids: Sequence[int], pad_id: int):
+        self.eng, self.n_slots, self.max_len, self.max_new_cap = eng, int(n_slots), int(max_len), int(max_new_cap)
+        eos = _i32(list(eos_ids))
+        self.is_open = False
+        eng._chk(eng.lib.rk_llama_session_open(eng.h, self.n_slots, self.max_len, self.max_new_cap, eos.ctypes.data_as(_i32p),
+                                               len(eos), int(pad_id)))
+        self.is_open = True
+        self.busy = set()
+        self.steps = 0                                   # steps issued so far (every step decodes all n_slots rows)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def close(self):
+        if self.is_open and getattr(self.eng, "h", None):
+            self.is_open = False
+            self.eng._chk(self.eng.lib.rk_llama_session_close(self.eng.h))
+
+    def free_slots(self):
+        return [s for s in range(self.n_slots) if s not in self.busy]
+
+    def admit(self, seqs: Sequence[Sequence[int]], slots: Sequence[int], max_new: Sequence[int]) -> None:
+        """ONE prefill of `seqs` into the free slots `slots`; prompt b generates up to max_new[b] tokens."""
+        if not (len(seqs) == len(slots) == len(max_new)):
+            raise ValueError("admit: seqs, slots and max_new must have one entry per prompt")
+        tok, off = pack_ragged(seqs)
+        sl, mn = _i32(list(slots)), _i32(list(max_new))
+        self.eng._chk(self.eng.lib.rk_llama_session_admit(self.eng.h, tok.ctypes.data_as(_i32p), off.ctypes.data_as(_i32p),
+                                                          sl.ctypes.data_as(_i32p), mn.ctypes.data_as(_i32p), len(seqs)))
+        self.busy.update(int(s) for s in sl)
+
+    def run(self, max_steps: int = 1 << 30):
+        """Steps until a slot has newly finished (or nothing is active, or max_steps) -> (finished slots, steps issued)."""
+        fin = np.empty(self.n_slots, dtype=np.int32)
+        n, steps = C.c_int32(0), C.c_int32(0)
+        self.eng._chk(self.eng.lib.rk_llama_session_run(self.eng.h, int(max_steps), fin.ctypes.data_as(_i32p), C.byref(n), C.byref(steps)))
+        self.steps += int(steps.value)
+        return [int(s) for s in fin[:n.value]], int(steps.value)
+
+    def read(self, slot: int) -> np.ndarray:
+        """The finished slot's new tokens (its EOS included); the slot is free afterwards."""
+        out = np.empty(self.max_new_cap, dtype=np.int32)
+        n = C.c_int32(0)
+        self.eng._chk(self.eng.lib.rk_llama_session_read(self.eng.h, int(slot), out.ctypes.data_as(_i32p), len(out), C.byref(n)))
+        self.busy.discard(int(slot))
+        return out[:n.value].copy()
 
 
 def rel_bucket(rel: int, bidirectional: bool, num_buckets: int = 32, max_distance: int = 128) -> int:

@@ -579,12 +579,121 @@ class LlamaRuntime:
                 raise ValueError(f"a prompt of {len(s)} tokens + {max_new} new ones exceeds the engine capacity {self.max_tokens}")
         return self._chunks(seqs)
 
+    def open_pool(self, max_new_cap, eos_ids, pad_id, n_slots=None) -> "DecodePool":
+        """A pool of `n_slots` (default: max_seqs) decoding slots over one engine session: requests are queued with `submit`,
+        `wait` returns completed ones while the rest keep decoding, a finished row's slot goes to the next request.  A request's
+        tokens are what `generate` gives for it alone.  A context manager; the engine's other calls are refused until it is
+        closed."""
+        n_slots = self.max_seqs if n_slots is None else int(n_slots)
+        if not 0 < n_slots <= self.max_seqs:
+            raise ValueError(f"n_slots {n_slots} outside 1..max_seqs {self.max_seqs}")
+        eos_ids, pad_id = list(eos_ids), int(pad_id)
+        return DecodePool(lambda max_len: self.engine.session(n_slots, max_len, int(max_new_cap), eos_ids, pad_id),
+                          n_slots, self.max_tokens, int(max_new_cap))
+
     def greedy1(self, seqs) -> np.ndarray:
         """next token (first arg-max of the last position's logits) of every prompt"""
         return np.concatenate([self.engine.greedy1(c) for c in self._chunks(seqs)], axis=0)
 
     def last_logits(self, seqs, out_ids) -> np.ndarray:
         return np.concatenate([self.engine.last_logits(c, out_ids) for c in self._chunks(seqs)], axis=0)
+
+
+class DecodePool:
+    """The scheduler between callers with many independent greedy requests and ONE decoding session (RkLlamaEngine.session, or a
+    test double with its interface: n_slots, busy, admit, run, read, close).
+
+    submit(key, ids, max_new) queues a request; the queue is FIFO.  wait() fills the free slots from the head of the queue - all
+    of them in ONE admit, as far as the prefill's token capacity goes - runs the session until a slot finishes and returns
+    [(key, new tokens)] of every request that completed (the EOS that ended a row included).  The session is opened at the first
+    wait with max_len = the largest len + max_new queued, rounded up to LEN_STEP positions; a later request that needs more waits
+    at the head of the queue until the running rows have drained, then the session is re-opened with the larger max_len (sizes
+    never shrink, so the steady state re-opens and re-captures nothing)."""
+    LEN_STEP = 512
+
+    def __init__(self, open_session, n_slots: int, max_tokens: int, max_new_cap: int):
+        self._open_session, self.n_slots, self.max_tokens, self.max_new_cap = open_session, int(n_slots), int(max_tokens), int(max_new_cap)
+        self.session = None
+        self.max_len = 0
+        self._queue = []                    # [(key, ids, max_new)] oldest first
+        self._owner = {}                    # slot -> (key, prompt length)
+        self.steps = self.admits = self.opens = self.tokens_out = 0
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def close(self):
+        """Ends the session whatever is still queued or decoding (the engine drains its stream): the engine is usable afterwards."""
+        session, self.session = self.session, None
+        self._queue.clear()
+        self._owner.clear()
+        if session is not None:
+            session.close()
+
+    def submit(self, key, ids, max_new: int):
+        ids, max_new = [int(t) for t in ids], int(max_new)
+        if not ids or max_new <= 0:
+            raise ValueError(f"request {key!r}: an empty prompt or max_new {max_new}")
+        if max_new > self.max_new_cap:
+            raise ValueError(f"request {key!r}: max_new {max_new} exceeds the pool's max_new_cap {self.max_new_cap}")
+        if len(ids) + max_new > self.max_tokens:
+            raise ValueError(f"request {key!r}: a prompt of {len(ids)} tokens + {max_new} new ones exceeds the engine capacity {self.max_tokens}")
+        self._queue.append((key, ids, max_new))
+
+    def pending(self) -> int:
+        """requests queued or decoding"""
+        return len(self._queue) + len(self._owner)
+
+    def _fill(self):
+        """the head of the queue into the free slots: one admit"""
+        if not self._queue:
+            return
+        need = max(len(ids) + max_new for _, ids, max_new in self._queue)
+        if self.session is None or (need > self.max_len and not self._owner):
+            if self.session is not None:
+                self.session.close()
+                self.session = None
+            step = self.LEN_STEP
+            self.max_len = min(max(self.max_len, (need + step - 1) // step * step), self.max_tokens)
+            self.session = self._open_session(self.max_len)
+            self.opens += 1
+        free = [s for s in range(self.n_slots) if s not in self.session.busy]
+        take, tokens = [], 0
+        for key, ids, max_new in self._queue[:len(free)]:
+            if len(ids) + max_new > self.max_len or tokens + len(ids) > self.max_tokens:
+                break                       # (FIFO: nothing overtakes a request that waits for a larger session or the next prefill)
+            take.append((key, ids, max_new))
+            tokens += len(ids)
+        if not take:
+            return
+        slots = free[:len(take)]
+        self.session.admit([ids for _, ids, _ in take], slots, [m for _, _, m in take])
+        self.admits += 1
+        del self._queue[:len(take)]
+        for slot, (key, ids, _) in zip(slots, take):
+            self._owner[slot] = (key, len(ids))
+
+    def wait(self):
+        """Blocks until at least one request is complete -> [(key, tokens)]; [] when nothing is queued or decoding."""
+        while self._queue or self._owner:
+            self._fill()
+            finished, steps = self.session.run()
+            self.steps += steps
+            done = []
+            for slot in finished:
+                key, _ = self._owner.pop(slot)
+                tokens = np.asarray(self.session.read(slot), dtype=np.int32)
+                self.tokens_out += len(tokens)
+                done.append((key, tokens))
+            if done:
+                return done
+            if not self._owner:             # (submit's checks rule it out: an empty session always takes the head of the queue)
+                raise RuntimeError("the head of the queue fits neither the session nor the prefill")
+        return []
 
 
 def generation_plan(runtime, prompt_lens) -> dict:

@@ -33,10 +33,11 @@ QUESTION = 'Given a query "{query}", which of the following passages is the most
 INSTRUCTION = '\n\nOutput only the passage label of the most relevant passage:'
 
 
-def vote(refs, answers, characters, say):
+def vote(refs, answers, characters, say, rng=random):
     """The permutation vote (ref: setwise.py:132-150, 520-548): refs[p] = (docids, labels) of permutation p, answers[p] what
     the model said to it.  Answers that name no label of their permutation are reported through `say` and dropped; the docid
-    named most often wins, a tie is broken by one `random.choice`; no usable answer at all -> "Unexpected voting."."""
+    named most often wins, a tie is broken by one `rng.choice` (the module-level `random` like the reference, unless the caller
+    brings a generator of its own); no usable answer at all -> "Unexpected voting."."""
     candidates = []
     for (docids, labels), answer in zip(refs, answers):
         if answer not in labels:
@@ -48,7 +49,7 @@ def vote(refs, answers, characters, say):
     counts = Counter(candidates)
     top = max(counts.values())
     winners = [c for c, v in counts.items() if v == top]
-    return characters[winners[0] if len(winners) == 1 else random.choice(winners)]
+    return characters[winners[0] if len(winners) == 1 else rng.choice(winners)]
 
 
 class SetwiseLlmRanker(LlmRanker):
@@ -374,7 +375,7 @@ class SetwiseLlmRanker(LlmRanker):
         engine together, one call per step of all the chains - several ~900-token prompts per launch sequence instead of one
         (a compare's result does not depend on what shares its engine call: ragged execution, bit-exact).
         heapsort and bubblesort with the draw-free default settings; anything else (permutation voting, a compare() of a
-        subclass such as Rank-R1's) is one rerank per query."""
+        subclass - Rank-R1's has a rerank_many of its own) is one rerank per query."""
         items = list(items)
         if self.method not in ("heapsort", "bubblesort") or not self._batched_ok() or len(items) < 2:
             out, counters = [], []
@@ -486,7 +487,8 @@ class RankR1SetwiseLlmRanker(SetwiseLlmRanker):
     """Rank-R1, the reasoning setwise reranker (ref: llmrankers/setwise.py:406-553; Qwen2.5-Instruct + a LoRA adapter served by
     vLLM there): one compare = a chat prompt listing the passages as "[n] text", a generated chain of thought of up to
     max_new_tokens tokens, and a regular expression that takes the answer's "[n]" label out of it.  Here the checkpoint (the
-    adapter merged on the host, _runtime.merge_lora) runs on the engine's KV-cached greedy decoder (rk_llama_generate).  Same
+    adapter merged on the host, _runtime.merge_lora) runs on the engine's KV-cached greedy decoder (rk_llama_generate; several
+    queries at once: rerank_many over a decoding session, rk_llama_session_*).  Same
     constructor, compare() contract, counters, vote and sort drivers as the reference; stand-ins for vLLM ("Qwen2 family and Rank-R1"):
     the stop ids are the checkpoint's generation settings, the EOS that ended a row counts as a completion token, the completion
     text is the new tokens decoded without special tokens."""
@@ -538,31 +540,47 @@ class RankR1SetwiseLlmRanker(SetwiseLlmRanker):
         self.total_completion_tokens = 0
         self.total_prompt_tokens = 0
 
+    compare_rng = None    # the generator compare() draws from; None: the module-level `random`, the reference's one global stream
+
     def compare(self, query: str, docs: List):
-        # ref: setwise.py:462-553
-        import re
+        # ref: setwise.py:462-553, in three parts: the prompts (draws), ONE engine call, the verdict (draws on a tie)
+        rng = self.compare_rng if self.compare_rng is not None else random
         self.total_compare += 1 if self.num_permutation == 1 else self.num_permutation
+        batch_ref, input_text, ids = self._compare_prompts(query, docs, rng)
+        gen = self.llm.generation
+        rows = np.asarray(self.llm.generate(ids, self.max_new_tokens, list(gen["eos_token_ids"]), int(gen["pad_token_id"])))   # ONE engine call
+        output, prompt_tokens, completion_tokens = self._compare_verdict(query, batch_ref, input_text, ids, rows, rng)
+        self.total_prompt_tokens += prompt_tokens
+        self.total_completion_tokens += completion_tokens
+        return output
+
+    def _compare_prompts(self, query: str, docs: List, rng):
+        """-> (batch_ref, messages, prompt ids) of the window's num_permutation prompts"""
         id_passage = [(i, p) for i, p in enumerate(docs)]
         labels = [self.CHARACTERS[i] for i in range(len(docs))]
         batch_ref, input_text = [], []
         for _ in range(self.num_permutation):               # one draw per permutation (also for a single one); labels stay in order
-            shuffled = random.sample(id_passage, len(id_passage))
+            shuffled = rng.sample(id_passage, len(id_passage))
             batch_ref.append(([p[0] for p in shuffled], list(labels)))
             passages = "\n".join(f'{c} {p[1].text}' for p, c in zip(shuffled, labels))
             input_text.append([{'role': "system", 'content': self.prompt["prompt_system"]},
                                {'role': "user", 'content': self.prompt['prompt_user'].format(query=query, docs=passages)}])
-        ids = [self._chat_ids(messages) for messages in input_text]
-        gen = self.llm.generation
-        eos_ids = list(gen["eos_token_ids"])
-        rows = np.asarray(self.llm.generate(ids, self.max_new_tokens, eos_ids, int(gen["pad_token_id"])))   # ONE engine call
+        return batch_ref, input_text, [self._chat_ids(messages) for messages in input_text]
+
+    def _compare_verdict(self, query: str, batch_ref, input_text, ids, rows, rng):
+        """rows[p] = the new tokens of prompt p (columns < 0 and whatever follows the EOS that ended the row are not part of it)
+        -> (label, prompt tokens, completion tokens): the regular expression, then the vote"""
+        import re
+        eos_ids = list(self.llm.generation["eos_token_ids"])
+        prompt_tokens = completion_tokens = 0
         results = []
         for prompt_ids, row, messages in zip(ids, rows, input_text):
             new = [int(t) for t in row if t >= 0]
             stop = next((i for i, t in enumerate(new) if t in eos_ids), None)
             if stop is not None:                             # vLLM's token_ids keep the EOS that ended the row
                 new = new[:stop + 1]
-            self.total_completion_tokens += len(new)
-            self.total_prompt_tokens += len(prompt_ids)
+            completion_tokens += len(new)
+            prompt_tokens += len(prompt_ids)
             completion = self.tokenizer.decode(new, skip_special_tokens=True)
             if self.verbose:
                 print('--------------------------------------')
@@ -573,11 +591,66 @@ class RankR1SetwiseLlmRanker(SetwiseLlmRanker):
             match = re.search(rf'{self.prompt["pattern"]}', completion.lower(), re.DOTALL)
             results.append(match.group(1).strip() if match else f'input_text:\n{messages}, completion:\n{completion}')
         say = print if self.verbose else (lambda *_: None)
-        output = vote(batch_ref, [result.strip() for result in results], self.CHARACTERS, say)
+        output = vote(batch_ref, [result.strip() for result in results], self.CHARACTERS, say, rng)
         if output not in self.CHARACTERS:
             say(f"Unexpected voting: {results}")
             say(f"Unexpected output: {output}")
-        return output
+        return output, prompt_tokens, completion_tokens
+
+    def rerank_many(self, items):
+        """Several queries at once over the runtime's decoding pool (LlamaRuntime.open_pool: continuous batching, what vLLM gives
+        the reference): every query is a chain of its own - its pending window's num_permutation prompts are submitted, the window
+        is answered (regular expression, then the vote, as in compare) when all its completions have returned, and that chain alone
+        advances and submits its next window.  No lock step: chains of thought end at any length, and a finished row's slot goes to
+        whichever chain is waiting.
+        Randomness: compare draws (one `sample` per permutation, one `choice` per tied vote), and interleaved queries cannot share
+        one stream reproducibly.  Query i gets its own random.Random(seed_i), seed_i = random.getrandbits(64) drawn from the
+        module-level stream in item order at the start of the call - a documented deviation from the reference's one global stream
+        (DESIGN.md section 4).  results[i], counters[i] and the caller's re-ordered list equal `rerank(*items[i])` run with that
+        generator as `compare_rng`.  One query, or a runtime without a pool: one `rerank` per query on the module-level stream."""
+        items = list(items)
+        if (len(items) < 2 or not hasattr(self.llm, "open_pool") or self.method not in ("heapsort", "bubblesort")
+                or "compare" in self.__dict__):             # (a compare replaced on the instance is the caller's: one at a time)
+            return super().rerank_many(items)
+        rngs = [random.Random(seed) for seed in [random.getrandbits(64) for _ in items]]
+        originals = [[doc.docid for doc in ranking] for _, ranking in items]
+        counts = [[0, 0, 0] for _ in items]
+        chains = [Lockstep({0: self._sort_steps(ranking, False)}) for _, ranking in items]
+        waiting = {}                                         # query -> its pending window: prompts, references, rows so far
+        gen = self.llm.generation
+
+        def submit(pool, q):
+            (docs,) = chains[q].pending()[1]
+            counts[q][0] += 1 if self.num_permutation == 1 else self.num_permutation
+            batch_ref, input_text, ids = self._compare_prompts(items[q][0], docs, rngs[q])
+            waiting[q] = (batch_ref, input_text, ids, {})
+            for p, prompt in enumerate(ids):
+                pool.submit((q, p), prompt, self.max_new_tokens)
+
+        with self.llm.open_pool(max_new_cap=self.max_new_tokens, eos_ids=list(gen["eos_token_ids"]), pad_id=int(gen["pad_token_id"])) as pool:
+            for q in range(len(items)):
+                if chains[q]:
+                    submit(pool, q)
+            while waiting:
+                for (q, p), tokens in pool.wait():
+                    batch_ref, input_text, ids, rows = waiting[q]
+                    rows[p] = tokens
+                    if len(rows) < len(ids):
+                        continue
+                    del waiting[q]
+                    label, prompt_tokens, completion_tokens = self._compare_verdict(items[q][0], batch_ref, input_text, ids,
+                                                                                    [rows[i] for i in range(len(ids))], rngs[q])
+                    counts[q][1] += prompt_tokens
+                    counts[q][2] += completion_tokens
+                    chains[q].advance([label])
+                    if chains[q]:
+                        submit(pool, q)
+        heap = self.method == "heapsort"
+        results = [top_k_then_rest(list(reversed(ranking)) if heap else ranking, original, self.k)
+                   for (_, ranking), original in zip(items, originals)]
+        counters = [tuple(c) for c in counts]
+        self.total_compare, self.total_prompt_tokens, self.total_completion_tokens = counters[-1]
+        return results, counters
 
     def _chat_ids(self, messages) -> List[int]:
         """what vLLM's LLM.chat feeds the model: the chat template with the generation prompt, tokenized"""

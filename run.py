@@ -238,6 +238,14 @@ def build_ranker(args):
     if args.setwise:
         if args.run.openai_key:
             raise NotImplementedError("OpenAI rankers are remote HTTP calls, not part of the MI355X hot path; use the reference")
+        if getattr(args.run, "prompt_file", None):               # the Rank-R1 reasoning reranker (ref: Rank-R1/run_setwise.py:120-132)
+            from llmrankers.setwise import RankR1SetwiseLlmRanker
+            return RankR1SetwiseLlmRanker(model_name_or_path=args.run.model_name_or_path, prompt_file=args.run.prompt_file,
+                                          lora_name_or_path=args.run.lora_name_or_path,
+                                          tokenizer_name_or_path=args.run.tokenizer_name_or_path, device=args.run.device,
+                                          cache_dir=args.run.cache_dir, num_child=args.setwise.num_child, scoring=args.run.scoring,
+                                          method=args.setwise.method, num_permutation=args.setwise.num_permutation, k=args.setwise.k,
+                                          max_new_tokens=args.run.max_new_tokens)
         from llmrankers.setwise import SetwiseLlmRanker
         return SetwiseLlmRanker(model_name_or_path=args.run.model_name_or_path, tokenizer_name_or_path=args.run.tokenizer_name_or_path,
                                 device=args.run.device, cache_dir=args.run.cache_dir, num_child=args.setwise.num_child,
@@ -382,12 +390,15 @@ def main(args):
         if args.pairwise:
             from llmrankers.pairwise import DuoT5LlmRanker
             kind = "duot5" if isinstance(ranker, DuoT5LlmRanker) else "pairwise"
-        per_call = default_queries_per_call(kind, args.run.hits)
+        if args.setwise and getattr(args.run, "prompt_file", None):  # Rank-R1: enough queries to fill the decoding pool's slots
+            kind = "rankr1"
+        per_call = default_queries_per_call(kind, args.run.hits, slots=getattr(getattr(ranker, "llm", None), "max_seqs", 16))
     if per_call > 1 and not hasattr(ranker, "rerank_many"):
         per_call = 1
-    if per_call > 1 and args.run.shuffle_ranking == "random" and getattr(ranker, "num_permutation", 1) > 1:
-        # permutation voting draws from the same global RNG as --shuffle_ranking random: queued queries would be shuffled
-        # before earlier ones have drawn their permutations - a different random sequence than one query at a time
+    draws = getattr(ranker, "num_permutation", 1) > 1 or bool(args.setwise and getattr(args.run, "prompt_file", None))
+    if per_call > 1 and args.run.shuffle_ranking == "random" and draws:
+        # permutation voting (and every Rank-R1 compare) draws from the same global RNG as --shuffle_ranking random: queued
+        # queries would be shuffled before earlier ones have drawn - a different random sequence than one query at a time
         per_call = 1
     pending = []
 
@@ -499,6 +510,12 @@ def build_parser():
     rp.add_argument("--save_path", type=str, help="Path to save the reranked run file (TREC format).")
     rp.add_argument("--model_name_or_path", type=str, help="Local HuggingFace-layout checkpoint directory.")
     rp.add_argument("--tokenizer_name_or_path", type=str, default=None)
+    rp.add_argument("--prompt_file", type=str, default=None,
+                    help="setwise: a Rank-R1 prompt file (TOML: prompt_system, prompt_user, pattern) selects the reasoning reranker "
+                         "RankR1SetwiseLlmRanker (ref: Rank-R1/run_setwise.py)")
+    rp.add_argument("--lora_name_or_path", "--lora_path_or_name", type=str, default=None, dest="lora_name_or_path",
+                    help="Rank-R1: a PEFT LoRA adapter directory, merged into the checkpoint's weights on load")
+    rp.add_argument("--max_new_tokens", type=int, default=2048, help="Rank-R1: tokens of reasoning and answer per compare")
     rp.add_argument("--ir_dataset_name", type=str, default=None)
     rp.add_argument("--pyserini_index", type=str, default=None)
     rp.add_argument("--query_file", type=str, default=None, help="offline source: TSV/JSONL of queries")
@@ -524,7 +541,7 @@ def build_parser():
                     help="pointwise / setwise / listwise / duoT5 pairwise: queries handed to the engine together (same rankings and counters as one at a time); "
                          "0 = auto (llmrankers._batching.default_queries_per_call): pointwise enough queries for >= 1600 passages "
                          f"per call, at most 16 ({_auto_per_call('pointwise', 100)} at hits=100), setwise {_auto_per_call('setwise', 100)} "
-                         f"heapsorts in lockstep, duoT5 {_auto_per_call('duot5', 100)}; with --resume the run file is appended once per call, i.e. every that many queries; "
+                         f"heapsorts in lockstep, duoT5 {_auto_per_call('duot5', 100)}, Rank-R1 (--prompt_file) the runtime's decoding slots; with --resume the run file is appended once per call, i.e. every that many queries; "
                          "1 = the reference's one query at a time (and its per-query flush)")
     pw = commands.add_parser("pointwise")
     pw.add_argument("--method", type=str, default="yes_no", choices=["qlm", "yes_no"])
