@@ -329,7 +329,8 @@ int rk_debug_gemm_ex(rk_engine* e, rk_debug_gemm_call* call);
  *                        or the tree form: tree_rows query rows, row r at position tree_pos[r] sees rows tree_keys[r * Ld + j], j <=
  *                        tree_pos[r].  cross = 1: q [rows, ldq], kv [Tk, ldkv] (k at k_col, v at v_col), seq_off = key offsets, no bias,
  *                        no mask.  out = ctx [rows, ldctx].  Options dec_cross_mfma, dec_attn_seq, xattn_direct.
- *   3 query-side cross   plan_xattn(fuse = false), the chunk kernel and xattn_combine_kernel only: q = qk [M, H, d] (ldq = H d), kv = enc
+ *   3 query-side cross   plan_xattn(fuse = false), the chunk kernel and xattn_combine_kernel only (the whole chain, fused form included:
+ *                        rk_debug_xattn_chain below): q = qk [M, H, d] (ldq = H d), kv = enc
  *                        [T, d] (ldkv = d), seq_off; query m belongs to sequence row_seq[row0 + m] (n_row_seq entries) or (row0 + m) / Ld;
  *                        out [M, H, d] (ldctx = H d) = sum_t softmax_t(qk_h . enc_t) enc_t.  Option xattn_mfma.
  *   4 Llama prefill      plan_llama_attn: q = rotated qkv [T, ldq] (H query heads, n_kv key heads, n_kv value heads of 128), seq_off,
@@ -368,6 +369,50 @@ typedef struct rk_debug_attn_call {
       out_heads_per_wg, out_n_cu;
 } rk_debug_attn_call;
 int rk_debug_attn(rk_engine* e, rk_debug_attn_call* call);
+/* debug: the WHOLE query-side cross-attention chain of one T5 decoder layer on host data (csrc/rk_engine.hip: struct XAttnChain ->
+ * run_xattn_chain, the function run_decoder calls: the fuse decision, the q projection, the loop over blocks of rows, plan_xattn
+ * and the launches of every block; no kernel and no dispatch of its own).  Fused (fuse_asked != 0 and d % 128 == 0): dec_cross_qk_kernel,
+ * the chunk kernel, dec_cross_cv_kernel (beyond DECV_MAXCH chunks: xattn_combine_kernel + the W_v GEMM per head); else the five-launch
+ * form (q GEMM, W_k^T GEMM per head, chunk kernel, xattn_combine_kernel, W_v GEMM per head) - out_fused says which ran.
+ *   x [M, ldx] fp16, wq / wk / wv [H 64, d] fp16 in HF layout (the call regroups W_k as rk_engine_finalize does), enc: the WHOLE
+ *   allocation, band_rows rows in front of and behind the enc_rows interior rows of d elements, bands filled by the caller with finite
+ *   values; seq_off[n_seq + 1]; decoder row m belongs to sequence row_seq[row0 + m] (n_row_seq entries) or (row0 + m) / Ld.
+ *   Norm fold of the q projection: rowscale[M], or ssq_in[M][nb_in] (block sums of squares of x / out_xs: the factor is
+ *   rsqrt(sum / d + out_eps) / out_xs, out_eps = the engine's layer_norm_epsilon), or neither: factor 1.
+ *   ctx: optional interior [M, ldo] the output starts from (ldo >= 64 H: pad columns are the caller's), else sentinel bytes.
+ * Outputs, each the whole device allocation after the call, filled with the byte RK_DEBUG_SENTINEL before it, a band in front and behind:
+ *   qk_all   (band_rows + M + band_rows) x H d fp16
+ *   part_all out_n_blocks x (band_rows H d + R nch H d + band_rows H d) fp32, stat_all out_n_blocks x (band_rows H 2 + R nch H 2 + band_rows H 2)
+ *            fp32, xctx_all out_n_blocks x (band_rows + R + band_rows) x H d fp16, R = min(out_block_rows, M): the workspaces have the size
+ *            of one block of the row loop, are refilled with the sentinel in front of every block and copied out behind it; ws_fill != 0:
+ *            the interiors of part and stat are refilled with this 32-bit pattern instead (0x7F800000, +inf: a chunk no kernel may read
+ *            turns its row into NaN if one does - the engine's workspaces are never initialised)
+ *   ctx_all  (band_rows + M + band_rows) x ldo fp16
+ * plan_only != 0: nothing is allocated or launched, only the out_* fields are filled: out_fused, out_block_rows / out_n_blocks (the row
+ * loop), out_nch, out_n_cu, out_eps / out_xs, and per [first block, last block]: out_qk_R, out_qk_CS (0 when the W_k^T GEMM runs), out_part_kind
+ * (MFMA_FEW 0 / MFMA 1 / VALU16 2 / VALU4 3), out_part_grid, out_fuse_cv, out_cv_R (0 when the merge is not fused).
+ * The five-launch form's q GEMM runs on the weight-streaming family for Ld <= 4 and on the tiled family beyond, as run_decoder's does
+ * (its few-row GEMV family, a choice of the whole decoder pass, is not reachable here); where that GEMM plans onto the persistent
+ * ping-pong kernel, which takes ready-made row factors, ssq_in is refused with RK_ERR_STATE: pass rowscale.
+ * Every extent is checked before anything is launched: RK_ERR_INVALID for d not a multiple of 32, a row whose sequence index is out of
+ * range, leading dimensions or enc_rows too small; RK_ERR_STATE for more than 65536 keys in a sequence or a GEMM of the unfused form
+ * outside its kernel family's contract; nothing is launched after any of them. */
+typedef struct rk_debug_xattn_chain_call {
+  int M, Ld, H, d, n_seq, row0, ldx, ldo, band_rows, fuse_asked;
+  const uint16_t* x;
+  const uint16_t* wq; const uint16_t* wk; const uint16_t* wv;
+  const uint16_t* enc; int64_t enc_rows;
+  const int32_t* seq_off; const int32_t* row_seq; int n_row_seq;
+  const float* rowscale; const float* ssq_in; int nb_in;
+  const uint16_t* ctx;
+  uint16_t* qk_all; float* part_all; float* stat_all; uint16_t* xctx_all; uint16_t* ctx_all;
+  uint32_t ws_fill;
+  int plan_only;
+  int out_fused, out_block_rows, out_n_blocks, out_nch, out_n_cu;
+  int out_qk_R[2], out_qk_CS[2], out_part_kind[2], out_part_grid[2][3], out_fuse_cv[2], out_cv_R[2];
+  float out_eps, out_xs;
+} rk_debug_xattn_chain_call;
+int rk_debug_xattn_chain(rk_engine* e, rk_debug_xattn_chain_call* call);
 /* measurement: average ms per launch of the engine's GEMM kernel at one shape (epi = 0 store f16, 1 residual f32,
  * 2 GEGLU, 3 ReLU, 4 store f32), random operands, `iters` back-to-back launches timed with HIP events */
 int rk_debug_gemm_bench(rk_engine* e, int M, int N, int K, int epi, int iters, float* out_ms);

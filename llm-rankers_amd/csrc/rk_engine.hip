@@ -969,28 +969,84 @@ void launch_xattn_part(rk_engine* e, hipStream_t st, const XAttnPlan& p, const X
   if (!p.fuse_cv) hipLaunchKernelGGL(xattn_combine_kernel, dim3(xa.H, p.nr), dim3(256), 0, st, xa);
 }
 
-// Rows [r0, r0 + p.nr) of decoder layer l.  Fused: x, wq and in1 are the q projection's input, weight and norm; else sl.dq holds
-// q.  row_seq: decoder row -> encoder sequence (tree form) or nullptr.
-int launch_xattn(rk_engine* e, hipStream_t st, Slot& sl, const XAttnPlan& p, int l, int Ld, int r0, const half_t* x,
-                 const half_t* wq, const GemmFold& in1, const int* row_seq) {
-  const rk_model_desc& d = e->d;
-  const int H = d.n_heads, dm = d.d_model, I = e->inner, nr = p.nr;
-  const half_t* wv = e->cross_kv_w + ((size_t)l * 2 * I + I) * dm;
+// W_k of one cross-attention layer ([H * 64, dm], HF layout) regrouped per head and transposed, as dec_cross_qk_kernel and the
+// per-head W_k^T GEMM read it: ckT[h][c][j] = W_k[h * 64 + j][c]
+std::vector<half_t> regroup_ckT(const half_t* wk, int H, int dm) {
+  std::vector<half_t> t((size_t)H * 64 * dm);
+  for (int h = 0; h < H; ++h)
+    for (int c = 0; c < dm; ++c)
+      for (int j = 0; j < 64; ++j) t[((size_t)h * dm + c) * 64 + j] = wk[((size_t)h * 64 + j) * dm + c];
+  return t;
+}
+
+// The whole query-side cross-attention chain of one decoder layer over M rows: what run_xattn_chain reads of a call.  run_decoder
+// fills it from its slot and layer, rk_debug_xattn_chain from host operands.
+struct XAttnChain {
+  const half_t* x; int ldx;                   // [M, ldx] input of the q projection (the norm folded: fold, or the normalised rows)
+  const half_t *wq, *wkT, *wv;                // [H * 64, dm], [H][dm][64] (regroup_ckT), [H * 64, dm]
+  GemmFold fold;                              // the q projection's norm hooks: rowscale, or ssq_in / nb_in, or neither
+  GemmFamily family;                          // kernel family of the q projection when it is a GEMM of its own
+  const half_t* enc; const int* seq_off; const int* row_seq; int Ld, row0;   // encoder rows; decoder row row0 + m -> sequence (XAttnArgs)
+  half_t* q;                                  // [M, H * 64] workspace: q of the unfused form
+  half_t* qk; float* part; float* stat; half_t* xctx;   // workspaces of ONE block of rows (xattn_block_rows)
+  half_t* ctx; int ldo;                       // [M, ldo] out: column h * 64 + n
+  int M, H, dm, maxL, T;                      // rows, heads, model width, the longest sequence, encoder tokens (profile only)
+  bool fuse_asked;                            // the caller's regime asks for the fused projections (run_decoder)
+};
+// the fused form needs eight K ranges of whole k16 steps per workgroup; other widths take the five-launch form
+inline bool xattn_chain_fused(const XAttnChain& c) { return c.fuse_asked && c.dm % 128 == 0; }
+// rows per block: what the workspaces of one pass hold
+inline int xattn_block_rows(int maxL) { return std::max(1, std::min(XA_MAX_ROWS, XA_MAX_CHUNKS / ((maxL + 63) / 64))); }
+// the three GEMMs of the unfused form: q = W_q x over all rows, then per block qk_h = W_k,h^T q_h and ctx_h = W_v,h (.) per head
+inline Gemm xattn_q_gemm(const XAttnChain& c) {
+  return Gemm(PC_DEC_GEMM, EPI_STORE_F16, c.x, c.ldx, c.wq, c.dm, c.q, c.H * 64, c.M, c.H * 64, c.dm).on(c.family).with(c.fold);
+}
+inline Gemm xattn_qk_gemm(const XAttnChain& c, int r0, int nr, half_t* qk) {
+  const int I = c.H * 64;
+  return Gemm(PC_DEC_GEMM, EPI_STORE_F16, c.q + (size_t)r0 * I, I, c.wkT, 64, qk, c.H * c.dm, nr, c.dm, 64).heads(c.H, 64, (long)c.dm * 64, c.dm);
+}
+inline Gemm xattn_cv_gemm(const XAttnChain& c, int r0, int nr) {
+  return Gemm(PC_DEC_GEMM, EPI_STORE_F16, c.xctx, c.H * c.dm, c.wv, c.dm, c.ctx + (size_t)r0 * c.ldo, c.ldo, nr, 64, c.dm).heads(c.H, c.dm, (long)64 * c.dm, 64);
+}
+
+// Rows [r0, r0 + p.nr) of the chain, their qk going to `qk` (the block's workspace).  Fused: c.x, c.wq and c.fold are the q projection's input, weight and norm; else c.q holds q.
+int launch_xattn(rk_engine* e, hipStream_t st, const XAttnChain& c, const XAttnPlan& p, int r0, half_t* qk) {
+  const int H = c.H, dm = c.dm, I = H * 64, nr = p.nr;
   int rc = RK_OK;
   if (p.fuse_qk) {
-    DecQKArgs qa{x + (size_t)r0 * dm, dm, wq, e->dec[l].ckT, sl.xqk, nr, dm, H, in1.rowscale ? in1.rowscale + r0 : nullptr,
-                 in1.ssq_in ? in1.ssq_in + (size_t)r0 * in1.nb_in : nullptr, in1.nb_in, d.eps, RK_XRAW_SCALE, p.qk_R, p.qk_CS};
+    DecQKArgs qa{c.x + (size_t)r0 * c.ldx, c.ldx, c.wq, c.wkT, qk, nr, dm, H, c.fold.rowscale ? c.fold.rowscale + r0 : nullptr,
+                 c.fold.ssq_in ? c.fold.ssq_in + (size_t)r0 * c.fold.nb_in : nullptr, c.fold.nb_in, e->d.eps, RK_XRAW_SCALE, p.qk_R, p.qk_CS};
     Bracket br(e, st, PC_DEC_GEMM, 2.0 * nr * (double)dm * I * 2, 2.0 * ((double)I * dm * 2 + (double)nr * H * dm));
     hipLaunchKernelGGL(dec_cross_qk_kernel, dim3(H, (nr + p.qk_R - 1) / p.qk_R, p.qk_CS), dim3(64 * DEC_NW), 0, st, qa);
   } else {
-    RC(gemm(e, st, Gemm(PC_DEC_GEMM, EPI_STORE_F16, sl.dq + (size_t)r0 * I, I, e->dec[l].ckT, 64, sl.xqk, H * dm, nr, dm, 64).heads(H, 64, (long)dm * 64, dm)));
+    RC(gemm(e, st, xattn_qk_gemm(c, r0, nr, qk)));
   }
-  launch_xattn_part(e, st, p, XAttnArgs{sl.xqk, sl.enc_out, sl.d_seq_off, sl.xpart, sl.xstat, sl.xctx, Ld, H, dm, p.nch, r0, row_seq}, sl.maxL, sl.T);
-  if (!p.fuse_cv)
-    return gemm(e, st, Gemm(PC_DEC_GEMM, EPI_STORE_F16, sl.xctx, H * dm, wv, dm, sl.dctx + (size_t)r0 * I, I, nr, 64, dm).heads(H, dm, (long)64 * dm, 64));
-  DecCVArgs ca{sl.xpart, sl.xstat, sl.d_seq_off, row_seq, Ld, r0, wv, sl.dctx + (size_t)r0 * I, nr, dm, H, p.nch, I, p.cv_R};
+  launch_xattn_part(e, st, p, XAttnArgs{qk, c.enc, c.seq_off, c.part, c.stat, c.xctx, c.Ld, H, dm, p.nch, c.row0 + r0, c.row_seq}, c.maxL, c.T);
+  if (!p.fuse_cv) return gemm(e, st, xattn_cv_gemm(c, r0, nr));
+  DecCVArgs ca{c.part, c.stat, c.seq_off, c.row_seq, c.Ld, c.row0 + r0, c.wv, c.ctx + (size_t)r0 * c.ldo, nr, dm, H, p.nch, c.ldo, p.cv_R};
   Bracket br(e, st, PC_DEC_GEMM, 2.0 * nr * (double)dm * I, 2.0 * (double)I * dm + 4.0 * (double)nr * p.nch * H * dm);
   launch_lds<dec_cross_cv_kernel>(st, dim3(H, (nr + p.cv_R - 1) / p.cv_R), dim3(64 * DEC_NW), (int)dec_cv_lds_bytes(dm, p.cv_R), 160 * 1024, ca);
+  return RK_OK;
+}
+
+// The chain over all M rows: the fuse decision, the q projection as a GEMM of its own when not fused, then blocks of rows that fit
+// the workspaces, each planned by plan_xattn.  between (optional; the debug call): called in front of every block's launches and
+// behind them with the block's first row and plan (front = true / false); in front it may give the block another qk workspace than
+// c.qk through *qk (the debug call keeps every block's qk); the chain itself is never changed.  A non-zero return ends the chain
+// with that status.
+struct XAttnChainHook { int (*fn)(void* user, bool front, int r0, const XAttnPlan& p, half_t** qk); void* user; };
+int run_xattn_chain(rk_engine* e, hipStream_t st, const XAttnChain& c, const XAttnChainHook* between = nullptr) {
+  const bool fuse = xattn_chain_fused(c);
+  int rc = RK_OK;
+  if (!fuse) RC(gemm(e, st, xattn_q_gemm(c)));
+  const int blk = xattn_block_rows(c.maxL);
+  for (int r0 = 0; r0 < c.M; r0 += blk) {
+    const XAttnPlan xp = plan_xattn(e, fuse, std::min(blk, c.M - r0), c.maxL, c.H, c.dm);
+    half_t* qk = c.qk;
+    if (between) RC(between->fn(between->user, true, r0, xp, &qk));
+    RC(launch_xattn(e, st, c, xp, r0, qk));
+    if (between) RC(between->fn(between->user, false, r0, xp, &qk));
+  }
   return RK_OK;
 }
 
@@ -1155,7 +1211,6 @@ int run_decoder(rk_engine* e, Slot& sl, int Ld, const DecRows* rows = nullptr, c
   // spread the cold weights of a layer over 512 + 5120 workgroups).  The family follows from the CALL SHAPE, never from the batch
   // (the two round differently): fused for one decoder position, separate beyond (dec_fuse = 2 forces the fused form: tests)
   const bool fuse_asked = e->opt.dec_fuse == 2 || (e->opt.dec_fuse == 1 && lc.one);
-  const bool fuse = fuse_asked && !have_kv && dm % 128 == 0;   // (eight K ranges of whole k16 steps per workgroup)
   const bool few = dfold && e->opt.dec_gemv && !lc.one && M <= e->opt.dec_gemv_rows && !fuse_asked &&
                    gemv_fits(M, dm) && gemv_fits(M, I) && gemv_fits(M, F);   // every K of the pass's projections
   const GemmFamily fam = few ? GEMM_GEMV : (ws ? GEMM_STREAM : GEMM_TILED);
@@ -1195,17 +1250,14 @@ int run_decoder(rk_engine* e, Slot& sl, int Ld, const DecRows* rows = nullptr, c
       }
       RC(resid(Gemm(PC_DEC_GEMM, EPI_RESID_F32, sl.dctx, I, w.o, I, ns.hidden, dm, M, dm, I)));
     }
-    // the cross-attention q projection: a GEMM of its own, or fused into launch_xattn's first kernel, which takes the same norm hooks
+    // the cross-attention q projection: a GEMM of its own, or fused into the chain's first kernel, which takes the same norm hooks
     const Gemm cq = normed(w.ln1, Gemm(PC_DEC_GEMM, EPI_STORE_F16, ns.x(), dm, dfold ? w.cq_f : w.cq, dm, sl.dq, I, M, I, dm));
-    if (!fuse) RC(gemm(e, st, cq));
     if (!have_kv) {
-      // in blocks of rows that fit the workspace
-      const int blk = std::max(1, std::min(XA_MAX_ROWS, XA_MAX_CHUNKS / ((sl.maxL + 63) / 64)));
-      for (int r0 = 0; r0 < M; r0 += blk) {
-        const XAttnPlan xp = plan_xattn(e, fuse, std::min(blk, M - r0), sl.maxL, d.n_heads, dm);
-        RC(launch_xattn(e, st, sl, xp, l, Ld, r0, cq.A, cq.W, cq.fold, rows ? rows->seq : nullptr));
-      }
+      RC(run_xattn_chain(e, st, XAttnChain{cq.A, cq.lda, cq.W, w.ckT, e->cross_kv_w + ((size_t)l * 2 * I + I) * dm, cq.fold, cq.family,
+                                           sl.enc_out, sl.d_seq_off, rows ? rows->seq : nullptr, Ld, 0, sl.dq, sl.xqk, sl.xpart, sl.xstat, sl.xctx,
+                                           sl.dctx, I, M, d.n_heads, dm, sl.maxL, sl.T, fuse_asked}));
     } else {
+      RC(gemm(e, st, cq));
       const half_t* kv = sl.cross_kv + (size_t)l * d.max_tokens * 2 * I;
       launch_dec_attn(e, st, cross_plan, AttnDecArgs{sl.dq, I, kv, kv + I, 2 * I, seq_off, sl.dctx, I, nullptr, Ld, 0, sl.maxL, nullptr, nullptr, 0,
                                                        ragged ? rows->row_off : nullptr},
@@ -1855,14 +1907,7 @@ int rk_engine_finalize(rk_engine* e) {
     RC(up_h(&w.o, H(p + ".0.SelfAttention.o.weight")));
     RC(up_h(&w.cq, H(p + ".1.EncDecAttention.q.weight")));
     RC(up_h(&w.co, H(p + ".1.EncDecAttention.o.weight")));
-    {   // W_k regrouped per head and transposed: ckT[h][c][j] = W_k[h*64 + j][c]
-      const auto& wk = H(p + ".1.EncDecAttention.k.weight");
-      std::vector<half_t> t((size_t)I * dm);
-      for (int h = 0; h < d.n_heads; ++h)
-        for (int c = 0; c < dm; ++c)
-          for (int j = 0; j < 64; ++j) t[((size_t)h * dm + c) * 64 + j] = wk[((size_t)h * 64 + j) * dm + c];
-      RC(up_h(&w.ckT, t));
-    }
+    RC(up_h(&w.ckT, regroup_ckT(H(p + ".1.EncDecAttention.k.weight").data(), d.n_heads, dm)));
     RC(up_h(&w.ffn_in, ffn_in(p + ".2.DenseReluDense")));
     RC(up_h(&w.ffn_out, H(p + ".2.DenseReluDense.wo.weight")));
     RC(up_f(&w.ln0, Fv(p + ".0.layer_norm.weight")));
@@ -3458,6 +3503,154 @@ int rk_debug_attn(rk_engine* e, rk_debug_attn_call* q) {
   DBG_HIP(hipGetLastError());
   DBG_HIP(hipMemcpy(q->out_all, dO, o_all * 2, hipMemcpyDeviceToHost));
   if (dC) DBG_HIP(hipMemcpy(q->cache_all, dC, c_all * 2, hipMemcpyDeviceToHost));
+#undef DBG_HIP
+  return done(RK_OK);
+}
+
+// debug: the whole query-side cross-attention chain of one decoder layer on host operands (include/rk_engine.h).  No kernel and no
+// dispatch of its own: it uploads the operands, regroups W_k as finalize does, fills an XAttnChain and calls run_xattn_chain - the
+// function run_decoder calls.  The workspaces of a block are refilled with the sentinel in front of every block and copied out
+// behind it.
+int rk_debug_xattn_chain(rk_engine* e, rk_debug_xattn_chain_call* q) {
+  if (!e || !q) return RK_ERR_INVALID;
+  int rc = set_device(e);
+  if (rc) return rc;
+  if (!e->finalized) return fail(e, RK_ERR_STATE, "debug xattn chain: engine not finalized");
+  if (e->family != 0) return fail(e, RK_ERR_STATE, "debug xattn chain: needs a T5 engine");
+  const int M = q->M, H = q->H, d = q->d, Ld = q->Ld, B = q->n_seq, band = q->band_rows, I = H * 64;
+  if (B <= 0 || B > (1 << 16) || H <= 0 || H > 1024) return fail(e, RK_ERR_INVALID, "debug xattn chain: n_seq and H");
+  if (M <= 0 || M > (1 << 16) || d <= 0 || d % 32 || d > 16384 || Ld <= 0 || q->row0 < 0)
+    return fail(e, RK_ERR_INVALID, "debug xattn chain: M, Ld, row0 and d (a multiple of 32)");
+  if (!q->seq_off || q->seq_off[0] != 0) return fail(e, RK_ERR_INVALID, "debug xattn chain: seq_off[n_seq + 1] starting at 0");
+  int maxL = 0;
+  for (int b = 0; b < B; ++b) {
+    const int L = q->seq_off[b + 1] - q->seq_off[b];
+    if (L <= 0 || L > (1 << 20)) return fail(e, RK_ERR_INVALID, "debug xattn chain: sequence %d has %d keys", b, L);
+    maxL = std::max(maxL, L);
+  }
+  const int T = q->seq_off[B];
+  if (maxL > 65536) return fail(e, RK_ERR_STATE, "debug xattn chain: the chunk merge takes sequences of at most 65536 keys");
+  for (int m = 0; m < M; ++m) {
+    if (q->row_seq && q->row0 + m >= q->n_row_seq) return fail(e, RK_ERR_INVALID, "debug xattn chain: row_seq has %d entries, row %d is read", q->n_row_seq, q->row0 + m);
+    const int b = q->row_seq ? q->row_seq[q->row0 + m] : (q->row0 + m) / Ld;
+    if (b < 0 || b >= B) return fail(e, RK_ERR_INVALID, "debug xattn chain: row %d belongs to sequence %d of %d", q->row0 + m, b, B);
+  }
+  if (q->rowscale && q->ssq_in) return fail(e, RK_ERR_INVALID, "debug xattn chain: rowscale or ssq_in, not both");
+  if (q->ssq_in && (q->nb_in <= 0 || q->nb_in > 4096)) return fail(e, RK_ERR_INVALID, "debug xattn chain: ssq_in needs nb_in in 1..4096");
+  // ---- the plan: of the first and of the last block of the row loop ----
+  XAttnChain c{};
+  c.ldx = q->ldx; c.Ld = Ld; c.row0 = q->row0; c.ldo = q->ldo; c.M = M; c.H = H; c.dm = d; c.maxL = maxL; c.T = T; c.fuse_asked = q->fuse_asked != 0;
+  c.family = dec_len_class(e, Ld).stream ? GEMM_STREAM : GEMM_TILED;
+  const bool fuse = xattn_chain_fused(c);
+  const int blk = xattn_block_rows(maxL), n_blocks = (M + blk - 1) / blk, wrows = std::min(blk, M), nch = (maxL + 63) / 64;
+  q->out_fused = fuse; q->out_block_rows = blk; q->out_n_blocks = n_blocks; q->out_nch = nch; q->out_n_cu = e->n_cu;
+  q->out_eps = e->d.eps; q->out_xs = RK_XRAW_SCALE;
+  for (int i = 0; i < 2; ++i) {
+    const int r0 = i ? (n_blocks - 1) * blk : 0;
+    const XAttnPlan xp = plan_xattn(e, fuse, std::min(blk, M - r0), maxL, H, d);
+    q->out_qk_R[i] = xp.fuse_qk ? xp.qk_R : 0; q->out_qk_CS[i] = xp.fuse_qk ? xp.qk_CS : 0; q->out_part_kind[i] = (int)xp.part;
+    q->out_part_grid[i][0] = (int)xp.part_grid.x; q->out_part_grid[i][1] = (int)xp.part_grid.y; q->out_part_grid[i][2] = (int)xp.part_grid.z;
+    q->out_fuse_cv[i] = xp.fuse_cv; q->out_cv_R[i] = xp.fuse_cv ? xp.cv_R : 0;
+  }
+  if (q->plan_only) return RK_OK;
+  // ---- extents, from the addressing of the chain, against what the caller gave ----
+  if (!q->x || !q->wq || !q->wk || !q->wv || !q->enc || !q->qk_all || !q->part_all || !q->stat_all || !q->xctx_all || !q->ctx_all || band < 1)
+    return fail(e, RK_ERR_INVALID, "debug xattn chain: x, wq, wk, wv, enc, the five outputs and band_rows >= 1");
+  if (q->ldx < d || q->ldx % 8 || q->ldx > (1 << 20) || q->ldo < I || q->ldo % 8 || q->ldo > (1 << 20))
+    return fail(e, RK_ERR_INVALID, "debug xattn chain: leading dimensions (ldx %d >= %d, ldo %d >= %d; multiples of 8, at most 2^20)", q->ldx, d, q->ldo, I);
+  if (q->enc_rows < T) return fail(e, RK_ERR_INVALID, "debug xattn chain: the call reaches beyond enc (%d of %ld rows)", T, (long)q->enc_rows);
+  const size_t Hd = (size_t)H * d;
+  const size_t part_in = (size_t)wrows * nch * Hd, part_band = (size_t)band * Hd, part_all = part_in + 2 * part_band;
+  const size_t stat_in = (size_t)wrows * nch * H * 2, stat_band = (size_t)band * H * 2, stat_all = stat_in + 2 * stat_band;
+  const size_t xc_in = (size_t)wrows * Hd, xc_all = xc_in + 2 * part_band;
+  const size_t qk_all = ((size_t)M + 2 * band) * Hd, ctx_band = (size_t)band * q->ldo, ctx_in = (size_t)M * q->ldo, ctx_all = ctx_in + 2 * ctx_band;
+  const size_t enc_all = ((size_t)q->enc_rows + 2 * band) * d;
+  if (enc_all >= (1ul << 31) || qk_all >= (1ul << 31) || part_all >= (1ul << 31) || stat_all >= (1ul << 31) || ctx_all >= (1ul << 31) || (size_t)M * q->ldx >= (1ul << 31))
+    return fail(e, RK_ERR_INVALID, "debug xattn chain: operands of 2^31 elements or more");
+  std::vector<void*> dev;
+  auto alloc = [&](size_t bytes, int fill) -> void* {
+    void* ptr = nullptr;
+    if (hipMalloc(&ptr, bytes ? bytes : 16) != hipSuccess) return nullptr;
+    dev.push_back(ptr);
+    if (fill >= 0 && hipMemset(ptr, fill, bytes) != hipSuccess) return nullptr;
+    return ptr;
+  };
+  auto done = [&](int r) { for (void* ptr : dev) hipFree(ptr); return r; };
+#define DBG_HIP(x) do { if ((x) != hipSuccess) return done(fail(e, RK_ERR_HIP, "debug xattn chain: %s", #x)); } while (0)
+  auto up = [&](const void* src, size_t bytes) -> void* {
+    void* ptr = alloc(bytes, -1);
+    if (ptr && hipMemcpy(ptr, src, bytes, hipMemcpyHostToDevice) != hipSuccess) return nullptr;
+    return ptr;
+  };
+  const std::vector<half_t> ckT = regroup_ckT((const half_t*)q->wk, H, d);
+  half_t* dX = (half_t*)up(q->x, (size_t)M * q->ldx * 2);
+  half_t* dWq = (half_t*)up(q->wq, (size_t)I * d * 2);
+  half_t* dWkT = (half_t*)up(ckT.data(), (size_t)I * d * 2);
+  half_t* dWv = (half_t*)up(q->wv, (size_t)I * d * 2);
+  half_t* dEnc = (half_t*)up(q->enc, enc_all * 2);
+  int* dOff = (int*)up(q->seq_off, (size_t)(B + 1) * 4);
+  int* dRs = q->row_seq ? (int*)up(q->row_seq, (size_t)q->n_row_seq * 4) : nullptr;
+  float* dScale = q->rowscale ? (float*)up(q->rowscale, (size_t)M * 4) : nullptr;
+  float* dSsq = q->ssq_in ? (float*)up(q->ssq_in, (size_t)M * q->nb_in * 4) : nullptr;
+  half_t* dQ = (half_t*)alloc((size_t)M * I * 2, RK_DEBUG_SENTINEL);
+  half_t* dQk = (half_t*)alloc(qk_all * 2, RK_DEBUG_SENTINEL);
+  float* dPart = (float*)alloc(part_all * 4, RK_DEBUG_SENTINEL);
+  float* dStat = (float*)alloc(stat_all * 4, RK_DEBUG_SENTINEL);
+  half_t* dXc = (half_t*)alloc(xc_all * 2, RK_DEBUG_SENTINEL);
+  half_t* dCtx = (half_t*)alloc(ctx_all * 2, RK_DEBUG_SENTINEL);
+  if (!dX || !dWq || !dWkT || !dWv || !dEnc || !dOff || (q->row_seq && !dRs) || (q->rowscale && !dScale) || (q->ssq_in && !dSsq) || !dQ || !dQk ||
+      !dPart || !dStat || !dXc || !dCtx)
+    return done(fail(e, RK_ERR_HIP, "debug xattn chain: device allocation or upload failed"));
+  if (q->ctx) DBG_HIP(hipMemcpy(dCtx + ctx_band, q->ctx, ctx_in * 2, hipMemcpyHostToDevice));
+  c.x = dX; c.wq = dWq; c.wkT = dWkT; c.wv = dWv;
+  c.fold.rowscale = dScale; c.fold.ssq_in = dSsq; c.fold.nb_in = q->ssq_in ? q->nb_in : 0;
+  c.enc = dEnc + (size_t)band * d; c.seq_off = dOff; c.row_seq = dRs;
+  c.q = dQ; c.qk = dQk + (size_t)band * Hd; c.part = dPart + part_band; c.stat = dStat + stat_band; c.xctx = dXc + part_band;
+  c.ctx = dCtx + ctx_band;
+  hipStream_t st = e->slots[0].se;
+  // the GEMMs of the unfused form against the contract of their kernel family, before anything is launched
+  if (!fuse || nch > DECV_MAXCH) {
+    std::vector<Gemm> gs;
+    if (!fuse) { gs.push_back(xattn_q_gemm(c)); gs.push_back(xattn_qk_gemm(c, 0, wrows, c.qk)); }
+    gs.push_back(xattn_cv_gemm(c, 0, wrows));
+    for (const Gemm& g : gs) {
+      const GemmPlan gp = plan_gemm(e, g, st);
+      // (run_decoder hands a GEMM on the persistent ping-pong kernel ready-made row factors - NormStream::consumer; this call does not)
+      if (q->ssq_in && &g == &gs[0] && !fuse && gp.pp2())
+        return done(fail(e, RK_ERR_STATE, "debug xattn chain: the q GEMM of this shape takes ready-made row factors: pass rowscale, not ssq_in"));
+      if (gp.family == GEMM_NONE) return done(fail(e, RK_ERR_STATE, "debug xattn chain: no kernel takes the GEMM M=%d N=%d K=%d of the unfused form: %s", g.M, g.N, g.K, gp.why ? gp.why : ""));
+    }
+  }
+  // the qk workspace holds ONE block in the engine; here every block has rows of its own in qk_all (the front hook hands them out), the part / stat / xctx workspaces are refilled in front of a block and copied out behind it
+  struct Ctx { rk_engine* e; rk_debug_xattn_chain_call* q; const XAttnChain* c; hipStream_t st; half_t* qk0; float *dPart, *dStat; half_t* dXc;
+               size_t Hd, part_all, stat_all, xc_all, part_in, stat_in; int blk; } hc{e, q, &c, st, c.qk, dPart, dStat, dXc, Hd, part_all, stat_all, xc_all, part_in, stat_in, blk};
+  XAttnChainHook hook{[](void* user, bool front, int r0, const XAttnPlan&, half_t** qk) -> int {
+    Ctx& h = *(Ctx*)user;
+    const int k = r0 / h.blk;
+    bool ok = true;
+    if (front) {
+      *qk = h.qk0 + (size_t)r0 * h.Hd;
+      ok = hipMemsetAsync(h.dPart, RK_DEBUG_SENTINEL, h.part_all * 4, h.st) == hipSuccess && hipMemsetAsync(h.dStat, RK_DEBUG_SENTINEL, h.stat_all * 4, h.st) == hipSuccess &&
+           hipMemsetAsync(h.dXc, RK_DEBUG_SENTINEL, h.xc_all * 2, h.st) == hipSuccess;
+      if (ok && h.q->ws_fill)   // the caller's 32-bit pattern in the interiors (e.g. +inf: a chunk that must not be read poisons its row)
+        ok = hipMemsetD32Async((hipDeviceptr_t)h.c->part, (int)h.q->ws_fill, h.part_in, h.st) == hipSuccess &&
+             hipMemsetD32Async((hipDeviceptr_t)h.c->stat, (int)h.q->ws_fill, h.stat_in, h.st) == hipSuccess;
+    } else {
+      ok = hipStreamSynchronize(h.st) == hipSuccess && hipGetLastError() == hipSuccess &&
+           hipMemcpy(h.q->part_all + (size_t)k * h.part_all, h.dPart, h.part_all * 4, hipMemcpyDeviceToHost) == hipSuccess &&
+           hipMemcpy(h.q->stat_all + (size_t)k * h.stat_all, h.dStat, h.stat_all * 4, hipMemcpyDeviceToHost) == hipSuccess &&
+           hipMemcpy(h.q->xctx_all + (size_t)k * h.xc_all, h.dXc, h.xc_all * 2, hipMemcpyDeviceToHost) == hipSuccess;
+    }
+    if (!ok) { return fail(h.e, RK_ERR_HIP, "debug xattn chain: a HIP call failed at the block of row %d", r0); }
+    return RK_OK;
+  }, &hc};
+  DBG_HIP(hipDeviceSynchronize());
+  rc = run_xattn_chain(e, st, c, &hook);
+  if (rc) { hipStreamSynchronize(st); return done(rc); }
+  DBG_HIP(hipStreamSynchronize(st));
+  DBG_HIP(hipGetLastError());
+  DBG_HIP(hipMemcpy(q->qk_all, dQk, qk_all * 2, hipMemcpyDeviceToHost));
+  DBG_HIP(hipMemcpy(q->ctx_all, dCtx, ctx_all * 2, hipMemcpyDeviceToHost));
 #undef DBG_HIP
   return done(RK_OK);
 }

@@ -63,6 +63,18 @@ class RkDebugAttnCall(C.Structure):
                                        "out_heads_per_wg", "out_n_cu")]
 
 
+class RkDebugXattnChainCall(C.Structure):
+    """rk_debug_xattn_chain_call of include/rk_engine.h, field for field."""
+    _fields_ = [(n, C.c_int) for n in ("M", "Ld", "H", "d", "n_seq", "row0", "ldx", "ldo", "band_rows", "fuse_asked")] + \
+               [("x", C.c_void_p), ("wq", C.c_void_p), ("wk", C.c_void_p), ("wv", C.c_void_p), ("enc", C.c_void_p), ("enc_rows", C.c_int64),
+                ("seq_off", C.c_void_p), ("row_seq", C.c_void_p), ("n_row_seq", C.c_int), ("rowscale", C.c_void_p), ("ssq_in", C.c_void_p),
+                ("nb_in", C.c_int), ("ctx", C.c_void_p), ("qk_all", C.c_void_p), ("part_all", C.c_void_p), ("stat_all", C.c_void_p),
+                ("xctx_all", C.c_void_p), ("ctx_all", C.c_void_p), ("ws_fill", C.c_uint32), ("plan_only", C.c_int)] + \
+               [(n, C.c_int) for n in ("out_fused", "out_block_rows", "out_n_blocks", "out_nch", "out_n_cu")] + \
+               [("out_qk_R", C.c_int * 2), ("out_qk_CS", C.c_int * 2), ("out_part_kind", C.c_int * 2), ("out_part_grid", (C.c_int * 3) * 2),
+                ("out_fuse_cv", C.c_int * 2), ("out_cv_R", C.c_int * 2), ("out_eps", C.c_float), ("out_xs", C.c_float)]
+
+
 DEBUG_SENTINEL = 0xCD                      # RK_DEBUG_SENTINEL: the byte the guard bands of rk_debug_gemm_ex are filled with
 DEBUG_BAND_ROWS = 256
 GEMM_OUT_DTYPE = {0: np.float16, 1: np.float32, 2: np.float16, 3: np.float16, 4: np.float32, 5: np.float16, 6: np.float32, 7: np.float32}
@@ -129,6 +141,7 @@ ABI = {
     "rk_debug_gemm": (C.c_int, [C.c_void_p, _P(C.c_uint16), _P(C.c_uint16), _f32p, C.c_int, C.c_int, C.c_int, C.c_int]),
     "rk_debug_gemm_ex": (C.c_int, [C.c_void_p, _P(RkDebugGemmCall)]),
     "rk_debug_attn": (C.c_int, [C.c_void_p, _P(RkDebugAttnCall)]),
+    "rk_debug_xattn_chain": (C.c_int, [C.c_void_p, _P(RkDebugXattnChainCall)]),
     "rk_debug_gemm_bench": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _f32p]),
     "rk_debug_read": (C.c_int64, [C.c_void_p, C.c_char_p, _f32p, C.c_int64]),
 }
@@ -583,6 +596,87 @@ class RkEngine:
                 res[k[4:]] = v if isinstance(v, int) else tuple(v)
         if not plan_only:
             res.update(out=out_all, cache=cache_all)
+        return res
+
+    def debug_xattn_chain(self, *, M: int, Ld: int, H: int, d: int, seq_off, x=None, wq=None, wk=None, wv=None, enc=None, row0=0, row_seq=None,
+                          rowscale=None, ssq_in=None, ctx=None, ldo=0, band_rows=8, fuse_asked=True, ws_fill=0, plan_only=False) -> dict:
+        """The decoder's query-side cross-attention chain through rk_debug_xattn_chain (include/rk_engine.h).  x [M, ldx], wq / wk / wv
+        [H 64, d], enc [band_rows + T + band_rows, d] (the caller's bands), ctx [M, ldo] (the pre-filled interior) or None: fp16.
+        Returns the plan fields and, unless plan_only, the whole device allocations after the call: "qk" [band_rows + M + band_rows,
+        H, d], "ctx" [band_rows + M + band_rows, ldo], and per block of the row loop "part" [n_blocks, band_rows H d + R nch H d +
+        band_rows H d], "stat" [n_blocks, band_rows H 2 + R nch H 2 + band_rows H 2] fp32 and "xctx" [n_blocks, band_rows + R + band_rows,
+        H d], R = min(block_rows, M).  The host buffers hold sentinel bytes before the call; a refused call raises RkError with them
+        in its `outputs` attribute (a call that launched nothing leaves them as they were)."""
+        c = RkDebugXattnChainCall()
+        seq_off = np.ascontiguousarray(seq_off, dtype=np.int32)
+        ldo = ldo or 64 * H
+        c.M, c.Ld, c.H, c.d, c.n_seq, c.row0, c.ldo, c.band_rows = M, Ld, H, d, seq_off.size - 1, row0, ldo, band_rows
+        c.fuse_asked, c.ws_fill, c.seq_off = int(fuse_asked), ws_fill, seq_off.ctypes.data
+        keep = [seq_off]
+
+        def put(field, a, dt):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dtype=dt)
+            keep.append(a)
+            setattr(c, field, a.ctypes.data)
+            return a
+
+        def sentinel(shape, dt):
+            return np.frombuffer(bytes([DEBUG_SENTINEL]) * (int(np.prod(shape)) * np.dtype(dt).itemsize), dtype=dt).reshape(shape).copy()
+
+        a = put("row_seq", row_seq, np.int32)
+        if a is not None:
+            c.n_row_seq = a.size
+        if x is not None:
+            x = put("x", x, np.float16)
+            assert x.ndim == 2 and x.shape[0] == M
+            c.ldx = x.shape[1]
+        for name, w in (("wq", wq), ("wk", wk), ("wv", wv)):
+            w = put(name, w, np.float16)
+            assert w is None or w.shape == (64 * H, d)
+        if enc is not None:
+            enc = put("enc", enc, np.float16)
+            assert enc.ndim == 2 and enc.shape[1] == d and enc.shape[0] >= 2 * band_rows
+            c.enc_rows = enc.shape[0] - 2 * band_rows
+        a = put("rowscale", rowscale, np.float32)
+        assert a is None or a.size == M
+        a = put("ssq_in", ssq_in, np.float32)
+        if a is not None:
+            assert a.ndim == 2 and a.shape[0] == M
+            c.nb_in = a.shape[1]
+        a = put("ctx", ctx, np.float16)
+        assert a is None or a.shape == (M, ldo)
+
+        def fields():
+            res = {}
+            for k, _ in RkDebugXattnChainCall._fields_:
+                if k.startswith("out_"):
+                    v = getattr(c, k)
+                    res[k[4:]] = v if isinstance(v, (int, float)) else tuple(tuple(u) if hasattr(u, "__len__") else u for u in v)
+            return res
+
+        c.plan_only = 1                                     # the row loop's block size decides the size of the outputs
+        rc = self.lib.rk_debug_xattn_chain(self.h, C.byref(c))
+        if plan_only:
+            self._chk(rc)
+            return fields()
+        # (a call the plan already refuses is issued all the same, with one-block buffers: it must refuse again and touch nothing)
+        R, nb, nch, Hd = (1, 1, 1, H * max(d, 1)) if rc else (min(c.out_block_rows, M), c.out_n_blocks, c.out_nch, H * d)
+        c.plan_only = 0
+        outs = dict(qk=put("qk_all", sentinel((M + 2 * band_rows, H, max(d, 1)), np.float16), np.float16),
+                    part=put("part_all", sentinel((nb, R * nch * Hd + 2 * band_rows * Hd), np.float32), np.float32),
+                    stat=put("stat_all", sentinel((nb, R * nch * H * 2 + 2 * band_rows * H * 2), np.float32), np.float32),
+                    xctx=put("xctx_all", sentinel((nb, R + 2 * band_rows, Hd), np.float16), np.float16),
+                    ctx=put("ctx_all", sentinel((M + 2 * band_rows, ldo), np.float16), np.float16))
+        try:
+            self._chk(self.lib.rk_debug_xattn_chain(self.h, C.byref(c)))
+        except RkError as err:
+            err.outputs = outs
+            raise
+        del keep
+        res = fields()
+        res.update(outs)
         return res
 
     def debug_read(self, name: str, n_floats: int) -> np.ndarray:

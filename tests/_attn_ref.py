@@ -48,6 +48,35 @@ probability rounded against a tile's running maximum instead of the row's.  With
 below one fp16 half-ulp: such a kernel must deliver the correctly rounded result or its neighbour at a tie.  With fp16 probabilities
 C * E is of the order of the half-ulp itself.  The mutants of the host test fail by orders of magnitude more: C is not what
 separates them.
+
+The decoder's query-side chain (csrc/decoder_kernels.h; build_chain / judge_chain below, rk_debug_xattn_chain on the device).
+hf: T5LayerCrossAttention as restated at the top of decoder_kernels.h, per decoder row m and head h:
+  q_h = rowfactor_m (W_q,h x_m);  qk_h = W_k,h^T q_h;  ctx' = sum_t softmax_t(qk_h . e_t) e_t over the row's sequence;  ctx_h = W_v,h ctx'
+with fp16 roundings at q, qk, ctx' (the merged sums) and ctx.  Each STAGE is judged against fp64 of its own inputs as the device
+left them (rk_debug_xattn_chain returns every intermediate buffer), so an early rounding flip never sets a later tolerance:
+  A  qk   from the host x, W_q, W_k and the row factor            (two roundings: q inside, qk at the end)
+  B  part / stat merged in fp64, from the device's qk bytes and enc (fp32 partials, no rounding of their own); of a chunk that a
+     shorter row does not have, part is never written and stat holds the kernels' empty mark (EMPTY_CHUNK)
+  C  ctx  from the device's part / stat bytes and W_v              (two roundings: the merged sums inside, ctx at the end)
+Tolerance of an fp16 output: half an fp16 ulp of the expected value + C_CHAIN E + flip.  E is the largest error against fp64 of
+the stage's LAST product in fp32 (one k-ordered chain) given the reference's own inner fp16 values, on the sample rows.  flip bounds the
+inner rounding element by element: an inner value (q_j, a merged sum) whose fp64 value lies within C_CHAIN E_inner
+of an fp16 rounding boundary (E_inner = the fp32 emulation's largest error of the inner values on the sample) may be delivered as
+either neighbour, and each such value moves output n by at most ulp(inner) |W[n, j]|: flip[n] = the sum of that over the ambiguous
+inner values of the very (row, head) - per element, computed for every row, nothing chosen in advance and 0 for most elements.
+The fp32 partials of stage B get C_CHAIN E alone, E = `yardstick` of the XATTN problem made of the device's qk bytes.
+
+C_CHAIN, measured on the CPU as C was (tests/test_attn_ref_host.py::test_chain_honest_orders_pass recomputes it and fails above
+it): the honest summation orders stand in for the kernel on the chain fixtures of that file and on the GPU test's own shapes
+(CHAIN_SHAPES, but the two widest) - K in contiguous eighths with the fixed tree ((w0 + w4) + (w2 + w6)) + ((w1 + w5) + (w3 + w7)),
+16-steps interleaved over four accumulators, one sequential chain; the chunk merge as an fma chain and with 4 and with 16 chunk
+products summed before they meet the accumulator.  Largest (error - half ulp - flip) / E over whole outputs, and largest inner
+error / E_inner (what the flip window is made of):
+  stage A (qk) 0.05   inner q 1.00   stage B (merged partials) 1.95   inner merged sums 2.06   xctx 0.22   stage C (ctx) 0.21
+(a stage's last product is one short chain on exact fp16 inputs: what is left beyond the half ulp and the flips is next to nothing.
+E is a maximum over SAMPLE rows - `chain_sample`: rows of every key length - while an output is held to it element by element,
+hence figures above 1 where the error grows with the chunk count: 23 and 65 chunks.)  The largest is 2.06; C_CHAIN is twice that,
+rounded up to a tenth.  The mutants of the host test fail by orders of magnitude more: C_CHAIN is not what separates them.
 """
 from types import SimpleNamespace
 
@@ -758,3 +787,395 @@ def build_step(seed, H, n_kv, pos, P, tier, *, bias=False, band=8):
             p.qkv_bias = (rs.standard_normal(ldq) * np.where(rs.rand(ldq) < 0.02, 8.0, 0.5)).astype(f32)
     p.q, p.out = q, sentinel16((n_seq, Q))
     return p
+
+
+# ---- the decoder's query-side chain: q projection -> W_k^T q -> chunk kernel -> merge -> W_v (csrc/decoder_kernels.h) ------------
+# (what is judged, the tolerance and the measured C_CHAIN: the module docstring)
+C_CHAIN = 4.2
+XS, EPS = 0.0625, 1e-6            # RK_XRAW_SCALE and the toy checkpoints' layer_norm_epsilon (the GPU test checks both against the engine)
+WS_FILL = np.array([0x7F800000], dtype=np.uint32).view(f32)[0]   # +inf: what the test puts into the part / stat workspaces - a chunk a
+                                                                    # kernel must not read turns the row into NaN if it is read
+
+
+EMPTY_CHUNK = (-1e30, 0.0)        # what the chunk kernels leave in stat for a chunk of the call's grid that a shorter row does not have
+                                  # (attention.h: "mark the chunk empty for the combine step"); its partial sums are never written
+
+
+def _perm_heads(rs, d, H):
+    """H disjoint 64-column supports of the d columns."""
+    return rs.permutation(d)[:H * 64].reshape(H, 64)
+
+
+def build_chain(seed, M, Ld, H, d, lens, tier, *, norm="none", nb=0, row0=0, row_seq=None, band=8, ldx_pad=0, ldo_pad=0):
+    """One call of rk_debug_xattn_chain.  norm: "none" (factor 1), "rowscale" or "ssq" (nb block sums per row).  Tier S: selection
+    matrices with disjoint column supports per head (needs 64 H <= d), x = the winner's +-4 entries / a power-of-two row factor that
+    differs from row to row; winners and traps per head as build_dec's cross form places them (first and last key, both sides of every
+    64-key edge, the row in front of the sequence and the one behind it as a doubled copy); margin asserted by `selector`."""
+    rs = np.random.RandomState(seed)
+    off = np.concatenate([[0], np.cumsum(lens)]).astype(np.int32)
+    T, I = int(off[-1]), 64 * H
+    p = SimpleNamespace(M=M, Ld=Ld, H=H, d=d, n_seq=len(lens), seq_off=off, row0=row0, band=band, ldx=d + ldx_pad, ldo=I + ldo_pad, tier=tier,
+                        norm=norm, nb=nb, eps=EPS, xs=XS, rowscale=None, ssq=None, n_traps=0,
+                        row_seq=None if row_seq is None else np.asarray(row_seq, dtype=np.int32))
+    p.seq = chain_seq(p)
+    assert p.seq.min() >= 0 and p.seq.max() < p.n_seq
+    enc = _rows_buffer(rs, T, d, band, tier)
+    x = _rows_buffer(rs, M, p.ldx, 0, tier)
+    if tier == "S":
+        assert I <= d, "tier S needs disjoint column supports per head: 64 H <= d"
+        rf = 2.0 ** ((np.arange(M) * 3) % 5 - 2.0)                                      # 1/4 .. 4, neighbours differ
+        sq, sk, sv = _perm_heads(rs, d, H), _perm_heads(rs, d, H), _perm_heads(rs, d, H)
+        wq, wk, wv = np.zeros((I, d), dtype=f16), np.zeros((I, d), dtype=f16), np.zeros((I, d), dtype=f16)
+        for h in range(H):
+            wq[h * 64 + np.arange(64), sq[h]] = 1
+            wk[h * 64 + np.arange(64), sk[h]] = 1
+            wv[h * 64 + np.arange(64), sv[h]] = 1
+            queries, traps = [], []
+            for m in range(M):
+                b = int(p.seq[m])
+                adm, sp = range(band + off[b], band + off[b + 1]), [band + off[b] + k for k in edges_of(lens[b], 64)]
+                queries.append((adm, _prefer(rs, adm, sp[(m + h) % len(sp):] + sp[:(m + h) % len(sp)], 2 * (m + h) + (m & 1))))
+                traps.append((m, adm.stop if (m + h) % 2 else adm.start - 1))
+            K, win, placed = selector(rs, T + 2 * band, 64, 4, queries, traps, strict=True, what=f"chain head {h}")
+            p.n_traps += len(placed)
+            enc[:, sk[h]] = K
+            x[:, sq[h]] = K[win] / rf[:, None]
+    else:
+        wq = (rs.standard_normal((I, d)) / np.sqrt(d)).astype(f16)
+        wk = (rs.standard_normal((I, d)) / np.sqrt(d)).astype(f16)       # 1 / sqrt(64) for K = 64, and 8 / sqrt(d): T5-like scores (build_xattn)
+        wv = (rs.standard_normal((I, d)) / np.sqrt(d)).astype(f16)
+        amp = np.where(np.arange(M) % 5 == 3, 2e-3, np.exp(rs.uniform(-1, 2, size=M)))    # every fifth row: a mean square of a few eps
+        raw = (rs.standard_normal((M, d)) * amp[:, None]).astype(f32)
+        ms = (raw.astype(f64) ** 2).mean(axis=1)
+        if norm == "none":
+            rf = np.ones(M)
+            x[:, :d] = (raw / np.sqrt(ms + EPS)[:, None]).astype(f16)
+        else:
+            x[:, :d] = (raw * f32(XS)).astype(f16)
+            if norm == "ssq":
+                p.ssq = np.stack([(b.astype(f32) ** 2).sum(axis=1, dtype=f32) for b in np.array_split(raw, nb, axis=1)], axis=1).astype(f32)
+            else:
+                rf = (1.0 / np.sqrt(ms + EPS) / XS).astype(f32).astype(f64)
+    if norm == "rowscale":
+        p.rowscale = rf.astype(f32)
+    elif norm == "ssq" and tier == "S":       # block sums that give (about) the power of two: the fp16 rounding of q absorbs the fp32 rsqrt
+        tot = d * ((rf * XS) ** -2.0 - EPS)
+        p.ssq = (tot[:, None] * rs.dirichlet(np.ones(nb), size=M)).astype(f32)
+    elif norm == "none" and tier == "S":
+        x[:] = (x.astype(f64) * np.repeat(rf[:, None], p.ldx, axis=1)).astype(f16)        # factor 1: x carries the entries themselves
+    p.x, p.wq, p.wk, p.wv, p.enc = x, wq, wk, wv, enc
+    p.ctx0 = sentinel16((M, p.ldo))
+    return p
+
+
+_MIX = [1, 63, 64, 65, 129, 200, 7, 130, 128, 33, 2, 127, 70]
+_SHORT = [1, 64, 130, 65, 7, 128, 33, 129, 63, 100, 2]
+# The shapes of tests/test_gpu_xattn_chain.py, name -> (M, Ld, H, d, key lengths, extra builder arguments): the smallest that reach each
+# path of the two kernels of decoder_kernels.h and of the block loop (DESIGN.md, "How the decoder's chain is tested")
+CHAIN_SHAPES = {
+    "one-key": (1, 1, 2, 128, [1], {}),
+    "one-chunk": (1, 1, 2, 128, [64], {}),
+    "setwise": (13, 1, 6, 512, [1450, 1, 64, 65, 700, 1409, 128, 129, 63, 1000, 23, 1450, 333], {}),
+    "valu": (33, 1, 6, 384, [_MIX[i % 13] for i in range(33)], {}),
+    "large": (257, 1, 16, 1024, [_SHORT[i % 11] for i in range(257)], {}),
+    "wide": (130, 1, 16, 1280, [_MIX[i % 13] for i in range(130)], {}),
+    "row0": (33, 4, 6, 512, [130, 64, 5, 200, 1, 65, 63, 129, 70], dict(row0=3)),
+    "tree": (33, 4, 6, 512, [130, 64, 5, 200, 1, 65, 63, 129, 70], dict(row0=3, row_seq=[(7 * i + i // 5) % 9 for i in range(36)])),
+    "long": (70, 1, 2, 128, [4100, 70], dict(row_seq=[(i % 3 == 1) * 1 for i in range(70)])),
+    "rows": (520, 1, 2, 128, [1, 5, 33, 63, 64, 64, 17, 50], dict(row_seq=[(5 * i + i // 8) % 8 for i in range(520)])),
+}
+
+
+def build_chain_shape(name, norm, nb, tier, band=8):
+    M, Ld, H, d, lens, kw = CHAIN_SHAPES[name]
+    return build_chain(700 + sorted(CHAIN_SHAPES).index(name), M, Ld, H, d, lens, tier, norm=norm, nb=nb, band=band, ldx_pad=8 if name == "valu" else 0,
+                       ldo_pad=8 if name in ("valu", "one-key", "tree") else 0, **kw)
+
+
+def chain_seq(p, mut=None):
+    m = np.arange(p.M)
+    if mut == "seq_ignores_row0":
+        return m // p.Ld if p.row_seq is None else p.row_seq[m]
+    if p.row_seq is None or mut == "row_seq_ignored":
+        return (p.row0 + m) // p.Ld
+    return p.row_seq[p.row0 + m]
+
+
+def chain_factor(p, mut=None, dt=f64):
+    """Row factors [M]: rowscale, or rsqrt(sum of the block sums / d + eps) / xs, or 1.  dt = f32: the kernels' arithmetic."""
+    if mut == "no_factor" or p.norm == "none":
+        rf = np.ones(p.M, dtype=dt)
+    elif p.norm == "rowscale":
+        rf = p.rowscale.astype(dt)
+    else:
+        s = p.ssq[:, :p.nb - 1] if mut == "ssq_nb_minus1" else p.ssq
+        s = _chain(s, 1).astype(dt) if dt == f32 else s.astype(f64).sum(axis=1)
+        rf = (dt(1) / np.sqrt(s / dt(p.d) + (dt(0) if mut == "no_eps" else dt(p.eps))) / dt(p.xs)).astype(dt)
+    return np.roll(rf, -1) if mut == "factor_next_row" else rf
+
+
+def _heads(w, H):
+    return w.reshape(H, 64, -1)
+
+
+def chain_qk64(p):
+    """Stage A in fp64: q [M, H, 64] before its rounding, and qk [M, H, d] from the fp16-rounded (saturated) q."""
+    q = chain_factor(p)[:, None, None] * np.einsum("hjc,mc->mhj", _heads(p.wq.astype(f64), p.H), p.x[:, :p.d].astype(f64))
+    return q, np.einsum("hjc,mhj->mhc", _heads(p.wk.astype(f64), p.H), f16_sat(q).astype(f64))
+
+
+def chain_ctxp64(p, qk):
+    """Stage B in fp64: ctx' [M, H, d] = sum_t softmax_t(qk_h . e_t) e_t over the keys of every row's own sequence, from qk [M, H, d]."""
+    out = np.empty((p.M, p.H, p.d))
+    for m in range(p.M):
+        e = p.enc[p.band + p.seq_off[p.seq[m]]:p.band + p.seq_off[p.seq[m] + 1]].astype(f64)
+        s = qk[m].astype(f64) @ e.T
+        w = np.exp(s - s.max(axis=1, keepdims=True))
+        out[m] = (w / w.sum(axis=1, keepdims=True)) @ e
+    return out
+
+
+def chain_xattn_problem(p, qk, rows):
+    """Stage B's inputs for the rows given as an XATTN problem of their own (the yardstick's sample): the device's qk rows and the
+    encoder rows."""
+    B = p.band
+    pb = problem(XATTN, H=p.H, n_seq=p.n_seq, d=p.d, M=len(rows), Ld=1, row0=0, seq_off=p.seq_off, band=B, ldq=p.H * p.d, ldkv=p.d,
+                 ldctx=p.H * p.d, out_rows=len(rows), tier=p.tier, p16=True, row_seq=p.seq[rows].astype(np.int32))
+    pb.q = np.zeros((len(rows) + 2 * B, p.H * p.d), dtype=f16)
+    pb.q[B:B + len(rows)] = np.asarray(qk)[rows].reshape(len(rows), -1)
+    pb.kv, pb.out = p.enc, sentinel16((len(rows), p.H * p.d))
+    return pb
+
+
+def chain_sample(p):
+    """Rows that go into E: `_sample` of the rows and the first two rows of every distinct key length (the error of the softmax stage
+    depends on the number of keys first of all: a row of two keys has the least averaging)."""
+    L = np.diff(p.seq_off)[p.seq]
+    return np.unique(np.concatenate([_sample(p.M)] + [np.nonzero(L == v)[0][:2] for v in np.unique(L)]))
+
+
+def chain_nv(p):
+    """64-key chunks of every row's own sequence."""
+    return (np.diff(p.seq_off)[p.seq] + 63) // 64
+
+
+def chain_merge64(p, part, stat, mut=None):
+    """The normalised merge of part [M, nch, H, d] / stat [M, nch, H, 2] over every row's own chunks, fp64 -> [M, H, d]."""
+    nch = part.shape[1]
+    valid = (np.arange(nch)[None, :] < (nch if mut == "merge_call_nch" else chain_nv(p)[:, None]))[:, :, None]
+    with np.errstate(invalid="ignore", over="ignore"):
+        mx = np.where(valid, stat[..., 0].astype(f64), -np.inf)
+        w = np.ones_like(mx) * valid if mut == "merge_no_rescale" else np.exp(mx - mx.max(axis=1, keepdims=True))
+        w = np.where(valid, w, 0.0)
+        den = (w * np.where(valid, stat[..., 1].astype(f64), 0.0)).sum(axis=1)
+        return (w[..., None] * np.where(valid[..., None], part.astype(f64), 0.0)).sum(axis=1) / den[..., None]
+
+
+def chain_ctx64(p, merged):
+    """Stage C's product in fp64 from the fp16-rounded merged sums: [M, 64 H]."""
+    return np.einsum("hnc,mhc->mhn", _heads(p.wv.astype(f64), p.H), f16_sat(merged).astype(f64)).reshape(p.M, 64 * p.H)
+
+
+# the documented fp32 arithmetic of the chain's products, in the orders a kernel may take
+def _dot32(w, x, order="chain"):
+    """x [R, K] . w [N, K]^T in fp32 -> [R, N].  chain: one k-ordered chain; eighths: K in eight contiguous ranges, one chain each,
+    the fixed tree of dec_tree_reduce2; inter16: 16-steps dealt in turn to four accumulators, (a0 + a1) + (a2 + a3)."""
+    prod = x.astype(f32)[:, None, :] * w.astype(f32)[None, :, :]
+    K = prod.shape[2]
+    if order == "chain" or K < 128:
+        return _chain(prod, 2)
+    if order == "eighths":
+        a = [_chain(prod[:, :, i * K // 8:(i + 1) * K // 8], 2) for i in range(8)]
+        return (((a[0] + a[4]) + (a[2] + a[6])) + ((a[1] + a[5]) + (a[3] + a[7]))).astype(f32)
+    st = prod.reshape(prod.shape[0], prod.shape[1], K // 16, 16)
+    a = [_chain(st[:, :, i::4].reshape(prod.shape[0], prod.shape[1], -1), 2) for i in range(4)]
+    return ((a[0] + a[1]) + (a[2] + a[3])).astype(f32)
+
+
+def emul_q(p, rows, order="chain", mut=None):
+    """q [R, H, 64] in fp32 BEFORE its rounding."""
+    H = p.H
+    wq = np.roll(_heads(p.wq, H), -1, axis=0) if mut == "wq_head" else _heads(p.wq, H)
+    y = np.stack([_dot32(wq[h], p.x[rows, :p.d], order) for h in range(H)], axis=1)
+    rf = chain_factor(p, mut, f32)[rows, None, None]
+    if mut == "factor_after_round":
+        return f16_sat(y).astype(f32) * rf
+    return (y * rf).astype(f32)
+
+
+def emul_qk(p, q16, mut=None):
+    """qk [R, H, d] in fp32 BEFORE its rounding, from fp16 q [R, H, 64] (K = 64: one chain)."""
+    wk = _heads(p.wk, p.H)
+    if mut == "wk_untransposed":                                    # the head's block read as [d][64] without the regrouping
+        return np.stack([_chain(q16[:, h].astype(f32)[:, None, :] * wk[h].reshape(p.d, 64).astype(f32)[None], 2) for h in range(p.H)], axis=1)
+    return np.stack([_chain(q16[:, h].astype(f32)[:, :, None] * wk[h].astype(f32)[None], 1) for h in range(p.H)], axis=1)
+
+
+def emul_part(p, qk16, mut=None):
+    """The chunk kernel in fp32: part [M, nch, H, d], stat [M, nch, H, 2]; chunks beyond a row's own stay WS_FILL."""
+    nch = int((np.diff(p.seq_off).max() + 63) // 64)
+    part, stat = np.full((p.M, nch, p.H, p.d), WS_FILL, dtype=f32), np.full((p.M, nch, p.H, 2), WS_FILL, dtype=f32)
+    stat[:] = EMPTY_CHUNK
+    seq = chain_seq(p, mut)
+    for m in range(p.M):
+        e = p.enc[p.band + p.seq_off[seq[m]]:p.band + p.seq_off[seq[m] + 1]].astype(f32)
+        s = _chain(qk16[m].astype(f32)[:, None, :] * e[None], 2)                                  # [H, L]
+        for ck in range((len(e) + 63) // 64):
+            sc, ec = s[:, ck * 64:ck * 64 + 64], e[ck * 64:ck * 64 + 64]
+            mc = sc.max(axis=1)
+            pr = _exp2(sc - mc[:, None])
+            stat[m, ck, :, 0], stat[m, ck, :, 1] = mc, _chain(pr, 1)
+            part[m, ck] = _chain(pr.astype(f16).astype(f32)[:, :, None] * ec[None], 1)
+    return part, stat
+
+
+def emul_merge(p, part, stat, rows, merge="fma", mut=None):
+    """The merge of dec_cross_cv_kernel / xattn_combine_kernel in fp32 -> merged [R, H, d] BEFORE its rounding.  merge: "fma" (one
+    fused chain in chunk order), 4 or 16 (that many chunk products summed first, then added)."""
+    out = np.zeros((len(rows), p.H, p.d), dtype=f32)
+    nvs = chain_nv(p)
+    for i, m in enumerate(rows):
+        nv = part.shape[1] if mut == "merge_call_nch" else int(nvs[m])
+        mx, sm = stat[m, :nv, :, 0], stat[m, :nv, :, 1]
+        with np.errstate(invalid="ignore", over="ignore"):
+            w = np.ones_like(mx) if mut == "merge_no_rescale" else np.exp((mx - mx.max(axis=0)).astype(f32)).astype(f32)
+            den = _chain(w * sm, 0)
+            if merge == "fma":
+                acc = np.zeros((p.H, p.d), dtype=f32)
+                for ck in range(nv):
+                    acc = (w[ck].astype(f64)[:, None] * part[m, ck].astype(f64) + acc.astype(f64)).astype(f32)
+            else:
+                acc = np.zeros((p.H, p.d), dtype=f32)
+                for c0 in range(0, nv, merge):
+                    acc = (acc + _chain(w[c0:c0 + merge, :, None] * part[m, c0:min(c0 + merge, nv)], 0)).astype(f32)
+            out[i] = acc * (f32(1) / den)[:, None]
+    return out
+
+
+def emul_ctx(p, s16, order="chain", mut=None):
+    """ctx [R, 64 H] in fp32 BEFORE its rounding, from merged sums [R, H, d] (fp16, or fp32 for the mutant that skips the rounding)."""
+    wv = np.roll(_heads(p.wv, p.H), -1, axis=0) if mut == "wv_head" else _heads(p.wv, p.H)
+    return np.concatenate([_dot32(wv[h], s16[:, h], order) for h in range(p.H)], axis=1)
+
+
+def emulated_chain(p, order="chain", merge="fma", mut=None, fused=True):
+    """What rk_debug_xattn_chain returns when kernels of the documented arithmetic run it: dict of qk (whole allocation, sentinel
+    bands), part, stat, xctx (None when fused), ctx [M, ldo], and the inner values q32 / merged32 for the host test's record."""
+    rows = np.arange(p.M)
+    q32 = emul_q(p, rows, order, mut)
+    qk = sentinel16((p.M + 2 * p.band, p.H, p.d))
+    qk[p.band:p.band + p.M] = f16_sat(emul_qk(p, f16_sat(q32), mut))
+    part, stat = emul_part(p, qk[p.band:p.band + p.M], mut)
+    merged32 = emul_merge(p, part, stat, rows, merge, mut)
+    with np.errstate(invalid="ignore"):
+        inner = merged32 if mut == "no_inner_round" else f16_sat(merged32)
+        ctx = p.ctx0.copy()
+        val = f16_sat(emul_ctx(p, inner, order, mut))
+    if mut == "ctx_slab_later":
+        ctx[2:, :64 * p.H] = val[:-2]
+    else:
+        ctx[:, :64 * p.H] = val
+    return dict(qk=qk, part=part, stat=stat, xctx=None if fused else f16_sat(merged32).reshape(p.M, -1), ctx=ctx, q32=q32, merged32=merged32)
+
+
+def _amb_flip(v64, E_inner, wabs):
+    """flip [R, H, N]: v64 [R, H, K] inner values in fp64, wabs [H, N, K] = |W|.  An inner value within C_CHAIN E_inner of an fp16 rounding
+    boundary may be either neighbour: each moves output n by at most one ulp of it times |W[n, k]|."""
+    hu = half_ulp16(v64)
+    dist = hu - np.abs(v64 - f16_sat(v64).astype(f64))
+    amb = (dist <= C_CHAIN * E_inner) * 2.0 * hu
+    return np.einsum("rhk,hnk->rhn", amb, wabs)
+
+
+def chain_reference(p, res, cache=None):
+    """Everything judge_chain holds a result to, from the problem and the DEVICE's intermediate bytes.  cache: dict shared by the
+    runs of one problem - stage A depends on the host operands only, stages B and C on the bytes of qk and of part / stat."""
+    import hashlib
+    cache = {} if cache is None else cache
+    H, d, M, B = p.H, p.d, p.M, p.band
+    rows = chain_sample(p)
+    if "A" not in cache:
+        q64, want = chain_qk64(p)
+        a = dict(want=want)
+        if p.tier != "S":
+            qs = emul_q(p, rows)
+            a["Eq"] = float(np.abs(qs.astype(f64) - q64[rows]).max())
+            a["E"] = float(np.abs(emul_qk(p, f16_sat(q64[rows])).astype(f64) - want[rows]).max())
+            a["flip"] = _amb_flip(q64, a["Eq"], np.abs(_heads(p.wk.astype(f64), H)).transpose(0, 2, 1))
+            a["q64"] = q64
+        cache["A"] = a
+    out = dict(A=cache["A"])
+    qk = np.asarray(res["qk"])[B:B + M]
+    key = ("B", hashlib.sha1(qk.tobytes()).hexdigest())
+    if key not in cache:
+        cache[key] = dict(want=chain_ctxp64(p, qk), E=None if p.tier == "S" else yardstick(chain_xattn_problem(p, qk, rows))[True])
+    out["B"] = cache[key]
+    part, stat = res["part"], res["stat"]
+    key = ("C", hashlib.sha1(part.tobytes() + stat.tobytes()).hexdigest())
+    if key not in cache:
+        merged = chain_merge64(p, part, stat)
+        c = dict(merged=merged, want=chain_ctx64(p, merged))
+        if p.tier != "S" and np.isfinite(merged).all():
+            c["Em"] = float(np.abs(emul_merge(p, part, stat, rows).astype(f64) - merged[rows]).max())
+            c["E"] = float(np.abs(emul_ctx(p, f16_sat(merged[rows])).astype(f64) - c["want"][rows]).max())
+            c["flip"] = _amb_flip(merged, c["Em"], np.abs(_heads(p.wv.astype(f64), H))).reshape(M, 64 * H)
+        cache[key] = c
+    out["C"] = cache[key]
+    return out
+
+
+def _bits_equal(got, want64, what):
+    bad = np.asarray(got).view(np.uint16) != f16_sat(want64).view(np.uint16)
+    assert not bad.any(), f"{what}: element {tuple(np.argwhere(bad)[0])}: got {np.asarray(got)[tuple(np.argwhere(bad)[0])]}, the selection gives {want64[tuple(np.argwhere(bad)[0])]}"
+
+
+def _within(got, want64, E, flip, what, half=True):
+    """(error - half ulp - flip) / E over the whole output; asserts it stays within C_CHAIN."""
+    assert np.isfinite(np.asarray(got, dtype=f64)).all(), f"{what}: non-finite output"
+    over = np.abs(np.asarray(got, dtype=f64) - want64) - (half_ulp16(want64) if half else 0.0) - flip
+    if (over > C_CHAIN * E).any():
+        i = tuple(np.argwhere(over > C_CHAIN * E)[0])
+        raise AssertionError(f"{what}: element {i}: got {np.asarray(got)[i]}, fp64 {want64[i]:.6g}, beyond the tolerance by {over[i]:.3g} > {C_CHAIN} x E ({E:.3g}); "
+                             f"{int((over > C_CHAIN * E).sum())} of {over.size} elements fail")
+    return float(over.max()) / E if E > 0 else 0.0
+
+
+def judge_chain(p, res, what="", cache=None):
+    """Holds one result of the chain (device or emulation) to the three stages.  res: qk [band + M + band, H, d] fp16, part [M, nch,
+    H, d] / stat [M, nch, H, 2] fp32 (the rows' blocks put together), xctx [M, H d] fp16 or None, ctx [M, ldo] fp16.  Returns the
+    largest ratios per stage (tier R)."""
+    ref = chain_reference(p, res, cache)
+    H, d, M, B = p.H, p.d, p.M, p.band
+    qk = np.asarray(res["qk"])[B:B + M]
+    part, stat, ctx = res["part"], res["stat"], np.asarray(res["ctx"])
+    ratios = {}
+    # the chunks a row does not have: never written
+    nv, nch = chain_nv(p), part.shape[1]
+    dead = np.arange(nch)[None, :] >= nv[:, None]
+    fill = res.get("fill_bits", WS_FILL.view(np.uint32))
+    assert (part.view(np.uint32)[dead] == fill).all(), f"{what}: partial sums of a chunk beyond a row's own were written"
+    mark = np.array(EMPTY_CHUNK, dtype=f32).view(np.uint32)
+    assert (stat.view(np.uint32)[dead] == mark).all(), f"{what}: the statistics of a chunk beyond a row's own are not the chunk kernel's empty mark"
+    assert np.isfinite(part[~dead]).all() and np.isfinite(stat[~dead]).all(), f"{what}: a chunk of a row was not written (or not finite)"
+    pad = ctx[:, 64 * H:]
+    assert pad.tobytes() == p.ctx0[:, 64 * H:].tobytes(), f"{what}: a pad column of ctx was written"
+    A_, B_, C_ = ref["A"], ref["B"], ref["C"]
+    if p.tier == "S":
+        _bits_equal(qk, A_["want"], f"{what}: stage A (qk)")
+        assert np.isfinite(C_["merged"]).all(), f"{what}: stage B: non-finite merge"
+        gap = np.abs(C_["merged"] - B_["want"]).max()
+        assert gap <= 2.0 ** -40, f"{what}: stage B: the merged partials are not the winner's row (off by {gap:.3g})"
+        if res.get("xctx") is not None:
+            _bits_equal(np.asarray(res["xctx"]).reshape(M, H, d), C_["merged"], f"{what}: xctx")
+        _bits_equal(ctx[:, :64 * H], C_["want"], f"{what}: stage C (ctx)")
+        return ratios
+    ratios["A"] = _within(qk, A_["want"], A_["E"], A_["flip"], f"{what}: stage A (qk)")
+    assert np.isfinite(C_["merged"]).all(), f"{what}: stage B: non-finite merge of the partials"
+    ratios["B"] = _within(C_["merged"], B_["want"], B_["E"], 0.0, f"{what}: stage B (merged partials)", half=False)
+    if res.get("xctx") is not None:
+        ratios["xctx"] = _within(np.asarray(res["xctx"]).reshape(M, H, d), C_["merged"], C_["Em"], 0.0, f"{what}: xctx")
+    ratios["C"] = _within(ctx[:, :64 * H], C_["want"], C_["E"], C_["flip"], f"{what}: stage C (ctx)")
+    if "q32" in res:                                             # (the emulation's inner values: the host test's record)
+        ratios["q"] = float(np.abs(res["q32"].astype(f64) - A_["q64"]).max()) / max(A_["Eq"], 1e-300)
+        ratios["merged"] = float(np.abs(res["merged32"].astype(f64) - C_["merged"]).max()) / max(C_["Em"], 1e-300)
+    return ratios

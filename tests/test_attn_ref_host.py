@@ -140,3 +140,93 @@ def test_builder_refuses_a_thin_margin():
     queries = [(range(0, i + 1), []) for i in range(700)]
     with pytest.raises(AssertionError, match="margin"):
         A.selector(rs, 700, 128, 4, queries, [], scale=128.0 ** -0.5, what="thin")
+
+
+# ---- the decoder's query-side chain (rk_debug_xattn_chain; _attn_ref.py: build_chain / judge_chain) -----------------------------
+CHAIN_LENS = [1, 63, 64, 65, 129, 200, 7, 64, 128, 130, 1, 33, 70]
+TREE_SEQ = [0, 0, 0, 2, 1, 1, 0, 2, 2, 1, 0, 1, 2, 0, 1, 2]        # row_seq of the tree form: row -> sequence, not row // Ld
+_CHAIN = {}
+
+
+def chain_fixtures():
+    """name -> chain problem: 13 rows at one position (every norm form, both paths of the block sum), and 9 rows of a 4-position call
+    starting at row 3, with and without row_seq."""
+    if not _CHAIN:
+        for tier in "SR":
+            for norm, nb in (("none", 0), ("rowscale", 0), ("ssq", 5), ("ssq", 8)):
+                _CHAIN[f"{tier}_{norm}{nb or ''}"] = A.build_chain(30, 13, 1, 2, 128, CHAIN_LENS, tier, norm=norm, nb=nb, ldo_pad=8)
+            _CHAIN[f"{tier}_row0"] = A.build_chain(31, 9, 4, 2, 128, [130, 64, 5], tier, norm="rowscale", row0=3)
+            _CHAIN[f"{tier}_tree"] = A.build_chain(32, 9, 4, 2, 128, [130, 64, 5], tier, norm="ssq", nb=4, row0=3, row_seq=TREE_SEQ)
+        _CHAIN["R_chunks"] = A.build_chain(34, 6, 1, 2, 128, [1450, 1, 4100, 700, 64], "R", norm="rowscale", row_seq=[0, 1, 2, 3, 4, 2])   # 23 and 65 chunks
+        _CHAIN["R_wide"] = A.build_chain(33, 5, 1, 6, 512, [300, 64, 1, 129, 65], "R", norm="ssq", nb=16)    # K = 512: the orders differ more
+    return _CHAIN
+
+
+CHAIN_ORDERS = [("chain", "fma", True), ("eighths", "fma", True), ("eighths", 4, True), ("eighths", 16, True), ("inter16", "fma", False), ("inter16", 4, False)]
+# mutant -> fixtures that must reject it (at least one of each group); "R:" groups must do so on the random tier alone
+CHAIN_MUTANTS = {
+    "wq_head": [["S_rowscale"], ["R_rowscale"]],
+    "wk_untransposed": [["S_rowscale"], ["R_rowscale"]],
+    "no_factor": [["S_rowscale"], ["S_ssq5"], ["R_rowscale"], ["R_ssq8"]],
+    "factor_next_row": [["S_rowscale"], ["S_ssq5"], ["R_rowscale"]],
+    "factor_after_round": [["R_rowscale"], ["R_ssq5"]],
+    "ssq_nb_minus1": [["S_ssq5"], ["R_ssq5"], ["R_ssq8"]],
+    "no_eps": [["R_ssq5"], ["R_ssq8"]],
+    "seq_ignores_row0": [["S_row0"], ["S_tree"], ["R_row0"]],
+    "row_seq_ignored": [["S_tree"], ["R_tree"]],
+    "merge_call_nch": [["S_rowscale"], ["R_rowscale"]],
+    "merge_no_rescale": [["R_rowscale"], ["R_wide"]],
+    "wv_head": [["S_rowscale"], ["R_rowscale"]],
+    "ctx_slab_later": [["S_rowscale"], ["R_rowscale"]],
+    "no_inner_round": [["R_rowscale"], ["R_wide"]],
+}
+
+
+def _chain_rejects(p, res, what):
+    try:
+        A.judge_chain(p, res, what=what)
+    except AssertionError as err:
+        return str(err)
+    return ""
+
+
+@pytest.mark.parametrize("mut", sorted(CHAIN_MUTANTS))
+def test_chain_mutant_is_rejected(mut):
+    fx = chain_fixtures()
+    for group in CHAIN_MUTANTS[mut]:
+        why = [_chain_rejects(fx[n], A.emulated_chain(fx[n], mut=mut), f"{mut} on {n}") for n in group]
+        print(mut, group, [w[:200] for w in why])
+        assert any(why), f"chain mutant {mut} passes on {group}: the fixtures or the tolerance are too weak"
+
+
+def test_chain_honest_orders_pass():
+    """Every chain fixture in every honest order (fused and five-launch form): accepted; the largest ratios per stage - and of the
+    inner values q and merged sums against their own E, which is what the flip window is made of - stay within C_CHAIN.  Prints the
+    figures quoted in _attn_ref.py; C_CHAIN must be at least twice the largest."""
+    table = {}
+    for name, p in chain_fixtures().items():
+        cache = {}
+        for order, merge, fused in CHAIN_ORDERS:
+            r = A.judge_chain(p, A.emulated_chain(p, order, merge, fused=fused), what=f"{name} {order} merge {merge}", cache=cache)
+            for k, v in r.items():
+                table[k] = max(table.get(k, 0.0), v)
+    # the GPU test's own shapes (but the two widest, whose emulation takes the CPU a minute), the fused and the five-launch form
+    for shape in sorted(set(A.CHAIN_SHAPES) - {"large", "wide"}):
+        p, cache = A.build_chain_shape(shape, "ssq", 5, "R"), {}
+        for order, merge, fused in (("eighths", "fma", True), ("inter16", 4, False)):
+            for k, v in A.judge_chain(p, A.emulated_chain(p, order, merge, fused=fused), what=f"{shape} {order} merge {merge}", cache=cache).items():
+                table[k] = max(table.get(k, 0.0), v)
+    for k in sorted(table):
+        print("chain stage %-6s ratio %.2f" % (k, table[k]))
+    assert set(table) == {"A", "B", "C", "xctx", "q", "merged"}
+    assert 2 * max(table.values()) <= A.C_CHAIN
+    assert table["q"] > 0.5 and table["merged"] > 0.5
+
+
+def test_chain_selector_fixtures_carry_their_traps():
+    for name, p in chain_fixtures().items():
+        if p.tier == "S":
+            assert p.n_traps >= p.H, f"{name}: {p.n_traps} traps"
+        if p.tier == "S" and p.norm != "none":
+            rf = A.chain_factor(p)
+            assert len(set(rf.round(6))) >= 3 and (np.log2(rf).round(3) % 1 == 0).all(), f"{name}: row factors are not distinct powers of two"
