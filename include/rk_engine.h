@@ -43,7 +43,12 @@ typedef enum rk_status {
 
 typedef enum rk_dtype { RK_F32 = 0, RK_F16 = 1, RK_BF16 = 2 } rk_dtype;
 
-/* Mirrors the fields of HF's T5Config the path depends on (hf: models/t5/configuration_t5.py). */
+/* Mirrors the fields of HF's T5Config the path depends on (hf: models/t5/configuration_t5.py).
+ * d_kv is 64 or 128 (RK_ERR_INVALID otherwise).  d_kv = 128 (t5-3b, t5-11b: monoT5-3B, duoT5-3B) is served at ONE decoder position:
+ * rk_t5_score with dec_len == 1 (blocking, staged, slots), rk_t5_compare and the rk_comm_* calls behind them.  On such an engine
+ * rk_t5_score with dec_len > 1, rk_t5_qlm, rk_t5_qlm_many, rk_t5_greedy, rk_t5_greedy2 and rk_t5_generate return RK_ERR_STATE with a
+ * message that names d_kv=128 and the entry point, before anything is launched; so do the one-position calls while an option selects
+ * a path without a 128-wide form (xattn_direct = 0, dec_fuse = 2). */
 typedef struct rk_model_desc {
   int32_t vocab, d_model, n_heads, d_kv, d_ff;
   int32_t n_enc_layers, n_dec_layers;
@@ -320,8 +325,9 @@ typedef struct rk_debug_gemm_call {
 int rk_debug_gemm_ex(rk_engine* e, rk_debug_gemm_call* call);
 /* debug: run ANY attention call of the engine (csrc/rk_engine.hip: plan_*attn -> the plan's launcher, no kernel and no dispatch of
  * its own) on host data, every output inside guard bands.  kind selects the plan; heads have the kernels' own width (64 for the T5
- * kinds, 128 for the Llama kinds); an engine of the other family gets RK_ERR_STATE.
- *   1 T5 encoder         plan_enc_attn: q = packed qkv [T, ldq] (q | k | v at columns 0 | I | 2I, I = 64 H), seq_off[n_seq + 1], bias_lut
+ * kinds - 128 on a T5 engine created with d_kv = 128, where kind 1 runs the 128-wide plan (out_kind 3) whatever attn_short / attn_long
+ * say, kind 2 is RK_ERR_STATE and kind 3 is unchanged -, 128 for the Llama kinds); an engine of the other family gets RK_ERR_STATE.
+ *   1 T5 encoder         plan_enc_attn: q = packed qkv [T, ldq] (q | k | v at columns 0 | I | 2I, I = 64 H or 128 H), seq_off[n_seq + 1], bias_lut
  *                        [H][257] (entry rel + 128 for rel = key - query clamped to +-128; the table itself, not built from weights),
  *                        out = ctx [T, ldctx].  Options attn_short, attn_heads_per_wg, attn_long, attn_long_nw, attn_long_xcd.
  *   2 T5 decoder         plan_dec_attn.  cross = 0 (causal self-attention): q = fused rows [rows, ldq], keys / values in the same rows
@@ -343,7 +349,7 @@ int rk_debug_gemm_ex(rk_engine* e, rk_debug_gemm_call* call);
  * the first interior row.  out: the interior, out_rows x ldctx elements, copied to the device as it is (the caller pre-fills what no
  * kernel may touch); out_all: (out_rows + 2 band_rows) x ldctx elements, the whole device allocation after the call, the bands filled
  * with the byte RK_DEBUG_SENTINEL before it.  cache / cache_all: the same with bands of band_rows x 128 elements.
- * plan_only != 0: nothing is allocated or launched, only the out_* fields are filled: out_kind (1: DMA 0 / LONG 1 / TILED 2; 2: the
+ * plan_only != 0: nothing is allocated or launched, only the out_* fields are filled: out_kind (1: DMA 0 / LONG 1 / TILED 2 / D128 3; 2: the
  * staged kernel NONE 0 / SEQ 1 / ROW 2; 3: part MFMA_FEW 0 / MFMA 1 / VALU16 2 / VALU4 3; 4: dma 0 / 1), out_tparam (the kernel's template
  * parameter: wave groups, waves, heads per workgroup or R), out_grid (the first kernel's), out_grid2 (the tiled / staged / merge
  * kernel's), out_lds, out_staged, out_mfma, out_part, out_R, out_nch, out_skip_long, out_heads_per_wg, out_n_cu.
@@ -374,7 +380,8 @@ int rk_debug_attn(rk_engine* e, rk_debug_attn_call* call);
  * and the launches of every block; no kernel and no dispatch of its own).  Fused (fuse_asked != 0 and d % 128 == 0): dec_cross_qk_kernel,
  * the chunk kernel, dec_cross_cv_kernel (beyond DECV_MAXCH chunks: xattn_combine_kernel + the W_v GEMM per head); else the five-launch
  * form (q GEMM, W_k^T GEMM per head, chunk kernel, xattn_combine_kernel, W_v GEMM per head) - out_fused says which ran.
- *   x [M, ldx] fp16, wq / wk / wv [H 64, d] fp16 in HF layout (the call regroups W_k as rk_engine_finalize does), enc: the WHOLE
+ *   x [M, ldx] fp16, wq / wk / wv [H 64, d] fp16 in HF layout ([H 128, d] on an engine created with d_kv = 128, which always runs the
+ *   five-launch form - out_fused = 0 whatever fuse_asked says - and takes ldo >= 128 H) (the call regroups W_k as rk_engine_finalize does), enc: the WHOLE
  *   allocation, band_rows rows in front of and behind the enc_rows interior rows of d elements, bands filled by the caller with finite
  *   values; seq_off[n_seq + 1]; decoder row m belongs to sequence row_seq[row0 + m] (n_row_seq entries) or (row0 + m) / Ld.
  *   Norm fold of the q projection: rowscale[M], or ssq_in[M][nb_in] (block sums of squares of x / out_xs: the factor is

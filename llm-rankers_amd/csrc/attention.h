@@ -1,4 +1,5 @@
-// T5 attention kernels for gfx950 (d_kv = 64 only; every public T5 up to xl uses 64).
+// T5 attention kernels for gfx950 at d_kv = 64 (every public T5 up to xl); the encoder self-attention at d_kv = 128 (t5-3b, t5-11b):
+// attention_d128.h, which shares the tile helpers below.
 //
 // Semantics restated from hf: models/t5/modeling_t5.py:144-173 with scaling = 1.0 (:196-197):
 //   P = softmax(Q K^T + bias[h, bucket(j - i)] + mask),  ctx = P V

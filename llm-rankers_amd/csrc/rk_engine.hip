@@ -22,6 +22,7 @@
 
 #include "../../include/rk_engine.h"
 #include "attention.h"
+#include "attention_d128.h"
 #include "decoder_kernels.h"
 #include "gemm.h"
 #include "gemv_rows.h"
@@ -336,7 +337,7 @@ void launch_pp2(hipStream_t st, const GemmArgs& a, int max_wgs) {
 // only when the launch has at most half as many 256 x 256 tiles as the chip has CUs and K >= 6 144 (96 K tiles).  Measured
 // (profiles/r06_gemm_ksplit.txt, M = 1 536, N = 4 096): K = 14 336 281.6 -> 212.0 us, K = 8 192 155.9 -> 123.6 us, K = 4 096
 // 76.9 -> 75.1 us (not worth a different rounding); three / four ways lose (every slab is published and re-read).  Needs the
-// workspace of the launch's stream (plan_gemm).  flan-t5-large / -xl never qualify (K <= 5 120).
+// workspace of the launch's stream (plan_gemm).  flan-t5-large / -xl never qualify (K <= 5 120); t5-3b would and is kept off it (below).
 int choose_ksplit(const rk_engine* e, int epi, int M, int N, int K) {
   if (!e->opt.gemm_sk || !(epi == EPI_RESID_F32 || epi == EPI_STORE_F32) || K % 64) return 1;
   const long tiles = (long)((M + 255) / 256) * ((N + 255) / 256);
@@ -344,6 +345,11 @@ int choose_ksplit(const rk_engine* e, int epi, int M, int N, int K) {
   if (e->opt.gemm_sk == 2)                                             // tests / measurement: two ways wherever they fit
     return (nk >= 4 && tiles * 2 <= KSPLIT_MAX_SLABS) ? 2 : 1;
   if (epi != EPI_RESID_F32 || tiles < 1 || tiles * 2 > wgs || nk < 96) return 1;
+  // T5: never by this rule.  The split rounds differently from the unsplit sum and is decided from the TILE COUNT of the launch, i.e.
+  // from the batch - and a T5 sequence's logits are promised not to depend on what shares its call.  No T5 shape qualified until
+  // t5-3b (FFN-out: N = 1 024, K = 16 384), where 32 sequences took the split and two of them alone did not
+  // (tests/test_gpu_t5_d128.py); the Llama prefill (o / down projections), which the rule was measured on, keeps it.
+  if (e->family == 0) return 1;
   return 2;
 }
 
@@ -790,6 +796,23 @@ int DecIndex::tree(rk_engine* e, hipStream_t st, std::vector<int>& sig, std::ini
 }
 
 // ---- forward passes -----------------------------------------------------------------------------------------
+// Head width of the T5 kernels: 64, or 128 (t5-3b / t5-11b: monoT5-3B, duoT5-3B).  A 128-wide engine serves the ONE-POSITION calls
+// only (rk_t5_score with dec_len 1, rk_t5_compare): the encoder through attn_enc128_kernel, the decoder through the W_o W_v product
+// and the five-launch query-side cross-attention chain, whose per-head GEMMs carry the width.  Every other 64-wide kernel
+// (decoder self-attention, the materialised K / V, the fused chain projections) is never launched there: refuse_wide.
+inline int head_width(const rk_engine* e) { return e->family == 0 ? e->d.d_kv : 64; }
+inline bool wide_heads(const rk_engine* e) { return head_width(e) == 128; }
+int refuse_wide(rk_engine* e, const char* entry, const char* what) {
+  return fail(e, RK_ERR_STATE, "%s: d_kv=128 engines serve one decoder position only (rk_t5_score with dec_len 1, rk_t5_compare); %s", entry, what);
+}
+// a one-position call on a 128-wide engine: the options must select the paths that have a 128 form
+int check_wide_one(rk_engine* e, const char* entry) {
+  if (!wide_heads(e)) return RK_OK;
+  if (!e->opt.xattn_direct) return refuse_wide(e, entry, "option xattn_direct = 0 selects the materialised K / V, which have no 128-wide kernel");
+  if (e->opt.dec_fuse == 2) return refuse_wide(e, entry, "option dec_fuse = 2 forces the fused chain projections, which have no 128-wide kernel");
+  return RK_OK;
+}
+
 #define XA_MAX_ROWS 512     // decoder rows (sequences x positions) per pass of the direct cross-attention path
 #define XA_MAX_CHUNKS 4096  // rows x 64-key chunks of partial-sum workspace per pass
 #define XA_MAX_LD 16        // decoder positions per sequence up to which the query-side form is used
@@ -834,7 +857,7 @@ inline size_t attn_dec_lds(int keys) { return (64 + 256 + 8 + (size_t)keys) * si
 
 // Encoder self-attention of one run_encoder call (hf: modeling_t5.py:144-173)
 struct EncAttnPlan {
-  enum Kind { DMA, LONG, TILED } kind = TILED;
+  enum Kind { DMA, LONG, TILED, D128 } kind = TILED;   // D128: attn_enc128_kernel (attention_d128.h), every call of a 128-wide engine
   int ng = 0, heads_per_wg = 0;       // DMA: attn_enc_dma_kernel<ng> (wave groups per workgroup), (sequence, head) items per group
   int nw = 0, nqb = 0, xcd_map = 0;   // LONG: attn_enc_long_kernel<nw> (waves per workgroup), query blocks of 32 nw, XCD grouping
   bool skip_long = false;             // LONG: attn_enc_kernel first, for the batch's sequences of at most ATT_ROW_MAXL keys
@@ -843,6 +866,15 @@ struct EncAttnPlan {
 EncAttnPlan plan_enc_attn(const rk_engine* e, int n_seq, int maxL, int minL, int H) {
   const auto& o = e->opt;
   EncAttnPlan p;
+  if (wide_heads(e)) {
+    // 128-wide heads: ONE kernel for every length, whatever attn_short / attn_long say (they choose between 64-wide kernels).
+    // One workgroup of four waves per 128 queries of a (sequence, head) pair: the pointwise batch (32 sequences x 184 tokens x 32
+    // heads) is 2 048 workgroups, two resident per CU (LDS) - four rounds; a single duoT5 pair (2 x 512 tokens) 256: one per CU
+    p.kind = EncAttnPlan::D128;
+    p.nw = ATT128_NW;
+    p.grid = dim3((maxL + 32 * p.nw - 1) / (32 * p.nw), H, n_seq); p.block = 64 * p.nw; p.lds = ATT128_LDS_BYTES;
+    return p;
+  }
   if (maxL <= ATT_ROW_MAXL && o.attn_short) {
     // Every sequence of the batch at most ATT_ROW_MAXL keys: the DMA kernel (attn_short = 5, the default: two six-wave groups
     // per 768-thread workgroup; 6: one group per workgroup).  The two compute a sequence bit-identically (attention.h: ATT_ROW_MAXL).
@@ -874,6 +906,12 @@ EncAttnPlan plan_enc_attn(const rk_engine* e, int n_seq, int maxL, int minL, int
 struct EncAttnCall { const half_t* qkv; half_t* ctx; const int* seq_off; const float* lut; int ld, ldctx, I, H, n_seq, maxL, T; };
 void launch_enc_attn(rk_engine* e, hipStream_t st, const EncAttnCall& c, const EncAttnPlan& p) {
   const int I = c.I;
+  if (p.kind == EncAttnPlan::D128) {
+    const AttnEnc128Args a{c.qkv, c.ctx, c.seq_off, c.lut, c.ld, c.ldctx, I};
+    Bracket br(e, st, PC_ENC_ATTN, 4.0 * (double)c.maxL * c.T * I, (double)c.T * 4 * I * 2.0);
+    launch_lds<attn_enc128_kernel>(st, p.grid, p.block, p.lds, p.lds, a);
+    return;
+  }
   AttnEncArgs a{c.qkv, c.ctx, c.seq_off, c.lut, c.ld, c.ldctx, I, 1, e->opt.attn_ko};
 #ifdef RK_MEASURE
   a.trace = e->attn_trace;
@@ -969,13 +1007,13 @@ void launch_xattn_part(rk_engine* e, hipStream_t st, const XAttnPlan& p, const X
   if (!p.fuse_cv) hipLaunchKernelGGL(xattn_combine_kernel, dim3(xa.H, p.nr), dim3(256), 0, st, xa);
 }
 
-// W_k of one cross-attention layer ([H * 64, dm], HF layout) regrouped per head and transposed, as dec_cross_qk_kernel and the
-// per-head W_k^T GEMM read it: ckT[h][c][j] = W_k[h * 64 + j][c]
-std::vector<half_t> regroup_ckT(const half_t* wk, int H, int dm) {
-  std::vector<half_t> t((size_t)H * 64 * dm);
+// W_k of one cross-attention layer ([H * hd, dm], HF layout; hd = the head width) regrouped per head and transposed, as
+// dec_cross_qk_kernel (hd = 64 only) and the per-head W_k^T GEMM read it: ckT[h][c][j] = W_k[h * hd + j][c]
+std::vector<half_t> regroup_ckT(const half_t* wk, int H, int dm, int hd) {
+  std::vector<half_t> t((size_t)H * hd * dm);
   for (int h = 0; h < H; ++h)
     for (int c = 0; c < dm; ++c)
-      for (int j = 0; j < 64; ++j) t[((size_t)h * dm + c) * 64 + j] = wk[((size_t)h * 64 + j) * dm + c];
+      for (int j = 0; j < hd; ++j) t[((size_t)h * dm + c) * hd + j] = wk[((size_t)h * hd + j) * dm + c];
   return t;
 }
 
@@ -983,35 +1021,37 @@ std::vector<half_t> regroup_ckT(const half_t* wk, int H, int dm) {
 // fills it from its slot and layer, rk_debug_xattn_chain from host operands.
 struct XAttnChain {
   const half_t* x; int ldx;                   // [M, ldx] input of the q projection (the norm folded: fold, or the normalised rows)
-  const half_t *wq, *wkT, *wv;                // [H * 64, dm], [H][dm][64] (regroup_ckT), [H * 64, dm]
+  const half_t *wq, *wkT, *wv;                // [H * hd, dm], [H][dm][hd] (regroup_ckT), [H * hd, dm]
   GemmFold fold;                              // the q projection's norm hooks: rowscale, or ssq_in / nb_in, or neither
   GemmFamily family;                          // kernel family of the q projection when it is a GEMM of its own
   const half_t* enc; const int* seq_off; const int* row_seq; int Ld, row0;   // encoder rows; decoder row row0 + m -> sequence (XAttnArgs)
-  half_t* q;                                  // [M, H * 64] workspace: q of the unfused form
+  half_t* q;                                  // [M, H * hd] workspace: q of the unfused form
   half_t* qk; float* part; float* stat; half_t* xctx;   // workspaces of ONE block of rows (xattn_block_rows)
-  half_t* ctx; int ldo;                       // [M, ldo] out: column h * 64 + n
+  half_t* ctx; int ldo;                       // [M, ldo] out: column h * hd + n
   int M, H, dm, maxL, T;                      // rows, heads, model width, the longest sequence, encoder tokens (profile only)
   bool fuse_asked;                            // the caller's regime asks for the fused projections (run_decoder)
+  int hd = 64;                                // head width: 64, or 128 (only the three GEMMs of the unfused form see it)
 };
-// the fused form needs eight K ranges of whole k16 steps per workgroup; other widths take the five-launch form
-inline bool xattn_chain_fused(const XAttnChain& c) { return c.fuse_asked && c.dm % 128 == 0; }
+// the fused form needs eight K ranges of whole k16 steps per workgroup, and its kernels are built for 64-wide heads; other model
+// widths and 128-wide heads take the five-launch form
+inline bool xattn_chain_fused(const XAttnChain& c) { return c.fuse_asked && c.dm % 128 == 0 && c.hd == 64; }
 // rows per block: what the workspaces of one pass hold
 inline int xattn_block_rows(int maxL) { return std::max(1, std::min(XA_MAX_ROWS, XA_MAX_CHUNKS / ((maxL + 63) / 64))); }
 // the three GEMMs of the unfused form: q = W_q x over all rows, then per block qk_h = W_k,h^T q_h and ctx_h = W_v,h (.) per head
 inline Gemm xattn_q_gemm(const XAttnChain& c) {
-  return Gemm(PC_DEC_GEMM, EPI_STORE_F16, c.x, c.ldx, c.wq, c.dm, c.q, c.H * 64, c.M, c.H * 64, c.dm).on(c.family).with(c.fold);
+  return Gemm(PC_DEC_GEMM, EPI_STORE_F16, c.x, c.ldx, c.wq, c.dm, c.q, c.H * c.hd, c.M, c.H * c.hd, c.dm).on(c.family).with(c.fold);
 }
 inline Gemm xattn_qk_gemm(const XAttnChain& c, int r0, int nr, half_t* qk) {
-  const int I = c.H * 64;
-  return Gemm(PC_DEC_GEMM, EPI_STORE_F16, c.q + (size_t)r0 * I, I, c.wkT, 64, qk, c.H * c.dm, nr, c.dm, 64).heads(c.H, 64, (long)c.dm * 64, c.dm);
+  const int I = c.H * c.hd;
+  return Gemm(PC_DEC_GEMM, EPI_STORE_F16, c.q + (size_t)r0 * I, I, c.wkT, c.hd, qk, c.H * c.dm, nr, c.dm, c.hd).heads(c.H, c.hd, (long)c.dm * c.hd, c.dm);
 }
 inline Gemm xattn_cv_gemm(const XAttnChain& c, int r0, int nr) {
-  return Gemm(PC_DEC_GEMM, EPI_STORE_F16, c.xctx, c.H * c.dm, c.wv, c.dm, c.ctx + (size_t)r0 * c.ldo, c.ldo, nr, 64, c.dm).heads(c.H, c.dm, (long)64 * c.dm, 64);
+  return Gemm(PC_DEC_GEMM, EPI_STORE_F16, c.xctx, c.H * c.dm, c.wv, c.dm, c.ctx + (size_t)r0 * c.ldo, c.ldo, nr, c.hd, c.dm).heads(c.H, c.dm, (long)c.hd * c.dm, c.hd);
 }
 
 // Rows [r0, r0 + p.nr) of the chain, their qk going to `qk` (the block's workspace).  Fused: c.x, c.wq and c.fold are the q projection's input, weight and norm; else c.q holds q.
 int launch_xattn(rk_engine* e, hipStream_t st, const XAttnChain& c, const XAttnPlan& p, int r0, half_t* qk) {
-  const int H = c.H, dm = c.dm, I = H * 64, nr = p.nr;
+  const int H = c.H, dm = c.dm, I = H * c.hd, nr = p.nr;
   int rc = RK_OK;
   if (p.fuse_qk) {
     DecQKArgs qa{c.x + (size_t)r0 * c.ldx, c.ldx, c.wq, c.wkT, qk, nr, dm, H, c.fold.rowscale ? c.fold.rowscale + r0 : nullptr,
@@ -1190,6 +1230,9 @@ int run_decoder(rk_engine* e, Slot& sl, int Ld, const DecRows* rows = nullptr, c
   if (tree && (have_kv || lc.one)) return fail(e, RK_ERR_STATE, "the tree form needs the query-side cross-attention and L_d >= 2");
   if (ragged && have_kv && !sl.have_cross_kv) return fail(e, RK_ERR_STATE, "the ragged pass needs the K / V the encoder did not materialise");
   if (cache && (rows || have_kv || Ld != 1)) return fail(e, RK_ERR_STATE, "the incremental pass needs the query-side cross-attention and one row per sequence");
+  // 128-wide heads: the plain one-position pass only (the entry points refuse everything else before they stage or launch)
+  if (wide_heads(e) && (!lc.one || rows || cache || have_kv || e->opt.dec_fuse == 2))
+    return refuse_wide(e, "run_decoder", "this pass would launch a 64-wide kernel");
   const bool ws = lc.stream;   // few decoder positions: weight-streaming GEMMs (any number of sequences); else tiled
   // Folded RMSNorm on the weight-streaming path (as in the encoder, minus the statistics kernel): the residual GEMMs leave
   // the new rows as fp16 with their sums of squares per 32-column block, the GEMM behind the norm reads those with the norm
@@ -1255,7 +1298,7 @@ int run_decoder(rk_engine* e, Slot& sl, int Ld, const DecRows* rows = nullptr, c
     if (!have_kv) {
       RC(run_xattn_chain(e, st, XAttnChain{cq.A, cq.lda, cq.W, w.ckT, e->cross_kv_w + ((size_t)l * 2 * I + I) * dm, cq.fold, cq.family,
                                            sl.enc_out, sl.d_seq_off, rows ? rows->seq : nullptr, Ld, 0, sl.dq, sl.xqk, sl.xpart, sl.xstat, sl.xctx,
-                                           sl.dctx, I, M, d.n_heads, dm, sl.maxL, sl.T, fuse_asked}));
+                                           sl.dctx, I, M, d.n_heads, dm, sl.maxL, sl.T, fuse_asked, head_width(e)}));
     } else {
       RC(gemm(e, st, cq));
       const half_t* kv = sl.cross_kv + (size_t)l * d.max_tokens * 2 * I;
@@ -1291,6 +1334,7 @@ int run_decoder(rk_engine* e, Slot& sl, int Ld, const DecRows* rows = nullptr, c
 // need_cross_kv: some decoder pass of the call reads the materialised K / V.
 int encoder_then_handoff_kv(rk_engine* e, Slot& sl, bool need_cross_kv) {
   hipStream_t se = enc_stream(e, sl), sd = dec_stream(e, sl);
+  if (need_cross_kv && !sl.cross_kv) return refuse_wide(e, "encoder", "the materialised cross-attention K / V are not allocated");
   if (sl.dec_pending && sd != se) HIPCHK(e, hipStreamWaitEvent(se, sl.ev_dec, 0));
   int rc = run_encoder(e, sl, need_cross_kv);
   if (rc) return rc;
@@ -1511,6 +1555,8 @@ int score_slot(rk_engine* e, int slot, const int32_t* dec_prefix, int dec_len, c
   if (!dec_prefix || dec_len <= 0 || dec_len > e->d.max_dec_len) return fail(e, RK_ERR_CAPACITY, "dec_len %d out of range (max %d)", dec_len, e->d.max_dec_len);
   if (!out_token_ids || n_out <= 0 || n_out > 64) return fail(e, RK_ERR_INVALID, "n_out must be in 1..64 (got %d)", n_out);
   if ((rc = check_ids(e, dec_prefix, dec_len, "decoder")) || (rc = check_ids(e, out_token_ids, n_out, "output"))) return rc;
+  if (wide_heads(e) && dec_len > 1) return refuse_wide(e, "rk_t5_score", "dec_len > 1 has no 128-wide decoder self-attention");
+  if ((rc = check_wide_one(e, "rk_t5_score"))) return rc;
   hipStream_t sd = dec_stream(e, sl);
   if ((rc = put_dec_ids_shared(e, sl, dec_prefix, dec_len))) return rc;
   if ((rc = sl.idx.put(e, sd, IX_OUT_IDS, out_token_ids, n_out))) return rc;
@@ -1552,6 +1598,7 @@ int compare_slot(rk_engine* e, int slot, int dec_start_id, int false_id, int tru
   const int32_t out_ids[2] = {false_id, true_id};
   if ((rc = check_ids(e, &dec_start_id, 1, "decoder")) || (rc = check_ids(e, out_ids, 2, "output"))) return rc;
   if (false_id == true_id) return fail(e, RK_ERR_INVALID, "false_id and true_id are the same id %d", false_id);
+  if ((rc = check_wide_one(e, "rk_t5_compare"))) return rc;
   hipStream_t sd = dec_stream(e, sl);
   if ((rc = put_dec_ids_shared(e, sl, &dec_start_id, 1))) return rc;
   std::vector<int> rows(sl.n_seq);
@@ -1688,7 +1735,8 @@ int rk_engine_create(const rk_model_desc* desc, int device_ordinal, rk_engine** 
   if (!desc || !out) return fail(nullptr, RK_ERR_INVALID, "null argument");
   *out = nullptr;
   const rk_model_desc& d = *desc;
-  if (d.d_kv != 64) return fail(nullptr, RK_ERR_INVALID, "d_kv=%d unsupported: the gfx950 attention kernels are built for d_kv=64", d.d_kv);
+  if (d.d_kv != 64 && d.d_kv != 128)
+    return fail(nullptr, RK_ERR_INVALID, "d_kv=%d unsupported: the gfx950 attention kernels are built for d_kv=64 and, for one decoder position, d_kv=128", d.d_kv);
   if (d.d_model % 64 || (d.n_heads * d.d_kv) % 64 || d.d_ff % 64 || d.vocab % 4)
     return fail(nullptr, RK_ERR_INVALID, "d_model, n_heads*d_kv, d_ff must be multiples of 64 and vocab of 4");
   if (d.max_distance > RK_LUT_R || d.n_buckets < 4 || d.n_buckets > 256)
@@ -1907,7 +1955,7 @@ int rk_engine_finalize(rk_engine* e) {
     RC(up_h(&w.o, H(p + ".0.SelfAttention.o.weight")));
     RC(up_h(&w.cq, H(p + ".1.EncDecAttention.q.weight")));
     RC(up_h(&w.co, H(p + ".1.EncDecAttention.o.weight")));
-    RC(up_h(&w.ckT, regroup_ckT(H(p + ".1.EncDecAttention.k.weight").data(), d.n_heads, dm)));
+    RC(up_h(&w.ckT, regroup_ckT(H(p + ".1.EncDecAttention.k.weight").data(), d.n_heads, dm, d.d_kv)));
     RC(up_h(&w.ffn_in, ffn_in(p + ".2.DenseReluDense")));
     RC(up_h(&w.ffn_out, H(p + ".2.DenseReluDense.wo.weight")));
     RC(up_f(&w.ln0, Fv(p + ".0.layer_norm.weight")));
@@ -1954,7 +2002,8 @@ int rk_engine_finalize(rk_engine* e) {
     RC(dalloc(e, &sl.enc.xraw[0], Tc * dm)); RC(dalloc(e, &sl.enc.ssq[0], Tc * ((dm + 63) / 64))); RC(dalloc(e, &sl.enc.factors, Tc + 512));   // padded: the ping-pong GEMM reads the row factors of a whole 256-row tile
     HIPCHK(e, hipMemset(sl.enc.factors, 0, (Tc + 512) * sizeof(float)));
     RC(dalloc(e, &sl.d_tokens, Tc)); RC(dalloc(e, &sl.d_seq_off, Bc + 1));
-    RC(dalloc(e, &sl.cross_kv, (size_t)d.n_dec_layers * Tc * 2 * I));
+    // (128-wide heads: one decoder position only, which never reads the materialised K / V - 393 KB per token at t5-3b)
+    if (!wide_heads(e)) RC(dalloc(e, &sl.cross_kv, (size_t)d.n_dec_layers * Tc * 2 * I));
     RC(dalloc(e, &sl.idx.d[IX_DEC_IDS], Mc)); RC(dalloc(e, &sl.idx.d[IX_LAST_ROWS], Bc)); RC(dalloc(e, &sl.idx.d[IX_OUT_IDS], 8192));
     RC(dalloc(e, &sl.idx.d[IX_ROW_LABEL], Mc)); RC(dalloc(e, &sl.idx.d[IX_ROW_OFF], 2 * Bc + 1)); RC(dalloc(e, &sl.idx.d[IX_OUT_IDX], Bc)); RC(dalloc(e, &sl.d_argmax, Bc));
     RC(dalloc(e, &sl.idx.d[IX_ROW_SEQ], Mc)); RC(dalloc(e, &sl.idx.d[IX_TREE_KEYS], Mc * (size_t)d.max_dec_len)); RC(dalloc(e, &sl.idx.d[IX_TREE_POS], Mc));
@@ -2089,6 +2138,7 @@ static int run_qlm(rk_engine* e, Slot& sl, const std::vector<QlmPass>& passes, f
 int rk_t5_qlm(rk_engine* e, const int32_t* tokens, const int32_t* seq_offsets, int n_seq, const int32_t* labels,
               int n_labels, float* out_scores) {
   int rc;
+  if (e && wide_heads(e)) return refuse_wide(e, "rk_t5_qlm", "qlm scores several decoder positions");
   if ((rc = rk_t5_stage(e, tokens, seq_offsets, n_seq))) return rc;
   Slot& sl = e->slots[0];
   if (!labels || n_labels <= 0 || n_labels > e->d.max_dec_len) return fail(e, RK_ERR_CAPACITY, "n_labels %d out of range (max %d)", n_labels, e->d.max_dec_len);
@@ -2112,6 +2162,7 @@ int rk_t5_qlm_many(rk_engine* e, const int32_t* tokens, const int32_t* seq_offse
                    const int32_t* label_offsets, float* out_scores) {
   if (!e) return RK_ERR_INVALID;
   if (e->family != 0) return fail(e, RK_ERR_STATE, "T5 entry point called on a Llama engine (use rk_llama_*)");
+  if (wide_heads(e)) return refuse_wide(e, "rk_t5_qlm_many", "qlm scores several decoder positions");
   int rc;
   if ((rc = check_batch(e, nullptr, tokens, seq_offsets, n_seq))) return rc;   // before the reorder reads the batch
   if (!out_scores || !labels || !label_offsets || label_offsets[0] != 0) return fail(e, RK_ERR_INVALID, "labels, label_offsets (from 0) or output missing");
@@ -2212,6 +2263,7 @@ static int greedy_step(rk_engine* e, Slot& sl, const std::vector<std::vector<int
 int rk_t5_greedy(rk_engine* e, const int32_t* tokens, const int32_t* seq_offsets, int n_seq, const int32_t* dec_prefix,
                  int dec_len, int max_new, int eos_id, int pad_id, int32_t* out_tokens, int32_t* out_steps) {
   int rc;
+  if (e && wide_heads(e)) return refuse_wide(e, "rk_t5_greedy", "greedy decoding runs the decoder self-attention");
   if ((rc = rk_t5_stage(e, tokens, seq_offsets, n_seq))) return rc;
   Slot& sl = e->slots[0];
   if ((rc = check_greedy_args(e, dec_prefix, dec_len, max_new))) return rc;
@@ -2264,6 +2316,7 @@ static int ensure_gen(rk_engine* e, int n_seq, int P) {
 int rk_t5_generate(rk_engine* e, const int32_t* tokens, const int32_t* seq_offsets, int n_seq, const int32_t* dec_prefix,
                    int dec_len, int max_new, int eos_id, int pad_id, int32_t* out_tokens, int32_t* out_steps) {
   int rc;
+  if (e && wide_heads(e)) return refuse_wide(e, "rk_t5_generate", "cached decoding runs the decoder self-attention");
   if ((rc = rk_t5_stage(e, tokens, seq_offsets, n_seq))) return rc;
   Slot& sl = e->slots[0];
   if ((rc = check_greedy_args(e, dec_prefix, dec_len, max_new))) return rc;
@@ -2312,6 +2365,7 @@ int rk_t5_generate(rk_engine* e, const int32_t* tokens, const int32_t* seq_offse
 int rk_t5_greedy2(rk_engine* e, const int32_t* tokens, const int32_t* seq_offsets, int n_seq, const int32_t* dec_prefix,
                   int dec_len, const int32_t* cand_ids, int n_cand, int eos_id, int pad_id, int32_t* out_tokens, int32_t* out_steps) {
   if (!e) return RK_ERR_INVALID;
+  if (wide_heads(e)) return refuse_wide(e, "rk_t5_greedy2", "greedy decoding runs the decoder self-attention");
   const int Ld = dec_len + 1;
   const long per_seq = (long)dec_len + n_cand;                         // rows of one prompt: the prefix once, one row per candidate
   const long M = (long)n_seq * per_seq, R = (long)n_seq * (1 + n_cand);
@@ -3313,7 +3367,8 @@ int rk_debug_attn(rk_engine* e, rk_debug_attn_call* q) {
   if (e->family != (kind >= 4 ? 1 : 0)) return fail(e, RK_ERR_STATE, "debug attn: kind %d needs a %s engine", kind, kind >= 4 ? "Llama" : "T5");
   if (B <= 0 || B > (1 << 16) || H <= 0 || H > 1024) return fail(e, RK_ERR_INVALID, "debug attn: n_seq and H");
   const bool planning = q->plan_only != 0;
-  const int hd = kind >= 4 ? 128 : 64, band = q->band_rows;
+  const int hd = kind >= 4 ? 128 : head_width(e), band = q->band_rows;
+  if (kind == 2 && hd != 64) return refuse_wide(e, "debug attn", "kind 2 (the decoder kernels) has no 128-wide form");
   if (!planning && (!q->q || !q->out || !q->out_all || band < 1)) return fail(e, RK_ERR_INVALID, "debug attn: q, out, out_all and band_rows >= 1");
   // ---- the offsets: lengths, the longest and the shortest ----
   int maxL = 0, minL = 1 << 30, T = 0;
@@ -3338,7 +3393,7 @@ int rk_debug_attn(rk_engine* e, rk_debug_attn_call* q) {
   EncAttnPlan ep; DecAttnPlan dp; XAttnPlan xp; CausalAttnPlan cp; LlamaDecAttnPlan lp;
   int dec_rows = 0, dec_keys = 0;
   if (kind == 1) {
-    const int I = H * 64;
+    const int I = H * hd;
     ldq_min = 3L * I; ldctx_min = I; q_rows_need = out_rows_need = T;
     if (!planning && !q->bias_lut) return fail(e, RK_ERR_INVALID, "debug attn: the encoder needs bias_lut");
     ep = plan_enc_attn(e, B, maxL, minL, H);
@@ -3460,7 +3515,7 @@ int rk_debug_attn(rk_engine* e, rk_debug_attn_call* q) {
   half_t* dC = nullptr; size_t c_all = 0;
   if (kind == 1) {
     DBG_HIP(hipDeviceSynchronize());
-    launch_enc_attn(e, st, EncAttnCall{qi, oi, dOff, dLut, q->ldq, q->ldctx, H * 64, H, B, maxL, T}, ep);
+    launch_enc_attn(e, st, EncAttnCall{qi, oi, dOff, dLut, q->ldq, q->ldctx, H * hd, H, B, maxL, T}, ep);
   } else if (kind == 2) {
     int *dRow = nullptr, *dTk = nullptr, *dTp = nullptr;
     if (q->row_off && !(dRow = (int*)up(q->row_off, (size_t)(B + 1) * 4))) return done(fail(e, RK_ERR_HIP, "debug attn: upload failed"));
@@ -3517,7 +3572,8 @@ int rk_debug_xattn_chain(rk_engine* e, rk_debug_xattn_chain_call* q) {
   if (rc) return rc;
   if (!e->finalized) return fail(e, RK_ERR_STATE, "debug xattn chain: engine not finalized");
   if (e->family != 0) return fail(e, RK_ERR_STATE, "debug xattn chain: needs a T5 engine");
-  const int M = q->M, H = q->H, d = q->d, Ld = q->Ld, B = q->n_seq, band = q->band_rows, I = H * 64;
+  const int hd = head_width(e);
+  const int M = q->M, H = q->H, d = q->d, Ld = q->Ld, B = q->n_seq, band = q->band_rows, I = H * hd;
   if (B <= 0 || B > (1 << 16) || H <= 0 || H > 1024) return fail(e, RK_ERR_INVALID, "debug xattn chain: n_seq and H");
   if (M <= 0 || M > (1 << 16) || d <= 0 || d % 32 || d > 16384 || Ld <= 0 || q->row0 < 0)
     return fail(e, RK_ERR_INVALID, "debug xattn chain: M, Ld, row0 and d (a multiple of 32)");
@@ -3539,7 +3595,7 @@ int rk_debug_xattn_chain(rk_engine* e, rk_debug_xattn_chain_call* q) {
   if (q->ssq_in && (q->nb_in <= 0 || q->nb_in > 4096)) return fail(e, RK_ERR_INVALID, "debug xattn chain: ssq_in needs nb_in in 1..4096");
   // ---- the plan: of the first and of the last block of the row loop ----
   XAttnChain c{};
-  c.ldx = q->ldx; c.Ld = Ld; c.row0 = q->row0; c.ldo = q->ldo; c.M = M; c.H = H; c.dm = d; c.maxL = maxL; c.T = T; c.fuse_asked = q->fuse_asked != 0;
+  c.ldx = q->ldx; c.Ld = Ld; c.row0 = q->row0; c.ldo = q->ldo; c.M = M; c.H = H; c.dm = d; c.maxL = maxL; c.T = T; c.fuse_asked = q->fuse_asked != 0; c.hd = hd;
   c.family = dec_len_class(e, Ld).stream ? GEMM_STREAM : GEMM_TILED;
   const bool fuse = xattn_chain_fused(c);
   const int blk = xattn_block_rows(maxL), n_blocks = (M + blk - 1) / blk, wrows = std::min(blk, M), nch = (maxL + 63) / 64;
@@ -3582,7 +3638,7 @@ int rk_debug_xattn_chain(rk_engine* e, rk_debug_xattn_chain_call* q) {
     if (ptr && hipMemcpy(ptr, src, bytes, hipMemcpyHostToDevice) != hipSuccess) return nullptr;
     return ptr;
   };
-  const std::vector<half_t> ckT = regroup_ckT((const half_t*)q->wk, H, d);
+  const std::vector<half_t> ckT = regroup_ckT((const half_t*)q->wk, H, d, hd);
   half_t* dX = (half_t*)up(q->x, (size_t)M * q->ldx * 2);
   half_t* dWq = (half_t*)up(q->wq, (size_t)I * d * 2);
   half_t* dWkT = (half_t*)up(ckT.data(), (size_t)I * d * 2);

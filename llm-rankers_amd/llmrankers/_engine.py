@@ -601,7 +601,7 @@ class RkEngine:
     def debug_xattn_chain(self, *, M: int, Ld: int, H: int, d: int, seq_off, x=None, wq=None, wk=None, wv=None, enc=None, row0=0, row_seq=None,
                           rowscale=None, ssq_in=None, ctx=None, ldo=0, band_rows=8, fuse_asked=True, ws_fill=0, plan_only=False) -> dict:
         """The decoder's query-side cross-attention chain through rk_debug_xattn_chain (include/rk_engine.h).  x [M, ldx], wq / wk / wv
-        [H 64, d], enc [band_rows + T + band_rows, d] (the caller's bands), ctx [M, ldo] (the pre-filled interior) or None: fp16.
+        [H hd, d] (hd = the engine's head width, 64 or 128), enc [band_rows + T + band_rows, d] (the caller's bands), ctx [M, ldo] (the pre-filled interior) or None: fp16.
         Returns the plan fields and, unless plan_only, the whole device allocations after the call: "qk" [band_rows + M + band_rows,
         H, d], "ctx" [band_rows + M + band_rows, ldo], and per block of the row loop "part" [n_blocks, band_rows H d + R nch H d +
         band_rows H d], "stat" [n_blocks, band_rows H 2 + R nch H 2 + band_rows H 2] fp32 and "xctx" [n_blocks, band_rows + R + band_rows,
@@ -609,7 +609,8 @@ class RkEngine:
         in its `outputs` attribute (a call that launched nothing leaves them as they were)."""
         c = RkDebugXattnChainCall()
         seq_off = np.ascontiguousarray(seq_off, dtype=np.int32)
-        ldo = ldo or 64 * H
+        hd = 128 if int(getattr(self.desc, "d_kv", 64)) == 128 else 64
+        ldo = ldo or hd * H
         c.M, c.Ld, c.H, c.d, c.n_seq, c.row0, c.ldo, c.band_rows = M, Ld, H, d, seq_off.size - 1, row0, ldo, band_rows
         c.fuse_asked, c.ws_fill, c.seq_off = int(fuse_asked), ws_fill, seq_off.ctypes.data
         keep = [seq_off]
@@ -634,7 +635,7 @@ class RkEngine:
             c.ldx = x.shape[1]
         for name, w in (("wq", wq), ("wk", wk), ("wv", wv)):
             w = put(name, w, np.float16)
-            assert w is None or w.shape == (64 * H, d)
+            assert w is None or w.shape == (hd * H, d)
         if enc is not None:
             enc = put("enc", enc, np.float16)
             assert enc.ndim == 2 and enc.shape[1] == d and enc.shape[0] >= 2 * band_rows

@@ -14,7 +14,7 @@ from typing import Iterator, List, Sequence, Tuple
 import numpy as np
 
 from . import _synth
-from ._engine import RkEngine, RkLlamaEngine
+from ._engine import RkEngine, RkError, RkLlamaEngine
 
 
 def parse_device(device) -> int:
@@ -199,8 +199,31 @@ def _iter_torch_bin(model_dir: str) -> Iterator[Tuple[str, np.ndarray]]:
                 yield k, t.float().numpy()
 
 
+def require_decoder_positions(runtime, who: str) -> None:
+    """Rankers that score or decode beyond ONE decoder position (qlm, setwise, listwise, PRP) call this when they are built: a
+    T5 with 128-wide heads (t5-3b / t5-11b: monoT5-3B, duoT5-3B) runs on the engine at one position only, and none of the public
+    checkpoints of that width is an instruction model such rankers could use."""
+    if getattr(runtime, "one_position_only", False):
+        raise NotImplementedError(f"{who} needs more than one decoder position; a T5 with d_kv=128 is served at one position only "
+                                  "(MonoT5LlmRanker, PointwiseLlmRanker(method='yes_no'), DuoT5LlmRanker)")
+
+
 class T5Runtime:
     """Engine + chunking so a call may exceed the engine's token capacity (results are batch-independent)."""
+
+    @property
+    def one_position_only(self) -> bool:
+        """The model has 128-wide heads: the engine serves score() with a one-token decoder prefix and compare_pairs() only."""
+        return int(self.dims.d_kv) == 128
+
+    def _served(self, call, *args):
+        """An engine call; the engine's refusal of an entry point a 128-wide model does not have -> NotImplementedError with its message."""
+        try:
+            return call(*args)
+        except RkError as err:
+            if self.one_position_only and "d_kv=128" in str(err):
+                raise NotImplementedError(str(err)) from None
+            raise
 
     def __init__(self, model_name_or_path: str, device, max_tokens: int = 49152, max_seqs: int = 256,
                  max_dec_len: int = 136, cache_dir=None):
@@ -315,7 +338,7 @@ class T5Runtime:
             yield cur
 
     def score(self, seqs, dec_prefix, out_ids) -> np.ndarray:
-        return np.concatenate([self.engine.score(c, dec_prefix, out_ids) for c in self._chunks(seqs)], axis=0)
+        return np.concatenate([self._served(self.engine.score, c, dec_prefix, out_ids) for c in self._chunks(seqs)], axis=0)
 
     def score_stream(self, groups, dec_prefix, out_ids) -> np.ndarray:
         """Scores [n, len(out_ids)] of the token sequences that the iterable `groups` yields (lists of sequences, e.g. one
@@ -432,14 +455,14 @@ class T5Runtime:
         return self.engine.read_scores(handle)
 
     def qlm(self, seqs, labels) -> np.ndarray:
-        return np.concatenate([self.engine.qlm(c, labels) for c in self._chunks(seqs)], axis=0)
+        return np.concatenate([self._served(self.engine.qlm, c, labels) for c in self._chunks(seqs)], axis=0)
 
     def qlm_many(self, seqs, labels_per_seq) -> np.ndarray:
         """qlm scores of sequences with their OWN labels each (the passages of several queries): one engine call per capacity
         chunk, whatever the number of queries in it.  Element b is bit for bit what qlm gives seqs[b] with labels_per_seq[b]."""
         parts, done = [], 0
         for c in self._chunks(seqs):
-            parts.append(self.engine.qlm_many(c, labels_per_seq[done:done + len(c)]))
+            parts.append(self._served(self.engine.qlm_many, c, labels_per_seq[done:done + len(c)]))
             done += len(c)
         return np.concatenate(parts, axis=0) if parts else np.zeros(0, np.float32)
 
@@ -462,7 +485,7 @@ class T5Runtime:
         RkEngine.greedy (a hint that never changes the result)."""
         parts = []
         for c in self._chunks(seqs):
-            toks, steps = self.engine.greedy(c, dec_prefix, max_new, eos_id, pad_id, candidates)
+            toks, steps = self._served(self.engine.greedy, c, dec_prefix, max_new, eos_id, pad_id, candidates)
             toks = toks.copy()
             toks[:, steps:] = -1
             parts.append(toks)
@@ -474,7 +497,7 @@ class T5Runtime:
         KV-cached incremental decoder (RkEngine.generate); chunked by capacity the same way."""
         parts = []
         for c in self._chunks(seqs):
-            toks, steps = self.engine.generate(c, dec_prefix, max_new, eos_id, pad_id)
+            toks, steps = self._served(self.engine.generate, c, dec_prefix, max_new, eos_id, pad_id)
             toks = toks.copy()
             toks[:, steps:] = -1
             parts.append(toks)

@@ -97,6 +97,12 @@ TOY_RELU_TIED = T5Dims(vocab=256, d_model=128, n_heads=3, d_kv=64, d_ff=256, n_e
 TOY_MONOT5 = T5Dims(vocab=6144, d_model=128, n_heads=3, d_kv=64, d_ff=256, n_enc=2, n_dec=2, gated=False, tied_head=True)
 # duot5-base (T5 v1.0 base: relu, tied + scaled head), the published duoT5 checkpoint's dimensions (tools/bench_duot5.py)
 DUOT5_BASE = T5Dims(vocab=32128, d_model=768, n_heads=12, d_kv=64, d_ff=3072, n_enc=12, n_dec=12, gated=False, tied_head=True)
+# t5-3b (T5 v1.0: relu, tied + scaled head, 128-WIDE heads): the dimensions of castorini/monot5-3b-msmarco and duot5-3b-msmarco,
+# the checkpoints the reference's README names.  Served at ONE decoder position (monoT5, yes_no, duoT5).
+T5_3B = T5Dims(vocab=32128, d_model=1024, n_heads=32, d_kv=128, d_ff=16384, n_enc=24, n_dec=24, gated=False, tied_head=True)
+# TOY_MONOT5 with 128-wide heads
+TOY_MONOT5_D128 = T5Dims(vocab=6144, d_model=128, n_heads=3, d_kv=128, d_ff=256, n_enc=2, n_dec=2, gated=False, tied_head=True)
+
 
 @dataclass(frozen=True)
 class LlamaDims:
@@ -221,6 +227,7 @@ def llama_tensor_specs(d: "LlamaDims") -> Iterator[Tuple[str, Tuple[int, ...], f
 NAMED_DIMS = {
     "flan-t5-small": FLAN_T5_SMALL, "flan-t5-base": FLAN_T5_BASE, "flan-t5-large": FLAN_T5_LARGE,
     "flan-t5-xl": FLAN_T5_XL, "toy-gated-untied": TOY_GATED_UNTIED, "toy-relu-tied": TOY_RELU_TIED, "toy-monot5": TOY_MONOT5, "duot5-base": DUOT5_BASE,
+    "t5-3b": T5_3B, "toy-monot5-d128": TOY_MONOT5_D128,
     "llama-3-8b": LLAMA_3_8B, "toy-llama": TOY_LLAMA, "toy-llama3rope": TOY_LLAMA3ROPE,
     "qwen2.5-7b": QWEN25_7B, "toy-qwen2": TOY_QWEN2,
 }

@@ -119,6 +119,8 @@ class ListwiseLlmRanker(LlmRanker):
         return self
 
     def _setup(self, runtime, tokenizer, device, window_size, step_size, scoring, num_repeat, max_new):
+        from ._runtime import require_decoder_positions
+        require_decoder_positions(runtime, type(self).__name__)
         self.model_type = getattr(runtime, "model_type", "t5")
         if self.model_type == "llama" and not hasattr(runtime, "generate"):
             raise NotImplementedError(f"{LLAMA_MESSAGE} (Llama runtime {type(runtime).__name__})")

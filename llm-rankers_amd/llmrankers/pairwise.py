@@ -30,6 +30,7 @@ WIN = ["Passage A", "Passage B"]       # the first passage of the pair wins iff 
 
 
 class PairwiseLlmRanker(LlmRanker):
+    needs_decoder_positions = True            # PRP generates two tokens behind "<pad> Passage" (DuoT5LlmRanker: one position)
 
     def __init__(self, model_name_or_path, tokenizer_name_or_path, device, method="allpair", batch_size=2, k=10,
                  cache_dir=None):
@@ -62,6 +63,9 @@ class PairwiseLlmRanker(LlmRanker):
         return self
 
     def _setup(self, runtime, tokenizer, device, method, batch_size, k):
+        if self.needs_decoder_positions:
+            from ._runtime import require_decoder_positions
+            require_decoder_positions(runtime, type(self).__name__)
         self.device, self.method, self.batch_size, self.k = device, method, batch_size, k
         self.prompt = PROMPT
         self.llm, self.tokenizer = runtime, tokenizer
@@ -224,6 +228,7 @@ class DuoT5LlmRanker(PairwiseLlmRanker):
     result assembly as the reference; the caller's list is not reordered."""
     FALSE_ID, TRUE_ID = 6136, 1176            # the ids of "false" / "true" in the T5 vocabulary (ref :314-315)
     fp16_scores = False                       # True: the host verdict from the returned logits, rounded as the reference's fp16 model does
+    needs_decoder_positions = False
 
     def _setup(self, runtime, tokenizer, device, method, batch_size, k):
         super()._setup(runtime, tokenizer, device, method, batch_size, k)

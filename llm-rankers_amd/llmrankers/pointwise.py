@@ -36,6 +36,7 @@ class PointwiseLlmRanker(LlmRanker):
     # Scores are fp32 softmaxes of the engine's fp32 logits (closest to the reference's CPU ground truth).  Set to True to
     # get the reference's 'cuda' score values instead: fp16 logits and fp16 probabilities, hence its exact ties.
     fp16_scores = False
+    ignores_method = False      # MonoT5LlmRanker: one scoring form whatever `method` says
 
     def __init__(self, model_name_or_path, tokenizer_name_or_path, device, method="qlm", batch_size=1, cache_dir=None,
                  shard_candidates=False):
@@ -56,6 +57,9 @@ class PointwiseLlmRanker(LlmRanker):
         return self
 
     def _setup(self, runtime, tokenizer, device, method, batch_size, shard_candidates):
+        if method == "qlm" and not self.ignores_method:
+            from ._runtime import require_decoder_positions
+            require_decoder_positions(runtime, "PointwiseLlmRanker(method='qlm')")
         self.tokenizer = tokenizer
         self.llm = runtime
         self.config = getattr(runtime, "config", None)
@@ -337,6 +341,7 @@ class MonoT5LlmRanker(PointwiseLlmRanker):
     """ref: pointwise.py:136-186 — softmax over the fixed ids of 'false'/'true', decoder start token as input;
     the reference's rerank ignores `method`."""
     FALSE_ID, TRUE_ID = 6136, 1176
+    ignores_method = True
 
     def _spec(self, query: str, docs: List[SearchResult]):
         prompts = [MONOT5_PROMPT.format(query=query, document=doc.text) for doc in docs]

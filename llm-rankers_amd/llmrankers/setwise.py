@@ -86,6 +86,8 @@ class SetwiseLlmRanker(LlmRanker):
         return self
 
     def _setup(self, runtime, tokenizer, device, num_child, k, scoring, method, num_permutation):
+        from ._runtime import require_decoder_positions
+        require_decoder_positions(runtime, type(self).__name__)
         self.device = device
         self.num_child = num_child
         self.num_permutation = num_permutation
