@@ -156,7 +156,7 @@ int rk_t5_scores_device_ptr(rk_engine* e, void** out_ptr);
  * (ref: llmrankers/setwise.py:60-69, 159-177): self.llm.generate(input_ids, do_sample=False, max_new_tokens=1) = prefill
  * of the prompt + arg-max of the last position's logits; and of its listwise ranker (ref: llmrankers/listwise.py:261-271):
  * self.llm.generate(input_ids) = rk_llama_generate, the prefill once and then one KV-cached row per new token.  hf: models/llama/modeling_llama.py (RMSNorm, RoPE with
- * rope_theta, grouped-query causal attention with head_dim 128, SwiGLU).  Weights go through rk_engine_load_tensor with
+ * rope_theta, grouped-query causal attention with head_dim 64 or 128 - RK_ERR_INVALID for any other width -, SwiGLU).  Weights go through rk_engine_load_tensor with
  * the HF Llama names ("model.layers.0.self_attn.q_proj.weight", ...) and rk_engine_finalize; rk_engine_destroy frees. */
 typedef struct rk_llama_desc {
   int32_t vocab, hidden, n_heads, n_kv_heads, head_dim, intermediate, n_layers;
@@ -173,7 +173,7 @@ int rk_llama_create(const rk_llama_desc* desc, int device_ordinal, rk_engine** o
 int rk_llama_set_rope_scaling(rk_engine* e, float factor, float low_freq_factor, float high_freq_factor, int original_max_pos);
 /* Qwen2 family (hf: models/qwen2/modeling_qwen2.py; Qwen2.5-Instruct checkpoints, the Rank-R1 rerankers of ref:
  * llmrankers/setwise.py:406-553): the q / k / v projections carry a bias.  on != 0: rk_engine_finalize requires
- * model.layers.N.self_attn.{q,k,v}_proj.bias (shapes n_heads * 128, n_kv_heads * 128, n_kv_heads * 128) and the engine adds them
+ * model.layers.N.self_attn.{q,k,v}_proj.bias (shapes n_heads * head_dim, n_kv_heads * head_dim, n_kv_heads * head_dim) and the engine adds them
  * in fp32 to the projections' output before the rotation.  Call between rk_llama_create and the first rk_engine_load_tensor;
  * RK_ERR_STATE on a T5 engine or after finalize.  Never calling it (or on = 0): the bias names are ignored. */
 int rk_llama_set_qkv_bias(rk_engine* e, int on);
@@ -326,7 +326,8 @@ int rk_debug_gemm_ex(rk_engine* e, rk_debug_gemm_call* call);
 /* debug: run ANY attention call of the engine (csrc/rk_engine.hip: plan_*attn -> the plan's launcher, no kernel and no dispatch of
  * its own) on host data, every output inside guard bands.  kind selects the plan; heads have the kernels' own width (64 for the T5
  * kinds - 128 on a T5 engine created with d_kv = 128, where kind 1 runs the 128-wide plan (out_kind 3) whatever attn_short / attn_long
- * say, kind 2 is RK_ERR_STATE and kind 3 is unchanged -, 128 for the Llama kinds); an engine of the other family gets RK_ERR_STATE.
+ * say, kind 2 is RK_ERR_STATE and kind 3 is unchanged -, the engine's head_dim hd, 64 or 128, for the Llama kinds: a 64-wide Llama engine
+ * runs the 64-wide plans, written below with hd = 128); an engine of the other family gets RK_ERR_STATE.
  *   1 T5 encoder         plan_enc_attn: q = packed qkv [T, ldq] (q | k | v at columns 0 | I | 2I, I = 64 H or 128 H), seq_off[n_seq + 1], bias_lut
  *                        [H][257] (entry rel + 128 for rel = key - query clamped to +-128; the table itself, not built from weights),
  *                        out = ctx [T, ldctx].  Options attn_short, attn_heads_per_wg, attn_long, attn_long_nw, attn_long_xcd.
@@ -340,17 +341,17 @@ int rk_debug_gemm_ex(rk_engine* e, rk_debug_gemm_call* call);
  *                        [T, d] (ldkv = d), seq_off; query m belongs to sequence row_seq[row0 + m] (n_row_seq entries) or (row0 + m) / Ld;
  *                        out [M, H, d] (ldctx = H d) = sum_t softmax_t(qk_h . enc_t) enc_t.  Option xattn_mfma.
  *   4 Llama prefill      plan_llama_attn: q = rotated qkv [T, ldq] (H query heads, n_kv key heads, n_kv value heads of 128), seq_off,
- *                        out = ctx [T, ldctx].  Options llama_attn_dma, llama_attn_nw.
+ *                        out = ctx [T, ldctx].  Options llama_attn_dma, llama_attn_nw (ignored at hd = 64: one kernel, out_kind 2).
  *   5 Llama cached step  plan_llama_dec_attn: q = the step's rows [n_seq, ldq], NOT rotated; cache = K [n_seq][n_kv][P][128] then V, pos[n_seq]
- *                        (< P, < max_pos), cos_t / sin_t [max_pos][64], qkv_bias [(H + 2 n_kv) 128] fp32 or null; out = ctx [n_seq, H 128]
+ *                        (< P, < max_pos), cos_t / sin_t [max_pos][64] ([max_pos][32] at hd = 64), qkv_bias [(H + 2 n_kv) 128] fp32 or null; out = ctx [n_seq, H 128]
  *                        (ldctx = H 128); cache_all = the cache afterwards (the row's rotated key and its value appended at pos).  Option llama_dec_r.
  * Inputs q / kv: host fp16, the WHOLE allocation: band_rows rows in front of and behind the q_rows / kv_rows interior rows, all of ldq /
  * ldkv elements; the caller fills the bands (finite values: a kernel may load a masked row and give it weight 0); the call's pointer is
  * the first interior row.  out: the interior, out_rows x ldctx elements, copied to the device as it is (the caller pre-fills what no
  * kernel may touch); out_all: (out_rows + 2 band_rows) x ldctx elements, the whole device allocation after the call, the bands filled
- * with the byte RK_DEBUG_SENTINEL before it.  cache / cache_all: the same with bands of band_rows x 128 elements.
+ * with the byte RK_DEBUG_SENTINEL before it.  cache / cache_all: the same with bands of band_rows x hd elements.
  * plan_only != 0: nothing is allocated or launched, only the out_* fields are filled: out_kind (1: DMA 0 / LONG 1 / TILED 2 / D128 3; 2: the
- * staged kernel NONE 0 / SEQ 1 / ROW 2; 3: part MFMA_FEW 0 / MFMA 1 / VALU16 2 / VALU4 3; 4: dma 0 / 1), out_tparam (the kernel's template
+ * staged kernel NONE 0 / SEQ 1 / ROW 2; 3: part MFMA_FEW 0 / MFMA 1 / VALU16 2 / VALU4 3; 4: dma 0 / 1, or 2 = the 64-wide kernel), out_tparam (the kernel's template
  * parameter: wave groups, waves, heads per workgroup or R), out_grid (the first kernel's), out_grid2 (the tiled / staged / merge
  * kernel's), out_lds, out_staged, out_mfma, out_part, out_R, out_nch, out_skip_long, out_heads_per_wg, out_n_cu.
  * Every extent is checked against the sizes given before anything is launched (RK_ERR_INVALID); a shape no kernel of the plan takes

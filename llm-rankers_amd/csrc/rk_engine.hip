@@ -27,6 +27,7 @@
 #include "gemm.h"
 #include "gemv_rows.h"
 #include "llama_kernels.h"
+#include "llama_kernels_hd64.h"
 #include "misc_kernels.h"
 
 namespace {
@@ -199,7 +200,7 @@ struct rk_engine {
   float rope_factor = 0.f, rope_low = 1.f, rope_high = 4.f; int rope_orig = 0;   // rope type llama3 when rope_factor > 0
   bool qkv_bias = false;                                                          // Qwen2 family: q / k / v projections carry a bias
   std::vector<LlamaLayerW> ll; float *l_final_ln = nullptr, *rope_cos = nullptr, *rope_sin = nullptr; int* d_pos = nullptr;
-  // rk_llama_generate: K / V cache [n_layers][2][n_seq][n_kv][P][128], the attention partials and the call's int block (grown
+  // rk_llama_generate: K / V cache [n_layers][2][n_seq][n_kv][P][head_dim], the attention partials and the call's int block (grown
   // between calls; lkv_gen counts the moves and is part of the step graph's key), and the step's activation rows (max_seqs each)
   Grown<half_t> lkv; Grown<float> lpart; Grown<int> lints; int lkv_gen = 0;
   struct LlamaStep { NormStream stream; half_t *qkv = nullptr, *ctx = nullptr, *ffh = nullptr; } lg;
@@ -800,8 +801,10 @@ int DecIndex::tree(rk_engine* e, hipStream_t st, std::vector<int>& sig, std::ini
 // only (rk_t5_score with dec_len 1, rk_t5_compare): the encoder through attn_enc128_kernel, the decoder through the W_o W_v product
 // and the five-launch query-side cross-attention chain, whose per-head GEMMs carry the width.  Every other 64-wide kernel
 // (decoder self-attention, the materialised K / V, the fused chain projections) is never launched there: refuse_wide.
-inline int head_width(const rk_engine* e) { return e->family == 0 ? e->d.d_kv : 64; }
-inline bool wide_heads(const rk_engine* e) { return head_width(e) == 128; }
+// A Llama-family engine's is its head_dim (64 or 128: llama_kernels_hd64.h / llama_kernels.h serve every entry point at both); no T5
+// path reads it there - every T5 entry point refuses a Llama engine first, and wide_heads, the T5 refusals' test, is T5 only.
+inline int head_width(const rk_engine* e) { return e->family == 0 ? e->d.d_kv : e->ld.head_dim; }
+inline bool wide_heads(const rk_engine* e) { return e->family == 0 && head_width(e) == 128; }
 int refuse_wide(rk_engine* e, const char* entry, const char* what) {
   return fail(e, RK_ERR_STATE, "%s: d_kv=128 engines serve one decoder position only (rk_t5_score with dec_len 1, rk_t5_compare); %s", entry, what);
 }
@@ -1093,10 +1096,17 @@ int run_xattn_chain(rk_engine* e, hipStream_t st, const XAttnChain& c, const XAt
 // Causal attention of one llama_prefill call (hf: modeling_llama.py:130-214)
 struct CausalAttnPlan {
   bool dma = false; int nw = 0, nqb = 0;   // attn_causal128_dma_kernel<nw>, query blocks of 32 nw; else attn_causal128_kernel
+  bool hd64 = false;                       // attn_causal64_kernel (llama_kernels_hd64.h), every call of a 64-wide engine
   dim3 grid; int block = 256, lds = 0, lds_opt_in = 0;
 };
 CausalAttnPlan plan_llama_attn(const rk_engine* e, int n_seq, int maxL, int n_heads, int n_kv) {
   CausalAttnPlan p;
+  if (head_width(e) == 64) {
+    // 64-wide heads: ONE kernel for every length, whatever llama_attn_dma / llama_attn_nw say (they choose between 128-wide
+    // kernels): plan_enc_attn's D128 precedent.  Static LDS (reported, not requested at launch).
+    p.hd64 = true; p.grid = dim3((maxL + 127) / 128, n_heads, n_seq); p.lds = ATC64_LDS_BYTES;
+    return p;
+  }
   p.dma = e->opt.llama_attn_dma;   // K / V chunks by LDS-DMA, V^T by transposing reads (round 5); chosen by the option alone: batch-independent
   if (!p.dma) { p.grid = dim3((maxL + 127) / 128, n_heads, n_seq); return p; }
   p.nw = e->opt.llama_attn_nw == 8 ? 8 : 4;   // same bits either way
@@ -1112,10 +1122,12 @@ CausalAttnPlan plan_llama_attn(const rk_engine* e, int n_seq, int maxL, int n_he
 // what the launcher reads of a call: llama_prefill fills it from its slot and the model, rk_debug_attn from host operands
 struct CausalAttnCall { const half_t* qkv; half_t* ctx; const int* seq_off; int ld, ldctx, n_heads, n_kv, n_seq, maxL, T; };
 void launch_llama_attn(rk_engine* e, hipStream_t st, const CausalAttnCall& c, const CausalAttnPlan& p) {
-  const int T = c.T, Q = c.n_heads * 128, KV = c.n_kv * 128;
-  const float scale_log2e = (1.0f / std::sqrt(128.0f)) * 1.4426950408889634f;   // head_dim**-0.5 * log2(e)
+  const int hd = p.hd64 ? 64 : 128;
+  const int T = c.T, Q = c.n_heads * hd, KV = c.n_kv * hd;
+  const float scale_log2e = (1.0f / std::sqrt((float)hd)) * 1.4426950408889634f;   // head_dim**-0.5 * log2(e)
   AttnCausalArgs a{c.qkv, c.ctx, c.seq_off, c.ld, c.ldctx, c.n_heads, c.n_kv, scale_log2e, 0, 0, e->opt.attn_ko};
   Bracket br(e, st, PC_ENC_ATTN, 2.0 * (double)c.maxL * T * Q, (double)T * (2 * Q + 2 * KV) * 2.0);   // causal: half of 4 L T Q
+  if (p.hd64) { hipLaunchKernelGGL(attn_causal64_kernel, p.grid, dim3(p.block), 0, st, a); return; }
   if (!p.dma) { hipLaunchKernelGGL(attn_causal128_kernel, p.grid, dim3(p.block), 0, st, a); return; }
   a.n_seq = c.n_seq; a.nqb = p.nqb;
   if (p.nw == 8) launch_lds<attn_causal128_dma_kernel<8>>(st, p.grid, p.block, p.lds, p.lds_opt_in, a);
@@ -1130,13 +1142,16 @@ void launch_llama_attn(rk_engine* e, hipStream_t st, const CausalAttnCall& c, co
 // option llama_dec_r = 2 (measurement and tests only; G = 6 / 5 / 3 were not measured and have none), but is NOT the rule: measured at Qwen2.5-7B widths it lost at one row (6.19 against 5.95 ms
 // per token: 17 chunks x 4 kv heads = 68 workgroups on 256 CUs, where R = 1 has 476 and L2 serves the re-reads) and only tied
 // at eight rows (7.60 / 7.65; profiles/rankr1_bench.txt).  llama_dec_r = 1 forces R = 1.  Same bits whichever (tests).
-struct LlamaDecAttnPlan { int R = 1, nch = 1; dim3 grid, cgrid; };
+// A 64-wide engine (llama_kernels_hd64.h) follows the same rule with the same chunk length; it has no R = 7 instantiation, so
+// llama_dec_r = 2 falls back to the rule there.
+struct LlamaDecAttnPlan { int R = 1, nch = 1, hd = 128; dim3 grid, cgrid; };
 LlamaDecAttnPlan plan_llama_dec_attn(const rk_engine* e, int rows, int P, int n_heads, int n_kv) {
   LlamaDecAttnPlan p;                                        // (no CU count enters: fixed chunk length, model-constant R)
   const int G = n_heads / n_kv;
+  p.hd = head_width(e);
   p.R = G % 8 == 0 ? 8 : (G % 4 == 0 ? 4 : (G % 2 == 0 ? 2 : 1));
   if (e->opt.llama_dec_r == 1) p.R = 1;
-  if (e->opt.llama_dec_r == 2 && G == 7) p.R = 7;
+  if (e->opt.llama_dec_r == 2 && G == 7 && p.hd == 128) p.R = 7;
   p.nch = (P + LDC_CHUNK - 1) / LDC_CHUNK;
   p.grid = dim3(p.nch, n_heads / p.R, rows);
   p.cgrid = dim3(n_heads, rows);
@@ -1145,7 +1160,23 @@ LlamaDecAttnPlan plan_llama_dec_attn(const rk_engine* e, int rows, int P, int n_
 
 void launch_llama_dec_attn(rk_engine* e, hipStream_t st, const LlamaDecAttnPlan& p, AttnDecCached128Args a, int rows) {
   a.nch = p.nch;
-  Bracket br(e, st, PC_DEC_ATTN, 4.0 * rows * (double)a.P * a.n_heads * 128, 2.0 * rows * (double)a.P * a.n_kv * 128 * 2.0);
+  Bracket br(e, st, PC_DEC_ATTN, 4.0 * rows * (double)a.P * a.n_heads * p.hd, 2.0 * rows * (double)a.P * a.n_kv * p.hd * 2.0);
+  if (p.hd == 64) {
+    auto go64 = [&](auto rc) {
+      constexpr int R = decltype(rc)::value;
+      if (a.bias) hipLaunchKernelGGL(attn_dec_cached64_bias_kernel<R>, p.grid, dim3(256), 0, st, a);
+      else hipLaunchKernelGGL(attn_dec_cached64_kernel<R>, p.grid, dim3(256), 0, st, a);
+    };
+    using std::integral_constant;
+    switch (p.R) {
+      case 8: go64(integral_constant<int, 8>{}); break;
+      case 4: go64(integral_constant<int, 4>{}); break;
+      case 2: go64(integral_constant<int, 2>{}); break;
+      default: go64(integral_constant<int, 1>{}); break;
+    }
+    hipLaunchKernelGGL(attn_dec_combine64_kernel, p.cgrid, dim3(64), 0, st, a);
+    return;
+  }
   auto go = [&](auto rc) {                                   // the bias-free instantiation is the Llama kernel as it was
     constexpr int R = decltype(rc)::value;
     if (a.bias) hipLaunchKernelGGL(attn_dec_cached128_bias_kernel<R>, p.grid, dim3(256), 0, st, a);
@@ -2445,7 +2476,8 @@ int rk_llama_create(const rk_llama_desc* desc, int device_ordinal, rk_engine** o
   if (!desc || !out) return fail(nullptr, RK_ERR_INVALID, "null argument");
   *out = nullptr;
   const rk_llama_desc& l = *desc;
-  if (l.head_dim != 128) return fail(nullptr, RK_ERR_INVALID, "head_dim=%d unsupported: the gfx950 causal attention kernel is built for head_dim=128", l.head_dim);
+  if (l.head_dim != 64 && l.head_dim != 128)
+    return fail(nullptr, RK_ERR_INVALID, "head_dim=%d unsupported: the gfx950 causal attention kernels are built for head_dim=64 and head_dim=128", l.head_dim);
   if (l.n_kv_heads <= 0 || l.n_heads % l.n_kv_heads) return fail(nullptr, RK_ERR_INVALID, "n_heads must be a multiple of n_kv_heads");
   if (l.hidden % 64 || l.intermediate % 64 || l.vocab % 4 || l.hidden > 4096) return fail(nullptr, RK_ERR_INVALID, "hidden / intermediate must be multiples of 64 (hidden <= 4096), vocab of 4");
   if (l.max_tokens <= 0 || l.max_seqs <= 0 || l.n_layers <= 0) return fail(nullptr, RK_ERR_INVALID, "capacities and layer count must be positive");
@@ -2462,7 +2494,7 @@ int rk_llama_create(const rk_llama_desc* desc, int device_ordinal, rk_engine** o
 
 static int llama_finalize(rk_engine* e) {
   const rk_llama_desc& l = e->ld;
-  const int dm = l.hidden, Q = l.n_heads * 128, KV = l.n_kv_heads * 128, F = l.intermediate, V = l.vocab;
+  const int hd = l.head_dim, dm = l.hidden, Q = l.n_heads * hd, KV = l.n_kv_heads * hd, F = l.intermediate, V = l.vocab;
   std::string missing;
   auto N2 = [&](const std::string& n, int64_t r, int64_t c) { return need(e, n, r, c, &missing); };
   auto N1 = [&](const std::string& n, int64_t r) { return need(e, n, r, -1, &missing); };
@@ -2526,12 +2558,13 @@ static int llama_finalize(rk_engine* e) {
     RC(upload(e, &w.down, H(p + ".mlp.down_proj.weight").data(), (size_t)dm * F));
   }
   e->host.clear();
-  {   // rotary tables, float32 like hf: modeling_llama.py:94-127: freq_i = theta^(-2i/128), then the llama3 rope type's
+  {   // rotary tables [max_tokens][hd / 2], float32 like hf: modeling_llama.py:94-127: freq_i = theta^(-2i/hd), then the llama3 rope type's
       // wavelength-dependent scaling (hf: modeling_rope_utils.py _compute_llama3_parameters) when it was asked for
     const size_t Tc = l.max_tokens;
-    std::vector<float> c(Tc * 64), sn(Tc * 64);
-    for (int i = 0; i < 64; ++i) {
-      float inv = 1.0f / powf(l.rope_theta, (float)(2 * i) / 128.0f);
+    const size_t hh = (size_t)hd / 2;
+    std::vector<float> c(Tc * hh), sn(Tc * hh);
+    for (int i = 0; i < (int)hh; ++i) {
+      float inv = 1.0f / powf(l.rope_theta, (float)(2 * i) / (float)hd);
       if (e->rope_factor > 0.f) {
         const float orig = (float)e->rope_orig, wavelen = 6.283185307179586f / inv;
         const float scaled = wavelen > orig / e->rope_low ? inv / e->rope_factor : inv;
@@ -2539,7 +2572,7 @@ static int llama_finalize(rk_engine* e) {
         const bool medium = !(wavelen < orig / e->rope_high) && !(wavelen > orig / e->rope_low);
         inv = medium ? (1.0f - smooth) * scaled / e->rope_factor + smooth * scaled : scaled;
       }
-      for (size_t t = 0; t < Tc; ++t) { const float a = (float)t * inv; c[t * 64 + i] = cosf(a); sn[t * 64 + i] = sinf(a); }
+      for (size_t t = 0; t < Tc; ++t) { const float a = (float)t * inv; c[t * hh + i] = cosf(a); sn[t * hh + i] = sinf(a); }
     }
     RC(upload(e, &e->rope_cos, c.data(), c.size())); RC(upload(e, &e->rope_sin, sn.data(), sn.size()));
   }
@@ -2570,7 +2603,7 @@ static int llama_prefill(rk_engine* e, const int32_t* tokens, const int32_t* off
   Slot& sl = e->slots[0];
   if ((rc = check_batch(e, &sl, tokens, off, n_seq))) return rc;
   const rk_llama_desc& l = e->ld;
-  const int T = sl.T, dm = l.hidden, Q = l.n_heads * 128, KV = l.n_kv_heads * 128, F = l.intermediate, ldq = Q + 2 * KV;
+  const int hd = l.head_dim, T = sl.T, dm = l.hidden, Q = l.n_heads * hd, KV = l.n_kv_heads * hd, F = l.intermediate, ldq = Q + 2 * KV;
   hipStream_t st = sl.se;
   HIPCHK(e, hipStreamSynchronize(st));
   std::vector<int> pos(T), last(n_seq);
@@ -2592,7 +2625,13 @@ static int llama_prefill(rk_engine* e, const int32_t* tokens, const int32_t* off
     RC(gemm(e, st, ns.consumer(e, st, nullptr, Gemm(PC_ENC_GEMM_QKV, EPI_STORE_F16, ns.x(), dm, w.qkv_f, dm, sl.qkv, ldq, T, ldq, dm), false)));
     {
       Bracket br(e, st, PC_OTHER, 0, (double)T * (Q + KV) * 4.0);
-      if (w.qkv_bias)
+      if (hd == 64 && w.qkv_bias)
+        hipLaunchKernelGGL(rope64_kernel<true>, dim3(T), dim3(256), 0, st, sl.qkv, e->d_pos, e->rope_cos, e->rope_sin, ldq, l.n_heads + l.n_kv_heads,
+                           w.qkv_bias, l.n_kv_heads);
+      else if (hd == 64)
+        hipLaunchKernelGGL(rope64_kernel<false>, dim3(T), dim3(256), 0, st, sl.qkv, e->d_pos, e->rope_cos, e->rope_sin, ldq, l.n_heads + l.n_kv_heads,
+                           (const float*)nullptr, 0);
+      else if (w.qkv_bias)
         hipLaunchKernelGGL(rope128_kernel<true>, dim3(T), dim3(256), 0, st, sl.qkv, e->d_pos, e->rope_cos, e->rope_sin, ldq, l.n_heads + l.n_kv_heads,
                            w.qkv_bias, l.n_kv_heads);
       else
@@ -2600,10 +2639,16 @@ static int llama_prefill(rk_engine* e, const int32_t* tokens, const int32_t* off
                            (const float*)nullptr, 0);
     }
     if (keep) {
-      const size_t half_layer = (size_t)(keep->slots ? keep->rows : n_seq) * l.n_kv_heads * keep->P * 128;
+      const size_t half_layer = (size_t)(keep->slots ? keep->rows : n_seq) * KV * keep->P;
       half_t* kc = keep->kv + (size_t)i * 2 * half_layer;
       Bracket br(e, st, PC_OTHER, 0, (double)T * KV * 8.0);
-      if (keep->slots)
+      if (hd == 64 && keep->slots)
+        hipLaunchKernelGGL(kv_cache_fill64_slots_kernel, dim3(sl.maxL, n_seq), dim3(256), 0, st, sl.qkv, sl.d_seq_off, keep->slots, keep->rows,
+                           kc, kc + half_layer, ldq, l.n_heads, l.n_kv_heads, keep->P);
+      else if (hd == 64)
+        hipLaunchKernelGGL(kv_cache_fill64_kernel, dim3(sl.maxL, n_seq), dim3(256), 0, st, sl.qkv, sl.d_seq_off, kc, kc + half_layer, ldq,
+                           l.n_heads, l.n_kv_heads, keep->P);
+      else if (keep->slots)
         hipLaunchKernelGGL(kv_cache_fill128_slots_kernel, dim3(sl.maxL, n_seq), dim3(256), 0, st, sl.qkv, sl.d_seq_off, keep->slots, keep->rows,
                            kc, kc + half_layer, ldq, l.n_heads, l.n_kv_heads, keep->P);
       else
@@ -2672,9 +2717,9 @@ int rk_llama_greedy1(rk_engine* e, const int32_t* tokens, const int32_t* seq_off
 // the call's int block (`ints` of them); once: the step's activation rows.  A decoding session (below) holds the same three.
 static int ensure_llama_gen(rk_engine* e, int n_seq, int P, size_t ints) {
   const rk_llama_desc& l = e->ld;
-  const size_t S = (size_t)l.max_seqs, dm = l.hidden, Q = (size_t)l.n_heads * 128, KV = (size_t)l.n_kv_heads * 128, F = l.intermediate;
+  const size_t S = (size_t)l.max_seqs, dm = l.hidden, Q = (size_t)l.n_heads * l.head_dim, KV = (size_t)l.n_kv_heads * l.head_dim, F = l.intermediate;
   const size_t kv = (size_t)l.n_layers * 2 * n_seq * KV * P;
-  const size_t part = (size_t)n_seq * l.n_heads * ((P + LDC_CHUNK - 1) / LDC_CHUNK) * LDC_PSTR;
+  const size_t part = (size_t)n_seq * l.n_heads * ((P + LDC_CHUNK - 1) / LDC_CHUNK) * (l.head_dim == 64 ? LDC64_PSTR : LDC_PSTR);
   int rc = RK_OK;
   RC(e->lkv.reserve(e, kv, &e->lkv_gen)); RC(e->lpart.reserve(e, part, &e->lkv_gen)); RC(e->lints.reserve(e, ints, &e->lkv_gen));
   if (!e->lg.stream.hidden) {
@@ -2692,10 +2737,10 @@ static int ensure_llama_gen(rk_engine* e, int n_seq, int P, size_t ints) {
 // tokens and position.
 static int llama_step_rows(rk_engine* e, hipStream_t st, int rows, int P, const int* d_next, const int* d_pos) {
   const rk_llama_desc& l = e->ld;
-  const int dm = l.hidden, Q = l.n_heads * 128, KV = l.n_kv_heads * 128, F = l.intermediate, ldq = Q + 2 * KV;
+  const int dm = l.hidden, Q = l.n_heads * l.head_dim, KV = l.n_kv_heads * l.head_dim, F = l.intermediate, ldq = Q + 2 * KV;
   const LlamaDecAttnPlan ap = plan_llama_dec_attn(e, rows, P, l.n_heads, l.n_kv_heads);
   const size_t half_layer = (size_t)rows * KV * P;
-  const float scale_log2e = (1.0f / std::sqrt(128.0f)) * 1.4426950408889634f;
+  const float scale_log2e = (1.0f / std::sqrt((float)l.head_dim)) * 1.4426950408889634f;
   const auto& lg = e->lg;
   int rc = RK_OK;
   NormStream ns = lg.stream;
@@ -3367,7 +3412,7 @@ int rk_debug_attn(rk_engine* e, rk_debug_attn_call* q) {
   if (e->family != (kind >= 4 ? 1 : 0)) return fail(e, RK_ERR_STATE, "debug attn: kind %d needs a %s engine", kind, kind >= 4 ? "Llama" : "T5");
   if (B <= 0 || B > (1 << 16) || H <= 0 || H > 1024) return fail(e, RK_ERR_INVALID, "debug attn: n_seq and H");
   const bool planning = q->plan_only != 0;
-  const int hd = kind >= 4 ? 128 : head_width(e), band = q->band_rows;
+  const int hd = head_width(e), band = q->band_rows;   // (kinds 4 and 5: the Llama engine's head_dim, 64 or 128)
   if (kind == 2 && hd != 64) return refuse_wide(e, "debug attn", "kind 2 (the decoder kernels) has no 128-wide form");
   if (!planning && (!q->q || !q->out || !q->out_all || band < 1)) return fail(e, RK_ERR_INVALID, "debug attn: q, out, out_all and band_rows >= 1");
   // ---- the offsets: lengths, the longest and the shortest ----
@@ -3456,14 +3501,14 @@ int rk_debug_attn(rk_engine* e, rk_debug_attn_call* q) {
   } else if (kind == 4) {
     const int n_kv = q->n_kv;
     if (n_kv <= 0 || H % n_kv) return fail(e, RK_ERR_INVALID, "debug attn: n_kv must divide H");
-    ldq_min = (long)(H + 2 * n_kv) * 128; ldctx_min = (long)H * 128; q_rows_need = out_rows_need = T;
+    ldq_min = (long)(H + 2 * n_kv) * hd; ldctx_min = (long)H * hd; q_rows_need = out_rows_need = T;
     cp = plan_llama_attn(e, B, maxL, H, n_kv);
-    plan_out((int)cp.dma, cp.nw, cp.grid, dim3(0, 0, 0), cp.lds);
+    plan_out(cp.hd64 ? 2 : (int)cp.dma, cp.nw, cp.grid, dim3(0, 0, 0), cp.lds);
   } else {
     const int n_kv = q->n_kv, P = q->P;
     if (n_kv <= 0 || H % n_kv || P <= 0 || P > (1 << 20)) return fail(e, RK_ERR_INVALID, "debug attn: n_kv must divide H, P > 0");
-    if (q->ldctx != H * 128) return fail(e, RK_ERR_INVALID, "debug attn: the step's ctx is dense: ldctx = 128 H");
-    ldq_min = (long)(H + 2 * n_kv) * 128; ldctx_min = (long)H * 128; q_rows_need = out_rows_need = B;
+    if (q->ldctx != H * hd) return fail(e, RK_ERR_INVALID, "debug attn: the step's ctx is dense: ldctx = %d H", hd);
+    ldq_min = (long)(H + 2 * n_kv) * hd; ldctx_min = (long)H * hd; q_rows_need = out_rows_need = B;
     if (!planning) {
       if (!q->pos || !q->cos_t || !q->sin_t || !q->cache || !q->cache_all) return fail(e, RK_ERR_INVALID, "debug attn: the step needs pos, cos_t, sin_t, cache and cache_all");
       for (int b = 0; b < B; ++b)
@@ -3539,18 +3584,18 @@ int rk_debug_attn(rk_engine* e, rk_debug_attn_call* q) {
     DBG_HIP(hipDeviceSynchronize());
     launch_llama_attn(e, st, CausalAttnCall{qi, oi, dOff, q->ldq, q->ldctx, H, q->n_kv, B, maxL, T}, cp);
   } else {
-    const size_t half_layer = (size_t)B * q->n_kv * q->P * 128, c_band = (size_t)band * 128;
+    const size_t half_layer = (size_t)B * q->n_kv * q->P * hd, c_band = (size_t)band * hd;
     c_all = 2 * half_layer + 2 * c_band;
     dC = (half_t*)alloc(c_all * 2, RK_DEBUG_SENTINEL);
     int* dPos = (int*)up(q->pos, (size_t)B * 4);
-    float* dCos = (float*)up(q->cos_t, (size_t)q->max_pos * 64 * 4);
-    float* dSin = (float*)up(q->sin_t, (size_t)q->max_pos * 64 * 4);
-    float* dBias = q->qkv_bias ? (float*)up(q->qkv_bias, (size_t)(H + 2 * q->n_kv) * 128 * 4) : nullptr;
-    float* dPart = (float*)alloc((size_t)B * H * lp.nch * LDC_PSTR * 4, RK_DEBUG_SENTINEL);
+    float* dCos = (float*)up(q->cos_t, (size_t)q->max_pos * (hd / 2) * 4);
+    float* dSin = (float*)up(q->sin_t, (size_t)q->max_pos * (hd / 2) * 4);
+    float* dBias = q->qkv_bias ? (float*)up(q->qkv_bias, (size_t)(H + 2 * q->n_kv) * hd * 4) : nullptr;
+    float* dPart = (float*)alloc((size_t)B * H * lp.nch * (hd == 64 ? LDC64_PSTR : LDC_PSTR) * 4, RK_DEBUG_SENTINEL);
     if (!dC || !dPos || !dCos || !dSin || (q->qkv_bias && !dBias) || !dPart) return done(fail(e, RK_ERR_HIP, "debug attn: device allocation or upload failed"));
     DBG_HIP(hipMemcpy(dC + c_band, q->cache, 2 * half_layer * 2, hipMemcpyHostToDevice));
     DBG_HIP(hipDeviceSynchronize());
-    const float scale_log2e = (1.0f / std::sqrt(128.0f)) * 1.4426950408889634f;
+    const float scale_log2e = (1.0f / std::sqrt((float)hd)) * 1.4426950408889634f;
     half_t* kc = dC + c_band;
     launch_llama_dec_attn(e, st, lp, AttnDecCached128Args{qi, kc, kc + half_layer, dPos, dCos, dSin, dPart, oi, q->ldq, H, q->n_kv, q->P, lp.nch, scale_log2e, dBias}, B);
   }

@@ -538,7 +538,8 @@ class RkEngine:
         """One attention call through rk_debug_attn (include/rk_engine.h).  q / kv: 2-D fp16 [band_rows + rows + band_rows, ld], the
         WHOLE allocation with the caller's bands; out: 2-D fp16 [rows, ldctx], the pre-filled interior; cache (kind 5): flat fp16, K then
         V.  Returns the plan fields and, unless plan_only, "out" [band_rows + rows + band_rows, ldctx] and "cache" (flat, with bands
-        of band_rows * 128 elements): the whole device allocations after the call."""
+        of band_rows * hd elements, hd = a Llama engine's head width): the whole device allocations after the call."""
+        hd = int(getattr(self.desc, "head_dim", 128))   # the Llama kinds' head width (64 or 128); the T5 kinds have no such operand
         c = RkDebugAttnCall()
         c.kind, c.n_seq, c.H, c.n_kv, c.Ld, c.cross, c.M, c.row0, c.d, c.P = kind, n_seq, H, n_kv, Ld, int(cross), M, row0, d, P
         c.ldq, c.ldkv, c.ldctx, c.k_col, c.v_col, c.band_rows, c.plan_only = ldq, ldkv, ldctx, k_col, v_col, band_rows, int(plan_only)
@@ -573,10 +574,10 @@ class RkEngine:
             assert put("bias_lut", bias_lut, np.float32).shape == (H, 257)
         if cos is not None:
             cos, sin = put("cos_t", cos, np.float32), put("sin_t", sin, np.float32)
-            assert cos.ndim == 2 and cos.shape[1] == 64 and sin.shape == cos.shape
+            assert cos.ndim == 2 and cos.shape[1] == hd // 2 and sin.shape == cos.shape
             c.max_pos = cos.shape[0]
         if qkv_bias is not None:
-            assert put("qkv_bias", qkv_bias, np.float32).size == (H + 2 * n_kv) * 128
+            assert put("qkv_bias", qkv_bias, np.float32).size == (H + 2 * n_kv) * hd
         out_all = cache_all = None
         if out is not None:
             out = put("out", out, np.float16)
@@ -585,8 +586,8 @@ class RkEngine:
             out_all = put("out_all", np.zeros((out.shape[0] + 2 * band_rows, ldctx)), np.float16)
         if cache is not None:
             cache = put("cache", cache, np.float16).reshape(-1)
-            assert cache.size == 2 * n_seq * n_kv * P * 128
-            cache_all = put("cache_all", np.zeros(cache.size + 2 * band_rows * 128), np.float16)
+            assert cache.size == 2 * n_seq * n_kv * P * hd
+            cache_all = put("cache_all", np.zeros(cache.size + 2 * band_rows * hd), np.float16)
         self._chk(self.lib.rk_debug_attn(self.h, C.byref(c)))
         del keep
         res = {}

@@ -556,9 +556,9 @@ class LlamaRuntime:
         self.dims = _synth.LlamaDims.from_hf_config(cfg)
         self.max_tokens, self.max_seqs = max_tokens, max_seqs
         self.generation = read_generation_settings(model_name_or_path, cfg)
-        if self.dims.head_dim != 128 or self.dims.hidden > 4096:
-            raise NotImplementedError(f"head_dim {self.dims.head_dim} / hidden {self.dims.hidden}: the MI355X engine serves head_dim 128 and "
-                                      "hidden <= 4096 (Llama-2/3 up to 8B, Qwen2.5-1.5B / 3B / 7B)")
+        if self.dims.head_dim not in (64, 128) or self.dims.hidden > 4096:
+            raise NotImplementedError(f"head_dim {self.dims.head_dim} / hidden {self.dims.hidden}: the MI355X engine serves head_dim 64 or 128 and "
+                                      "hidden <= 4096 (Llama-2/3 up to 8B, Llama-3.2-1B, TinyLlama, SmolLM2, Qwen2.5-0.5B to 7B)")
         self.engine = RkLlamaEngine(self.dims, parse_device(device), max_tokens, max_seqs)
         tensors = iter_checkpoint_tensors(model_name_or_path)
         self.engine.load_state(merge_lora(tensors, adapter_dir) if adapter_dir else tensors)

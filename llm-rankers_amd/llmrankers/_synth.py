@@ -201,6 +201,24 @@ TOY_QWEN2 = LlamaDims(vocab=512, hidden=256, n_heads=7, n_kv_heads=1, head_dim=1
                       rope_theta=1000000.0, eps=1e-6, tied_head=True, qkv_bias=True)
 
 
+# ---- 64-wide heads (llama_kernels_hd64.h): the small decoder-only chat models ----
+# Llama-3.2-1B-Instruct: tied head, rope type llama3 with factor 32; TinyLlama-1.1B-Chat; Qwen2.5-0.5B-Instruct (tied head, biases).
+# Timing tools and the real-width test only.
+LLAMA_32_1B = LlamaDims(vocab=128256, hidden=2048, n_heads=32, n_kv_heads=8, head_dim=64, intermediate=8192, n_layers=16,
+                        tied_head=True, bos_token_id=128000, eos_token_id=128001, rope_scaling=(32.0, 1.0, 4.0, 8192))
+TINYLLAMA_1B = LlamaDims(vocab=32000, hidden=2048, n_heads=32, n_kv_heads=4, head_dim=64, intermediate=5632, n_layers=22,
+                         rope_theta=10000.0)
+QWEN25_05B = LlamaDims(vocab=151936, hidden=896, n_heads=14, n_kv_heads=2, head_dim=64, intermediate=4864, n_layers=24,
+                       rope_theta=1000000.0, eps=1e-6, tied_head=True, bos_token_id=151643, eos_token_id=151645, qkv_bias=True)
+# TOY_LLAMA with 8 query heads on 2 kv heads of 64 (G = 4; the q width 512 differs from hidden 256)
+TOY_LLAMA_HD64 = LlamaDims(vocab=256, hidden=256, n_heads=8, n_kv_heads=2, head_dim=64, intermediate=512, n_layers=2)
+# TOY_QWEN2 at width 64: 7 query heads on ONE kv head (G = 7: the decode attention takes one head per workgroup), tied head, biases
+TOY_QWEN2_HD64 = LlamaDims(vocab=512, hidden=256, n_heads=7, n_kv_heads=1, head_dim=64, intermediate=512, n_layers=2,
+                           rope_theta=1000000.0, eps=1e-6, tied_head=True, qkv_bias=True)
+# multi-head attention (G = 1) with an odd head count: q width 192
+TOY_LLAMA_MHA_HD64 = LlamaDims(vocab=256, hidden=256, n_heads=3, n_kv_heads=3, head_dim=64, intermediate=512, n_layers=2)
+
+
 def llama_tensor_specs(d: "LlamaDims") -> Iterator[Tuple[str, Tuple[int, ...], float, bool]]:
     """(hf_name, shape, std, is_norm_weight) of a LlamaForCausalLM checkpoint, in a fixed order."""
     yield "model.embed_tokens.weight", (d.vocab, d.hidden), 1.0, False
@@ -230,6 +248,8 @@ NAMED_DIMS = {
     "t5-3b": T5_3B, "toy-monot5-d128": TOY_MONOT5_D128,
     "llama-3-8b": LLAMA_3_8B, "toy-llama": TOY_LLAMA, "toy-llama3rope": TOY_LLAMA3ROPE,
     "qwen2.5-7b": QWEN25_7B, "toy-qwen2": TOY_QWEN2,
+    "llama-3.2-1b": LLAMA_32_1B, "tinyllama-1.1b": TINYLLAMA_1B, "qwen2.5-0.5b": QWEN25_05B,
+    "toy-llama-hd64": TOY_LLAMA_HD64, "toy-qwen2-hd64": TOY_QWEN2_HD64, "toy-llama-mha-hd64": TOY_LLAMA_MHA_HD64,
 }
 
 _M64 = np.uint64(0xFFFFFFFFFFFFFFFF)
