@@ -44,6 +44,7 @@ typedef enum rk_status {
 typedef enum rk_dtype { RK_F32 = 0, RK_F16 = 1, RK_BF16 = 2 } rk_dtype;
 
 /* Mirrors the fields of HF's T5Config the path depends on (hf: models/t5/configuration_t5.py).
+ * d_model is at most 4096 (RK_ERR_INVALID beyond: the RMSNorm kernel holds one row of at most 4096 columns in registers).
  * d_kv is 64 or 128 (RK_ERR_INVALID otherwise).  d_kv = 128 (t5-3b, t5-11b: monoT5-3B, duoT5-3B) is served at ONE decoder position:
  * rk_t5_score with dec_len == 1 (blocking, staged, slots), rk_t5_compare and the rk_comm_* calls behind them.  On such an engine
  * rk_t5_score with dec_len > 1, rk_t5_qlm, rk_t5_qlm_many, rk_t5_greedy, rk_t5_greedy2 and rk_t5_generate return RK_ERR_STATE with a
@@ -345,6 +346,12 @@ int rk_debug_gemm_ex(rk_engine* e, rk_debug_gemm_call* call);
  *   5 Llama cached step  plan_llama_dec_attn: q = the step's rows [n_seq, ldq], NOT rotated; cache = K [n_seq][n_kv][P][128] then V, pos[n_seq]
  *                        (< P, < max_pos), cos_t / sin_t [max_pos][64] ([max_pos][32] at hd = 64), qkv_bias [(H + 2 n_kv) 128] fp32 or null; out = ctx [n_seq, H 128]
  *                        (ldctx = H 128); cache_all = the cache afterwards (the row's rotated key and its value appended at pos).  Option llama_dec_r.
+ *   6 T5 cached step     the self-attention of rk_t5_generate's step, through the launcher run_decoder's cached branch calls: q = the step's
+ *                        fused rows [n_seq, ldq] (q | k | v at columns 0 | 64 H | 128 H), cache [n_seq][P][2 x 64 H] (k | v per position),
+ *                        pos: ONE value (the kernel reads one device word; outside [0, P): RK_ERR_INVALID, nothing launched), bias_lut;
+ *                        out = ctx [n_seq, ldctx]; cache_all = the cache afterwards (row pos holds the step's k and v), bands of
+ *                        band_rows x 64 elements.  Option dec_cached_attn: attn_dec_cached_kernel (1, out_kind 1) or kv_append_kernel +
+ *                        attn_dec_kernel's tree form (0, out_kind 0, out_grid2 the tree form's).  P <= 8192.  RK_ERR_STATE on a d_kv = 128 engine.
  * Inputs q / kv: host fp16, the WHOLE allocation: band_rows rows in front of and behind the q_rows / kv_rows interior rows, all of ldq /
  * ldkv elements; the caller fills the bands (finite values: a kernel may load a masked row and give it weight 0); the call's pointer is
  * the first interior row.  out: the interior, out_rows x ldctx elements, copied to the device as it is (the caller pre-fills what no
@@ -421,6 +428,62 @@ typedef struct rk_debug_xattn_chain_call {
   float out_eps, out_xs;
 } rk_debug_xattn_chain_call;
 int rk_debug_xattn_chain(rk_engine* e, rk_debug_xattn_chain_call* call);
+/* debug: run ONE launch of a row kernel or device state machine (csrc/misc_kernels.h, the rope and cache-fill kernels of
+ * csrc/llama_kernels*.h) on host data through the launcher the production path calls (csrc/rk_engine.hip: launch_rmsnorm, launch_embed,
+ * launch_rope, launch_kv_fill, ...; no kernel, grid rule or dispatch of its own), every output inside guard bands.  Works on an engine
+ * of either family: every width comes from the call, none from the engine.
+ *   in[i]   an input: data = the WHOLE allocation of `bytes` bytes, the kernel's pointer = data + off (off a multiple of 16).  What lies
+ *           in front of off and behind the interior is the caller's band (finite values): a table gets a band row in front and behind.
+ *           data = null: the kernel gets a null pointer (optional operands only).
+ *   out[i]  an output: interior = `bytes` bytes copied to the device as they are (the caller pre-fills what the kernel must not
+ *           touch; for an in-place operand or a state word this is the input); all = n_steps x (band + bytes + band) bytes, the WHOLE
+ *           device allocation after each launch, the two bands (band bytes each, a multiple of 16, >= 64) filled with the byte
+ *           RK_DEBUG_SENTINEL before the first launch.  n_steps is 1 except for op 10.
+ * op and operands (fp16 = uint16 bit patterns, f32 = float, i32 = int32):
+ *   1 embed          rows, d (multiple of 8), vocab, kind = 1 folded-norm form / 0 plain, eps, xs.  in0 ids i32[rows] (any value: the kernel
+ *                    clamps), in1 table fp16 [vocab][d].  out0 out f32 [rows][d], out1 xraw fp16 [rows][d], out2 rowscale f32 [rows]
+ *                    (kind 0: the kernel gets null for both and they keep their pre-fill).
+ *   2 rowscale       rows, nb, d, eps, xs.  in0 ssq f32 [rows][nb].  out0 f32 [rows].
+ *   3 rmsnorm        rows, d (multiple of 4, <= 4096), src_rows, eps, out_scale.  in0 x f32 [src_rows][d], in1 w f32 [d], in2 row_map
+ *                    i32[rows] (each in [0, src_rows)) or null.  out0 fp16 [rows][d].  out_tparam = NV.
+ *   4 head_rows      rows (= n_seq), n_out, d (multiple of 8), vocab.  in0 x fp16 [rows][d], in1 head fp16 [vocab][d], in2 out_ids
+ *                    i32[n_out] (each in [0, vocab)).  out0 f32 [rows][n_out].
+ *   5 pair_verdict   rows (= n_seq >= 2), d, vocab, false_id, true_id.  in0 x, in1 head as for 4.  out0 f32 [3 rows + rows / 2].
+ *   6 argmax_blocks  rows, nb (= n_blocks).  in0 bval f32 [rows][nb], in1 bidx i32 [rows][nb].  out0 i32 [rows].
+ *   7 qlm_lse        rows (= n_seq), nb (= nblk), n_pos.  in0 stats f32 [R][nb][2], in1 xlab f32 [R], in2 row_off i32[rows + 1] (growing
+ *                    from >= 0; R = row_off[rows]) or null (R = rows n_pos), in3 out_idx i32[rows] (each in [0, rows)) or null.  out0 f32 [rows].
+ *   8 rope           rows (= T), H, n_kv, hd (64 or 128), ld (multiple of 8, >= (H + 2 n_kv) hd), max_pos.  in0 pos i32[T] (each in
+ *                    [0, max_pos)), in1 cos_t f32 [max_pos][hd / 2], in2 sin_t, in3 bias f32 [(H + 2 n_kv) hd] or null.  out0 qkv fp16
+ *                    [T][ld], rotated in place.  out_tparam = hd, out_variant = 1 with bias.
+ *   9 kv_fill        rows (= n_seq), H, n_kv, hd, ld, P, n_slots.  in0 qkv fp16 [T][ld], in1 seq_off i32[rows + 1] (growing from 0, T =
+ *                    seq_off[rows], the longest sequence >= 1), in2 slots i32[rows] (any value: the kernel skips what is outside [0, n_slots))
+ *                    or null (then the cache has `rows` rows).  out0 cache fp16: K [cache rows][n_kv][P][hd], then V.  out_tparam = hd,
+ *                    out_variant = 1 with a slot map.
+ *  10 advance        kind 0 greedy_advance_kernel, 1 llama_advance_kernel, 2 llama_session_advance_kernel; rows (= n_seq / n_slots),
+ *                    n_steps >= 1 launches, one per scripted arg-max row: in0 argmax i32 [n_steps][R], R = rows (kind 2: max(rows, max_admit)).
+ *                    The interiors are the initial state; all[s] is the complete state after launch s.
+ *                    kind 0: dec_len, max_new; in1 prefix i32[dec_len]; out0 st i32[4] (st[0] >= 0), out1 done i32[rows], out2 out
+ *                            i32 [rows][max_new], out3 next_ids i32[rows].
+ *                    kind 1: in1 len i32[rows]; out0 st i32[16] (st[0] >= 0, n_eos = st[3] in 0..8, max_new = st[4] > 0), out1 done, out2 pos,
+ *                            out3 out i32 [rows][st[4]], out4 next_ids.
+ *                    kind 2: in1 admit script i32 [n_steps][1 + 3 max_admit] or null: per step n_admit (-1: a plain step, the kernel gets
+ *                            null; else 0..max_admit) and then slot[n_admit] | len[n_admit] | max_new[n_admit] packed; out0 st i32[16]
+ *                            (n_eos = st[2] in 0..8, cap = st[4] > 0), out1 len, out2 col (each >= 0), out3 max_new, out4 done, out5 pos,
+ *                            out6 out i32 [rows][cap], out7 next_ids (all i32[rows]).
+ * plan_only != 0: nothing is allocated or launched, only out_grid, out_tparam and out_variant are filled (from the launchers' own grid
+ * functions).  Every extent is checked against the sizes given before anything is launched: RK_ERR_INVALID, nothing launched. */
+typedef struct rk_debug_rows_in { const void* data; int64_t bytes, off; } rk_debug_rows_in;
+typedef struct rk_debug_rows_out { const void* interior; int64_t bytes, band; void* all; } rk_debug_rows_out;
+typedef struct rk_debug_rows_call {
+  int op, kind;
+  int rows, d, vocab, src_rows, n_out, nb, n_pos, H, n_kv, hd, ld, P, n_slots, max_pos, false_id, true_id, dec_len, max_new, n_steps, max_admit;
+  float eps, xs, out_scale;
+  rk_debug_rows_in in[4];
+  rk_debug_rows_out out[8];
+  int plan_only;
+  int out_grid[3], out_tparam, out_variant;
+} rk_debug_rows_call;
+int rk_debug_rows(rk_engine* e, rk_debug_rows_call* call);
 /* measurement: average ms per launch of the engine's GEMM kernel at one shape (epi = 0 store f16, 1 residual f32,
  * 2 GEGLU, 3 ReLU, 4 store f32), random operands, `iters` back-to-back launches timed with HIP events */
 int rk_debug_gemm_bench(rk_engine* e, int M, int N, int K, int epi, int iters, float* out_ms);

@@ -674,28 +674,88 @@ int gemm(rk_engine* e, hipStream_t st, const Gemm& c, int* nb = nullptr) {
   return RK_OK;
 }
 
+// ---- launchers of the row kernels and the device state machines (misc_kernels.h, llama_kernels*.h) ----
+// Each takes what its kernel takes and holds the grid rule and the choice of template parameter / width: the production call sites
+// and rk_debug_rows both launch through these, so the debug entry has no launch code of its own.
+int rmsnorm_nv(int d) { return d <= 1024 ? 4 : (d <= 2048 ? 8 : 16); }   // rmsnorm_kernel<NV> holds 256 NV columns: d <= 4096
+dim3 grid_waves(int items) { return dim3((items + 3) / 4); }             // one wave per row or dot product, four to a workgroup
+dim3 grid_rowscale(int rows) { return dim3((rows + 255) / 256); }        // one thread per row
+dim3 grid_pairs(int n_seq) { return dim3(n_seq / 2); }                   // one workgroup per pair; an unpaired last sequence gets none
+dim3 grid_kv_fill(int maxL, int n_seq) { return dim3(maxL, n_seq); }     // one workgroup per (position, sequence)
+void launch_rmsnorm(hipStream_t st, const float* x, const float* w, half_t* out, const int* row_map, int rows, int d, float eps, float scale) {
+  const dim3 g = grid_waves(rows), b(256);
+  if (d <= 1024) hipLaunchKernelGGL(rmsnorm_kernel<4>, g, b, 0, st, x, w, out, row_map, rows, d, eps, scale);
+  else if (d <= 2048) hipLaunchKernelGGL(rmsnorm_kernel<8>, g, b, 0, st, x, w, out, row_map, rows, d, eps, scale);
+  else hipLaunchKernelGGL(rmsnorm_kernel<16>, g, b, 0, st, x, w, out, row_map, rows, d, eps, scale);
+}
+void launch_embed(hipStream_t st, const int* ids, const half_t* table, float* out, int rows, int d, int vocab, half_t* xraw, float* rowscale,
+                  float xs, float eps) {
+  hipLaunchKernelGGL(embed_gather_kernel, grid_waves(rows), dim3(256), 0, st, ids, table, out, rows, d, vocab, xraw, rowscale, xs, eps);
+}
+void launch_rowscale(hipStream_t st, const float* ssq, float* out, int rows, int nb, int d, float eps, float xs) {
+  hipLaunchKernelGGL(rowscale_kernel, grid_rowscale(rows), dim3(256), 0, st, ssq, out, rows, nb, d, eps, xs);
+}
+void launch_head_rows(hipStream_t st, const half_t* x, const half_t* head, const int* out_ids, float* out, int n_seq, int n_out, int d) {
+  hipLaunchKernelGGL(head_rows_kernel, grid_waves(n_seq * n_out), dim3(256), 0, st, x, head, out_ids, out, n_seq, n_out, d);
+}
+void launch_pair_verdict(hipStream_t st, const half_t* x, const half_t* head, int false_id, int true_id, float* out, int n_seq, int d) {
+  hipLaunchKernelGGL(pair_verdict_kernel, grid_pairs(n_seq), dim3(256), 0, st, x, head, false_id, true_id, out, n_seq, d);
+}
+void launch_argmax_blocks(hipStream_t st, const float* bval, const int* bidx, int n_blocks, int* out, int rows) {
+  hipLaunchKernelGGL(argmax_blocks_kernel, dim3(rows), dim3(256), 0, st, bval, bidx, n_blocks, out);
+}
+void launch_qlm_lse(hipStream_t st, const float2* stats, int nblk, const float* xlab, int n_pos, const int* row_off, const int* out_idx,
+                    float* out, int n_seq) {
+  hipLaunchKernelGGL(qlm_lse_kernel, dim3(n_seq), dim3(256), 0, st, stats, nblk, xlab, n_pos, row_off, out_idx, out);
+}
+// the prefill's rotation, in place on T rows of the fused QKV buffer: head width 64 or 128, with the Qwen2 bias (then the n_v
+// value heads get theirs) or without (value heads untouched)
+void launch_rope(hipStream_t st, int hd, half_t* qkv, const int* pos, const float* cos_t, const float* sin_t, int ld, int n_rot,
+                 const float* bias, int n_v, int T) {
+  if (hd == 64 && bias) hipLaunchKernelGGL(rope64_kernel<true>, dim3(T), dim3(256), 0, st, qkv, pos, cos_t, sin_t, ld, n_rot, bias, n_v);
+  else if (hd == 64) hipLaunchKernelGGL(rope64_kernel<false>, dim3(T), dim3(256), 0, st, qkv, pos, cos_t, sin_t, ld, n_rot, (const float*)nullptr, 0);
+  else if (bias) hipLaunchKernelGGL(rope128_kernel<true>, dim3(T), dim3(256), 0, st, qkv, pos, cos_t, sin_t, ld, n_rot, bias, n_v);
+  else hipLaunchKernelGGL(rope128_kernel<false>, dim3(T), dim3(256), 0, st, qkv, pos, cos_t, sin_t, ld, n_rot, (const float*)nullptr, 0);
+}
+// the prompt's rotated keys and its values into the cache: sequence b to cache row b, or to row slots[b] of n_slots
+void launch_kv_fill(hipStream_t st, int hd, const half_t* qkv, const int* seq_off, const int* slots, int n_slots, half_t* kc, half_t* vc,
+                    int ld, int n_heads, int n_kv, int P, int maxL, int n_seq) {
+  const dim3 g = grid_kv_fill(maxL, n_seq), b(256);
+  if (hd == 64 && slots) hipLaunchKernelGGL(kv_cache_fill64_slots_kernel, g, b, 0, st, qkv, seq_off, slots, n_slots, kc, vc, ld, n_heads, n_kv, P);
+  else if (hd == 64) hipLaunchKernelGGL(kv_cache_fill64_kernel, g, b, 0, st, qkv, seq_off, kc, vc, ld, n_heads, n_kv, P);
+  else if (slots) hipLaunchKernelGGL(kv_cache_fill128_slots_kernel, g, b, 0, st, qkv, seq_off, slots, n_slots, kc, vc, ld, n_heads, n_kv, P);
+  else hipLaunchKernelGGL(kv_cache_fill128_kernel, g, b, 0, st, qkv, seq_off, kc, vc, ld, n_heads, n_kv, P);
+}
+void launch_greedy_advance(hipStream_t st, const int* argmax, int* state, const int* prefix, int* done, int* out, int* next_ids, int n_seq,
+                           int dec_len, int max_new) {
+  hipLaunchKernelGGL(greedy_advance_kernel, dim3(1), dim3(256), 0, st, argmax, state, prefix, done, out, next_ids, n_seq, dec_len, max_new);
+}
+void launch_llama_advance(hipStream_t st, const int* argmax, int* state, const int* len, int* done, int* pos, int* out, int* next_ids, int n_seq) {
+  hipLaunchKernelGGL(llama_advance_kernel, dim3(1), dim3(256), 0, st, argmax, state, len, done, pos, out, next_ids, n_seq);
+}
+void launch_session_advance(hipStream_t st, const int* argmax, int* state, int* len, int* col, int* max_new, int* done, int* pos, int* out,
+                            int* next_ids, int n_slots, const int* admit, int n_admit) {
+  hipLaunchKernelGGL(llama_session_advance_kernel, dim3(1), dim3(256), 0, st, argmax, state, len, col, max_new, done, pos, out, next_ids, n_slots,
+                     admit, n_admit);
+}
+
 void rmsnorm(rk_engine* e, hipStream_t st, const float* x, const float* w, half_t* out, const int* row_map, int rows, float scale = 1.f) {
   if (rows <= 0) return;
   Bracket br(e, st, PC_NORM, 3.0 * rows * e->d.d_model, (double)rows * e->d.d_model * 6.0);
-  const int dm = e->d.d_model;
-  const dim3 g((rows + 3) / 4), b(256);
-  if (dm <= 1024) hipLaunchKernelGGL(rmsnorm_kernel<4>, g, b, 0, st, x, w, out, row_map, rows, dm, e->d.eps, scale);
-  else if (dm <= 2048) hipLaunchKernelGGL(rmsnorm_kernel<8>, g, b, 0, st, x, w, out, row_map, rows, dm, e->d.eps, scale);
-  else hipLaunchKernelGGL(rmsnorm_kernel<16>, g, b, 0, st, x, w, out, row_map, rows, dm, e->d.eps, scale);
+  launch_rmsnorm(st, x, w, out, row_map, rows, e->d.d_model, e->d.eps, scale);
 }
 
 void embed(rk_engine* e, hipStream_t st, const int* ids, float* out, int rows, half_t* xraw = nullptr, float* rowscale = nullptr) {
   if (rows <= 0) return;
   Bracket br(e, st, PC_EMBED, 0, (double)rows * e->d.d_model * 6.0);
-  hipLaunchKernelGGL(embed_gather_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, ids, e->emb, out, rows,
-                     e->d.d_model, e->d.vocab, xraw, rowscale, RK_XRAW_SCALE, e->d.eps);
+  launch_embed(st, ids, e->emb, out, rows, e->d.d_model, e->d.vocab, xraw, rowscale, RK_XRAW_SCALE, e->d.eps);
 }
 
 // folded RMSNorm: block sums of squares (left by the residual GEMM epilogue) -> row factors
 void rowscale(rk_engine* e, hipStream_t st, const float* ssq, float* out, int rows, int nb) {   // nb: block sums per row (the producer's plan)
   if (rows <= 0) return;
   Bracket br(e, st, PC_NORM, 0, (double)rows * (nb + 1) * 4.0);
-  hipLaunchKernelGGL(rowscale_kernel, dim3((rows + 255) / 256), dim3(256), 0, st, ssq, out, rows, nb, e->d.d_model, e->d.eps, RK_XRAW_SCALE);
+  launch_rowscale(st, ssq, out, rows, nb, e->d.d_model, e->d.eps, RK_XRAW_SCALE);
 }
 
 void NormStream::begin(rk_engine* e, hipStream_t st, const int* ids, int rows_, bool fold_) {
@@ -1246,6 +1306,19 @@ struct DecRows {
 // new row, then attn_dec_cached_kernel over the cache.  tree_keys / tree_pos: option dec_cached_attn = 0 (attn_dec_kernel's
 // tree form over the cache rows b * P + j).
 struct DecCache { half_t* kv; int P; const int* pos; const int* tree_keys; int* tree_pos; };
+// The T5 cached step's self-attention, one new row per sequence: attn_dec_cached_kernel, or (option dec_cached_attn = 0) the cache
+// append and attn_dec_kernel's tree form over the cache rows tree_keys [B][P] names (row b P + j), at the position kv_append_kernel
+// publishes in tree_pos.  run_decoder's cached branch and rk_debug_attn kind 6 both launch through here.
+void launch_dec_cached_step(const rk_engine* e, hipStream_t st, const AttnCachedArgs& ca, int B, int H, const int* tree_keys, int* tree_pos) {
+  if (e->opt.dec_cached_attn) {
+    hipLaunchKernelGGL(attn_dec_cached_kernel, dim3(H, B), dim3(256), attn_dec_lds(ca.P), st, ca);
+  } else {
+    hipLaunchKernelGGL(kv_append_kernel, dim3(B), dim3(256), 0, st, ca, tree_pos);
+    hipLaunchKernelGGL(attn_dec_kernel, dim3(1, H, B), dim3(256), attn_dec_lds(ca.P), st,
+                       AttnDecArgs{ca.qkv, ca.ldqkv, ca.cache, ca.cache + ca.inner, 2 * ca.inner, nullptr, ca.ctx, ca.ldctx, ca.bias_lut, ca.P, 1, ca.P,
+                                   tree_keys, tree_pos});
+  }
+}
 // (Tried and dropped, round 3: the single-position pass of 320 rows as TWO or THREE chains of 32-row-aligned row ranges on
 // helper streams, fork / join by events (parallel branches of the decoder graph) - bit-identical, but 6.4-6.6k passages/s
 // against 7.3k: what the decoder costs the encoder running beside it is every one of its kernels delaying the persistent
@@ -1309,14 +1382,7 @@ int run_decoder(rk_engine* e, Slot& sl, int Ld, const DecRows* rows = nullptr, c
       if (cache) {
         const AttnCachedArgs ca{sl.dqkv, 3 * I, cache->kv + (size_t)l * B * cache->P * 2 * I, cache->P, I, cache->pos, sl.dctx, I, e->lut_dec};
         Bracket br(e, st, PC_DEC_ATTN, 4.0 * B * (double)cache->P * I, (double)B * cache->P * 2 * I * 2.0);
-        if (e->opt.dec_cached_attn) {
-          hipLaunchKernelGGL(attn_dec_cached_kernel, dim3(d.n_heads, B), dim3(256), attn_dec_lds(cache->P), st, ca);
-        } else {
-          hipLaunchKernelGGL(kv_append_kernel, dim3(B), dim3(256), 0, st, ca, cache->tree_pos);
-          hipLaunchKernelGGL(attn_dec_kernel, dim3(1, d.n_heads, B), dim3(256), attn_dec_lds(cache->P), st,
-                             AttnDecArgs{sl.dqkv, 3 * I, ca.cache, ca.cache + I, 2 * I, nullptr, sl.dctx, I, e->lut_dec, cache->P, 1, cache->P,
-                                         cache->tree_keys, cache->tree_pos});
-        }
+        launch_dec_cached_step(e, st, ca, B, d.n_heads, cache->tree_keys, cache->tree_pos);
       } else {
         launch_dec_attn(e, st, self_plan, AttnDecArgs{sl.dqkv, 3 * I, sl.dqkv + I, sl.dqkv + 2 * I, 3 * I, nullptr, sl.dctx, I, e->lut_dec, Ld, 1, Ld,
                                                       tree ? rows->keys : nullptr, tree ? rows->pos : nullptr, 0, ragged ? rows->row_off : nullptr},
@@ -1605,8 +1671,7 @@ int score_slot(rk_engine* e, int slot, const int32_t* dec_prefix, int dec_len, c
     if (!skip_dec && (r = run_decoder(e, sl, dec_len))) return r;
     rmsnorm(e, sd, sl.dec.hidden, e->dec_final_ln, sl.dlast, sl.idx.d[IX_LAST_ROWS], sl.n_seq, head_scale(e));
     Bracket br(e, sd, PC_HEAD, 2.0 * sl.n_seq * n_out * e->d.d_model, 0);
-    hipLaunchKernelGGL(head_rows_kernel, dim3((sl.n_seq * n_out + 3) / 4), dim3(256), 0, sd, sl.dlast, e->lm_head,
-                       sl.idx.d[IX_OUT_IDS], sl.d_scores, sl.n_seq, n_out, e->d.d_model);
+    launch_head_rows(sd, sl.dlast, e->lm_head, sl.idx.d[IX_OUT_IDS], sl.d_scores, sl.n_seq, n_out, e->d.d_model);
     return RK_OK;
   });
   if (rc) return rc;
@@ -1641,8 +1706,7 @@ int compare_slot(rk_engine* e, int slot, int dec_start_id, int false_id, int tru
     if ((r = run_decoder(e, sl, 1))) return r;
     rmsnorm(e, sd, sl.dec.hidden, e->dec_final_ln, sl.dlast, sl.idx.d[IX_LAST_ROWS], sl.n_seq, head_scale(e));
     Bracket br(e, sd, PC_HEAD, 2.0 * sl.n_seq * 2 * e->d.d_model, 0);
-    hipLaunchKernelGGL(pair_verdict_kernel, dim3(sl.n_seq / 2), dim3(256), 0, sd, sl.dlast, e->lm_head, false_id, true_id,
-                       sl.d_scores, sl.n_seq, e->d.d_model);
+    launch_pair_verdict(sd, sl.dlast, e->lm_head, false_id, true_id, sl.d_scores, sl.n_seq, e->d.d_model);
     return RK_OK;
   });
   if (rc) return rc;
@@ -1770,6 +1834,8 @@ int rk_engine_create(const rk_model_desc* desc, int device_ordinal, rk_engine** 
     return fail(nullptr, RK_ERR_INVALID, "d_kv=%d unsupported: the gfx950 attention kernels are built for d_kv=64 and, for one decoder position, d_kv=128", d.d_kv);
   if (d.d_model % 64 || (d.n_heads * d.d_kv) % 64 || d.d_ff % 64 || d.vocab % 4)
     return fail(nullptr, RK_ERR_INVALID, "d_model, n_heads*d_kv, d_ff must be multiples of 64 and vocab of 4");
+  if (d.d_model > 4096)
+    return fail(nullptr, RK_ERR_INVALID, "d_model=%d unsupported: rmsnorm_kernel holds a row of at most 4096 columns in registers (d_model <= 4096)", d.d_model);
   if (d.max_distance > RK_LUT_R || d.n_buckets < 4 || d.n_buckets > 256)
     return fail(nullptr, RK_ERR_INVALID, "relative attention config unsupported (max_distance<=%d)", RK_LUT_R);
   if (d.max_tokens <= 0 || d.max_seqs <= 0 || d.max_dec_len <= 0 || d.n_enc_layers <= 0 || d.n_dec_layers <= 0)
@@ -2160,8 +2226,7 @@ static int run_qlm(rk_engine* e, Slot& sl, const std::vector<QlmPass>& passes, f
     rmsnorm(e, sd, sl.dec.hidden, e->dec_final_ln, sl.dec.xn, nullptr, p.rows, head_scale(e));
     float* xlab = e->logits.p + (size_t)p.rows * nblk * 2;
     RC(gemm(e, sd, Gemm(PC_HEAD, EPI_LSE_F32, sl.dec.xn, dm, e->lm_head, dm, e->logits.p, nblk, p.rows, e->d.vocab, dm).lse(ix[IX_ROW_LABEL] + p.r0, xlab)));
-    hipLaunchKernelGGL(qlm_lse_kernel, dim3(p.n_seq), dim3(256), 0, sd, (const float2*)e->logits.p, nblk, xlab, ragged ? 0 : p.ld, off,
-                       ragged ? ix[IX_OUT_IDX] + p.s0 : nullptr, sl.d_scores);
+    launch_qlm_lse(sd, (const float2*)e->logits.p, nblk, xlab, ragged ? 0 : p.ld, off, ragged ? ix[IX_OUT_IDX] + p.s0 : nullptr, sl.d_scores, p.n_seq);
   }
   return read_scores_blocking(e, sl, sd, (size_t)sl.n_seq, out_scores);
 }
@@ -2257,7 +2322,7 @@ static int ensure_amax(rk_engine* e, size_t rows) {
 static int head_argmax(rk_engine* e, hipStream_t st, const half_t* x, int rows, int d_model, int vocab, int* d_out) {
   const int nblk = (vocab + 31) / 32;
   const int rc = gemm(e, st, Gemm(PC_HEAD, EPI_ARGMAX_F32, x, d_model, e->lm_head, d_model, e->amax_val.p, nblk, rows, vocab, d_model).on(GEMM_STREAM).argmax(e->amax_idx.p));
-  if (rc == RK_OK) hipLaunchKernelGGL(argmax_blocks_kernel, dim3(rows), dim3(256), 0, st, e->amax_val.p, e->amax_idx.p, nblk, d_out);
+  if (rc == RK_OK) launch_argmax_blocks(st, e->amax_val.p, e->amax_idx.p, nblk, d_out, rows);
   return rc;
 }
 // T5: final norm of `rows` decoder rows (row_map, or the first rows) -> arg-max head -> sl.d_argmax
@@ -2376,8 +2441,7 @@ int rk_t5_generate(rk_engine* e, const int32_t* tokens, const int32_t* seq_offse
     int r = run_decoder(e, sl, 1, nullptr, &kc);
     if (r || (r = final_argmax(e, sd, sl, nullptr, n_seq))) return r;
     Bracket br(e, sd, PC_OTHER, 0, 0);
-    hipLaunchKernelGGL(greedy_advance_kernel, dim3(1), dim3(256), 0, sd, sl.d_argmax, g, g + o_pre, g + o_done, g + o_out, sl.idx.d[IX_DEC_IDS],
-                       n_seq, dec_len, max_new);
+    launch_greedy_advance(sd, sl.d_argmax, g, g + o_pre, g + o_done, g + o_out, sl.idx.d[IX_DEC_IDS], n_seq, dec_len, max_new);
     return RK_OK;
   };
   const std::vector<int> key{GK_T5_GENERATE_STEP, 0, n_seq, (sl.maxL + 63) / 64, dec_len, max_new, e->amax_gen, e->kv_gen};
@@ -2625,35 +2689,13 @@ static int llama_prefill(rk_engine* e, const int32_t* tokens, const int32_t* off
     RC(gemm(e, st, ns.consumer(e, st, nullptr, Gemm(PC_ENC_GEMM_QKV, EPI_STORE_F16, ns.x(), dm, w.qkv_f, dm, sl.qkv, ldq, T, ldq, dm), false)));
     {
       Bracket br(e, st, PC_OTHER, 0, (double)T * (Q + KV) * 4.0);
-      if (hd == 64 && w.qkv_bias)
-        hipLaunchKernelGGL(rope64_kernel<true>, dim3(T), dim3(256), 0, st, sl.qkv, e->d_pos, e->rope_cos, e->rope_sin, ldq, l.n_heads + l.n_kv_heads,
-                           w.qkv_bias, l.n_kv_heads);
-      else if (hd == 64)
-        hipLaunchKernelGGL(rope64_kernel<false>, dim3(T), dim3(256), 0, st, sl.qkv, e->d_pos, e->rope_cos, e->rope_sin, ldq, l.n_heads + l.n_kv_heads,
-                           (const float*)nullptr, 0);
-      else if (w.qkv_bias)
-        hipLaunchKernelGGL(rope128_kernel<true>, dim3(T), dim3(256), 0, st, sl.qkv, e->d_pos, e->rope_cos, e->rope_sin, ldq, l.n_heads + l.n_kv_heads,
-                           w.qkv_bias, l.n_kv_heads);
-      else
-        hipLaunchKernelGGL(rope128_kernel<false>, dim3(T), dim3(256), 0, st, sl.qkv, e->d_pos, e->rope_cos, e->rope_sin, ldq, l.n_heads + l.n_kv_heads,
-                           (const float*)nullptr, 0);
+      launch_rope(st, hd, sl.qkv, e->d_pos, e->rope_cos, e->rope_sin, ldq, l.n_heads + l.n_kv_heads, w.qkv_bias, l.n_kv_heads, T);
     }
     if (keep) {
       const size_t half_layer = (size_t)(keep->slots ? keep->rows : n_seq) * KV * keep->P;
       half_t* kc = keep->kv + (size_t)i * 2 * half_layer;
       Bracket br(e, st, PC_OTHER, 0, (double)T * KV * 8.0);
-      if (hd == 64 && keep->slots)
-        hipLaunchKernelGGL(kv_cache_fill64_slots_kernel, dim3(sl.maxL, n_seq), dim3(256), 0, st, sl.qkv, sl.d_seq_off, keep->slots, keep->rows,
-                           kc, kc + half_layer, ldq, l.n_heads, l.n_kv_heads, keep->P);
-      else if (hd == 64)
-        hipLaunchKernelGGL(kv_cache_fill64_kernel, dim3(sl.maxL, n_seq), dim3(256), 0, st, sl.qkv, sl.d_seq_off, kc, kc + half_layer, ldq,
-                           l.n_heads, l.n_kv_heads, keep->P);
-      else if (keep->slots)
-        hipLaunchKernelGGL(kv_cache_fill128_slots_kernel, dim3(sl.maxL, n_seq), dim3(256), 0, st, sl.qkv, sl.d_seq_off, keep->slots, keep->rows,
-                           kc, kc + half_layer, ldq, l.n_heads, l.n_kv_heads, keep->P);
-      else
-        hipLaunchKernelGGL(kv_cache_fill128_kernel, dim3(sl.maxL, n_seq), dim3(256), 0, st, sl.qkv, sl.d_seq_off, kc, kc + half_layer, ldq,
-                           l.n_heads, l.n_kv_heads, keep->P);
+      launch_kv_fill(st, hd, sl.qkv, sl.d_seq_off, keep->slots, keep->rows, kc, kc + half_layer, ldq, l.n_heads, l.n_kv_heads, keep->P, sl.maxL, n_seq);
     }
     launch_llama_attn(e, st, CausalAttnCall{sl.qkv, sl.ctx, sl.d_seq_off, ldq, Q, l.n_heads, l.n_kv_heads, sl.n_seq, sl.maxL, T}, ap);
     RC(ns.producer(e, st, Gemm(PC_ENC_GEMM_O, EPI_RESID_F32, sl.ctx, Q, w.o, Q, ns.hidden, dm, T, dm, Q)));
@@ -2676,8 +2718,7 @@ int rk_llama_last_logits(rk_engine* e, const int32_t* tokens, const int32_t* seq
   Slot& sl = e->slots[0];
   hipStream_t st = sl.se;
   HIPCHK(e, hipMemcpyAsync(sl.idx.d[IX_OUT_IDS], out_token_ids, n_out * sizeof(int), hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(head_rows_kernel, dim3((n_seq * n_out + 3) / 4), dim3(256), 0, st, sl.dlast, e->lm_head, sl.idx.d[IX_OUT_IDS],
-                     sl.d_scores, n_seq, n_out, e->ld.hidden);
+  launch_head_rows(st, sl.dlast, e->lm_head, sl.idx.d[IX_OUT_IDS], sl.d_scores, n_seq, n_out, e->ld.hidden);
   return read_scores_blocking(e, sl, st, (size_t)n_seq * n_out, out_logits);
 }
 
@@ -2808,7 +2849,7 @@ int rk_llama_generate(rk_engine* e, const int32_t* tokens, const int32_t* seq_of
     int r = head_argmax(e, st, sl.dlast, n_seq, l.hidden, l.vocab, sl.d_argmax);
     if (r) return r;
     Bracket br(e, st, PC_OTHER, 0, 0);
-    hipLaunchKernelGGL(llama_advance_kernel, dim3(1), dim3(256), 0, st, sl.d_argmax, g, d_len, d_done, d_pos, d_out, d_next, n_seq);
+    launch_llama_advance(st, sl.d_argmax, g, d_len, d_done, d_pos, d_out, d_next, n_seq);
     return RK_OK;
   };
   if ((rc = head_and_advance())) return rc;
@@ -2920,8 +2961,7 @@ int rk_llama_session_admit(rk_engine* e, const int32_t* tokens, const int32_t* s
   if ((rc = head_argmax(e, st, sl.dlast, n, e->ld.hidden, e->ld.vocab, sl.d_argmax))) return rc;
   {
     Bracket br(e, st, PC_OTHER, 0, 0);
-    hipLaunchKernelGGL(llama_session_advance_kernel, dim3(1), dim3(256), 0, st, sl.d_argmax, d.st, d.len, d.col, d.max_new, d.done, d.pos, d.out,
-                       d.next, ls.n_slots, d.admit, n);
+    launch_session_advance(st, sl.d_argmax, d.st, d.len, d.col, d.max_new, d.done, d.pos, d.out, d.next, ls.n_slots, d.admit, n);
   }
   for (int b = 0; b < n; ++b) { const int s = slots[b]; ls.busy[s] = 1; ls.told[s] = 0; ls.len[s] = adm[n + b]; ls.max_new[s] = max_new[b]; }
   return session_read_back(e, st);
@@ -2945,8 +2985,7 @@ int rk_llama_session_run(rk_engine* e, int max_steps, int32_t* out_finished, int
       int r = llama_step_rows(e, st, ls.n_slots, ls.max_len, d.next, d.pos);
       if (r || (r = head_argmax(e, st, sl.dlast, ls.n_slots, e->ld.hidden, e->ld.vocab, sl.d_argmax))) return r;
       Bracket br(e, st, PC_OTHER, 0, 0);
-      hipLaunchKernelGGL(llama_session_advance_kernel, dim3(1), dim3(256), 0, st, sl.d_argmax, d.st, d.len, d.col, d.max_new, d.done, d.pos,
-                         d.out, d.next, ls.n_slots, (const int*)nullptr, 0);
+      launch_session_advance(st, sl.d_argmax, d.st, d.len, d.col, d.max_new, d.done, d.pos, d.out, d.next, ls.n_slots, nullptr, 0);
       return RK_OK;
     };
     const std::vector<int> key{GK_LLAMA_SESSION_STEP, 0, ls.n_slots, ls.max_len, ls.cap, e->amax_gen, e->lkv_gen};
@@ -3381,7 +3420,7 @@ int rk_debug_gemm_ex(rk_engine* e, rk_debug_gemm_call* q) {
   c.fold = GemmFold();
   if (q->rowscale) c.fold.rowscale = dR;
   else if (q->ssq_in && q->factors_kernel) {
-    hipLaunchKernelGGL(rowscale_kernel, dim3((M + 255) / 256), dim3(256), 0, st, dQ, dR, M, q->nb_in, K, e->d.eps, RK_XRAW_SCALE);
+    launch_rowscale(st, dQ, dR, M, q->nb_in, K, e->d.eps, RK_XRAW_SCALE);
     c.fold.rowscale = dR;
   } else if (q->ssq_in) { c.fold.ssq_in = dQ; c.fold.nb_in = q->nb_in; }
   if (producer) { c.fold.xraw = dX + xband; c.fold.ssq = dS + sband; }
@@ -3408,12 +3447,13 @@ int rk_debug_attn(rk_engine* e, rk_debug_attn_call* q) {
   if (rc) return rc;
   if (!e->finalized) return fail(e, RK_ERR_STATE, "debug attn: engine not finalized");
   const int kind = q->kind, B = q->n_seq, H = q->H;
-  if (kind < 1 || kind > 5) return fail(e, RK_ERR_INVALID, "debug attn: kind 1..5");
-  if (e->family != (kind >= 4 ? 1 : 0)) return fail(e, RK_ERR_STATE, "debug attn: kind %d needs a %s engine", kind, kind >= 4 ? "Llama" : "T5");
+  if (kind < 1 || kind > 6) return fail(e, RK_ERR_INVALID, "debug attn: kind 1..6");
+  const bool llama_kind = kind == 4 || kind == 5;
+  if (e->family != (llama_kind ? 1 : 0)) return fail(e, RK_ERR_STATE, "debug attn: kind %d needs a %s engine", kind, llama_kind ? "Llama" : "T5");
   if (B <= 0 || B > (1 << 16) || H <= 0 || H > 1024) return fail(e, RK_ERR_INVALID, "debug attn: n_seq and H");
   const bool planning = q->plan_only != 0;
   const int hd = head_width(e), band = q->band_rows;   // (kinds 4 and 5: the Llama engine's head_dim, 64 or 128)
-  if (kind == 2 && hd != 64) return refuse_wide(e, "debug attn", "kind 2 (the decoder kernels) has no 128-wide form");
+  if ((kind == 2 || kind == 6) && hd != 64) return refuse_wide(e, "debug attn", "kinds 2 and 6 (the decoder kernels) have no 128-wide form");
   if (!planning && (!q->q || !q->out || !q->out_all || band < 1)) return fail(e, RK_ERR_INVALID, "debug attn: q, out, out_all and band_rows >= 1");
   // ---- the offsets: lengths, the longest and the shortest ----
   int maxL = 0, minL = 1 << 30, T = 0;
@@ -3504,6 +3544,16 @@ int rk_debug_attn(rk_engine* e, rk_debug_attn_call* q) {
     ldq_min = (long)(H + 2 * n_kv) * hd; ldctx_min = (long)H * hd; q_rows_need = out_rows_need = T;
     cp = plan_llama_attn(e, B, maxL, H, n_kv);
     plan_out(cp.hd64 ? 2 : (int)cp.dma, cp.nw, cp.grid, dim3(0, 0, 0), cp.lds);
+  } else if (kind == 6) {
+    const int P = q->P;
+    if (P <= 0 || P > 8192) return fail(e, RK_ERR_INVALID, "debug attn: the T5 cached step takes a cache of 1..8192 positions");
+    ldq_min = 3L * H * 64; ldctx_min = (long)H * 64; q_rows_need = out_rows_need = B;
+    if (!planning) {
+      if (!q->pos || !q->bias_lut || !q->cache || !q->cache_all) return fail(e, RK_ERR_INVALID, "debug attn: the T5 cached step needs pos, bias_lut, cache and cache_all");
+      if (q->pos[0] < 0 || q->pos[0] >= P) return fail(e, RK_ERR_INVALID, "debug attn: pos = %d outside the cache of %d positions", q->pos[0], P);
+    }
+    const bool one = e->opt.dec_cached_attn != 0;
+    plan_out(one ? 1 : 0, 0, one ? dim3(H, B) : dim3(B), one ? dim3(0, 0, 0) : dim3(1, H, B), (int)attn_dec_lds(P));
   } else {
     const int n_kv = q->n_kv, P = q->P;
     if (n_kv <= 0 || H % n_kv || P <= 0 || P > (1 << 20)) return fail(e, RK_ERR_INVALID, "debug attn: n_kv must divide H, P > 0");
@@ -3554,8 +3604,9 @@ int rk_debug_attn(rk_engine* e, rk_debug_attn_call* q) {
   half_t* const oi = dO + o_band;
   int* dOff = has_off ? (int*)up(q->seq_off, (size_t)(B + 1) * 4) : nullptr;
   if (has_off && !dOff) return done(fail(e, RK_ERR_HIP, "debug attn: upload failed"));
-  float* dLut = q->bias_lut && kind <= 2 ? (float*)up(q->bias_lut, (size_t)H * RK_LUT_N * 4) : nullptr;
-  if (q->bias_lut && kind <= 2 && !dLut) return done(fail(e, RK_ERR_HIP, "debug attn: upload failed"));
+  const bool takes_lut = kind <= 2 || kind == 6;
+  float* dLut = q->bias_lut && takes_lut ? (float*)up(q->bias_lut, (size_t)H * RK_LUT_N * 4) : nullptr;
+  if (q->bias_lut && takes_lut && !dLut) return done(fail(e, RK_ERR_HIP, "debug attn: upload failed"));
   hipStream_t st = e->slots[0].se;
   half_t* dC = nullptr; size_t c_all = 0;
   if (kind == 1) {
@@ -3583,6 +3634,20 @@ int rk_debug_attn(rk_engine* e, rk_debug_attn_call* q) {
   } else if (kind == 4) {
     DBG_HIP(hipDeviceSynchronize());
     launch_llama_attn(e, st, CausalAttnCall{qi, oi, dOff, q->ldq, q->ldctx, H, q->n_kv, B, maxL, T}, cp);
+  } else if (kind == 6) {
+    const int I = H * 64, P = q->P;
+    const size_t c_in = (size_t)B * P * 2 * I, c_band = (size_t)band * 64;
+    c_all = c_in + 2 * c_band;
+    dC = (half_t*)alloc(c_all * 2, RK_DEBUG_SENTINEL);
+    std::vector<int> keys((size_t)B * P);
+    for (int b = 0; b < B; ++b) for (int j = 0; j < P; ++j) keys[(size_t)b * P + j] = b * P + j;   // (as rk_t5_generate lays them out)
+    int* dPos = (int*)up(q->pos, 4);
+    int* dTk = (int*)up(keys.data(), keys.size() * 4);
+    int* dTp = (int*)alloc((size_t)B * 4, 0);
+    if (!dC || !dPos || !dTk || !dTp) return done(fail(e, RK_ERR_HIP, "debug attn: device allocation or upload failed"));
+    DBG_HIP(hipMemcpy(dC + c_band, q->cache, c_in * 2, hipMemcpyHostToDevice));
+    DBG_HIP(hipDeviceSynchronize());
+    launch_dec_cached_step(e, st, AttnCachedArgs{qi, q->ldq, dC + c_band, P, I, dPos, oi, q->ldctx, dLut}, B, H, dTk, dTp);
   } else {
     const size_t half_layer = (size_t)B * q->n_kv * q->P * hd, c_band = (size_t)band * hd;
     c_all = 2 * half_layer + 2 * c_band;
@@ -3755,6 +3820,251 @@ int rk_debug_xattn_chain(rk_engine* e, rk_debug_xattn_chain_call* q) {
 #undef DBG_HIP
   return done(RK_OK);
 }
+
+// debug: one launch of a row kernel or device state machine on host data, every output between sentinel bands
+// (include/rk_engine.h).  No kernel, grid rule or dispatch of its own: it uploads the operands and calls the launcher of the op,
+// the function the production path calls.
+int rk_debug_rows(rk_engine* e, rk_debug_rows_call* q) {
+  if (!e || !q) return RK_ERR_INVALID;
+  int rc = set_device(e);
+  if (rc) return rc;
+  const int op = q->op, rows = q->rows, d = q->d;
+  const long R = rows;
+  if (op < 1 || op > 10) return fail(e, RK_ERR_INVALID, "debug rows: op 1..10");
+  if (rows <= 0 || rows > (1 << 20)) return fail(e, RK_ERR_INVALID, "debug rows: rows = %d", rows);
+  const int n_steps = op == 10 ? q->n_steps : 1;
+  if (n_steps < 1 || n_steps > 4096) return fail(e, RK_ERR_INVALID, "debug rows: n_steps = %d", n_steps);
+  // ---- what the launch addresses: bytes of every operand (0: unused; in_opt: may be null), from the op's arguments alone ----
+  long in_need[4] = {0, 0, 0, 0}, out_need[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  bool in_opt[4] = {false, false, false, false};
+  dim3 grid(1);
+  int tparam = 0, variant = 0, maxL = 0;
+  auto ints = [&](int i, long n) -> const int* { return (q->in[i].data && q->in[i].off >= 0 && q->in[i].off + n * 4 <= q->in[i].bytes) ? (const int*)((const char*)q->in[i].data + q->in[i].off) : nullptr; };
+  auto state = [&](int i, long n) -> const int* { return (q->out[i].interior && n * 4 <= q->out[i].bytes) ? (const int*)q->out[i].interior : nullptr; };
+  const bool planning = q->plan_only != 0;
+  auto bad = [&](const char* what) { return fail(e, RK_ERR_INVALID, "debug rows: op %d: %s", op, what); };
+  switch (op) {
+    case 1: {
+      if (d <= 0 || d % 8 || d > (1 << 16) || q->vocab <= 0 || q->vocab > (1 << 22)) return bad("d (a multiple of 8) and vocab");
+      in_need[0] = R * 4; in_need[1] = (long)q->vocab * d * 2;
+      out_need[0] = R * d * 4; out_need[1] = R * d * 2; out_need[2] = R * 4;
+      grid = grid_waves(rows); variant = q->kind != 0;
+    } break;
+    case 2: {
+      if (q->nb <= 0 || q->nb > (1 << 16) || d <= 0) return bad("nb and d");
+      in_need[0] = R * q->nb * 4; out_need[0] = R * 4;
+      grid = grid_rowscale(rows);
+    } break;
+    case 3: {
+      if (d <= 0 || d % 4 || d > 4096) return bad("d must be a multiple of 4 and at most 4096 (rmsnorm_kernel<16> holds 4096 columns)");
+      if (q->src_rows <= 0 || q->src_rows > (1 << 20)) return bad("src_rows");
+      in_need[0] = (long)q->src_rows * d * 4; in_need[1] = (long)d * 4; in_need[2] = R * 4; in_opt[2] = true;
+      out_need[0] = R * d * 2;
+      grid = grid_waves(rows); tparam = rmsnorm_nv(d);
+      if (!planning) {
+        if (q->in[2].data) {
+          const int* m = ints(2, R);
+          if (!m) return bad("row_map of rows ints");
+          for (long r = 0; r < R; ++r) if (m[r] < 0 || m[r] >= q->src_rows) return bad("row_map entry outside [0, src_rows)");
+        } else if (rows > q->src_rows) return bad("rows beyond src_rows without a row_map");
+      }
+    } break;
+    case 4: case 5: {
+      const int n_out = op == 4 ? q->n_out : 2;
+      if (d <= 0 || d % 8 || d > (1 << 16) || q->vocab <= 0 || q->vocab > (1 << 22) || n_out <= 0 || n_out > 4096) return bad("d (a multiple of 8), vocab and n_out");
+      if (op == 5 && (rows < 2 || q->false_id < 0 || q->false_id >= q->vocab || q->true_id < 0 || q->true_id >= q->vocab)) return bad("at least 2 sequences, false_id and true_id inside the vocabulary");
+      in_need[0] = R * d * 2; in_need[1] = (long)q->vocab * d * 2;
+      if (op == 4) {
+        in_need[2] = (long)n_out * 4; out_need[0] = R * n_out * 4;
+        if (!planning) {
+          const int* ids = ints(2, n_out);
+          if (!ids) return bad("out_ids of n_out ints");
+          for (int j = 0; j < n_out; ++j) if (ids[j] < 0 || ids[j] >= q->vocab) return bad("out_ids entry outside the vocabulary");
+        }
+        grid = grid_waves(rows * n_out);
+      } else { out_need[0] = (3 * R + R / 2) * 4; grid = grid_pairs(rows); }
+    } break;
+    case 6: {
+      if (q->nb <= 0 || q->nb > (1 << 20)) return bad("nb");
+      in_need[0] = in_need[1] = R * q->nb * 4; out_need[0] = R * 4;
+      grid = dim3(rows);
+    } break;
+    case 7: {
+      if (q->nb <= 0 || q->nb > (1 << 20) || q->n_pos < 0 || q->n_pos > (1 << 16)) return bad("nb and n_pos");
+      long n_rows = R * q->n_pos;
+      in_need[2] = (R + 1) * 4; in_opt[2] = true; in_need[3] = R * 4; in_opt[3] = true;
+      if (!planning && q->in[2].data) {
+        const int* ro = ints(2, R + 1);
+        if (!ro || ro[0] < 0) return bad("row_off of rows + 1 ints from >= 0");
+        for (long b = 0; b < R; ++b) if (ro[b + 1] < ro[b]) return bad("row_off must not shrink");
+        n_rows = ro[R];
+      }
+      if (!planning && q->in[3].data) {
+        const int* oi = ints(3, R);
+        if (!oi) return bad("out_idx of rows ints");
+        for (long b = 0; b < R; ++b) if (oi[b] < 0 || oi[b] >= rows) return bad("out_idx entry outside [0, rows)");
+      }
+      in_need[0] = n_rows * q->nb * 8; in_need[1] = n_rows * 4; out_need[0] = R * 4;
+      grid = dim3(rows);
+    } break;
+    case 8: {
+      const int hd = q->hd, H = q->H, n_kv = q->n_kv;
+      if ((hd != 64 && hd != 128) || H <= 0 || n_kv <= 0 || H > 1024 || n_kv > 1024 || q->max_pos <= 0) return bad("hd 64 or 128, H, n_kv, max_pos");
+      if (q->ld % 8 || q->ld < (H + 2 * n_kv) * hd) return bad("ld: a multiple of 8, at least (H + 2 n_kv) hd");
+      in_need[0] = R * 4; in_need[1] = in_need[2] = (long)q->max_pos * (hd / 2) * 4; in_need[3] = (long)(H + 2 * n_kv) * hd * 4; in_opt[3] = true;
+      out_need[0] = R * q->ld * 2;
+      if (!planning) {
+        const int* pos = ints(0, R);
+        if (!pos) return bad("pos of rows ints");
+        for (long t = 0; t < R; ++t) if (pos[t] < 0 || pos[t] >= q->max_pos) return bad("pos entry outside the tables");
+      }
+      grid = dim3(rows); tparam = hd; variant = q->in[3].data != nullptr;
+    } break;
+    case 9: {
+      const int hd = q->hd, H = q->H, n_kv = q->n_kv;
+      if ((hd != 64 && hd != 128) || H <= 0 || n_kv <= 0 || H > 1024 || n_kv > 1024 || q->P <= 0 || q->P > (1 << 20)) return bad("hd 64 or 128, H, n_kv, P");
+      if (q->ld % 8 || q->ld < (H + 2 * n_kv) * hd) return bad("ld: a multiple of 8, at least (H + 2 n_kv) hd");
+      const bool slots = q->in[2].data != nullptr;
+      if (slots && (q->n_slots <= 0 || q->n_slots > (1 << 16))) return bad("n_slots");
+      const int* so = ints(1, R + 1);
+      if (!so || so[0] != 0) return bad("seq_off of rows + 1 ints from 0");
+      for (long b = 0; b < R; ++b) { if (so[b + 1] < so[b]) return bad("seq_off must not shrink"); maxL = std::max(maxL, so[b + 1] - so[b]); }
+      if (maxL < 1 || maxL > (1 << 16)) return bad("the longest sequence has 1..65536 rows");
+      in_need[0] = (long)so[R] * q->ld * 2; in_need[1] = (R + 1) * 4; in_need[2] = R * 4; in_opt[2] = true;
+      out_need[0] = 2L * (slots ? q->n_slots : rows) * n_kv * q->P * hd * 2;
+      grid = grid_kv_fill(maxL, rows); tparam = hd; variant = slots;
+    } break;
+    default: {
+      const int kind = q->kind;
+      if (kind < 0 || kind > 2) return bad("kind 0..2");
+      const long A = kind == 2 ? std::max<long>(R, q->max_admit) : R;
+      if (kind == 2 && (q->max_admit < 0 || q->max_admit > (1 << 20))) return bad("max_admit");
+      in_need[0] = (long)n_steps * A * 4;
+      variant = kind;
+      if (planning) break;
+      if (kind == 0) {
+        if (q->dec_len <= 0 || q->max_new <= 0 || q->dec_len > (1 << 16) || q->max_new > (1 << 16)) return bad("dec_len and max_new");
+        in_need[1] = (long)q->dec_len * 4;
+        out_need[0] = 16; out_need[1] = R * 4; out_need[2] = R * q->max_new * 4; out_need[3] = R * 4;
+        const int* st = state(0, 4);
+        if (!st || st[0] < 0) return bad("st of 4 ints with st[0] >= 0");
+      } else if (kind == 1) {
+        const int* st = state(0, 16);
+        if (!st || st[0] < 0 || st[3] < 0 || st[3] > 8 || st[4] <= 0 || st[4] > (1 << 16)) return bad("st of 16 ints: n >= 0, n_eos in 0..8, max_new > 0");
+        in_need[1] = R * 4;
+        out_need[0] = 64; out_need[1] = out_need[2] = out_need[4] = R * 4; out_need[3] = R * st[4] * 4;
+      } else {
+        const int* st = state(0, 16);
+        if (!st || st[2] < 0 || st[2] > 8 || st[4] <= 0 || st[4] > (1 << 16)) return bad("st of 16 ints: n_eos in 0..8, cap > 0");
+        out_need[0] = 64;
+        for (int i = 1; i <= 7; ++i) out_need[i] = R * 4;
+        out_need[6] = R * st[4] * 4;
+        const int* col = state(2, R);
+        if (!col) return bad("col of rows ints");
+        for (long b = 0; b < R; ++b) if (col[b] < 0) return bad("col entry negative");
+        in_need[1] = (long)n_steps * (1 + 3L * q->max_admit) * 4; in_opt[1] = true;
+        if (q->in[1].data) {
+          const int* ad = ints(1, (long)n_steps * (1 + 3L * q->max_admit));
+          if (!ad) return bad("admit script of n_steps x (1 + 3 max_admit) ints");
+          for (int s = 0; s < n_steps; ++s) {
+            const int n = ad[(long)s * (1 + 3L * q->max_admit)];
+            if (n < -1 || n > q->max_admit) return bad("admit count outside -1..max_admit");
+          }
+        }
+      }
+    } break;
+  }
+  q->out_grid[0] = (int)grid.x; q->out_grid[1] = (int)grid.y; q->out_grid[2] = (int)grid.z; q->out_tparam = tparam; q->out_variant = variant;
+  if (planning) return RK_OK;
+  // ---- extents against what the caller gave ----
+  for (int i = 0; i < 4; ++i) {
+    const rk_debug_rows_in& b = q->in[i];
+    if (!in_need[i] || (in_opt[i] && !b.data)) continue;
+    if (!b.data || b.off < 0 || b.off % 16 || b.off + in_need[i] > b.bytes)
+      return fail(e, RK_ERR_INVALID, "debug rows: op %d: input %d needs %ld bytes at offset %ld (a multiple of 16) of %ld", op, i, in_need[i], (long)b.off, (long)b.bytes);
+  }
+  for (int i = 0; i < 8; ++i) {
+    const rk_debug_rows_out& b = q->out[i];
+    if (!out_need[i]) continue;
+    if (!b.interior || !b.all || b.band < 64 || b.band % 16 || b.band > (1 << 26) || out_need[i] > b.bytes || b.bytes > (1L << 31))
+      return fail(e, RK_ERR_INVALID, "debug rows: op %d: output %d needs %ld of %ld bytes, interior, all and a band of 64 bytes or more (a multiple of 16)", op, i, out_need[i], (long)b.bytes);
+  }
+  std::vector<void*> dev;
+  auto alloc = [&](size_t bytes, int fill) -> void* {
+    void* ptr = nullptr;
+    if (hipMalloc(&ptr, bytes ? bytes : 16) != hipSuccess) return nullptr;
+    dev.push_back(ptr);
+    if (fill >= 0 && hipMemset(ptr, fill, bytes) != hipSuccess) return nullptr;
+    return ptr;
+  };
+  auto done = [&](int r) { for (void* ptr : dev) hipFree(ptr); return r; };
+#define DBG_HIP(x) do { if ((x) != hipSuccess) return done(fail(e, RK_ERR_HIP, "debug rows: %s", #x)); } while (0)
+  char* din[4] = {nullptr, nullptr, nullptr, nullptr};      // the kernels' pointers
+  char* dall[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  char* dout[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  for (int i = 0; i < 4; ++i) {
+    const rk_debug_rows_in& b = q->in[i];
+    if (!in_need[i] || !b.data) continue;
+    char* p = (char*)alloc((size_t)b.bytes, -1);
+    if (!p) return done(fail(e, RK_ERR_HIP, "debug rows: device allocation failed"));
+    DBG_HIP(hipMemcpy(p, b.data, (size_t)b.bytes, hipMemcpyHostToDevice));
+    din[i] = p + b.off;
+  }
+  for (int i = 0; i < 8; ++i) {
+    const rk_debug_rows_out& b = q->out[i];
+    if (!out_need[i]) continue;
+    dall[i] = (char*)alloc((size_t)(b.bytes + 2 * b.band), RK_DEBUG_SENTINEL);
+    if (!dall[i]) return done(fail(e, RK_ERR_HIP, "debug rows: device allocation failed"));
+    dout[i] = dall[i] + b.band;
+    DBG_HIP(hipMemcpy(dout[i], b.interior, (size_t)b.bytes, hipMemcpyHostToDevice));
+  }
+  DBG_HIP(hipDeviceSynchronize());
+  hipStream_t st = e->slots[0].se;
+  const long A = (op == 10 && q->kind == 2) ? std::max<long>(R, q->max_admit) : R, rec = 1 + 3L * q->max_admit;
+  for (int s = 0; s < n_steps; ++s) {
+    switch (op) {
+      case 1: launch_embed(st, (const int*)din[0], (const half_t*)din[1], (float*)dout[0], rows, d, q->vocab, q->kind ? (half_t*)dout[1] : nullptr,
+                           q->kind ? (float*)dout[2] : nullptr, q->xs, q->eps); break;
+      case 2: launch_rowscale(st, (const float*)din[0], (float*)dout[0], rows, q->nb, d, q->eps, q->xs); break;
+      case 3: launch_rmsnorm(st, (const float*)din[0], (const float*)din[1], (half_t*)dout[0], (const int*)din[2], rows, d, q->eps, q->out_scale); break;
+      case 4: launch_head_rows(st, (const half_t*)din[0], (const half_t*)din[1], (const int*)din[2], (float*)dout[0], rows, q->n_out, d); break;
+      case 5: launch_pair_verdict(st, (const half_t*)din[0], (const half_t*)din[1], q->false_id, q->true_id, (float*)dout[0], rows, d); break;
+      case 6: launch_argmax_blocks(st, (const float*)din[0], (const int*)din[1], q->nb, (int*)dout[0], rows); break;
+      case 7: launch_qlm_lse(st, (const float2*)din[0], q->nb, (const float*)din[1], q->n_pos, (const int*)din[2], (const int*)din[3], (float*)dout[0], rows); break;
+      case 8: launch_rope(st, q->hd, (half_t*)dout[0], (const int*)din[0], (const float*)din[1], (const float*)din[2], q->ld, q->H + q->n_kv,
+                          (const float*)din[3], q->n_kv, rows); break;
+      case 9: {
+        half_t* kc = (half_t*)dout[0];
+        launch_kv_fill(st, q->hd, (const half_t*)din[0], (const int*)din[1], (const int*)din[2], q->n_slots, kc,
+                       kc + (size_t)(din[2] ? q->n_slots : rows) * q->n_kv * q->P * q->hd, q->ld, q->H, q->n_kv, q->P, maxL, rows);
+      } break;
+      default: {
+        const int* am = (const int*)din[0] + (size_t)s * A;
+        if (q->kind == 0)
+          launch_greedy_advance(st, am, (int*)dout[0], (const int*)din[1], (int*)dout[1], (int*)dout[2], (int*)dout[3], rows, q->dec_len, q->max_new);
+        else if (q->kind == 1)
+          launch_llama_advance(st, am, (int*)dout[0], (const int*)din[1], (int*)dout[1], (int*)dout[2], (int*)dout[3], (int*)dout[4], rows);
+        else {
+          const int* host_rec = din[1] ? (const int*)((const char*)q->in[1].data + q->in[1].off) + (size_t)s * rec : nullptr;
+          const int n_admit = host_rec ? host_rec[0] : -1;
+          const int* adm = n_admit >= 0 ? (const int*)din[1] + (size_t)s * rec + 1 : nullptr;
+          launch_session_advance(st, am, (int*)dout[0], (int*)dout[1], (int*)dout[2], (int*)dout[3], (int*)dout[4], (int*)dout[5], (int*)dout[6],
+                                 (int*)dout[7], rows, adm, n_admit >= 0 ? n_admit : 0);
+        }
+      } break;
+    }
+    DBG_HIP(hipStreamSynchronize(st));
+    DBG_HIP(hipGetLastError());
+    for (int i = 0; i < 8; ++i)
+      if (dall[i]) {
+        const size_t all = (size_t)(q->out[i].bytes + 2 * q->out[i].band);
+        DBG_HIP(hipMemcpy((char*)q->out[i].all + (size_t)s * all, dall[i], all, hipMemcpyDeviceToHost));
+      }
+  }
+#undef DBG_HIP
+  return done(RK_OK);
+}
+
 
 int rk_debug_gemm(rk_engine* e, const uint16_t* A, const uint16_t* W, float* C, int M, int N, int K, int use_glds) {
   if (!e || !A || !W || !C) return RK_ERR_INVALID;

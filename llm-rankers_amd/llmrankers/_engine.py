@@ -75,6 +75,22 @@ class RkDebugXattnChainCall(C.Structure):
                 ("out_fuse_cv", C.c_int * 2), ("out_cv_R", C.c_int * 2), ("out_eps", C.c_float), ("out_xs", C.c_float)]
 
 
+class RkDebugRowsIn(C.Structure):
+    _fields_ = [("data", C.c_void_p), ("bytes", C.c_int64), ("off", C.c_int64)]
+
+
+class RkDebugRowsOut(C.Structure):
+    _fields_ = [("interior", C.c_void_p), ("bytes", C.c_int64), ("band", C.c_int64), ("all", C.c_void_p)]
+
+
+class RkDebugRowsCall(C.Structure):
+    """rk_debug_rows_call of include/rk_engine.h, field for field."""
+    _fields_ = [(n, C.c_int) for n in ("op", "kind", "rows", "d", "vocab", "src_rows", "n_out", "nb", "n_pos", "H", "n_kv", "hd", "ld", "P",
+                                       "n_slots", "max_pos", "false_id", "true_id", "dec_len", "max_new", "n_steps", "max_admit")] + \
+               [("eps", C.c_float), ("xs", C.c_float), ("out_scale", C.c_float), ("in_", RkDebugRowsIn * 4), ("out", RkDebugRowsOut * 8),
+                ("plan_only", C.c_int), ("out_grid", C.c_int * 3), ("out_tparam", C.c_int), ("out_variant", C.c_int)]
+
+
 DEBUG_SENTINEL = 0xCD                      # RK_DEBUG_SENTINEL: the byte the guard bands of rk_debug_gemm_ex are filled with
 DEBUG_BAND_ROWS = 256
 GEMM_OUT_DTYPE = {0: np.float16, 1: np.float32, 2: np.float16, 3: np.float16, 4: np.float32, 5: np.float16, 6: np.float32, 7: np.float32}
@@ -142,6 +158,7 @@ ABI = {
     "rk_debug_gemm_ex": (C.c_int, [C.c_void_p, _P(RkDebugGemmCall)]),
     "rk_debug_attn": (C.c_int, [C.c_void_p, _P(RkDebugAttnCall)]),
     "rk_debug_xattn_chain": (C.c_int, [C.c_void_p, _P(RkDebugXattnChainCall)]),
+    "rk_debug_rows": (C.c_int, [C.c_void_p, _P(RkDebugRowsCall)]),
     "rk_debug_gemm_bench": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _f32p]),
     "rk_debug_read": (C.c_int64, [C.c_void_p, C.c_char_p, _f32p, C.c_int64]),
 }
@@ -537,7 +554,7 @@ class RkEngine:
                    row_seq=None, pos=None, bias_lut=None, cos=None, sin=None, qkv_bias=None, cache=None, plan_only=False) -> dict:
         """One attention call through rk_debug_attn (include/rk_engine.h).  q / kv: 2-D fp16 [band_rows + rows + band_rows, ld], the
         WHOLE allocation with the caller's bands; out: 2-D fp16 [rows, ldctx], the pre-filled interior; cache (kind 5): flat fp16, K then
-        V.  Returns the plan fields and, unless plan_only, "out" [band_rows + rows + band_rows, ldctx] and "cache" (flat, with bands
+        V (kind 6, the T5 cached step: [n_seq][P][k | v] of 64 H each, bands of band_rows * 64 elements, pos one value).  Returns the plan fields and, unless plan_only, "out" [band_rows + rows + band_rows, ldctx] and "cache" (flat, with bands
         of band_rows * hd elements, hd = a Llama engine's head width): the whole device allocations after the call."""
         hd = int(getattr(self.desc, "head_dim", 128))   # the Llama kinds' head width (64 or 128); the T5 kinds have no such operand
         c = RkDebugAttnCall()
@@ -564,7 +581,7 @@ class RkEngine:
         for name, a in (("seq_off", seq_off), ("row_off", row_off), ("tree_keys", tree_keys), ("tree_pos", tree_pos), ("row_seq", row_seq), ("pos", pos)):
             a = put(name, a, np.int32)
             if a is not None:
-                assert a.size >= {"seq_off": n_seq + 1, "row_off": n_seq + 1, "pos": n_seq}.get(name, 0)
+                assert a.size >= {"seq_off": n_seq + 1, "row_off": n_seq + 1, "pos": 1 if kind == 6 else n_seq}.get(name, 0)
                 if name == "tree_pos":
                     c.tree_rows = a.size
                     assert tree_keys is not None and np.asarray(tree_keys).size == a.size * Ld
@@ -586,7 +603,11 @@ class RkEngine:
             out_all = put("out_all", np.zeros((out.shape[0] + 2 * band_rows, ldctx)), np.float16)
         if cache is not None:
             cache = put("cache", cache, np.float16).reshape(-1)
-            assert cache.size == 2 * n_seq * n_kv * P * hd
+            if kind == 6:                                   # the T5 cached step: [n_seq][P][k | v] of 64 H each, bands of band_rows x 64
+                hd = 64
+                assert cache.size == n_seq * P * 2 * 64 * H
+            else:
+                assert cache.size == 2 * n_seq * n_kv * P * hd
             cache_all = put("cache_all", np.zeros(cache.size + 2 * band_rows * hd), np.float16)
         self._chk(self.lib.rk_debug_attn(self.h, C.byref(c)))
         del keep
@@ -597,6 +618,43 @@ class RkEngine:
                 res[k[4:]] = v if isinstance(v, int) else tuple(v)
         if not plan_only:
             res.update(out=out_all, cache=cache_all)
+        return res
+
+    def debug_rows(self, op: int, *, ins=(), outs=(), band=256, n_steps=1, plan_only=False, check=True, **params) -> dict:
+        """One launch of a row kernel or state machine through rk_debug_rows (include/rk_engine.h).  ins: per input None, an array
+        (no bands) or (whole array, interior offset in ELEMENTS); outs: per output the pre-filled interior array.  params: the call's
+        int / float fields by name.  Returns "grid", "tparam", "variant", "rc" and, unless plan_only, "all": per output a byte array
+        [n_steps, band + bytes + band] - the whole device allocations after every launch.  check=False: a refusal is returned as rc
+        (the outputs then still hold what the caller gave) instead of raised."""
+        c = RkDebugRowsCall()
+        c.op, c.n_steps, c.plan_only = op, n_steps, int(plan_only)
+        for k, v in params.items():
+            assert k in dict(RkDebugRowsCall._fields_) and k not in ("in_", "out"), k
+            setattr(c, k, v)
+        keep, alls = [], []
+        for i, a in enumerate(ins):
+            if a is None:
+                continue
+            a, off = a if isinstance(a, tuple) else (a, 0)
+            a = np.ascontiguousarray(a)
+            keep.append(a)
+            c.in_[i].data, c.in_[i].bytes, c.in_[i].off = a.ctypes.data, a.nbytes, off * a.itemsize
+        for i, a in enumerate(outs):
+            if a is None:
+                alls.append(None)
+                continue
+            a = np.ascontiguousarray(a)
+            whole = np.full((n_steps, a.nbytes + 2 * band), DEBUG_SENTINEL, np.uint8)      # (a refused call leaves the sentinel everywhere)
+            keep.append(a)
+            alls.append(whole)
+            c.out[i].interior, c.out[i].bytes, c.out[i].band, c.out[i].all = a.ctypes.data, a.nbytes, band, whole.ctypes.data
+        rc = self.lib.rk_debug_rows(self.h, C.byref(c))
+        if check:
+            self._chk(rc)
+        del keep
+        res = {"rc": rc, "grid": tuple(c.out_grid), "tparam": c.out_tparam, "variant": c.out_variant}
+        if not plan_only:
+            res["all"] = alls
         return res
 
     def debug_xattn_chain(self, *, M: int, Ld: int, H: int, d: int, seq_off, x=None, wq=None, wk=None, wv=None, enc=None, row0=0, row_seq=None,
