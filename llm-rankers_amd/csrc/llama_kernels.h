@@ -1,5 +1,6 @@
 // Decoder-only (Llama family) kernels for gfx950: rotary position embedding and causal grouped-query attention with
-// head_dim = 128 (every Llama-2/3 size).  Everything else of the Llama forward - RMSNorm (folded), the QKV / O / gate-up /
+// head_dim = 128 (every Llama-2/3 size), and the decode step against a K / V cache for head_dim = 128 and 64 (the rest of the
+// 64-wide kernels: llama_kernels_hd64.h).  Everything else of the Llama forward - RMSNorm (folded), the QKV / O / gate-up /
 // down projections (SwiGLU epilogue), the final-token head - runs on the kernels the T5 path already uses.
 //
 // Semantics restated from hf: models/llama/modeling_llama.py: apply_rotary_pos_emb :137-160 (rotate_half pairs element i
@@ -12,7 +13,7 @@
 // The q / k / v projection bias of the Qwen2 family (hf: models/qwen2/modeling_qwen2.py: Qwen2Attention, q_proj / k_proj / v_proj
 // with bias=True): fp32, added to the fp16 GEMM output.  It cannot be folded into the weights - the QKV GEMM multiplies its
 // output by the folded RMSNorm's row factor, the bias comes after that - so it is added where the row is touched next: here (prefill)
-// and in attn_dec_cached128_kernel's row load (decode step), by THESE helpers, so that both form the same bits.
+// and in attn_dec_cached_kernel's row load (decode step), by THESE helpers, so that both form the same bits.
 __device__ __forceinline__ void bias_add8(float (&x)[8], const half8 a, const float* __restrict__ b) {
   const f32x4 b0 = *(const f32x4*)b, b1 = *(const f32x4*)(b + 4);
 #pragma unroll
@@ -520,96 +521,77 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_causal128_dma_kernel(AttnCaus
 }
 
 // =========================== incremental decoding: one new row per sequence against a K / V cache ===========================
-// rk_llama_generate keeps every layer's rotated keys and its values: per layer K [n_seq][n_kv][P][128] then V, fp16, the keys
-// of one kv head contiguous.  kv_cache_fill128_kernel copies the prompt's rows out of the prefill's fused QKV buffer (after
-// rope128_kernel); grid = (longest prompt, n_seq), a thread moves one 16-byte piece of K and of V.
-__global__ __launch_bounds__(256) void kv_cache_fill128_kernel(const half_t* __restrict__ qkv, const int* __restrict__ seq_off,
-                                                               half_t* __restrict__ kc, half_t* __restrict__ vc, int ld,
-                                                               int n_heads, int n_kv, int P) {
+// ONE kernel family for both head widths, templated on D = head_dim (128, or 64 with llama_kernels_hd64.h included).
+// rk_llama_generate keeps every layer's rotated keys and its values: per layer K [rows][n_kv][P][D] then V, fp16, the keys of one
+// kv head contiguous.  kv_cache_fill_kernel copies the prompt's rows out of the prefill's fused QKV buffer (after rope128_kernel /
+// rope64_kernel); grid = (longest prompt, n_seq), a thread moves one 16-byte piece of K and of V (D / 8 pieces per head).
+// SLOTS is the decoding session's fill (rk_llama_session_admit): the same copy, but sequence b of the call goes to cache row
+// slots[b] of a cache of n_slots rows that holds other, running rows - two 16-byte stores per thread, addresses from the slot map
+// alone.  Without SLOTS sequence b goes to row b and slots / n_slots are null / 0.
+template <int D, bool SLOTS>
+__global__ __launch_bounds__(256) void kv_cache_fill_kernel(const half_t* __restrict__ qkv, const int* __restrict__ seq_off,
+                                                            const int* __restrict__ slots, int n_slots,
+                                                            half_t* __restrict__ kc, half_t* __restrict__ vc, int ld,
+                                                            int n_heads, int n_kv, int P) {
   const int b = blockIdx.y, t = blockIdx.x;
-  const int tok0 = seq_off[b];
-  if (t >= seq_off[b + 1] - tok0 || t >= P) return;
-  const half_t* row = qkv + (size_t)(tok0 + t) * ld + (size_t)n_heads * 128;
-  for (int c = threadIdx.x; c < n_kv * 16; c += 256) {
-    const int h = c >> 4, piece = (c & 15) * 8;
-    const size_t dst = (((size_t)b * n_kv + h) * P + t) * 128 + piece;
-    *(half8*)(kc + dst) = *(const half8*)(row + h * 128 + piece);
-    *(half8*)(vc + dst) = *(const half8*)(row + (size_t)(n_kv + h) * 128 + piece);
+  const int tok0 = seq_off[b], crow = SLOTS ? slots[b] : b;
+  if (t >= seq_off[b + 1] - tok0 || t >= P || (SLOTS && (crow < 0 || crow >= n_slots))) return;
+  const half_t* row = qkv + (size_t)(tok0 + t) * ld + (size_t)n_heads * D;
+  for (int c = threadIdx.x; c < n_kv * (D / 8); c += 256) {
+    const int h = c / (D / 8), piece = (c % (D / 8)) * 8;
+    const size_t dst = (((size_t)crow * n_kv + h) * P + t) * D + piece;
+    *(half8*)(kc + dst) = *(const half8*)(row + h * D + piece);
+    *(half8*)(vc + dst) = *(const half8*)(row + (size_t)(n_kv + h) * D + piece);
   }
 }
 
-// The decoding session's fill (rk_llama_session_admit): the same copy, but sequence b of the call goes to cache row slots[b] of
-// a cache that holds other, running rows.  Two 16-byte stores per thread, addresses from the slot map alone.
-__global__ __launch_bounds__(256) void kv_cache_fill128_slots_kernel(const half_t* __restrict__ qkv, const int* __restrict__ seq_off,
-                                                                     const int* __restrict__ slots, int n_slots,
-                                                                     half_t* __restrict__ kc, half_t* __restrict__ vc, int ld,
-                                                                     int n_heads, int n_kv, int P) {
-  const int b = blockIdx.y, t = blockIdx.x;
-  const int tok0 = seq_off[b], slot = slots[b];
-  if (t >= seq_off[b + 1] - tok0 || t >= P || slot < 0 || slot >= n_slots) return;
-  const half_t* row = qkv + (size_t)(tok0 + t) * ld + (size_t)n_heads * 128;
-  for (int c = threadIdx.x; c < n_kv * 16; c += 256) {
-    const int h = c >> 4, piece = (c & 15) * 8;
-    const size_t dst = (((size_t)slot * n_kv + h) * P + t) * 128 + piece;
-    *(half8*)(kc + dst) = *(const half8*)(row + h * 128 + piece);
-    *(half8*)(vc + dst) = *(const half8*)(row + (size_t)(n_kv + h) * 128 + piece);
-  }
-}
-
-struct AttnDecCached128Args {
-  const half_t* qkv;     // [n_seq, ld]: the step's fused q | k | v rows, NOT yet rotated
-  half_t* kc;            // this layer's key cache [n_seq][n_kv][P][128]; the new key is written at the row's position
+struct LlamaDecAttnArgs {
+  const half_t* qkv;     // [rows, ld]: the step's fused q | k | v rows, NOT yet rotated
+  half_t* kc;            // this layer's key cache [rows][n_kv][P][D]; the new key is written at the row's position
   half_t* vc;            // value cache, same shape
-  const int* pos;        // [n_seq] position of the new row (device: it advances inside the replayed step graph)
-  const float* cos_t;    // rotary tables [max_pos, 64]
+  const int* pos;        // [rows] position of the new row (device: it advances inside the replayed step graph)
+  const float* cos_t;    // rotary tables [max_pos, D / 2]
   const float* sin_t;
-  float* part;           // [n_seq][n_heads][nch][LDC_PSTR]: per key chunk 128 accumulators, running maximum, sum
-  half_t* ctx;           // [n_seq, n_heads * 128]
+  float* part;           // [rows][n_heads][nch][ldc_pstr(D)]: per key chunk D accumulators, running maximum, sum
+  half_t* ctx;           // [rows, n_heads * D]
   int ld, n_heads, n_kv, P, nch;
   float scale_log2e;     // head_dim**-0.5 * log2(e)
-  const float* bias;     // Qwen2: this layer's q | k | v projection bias [(n_heads + 2 n_kv) * 128] fp32, else null
+  const float* bias;     // Qwen2: this layer's q | k | v projection bias [(n_heads + 2 n_kv) * D] fp32, else null
 };
 #define LDC_CHUNK 128    // keys per workgroup: FIXED, so the chunk boundaries of a sequence follow from its own position alone
-#define LDC_PSTR 132     // floats per partial: 128 accumulators, maximum, sum, 2 unused (16-byte rows)
+constexpr int ldc_pstr(int D) { return D + 4; }   // floats per partial: D accumulators, maximum, sum, 2 unused (16-byte rows)
 
-// Single-token attention over the cache (hf: modeling_llama.py:130-214 at one query position: scaling head_dim**-0.5, fp32
-// softmax, repeat_kv), d = 128.  grid = (key chunks of the longest cache, n_heads / R, n_seq), 256 threads.  A workgroup takes
-// ONE chunk of LDC_CHUNK keys of one kv head and R query heads that share it: with R = n_heads / n_kv_heads (Llama-3-8B: 4)
-// every K / V byte is read once per kv head.  K / V go straight to registers (no LDS staging: each byte is used once): a lane
-// holds 8 of a key's 128 dims, 16 lanes a key, a wave 4 keys per load and 32 keys in all, every load issued before the first
-// use.  The new row is rotated here (rope128_kernel's arithmetic on the same table entries), its key and value are used from
-// registers and written to the cache by the workgroup that owns the position's chunk.  Each workgroup leaves one (maximum, sum,
-// accumulator) partial per head - its four waves merged in wave order - and attn_dec_combine128_kernel merges a row's chunks
-// in key order: nobody waits on another workgroup, and a row's context depends on its own position only, never on the batch.
-// BIAS (Qwen2): the row's q / k / v get the projection bias where they are loaded - bias_add8 / bias_v8, rope128_kernel<true>'s
-// arithmetic and rounding - so the key a step writes to the cache is bit for bit the key a prefill writes for that token.
-// A head's arithmetic does not depend on R (every per-head array is indexed by r alone, the merge is per head).
-template <int R, bool BIAS>
-__device__ __forceinline__ void attn_dec_cached128_body(const AttnDecCached128Args& p) {
-  __shared__ float s_m[4][R], s_l[4][R];
-  __shared__ __attribute__((aligned(16))) float s_acc[4][R][128];
-  const int ch = blockIdx.x, h0 = blockIdx.y * R, b = blockIdx.z;
-  int pos = p.pos[b];
-  pos = pos < 0 ? 0 : (pos < p.P - 1 ? pos : p.P - 1);   // (the host keeps it inside the cache; the clamp keeps a bad word from faulting)
-  const int key0 = ch * LDC_CHUNK;
-  if (key0 > pos) return;                                 // uniform: this chunk lies beyond the row's keys
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, kg = lane >> 4, c = lane & 15;
-  const int G = p.n_heads / p.n_kv, kvh = h0 / G;
-  const half_t* row = p.qkv + (size_t)b * p.ld;
-  const int i0 = (c & 7) * 8;
-  const bool hi = c >= 8;                                 // this lane's dims are in the second half of the head
-  float co[8], si[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) { co[j] = p.cos_t[(size_t)pos * 64 + i0 + j]; si[j] = p.sin_t[(size_t)pos * 64 + i0 + j]; }
-  // this lane's 8 dims of rotated head hd (of q | k), rounded as rope128_kernel does (BIAS: the same rope_rot calls)
-  auto rotated = [&](int hd) {
-    const half_t* head = row + (size_t)hd * 128;
+__device__ __forceinline__ float row8_sum_f(float v) {   // sum over an aligned group of 8 lanes, every lane gets it; fixed order
+  v += __shfl_xor(v, 1);
+  v += __shfl_xor(v, 2);
+  v += __shfl_xor(v, 4);
+  return v;
+}
+
+template <bool BIAS>   // llama_kernels_hd64.h
+__device__ __forceinline__ void rope64_pairs(const half_t* __restrict__ head, const float* __restrict__ bias_head, int i0,
+                                             const float (&co)[8], const float (&si)[8], half8& oa, half8& ob);
+
+// The step's rotation of the new row, the one thing the two widths do differently: this lane's 8 dims (elements i0 .. i0 + 7 of
+// the first half of the head, or with `hi` their partners in the second) of rotated head hd (of q | k) of `row`, rounded as the
+// prefill's kernel of that width does, on the same table entries co / si.  D = 64: rope64_pairs, rope64_kernel's own form.
+// D = 128: rope128_kernel's arithmetic - bias-free the plain expression (the Llama kernel as it always was), BIAS bias_add8 and
+// the same rope_rot calls.
+template <int D, bool BIAS>
+__device__ __forceinline__ half8 rope_lane8(const half_t* row, const float* bias, int hd, int i0, bool hi,
+                                            const float (&co)[8], const float (&si)[8]) {
+  const half_t* head = row + (size_t)hd * D;
+  if constexpr (D == 64) {
+    half8 oa, ob;
+    rope64_pairs<BIAS>(head, BIAS ? bias + (size_t)hd * 64 : nullptr, i0, co, si, oa, ob);
+    return hi ? ob : oa;
+  } else {
     const half8 a = *(const half8*)(head + i0), bb = *(const half8*)(head + 64 + i0);
     half8 o;
     if constexpr (BIAS) {
       float xa[8], xb[8];
-      bias_add8(xa, a, p.bias + (size_t)hd * 128 + i0);
-      bias_add8(xb, bb, p.bias + (size_t)hd * 128 + 64 + i0);
+      bias_add8(xa, a, bias + (size_t)hd * 128 + i0);
+      bias_add8(xb, bb, bias + (size_t)hd * 128 + 64 + i0);
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         float lo, up;
@@ -626,16 +608,60 @@ __device__ __forceinline__ void attn_dec_cached128_body(const AttnDecCached128Ar
       }
     }
     return o;
-  };
+  }
+}
+
+// Single-token attention over the cache (hf: modeling_llama.py:130-214 at one query position: scaling head_dim**-0.5, fp32
+// softmax, repeat_kv), d = D.  grid = (key chunks of the longest cache, n_heads / R, rows), 256 threads.  The contract, for both
+// widths:
+// * FIXED chunks.  A workgroup takes ONE chunk of LDC_CHUNK keys - cut from the row's own position, whatever P and whatever the
+//   other rows hold - of one kv head and R query heads that share it: with R = n_heads / n_kv_heads (Llama-3-8B: 4) every K / V
+//   byte is read once per kv head.  K / V go straight to registers (no LDS staging: each byte is used once): a lane holds 8 of a
+//   key's D dims, D / 8 lanes a key, a wave 512 / D keys per load and 32 keys in all (D / 16 loads), every load issued before the
+//   first use.
+// * Who writes the cache.  The new row is rotated here by rope_lane8 - the arithmetic of the prefill's kernel of this width on the
+//   same table entries - its key and value are used from registers and written to the cache by the workgroup that owns the
+//   position's chunk, once per kv head.  BIAS (Qwen2): the row's q / k / v get the projection bias where they are loaded -
+//   bias_add8 / bias_v8, the prefill kernel's arithmetic and rounding.  With and without it the key a step writes to the cache is
+//   bit for bit the key a prefill writes for that token.
+// * The merge.  Each workgroup leaves one (maximum, sum, D accumulators) partial per head - its four waves merged in wave order -
+//   and attn_dec_combine_kernel merges a row's chunks in key order: nobody waits on another workgroup.
+// * Independence.  A row's context depends on its own position only, never on the batch, and a head's arithmetic does not depend
+//   on R (every per-head array is indexed by r alone, the merge is per head).
+// BIAS = false is the Llama kernel as it always was.  The sum over a key's lanes is what each width always used: row16_sum_f
+// (DPP) at 128, the three shuffles of row8_sum_f at 64.
+// (The kernel is an entry point around a body, `rotated` a lambda around rope_lane8 and the shuffles across a wave's keys are
+// written out, because that is the form the compiler in use turns into the instructions these kernels always had; the T5 step's
+// attn_dec_cached_kernel(AttnCachedArgs) in attention.h is another kernel.)
+template <int D, int R, bool BIAS>
+__device__ __forceinline__ void attn_dec_cached_body(const LlamaDecAttnArgs& p) {
+  static_assert(D == 128 || D == 64, "lanes per key 16 or 8");
+  constexpr int LK = D / 8, KL = 512 / D, NL = D / 16;   // lanes per key, keys per wave load, loads per wave
+  __shared__ float s_m[4][R], s_l[4][R];
+  __shared__ __attribute__((aligned(16))) float s_acc[4][R][D];
+  const int ch = blockIdx.x, h0 = blockIdx.y * R, b = blockIdx.z;
+  int pos = p.pos[b];
+  pos = pos < 0 ? 0 : (pos < p.P - 1 ? pos : p.P - 1);   // (the host keeps it inside the cache; the clamp keeps a bad word from faulting)
+  const int key0 = ch * LDC_CHUNK;
+  if (key0 > pos) return;                                 // uniform: this chunk lies beyond the row's keys
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, kg = lane / LK, c = lane % LK;
+  const int G = p.n_heads / p.n_kv, kvh = h0 / G;
+  const half_t* row = p.qkv + (size_t)b * p.ld;
+  const int i0 = (c % NL) * 8;
+  const bool hi = c >= NL;                                // this lane's dims are in the second half of the head
+  float co[8], si[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) { co[j] = p.cos_t[(size_t)pos * (D / 2) + i0 + j]; si[j] = p.sin_t[(size_t)pos * (D / 2) + i0 + j]; }
+  auto rotated = [&](int hd) { return rope_lane8<D, BIAS>(row, p.bias, hd, i0, hi, co, si); };
   const half8 knew = rotated(p.n_heads + kvh);
-  const size_t voff = (size_t)(p.n_heads + p.n_kv + kvh) * 128 + c * 8;
+  const size_t voff = (size_t)(p.n_heads + p.n_kv + kvh) * D + c * 8;
   half8 vnew = *(const half8*)(row + voff);
   if constexpr (BIAS) vnew = bias_v8(vnew, p.bias + voff);
-  half_t* kbase = p.kc + ((size_t)b * p.n_kv + kvh) * p.P * 128 + c * 8;
-  half_t* vbase = p.vc + ((size_t)b * p.n_kv + kvh) * p.P * 128 + c * 8;
+  half_t* kbase = p.kc + ((size_t)b * p.n_kv + kvh) * p.P * D + c * 8;
+  half_t* vbase = p.vc + ((size_t)b * p.n_kv + kvh) * p.P * D + c * 8;
   if (pos - key0 < LDC_CHUNK && h0 % G == 0 && wave == 0 && kg == 0) {   // the position's chunk, once per kv head
-    *(half8*)(kbase + (size_t)pos * 128) = knew;
-    *(half8*)(vbase + (size_t)pos * 128) = vnew;
+    *(half8*)(kbase + (size_t)pos * D) = knew;
+    *(half8*)(vbase + (size_t)pos * D) = vnew;
   }
   const int wkey0 = key0 + wave * 32;
   float m_w[R], l_w[R], acc[R][8];
@@ -646,53 +672,57 @@ __device__ __forceinline__ void attn_dec_cached128_body(const AttnDecCached128Ar
     for (int j = 0; j < 8; ++j) acc[r][j] = 0.f;
   }
   if (wkey0 <= pos) {                                     // wave-uniform
-    half8 kf[8], vf[8];
+    half8 kf[NL], vf[NL];
     const int last_old = pos > 0 ? pos - 1 : 0;           // keys before the new one come from the cache
 #pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      const int key = wkey0 + 4 * i + kg;
+    for (int i = 0; i < NL; ++i) {
+      const int key = wkey0 + KL * i + kg;
       const int idx = key < last_old ? key : last_old;
-      kf[i] = *(const half8*)(kbase + (size_t)idx * 128);
-      vf[i] = *(const half8*)(vbase + (size_t)idx * 128);
+      kf[i] = *(const half8*)(kbase + (size_t)idx * D);
+      vf[i] = *(const half8*)(vbase + (size_t)idx * D);
     }
 #pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      const bool is_new = wkey0 + 4 * i + kg >= pos;
+    for (int i = 0; i < NL; ++i) {
+      const bool is_new = wkey0 + KL * i + kg >= pos;
       kf[i] = is_new ? knew : kf[i];
       vf[i] = is_new ? vnew : vf[i];
     }
-    float s[R][8];
+    float s[R][NL];
 #pragma unroll
     for (int r = 0; r < R; ++r) {
       const half8 q = rotated(h0 + r);
 #pragma unroll
-      for (int i = 0; i < 8; ++i) {
+      for (int i = 0; i < NL; ++i) {
         float d = 0.f;
 #pragma unroll
         for (int j = 0; j < 8; ++j) d = __builtin_fmaf((float)q[j], (float)kf[i][j], d);
-        d = row16_sum_f(d) * p.scale_log2e;
-        s[r][i] = wkey0 + 4 * i + kg <= pos ? d : -1e30f;
+        if constexpr (D == 128) d = row16_sum_f(d) * p.scale_log2e;
+        else d = row8_sum_f(d) * p.scale_log2e;
+        s[r][i] = wkey0 + KL * i + kg <= pos ? d : -1e30f;
       }
     }
 #pragma unroll
     for (int r = 0; r < R; ++r) {
       float mx = s[r][0];
 #pragma unroll
-      for (int i = 1; i < 8; ++i) mx = fmaxf(mx, s[r][i]);
+      for (int i = 1; i < NL; ++i) mx = fmaxf(mx, s[r][i]);
+      if constexpr (LK == 8) mx = fmaxf(mx, __shfl_xor(mx, 8));   // across the wave's keys: lanes LK, 2 LK .. 32 apart, in that order
       mx = fmaxf(mx, __shfl_xor(mx, 16));
       mx = fmaxf(mx, __shfl_xor(mx, 32));
       float sum = 0.f;
 #pragma unroll
-      for (int i = 0; i < 8; ++i) {
+      for (int i = 0; i < NL; ++i) {
         const float pr = __builtin_amdgcn_exp2f(s[r][i] - mx);   // masked keys: exp2(-1e30) = 0
         sum += pr;
 #pragma unroll
         for (int j = 0; j < 8; ++j) acc[r][j] = __builtin_fmaf(pr, (float)vf[i][j], acc[r][j]);
       }
+      if constexpr (LK == 8) sum += __shfl_xor(sum, 8);
       sum += __shfl_xor(sum, 16);
       sum += __shfl_xor(sum, 32);
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
+        if constexpr (LK == 8) acc[r][j] += __shfl_xor(acc[r][j], 8);
         acc[r][j] += __shfl_xor(acc[r][j], 16);
         acc[r][j] += __shfl_xor(acc[r][j], 32);
       }
@@ -708,7 +738,7 @@ __device__ __forceinline__ void attn_dec_cached128_body(const AttnDecCached128Ar
     }
   }
   __syncthreads();
-  if (tid < 128) {                                        // the four waves' partials, merged in wave order
+  if (tid < D) {                                          // the four waves' partials, merged in wave order
 #pragma unroll
     for (int r = 0; r < R; ++r) {
       const float M = fmaxf(fmaxf(s_m[0][r], s_m[1][r]), fmaxf(s_m[2][r], s_m[3][r]));
@@ -719,34 +749,32 @@ __device__ __forceinline__ void attn_dec_cached128_body(const AttnDecCached128Ar
         L = __builtin_fmaf(s_l[w][r], f, L);
         A = __builtin_fmaf(s_acc[w][r][tid], f, A);
       }
-      float* dst = p.part + (((size_t)b * p.n_heads + h0 + r) * p.nch + ch) * LDC_PSTR;
+      float* dst = p.part + (((size_t)b * p.n_heads + h0 + r) * p.nch + ch) * ldc_pstr(D);
       dst[tid] = A;
-      if (tid == 0) { dst[128] = M; dst[129] = L; }
+      if (tid == 0) { dst[D] = M; dst[D + 1] = L; }
     }
   }
 }
 
-// the two entry points of the body above: the bias-free kernel (Llama: the kernel as it always was) and the Qwen2 one
-template <int R>
-__global__ __launch_bounds__(256) void attn_dec_cached128_kernel(AttnDecCached128Args p) { attn_dec_cached128_body<R, false>(p); }
-template <int R>
-__global__ __launch_bounds__(256) void attn_dec_cached128_bias_kernel(AttnDecCached128Args p) { attn_dec_cached128_body<R, true>(p); }
+template <int D, int R, bool BIAS>
+__global__ __launch_bounds__(256) void attn_dec_cached_kernel(LlamaDecAttnArgs p) { attn_dec_cached_body<D, R, BIAS>(p); }
 
-// Merges the chunk partials of one (sequence, head) in key order and writes the fp16 context.  grid = (n_heads, n_seq), 128
-// threads = the head's 128 dims.
-__global__ __launch_bounds__(128) void attn_dec_combine128_kernel(AttnDecCached128Args p) {
+// Merges the chunk partials of one (sequence, head) in key order and writes the fp16 context.  grid = (n_heads, rows), D
+// threads = the head's D dims.
+template <int D>
+__global__ __launch_bounds__(D) void attn_dec_combine_kernel(LlamaDecAttnArgs p) {
   const int h = blockIdx.x, b = blockIdx.y, d = threadIdx.x;
   int pos = p.pos[b];
   pos = pos < 0 ? 0 : (pos < p.P - 1 ? pos : p.P - 1);
   const int n = pos / LDC_CHUNK + 1;
-  const float* src = p.part + ((size_t)b * p.n_heads + h) * p.nch * LDC_PSTR;
+  const float* src = p.part + ((size_t)b * p.n_heads + h) * p.nch * ldc_pstr(D);
   float M = -1e30f;
-  for (int k = 0; k < n; ++k) M = fmaxf(M, src[(size_t)k * LDC_PSTR + 128]);
+  for (int k = 0; k < n; ++k) M = fmaxf(M, src[(size_t)k * ldc_pstr(D) + D]);
   float L = 0.f, A = 0.f;
   for (int k = 0; k < n; ++k) {
-    const float f = __builtin_amdgcn_exp2f(src[(size_t)k * LDC_PSTR + 128] - M);
-    L = __builtin_fmaf(src[(size_t)k * LDC_PSTR + 129], f, L);
-    A = __builtin_fmaf(src[(size_t)k * LDC_PSTR + d], f, A);
+    const float f = __builtin_amdgcn_exp2f(src[(size_t)k * ldc_pstr(D) + D] - M);
+    L = __builtin_fmaf(src[(size_t)k * ldc_pstr(D) + D + 1], f, L);
+    A = __builtin_fmaf(src[(size_t)k * ldc_pstr(D) + d], f, A);
   }
-  p.ctx[(size_t)b * p.n_heads * 128 + h * 128 + d] = f2h_sat(A / L);   // a row always sees its own key: L > 0
+  p.ctx[(size_t)b * p.n_heads * D + h * D + d] = f2h_sat(A / L);   // a row always sees its own key: L > 0
 }

@@ -1,12 +1,14 @@
 // Decoder-only (Llama / Qwen2 family) kernels for gfx950 at head_dim = 64: Llama-3.2-1B, TinyLlama-1.1B, SmolLM2, Qwen2.5-0.5B.
 // The semantics are the ones quoted at the top of llama_kernels.h at this width: rotate_half pairs element i with i + 32, scaling
-// = 64**-0.5, rotary tables [max_pos][32], causal mask, fp32 softmax, repeat_kv.  The 128-wide kernels of llama_kernels.h are not
-// touched by anything here; what does not see the head width (bias_add8 / bias_v8 / rope_rot, AttnCausalArgs, LDC_CHUNK) is theirs.
+// = 64**-0.5, rotary tables [max_pos][32], causal mask, fp32 softmax, repeat_kv.  Here is what is this width's own: the rotation
+// and the prefill attention.  The 128-wide kernels of llama_kernels.h are not touched by anything here; what does not see the
+// head width (bias_add8 / bias_v8 / rope_rot, AttnCausalArgs) is theirs, and so is the decode step (cache fill, cached attention,
+// combine), one family templated on the width that rotates a 64-wide row by rope64_pairs below.
 #pragma once
 #include "llama_kernels.h"
 
 // The 8 rotated pairs a thread owns (elements i0 .. i0 + 7 of a head's first half and their partners 32 further), in ONE form for
-// the prefill (rope64_kernel) and the step (attn_dec_cached64_body), with and without the Qwen2 bias: fp32 sum of the fp16 GEMM
+// the prefill (rope64_kernel) and the step (attn_dec_cached_kernel<64>), with and without the Qwen2 bias: fp32 sum of the fp16 GEMM
 // output and the bias (bias-free: + 0.0f, which is what an all-zero bias adds - so "an all-zero bias gives the bias-free bits" holds
 // by construction, not by what a compiler contracts), then rope_rot's fused form for every pair, then ONE fp16 rounding.
 template <bool BIAS>
@@ -199,208 +201,4 @@ __global__ __launch_bounds__(256) void attn_causal64_kernel(AttnCausalArgs p) {
         *(half4*)(dst + f * 32 + 8 * q + 4 * hh) = a;
       }
   }
-}
-
-// =========================== incremental decoding: one new row per sequence against a K / V cache ===========================
-// Per layer K [rows][n_kv][P][64] then V, fp16, the keys of one kv head contiguous.  kv_cache_fill64_kernel copies the prompt's
-// rows out of the prefill's fused QKV buffer (after rope64_kernel); grid = (longest prompt, n_seq), a thread moves one 16-byte
-// piece of K and of V.
-__global__ __launch_bounds__(256) void kv_cache_fill64_kernel(const half_t* __restrict__ qkv, const int* __restrict__ seq_off,
-                                                              half_t* __restrict__ kc, half_t* __restrict__ vc, int ld,
-                                                              int n_heads, int n_kv, int P) {
-  const int b = blockIdx.y, t = blockIdx.x;
-  const int tok0 = seq_off[b];
-  if (t >= seq_off[b + 1] - tok0 || t >= P) return;
-  const half_t* row = qkv + (size_t)(tok0 + t) * ld + (size_t)n_heads * 64;
-  for (int c = threadIdx.x; c < n_kv * 8; c += 256) {
-    const int h = c >> 3, piece = (c & 7) * 8;
-    const size_t dst = (((size_t)b * n_kv + h) * P + t) * 64 + piece;
-    *(half8*)(kc + dst) = *(const half8*)(row + h * 64 + piece);
-    *(half8*)(vc + dst) = *(const half8*)(row + (size_t)(n_kv + h) * 64 + piece);
-  }
-}
-
-// The decoding session's fill (rk_llama_session_admit): sequence b of the call goes to cache row slots[b].
-__global__ __launch_bounds__(256) void kv_cache_fill64_slots_kernel(const half_t* __restrict__ qkv, const int* __restrict__ seq_off,
-                                                                    const int* __restrict__ slots, int n_slots,
-                                                                    half_t* __restrict__ kc, half_t* __restrict__ vc, int ld,
-                                                                    int n_heads, int n_kv, int P) {
-  const int b = blockIdx.y, t = blockIdx.x;
-  const int tok0 = seq_off[b], slot = slots[b];
-  if (t >= seq_off[b + 1] - tok0 || t >= P || slot < 0 || slot >= n_slots) return;
-  const half_t* row = qkv + (size_t)(tok0 + t) * ld + (size_t)n_heads * 64;
-  for (int c = threadIdx.x; c < n_kv * 8; c += 256) {
-    const int h = c >> 3, piece = (c & 7) * 8;
-    const size_t dst = (((size_t)slot * n_kv + h) * P + t) * 64 + piece;
-    *(half8*)(kc + dst) = *(const half8*)(row + h * 64 + piece);
-    *(half8*)(vc + dst) = *(const half8*)(row + (size_t)(n_kv + h) * 64 + piece);
-  }
-}
-
-#define LDC64_PSTR 68    // floats per partial of a 64-wide head: 64 accumulators, maximum, sum, 2 unused (16-byte rows)
-
-__device__ __forceinline__ float row8_sum_f(float v) {   // sum over an aligned group of 8 lanes, every lane gets it; fixed order
-  v += __shfl_xor(v, 1);
-  v += __shfl_xor(v, 2);
-  v += __shfl_xor(v, 4);
-  return v;
-}
-
-// Single-token attention over the cache, d = 64: the contract of attn_dec_cached128_body (AttnDecCached128Args with every 128
-// read as 64: caches [rows][n_kv][P][64], tables [max_pos][32], bias [(n_heads + 2 n_kv) * 64], part [rows][n_heads][nch][LDC64_PSTR],
-// ctx [rows, n_heads * 64]).  grid = (key chunks of the longest cache, n_heads / R, rows), 256 threads.  A workgroup takes ONE
-// chunk of LDC_CHUNK keys - FIXED, cut from the row's own position - of one kv head and R query heads that share it.  K / V go
-// straight to registers: a lane holds 8 of a key's 64 dims, 8 lanes a key, a wave 8 keys per load and 32 keys in all, every load
-// issued before the first use.  The new row is rotated here by rope64_pairs - rope64_kernel's arithmetic on the same table
-// entries, so the key a step writes is bit for bit the key a prefill writes for that token - and its key and value are written
-// by the workgroup that owns the position's chunk, once per kv head.  Each workgroup leaves one (maximum, sum, 64 accumulators)
-// partial per head - its four waves merged in wave order - and attn_dec_combine64_kernel merges a row's chunks in key order.
-// A head's arithmetic does not depend on R (every per-head array is indexed by r alone, the merge is per head).
-template <int R, bool BIAS>
-__device__ __forceinline__ void attn_dec_cached64_body(const AttnDecCached128Args& p) {
-  __shared__ float s_m[4][R], s_l[4][R];
-  __shared__ __attribute__((aligned(16))) float s_acc[4][R][64];
-  const int ch = blockIdx.x, h0 = blockIdx.y * R, b = blockIdx.z;
-  int pos = p.pos[b];
-  pos = pos < 0 ? 0 : (pos < p.P - 1 ? pos : p.P - 1);   // (the host keeps it inside the cache; the clamp keeps a bad word from faulting)
-  const int key0 = ch * LDC_CHUNK;
-  if (key0 > pos) return;                                 // uniform: this chunk lies beyond the row's keys
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, kg = lane >> 3, c = lane & 7;
-  const int G = p.n_heads / p.n_kv, kvh = h0 / G;
-  const half_t* row = p.qkv + (size_t)b * p.ld;
-  const int i0 = (c & 3) * 8;
-  const bool hi = c >= 4;                                 // this lane's dims are in the second half of the head
-  float co[8], si[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) { co[j] = p.cos_t[(size_t)pos * 32 + i0 + j]; si[j] = p.sin_t[(size_t)pos * 32 + i0 + j]; }
-  // this lane's 8 dims of rotated head hd (of q | k), rounded as rope64_kernel does
-  auto rotated = [&](int hd) {
-    half8 oa, ob;
-    rope64_pairs<BIAS>(row + (size_t)hd * 64, BIAS ? p.bias + (size_t)hd * 64 : nullptr, i0, co, si, oa, ob);
-    return hi ? ob : oa;
-  };
-  const half8 knew = rotated(p.n_heads + kvh);
-  const size_t voff = (size_t)(p.n_heads + p.n_kv + kvh) * 64 + c * 8;
-  half8 vnew = *(const half8*)(row + voff);
-  if constexpr (BIAS) vnew = bias_v8(vnew, p.bias + voff);
-  half_t* kbase = p.kc + ((size_t)b * p.n_kv + kvh) * p.P * 64 + c * 8;
-  half_t* vbase = p.vc + ((size_t)b * p.n_kv + kvh) * p.P * 64 + c * 8;
-  if (pos - key0 < LDC_CHUNK && h0 % G == 0 && wave == 0 && kg == 0) {   // the position's chunk, once per kv head
-    *(half8*)(kbase + (size_t)pos * 64) = knew;
-    *(half8*)(vbase + (size_t)pos * 64) = vnew;
-  }
-  const int wkey0 = key0 + wave * 32;
-  float m_w[R], l_w[R], acc[R][8];
-#pragma unroll
-  for (int r = 0; r < R; ++r) {
-    m_w[r] = -1e30f; l_w[r] = 0.f;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) acc[r][j] = 0.f;
-  }
-  if (wkey0 <= pos) {                                     // wave-uniform
-    half8 kf[4], vf[4];
-    const int last_old = pos > 0 ? pos - 1 : 0;           // keys before the new one come from the cache
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int key = wkey0 + 8 * i + kg;
-      const int idx = key < last_old ? key : last_old;
-      kf[i] = *(const half8*)(kbase + (size_t)idx * 64);
-      vf[i] = *(const half8*)(vbase + (size_t)idx * 64);
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const bool is_new = wkey0 + 8 * i + kg >= pos;
-      kf[i] = is_new ? knew : kf[i];
-      vf[i] = is_new ? vnew : vf[i];
-    }
-    float s[R][4];
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      const half8 q = rotated(h0 + r);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        float d = 0.f;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) d = __builtin_fmaf((float)q[j], (float)kf[i][j], d);
-        d = row8_sum_f(d) * p.scale_log2e;
-        s[r][i] = wkey0 + 8 * i + kg <= pos ? d : -1e30f;
-      }
-    }
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      float mx = s[r][0];
-#pragma unroll
-      for (int i = 1; i < 4; ++i) mx = fmaxf(mx, s[r][i]);
-      mx = fmaxf(mx, __shfl_xor(mx, 8));
-      mx = fmaxf(mx, __shfl_xor(mx, 16));
-      mx = fmaxf(mx, __shfl_xor(mx, 32));
-      float sum = 0.f;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const float pr = __builtin_amdgcn_exp2f(s[r][i] - mx);   // masked keys: exp2(-1e30) = 0
-        sum += pr;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) acc[r][j] = __builtin_fmaf(pr, (float)vf[i][j], acc[r][j]);
-      }
-      sum += __shfl_xor(sum, 8);
-      sum += __shfl_xor(sum, 16);
-      sum += __shfl_xor(sum, 32);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        acc[r][j] += __shfl_xor(acc[r][j], 8);
-        acc[r][j] += __shfl_xor(acc[r][j], 16);
-        acc[r][j] += __shfl_xor(acc[r][j], 32);
-      }
-      m_w[r] = mx; l_w[r] = sum;
-    }
-  }
-  if (kg == 0) {
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      *(f32x4*)&s_acc[wave][r][c * 8] = f32x4{acc[r][0], acc[r][1], acc[r][2], acc[r][3]};
-      *(f32x4*)&s_acc[wave][r][c * 8 + 4] = f32x4{acc[r][4], acc[r][5], acc[r][6], acc[r][7]};
-      if (c == 0) { s_m[wave][r] = m_w[r]; s_l[wave][r] = l_w[r]; }
-    }
-  }
-  __syncthreads();
-  if (tid < 64) {                                         // the four waves' partials, merged in wave order
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      const float M = fmaxf(fmaxf(s_m[0][r], s_m[1][r]), fmaxf(s_m[2][r], s_m[3][r]));
-      float L = 0.f, A = 0.f;
-#pragma unroll
-      for (int w = 0; w < 4; ++w) {
-        const float f = __builtin_amdgcn_exp2f(s_m[w][r] - M);
-        L = __builtin_fmaf(s_l[w][r], f, L);
-        A = __builtin_fmaf(s_acc[w][r][tid], f, A);
-      }
-      float* dst = p.part + (((size_t)b * p.n_heads + h0 + r) * p.nch + ch) * LDC64_PSTR;
-      dst[tid] = A;
-      if (tid == 0) { dst[64] = M; dst[65] = L; }
-    }
-  }
-}
-
-template <int R>
-__global__ __launch_bounds__(256) void attn_dec_cached64_kernel(AttnDecCached128Args p) { attn_dec_cached64_body<R, false>(p); }
-template <int R>
-__global__ __launch_bounds__(256) void attn_dec_cached64_bias_kernel(AttnDecCached128Args p) { attn_dec_cached64_body<R, true>(p); }
-
-// Merges the chunk partials of one (sequence, head) in key order and writes the fp16 context.  grid = (n_heads, rows), 64
-// threads = the head's 64 dims.
-__global__ __launch_bounds__(64) void attn_dec_combine64_kernel(AttnDecCached128Args p) {
-  const int h = blockIdx.x, b = blockIdx.y, d = threadIdx.x;
-  int pos = p.pos[b];
-  pos = pos < 0 ? 0 : (pos < p.P - 1 ? pos : p.P - 1);
-  const int n = pos / LDC_CHUNK + 1;
-  const float* src = p.part + ((size_t)b * p.n_heads + h) * p.nch * LDC64_PSTR;
-  float M = -1e30f;
-  for (int k = 0; k < n; ++k) M = fmaxf(M, src[(size_t)k * LDC64_PSTR + 64]);
-  float L = 0.f, A = 0.f;
-  for (int k = 0; k < n; ++k) {
-    const float f = __builtin_amdgcn_exp2f(src[(size_t)k * LDC64_PSTR + 64] - M);
-    L = __builtin_fmaf(src[(size_t)k * LDC64_PSTR + 65], f, L);
-    A = __builtin_fmaf(src[(size_t)k * LDC64_PSTR + d], f, A);
-  }
-  p.ctx[(size_t)b * p.n_heads * 64 + h * 64 + d] = f2h_sat(A / L);   // a row always sees its own key: L > 0
 }

@@ -14,6 +14,7 @@
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <map>
 #include <atomic>
@@ -640,6 +641,14 @@ void with_epi(int epi, F&& f) {
   else if constexpr (E < EPI_LSE_F32) with_epi<E + 1>(epi, f);
 }
 
+// f(std::integral_constant<int, head width>): the one map from a decoder-only engine's head width (64, else 128) to the
+// width-templated decode kernels
+template <class F>
+void with_width(int hd, F&& f) {
+  if (hd == 64) f(std::integral_constant<int, 64>());
+  else f(std::integral_constant<int, 128>());
+}
+
 // Runs plan_gemm's plan of the call.  *nb (optional): the plan's statistics layout, for the GEMMs that read what this one produced.
 int gemm(rk_engine* e, hipStream_t st, const Gemm& c, int* nb = nullptr) {
   if (c.M <= 0) return RK_OK;
@@ -721,10 +730,11 @@ void launch_rope(hipStream_t st, int hd, half_t* qkv, const int* pos, const floa
 void launch_kv_fill(hipStream_t st, int hd, const half_t* qkv, const int* seq_off, const int* slots, int n_slots, half_t* kc, half_t* vc,
                     int ld, int n_heads, int n_kv, int P, int maxL, int n_seq) {
   const dim3 g = grid_kv_fill(maxL, n_seq), b(256);
-  if (hd == 64 && slots) hipLaunchKernelGGL(kv_cache_fill64_slots_kernel, g, b, 0, st, qkv, seq_off, slots, n_slots, kc, vc, ld, n_heads, n_kv, P);
-  else if (hd == 64) hipLaunchKernelGGL(kv_cache_fill64_kernel, g, b, 0, st, qkv, seq_off, kc, vc, ld, n_heads, n_kv, P);
-  else if (slots) hipLaunchKernelGGL(kv_cache_fill128_slots_kernel, g, b, 0, st, qkv, seq_off, slots, n_slots, kc, vc, ld, n_heads, n_kv, P);
-  else hipLaunchKernelGGL(kv_cache_fill128_kernel, g, b, 0, st, qkv, seq_off, kc, vc, ld, n_heads, n_kv, P);
+  with_width(hd, [&](auto W) {
+    constexpr int D = decltype(W)::value;
+    if (slots) hipLaunchKernelGGL((kv_cache_fill_kernel<D, true>), g, b, 0, st, qkv, seq_off, slots, n_slots, kc, vc, ld, n_heads, n_kv, P);
+    else hipLaunchKernelGGL((kv_cache_fill_kernel<D, false>), g, b, 0, st, qkv, seq_off, (const int*)nullptr, 0, kc, vc, ld, n_heads, n_kv, P);
+  });
 }
 void launch_greedy_advance(hipStream_t st, const int* argmax, int* state, const int* prefix, int* done, int* out, int* next_ids, int n_seq,
                            int dec_len, int max_new) {
@@ -1197,12 +1207,12 @@ void launch_llama_attn(rk_engine* e, hipStream_t st, const CausalAttnCall& c, co
 // Single-token attention of one rk_llama_generate step over the K / V cache of P positions per sequence: the chunk kernel over
 // (key chunks of P, groups of R query heads, rows), then the merge per (head, row).  R = the largest of 8 / 4 / 2 / 1 that divides
 // the query heads per kv head G (Llama-3-8B: 4): a model constant, so a row's bits never depend on the call.  Nor do they depend
-// on R: a head's arithmetic in attn_dec_cached128_kernel indexes every per-head array by r alone and the merge is per head.
+// on R: a head's arithmetic in attn_dec_cached_kernel indexes every per-head array by r alone and the merge is per head.
 // R = G = 7 (Qwen2.5-7B: 28 heads on 4, R = 1 by the rule, every cached byte read 7 times) has an instantiation of its own behind
 // option llama_dec_r = 2 (measurement and tests only; G = 6 / 5 / 3 were not measured and have none), but is NOT the rule: measured at Qwen2.5-7B widths it lost at one row (6.19 against 5.95 ms
 // per token: 17 chunks x 4 kv heads = 68 workgroups on 256 CUs, where R = 1 has 476 and L2 serves the re-reads) and only tied
 // at eight rows (7.60 / 7.65; profiles/rankr1_bench.txt).  llama_dec_r = 1 forces R = 1.  Same bits whichever (tests).
-// A 64-wide engine (llama_kernels_hd64.h) follows the same rule with the same chunk length; it has no R = 7 instantiation, so
+// A 64-wide engine runs the same kernels at D = 64 by the same rule with the same chunk length; it has no R = 7 instantiation, so
 // llama_dec_r = 2 falls back to the rule there.
 struct LlamaDecAttnPlan { int R = 1, nch = 1, hd = 128; dim3 grid, cgrid; };
 LlamaDecAttnPlan plan_llama_dec_attn(const rk_engine* e, int rows, int P, int n_heads, int n_kv) {
@@ -1218,39 +1228,27 @@ LlamaDecAttnPlan plan_llama_dec_attn(const rk_engine* e, int rows, int P, int n_
   return p;
 }
 
-void launch_llama_dec_attn(rk_engine* e, hipStream_t st, const LlamaDecAttnPlan& p, AttnDecCached128Args a, int rows) {
+void launch_llama_dec_attn(rk_engine* e, hipStream_t st, const LlamaDecAttnPlan& p, LlamaDecAttnArgs a, int rows) {
   a.nch = p.nch;
   Bracket br(e, st, PC_DEC_ATTN, 4.0 * rows * (double)a.P * a.n_heads * p.hd, 2.0 * rows * (double)a.P * a.n_kv * p.hd * 2.0);
-  if (p.hd == 64) {
-    auto go64 = [&](auto rc) {
+  with_width(p.hd, [&](auto W) {
+    constexpr int D = decltype(W)::value;
+    auto go = [&](auto rc) {                                 // the bias-free instantiation is the Llama kernel as it was
       constexpr int R = decltype(rc)::value;
-      if (a.bias) hipLaunchKernelGGL(attn_dec_cached64_bias_kernel<R>, p.grid, dim3(256), 0, st, a);
-      else hipLaunchKernelGGL(attn_dec_cached64_kernel<R>, p.grid, dim3(256), 0, st, a);
+      if constexpr (R == 7 && D != 128) abort();             // no such kernel: plan_llama_dec_attn gives R = 7 at 128 alone
+      else if (a.bias) hipLaunchKernelGGL((attn_dec_cached_kernel<D, R, true>), p.grid, dim3(256), 0, st, a);
+      else hipLaunchKernelGGL((attn_dec_cached_kernel<D, R, false>), p.grid, dim3(256), 0, st, a);
     };
     using std::integral_constant;
     switch (p.R) {
-      case 8: go64(integral_constant<int, 8>{}); break;
-      case 4: go64(integral_constant<int, 4>{}); break;
-      case 2: go64(integral_constant<int, 2>{}); break;
-      default: go64(integral_constant<int, 1>{}); break;
+      case 8: go(integral_constant<int, 8>{}); break;
+      case 7: go(integral_constant<int, 7>{}); break;
+      case 4: go(integral_constant<int, 4>{}); break;
+      case 2: go(integral_constant<int, 2>{}); break;
+      default: go(integral_constant<int, 1>{}); break;
     }
-    hipLaunchKernelGGL(attn_dec_combine64_kernel, p.cgrid, dim3(64), 0, st, a);
-    return;
-  }
-  auto go = [&](auto rc) {                                   // the bias-free instantiation is the Llama kernel as it was
-    constexpr int R = decltype(rc)::value;
-    if (a.bias) hipLaunchKernelGGL(attn_dec_cached128_bias_kernel<R>, p.grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL(attn_dec_cached128_kernel<R>, p.grid, dim3(256), 0, st, a);
-  };
-  using std::integral_constant;
-  switch (p.R) {
-    case 8: go(integral_constant<int, 8>{}); break;
-    case 7: go(integral_constant<int, 7>{}); break;
-    case 4: go(integral_constant<int, 4>{}); break;
-    case 2: go(integral_constant<int, 2>{}); break;
-    default: go(integral_constant<int, 1>{}); break;
-  }
-  hipLaunchKernelGGL(attn_dec_combine128_kernel, p.cgrid, dim3(128), 0, st, a);
+    hipLaunchKernelGGL(attn_dec_combine_kernel<D>, p.cgrid, dim3(D), 0, st, a);
+  });
 }
 
 // hf: modeling_t5.py:663-750 (T5Stack.forward, encoder) over the slot's staged ragged batch, then the stacked
@@ -2760,7 +2758,7 @@ static int ensure_llama_gen(rk_engine* e, int n_seq, int P, size_t ints) {
   const rk_llama_desc& l = e->ld;
   const size_t S = (size_t)l.max_seqs, dm = l.hidden, Q = (size_t)l.n_heads * l.head_dim, KV = (size_t)l.n_kv_heads * l.head_dim, F = l.intermediate;
   const size_t kv = (size_t)l.n_layers * 2 * n_seq * KV * P;
-  const size_t part = (size_t)n_seq * l.n_heads * ((P + LDC_CHUNK - 1) / LDC_CHUNK) * (l.head_dim == 64 ? LDC64_PSTR : LDC_PSTR);
+  const size_t part = (size_t)n_seq * l.n_heads * ((P + LDC_CHUNK - 1) / LDC_CHUNK) * ldc_pstr(l.head_dim);
   int rc = RK_OK;
   RC(e->lkv.reserve(e, kv, &e->lkv_gen)); RC(e->lpart.reserve(e, part, &e->lkv_gen)); RC(e->lints.reserve(e, ints, &e->lkv_gen));
   if (!e->lg.stream.hidden) {
@@ -2772,7 +2770,7 @@ static int ensure_llama_gen(rk_engine* e, int n_seq, int P, size_t ints) {
 }
 
 // One decoding step over `rows` cache rows of P positions each (rk_llama_generate's rows, a session's slots), up to the final
-// norm: the embedding of next[rows], per layer QKV (folded norm) -> attn_dec_cached128_kernel at pos[rows] -> o + residual ->
+// norm: the embedding of next[rows], per layer QKV (folded norm) -> attn_dec_cached_kernel at pos[rows] -> o + residual ->
 // gate|up + SwiGLU -> down + residual, then the final-normed rows in slots[0].dlast.  The cache, the partials and the activation
 // rows are the engine's (ensure_llama_gen).  Nothing here depends on which rows are live: a row's bits follow from its own
 // tokens and position.
@@ -2793,7 +2791,7 @@ static int llama_step_rows(rk_engine* e, hipStream_t st, int rows, int P, const 
     const LlamaLayerW& w = e->ll[i];
     RC(gemm(e, st, normed(Gemm(PC_DEC_GEMM, EPI_STORE_F16, ns.x(), dm, w.qkv_f, dm, lg.qkv, ldq, rows, ldq, dm))));
     half_t* kc = e->lkv.p + (size_t)i * 2 * half_layer;
-    launch_llama_dec_attn(e, st, ap, AttnDecCached128Args{lg.qkv, kc, kc + half_layer, d_pos, e->rope_cos, e->rope_sin, e->lpart.p, lg.ctx,
+    launch_llama_dec_attn(e, st, ap, LlamaDecAttnArgs{lg.qkv, kc, kc + half_layer, d_pos, e->rope_cos, e->rope_sin, e->lpart.p, lg.ctx,
                                                           ldq, l.n_heads, l.n_kv_heads, P, ap.nch, scale_log2e, w.qkv_bias}, rows);
     RC(ns.producer(e, st, Gemm(PC_DEC_GEMM, EPI_RESID_F32, lg.ctx, Q, w.o, Q, ns.hidden, dm, rows, dm, Q).on(GEMM_STREAM)));
     RC(gemm(e, st, normed(Gemm(PC_DEC_GEMM, EPI_SWIGLU_F16, ns.x(), dm, w.gu_f, dm, lg.ffh, F, rows, 2 * F, dm))));
@@ -2805,7 +2803,7 @@ static int llama_step_rows(rk_engine* e, hipStream_t st, int rows, int P, const 
 
 // Greedy continuation with a K / V cache (hf: generation/utils.py greedy loop over LlamaForCausalLM with use_cache): the prefill
 // once, keeping every layer's rotated K and its V; column 0 = the prefill's arg-max (rk_llama_greedy1's token); then ONE new row
-// per sequence and step: embedding of the fed-back token, per layer QKV (folded norm) -> attn_dec_cached128_kernel -> o + residual
+// per sequence and step: embedding of the fed-back token, per layer QKV (folded norm) -> attn_dec_cached_kernel -> o + residual
 // -> gate|up + SwiGLU -> down + residual, final norm, arg-max head, llama_advance_kernel.  Every projection runs on the
 // weight-streaming family (the caller's regime, never the row count: a row's tokens do not depend on what shares the call).  The
 // step is one graph per (rows, P, cache generation), replayed; position, finished rows and next ids live on the device; the host
@@ -3656,13 +3654,13 @@ int rk_debug_attn(rk_engine* e, rk_debug_attn_call* q) {
     float* dCos = (float*)up(q->cos_t, (size_t)q->max_pos * (hd / 2) * 4);
     float* dSin = (float*)up(q->sin_t, (size_t)q->max_pos * (hd / 2) * 4);
     float* dBias = q->qkv_bias ? (float*)up(q->qkv_bias, (size_t)(H + 2 * q->n_kv) * hd * 4) : nullptr;
-    float* dPart = (float*)alloc((size_t)B * H * lp.nch * (hd == 64 ? LDC64_PSTR : LDC_PSTR) * 4, RK_DEBUG_SENTINEL);
+    float* dPart = (float*)alloc((size_t)B * H * lp.nch * ldc_pstr(hd) * 4, RK_DEBUG_SENTINEL);
     if (!dC || !dPos || !dCos || !dSin || (q->qkv_bias && !dBias) || !dPart) return done(fail(e, RK_ERR_HIP, "debug attn: device allocation or upload failed"));
     DBG_HIP(hipMemcpy(dC + c_band, q->cache, 2 * half_layer * 2, hipMemcpyHostToDevice));
     DBG_HIP(hipDeviceSynchronize());
     const float scale_log2e = (1.0f / std::sqrt((float)hd)) * 1.4426950408889634f;
     half_t* kc = dC + c_band;
-    launch_llama_dec_attn(e, st, lp, AttnDecCached128Args{qi, kc, kc + half_layer, dPos, dCos, dSin, dPart, oi, q->ldq, H, q->n_kv, q->P, lp.nch, scale_log2e, dBias}, B);
+    launch_llama_dec_attn(e, st, lp, LlamaDecAttnArgs{qi, kc, kc + half_layer, dPos, dCos, dSin, dPart, oi, q->ldq, H, q->n_kv, q->P, lp.nch, scale_log2e, dBias}, B);
   }
   DBG_HIP(hipStreamSynchronize(st));
   DBG_HIP(hipGetLastError());

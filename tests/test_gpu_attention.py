@@ -423,7 +423,7 @@ def test_llama_step(llama, heads, bias):
         for r in (0, 1, 2):
             with Options(llama, llama_dec_r=r) as o:
                 m = mirror_step(o, p)
-                bits[r] = run_case(llama, p, m, f"attn_dec_cached128<{m['R']}>" + ("+bias" if bias else ""), f"llama step {heads} bias={bias} {tname} rows={len(pos)} llama_dec_r={r}")
+                bits[r] = run_case(llama, p, m, f"attn_dec_cached<128, {m['R']}>" + ("+bias" if bias else ""), f"llama step {heads} bias={bias} {tname} rows={len(pos)} llama_dec_r={r}")
         same_bits(bits, f"llama step {heads} bias={bias} {tname}")
 
 

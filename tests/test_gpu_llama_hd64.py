@@ -16,7 +16,7 @@ from llmrankers._engine import RkError
 pytestmark = pytest.mark.gpu
 FLOOR = 5e-3              # fp16 noise floor of the toy scale (test_gpu_rerank.py)
 BOUND = 4e-3              # x logit scale: what the 128-wide prefill and step are held to (test_gpu_llama_listwise.py)
-CHUNK = 128               # attn_dec_cached64_kernel: keys per workgroup (csrc/llama_kernels.h: LDC_CHUNK)
+CHUNK = 128               # attn_dec_cached_kernel<64>: keys per workgroup (csrc/llama_kernels.h: LDC_CHUNK)
 ERR_INVALID, ERR_HIP = -1, -3
 TOYS = ["toy-llama-hd64", "toy-qwen2-hd64", "toy-llama-mha-hd64"]
 

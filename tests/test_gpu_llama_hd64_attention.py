@@ -189,4 +189,4 @@ def test_step_key_equals_the_prefill_key(eng):
 def test_zz_ratios():
     pre = max([0.0] + [r for k, r in RATIOS.items() if k.startswith("prefill64") and (" R " in k or " Rflat " in k)])
     st = max([0.0] + [r for k, r in RATIOS.items() if k.startswith("step64") and " R " in k])
-    print(f"largest (error - half ulp) / E, tier R: attn_causal64 {pre:.2f}, attn_dec_cached64 + combine {st:.2f} (C = {D.C})")
+    print(f"largest (error - half ulp) / E, tier R: attn_causal64 {pre:.2f}, attn_dec_cached<64> + combine {st:.2f} (C = {D.C})")

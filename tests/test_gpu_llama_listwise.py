@@ -14,7 +14,7 @@ from conftest import GOLD
 
 pytestmark = pytest.mark.gpu
 FLOOR = 5e-3              # fp16 noise floor of the toy scale (test_gpu_rerank.py)
-CHUNK = 128               # attn_dec_cached128_kernel: keys per workgroup (csrc/llama_kernels.h: LDC_CHUNK)
+CHUNK = 128               # attn_dec_cached_kernel: keys per workgroup (csrc/llama_kernels.h: LDC_CHUNK)
 
 
 @pytest.fixture(scope="module")

@@ -189,8 +189,8 @@ def test_vicuna_template_rule(gold, ckpt, monkeypatch):
 
 
 def test_cached_decode_attention_kernel_has_no_scratch(tmp_path_factory):
-    """attn_dec_cached128_kernel keeps 16 K / V pieces, the rotated queries and the accumulators of up to 8 query heads in
-    registers: no spills (scratch), in every instantiation, and the merge kernel neither"""
+    """attn_dec_cached_kernel<D, R> keeps D / 8 K / V pieces (16 at D = 128, 8 at D = 64), the rotated queries and the
+    accumulators of up to 8 query heads in registers: no spills (scratch), in every instantiation, and the merge kernel neither"""
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     if not os.path.exists(hipcc):
         pytest.skip("hipcc not available")
@@ -203,11 +203,12 @@ def test_cached_decode_attention_kernel_has_no_scratch(tmp_path_factory):
         start = next(i for i, l in enumerate(lines) if l.startswith(mangled + ":"))
         end = next(i for i in range(start, len(lines)) if lines[i].startswith(".Lfunc_end"))
         return lines[start:end + 1], "\n".join(lines[end:end + 400])
-    for r in (1, 2, 4, 8):
-        code, meta = body(f"_Z25attn_dec_cached128_kernelILi{r}EEv20AttnDecCached128Args")
-        assert not any("scratch_" in l for l in code), f"R = {r}: the cached decode attention kernel spills"
-        assert re.search(r"ScratchSize: 0\b", meta), r
-        assert sum("global_load_dwordx4" in l for l in code) >= 16        # K / V pieces straight to registers, 16 B per lane
-        assert not any("s_sleep" in l or "buffer_wbl2" in l for l in code)   # nobody waits on another workgroup
-    code, meta = body("_Z26attn_dec_combine128_kernel20AttnDecCached128Args")
-    assert not any("scratch_" in l for l in code) and re.search(r"ScratchSize: 0\b", meta)
+    for d, loads in ((128, 16), (64, 8)):                                     # a wave issues D / 16 K and D / 16 V loads
+        for r in (1, 2, 4, 8):
+            code, meta = body(f"_Z22attn_dec_cached_kernelILi{d}ELi{r}ELb0EEv16LlamaDecAttnArgs")
+            assert not any("scratch_" in l for l in code), f"D = {d}, R = {r}: the cached decode attention kernel spills"
+            assert re.search(r"ScratchSize: 0\b", meta), (d, r)
+            assert sum("global_load_dwordx4" in l for l in code) >= loads      # K / V pieces straight to registers, 16 B per lane
+            assert not any("s_sleep" in l or "buffer_wbl2" in l for l in code)   # nobody waits on another workgroup
+        code, meta = body(f"_Z23attn_dec_combine_kernelILi{d}EEv16LlamaDecAttnArgs")
+        assert not any("scratch_" in l for l in code) and re.search(r"ScratchSize: 0\b", meta), d
