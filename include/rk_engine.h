@@ -178,6 +178,15 @@ int rk_llama_set_rope_scaling(rk_engine* e, float factor, float low_freq_factor,
  * in fp32 to the projections' output before the rotation.  Call between rk_llama_create and the first rk_engine_load_tensor;
  * RK_ERR_STATE on a T5 engine or after finalize.  Never calling it (or on = 0): the bias names are ignored. */
 int rk_llama_set_qkv_bias(rk_engine* e, int on);
+/* Mistral family (hf: models/mistral/modeling_mistral.py, sliding_window_causal_mask; Zephyr / RankZephyr checkpoints): attention
+ * with a sliding window of `window` positions.  In the prefill query position i of a sequence sees keys max(0, i - window + 1) .. i;
+ * in the cached step (rk_llama_generate, rk_llama_session_*) the row at pos sees max(0, pos - window + 1) .. pos.  The K / V cache
+ * keeps every position (no rolling buffer): the window only limits what is read.  A sequence no longer than `window` gets, bit for
+ * bit, what an engine without a window gives on the same weights, whatever shares its call.  Call between rk_llama_create and
+ * rk_engine_finalize; window = 0, or never calling it: none.  RK_ERR_STATE on a T5 engine or after finalize, RK_ERR_INVALID for
+ * window < 0.  The register-staged 128-wide prefill kernel (option llama_attn_dma = 0) has no windowed form: with that option set a
+ * call whose longest sequence exceeds the window is RK_ERR_STATE, nothing launched. */
+int rk_llama_set_sliding_window(rk_engine* e, int window);
 /* next token of every prompt: first arg-max over the whole vocabulary of the logits at its last position */
 int rk_llama_greedy1(rk_engine* e, const int32_t* tokens, const int32_t* seq_offsets, int n_seq, int32_t* out_tokens);
 /* the same logits for a few vocabulary rows only -> out_logits[n_seq][n_out] fp32 (label scoring, tests) */
@@ -343,9 +352,14 @@ int rk_debug_gemm_ex(rk_engine* e, rk_debug_gemm_call* call);
  *                        out [M, H, d] (ldctx = H d) = sum_t softmax_t(qk_h . enc_t) enc_t.  Option xattn_mfma.
  *   4 Llama prefill      plan_llama_attn: q = rotated qkv [T, ldq] (H query heads, n_kv key heads, n_kv value heads of 128), seq_off,
  *                        out = ctx [T, ldctx].  Options llama_attn_dma, llama_attn_nw (ignored at hd = 64: one kernel, out_kind 2).
+ *                        On an engine with a sliding window W (rk_llama_set_sliding_window) the plan is the engine's: a call whose longest
+ *                        sequence exceeds W runs the windowed entry of its kernel (out_kind + 4: 5 = LDS-DMA, 6 = 64-wide; with
+ *                        llama_attn_dma = 0 at hd = 128 out_kind is 4 and the call is RK_ERR_STATE, nothing launched), any other call the plain one.
  *   5 Llama cached step  plan_llama_dec_attn: q = the step's rows [n_seq, ldq], NOT rotated; cache = K [n_seq][n_kv][P][128] then V, pos[n_seq]
  *                        (< P, < max_pos), cos_t / sin_t [max_pos][64] ([max_pos][32] at hd = 64), qkv_bias [(H + 2 n_kv) 128] fp32 or null; out = ctx [n_seq, H 128]
  *                        (ldctx = H 128); cache_all = the cache afterwards (the row's rotated key and its value appended at pos).  Option llama_dec_r.
+ *                        On an engine with a sliding window W every call runs the windowed entries (out_kind 1, else 0): row b reads keys
+ *                        max(0, pos[b] - W + 1) .. pos[b] and the cache below them is neither read into the result nor written.
  *   6 T5 cached step     the self-attention of rk_t5_generate's step, through the launcher run_decoder's cached branch calls: q = the step's
  *                        fused rows [n_seq, ldq] (q | k | v at columns 0 | 64 H | 128 H), cache [n_seq][P][2 x 64 H] (k | v per position),
  *                        pos: ONE value (the kernel reads one device word; outside [0, P): RK_ERR_INVALID, nothing launched), bias_lut;
@@ -358,7 +372,7 @@ int rk_debug_gemm_ex(rk_engine* e, rk_debug_gemm_call* call);
  * kernel may touch); out_all: (out_rows + 2 band_rows) x ldctx elements, the whole device allocation after the call, the bands filled
  * with the byte RK_DEBUG_SENTINEL before it.  cache / cache_all: the same with bands of band_rows x hd elements.
  * plan_only != 0: nothing is allocated or launched, only the out_* fields are filled: out_kind (1: DMA 0 / LONG 1 / TILED 2 / D128 3; 2: the
- * staged kernel NONE 0 / SEQ 1 / ROW 2; 3: part MFMA_FEW 0 / MFMA 1 / VALU16 2 / VALU4 3; 4: dma 0 / 1, or 2 = the 64-wide kernel), out_tparam (the kernel's template
+ * staged kernel NONE 0 / SEQ 1 / ROW 2; 3: part MFMA_FEW 0 / MFMA 1 / VALU16 2 / VALU4 3; 4: dma 0 / 1, or 2 = the 64-wide kernel, + 4 = its windowed entry; 5: 0, or 1 = the windowed entries), out_tparam (the kernel's template
  * parameter: wave groups, waves, heads per workgroup or R), out_grid (the first kernel's), out_grid2 (the tiled / staged / merge
  * kernel's), out_lds, out_staged, out_mfma, out_part, out_R, out_nch, out_skip_long, out_heads_per_wg, out_n_cu.
  * Every extent is checked against the sizes given before anything is launched (RK_ERR_INVALID); a shape no kernel of the plan takes

@@ -200,6 +200,7 @@ struct rk_engine {
   int family = 0; rk_llama_desc ld{};
   float rope_factor = 0.f, rope_low = 1.f, rope_high = 4.f; int rope_orig = 0;   // rope type llama3 when rope_factor > 0
   bool qkv_bias = false;                                                          // Qwen2 family: q / k / v projections carry a bias
+  int window = 0;                                                                 // Mistral family: sliding window W (rk_llama_set_sliding_window), 0 = none
   std::vector<LlamaLayerW> ll; float *l_final_ln = nullptr, *rope_cos = nullptr, *rope_sin = nullptr; int* d_pos = nullptr;
   // rk_llama_generate: K / V cache [n_layers][2][n_seq][n_kv][P][head_dim], the attention partials and the call's int block (grown
   // between calls; lkv_gen counts the moves and is part of the step graph's key), and the step's activation rows (max_seqs each)
@@ -1167,10 +1168,17 @@ int run_xattn_chain(rk_engine* e, hipStream_t st, const XAttnChain& c, const XAt
 struct CausalAttnPlan {
   bool dma = false; int nw = 0, nqb = 0;   // attn_causal128_dma_kernel<nw>, query blocks of 32 nw; else attn_causal128_kernel
   bool hd64 = false;                       // attn_causal64_kernel (llama_kernels_hd64.h), every call of a 64-wide engine
+  int window = 0;                          // > 0: the windowed entry of the kernel (attn_causal128_dma_win_kernel / attn_causal64_win_kernel)
+  bool no_win_kernel = false;              // the call needs a windowed kernel and the plan's kernel has none: refuse_window, nothing launched
   dim3 grid; int block = 256, lds = 0, lds_opt_in = 0;
 };
+// The sliding window (rk_llama_set_sliding_window: W = e->window) enters here and nowhere else: the windowed entry is planned for a
+// call whose LONGEST sequence exceeds W, the plain kernel otherwise.  That the choice may look at the call at all rests on the
+// windowed kernels' contract (llama_kernels.h): they differ from the plain ones only in chunks they skip and keys they mask, so a
+// sequence no longer than W gets the same bits from either - a row still depends on its own sequence alone.
 CausalAttnPlan plan_llama_attn(const rk_engine* e, int n_seq, int maxL, int n_heads, int n_kv) {
   CausalAttnPlan p;
+  if (e->window > 0 && maxL > e->window) p.window = e->window;
   if (head_width(e) == 64) {
     // 64-wide heads: ONE kernel for every length, whatever llama_attn_dma / llama_attn_nw say (they choose between 128-wide
     // kernels): plan_enc_attn's D128 precedent.  Static LDS (reported, not requested at launch).
@@ -1178,7 +1186,7 @@ CausalAttnPlan plan_llama_attn(const rk_engine* e, int n_seq, int maxL, int n_he
     return p;
   }
   p.dma = e->opt.llama_attn_dma;   // K / V chunks by LDS-DMA, V^T by transposing reads (round 5); chosen by the option alone: batch-independent
-  if (!p.dma) { p.grid = dim3((maxL + 127) / 128, n_heads, n_seq); return p; }
+  if (!p.dma) { p.grid = dim3((maxL + 127) / 128, n_heads, n_seq); p.no_win_kernel = p.window > 0; return p; }   // attn_causal128_kernel has no windowed form
   p.nw = e->opt.llama_attn_nw == 8 ? 8 : 4;   // same bits either way
   p.nqb = (maxL + 32 * p.nw - 1) / (32 * p.nw); p.grid = dim3(xcd_grid(n_seq * n_kv, (n_heads / n_kv) * p.nqb));
   p.block = 64 * p.nw; p.lds = p.lds_opt_in = ATCD_LDS_BYTES;
@@ -1197,11 +1205,23 @@ void launch_llama_attn(rk_engine* e, hipStream_t st, const CausalAttnCall& c, co
   const float scale_log2e = (1.0f / std::sqrt((float)hd)) * 1.4426950408889634f;   // head_dim**-0.5 * log2(e)
   AttnCausalArgs a{c.qkv, c.ctx, c.seq_off, c.ld, c.ldctx, c.n_heads, c.n_kv, scale_log2e, 0, 0, e->opt.attn_ko};
   Bracket br(e, st, PC_ENC_ATTN, 2.0 * (double)c.maxL * T * Q, (double)T * (2 * Q + 2 * KV) * 2.0);   // causal: half of 4 L T Q
-  if (p.hd64) { hipLaunchKernelGGL(attn_causal64_kernel, p.grid, dim3(p.block), 0, st, a); return; }
+  if (p.no_win_kernel) abort();                              // (the callers refuse such a plan: refuse_window)
+  if (p.hd64) {
+    if (p.window > 0) hipLaunchKernelGGL(attn_causal64_win_kernel, p.grid, dim3(p.block), 0, st, AttnCausalWinArgs{a, p.window});
+    else hipLaunchKernelGGL(attn_causal64_kernel, p.grid, dim3(p.block), 0, st, a);
+    return;
+  }
   if (!p.dma) { hipLaunchKernelGGL(attn_causal128_kernel, p.grid, dim3(p.block), 0, st, a); return; }
   a.n_seq = c.n_seq; a.nqb = p.nqb;
-  if (p.nw == 8) launch_lds<attn_causal128_dma_kernel<8>>(st, p.grid, p.block, p.lds, p.lds_opt_in, a);
+  if (p.window > 0) {
+    const AttnCausalWinArgs w{a, p.window};
+    if (p.nw == 8) launch_lds<attn_causal128_dma_win_kernel<8>>(st, p.grid, p.block, p.lds, p.lds_opt_in, w);
+    else launch_lds<attn_causal128_dma_win_kernel<4>>(st, p.grid, p.block, p.lds, p.lds_opt_in, w);
+  } else if (p.nw == 8) launch_lds<attn_causal128_dma_kernel<8>>(st, p.grid, p.block, p.lds, p.lds_opt_in, a);
   else launch_lds<attn_causal128_dma_kernel<4>>(st, p.grid, p.block, p.lds, p.lds_opt_in, a);
+}
+int refuse_window(rk_engine* e, const char* entry, int maxL) {
+  return fail(e, RK_ERR_STATE, "%s: a sequence of %d tokens on an engine with sliding window %d needs a windowed attention kernel, and option llama_attn_dma = 0 selects attn_causal128_kernel, which has none", entry, maxL, e->window);
 }
 
 // Single-token attention of one rk_llama_generate step over the K / V cache of P positions per sequence: the chunk kernel over
@@ -1214,7 +1234,9 @@ void launch_llama_attn(rk_engine* e, hipStream_t st, const CausalAttnCall& c, co
 // at eight rows (7.60 / 7.65; profiles/rankr1_bench.txt).  llama_dec_r = 1 forces R = 1.  Same bits whichever (tests).
 // A 64-wide engine runs the same kernels at D = 64 by the same rule with the same chunk length; it has no R = 7 instantiation, so
 // llama_dec_r = 2 falls back to the rule there.
-struct LlamaDecAttnPlan { int R = 1, nch = 1, hd = 128; dim3 grid, cgrid; };
+// On an engine with a sliding window every step runs the windowed entries (attn_dec_cached_win_kernel, attn_dec_combine_win_kernel):
+// a model constant again.  A row at pos < W skips and masks nothing there and gets the plain kernels' bits.
+struct LlamaDecAttnPlan { int R = 1, nch = 1, hd = 128, window = 0; dim3 grid, cgrid; };
 LlamaDecAttnPlan plan_llama_dec_attn(const rk_engine* e, int rows, int P, int n_heads, int n_kv) {
   LlamaDecAttnPlan p;                                        // (no CU count enters: fixed chunk length, model-constant R)
   const int G = n_heads / n_kv;
@@ -1225,17 +1247,22 @@ LlamaDecAttnPlan plan_llama_dec_attn(const rk_engine* e, int rows, int P, int n_
   p.nch = (P + LDC_CHUNK - 1) / LDC_CHUNK;
   p.grid = dim3(p.nch, n_heads / p.R, rows);
   p.cgrid = dim3(n_heads, rows);
+  p.window = e->window;
   return p;
 }
 
 void launch_llama_dec_attn(rk_engine* e, hipStream_t st, const LlamaDecAttnPlan& p, LlamaDecAttnArgs a, int rows) {
-  a.nch = p.nch;
+  a.nch = p.nch; a.window = p.window;
   Bracket br(e, st, PC_DEC_ATTN, 4.0 * rows * (double)a.P * a.n_heads * p.hd, 2.0 * rows * (double)a.P * a.n_kv * p.hd * 2.0);
   with_width(p.hd, [&](auto W) {
     constexpr int D = decltype(W)::value;
     auto go = [&](auto rc) {                                 // the bias-free instantiation is the Llama kernel as it was
       constexpr int R = decltype(rc)::value;
       if constexpr (R == 7 && D != 128) abort();             // no such kernel: plan_llama_dec_attn gives R = 7 at 128 alone
+      else if (p.window > 0) {
+        if (a.bias) hipLaunchKernelGGL((attn_dec_cached_win_kernel<D, R, true>), p.grid, dim3(256), 0, st, a);
+        else hipLaunchKernelGGL((attn_dec_cached_win_kernel<D, R, false>), p.grid, dim3(256), 0, st, a);
+      }
       else if (a.bias) hipLaunchKernelGGL((attn_dec_cached_kernel<D, R, true>), p.grid, dim3(256), 0, st, a);
       else hipLaunchKernelGGL((attn_dec_cached_kernel<D, R, false>), p.grid, dim3(256), 0, st, a);
     };
@@ -1247,7 +1274,8 @@ void launch_llama_dec_attn(rk_engine* e, hipStream_t st, const LlamaDecAttnPlan&
       case 2: go(integral_constant<int, 2>{}); break;
       default: go(integral_constant<int, 1>{}); break;
     }
-    hipLaunchKernelGGL(attn_dec_combine_kernel<D>, p.cgrid, dim3(D), 0, st, a);
+    if (p.window > 0) hipLaunchKernelGGL(attn_dec_combine_win_kernel<D>, p.cgrid, dim3(D), 0, st, a);
+    else hipLaunchKernelGGL(attn_dec_combine_kernel<D>, p.cgrid, dim3(D), 0, st, a);
   });
 }
 
@@ -2666,6 +2694,8 @@ static int llama_prefill(rk_engine* e, const int32_t* tokens, const int32_t* off
   if ((rc = check_batch(e, &sl, tokens, off, n_seq))) return rc;
   const rk_llama_desc& l = e->ld;
   const int hd = l.head_dim, T = sl.T, dm = l.hidden, Q = l.n_heads * hd, KV = l.n_kv_heads * hd, F = l.intermediate, ldq = Q + 2 * KV;
+  const CausalAttnPlan ap = plan_llama_attn(e, n_seq, sl.maxL, l.n_heads, l.n_kv_heads);
+  if (ap.no_win_kernel) return refuse_window(e, "llama prefill", sl.maxL);
   hipStream_t st = sl.se;
   HIPCHK(e, hipStreamSynchronize(st));
   std::vector<int> pos(T), last(n_seq);
@@ -2680,7 +2710,6 @@ static int llama_prefill(rk_engine* e, const int32_t* tokens, const int32_t* off
   // every consumer takes its row factors from rowscale_kernel (own_factors = false), also where a fill-in tile variant could
   // form them itself
   NormStream ns = sl.enc;
-  const CausalAttnPlan ap = plan_llama_attn(e, n_seq, sl.maxL, l.n_heads, l.n_kv_heads);
   ns.begin(e, st, sl.d_tokens, T, true);
   for (int i = 0; i < l.n_layers; ++i) {
     const LlamaLayerW& w = e->ll[i];
@@ -2727,6 +2756,15 @@ int rk_llama_set_rope_scaling(rk_engine* e, float factor, float low_freq_factor,
   if (!(factor > 0.f) || !(high_freq_factor > low_freq_factor) || !(low_freq_factor > 0.f) || original_max_pos <= 0)
     return fail(e, RK_ERR_INVALID, "bad llama3 rope scaling (factor %g, low %g, high %g, original_max_position_embeddings %d)", factor, low_freq_factor, high_freq_factor, original_max_pos);
   e->rope_factor = factor; e->rope_low = low_freq_factor; e->rope_high = high_freq_factor; e->rope_orig = original_max_pos;
+  return RK_OK;
+}
+
+int rk_llama_set_sliding_window(rk_engine* e, int window) {
+  if (!e) return RK_ERR_INVALID;
+  if (e->family != 1) return fail(e, RK_ERR_STATE, "a sliding window applies to Llama-family engines (rk_llama_create)");
+  if (e->finalized) return fail(e, RK_ERR_STATE, "rk_llama_set_sliding_window must precede rk_engine_finalize");
+  if (window < 0) return fail(e, RK_ERR_INVALID, "sliding window %d: a positive number of positions, or 0 for none", window);
+  e->window = window;
   return RK_OK;
 }
 
@@ -2792,7 +2830,7 @@ static int llama_step_rows(rk_engine* e, hipStream_t st, int rows, int P, const 
     RC(gemm(e, st, normed(Gemm(PC_DEC_GEMM, EPI_STORE_F16, ns.x(), dm, w.qkv_f, dm, lg.qkv, ldq, rows, ldq, dm))));
     half_t* kc = e->lkv.p + (size_t)i * 2 * half_layer;
     launch_llama_dec_attn(e, st, ap, LlamaDecAttnArgs{lg.qkv, kc, kc + half_layer, d_pos, e->rope_cos, e->rope_sin, e->lpart.p, lg.ctx,
-                                                          ldq, l.n_heads, l.n_kv_heads, P, ap.nch, scale_log2e, w.qkv_bias}, rows);
+                                                          ldq, l.n_heads, l.n_kv_heads, P, ap.nch, scale_log2e, w.qkv_bias, 0}, rows);
     RC(ns.producer(e, st, Gemm(PC_DEC_GEMM, EPI_RESID_F32, lg.ctx, Q, w.o, Q, ns.hidden, dm, rows, dm, Q).on(GEMM_STREAM)));
     RC(gemm(e, st, normed(Gemm(PC_DEC_GEMM, EPI_SWIGLU_F16, ns.x(), dm, w.gu_f, dm, lg.ffh, F, rows, 2 * F, dm))));
     RC(ns.producer(e, st, Gemm(PC_DEC_GEMM, EPI_RESID_F32, lg.ffh, F, w.down, F, ns.hidden, dm, rows, dm, F).on(GEMM_STREAM), i + 1 < l.n_layers));
@@ -3541,7 +3579,8 @@ int rk_debug_attn(rk_engine* e, rk_debug_attn_call* q) {
     if (n_kv <= 0 || H % n_kv) return fail(e, RK_ERR_INVALID, "debug attn: n_kv must divide H");
     ldq_min = (long)(H + 2 * n_kv) * hd; ldctx_min = (long)H * hd; q_rows_need = out_rows_need = T;
     cp = plan_llama_attn(e, B, maxL, H, n_kv);
-    plan_out(cp.hd64 ? 2 : (int)cp.dma, cp.nw, cp.grid, dim3(0, 0, 0), cp.lds);
+    plan_out((cp.hd64 ? 2 : (int)cp.dma) + (cp.window > 0 ? 4 : 0), cp.nw, cp.grid, dim3(0, 0, 0), cp.lds);
+    if (cp.no_win_kernel) return refuse_window(e, "debug attn", maxL);
   } else if (kind == 6) {
     const int P = q->P;
     if (P <= 0 || P > 8192) return fail(e, RK_ERR_INVALID, "debug attn: the T5 cached step takes a cache of 1..8192 positions");
@@ -3563,7 +3602,7 @@ int rk_debug_attn(rk_engine* e, rk_debug_attn_call* q) {
         if (q->pos[b] < 0 || q->pos[b] >= P || q->pos[b] >= q->max_pos) return fail(e, RK_ERR_INVALID, "debug attn: pos[%d] = %d outside the cache of %d / the tables of %d", b, q->pos[b], P, q->max_pos);
     }
     lp = plan_llama_dec_attn(e, B, P, H, n_kv);
-    plan_out(0, lp.R, lp.grid, lp.cgrid, 0);
+    plan_out(lp.window > 0 ? 1 : 0, lp.R, lp.grid, lp.cgrid, 0);
     q->out_R = lp.R; q->out_nch = lp.nch;
     if (H % lp.R) return fail(e, RK_ERR_STATE, "debug attn: R = %d does not divide %d heads", lp.R, H);
   }
@@ -3660,7 +3699,7 @@ int rk_debug_attn(rk_engine* e, rk_debug_attn_call* q) {
     DBG_HIP(hipDeviceSynchronize());
     const float scale_log2e = (1.0f / std::sqrt((float)hd)) * 1.4426950408889634f;
     half_t* kc = dC + c_band;
-    launch_llama_dec_attn(e, st, lp, LlamaDecAttnArgs{qi, kc, kc + half_layer, dPos, dCos, dSin, dPart, oi, q->ldq, H, q->n_kv, q->P, lp.nch, scale_log2e, dBias}, B);
+    launch_llama_dec_attn(e, st, lp, LlamaDecAttnArgs{qi, kc, kc + half_layer, dPos, dCos, dSin, dPart, oi, q->ldq, H, q->n_kv, q->P, lp.nch, scale_log2e, dBias, 0}, B);
   }
   DBG_HIP(hipStreamSynchronize(st));
   DBG_HIP(hipGetLastError());

@@ -124,6 +124,7 @@ ABI = {
     "rk_llama_create": (C.c_int, [_P(RkLlamaDesc), C.c_int, _P(C.c_void_p)]),
     "rk_llama_set_rope_scaling": (C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_int]),
     "rk_llama_set_qkv_bias": (C.c_int, [C.c_void_p, C.c_int]),
+    "rk_llama_set_sliding_window": (C.c_int, [C.c_void_p, C.c_int]),
     "rk_llama_greedy1": (C.c_int, [C.c_void_p, _i32p, _i32p, C.c_int, _i32p]),
     "rk_llama_last_logits": (C.c_int, [C.c_void_p, _i32p, _i32p, C.c_int, _i32p, C.c_int, _f32p]),
     "rk_llama_generate": (C.c_int, [C.c_void_p, _i32p, _i32p, C.c_int, C.c_int, C.c_int, _i32p, C.c_int, C.c_int, _i32p, _i32p]),
@@ -770,6 +771,8 @@ class RkLlamaEngine(RkEngine):
             self._chk(self.lib.rk_llama_set_rope_scaling(self.h, float(f), float(lo), float(hi), int(orig)))
         if getattr(dims, "qkv_bias", False):                          # Qwen2 family: before the first tensor is loaded
             self._chk(self.lib.rk_llama_set_qkv_bias(self.h, 1))
+        if getattr(dims, "sliding_window", 0) > 0:                    # Mistral family: the attention's window, before finalize
+            self._chk(self.lib.rk_llama_set_sliding_window(self.h, int(dims.sliding_window)))
 
     def greedy1(self, seqs: Sequence[Sequence[int]]) -> np.ndarray:
         tok, off = pack_ragged(seqs)

@@ -124,6 +124,10 @@ class LlamaDims:
     rope_scaling: Optional[Tuple[float, float, float, int]] = None
     # Qwen2 family (hf: models/qwen2/modeling_qwen2.py): the same decoder with a bias on the q / k / v projections (not on o_proj)
     qkv_bias: bool = False
+    # Mistral family (hf: models/mistral/modeling_mistral.py): the Llama decoder whose attention may carry a sliding window - query
+    # position i sees keys max(0, i - sliding_window + 1) .. i; 0 = none (the config's null).  `mistral` marks the config as Mistral's.
+    sliding_window: int = 0
+    mistral: bool = False
 
     def to_hf_config(self) -> dict:
         if self.qkv_bias:
@@ -139,11 +143,23 @@ class LlamaDims:
                 "tie_word_embeddings": bool(self.tied_head), "bos_token_id": self.bos_token_id, "eos_token_id": self.eos_token_id,
                 "use_cache": True,
             }
+        if self.sliding_window and not self.mistral:
+            raise NotImplementedError("a sliding window belongs to a Mistral configuration (LlamaDims.mistral)")
         scaling = None
         if self.rope_scaling is not None:
             f, lo, hi, orig = self.rope_scaling
             scaling = {"rope_type": "llama3", "factor": float(f), "low_freq_factor": float(lo), "high_freq_factor": float(hi),
                        "original_max_position_embeddings": int(orig)}
+        if self.mistral:
+            return {
+                "architectures": ["MistralForCausalLM"], "model_type": "mistral", "vocab_size": self.vocab,
+                "hidden_size": self.hidden, "intermediate_size": self.intermediate, "num_hidden_layers": self.n_layers,
+                "num_attention_heads": self.n_heads, "num_key_value_heads": self.n_kv_heads, "head_dim": self.head_dim,
+                "hidden_act": "silu", "rms_norm_eps": self.eps, "rope_theta": self.rope_theta, "rope_scaling": scaling,
+                "max_position_embeddings": 32768, "sliding_window": int(self.sliding_window) or None, "attention_dropout": 0.0,
+                "tie_word_embeddings": bool(self.tied_head), "bos_token_id": self.bos_token_id, "eos_token_id": self.eos_token_id,
+                "use_cache": True,
+            }
         return {
             "architectures": ["LlamaForCausalLM"], "model_type": "llama", "vocab_size": self.vocab,
             "hidden_size": self.hidden, "intermediate_size": self.intermediate, "num_hidden_layers": self.n_layers,
@@ -160,6 +176,7 @@ class LlamaDims:
         if cfg.get("hidden_act", "silu") != "silu" or cfg.get("attention_bias") or cfg.get("mlp_bias"):
             raise NotImplementedError("only bias-free SwiGLU Llama configurations are supported by the MI355X engine")
         qwen2 = cfg.get("model_type") == "qwen2"
+        mistral = cfg.get("model_type") == "mistral"   # no biases; head_dim and sliding_window may be absent or null
         if qwen2 and cfg.get("use_sliding_window"):
             raise NotImplementedError("Qwen2 configurations with use_sliding_window are not supported by the MI355X engine")
         rope = cfg.get("rope_parameters") or {}
@@ -179,7 +196,8 @@ class LlamaDims:
                          rope_theta=float(cfg.get("rope_theta") or rope.get("rope_theta") or 10000.0),
                          eps=cfg.get("rms_norm_eps", 1e-6), tied_head=bool(cfg.get("tie_word_embeddings", False)),
                          bos_token_id=cfg.get("bos_token_id", 1) or 1, eos_token_id=eos[0] if isinstance(eos, list) else eos,
-                         rope_scaling=rs, qkv_bias=qwen2)
+                         rope_scaling=rs, qkv_bias=qwen2, sliding_window=int(cfg.get("sliding_window") or 0) if mistral else 0,
+                         mistral=mistral)
 
 
 LLAMA_3_8B = LlamaDims(vocab=128256, hidden=4096, n_heads=32, n_kv_heads=8, head_dim=128, intermediate=14336, n_layers=32,
@@ -187,6 +205,9 @@ LLAMA_3_8B = LlamaDims(vocab=128256, hidden=4096, n_heads=32, n_kv_heads=8, head
 # Qwen2.5-7B-Instruct (the base of the Rank-R1 7B rerankers): 28 query heads on 4 kv heads; timing tools only
 QWEN25_7B = LlamaDims(vocab=152064, hidden=3584, n_heads=28, n_kv_heads=4, head_dim=128, intermediate=18944, n_layers=28,
                       rope_theta=1000000.0, eps=1e-6, bos_token_id=151643, eos_token_id=151645, qkv_bias=True)
+# Zephyr-7B / RankZephyr (castorini/rank_zephyr_7b_v1_full: Mistral-7B-v0.1 widths, sliding_window 4096); timing tools only
+MISTRAL_7B = LlamaDims(vocab=32000, hidden=4096, n_heads=32, n_kv_heads=8, head_dim=128, intermediate=14336, n_layers=32,
+                       rope_theta=10000.0, sliding_window=4096, mistral=True)
 # toy: kernel-friendly (head_dim 128 like every Llama-3), grouped-query (4 q heads on 2 kv heads), q width != hidden
 TOY_LLAMA = LlamaDims(vocab=256, hidden=256, n_heads=4, n_kv_heads=2, head_dim=128, intermediate=512, n_layers=2)
 # the same with Llama-3.1's rope type; a short original context and a small base so that most of the 64 frequencies fall in
@@ -215,6 +236,11 @@ TOY_LLAMA_HD64 = LlamaDims(vocab=256, hidden=256, n_heads=8, n_kv_heads=2, head_
 # TOY_QWEN2 at width 64: 7 query heads on ONE kv head (G = 7: the decode attention takes one head per workgroup), tied head, biases
 TOY_QWEN2_HD64 = LlamaDims(vocab=512, hidden=256, n_heads=7, n_kv_heads=1, head_dim=64, intermediate=512, n_layers=2,
                            rope_theta=1000000.0, eps=1e-6, tied_head=True, qkv_bias=True)
+# toy Mistral: TOY_LLAMA's / TOY_LLAMA_HD64's shape with a sliding window (the tests put their own: dataclasses.replace)
+TOY_MISTRAL = LlamaDims(vocab=256, hidden=256, n_heads=4, n_kv_heads=2, head_dim=128, intermediate=512, n_layers=2,
+                        sliding_window=64, mistral=True)
+TOY_MISTRAL_HD64 = LlamaDims(vocab=256, hidden=256, n_heads=8, n_kv_heads=2, head_dim=64, intermediate=512, n_layers=2,
+                             sliding_window=64, mistral=True)
 # multi-head attention (G = 1) with an odd head count: q width 192
 TOY_LLAMA_MHA_HD64 = LlamaDims(vocab=256, hidden=256, n_heads=3, n_kv_heads=3, head_dim=64, intermediate=512, n_layers=2)
 
@@ -250,6 +276,7 @@ NAMED_DIMS = {
     "qwen2.5-7b": QWEN25_7B, "toy-qwen2": TOY_QWEN2,
     "llama-3.2-1b": LLAMA_32_1B, "tinyllama-1.1b": TINYLLAMA_1B, "qwen2.5-0.5b": QWEN25_05B,
     "toy-llama-hd64": TOY_LLAMA_HD64, "toy-qwen2-hd64": TOY_QWEN2_HD64, "toy-llama-mha-hd64": TOY_LLAMA_MHA_HD64,
+    "mistral-7b": MISTRAL_7B, "toy-mistral": TOY_MISTRAL, "toy-mistral-hd64": TOY_MISTRAL_HD64,
 }
 
 _M64 = np.uint64(0xFFFFFFFFFFFFFFFF)

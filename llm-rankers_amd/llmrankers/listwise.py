@@ -294,3 +294,97 @@ class ListwiseLlmRanker(LlmRanker):
 
     def truncate(self, text, length):
         return self.tokenizer.convert_tokens_to_string(self.tokenizer.tokenize(text)[:length])
+
+
+class R1ListwiseLlmRanker(ListwiseLlmRanker):
+    """The listwise baseline of Rank-R1 (ref: Rank-R1/run_listwise.py:89-156; RankZephyr - a Zephyr / Mistral-7B checkpoint with a
+    sliding window - or any chat model, served by vLLM there): one compare = the two-message chat prompt of the prompt settings
+    (system, and the user message with the window's passages as "[n] text" lines), a greedy completion of up to max_new_tokens
+    tokens, and the settings' regular expression that takes the permutation out of it ('None' when it does not match: the window
+    stays as it is).  Here the checkpoint (a LoRA adapter merged on the host, _runtime.merge_lora) runs on the engine's KV-cached
+    greedy decoder; a Mistral checkpoint's sliding window is the engine's (rk_llama_set_sliding_window).  Same constructor,
+    compare() contract, counters and window walk as the reference; the stand-ins for vLLM are RankR1SetwiseLlmRanker's (DESIGN.md
+    section 3, "Qwen2 family and Rank-R1"): the stop ids and the pad id are the checkpoint's generation settings, the EOS that ended
+    a row counts as a completion token, the completion text is the new tokens decoded without special tokens.  Only the windows
+    call is this class's own: compare, rerank, rerank_many (the pending windows of all live queries in ONE generate call per step)
+    and truncate are ListwiseLlmRanker's."""
+    CHARACTERS = [f'[{i + 1}]' for i in range(20)]
+    ACCEPT_MODEL_TYPES = ("qwen2", "llama", "mistral")      # vLLM takes any chat model; these are the families the engine serves
+
+    def __init__(self, model_name_or_path, tokenizer_name_or_path, prompt, window_size, step_size, lora_path=None,
+                 scoring='generation', num_repeat=1, cache_dir=None, device="cuda", max_new_tokens=2048):
+        from transformers import AutoTokenizer
+        from ._runtime import LlamaRuntime, resolve_checkpoint
+        from .setwise import load_prompt_file
+        prompt = load_prompt_file(prompt)
+        lora_path = resolve_checkpoint(lora_path, cache_dir) if lora_path is not None else None
+        tokenizer = AutoTokenizer.from_pretrained(tokenizer_name_or_path if tokenizer_name_or_path is not None else model_name_or_path,
+                                                  cache_dir=cache_dir)
+        runtime = LlamaRuntime(model_name_or_path, device, cache_dir=cache_dir, accept_model_types=self.ACCEPT_MODEL_TYPES,
+                               adapter_dir=lora_path)
+        self._setup_r1(runtime, tokenizer, prompt, lora_path, device, window_size, step_size, scoring, num_repeat, max_new_tokens)
+
+    @classmethod
+    def from_runtime(cls, runtime, tokenizer, prompt, device="cuda", window_size=3, step_size=1, scoring='generation', num_repeat=1,
+                     max_new_tokens=2048):
+        """Build the ranker around an existing runtime (a loaded engine - adapter already merged - or a test double)."""
+        from .setwise import load_prompt_file
+        self = cls.__new__(cls)
+        self._setup_r1(runtime, tokenizer, load_prompt_file(prompt), None, device, window_size, step_size, scoring, num_repeat, max_new_tokens)
+        return self
+
+    def _setup_r1(self, runtime, tokenizer, prompt, lora_path, device, window_size, step_size, scoring, num_repeat, max_new_tokens):
+        if not hasattr(runtime, "generate"):
+            raise NotImplementedError(f"{LLAMA_MESSAGE} (runtime {type(runtime).__name__})")
+        self.prompt = prompt
+        self.lora_path = lora_path
+        self.device = device
+        self.window_size = window_size
+        self.step_size = step_size
+        self.num_repeat = num_repeat
+        self.scoring = scoring                              # (the reference takes the argument and never reads it)
+        self.max_new_tokens = int(max_new_tokens)           # the reference's SamplingParams(temperature=0.0, max_tokens=2048)
+        self.tokenizer = tokenizer
+        self.llm = runtime
+        self.config = getattr(runtime, "config", None)
+        self.model_type = getattr(runtime, "model_type", "mistral")
+        self.total_compare = 0
+        self.total_prompt_tokens = 0
+        self.total_completion_tokens = 0
+
+    def _chat_messages(self, query: str, docs: List) -> List[dict]:
+        passages = "\n".join(f'{self.CHARACTERS[i]} {doc.text}' for i, doc in enumerate(docs))
+        return [{'role': "system", 'content': self.prompt["prompt_system"]},
+                {'role': "user", 'content': self.prompt['prompt_user'].format(query=query, num=len(docs), docs=passages)}]
+
+    def _chat_ids(self, query: str, docs: List) -> List[int]:
+        """what vLLM's LLM.chat feeds the model: the chat template with the generation prompt, tokenized"""
+        out = self.tokenizer.apply_chat_template(self._chat_messages(query, docs), add_generation_prompt=True, tokenize=True)
+        if hasattr(out, "keys"):                             # transformers >= 5 returns a BatchEncoding
+            out = out["input_ids"]
+        return [int(t) for t in out]
+
+    def _compare_windows(self, queries: List[str], doc_lists: List[List]):
+        """ONE generate call for windows that may belong to different queries -> (returned strings, prompt tokens per window, new
+        tokens per window); touches no counter (ref: run_listwise.py:121-156 per window)."""
+        import re
+        ids = [self._chat_ids(q, docs) for q, docs in zip(queries, doc_lists)]
+        gen = self.llm.generation
+        eos_ids = list(gen["eos_token_ids"])
+        rows = np.asarray(self.llm.generate(ids, self.max_new_tokens, eos_ids, int(gen["pad_token_id"])))
+        outs, completion = [], []
+        for q, docs, row in zip(queries, doc_lists, rows):
+            new = [int(t) for t in row if t >= 0]
+            stop = next((i for i, t in enumerate(new) if t in eos_ids), None)
+            if stop is not None:                             # vLLM's token_ids keep the EOS that ended the row
+                new = new[:stop + 1]
+            completion.append(len(new))
+            text = self.tokenizer.decode(new, skip_special_tokens=True)
+            match = re.search(rf'{self.prompt["pattern"]}', text.lower(), re.DOTALL)
+            if match:
+                outs.append(match.group(1).strip())
+            else:
+                outs.append('None')
+                print('Input for no match:', self._chat_messages(q, docs))
+                print('Completion for no match:', text)
+        return outs, [len(i) for i in ids], completion

@@ -265,6 +265,12 @@ def build_ranker(args):
     if args.listwise:
         if args.run.openai_key:
             raise NotImplementedError("OpenAI rankers are remote HTTP calls, not part of the MI355X hot path; use the reference")
+        if getattr(args.run, "prompt_file", None):               # Rank-R1's listwise baseline (ref: Rank-R1/run_listwise.py:159-178)
+            from llmrankers.listwise import R1ListwiseLlmRanker
+            return R1ListwiseLlmRanker(model_name_or_path=args.run.model_name_or_path, tokenizer_name_or_path=args.run.tokenizer_name_or_path,
+                                       prompt=args.run.prompt_file, window_size=args.listwise.window_size, step_size=args.listwise.step_size,
+                                       lora_path=args.run.lora_name_or_path, num_repeat=args.listwise.num_repeat, cache_dir=args.run.cache_dir,
+                                       device=args.run.device, max_new_tokens=args.run.max_new_tokens)
         from llmrankers.listwise import ListwiseLlmRanker
         return ListwiseLlmRanker(model_name_or_path=args.run.model_name_or_path, tokenizer_name_or_path=args.run.tokenizer_name_or_path,
                                  device=args.run.device, cache_dir=args.run.cache_dir, window_size=args.listwise.window_size,
@@ -512,7 +518,8 @@ def build_parser():
     rp.add_argument("--tokenizer_name_or_path", type=str, default=None)
     rp.add_argument("--prompt_file", type=str, default=None,
                     help="setwise: a Rank-R1 prompt file (TOML: prompt_system, prompt_user, pattern) selects the reasoning reranker "
-                         "RankR1SetwiseLlmRanker (ref: Rank-R1/run_setwise.py)")
+                         "RankR1SetwiseLlmRanker (ref: Rank-R1/run_setwise.py); listwise: its listwise baseline R1ListwiseLlmRanker "
+                         "(ref: Rank-R1/run_listwise.py)")
     rp.add_argument("--lora_name_or_path", "--lora_path_or_name", type=str, default=None, dest="lora_name_or_path",
                     help="Rank-R1: a PEFT LoRA adapter directory, merged into the checkpoint's weights on load")
     rp.add_argument("--max_new_tokens", type=int, default=2048, help="Rank-R1: tokens of reasoning and answer per compare")
