@@ -139,7 +139,13 @@ int rk_engine_sync(rk_engine* e);
 int rk_t5_read_scores(rk_engine* e, float* out_logits, int n_floats);   /* waits for the batch's decoder, then copies */
 /* The same three calls for batch slot `slot` in [0, rk_engine_num_slots()).  Slots are independent batches in flight:
  * the latency-bound decoder chain of one slot runs on its own high-priority HIP stream while the MFMA-bound encoder
- * of the next slot occupies the chip (events order encoder -> decoder per slot).  The un-suffixed calls use slot 0. */
+ * of the next slot occupies the chip (events order encoder -> decoder per slot).  The un-suffixed calls use slot 0.
+ * A slot may be staged again while its launch is still in flight: the launch keeps the batch it was enqueued with (two
+ * generations of the staged arrays), its scores stay readable until the next launch on the slot, and the staging waits for
+ * no decoder.  The LAUNCH may: rk_t5_score_slot / rk_t5_compare_slot return without waiting only while the slot's n_seq, dec_prefix
+ * and out_token_ids (compare: n_seq and dec_start_id) equal those of the slot's previous launch; when one of them differs the
+ * call first blocks the host until the slot's earlier decoders are through (its index buffers are re-uploaded through one
+ * pinned staging area), then enqueues and returns. */
 int rk_engine_num_slots(void);
 int rk_t5_stage_slot(rk_engine* e, int slot, const int32_t* tokens, const int32_t* seq_offsets, int n_seq);
 int rk_t5_score_slot(rk_engine* e, int slot, const int32_t* dec_prefix, int dec_len, const int32_t* out_token_ids, int n_out);

@@ -136,11 +136,38 @@ struct DecIndex {
 // let (a) the latency-bound decoder chain of one batch hide under the MFMA-bound encoder of the next and (b) the
 // encoder kernels of both batches co-run, so workgroups of one fill the tile-quantisation tail of the other
 // (1104 GEMM tiles on 512 resident slots is 3 rounds alone but 2.16 rounds of work).
+//
+// Who touches what (T5; a launch = one encoder chain on se, then one decoder pass or several on sd).  Everything on one stream is
+// ordered by the stream; the table is about the other stream and the host.
+//   buffer                               written by                                read by
+//   stg_tokens[g], stg_seq_off[g]        host, stage_slot (generation g)           encoder chain of the launches staged in g
+//   enc, qkv, ctx, ffh                   encoder chain, from its first kernel      encoder chain only
+//   dec_seq_off                          encoder chain, copy behind the layers     decoder: cross-attention
+//   enc_out                              encoder chain, final rmsnorm              decoder: query-side cross-attention
+//   cross_kv                             encoder chain, last GEMM (if needed)      decoder: cross-attention over materialised K / V
+//   idx.*                                decoder stream (DecIndex copies); the HOST     decoder, head
+//                                        waits for that stream first whenever the ints change (below)
+//   dec, dqkv .. dlast, x*, d_argmax, d_scores   decoder stream (kernels)          decoder, head, verdict, gathers
+//   h_scores                             decoder stream (copy behind the head)     host, behind ev_dec
+// So the decoder of the slot's PREVIOUS launch reads dec_seq_off, enc_out and cross_kv and nothing else an encoder writes: the next
+// encoder chain waits for ev_dec in front of its dec_seq_off copy (run_encoder: wait_prev_decoder), never earlier - its layers run
+// beside that decoder.  The staged arrays are read by encoder chains alone, so staging waits for an encoder (ev_enc of the
+// generation it writes), never for a decoder.  A new entry point that lets a decoder read another encoder-written buffer adds a row
+// here and moves that buffer's first write behind wait_prev_decoder.
+// One host wait for a decoder remains, in the LAUNCH and not in the staging: DecIndex::put / write reuse one pinned staging slot per
+// buffer and synchronise the decoder stream before they overwrite it.  put compares first, so a launch whose decoder ids, last rows
+// and output ids equal the slot's previous launch (same n_seq, dec_len, ids: the steady state of a stream of full calls) never
+// waits; one that differs blocks the host until the slot's earlier decoders are through (include/rk_engine.h says so).
 struct Slot {
   hipStream_t se = nullptr, sd = nullptr;   // this slot's encoder chain (MFMA-bound) | decoder chain (latency-bound)
   NormStream enc;                                              // the encoder's residual stream (Llama: the prefill's)
   half_t *qkv = nullptr, *ctx = nullptr, *ffh = nullptr, *enc_out = nullptr;
-  int* d_tokens = nullptr; int* d_seq_off = nullptr;
+  int* d_tokens = nullptr; int* d_seq_off = nullptr;           // Llama only: the staged batch (llama_prefill writes and reads it on one stream)
+  int* dec_seq_off = nullptr;                                  // T5 only: the DECODER's copy of the sequence offsets (the table above)
+  // T5: two generations of the staged batch.  stage_slot writes the one no enqueued launch reads: the other one once a launch has
+  // taken the current (gen_launched), else the current again.  stage_no counts the stagings, off_of is the one dec_seq_off holds.
+  int *stg_tokens[2] = {nullptr, nullptr}, *stg_seq_off[2] = {nullptr, nullptr};
+  int gen = 0; bool gen_launched = false; unsigned stage_no = 0, off_of = 0;
   int n_seq = 0, T = 0, maxL = 0, minL = 0; bool staged = false; int last_floats = 0;   // what the slot's last score / compare call left in its score buffer
   half_t* cross_kv = nullptr;                                  // [n_dec][max_tokens][2I] encoder -> decoder hand-off
   DecIndex idx; int* d_argmax = nullptr;                       // decoder ids, row maps, labels (see DecIndex) | the greedy head's result
@@ -150,7 +177,9 @@ struct Slot {
   half_t *xqk = nullptr, *xctx = nullptr;                      // direct cross-attention: [32][H*d] each
   float *xpart = nullptr, *xstat = nullptr; bool have_cross_kv = false;
   float* d_scores = nullptr; float* h_scores = nullptr;
-  hipEvent_t ev_enc = nullptr, ev_dec = nullptr; bool dec_pending = false;
+  // ev_enc[g]: the last encoder chain that read generation g is done (hand-off to the decoder; staging g again waits for it);
+  // enc_gen: the generation of the last chain enqueued (-1: none).  ev_dec: the slot's last launch is done.
+  hipEvent_t ev_enc[2] = {nullptr, nullptr}, ev_dec = nullptr; int enc_gen = -1; bool dec_pending = false;
 };
 
 struct rk_engine {
@@ -183,7 +212,7 @@ struct rk_engine {
         gemm_persistent = 1, fold_norm = 1, s64_stages = 0, dec_fold_norm = 1, greedy_spec = 160, consumer_stats = 1, xattn_mfma = 1,
         dec_ffn_tiled = 1, gemm_split = 1, dec_fuse = 1, dec_fuse_rows = 0, dec_attn_seq = 1, attn_long = 1, attn_long_nw = 0,
         llama_attn_dma = 1, attn_long_xcd = 1, llama_attn_nw = 0, dec_graph = 1, gemm_sk = 1, dec_cross_mfma = 1, dec_gemv = 1, dec_gemv_rows = 4,
-        dec_cached_attn = 1, llama_dec_r = 0;
+        dec_cached_attn = 1, llama_dec_r = 0, enc_serial = 0;
   } opt;
   float* attn_trace = nullptr;   // measurement builds only (option attn_trace)
   int n_cu = 256;
@@ -279,8 +308,7 @@ struct Bracket {
 };
 
 // overlap = 0 puts every launch of every slot on ONE stream (serial timeline, used for per-kernel event timing)
-// encoders alternate between TWO streams however many slots there are (more concurrent GEMM chains only thrash);
-// the extra slots exist to lengthen the distance between a decoder and the next encoder that reuses its buffers
+// encoders alternate between TWO streams however many slots there are (more concurrent GEMM chains only thrash)
 hipStream_t enc_stream(rk_engine* e, Slot& sl) { return e->opt.overlap ? e->slots[(&sl - e->slots) & 1].se : e->slots[0].se; }
 hipStream_t dec_stream(rk_engine* e, Slot& sl) { return e->opt.overlap ? sl.sd : e->slots[0].se; }
 
@@ -1279,6 +1307,14 @@ void launch_llama_dec_attn(rk_engine* e, hipStream_t st, const LlamaDecAttnPlan&
   });
 }
 
+// The slot's previous launch may still be in its decoder: the encoder chain stops here until that one is done.  (Read back
+// already, or everything on one stream: nothing to wait for.)
+int wait_prev_decoder(rk_engine* e, Slot& sl) {
+  hipStream_t se = enc_stream(e, sl);
+  if (sl.dec_pending && dec_stream(e, sl) != se) HIPCHK(e, hipStreamWaitEvent(se, sl.ev_dec, 0));
+  return RK_OK;
+}
+
 // hf: modeling_t5.py:663-750 (T5Stack.forward, encoder) over the slot's staged ragged batch, then the stacked
 // cross-attention K/V projections of all decoder layers (:325-326 with key_value_states = encoder output).
 int run_encoder(rk_engine* e, Slot& sl, bool need_cross_kv) {
@@ -1291,16 +1327,23 @@ int run_encoder(rk_engine* e, Slot& sl, bool need_cross_kv) {
   int rc = RK_OK;
   NormStream ns = sl.enc;
   const EncAttnPlan ap = plan_enc_attn(e, sl.n_seq, sl.maxL, sl.minL, d.n_heads);
-  ns.begin(e, st, sl.d_tokens, T, e->opt.fold_norm != 0);
+  const int* seq_off = sl.stg_seq_off[sl.gen];
+  ns.begin(e, st, sl.stg_tokens[sl.gen], T, e->opt.fold_norm != 0);
   for (int l = 0; l < d.n_enc_layers; ++l) {
     const EncLayerW& w = e->enc[l];
     const bool last = l + 1 == d.n_enc_layers;
     RC(gemm(e, st, ns.consumer(e, st, w.ln0, Gemm(PC_ENC_GEMM_QKV, EPI_STORE_F16, ns.x(), dm, ns.fold ? w.qkv_f : w.qkv, dm, sl.qkv, 3 * I, T, 3 * I, dm), own)));
-    launch_enc_attn(e, st, EncAttnCall{sl.qkv, sl.ctx, sl.d_seq_off, e->lut_enc, 3 * I, I, I, d.n_heads, sl.n_seq, sl.maxL, sl.T}, ap);
+    launch_enc_attn(e, st, EncAttnCall{sl.qkv, sl.ctx, seq_off, e->lut_enc, 3 * I, I, I, d.n_heads, sl.n_seq, sl.maxL, sl.T}, ap);
     RC(ns.producer(e, st, Gemm(PC_ENC_GEMM_O, EPI_RESID_F32, sl.ctx, I, w.o, I, ns.hidden, dm, T, dm, I)));
     RC(gemm(e, st, ns.consumer(e, st, w.ln1, Gemm(PC_ENC_GEMM_FFN_IN, d.gated_gelu ? EPI_GEGLU_F16 : EPI_RELU_F16, ns.x(), dm, ns.fold ? w.ffn_in_f : w.ffn_in, dm,
                                                  sl.ffh, F, T, d.gated_gelu ? 2 * F : F, dm), own)));
     RC(ns.producer(e, st, Gemm(PC_ENC_GEMM_FFN_OUT, EPI_RESID_F32, sl.ffh, F, w.ffn_out, F, ns.hidden, dm, T, dm, F), !last));
+  }
+  // From here on the chain writes what the decoder of the slot's previous launch reads (the table at Slot): dec_seq_off, enc_out, cross_kv
+  RC(wait_prev_decoder(e, sl));
+  if (sl.off_of != sl.stage_no) {   // the decoder's own copy of the offsets: it outlives the generation the host stages next
+    HIPCHK(e, hipMemcpyAsync(sl.dec_seq_off, seq_off, (size_t)(sl.n_seq + 1) * sizeof(int), hipMemcpyDeviceToDevice, st));
+    sl.off_of = sl.stage_no;
   }
   rmsnorm(e, st, ns.hidden, e->enc_final_ln, sl.enc_out, nullptr, T);
   // the stacked K/V projections are only materialised when the decoder has too many rows for the query-side form
@@ -1355,7 +1398,7 @@ int run_decoder(rk_engine* e, Slot& sl, int Ld, const DecRows* rows = nullptr, c
   const bool tree = rows && rows->tree(), ragged = rows && !rows->tree();
   const int B = ragged ? rows->n_seq : sl.n_seq, M = rows ? rows->rows : B * Ld, I = e->inner, dm = d.d_model, F = d.d_ff;
   const bool have_kv = ragged ? rows->cross_kv : sl.have_cross_kv;
-  const int* seq_off = sl.d_seq_off + (ragged ? rows->seq0 : 0);
+  const int* seq_off = sl.dec_seq_off + (ragged ? rows->seq0 : 0);
   const DecLenClass lc = dec_len_class(e, Ld);
   if (tree && (have_kv || lc.one)) return fail(e, RK_ERR_STATE, "the tree form needs the query-side cross-attention and L_d >= 2");
   if (ragged && have_kv && !sl.have_cross_kv) return fail(e, RK_ERR_STATE, "the ragged pass needs the K / V the encoder did not materialise");
@@ -1420,7 +1463,7 @@ int run_decoder(rk_engine* e, Slot& sl, int Ld, const DecRows* rows = nullptr, c
     const Gemm cq = normed(w.ln1, Gemm(PC_DEC_GEMM, EPI_STORE_F16, ns.x(), dm, dfold ? w.cq_f : w.cq, dm, sl.dq, I, M, I, dm));
     if (!have_kv) {
       RC(run_xattn_chain(e, st, XAttnChain{cq.A, cq.lda, cq.W, w.ckT, e->cross_kv_w + ((size_t)l * 2 * I + I) * dm, cq.fold, cq.family,
-                                           sl.enc_out, sl.d_seq_off, rows ? rows->seq : nullptr, Ld, 0, sl.dq, sl.xqk, sl.xpart, sl.xstat, sl.xctx,
+                                           sl.enc_out, sl.dec_seq_off, rows ? rows->seq : nullptr, Ld, 0, sl.dq, sl.xqk, sl.xpart, sl.xstat, sl.xctx,
                                            sl.dctx, I, M, d.n_heads, dm, sl.maxL, sl.T, fuse_asked, head_width(e)}));
     } else {
       RC(gemm(e, st, cq));
@@ -1451,20 +1494,24 @@ int run_decoder(rk_engine* e, Slot& sl, int Ld, const DecRows* rows = nullptr, c
   return RK_OK;
 }
 
-// Encoder on s_enc, decoder on s_dec, ordered by events; the decoder of this slot's PREVIOUS batch must have
-// finished reading cross_kv before the encoder overwrites it.
+// Encoder on s_enc, decoder on s_dec, ordered by events.  The decoder of this slot's PREVIOUS launch must be done before the
+// encoder overwrites what it reads - the chain's last kernels only (run_encoder: wait_prev_decoder), so the layers before them run
+// beside that decoder.  Option enc_serial: the chain also starts behind the OTHER slot's last encoder chain - one encoder at a
+// time with the decoder before it alongside, instead of two encoder chains sharing the chip kernel by kernel; same bits.
 // query_side: the caller's decoder takes the query-side cross-attention whatever its length (rk_t5_generate: one row per step).
 // need_cross_kv: some decoder pass of the call reads the materialised K / V.
 int encoder_then_handoff_kv(rk_engine* e, Slot& sl, bool need_cross_kv) {
   hipStream_t se = enc_stream(e, sl), sd = dec_stream(e, sl);
   if (need_cross_kv && !sl.cross_kv) return refuse_wide(e, "encoder", "the materialised cross-attention K / V are not allocated");
-  if (sl.dec_pending && sd != se) HIPCHK(e, hipStreamWaitEvent(se, sl.ev_dec, 0));
-  int rc = run_encoder(e, sl, need_cross_kv);
+  static_assert(RK_SLOTS == 2, "the other slot");
+  const Slot& other = e->slots[(&sl - e->slots) ^ 1];
+  if (e->opt.enc_serial && sd != se && other.enc_gen >= 0) HIPCHK(e, hipStreamWaitEvent(se, other.ev_enc[other.enc_gen], 0));
+  sl.gen_launched = true;
+  const int rc = run_encoder(e, sl, need_cross_kv);
+  HIPCHK(e, hipEventRecord(sl.ev_enc[sl.gen], se));   // (also behind a chain that stopped half-way: what it enqueued reads the generation)
+  sl.enc_gen = sl.gen;
   if (rc) return rc;
-  if (sd != se) {
-    HIPCHK(e, hipEventRecord(sl.ev_enc, se));
-    HIPCHK(e, hipStreamWaitEvent(sd, sl.ev_enc, 0));
-  }
+  if (sd != se) HIPCHK(e, hipStreamWaitEvent(sd, sl.ev_enc[sl.gen], 0));
   return RK_OK;
 }
 
@@ -1584,11 +1631,14 @@ int stage_slot(rk_engine* e, int slot, const int32_t* tokens, const int32_t* seq
   Slot& sl = e->slots[slot];
   sl.staged = false;
   if ((rc = check_batch(e, &sl, tokens, seq_offsets, n_seq))) return rc;
-  // the slot's previous batch (encoder reads tokens, decoder reads seq_off) must be done before overwriting
-  if (sl.dec_pending) { HIPCHK(e, hipEventSynchronize(sl.ev_dec)); sl.dec_pending = false; }
-  HIPCHK(e, hipStreamSynchronize(enc_stream(e, sl)));
-  HIPCHK(e, hipMemcpy(sl.d_tokens, tokens, (size_t)sl.T * sizeof(int), hipMemcpyHostToDevice));
-  HIPCHK(e, hipMemcpy(sl.d_seq_off, seq_offsets, (size_t)(n_seq + 1) * sizeof(int), hipMemcpyHostToDevice));
+  // The generation no enqueued launch reads (the table at Slot): the other one if a launch took the current, else the current
+  // again.  Its last reader was an encoder chain, the slot's last but one at the latest: this waits for no decoder and not for
+  // the slot's newest launch.
+  const int g = sl.gen_launched ? sl.gen ^ 1 : sl.gen;
+  HIPCHK(e, hipEventSynchronize(sl.ev_enc[g]));   // (never recorded: returns at once)
+  HIPCHK(e, hipMemcpy(sl.stg_tokens[g], tokens, (size_t)sl.T * sizeof(int), hipMemcpyHostToDevice));
+  HIPCHK(e, hipMemcpy(sl.stg_seq_off[g], seq_offsets, (size_t)(n_seq + 1) * sizeof(int), hipMemcpyHostToDevice));
+  sl.gen = g; sl.gen_launched = false; ++sl.stage_no;
   sl.staged = true;
   return RK_OK;
 }
@@ -1890,7 +1940,8 @@ int rk_engine_create(const rk_model_desc* desc, int device_ordinal, rk_engine** 
   ok = ok && hipEventCreate(&e->t0) == hipSuccess && hipEventCreate(&e->t1) == hipSuccess &&
        hipEventCreateWithFlags(&e->t_tmp, hipEventDisableTiming) == hipSuccess;
   for (int i = 0; ok && i < RK_SLOTS; ++i)
-    ok = hipEventCreateWithFlags(&e->slots[i].ev_enc, hipEventDisableTiming) == hipSuccess &&
+    ok = hipEventCreateWithFlags(&e->slots[i].ev_enc[0], hipEventDisableTiming) == hipSuccess &&
+         hipEventCreateWithFlags(&e->slots[i].ev_enc[1], hipEventDisableTiming) == hipSuccess &&
          hipEventCreateWithFlags(&e->slots[i].ev_dec, hipEventDisableTiming) == hipSuccess;
   for (int i = 0; ok && i < 2 * RK_SLOTS; ++i) {
     rk_engine::SkWs& w = e->sk_ws[i];
@@ -1925,7 +1976,7 @@ void rk_engine_destroy(rk_engine* e) {
   for (auto& sl : e->slots) {
     if (sl.h_scores) hipHostFree(sl.h_scores);
     if (sl.idx.pin) hipHostFree(sl.idx.pin);
-    if (sl.ev_enc) hipEventDestroy(sl.ev_enc);
+    for (hipEvent_t ev : sl.ev_enc) if (ev) hipEventDestroy(ev);
     if (sl.ev_dec) hipEventDestroy(sl.ev_dec);
   }
   for (auto& r : e->prof_recs) { hipEventDestroy(r.a); hipEventDestroy(r.b); }
@@ -2124,7 +2175,8 @@ int rk_engine_finalize(rk_engine* e) {
     RC(dalloc(e, &sl.ctx, Tc * I)); RC(dalloc(e, &sl.ffh, Tc * F)); RC(dalloc(e, &sl.enc_out, Tc * dm));
     RC(dalloc(e, &sl.enc.xraw[0], Tc * dm)); RC(dalloc(e, &sl.enc.ssq[0], Tc * ((dm + 63) / 64))); RC(dalloc(e, &sl.enc.factors, Tc + 512));   // padded: the ping-pong GEMM reads the row factors of a whole 256-row tile
     HIPCHK(e, hipMemset(sl.enc.factors, 0, (Tc + 512) * sizeof(float)));
-    RC(dalloc(e, &sl.d_tokens, Tc)); RC(dalloc(e, &sl.d_seq_off, Bc + 1));
+    for (int g = 0; g < 2; ++g) { RC(dalloc(e, &sl.stg_tokens[g], Tc)); RC(dalloc(e, &sl.stg_seq_off[g], Bc + 1)); }
+    RC(dalloc(e, &sl.dec_seq_off, Bc + 1));
     // (128-wide heads: one decoder position only, which never reads the materialised K / V - 393 KB per token at t5-3b)
     if (!wide_heads(e)) RC(dalloc(e, &sl.cross_kv, (size_t)d.n_dec_layers * Tc * 2 * I));
     RC(dalloc(e, &sl.idx.d[IX_DEC_IDS], Mc)); RC(dalloc(e, &sl.idx.d[IX_LAST_ROWS], Bc)); RC(dalloc(e, &sl.idx.d[IX_OUT_IDS], 8192));
@@ -3327,6 +3379,7 @@ const OptionDesc kOptions[] = {
   {"gemm_sk", &rk_engine::Options::gemm_sk, 0, 2, nullptr, "ping-pong GEMM, fp32 residual projections with few tiles and a long K: K split over two workgroups (1: choose_ksplit), never (0), wherever it fits (2: tests)"},
   {"dec_cached_attn", &rk_engine::Options::dec_cached_attn, 0, 1, nullptr, "rk_t5_generate's self-attention: attn_dec_cached_kernel (1) or the cache append + attn_dec_kernel's tree form (0); same bits"},
   {"llama_dec_r", &rk_engine::Options::llama_dec_r, 0, 2, nullptr, "rk_llama_generate's attention: query heads per workgroup by plan_llama_dec_attn's rule (0), one (1), or, where a kv head has 7, all seven (2: measurement and tests; every cached K / V byte read once per step); same bits"},
+  {"enc_serial", &rk_engine::Options::enc_serial, 0, 1, nullptr, "two slots: an encoder chain starts behind the other slot's (1: one encoder at a time beside the decoder before it) or as soon as it is enqueued (0: two chains interleave); same bits"},
   {"gemm_split", &rk_engine::Options::gemm_split, 0, 1, nullptr, "rows beyond the ping-pong kernel's last whole round on a fill-in tile variant (1) or one launch (0); same bits"},
 #ifdef RK_MEASURE
   {"attn_ko", &rk_engine::Options::attn_ko, 0, 1 << 20, nullptr, "timing-only knock-outs of the attention kernels (measurement builds)"},
