@@ -511,6 +511,26 @@ int rk_debug_gemm_bench(rk_engine* e, int M, int N, int K, int epi, int iters, f
  * "qkv" [T,3I], "ctx" [T,I], "dec_hidden" [B*Ld,d], "llama_last" [n_seq,hidden] (the final-normed last rows of the most recent
  * Llama call: after rk_llama_generate, the rows the last step's head read; after rk_llama_session_run, its n_slots rows). Returns number of floats written or a negative status. */
 int64_t rk_debug_read(rk_engine* e, const char* name, float* out, int64_t max_floats);
+/* debug: the table of decoder graphs and what became of every decoder chain since the engine was created (csrc/rk_engine.hip:
+ * run_graphed, the one function every chain of rk_t5_score / _compare / _greedy / _greedy2 / _generate, rk_llama_generate and
+ * rk_llama_session_run goes through; rk_t5_qlm and rk_t5_qlm_many launch outside it and count nowhere).  A chain is keyed by its
+ * kind, slot, shapes, buffer generations and the options epoch (every rk_engine_set_option starts a new epoch: no graph captured
+ * under other options is ever replayed).  Per key: the first sighting runs eagerly, the second is captured, instantiated and
+ * launched, later ones replay; a key whose capture fails runs eagerly from then on.  Every call is exactly one of
+ *   eager      the chain's kernels were launched one by one: dec_graph = 0, profiling on, a first sighting, a failed key
+ *   captures   the chain was captured, instantiated and launched as a graph
+ *   replays    the key's graph was launched
+ * and failed counts the keys marked failed (each also ran eagerly, unless the chain itself returned an error).
+ * The table holds at most RK_GRAPH_CACHE_KEYS keys: the new key that would pass the bound erases every other entry, after
+ * draining the streams a graph may be replaying on; evictions counts the instantiated graphs destroyed that way.  n_keys = entries
+ * in the table (<= max_keys = RK_GRAPH_CACHE_KEYS at every return), n_ready = entries that hold an instantiated graph.
+ * Host state only: nothing is launched or waited for. */
+#define RK_GRAPH_CACHE_KEYS 256
+typedef struct rk_debug_graph_stats_t {
+  int n_keys, n_ready, max_keys;
+  int64_t eager, captures, replays, failed, evictions;
+} rk_debug_graph_stats_t;
+int rk_debug_graph_stats(rk_engine* e, rk_debug_graph_stats_t* out);
 
 #ifdef __cplusplus
 }

@@ -241,9 +241,11 @@ struct rk_engine {
     bool open = false; int n_slots = 0, max_len = 0, cap = 0, seen = 0;   // seen: the session word at the last read-back
     std::vector<int> busy, told, len, max_new, col, done;                 // per slot; told: its finish was returned by a run
   } ls;
-  // decoder chains as HIP graphs: key = everything the launch parameters of a chain depend on
+  // decoder chains as HIP graphs: key = everything the launch parameters of a chain depend on; at most RK_GRAPH_CACHE_KEYS keys
+  // (run_graphed); graph_count: what run_graphed did since the engine was created (rk_debug_graph_stats)
   struct GraphEntry { int seen = 0; bool failed = false; hipGraphExec_t exec = nullptr; };
   std::map<std::vector<int>, GraphEntry> graphs; int opt_epoch = 0;
+  struct GraphCount { int64_t eager = 0, captures = 0, replays = 0, failed = 0, evictions = 0; } graph_count;
   // score collection across GPUs (K9): one RCCL communicator per engine = per process = per GPU
   ncclComm_t comm = nullptr; int comm_rank = 0, comm_world = 1;
   float* d_gather[RK_SLOTS] = {nullptr}; float* h_gather[RK_SLOTS] = {nullptr}; size_t gather_cap = 0;
@@ -1646,33 +1648,57 @@ int stage_slot(rk_engine* e, int slot, const int32_t* tokens, const int32_t* seq
 // The decoder chain of a call is ~300 dependent launches of kernels that run for a few microseconds each: issued eagerly
 // it is bound by the host's launch rate (about 10 us per launch end to end), replayed as ONE HIP graph by the GPU's own
 // dependent-kernel boundary (1-2 us).  `body` enqueues the chain on `st`; the second time a key is seen the chain is
-// captured, instantiated and cached, from then on it is replayed.  The key holds every value the launch parameters
-// depend on (shapes, options epoch); buffers are per-slot and never move.  Profiling runs stay eager (per-kernel events).
+// captured, instantiated and cached, from then on it is replayed.  A replay carries the launch arguments of the call it was
+// captured from, so the key holds every value those depend on (shapes, the chunk count or the longest sequence, buffer
+// generations, the options epoch); everything else a chain reads (lengths, ids, positions) lives in device memory that is
+// per-slot and never moves (tests/test_gpu_graph_replay.py replays every kind on batches that share a key and differ in the rest).
+// Profiling runs and dec_graph = 0 stay eager (per-kernel events) and leave the table alone.
+// The table holds at most RK_GRAPH_CACHE_KEYS keys: the key that would pass the bound ERASES every other entry (evict_graphs) -
+// their graphs, their sightings, and the entries of epochs that no call can reach any more - and the keys still in use come back
+// on their next two sightings.  One eviction per RK_GRAPH_CACHE_KEYS new keys; every outcome is counted (rk_debug_graph_stats).
 enum GraphKind { GK_T5_SCORE, GK_T5_GREEDY_STEP, GK_T5_GREEDY2, GK_T5_GENERATE_STEP, GK_LLAMA_STEP, GK_T5_COMPARE, GK_LLAMA_SESSION_STEP };   // which chain: the key's first int
+// Every entry but `keep` goes.  A graph of the other slot, or of this stream's previous call, may still be replaying: both slots'
+// decoder streams and slot 0's encoder stream (the Llama family's, and every decoder's with overlap = 0) are drained first, so
+// no graph is destroyed under a launch.  (Erasing the other elements of a std::map leaves the reference to `keep` valid.)
+int evict_graphs(rk_engine* e, const rk_engine::GraphEntry* keep) {
+  for (Slot& sl : e->slots) HIPCHK(e, hipStreamSynchronize(sl.sd));
+  HIPCHK(e, hipStreamSynchronize(e->slots[0].se));
+  for (auto it = e->graphs.begin(); it != e->graphs.end();) {
+    if (&it->second == keep) { ++it; continue; }
+    if (it->second.exec) { hipGraphExecDestroy(it->second.exec); ++e->graph_count.evictions; }
+    it = e->graphs.erase(it);
+  }
+  return RK_OK;
+}
 template <class F>
 int run_graphed(rk_engine* e, hipStream_t st, std::vector<int> key, F&& body) {
+  auto& n = e->graph_count;
+  auto eager = [&]() -> int { ++n.eager; return body(); };
   key.push_back(e->opt_epoch);
-  if (!e->opt.dec_graph || e->prof_on) return body();
+  if (!e->opt.dec_graph || e->prof_on) return eager();
   auto& g = e->graphs[key];
-  if (g.exec) { HIPCHK(e, hipGraphLaunch(g.exec, st)); return RK_OK; }
-  if (g.failed || g.seen++ == 0) return body();          // first sighting: eager (also does the one-off kernel attribute calls)
-  if (e->graphs.size() > 256) {                           // bounded cache: drop everything but this key's slot
-    for (auto& kv : e->graphs) if (kv.second.exec && &kv.second != &g) { hipGraphExecDestroy(kv.second.exec); kv.second.exec = nullptr; kv.second.seen = 0; }
+  if (g.exec) { HIPCHK(e, hipGraphLaunch(g.exec, st)); ++n.replays; return RK_OK; }
+  if ((int)e->graphs.size() > RK_GRAPH_CACHE_KEYS) {      // bounded cache: this key passed the bound, everything else goes
+    const int rc = evict_graphs(e, &g);
+    if (rc) return rc;
   }
+  if (g.failed || g.seen++ == 0) return eager();          // first sighting: eager (also does the one-off kernel attribute calls)
+  auto failed = [&]() -> int { g.failed = true; ++n.failed; return eager(); };   // nothing was executed during a capture: run it now
   hipGraph_t graph = nullptr;
-  if (hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) != hipSuccess) { (void)hipGetLastError(); g.failed = true; return body(); }
+  if (hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) != hipSuccess) { (void)hipGetLastError(); return failed(); }
   const int rc = body();
   const hipError_t ec = hipStreamEndCapture(st, &graph);
   if (rc != RK_OK || ec != hipSuccess || !graph) {
     (void)hipGetLastError();
     if (graph) hipGraphDestroy(graph);
-    g.failed = true;
-    return rc != RK_OK ? rc : body();                     // nothing was executed during the capture: run it now
+    if (rc != RK_OK) { g.failed = true; ++n.failed; return rc; }
+    return failed();
   }
   const hipError_t ei = hipGraphInstantiate(&g.exec, graph, nullptr, nullptr, 0);
   hipGraphDestroy(graph);
-  if (ei != hipSuccess || !g.exec) { (void)hipGetLastError(); g.exec = nullptr; g.failed = true; return body(); }
+  if (ei != hipSuccess || !g.exec) { (void)hipGetLastError(); g.exec = nullptr; return failed(); }
   HIPCHK(e, hipGraphLaunch(g.exec, st));
+  ++n.captures;
   return RK_OK;
 }
 
@@ -4219,6 +4245,17 @@ int rk_debug_gemm_bench(rk_engine* e, int M, int N, int K, int epi, int iters, f
   HIPCHK(e, hipGetLastError());
   *out_ms = ms / iters;
   hipFree(dA); hipFree(dW); hipFree(dC); if (dX) hipFree(dX); if (dS) hipFree(dS);
+  return RK_OK;
+}
+
+// debug: the decoder graph table and run_graphed's counters (host state only: nothing is launched or waited for)
+int rk_debug_graph_stats(rk_engine* e, rk_debug_graph_stats_t* out) {
+  if (!e || !out) return RK_ERR_INVALID;
+  int ready = 0;
+  for (const auto& kv : e->graphs) ready += kv.second.exec != nullptr;
+  const auto& n = e->graph_count;
+  out->n_keys = (int)e->graphs.size(); out->n_ready = ready; out->max_keys = RK_GRAPH_CACHE_KEYS;
+  out->eager = n.eager; out->captures = n.captures; out->replays = n.replays; out->failed = n.failed; out->evictions = n.evictions;
   return RK_OK;
 }
 

@@ -91,6 +91,12 @@ class RkDebugRowsCall(C.Structure):
                 ("plan_only", C.c_int), ("out_grid", C.c_int * 3), ("out_tparam", C.c_int), ("out_variant", C.c_int)]
 
 
+class RkDebugGraphStats(C.Structure):
+    """rk_debug_graph_stats_t of include/rk_engine.h, field for field."""
+    _fields_ = [(n, C.c_int) for n in ("n_keys", "n_ready", "max_keys")] + \
+               [(n, C.c_int64) for n in ("eager", "captures", "replays", "failed", "evictions")]
+
+
 DEBUG_SENTINEL = 0xCD                      # RK_DEBUG_SENTINEL: the byte the guard bands of rk_debug_gemm_ex are filled with
 DEBUG_BAND_ROWS = 256
 GEMM_OUT_DTYPE = {0: np.float16, 1: np.float32, 2: np.float16, 3: np.float16, 4: np.float32, 5: np.float16, 6: np.float32, 7: np.float32}
@@ -162,6 +168,7 @@ ABI = {
     "rk_debug_rows": (C.c_int, [C.c_void_p, _P(RkDebugRowsCall)]),
     "rk_debug_gemm_bench": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _f32p]),
     "rk_debug_read": (C.c_int64, [C.c_void_p, C.c_char_p, _f32p, C.c_int64]),
+    "rk_debug_graph_stats": (C.c_int, [C.c_void_p, _P(RkDebugGraphStats)]),
 }
 
 _lib = None
@@ -746,6 +753,13 @@ class RkEngine:
         if got < 0:
             self._chk(int(got))
         return out[:got]
+
+    def graph_stats(self) -> dict:
+        """The decoder graph table and its counters (rk_debug_graph_stats): n_keys, n_ready, max_keys, and since the engine was
+        created eager, captures, replays, failed, evictions."""
+        st = RkDebugGraphStats()
+        self._chk(self.lib.rk_debug_graph_stats(self.h, C.byref(st)))
+        return {k: int(getattr(st, k)) for k, _ in RkDebugGraphStats._fields_}
 
 
 class RkLlamaEngine(RkEngine):
