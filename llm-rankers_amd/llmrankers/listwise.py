@@ -16,8 +16,8 @@ from typing import List, Optional
 import numpy as np
 
 from ._batching import tokenize_prompts
-from ._lockstep import Lockstep
-from .rankers import LlmRanker, SearchResult
+from ._lockstep import Lockstep, drive
+from .rankers import LlmRanker, SearchResult, close_counters, tally
 
 # the "complete" prompt of the reference (ref: listwise.py:85-104) - model input, byte for byte
 HEAD = ("This is RankGPT, an intelligent assistant that can rank passages based on their relevancy to the query.\n\n"
@@ -266,10 +266,7 @@ class ListwiseLlmRanker(LlmRanker):
         self.total_compare = 0
         self.total_prompt_tokens = 0
         self.total_completion_tokens = 0
-        walk = Lockstep({0: self._walk(ranking)})
-        while walk:
-            walk.advance([self.compare(query, window) for window in walk.pending()[1]])
-        return walk.returned[0]
+        return drive(self._walk(ranking), lambda windows: [self.compare(query, window) for window in windows])
 
     def rerank_many(self, items):
         """Several queries at once: `items` = [(query, ranking), ...] -> (results, counters); results[i] and counters[i] =
@@ -280,17 +277,8 @@ class ListwiseLlmRanker(LlmRanker):
         walks = Lockstep({q: self._walk(ranking) for q, (_, ranking) in enumerate(items)})
         while walks:
             keys, windows = walks.pending()
-            outs, ptok, ctok = self._compare_windows([items[q][0] for q in keys], windows)
-            for q, p, c in zip(keys, ptok, ctok):
-                counts[q][0] += 1
-                counts[q][1] += p
-                counts[q][2] += c
-            walks.advance(outs)
-        results = [walks.returned[q] for q in range(len(items))]
-        counters = [tuple(c) for c in counts]
-        if counters:
-            self.total_compare, self.total_prompt_tokens, self.total_completion_tokens = counters[-1]
-        return results, counters
+            walks.advance(tally(counts, keys, *self._compare_windows([items[q][0] for q in keys], windows)))
+        return [walks.returned[q] for q in range(len(items))], close_counters(self, counts)
 
     def truncate(self, text, length):
         return self.tokenizer.convert_tokens_to_string(self.tokenizer.tokenize(text)[:length])

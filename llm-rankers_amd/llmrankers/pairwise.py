@@ -20,13 +20,33 @@ from typing import List
 import numpy as np
 
 from ._batching import batches, padded_token_count, tokenize_prompts
-from ._lockstep import Lockstep
+from ._lockstep import Lockstep, alternate, drive, heapsort_steps
 from .pointwise import _softmax_first
-from .rankers import LlmRanker, SearchResult, top_k_then_rest
+from .rankers import LlmRanker, SearchResult, close_counters, rerank_each, tally, top_k_then_rest
 
 PROMPT = ('Given a query "{query}", which of the following two passages is more relevant to the query?\n\n'
           'Passage A: "{doc1}"\n\nPassage B: "{doc2}"\n\nOutput Passage A or Passage B:')
 WIN = ["Passage A", "Passage B"]       # the first passage of the pair wins iff the A/B prompt says A and the B/A prompt says B
+
+
+def sift(arr, n, i):
+    """Sift node i of the binary max-heap arr[:n] down (ref: pairwise.py:133-147, a loop instead of tail recursion), as a chain
+    of _lockstep: yields one ordered pair [(a, b)] at a time and is sent its verdict `a > b`.  At most two compares per level,
+    in this order: (left, i) then (right, largest)."""
+    while True:
+        largest, left, right = i, 2 * i + 1, 2 * i + 2
+        if left < n:
+            (gt,) = yield [(arr[left], arr[i])]
+            if gt:
+                largest = left
+        if right < n:
+            (gt,) = yield [(arr[right], arr[largest])]
+            if gt:
+                largest = right
+        if largest == i:
+            return
+        arr[i], arr[largest] = arr[largest], arr[i]
+        i = largest
 
 
 class PairwiseLlmRanker(LlmRanker):
@@ -126,32 +146,6 @@ class PairwiseLlmRanker(LlmRanker):
         return self.compare(query, [a_text, b_text]) == WIN
 
     # -- sort drivers --------------------------------------------------------------------------------------------
-    def _heapify(self, arr, n, i, gt):
-        # ref: pairwise.py:133-147 (binary max-heap sift-down; at most two comparisons per level, in this order)
-        while True:
-            largest, left, right = i, 2 * i + 1, 2 * i + 2
-            if left < n and gt(arr[left], arr[i]):
-                largest = left
-            if right < n and gt(arr[right], arr[largest]):
-                largest = right
-            if largest == i:
-                return
-            arr[i], arr[largest] = arr[largest], arr[i]
-            i = largest
-
-    def _heap_sort(self, arr, k, gt):
-        # ref: pairwise.py:149-162
-        n = len(arr)
-        for i in range(n // 2, -1, -1):
-            self._heapify(arr, n, i, gt)
-        ranked = 0
-        for i in range(n - 1, 0, -1):
-            arr[i], arr[0] = arr[0], arr[i]
-            ranked += 1
-            if ranked == k:
-                break
-            self._heapify(arr, i, 0, gt)
-
     def _allpair(self, query, ranking):
         # ref: pairwise.py:169-216 — every unordered pair in both orders, one generation each; a win needs both
         # orderings to agree, anything else is half a point each
@@ -188,8 +182,8 @@ class PairwiseLlmRanker(LlmRanker):
         if self.method == "allpair":
             ranking = self._allpair(query, ranking)
         elif self.method == "heapsort":
-            arr = list(ranking)
-            self._heap_sort(arr, self.k, lambda a, b: self._first_wins(query, a.text, b.text))
+            arr = list(ranking)                                # ref: pairwise.py:149-162, one compare at a time
+            drive(heapsort_steps(arr, self.k, 2, sift, False), lambda pairs: [self._first_wins(query, a.text, b.text) for a, b in pairs])
             ranking = [SearchResult(docid=d.docid, score=-i, text=None) for i, d in enumerate(reversed(arr))]
         elif self.method == "bubblesort":
             # ref: pairwise.py:246-269 — the reference's variant that skips pairs already known to be in order
@@ -313,71 +307,12 @@ class DuoT5LlmRanker(PairwiseLlmRanker):
         return (getattr(self, "batch_independent_compares", False) and "compare" not in self.__dict__
                 and type(self).compare is DuoT5LlmRanker.compare)
 
-    # ---- the sort: pure index logic, must reproduce the reference's comparisons exactly ----------------------------
-    # A generator that yields a list of ordered pairs (a, b) whose compares are independent and is sent their verdicts `a > b`.
-    def _sift(self, arr, n, i):
-        """Sift node i of the binary max-heap arr[:n] down (ref: pairwise.py:133-147, a loop instead of tail recursion): at most
-        two compares per level, (left, i) then (right, largest)."""
-        while True:
-            largest, left, right = i, 2 * i + 1, 2 * i + 2
-            if left < n:
-                (gt,) = yield [(arr[left], arr[i])]
-                if gt:
-                    largest = left
-            if right < n:
-                (gt,) = yield [(arr[right], arr[largest])]
-                if gt:
-                    largest = right
-            if largest == i:
-                return
-            arr[i], arr[largest] = arr[largest], arr[i]
-            i = largest
-
-    def _heapsort_steps(self, arr, k, level_batched):
-        """ref: pairwise.py:149-162.  The build phase sifts the nodes n//2 .. 0.  Reference order: one after another.  Level
-        order: that walk goes level by level from the deepest one, and the nodes of a level root disjoint subtrees, so their
-        sift-downs touch disjoint array slots and commute - they advance in lock step, one list of pairs per step: the array,
-        the set of compares and every counter end up identical, only the order of compares inside a level differs.  Extraction
-        is a chain: one compare at a time."""
-        n = len(arr)
-        if level_batched:
-            levels, first, width = [], 0, 1                   # the nodes of depth d occupy [first, first + 2^d)
-            while first <= n // 2:
-                levels.append(range(min(first + width - 1, n // 2), first - 1, -1))
-                first, width = first + width, width * 2
-            for level in reversed(levels):
-                build = Lockstep({j: self._sift(arr, n, i) for j, i in enumerate(level)})
-                while build:
-                    build.advance((yield build.pending()[1]))
-        else:
-            for i in range(n // 2, -1, -1):
-                yield from self._sift(arr, n, i)
-        ranked = 0
-        for m in range(n - 1, 0, -1):
-            arr[m], arr[0] = arr[0], arr[m]
-            ranked += 1
-            if ranked == k:
-                break
-            yield from self._sift(arr, m, 0)
-
     def _compare_many(self, query, windows) -> List[bool]:
         """Independent compares of one query in ONE engine call: same verdicts and counters as `compare()` on each in turn."""
         verdicts, prompt_tokens = self._compare_pairs([query] * len(windows), [(a.text, b.text) for a, b in windows])
         self.total_compare += len(windows)
         self.total_prompt_tokens += sum(prompt_tokens)
         return verdicts
-
-    def _drive(self, query, steps, level_batched):
-        """Run a sort for one query.  Reference order: every pair through `compare`, one at a time (looked up on the instance:
-        tests, golden generators and subclasses replace it); level order: every yielded list is one `_compare_many`."""
-        verdicts = None
-        while True:
-            try:
-                windows = steps.send(verdicts)
-            except StopIteration:
-                return
-            verdicts = (self._compare_many(query, windows) if level_batched
-                        else [self.compare(query, [a.text, b.text]) for a, b in windows])
 
     def rerank(self, query: str, ranking: List[SearchResult]) -> List[SearchResult]:
         # ref: pairwise.py:320-352.  The sort works on a new list: the caller's is left as it is.
@@ -388,8 +323,12 @@ class DuoT5LlmRanker(PairwiseLlmRanker):
         if self.method != "heapsort":
             raise NotImplementedError(f'Method {self.method} is not implemented.')
         arr = list(ranking)
+        # the binary heapsort with the build phase level-batched (one `_compare_many` per yielded list of pairs); a replaced
+        # compare() gets the reference's order, one pair at a time (looked up on the instance: tests and subclasses replace it)
         level_batched = self._batched_ok()
-        self._drive(query, self._heapsort_steps(arr, self.k, level_batched), level_batched)
+        drive(heapsort_steps(arr, self.k, 2, sift, level_batched),
+              (lambda pairs: self._compare_many(query, pairs)) if level_batched
+              else (lambda pairs: [self.compare(query, [a.text, b.text]) for a, b in pairs]))
         return top_k_then_rest(list(reversed(arr)), original_docids, self.k)
 
     # ---- several queries at once ---------------------------------------------------------------------------
@@ -403,68 +342,25 @@ class DuoT5LlmRanker(PairwiseLlmRanker):
         blocking call for that round.  A replaced compare(), or fewer than two queries: one rerank per query."""
         items = list(items)
         if self.method != "heapsort" or not self._batched_ok() or len(items) < 2:
-            out, counters = [], []
-            for query, ranking in items:
-                out.append(self.rerank(query, ranking))
-                counters.append((self.total_compare, self.total_prompt_tokens, self.total_completion_tokens))
-            return out, counters
+            return rerank_each(self, items)
         originals = [[doc.docid for doc in ranking] for _, ranking in items]
         arrs = [list(ranking) for _, ranking in items]
         counts = [[0, 0, 0] for _ in items]
-        chains = Lockstep({q: self._heapsort_steps(arr, self.k, True) for q, arr in enumerate(arrs)})
+        chains = Lockstep({q: heapsort_steps(arr, self.k, 2, sift, True) for q, arr in enumerate(arrs)})
 
         def call_args(keys, windows):
             return [items[q][0] for q in keys], [(a.text, b.text) for a, b in windows]
 
-        def counted(keys, verdicts, prompt_tokens):
-            for q, p in zip(keys, prompt_tokens):
-                counts[q][0] += 1
-                counts[q][1] += p
-            return verdicts
+        def blocking(keys, windows):
+            return tally(counts, keys, *self._compare_pairs(*call_args(keys, windows)))
 
         if len(chains.live()) >= 4 and self._can_alternate():
             # two groups of chains alternate over the engine's two batch slots: while one group's call is on the GPU the host
-            # advances the other group's heaps, tokenises its prompts and launches them
-            groups = [Lockstep({}), Lockstep({})]
-            for i, q in enumerate(chains.live()):
-                groups[i % 2].absorb(chains, [q])
-            inflight = []                                            # [(group index, keys, launched)] oldest first
-
-            def collect():
-                g, keys, launched = inflight.pop(0)
-                groups[g].advance(counted(keys, *self._collect_pairs(launched)))
-
-            try:
-                while groups[0] or groups[1]:
-                    for g in (0, 1):                                 # group g's turn: its own call is the oldest one in flight
-                        while any(entry[0] == g for entry in inflight):
-                            collect()
-                        if not groups[g]:
-                            continue
-                        keys, windows = groups[g].pending()
-                        launched = self._launch_pairs(*call_args(keys, windows), slot=g)
-                        if launched is not None:
-                            inflight.append((g, keys, launched))
-                            continue
-                        # this round does not fit one engine call (the build phase of many long heaps): the slots are drained
-                        # and it goes through the blocking call, which cuts it; the next round is launched as before
-                        while inflight:
-                            collect()
-                        groups[g].advance(counted(keys, *self._compare_pairs(*call_args(keys, windows))))
-            finally:
-                # whatever raised above: a call still queued on its slot is collected before the exception leaves -
-                # compare_async's contract is that nothing else runs on the engine until then
-                for _, _, launched in inflight:
-                    try:
-                        self._collect_pairs(launched)
-                    except Exception:
-                        pass
-            for group in groups:
-                chains.absorb(group)
+            # advances the other group's heaps, tokenises its prompts and launches them; a round that does not fit one engine
+            # call (the build phase of many long heaps) goes through the blocking call, which cuts it
+            alternate(chains, lambda keys, windows, slot: self._launch_pairs(*call_args(keys, windows), slot=slot),
+                      lambda keys, launched: tally(counts, keys, *self._collect_pairs(launched)), blocking)
         while chains:
-            keys, windows = chains.pending()
-            chains.advance(counted(keys, *self._compare_pairs(*call_args(keys, windows))))
+            chains.advance(blocking(*chains.pending()))
         results = [top_k_then_rest(list(reversed(arr)), original, self.k) for arr, original in zip(arrs, originals)]
-        counters = [tuple(c) for c in counts]
-        self.total_compare, self.total_prompt_tokens, self.total_completion_tokens = counters[-1]
-        return results, counters
+        return results, close_counters(self, counts)

@@ -10,7 +10,7 @@ from typing import List
 import numpy as np
 
 from ._batching import batches, padded_token_count, tokenize_prompts
-from .rankers import LlmRanker, SearchResult
+from .rankers import LlmRanker, SearchResult, rerank_each
 
 YES_NO_PROMPT = "Passage: {text}\nQuery: {query}\nDoes the passage answer the query? Answer 'Yes' or 'No'"
 QLM_PROMPT = "Passage: {text}\nPlease write a question based on this passage."
@@ -296,11 +296,7 @@ class PointwiseLlmRanker(LlmRanker):
             if spec is None or specs[0] is None or not self._can_share(spec, specs[0] if len(specs) > 1 else None):
                 grouped = False
         if not grouped or not items:
-            out, counters = [], []
-            for query, ranking in items:
-                out.append(self.rerank(query, ranking))
-                counters.append((self.total_compare, self.total_prompt_tokens, self.total_completion_tokens))
-            return out, counters
+            return rerank_each(self, items)
         counters, sizes = [], []
 
         def tokenised_queries():

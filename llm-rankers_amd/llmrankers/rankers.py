@@ -28,6 +28,32 @@ def top_k_then_rest(ordered, original_docids, k) -> List[SearchResult]:
     return results
 
 
+def rerank_each(ranker, items):
+    """The fallback of every `rerank_many`: one `rerank` per query -> (results, the counters each call left)."""
+    out, counters = [], []
+    for query, ranking in items:
+        out.append(ranker.rerank(query, ranking))
+        counters.append((ranker.total_compare, ranker.total_prompt_tokens, ranker.total_completion_tokens))
+    return out, counters
+
+
+def tally(counts, keys, answers, prompt_tokens, completion_tokens=None):
+    """One answered compare per key: counts[q] = [compares, prompt tokens, completion tokens] of query q; -> answers."""
+    for q, p, c in zip(keys, prompt_tokens, completion_tokens or [0] * len(keys)):
+        counts[q][0] += 1
+        counts[q][1] += p
+        counts[q][2] += c
+    return answers
+
+
+def close_counters(ranker, counts):
+    """-> the per-query counters as tuples; the ranker's own totals are the last query's, as after one `rerank` per query."""
+    counters = [tuple(c) for c in counts]
+    if counters:
+        ranker.total_compare, ranker.total_prompt_tokens, ranker.total_completion_tokens = counters[-1]
+    return counters
+
+
 class LlmRanker:
     """Interface every ranker implements: rerank a candidate list for a query; truncate text by tokens."""
 

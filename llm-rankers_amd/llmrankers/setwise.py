@@ -14,8 +14,8 @@ from typing import List
 import numpy as np
 
 from ._batching import tokenize_prompts
-from ._lockstep import Lockstep
-from .rankers import LlmRanker, SearchResult, top_k_then_rest
+from ._lockstep import Lockstep, alternate, drive, heapsort_steps
+from .rankers import LlmRanker, SearchResult, close_counters, rerank_each, tally, top_k_then_rest
 
 random.seed(929)   # same import-time seeding as the reference (ref: setwise.py:18): permutation voting depends on it
 
@@ -228,7 +228,7 @@ class SetwiseLlmRanker(LlmRanker):
 
     def _launch_windows(self, queries: List[str], doc_lists: List[List], slot: int):
         """First half of `_compare_windows` (likelihood): prompts, tokens, ONE engine call enqueued on `slot`; returns at once.
-        None when the windows do not fit one engine call (the caller then takes the blocking path)."""
+        None when the windows do not fit one engine call (the caller then takes the blocking call for this round)."""
         if any(len(docs) == 0 for docs in doc_lists):
             raise IndexError("list index out of range")
         texts = [self._prompt(q, self.CHARACTERS[:len(docs)], [d.text for d in docs]) for q, docs in zip(queries, doc_lists)]
@@ -276,32 +276,6 @@ class SetwiseLlmRanker(LlmRanker):
             arr[i], arr[largest] = arr[largest], arr[i]
             i = largest
 
-    def _heapsort_steps(self, arr, k, level_batched):
-        """ref: setwise.py:219-232.  The build phase sifts the nodes n//c .. 0.  Reference order: one after another.  Level
-        order: the reference's walk goes level by level from the deepest one, and the nodes of a level root disjoint subtrees,
-        so their sift-downs touch disjoint array slots and commute - they advance in lock step, one list of windows per step:
-        the array, the set of compares and every counter end up identical, only the order of compares inside a level differs."""
-        c, n = self.num_child, len(arr)
-        if level_batched:
-            levels, first, width = [], 0, 1                   # the nodes of depth d occupy [first, first + c^d)
-            while first <= n // c:
-                levels.append(range(min(first + width - 1, n // c), first - 1, -1))
-                first, width = first + width, width * c
-            for level in reversed(levels):
-                build = Lockstep({j: self._sift(arr, n, i) for j, i in enumerate(level)})
-                while build:
-                    build.advance((yield build.pending()[1]))
-        else:
-            for i in range(n // c, -1, -1):
-                yield from self._sift(arr, n, i)
-        ranked = 0
-        for m in range(n - 1, 0, -1):
-            arr[m], arr[0] = arr[0], arr[m]
-            ranked += 1
-            if ranked == k:
-                break
-            yield from self._sift(arr, m, 0)
-
     def _bubblesort_steps(self, ranking):
         # ref: setwise.py:243-273 — sliding window of num_child+1 bubbling the best document to position i,
         # with the reference's `last_start` shortcut that skips windows already known to be in order.
@@ -333,30 +307,27 @@ class SetwiseLlmRanker(LlmRanker):
 
     def _sort_steps(self, ranking, level_batched):
         if self.method == "heapsort":
-            return self._heapsort_steps(ranking, self.k, level_batched)
+            return heapsort_steps(ranking, self.k, self.num_child, self._sift, level_batched)      # ref: setwise.py:219-232
         if self.method == "bubblesort":
             return self._bubblesort_steps(ranking)
         raise NotImplementedError(f'Method {self.method} is not implemented.')
 
-    def _drive(self, query, steps, level_batched):
-        """Run a sort for one query.  Reference order: every window through `compare`, one at a time (looked up on the
-        instance: tests, golden generators and subclasses replace it); level order: every yielded list is one `_compare_many`."""
-        labels = None
-        while True:
-            try:
-                windows = steps.send(labels)
-            except StopIteration:
-                return
-            labels = self._compare_many(query, windows) if level_batched else [self.compare(query, w) for w in windows]
+    def _answer(self, query, level_batched):
+        """How the windows of one query's sort are answered.  Reference order: every window through `compare`, one at a time
+        (looked up on the instance: tests, golden generators and subclasses replace it); level order: every yielded list is one
+        `_compare_many`."""
+        if level_batched:
+            return lambda windows: self._compare_many(query, windows)
+        return lambda windows: [self.compare(query, w) for w in windows]
 
     def heapify(self, arr, n, i, query):
         # ref: setwise.py:200-217, always one compare at a time
-        self._drive(query, self._sift(arr, n, i), False)
+        drive(self._sift(arr, n, i), self._answer(query, False))
 
     def heapSort(self, arr, query, k):
         # ref: setwise.py:219-232
         level_batched = self._batched_ok()
-        self._drive(query, self._heapsort_steps(arr, k, level_batched), level_batched)
+        drive(heapsort_steps(arr, k, self.num_child, self._sift, level_batched), self._answer(query, level_batched))
 
     def rerank(self, query: str, ranking: List[SearchResult]) -> List[SearchResult]:
         # ref: setwise.py:234-313.  NB: like the reference, the caller's list is re-ordered in place.
@@ -365,7 +336,7 @@ class SetwiseLlmRanker(LlmRanker):
         self.total_completion_tokens = 0
         self.total_prompt_tokens = 0
         level_batched = self.method == "heapsort" and self._batched_ok()
-        self._drive(query, self._sort_steps(ranking, level_batched), level_batched)
+        drive(self._sort_steps(ranking, level_batched), self._answer(query, level_batched))
         return top_k_then_rest(list(reversed(ranking)) if self.method == "heapsort" else ranking, original_docids, self.k)
 
     # ---- several queries at once ---------------------------------------------------------------------------
@@ -380,11 +351,7 @@ class SetwiseLlmRanker(LlmRanker):
         subclass - Rank-R1's has a rerank_many of its own) is one rerank per query."""
         items = list(items)
         if self.method not in ("heapsort", "bubblesort") or not self._batched_ok() or len(items) < 2:
-            out, counters = [], []
-            for query, ranking in items:
-                out.append(self.rerank(query, ranking))
-                counters.append((self.total_compare, self.total_prompt_tokens, self.total_completion_tokens))
-            return out, counters
+            return rerank_each(self, items)
         originals = [[doc.docid for doc in ranking] for _, ranking in items]
         counts = [[0, 0, 0] for _ in items]
         chains = Lockstep({q: self._sort_steps(ranking, True) for q, (_, ranking) in enumerate(items)})
@@ -392,67 +359,23 @@ class SetwiseLlmRanker(LlmRanker):
         def queries_of(keys):
             return [items[q][0] for q in keys]
 
-        def counted(keys, labels, prompt_tokens, completion_tokens):
-            for q, p, c in zip(keys, prompt_tokens, completion_tokens):
-                counts[q][0] += 1
-                counts[q][1] += p
-                counts[q][2] += c
-            return labels
+        def blocking(keys, windows):
+            return tally(counts, keys, *self._compare_windows(queries_of(keys), windows))
 
         if len(chains.live()) >= 4 and self._can_alternate():
             # Two groups of chains alternate over the engine's two batch slots: while one group's call is on the GPU the host
             # advances the other group's heaps, builds and tokenises its prompts and launches them - the launch-bound decoder
             # chain of one call runs under the encoder of the next, and the host part of a step is hidden.  A chain sees the
-            # same labels as alone (batch independence), so rankings and counters do not change (tests).
-            groups = [Lockstep({}), Lockstep({})]
-            for i, q in enumerate(chains.live()):
-                groups[i % 2].absorb(chains, [q])
-            inflight = []                                            # [(group index, keys, launched)] oldest first
-
-            def submit(g) -> bool:
-                keys, windows = groups[g].pending()
-                launched = self._launch_windows(queries_of(keys), windows, slot=g)
-                if launched is None:                                 # does not fit one engine call: back to the blocking loop below
-                    return False
-                inflight.append((g, keys, launched))
-                return True
-
-            def collect() -> int:
-                g, keys, launched = inflight.pop(0)
-                groups[g].advance(counted(keys, *self._collect_windows(launched)))
-                return g
-
-            ok = True
-            try:
-                for g in (0, 1):
-                    if ok and groups[g]:
-                        ok = submit(g)
-                while ok and inflight:
-                    g = collect()
-                    if groups[g]:
-                        ok = submit(g)
-                while inflight:                                      # (only after a call that did not fit)
-                    collect()
-            finally:
-                # whatever raised above (a tokenizer error, a capacity error of the other group's launch): a call still queued on
-                # its slot is collected before the exception leaves - score_async's contract is that nothing else runs on the
-                # engine until then, and the caller's next rerank() would
-                for _, _, launched in inflight:
-                    try:
-                        self._collect_windows(launched)
-                    except Exception:
-                        pass
-            for group in groups:
-                chains.absorb(group)
+            # same labels as alone (batch independence), so rankings and counters do not change (tests).  A round that does
+            # not fit one engine call takes the blocking call, which cuts it; the next round is launched again.
+            alternate(chains, lambda keys, windows, slot: self._launch_windows(queries_of(keys), windows, slot=slot),
+                      lambda keys, launched: tally(counts, keys, *self._collect_windows(launched)), blocking)
         while chains:
-            keys, windows = chains.pending()
-            chains.advance(counted(keys, *self._compare_windows(queries_of(keys), windows)))
+            chains.advance(blocking(*chains.pending()))
         heap = self.method == "heapsort"
         results = [top_k_then_rest(list(reversed(ranking)) if heap else ranking, original, self.k)
                    for (_, ranking), original in zip(items, originals)]
-        counters = [tuple(c) for c in counts]
-        self.total_compare, self.total_prompt_tokens, self.total_completion_tokens = counters[-1]
-        return results, counters
+        return results, close_counters(self, counts)
 
     def truncate(self, text, length):
         return self.tokenizer.convert_tokens_to_string(self.tokenizer.tokenize(text)[:length])
@@ -650,9 +573,7 @@ class RankR1SetwiseLlmRanker(SetwiseLlmRanker):
         heap = self.method == "heapsort"
         results = [top_k_then_rest(list(reversed(ranking)) if heap else ranking, original, self.k)
                    for (_, ranking), original in zip(items, originals)]
-        counters = [tuple(c) for c in counts]
-        self.total_compare, self.total_prompt_tokens, self.total_completion_tokens = counters[-1]
-        return results, counters
+        return results, close_counters(self, counts)
 
     def _chat_ids(self, messages) -> List[int]:
         """what vLLM's LLM.chat feeds the model: the chat template with the generation prompt, tokenized"""

@@ -115,7 +115,7 @@ def test_pairwise_cases(stack):
 @pytest.mark.parametrize("batched", [True, False])
 def test_setwise_cases(cases, stack, monkeypatch, batched):
     """batched=True is what ships: the build phase of the heapsort submits the independent sift-downs of a tree level
-    in one engine call (SetwiseLlmRanker._heapsort_steps in level order / _compare_many, incl. the multi-row greedy EOS trimming).
+    in one engine call (_lockstep.heapsort_steps in level order / _compare_many, incl. the multi-row greedy EOS trimming).
     Compares are logged by wrapping the CLASS methods, so the ranker's own dispatch (_batched_ok) is untouched; the
     level-wise order differs from the reference's inside a level, so the compare log is checked as a multiset there
     and as an exact sequence with batching off."""
@@ -404,6 +404,61 @@ def test_rerank_many_equals_one_query_at_a_time_on_the_engine(cases, stack):
             assert [[r.docid for r in ranking] for ranking in rankings] == lists
         checked += 1
     assert checked >= 8 and any(k[2] == "bubblesort" for k in groups)
+
+
+def test_setwise_rerank_many_with_refused_rounds_equals_rerank_one_by_one(cases, ckpt_dirs):
+    """SetwiseLlmRanker.rerank_many (heapsort, likelihood scoring) on a runtime too small for the build rounds: five queries of
+    14, 5, 12, 7 and 10 candidates at num_child = 3 run as group 0 (14, 12, 10) and group 1 (5, 7).  Group 0's first two rounds
+    hold 1 + 3 + 2 = 6 and 3 + 1 + 1 = 5 windows (the sift-downs of a tree level of each heap) and do not fit a call of
+    max_seqs = 4 sequences: each is answered by the blocking call, and the rounds behind them - a window per heap, at most 3 -
+    are launched on the slots again.  Results, callers' lists and counters are those of rerank() one query at a time."""
+    from transformers import T5Tokenizer
+    from llmrankers._runtime import T5Runtime
+    from llmrankers.rankers import SearchResult
+    from llmrankers.setwise import SetwiseLlmRanker
+    base = next(c for c in cases if c["kind"] == "setwise" and c["method"] == "heapsort" and c["scoring"] == "likelihood"
+                and c["ckpt"] == "ckpt_gated_untied" and len(c["input"]) >= 14)
+    path = ckpt_dirs[base["ckpt"]]
+    tok = T5Tokenizer.from_pretrained(path)
+    sizes = (14, 5, 12, 7, 10)
+
+    def items():
+        return [(base["query"] + f" {q}", [SearchResult(docid=d, score=s, text=t) for d, s, t in base["input"][q:q + n]])
+                for q, n in enumerate(sizes)]
+
+    rt = T5Runtime(path, "cuda", max_tokens=8192, max_seqs=4, max_dec_len=40)
+    try:
+        rk = SetwiseLlmRanker.from_runtime(rt, tok, num_child=3, k=5, scoring="likelihood", method="heapsort")
+        assert rk._can_alternate() and rk._batched_ok()
+        want, lists = [], []
+        with contextlib.redirect_stdout(io.StringIO()):
+            for query, ranking in items():
+                res = rk.rerank(query, ranking)
+                want.append(([(r.docid, r.score) for r in res], (rk.total_compare, rk.total_prompt_tokens, rk.total_completion_tokens)))
+                lists.append([r.docid for r in ranking])
+        calls = {"async": 0, "refused": 0, "blocking": 0}
+        real_async, real_score = rt.score_async, rt.score
+
+        def counted_async(*a):
+            h = real_async(*a)
+            calls["async" if h is not None else "refused"] += 1
+            return h
+
+        def counted_score(*a):
+            calls["blocking"] += 1
+            return real_score(*a)
+
+        rt.score_async, rt.score = counted_async, counted_score
+        mine = items()
+        with contextlib.redirect_stdout(io.StringIO()):
+            results, cnts = rk.rerank_many(mine)
+        assert [([(r.docid, r.score) for r in res], c) for res, c in zip(results, cnts)] == want
+        assert [[r.docid for r in ranking] for _, ranking in mine] == lists
+        assert (rk.total_compare, rk.total_prompt_tokens, rk.total_completion_tokens) == cnts[-1]
+        print(f"setwise rerank_many (max_seqs 4): {calls}")
+        assert calls["refused"] == calls["blocking"] > 0 and calls["async"] > 0
+    finally:
+        rt.engine.close()
 
 
 def tokenize_ids(rk, query, window):

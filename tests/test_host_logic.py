@@ -545,7 +545,8 @@ def test_pointwise_rerank_many_streams_and_equals_one_query_at_a_time():
 def test_setwise_lockstep_alternates_two_groups_over_the_slots(method, sizes):
     """SetwiseLlmRanker.rerank_many, likelihood scoring on a runtime with batch slots: the chains run as two groups that
     alternate over slots 0 and 1 (a launch on one slot happens while the other is still uncollected), rankings and counters
-    are those of rerank() one query at a time; a call that does not fit the engine sends the rest down the blocking loop."""
+    are those of rerank() one query at a time; a round that does not fit one engine call takes the blocking call for that
+    round, and the rounds after it are launched on the slots again."""
     from transformers import T5Tokenizer
     from llmrankers._runtime import T5Runtime
     from llmrankers import _synth
@@ -562,6 +563,14 @@ def test_setwise_lockstep_alternates_two_groups_over_the_slots(method, sizes):
         events = []
         eng = _EventEngine(events, max_tokens=max_tokens, max_seqs=64, max_dec_len=4)
         rt = T5Runtime.from_engine(eng, _synth.TOY_GATED_UNTIED)
+        launch = rt.score_async
+
+        def noted(seqs, dec_prefix, out_ids, slot):            # a launch that does not fit is refused before anything is staged
+            handle = launch(seqs, dec_prefix, out_ids, slot)
+            if handle is None:
+                events.append(("refused", slot))
+            return handle
+        rt.score_async = noted
         rk = SetwiseLlmRanker.from_runtime(rt, tok, num_child=3, k=4, scoring="likelihood", method=method)
         rk.alternate_groups = alternate
         with contextlib.redirect_stdout(io.StringIO()):
@@ -588,5 +597,11 @@ def test_setwise_lockstep_alternates_two_groups_over_the_slots(method, sizes):
     assert overlapped
     ev_single, _ = run(100000, alternate=False)
     assert all(e[1] == 0 for e in ev_single if e[0] == "stage")
-    # an engine too small for a group's call: same results through the blocking loop (asserted inside run)
-    run(260)
+    assert not any(e[0] == "refused" for e in events + ev_single)
+    # an engine too small for some rounds: same results (asserted inside run); a refused round is answered by the blocking call
+    # (which stages nothing), and later rounds are staged on slot 1 again
+    ev_small, _ = run(260)
+    kinds = [e[:2] for e in ev_small]
+    assert ("refused", 0) in kinds or ("refused", 1) in kinds
+    first_refused = min(i for i, e in enumerate(kinds) if e[0] == "refused")
+    assert ("stage", 1) in kinds[first_refused:], "no launch on slot 1 after a refused one: alternation was given up"
