@@ -531,6 +531,20 @@ typedef struct rk_debug_graph_stats_t {
   int64_t eager, captures, replays, failed, evictions;
 } rk_debug_graph_stats_t;
 int rk_debug_graph_stats(rk_engine* e, rk_debug_graph_stats_t* out);
+/* debug: the engine's grown buffers - device memory that is freed and reallocated between calls when a call needs more of it
+ * (csrc/rk_engine.hip: Grown<T>::reserve) - and the move counters that stand in the graph keys.  Per buffer its device address
+ * (0: never allocated) and its capacity in elements, in the order of RK_DEBUG_BUFFER_NAMES; amax_gen counts the moves of amax_val
+ * and amax_idx (two per growth), kv_gen those of kv_cache, lkv_gen those of lkv, lpart and lints; logits and gen_buf have no
+ * counter (no graph holds logits; gen_buf is sized by the engine's capacities alone and is allocated once).  With it a test can
+ * say which buffer a call moved.  Host state only: nothing is launched or waited for. */
+#define RK_DEBUG_N_BUFFERS 8
+#define RK_DEBUG_BUFFER_NAMES "logits amax_val amax_idx kv_cache gen_buf lkv lpart lints"
+typedef struct rk_debug_buffers_t {
+  uint64_t addr[RK_DEBUG_N_BUFFERS];
+  uint64_t cap[RK_DEBUG_N_BUFFERS];
+  int amax_gen, kv_gen, lkv_gen;
+} rk_debug_buffers_t;
+int rk_debug_buffers(rk_engine* e, rk_debug_buffers_t* out);
 
 #ifdef __cplusplus
 }

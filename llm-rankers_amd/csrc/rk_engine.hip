@@ -1652,6 +1652,7 @@ int stage_slot(rk_engine* e, int slot, const int32_t* tokens, const int32_t* seq
 // captured from, so the key holds every value those depend on (shapes, the chunk count or the longest sequence, buffer
 // generations, the options epoch); everything else a chain reads (lengths, ids, positions) lives in device memory that is
 // per-slot and never moves (tests/test_gpu_graph_replay.py replays every kind on batches that share a key and differ in the rest).
+// The buffers that DO move (Grown) stand in the key with their move counters: tests/test_gpu_graph_moves.py moves each behind a capture.
 // Profiling runs and dec_graph = 0 stay eager (per-kernel events) and leave the table alone.
 // The table holds at most RK_GRAPH_CACHE_KEYS keys: the key that would pass the bound ERASES every other entry (evict_graphs) -
 // their graphs, their sightings, and the entries of epochs that no call can reach any more - and the keys still in use come back
@@ -4256,6 +4257,17 @@ int rk_debug_graph_stats(rk_engine* e, rk_debug_graph_stats_t* out) {
   const auto& n = e->graph_count;
   out->n_keys = (int)e->graphs.size(); out->n_ready = ready; out->max_keys = RK_GRAPH_CACHE_KEYS;
   out->eager = n.eager; out->captures = n.captures; out->replays = n.replays; out->failed = n.failed; out->evictions = n.evictions;
+  return RK_OK;
+}
+
+// debug: where the grown buffers are, how much they hold, and their move counters (host state only, like rk_debug_graph_stats)
+int rk_debug_buffers(rk_engine* e, rk_debug_buffers_t* out) {
+  if (!e || !out) return RK_ERR_INVALID;
+  int i = 0;
+  auto put = [&](const auto& b) { out->addr[i] = (uint64_t)(uintptr_t)b.p; out->cap[i] = (uint64_t)b.cap; ++i; };
+  put(e->logits); put(e->amax_val); put(e->amax_idx); put(e->kv_cache); put(e->gen_buf); put(e->lkv); put(e->lpart); put(e->lints);   // RK_DEBUG_BUFFER_NAMES
+  static_assert(RK_DEBUG_N_BUFFERS == 8, "one put per grown buffer");
+  out->amax_gen = e->amax_gen; out->kv_gen = e->kv_gen; out->lkv_gen = e->lkv_gen;
   return RK_OK;
 }
 

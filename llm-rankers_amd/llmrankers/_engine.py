@@ -97,6 +97,15 @@ class RkDebugGraphStats(C.Structure):
                [(n, C.c_int64) for n in ("eager", "captures", "replays", "failed", "evictions")]
 
 
+BUFFER_NAMES = ("logits", "amax_val", "amax_idx", "kv_cache", "gen_buf", "lkv", "lpart", "lints")     # RK_DEBUG_BUFFER_NAMES
+
+
+class RkDebugBuffers(C.Structure):
+    """rk_debug_buffers_t of include/rk_engine.h, field for field."""
+    _fields_ = [("addr", C.c_uint64 * len(BUFFER_NAMES)), ("cap", C.c_uint64 * len(BUFFER_NAMES))] + \
+               [(n, C.c_int) for n in ("amax_gen", "kv_gen", "lkv_gen")]
+
+
 DEBUG_SENTINEL = 0xCD                      # RK_DEBUG_SENTINEL: the byte the guard bands of rk_debug_gemm_ex are filled with
 DEBUG_BAND_ROWS = 256
 GEMM_OUT_DTYPE = {0: np.float16, 1: np.float32, 2: np.float16, 3: np.float16, 4: np.float32, 5: np.float16, 6: np.float32, 7: np.float32}
@@ -169,6 +178,7 @@ ABI = {
     "rk_debug_gemm_bench": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _f32p]),
     "rk_debug_read": (C.c_int64, [C.c_void_p, C.c_char_p, _f32p, C.c_int64]),
     "rk_debug_graph_stats": (C.c_int, [C.c_void_p, _P(RkDebugGraphStats)]),
+    "rk_debug_buffers": (C.c_int, [C.c_void_p, _P(RkDebugBuffers)]),
 }
 
 _lib = None
@@ -760,6 +770,15 @@ class RkEngine:
         st = RkDebugGraphStats()
         self._chk(self.lib.rk_debug_graph_stats(self.h, C.byref(st)))
         return {k: int(getattr(st, k)) for k, _ in RkDebugGraphStats._fields_}
+
+    def buffers(self) -> dict:
+        """The grown device buffers and their move counters (rk_debug_buffers): per name of BUFFER_NAMES {"addr", "cap"} (device
+        address, 0 before the first allocation; capacity in elements), and amax_gen, kv_gen, lkv_gen.  Host state only."""
+        b = RkDebugBuffers()
+        self._chk(self.lib.rk_debug_buffers(self.h, C.byref(b)))
+        out = {n: {"addr": int(b.addr[i]), "cap": int(b.cap[i])} for i, n in enumerate(BUFFER_NAMES)}
+        out.update((k, int(getattr(b, k))) for k in ("amax_gen", "kv_gen", "lkv_gen"))
+        return out
 
 
 class RkLlamaEngine(RkEngine):

@@ -6,6 +6,7 @@ bit what the same call gives as the first call of a fresh engine."""
 import numpy as np
 import pytest
 
+from _entry_util import _bytes, _each_after_each
 from conftest import load_state
 
 pytestmark = pytest.mark.gpu
@@ -16,27 +17,10 @@ def _engine(dims, state):
     return RkEngine(dims, device=0, max_tokens=4096, max_seqs=64, max_dec_len=40).load_state(state.items())
 
 
-def _each_after_each(n):
-    """n * n + 1 kinds out of 0 .. n-1 in which every kind directly follows every kind (itself included) exactly once: an
-    Euler circuit of the complete directed graph with loops (Hierholzer)."""
-    out = [list(range(n)) for _ in range(n)]
-    stack, circuit = [0], []
-    while stack:
-        if out[stack[-1]]:
-            stack.append(out[stack[-1]].pop())
-        else:
-            circuit.append(stack.pop())
-    return circuit[::-1]
-
-
 def _staged(eng, seqs, prefix, out_ids, slot):
     eng.stage(seqs, slot)
     eng.score_staged(prefix, out_ids, slot)
     return eng.read_scores(slot)
-
-
-def _bytes(res):
-    return tuple(np.ascontiguousarray(a).tobytes() for a in (res if isinstance(res, tuple) else (res,)))
 
 
 @pytest.mark.parametrize("ckpt", ["ckpt_gated_untied", "ckpt_relu_tied"])
