@@ -184,6 +184,14 @@ int rk_llama_set_rope_scaling(rk_engine* e, float factor, float low_freq_factor,
  * in fp32 to the projections' output before the rotation.  Call between rk_llama_create and the first rk_engine_load_tensor;
  * RK_ERR_STATE on a T5 engine or after finalize.  Never calling it (or on = 0): the bias names are ignored. */
 int rk_llama_set_qkv_bias(rk_engine* e, int on);
+/* Qwen3 family (hf: models/qwen3/modeling_qwen3.py: Qwen3Attention.q_norm / k_norm; Qwen3-0.6B to 8B, the Rank-R1 v0.2 bases): an
+ * RMSNorm over head_dim on every query and key head, behind the projection and in front of the rotation, with a weight [head_dim]
+ * per layer for q and for k; its eps is the desc's.  on != 0: rk_engine_finalize requires model.layers.N.self_attn.{q,k}_norm.weight
+ * (shape head_dim) and the engine applies them in fp32 in the prefill's rotary kernel and in the cached step's row load - one fp16
+ * rounding behind norm and rotation, the step's cached key bit for bit the prefill's.  Call between rk_llama_create and
+ * rk_engine_finalize; RK_ERR_STATE on a T5 engine or after finalize.  rk_engine_finalize then refuses (RK_ERR_STATE) head_dim 64, a
+ * sliding window and q / k / v biases next to it: no Qwen3 checkpoint has them.  Never calling it (or on = 0): the names are ignored. */
+int rk_llama_set_qk_norm(rk_engine* e, int on);
 /* Mistral family (hf: models/mistral/modeling_mistral.py, sliding_window_causal_mask; Zephyr / RankZephyr checkpoints): attention
  * with a sliding window of `window` positions.  In the prefill query position i of a sequence sees keys max(0, i - window + 1) .. i;
  * in the cached step (rk_llama_generate, rk_llama_session_*) the row at pos sees max(0, pos - window + 1) .. pos.  The K / V cache
@@ -364,6 +372,8 @@ int rk_debug_gemm_ex(rk_engine* e, rk_debug_gemm_call* call);
  *   5 Llama cached step  plan_llama_dec_attn: q = the step's rows [n_seq, ldq], NOT rotated; cache = K [n_seq][n_kv][P][128] then V, pos[n_seq]
  *                        (< P, < max_pos), cos_t / sin_t [max_pos][64] ([max_pos][32] at hd = 64), qkv_bias [(H + 2 n_kv) 128] fp32 or null; out = ctx [n_seq, H 128]
  *                        (ldctx = H 128); cache_all = the cache afterwards (the row's rotated key and its value appended at pos).  Option llama_dec_r.
+ *                        qk_norm (the LAST fields of the call; null = off): Qwen3's q | k head-norm weights [2 x 128] fp32 with qk_eps > 0 - the
+ *                        step's entry with the norm (out_kind 2; hd = 128, no window, no qkv_bias: RK_ERR_STATE otherwise).
  *                        On an engine with a sliding window W every call runs the windowed entries (out_kind 1, else 0): row b reads keys
  *                        max(0, pos[b] - W + 1) .. pos[b] and the cache below them is neither read into the result nor written.
  *   6 T5 cached step     the self-attention of rk_t5_generate's step, through the launcher run_decoder's cached branch calls: q = the step's
@@ -401,6 +411,7 @@ typedef struct rk_debug_attn_call {
   int plan_only;
   int out_kind, out_tparam, out_grid[3], out_grid2[3], out_lds, out_staged, out_mfma, out_part, out_R, out_nch, out_skip_long,
       out_heads_per_wg, out_n_cu;
+  const float* qk_norm; float qk_eps;
 } rk_debug_attn_call;
 int rk_debug_attn(rk_engine* e, rk_debug_attn_call* call);
 /* debug: the WHOLE query-side cross-attention chain of one T5 decoder layer on host data (csrc/rk_engine.hip: struct XAttnChain ->
@@ -479,6 +490,8 @@ int rk_debug_xattn_chain(rk_engine* e, rk_debug_xattn_chain_call* call);
  *                    seq_off[rows], the longest sequence >= 1), in2 slots i32[rows] (any value: the kernel skips what is outside [0, n_slots))
  *                    or null (then the cache has `rows` rows).  out0 cache fp16: K [cache rows][n_kv][P][hd], then V.  out_tparam = hd,
  *                    out_variant = 1 with a slot map.
+ *  11 rope_qkn       op 8 with Qwen3's q / k head norm (rope128_qkn_kernel): hd = 128, eps > 0, in3 norm weights f32 [2 x 128] (q | k,
+ *                    required); the value heads stay as they are.  out_tparam = 128, out_variant = 2.
  *  10 advance        kind 0 greedy_advance_kernel, 1 llama_advance_kernel, 2 llama_session_advance_kernel; rows (= n_seq / n_slots),
  *                    n_steps >= 1 launches, one per scripted arg-max row: in0 argmax i32 [n_steps][R], R = rows (kind 2: max(rows, max_admit)).
  *                    The interiors are the initial state; all[s] is the complete state after launch s.

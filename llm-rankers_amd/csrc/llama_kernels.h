@@ -333,6 +333,8 @@ struct LlamaDecAttnArgs {
   float scale_log2e;     // head_dim**-0.5 * log2(e)
   const float* bias;     // Qwen2: this layer's q | k | v projection bias [(n_heads + 2 n_kv) * D] fp32, else null
   int window;            // the windowed kernels (Mistral's sliding window): W > 0, the row at pos sees keys max(0, pos - W + 1) .. pos
+  const float* qkn = nullptr;   // Qwen3 (attn_dec_cached_qkn_kernel, llama_kernels_qknorm.h): this layer's q | k head-norm weights [2 * 128] fp32, else null
+  float qkn_eps = 0.f;          // ... and the norm's eps
 };
 #define LDC_CHUNK 128    // keys per workgroup: FIXED, so the chunk boundaries of a sequence follow from its own position alone
 constexpr int ldc_pstr(int D) { return D + 4; }   // floats per partial: D accumulators, maximum, sum, 2 unused (16-byte rows)
@@ -347,6 +349,9 @@ __device__ __forceinline__ float row8_sum_f(float v) {   // sum over an aligned 
 template <bool BIAS>   // llama_kernels_hd64.h
 __device__ __forceinline__ void rope64_pairs(const half_t* __restrict__ head, const float* __restrict__ bias_head, int i0,
                                              const float (&co)[8], const float (&si)[8], half8& oa, half8& ob);
+
+__device__ __forceinline__ half8 qkn_lane8(const half_t* row, const float* w, float eps, int n_heads, int hd, int i0, bool hi,
+                                           const float (&co)[8], const float (&si)[8]);   // llama_kernels_qknorm.h
 
 // The step's rotation of the new row, the one thing the two widths do differently: this lane's 8 dims (elements i0 .. i0 + 7 of
 // the first half of the head, or with `hi` their partners in the second) of rotated head hd (of q | k) of `row`, rounded as the
@@ -415,7 +420,9 @@ __device__ __forceinline__ half8 rope_lane8(const half_t* row, const float* bias
 // keys below lo inside a visible wave get the -1e30 of the keys beyond pos; the merge walks chunks lo / LDC_CHUNK .. pos / LDC_CHUNK
 // only.  The cache keeps every position and the chunk that owns pos (always visible) still writes the new key and value.  With
 // pos < W nothing is skipped or masked: the plain kernel's bits.  WIN = false is the kernel as it was.
-template <int D, int R, bool BIAS, bool WIN>
+// QKN (Qwen3's q / k head norm; the entry attn_dec_cached_qkn_kernel in llama_kernels_qknorm.h): the row transform is qkn_lane8 - norm,
+// rotation, one rounding, the arithmetic of the prefill's rope128_qkn_kernel - instead of rope_lane8; nothing else differs.
+template <int D, int R, bool BIAS, bool WIN, bool QKN = false>
 __device__ __forceinline__ void attn_dec_cached_body(const LlamaDecAttnArgs& p) {
   static_assert(D == 128 || D == 64, "lanes per key 16 or 8");
   constexpr int LK = D / 8, KL = 512 / D, NL = D / 16;   // lanes per key, keys per wave load, loads per wave
@@ -436,7 +443,10 @@ __device__ __forceinline__ void attn_dec_cached_body(const LlamaDecAttnArgs& p) 
   float co[8], si[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) { co[j] = p.cos_t[(size_t)pos * (D / 2) + i0 + j]; si[j] = p.sin_t[(size_t)pos * (D / 2) + i0 + j]; }
-  auto rotated = [&](int hd) { return rope_lane8<D, BIAS>(row, p.bias, hd, i0, hi, co, si); };
+  auto rotated = [&](int hd) {
+    if constexpr (QKN) return qkn_lane8(row, p.qkn, p.qkn_eps, p.n_heads, hd, i0, hi, co, si);
+    else return rope_lane8<D, BIAS>(row, p.bias, hd, i0, hi, co, si);
+  };
   const half8 knew = rotated(p.n_heads + kvh);
   const size_t voff = (size_t)(p.n_heads + p.n_kv + kvh) * D + c * 8;
   half8 vnew = *(const half8*)(row + voff);

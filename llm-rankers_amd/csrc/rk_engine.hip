@@ -29,6 +29,7 @@
 #include "gemv_rows.h"
 #include "llama_kernels.h"
 #include "llama_kernels_hd64.h"
+#include "llama_kernels_qknorm.h"
 #include "misc_kernels.h"
 
 namespace {
@@ -62,7 +63,7 @@ struct DecLayerW {
 };
 
 // Llama-family decoder layer (hf: modeling_llama.py:291-330): fused q|k|v and interleaved gate|up carry the RMSNorm weights
-struct LlamaLayerW { half_t *qkv_f = nullptr, *o = nullptr, *gu_f = nullptr, *down = nullptr; float* qkv_bias = nullptr; };   // qkv_bias: Qwen2 only (rk_llama_set_qkv_bias), fp32 [Q + 2 KV], NOT scaled by the norm weight
+struct LlamaLayerW { half_t *qkv_f = nullptr, *o = nullptr, *gu_f = nullptr, *down = nullptr; float* qkv_bias = nullptr; float* qk_norm = nullptr; };   // qkv_bias: Qwen2 only (rk_llama_set_qkv_bias), fp32 [Q + 2 KV], NOT scaled by the norm weight; qk_norm: Qwen3 only (rk_llama_set_qk_norm), fp32 q | k head-norm weights [2 * 128]
 
 struct ProfRec { hipEvent_t a, b; int cls; };
 
@@ -229,6 +230,7 @@ struct rk_engine {
   int family = 0; rk_llama_desc ld{};
   float rope_factor = 0.f, rope_low = 1.f, rope_high = 4.f; int rope_orig = 0;   // rope type llama3 when rope_factor > 0
   bool qkv_bias = false;                                                          // Qwen2 family: q / k / v projections carry a bias
+  bool qk_norm = false;                                                           // Qwen3 family: RMSNorm over head_dim on every q and k head (rk_llama_set_qk_norm)
   int window = 0;                                                                 // Mistral family: sliding window W (rk_llama_set_sliding_window), 0 = none
   std::vector<LlamaLayerW> ll; float *l_final_ln = nullptr, *rope_cos = nullptr, *rope_sin = nullptr; int* d_pos = nullptr;
   // rk_llama_generate: K / V cache [n_layers][2][n_seq][n_kv][P][head_dim], the attention partials and the call's int block (grown
@@ -749,10 +751,12 @@ void launch_qlm_lse(hipStream_t st, const float2* stats, int nblk, const float* 
   hipLaunchKernelGGL(qlm_lse_kernel, dim3(n_seq), dim3(256), 0, st, stats, nblk, xlab, n_pos, row_off, out_idx, out);
 }
 // the prefill's rotation, in place on T rows of the fused QKV buffer: head width 64 or 128, with the Qwen2 bias (then the n_v
-// value heads get theirs) or without (value heads untouched)
+// value heads get theirs) or without (value heads untouched); qkn (Qwen3: the layer's q | k head-norm weights; width 128 and no
+// bias, rk_engine_finalize sees to it): the entry with the norm, n_v = the kv head count there too
 void launch_rope(hipStream_t st, int hd, half_t* qkv, const int* pos, const float* cos_t, const float* sin_t, int ld, int n_rot,
-                 const float* bias, int n_v, int T) {
-  if (hd == 64 && bias) hipLaunchKernelGGL(rope64_kernel<true>, dim3(T), dim3(256), 0, st, qkv, pos, cos_t, sin_t, ld, n_rot, bias, n_v);
+                 const float* bias, int n_v, int T, const float* qkn = nullptr, float qkn_eps = 0.f) {
+  if (qkn) hipLaunchKernelGGL(rope128_qkn_kernel, dim3(T), dim3(256), 0, st, qkv, pos, cos_t, sin_t, ld, n_rot - n_v, n_v, qkn, qkn_eps);
+  else if (hd == 64 && bias) hipLaunchKernelGGL(rope64_kernel<true>, dim3(T), dim3(256), 0, st, qkv, pos, cos_t, sin_t, ld, n_rot, bias, n_v);
   else if (hd == 64) hipLaunchKernelGGL(rope64_kernel<false>, dim3(T), dim3(256), 0, st, qkv, pos, cos_t, sin_t, ld, n_rot, (const float*)nullptr, 0);
   else if (bias) hipLaunchKernelGGL(rope128_kernel<true>, dim3(T), dim3(256), 0, st, qkv, pos, cos_t, sin_t, ld, n_rot, bias, n_v);
   else hipLaunchKernelGGL(rope128_kernel<false>, dim3(T), dim3(256), 0, st, qkv, pos, cos_t, sin_t, ld, n_rot, (const float*)nullptr, 0);
@@ -1289,6 +1293,10 @@ void launch_llama_dec_attn(rk_engine* e, hipStream_t st, const LlamaDecAttnPlan&
     auto go = [&](auto rc) {                                 // the bias-free instantiation is the Llama kernel as it was
       constexpr int R = decltype(rc)::value;
       if constexpr (R == 7 && D != 128) abort();             // no such kernel: plan_llama_dec_attn gives R = 7 at 128 alone
+      else if (a.qkn) {                                      // Qwen3's head norm: 128 wide, no bias, no window (rk_engine_finalize)
+        if constexpr (D == 128) hipLaunchKernelGGL((attn_dec_cached_qkn_kernel<D, R>), p.grid, dim3(256), 0, st, a);
+        else abort();
+      }
       else if (p.window > 0) {
         if (a.bias) hipLaunchKernelGGL((attn_dec_cached_win_kernel<D, R, true>), p.grid, dim3(256), 0, st, a);
         else hipLaunchKernelGGL((attn_dec_cached_win_kernel<D, R, false>), p.grid, dim3(256), 0, st, a);
@@ -2664,6 +2672,10 @@ int rk_llama_create(const rk_llama_desc* desc, int device_ordinal, rk_engine** o
 static int llama_finalize(rk_engine* e) {
   const rk_llama_desc& l = e->ld;
   const int hd = l.head_dim, dm = l.hidden, Q = l.n_heads * hd, KV = l.n_kv_heads * hd, F = l.intermediate, V = l.vocab;
+  // Qwen3's q / k head norm has kernels at width 128 without a bias and without a window: what every Qwen3 checkpoint is
+  if (e->qk_norm && (hd != 128 || e->window > 0 || e->qkv_bias))
+    return fail(e, RK_ERR_STATE, "the q / k head norm (rk_llama_set_qk_norm) is built for head_dim 128 without a sliding window and without q / k / v biases (got head_dim %d, window %d, biases %d): no Qwen3 checkpoint has another shape", hd, e->window, (int)e->qkv_bias);
+  if (e->qk_norm && !(l.eps > 0.f)) return fail(e, RK_ERR_INVALID, "the q / k head norm needs rms_norm_eps > 0 (got %g)", (double)l.eps);
   std::string missing;
   auto N2 = [&](const std::string& n, int64_t r, int64_t c) { return need(e, n, r, c, &missing); };
   auto N1 = [&](const std::string& n, int64_t r) { return need(e, n, r, -1, &missing); };
@@ -2677,6 +2689,7 @@ static int llama_finalize(rk_engine* e) {
     N2(p + ".mlp.gate_proj.weight", F, dm); N2(p + ".mlp.up_proj.weight", F, dm); N2(p + ".mlp.down_proj.weight", dm, F);
     N1(p + ".input_layernorm.weight", dm); N1(p + ".post_attention_layernorm.weight", dm);
     if (e->qkv_bias) { N1(p + ".self_attn.q_proj.bias", Q); N1(p + ".self_attn.k_proj.bias", KV); N1(p + ".self_attn.v_proj.bias", KV); }
+    if (e->qk_norm) { N1(p + ".self_attn.q_norm.weight", hd); N1(p + ".self_attn.k_norm.weight", hd); }
   }
   if (!missing.empty()) return fail(e, RK_ERR_MISSING, "missing or mis-shaped tensors: %s", missing.c_str());
   auto H = [&](const std::string& n) -> const std::vector<half_t>& { return e->host[n].h; };
@@ -2710,6 +2723,12 @@ static int llama_finalize(rk_engine* e) {
         bias.insert(bias.end(), src.begin(), src.end());
       }
       RC(upload(e, &w.qkv_bias, bias.data(), bias.size()));
+    }
+    if (e->qk_norm) {    // q | k head-norm weights, fp32 as they are (the kernels multiply in fp32, one fp16 rounding behind the rotation)
+      std::vector<float> nw(Fv(p + ".self_attn.q_norm.weight"));
+      const auto& kn = Fv(p + ".self_attn.k_norm.weight");
+      nw.insert(nw.end(), kn.begin(), kn.end());
+      RC(upload(e, &w.qk_norm, nw.data(), nw.size()));
     }
     RC(upload(e, &w.o, H(p + ".self_attn.o_proj.weight").data(), (size_t)dm * Q));
     {   // gate | up interleaved in groups of 32 rows (the SwiGLU epilogue pairs them in one lane), post-attention norm folded
@@ -2795,7 +2814,7 @@ static int llama_prefill(rk_engine* e, const int32_t* tokens, const int32_t* off
     RC(gemm(e, st, ns.consumer(e, st, nullptr, Gemm(PC_ENC_GEMM_QKV, EPI_STORE_F16, ns.x(), dm, w.qkv_f, dm, sl.qkv, ldq, T, ldq, dm), false)));
     {
       Bracket br(e, st, PC_OTHER, 0, (double)T * (Q + KV) * 4.0);
-      launch_rope(st, hd, sl.qkv, e->d_pos, e->rope_cos, e->rope_sin, ldq, l.n_heads + l.n_kv_heads, w.qkv_bias, l.n_kv_heads, T);
+      launch_rope(st, hd, sl.qkv, e->d_pos, e->rope_cos, e->rope_sin, ldq, l.n_heads + l.n_kv_heads, w.qkv_bias, l.n_kv_heads, T, w.qk_norm, l.eps);
     }
     if (keep) {
       const size_t half_layer = (size_t)(keep->slots ? keep->rows : n_seq) * KV * keep->P;
@@ -2855,6 +2874,14 @@ int rk_llama_set_qkv_bias(rk_engine* e, int on) {
   return RK_OK;
 }
 
+int rk_llama_set_qk_norm(rk_engine* e, int on) {
+  if (!e) return RK_ERR_INVALID;
+  if (e->family != 1) return fail(e, RK_ERR_STATE, "the q / k head norm applies to Llama-family engines (rk_llama_create)");
+  if (e->finalized) return fail(e, RK_ERR_STATE, "rk_llama_set_qk_norm must precede rk_engine_finalize (the norm weights are uploaded there)");
+  e->qk_norm = on != 0;
+  return RK_OK;
+}
+
 int rk_llama_greedy1(rk_engine* e, const int32_t* tokens, const int32_t* seq_offsets, int n_seq, int32_t* out_tokens) {
   if (!e || !out_tokens) return RK_ERR_INVALID;
   if (e->ls.open) return fail(e, RK_ERR_STATE, "rk_llama_greedy1 while a decoding session is open (it shares the prefill's buffers): rk_llama_session_close first");
@@ -2909,7 +2936,7 @@ static int llama_step_rows(rk_engine* e, hipStream_t st, int rows, int P, const 
     RC(gemm(e, st, normed(Gemm(PC_DEC_GEMM, EPI_STORE_F16, ns.x(), dm, w.qkv_f, dm, lg.qkv, ldq, rows, ldq, dm))));
     half_t* kc = e->lkv.p + (size_t)i * 2 * half_layer;
     launch_llama_dec_attn(e, st, ap, LlamaDecAttnArgs{lg.qkv, kc, kc + half_layer, d_pos, e->rope_cos, e->rope_sin, e->lpart.p, lg.ctx,
-                                                          ldq, l.n_heads, l.n_kv_heads, P, ap.nch, scale_log2e, w.qkv_bias, 0}, rows);
+                                                          ldq, l.n_heads, l.n_kv_heads, P, ap.nch, scale_log2e, w.qkv_bias, 0, w.qk_norm, l.eps}, rows);
     RC(ns.producer(e, st, Gemm(PC_DEC_GEMM, EPI_RESID_F32, lg.ctx, Q, w.o, Q, ns.hidden, dm, rows, dm, Q).on(GEMM_STREAM)));
     RC(gemm(e, st, normed(Gemm(PC_DEC_GEMM, EPI_SWIGLU_F16, ns.x(), dm, w.gu_f, dm, lg.ffh, F, rows, 2 * F, dm))));
     RC(ns.producer(e, st, Gemm(PC_DEC_GEMM, EPI_RESID_F32, lg.ffh, F, w.down, F, ns.hidden, dm, rows, dm, F).on(GEMM_STREAM), i + 1 < l.n_layers));
@@ -3681,8 +3708,10 @@ int rk_debug_attn(rk_engine* e, rk_debug_attn_call* q) {
       for (int b = 0; b < B; ++b)
         if (q->pos[b] < 0 || q->pos[b] >= P || q->pos[b] >= q->max_pos) return fail(e, RK_ERR_INVALID, "debug attn: pos[%d] = %d outside the cache of %d / the tables of %d", b, q->pos[b], P, q->max_pos);
     }
+    if (q->qk_norm && (hd != 128 || e->window > 0 || q->qkv_bias || !(q->qk_eps > 0.f)))
+      return fail(e, RK_ERR_STATE, "debug attn: the step with the q / k head norm takes head_dim 128, no window, no qkv_bias and qk_eps > 0");
     lp = plan_llama_dec_attn(e, B, P, H, n_kv);
-    plan_out(lp.window > 0 ? 1 : 0, lp.R, lp.grid, lp.cgrid, 0);
+    plan_out(lp.window > 0 ? 1 : (q->qk_norm ? 2 : 0), lp.R, lp.grid, lp.cgrid, 0);
     q->out_R = lp.R; q->out_nch = lp.nch;
     if (H % lp.R) return fail(e, RK_ERR_STATE, "debug attn: R = %d does not divide %d heads", lp.R, H);
   }
@@ -3773,13 +3802,14 @@ int rk_debug_attn(rk_engine* e, rk_debug_attn_call* q) {
     float* dCos = (float*)up(q->cos_t, (size_t)q->max_pos * (hd / 2) * 4);
     float* dSin = (float*)up(q->sin_t, (size_t)q->max_pos * (hd / 2) * 4);
     float* dBias = q->qkv_bias ? (float*)up(q->qkv_bias, (size_t)(H + 2 * q->n_kv) * hd * 4) : nullptr;
+    float* dQkn = q->qk_norm ? (float*)up(q->qk_norm, (size_t)2 * hd * 4) : nullptr;
     float* dPart = (float*)alloc((size_t)B * H * lp.nch * ldc_pstr(hd) * 4, RK_DEBUG_SENTINEL);
-    if (!dC || !dPos || !dCos || !dSin || (q->qkv_bias && !dBias) || !dPart) return done(fail(e, RK_ERR_HIP, "debug attn: device allocation or upload failed"));
+    if (!dC || !dPos || !dCos || !dSin || (q->qkv_bias && !dBias) || (q->qk_norm && !dQkn) || !dPart) return done(fail(e, RK_ERR_HIP, "debug attn: device allocation or upload failed"));
     DBG_HIP(hipMemcpy(dC + c_band, q->cache, 2 * half_layer * 2, hipMemcpyHostToDevice));
     DBG_HIP(hipDeviceSynchronize());
     const float scale_log2e = (1.0f / std::sqrt((float)hd)) * 1.4426950408889634f;
     half_t* kc = dC + c_band;
-    launch_llama_dec_attn(e, st, lp, LlamaDecAttnArgs{qi, kc, kc + half_layer, dPos, dCos, dSin, dPart, oi, q->ldq, H, q->n_kv, q->P, lp.nch, scale_log2e, dBias, 0}, B);
+    launch_llama_dec_attn(e, st, lp, LlamaDecAttnArgs{qi, kc, kc + half_layer, dPos, dCos, dSin, dPart, oi, q->ldq, H, q->n_kv, q->P, lp.nch, scale_log2e, dBias, 0, dQkn, q->qk_eps}, B);
   }
   DBG_HIP(hipStreamSynchronize(st));
   DBG_HIP(hipGetLastError());
@@ -3947,7 +3977,7 @@ int rk_debug_rows(rk_engine* e, rk_debug_rows_call* q) {
   if (rc) return rc;
   const int op = q->op, rows = q->rows, d = q->d;
   const long R = rows;
-  if (op < 1 || op > 10) return fail(e, RK_ERR_INVALID, "debug rows: op 1..10");
+  if (op < 1 || op > 11) return fail(e, RK_ERR_INVALID, "debug rows: op 1..11");
   if (rows <= 0 || rows > (1 << 20)) return fail(e, RK_ERR_INVALID, "debug rows: rows = %d", rows);
   const int n_steps = op == 10 ? q->n_steps : 1;
   if (n_steps < 1 || n_steps > 4096) return fail(e, RK_ERR_INVALID, "debug rows: n_steps = %d", n_steps);
@@ -4036,6 +4066,19 @@ int rk_debug_rows(rk_engine* e, rk_debug_rows_call* q) {
         for (long t = 0; t < R; ++t) if (pos[t] < 0 || pos[t] >= q->max_pos) return bad("pos entry outside the tables");
       }
       grid = dim3(rows); tparam = hd; variant = q->in[3].data != nullptr;
+    } break;
+    case 11: {   // op 8 with Qwen3's q / k head norm: 128 wide, in3 = the norm weights q | k (required), eps
+      const int hd = q->hd, H = q->H, n_kv = q->n_kv;
+      if (hd != 128 || H <= 0 || n_kv <= 0 || H > 1024 || n_kv > 1024 || q->max_pos <= 0 || !(q->eps > 0.f)) return bad("hd 128, H, n_kv, max_pos, eps > 0");
+      if (q->ld % 8 || q->ld < (H + 2 * n_kv) * hd) return bad("ld: a multiple of 8, at least (H + 2 n_kv) hd");
+      in_need[0] = R * 4; in_need[1] = in_need[2] = (long)q->max_pos * (hd / 2) * 4; in_need[3] = 2L * hd * 4;
+      out_need[0] = R * q->ld * 2;
+      if (!planning) {
+        const int* pos = ints(0, R);
+        if (!pos) return bad("pos of rows ints");
+        for (long t = 0; t < R; ++t) if (pos[t] < 0 || pos[t] >= q->max_pos) return bad("pos entry outside the tables");
+      }
+      grid = dim3(rows); tparam = hd; variant = 2;
     } break;
     case 9: {
       const int hd = q->hd, H = q->H, n_kv = q->n_kv;
@@ -4150,6 +4193,8 @@ int rk_debug_rows(rk_engine* e, rk_debug_rows_call* q) {
       case 7: launch_qlm_lse(st, (const float2*)din[0], q->nb, (const float*)din[1], q->n_pos, (const int*)din[2], (const int*)din[3], (float*)dout[0], rows); break;
       case 8: launch_rope(st, q->hd, (half_t*)dout[0], (const int*)din[0], (const float*)din[1], (const float*)din[2], q->ld, q->H + q->n_kv,
                           (const float*)din[3], q->n_kv, rows); break;
+      case 11: launch_rope(st, q->hd, (half_t*)dout[0], (const int*)din[0], (const float*)din[1], (const float*)din[2], q->ld, q->H + q->n_kv,
+                           nullptr, q->n_kv, rows, (const float*)din[3], q->eps); break;
       case 9: {
         half_t* kc = (half_t*)dout[0];
         launch_kv_fill(st, q->hd, (const half_t*)din[0], (const int*)din[1], (const int*)din[2], q->n_slots, kc,

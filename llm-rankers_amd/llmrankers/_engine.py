@@ -60,7 +60,8 @@ class RkDebugAttnCall(C.Structure):
                 ("out", C.c_void_p), ("out_rows", C.c_int64), ("out_all", C.c_void_p), ("cache", C.c_void_p), ("cache_all", C.c_void_p),
                 ("plan_only", C.c_int), ("out_kind", C.c_int), ("out_tparam", C.c_int), ("out_grid", C.c_int * 3), ("out_grid2", C.c_int * 3)] + \
                [(n, C.c_int) for n in ("out_lds", "out_staged", "out_mfma", "out_part", "out_R", "out_nch", "out_skip_long",
-                                       "out_heads_per_wg", "out_n_cu")]
+                                       "out_heads_per_wg", "out_n_cu")] + \
+               [("qk_norm", C.c_void_p), ("qk_eps", C.c_float)]
 
 
 class RkDebugXattnChainCall(C.Structure):
@@ -139,6 +140,7 @@ ABI = {
     "rk_llama_create": (C.c_int, [_P(RkLlamaDesc), C.c_int, _P(C.c_void_p)]),
     "rk_llama_set_rope_scaling": (C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_int]),
     "rk_llama_set_qkv_bias": (C.c_int, [C.c_void_p, C.c_int]),
+    "rk_llama_set_qk_norm": (C.c_int, [C.c_void_p, C.c_int]),
     "rk_llama_set_sliding_window": (C.c_int, [C.c_void_p, C.c_int]),
     "rk_llama_greedy1": (C.c_int, [C.c_void_p, _i32p, _i32p, C.c_int, _i32p]),
     "rk_llama_last_logits": (C.c_int, [C.c_void_p, _i32p, _i32p, C.c_int, _i32p, C.c_int, _f32p]),
@@ -569,7 +571,8 @@ class RkEngine:
 
     def debug_attn(self, kind: int, *, n_seq: int, H: int, q=None, out=None, kv=None, band_rows=8, n_kv=0, Ld=0, cross=False, M=0, row0=0,
                    d=0, P=0, ldq=0, ldkv=0, ldctx=0, k_col=0, v_col=0, seq_off=None, row_off=None, tree_keys=None, tree_pos=None,
-                   row_seq=None, pos=None, bias_lut=None, cos=None, sin=None, qkv_bias=None, cache=None, plan_only=False) -> dict:
+                   row_seq=None, pos=None, bias_lut=None, cos=None, sin=None, qkv_bias=None, cache=None, plan_only=False,
+                   qk_norm=None, qk_eps=0.0) -> dict:
         """One attention call through rk_debug_attn (include/rk_engine.h).  q / kv: 2-D fp16 [band_rows + rows + band_rows, ld], the
         WHOLE allocation with the caller's bands; out: 2-D fp16 [rows, ldctx], the pre-filled interior; cache (kind 5): flat fp16, K then
         V (kind 6, the T5 cached step: [n_seq][P][k | v] of 64 H each, bands of band_rows * 64 elements, pos one value).  Returns the plan fields and, unless plan_only, "out" [band_rows + rows + band_rows, ldctx] and "cache" (flat, with bands
@@ -613,6 +616,9 @@ class RkEngine:
             c.max_pos = cos.shape[0]
         if qkv_bias is not None:
             assert put("qkv_bias", qkv_bias, np.float32).size == (H + 2 * n_kv) * hd
+        if qk_norm is not None:                              # kind 5: Qwen3's q | k head-norm weights, the step's entry with the norm
+            assert put("qk_norm", qk_norm, np.float32).size == 2 * hd
+            c.qk_eps = float(qk_eps)
         out_all = cache_all = None
         if out is not None:
             out = put("out", out, np.float16)
@@ -804,6 +810,8 @@ class RkLlamaEngine(RkEngine):
             self._chk(self.lib.rk_llama_set_rope_scaling(self.h, float(f), float(lo), float(hi), int(orig)))
         if getattr(dims, "qkv_bias", False):                          # Qwen2 family: before the first tensor is loaded
             self._chk(self.lib.rk_llama_set_qkv_bias(self.h, 1))
+        if getattr(dims, "qk_norm", False):                           # Qwen3 family: the q / k head norm, before finalize
+            self._chk(self.lib.rk_llama_set_qk_norm(self.h, 1))
         if getattr(dims, "sliding_window", 0) > 0:                    # Mistral family: the attention's window, before finalize
             self._chk(self.lib.rk_llama_set_sliding_window(self.h, int(dims.sliding_window)))
 

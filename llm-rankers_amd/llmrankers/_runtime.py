@@ -559,6 +559,8 @@ class LlamaRuntime:
         if self.dims.head_dim not in (64, 128) or self.dims.hidden > 4096:
             raise NotImplementedError(f"head_dim {self.dims.head_dim} / hidden {self.dims.hidden}: the MI355X engine serves head_dim 64 or 128 and "
                                       "hidden <= 4096 (Llama-2/3 up to 8B, Llama-3.2-1B, TinyLlama, SmolLM2, Qwen2.5-0.5B to 7B)")
+        if self.dims.qk_norm and self.dims.head_dim != 128:            # (rk_engine_finalize refuses it too; no Qwen3 checkpoint has it)
+            raise NotImplementedError(f"Qwen3 with head_dim {self.dims.head_dim}: the MI355X engine's q / k head norm is built for head_dim 128")
         self.engine = RkLlamaEngine(self.dims, parse_device(device), max_tokens, max_seqs)
         tensors = iter_checkpoint_tensors(model_name_or_path)
         self.engine.load_state(merge_lora(tensors, adapter_dir) if adapter_dir else tensors)

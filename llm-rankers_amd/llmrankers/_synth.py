@@ -128,8 +128,24 @@ class LlamaDims:
     # position i sees keys max(0, i - sliding_window + 1) .. i; 0 = none (the config's null).  `mistral` marks the config as Mistral's.
     sliding_window: int = 0
     mistral: bool = False
+    # Qwen3 family (hf: models/qwen3/modeling_qwen3.py): no projection biases, an RMSNorm over head_dim on every query and key head
+    # (q_norm / k_norm, a weight [head_dim] per layer each) between the projection and the rotation
+    qk_norm: bool = False
 
     def to_hf_config(self) -> dict:
+        if self.qk_norm:
+            if self.rope_scaling is not None or self.qkv_bias or self.sliding_window or self.mistral:
+                raise NotImplementedError("a Qwen3 configuration has the default rope type, no q / k / v biases and no sliding window on the MI355X engine")
+            return {
+                "architectures": ["Qwen3ForCausalLM"], "model_type": "qwen3", "vocab_size": self.vocab,
+                "hidden_size": self.hidden, "intermediate_size": self.intermediate, "num_hidden_layers": self.n_layers,
+                "num_attention_heads": self.n_heads, "num_key_value_heads": self.n_kv_heads, "head_dim": self.head_dim,
+                "hidden_act": "silu", "rms_norm_eps": self.eps, "rope_theta": self.rope_theta, "rope_scaling": None,
+                "max_position_embeddings": 40960, "attention_bias": False, "use_sliding_window": False, "sliding_window": None,
+                "max_window_layers": self.n_layers, "layer_types": ["full_attention"] * self.n_layers, "attention_dropout": 0.0,
+                "tie_word_embeddings": bool(self.tied_head), "bos_token_id": self.bos_token_id, "eos_token_id": self.eos_token_id,
+                "use_cache": True,
+            }
         if self.qkv_bias:
             if self.rope_scaling is not None:
                 raise NotImplementedError("rope scaling on a Qwen2 configuration is not supported by the MI355X engine")
@@ -177,8 +193,13 @@ class LlamaDims:
             raise NotImplementedError("only bias-free SwiGLU Llama configurations are supported by the MI355X engine")
         qwen2 = cfg.get("model_type") == "qwen2"
         mistral = cfg.get("model_type") == "mistral"   # no biases; head_dim and sliding_window may be absent or null
+        qwen3 = cfg.get("model_type") == "qwen3"       # (attention_bias: true is refused above; qwen3_moe is another model_type)
         if qwen2 and cfg.get("use_sliding_window"):
             raise NotImplementedError("Qwen2 configurations with use_sliding_window are not supported by the MI355X engine")
+        if qwen3:
+            if cfg.get("use_sliding_window") or any(t != "full_attention" for t in cfg.get("layer_types") or ()):
+                raise NotImplementedError("Qwen3 configurations with use_sliding_window, or a layer_types entry other than full_attention, "
+                                          "are not supported by the MI355X engine")
         rope = cfg.get("rope_parameters") or {}
         scaling = cfg.get("rope_scaling") or ({k: v for k, v in rope.items() if k != "rope_theta"} if rope.get("rope_type", "default") != "default" else None)
         rs = None
@@ -197,7 +218,7 @@ class LlamaDims:
                          eps=cfg.get("rms_norm_eps", 1e-6), tied_head=bool(cfg.get("tie_word_embeddings", False)),
                          bos_token_id=cfg.get("bos_token_id", 1) or 1, eos_token_id=eos[0] if isinstance(eos, list) else eos,
                          rope_scaling=rs, qkv_bias=qwen2, sliding_window=int(cfg.get("sliding_window") or 0) if mistral else 0,
-                         mistral=mistral)
+                         mistral=mistral, qk_norm=qwen3)
 
 
 LLAMA_3_8B = LlamaDims(vocab=128256, hidden=4096, n_heads=32, n_kv_heads=8, head_dim=128, intermediate=14336, n_layers=32,
@@ -220,6 +241,16 @@ TOY_LLAMA3ROPE = LlamaDims(vocab=256, hidden=256, n_heads=4, n_kv_heads=2, head_
 # tied head, q / k / v biases; ids 1 / 2 are tests/golden/tok_qwen's <|im_start|> / <|im_end|>
 TOY_QWEN2 = LlamaDims(vocab=512, hidden=256, n_heads=7, n_kv_heads=1, head_dim=128, intermediate=512, n_layers=2,
                       rope_theta=1000000.0, eps=1e-6, tied_head=True, qkv_bias=True)
+
+# ---- Qwen3 (q / k head norm, llama_kernels_qknorm.h) ----
+# Qwen3-4B: the q width 32 x 128 = 4096 differs from hidden 2560, tied head; Qwen3-8B: untied.  Timing tools and the real-width test only.
+QWEN3_4B = LlamaDims(vocab=151936, hidden=2560, n_heads=32, n_kv_heads=8, head_dim=128, intermediate=9728, n_layers=36,
+                     rope_theta=1000000.0, eps=1e-6, tied_head=True, bos_token_id=151643, eos_token_id=151645, qk_norm=True)
+QWEN3_8B = LlamaDims(vocab=151936, hidden=4096, n_heads=32, n_kv_heads=8, head_dim=128, intermediate=12288, n_layers=36,
+                     rope_theta=1000000.0, eps=1e-6, bos_token_id=151643, eos_token_id=151645, qk_norm=True)
+# toy Qwen3: 4 query heads on 2 kv heads of 128 (q width 512 against hidden 256), tied head; ids 1 / 2 as for TOY_QWEN2
+TOY_QWEN3 = LlamaDims(vocab=512, hidden=256, n_heads=4, n_kv_heads=2, head_dim=128, intermediate=512, n_layers=2,
+                      rope_theta=1000000.0, eps=1e-6, tied_head=True, qk_norm=True)
 
 
 # ---- 64-wide heads (llama_kernels_hd64.h): the small decoder-only chat models ----
@@ -258,6 +289,9 @@ def llama_tensor_specs(d: "LlamaDims") -> Iterator[Tuple[str, Tuple[int, ...], f
             yield f"{p}.self_attn.q_proj.bias", (d.n_heads * d.head_dim,), 0.5, False
             yield f"{p}.self_attn.k_proj.bias", (d.n_kv_heads * d.head_dim,), 0.5, False
             yield f"{p}.self_attn.v_proj.bias", (d.n_kv_heads * d.head_dim,), 0.5, False
+        if d.qk_norm:                                 # (only with the switch on: no stream of another recipe moves)
+            yield f"{p}.self_attn.q_norm.weight", (d.head_dim,), 0.1, True
+            yield f"{p}.self_attn.k_norm.weight", (d.head_dim,), 0.1, True
         yield f"{p}.input_layernorm.weight", (d.hidden,), 0.1, True
         yield f"{p}.mlp.gate_proj.weight", (d.intermediate, d.hidden), d.hidden ** -0.5, False
         yield f"{p}.mlp.up_proj.weight", (d.intermediate, d.hidden), d.hidden ** -0.5, False
@@ -277,6 +311,7 @@ NAMED_DIMS = {
     "llama-3.2-1b": LLAMA_32_1B, "tinyllama-1.1b": TINYLLAMA_1B, "qwen2.5-0.5b": QWEN25_05B,
     "toy-llama-hd64": TOY_LLAMA_HD64, "toy-qwen2-hd64": TOY_QWEN2_HD64, "toy-llama-mha-hd64": TOY_LLAMA_MHA_HD64,
     "mistral-7b": MISTRAL_7B, "toy-mistral": TOY_MISTRAL, "toy-mistral-hd64": TOY_MISTRAL_HD64,
+    "qwen3-4b": QWEN3_4B, "qwen3-8b": QWEN3_8B, "toy-qwen3": TOY_QWEN3,
 }
 
 _M64 = np.uint64(0xFFFFFFFFFFFFFFFF)

@@ -297,7 +297,7 @@ class R1ListwiseLlmRanker(ListwiseLlmRanker):
     call is this class's own: compare, rerank, rerank_many (the pending windows of all live queries in ONE generate call per step)
     and truncate are ListwiseLlmRanker's."""
     CHARACTERS = [f'[{i + 1}]' for i in range(20)]
-    ACCEPT_MODEL_TYPES = ("qwen2", "llama", "mistral")      # vLLM takes any chat model; these are the families the engine serves
+    ACCEPT_MODEL_TYPES = ("qwen2", "llama", "mistral", "qwen3")      # vLLM takes any chat model; these are the families the engine serves
 
     def __init__(self, model_name_or_path, tokenizer_name_or_path, prompt, window_size, step_size, lora_path=None,
                  scoring='generation', num_repeat=1, cache_dir=None, device="cuda", max_new_tokens=2048):

@@ -430,7 +430,7 @@ class RankR1SetwiseLlmRanker(SetwiseLlmRanker):
         lora_path = resolve_checkpoint(lora_name_or_path, cache_dir) if lora_name_or_path is not None else None
         tokenizer = AutoTokenizer.from_pretrained(tokenizer_name_or_path if tokenizer_name_or_path is not None else model_name_or_path,
                                                   cache_dir=cache_dir)
-        runtime = LlamaRuntime(model_name_or_path, device, cache_dir=cache_dir, accept_model_types=("qwen2", "llama", "mistral"),
+        runtime = LlamaRuntime(model_name_or_path, device, cache_dir=cache_dir, accept_model_types=("qwen2", "llama", "mistral", "qwen3"),
                                adapter_dir=lora_path)
         self._setup_r1(runtime, tokenizer, prompt, lora_path, device, num_child, k, method, num_permutation, verbose, max_new_tokens)
 
