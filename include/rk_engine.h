@@ -347,6 +347,44 @@ typedef struct rk_debug_gemm_call {
   float out_eps, out_xs;
 } rk_debug_gemm_call;
 int rk_debug_gemm_ex(rk_engine* e, rk_debug_gemm_call* call);
+/* debug: n_launch (1 .. 64) launches of ONE described call of the engine's GEMM, back to back on slot 0's encoder stream, with NEW
+ * data per launch and optionally beside a background load - what rk_debug_gemm_ex (one launch between host copies on an idle
+ * chip) cannot show of the ping-pong kernel's timing-dependent parts: the K-split hand-off (every split launch uses the
+ * stream's one workspace: slab and ticket addresses repeat while the data changes) and the row-factor wait.  Same contract as
+ * rk_debug_gemm_ex: struct Gemm -> plan_gemm -> the launchers, no kernel and no dispatch of its own; every extent is checked
+ * before anything is launched; plan_only != 0 fills the out_* fields only.  No host work, copy or synchronisation between the
+ * launches: every operand is uploaded before the first, every output read back after the last.
+ *   epi, family, M, N, K, lda, ldw, ldc   the call, as in rk_debug_gemm_call (one batch, no n_split, no producer, epi 0 .. 5)
+ *   W        shared, w_elems elements.  A: n_launch x a_elems elements, launch i reads A + i * a_elems.  rowscale (optional):
+ *            n_launch x M row factors, launch i reads its own M
+ *   C        n_launch interiors of c_elems elements of the output type, copied to the device as they are; C_out: n_launch whole
+ *            allocations [band | interior | band] (band_rows >= 256 rows of ldc elements each, RK_DEBUG_SENTINEL-filled before the
+ *            first launch): launch i writes its own allocation
+ *   accumulate != 0 (epi 1 only, else RK_ERR_INVALID): ONE interior and ONE allocation; every launch adds into it, as successive
+ *            layers add into the residual stream
+ *   background (bg_per_fg > 0): a second described call (bg_epi 0 / 1 / 3 / 4, bg_family, bg_M, bg_N, bg_K; tight leading
+ *            dimensions, operands made up on the host, outputs discarded) whose plan must NOT put rows on the ping-pong kernel
+ *            (RK_ERR_INVALID otherwise: the weight-streaming family or another tile variant - the engine's gemm_variant option is
+ *            bg_variant for the background's plan and launches); bg_per_fg launches of it go on slot 0's decoder stream per
+ *            foreground launch, enqueued in front of it (bg_first != 0) or behind it.  The ping-pong kernel owns whole CUs: a
+ *            background grid covering part of the chip delays some of its workgroups.
+ * out_*: the foreground's plan, bg_out_*: the background's. */
+typedef struct rk_debug_gemm_chain_call {
+  int epi, family;
+  int M, N, K, lda, ldw, ldc;
+  int n_launch, accumulate;
+  const uint16_t* A; int64_t a_elems;
+  const uint16_t* W; int64_t w_elems;
+  const void* C; int64_t c_elems;
+  void* C_out;
+  int band_rows;
+  const float* rowscale;
+  int bg_epi, bg_family, bg_M, bg_N, bg_K, bg_variant, bg_per_fg, bg_first;
+  int plan_only;
+  int out_family, out_variant, out_m_pp2, out_ksplit, out_n_cu;
+  int bg_out_family, bg_out_variant, bg_out_m_pp2, bg_out_ksplit;
+} rk_debug_gemm_chain_call;
+int rk_debug_gemm_chain(rk_engine* e, rk_debug_gemm_chain_call* call);
 /* debug: run ANY attention call of the engine (csrc/rk_engine.hip: plan_*attn -> the plan's launcher, no kernel and no dispatch of
  * its own) on host data, every output inside guard bands.  kind selects the plan; heads have the kernels' own width (64 for the T5
  * kinds - 128 on a T5 engine created with d_kv = 128, where kind 1 runs the 128-wide plan (out_kind 3) whatever attn_short / attn_long

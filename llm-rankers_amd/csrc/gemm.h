@@ -1285,6 +1285,9 @@ __global__ __launch_bounds__(512, 2) void gemm_pp2_kernel(GemmArgs p) {
         if (last) {
           __hip_atomic_store(p.ks_cnt + t_out, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // nobody touches this ticket again
           __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+          // the fence's cache invalidate completes asynchronously: it is waited for HERE, before the barrier below releases the
+          // other seven waves to their plain loads of the partner's slab (tests/test_isa_guards.py holds the order)
+          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
         *flag = last;
       }

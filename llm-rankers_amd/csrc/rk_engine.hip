@@ -3582,6 +3582,123 @@ int rk_debug_gemm_ex(rk_engine* e, rk_debug_gemm_call* q) {
   return done(RK_OK);
 }
 
+// debug: n_launch back-to-back launches of one Gemm call with new data per launch, optionally beside a background call on the
+// slot's decoder stream (include/rk_engine.h).  No launch code of its own: it builds the Gemms and calls gemm().
+int rk_debug_gemm_chain(rk_engine* e, rk_debug_gemm_chain_call* q) {
+  if (!e || !q) return RK_ERR_INVALID;
+  int rc = set_device(e);
+  if (rc) return rc;
+  const int epi = q->epi, M = q->M, N = q->N, K = q->K, nl = q->n_launch;
+  if (epi < 0 || epi > EPI_SWIGLU_F16 || q->family < 0 || q->family > 2 || M <= 0 || N <= 0 || K <= 0 || q->lda <= 0 || q->ldw <= 0 || q->ldc <= 0 ||
+      M > (1 << 22))
+    return fail(e, RK_ERR_INVALID, "debug gemm chain: bad shape");
+  if (nl < 1 || nl > 64) return fail(e, RK_ERR_INVALID, "debug gemm chain: n_launch 1..64");
+  if (q->accumulate && epi != EPI_RESID_F32) return fail(e, RK_ERR_INVALID, "debug gemm chain: accumulate is the fp32 residual epilogue's");
+  const bool bg = q->bg_per_fg > 0;
+  if (q->bg_per_fg < 0 || q->bg_per_fg > 16) return fail(e, RK_ERR_INVALID, "debug gemm chain: bg_per_fg 0..16");
+  if (bg && (q->bg_M <= 0 || q->bg_N <= 0 || q->bg_K <= 0 || q->bg_M > (1 << 16) || q->bg_N > (1 << 16) || q->bg_K > (1 << 16) || q->bg_family < 0 ||
+             q->bg_family > 2 || q->bg_variant < 0 || q->bg_variant > 6 ||
+             !(q->bg_epi == EPI_STORE_F16 || q->bg_epi == EPI_RESID_F32 || q->bg_epi == EPI_RELU_F16 || q->bg_epi == EPI_STORE_F32)))
+    return fail(e, RK_ERR_INVALID, "debug gemm chain: bad background call");
+  const bool gated = EPI_IS_GATED(epi), f16 = epi == EPI_STORE_F16 || epi == EPI_RELU_F16 || gated;
+  const size_t celt = f16 ? 2 : 4;
+  auto family_of = [](int f) { return f == 2 ? GEMM_GEMV : (f == 1 ? GEMM_STREAM : GEMM_TILED); };
+  // the plans first (pointers only count as aligned / present): a call outside the contract stops here, before any allocation
+  half_t* const dummy = (half_t*)(uintptr_t)256;
+  hipStream_t st = e->slots[0].se, sb = e->slots[0].sd;
+  Gemm c(PC_OTHER, epi, dummy, q->lda, dummy, q->ldw, dummy, q->ldc, M, N, K);
+  c.on(family_of(q->family));
+  if (q->rowscale) c.fold.rowscale = (const float*)dummy;
+  const GemmPlan p = plan_gemm(e, c, st);
+  q->out_family = (int)p.family; q->out_variant = p.variant; q->out_m_pp2 = p.m_pp2; q->out_ksplit = p.m_pp2 > 0 ? p.ks_pp2 : p.ksplit;
+  q->out_n_cu = e->n_cu;
+  q->bg_out_family = GEMM_NONE; q->bg_out_variant = q->bg_out_m_pp2 = 0; q->bg_out_ksplit = 1;
+  if (p.family == GEMM_NONE)
+    return fail(e, RK_ERR_STATE, "no kernel of family %d takes the GEMM M=%d N=%d K=%d (epilogue %d, batch 1): %s", q->family, M, N, K, epi, p.why ? p.why : "");
+  // the background's plan and launches see bg_variant as the engine's gemm_variant option (the foreground keeps the engine's own)
+  const int fg_variant = e->opt.gemm_variant;
+  Gemm b(PC_OTHER, bg ? q->bg_epi : EPI_STORE_F16, dummy, q->bg_K, dummy, q->bg_K, dummy, q->bg_N, q->bg_M, q->bg_N, q->bg_K);
+  if (bg) {
+    b.on(family_of(q->bg_family));
+    e->opt.gemm_variant = q->bg_variant;
+    const GemmPlan pb = plan_gemm(e, b, sb);
+    e->opt.gemm_variant = fg_variant;
+    q->bg_out_family = (int)pb.family; q->bg_out_variant = pb.variant; q->bg_out_m_pp2 = pb.m_pp2; q->bg_out_ksplit = pb.m_pp2 > 0 ? pb.ks_pp2 : pb.ksplit;
+    if (pb.family == GEMM_NONE)
+      return fail(e, RK_ERR_STATE, "no kernel of family %d takes the background GEMM M=%d N=%d K=%d (epilogue %d): %s", q->bg_family, q->bg_M, q->bg_N, q->bg_K, q->bg_epi, pb.why ? pb.why : "");
+    if (pb.pp2()) return fail(e, RK_ERR_INVALID, "debug gemm chain: the background's plan puts rows on the ping-pong kernel");
+  }
+  if (q->plan_only) return RK_OK;
+  // extents, from the addressing of the call, against what the caller gave
+  if (!q->A || !q->W || !q->C || !q->C_out || q->band_rows < 256) return fail(e, RK_ERR_INVALID, "debug gemm chain: A, W, C, C_out and band_rows >= 256");
+  const long width = gated ? N / 2 : N;
+  const long a_need = (long)(M - 1) * q->lda + K, w_need = (long)(N - 1) * q->ldw + K, c_need = (long)(M - 1) * q->ldc + width;
+  if (a_need > q->a_elems || w_need > q->w_elems || c_need > q->c_elems)
+    return fail(e, RK_ERR_INVALID, "debug gemm chain: the call reaches beyond A (%ld of %ld), W (%ld of %ld) or C (%ld of %ld)", a_need, (long)q->a_elems, w_need, (long)q->w_elems, c_need, (long)q->c_elems);
+  const int n_out = q->accumulate ? 1 : nl;
+  const size_t band = (size_t)q->band_rows * q->ldc, c_all = 2 * band + (size_t)q->c_elems;
+  const size_t m_pad = ((size_t)M + 255) / 256 * 256 + 256;     // the ping-pong kernel reads the row factors of whole 256-row panels
+  std::vector<void*> dev;
+  auto alloc = [&](size_t bytes, int fill) -> void* {
+    void* ptr = nullptr;
+    if (hipMalloc(&ptr, bytes ? bytes : 16) != hipSuccess) return nullptr;
+    dev.push_back(ptr);
+    if (fill >= 0 && hipMemset(ptr, fill, bytes) != hipSuccess) return nullptr;
+    return ptr;
+  };
+  auto done = [&](int r) { for (void* ptr : dev) hipFree(ptr); return r; };
+#define DBG_HIP(x) do { if ((x) != hipSuccess) return done(fail(e, RK_ERR_HIP, "debug gemm chain: %s", #x)); } while (0)
+  half_t* dA = (half_t*)alloc((size_t)nl * q->a_elems * 2, -1);
+  half_t* dW = (half_t*)alloc((size_t)q->w_elems * 2, -1);
+  char* dC = (char*)alloc((size_t)n_out * c_all * celt, RK_DEBUG_SENTINEL);
+  float* dR = q->rowscale ? (float*)alloc((size_t)nl * m_pad * 4, 0) : nullptr;
+  const size_t bga = (size_t)q->bg_M * q->bg_K, bgw = (size_t)q->bg_N * q->bg_K, bgc = (size_t)q->bg_M * q->bg_N;
+  half_t* dBA = bg ? (half_t*)alloc(bga * 2, -1) : nullptr;
+  half_t* dBW = bg ? (half_t*)alloc(bgw * 2, -1) : nullptr;
+  float* dBC = bg ? (float*)alloc(bgc * 4, 0) : nullptr;
+  if (!dA || !dW || !dC || (q->rowscale && !dR) || (bg && (!dBA || !dBW || !dBC)))
+    return done(fail(e, RK_ERR_HIP, "debug gemm chain: device allocation failed"));
+  DBG_HIP(hipMemcpy(dA, q->A, (size_t)nl * q->a_elems * 2, hipMemcpyHostToDevice));
+  DBG_HIP(hipMemcpy(dW, q->W, (size_t)q->w_elems * 2, hipMemcpyHostToDevice));
+  for (int i = 0; i < n_out; ++i)
+    DBG_HIP(hipMemcpy(dC + ((size_t)i * c_all + band) * celt, (const char*)q->C + (size_t)i * q->c_elems * celt, (size_t)q->c_elems * celt, hipMemcpyHostToDevice));
+  for (int i = 0; q->rowscale && i < nl; ++i)
+    DBG_HIP(hipMemcpy(dR + (size_t)i * m_pad, q->rowscale + (size_t)i * M, (size_t)M * 4, hipMemcpyHostToDevice));
+  if (bg) {
+    std::vector<half_t> h(std::max(bga, bgw));
+    uint32_t x = 2463534242u;
+    for (size_t i = 0; i < h.size(); ++i) { x = x * 1664525u + 1013904223u; h[i] = (half_t)(((int)(x >> 16) % 2001 - 1000) * 1e-3f); }
+    DBG_HIP(hipMemcpy(dBA, h.data(), bga * 2, hipMemcpyHostToDevice));
+    DBG_HIP(hipMemcpy(dBW, h.data(), bgw * 2, hipMemcpyHostToDevice));
+    b.A = dBA; b.W = dBW; b.C = dBC;
+  }
+  DBG_HIP(hipDeviceSynchronize());
+  c.W = dW;
+  auto background = [&]() {
+    e->opt.gemm_variant = q->bg_variant;
+    int r = RK_OK;
+    for (int j = 0; r == RK_OK && j < q->bg_per_fg; ++j) r = gemm(e, sb, b);
+    e->opt.gemm_variant = fg_variant;
+    return r;
+  };
+  for (int i = 0; rc == RK_OK && i < nl; ++i) {
+    c.A = dA + (size_t)i * q->a_elems;
+    c.C = dC + ((size_t)(q->accumulate ? 0 : i) * c_all + band) * celt;
+    c.fold = GemmFold();
+    if (q->rowscale) c.fold.rowscale = dR + (size_t)i * m_pad;
+    if (bg && q->bg_first) rc = background();
+    if (rc == RK_OK) rc = gemm(e, st, c);
+    if (rc == RK_OK && bg && !q->bg_first) rc = background();
+  }
+  const hipError_t s1 = hipStreamSynchronize(st), s2 = hipStreamSynchronize(sb);   // whatever was enqueued is waited for
+  if (rc) return done(rc);
+  DBG_HIP(s1); DBG_HIP(s2);
+  DBG_HIP(hipGetLastError());
+  DBG_HIP(hipMemcpy(q->C_out, dC, (size_t)n_out * c_all * celt, hipMemcpyDeviceToHost));
+#undef DBG_HIP
+  return done(RK_OK);
+}
+
 // debug: one attention call on host data, every output between sentinel bands (include/rk_engine.h).  No kernel and no dispatch of
 // its own: it uploads the operands, asks the plan_*attn function of the kind and hands the plan to that plan's launcher.
 int rk_debug_attn(rk_engine* e, rk_debug_attn_call* q) {

@@ -49,6 +49,16 @@ class RkDebugGemmCall(C.Structure):
                [("out_eps", C.c_float), ("out_xs", C.c_float)]
 
 
+class RkDebugGemmChainCall(C.Structure):
+    """rk_debug_gemm_chain_call of include/rk_engine.h, field for field."""
+    _fields_ = [(n, C.c_int) for n in ("epi", "family", "M", "N", "K", "lda", "ldw", "ldc", "n_launch", "accumulate")] + \
+               [("A", C.c_void_p), ("a_elems", C.c_int64), ("W", C.c_void_p), ("w_elems", C.c_int64),
+                ("C", C.c_void_p), ("c_elems", C.c_int64), ("C_out", C.c_void_p), ("band_rows", C.c_int), ("rowscale", C.c_void_p)] + \
+               [(n, C.c_int) for n in ("bg_epi", "bg_family", "bg_M", "bg_N", "bg_K", "bg_variant", "bg_per_fg", "bg_first", "plan_only",
+                                       "out_family", "out_variant", "out_m_pp2", "out_ksplit", "out_n_cu",
+                                       "bg_out_family", "bg_out_variant", "bg_out_m_pp2", "bg_out_ksplit")]
+
+
 class RkDebugAttnCall(C.Structure):
     """rk_debug_attn_call of include/rk_engine.h, field for field."""
     _fields_ = [(n, C.c_int) for n in ("kind", "n_seq", "H", "n_kv", "Ld", "cross", "M", "row0", "d", "P",
@@ -174,6 +184,7 @@ ABI = {
     "rk_rel_bucket": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "rk_debug_gemm": (C.c_int, [C.c_void_p, _P(C.c_uint16), _P(C.c_uint16), _f32p, C.c_int, C.c_int, C.c_int, C.c_int]),
     "rk_debug_gemm_ex": (C.c_int, [C.c_void_p, _P(RkDebugGemmCall)]),
+    "rk_debug_gemm_chain": (C.c_int, [C.c_void_p, _P(RkDebugGemmChainCall)]),
     "rk_debug_attn": (C.c_int, [C.c_void_p, _P(RkDebugAttnCall)]),
     "rk_debug_xattn_chain": (C.c_int, [C.c_void_p, _P(RkDebugXattnChainCall)]),
     "rk_debug_rows": (C.c_int, [C.c_void_p, _P(RkDebugRowsCall)]),
@@ -567,6 +578,52 @@ class RkEngine:
         out.update(C=c_out, band=band, idx=idx, xlab=xlab, ldc=ldc, c_elems=c_elems)
         if producer:
             out.update(xraw=xraw, ssq=ssq[:rows_all * q.out_nb].reshape(rows_all, q.out_nb))
+        return out
+
+    def debug_gemm_chain(self, epi: int, a16: np.ndarray, w16: np.ndarray, M: int, N: int, K: int, *, family=0, ldc=None,
+                         c_in: Optional[np.ndarray] = None, accumulate=False, rowscale=None, bg: Optional[dict] = None, bg_per_fg=0,
+                         bg_first=True, n_launch=None, plan_only=False, c_out: Optional[np.ndarray] = None) -> dict:
+        """n_launch back-to-back launches of one GEMM call with new data per launch through rk_debug_gemm_chain (include/rk_engine.h).
+        a16: fp16 [n_launch, M, K] (launch i's A); w16: fp16 [N, K], shared; rowscale: [n_launch, M] or None; c_in: [n_out, M * ldc]
+        interiors in the output type, n_out = 1 with accumulate (epi 1) else n_launch, default all sentinel bytes; bg: dict(epi, family,
+        M, N, K, variant) of the background call, bg_per_fg launches of it per foreground launch on the decoder stream.  c_out: the host
+        array the allocations are read back into (default: a new one, sentinel-filled).  Returns the plan fields ("bg_family", ... for
+        the background's) and "C" [n_out, band + M * ldc + band]: the whole device allocations after the last launch."""
+        a16 = np.ascontiguousarray(a16, dtype=np.float16)
+        w16 = np.ascontiguousarray(w16, dtype=np.float16).reshape(-1)
+        nl = a16.shape[0] if n_launch is None else int(n_launch)
+        a_elems = a16.size // max(1, a16.shape[0])
+        width = N // 2 if epi in (2, 5) else N
+        ldc = ldc or width
+        dt = GEMM_OUT_DTYPE[epi]
+        n_out = 1 if accumulate else max(1, a16.shape[0])
+        c_elems, band = M * ldc, DEBUG_BAND_ROWS * ldc
+        q = RkDebugGemmChainCall()
+        if not plan_only:
+            if c_in is None:
+                c_in = np.frombuffer(bytes([DEBUG_SENTINEL]) * (n_out * c_elems * np.dtype(dt).itemsize), dtype=dt).copy()
+            c_in = np.ascontiguousarray(c_in, dtype=dt).reshape(-1)
+            assert c_in.size == n_out * c_elems
+            if c_out is None:
+                c_out = np.frombuffer(bytes([DEBUG_SENTINEL]) * (n_out * (2 * band + c_elems) * np.dtype(dt).itemsize), dtype=dt).copy()
+            assert c_out.dtype == dt and c_out.size == n_out * (2 * band + c_elems) and c_out.flags["C_CONTIGUOUS"]
+            q.C, q.C_out = c_in.ctypes.data, c_out.ctypes.data
+        q.epi, q.family, q.M, q.N, q.K, q.lda, q.ldw, q.ldc, q.n_launch, q.accumulate = epi, family, M, N, K, K, K, ldc, nl, int(accumulate)
+        q.A, q.a_elems, q.W, q.w_elems = a16.ctypes.data, a_elems, w16.ctypes.data, w16.size
+        q.c_elems, q.band_rows = c_elems, DEBUG_BAND_ROWS
+        if rowscale is not None:
+            rowscale = np.ascontiguousarray(rowscale, dtype=np.float32)
+            assert rowscale.shape == (a16.shape[0], M)
+            q.rowscale = rowscale.ctypes.data
+        if bg is not None:
+            q.bg_epi, q.bg_family, q.bg_M, q.bg_N, q.bg_K, q.bg_variant = bg["epi"], bg["family"], bg["M"], bg["N"], bg["K"], bg.get("variant", 0)
+            q.bg_per_fg, q.bg_first = int(bg_per_fg), int(bg_first)
+        q.plan_only = int(plan_only)
+        self._chk(self.lib.rk_debug_gemm_chain(self.h, C.byref(q)))
+        out = {k[4:]: getattr(q, k) for k, _ in RkDebugGemmChainCall._fields_ if k.startswith("out_")}
+        out.update({"bg_" + k[7:]: getattr(q, k) for k, _ in RkDebugGemmChainCall._fields_ if k.startswith("bg_out_")})
+        if not plan_only:
+            out.update(C=c_out.reshape(n_out, 2 * band + c_elems), band=band, ldc=ldc)
         return out
 
     def debug_attn(self, kind: int, *, n_seq: int, H: int, q=None, out=None, kv=None, band_rows=8, n_kv=0, Ld=0, cross=False, M=0, row0=0,

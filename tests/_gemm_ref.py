@@ -96,11 +96,12 @@ def consumer_factor(K, eps, rowscale=None, ssq_in=None):
     return None
 
 
-def expected(epi, a16, w16, *, c_in=None, factor=None, labels=None):
+def expected(epi, a16, w16, *, c_in=None, factor=None, labels=None, acc=None):
     """fp64 expected output of one epilogue on the logical [M, N] problem (addressing is the caller's business).
+    acc: acc64(a16, w16) where the caller already holds it (one fp64 product shared by several tests).
     Returns a dict: "out" (fp64, before any rounding to the output type), and for the block epilogues "max", "idx" / "sumexp",
     "xlab"; for the gated ones also "lip" (the Lipschitz factor of the output in the accumulators)."""
-    acc = acc64(a16, w16)
+    acc = acc64(a16, w16) if acc is None else np.asarray(acc, dtype=np.float64)
     if factor is not None:
         acc = acc * np.asarray(factor, dtype=np.float64)[:, None]
     if epi == EPI_STORE_F16 or epi == EPI_STORE_F32:

@@ -41,7 +41,7 @@ def eng(ckpt_dirs):
 
 class Options:
     """Engine options for the length of a block, restored to the defaults after it."""
-    DEFAULTS = {"gemm_variant": 0, "gemm_glds": 1, "gemm_sk": 1, "gemm_s64_stages": 0, "gemm_split": 1}
+    DEFAULTS = {"gemm_variant": 0, "gemm_glds": 1, "gemm_sk": 1, "gemm_s64_stages": 0, "gemm_split": 1, "gemm_persistent": 1}
 
     def __init__(self, eng, **kw):
         self.eng, self.kw = eng, kw
@@ -304,6 +304,44 @@ def test_k_split_pingpong(eng, epi, tier):
         for i, (m, n, k) in enumerate([(300, 260, 1024), (777, 516, 2816 if tier == "B" else 512), (257, 256, 256), (64, 64, 384)]):
             r = run_case(eng, R.TILED, epi, m, n, k, tier, 7000 + i, layout=i % 3, producer=epi == R.EPI_RESID_F32 and i % 2 == 0)
             assert r["ksplit"] == 2, (m, n, k, r["ksplit"])
+
+
+@pytest.mark.parametrize("case", [(R.EPI_STORE_F16, 300, 520, 192, "rowscale", False), (R.EPI_RESID_F32, 777, 516, 1024, None, True),
+                                  (R.EPI_GEGLU_F16, 2100, 2048, 128, "rowscale", False)],       # 9 x 8 = 72 tiles: more than 64 workgroups
+                         ids=lambda c: R.EPI_NAMES[c[0]])
+def test_pingpong_grid_option_gives_the_same_bytes(eng, case):
+    """Option gemm_persistent on the ping-pong variant: one workgroup per tile (0), 8 or 64 workgroups walking the tiles - the same
+    bytes as the default (1: one workgroup per CU), which is held to the fp64 reference here; a value other than 1 plans no K split."""
+    epi, m, n, k, consumer, outliers = case
+    rs = np.random.RandomState(9300 + epi)
+    a, w = R.normal_operands(rs, m, n, k, outliers)
+    c_old = rs.standard_normal((m, n)).astype(np.float32) if epi == R.EPI_RESID_F32 else None
+    rsc = rs.uniform(0.5, 2.0, size=m).astype(np.float32) if consumer else None
+    width = n // 2 if epi in R.GATED else n
+
+    def run():
+        r = eng.debug_gemm_ex(epi, R.TILED, a, w, m, n, k, c_in=c_old, rowscale=rsc)
+        assert r["variant"] == 5 and r["m_pp2"] == 0 and r["ksplit"] == 1, r
+        assert (r["C"][:r["band"]].view(np.uint8) == R.SENTINEL).all() and (r["C"][r["band"] + m * width:].view(np.uint8) == R.SENTINEL).all()
+        return r["C"]
+
+    with Options(eng, gemm_variant=5):
+        base = run()
+        got = base[BAND_ROWS * width:BAND_ROWS * width + m * width].reshape(m, width)
+        e = R.expected(epi, a, w, c_in=c_old, factor=None if rsc is None else rsc.astype(np.float64))
+        if epi == R.EPI_RESID_F32:
+            R.check_f32(got, e["out"], R.tau(a, w), R.EPI_NAMES[epi])
+        else:
+            R.check_f16(got, e["out"], R.tau(a, w), R.EPI_NAMES[epi], lip=e["lip"], factor=rsc)
+        for value in (0, 8, 64):
+            with Options(eng, gemm_persistent=value):
+                assert run().tobytes() == base.tobytes(), f"{R.EPI_NAMES[epi]} {(m, n, k)}: gemm_persistent = {value} differs from 1"
+    z = np.zeros(8, np.float16)
+    with Options(eng, gemm_variant=5, gemm_sk=2):
+        assert eng.debug_gemm_ex(R.EPI_STORE_F32, R.TILED, z, z, 300, 260, 1024, plan_only=True)["ksplit"] == 2
+        for value in (0, 8, 64):
+            with Options(eng, gemm_persistent=value):
+                assert eng.debug_gemm_ex(R.EPI_STORE_F32, R.TILED, z, z, 300, 260, 1024, plan_only=True)["ksplit"] == 1, value
 
 
 @pytest.mark.parametrize("tier", ["A", "B"])

@@ -685,6 +685,47 @@ def test_decoder_folded_rmsnorm_matches_separate_norm_kernels(toy, ckpt):
 
 
 @pytest.mark.parametrize("ckpt", ["ckpt_gated_untied", "ckpt_relu_tied"])
+def test_decoder_one_position_with_ffn_in_streamed_and_few_row_gemms_tiled(toy, ckpt):
+    """Options dec_ffn_tiled = 0 (the one-position decoder's FFN-in on the weight-streaming kernel) and gemm_skinny = 0 (every
+    few-row GEMM on the tiled kernels - which also takes the decoder off the folded norm: it needs the weight-streaming family),
+    each alone and both together, at one decoder position: within the oracle bound of this file, within the 5e-3 this file allows
+    between the folded and the separate-norm path, and the passages in the same order as under the defaults.
+    The order is compared on the passages the ORACLE tells apart: walking down its margins (logit 11 - logit 12), a passage is kept
+    when it lies at least 2e-2 below the last one kept - four times the 5e-3 above: two paths, two logits per margin.  Closer
+    passages have no order that fp16 arithmetic owes anybody: of the 37 passages here, 20 and 30 of the ReLU checkpoint are
+    3.7e-4 apart in the oracle (-0.798362 / -0.798728), the default path has them the other way round (-0.799041 / -0.798520) and
+    gemm_skinny = 0 the oracle's way (-0.797198 / -0.797602) - bit for bit what dec_fold_norm = 0 gives, an order the test above
+    has accepted since the fold exists."""
+    from llmrankers import _synth
+    from oracle.t5_numpy import T5Oracle
+    dims, state, eng = toy[ckpt]
+    seqs = _synth.synth_token_batch(37, 3, 150, dims.vocab, seed=79)
+    ids = [11, 12, 13, 14]
+    want = T5Oracle(dims, state).score_last(seqs, [0], ids)
+    dw = want[:, 0] - want[:, 1]
+    apart = []
+    for i in np.argsort(-dw, kind="stable"):
+        if not apart or dw[apart[-1]] - dw[i] >= 2e-2:
+            apart.append(int(i))
+    assert len(apart) >= 6, (len(apart), np.sort(dw))
+    base = eng.score(seqs, [0], ids)
+    assert np.abs(base - want).max() < LOGIT_TOL
+    for opts in ({"dec_ffn_tiled": 0}, {"gemm_skinny": 0}, {"dec_ffn_tiled": 0, "gemm_skinny": 0}):
+        try:
+            for key, v in opts.items():
+                eng.set_option(key, v)
+            got = eng.score(seqs, [0], ids)
+        finally:
+            eng.set_option("dec_ffn_tiled", 1)
+            eng.set_option("gemm_skinny", 1)                              # (1 = every epilogue kind: the default)
+        assert np.abs(got - want).max() < LOGIT_TOL, (opts, np.abs(got - want).max())
+        assert np.abs(_sigm(got[:, 0] - got[:, 1]) - _sigm(dw)).max() < SCORE_TOL, opts
+        assert np.abs(got - base).max() < 5e-3, (opts, np.abs(got - base).max())
+        db, dg = (base[:, 0] - base[:, 1])[apart], (got[:, 0] - got[:, 1])[apart]
+        np.testing.assert_array_equal(np.argsort(-dg, kind="stable"), np.argsort(-db, kind="stable"), err_msg=str(opts))
+
+
+@pytest.mark.parametrize("ckpt", ["ckpt_gated_untied", "ckpt_relu_tied"])
 def test_two_token_greedy_with_candidates_equals_two_steps(toy, ckpt):
     """rk_t5_greedy2: the second step computed speculatively for every candidate first token, in the same decoder pass as
     the first - tokens and step count identical to rk_t5_greedy(max_new=2), whether the first token is a candidate

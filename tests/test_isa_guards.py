@@ -145,6 +145,43 @@ def _instructions(body):
     return out
 
 
+@pytest.mark.parametrize("epi,rs,split", [(1, 0, 1), (4, 0, 1)])
+def test_pingpong_gemm_k_split_hand_off_follows_the_recipe(isa, epi, rs, split):
+    """gemm_pp2_kernel<.., SPLIT>: the one cross-workgroup hand-off of the library (a partial tile travels as a slab from the first
+    arriver to the last).  Consumer: ONE agent acquire (buffer_inv sc1) by the lane that took the ticket, an s_waitcnt vmcnt(0)
+    behind it - the invalidate completes asynchronously, only the wait holds the workgroup barrier until it has - then the barrier,
+    then plain loads of the slab by all eight waves; never a flat_ load.  Producer: every sc1 slab store is drained by its own wave
+    (s_waitcnt vmcnt(0)) in front of the barrier behind which one lane takes the ticket.  DESIGN.md "How the K-split hand-off is
+    tested"."""
+    body = kernel_body(isa, f"_Z15gemm_pp2_kernelILi{epi}ELi0ELb{rs}ELb{split}EEv8GemmArgs")
+    ins = [code for _, code in _instructions(body)]
+    assert not any(c.startswith("flat_load") for c in ins), "flat_ load in the K-split kernel"
+
+    def next_barrier(pos):
+        return next(j for j in range(pos + 1, len(ins)) if ins[j].startswith("s_barrier"))
+
+    def drained(lo, hi):
+        return any(c.startswith("s_waitcnt") and "vmcnt(0)" in c for c in ins[lo + 1:hi])
+
+    # ---- producer: 32 slab stores, each drained before the next barrier; the ticket is taken behind that barrier ----
+    stores = [j for j, c in enumerate(ins) if re.match(r"global_store_dwordx4 .*\bsc1\b", c)]
+    assert len(stores) == 32, len(stores)
+    for j in stores:
+        assert drained(j, next_barrier(j)), f"slab store not drained before the barrier: {ins[j]}"
+    publish_barrier = next_barrier(stores[-1])
+    tickets = [j for j, c in enumerate(ins) if c.startswith("global_atomic_add")]
+    assert len(tickets) == 1 and tickets[0] > publish_barrier, "the ticket must be taken behind the barrier that follows the slab stores"
+    # ---- consumer: one acquire behind the ticket, waited for before the barrier; the slab loads behind that barrier ----
+    invs = [j for j, c in enumerate(ins) if re.match(r"buffer_inv\b.*\bsc1\b", c)]
+    assert len(invs) == 1 and invs[0] > tickets[0], [ins[j] for j in invs]
+    acquire_barrier = next_barrier(invs[0])
+    assert drained(invs[0], acquire_barrier), "no s_waitcnt vmcnt(0) between the acquire's buffer_inv and the barrier that releases the other waves"
+    # the slab loads: the plain 16-byte loads (the residual epilogue's loads of the old rows are `nt`, the operands travel by LDS-DMA)
+    slab = [j for j, c in enumerate(ins) if re.match(r"global_load_dwordx4\b", c) and not re.search(r"\bnt\b", c)]
+    assert len(slab) == 32, len(slab)
+    assert min(slab) > acquire_barrier, f"slab load in front of the acquire's barrier: {ins[min(slab)]}"
+
+
 def test_no_valu_written_sgpr_feeds_an_inline_asm_memory_instruction_without_wait_states(isa):
     """gfx9 / CDNA hazard: a VALU instruction that writes an SGPR (v_readlane / v_readfirstlane - which is how the compiler brings
     a spilled SGPR back - , v_cmp with an SGPR destination) needs FIVE wait states before a VMEM instruction reads that SGPR.
