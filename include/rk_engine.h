@@ -218,6 +218,29 @@ int rk_llama_generate(rk_engine* e, const int32_t* tokens, const int32_t* seq_of
                       int max_new, int max_total, const int32_t* eos_ids, int n_eos, int pad_id,
                       int32_t* out_tokens, int32_t* out_steps);
 
+/* ---- sampling (hf: generation/logits_process.py TemperatureLogitsWarper -> TopKLogitsWarper -> TopPLogitsWarper, softmax, one
+ * multinomial draw per token; what the reference's bare self.llm.generate(input_ids), ref: llmrankers/listwise.py:268, does on a
+ * checkpoint whose generation_config.json says do_sample: true).  Opt-in: rk_llama_generate and rk_llama_session_admit stay greedy
+ * whatever is set here.  temperature 0 = off (greedy), top_k 0 = off, top_p 1 = off.  With temperature > 0 the `_sampled` entry
+ * points put a second head between the final norm and the token feedback: the full-vocabulary fp32 logits of the step's rows, then
+ * per row z = x / T; keep z >= the min(top_k, vocab)-th largest (ties at the threshold all stay); of those keep id i iff the softmax
+ * mass of the kept ids with z_j <= z_i exceeds 1 - top_p (HF's rule on values; the largest always stays); the token is the first kept
+ * id in vocabulary order whose running sum of w = exp((x - max x) / T) exceeds u * sum(w), u = (first word of Philox4x32-10 >> 8) *
+ * 2^-24 with key = the row's 64-bit seed (low word, high word) and counter = (index of the new token in its sequence, 0, 0, 0).  A
+ * row's token is a function of its logit bits, (T, k, p), its seed and that index: not of the batch, the slot, what the slot held
+ * before, or whether the step ran eagerly or from a graph (the index is read from the decoders' device positions).  The vocabulary
+ * must be a multiple of 4 (the fp32 store of the weight-streaming GEMM; RK_ERR_STATE from the first sampled call otherwise).
+ * Distribution parity with HF, not token parity: HF draws from torch's generator.
+ * RK_ERR_INVALID for temperature < 0, NaN or infinite, top_k < 0, top_p outside (0, 1]; RK_ERR_STATE on a T5 engine or while a
+ * session is open (a session latches the parameters at its open).  May be called after finalize; starts a new graph epoch, as
+ * rk_engine_set_option does. */
+int rk_llama_set_sampling(rk_engine* e, float temperature, int top_k, float top_p);
+/* rk_llama_generate's arguments, checks and contract, plus seeds[n_seq] (null: RK_ERR_INVALID): row b draws its tokens from its own
+ * Philox stream seeds[b].  With sampling off: rk_llama_generate bit for bit, the seeds ignored. */
+int rk_llama_generate_sampled(rk_engine* e, const int32_t* tokens, const int32_t* seq_offsets, int n_seq,
+                              int max_new, int max_total, const int32_t* eos_ids, int n_eos, int pad_id,
+                              int32_t* out_tokens, int32_t* out_steps, const uint64_t* seeds);
+
 /* ---- decoding session: continuous batching for long greedy decodes (the Rank-R1 ranker; the reference serves it through
  * vLLM, ref: llmrankers/setwise.py:406-553, which gives a finished row's place to the next request).  A session has a fixed
  * number of cache slots of max_len positions each; prompts are admitted into free slots while the other slots keep their state;
@@ -233,6 +256,13 @@ int rk_llama_session_open(rk_engine* e, int n_slots, int max_len, int max_new_ca
  * or named twice, RK_ERR_CAPACITY for len + max_new > max_len, max_new > max_new_cap or a batch beyond the prefill's capacities. */
 int rk_llama_session_admit(rk_engine* e, const int32_t* tokens, const int32_t* seq_offsets, const int32_t* slots,
                            const int32_t* max_new, int n);
+/* rk_llama_session_admit's arguments, checks and contract, plus seeds[n] (null: RK_ERR_INVALID): prompt b draws from seeds[b], in
+ * its column 0 and in every later step of its slot; its tokens are bit for bit rk_llama_generate_sampled's for it alone with that
+ * seed, whatever shares the session and whatever the slot held before.  A session latches the sampling parameters at
+ * rk_llama_session_open: opened with sampling on, every admit is this one and plain rk_llama_session_admit is RK_ERR_STATE; opened
+ * with sampling off, this one is RK_ERR_STATE.  A refused admit touches nothing. */
+int rk_llama_session_admit_sampled(rk_engine* e, const int32_t* tokens, const int32_t* seq_offsets, const int32_t* slots,
+                                   const int32_t* max_new, int n, const uint64_t* seeds);
 /* Steps until at least one slot has newly finished, no slot is active, or max_steps steps were issued (one step stays queued
  * ahead of the host's check, so a finish is seen one step late; that step changes nothing for the finished slot).
  * out_finished[n_slots] receives the slots that finished since the last run (at admit included), *out_n_finished their number,
@@ -586,7 +616,8 @@ int rk_debug_graph_stats(rk_engine* e, rk_debug_graph_stats_t* out);
  * (csrc/rk_engine.hip: Grown<T>::reserve) - and the move counters that stand in the graph keys.  Per buffer its device address
  * (0: never allocated) and its capacity in elements, in the order of RK_DEBUG_BUFFER_NAMES; amax_gen counts the moves of amax_val
  * and amax_idx (two per growth), kv_gen those of kv_cache, lkv_gen those of lkv, lpart and lints; logits and gen_buf have no
- * counter (no graph holds logits; gen_buf is sized by the engine's capacities alone and is allocated once).  With it a test can
+ * counter here (the graphs of the sampled Llama steps hold logits and carry an internal counter of its moves in their keys; a move
+ * shows as a new address; gen_buf is sized by the engine's capacities alone and is allocated once).  With it a test can
  * say which buffer a call moved.  Host state only: nothing is launched or waited for. */
 #define RK_DEBUG_N_BUFFERS 8
 #define RK_DEBUG_BUFFER_NAMES "logits amax_val amax_idx kv_cache gen_buf lkv lpart lints"
@@ -596,6 +627,22 @@ typedef struct rk_debug_buffers_t {
   int amax_gen, kv_gen, lkv_gen;
 } rk_debug_buffers_t;
 int rk_debug_buffers(rk_engine* e, rk_debug_buffers_t* out);
+/* debug: sample_rows_kernel (csrc/sampling_kernels.h) alone, through the launcher the sampling head calls, on host data.  Works on
+ * an engine of either family and needs no rk_llama_set_sampling: everything comes from the call.
+ *   logits      host fp32 [logit_rows][V], 1 <= V <= 2^23 (any such V: the kernel itself has no multiple-of-4 rule); row r of the call reads logits
+ *               row r % logit_rows, so many (seed, index) pairs can be drawn from a few rows in one launch (1 <= logit_rows <= rows)
+ *   temperature > 0, top_k >= 0 (0 or >= V: off), top_p in (0, 1] (1: off)
+ *   seeds[rows], index[rows] (>= 0): the row's Philox key and counter word
+ *   out_token[rows]; out_kept_k[rows], out_kept_p[rows] (optional): the ids kept after top-k, and after top-p
+ * RK_ERR_INVALID for anything outside that, nothing launched. */
+typedef struct rk_debug_sample_call {
+  int rows, logit_rows, V;
+  float temperature; int top_k; float top_p;
+  const float* logits;
+  const uint64_t* seeds; const int32_t* index;
+  int32_t* out_token; int32_t* out_kept_k; int32_t* out_kept_p;
+} rk_debug_sample_call;
+int rk_debug_sample(rk_engine* e, rk_debug_sample_call* call);
 
 #ifdef __cplusplus
 }

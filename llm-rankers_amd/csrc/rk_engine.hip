@@ -31,6 +31,7 @@
 #include "llama_kernels_hd64.h"
 #include "llama_kernels_qknorm.h"
 #include "misc_kernels.h"
+#include "sampling_kernels.h"
 
 namespace {
 
@@ -196,7 +197,8 @@ struct rk_engine {
   std::vector<EncLayerW> enc;
   std::vector<DecLayerW> dec;
   float *enc_final_ln = nullptr, *dec_final_ln = nullptr, *lut_enc = nullptr, *lut_dec = nullptr;
-  Grown<float> logits;                                         // qlm head: per-block (max, sum exp) pairs [rows, vocab/32] + label logits [rows]; slot 0 only
+  Grown<float> logits; int logits_gen = 0;                     // qlm head: per-block (max, sum exp) pairs [rows, vocab/32] + label logits [rows]; slot 0 only.
+                                                               // Llama sampling head: the step's fp32 logits [rows, vocab] (logits_gen counts the moves)
   Grown<float> amax_val; Grown<int> amax_idx; int amax_gen = 0;   // greedy head: per-row block maxima / first columns
   // rk_t5_generate: self-attention K / V cache [n_dec_layers][n_seq][P][2 inner] (kv_gen counts the moves) and the per-call int
   // block on the device (state, prefix, finished rows, output, tree arrays); decode_cached: pinned read-back of the finished step
@@ -233,6 +235,10 @@ struct rk_engine {
   bool qk_norm = false;                                                           // Qwen3 family: RMSNorm over head_dim on every q and k head (rk_llama_set_qk_norm)
   int window = 0;                                                                 // Mistral family: sliding window W (rk_llama_set_sliding_window), 0 = none
   std::vector<LlamaLayerW> ll; float *l_final_ln = nullptr, *rope_cos = nullptr, *rope_sin = nullptr; int* d_pos = nullptr;
+  // rk_llama_set_sampling: temperature 0 = off (every entry point is greedy); d_seeds: one Philox key per row / session slot
+  // (max_seqs of them, allocated once: no graph ever sees it move)
+  struct Sampling { float T = 0.f; int k = 0; float p = 1.f; bool on() const { return T > 0.f; } } samp;
+  unsigned long long* d_seeds = nullptr;
   // rk_llama_generate: K / V cache [n_layers][2][n_seq][n_kv][P][head_dim], the attention partials and the call's int block (grown
   // between calls; lkv_gen counts the moves and is part of the step graph's key), and the step's activation rows (max_seqs each)
   Grown<half_t> lkv; Grown<float> lpart; Grown<int> lints; int lkv_gen = 0;
@@ -242,6 +248,7 @@ struct rk_engine {
   struct LlamaSession {
     bool open = false; int n_slots = 0, max_len = 0, cap = 0, seen = 0;   // seen: the session word at the last read-back
     std::vector<int> busy, told, len, max_new, col, done;                 // per slot; told: its finish was returned by a run
+    bool sampled = false; std::vector<unsigned long long> seeds;          // latched at open: the sampling head; every slot's seed
   } ls;
   // decoder chains as HIP graphs: key = everything the launch parameters of a chain depend on; at most RK_GRAPH_CACHE_KEYS keys
   // (run_graphed); graph_count: what run_graphed did since the engine was created (rk_debug_graph_stats)
@@ -1567,7 +1574,7 @@ int Grown<T>::reserve(rk_engine* e, size_t n, int* gen) {
 int ensure_logits(rk_engine* e, size_t rows) {
   // fused qlm head: rows x ceil(vocab / 32) float2 block statistics, then rows floats of label logits (the [rows, vocab]
   // fp32 logits this buffer used to hold are never materialised)
-  return e->logits.reserve(e, rows * (2 * ((size_t)(e->d.vocab + 31) / 32) + 1));
+  return e->logits.reserve(e, rows * (2 * ((size_t)(e->d.vocab + 31) / 32) + 1), &e->logits_gen);
 }
 
 float head_scale(const rk_engine* e) {   // hf: modeling_t5.py:1044-1045 (scale_decoder_outputs)
@@ -1665,7 +1672,7 @@ int stage_slot(rk_engine* e, int slot, const int32_t* tokens, const int32_t* seq
 // The table holds at most RK_GRAPH_CACHE_KEYS keys: the key that would pass the bound ERASES every other entry (evict_graphs) -
 // their graphs, their sightings, and the entries of epochs that no call can reach any more - and the keys still in use come back
 // on their next two sightings.  One eviction per RK_GRAPH_CACHE_KEYS new keys; every outcome is counted (rk_debug_graph_stats).
-enum GraphKind { GK_T5_SCORE, GK_T5_GREEDY_STEP, GK_T5_GREEDY2, GK_T5_GENERATE_STEP, GK_LLAMA_STEP, GK_T5_COMPARE, GK_LLAMA_SESSION_STEP };   // which chain: the key's first int
+enum GraphKind { GK_T5_SCORE, GK_T5_GREEDY_STEP, GK_T5_GREEDY2, GK_T5_GENERATE_STEP, GK_LLAMA_STEP, GK_T5_COMPARE, GK_LLAMA_SESSION_STEP, GK_LLAMA_STEP_SAMPLED, GK_LLAMA_SESSION_STEP_SAMPLED };   // which chain: the key's first int
 // Every entry but `keep` goes.  A graph of the other slot, or of this stream's previous call, may still be replaying: both slots'
 // decoder streams and slot 0's encoder stream (the Llama family's, and every decoder's with overlap = 0) are drained first, so
 // no graph is destroyed under a launch.  (Erasing the other elements of a std::map leaves the reference to `keep` valid.)
@@ -2438,6 +2445,31 @@ static int head_argmax(rk_engine* e, hipStream_t st, const half_t* x, int rows, 
   if (rc == RK_OK) launch_argmax_blocks(st, e->amax_val.p, e->amax_idx.p, nblk, d_out, rows);
   return rc;
 }
+// Sampling head (Llama family, rk_llama_set_sampling): the full-vocabulary fp32 logits of `rows` final-normed rows into e->logits
+// - the weight-streaming family again, a row's logits are its own dot products whatever shares the launch - and one draw per row by
+// sample_rows_kernel (sampling_kernels.h) into d_out, where the advance kernels expect the arg-max.  The token index of row r is
+// pos[pos_map ? pos_map[r] : r] + 1 (the decoders' device positions: the row's last token), its seed e->d_seeds[seed_map ?
+// seed_map[r] : r].  ensure_sample_head before the chain starts, never inside a capture: logits_gen stands in the graph keys.
+static int ensure_sample_head(rk_engine* e, size_t rows) {
+  if (e->d.vocab > sampling::MAX_VOCAB) return fail(e, RK_ERR_STATE, "sampling head: vocabulary %d beyond %d (the fixed-point sums' headroom)", e->d.vocab, sampling::MAX_VOCAB);
+  int rc = e->logits.reserve(e, rows * (size_t)e->d.vocab, &e->logits_gen);
+  if (rc == RK_OK && !e->d_seeds) rc = dalloc(e, &e->d_seeds, (size_t)e->d.max_seqs);
+  return rc;
+}
+static void launch_sample_rows(hipStream_t st, const float* logits, int n_logit_rows, int vocab, const rk_engine::Sampling& sp,
+                               const unsigned long long* seeds, const int* seed_map, const int* pos, const int* pos_map, int pos_add,
+                               int* d_out, int* kept, int rows) {
+  hipLaunchKernelGGL(sample_rows_kernel, dim3(rows), dim3(sampling::THREADS), 0, st, logits, n_logit_rows, (long)vocab, vocab, sp.T, sp.k, sp.p,
+                     seeds, seed_map, pos, pos_map, pos_add, d_out, kept);
+}
+static int head_sample(rk_engine* e, hipStream_t st, const half_t* x, int rows, int d_model, int vocab, const rk_engine::Sampling& sp,
+                       const int* seed_map, const int* pos, const int* pos_map, int* d_out) {
+  const int rc = gemm(e, st, Gemm(PC_HEAD, EPI_STORE_F32, x, d_model, e->lm_head, d_model, e->logits.p, vocab, rows, vocab, d_model).on(GEMM_STREAM));
+  if (rc) return rc;
+  Bracket br(e, st, PC_HEAD, 0, 10.0 * rows * vocab * 4.0);
+  launch_sample_rows(st, e->logits.p, rows, vocab, sp, e->d_seeds, seed_map, pos, pos_map, 1, d_out, nullptr, rows);
+  return RK_OK;
+}
 // T5: final norm of `rows` decoder rows (row_map, or the first rows) -> arg-max head -> sl.d_argmax
 static int final_argmax(rk_engine* e, hipStream_t st, Slot& sl, const int* row_map, int rows) {
   rmsnorm(e, st, sl.dec.hidden, e->dec_final_ln, sl.dlast, row_map, rows, head_scale(e));
@@ -2952,8 +2984,10 @@ static int llama_step_rows(rk_engine* e, hipStream_t st, int rows, int P, const 
 // weight-streaming family (the caller's regime, never the row count: a row's tokens do not depend on what shares the call).  The
 // step is one graph per (rows, P, cache generation), replayed; position, finished rows and next ids live on the device; the host
 // reads one word per step and keeps one step queued ahead (rk_t5_generate's loop).
-int rk_llama_generate(rk_engine* e, const int32_t* tokens, const int32_t* seq_offsets, int n_seq, int max_new, int max_total,
-                      const int32_t* eos_ids, int n_eos, int pad_id, int32_t* out_tokens, int32_t* out_steps) {
+// seeds != null (rk_llama_generate_sampled with sampling on): head_sample in head_argmax's place, in the prefill's head and in the
+// step - a graph of its own kind, keyed by logits_gen too.  Everything else is the greedy call's.
+static int llama_generate(rk_engine* e, const int32_t* tokens, const int32_t* seq_offsets, int n_seq, int max_new, int max_total,
+                          const int32_t* eos_ids, int n_eos, int pad_id, int32_t* out_tokens, int32_t* out_steps, const uint64_t* seeds) {
   if (!e) return RK_ERR_INVALID;
   if (e->family != 1) return fail(e, RK_ERR_STATE, "rk_llama_generate called on a T5 engine (use rk_t5_generate)");
   if (e->ls.open) return fail(e, RK_ERR_STATE, "rk_llama_generate while a decoding session is open (it shares the cache and the step's rows): rk_llama_session_close first");
@@ -2974,6 +3008,7 @@ int rk_llama_generate(rk_engine* e, const int32_t* tokens, const int32_t* seq_of
   const int P = sl.maxL + max_new, S = l.max_seqs;
   if ((rc = ensure_amax(e, (size_t)n_seq))) return rc;
   if ((rc = ensure_llama_gen(e, n_seq, P, 16 + 4 * (size_t)S + (size_t)n_seq * max_new))) return rc;
+  if (seeds && (rc = ensure_sample_head(e, (size_t)n_seq))) return rc;
   hipStream_t st = sl.se;
   // the call's int block: {n, finished step, pad, n_eos, max_new, max_total, P, 0, eos[8]} | len[S] | done[S] | pos[S] | next[S] | out[n][max_new]
   int* g = e->lints.p;
@@ -2985,23 +3020,53 @@ int rk_llama_generate(rk_engine* e, const int32_t* tokens, const int32_t* seq_of
   for (size_t k = 0; k < (size_t)n_seq * max_new; ++k) init[16 + 4 * (size_t)S + k] = pad_id;
   HIPCHK(e, hipStreamSynchronize(st));
   HIPCHK(e, hipMemcpy(g, init.data(), init.size() * sizeof(int), hipMemcpyHostToDevice));
+  if (seeds) HIPCHK(e, hipMemcpy(e->d_seeds, seeds, (size_t)n_seq * sizeof(uint64_t), hipMemcpyHostToDevice));
   const LlamaKeep keep{e->lkv.p, P};
   if ((rc = llama_prefill(e, tokens, seq_offsets, n_seq, &keep))) return rc;
-  auto head_and_advance = [&]() -> int {
-    int r = head_argmax(e, st, sl.dlast, n_seq, l.hidden, l.vocab, sl.d_argmax);
+  // the token index of the row's new token = the position of its last token + 1: the prefill's positions at the last rows for
+  // column 0, the advance kernel's pos[] (len + column - 1) for the steps
+  auto head_and_advance = [&](bool prefill) -> int {
+    int r = !seeds ? head_argmax(e, st, sl.dlast, n_seq, l.hidden, l.vocab, sl.d_argmax)
+                   : head_sample(e, st, sl.dlast, n_seq, l.hidden, l.vocab, e->samp, nullptr, prefill ? e->d_pos : d_pos,
+                                 prefill ? sl.idx.d[IX_LAST_ROWS] : nullptr, sl.d_argmax);
     if (r) return r;
     Bracket br(e, st, PC_OTHER, 0, 0);
     launch_llama_advance(st, sl.d_argmax, g, d_len, d_done, d_pos, d_out, d_next, n_seq);
     return RK_OK;
   };
-  if ((rc = head_and_advance())) return rc;
+  if ((rc = head_and_advance(true))) return rc;
   auto step = [&]() -> int {
     const int r = llama_step_rows(e, st, n_seq, P, d_next, d_pos);
-    return r ? r : head_and_advance();
+    return r ? r : head_and_advance(false);
   };
-  const std::vector<int> key{GK_LLAMA_STEP, 0, n_seq, P, e->amax_gen, e->lkv_gen};
+  const std::vector<int> key = seeds ? std::vector<int>{GK_LLAMA_STEP_SAMPLED, 0, n_seq, P, e->logits_gen, e->lkv_gen}
+                                     : std::vector<int>{GK_LLAMA_STEP, 0, n_seq, P, e->amax_gen, e->lkv_gen};
   // column 0 is the prefill's: the steps produce columns 1 .. max_new - 1
   return decode_cached(e, st, key, step, 0, 1, n_seq, max_new, g + 1, d_out, out_tokens, out_steps);
+}
+int rk_llama_generate(rk_engine* e, const int32_t* tokens, const int32_t* seq_offsets, int n_seq, int max_new, int max_total,
+                      const int32_t* eos_ids, int n_eos, int pad_id, int32_t* out_tokens, int32_t* out_steps) {
+  return llama_generate(e, tokens, seq_offsets, n_seq, max_new, max_total, eos_ids, n_eos, pad_id, out_tokens, out_steps, nullptr);
+}
+int rk_llama_generate_sampled(rk_engine* e, const int32_t* tokens, const int32_t* seq_offsets, int n_seq, int max_new, int max_total,
+                              const int32_t* eos_ids, int n_eos, int pad_id, int32_t* out_tokens, int32_t* out_steps, const uint64_t* seeds) {
+  if (!e) return RK_ERR_INVALID;
+  if (!seeds) return fail(e, RK_ERR_INVALID, "rk_llama_generate_sampled: null seeds");
+  return llama_generate(e, tokens, seq_offsets, n_seq, max_new, max_total, eos_ids, n_eos, pad_id, out_tokens, out_steps,
+                        e->family == 1 && e->samp.on() ? seeds : nullptr);
+}
+
+// temperature 0 = off.  Like an option: the step graphs hold (T, k, p) as launch arguments, so a new graph epoch starts.
+int rk_llama_set_sampling(rk_engine* e, float temperature, int top_k, float top_p) {
+  if (!e) return RK_ERR_INVALID;
+  if (e->family != 1) return fail(e, RK_ERR_STATE, "rk_llama_set_sampling called on a T5 engine (the T5 rankers decode greedily)");
+  if (e->ls.open) return fail(e, RK_ERR_STATE, "rk_llama_set_sampling while a decoding session is open (it latched the parameters at its open): rk_llama_session_close first");
+  if (!(temperature >= 0.f) || std::isinf(temperature)) return fail(e, RK_ERR_INVALID, "temperature must be finite and >= 0 (got %g; 0 = greedy)", (double)temperature);
+  if (top_k < 0) return fail(e, RK_ERR_INVALID, "top_k must be >= 0 (got %d; 0 = off)", top_k);
+  if (!(top_p > 0.f && top_p <= 1.f)) return fail(e, RK_ERR_INVALID, "top_p must be in (0, 1] (got %g; 1 = off)", (double)top_p);
+  e->samp.T = temperature; e->samp.k = top_k; e->samp.p = top_p;
+  e->opt_epoch++;
+  return RK_OK;
 }
 
 // ---- decoding session: fixed cache slots, prompts admitted while the other slots keep their state, ONE replayed step graph ----
@@ -3055,8 +3120,10 @@ int rk_llama_session_open(rk_engine* e, int n_slots, int max_len, int max_new_ca
   const size_t S = (size_t)n_slots, n_ints = 16 + 9 * S + S * (size_t)max_new_cap;
   if ((rc = ensure_amax(e, S))) return rc;
   if ((rc = ensure_llama_gen(e, n_slots, max_len, n_ints))) return rc;
+  if (e->samp.on() && (rc = ensure_sample_head(e, S))) return rc;
   auto& ls = e->ls;
   ls.n_slots = n_slots; ls.max_len = max_len; ls.cap = max_new_cap; ls.seen = 0;
+  ls.sampled = e->samp.on(); ls.seeds.assign(S, 0);          // latched: rk_llama_set_sampling is refused until the close
   ls.busy.assign(S, 0); ls.told.assign(S, 0); ls.len.assign(S, 0); ls.max_new.assign(S, 0); ls.col.assign(S, 0); ls.done.assign(S, 1);
   std::vector<int> init(n_ints, 0);                        // every slot idle: done, position 0, pad as its next id
   init[1] = pad_id; init[2] = n_eos; init[3] = max_len; init[4] = max_new_cap;
@@ -3070,10 +3137,15 @@ int rk_llama_session_open(rk_engine* e, int n_slots, int max_len, int max_new_ca
   return RK_OK;
 }
 
-int rk_llama_session_admit(rk_engine* e, const int32_t* tokens, const int32_t* seq_offsets, const int32_t* slots, const int32_t* max_new, int n) {
-  int rc = session_check(e, "rk_llama_session_admit");
+// seeds: null from rk_llama_session_admit, the prompts' seeds from rk_llama_session_admit_sampled; which of the two a session takes
+// was decided at its open
+static int session_admit(rk_engine* e, const int32_t* tokens, const int32_t* seq_offsets, const int32_t* slots, const int32_t* max_new, int n,
+                         const uint64_t* seeds, const char* who) {
+  int rc = session_check(e, who);
   if (rc) return rc;
   auto& ls = e->ls;
+  if (seeds && !ls.sampled) return fail(e, RK_ERR_STATE, "%s: the session was opened with sampling off (rk_llama_set_sampling before rk_llama_session_open)", who);
+  if (!seeds && ls.sampled) return fail(e, RK_ERR_STATE, "%s: the session was opened with sampling on: every admit is rk_llama_session_admit_sampled", who);
   if (!tokens || !seq_offsets || !slots || !max_new || n <= 0) return fail(e, RK_ERR_INVALID, "empty admit (n=%d)", n);
   // every check before anything is touched: a refused admit leaves the session as it was
   std::vector<char> taken(ls.n_slots, 0);
@@ -3098,15 +3170,30 @@ int rk_llama_session_admit(rk_engine* e, const int32_t* tokens, const int32_t* s
   for (int b = 0; b < n; ++b) { adm[b] = slots[b]; adm[n + b] = seq_offsets[b + 1] - seq_offsets[b]; adm[2 * n + b] = max_new[b]; }
   HIPCHK(e, hipStreamSynchronize(st));                     // (nothing is in flight between two session calls)
   HIPCHK(e, hipMemcpy(d.admit, adm.data(), adm.size() * sizeof(int), hipMemcpyHostToDevice));
+  if (seeds) {                                             // a slot keeps its seed until its next admit
+    for (int b = 0; b < n; ++b) ls.seeds[slots[b]] = seeds[b];
+    HIPCHK(e, hipMemcpy(e->d_seeds, ls.seeds.data(), ls.seeds.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
+  }
   const LlamaKeep keep{e->lkv.p, ls.max_len, d.admit, ls.n_slots};
   if ((rc = llama_prefill(e, tokens, seq_offsets, n, &keep))) return rc;
-  if ((rc = head_argmax(e, st, sl.dlast, n, e->ld.hidden, e->ld.vocab, sl.d_argmax))) return rc;
+  // (sampled: row r draws with its slot's seed, admit[r], at the index behind its prompt's last token)
+  if ((rc = !seeds ? head_argmax(e, st, sl.dlast, n, e->ld.hidden, e->ld.vocab, sl.d_argmax)
+                   : head_sample(e, st, sl.dlast, n, e->ld.hidden, e->ld.vocab, e->samp, d.admit, e->d_pos, sl.idx.d[IX_LAST_ROWS], sl.d_argmax))) return rc;
   {
     Bracket br(e, st, PC_OTHER, 0, 0);
     launch_session_advance(st, sl.d_argmax, d.st, d.len, d.col, d.max_new, d.done, d.pos, d.out, d.next, ls.n_slots, d.admit, n);
   }
   for (int b = 0; b < n; ++b) { const int s = slots[b]; ls.busy[s] = 1; ls.told[s] = 0; ls.len[s] = adm[n + b]; ls.max_new[s] = max_new[b]; }
   return session_read_back(e, st);
+}
+int rk_llama_session_admit(rk_engine* e, const int32_t* tokens, const int32_t* seq_offsets, const int32_t* slots, const int32_t* max_new, int n) {
+  return session_admit(e, tokens, seq_offsets, slots, max_new, n, nullptr, "rk_llama_session_admit");
+}
+int rk_llama_session_admit_sampled(rk_engine* e, const int32_t* tokens, const int32_t* seq_offsets, const int32_t* slots, const int32_t* max_new, int n,
+                                   const uint64_t* seeds) {
+  if (!e) return RK_ERR_INVALID;
+  if (!seeds) return fail(e, RK_ERR_INVALID, "rk_llama_session_admit_sampled: null seeds");
+  return session_admit(e, tokens, seq_offsets, slots, max_new, n, seeds, "rk_llama_session_admit_sampled");
 }
 
 int rk_llama_session_run(rk_engine* e, int max_steps, int32_t* out_finished, int32_t* out_n_finished, int32_t* out_steps) {
@@ -3125,12 +3212,14 @@ int rk_llama_session_run(rk_engine* e, int max_steps, int32_t* out_finished, int
   if (!untold() && live > 0 && max_steps > 0) {
     auto step = [&]() -> int {
       int r = llama_step_rows(e, st, ls.n_slots, ls.max_len, d.next, d.pos);
-      if (r || (r = head_argmax(e, st, sl.dlast, ls.n_slots, e->ld.hidden, e->ld.vocab, sl.d_argmax))) return r;
+      if (r || (r = !ls.sampled ? head_argmax(e, st, sl.dlast, ls.n_slots, e->ld.hidden, e->ld.vocab, sl.d_argmax)
+                                : head_sample(e, st, sl.dlast, ls.n_slots, e->ld.hidden, e->ld.vocab, e->samp, nullptr, d.pos, nullptr, sl.d_argmax))) return r;
       Bracket br(e, st, PC_OTHER, 0, 0);
       launch_session_advance(st, sl.d_argmax, d.st, d.len, d.col, d.max_new, d.done, d.pos, d.out, d.next, ls.n_slots, nullptr, 0);
       return RK_OK;
     };
-    const std::vector<int> key{GK_LLAMA_SESSION_STEP, 0, ls.n_slots, ls.max_len, ls.cap, e->amax_gen, e->lkv_gen};
+    const std::vector<int> key = ls.sampled ? std::vector<int>{GK_LLAMA_SESSION_STEP_SAMPLED, 0, ls.n_slots, ls.max_len, ls.cap, e->logits_gen, e->lkv_gen}
+                                            : std::vector<int>{GK_LLAMA_SESSION_STEP, 0, ls.n_slots, ls.max_len, ls.cap, e->amax_gen, e->lkv_gen};
     int* pin = e->gen_pin;
     const int limit = std::min(max_steps, live);
     bool stop = false;
@@ -4431,6 +4520,45 @@ int rk_debug_buffers(rk_engine* e, rk_debug_buffers_t* out) {
   static_assert(RK_DEBUG_N_BUFFERS == 8, "one put per grown buffer");
   out->amax_gen = e->amax_gen; out->kv_gen = e->kv_gen; out->lkv_gen = e->lkv_gen;
   return RK_OK;
+}
+
+// debug: sample_rows_kernel alone on host logits, through the launcher the sampling head calls (include/rk_engine.h).  Memory of its
+// own, freed on return; works on an engine of either family (every width comes from the call).
+int rk_debug_sample(rk_engine* e, rk_debug_sample_call* q) {
+  if (!e || !q) return RK_ERR_INVALID;
+  if (q->rows <= 0 || q->rows > (1 << 20) || q->logit_rows <= 0 || q->logit_rows > q->rows || q->V <= 0 || q->V > sampling::MAX_VOCAB)
+    return fail(e, RK_ERR_INVALID, "rk_debug_sample: rows %d (1 .. 2^20), logit_rows %d (1 .. rows), V %d (1 .. %d)", q->rows, q->logit_rows, q->V, sampling::MAX_VOCAB);
+  if (!q->logits || !q->seeds || !q->index || !q->out_token) return fail(e, RK_ERR_INVALID, "rk_debug_sample: null logits, seeds, index or out_token");
+  if (!(q->temperature > 0.f) || std::isinf(q->temperature) || q->top_k < 0 || !(q->top_p > 0.f && q->top_p <= 1.f))
+    return fail(e, RK_ERR_INVALID, "rk_debug_sample: temperature %g (> 0), top_k %d (>= 0), top_p %g (in (0, 1])", (double)q->temperature, q->top_k, (double)q->top_p);
+  for (int r = 0; r < q->rows; ++r)
+    if (q->index[r] < 0) return fail(e, RK_ERR_INVALID, "rk_debug_sample: token index %d of row %d is negative", q->index[r], r);
+  int rc = set_device(e);
+  if (rc) return rc;
+  const size_t rows = (size_t)q->rows, nl = (size_t)q->logit_rows * q->V;
+  float* d_logits = nullptr; unsigned long long* d_seeds = nullptr; int* d_ints = nullptr;   // ints: index[rows] | token[rows] | kept[rows][2]
+  auto done = [&](int r) { if (d_logits) hipFree(d_logits); if (d_seeds) hipFree(d_seeds); if (d_ints) hipFree(d_ints); return r; };
+  if (hipMalloc((void**)&d_logits, nl * sizeof(float)) != hipSuccess || hipMalloc((void**)&d_seeds, rows * sizeof(uint64_t)) != hipSuccess ||
+      hipMalloc((void**)&d_ints, 4 * rows * sizeof(int)) != hipSuccess)
+    return done(fail(e, RK_ERR_HIP, "rk_debug_sample: hipMalloc failed"));
+  hipStream_t st = e->slots[0].se;
+  std::vector<int> ints(4 * rows, -1);
+  memcpy(ints.data(), q->index, rows * sizeof(int));
+  if (hipMemcpy(d_logits, q->logits, nl * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(d_seeds, q->seeds, rows * sizeof(uint64_t), hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(d_ints, ints.data(), ints.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess)
+    return done(fail(e, RK_ERR_HIP, "rk_debug_sample: upload failed"));
+  const rk_engine::Sampling sp{q->temperature, q->top_k, q->top_p};
+  launch_sample_rows(st, d_logits, q->logit_rows, q->V, sp, d_seeds, nullptr, d_ints, nullptr, 0, d_ints + rows, d_ints + 2 * rows, q->rows);
+  if (hipStreamSynchronize(st) != hipSuccess || hipGetLastError() != hipSuccess ||
+      hipMemcpy(ints.data(), d_ints, ints.size() * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess)
+    return done(fail(e, RK_ERR_HIP, "rk_debug_sample: the launch failed"));
+  for (size_t r = 0; r < rows; ++r) {
+    q->out_token[r] = ints[rows + r];
+    if (q->out_kept_k) q->out_kept_k[r] = ints[2 * rows + 2 * r];
+    if (q->out_kept_p) q->out_kept_p[r] = ints[2 * rows + 2 * r + 1];
+  }
+  return done(RK_OK);
 }
 
 int64_t rk_debug_read(rk_engine* e, const char* name, float* out, int64_t max_floats) {

@@ -117,7 +117,14 @@ class RkDebugBuffers(C.Structure):
                [(n, C.c_int) for n in ("amax_gen", "kv_gen", "lkv_gen")]
 
 
-DEBUG_SENTINEL = 0xCD                      # RK_DEBUG_SENTINEL: the byte the guard bands of rk_debug_gemm_ex are filled with
+class RkDebugSampleCall(C.Structure):
+    """rk_debug_sample_call of include/rk_engine.h, field for field."""
+    _fields_ = [("rows", C.c_int), ("logit_rows", C.c_int), ("V", C.c_int), ("temperature", C.c_float), ("top_k", C.c_int),
+                ("top_p", C.c_float), ("logits", C.c_void_p), ("seeds", C.c_void_p), ("index", C.c_void_p),
+                ("out_token", C.c_void_p), ("out_kept_k", C.c_void_p), ("out_kept_p", C.c_void_p)]
+
+
+DEBUG_SENTINEL = 0xCD                    # RK_DEBUG_SENTINEL: the byte the guard bands of rk_debug_gemm_ex are filled with
 DEBUG_BAND_ROWS = 256
 GEMM_OUT_DTYPE = {0: np.float16, 1: np.float32, 2: np.float16, 3: np.float16, 4: np.float32, 5: np.float16, 6: np.float32, 7: np.float32}
 
@@ -155,6 +162,11 @@ ABI = {
     "rk_llama_greedy1": (C.c_int, [C.c_void_p, _i32p, _i32p, C.c_int, _i32p]),
     "rk_llama_last_logits": (C.c_int, [C.c_void_p, _i32p, _i32p, C.c_int, _i32p, C.c_int, _f32p]),
     "rk_llama_generate": (C.c_int, [C.c_void_p, _i32p, _i32p, C.c_int, C.c_int, C.c_int, _i32p, C.c_int, C.c_int, _i32p, _i32p]),
+    "rk_llama_set_sampling": (C.c_int, [C.c_void_p, C.c_float, C.c_int, C.c_float]),
+    "rk_llama_generate_sampled": (C.c_int, [C.c_void_p, _i32p, _i32p, C.c_int, C.c_int, C.c_int, _i32p, C.c_int, C.c_int, _i32p, _i32p,
+                                            _P(C.c_uint64)]),
+    "rk_llama_session_admit_sampled": (C.c_int, [C.c_void_p, _i32p, _i32p, _i32p, _i32p, C.c_int, _P(C.c_uint64)]),
+    "rk_debug_sample": (C.c_int, [C.c_void_p, _P(RkDebugSampleCall)]),
     "rk_llama_session_open": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, _i32p, C.c_int, C.c_int]),
     "rk_llama_session_admit": (C.c_int, [C.c_void_p, _i32p, _i32p, _i32p, _i32p, C.c_int]),
     "rk_llama_session_run": (C.c_int, [C.c_void_p, C.c_int, _i32p, _i32p, _i32p]),
@@ -231,6 +243,13 @@ def load_library(path: Optional[str] = None, make_default: bool = False):
 
 def _i32(a) -> np.ndarray:
     return np.ascontiguousarray(a, dtype=np.int32)
+
+
+def _seeds(seeds, n: int) -> np.ndarray:
+    """n 64-bit seeds as the engine takes them (Python ints are reduced mod 2^64)."""
+    if len(seeds) != n:
+        raise ValueError(f"{n} prompts but {len(seeds)} seeds")
+    return np.array([int(s) & 0xFFFFFFFFFFFFFFFF for s in seeds], dtype=np.uint64)
 
 
 def pack_ragged(seqs: Sequence[Sequence[int]]) -> Tuple[np.ndarray, np.ndarray]:
@@ -827,6 +846,27 @@ class RkEngine:
             self._chk(int(got))
         return out[:got]
 
+    def debug_sample(self, logits: np.ndarray, temperature: float, top_k: int, top_p: float, seeds, index, check=True):
+        """sample_rows_kernel alone through rk_debug_sample (include/rk_engine.h).  logits: fp32 [logit_rows, V]; seeds (uint64) and
+        index (int32), one per row of the call: row r draws from logits row r % logit_rows.  -> (token, kept after top-k, kept after
+        top-p), int32 [rows] each.  check=False: a refusal is returned as its code instead of raised."""
+        logits = np.ascontiguousarray(logits, dtype=np.float32)
+        assert logits.ndim == 2
+        seeds = np.ascontiguousarray(seeds, dtype=np.uint64).reshape(-1)
+        index = np.ascontiguousarray(index, dtype=np.int32).reshape(-1)
+        assert seeds.size == index.size
+        tok, kk, kp = (np.full(seeds.size, -1, np.int32) for _ in range(3))
+        q = RkDebugSampleCall()
+        q.rows, q.logit_rows, q.V = seeds.size, logits.shape[0], logits.shape[1]
+        q.temperature, q.top_k, q.top_p = float(temperature), int(top_k), float(top_p)
+        q.logits, q.seeds, q.index = logits.ctypes.data, seeds.ctypes.data, index.ctypes.data
+        q.out_token, q.out_kept_k, q.out_kept_p = tok.ctypes.data, kk.ctypes.data, kp.ctypes.data
+        rc = self.lib.rk_debug_sample(self.h, C.byref(q))
+        if not check and rc != 0:
+            return rc
+        self._chk(rc)
+        return tok, kk, kp
+
     def graph_stats(self) -> dict:
         """The decoder graph table and its counters (rk_debug_graph_stats): n_keys, n_ready, max_keys, and since the engine was
         created eager, captures, replays, failed, evictions."""
@@ -887,15 +927,27 @@ class RkLlamaEngine(RkEngine):
                                                 oi.ctypes.data_as(_i32p), len(oi), out.ctypes.data_as(_f32p)))
         return out
 
+    def set_sampling(self, temperature: float, top_k: int, top_p: float):
+        """rk_llama_set_sampling: temperature 0 = off (greedy), top_k 0 = off, top_p 1 = off.  Only the calls that pass seeds
+        sample; a session latches the setting at its open."""
+        self._chk(self.lib.rk_llama_set_sampling(self.h, float(temperature), int(top_k), float(top_p)))
+
     def generate(self, seqs: Sequence[Sequence[int]], max_new: int, eos_ids: Sequence[int], pad_id: int,
-                 max_total: int = 0) -> Tuple[np.ndarray, int]:
+                 max_total: int = 0, seeds: Optional[Sequence[int]] = None) -> Tuple[np.ndarray, int]:
         """Greedy continuation of every prompt (rk_llama_generate: the prefill once, then one KV-cached row per sequence and
         step) -> (tokens [B, max_new], columns produced).  A row finishes at one of `eos_ids` (at most 8) or, with max_total >
-        0, at that total length; finished rows emit pad_id."""
+        0, at that total length; finished rows emit pad_id.  seeds (one 64-bit seed per prompt): rk_llama_generate_sampled - every
+        row draws from its own stream under set_sampling's parameters (greedy while sampling is off)."""
         tok, off = pack_ragged(seqs)
         eos = _i32(list(eos_ids))
         out = np.empty((len(seqs), max_new), dtype=np.int32)
         steps = C.c_int32(0)
+        if seeds is not None:
+            sd = _seeds(seeds, len(seqs))
+            self._chk(self.lib.rk_llama_generate_sampled(self.h, tok.ctypes.data_as(_i32p), off.ctypes.data_as(_i32p), len(seqs),
+                                                         int(max_new), int(max_total), eos.ctypes.data_as(_i32p), len(eos), int(pad_id),
+                                                         out.ctypes.data_as(_i32p), C.byref(steps), sd.ctypes.data_as(_P(C.c_uint64))))
+            return out, int(steps.value)
         self._chk(self.lib.rk_llama_generate(self.h, tok.ctypes.data_as(_i32p), off.ctypes.data_as(_i32p), len(seqs), int(max_new),
                                              int(max_total), eos.ctypes.data_as(_i32p), len(eos), int(pad_id),
                                              out.ctypes.data_as(_i32p), C.byref(steps)))
@@ -937,14 +989,22 @@ class LlamaSession:
     def free_slots(self):
         return [s for s in range(self.n_slots) if s not in self.busy]
 
-    def admit(self, seqs: Sequence[Sequence[int]], slots: Sequence[int], max_new: Sequence[int]) -> None:
-        """ONE prefill of `seqs` into the free slots `slots`; prompt b generates up to max_new[b] tokens."""
+    def admit(self, seqs: Sequence[Sequence[int]], slots: Sequence[int], max_new: Sequence[int],
+              seeds: Optional[Sequence[int]] = None) -> None:
+        """ONE prefill of `seqs` into the free slots `slots`; prompt b generates up to max_new[b] tokens.  seeds (one per prompt):
+        rk_llama_session_admit_sampled, the admit of a session opened while sampling was on."""
         if not (len(seqs) == len(slots) == len(max_new)):
             raise ValueError("admit: seqs, slots and max_new must have one entry per prompt")
         tok, off = pack_ragged(seqs)
         sl, mn = _i32(list(slots)), _i32(list(max_new))
-        self.eng._chk(self.eng.lib.rk_llama_session_admit(self.eng.h, tok.ctypes.data_as(_i32p), off.ctypes.data_as(_i32p),
-                                                          sl.ctypes.data_as(_i32p), mn.ctypes.data_as(_i32p), len(seqs)))
+        if seeds is not None:
+            sd = _seeds(seeds, len(seqs))
+            self.eng._chk(self.eng.lib.rk_llama_session_admit_sampled(self.eng.h, tok.ctypes.data_as(_i32p), off.ctypes.data_as(_i32p),
+                                                                      sl.ctypes.data_as(_i32p), mn.ctypes.data_as(_i32p), len(seqs),
+                                                                      sd.ctypes.data_as(_P(C.c_uint64))))
+        else:
+            self.eng._chk(self.eng.lib.rk_llama_session_admit(self.eng.h, tok.ctypes.data_as(_i32p), off.ctypes.data_as(_i32p),
+                                                              sl.ctypes.data_as(_i32p), mn.ctypes.data_as(_i32p), len(seqs)))
         self.busy.update(int(s) for s in sl)
 
     def run(self, max_steps: int = 1 << 30):

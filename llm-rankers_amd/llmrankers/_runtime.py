@@ -506,7 +506,8 @@ class T5Runtime:
 def read_generation_settings(model_dir, cfg: dict) -> dict:
     """What the reference's bare `self.llm.generate(input_ids)` (ref: llmrankers/listwise.py:268) takes from the checkpoint:
     generation_config.json over config.json for eos_token_id (int or list -> list), pad_token_id (absent: the first EOS id, as
-    HF's generate does), max_new_tokens, max_length, do_sample."""
+    HF's generate does), max_new_tokens, max_length, do_sample, and the sampling parameters temperature, top_k, top_p (absent:
+    the defaults of HF's GenerationConfig, 1.0 / 50 / 1.0)."""
     gc = {}
     if model_dir and os.path.exists(os.path.join(model_dir, "generation_config.json")):
         with open(os.path.join(model_dir, "generation_config.json")) as f:
@@ -518,7 +519,20 @@ def read_generation_settings(model_dir, cfg: dict) -> dict:
     eos = [] if eos is None else ([int(t) for t in eos] if isinstance(eos, (list, tuple)) else [int(eos)])
     pad = pick("pad_token_id")
     return {"eos_token_ids": eos, "pad_token_id": int(pad) if pad is not None else (eos[0] if eos else 0),
-            "max_new_tokens": gc.get("max_new_tokens"), "max_length": gc.get("max_length"), "do_sample": bool(gc.get("do_sample"))}
+            "max_new_tokens": gc.get("max_new_tokens"), "max_length": gc.get("max_length"), "do_sample": bool(gc.get("do_sample")),
+            "temperature": float(gc["temperature"]) if gc.get("temperature") is not None else 1.0,
+            "top_k": int(gc["top_k"]) if gc.get("top_k") is not None else 50,
+            "top_p": float(gc["top_p"]) if gc.get("top_p") is not None else 1.0}
+
+
+def sampling_plan(runtime):
+    """None for a checkpoint that decodes greedily (no do_sample: true in its generation settings), else (temperature, top_k,
+    top_p) as HF's generate would apply them: the arguments of `set_sampling`.  For any runtime with a `generation` dict; a dict
+    built by hand may lack the three keys (HF's defaults then)."""
+    g = runtime.generation
+    if not g.get("do_sample"):
+        return None
+    return float(g.get("temperature", 1.0)), int(g.get("top_k", 50)), float(g.get("top_p", 1.0))
 
 
 def default_generation_length():
@@ -586,13 +600,27 @@ class LlamaRuntime:
         once."""
         return generation_plan(self, prompt_lens)
 
-    def generate(self, seqs, max_new, eos_ids, pad_id, max_total=0) -> np.ndarray:
+    sampling_on = False
+
+    def set_sampling(self, temperature, top_k, top_p):
+        """RkLlamaEngine.set_sampling; from then on `generate(..., seeds=...)` and a pool's `submit(..., seed=...)` sample
+        (temperature 0: off again) and generation_plan has no deviation to warn of."""
+        self.engine.set_sampling(temperature, top_k, top_p)
+        self.sampling_on = float(temperature) > 0
+
+    def generate(self, seqs, max_new, eos_ids, pad_id, max_total=0, seeds=None) -> np.ndarray:
         """[B, max_new] new tokens of every prompt (RkLlamaEngine.generate: prefill once, then one KV-cached row per token);
         chunked by capacity like T5Runtime.generate, the columns after the step at which every row of an engine call had
-        finished hold -1.  A chunk leaves room for its continuations in the engine's token capacity."""
+        finished hold -1.  A chunk leaves room for its continuations in the engine's token capacity.  seeds: one per prompt,
+        the sampled form (a prompt's tokens depend on its own seed only, not on its chunk)."""
         parts = []
+        done = 0
         for c in self._gen_chunks(seqs, max_new):
-            toks, steps = self.engine.generate(c, max_new, eos_ids, pad_id, max_total)
+            if seeds is not None:
+                toks, steps = self.engine.generate(c, max_new, eos_ids, pad_id, max_total, seeds=list(seeds[done:done + len(c)]))
+                done += len(c)
+            else:
+                toks, steps = self.engine.generate(c, max_new, eos_ids, pad_id, max_total)
             toks = toks.copy()
             toks[:, steps:] = -1
             parts.append(toks)
@@ -640,7 +668,8 @@ class DecodePool:
         self._open_session, self.n_slots, self.max_tokens, self.max_new_cap = open_session, int(n_slots), int(max_tokens), int(max_new_cap)
         self.session = None
         self.max_len = 0
-        self._queue = []                    # [(key, ids, max_new)] oldest first
+        self._queue = []                    # [(key, ids, max_new, seed)] oldest first
+        self._seeded = False                # the requests carry sampling seeds (submit)
         self._owner = {}                    # slot -> (key, prompt length)
         self.steps = self.admits = self.opens = self.tokens_out = 0
 
@@ -659,15 +688,21 @@ class DecodePool:
         if session is not None:
             session.close()
 
-    def submit(self, key, ids, max_new: int):
+    def submit(self, key, ids, max_new: int, seed=None):
+        """seed: the request's 64-bit sampling seed, for a pool over a session opened while sampling was on (every request of
+        such a pool has one; a greedy pool's requests have none)."""
         ids, max_new = [int(t) for t in ids], int(max_new)
+        if self._queue or self._owner:
+            if (seed is None) != (not self._seeded):
+                raise ValueError(f"request {key!r}: a pool's requests all carry a seed or none does")
+        self._seeded = seed is not None
         if not ids or max_new <= 0:
             raise ValueError(f"request {key!r}: an empty prompt or max_new {max_new}")
         if max_new > self.max_new_cap:
             raise ValueError(f"request {key!r}: max_new {max_new} exceeds the pool's max_new_cap {self.max_new_cap}")
         if len(ids) + max_new > self.max_tokens:
             raise ValueError(f"request {key!r}: a prompt of {len(ids)} tokens + {max_new} new ones exceeds the engine capacity {self.max_tokens}")
-        self._queue.append((key, ids, max_new))
+        self._queue.append((key, ids, max_new, seed))
 
     def pending(self) -> int:
         """requests queued or decoding"""
@@ -677,7 +712,7 @@ class DecodePool:
         """the head of the queue into the free slots: one admit"""
         if not self._queue:
             return
-        need = max(len(ids) + max_new for _, ids, max_new in self._queue)
+        need = max(len(ids) + max_new for _, ids, max_new, _ in self._queue)
         if self.session is None or (need > self.max_len and not self._owner):
             if self.session is not None:
                 self.session.close()
@@ -688,18 +723,21 @@ class DecodePool:
             self.opens += 1
         free = [s for s in range(self.n_slots) if s not in self.session.busy]
         take, tokens = [], 0
-        for key, ids, max_new in self._queue[:len(free)]:
+        for key, ids, max_new, seed in self._queue[:len(free)]:
             if len(ids) + max_new > self.max_len or tokens + len(ids) > self.max_tokens:
                 break                       # (FIFO: nothing overtakes a request that waits for a larger session or the next prefill)
-            take.append((key, ids, max_new))
+            take.append((key, ids, max_new, seed))
             tokens += len(ids)
         if not take:
             return
         slots = free[:len(take)]
-        self.session.admit([ids for _, ids, _ in take], slots, [m for _, _, m in take])
+        if self._seeded:
+            self.session.admit([t[1] for t in take], slots, [t[2] for t in take], seeds=[t[3] for t in take])
+        else:                               # (the greedy call shape, as every session double implements it)
+            self.session.admit([t[1] for t in take], slots, [t[2] for t in take])
         self.admits += 1
         del self._queue[:len(take)]
-        for slot, (key, ids, _) in zip(slots, take):
+        for slot, (key, ids, _, _) in zip(slots, take):
             self._owner[slot] = (key, len(ids))
 
     def wait(self):
@@ -725,10 +763,10 @@ def generation_plan(runtime, prompt_lens) -> dict:
     """LlamaRuntime.generation_plan for any runtime with a `generation` dict (the engine's, or a test double's)."""
     import logging
     g = runtime.generation
-    if g.get("do_sample") and not getattr(runtime, "_warned_sampling", False):
+    if g.get("do_sample") and not getattr(runtime, "sampling_on", False) and not getattr(runtime, "_warned_sampling", False):
         logging.getLogger("llmrankers").warning(
             "the checkpoint's generation_config.json asks for sampling (do_sample: true); the MI355X engine decodes greedily "
-            "(documented deviation, DESIGN.md section 4)")
+            "unless the ranker is given sample_seed (opt-in, DESIGN.md section 4)")
         runtime._warned_sampling = True
     longest = max(prompt_lens)
     new, total = g.get("max_new_tokens"), g.get("max_length")

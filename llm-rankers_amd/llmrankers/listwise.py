@@ -83,8 +83,11 @@ class ListwiseLlmRanker(LlmRanker):
                   "M", "N", "O", "P", "Q", "R", "S", "T", "U", "V", "W"]
 
     def __init__(self, model_name_or_path, tokenizer_name_or_path, device, window_size, step_size,
-                 scoring='generation', num_repeat=1, cache_dir=None):
+                 scoring='generation', num_repeat=1, cache_dir=None, sample_seed=None):
         # ref: listwise.py:207-247: T5 or Llama by config.model_type, NotImplementedError otherwise
+        # sample_seed (decoder-only checkpoints; not in the reference, whose sampling follows torch's global generator): None =
+        # greedy decoding whatever the checkpoint's generation settings say; an integer = a checkpoint that says do_sample: true
+        # is sampled on the device with its own temperature / top_k / top_p, reproducibly (see _setup)
         from ._runtime import load_runtime, resolve_checkpoint
         path = resolve_checkpoint(model_name_or_path, cache_dir)
         try:
@@ -98,7 +101,7 @@ class ListwiseLlmRanker(LlmRanker):
             tokenizer.use_default_system_prompt = False
             if 'v1.5' in model_name_or_path:       # the reference's `'vicuna' and 'v1.5' in name` (ref :238)
                 tokenizer.chat_template = VICUNA_TEMPLATE
-            self._setup(runtime, tokenizer, device, window_size, step_size, scoring, num_repeat, None)
+            self._setup(runtime, tokenizer, device, window_size, step_size, scoring, num_repeat, None, sample_seed)
             return
         from transformers import T5Tokenizer
         tokenizer = T5Tokenizer.from_pretrained(
@@ -107,18 +110,19 @@ class ListwiseLlmRanker(LlmRanker):
 
     @classmethod
     def from_runtime(cls, runtime, tokenizer, device="cuda", window_size=3, step_size=1, scoring='generation', num_repeat=1,
-                     max_new=None):
+                     max_new=None, sample_seed=None):
         """Build the ranker around an existing runtime (a loaded engine, or a test double) and tokenizer.  max_new: new tokens
-        per `generation` compare (None: the installed transformers' default, resolve_max_new)."""
+        per `generation` compare (None: the installed transformers' default, resolve_max_new).  sample_seed: as in __init__
+        (decoder-only runtimes)."""
         self = cls.__new__(cls)
         if getattr(runtime, "model_type", "t5") == "llama":        # the length comes from the runtime's generation settings
-            self._setup(runtime, tokenizer, device, window_size, step_size, scoring, num_repeat, max_new)
+            self._setup(runtime, tokenizer, device, window_size, step_size, scoring, num_repeat, max_new, sample_seed)
         else:
             self._setup(runtime, tokenizer, device, window_size, step_size, scoring, num_repeat,
                         resolve_max_new() if max_new is None else int(max_new))
         return self
 
-    def _setup(self, runtime, tokenizer, device, window_size, step_size, scoring, num_repeat, max_new):
+    def _setup(self, runtime, tokenizer, device, window_size, step_size, scoring, num_repeat, max_new, sample_seed=None):
         from ._runtime import require_decoder_positions
         require_decoder_positions(runtime, type(self).__name__)
         self.model_type = getattr(runtime, "model_type", "t5")
@@ -136,7 +140,14 @@ class ListwiseLlmRanker(LlmRanker):
         self.total_compare = 0
         self.total_prompt_tokens = 0
         self.total_completion_tokens = 0
+        self._seed_rng = None                    # sampling: one seed per compare, in compare order (the row's Philox key)
         if self.model_type == "llama":           # no decoder prompt / label ids: the reference's Llama branch sets none (ref :235-245)
+            from ._runtime import sampling_plan
+            plan = sampling_plan(runtime) if sample_seed is not None else None
+            if plan is not None:                 # (an integer on a greedy checkpoint changes nothing)
+                import random
+                runtime.set_sampling(*plan)
+                self._seed_rng = random.Random(int(sample_seed))
             return
         self.decoder_start = [int(getattr(runtime, "decoder_start_token_id", 0) or 0)]
         # likelihood: decoder prompt "<pad> Passage" and the last token of "<pad> Passage {label}" (ref: listwise.py:225-231)
@@ -179,7 +190,11 @@ class ListwiseLlmRanker(LlmRanker):
         plan = generation_plan(self.llm, [len(i) for i in ids])
         if self.max_new is not None:
             plan["max_new"], plan["max_total"] = int(self.max_new), 0
-        new = np.asarray(self.llm.generate(ids, plan["max_new"], plan["eos_ids"], plan["pad_id"], plan["max_total"]))
+        if self._seed_rng is not None:
+            seeds = [self._seed_rng.getrandbits(64) for _ in ids]
+            new = np.asarray(self.llm.generate(ids, plan["max_new"], plan["eos_ids"], plan["pad_id"], plan["max_total"], seeds=seeds))
+        else:
+            new = np.asarray(self.llm.generate(ids, plan["max_new"], plan["eos_ids"], plan["pad_id"], plan["max_total"]))
         outs, completion = [], []
         for prompt, row in zip(ids, new):
             toks = [int(t) for t in row if t >= 0]

@@ -274,7 +274,8 @@ def build_ranker(args):
         from llmrankers.listwise import ListwiseLlmRanker
         return ListwiseLlmRanker(model_name_or_path=args.run.model_name_or_path, tokenizer_name_or_path=args.run.tokenizer_name_or_path,
                                  device=args.run.device, cache_dir=args.run.cache_dir, window_size=args.listwise.window_size,
-                                 step_size=args.listwise.step_size, scoring=args.run.scoring, num_repeat=args.listwise.num_repeat)
+                                 step_size=args.listwise.step_size, scoring=args.run.scoring, num_repeat=args.listwise.num_repeat,
+                                 **({} if getattr(args.listwise, "sample_seed", None) is None else {"sample_seed": args.listwise.sample_seed}))
     raise ValueError("Must specify either --pointwise, --setwise, --pairwise or --listwise.")
 
 
@@ -566,6 +567,9 @@ def build_parser():
     lw.add_argument("--window_size", type=int, default=3)
     lw.add_argument("--step_size", type=int, default=1)
     lw.add_argument("--num_repeat", type=int, default=1)
+    lw.add_argument("--sample_seed", type=int, default=None,
+                    help="decoder-only checkpoints whose generation_config.json says do_sample: true: sample on the device with the "
+                         "checkpoint's temperature / top_k / top_p, reproducibly from this seed (default: greedy decoding, one warning)")
     return parser, commands
 
 
