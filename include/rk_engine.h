@@ -192,6 +192,21 @@ int rk_llama_set_qkv_bias(rk_engine* e, int on);
  * rk_engine_finalize; RK_ERR_STATE on a T5 engine or after finalize.  rk_engine_finalize then refuses (RK_ERR_STATE) head_dim 64, a
  * sliding window and q / k / v biases next to it: no Qwen3 checkpoint has them.  Never calling it (or on = 0): the names are ignored. */
 int rk_llama_set_qk_norm(rk_engine* e, int on);
+/* FP8 step weights (opt-in, LOSSY: one e4m3 rounding per weight of the matrices the decoding step streams; vLLM's
+ * quantization="fp8" is the same option).  on != 0: rk_engine_finalize - behind the norm folding - quantises every layer's fused
+ * q|k|v, o, gate|up and down matrix, keeps the bytes and exponents (weights grow to 1.5x) and OVERWRITES the fp16 matrix with the
+ * dequantised values: prefill, rk_llama_greedy1, rk_llama_last_logits, the session admit and the step all run one model, which is
+ * bit for bit an fp16 engine loaded with the dequantised matrices.  The step (rk_llama_generate, rk_llama_session_*) then reads the
+ * bytes - half the weight stream - unless option llama_step_fp8 is 0 (the fp16 kernel on the dequantised matrices: same bits).
+ * Embeddings, the head, norm weights, Qwen2 biases and Qwen3 q / k norm weights stay as they are.
+ * The engine-private format of a matrix W [N][K] (K % 16):
+ *   groups  128 consecutive k of one output row; the last group may be shorter
+ *   e       per (row, group) one int8 exponent: the smallest integer with absmax <= 448 * 2^e, clamped to [-15, 7] (all-zero: -15)
+ *   q       per weight one OCP e4m3fn byte: w * 2^-e rounded to nearest even, saturating at +-448
+ *   d       the dequantised weight q * 2^e - an fp16 number by construction (2^-9 * 2^-15 is the smallest fp16 subnormal, 448 * 2^7 < 65 504)
+ * Call between rk_llama_create and rk_engine_finalize; RK_ERR_STATE on a T5 engine or after finalize.  Never calling it (or
+ * on = 0) leaves the fp16 engine, byte for byte. */
+int rk_llama_set_weight_fp8(rk_engine* e, int on);
 /* Mistral family (hf: models/mistral/modeling_mistral.py, sliding_window_causal_mask; Zephyr / RankZephyr checkpoints): attention
  * with a sliding window of `window` positions.  In the prefill query position i of a sequence sees keys max(0, i - window + 1) .. i;
  * in the cached step (rk_llama_generate, rk_llama_session_*) the row at pos sees max(0, pos - window + 1) .. pos.  The K / V cache
@@ -377,6 +392,15 @@ typedef struct rk_debug_gemm_call {
   float out_eps, out_xs;
 } rk_debug_gemm_call;
 int rk_debug_gemm_ex(rk_engine* e, rk_debug_gemm_call* call);
+/* debug: the engine's FP8 quantiser (rk_llama_set_weight_fp8: the format) on host data W [N][K] fp16, row stride ldw (K % 16,
+ * ldw % 8, ldw >= K).  Any engine.  q_out: the bytes row-major [N][K] (the device order is the engine's own); exp_out: the
+ * exponents [N][ceil(K / 128)]; deq_out: the dequantised fp16 matrix [N][K].  Each may be null. */
+int rk_debug_quant_fp8(rk_engine* e, const uint16_t* W, int N, int K, int ldw, uint8_t* q_out, int8_t* exp_out, uint16_t* deq_out);
+/* debug: rk_debug_gemm_ex with family = 1 (required) on FP8 step weights: W is quantised by the engine's quantiser and the FP8
+ * weight-streaming kernel forms the product from the bytes.  Same struct, checks, guard bands and sentinel rules; epilogues 0, 1
+ * and 5, one batch (anything else: RK_ERR_STATE, nothing launched).  Its outputs equal, byte for byte, rk_debug_gemm_ex's on
+ * rk_debug_quant_fp8's deq_out. */
+int rk_debug_gemm_fp8(rk_engine* e, rk_debug_gemm_call* call);
 /* debug: n_launch (1 .. 64) launches of ONE described call of the engine's GEMM, back to back on slot 0's encoder stream, with NEW
  * data per launch and optionally beside a background load - what rk_debug_gemm_ex (one launch between host copies on an idle
  * chip) cannot show of the ping-pong kernel's timing-dependent parts: the K-split hand-off (every split launch uses the

@@ -26,6 +26,7 @@
 #include "attention_d128.h"
 #include "decoder_kernels.h"
 #include "gemm.h"
+#include "gemm_fp8.h"
 #include "gemv_rows.h"
 #include "llama_kernels.h"
 #include "llama_kernels_hd64.h"
@@ -64,7 +65,9 @@ struct DecLayerW {
 };
 
 // Llama-family decoder layer (hf: modeling_llama.py:291-330): fused q|k|v and interleaved gate|up carry the RMSNorm weights
-struct LlamaLayerW { half_t *qkv_f = nullptr, *o = nullptr, *gu_f = nullptr, *down = nullptr; float* qkv_bias = nullptr; float* qk_norm = nullptr; };   // qkv_bias: Qwen2 only (rk_llama_set_qkv_bias), fp32 [Q + 2 KV], NOT scaled by the norm weight; qk_norm: Qwen3 only (rk_llama_set_qk_norm), fp32 q | k head-norm weights [2 * 128]
+// qkv8 .. down8: the four matrices a second time as FP8 step weights (rk_llama_set_weight_fp8; the fp16 matrices then hold the dequantised values)
+struct LlamaLayerW { half_t *qkv_f = nullptr, *o = nullptr, *gu_f = nullptr, *down = nullptr; float* qkv_bias = nullptr; float* qk_norm = nullptr;
+                     GemmW8 qkv8{nullptr, nullptr, 0, 0}, o8{nullptr, nullptr, 0, 0}, gu8{nullptr, nullptr, 0, 0}, down8{nullptr, nullptr, 0, 0}; };   // qkv_bias: Qwen2 only (rk_llama_set_qkv_bias), fp32 [Q + 2 KV], NOT scaled by the norm weight; qk_norm: Qwen3 only (rk_llama_set_qk_norm), fp32 q | k head-norm weights [2 * 128]
 
 struct ProfRec { hipEvent_t a, b; int cls; };
 
@@ -215,7 +218,7 @@ struct rk_engine {
         gemm_persistent = 1, fold_norm = 1, s64_stages = 0, dec_fold_norm = 1, greedy_spec = 160, consumer_stats = 1, xattn_mfma = 1,
         dec_ffn_tiled = 1, gemm_split = 1, dec_fuse = 1, dec_fuse_rows = 0, dec_attn_seq = 1, attn_long = 1, attn_long_nw = 0,
         llama_attn_dma = 1, attn_long_xcd = 1, llama_attn_nw = 0, dec_graph = 1, gemm_sk = 1, dec_cross_mfma = 1, dec_gemv = 1, dec_gemv_rows = 4,
-        dec_cached_attn = 1, llama_dec_r = 0, enc_serial = 0;
+        dec_cached_attn = 1, llama_dec_r = 0, enc_serial = 0, llama_step_fp8 = 1;
   } opt;
   float* attn_trace = nullptr;   // measurement builds only (option attn_trace)
   int n_cu = 256;
@@ -233,6 +236,7 @@ struct rk_engine {
   float rope_factor = 0.f, rope_low = 1.f, rope_high = 4.f; int rope_orig = 0;   // rope type llama3 when rope_factor > 0
   bool qkv_bias = false;                                                          // Qwen2 family: q / k / v projections carry a bias
   bool qk_norm = false;                                                           // Qwen3 family: RMSNorm over head_dim on every q and k head (rk_llama_set_qk_norm)
+  bool weight_fp8 = false;                                                        // rk_llama_set_weight_fp8: the step's four projections also kept as FP8 step weights
   int window = 0;                                                                 // Mistral family: sliding window W (rk_llama_set_sliding_window), 0 = none
   std::vector<LlamaLayerW> ll; float *l_final_ln = nullptr, *rope_cos = nullptr, *rope_sin = nullptr; int* d_pos = nullptr;
   // rk_llama_set_sampling: temperature 0 = off (every entry point is greedy); d_seeds: one Philox key per row / session slot
@@ -430,6 +434,7 @@ enum GemmFamily { GEMM_NONE = -1, GEMM_TILED, GEMM_STREAM, GEMM_GEMV };
 constexpr bool gemv_has(int E) { return E == EPI_STORE_F16 || E == EPI_RESID_F32 || E == EPI_GEGLU_F16 || E == EPI_RELU_F16 || E == EPI_STORE_F32; }
 constexpr bool stream_has(int E) { return E != EPI_LSE_F32; }
 constexpr bool tiled_has(int E) { return E != EPI_ARGMAX_F32; }
+constexpr bool fp8_has(int E) { return E == EPI_STORE_F16 || E == EPI_RESID_F32 || E == EPI_SWIGLU_F16; }   // gemm_skinny_fp8_kernel: what the step needs
 // the rows and K the GEMV kernel takes: all rows staged in LDS, K in 16-byte pieces, at most GEMV_MAX_PIECES per lane
 inline bool gemv_fits(int M, int K) { return M <= GEMV_MAX_ROWS && K % 8 == 0 && K <= 512 * GEMV_MAX_PIECES; }
 
@@ -442,6 +447,7 @@ struct Gemm {
   GemmFold fold;
   const int* lse_labels = nullptr; float* lse_xlab = nullptr;   // EPI_LSE_F32: the label of every row, where its logit goes
   int* amax_idx = nullptr;                        // EPI_ARGMAX_F32: the first column of every block maximum, laid out like C
+  GemmW8 fp8{nullptr, nullptr, 0, 0};             // W a second time as FP8 step weights (gemm_fp8.h): the stream family reads these
   Gemm(int cls_, int epi_, const half_t* A_, int lda_, const half_t* W_, int ldw_, void* C_, int ldc_, int M_, int N_, int K_)
       : cls(cls_), epi(epi_), A(A_), lda(lda_), W(W_), ldw(ldw_), C(C_), ldc(ldc_), M(M_), N(N_), K(K_) {}
   Gemm& heads(int b, long sA, long sW, long sC) { batch = b; bsA = sA; bsW = sW; bsC = sC; return *this; }
@@ -450,6 +456,7 @@ struct Gemm {
   Gemm& with(const GemmFold& f) { fold = f; return *this; }
   Gemm& lse(const int* labels, float* xlab) { lse_labels = labels; lse_xlab = xlab; return *this; }
   Gemm& argmax(int* idx) { amax_idx = idx; return *this; }
+  Gemm& w8(const GemmW8& w) { fp8 = w; return *this; }
 };
 
 // Launch plan of one GEMM call: everything gemm() launches, decided here and nowhere else.
@@ -461,6 +468,7 @@ struct GemmPlan {
   // (1 = 128x128, 2..4 = 256-row v2 tiles, 5 = ping-pong, 6 = 64x64 with `stages` LDS stages; K split `ksplit` on variant 5)
   int m_pp2 = 0, ks_pp2 = 1, variant = 0, ksplit = 1, stages = 0;
   int wgs = 0;       // ping-pong grid: persistent workgroups (<= 0: one per tile)
+  bool w8 = false;   // STREAM: gemm_skinny_fp8_kernel on the call's FP8 bytes (Gemm::w8), same bits as the fp16 kernel on W
   int ko = 0;        // measurement builds: ping-pong knock-out mask (gemm_variant 80 + mask)
   const rk_engine::SkWs* ks_ws = nullptr;   // the stream's K-split workspace
   // rows on the persistent ping-pong kernel?  A folded-norm consumer there takes its row factors ready-made (rowscale_kernel in
@@ -481,6 +489,8 @@ struct GemmPlan {
 //             choose_variant) and no n_split.  One launch: batch > 1 always goes to the weight-streaming kernel.
 //   STREAM    K % 16 (k16 steps), 4-column pieces (N % 4, ldc % 4) except argmax blocks; no n_split (plan_gemm sends such a call to
 //             the tiles); batches share neither fold buffers nor the argmax index buffer (not offset per batch)
+//             FP8 bytes (Gemm::w8): store / residual / SwiGLU epilogues, one batch, rows of the device order (ldq >= K rounded up
+//             to 256, 16-byte aligned), exponent rows of whole dwords
 //   GEMV      M <= 16, K % 8, K <= 3072 (gemv_fits), scalar stores: any N, any ldc
 //   gated     N % 64 everywhere: gate / up rows interleaved in groups of 32, a 64-row weight tile = 32 output columns
 const char* gemm_contract(const Gemm& c, GemmFamily fam) {
@@ -512,6 +522,13 @@ const char* gemm_contract(const Gemm& c, GemmFamily fam) {
   if (fam == GEMM_STREAM) {
     if (c.K % 16) return "weight-streaming kernel: K % 16";
     if (c.batch > 1 && epi == EPI_ARGMAX_F32) return "argmax blocks: one batch";
+    if (c.fp8.q) {
+      if (!fp8_has(epi) || c.batch > 1) return "FP8 step weights: store, residual and SwiGLU epilogues, one batch";
+      if (!c.fp8.exps || c.fp8.ldq < fp8_ldq(c.K) || c.fp8.ldq % 16 || c.fp8.lde < fp8_lde(c.K) || c.fp8.lde % 4 ||
+          (uintptr_t)c.fp8.q % 16 || (uintptr_t)c.fp8.exps % 4)
+        return "FP8 step weights: byte rows of K rounded up to 256 (16-byte aligned), exponent rows of whole dwords";
+      if ((double)c.N * c.fp8.ldq >= 4294967296.0) return "FP8 step weights: the kernel addresses the bytes with 32-bit offsets (N * ldq < 4 GiB)";
+    }
     return nullptr;
   }
   if (c.batch > 1) return "tiled kernels: one batch (a batch with n_split has no kernel)";
@@ -541,7 +558,7 @@ GemmPlan plan_gemm(const rk_engine* e, const Gemm& c, hipStream_t st) {
     return p;
   }
   if ((c.family == GEMM_STREAM || c.batch > 1) && c.n_split == 0 && (((e->opt.skinny >> epi) & 1) || c.batch > 1 || epi == EPI_ARGMAX_F32)) {
-    if (stream_has(epi) && (p.why = gemm_contract(c, GEMM_STREAM)) == nullptr) { p.family = GEMM_STREAM; p.nb = (N + 31) / 32; }   // producer blocks of 32 columns
+    if (stream_has(epi) && (p.why = gemm_contract(c, GEMM_STREAM)) == nullptr) { p.family = GEMM_STREAM; p.nb = (N + 31) / 32; p.w8 = c.fp8.q != nullptr; }   // producer blocks of 32 columns
     return p;
   }
   if (!tiled_has(epi)) return p;
@@ -664,13 +681,16 @@ void launch_gemv(const rk_engine* e, hipStream_t st, const GemmArgs& a) {
 }
 
 template <int EPI>
-void launch_stream(hipStream_t st, const GemmArgs& a, int batch) {
+void launch_stream(hipStream_t st, const GemmArgs& a, int batch, const GemmW8* w8 = nullptr) {
   // (a form where one workgroup takes up to 8 row slabs - 8x fewer, fatter workgroups - was bit-identical but made
   // the step 6 % slower: what the decoder costs the concurrent encoder GEMMs is the serial LENGTH of its chain, every
   // kernel delaying some tile of the GEMM in flight, not its CU-time; so: many short workgroups)
   // (tried and dropped, round 3: a 1-D launch that runs all row slabs of a column block on ONE XCD, so that a weight row is
   // fetched into one L2 only - dec_gemm 0.337 vs 0.328 ms per step at 320 rows: the slabs are not bound by weight traffic)
   constexpr int NT = EPI_IS_GATED(EPI) ? 2 : 1;                    // gated: the gate and up blocks of 32 columns together
+  if constexpr (fp8_has(EPI)) {
+    if (w8) { hipLaunchKernelGGL((gemm_skinny_fp8_kernel<EPI, NT>), dim3((a.N + 32 * NT - 1) / (32 * NT), 1, (a.M + 31) / 32), dim3(SKINNY_THREADS), 0, st, a, *w8); return; }
+  }
   hipLaunchKernelGGL((gemm_skinny_kernel<EPI, NT>), dim3((a.N + 32 * NT - 1) / (32 * NT), batch, (a.M + 31) / 32), dim3(SKINNY_THREADS), 0, st, a);
 }
 
@@ -703,7 +723,7 @@ int gemm(rk_engine* e, hipStream_t st, const Gemm& c, int* nb = nullptr) {
   a.amax_idx = c.amax_idx; a.lse_labels = c.lse_labels; a.lse_xlab = c.lse_xlab;
   const double flops = 2.0 * c.M * (double)c.N * c.K * c.batch;
   const double out_elems = EPI_IS_GATED(c.epi) ? (double)c.M * c.N / 2 : (double)c.M * c.N;
-  const double bytes = 2.0 * ((double)c.M * c.K + (double)c.N * c.K) +
+  const double bytes = 2.0 * (double)c.M * c.K + (p.w8 ? 1.0 : 2.0) * (double)c.N * c.K +
                        out_elems * (c.epi == EPI_RESID_F32 ? 8.0 : (c.epi == EPI_STORE_F32 ? 4.0 : 2.0));
   Bracket br(e, st, c.cls, flops, bytes);
   with_epi(c.epi, [&](auto E) {
@@ -717,7 +737,7 @@ int gemm(rk_engine* e, hipStream_t st, const Gemm& c, int* nb = nullptr) {
         return;
       }
     }
-    if constexpr (stream_has(EPI)) { if (p.family == GEMM_STREAM) { launch_stream<EPI>(st, a, c.batch); return; } }
+    if constexpr (stream_has(EPI)) { if (p.family == GEMM_STREAM) { launch_stream<EPI>(st, a, c.batch, p.w8 ? &c.fp8 : nullptr); return; } }
     if constexpr (tiled_has(EPI)) { if (p.family == GEMM_TILED) launch_tiled<EPI>(e, st, a, p); }
   });
   return RK_OK;
@@ -2701,6 +2721,23 @@ int rk_llama_create(const rk_llama_desc* desc, int device_ordinal, rk_engine** o
   return RK_OK;
 }
 
+// The engine's FP8 quantiser (gemm_fp8.h) on a device matrix W [N][K] (row stride ldw): allocates the bytes in device order and the
+// exponents (engine-owned) and describes them in *out; q_rm (optional): the bytes row-major [N][K]; deq (optional, may be W): the
+// dequantised fp16 matrix, row stride ldw.
+static int quant_fp8(rk_engine* e, hipStream_t st, const half_t* W, int N, int K, int ldw, GemmW8* out, uint8_t* q_rm, half_t* deq) {
+  if (N <= 0 || K <= 0 || K % 16 || ldw < K || ldw % 8 || (double)N * fp8_ldq(K) >= 4294967296.0)
+    return fail(e, RK_ERR_INVALID, "FP8 quantiser: K %% 16, ldw >= K, ldw %% 8, N * K below 4 Gi (got N=%d K=%d ldw=%d)", N, K, ldw);
+  uint8_t* q = nullptr; int8_t* ex = nullptr;
+  const int ldq = fp8_ldq(K), lde = fp8_lde(K);
+  int rc = RK_OK;
+  RC(dalloc(e, &q, (size_t)N * ldq)); RC(dalloc(e, &ex, (size_t)N * lde));
+  HIPCHK(e, hipMemsetAsync(q, 0, (size_t)N * ldq, st)); HIPCHK(e, hipMemsetAsync(ex, 0, (size_t)N * lde, st));
+  hipLaunchKernelGGL(quant_fp8_rows_kernel, dim3((unsigned)((fp8_groups(K) + 3) / 4) * (unsigned)N), dim3(256), 0, st, QuantFp8Args{W, ldw, N, K, q, ldq, ex, lde, q_rm, deq, ldw});
+  HIPCHK(e, hipGetLastError());
+  *out = GemmW8{q, ex, ldq, lde};
+  return RK_OK;
+}
+
 static int llama_finalize(rk_engine* e) {
   const rk_llama_desc& l = e->ld;
   const int hd = l.head_dim, dm = l.hidden, Q = l.n_heads * hd, KV = l.n_kv_heads * hd, F = l.intermediate, V = l.vocab;
@@ -2776,6 +2813,13 @@ static int llama_finalize(rk_engine* e) {
       RC(upload(e, &w.gu_f, buf.data(), buf.size()));
     }
     RC(upload(e, &w.down, H(p + ".mlp.down_proj.weight").data(), (size_t)dm * F));
+    if (e->weight_fp8) {
+      // FP8 step weights: bytes and exponents kept, the fp16 matrix overwritten with the dequantised values - prefill, the heads,
+      // the session admit and the step (either kernel) then run ONE model
+      hipStream_t st = e->slots[0].se;
+      RC(quant_fp8(e, st, w.qkv_f, Q + 2 * KV, dm, dm, &w.qkv8, nullptr, w.qkv_f)); RC(quant_fp8(e, st, w.o, dm, Q, Q, &w.o8, nullptr, w.o));
+      RC(quant_fp8(e, st, w.gu_f, 2 * F, dm, dm, &w.gu8, nullptr, w.gu_f)); RC(quant_fp8(e, st, w.down, dm, F, F, &w.down8, nullptr, w.down));
+    }
   }
   e->host.clear();
   {   // rotary tables [max_tokens][hd / 2], float32 like hf: modeling_llama.py:94-127: freq_i = theta^(-2i/hd), then the llama3 rope type's
@@ -2914,6 +2958,14 @@ int rk_llama_set_qk_norm(rk_engine* e, int on) {
   return RK_OK;
 }
 
+int rk_llama_set_weight_fp8(rk_engine* e, int on) {
+  if (!e) return RK_ERR_INVALID;
+  if (e->family != 1) return fail(e, RK_ERR_STATE, "FP8 step weights apply to Llama-family engines (rk_llama_create)");
+  if (e->finalized) return fail(e, RK_ERR_STATE, "rk_llama_set_weight_fp8 must precede rk_engine_finalize (the matrices are quantised there)");
+  e->weight_fp8 = on != 0;
+  return RK_OK;
+}
+
 int rk_llama_greedy1(rk_engine* e, const int32_t* tokens, const int32_t* seq_offsets, int n_seq, int32_t* out_tokens) {
   if (!e || !out_tokens) return RK_ERR_INVALID;
   if (e->ls.open) return fail(e, RK_ERR_STATE, "rk_llama_greedy1 while a decoding session is open (it shares the prefill's buffers): rk_llama_session_close first");
@@ -2962,16 +3014,19 @@ static int llama_step_rows(rk_engine* e, hipStream_t st, int rows, int P, const 
   // the GEMM behind a norm forms its row factors from the producer's block sums in its own epilogue, or - more block sums than
   // that path stages by DMA (64: hidden > 2 048) - takes them from rowscale_kernel in front of it.  A function of the model only.
   auto normed = [&](Gemm c) { return ns.consumer(e, st, nullptr, c.on(GEMM_STREAM), ns.nb <= 64); };
+  // FP8 engines: the four projections read the FP8 bytes - by the engine's mode, never by the row count (same bits either way)
+  const bool f8 = e->weight_fp8 && e->opt.llama_step_fp8;
+  auto b8 = [&](const GemmW8& w8) { return f8 ? w8 : GemmW8{nullptr, nullptr, 0, 0}; };
   ns.begin(e, st, d_next, rows, true);
   for (int i = 0; i < l.n_layers; ++i) {
     const LlamaLayerW& w = e->ll[i];
-    RC(gemm(e, st, normed(Gemm(PC_DEC_GEMM, EPI_STORE_F16, ns.x(), dm, w.qkv_f, dm, lg.qkv, ldq, rows, ldq, dm))));
+    RC(gemm(e, st, normed(Gemm(PC_DEC_GEMM, EPI_STORE_F16, ns.x(), dm, w.qkv_f, dm, lg.qkv, ldq, rows, ldq, dm).w8(b8(w.qkv8)))));
     half_t* kc = e->lkv.p + (size_t)i * 2 * half_layer;
     launch_llama_dec_attn(e, st, ap, LlamaDecAttnArgs{lg.qkv, kc, kc + half_layer, d_pos, e->rope_cos, e->rope_sin, e->lpart.p, lg.ctx,
                                                           ldq, l.n_heads, l.n_kv_heads, P, ap.nch, scale_log2e, w.qkv_bias, 0, w.qk_norm, l.eps}, rows);
-    RC(ns.producer(e, st, Gemm(PC_DEC_GEMM, EPI_RESID_F32, lg.ctx, Q, w.o, Q, ns.hidden, dm, rows, dm, Q).on(GEMM_STREAM)));
-    RC(gemm(e, st, normed(Gemm(PC_DEC_GEMM, EPI_SWIGLU_F16, ns.x(), dm, w.gu_f, dm, lg.ffh, F, rows, 2 * F, dm))));
-    RC(ns.producer(e, st, Gemm(PC_DEC_GEMM, EPI_RESID_F32, lg.ffh, F, w.down, F, ns.hidden, dm, rows, dm, F).on(GEMM_STREAM), i + 1 < l.n_layers));
+    RC(ns.producer(e, st, Gemm(PC_DEC_GEMM, EPI_RESID_F32, lg.ctx, Q, w.o, Q, ns.hidden, dm, rows, dm, Q).on(GEMM_STREAM).w8(b8(w.o8))));
+    RC(gemm(e, st, normed(Gemm(PC_DEC_GEMM, EPI_SWIGLU_F16, ns.x(), dm, w.gu_f, dm, lg.ffh, F, rows, 2 * F, dm).w8(b8(w.gu8)))));
+    RC(ns.producer(e, st, Gemm(PC_DEC_GEMM, EPI_RESID_F32, lg.ffh, F, w.down, F, ns.hidden, dm, rows, dm, F).on(GEMM_STREAM).w8(b8(w.down8)), i + 1 < l.n_layers));
   }
   rmsnorm(e, st, ns.hidden, e->l_final_ln, e->slots[0].dlast, nullptr, rows);
   return RK_OK;
@@ -3523,6 +3578,7 @@ const OptionDesc kOptions[] = {
   {"dec_cached_attn", &rk_engine::Options::dec_cached_attn, 0, 1, nullptr, "rk_t5_generate's self-attention: attn_dec_cached_kernel (1) or the cache append + attn_dec_kernel's tree form (0); same bits"},
   {"llama_dec_r", &rk_engine::Options::llama_dec_r, 0, 2, nullptr, "rk_llama_generate's attention: query heads per workgroup by plan_llama_dec_attn's rule (0), one (1), or, where a kv head has 7, all seven (2: measurement and tests; every cached K / V byte read once per step); same bits"},
   {"enc_serial", &rk_engine::Options::enc_serial, 0, 1, nullptr, "two slots: an encoder chain starts behind the other slot's (1: one encoder at a time beside the decoder before it) or as soon as it is enqueued (0: two chains interleave); same bits"},
+  {"llama_step_fp8", &rk_engine::Options::llama_step_fp8, 0, 1, nullptr, "FP8 engines: the step's projections read the FP8 bytes (1, default) or the dequantised fp16 matrices through the fp16 kernel (0); same bits; no effect on an engine without FP8 weights"},
   {"gemm_split", &rk_engine::Options::gemm_split, 0, 1, nullptr, "rows beyond the ping-pong kernel's last whole round on a fill-in tile variant (1) or one launch (0); same bits"},
 #ifdef RK_MEASURE
   {"attn_ko", &rk_engine::Options::attn_ko, 0, 1 << 20, nullptr, "timing-only knock-outs of the attention kernels (measurement builds)"},
@@ -3572,11 +3628,12 @@ int rk_engine_set_option(rk_engine* e, const char* key, int value) {
 }
 
 // debug: one Gemm call on host data, every output between sentinel bands (include/rk_engine.h).  No launch code of its own: it
-// builds the Gemm and calls gemm().
-int rk_debug_gemm_ex(rk_engine* e, rk_debug_gemm_call* q) {
+// builds the Gemm and calls gemm().  fp8 (rk_debug_gemm_fp8): W also goes through the engine's quantiser and the call carries the bytes.
+static int debug_gemm(rk_engine* e, rk_debug_gemm_call* q, bool fp8) {
   if (!e || !q) return RK_ERR_INVALID;
   int rc = set_device(e);
   if (rc) return rc;
+  if (fp8 && q->family != 1) return fail(e, RK_ERR_INVALID, "debug gemm fp8: family must be 1 (the weight-streaming kernels read FP8 step weights)");
   const int epi = q->epi, M = q->M, N = q->N, K = q->K, batch = q->batch > 0 ? q->batch : 1;
   if (epi < 0 || epi > EPI_LSE_F32 || q->family < 0 || q->family > 2 || M <= 0 || N <= 0 || K <= 0 || q->lda <= 0 || q->ldw <= 0 || q->ldc <= 0 ||
       q->n_split < 0 || q->split_stride < 0 || q->bsA < 0 || q->bsW < 0 || q->bsC < 0 || q->c_off < 0 || (long)M * batch > (1 << 22))
@@ -3595,12 +3652,14 @@ int rk_debug_gemm_ex(rk_engine* e, rk_debug_gemm_call* q) {
   if (q->ssq_in && q->nb_in <= 0) return fail(e, RK_ERR_INVALID, "debug gemm: ssq_in without nb_in");
   if (producer) { c.fold.xraw = dummy; c.fold.ssq = (float*)dummy; }
   c.lse((const int*)dummy, (float*)dummy).argmax((int*)dummy);
+  if (fp8) c.w8(GemmW8{(const uint8_t*)dummy, (const int8_t*)dummy, fp8_ldq(K), fp8_lde(K)});
   hipStream_t st = e->slots[0].se;
   const GemmPlan p = plan_gemm(e, c, st);
   q->out_family = (int)p.family; q->out_variant = p.variant; q->out_m_pp2 = p.m_pp2; q->out_ksplit = p.m_pp2 > 0 ? p.ks_pp2 : p.ksplit;
   q->out_nb = p.nb; q->out_n_cu = e->n_cu; q->out_eps = e->d.eps; q->out_xs = RK_XRAW_SCALE;
   if (p.family == GEMM_NONE)
     return fail(e, RK_ERR_STATE, "no kernel of family %d takes the GEMM M=%d N=%d K=%d (epilogue %d, batch %d): %s", (int)fam, M, N, K, epi, batch, p.why ? p.why : "");
+  if (fp8 && !p.w8) return fail(e, RK_ERR_STATE, "debug gemm fp8: the plan does not put the call on the weight-streaming family (option gemm_skinny)");
   if (planning) return RK_OK;
   // extents, from the addressing of the call, against what the caller gave
   if (!q->A || !q->W || !q->C || !q->C_out || q->band_rows < 256) return fail(e, RK_ERR_INVALID, "debug gemm: A, W, C, C_out and band_rows >= 256");
@@ -3657,17 +3716,51 @@ int rk_debug_gemm_ex(rk_engine* e, rk_debug_gemm_call* q) {
   } else if (q->ssq_in) { c.fold.ssq_in = dQ; c.fold.nb_in = q->nb_in; }
   if (producer) { c.fold.xraw = dX + xband; c.fold.ssq = dS + sband; }
   c.lse(dL, dXl).argmax(dI ? dI + band + q->c_off : nullptr);
+  const size_t n_own = e->allocs.size();             // the quantiser's buffers are engine-owned: given back below
+  auto free8 = [&]() { while (fp8 && e->allocs.size() > n_own) { hipFree(e->allocs.back()); e->allocs.pop_back(); } };   // (fp8 only: nothing else here allocates engine memory)
+  auto done8 = [&](int r) { free8(); return done(r); };
+  if (fp8) {
+    GemmW8 w8{nullptr, nullptr, 0, 0};
+    if ((rc = quant_fp8(e, st, dW, N, K, q->ldw, &w8, nullptr, nullptr))) return done8(rc);
+    c.w8(w8);
+  }
   int nb = 0;
   rc = gemm(e, st, c, &nb);
-  if (rc) return done(rc);
-  DBG_HIP(hipStreamSynchronize(st));
-  DBG_HIP(hipGetLastError());
+  if (rc) return done8(rc);
+  if (hipStreamSynchronize(st) != hipSuccess) return done8(fail(e, RK_ERR_HIP, "debug gemm: %s", "hipStreamSynchronize(st)"));
+  if (hipGetLastError() != hipSuccess) return done8(fail(e, RK_ERR_HIP, "debug gemm: %s", "hipGetLastError()"));
+  free8();
   q->out_nb = nb;
   DBG_HIP(hipMemcpy(q->C_out, dC, c_all * celt, hipMemcpyDeviceToHost));
   if (dI) DBG_HIP(hipMemcpy(q->idx_out, dI, c_all * 4, hipMemcpyDeviceToHost));
   if (producer) { DBG_HIP(hipMemcpy(q->xraw_out, dX, x_all * 2, hipMemcpyDeviceToHost)); DBG_HIP(hipMemcpy(q->ssq_out, dS, s_all * 4, hipMemcpyDeviceToHost)); }
   if (dXl) DBG_HIP(hipMemcpy(q->xlab, dXl, (size_t)M * 4, hipMemcpyDeviceToHost));
 #undef DBG_HIP
+  return done(RK_OK);
+}
+int rk_debug_gemm_ex(rk_engine* e, rk_debug_gemm_call* q) { return debug_gemm(e, q, false); }
+int rk_debug_gemm_fp8(rk_engine* e, rk_debug_gemm_call* q) { return debug_gemm(e, q, true); }
+
+// debug: the engine's FP8 quantiser on host data (include/rk_engine.h): quant_fp8, the read-backs, nothing of its own
+int rk_debug_quant_fp8(rk_engine* e, const uint16_t* W, int N, int K, int ldw, uint8_t* q_out, int8_t* exp_out, uint16_t* deq_out) {
+  if (!e || !W) return RK_ERR_INVALID;
+  int rc = set_device(e);
+  if (rc) return rc;
+  if (N <= 0 || K <= 0 || K % 16 || ldw < K || ldw % 8 || (long)N * ldw > (1L << 30)) return fail(e, RK_ERR_INVALID, "debug quant fp8: K %% 16, ldw >= K, ldw %% 8");
+  hipStream_t st = e->slots[0].se;
+  const size_t n_own = e->allocs.size();
+  auto done = [&](int r) { while (e->allocs.size() > n_own) { hipFree(e->allocs.back()); e->allocs.pop_back(); } return r; };
+  half_t* dW = nullptr; uint8_t* dQ = nullptr;
+  if ((rc = dalloc(e, &dW, (size_t)N * ldw)) || (rc = dalloc(e, &dQ, (size_t)N * K))) return done(rc);
+  if (hipMemcpy(dW, W, (size_t)N * ldw * 2, hipMemcpyHostToDevice) != hipSuccess) return done(fail(e, RK_ERR_HIP, "debug quant fp8: copy in"));
+  GemmW8 w8{nullptr, nullptr, 0, 0};
+  if ((rc = quant_fp8(e, st, dW, N, K, ldw, &w8, dQ, dW))) return done(rc);
+  if (hipStreamSynchronize(st) != hipSuccess || hipGetLastError() != hipSuccess) return done(fail(e, RK_ERR_HIP, "debug quant fp8: the launch failed"));
+  const int groups = fp8_groups(K);
+  if ((q_out && hipMemcpy(q_out, dQ, (size_t)N * K, hipMemcpyDeviceToHost) != hipSuccess) ||
+      (exp_out && hipMemcpy2D(exp_out, groups, w8.exps, w8.lde, groups, N, hipMemcpyDeviceToHost) != hipSuccess) ||
+      (deq_out && hipMemcpy2D(deq_out, (size_t)K * 2, dW, (size_t)ldw * 2, (size_t)K * 2, N, hipMemcpyDeviceToHost) != hipSuccess))
+    return done(fail(e, RK_ERR_HIP, "debug quant fp8: copy out"));
   return done(RK_OK);
 }
 

@@ -159,6 +159,7 @@ ABI = {
     "rk_llama_set_qkv_bias": (C.c_int, [C.c_void_p, C.c_int]),
     "rk_llama_set_qk_norm": (C.c_int, [C.c_void_p, C.c_int]),
     "rk_llama_set_sliding_window": (C.c_int, [C.c_void_p, C.c_int]),
+    "rk_llama_set_weight_fp8": (C.c_int, [C.c_void_p, C.c_int]),
     "rk_llama_greedy1": (C.c_int, [C.c_void_p, _i32p, _i32p, C.c_int, _i32p]),
     "rk_llama_last_logits": (C.c_int, [C.c_void_p, _i32p, _i32p, C.c_int, _i32p, C.c_int, _f32p]),
     "rk_llama_generate": (C.c_int, [C.c_void_p, _i32p, _i32p, C.c_int, C.c_int, C.c_int, _i32p, C.c_int, C.c_int, _i32p, _i32p]),
@@ -196,6 +197,8 @@ ABI = {
     "rk_rel_bucket": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "rk_debug_gemm": (C.c_int, [C.c_void_p, _P(C.c_uint16), _P(C.c_uint16), _f32p, C.c_int, C.c_int, C.c_int, C.c_int]),
     "rk_debug_gemm_ex": (C.c_int, [C.c_void_p, _P(RkDebugGemmCall)]),
+    "rk_debug_quant_fp8": (C.c_int, [C.c_void_p, _P(C.c_uint16), C.c_int, C.c_int, C.c_int, _P(C.c_uint8), _P(C.c_int8), _P(C.c_uint16)]),
+    "rk_debug_gemm_fp8": (C.c_int, [C.c_void_p, _P(RkDebugGemmCall)]),
     "rk_debug_gemm_chain": (C.c_int, [C.c_void_p, _P(RkDebugGemmChainCall)]),
     "rk_debug_attn": (C.c_int, [C.c_void_p, _P(RkDebugAttnCall)]),
     "rk_debug_xattn_chain": (C.c_int, [C.c_void_p, _P(RkDebugXattnChainCall)]),
@@ -539,8 +542,9 @@ class RkEngine:
 
     def debug_gemm_ex(self, epi: int, family: int, a16: np.ndarray, w16: np.ndarray, M: int, N: int, K: int, *, lda=None, ldw=None,
                       ldc=None, c_in: Optional[np.ndarray] = None, c_off=0, rowscale=None, ssq_in=None, factors_kernel=False,
-                      producer=False, n_split=0, split_stride=0, batch=1, bsA=0, bsW=0, bsC=0, labels=None, plan_only=False) -> dict:
-        """One call of the engine's GEMM through rk_debug_gemm_ex (include/rk_engine.h).  a16 / w16: flat or 2-D fp16 arrays holding
+                      producer=False, n_split=0, split_stride=0, batch=1, bsA=0, bsW=0, bsC=0, labels=None, plan_only=False,
+                      entry: str = "rk_debug_gemm_ex") -> dict:
+        """One call of the engine's GEMM through rk_debug_gemm_ex (include/rk_engine.h; entry: rk_debug_gemm_fp8's name for its form).  a16 / w16: flat or 2-D fp16 arrays holding
         everything the call addresses; c_in: the flat INTERIOR of the output in the output type (epi 7: two floats per element),
         default = all sentinel bytes.  Returns the plan fields and the WHOLE device allocations after the call, bands included:
         "C" (flat, band | interior | band; "band" = elements per band), "idx", "xraw" [(2 band_rows + M), N], "ssq"
@@ -589,7 +593,7 @@ class RkEngine:
             xlab = np.frombuffer(bytes([DEBUG_SENTINEL]) * (4 * M), dtype=np.float32).copy()
             q.labels, q.xlab = labels.ctypes.data, xlab.ctypes.data
         q.plan_only = int(plan_only)
-        self._chk(self.lib.rk_debug_gemm_ex(self.h, C.byref(q)))
+        self._chk(getattr(self.lib, entry)(self.h, C.byref(q)))
         del keep
         out = {k[4:]: getattr(q, k) for k, _ in RkDebugGemmCall._fields_ if k.startswith("out_")}
         if plan_only:
@@ -598,6 +602,25 @@ class RkEngine:
         if producer:
             out.update(xraw=xraw, ssq=ssq[:rows_all * q.out_nb].reshape(rows_all, q.out_nb))
         return out
+
+    def debug_gemm_fp8(self, epi: int, a16: np.ndarray, w16: np.ndarray, M: int, N: int, K: int, **kw) -> dict:
+        """debug_gemm_ex with family = 1 on FP8 step weights (rk_debug_gemm_fp8): w16 goes through the engine's quantiser and the FP8
+        weight-streaming kernel forms the product from the bytes.  Same keywords, same result layout."""
+        return self.debug_gemm_ex(epi, 1, a16, w16, M, N, K, entry="rk_debug_gemm_fp8", **kw)
+
+    def debug_quant_fp8(self, w16: np.ndarray, K: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """The engine's FP8 quantiser on a host matrix (rk_debug_quant_fp8; the format: include/rk_engine.h at rk_llama_set_weight_fp8).
+        w16: fp16 [N, ldw]; K (default ldw): the columns that count.  Returns (e4m3fn bytes [N, K] uint8 row-major, exponents
+        [N, ceil(K / 128)] int8, the dequantised fp16 matrix [N, K])."""
+        w16 = np.ascontiguousarray(w16, dtype=np.float16)
+        N, ld = w16.shape
+        K = ld if K is None else int(K)
+        q = np.zeros((N, K), dtype=np.uint8)
+        ex = np.zeros((N, -(-K // 128)), dtype=np.int8)
+        deq = np.zeros((N, K), dtype=np.float16)
+        self._chk(self.lib.rk_debug_quant_fp8(self.h, w16.ctypes.data_as(_P(C.c_uint16)), N, K, ld, q.ctypes.data_as(_P(C.c_uint8)),
+                                              ex.ctypes.data_as(_P(C.c_int8)), deq.ctypes.data_as(_P(C.c_uint16))))
+        return q, ex, deq
 
     def debug_gemm_chain(self, epi: int, a16: np.ndarray, w16: np.ndarray, M: int, N: int, K: int, *, family=0, ldc=None,
                          c_in: Optional[np.ndarray] = None, accumulate=False, rowscale=None, bg: Optional[dict] = None, bg_per_fg=0,
@@ -888,9 +911,10 @@ class RkLlamaEngine(RkEngine):
     """Decoder-only engine (rk_llama_*): prefill + last-position logits.  Shares weight loading, options, profiling and
     lifetime with RkEngine; the T5 entry points refuse it."""
 
-    def __init__(self, dims, device: int = 0, max_tokens: int = 16384, max_seqs: int = 16):
+    def __init__(self, dims, device: int = 0, max_tokens: int = 16384, max_seqs: int = 16, weight_fp8: bool = False):
         self.lib = load_library()
         self.dims = dims
+        self.weight_fp8 = bool(weight_fp8)
         self.desc = RkLlamaDesc(vocab=dims.vocab, hidden=dims.hidden, n_heads=dims.n_heads, n_kv_heads=dims.n_kv_heads,
                                 head_dim=dims.head_dim, intermediate=dims.intermediate, n_layers=dims.n_layers,
                                 tied_head=int(dims.tied_head), eps=dims.eps, rope_theta=dims.rope_theta,
@@ -902,6 +926,8 @@ class RkLlamaEngine(RkEngine):
         self.h = h
         self.device = device
         self.comm_rank, self.comm_world = 0, 1
+        if self.weight_fp8:                                           # FP8 step weights (opt-in, lossy): before the first tensor is loaded
+            self._chk(self.lib.rk_llama_set_weight_fp8(self.h, 1))
         if getattr(dims, "rope_scaling", None) is not None:          # rope type llama3: before finalize builds the rotary tables
             f, lo, hi, orig = dims.rope_scaling
             self._chk(self.lib.rk_llama_set_rope_scaling(self.h, float(f), float(lo), float(hi), int(orig)))

@@ -552,15 +552,38 @@ def hf_prompt_too_long_error():
     return ValueError
 
 
+WEIGHT_DTYPES = ("fp16", "fp8")
+
+
+def refuse_t5_weight_dtype(weight_dtype):
+    """The rankers' weight_dtype on a T5 checkpoint: "fp16" is what T5 runs; FP8 step weights exist for the Llama family only."""
+    if weight_dtype not in WEIGHT_DTYPES:
+        raise ValueError(f"weight_dtype must be one of {WEIGHT_DTYPES} (got {weight_dtype!r})")
+    if weight_dtype != "fp16":
+        raise NotImplementedError(f"weight_dtype={weight_dtype!r} is not supported for T5 checkpoints: FP8 step weights serve the Llama "
+                                  "family's decoding step (weight_dtype='fp16' is what the T5 engine runs)")
+
+
+def weight_dtype_kw(weight_dtype) -> dict:
+    """The keyword a ranker adds to its runtime call: none for the default (the calls of a default ranker stay what they were)."""
+    if weight_dtype not in WEIGHT_DTYPES:
+        raise ValueError(f"weight_dtype must be one of {WEIGHT_DTYPES} (got {weight_dtype!r})")
+    return {} if weight_dtype == "fp16" else {"weight_dtype": weight_dtype}
+
+
 class LlamaRuntime:
     """Decoder-only (Llama family) counterpart of T5Runtime: checkpoint directory -> rk_llama_* engine.  Replaces
     `AutoModelForCausalLM.from_pretrained(..., device_map='auto', torch_dtype=fp16)` of ref: llmrankers/setwise.py:65-69."""
 
     def __init__(self, model_name_or_path: str, device, max_tokens: int = 32768, max_seqs: int = 16, cache_dir=None,
-                 accept_model_types=("llama",), adapter_dir=None):
+                 accept_model_types=("llama",), adapter_dir=None, weight_dtype="fp16"):
         """accept_model_types: the config.model_type values the caller serves - the reference's setwise / pairwise / listwise
         rankers refuse Qwen (ref: setwise.py:71), its Rank-R1 ranker runs on it.  adapter_dir: a PEFT LoRA adapter merged into
-        the weights on the way in (merge_lora)."""
+        the weights on the way in (merge_lora).  weight_dtype: "fp16", or "fp8" - FP8 step weights (RkLlamaEngine(weight_fp8=True):
+        opt-in and lossy, one e4m3 rounding per weight of the projections the decoding step streams, behind the LoRA merge)."""
+        if weight_dtype not in WEIGHT_DTYPES:
+            raise ValueError(f"weight_dtype must be one of {WEIGHT_DTYPES} (got {weight_dtype!r})")
+        self.weight_dtype = weight_dtype
         model_name_or_path = resolve_checkpoint(model_name_or_path, cache_dir)
         cfg = read_config(model_name_or_path)
         self.model_type = cfg.get("model_type")
@@ -575,7 +598,7 @@ class LlamaRuntime:
                                       "hidden <= 4096 (Llama-2/3 up to 8B, Llama-3.2-1B, TinyLlama, SmolLM2, Qwen2.5-0.5B to 7B)")
         if self.dims.qk_norm and self.dims.head_dim != 128:            # (rk_engine_finalize refuses it too; no Qwen3 checkpoint has it)
             raise NotImplementedError(f"Qwen3 with head_dim {self.dims.head_dim}: the MI355X engine's q / k head norm is built for head_dim 128")
-        self.engine = RkLlamaEngine(self.dims, parse_device(device), max_tokens, max_seqs)
+        self.engine = RkLlamaEngine(self.dims, parse_device(device), max_tokens, max_seqs, **({"weight_fp8": True} if weight_dtype == "fp8" else {}))
         tensors = iter_checkpoint_tensors(model_name_or_path)
         self.engine.load_state(merge_lora(tensors, adapter_dir) if adapter_dir else tensors)
 
@@ -588,6 +611,7 @@ class LlamaRuntime:
         self.generation = read_generation_settings(None, self.config)
         self.max_tokens, self.max_seqs = int(engine.desc.max_tokens), int(engine.desc.max_seqs)
         self.engine = engine
+        self.weight_dtype = "fp8" if getattr(engine, "weight_fp8", False) else "fp16"
         return self
 
     _chunks = T5Runtime._chunks
@@ -784,13 +808,17 @@ def generation_plan(runtime, prompt_lens) -> dict:
     return {"max_new": max_new, "max_total": max_total, "eos_ids": list(g["eos_token_ids"]), "pad_id": int(g["pad_token_id"])}
 
 
-def load_runtime(model_name_or_path: str, device, cache_dir=None):
+def load_runtime(model_name_or_path: str, device, cache_dir=None, weight_dtype="fp16"):
     """T5Runtime or LlamaRuntime by the checkpoint's config.model_type (ref: setwise.py:40-71 dispatches the same way);
-    anything else raises NotImplementedError like the reference."""
+    anything else raises NotImplementedError like the reference.  weight_dtype: LlamaRuntime's; "fp8" on a T5 checkpoint raises
+    NotImplementedError."""
     path = resolve_checkpoint(model_name_or_path, cache_dir)
     mt = read_config(path).get("model_type")
     if mt == "t5":
+        refuse_t5_weight_dtype(weight_dtype)
         return T5Runtime(path, device, cache_dir=cache_dir)
     if mt == "llama":
+        if weight_dtype != "fp16":
+            return LlamaRuntime(path, device, cache_dir=cache_dir, weight_dtype=weight_dtype)
         return LlamaRuntime(path, device, cache_dir=cache_dir)
     raise NotImplementedError(f"Model type {mt} is not supported yet by the MI355X engine")

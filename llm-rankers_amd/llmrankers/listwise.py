@@ -83,15 +83,16 @@ class ListwiseLlmRanker(LlmRanker):
                   "M", "N", "O", "P", "Q", "R", "S", "T", "U", "V", "W"]
 
     def __init__(self, model_name_or_path, tokenizer_name_or_path, device, window_size, step_size,
-                 scoring='generation', num_repeat=1, cache_dir=None, sample_seed=None):
+                 scoring='generation', num_repeat=1, cache_dir=None, sample_seed=None, weight_dtype="fp16"):
         # ref: listwise.py:207-247: T5 or Llama by config.model_type, NotImplementedError otherwise
         # sample_seed (decoder-only checkpoints; not in the reference, whose sampling follows torch's global generator): None =
         # greedy decoding whatever the checkpoint's generation settings say; an integer = a checkpoint that says do_sample: true
         # is sampled on the device with its own temperature / top_k / top_p, reproducibly (see _setup)
-        from ._runtime import load_runtime, resolve_checkpoint
+        # weight_dtype (not in the reference): "fp8" = FP8 step weights on a Llama-family checkpoint (LlamaRuntime; lossy, opt-in)
+        from ._runtime import load_runtime, resolve_checkpoint, weight_dtype_kw
         path = resolve_checkpoint(model_name_or_path, cache_dir)
         try:
-            runtime = load_runtime(path, device, cache_dir=cache_dir)
+            runtime = load_runtime(path, device, cache_dir=cache_dir, **weight_dtype_kw(weight_dtype))
         except NotImplementedError as exc:   # same message shape as ref: listwise.py:247
             raise NotImplementedError(f"{exc} (listwise)") from None
         if runtime.model_type == "llama":
@@ -299,6 +300,9 @@ class ListwiseLlmRanker(LlmRanker):
         return self.tokenizer.convert_tokens_to_string(self.tokenizer.tokenize(text)[:length])
 
 
+_WEIGHT_DTYPE_CLASSES = {}      # (class, weight_dtype) -> the subclass with_weight_dtype hands out
+
+
 class R1ListwiseLlmRanker(ListwiseLlmRanker):
     """The listwise baseline of Rank-R1 (ref: Rank-R1/run_listwise.py:89-156; RankZephyr - a Zephyr / Mistral-7B checkpoint with a
     sliding window - or any chat model, served by vLLM there): one compare = the two-message chat prompt of the prompt settings
@@ -314,17 +318,32 @@ class R1ListwiseLlmRanker(ListwiseLlmRanker):
     CHARACTERS = [f'[{i + 1}]' for i in range(20)]
     ACCEPT_MODEL_TYPES = ("qwen2", "llama", "mistral", "qwen3")      # vLLM takes any chat model; these are the families the engine serves
 
+    # FP8 step weights (LlamaRuntime's weight_dtype; lossy, opt-in).  The constructor keeps the reference's parameter list, so the
+    # option is the class's: R1ListwiseLlmRanker.with_weight_dtype("fp8")(model, tokenizer, prompt, ...)
+    weight_dtype = "fp16"
+
+    @classmethod
+    def with_weight_dtype(cls, weight_dtype):
+        from ._runtime import weight_dtype_kw
+        weight_dtype_kw(weight_dtype)                                  # ValueError for anything but "fp16" / "fp8"
+        if weight_dtype == cls.weight_dtype:
+            return cls
+        made = _WEIGHT_DTYPE_CLASSES
+        if (cls, weight_dtype) not in made:                            # one subclass per (class, dtype), not one per call
+            made[cls, weight_dtype] = type(cls.__name__, (cls,), {"weight_dtype": weight_dtype})
+        return made[cls, weight_dtype]
+
     def __init__(self, model_name_or_path, tokenizer_name_or_path, prompt, window_size, step_size, lora_path=None,
                  scoring='generation', num_repeat=1, cache_dir=None, device="cuda", max_new_tokens=2048):
         from transformers import AutoTokenizer
-        from ._runtime import LlamaRuntime, resolve_checkpoint
+        from ._runtime import LlamaRuntime, resolve_checkpoint, weight_dtype_kw
         from .setwise import load_prompt_file
         prompt = load_prompt_file(prompt)
         lora_path = resolve_checkpoint(lora_path, cache_dir) if lora_path is not None else None
         tokenizer = AutoTokenizer.from_pretrained(tokenizer_name_or_path if tokenizer_name_or_path is not None else model_name_or_path,
                                                   cache_dir=cache_dir)
         runtime = LlamaRuntime(model_name_or_path, device, cache_dir=cache_dir, accept_model_types=self.ACCEPT_MODEL_TYPES,
-                               adapter_dir=lora_path)
+                               adapter_dir=lora_path, **weight_dtype_kw(self.weight_dtype))
         self._setup_r1(runtime, tokenizer, prompt, lora_path, device, window_size, step_size, scoring, num_repeat, max_new_tokens)
 
     @classmethod

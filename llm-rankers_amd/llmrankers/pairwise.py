@@ -53,11 +53,12 @@ class PairwiseLlmRanker(LlmRanker):
     needs_decoder_positions = True            # PRP generates two tokens behind "<pad> Passage" (DuoT5LlmRanker: one position)
 
     def __init__(self, model_name_or_path, tokenizer_name_or_path, device, method="allpair", batch_size=2, k=10,
-                 cache_dir=None):
+                 cache_dir=None, weight_dtype="fp16"):
         # ref: pairwise.py:30-82: T5 or Llama family by config.model_type, NotImplementedError otherwise
-        from ._runtime import load_runtime
+        # weight_dtype (not in the reference): "fp8" = FP8 step weights on a Llama-family checkpoint (LlamaRuntime; lossy, opt-in)
+        from ._runtime import load_runtime, weight_dtype_kw
         try:
-            runtime = load_runtime(model_name_or_path, device, cache_dir=cache_dir)
+            runtime = load_runtime(model_name_or_path, device, cache_dir=cache_dir, **weight_dtype_kw(weight_dtype))
         except NotImplementedError as exc:
             raise NotImplementedError(f"{exc} (pairwise)") from None
         if runtime.model_type == "llama":

@@ -58,11 +58,12 @@ class SetwiseLlmRanker(LlmRanker):
                   "M", "N", "O", "P", "Q", "R", "S", "T", "U", "V", "W"]
 
     def __init__(self, model_name_or_path, tokenizer_name_or_path, device, num_child=3, k=10, scoring='generation',
-                 method="heapsort", num_permutation=1, cache_dir=None):
+                 method="heapsort", num_permutation=1, cache_dir=None, weight_dtype="fp16"):
         # ref: setwise.py:25-77: T5 or Llama family by config.model_type, NotImplementedError otherwise
-        from ._runtime import load_runtime
+        # weight_dtype (not in the reference): "fp8" = FP8 step weights on a Llama-family checkpoint (LlamaRuntime; lossy, opt-in)
+        from ._runtime import load_runtime, weight_dtype_kw
         try:
-            runtime = load_runtime(model_name_or_path, device, cache_dir=cache_dir)
+            runtime = load_runtime(model_name_or_path, device, cache_dir=cache_dir, **weight_dtype_kw(weight_dtype))
         except NotImplementedError as exc:   # same message shape as ref: setwise.py:71
             raise NotImplementedError(f"{exc} (setwise)") from None
         if runtime.model_type == "llama":
@@ -408,6 +409,9 @@ def load_prompt_file(prompt_file):
     return prompt
 
 
+_WEIGHT_DTYPE_CLASSES = {}      # (class, weight_dtype) -> the subclass with_weight_dtype hands out
+
+
 class RankR1SetwiseLlmRanker(SetwiseLlmRanker):
     """Rank-R1, the reasoning setwise reranker (ref: llmrankers/setwise.py:406-553; Qwen2.5-Instruct + a LoRA adapter served by
     vLLM there): one compare = a chat prompt listing the passages as "[n] text", a generated chain of thought of up to
@@ -419,19 +423,34 @@ class RankR1SetwiseLlmRanker(SetwiseLlmRanker):
     text is the new tokens decoded without special tokens."""
     CHARACTERS = [f'[{i + 1}]' for i in range(20)]
 
+    # FP8 step weights (LlamaRuntime's weight_dtype; lossy, opt-in).  The constructor keeps the reference's parameter list, so the
+    # option is the class's: RankR1SetwiseLlmRanker.with_weight_dtype("fp8")(model, prompt_file, ...)
+    weight_dtype = "fp16"
+
+    @classmethod
+    def with_weight_dtype(cls, weight_dtype):
+        from ._runtime import weight_dtype_kw
+        weight_dtype_kw(weight_dtype)                                  # ValueError for anything but "fp16" / "fp8"
+        if weight_dtype == cls.weight_dtype:
+            return cls
+        made = _WEIGHT_DTYPE_CLASSES
+        if (cls, weight_dtype) not in made:                            # one subclass per (class, dtype), not one per call
+            made[cls, weight_dtype] = type(cls.__name__, (cls,), {"weight_dtype": weight_dtype})
+        return made[cls, weight_dtype]
+
     def __init__(self, model_name_or_path, prompt_file, lora_name_or_path=None, tokenizer_name_or_path=None, num_child=19, k=10,
                  scoring='generation', method="heapsort", num_permutation=1, cache_dir=None, verbose=False, device="cuda",
                  max_new_tokens=2048):
         if scoring != 'generation':
             raise NotImplementedError(f"Scoring method {scoring} is not supported for RankR1SetwiseLlmRanker. RankR1SetwiseLlmRanker only supports 'generation' scoring.")
         from transformers import AutoTokenizer
-        from ._runtime import LlamaRuntime, resolve_checkpoint
+        from ._runtime import LlamaRuntime, resolve_checkpoint, weight_dtype_kw
         prompt = load_prompt_file(prompt_file)
         lora_path = resolve_checkpoint(lora_name_or_path, cache_dir) if lora_name_or_path is not None else None
         tokenizer = AutoTokenizer.from_pretrained(tokenizer_name_or_path if tokenizer_name_or_path is not None else model_name_or_path,
                                                   cache_dir=cache_dir)
         runtime = LlamaRuntime(model_name_or_path, device, cache_dir=cache_dir, accept_model_types=("qwen2", "llama", "mistral", "qwen3"),
-                               adapter_dir=lora_path)
+                               adapter_dir=lora_path, **weight_dtype_kw(self.weight_dtype))
         self._setup_r1(runtime, tokenizer, prompt, lora_path, device, num_child, k, method, num_permutation, verbose, max_new_tokens)
 
     @classmethod

@@ -229,7 +229,13 @@ def candidates_sharded(args, world):
 
 
 def build_ranker(args):
+    # --weight_dtype: forwarded only when given (a run without the flag makes the calls it always made); the T5-only rankers refuse fp8
+    wd = getattr(args.run, "weight_dtype", None)
+    wd_kw = {} if wd is None else {"weight_dtype": wd}
     if args.pointwise:
+        if wd == "fp8":
+            raise NotImplementedError("--weight_dtype fp8 is not supported by the pointwise rankers: they serve T5 checkpoints, FP8 step "
+                                      "weights the Llama family's decoding step")
         from llmrankers.pointwise import MonoT5LlmRanker, PointwiseLlmRanker
         cls = MonoT5LlmRanker if "monot5" in args.run.model_name_or_path else PointwiseLlmRanker
         return cls(model_name_or_path=args.run.model_name_or_path, tokenizer_name_or_path=args.run.tokenizer_name_or_path,
@@ -240,6 +246,8 @@ def build_ranker(args):
             raise NotImplementedError("OpenAI rankers are remote HTTP calls, not part of the MI355X hot path; use the reference")
         if getattr(args.run, "prompt_file", None):               # the Rank-R1 reasoning reranker (ref: Rank-R1/run_setwise.py:120-132)
             from llmrankers.setwise import RankR1SetwiseLlmRanker
+            if wd is not None:                                   # (the two R1 constructors keep the reference's parameter lists)
+                RankR1SetwiseLlmRanker = RankR1SetwiseLlmRanker.with_weight_dtype(wd)
             return RankR1SetwiseLlmRanker(model_name_or_path=args.run.model_name_or_path, prompt_file=args.run.prompt_file,
                                           lora_name_or_path=args.run.lora_name_or_path,
                                           tokenizer_name_or_path=args.run.tokenizer_name_or_path, device=args.run.device,
@@ -250,7 +258,7 @@ def build_ranker(args):
         return SetwiseLlmRanker(model_name_or_path=args.run.model_name_or_path, tokenizer_name_or_path=args.run.tokenizer_name_or_path,
                                 device=args.run.device, cache_dir=args.run.cache_dir, num_child=args.setwise.num_child,
                                 scoring=args.run.scoring, method=args.setwise.method,
-                                num_permutation=args.setwise.num_permutation, k=args.setwise.k)
+                                num_permutation=args.setwise.num_permutation, k=args.setwise.k, **wd_kw)
     if args.pairwise:
         if args.pairwise.method != "allpair":                    # ref: run.py:88-90
             args.pairwise.batch_size = 2
@@ -259,14 +267,20 @@ def build_ranker(args):
             raise NotImplementedError("OpenAI rankers are remote HTTP calls, not part of the MI355X hot path; use the reference")
         from llmrankers.pairwise import DuoT5LlmRanker, PairwiseLlmRanker
         cls = DuoT5LlmRanker if "duot5" in args.run.model_name_or_path else PairwiseLlmRanker        # ref: run.py:99-106
+        if cls is DuoT5LlmRanker and wd == "fp8":
+            raise NotImplementedError("--weight_dtype fp8 is not supported by the duoT5 ranker: it serves T5 checkpoints")
+        if cls is DuoT5LlmRanker:
+            wd_kw = {}
         return cls(model_name_or_path=args.run.model_name_or_path, tokenizer_name_or_path=args.run.tokenizer_name_or_path,
                                  device=args.run.device, cache_dir=args.run.cache_dir, method=args.pairwise.method,
-                                 batch_size=args.pairwise.batch_size, k=args.pairwise.k)
+                                 batch_size=args.pairwise.batch_size, k=args.pairwise.k, **wd_kw)
     if args.listwise:
         if args.run.openai_key:
             raise NotImplementedError("OpenAI rankers are remote HTTP calls, not part of the MI355X hot path; use the reference")
         if getattr(args.run, "prompt_file", None):               # Rank-R1's listwise baseline (ref: Rank-R1/run_listwise.py:159-178)
             from llmrankers.listwise import R1ListwiseLlmRanker
+            if wd is not None:
+                R1ListwiseLlmRanker = R1ListwiseLlmRanker.with_weight_dtype(wd)
             return R1ListwiseLlmRanker(model_name_or_path=args.run.model_name_or_path, tokenizer_name_or_path=args.run.tokenizer_name_or_path,
                                        prompt=args.run.prompt_file, window_size=args.listwise.window_size, step_size=args.listwise.step_size,
                                        lora_path=args.run.lora_name_or_path, num_repeat=args.listwise.num_repeat, cache_dir=args.run.cache_dir,
@@ -275,7 +289,7 @@ def build_ranker(args):
         return ListwiseLlmRanker(model_name_or_path=args.run.model_name_or_path, tokenizer_name_or_path=args.run.tokenizer_name_or_path,
                                  device=args.run.device, cache_dir=args.run.cache_dir, window_size=args.listwise.window_size,
                                  step_size=args.listwise.step_size, scoring=args.run.scoring, num_repeat=args.listwise.num_repeat,
-                                 **({} if getattr(args.listwise, "sample_seed", None) is None else {"sample_seed": args.listwise.sample_seed}))
+                                 **({} if getattr(args.listwise, "sample_seed", None) is None else {"sample_seed": args.listwise.sample_seed}), **wd_kw)
     raise ValueError("Must specify either --pointwise, --setwise, --pairwise or --listwise.")
 
 
@@ -532,6 +546,9 @@ def build_parser():
     rp.add_argument("--query_length", type=int, default=128)
     rp.add_argument("--passage_length", type=int, default=128)
     rp.add_argument("--device", type=str, default="cuda")
+    rp.add_argument("--weight_dtype", type=str, default=None, choices=["fp16", "fp8"],
+                    help="Llama-family checkpoints: fp8 keeps the projections the decoding step streams as FP8 step weights (lossy: one "
+                         "e4m3 rounding per weight; rankings can differ from fp16).  Default: fp16")
     rp.add_argument("--cache_dir", type=str, default=None)
     rp.add_argument("--openai_key", type=str, default=None)
     rp.add_argument("--scoring", type=str, default="generation", choices=["generation", "likelihood"])
