@@ -288,6 +288,22 @@ int rk_llama_session_run(rk_engine* e, int max_steps, int32_t* out_finished, int
 int rk_llama_session_read(rk_engine* e, int slot, int32_t* out_tokens, int cap, int32_t* out_n);
 /* Drains the stream and ends the session (a no-op without one).  Cache and step graph stay for the next open of the same sizes. */
 int rk_llama_session_close(rk_engine* e);
+/* Drafting by prompt lookup (vLLM's [ngram] speculative mode, hf generate's prompt_lookup_num_tokens): rk_llama_session_open with
+ * `draft` = Kd in 1..7 extra rows per slot and step.  Row 0 of a slot is the plain session's row; row j feeds draft token d_j at
+ * the next position.  The step's first token is always accepted, the token of row j while d_j equals the token of row j - 1 and no
+ * accepted token ended the request (EOS, max_new, max_new_cap).  The drafts are the continuation of the most recent earlier
+ * occurrence of the request's last N tokens in its own prompt + output, N from ngram_max down to ngram_min.  The tokens of a
+ * request, and where it finishes, are bit for bit the plain session's; only the number of steps differs.  draft = 0 IS
+ * rk_llama_session_open.  Every other session call is used as before.
+ * RK_ERR_INVALID for draft outside 0..7 or ngram_min / ngram_max outside 1 <= min <= max <= 8; RK_ERR_CAPACITY for
+ * n_slots * (draft + 1) > max_seqs (the step's activation rows); RK_ERR_STATE with draft > 0 while sampling is on (greedy only);
+ * rk_llama_session_admit_sampled on a drafting session is RK_ERR_STATE. */
+int rk_llama_session_open_draft(rk_engine* e, int n_slots, int max_len, int max_new_cap, const int32_t* eos_ids, int n_eos, int pad_id,
+                                int draft, int ngram_min, int ngram_max);
+/* Any open session.  *out_steps: the steps rk_llama_session_run issued since the open; *out_tokens: the tokens those steps emitted
+ * (the admits' first tokens not counted); out_slot_steps[n_slots]: the steps each slot's current request was active in;
+ * out_slot_cols[n_slots]: its output column (tokens so far).  0 for an idle slot.  Any pointer may be null. */
+int rk_llama_session_stats(rk_engine* e, int64_t* out_steps, int64_t* out_tokens, int32_t* out_slot_steps, int32_t* out_slot_cols);
 
 /* ---- score collection across the GPUs of one node: one process per GPU, one engine per process.
  * The reference has no counterpart (its multi-GPU mode is accelerate's layer placement, ref: pointwise.py:21); this
@@ -636,6 +652,12 @@ typedef struct rk_debug_graph_stats_t {
   int64_t eager, captures, replays, failed, evictions;
 } rk_debug_graph_stats_t;
 int rk_debug_graph_stats(rk_engine* e, rk_debug_graph_stats_t* out);
+/* debug (tests, tools/bench_llama_draft.py): the proposer of `slot` of the open drafting session takes its drafts from the caller's
+ * continuation table tokens[n], indexed by output column (the draft for column c is tokens[c]), in place of the n-gram lookup, so
+ * that acceptance is a function of the table whatever a toy model emits.  It holds until it is replaced; tokens = null, n = 0:
+ * back to the lookup.  In force from the slot's next admit or step.  RK_ERR_STATE without a drafting session, RK_ERR_CAPACITY for
+ * n > max_new_cap. */
+int rk_debug_session_drafts(rk_engine* e, int slot, const int32_t* tokens, int n);
 /* debug: the engine's grown buffers - device memory that is freed and reallocated between calls when a call needs more of it
  * (csrc/rk_engine.hip: Grown<T>::reserve) - and the move counters that stand in the graph keys.  Per buffer its device address
  * (0: never allocated) and its capacity in elements, in the order of RK_DEBUG_BUFFER_NAMES; amax_gen counts the moves of amax_val

@@ -422,8 +422,13 @@ __device__ __forceinline__ half8 rope_lane8(const half_t* row, const float* bias
 // pos < W nothing is skipped or masked: the plain kernel's bits.  WIN = false is the kernel as it was.
 // QKN (Qwen3's q / k head norm; the entry attn_dec_cached_qkn_kernel in llama_kernels_qknorm.h): the row transform is qkn_lane8 - norm,
 // rotation, one rounding, the arithmetic of the prefill's rope128_qkn_kernel - instead of rope_lane8; nothing else differs.
-template <int D, int R, bool BIAS, bool WIN, bool QKN = false>
-__device__ __forceinline__ void attn_dec_cached_body(const LlamaDecAttnArgs& p) {
+// KEYS (a drafting session's step, LlamaDecAttnKeysArgs; the entries attn_dec_keys_*_kernel below): the step's rows are G1 per
+// cache row - row b reads cache row b / G1 - and every key <= pos, the row's own included, is already in the cache
+// (kv_cache_append_kernel ran in front): no new key is formed, none is selected and nothing is written.  The bytes the append left
+// are the bytes `knew` / `vnew` hold in the plain form, so a row's context is the plain kernel's bit for bit.  KEYS = false is the
+// kernel as it was.
+template <int D, int R, bool BIAS, bool WIN, bool QKN = false, bool KEYS = false, class ARGS = LlamaDecAttnArgs>
+__device__ __forceinline__ void attn_dec_cached_body(const ARGS& p) {
   static_assert(D == 128 || D == 64, "lanes per key 16 or 8");
   constexpr int LK = D / 8, KL = 512 / D, NL = D / 16;   // lanes per key, keys per wave load, loads per wave
   __shared__ float s_m[4][R], s_l[4][R];
@@ -447,15 +452,22 @@ __device__ __forceinline__ void attn_dec_cached_body(const LlamaDecAttnArgs& p) 
     if constexpr (QKN) return qkn_lane8(row, p.qkn, p.qkn_eps, p.n_heads, hd, i0, hi, co, si);
     else return rope_lane8<D, BIAS>(row, p.bias, hd, i0, hi, co, si);
   };
-  const half8 knew = rotated(p.n_heads + kvh);
-  const size_t voff = (size_t)(p.n_heads + p.n_kv + kvh) * D + c * 8;
-  half8 vnew = *(const half8*)(row + voff);
-  if constexpr (BIAS) vnew = bias_v8(vnew, p.bias + voff);
-  half_t* kbase = p.kc + ((size_t)b * p.n_kv + kvh) * p.P * D + c * 8;
-  half_t* vbase = p.vc + ((size_t)b * p.n_kv + kvh) * p.P * D + c * 8;
-  if (pos - key0 < LDC_CHUNK && h0 % G == 0 && wave == 0 && kg == 0) {   // the position's chunk, once per kv head
-    *(half8*)(kbase + (size_t)pos * D) = knew;
-    *(half8*)(vbase + (size_t)pos * D) = vnew;
+  half8 knew, vnew;
+  int crow = b;                                           // the row's cache row
+  if constexpr (KEYS) crow = b / p.g1;
+  else {
+    knew = rotated(p.n_heads + kvh);
+    const size_t voff = (size_t)(p.n_heads + p.n_kv + kvh) * D + c * 8;
+    vnew = *(const half8*)(row + voff);
+    if constexpr (BIAS) vnew = bias_v8(vnew, p.bias + voff);
+  }
+  half_t* kbase = p.kc + ((size_t)crow * p.n_kv + kvh) * p.P * D + c * 8;
+  half_t* vbase = p.vc + ((size_t)crow * p.n_kv + kvh) * p.P * D + c * 8;
+  if constexpr (!KEYS) {
+    if (pos - key0 < LDC_CHUNK && h0 % G == 0 && wave == 0 && kg == 0) {   // the position's chunk, once per kv head
+      *(half8*)(kbase + (size_t)pos * D) = knew;
+      *(half8*)(vbase + (size_t)pos * D) = vnew;
+    }
   }
   const int wkey0 = key0 + wave * 32;
   float m_w[R], l_w[R], acc[R][8];
@@ -467,7 +479,7 @@ __device__ __forceinline__ void attn_dec_cached_body(const LlamaDecAttnArgs& p) 
   }
   if (wkey0 <= pos && (!WIN || wkey0 + 31 >= lo)) {       // wave-uniform
     half8 kf[NL], vf[NL];
-    const int last_old = pos > 0 ? pos - 1 : 0;           // keys before the new one come from the cache
+    const int last_old = KEYS ? pos : (pos > 0 ? pos - 1 : 0);   // keys before the new one come from the cache (KEYS: all of them)
 #pragma unroll
     for (int i = 0; i < NL; ++i) {
       const int key = wkey0 + KL * i + kg;
@@ -475,11 +487,13 @@ __device__ __forceinline__ void attn_dec_cached_body(const LlamaDecAttnArgs& p) 
       kf[i] = *(const half8*)(kbase + (size_t)idx * D);
       vf[i] = *(const half8*)(vbase + (size_t)idx * D);
     }
+    if constexpr (!KEYS) {
 #pragma unroll
-    for (int i = 0; i < NL; ++i) {
-      const bool is_new = wkey0 + KL * i + kg >= pos;
-      kf[i] = is_new ? knew : kf[i];
-      vf[i] = is_new ? vnew : vf[i];
+      for (int i = 0; i < NL; ++i) {
+        const bool is_new = wkey0 + KL * i + kg >= pos;
+        kf[i] = is_new ? knew : kf[i];
+        vf[i] = is_new ? vnew : vf[i];
+      }
     }
     float s[R][NL];
 #pragma unroll
@@ -555,6 +569,53 @@ template <int D, int R, bool BIAS>
 __global__ __launch_bounds__(256) void attn_dec_cached_kernel(LlamaDecAttnArgs p) { attn_dec_cached_body<D, R, BIAS, false>(p); }
 template <int D, int R, bool BIAS>
 __global__ __launch_bounds__(256) void attn_dec_cached_win_kernel(LlamaDecAttnArgs p) { attn_dec_cached_body<D, R, BIAS, true>(p); }
+
+// ---- a drafting session's step (rk_llama_session_open_draft): G1 rows per cache row, the keys appended in front of the attention ----
+struct LlamaDecAttnKeysArgs : LlamaDecAttnArgs {   // the drafting entries' arguments; the plain kernels' struct stays what it was
+  int g1;                // rows per cache row: step row b belongs to cache row b / g1
+  const int* live;       // [rows] kv_cache_append_kernel: 1 = the row's key and value go to the cache, 0 = a dead row, nothing is written
+};
+// The cache append of a drafting step, in front of each layer's attention: row b's rotated key and its value go to cache row
+// b / g1 at the row's position - formed by the helpers the step kernel forms `knew` / `vnew` with (rope_lane8 / bias_v8 / qkn_lane8,
+// on the lane mapping of attn_dec_cached_body: lane c of a key's D / 8 holds 8 dims), so the bytes are those a plain step writes.
+// grid = rows; an item is (kv head, lane c).  A dead row (live[b] = 0) or a position outside the cache writes nothing.  QKN: the 8
+// lanes of an aligned group hold the items of one half of ONE head (D / 8 = 16 items per head) and the bound n_kv * 16 is a multiple
+// of 8, so a group enters and leaves the loop together and qkn_pairs' shuffles read active lanes only.
+template <int D, bool BIAS, bool QKN>
+__global__ __launch_bounds__(256) void kv_cache_append_kernel(LlamaDecAttnKeysArgs p) {
+  constexpr int LK = D / 8, NL = D / 16;
+  const int b = blockIdx.x;
+  if (!p.live[b]) return;                                 // uniform
+  const int pos = p.pos[b];
+  if (pos < 0 || pos > p.P - 1) return;                   // uniform: no write outside the cache
+  const int crow = b / p.g1;
+  const half_t* row = p.qkv + (size_t)b * p.ld;
+  for (int it = threadIdx.x; it < p.n_kv * LK; it += 256) {
+    const int kvh = it / LK, c = it % LK;
+    const int i0 = (c % NL) * 8;
+    const bool hi = c >= NL;
+    float co[8], si[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) { co[j] = p.cos_t[(size_t)pos * (D / 2) + i0 + j]; si[j] = p.sin_t[(size_t)pos * (D / 2) + i0 + j]; }
+    auto rotated = [&](int hd) {
+      if constexpr (QKN) return qkn_lane8(row, p.qkn, p.qkn_eps, p.n_heads, hd, i0, hi, co, si);
+      else return rope_lane8<D, BIAS>(row, p.bias, hd, i0, hi, co, si);
+    };
+    const half8 knew = rotated(p.n_heads + kvh);
+    const size_t voff = (size_t)(p.n_heads + p.n_kv + kvh) * D + c * 8;
+    half8 vnew = *(const half8*)(row + voff);
+    if constexpr (BIAS) vnew = bias_v8(vnew, p.bias + voff);
+    const size_t dst = (((size_t)crow * p.n_kv + kvh) * p.P + pos) * D + c * 8;
+    *(half8*)(p.kc + dst) = knew;
+    *(half8*)(p.vc + dst) = vnew;
+  }
+}
+template <int D, int R, bool BIAS>
+__global__ __launch_bounds__(256) void attn_dec_keys_kernel(LlamaDecAttnKeysArgs p) { attn_dec_cached_body<D, R, BIAS, false, false, true>(p); }
+template <int D, int R, bool BIAS>
+__global__ __launch_bounds__(256) void attn_dec_keys_win_kernel(LlamaDecAttnKeysArgs p) { attn_dec_cached_body<D, R, BIAS, true, false, true>(p); }
+template <int D, int R>
+__global__ __launch_bounds__(256) void attn_dec_keys_qkn_kernel(LlamaDecAttnKeysArgs p) { attn_dec_cached_body<D, R, false, false, true, true>(p); }
 
 // Merges the chunk partials of one (sequence, head) in key order and writes the fp16 context.  grid = (n_heads, rows), D
 // threads = the head's D dims.

@@ -277,6 +277,118 @@ __global__ __launch_bounds__(256) void llama_session_advance_kernel(const int* _
   if (tid == 0 && s_fin) st[0] += s_fin;
 }
 
+// Token feedback of a DRAFTING session (rk_llama_session_open_draft): llama_session_advance_kernel's state machine over g1 = Kd + 1
+// rows per slot.  Row (s, 0) fed the slot's last accepted token, row (s, j) the draft token d_j = rnext[s g1 + j] at the next
+// positions; dlen[s] of the extra rows are live.  t_0 = argmax(row 0) is always accepted; t_j = argmax(row j) is accepted while
+// d_j == t_{j-1} and no accepted token has ended the slot (an EOS id, its max_new-th token, cap).  Accepted tokens go to the slot's
+// output columns and to its history hist[s][len + column] (the prompt in front: what draft_lookup_kernel searches); col advances by
+// the number accepted.  nstep[s] counts the steps the slot's request was active in.  st as above, st[5] / st[6] = ngram_min / max.
+// admit != null: row r of argmax is the prefill's last row of slot admit[r]; the slot starts here, its prompt tokens[seq_off[r] ..]
+// is copied to its history and t_0 is its column 0.  One workgroup; rnext / dlen are written by draft_lookup_kernel behind this.
+__global__ __launch_bounds__(256) void llama_session_advance_draft_kernel(const int* __restrict__ argmax, int* st, int* len, int* col,
+                                                                          int* max_new, int* done, int* out, int n_slots,
+                                                                          const int* __restrict__ admit, int n_admit, int g1,
+                                                                          const int* __restrict__ rnext, const int* __restrict__ dlen,
+                                                                          int* hist, int* nstep, const int* __restrict__ tokens,
+                                                                          const int* __restrict__ seq_off) {
+  __shared__ int s_fin;
+  const int tid = threadIdx.x, n_eos = st[2], max_len = st[3], cap = st[4];
+  if (tid == 0) s_fin = 0;
+  if (admit) {                                             // the prompts into the histories, every thread
+    for (int r = 0; r < n_admit; ++r) {
+      const int b = admit[r], L = admit[n_admit + r], t0 = seq_off[r];
+      if (b < 0 || b >= n_slots) continue;
+      for (int t = tid; t < L && t < max_len; t += 256) hist[(size_t)b * max_len + t] = tokens[t0 + t];
+    }
+  }
+  __syncthreads();
+  const int rows = admit ? n_admit : n_slots;
+  for (int r = tid; r < rows; r += 256) {
+    int b = r;
+    if (admit) {
+      b = admit[r];
+      if (b < 0 || b >= n_slots) continue;
+      len[b] = admit[n_admit + r]; max_new[b] = admit[2 * n_admit + r]; col[b] = 0; done[b] = 0; nstep[b] = 0;
+    }
+    if (done[b]) continue;
+    const int row0 = admit ? r : b * g1, dl = admit ? 0 : dlen[b], L = len[b], mn = max_new[b];
+    int c = col[b], prev = 0;
+    bool fin = false;
+    for (int j = 0; j <= dl && j < g1 && !fin; ++j) {
+      const int tok = argmax[row0 + j];
+      if (j > 0 && rnext[b * g1 + j] != prev) break;       // the draft fed to row j was not the token row j - 1 chose
+      if (c < cap) out[(size_t)b * cap + c] = tok;
+      if (L + c < max_len) hist[(size_t)b * max_len + L + c] = tok;
+      ++c;
+      prev = tok;
+      fin = c >= mn || c >= cap;
+      for (int k = 0; k < n_eos; ++k) fin = fin || tok == st[8 + k];
+    }
+    col[b] = c;
+    if (!admit) nstep[b] += 1;
+    if (fin) { done[b] = 1; atomicAdd(&s_fin, 1); }
+  }
+  __syncthreads();
+  if (tid == 0 && s_fin) st[0] += s_fin;
+}
+
+// The proposer of a drafting session, one workgroup per slot, behind llama_session_advance_draft_kernel: the next step's g1 rows of
+// the slot.  Row 0 feeds the last accepted token h[n - 1] at position n - 1 (n = len + col, the history's length).  The drafts:
+// for N from ngram_max down to ngram_min the LARGEST i with h[i, i + N) == h[n - N, n) and i + N < n (a max-reduction over the
+// candidates: the same answer whatever the thread order) proposes h[i + N, min(i + N + Kd, n)) - prompt lookup (hf: generation/
+// candidate_generator.py PromptLookupCandidateGenerator; vLLM's [ngram] mode).  tabn[s] >= 0 (rk_debug_session_drafts): the drafts
+// come from the caller's table instead, d_j = tab[s][col + j - 1].  They are clipped so that no live row lies beyond position
+// max_len - 1 or beyond the slot's remaining max_new / cap.  Row j <= dlen: id d_j, position n - 1 + j, live; the others are dead:
+// pad, position 0, not live (no cache write, results ignored).  An idle or done slot: no drafts, row 0 feeds pad at the position
+// it has (llama_session_advance_kernel's rule).
+__global__ __launch_bounds__(256) void draft_lookup_kernel(const int* __restrict__ st, const int* __restrict__ len, const int* __restrict__ col,
+                                                           const int* __restrict__ max_new, const int* __restrict__ done, int g1,
+                                                           int* rnext, int* rpos, int* rlive, int* dlen, const int* __restrict__ hist,
+                                                           const int* __restrict__ tab, const int* __restrict__ tabn) {
+  __shared__ int s_best;
+  const int s = blockIdx.x, tid = threadIdx.x, Kd = g1 - 1;
+  const int pad = st[1], max_len = st[3], cap = st[4], nmin = st[5], nmax = st[6];
+  int* nx = rnext + (size_t)s * g1; int* ps = rpos + (size_t)s * g1; int* lv = rlive + (size_t)s * g1;
+  if (done[s]) {                                           // uniform
+    if (tid == 0) { nx[0] = pad; lv[0] = 1; dlen[s] = 0; }
+    if (tid >= 1 && tid < g1) { nx[tid] = pad; ps[tid] = 0; lv[tid] = 0; }
+    return;
+  }
+  const int c = col[s], n = len[s] + c;
+  const int* h = hist + (size_t)s * max_len;
+  int lim = min(min(Kd, max_len - n), min(max_new[s], cap) - c - 1);
+  lim = lim > 0 ? lim : 0;
+  int dl = 0, src = 0;                                     // drafts d_j = from[src + j - 1]
+  const int* from = h;
+  if (tabn[s] >= 0) {
+    from = tab + (size_t)s * cap; src = c;
+    dl = min(lim, tabn[s] - c);
+    dl = dl > 0 ? dl : 0;
+  } else if (lim > 0) {
+    for (int N = nmax; N >= nmin; --N) {
+      if (N > n - 1) continue;                             // uniform
+      if (tid == 0) s_best = -1;
+      __syncthreads();
+      int best = -1;
+      for (int i = tid; i + N < n; i += 256) {
+        bool eq = true;
+        for (int k = 0; k < N; ++k) eq = eq && h[i + k] == h[n - N + k];
+        if (eq) best = i;
+      }
+      if (best >= 0) atomicMax(&s_best, best);
+      __syncthreads();
+      best = s_best;
+      __syncthreads();
+      if (best >= 0) { src = best + N; dl = min(lim, n - src); break; }   // uniform
+    }
+  }
+  if (tid == 0) { nx[0] = h[n - 1]; ps[0] = n - 1 < max_len - 1 ? n - 1 : max_len - 1; lv[0] = 1; dlen[s] = dl; }
+  if (tid >= 1 && tid < g1) {
+    const bool on = tid <= dl;
+    nx[tid] = on ? from[src + tid - 1] : pad; ps[tid] = on ? n - 1 + tid : 0; lv[tid] = on ? 1 : 0;
+  }
+}
+
 // QLM score (ref: llmrankers/pointwise.py:77-79) from the fused head (gemm.h: EPI_LSE_F32): stats [rows, nblk] = (block max, sum exp(x - block max)), xlab [rows] =
 // the label's logit.  out[b] = -sum_t ( logsumexp_t - xlab[b, t] ), logsumexp_t = M + log(sum_blocks s * exp(m - M)).
 // One block per sequence; the blocks of a position are merged in a fixed order, the positions summed in order (deterministic).

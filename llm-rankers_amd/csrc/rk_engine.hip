@@ -253,6 +253,8 @@ struct rk_engine {
     bool open = false; int n_slots = 0, max_len = 0, cap = 0, seen = 0;   // seen: the session word at the last read-back
     std::vector<int> busy, told, len, max_new, col, done;                 // per slot; told: its finish was returned by a run
     bool sampled = false; std::vector<unsigned long long> seeds;          // latched at open: the sampling head; every slot's seed
+    int draft = 0, ngram_min = 1, ngram_max = 3;                          // rk_llama_session_open_draft: Kd extra rows per slot (0: none)
+    long long steps = 0, tokens = 0;                                      // rk_llama_session_stats: steps issued, tokens they emitted
   } ls;
   // decoder chains as HIP graphs: key = everything the launch parameters of a chain depend on; at most RK_GRAPH_CACHE_KEYS keys
   // (run_graphed); graph_count: what run_graphed did since the engine was created (rk_debug_graph_stats)
@@ -810,6 +812,18 @@ void launch_session_advance(hipStream_t st, const int* argmax, int* state, int* 
   hipLaunchKernelGGL(llama_session_advance_kernel, dim3(1), dim3(256), 0, st, argmax, state, len, col, max_new, done, pos, out, next_ids, n_slots,
                      admit, n_admit);
 }
+// a drafting session's int arrays behind the plain session's (session_draft_ints)
+struct DraftInts { int *rnext, *rpos, *rlive, *dlen, *nstep, *tabn, *tab, *hist; };
+void launch_session_advance_draft(hipStream_t st, const int* argmax, int* state, int* len, int* col, int* max_new, int* done, int* out,
+                                  int n_slots, const int* admit, int n_admit, int g1, const DraftInts& x, const int* tokens, const int* seq_off) {
+  hipLaunchKernelGGL(llama_session_advance_draft_kernel, dim3(1), dim3(256), 0, st, argmax, state, len, col, max_new, done, out, n_slots,
+                     admit, n_admit, g1, (const int*)x.rnext, (const int*)x.dlen, x.hist, x.nstep, tokens, seq_off);
+}
+void launch_draft_lookup(hipStream_t st, const int* state, const int* len, const int* col, const int* max_new, const int* done, int n_slots,
+                         int g1, const DraftInts& x) {
+  hipLaunchKernelGGL(draft_lookup_kernel, dim3(n_slots), dim3(256), 0, st, state, len, col, max_new, done, g1, x.rnext, x.rpos, x.rlive, x.dlen,
+                     (const int*)x.hist, (const int*)x.tab, (const int*)x.tabn);
+}
 
 void rmsnorm(rk_engine* e, hipStream_t st, const float* x, const float* w, half_t* out, const int* row_map, int rows, float scale = 1.f) {
   if (rows <= 0) return;
@@ -1344,6 +1358,49 @@ void launch_llama_dec_attn(rk_engine* e, hipStream_t st, const LlamaDecAttnPlan&
   });
 }
 
+// A drafting session's step (rk_llama_session_open_draft): `rows` = n_slots * g1 step rows over a cache of n_slots rows.
+// kv_cache_append_kernel puts every live row's key and value where a plain step would have written them, then the keys-cached
+// entries (attn_dec_keys_*_kernel: the plain body without the new-key select and the cache write) run by the SAME plan rule over
+// `rows`, and the plain merge.  One more small launch per layer than the plain step.
+void launch_llama_dec_attn_keys(rk_engine* e, hipStream_t st, const LlamaDecAttnPlan& p, LlamaDecAttnKeysArgs a, int rows) {
+  a.nch = p.nch; a.window = p.window;
+  Bracket br(e, st, PC_DEC_ATTN, 4.0 * rows * (double)a.P * a.n_heads * p.hd, 2.0 * rows * (double)a.P * a.n_kv * p.hd * 2.0);
+  with_width(p.hd, [&](auto W) {
+    constexpr int D = decltype(W)::value;
+    if (a.qkn) {
+      if constexpr (D == 128) hipLaunchKernelGGL((kv_cache_append_kernel<D, false, true>), dim3(rows), dim3(256), 0, st, a);
+      else abort();
+    }
+    else if (a.bias) hipLaunchKernelGGL((kv_cache_append_kernel<D, true, false>), dim3(rows), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((kv_cache_append_kernel<D, false, false>), dim3(rows), dim3(256), 0, st, a);
+    auto go = [&](auto rc) {
+      constexpr int R = decltype(rc)::value;
+      if constexpr (R == 7 && D != 128) abort();             // no such kernel: plan_llama_dec_attn gives R = 7 at 128 alone
+      else if (a.qkn) {
+        if constexpr (D == 128) hipLaunchKernelGGL((attn_dec_keys_qkn_kernel<D, R>), p.grid, dim3(256), 0, st, a);
+        else abort();
+      }
+      else if (p.window > 0) {
+        if (a.bias) hipLaunchKernelGGL((attn_dec_keys_win_kernel<D, R, true>), p.grid, dim3(256), 0, st, a);
+        else hipLaunchKernelGGL((attn_dec_keys_win_kernel<D, R, false>), p.grid, dim3(256), 0, st, a);
+      }
+      else if (a.bias) hipLaunchKernelGGL((attn_dec_keys_kernel<D, R, true>), p.grid, dim3(256), 0, st, a);
+      else hipLaunchKernelGGL((attn_dec_keys_kernel<D, R, false>), p.grid, dim3(256), 0, st, a);
+    };
+    using std::integral_constant;
+    switch (p.R) {
+      case 8: go(integral_constant<int, 8>{}); break;
+      case 7: go(integral_constant<int, 7>{}); break;
+      case 4: go(integral_constant<int, 4>{}); break;
+      case 2: go(integral_constant<int, 2>{}); break;
+      default: go(integral_constant<int, 1>{}); break;
+    }
+    const LlamaDecAttnArgs base = a;                         // the merge is per (head, row): the plain kernels
+    if (p.window > 0) hipLaunchKernelGGL(attn_dec_combine_win_kernel<D>, p.cgrid, dim3(D), 0, st, base);
+    else hipLaunchKernelGGL(attn_dec_combine_kernel<D>, p.cgrid, dim3(D), 0, st, base);
+  });
+}
+
 // The slot's previous launch may still be in its decoder: the encoder chain stops here until that one is done.  (Read back
 // already, or everything on one stream: nothing to wait for.)
 int wait_prev_decoder(rk_engine* e, Slot& sl) {
@@ -1692,7 +1749,7 @@ int stage_slot(rk_engine* e, int slot, const int32_t* tokens, const int32_t* seq
 // The table holds at most RK_GRAPH_CACHE_KEYS keys: the key that would pass the bound ERASES every other entry (evict_graphs) -
 // their graphs, their sightings, and the entries of epochs that no call can reach any more - and the keys still in use come back
 // on their next two sightings.  One eviction per RK_GRAPH_CACHE_KEYS new keys; every outcome is counted (rk_debug_graph_stats).
-enum GraphKind { GK_T5_SCORE, GK_T5_GREEDY_STEP, GK_T5_GREEDY2, GK_T5_GENERATE_STEP, GK_LLAMA_STEP, GK_T5_COMPARE, GK_LLAMA_SESSION_STEP, GK_LLAMA_STEP_SAMPLED, GK_LLAMA_SESSION_STEP_SAMPLED };   // which chain: the key's first int
+enum GraphKind { GK_T5_SCORE, GK_T5_GREEDY_STEP, GK_T5_GREEDY2, GK_T5_GENERATE_STEP, GK_LLAMA_STEP, GK_T5_COMPARE, GK_LLAMA_SESSION_STEP, GK_LLAMA_STEP_SAMPLED, GK_LLAMA_SESSION_STEP_SAMPLED, GK_LLAMA_SESSION_STEP_DRAFT };   // which chain: the key's first int
 // Every entry but `keep` goes.  A graph of the other slot, or of this stream's previous call, may still be replaying: both slots'
 // decoder streams and slot 0's encoder stream (the Llama family's, and every decoder's with overlap = 0) are drained first, so
 // no graph is destroyed under a launch.  (Erasing the other elements of a std::map leaves the reference to `keep` valid.)
@@ -2982,11 +3039,12 @@ int rk_llama_greedy1(rk_engine* e, const int32_t* tokens, const int32_t* seq_off
 // rk_llama_generate's device memory, grown between calls only (never inside a capture; a move of any of the three changes
 // lkv_gen, which is part of the step graph's key: the step holds all three addresses): the K / V cache, the attention partials,
 // the call's int block (`ints` of them); once: the step's activation rows.  A decoding session (below) holds the same three.
-static int ensure_llama_gen(rk_engine* e, int n_seq, int P, size_t ints) {
+// step_rows (a drafting session: n_seq * g1 step rows over n_seq cache rows): the rows the partials are sized for, 0 = n_seq
+static int ensure_llama_gen(rk_engine* e, int n_seq, int P, size_t ints, int step_rows = 0) {
   const rk_llama_desc& l = e->ld;
   const size_t S = (size_t)l.max_seqs, dm = l.hidden, Q = (size_t)l.n_heads * l.head_dim, KV = (size_t)l.n_kv_heads * l.head_dim, F = l.intermediate;
   const size_t kv = (size_t)l.n_layers * 2 * n_seq * KV * P;
-  const size_t part = (size_t)n_seq * l.n_heads * ((P + LDC_CHUNK - 1) / LDC_CHUNK) * ldc_pstr(l.head_dim);
+  const size_t part = (size_t)std::max(n_seq, step_rows) * l.n_heads * ((P + LDC_CHUNK - 1) / LDC_CHUNK) * ldc_pstr(l.head_dim);
   int rc = RK_OK;
   RC(e->lkv.reserve(e, kv, &e->lkv_gen)); RC(e->lpart.reserve(e, part, &e->lkv_gen)); RC(e->lints.reserve(e, ints, &e->lkv_gen));
   if (!e->lg.stream.hidden) {
@@ -3002,11 +3060,14 @@ static int ensure_llama_gen(rk_engine* e, int n_seq, int P, size_t ints) {
 // gate|up + SwiGLU -> down + residual, then the final-normed rows in slots[0].dlast.  The cache, the partials and the activation
 // rows are the engine's (ensure_llama_gen).  Nothing here depends on which rows are live: a row's bits follow from its own
 // tokens and position.
-static int llama_step_rows(rk_engine* e, hipStream_t st, int rows, int P, const int* d_next, const int* d_pos) {
+// g1 > 1 (a drafting session): `rows` = cache rows * g1 step rows, g1 consecutive ones per cache row; live[rows] says whose key
+// and value go to the cache (kv_cache_append_kernel), and the attention reads every key from there (launch_llama_dec_attn_keys).
+static int llama_step_rows(rk_engine* e, hipStream_t st, int rows, int P, const int* d_next, const int* d_pos, int g1 = 1,
+                           const int* d_live = nullptr) {
   const rk_llama_desc& l = e->ld;
   const int dm = l.hidden, Q = l.n_heads * l.head_dim, KV = l.n_kv_heads * l.head_dim, F = l.intermediate, ldq = Q + 2 * KV;
   const LlamaDecAttnPlan ap = plan_llama_dec_attn(e, rows, P, l.n_heads, l.n_kv_heads);
-  const size_t half_layer = (size_t)rows * KV * P;
+  const size_t half_layer = (size_t)(rows / g1) * KV * P;
   const float scale_log2e = (1.0f / std::sqrt((float)l.head_dim)) * 1.4426950408889634f;
   const auto& lg = e->lg;
   int rc = RK_OK;
@@ -3022,8 +3083,10 @@ static int llama_step_rows(rk_engine* e, hipStream_t st, int rows, int P, const 
     const LlamaLayerW& w = e->ll[i];
     RC(gemm(e, st, normed(Gemm(PC_DEC_GEMM, EPI_STORE_F16, ns.x(), dm, w.qkv_f, dm, lg.qkv, ldq, rows, ldq, dm).w8(b8(w.qkv8)))));
     half_t* kc = e->lkv.p + (size_t)i * 2 * half_layer;
-    launch_llama_dec_attn(e, st, ap, LlamaDecAttnArgs{lg.qkv, kc, kc + half_layer, d_pos, e->rope_cos, e->rope_sin, e->lpart.p, lg.ctx,
-                                                          ldq, l.n_heads, l.n_kv_heads, P, ap.nch, scale_log2e, w.qkv_bias, 0, w.qk_norm, l.eps}, rows);
+    const LlamaDecAttnArgs aa{lg.qkv, kc, kc + half_layer, d_pos, e->rope_cos, e->rope_sin, e->lpart.p, lg.ctx,
+                              ldq, l.n_heads, l.n_kv_heads, P, ap.nch, scale_log2e, w.qkv_bias, 0, w.qk_norm, l.eps};
+    if (g1 == 1) launch_llama_dec_attn(e, st, ap, aa, rows);
+    else launch_llama_dec_attn_keys(e, st, ap, LlamaDecAttnKeysArgs{aa, g1, d_live}, rows);
     RC(ns.producer(e, st, Gemm(PC_DEC_GEMM, EPI_RESID_F32, lg.ctx, Q, w.o, Q, ns.hidden, dm, rows, dm, Q).on(GEMM_STREAM).w8(b8(w.o8))));
     RC(gemm(e, st, normed(Gemm(PC_DEC_GEMM, EPI_SWIGLU_F16, ns.x(), dm, w.gu_f, dm, lg.ffh, F, rows, 2 * F, dm).w8(b8(w.gu8)))));
     RC(ns.producer(e, st, Gemm(PC_DEC_GEMM, EPI_RESID_F32, lg.ffh, F, w.down, F, ns.hidden, dm, rows, dm, F).on(GEMM_STREAM).w8(b8(w.down8)), i + 1 < l.n_layers));
@@ -3138,6 +3201,18 @@ SessionInts session_ints(rk_engine* e) {
   int* g = e->lints.p;
   return SessionInts{g, g + 16, g + 16 + S, g + 16 + 2 * S, g + 16 + 3 * S, g + 16 + 4 * S, g + 16 + 5 * S, g + 16 + 6 * S, g + 16 + 9 * S};
 }
+// a drafting session's arrays behind out[S][cap] (R = S * (Kd + 1) step rows):
+// rnext[R] | rpos[R] | rlive[R] | dlen[S] | nstep[S] | tabn[S] | tab[S][cap] | hist[S][max_len]
+size_t session_n_ints(int n_slots, int cap, int max_len, int draft) {
+  const size_t S = (size_t)n_slots, plain = 16 + 9 * S + S * (size_t)cap;
+  return draft ? plain + 3 * S * (size_t)(draft + 1) + 3 * S + S * (size_t)cap + S * (size_t)max_len : plain;
+}
+DraftInts session_draft_ints(rk_engine* e) {
+  const auto& ls = e->ls;
+  const size_t S = (size_t)ls.n_slots, R = S * (size_t)(ls.draft + 1);
+  int* x = e->lints.p + 16 + 9 * S + S * (size_t)ls.cap;
+  return DraftInts{x, x + R, x + 2 * R, x + 3 * R, x + 3 * R + S, x + 3 * R + 2 * S, x + 3 * R + 3 * S, x + 3 * R + 3 * S + S * (size_t)ls.cap};
+}
 int session_check(rk_engine* e, const char* who) {
   if (!e) return RK_ERR_INVALID;
   if (e->family != 1) return fail(e, RK_ERR_STATE, "%s called on a T5 engine", who);
@@ -3159,7 +3234,9 @@ int session_read_back(rk_engine* e, hipStream_t st) {
 }
 }  // namespace
 
-int rk_llama_session_open(rk_engine* e, int n_slots, int max_len, int max_new_cap, const int32_t* eos_ids, int n_eos, int pad_id) {
+// draft = Kd > 0 (rk_llama_session_open_draft): Kd extra rows per slot and step, fed with drafted tokens; see the drafting block below
+static int session_open(rk_engine* e, int n_slots, int max_len, int max_new_cap, const int32_t* eos_ids, int n_eos, int pad_id,
+                        int draft, int ngram_min, int ngram_max) {
   if (!e) return RK_ERR_INVALID;
   if (e->family != 1) return fail(e, RK_ERR_STATE, "rk_llama_session_open called on a T5 engine");
   if (!e->finalized) return fail(e, RK_ERR_STATE, "engine not finalized");
@@ -3167,17 +3244,21 @@ int rk_llama_session_open(rk_engine* e, int n_slots, int max_len, int max_new_ca
   const rk_llama_desc& l = e->ld;
   if (n_slots <= 0 || max_len <= 1 || max_new_cap <= 0) return fail(e, RK_ERR_INVALID, "n_slots, max_new_cap must be positive and max_len > 1 (got %d, %d, %d)", n_slots, max_new_cap, max_len);
   if (n_slots > l.max_seqs) return fail(e, RK_ERR_CAPACITY, "n_slots %d > max_seqs %d", n_slots, l.max_seqs);
+  if (draft && e->samp.on()) return fail(e, RK_ERR_STATE, "rk_llama_session_open_draft while sampling is on: drafting is lossless for greedy decoding only (rk_llama_set_sampling(0, ...) first, or draft = 0)");
+  if (draft && (long)n_slots * (draft + 1) > l.max_seqs)
+    return fail(e, RK_ERR_CAPACITY, "n_slots %d x (draft %d + 1) = %ld step rows > max_seqs %d (the step's activation rows)", n_slots, draft, (long)n_slots * (draft + 1), l.max_seqs);
   if (max_len > l.max_tokens) return fail(e, RK_ERR_CAPACITY, "max_len %d > max_tokens %d (the rotary tables end there)", max_len, l.max_tokens);
   if (n_eos < 0 || n_eos > 8 || (n_eos > 0 && !eos_ids)) return fail(e, RK_ERR_INVALID, "n_eos must be in 0..8 (got %d)", n_eos);
   int rc;
   if ((rc = check_ids(e, eos_ids, n_eos, "eos")) || (rc = check_ids(e, &pad_id, 1, "pad"))) return rc;
   if ((rc = set_device(e))) return rc;
-  const size_t S = (size_t)n_slots, n_ints = 16 + 9 * S + S * (size_t)max_new_cap;
-  if ((rc = ensure_amax(e, S))) return rc;
-  if ((rc = ensure_llama_gen(e, n_slots, max_len, n_ints))) return rc;
+  const size_t S = (size_t)n_slots, G1 = (size_t)draft + 1, n_ints = session_n_ints(n_slots, max_new_cap, max_len, draft);
+  if ((rc = ensure_amax(e, S * G1))) return rc;
+  if ((rc = ensure_llama_gen(e, n_slots, max_len, n_ints, (int)(S * G1)))) return rc;
   if (e->samp.on() && (rc = ensure_sample_head(e, S))) return rc;
   auto& ls = e->ls;
   ls.n_slots = n_slots; ls.max_len = max_len; ls.cap = max_new_cap; ls.seen = 0;
+  ls.draft = draft; ls.ngram_min = ngram_min; ls.ngram_max = ngram_max; ls.steps = 0; ls.tokens = 0;
   ls.sampled = e->samp.on(); ls.seeds.assign(S, 0);          // latched: rk_llama_set_sampling is refused until the close
   ls.busy.assign(S, 0); ls.told.assign(S, 0); ls.len.assign(S, 0); ls.max_new.assign(S, 0); ls.col.assign(S, 0); ls.done.assign(S, 1);
   std::vector<int> init(n_ints, 0);                        // every slot idle: done, position 0, pad as its next id
@@ -3185,11 +3266,39 @@ int rk_llama_session_open(rk_engine* e, int n_slots, int max_len, int max_new_ca
   for (int k = 0; k < n_eos; ++k) init[8 + k] = eos_ids[k];
   for (size_t b = 0; b < S; ++b) { init[16 + 3 * S + b] = 1; init[16 + 5 * S + b] = pad_id; }
   for (size_t k = 0; k < S * (size_t)max_new_cap; ++k) init[16 + 9 * S + k] = pad_id;
+  if (draft) {                                             // every row feeds pad at position 0; row 0 of a slot is live, no table
+    init[5] = ngram_min; init[6] = ngram_max;
+    const size_t x = 16 + 9 * S + S * (size_t)max_new_cap, R = S * G1;
+    for (size_t r = 0; r < R; ++r) { init[x + r] = pad_id; init[x + 2 * R + r] = r % G1 == 0; }
+    for (size_t b = 0; b < S; ++b) init[x + 3 * R + 2 * S + b] = -1;
+    for (size_t k = 0; k < S * (size_t)max_new_cap + S * (size_t)max_len; ++k) init[x + 3 * R + 3 * S + k] = pad_id;
+  }
   hipStream_t st = e->slots[0].se;
   HIPCHK(e, hipStreamSynchronize(st));
   HIPCHK(e, hipMemcpy(e->lints.p, init.data(), n_ints * sizeof(int), hipMemcpyHostToDevice));
   ls.open = true;
   return RK_OK;
+}
+
+int rk_llama_session_open(rk_engine* e, int n_slots, int max_len, int max_new_cap, const int32_t* eos_ids, int n_eos, int pad_id) {
+  return session_open(e, n_slots, max_len, max_new_cap, eos_ids, n_eos, pad_id, 0, 1, 1);
+}
+
+// ---- drafting by prompt lookup: the same tokens in fewer steps ----
+// A session opened with draft = Kd in 1..7 runs G1 = Kd + 1 rows per slot and step: row (s, 0) is the plain session's row, row (s, j)
+// feeds draft token d_j at the next position.  A row's bits follow from its own tokens and position and the key a row leaves in the
+// cache is the one any other route writes for that token, so the arg-max of row j IS the plain session's token wherever the drafts
+// in front of it were right: llama_session_advance_draft_kernel accepts exactly those, and the tokens of a request are bit for bit
+// the plain session's - only the number of steps differs.  Keys a rejected row left beyond the accepted position are overwritten
+// by the rows that get there before any row reads them (a row reads keys <= its own position, all written in this step or before
+// by accepted rows).  The drafts come from draft_lookup_kernel (n-gram lookup in the slot's own prompt and output).
+int rk_llama_session_open_draft(rk_engine* e, int n_slots, int max_len, int max_new_cap, const int32_t* eos_ids, int n_eos, int pad_id,
+                                int draft, int ngram_min, int ngram_max) {
+  if (!e) return RK_ERR_INVALID;
+  if (draft < 0 || draft > 7) return fail(e, RK_ERR_INVALID, "draft must be in 0..7 extra rows per slot (got %d)", draft);
+  if (ngram_min < 1 || ngram_max > 8 || ngram_min > ngram_max)
+    return fail(e, RK_ERR_INVALID, "ngram_min / ngram_max must satisfy 1 <= min <= max <= 8 (got %d, %d)", ngram_min, ngram_max);
+  return session_open(e, n_slots, max_len, max_new_cap, eos_ids, n_eos, pad_id, draft, ngram_min, ngram_max);
 }
 
 // seeds: null from rk_llama_session_admit, the prompts' seeds from rk_llama_session_admit_sampled; which of the two a session takes
@@ -3199,6 +3308,7 @@ static int session_admit(rk_engine* e, const int32_t* tokens, const int32_t* seq
   int rc = session_check(e, who);
   if (rc) return rc;
   auto& ls = e->ls;
+  if (seeds && ls.draft) return fail(e, RK_ERR_STATE, "%s on a drafting session (rk_llama_session_open_draft): drafting decodes greedily, admit with rk_llama_session_admit", who);
   if (seeds && !ls.sampled) return fail(e, RK_ERR_STATE, "%s: the session was opened with sampling off (rk_llama_set_sampling before rk_llama_session_open)", who);
   if (!seeds && ls.sampled) return fail(e, RK_ERR_STATE, "%s: the session was opened with sampling on: every admit is rk_llama_session_admit_sampled", who);
   if (!tokens || !seq_offsets || !slots || !max_new || n <= 0) return fail(e, RK_ERR_INVALID, "empty admit (n=%d)", n);
@@ -3236,7 +3346,13 @@ static int session_admit(rk_engine* e, const int32_t* tokens, const int32_t* seq
                    : head_sample(e, st, sl.dlast, n, e->ld.hidden, e->ld.vocab, e->samp, d.admit, e->d_pos, sl.idx.d[IX_LAST_ROWS], sl.d_argmax))) return rc;
   {
     Bracket br(e, st, PC_OTHER, 0, 0);
-    launch_session_advance(st, sl.d_argmax, d.st, d.len, d.col, d.max_new, d.done, d.pos, d.out, d.next, ls.n_slots, d.admit, n);
+    if (!ls.draft) launch_session_advance(st, sl.d_argmax, d.st, d.len, d.col, d.max_new, d.done, d.pos, d.out, d.next, ls.n_slots, d.admit, n);
+    else {                                                 // the prompts' ids and offsets are the prefill's device copies
+      const DraftInts x = session_draft_ints(e);
+      launch_session_advance_draft(st, sl.d_argmax, d.st, d.len, d.col, d.max_new, d.done, d.out, ls.n_slots, d.admit, n, ls.draft + 1, x,
+                                   sl.d_tokens, sl.d_seq_off);
+      launch_draft_lookup(st, d.st, d.len, d.col, d.max_new, d.done, ls.n_slots, ls.draft + 1, x);
+    }
   }
   for (int b = 0; b < n; ++b) { const int s = slots[b]; ls.busy[s] = 1; ls.told[s] = 0; ls.len[s] = adm[n + b]; ls.max_new[s] = max_new[b]; }
   return session_read_back(e, st);
@@ -3265,7 +3381,18 @@ int rk_llama_session_run(rk_engine* e, int max_steps, int32_t* out_finished, int
   for (int b = 0; b < ls.n_slots; ++b) if (ls.busy[b] && !ls.done[b]) live = std::max(live, ls.max_new[b] - ls.col[b]);
   int steps = 0;
   if (!untold() && live > 0 && max_steps > 0) {
+    const int G1 = ls.draft + 1;
+    auto draft_step = [&]() -> int {                       // G1 rows per slot: step, head, accept, propose
+      const DraftInts x = session_draft_ints(e);
+      int r = llama_step_rows(e, st, ls.n_slots * G1, ls.max_len, x.rnext, x.rpos, G1, x.rlive);
+      if (r || (r = head_argmax(e, st, sl.dlast, ls.n_slots * G1, e->ld.hidden, e->ld.vocab, sl.d_argmax))) return r;
+      Bracket br(e, st, PC_OTHER, 0, 0);
+      launch_session_advance_draft(st, sl.d_argmax, d.st, d.len, d.col, d.max_new, d.done, d.out, ls.n_slots, nullptr, 0, G1, x, nullptr, nullptr);
+      launch_draft_lookup(st, d.st, d.len, d.col, d.max_new, d.done, ls.n_slots, G1, x);
+      return RK_OK;
+    };
     auto step = [&]() -> int {
+      if (ls.draft) return draft_step();
       int r = llama_step_rows(e, st, ls.n_slots, ls.max_len, d.next, d.pos);
       if (r || (r = !ls.sampled ? head_argmax(e, st, sl.dlast, ls.n_slots, e->ld.hidden, e->ld.vocab, sl.d_argmax)
                                 : head_sample(e, st, sl.dlast, ls.n_slots, e->ld.hidden, e->ld.vocab, e->samp, nullptr, d.pos, nullptr, sl.d_argmax))) return r;
@@ -3273,7 +3400,8 @@ int rk_llama_session_run(rk_engine* e, int max_steps, int32_t* out_finished, int
       launch_session_advance(st, sl.d_argmax, d.st, d.len, d.col, d.max_new, d.done, d.pos, d.out, d.next, ls.n_slots, nullptr, 0);
       return RK_OK;
     };
-    const std::vector<int> key = ls.sampled ? std::vector<int>{GK_LLAMA_SESSION_STEP_SAMPLED, 0, ls.n_slots, ls.max_len, ls.cap, e->logits_gen, e->lkv_gen}
+    const std::vector<int> key = ls.draft ? std::vector<int>{GK_LLAMA_SESSION_STEP_DRAFT, 0, ls.n_slots, ls.max_len, ls.cap, e->amax_gen, e->lkv_gen, ls.draft}
+                               : ls.sampled ? std::vector<int>{GK_LLAMA_SESSION_STEP_SAMPLED, 0, ls.n_slots, ls.max_len, ls.cap, e->logits_gen, e->lkv_gen}
                                             : std::vector<int>{GK_LLAMA_SESSION_STEP, 0, ls.n_slots, ls.max_len, ls.cap, e->amax_gen, e->lkv_gen};
     int* pin = e->gen_pin;
     const int limit = std::min(max_steps, live);
@@ -3288,8 +3416,12 @@ int rk_llama_session_run(rk_engine* e, int max_steps, int32_t* out_finished, int
         stop = pin[(c - 1) & 1] != ls.seen;
       }
     }
-    sl.n_seq = ls.n_slots;                                 // rk_debug_read("llama_last"): the step's final rows
+    sl.n_seq = ls.n_slots * G1;                            // rk_debug_read("llama_last"): the step's final rows
+    long long before = 0, after = 0;
+    for (int b = 0; b < ls.n_slots; ++b) before += ls.col[b];
     RC(session_read_back(e, st));
+    for (int b = 0; b < ls.n_slots; ++b) after += ls.col[b];
+    ls.steps += steps; ls.tokens += after - before;        // rk_llama_session_stats
   }
   int nf = 0;
   for (int b = 0; b < ls.n_slots; ++b)
@@ -3311,9 +3443,53 @@ int rk_llama_session_read(rk_engine* e, int slot, int32_t* out_tokens, int cap, 
   const SessionInts d = session_ints(e);
   HIPCHK(e, hipMemcpy(out_tokens, d.out + (size_t)slot * ls.cap, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
   const int zero = 0;                                      // idle again: one key chunk of attention per step
-  HIPCHK(e, hipMemcpy(d.pos + slot, &zero, sizeof(int), hipMemcpyHostToDevice));
+  HIPCHK(e, hipMemcpy(ls.draft ? session_draft_ints(e).rpos + (size_t)slot * (ls.draft + 1) : d.pos + slot, &zero, sizeof(int), hipMemcpyHostToDevice));
   *out_n = n;
   ls.busy[slot] = 0; ls.told[slot] = 0;
+  return RK_OK;
+}
+
+// steps issued by rk_llama_session_run since the open and the tokens they emitted (the admits' first tokens not counted); per slot
+// (null: not wanted) the steps its current request was active in and its output column.  The host mirror, and for a drafting
+// session's slot steps one read of the device counters: the stream is idle between two session calls.
+int rk_llama_session_stats(rk_engine* e, int64_t* out_steps, int64_t* out_tokens, int32_t* out_slot_steps, int32_t* out_slot_cols) {
+  int rc = session_check(e, "rk_llama_session_stats");
+  if (rc) return rc;
+  auto& ls = e->ls;
+  if (out_steps) *out_steps = ls.steps;
+  if (out_tokens) *out_tokens = ls.tokens;
+  if (out_slot_cols) for (int b = 0; b < ls.n_slots; ++b) out_slot_cols[b] = ls.busy[b] ? ls.col[b] : 0;
+  if (out_slot_steps) {
+    if (ls.draft) HIPCHK(e, hipMemcpy(out_slot_steps, session_draft_ints(e).nstep, (size_t)ls.n_slots * sizeof(int), hipMemcpyDeviceToHost));
+    for (int b = 0; b < ls.n_slots; ++b) {
+      if (!ls.busy[b]) out_slot_steps[b] = 0;
+      else if (!ls.draft) out_slot_steps[b] = ls.col[b] - 1;   // one token per step behind the admit's
+    }
+  }
+  return RK_OK;
+}
+
+// debug (tests, tools/bench_llama_draft.py): the slot's proposer takes its drafts from `tokens` [n], indexed by output column
+// (d_j = tokens[col + j - 1]: the continuation a caller expects), in place of the lookup - acceptance becomes a function of the
+// table whatever a toy model emits.  n = 0 with tokens = null: back to the lookup.  In force from the slot's next admit or step.
+int rk_debug_session_drafts(rk_engine* e, int slot, const int32_t* tokens, int n) {
+  int rc = session_check(e, "rk_debug_session_drafts");
+  if (rc) return rc;
+  auto& ls = e->ls;
+  if (!ls.draft) return fail(e, RK_ERR_STATE, "rk_debug_session_drafts on a session without drafting (rk_llama_session_open_draft)");
+  if (slot < 0 || slot >= ls.n_slots) return fail(e, RK_ERR_INVALID, "slot %d out of range (the session has %d)", slot, ls.n_slots);
+  if (n < 0 || n > ls.cap || (n > 0 && !tokens)) return fail(e, RK_ERR_CAPACITY, "a draft table holds 0..max_new_cap = %d tokens (got %d)", ls.cap, n);
+  if ((rc = check_ids(e, tokens, n, "draft"))) return rc;
+  const DraftInts x = session_draft_ints(e);
+  const SessionInts d = session_ints(e);
+  hipStream_t st = e->slots[0].se;
+  const int tabn = tokens ? n : -1;
+  HIPCHK(e, hipStreamSynchronize(st));
+  if (n > 0) HIPCHK(e, hipMemcpy(x.tab + (size_t)slot * ls.cap, tokens, (size_t)n * sizeof(int), hipMemcpyHostToDevice));
+  HIPCHK(e, hipMemcpy(x.tabn + slot, &tabn, sizeof(int), hipMemcpyHostToDevice));
+  launch_draft_lookup(st, d.st, d.len, d.col, d.max_new, d.done, ls.n_slots, ls.draft + 1, x);   // the next step's rows, by the new table
+  HIPCHK(e, hipStreamSynchronize(st));
+  HIPCHK(e, hipGetLastError());
   return RK_OK;
 }
 

@@ -173,6 +173,9 @@ ABI = {
     "rk_llama_session_run": (C.c_int, [C.c_void_p, C.c_int, _i32p, _i32p, _i32p]),
     "rk_llama_session_read": (C.c_int, [C.c_void_p, C.c_int, _i32p, C.c_int, _i32p]),
     "rk_llama_session_close": (C.c_int, [C.c_void_p]),
+    "rk_llama_session_open_draft": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, _i32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "rk_llama_session_stats": (C.c_int, [C.c_void_p, _P(C.c_int64), _P(C.c_int64), _i32p, _i32p]),
+    "rk_debug_session_drafts": (C.c_int, [C.c_void_p, C.c_int, _i32p, C.c_int]),
     "rk_comm_unique_id": (C.c_int, [_P(C.c_uint8), C.c_int]),
     "rk_comm_init": (C.c_int, [C.c_void_p, _P(C.c_uint8), C.c_int, C.c_int, C.c_int, C.c_int]),
     "rk_comm_world": (C.c_int, [C.c_void_p, _i32p, _i32p]),
@@ -979,23 +982,32 @@ class RkLlamaEngine(RkEngine):
                                              out.ctypes.data_as(_i32p), C.byref(steps)))
         return out, int(steps.value)
 
-    def session(self, n_slots: int, max_len: int, max_new_cap: int, eos_ids: Sequence[int], pad_id: int) -> "LlamaSession":
+    def session(self, n_slots: int, max_len: int, max_new_cap: int, eos_ids: Sequence[int], pad_id: int,
+                draft: int = 0, ngram: Tuple[int, int] = (1, 3)) -> "LlamaSession":
         """A decoding session (rk_llama_session_*): `n_slots` cache slots of `max_len` positions, prompts admitted into free
         slots while the others decode.  A context manager; one per engine, and generate / greedy1 / last_logits are refused
-        while it is open."""
-        return LlamaSession(self, n_slots, max_len, max_new_cap, eos_ids, pad_id)
+        while it is open.  draft = Kd in 1..7 (rk_llama_session_open_draft): Kd extra rows per slot and step fed with tokens
+        drafted by n-gram lookup (ngram = (min, max) lengths) in the request's own prompt and output - the same tokens in fewer
+        steps; n_slots * (Kd + 1) <= max_seqs.  draft = 0 launches exactly what it always did."""
+        return LlamaSession(self, n_slots, max_len, max_new_cap, eos_ids, pad_id, draft=draft, ngram=ngram)
 
 
 class LlamaSession:
     """The five session calls of one RkLlamaEngine.  `busy` is the set of slots that hold a request (decoding, or finished and
     not yet read)."""
 
-    def __init__(self, eng: RkLlamaEngine, n_slots: int, max_len: int, max_new_cap: int, eos_ids: Sequence[int], pad_id: int):
+    def __init__(self, eng: RkLlamaEngine, n_slots: int, max_len: int, max_new_cap: int, eos_ids: Sequence[int], pad_id: int,
+                 draft: int = 0, ngram: Tuple[int, int] = (1, 3)):
         self.eng, self.n_slots, self.max_len, self.max_new_cap = eng, int(n_slots), int(max_len), int(max_new_cap)
+        self.draft, self.ngram = int(draft), (int(ngram[0]), int(ngram[1]))
         eos = _i32(list(eos_ids))
         self.is_open = False
-        eng._chk(eng.lib.rk_llama_session_open(eng.h, self.n_slots, self.max_len, self.max_new_cap, eos.ctypes.data_as(_i32p),
-                                               len(eos), int(pad_id)))
+        if self.draft == 0:                              # the plain entry point, as ever
+            eng._chk(eng.lib.rk_llama_session_open(eng.h, self.n_slots, self.max_len, self.max_new_cap, eos.ctypes.data_as(_i32p),
+                                                   len(eos), int(pad_id)))
+        else:
+            eng._chk(eng.lib.rk_llama_session_open_draft(eng.h, self.n_slots, self.max_len, self.max_new_cap, eos.ctypes.data_as(_i32p),
+                                                         len(eos), int(pad_id), self.draft, self.ngram[0], self.ngram[1]))
         self.is_open = True
         self.busy = set()
         self.steps = 0                                   # steps issued so far (every step decodes all n_slots rows)
@@ -1040,6 +1052,23 @@ class LlamaSession:
         self.eng._chk(self.eng.lib.rk_llama_session_run(self.eng.h, int(max_steps), fin.ctypes.data_as(_i32p), C.byref(n), C.byref(steps)))
         self.steps += int(steps.value)
         return [int(s) for s in fin[:n.value]], int(steps.value)
+
+    def stats(self) -> dict:
+        """rk_llama_session_stats: steps issued by run() since the open, the tokens those steps emitted, and per slot the steps its
+        current request was active in and its output column."""
+        st, tk = C.c_int64(0), C.c_int64(0)
+        ss, sc = np.zeros(self.n_slots, dtype=np.int32), np.zeros(self.n_slots, dtype=np.int32)
+        self.eng._chk(self.eng.lib.rk_llama_session_stats(self.eng.h, C.byref(st), C.byref(tk), ss.ctypes.data_as(_i32p), sc.ctypes.data_as(_i32p)))
+        return {"steps": int(st.value), "tokens": int(tk.value), "slot_steps": ss, "slot_cols": sc}
+
+    def set_drafts(self, slot: int, tokens: Optional[Sequence[int]]) -> None:
+        """debug (rk_debug_session_drafts): the slot's drafts come from this continuation table, indexed by output column, in place
+        of the lookup; None: back to the lookup."""
+        if tokens is None:
+            self.eng._chk(self.eng.lib.rk_debug_session_drafts(self.eng.h, int(slot), None, 0))
+            return
+        t = _i32(list(tokens))
+        self.eng._chk(self.eng.lib.rk_debug_session_drafts(self.eng.h, int(slot), t.ctypes.data_as(_i32p), len(t)))
 
     def read(self, slot: int) -> np.ndarray:
         """The finished slot's new tokens (its EOS included); the slot is free afterwards."""

@@ -571,6 +571,36 @@ def weight_dtype_kw(weight_dtype) -> dict:
     return {} if weight_dtype == "fp16" else {"weight_dtype": weight_dtype}
 
 
+MAX_DRAFT_TOKENS = 7
+
+
+def draft_tokens_kw(draft_tokens) -> dict:
+    """The keyword a caller adds to open_pool: none for 0 (the calls of a default ranker stay what they were)."""
+    try:
+        n = int(draft_tokens)
+    except (TypeError, ValueError):
+        n = -1
+    if n != draft_tokens or not 0 <= n <= MAX_DRAFT_TOKENS:
+        raise ValueError(f"draft_tokens must be an integer in 0..{MAX_DRAFT_TOKENS} (got {draft_tokens!r})")
+    return {} if n == 0 else {"draft_tokens": n}
+
+
+def generate_drafted(runtime, seqs, max_new, eos_ids, pad_id, draft_tokens) -> np.ndarray:
+    """`runtime.generate`'s [B, max_new] rows (-1 behind a row's last token) decoded through a drafting pool of as many slots as there
+    are prompts (one prompt: ONE slot, where the step has the most room for draft rows).  The tokens are generate's by the
+    session's contract; only the number of steps differs."""
+    kw = draft_tokens_kw(draft_tokens)
+    n_slots = max(1, min(len(seqs), int(runtime.max_seqs) // (int(draft_tokens) + 1)))
+    out = np.full((len(seqs), int(max_new)), -1, dtype=np.int32)
+    with runtime.open_pool(max_new_cap=int(max_new), eos_ids=list(eos_ids), pad_id=int(pad_id), n_slots=n_slots, **kw) as pool:
+        for b, ids in enumerate(seqs):
+            pool.submit(b, ids, max_new)
+        while pool.pending():
+            for b, tokens in pool.wait():
+                out[b, :len(tokens)] = tokens
+    return out
+
+
 class LlamaRuntime:
     """Decoder-only (Llama family) counterpart of T5Runtime: checkpoint directory -> rk_llama_* engine.  Replaces
     `AutoModelForCausalLM.from_pretrained(..., device_map='auto', torch_dtype=fp16)` of ref: llmrankers/setwise.py:65-69."""
@@ -656,16 +686,19 @@ class LlamaRuntime:
                 raise ValueError(f"a prompt of {len(s)} tokens + {max_new} new ones exceeds the engine capacity {self.max_tokens}")
         return self._chunks(seqs)
 
-    def open_pool(self, max_new_cap, eos_ids, pad_id, n_slots=None) -> "DecodePool":
+    def open_pool(self, max_new_cap, eos_ids, pad_id, n_slots=None, draft_tokens=0) -> "DecodePool":
         """A pool of `n_slots` (default: max_seqs) decoding slots over one engine session: requests are queued with `submit`,
         `wait` returns completed ones while the rest keep decoding, a finished row's slot goes to the next request.  A request's
         tokens are what `generate` gives for it alone.  A context manager; the engine's other calls are refused until it is
-        closed."""
-        n_slots = self.max_seqs if n_slots is None else int(n_slots)
-        if not 0 < n_slots <= self.max_seqs:
-            raise ValueError(f"n_slots {n_slots} outside 1..max_seqs {self.max_seqs}")
+        closed.  draft_tokens = Kd in 1..7: a drafting session (RkLlamaEngine.session(draft=Kd): prompt-lookup drafts, the same
+        tokens in fewer steps); every slot takes Kd + 1 of the step's max_seqs rows, so the default is max_seqs // (Kd + 1) slots."""
+        draft = draft_tokens_kw(draft_tokens).get("draft_tokens", 0)
+        n_slots = max(1, self.max_seqs // (draft + 1)) if n_slots is None else int(n_slots)
+        if not 0 < n_slots * (draft + 1) <= self.max_seqs:
+            raise ValueError(f"n_slots {n_slots}" + (f" x (draft_tokens {draft} + 1)" if draft else "") + f" outside 1..max_seqs {self.max_seqs}")
         eos_ids, pad_id = list(eos_ids), int(pad_id)
-        return DecodePool(lambda max_len: self.engine.session(n_slots, max_len, int(max_new_cap), eos_ids, pad_id),
+        kw = {"draft": draft} if draft else {}               # (without drafting: the call it always was)
+        return DecodePool(lambda max_len: self.engine.session(n_slots, max_len, int(max_new_cap), eos_ids, pad_id, **kw),
                           n_slots, self.max_tokens, int(max_new_cap))
 
     def greedy1(self, seqs) -> np.ndarray:
@@ -727,6 +760,12 @@ class DecodePool:
         if len(ids) + max_new > self.max_tokens:
             raise ValueError(f"request {key!r}: a prompt of {len(ids)} tokens + {max_new} new ones exceeds the engine capacity {self.max_tokens}")
         self._queue.append((key, ids, max_new, seed))
+
+    @property
+    def tokens_per_step(self) -> float:
+        """new tokens of the completed requests per step issued so far (their first tokens, which the admits' prefills produce,
+        included): about the number of busy slots for a plain session, more where drafts are accepted; 0.0 before the first step"""
+        return self.tokens_out / self.steps if self.steps else 0.0
 
     def pending(self) -> int:
         """requests queued or decoding"""

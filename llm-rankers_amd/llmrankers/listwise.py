@@ -333,6 +333,22 @@ class R1ListwiseLlmRanker(ListwiseLlmRanker):
             made[cls, weight_dtype] = type(cls.__name__, (cls,), {"weight_dtype": weight_dtype})
         return made[cls, weight_dtype]
 
+    # Drafting by prompt lookup (LlamaRuntime.open_pool's draft_tokens; lossless, opt-in: the same tokens in fewer steps):
+    # R1ListwiseLlmRanker.with_draft_tokens(3)(model, tokenizer, prompt, ...).  With it on, the windows of a call decode through a
+    # drafting pool instead of rk_llama_generate.
+    draft_tokens = 0
+
+    @classmethod
+    def with_draft_tokens(cls, draft_tokens):
+        from ._runtime import draft_tokens_kw
+        draft_tokens_kw(draft_tokens)                                  # ValueError outside 0..7
+        if int(draft_tokens) == cls.draft_tokens:
+            return cls
+        made = _WEIGHT_DTYPE_CLASSES
+        if (cls, "draft_tokens", int(draft_tokens)) not in made:
+            made[cls, "draft_tokens", int(draft_tokens)] = type(cls.__name__, (cls,), {"draft_tokens": int(draft_tokens)})
+        return made[cls, "draft_tokens", int(draft_tokens)]
+
     def __init__(self, model_name_or_path, tokenizer_name_or_path, prompt, window_size, step_size, lora_path=None,
                  scoring='generation', num_repeat=1, cache_dir=None, device="cuda", max_new_tokens=2048):
         from transformers import AutoTokenizer
@@ -393,7 +409,11 @@ class R1ListwiseLlmRanker(ListwiseLlmRanker):
         ids = [self._chat_ids(q, docs) for q, docs in zip(queries, doc_lists)]
         gen = self.llm.generation
         eos_ids = list(gen["eos_token_ids"])
-        rows = np.asarray(self.llm.generate(ids, self.max_new_tokens, eos_ids, int(gen["pad_token_id"])))
+        if self.draft_tokens and hasattr(self.llm, "open_pool"):           # the same tokens through a drafting pool
+            from ._runtime import generate_drafted
+            rows = generate_drafted(self.llm, ids, self.max_new_tokens, eos_ids, int(gen["pad_token_id"]), self.draft_tokens)
+        else:
+            rows = np.asarray(self.llm.generate(ids, self.max_new_tokens, eos_ids, int(gen["pad_token_id"])))
         outs, completion = [], []
         for q, docs, row in zip(queries, doc_lists, rows):
             new = [int(t) for t in row if t >= 0]

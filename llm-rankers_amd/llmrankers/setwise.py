@@ -438,6 +438,22 @@ class RankR1SetwiseLlmRanker(SetwiseLlmRanker):
             made[cls, weight_dtype] = type(cls.__name__, (cls,), {"weight_dtype": weight_dtype})
         return made[cls, weight_dtype]
 
+    # Drafting by prompt lookup (LlamaRuntime.open_pool's draft_tokens; lossless, opt-in: the same tokens in fewer steps).  Like
+    # weight_dtype the option is the class's: RankR1SetwiseLlmRanker.with_draft_tokens(3)(model, prompt_file, ...).  With it on,
+    # compare() decodes its prompts through a pool of one slot per prompt instead of rk_llama_generate.
+    draft_tokens = 0
+
+    @classmethod
+    def with_draft_tokens(cls, draft_tokens):
+        from ._runtime import draft_tokens_kw
+        draft_tokens_kw(draft_tokens)                                  # ValueError outside 0..7
+        if int(draft_tokens) == cls.draft_tokens:
+            return cls
+        made = _WEIGHT_DTYPE_CLASSES
+        if (cls, "draft_tokens", int(draft_tokens)) not in made:
+            made[cls, "draft_tokens", int(draft_tokens)] = type(cls.__name__, (cls,), {"draft_tokens": int(draft_tokens)})
+        return made[cls, "draft_tokens", int(draft_tokens)]
+
     def __init__(self, model_name_or_path, prompt_file, lora_name_or_path=None, tokenizer_name_or_path=None, num_child=19, k=10,
                  scoring='generation', method="heapsort", num_permutation=1, cache_dir=None, verbose=False, device="cuda",
                  max_new_tokens=2048):
@@ -492,7 +508,11 @@ class RankR1SetwiseLlmRanker(SetwiseLlmRanker):
         self.total_compare += 1 if self.num_permutation == 1 else self.num_permutation
         batch_ref, input_text, ids = self._compare_prompts(query, docs, rng)
         gen = self.llm.generation
-        rows = np.asarray(self.llm.generate(ids, self.max_new_tokens, list(gen["eos_token_ids"]), int(gen["pad_token_id"])))   # ONE engine call
+        if self.draft_tokens and hasattr(self.llm, "open_pool"):           # the same tokens through a drafting pool, one slot per prompt
+            from ._runtime import generate_drafted
+            rows = generate_drafted(self.llm, ids, self.max_new_tokens, list(gen["eos_token_ids"]), int(gen["pad_token_id"]), self.draft_tokens)
+        else:
+            rows = np.asarray(self.llm.generate(ids, self.max_new_tokens, list(gen["eos_token_ids"]), int(gen["pad_token_id"])))   # ONE engine call
         output, prompt_tokens, completion_tokens = self._compare_verdict(query, batch_ref, input_text, ids, rows, rng)
         self.total_prompt_tokens += prompt_tokens
         self.total_completion_tokens += completion_tokens
@@ -571,7 +591,9 @@ class RankR1SetwiseLlmRanker(SetwiseLlmRanker):
             for p, prompt in enumerate(ids):
                 pool.submit((q, p), prompt, self.max_new_tokens)
 
-        with self.llm.open_pool(max_new_cap=self.max_new_tokens, eos_ids=list(gen["eos_token_ids"]), pad_id=int(gen["pad_token_id"])) as pool:
+        from ._runtime import draft_tokens_kw
+        with self.llm.open_pool(max_new_cap=self.max_new_tokens, eos_ids=list(gen["eos_token_ids"]), pad_id=int(gen["pad_token_id"]),
+                                **draft_tokens_kw(self.draft_tokens)) as pool:
             for q in range(len(items)):
                 if chains[q]:
                     submit(pool, q)

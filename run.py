@@ -232,6 +232,10 @@ def build_ranker(args):
     # --weight_dtype: forwarded only when given (a run without the flag makes the calls it always made); the T5-only rankers refuse fp8
     wd = getattr(args.run, "weight_dtype", None)
     wd_kw = {} if wd is None else {"weight_dtype": wd}
+    # --draft_tokens: the two Rank-R1 rankers (--setwise / --listwise with --prompt_file); 0, the default, changes nothing
+    dt = int(getattr(args.run, "draft_tokens", 0) or 0)
+    if dt and not ((args.setwise or args.listwise) and getattr(args.run, "prompt_file", None)):
+        raise NotImplementedError("--draft_tokens serves the Rank-R1 rankers' long decodes: --setwise --prompt_file or --listwise --prompt_file")
     if args.pointwise:
         if wd == "fp8":
             raise NotImplementedError("--weight_dtype fp8 is not supported by the pointwise rankers: they serve T5 checkpoints, FP8 step "
@@ -248,6 +252,8 @@ def build_ranker(args):
             from llmrankers.setwise import RankR1SetwiseLlmRanker
             if wd is not None:                                   # (the two R1 constructors keep the reference's parameter lists)
                 RankR1SetwiseLlmRanker = RankR1SetwiseLlmRanker.with_weight_dtype(wd)
+            if dt:
+                RankR1SetwiseLlmRanker = RankR1SetwiseLlmRanker.with_draft_tokens(dt)
             return RankR1SetwiseLlmRanker(model_name_or_path=args.run.model_name_or_path, prompt_file=args.run.prompt_file,
                                           lora_name_or_path=args.run.lora_name_or_path,
                                           tokenizer_name_or_path=args.run.tokenizer_name_or_path, device=args.run.device,
@@ -281,6 +287,8 @@ def build_ranker(args):
             from llmrankers.listwise import R1ListwiseLlmRanker
             if wd is not None:
                 R1ListwiseLlmRanker = R1ListwiseLlmRanker.with_weight_dtype(wd)
+            if dt:
+                R1ListwiseLlmRanker = R1ListwiseLlmRanker.with_draft_tokens(dt)
             return R1ListwiseLlmRanker(model_name_or_path=args.run.model_name_or_path, tokenizer_name_or_path=args.run.tokenizer_name_or_path,
                                        prompt=args.run.prompt_file, window_size=args.listwise.window_size, step_size=args.listwise.step_size,
                                        lora_path=args.run.lora_name_or_path, num_repeat=args.listwise.num_repeat, cache_dir=args.run.cache_dir,
@@ -549,6 +557,9 @@ def build_parser():
     rp.add_argument("--weight_dtype", type=str, default=None, choices=["fp16", "fp8"],
                     help="Llama-family checkpoints: fp8 keeps the projections the decoding step streams as FP8 step weights (lossy: one "
                          "e4m3 rounding per weight; rankings can differ from fp16).  Default: fp16")
+    rp.add_argument("--draft_tokens", type=int, default=0, choices=range(0, 8), metavar="N",
+                    help="Rank-R1 rankers (--prompt_file): decode with N in 1..7 prompt-lookup draft tokens per step - the same tokens "
+                         "in fewer steps where the reasoning text repeats its prompt or itself.  Default 0: off")
     rp.add_argument("--cache_dir", type=str, default=None)
     rp.add_argument("--openai_key", type=str, default=None)
     rp.add_argument("--scoring", type=str, default="generation", choices=["generation", "likelihood"])
