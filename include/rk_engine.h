@@ -484,6 +484,13 @@ int rk_debug_gemm_chain(rk_engine* e, rk_debug_gemm_chain_call* call);
  *                        step's entry with the norm (out_kind 2; hd = 128, no window, no qkv_bias: RK_ERR_STATE otherwise).
  *                        On an engine with a sliding window W every call runs the windowed entries (out_kind 1, else 0): row b reads keys
  *                        max(0, pos[b] - W + 1) .. pos[b] and the cache below them is neither read into the result nor written.
+ *                        g1 / live (the LAST fields of the call, behind qk_norm / qk_eps; g1 = 0 or 1: the plain call, unchanged): a drafting
+ *                        session's step, plan_llama_dec_attn over the n_seq step rows and launch_llama_dec_attn_keys as llama_step_rows calls
+ *                        them.  n_seq = g1 x the cache's rows (cache = K [n_seq / g1][n_kv][P][hd] then V), step row b belongs to cache row
+ *                        b / g1 at pos[b]; live[n_seq]: 1 = the row's rotated key and its value are appended at pos[b] in front of the
+ *                        attention, 0 = a dead row (nothing written, its context unspecified).  Every row reads keys <= pos[b] of its cache
+ *                        row.  The same out_* fields.  g1 > 8, g1 < 0, n_seq not a multiple of g1 or live = null: RK_ERR_INVALID; the qk_norm /
+ *                        window / bias combinations as above.
  *   6 T5 cached step     the self-attention of rk_t5_generate's step, through the launcher run_decoder's cached branch calls: q = the step's
  *                        fused rows [n_seq, ldq] (q | k | v at columns 0 | 64 H | 128 H), cache [n_seq][P][2 x 64 H] (k | v per position),
  *                        pos: ONE value (the kernel reads one device word; outside [0, P): RK_ERR_INVALID, nothing launched), bias_lut;
@@ -520,6 +527,7 @@ typedef struct rk_debug_attn_call {
   int out_kind, out_tparam, out_grid[3], out_grid2[3], out_lds, out_staged, out_mfma, out_part, out_R, out_nch, out_skip_long,
       out_heads_per_wg, out_n_cu;
   const float* qk_norm; float qk_eps;
+  int g1; const int32_t* live;
 } rk_debug_attn_call;
 int rk_debug_attn(rk_engine* e, rk_debug_attn_call* call);
 /* debug: the WHOLE query-side cross-attention chain of one T5 decoder layer on host data (csrc/rk_engine.hip: struct XAttnChain ->
@@ -625,6 +633,32 @@ typedef struct rk_debug_rows_call {
   int out_grid[3], out_tparam, out_variant;
 } rk_debug_rows_call;
 int rk_debug_rows(rk_engine* e, rk_debug_rows_call* call);
+/* debug: the two state kernels of a DRAFTING session (csrc/misc_kernels.h: llama_session_advance_draft_kernel, the accept machine, and
+ * draft_lookup_kernel, the proposer) on host state, through launch_session_advance_draft and launch_draft_lookup in the order the
+ * session calls them; no kernel, grid rule or dispatch of its own.  Works on an engine of either family.
+ *   state[i]  the session's int arrays, each a device allocation of its own between sentinel bands (rk_debug_rows' out[i]: interior = the
+ *             initial state, all = n_steps x (band + bytes + band) bytes, the whole allocation after every step), in this order:
+ *             st[16] (finishes, pad, n_eos, max_len, cap, ngram_min, ngram_max, 0, eos[8]), len, col, max_new, done (all [n_slots]),
+ *             out [n_slots][cap], rnext, rpos, rlive (all [n_slots][g1]), dlen, nstep, tabn (all [n_slots]), tab [n_slots][cap],
+ *             hist [n_slots][max_len].  bytes is exactly the array's size.
+ *   script    i32 [n_steps][rec], rec = 4 + A + 3 max_admit + (max_admit + 1) + max_tokens, A = max(n_slots g1, max_admit); a record is
+ *             kind | n | slot | 0 | argmax[A] | admit[3 max_admit] | seq_off[max_admit + 1] | tokens[max_tokens]:
+ *             kind 0, a step: argmax[n_slots g1]; the accept machine without an admit list, then the proposer.
+ *             kind 1, an admit: n = n_admit in 0..max_admit, admit = slot[n] | len[n] | max_new[n] packed, prompt r = tokens[seq_off[r] ..
+ *                     seq_off[r] + len[r]), argmax[n_admit]; the accept machine with the list, then the proposer (session_admit's pair).
+ *             kind 2, a table change: tab[slot] = tokens[0, n) and tabn[slot] = n (n = -1: back to the lookup), then the proposer alone
+ *                     (rk_debug_session_drafts).
+ * Checked before anything is allocated or launched (RK_ERR_INVALID): n_eos <= 8, 1 <= ngram_min <= ngram_max <= 8, 1 <= g1 <= 8; for every
+ * active slot of the initial state and every entry of every admit len >= 1, 1 <= max_new <= cap, len + max_new <= max_len (initially
+ * also 0 <= col < max_new, 0 <= dlen < g1, tabn in -1..cap); a prompt inside the record's tokens; no slot twice in one admit; a table of
+ * at most min(cap, max_tokens) tokens for a slot in range.  An admitted slot id outside [0, n_slots) is allowed: the kernels skip it. */
+#define RK_DEBUG_DRAFT_ARRAYS 14
+typedef struct rk_debug_draft_steps_call {
+  int n_slots, g1, n_steps, max_admit, max_tokens;
+  const int32_t* script; int64_t script_ints;
+  rk_debug_rows_out state[RK_DEBUG_DRAFT_ARRAYS];
+} rk_debug_draft_steps_call;
+int rk_debug_draft_steps(rk_engine* e, rk_debug_draft_steps_call* call);
 /* measurement: average ms per launch of the engine's GEMM kernel at one shape (epi = 0 store f16, 1 residual f32,
  * 2 GEGLU, 3 ReLU, 4 store f32), random operands, `iters` back-to-back launches timed with HIP events */
 int rk_debug_gemm_bench(rk_engine* e, int M, int N, int K, int epi, int iters, float* out_ms);

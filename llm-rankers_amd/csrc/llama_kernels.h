@@ -577,10 +577,33 @@ struct LlamaDecAttnKeysArgs : LlamaDecAttnArgs {   // the drafting entries' argu
 };
 // The cache append of a drafting step, in front of each layer's attention: row b's rotated key and its value go to cache row
 // b / g1 at the row's position - formed by the helpers the step kernel forms `knew` / `vnew` with (rope_lane8 / bias_v8 / qkn_lane8,
-// on the lane mapping of attn_dec_cached_body: lane c of a key's D / 8 holds 8 dims), so the bytes are those a plain step writes.
+// on the lane mapping of attn_dec_cached_body: lane c of a key's D / 8 holds 8 dims; the bias-free 128-wide key by
+// rope_key128_fixed below, the step kernels' compiled form written out), so the bytes are those a plain step writes.
 // grid = rows; an item is (kv head, lane c).  A dead row (live[b] = 0) or a position outside the cache writes nothing.  QKN: the 8
 // lanes of an aligned group hold the items of one half of ONE head (D / 8 = 16 items per head) and the bound n_kv * 16 is a multiple
 // of 8, so a group enters and leaves the loop together and qkn_pairs' shuffles read active lanes only.
+// The bias-free 128-wide key in a FIXED form (no contraction left to the compiler): what the compiler in use makes of `knew` in every
+// bias-free attn_dec_cached_kernel<128, R> / _win_ instantiation - element 0 of the lane's eight as one fma over a rounded product,
+// lo = fma(cos, x1, -(sin x2)) and up = fma(sin, x1, cos x2), the other seven as two rounded products and an add.  Left to the
+// compiler, this kernel's copy of rope_lane8 came out with up = fma(cos, x2, sin x1) (rope128_kernel's form), one fp16 ulp away from
+// the plain step's key where the two roundings part: the cache of a drafting session was then not the plain session's
+// (tests/test_gpu_draft_attention.py: g1 plain steps leave the same cache, byte for byte).
+__device__ __forceinline__ half8 rope_key128_fixed(const half_t* row, int hd, int i0, bool hi, const float (&co)[8], const float (&si)[8]) {
+#pragma clang fp contract(off)
+  const half_t* head = row + (size_t)hd * 128;
+  const half8 a = *(const half8*)(head + i0), bb = *(const half8*)(head + 64 + i0);
+  half8 o;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const float x1 = (float)a[j], x2 = (float)bb[j];
+    float lo, up;
+    if (j == 0) { lo = __builtin_fmaf(co[j], x1, -(si[j] * x2)); up = __builtin_fmaf(si[j], x1, co[j] * x2); }
+    else { lo = x1 * co[j] - x2 * si[j]; up = x2 * co[j] + x1 * si[j]; }
+    o[j] = hi ? f2h_sat(up) : f2h_sat(lo);
+  }
+  return o;
+}
+
 template <int D, bool BIAS, bool QKN>
 __global__ __launch_bounds__(256) void kv_cache_append_kernel(LlamaDecAttnKeysArgs p) {
   constexpr int LK = D / 8, NL = D / 16;
@@ -599,6 +622,7 @@ __global__ __launch_bounds__(256) void kv_cache_append_kernel(LlamaDecAttnKeysAr
     for (int j = 0; j < 8; ++j) { co[j] = p.cos_t[(size_t)pos * (D / 2) + i0 + j]; si[j] = p.sin_t[(size_t)pos * (D / 2) + i0 + j]; }
     auto rotated = [&](int hd) {
       if constexpr (QKN) return qkn_lane8(row, p.qkn, p.qkn_eps, p.n_heads, hd, i0, hi, co, si);
+      else if constexpr (D == 128 && !BIAS) return rope_key128_fixed(row, hd, i0, hi, co, si);
       else return rope_lane8<D, BIAS>(row, p.bias, hd, i0, hi, co, si);
     };
     const half8 knew = rotated(p.n_heads + kvh);

@@ -4183,6 +4183,8 @@ int rk_debug_attn(rk_engine* e, rk_debug_attn_call* q) {
       for (int b = 0; b < B; ++b)
         if (q->pos[b] < 0 || q->pos[b] >= P || q->pos[b] >= q->max_pos) return fail(e, RK_ERR_INVALID, "debug attn: pos[%d] = %d outside the cache of %d / the tables of %d", b, q->pos[b], P, q->max_pos);
     }
+    if (q->g1 < 0 || q->g1 > 8 || (q->g1 > 1 && B % q->g1)) return fail(e, RK_ERR_INVALID, "debug attn: the drafting step takes g1 in 2..8 rows per cache row and n_seq a multiple of it (g1 = %d, n_seq = %d)", q->g1, B);
+    if (q->g1 > 1 && !planning && !q->live) return fail(e, RK_ERR_INVALID, "debug attn: the drafting step needs live[n_seq]");
     if (q->qk_norm && (hd != 128 || e->window > 0 || q->qkv_bias || !(q->qk_eps > 0.f)))
       return fail(e, RK_ERR_STATE, "debug attn: the step with the q / k head norm takes head_dim 128, no window, no qkv_bias and qk_eps > 0");
     lp = plan_llama_dec_attn(e, B, P, H, n_kv);
@@ -4270,7 +4272,8 @@ int rk_debug_attn(rk_engine* e, rk_debug_attn_call* q) {
     DBG_HIP(hipDeviceSynchronize());
     launch_dec_cached_step(e, st, AttnCachedArgs{qi, q->ldq, dC + c_band, P, I, dPos, oi, q->ldctx, dLut}, B, H, dTk, dTp);
   } else {
-    const size_t half_layer = (size_t)B * q->n_kv * q->P * hd, c_band = (size_t)band * hd;
+    const int g1 = q->g1 > 1 ? q->g1 : 1;                     // the drafting step: g1 step rows per cache row
+    const size_t half_layer = (size_t)(B / g1) * q->n_kv * q->P * hd, c_band = (size_t)band * hd;
     c_all = 2 * half_layer + 2 * c_band;
     dC = (half_t*)alloc(c_all * 2, RK_DEBUG_SENTINEL);
     int* dPos = (int*)up(q->pos, (size_t)B * 4);
@@ -4279,12 +4282,15 @@ int rk_debug_attn(rk_engine* e, rk_debug_attn_call* q) {
     float* dBias = q->qkv_bias ? (float*)up(q->qkv_bias, (size_t)(H + 2 * q->n_kv) * hd * 4) : nullptr;
     float* dQkn = q->qk_norm ? (float*)up(q->qk_norm, (size_t)2 * hd * 4) : nullptr;
     float* dPart = (float*)alloc((size_t)B * H * lp.nch * ldc_pstr(hd) * 4, RK_DEBUG_SENTINEL);
-    if (!dC || !dPos || !dCos || !dSin || (q->qkv_bias && !dBias) || (q->qk_norm && !dQkn) || !dPart) return done(fail(e, RK_ERR_HIP, "debug attn: device allocation or upload failed"));
+    int* dLive = g1 > 1 ? (int*)up(q->live, (size_t)B * 4) : nullptr;
+    if (!dC || !dPos || !dCos || !dSin || (q->qkv_bias && !dBias) || (q->qk_norm && !dQkn) || !dPart || (g1 > 1 && !dLive)) return done(fail(e, RK_ERR_HIP, "debug attn: device allocation or upload failed"));
     DBG_HIP(hipMemcpy(dC + c_band, q->cache, 2 * half_layer * 2, hipMemcpyHostToDevice));
     DBG_HIP(hipDeviceSynchronize());
     const float scale_log2e = (1.0f / std::sqrt((float)hd)) * 1.4426950408889634f;
     half_t* kc = dC + c_band;
-    launch_llama_dec_attn(e, st, lp, LlamaDecAttnArgs{qi, kc, kc + half_layer, dPos, dCos, dSin, dPart, oi, q->ldq, H, q->n_kv, q->P, lp.nch, scale_log2e, dBias, 0, dQkn, q->qk_eps}, B);
+    const LlamaDecAttnArgs aa{qi, kc, kc + half_layer, dPos, dCos, dSin, dPart, oi, q->ldq, H, q->n_kv, q->P, lp.nch, scale_log2e, dBias, 0, dQkn, q->qk_eps};
+    if (g1 == 1) launch_llama_dec_attn(e, st, lp, aa, B);
+    else launch_llama_dec_attn_keys(e, st, lp, LlamaDecAttnKeysArgs{aa, g1, dLive}, B);   // (llama_step_rows' branch)
   }
   DBG_HIP(hipStreamSynchronize(st));
   DBG_HIP(hipGetLastError());
@@ -4697,6 +4703,115 @@ int rk_debug_rows(rk_engine* e, rk_debug_rows_call* q) {
         const size_t all = (size_t)(q->out[i].bytes + 2 * q->out[i].band);
         DBG_HIP(hipMemcpy((char*)q->out[i].all + (size_t)s * all, dall[i], all, hipMemcpyDeviceToHost));
       }
+  }
+#undef DBG_HIP
+  return done(RK_OK);
+}
+
+// debug: a drafting session's accept machine and proposer on host state, one scripted launch group per step (include/rk_engine.h).
+// No kernel, grid rule or dispatch of its own: launch_session_advance_draft and launch_draft_lookup, in the order session_admit,
+// rk_llama_session_run's step and rk_debug_session_drafts call them.  Every extent the two kernels rely on is checked on the host
+// before anything is allocated.
+int rk_debug_draft_steps(rk_engine* e, rk_debug_draft_steps_call* q) {
+  if (!e || !q) return RK_ERR_INVALID;
+  int rc = set_device(e);
+  if (rc) return rc;
+  auto bad = [&](const char* what) { return fail(e, RK_ERR_INVALID, "debug draft steps: %s", what); };
+  const int S = q->n_slots, g1 = q->g1, n_steps = q->n_steps, MA = q->max_admit, MT = q->max_tokens;
+  if (S <= 0 || S > (1 << 16) || g1 < 1 || g1 > 8) return bad("n_slots in 1..65536 and g1 in 1..8");
+  if (n_steps < 1 || n_steps > 4096 || MA < 0 || MA > (1 << 16) || MT < 0 || MT > (1 << 20)) return bad("n_steps in 1..4096, max_admit, max_tokens");
+  const long A = std::max<long>((long)S * g1, MA), rec = 4 + A + 3L * MA + (MA + 1) + MT;
+  if (!q->script || q->script_ints < (int64_t)n_steps * rec) return bad("script of n_steps x (4 + max(n_slots g1, max_admit) + 3 max_admit + max_admit + 1 + max_tokens) ints");
+  auto state = [&](int i, long n) -> const int* { return (q->state[i].interior && n * 4 <= q->state[i].bytes) ? (const int*)q->state[i].interior : nullptr; };
+  const int* st0 = state(0, 16);
+  if (!st0) return bad("st of 16 ints");
+  const int n_eos = st0[2], max_len = st0[3], cap = st0[4], nmin = st0[5], nmax = st0[6];
+  if (n_eos < 0 || n_eos > 8) return bad("n_eos = st[2] in 0..8");
+  if (max_len < 1 || max_len > (1 << 20) || cap < 1 || cap > (1 << 16)) return bad("max_len = st[3] in 1..2^20, cap = st[4] in 1..65536");
+  if (nmin < 1 || nmin > nmax || nmax > 8) return bad("1 <= ngram_min = st[5] <= ngram_max = st[6] <= 8");
+  if ((long)S * max_len * 4 > (1L << 31)) return bad("hist beyond 2^31 bytes");
+  // st, len, col, max_new, done, out, rnext, rpos, rlive, dlen, nstep, tabn, tab, hist
+  const long need[RK_DEBUG_DRAFT_ARRAYS] = {16, S, S, S, S, (long)S * cap, (long)S * g1, (long)S * g1, (long)S * g1, S, S, S, (long)S * cap, (long)S * max_len};
+  for (int i = 0; i < RK_DEBUG_DRAFT_ARRAYS; ++i) {
+    const rk_debug_rows_out& b = q->state[i];
+    if (!b.interior || !b.all || b.band < 64 || b.band % 16 || b.band > (1 << 26) || need[i] * 4 != b.bytes)
+      return fail(e, RK_ERR_INVALID, "debug draft steps: state array %d has %ld bytes (%ld given) and needs interior, all and a band of 64 bytes or more (a multiple of 16)", i, need[i] * 4, (long)b.bytes);
+  }
+  {
+    const int *len = state(1, S), *col = state(2, S), *mn = state(3, S), *dn = state(4, S), *dlen = state(9, S), *tabn = state(11, S);
+    for (int s = 0; s < S; ++s) {
+      if (tabn[s] < -1 || tabn[s] > cap) return bad("tabn entry outside -1..cap");
+      if (dn[s]) continue;
+      if (len[s] < 1 || mn[s] < 1 || mn[s] > cap || (long)len[s] + mn[s] > max_len) return bad("an active slot needs len >= 1, 1 <= max_new <= cap and len + max_new <= max_len");
+      if (col[s] < 0 || col[s] >= mn[s]) return bad("an active slot's col must lie in [0, max_new)");
+      if (dlen[s] < 0 || dlen[s] >= g1) return bad("an active slot's dlen must lie in [0, g1)");
+    }
+  }
+  for (int s = 0; s < n_steps; ++s) {
+    const int* r = q->script + (size_t)s * rec;
+    const int kind = r[0], n = r[1];
+    if (kind == 0) continue;
+    if (kind == 1) {
+      if (n < 0 || n > MA) return bad("admit count outside 0..max_admit");
+      const int *adm = r + 4 + A, *so = adm + 3L * MA;
+      std::vector<char> taken(S, 0);
+      for (int b = 0; b < n; ++b) {
+        const int slot = adm[b], L = adm[n + b], m = adm[2 * n + b];
+        if (L < 1) return bad("an admitted prompt has at least one token");
+        if (m < 1 || m > cap) return bad("an admit's max_new must lie in 1..cap");
+        if ((long)L + m > max_len) return bad("an admit's len + max_new exceeds max_len");
+        if (so[b] < 0 || (long)so[b] + L > MT) return bad("an admitted prompt lies outside the step's tokens");
+        if (slot < 0 || slot >= S) continue;                 // (the kernels skip it)
+        if (taken[slot]) return bad("a slot named twice in one admit");
+        taken[slot] = 1;
+      }
+    } else if (kind == 2) {
+      if (r[2] < 0 || r[2] >= S) return bad("a table change's slot is out of range");
+      if (n < -1 || n > cap || n > MT) return bad("a table holds -1 (back to the lookup) or 0..min(cap, max_tokens) tokens");
+    } else return bad("script kind 0 (step), 1 (admit) or 2 (table)");
+  }
+  std::vector<void*> dev;
+  auto alloc = [&](size_t bytes, int fill) -> void* {
+    void* ptr = nullptr;
+    if (hipMalloc(&ptr, bytes ? bytes : 16) != hipSuccess) return nullptr;
+    dev.push_back(ptr);
+    if (fill >= 0 && hipMemset(ptr, fill, bytes) != hipSuccess) return nullptr;
+    return ptr;
+  };
+  auto done = [&](int r) { for (void* ptr : dev) hipFree(ptr); return r; };
+#define DBG_HIP(x) do { if ((x) != hipSuccess) return done(fail(e, RK_ERR_HIP, "debug draft steps: %s", #x)); } while (0)
+  int* dscript = (int*)alloc((size_t)n_steps * rec * 4, -1);
+  if (!dscript) return done(fail(e, RK_ERR_HIP, "debug draft steps: device allocation failed"));
+  DBG_HIP(hipMemcpy(dscript, q->script, (size_t)n_steps * rec * 4, hipMemcpyHostToDevice));
+  char* dall[RK_DEBUG_DRAFT_ARRAYS]; int* d[RK_DEBUG_DRAFT_ARRAYS];
+  for (int i = 0; i < RK_DEBUG_DRAFT_ARRAYS; ++i) {
+    const rk_debug_rows_out& b = q->state[i];
+    dall[i] = (char*)alloc((size_t)(b.bytes + 2 * b.band), RK_DEBUG_SENTINEL);
+    if (!dall[i]) return done(fail(e, RK_ERR_HIP, "debug draft steps: device allocation failed"));
+    d[i] = (int*)(dall[i] + b.band);
+    DBG_HIP(hipMemcpy(d[i], b.interior, (size_t)b.bytes, hipMemcpyHostToDevice));
+  }
+  DBG_HIP(hipDeviceSynchronize());
+  hipStream_t stream = e->slots[0].se;
+  const DraftInts x{d[6], d[7], d[8], d[9], d[10], d[11], d[12], d[13]};
+  for (int s = 0; s < n_steps; ++s) {
+    const int* r = q->script + (size_t)s * rec;
+    const int* dr = dscript + (size_t)s * rec;
+    const int kind = r[0], n = r[1];
+    if (kind == 0) launch_session_advance_draft(stream, dr + 4, d[0], d[1], d[2], d[3], d[4], d[5], S, nullptr, 0, g1, x, nullptr, nullptr);
+    else if (kind == 1) launch_session_advance_draft(stream, dr + 4, d[0], d[1], d[2], d[3], d[4], d[5], S, dr + 4 + A, n, g1, x, dr + 4 + A + 3L * MA + MA + 1, dr + 4 + A + 3L * MA);
+    else {
+      const int slot = r[2];
+      if (n > 0) DBG_HIP(hipMemcpy(x.tab + (size_t)slot * cap, r + 4 + A + 3L * MA + MA + 1, (size_t)n * sizeof(int), hipMemcpyHostToDevice));
+      DBG_HIP(hipMemcpy(x.tabn + slot, &n, sizeof(int), hipMemcpyHostToDevice));
+    }
+    launch_draft_lookup(stream, d[0], d[1], d[2], d[3], d[4], S, g1, x);
+    DBG_HIP(hipStreamSynchronize(stream));
+    DBG_HIP(hipGetLastError());
+    for (int i = 0; i < RK_DEBUG_DRAFT_ARRAYS; ++i) {
+      const size_t all = (size_t)(q->state[i].bytes + 2 * q->state[i].band);
+      DBG_HIP(hipMemcpy((char*)q->state[i].all + (size_t)s * all, dall[i], all, hipMemcpyDeviceToHost));
+    }
   }
 #undef DBG_HIP
   return done(RK_OK);

@@ -71,7 +71,7 @@ class RkDebugAttnCall(C.Structure):
                 ("plan_only", C.c_int), ("out_kind", C.c_int), ("out_tparam", C.c_int), ("out_grid", C.c_int * 3), ("out_grid2", C.c_int * 3)] + \
                [(n, C.c_int) for n in ("out_lds", "out_staged", "out_mfma", "out_part", "out_R", "out_nch", "out_skip_long",
                                        "out_heads_per_wg", "out_n_cu")] + \
-               [("qk_norm", C.c_void_p), ("qk_eps", C.c_float)]
+               [("qk_norm", C.c_void_p), ("qk_eps", C.c_float), ("g1", C.c_int), ("live", C.c_void_p)]
 
 
 class RkDebugXattnChainCall(C.Structure):
@@ -100,6 +100,15 @@ class RkDebugRowsCall(C.Structure):
                                        "n_slots", "max_pos", "false_id", "true_id", "dec_len", "max_new", "n_steps", "max_admit")] + \
                [("eps", C.c_float), ("xs", C.c_float), ("out_scale", C.c_float), ("in_", RkDebugRowsIn * 4), ("out", RkDebugRowsOut * 8),
                 ("plan_only", C.c_int), ("out_grid", C.c_int * 3), ("out_tparam", C.c_int), ("out_variant", C.c_int)]
+
+
+class RkDebugDraftStepsCall(C.Structure):
+    """rk_debug_draft_steps_call of include/rk_engine.h, field for field."""
+    _fields_ = [(n, C.c_int) for n in ("n_slots", "g1", "n_steps", "max_admit", "max_tokens")] + \
+               [("script", C.c_void_p), ("script_ints", C.c_int64), ("state", RkDebugRowsOut * 14)]
+
+
+DRAFT_ARRAYS = ("st", "len", "col", "max_new", "done", "out", "rnext", "rpos", "rlive", "dlen", "nstep", "tabn", "tab", "hist")
 
 
 class RkDebugGraphStats(C.Structure):
@@ -206,6 +215,7 @@ ABI = {
     "rk_debug_attn": (C.c_int, [C.c_void_p, _P(RkDebugAttnCall)]),
     "rk_debug_xattn_chain": (C.c_int, [C.c_void_p, _P(RkDebugXattnChainCall)]),
     "rk_debug_rows": (C.c_int, [C.c_void_p, _P(RkDebugRowsCall)]),
+    "rk_debug_draft_steps": (C.c_int, [C.c_void_p, _P(RkDebugDraftStepsCall)]),
     "rk_debug_gemm_bench": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _f32p]),
     "rk_debug_read": (C.c_int64, [C.c_void_p, C.c_char_p, _f32p, C.c_int64]),
     "rk_debug_graph_stats": (C.c_int, [C.c_void_p, _P(RkDebugGraphStats)]),
@@ -674,7 +684,7 @@ class RkEngine:
     def debug_attn(self, kind: int, *, n_seq: int, H: int, q=None, out=None, kv=None, band_rows=8, n_kv=0, Ld=0, cross=False, M=0, row0=0,
                    d=0, P=0, ldq=0, ldkv=0, ldctx=0, k_col=0, v_col=0, seq_off=None, row_off=None, tree_keys=None, tree_pos=None,
                    row_seq=None, pos=None, bias_lut=None, cos=None, sin=None, qkv_bias=None, cache=None, plan_only=False,
-                   qk_norm=None, qk_eps=0.0) -> dict:
+                   qk_norm=None, qk_eps=0.0, g1=0, live=None) -> dict:
         """One attention call through rk_debug_attn (include/rk_engine.h).  q / kv: 2-D fp16 [band_rows + rows + band_rows, ld], the
         WHOLE allocation with the caller's bands; out: 2-D fp16 [rows, ldctx], the pre-filled interior; cache (kind 5): flat fp16, K then
         V (kind 6, the T5 cached step: [n_seq][P][k | v] of 64 H each, bands of band_rows * 64 elements, pos one value).  Returns the plan fields and, unless plan_only, "out" [band_rows + rows + band_rows, ldctx] and "cache" (flat, with bands
@@ -721,6 +731,9 @@ class RkEngine:
         if qk_norm is not None:                              # kind 5: Qwen3's q | k head-norm weights, the step's entry with the norm
             assert put("qk_norm", qk_norm, np.float32).size == 2 * hd
             c.qk_eps = float(qk_eps)
+        c.g1 = int(g1)                                       # kind 5: a drafting step, g1 step rows per cache row (0 / 1: the plain call)
+        if live is not None:
+            assert put("live", live, np.int32).size == n_seq
         out_all = cache_all = None
         if out is not None:
             out = put("out", out, np.float16)
@@ -733,7 +746,7 @@ class RkEngine:
                 hd = 64
                 assert cache.size == n_seq * P * 2 * 64 * H
             else:
-                assert cache.size == 2 * n_seq * n_kv * P * hd
+                assert cache.size == 2 * (n_seq // max(int(g1), 1)) * n_kv * P * hd
             cache_all = put("cache_all", np.zeros(cache.size + 2 * band_rows * hd), np.float16)
         self._chk(self.lib.rk_debug_attn(self.h, C.byref(c)))
         del keep
@@ -782,6 +795,29 @@ class RkEngine:
         if not plan_only:
             res["all"] = alls
         return res
+
+    def debug_draft_steps(self, *, n_slots: int, g1: int, script, state, max_admit=0, max_tokens=0, band=256, check=True) -> dict:
+        """A drafting session's accept machine and proposer through rk_debug_draft_steps (include/rk_engine.h).  script: int32
+        [n_steps, rec] (the header's record layout); state: the 14 initial int32 arrays in DRAFT_ARRAYS' order.  Returns "rc" and
+        "all": per array a byte array [n_steps, band + bytes + band], the whole device allocation after every step (sentinel bytes
+        where a refused call launched nothing).  check=False: a refusal is returned as rc instead of raised."""
+        script = np.ascontiguousarray(script, dtype=np.int32)
+        assert script.ndim == 2 and len(state) == len(DRAFT_ARRAYS)
+        c = RkDebugDraftStepsCall()
+        c.n_slots, c.g1, c.n_steps, c.max_admit, c.max_tokens = n_slots, g1, script.shape[0], max_admit, max_tokens
+        c.script, c.script_ints = script.ctypes.data, script.size
+        keep, alls = [script], []
+        for i, a in enumerate(state):
+            a = np.ascontiguousarray(a, dtype=np.int32)
+            whole = np.full((script.shape[0], a.nbytes + 2 * band), DEBUG_SENTINEL, np.uint8)
+            keep.append(a)
+            alls.append(whole)
+            c.state[i].interior, c.state[i].bytes, c.state[i].band, c.state[i].all = a.ctypes.data, a.nbytes, band, whole.ctypes.data
+        rc = self.lib.rk_debug_draft_steps(self.h, C.byref(c))
+        if check:
+            self._chk(rc)
+        del keep
+        return {"rc": rc, "all": alls}
 
     def debug_xattn_chain(self, *, M: int, Ld: int, H: int, d: int, seq_off, x=None, wq=None, wk=None, wv=None, enc=None, row0=0, row_seq=None,
                           rowscale=None, ssq_in=None, ctx=None, ldo=0, band_rows=8, fuse_asked=True, ws_fill=0, plan_only=False) -> dict:

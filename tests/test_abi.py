@@ -86,3 +86,32 @@ def test_header_is_plain_c_and_a_c_caller_links(tmp_path):
     exported = subprocess.run(["nm", "-D", "--defined-only", lib], check=True, capture_output=True, text=True).stdout
     exported = {line.split()[-1] for line in exported.splitlines() if line.split()}
     assert undefined <= exported
+
+
+def test_debug_call_structs_have_the_headers_layout(tmp_path):
+    """The ctypes mirrors of the debug call structs against the C compiler's layout of include/rk_engine.h: sizes, and the offsets of
+    the fields appended last (rk_debug_attn_call: qk_norm / qk_eps, then the drafting step's g1 / live) and of the state arrays."""
+    import ctypes as C
+    import shutil
+    import subprocess
+    from llmrankers import _engine
+    gcc = shutil.which("gcc")
+    if gcc is None:
+        import pytest
+        pytest.skip("gcc not available")
+    want = [("rk_debug_attn_call", _engine.RkDebugAttnCall, ["kind", "q", "pos", "plan_only", "out_n_cu", "qk_norm", "qk_eps", "g1", "live"]),
+            ("rk_debug_rows_call", _engine.RkDebugRowsCall, ["op", "eps", "plan_only", "out_variant"]),
+            ("rk_debug_rows_out", _engine.RkDebugRowsOut, ["interior", "bytes", "band", "all"]),
+            ("rk_debug_draft_steps_call", _engine.RkDebugDraftStepsCall, ["n_slots", "g1", "n_steps", "max_admit", "max_tokens", "script", "script_ints", "state"])]
+    src = tmp_path / "layout.c"
+    src.write_text('#include "rk_engine.h"\n#include <stddef.h>\n#include <stdio.h>\nint main(void) {\n'
+                   + "".join(f'  printf("%zu\\n", sizeof({c}));\n' + "".join(f'  printf("%zu\\n", offsetof({c}, {f}));\n' for f in fields)
+                             for c, _, fields in want) + "  return 0;\n}\n")
+    exe = tmp_path / "layout"
+    subprocess.run([gcc, "-std=c99", "-I", os.path.join(REPO, "include"), str(src), "-o", str(exe)], check=True)
+    got = [int(x) for x in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
+    mine = []
+    for _, t, fields in want:
+        mine += [C.sizeof(t)] + [getattr(t, f).offset for f in fields]
+    assert got == mine
+    assert len(_engine.DRAFT_ARRAYS) == 14 and "#define RK_DEBUG_DRAFT_ARRAYS 14" in open(os.path.join(REPO, "include", "rk_engine.h")).read()

@@ -3,9 +3,11 @@ fed with drafted tokens, accepted on the device.  The contract: a request's toke
 session's - only the number of steps differs, and that number is the reference machine's (tests/_draft_ref.py) exactly.
 
 Every engine form the step has: toy-llama (128 wide, R = 2), toy-qwen2 (bias, 7 heads on one kv head: R = 1, and R = 7 under
-llama_dec_r = 2), toy-qwen3 (q / k head norm), toy-mistral (window 64) and the 64-wide llama / qwen2 / mistral.  Prompt lengths 28,
+llama_dec_r = 2), toy-qwen3 (q / k head norm), toy-mistral (window 64), the 64-wide llama / qwen2 / mistral and toy-llama on one kv head (128 wide, R = 4).  Prompt lengths 28,
 60 and 124 put a step's rows across positions 31 / 32 (a wave's keys), 63 / 64 (the Mistral toys' window: the first visible key
 moves inside one step's rows) and 127 / 128 (LDC_CHUNK)."""
+import dataclasses
+
 import numpy as np
 import pytest
 
@@ -17,7 +19,8 @@ PAD = 0
 LENS = (5, 28, 60, 124)
 MAX_NEW, MAX_LEN = 24, 160
 FORMS = [("toy-llama", 0), ("toy-qwen2", 0), ("toy-qwen2", 2), ("toy-qwen3", 0), ("toy-mistral", 0), ("toy-llama-hd64", 0),
-         ("toy-qwen2-hd64", 0), ("toy-mistral-hd64", 0)]
+         ("toy-qwen2-hd64", 0), ("toy-mistral-hd64", 0), ("toy-llama-g4", 0)]
+G4 = "toy-llama-g4"                 # toy-llama with ONE kv head: four query heads per kv head at width 128, the R = 4 entries Llama-3-8B runs
 
 
 def _engine(dims, state, **kw):
@@ -68,7 +71,7 @@ def form(request):
     """engine, prompts and the PLAIN session's tokens, rows and steps for them, without EOS - computed once, never modified"""
     from llmrankers import _synth
     name, dec_r = request.param
-    dims = _synth.NAMED_DIMS[name]
+    dims = dataclasses.replace(_synth.TOY_LLAMA, n_kv_heads=1) if name == G4 else _synth.NAMED_DIMS[name]
     state = _synth.synth_state_dict(dims, seed=929)
     base = _synth.synth_token_batch(1, 200, 200, dims.vocab, seed=17)[0]
     prompts = [[int(t) for t in base[7 * i:7 * i + n]] for i, n in enumerate(LENS)]
@@ -212,7 +215,7 @@ def test_independence_refill_hygiene_and_graphs(form):
 def test_fp8_step_weights(name):
     """Check 4, FP8: drafting on an engine with FP8 step weights against the plain session of that engine"""
     from llmrankers import _synth
-    dims = _synth.NAMED_DIMS[name]
+    dims = dataclasses.replace(_synth.TOY_LLAMA, n_kv_heads=1) if name == G4 else _synth.NAMED_DIMS[name]
     state = _synth.synth_state_dict(dims, seed=929)
     base = _synth.synth_token_batch(1, 200, 200, dims.vocab, seed=17)[0]
     prompts = [[int(t) for t in base[7 * i:7 * i + n]] for i, n in enumerate(LENS)]

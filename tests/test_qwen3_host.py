@@ -155,8 +155,9 @@ def test_the_engine_binding_switches_the_head_norm_on(monkeypatch):
     from llmrankers import _engine
     header = open(os.path.join(REPO, "include", "rk_engine.h")).read()
     assert "int rk_llama_set_qk_norm(rk_engine* e, int on);" in header
-    assert "const float* qk_norm; float qk_eps;\n} rk_debug_attn_call;" in header              # appended: earlier callers' layout stays
-    assert [n for n, _ in _engine.RkDebugAttnCall._fields_][-2:] == ["qk_norm", "qk_eps"]
+    # appended behind out_n_cu, and the drafting step's g1 / live appended behind them: earlier callers' layout stays
+    assert "out_heads_per_wg, out_n_cu;\n  const float* qk_norm; float qk_eps;\n  int g1; const int32_t* live;\n} rk_debug_attn_call;" in header
+    assert [n for n, _ in _engine.RkDebugAttnCall._fields_][-5:] == ["out_n_cu", "qk_norm", "qk_eps", "g1", "live"]
     for dims in (_synth.TOY_QWEN3, _synth.QWEN3_8B, _synth.TOY_QWEN2, _synth.TOY_LLAMA, _synth.TOY_MISTRAL):
         lib = _StubLib()
         monkeypatch.setattr(_engine, "load_library", lambda lib=lib: lib)
