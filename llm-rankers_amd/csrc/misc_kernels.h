@@ -2,6 +2,7 @@
 // One wave (64 lanes) per row, 16-byte vector accesses, shuffle reductions.
 #pragma once
 #include "common.h"
+#include "decode_ints.h"
 
 // hf: modeling_t5.py:644,678 (embed_tokens): hidden[t][:] = (fp32) E[ids[t]][:]; no scaling, dropout = identity.
 // Folded-norm form of the encoder (xraw != nullptr): the row also goes out as fp16 x xs (A operand of the first QKV GEMM)
@@ -206,15 +207,15 @@ __global__ __launch_bounds__(256) void greedy_advance_kernel(const int* __restri
 }
 
 // Token feedback of rk_llama_generate, the sibling of greedy_advance_kernel for a decoder-only model: a SET of EOS ids and a limit
-// on a row's total length.  st = {n, finished step, pad, n_eos, max_new, max_total, P, 0, eos[8]}: column n of the output gets
+// on a row's total length.  st = the block's head, GenWord and the EOS ids from INTS_EOS0 on (decode_ints.h): column n = st[GEN_N] of the output gets
 // the row's arg-max, or pad once the row has finished (hf: generation/utils.py greedy); a row finishes at one of the EOS ids or,
 // with max_total > 0, once prompt + new tokens == max_total (hf: MaxLengthCriteria).  The token is the row's next input at
-// position len[b] + n, held inside the cache.  st[1] (0 until then) becomes n + 1 at the column where the last row finished, or
+// position len[b] + n, held inside the cache.  st[GEN_FINISHED] (0 until then) becomes n + 1 at the column where the last row finished, or
 // max_new.  A step enqueued after that writes pads over pads (every row has finished) or nothing (n == max_new).  One workgroup.
 __global__ __launch_bounds__(256) void llama_advance_kernel(const int* __restrict__ argmax, int* st, const int* __restrict__ len,
                                                             int* done, int* pos, int* out, int* next_ids, int n_seq) {
   __shared__ int s_all;
-  const int tid = threadIdx.x, n = st[0], pad = st[2], n_eos = st[3], max_new = st[4], max_total = st[5], P = st[6];
+  const int tid = threadIdx.x, n = st[GEN_N], pad = st[GEN_PAD], n_eos = st[GEN_N_EOS], max_new = st[GEN_MAX_NEW], max_total = st[GEN_MAX_TOTAL], P = st[GEN_P];
   if (n >= max_new) return;
   if (tid == 0) s_all = 1;
   __syncthreads();
@@ -223,7 +224,7 @@ __global__ __launch_bounds__(256) void llama_advance_kernel(const int* __restric
     out[(size_t)b * max_new + n] = tok;
     if (!done[b]) {
       bool fin = max_total > 0 && len[b] + n + 1 >= max_total;
-      for (int k = 0; k < n_eos; ++k) fin = fin || tok == st[8 + k];
+      for (int k = 0; k < n_eos; ++k) fin = fin || tok == st[INTS_EOS0 + k];
       if (fin) done[b] = 1;
     }
     next_ids[b] = tok;
@@ -233,17 +234,17 @@ __global__ __launch_bounds__(256) void llama_advance_kernel(const int* __restric
   }
   __syncthreads();
   if (tid == 0) {
-    if (st[1] == 0 && (s_all || n == max_new - 1)) st[1] = n + 1;
-    st[0] = n + 1;
+    if (st[GEN_FINISHED] == 0 && (s_all || n == max_new - 1)) st[GEN_FINISHED] = n + 1;
+    st[GEN_N] = n + 1;
   }
 }
 
 // Token feedback of a decoding session (rk_llama_session_*), the sibling of llama_advance_kernel for rows that start and end on
 // their own: every cache slot has its prompt length, its own column counter, its own max_new and a done flag (1: idle or
-// finished).  st = {finishes so far, pad, n_eos, max_len, max_new_cap, 0, 0, 0, eos[8]}.  An active slot's column col[b] gets its
+// finished).  st = the block's head, SesWord and the EOS ids from INTS_EOS0 on (decode_ints.h).  An active slot's column col[b] gets its
 // arg-max; the slot finishes at one of the EOS ids or at its max_new-th token; the token is its next input at position
 // len[b] + col[b], held inside the cache.  A slot that is idle or done emits nothing, keeps its position, feeds pad and is not
-// counted again: the step queued behind a finish changes nothing for that slot.  st[0], the session word, is the running number
+// counted again: the step queued behind a finish changes nothing for that slot.  st[SES_FINISHES], the session word, is the running number
 // of finishes (the host compares it with what it has seen).
 // admit != null (rk_llama_session_admit, behind the prefill's head; admit = slot[n] | len[n] | max_new[n]): row r of argmax belongs
 // to slot admit[r], which starts here with that prompt length and max_new; only those slots are touched.  One workgroup.
@@ -251,7 +252,7 @@ __global__ __launch_bounds__(256) void llama_session_advance_kernel(const int* _
                                                                     int* max_new, int* done, int* pos, int* out, int* next_ids,
                                                                     int n_slots, const int* __restrict__ admit, int n_admit) {
   __shared__ int s_fin;
-  const int tid = threadIdx.x, pad = st[1], n_eos = st[2], max_len = st[3], cap = st[4];
+  const int tid = threadIdx.x, pad = st[SES_PAD], n_eos = st[SES_N_EOS], max_len = st[SES_MAX_LEN], cap = st[SES_CAP];
   if (tid == 0) s_fin = 0;
   __syncthreads();
   const int rows = admit ? n_admit : n_slots;
@@ -265,7 +266,7 @@ __global__ __launch_bounds__(256) void llama_session_advance_kernel(const int* _
     if (done[b]) { next_ids[b] = pad; continue; }
     const int tok = argmax[r], c = col[b];
     bool fin = c + 1 >= max_new[b] || c + 1 >= cap;
-    for (int k = 0; k < n_eos; ++k) fin = fin || tok == st[8 + k];
+    for (int k = 0; k < n_eos; ++k) fin = fin || tok == st[INTS_EOS0 + k];
     if (c < cap) out[(size_t)b * cap + c] = tok;
     next_ids[b] = tok;
     const int p = len[b] + c;
@@ -274,7 +275,7 @@ __global__ __launch_bounds__(256) void llama_session_advance_kernel(const int* _
     if (fin) { done[b] = 1; atomicAdd(&s_fin, 1); }
   }
   __syncthreads();
-  if (tid == 0 && s_fin) st[0] += s_fin;
+  if (tid == 0 && s_fin) st[SES_FINISHES] += s_fin;
 }
 
 // Token feedback of a DRAFTING session (rk_llama_session_open_draft): llama_session_advance_kernel's state machine over g1 = Kd + 1
@@ -282,7 +283,7 @@ __global__ __launch_bounds__(256) void llama_session_advance_kernel(const int* _
 // positions; dlen[s] of the extra rows are live.  t_0 = argmax(row 0) is always accepted; t_j = argmax(row j) is accepted while
 // d_j == t_{j-1} and no accepted token has ended the slot (an EOS id, its max_new-th token, cap).  Accepted tokens go to the slot's
 // output columns and to its history hist[s][len + column] (the prompt in front: what draft_lookup_kernel searches); col advances by
-// the number accepted.  nstep[s] counts the steps the slot's request was active in.  st as above, st[5] / st[6] = ngram_min / max.
+// the number accepted.  nstep[s] counts the steps the slot's request was active in.  st as above, with SES_NGRAM_MIN / SES_NGRAM_MAX.
 // admit != null: row r of argmax is the prefill's last row of slot admit[r]; the slot starts here, its prompt tokens[seq_off[r] ..]
 // is copied to its history and t_0 is its column 0.  One workgroup; rnext / dlen are written by draft_lookup_kernel behind this.
 __global__ __launch_bounds__(256) void llama_session_advance_draft_kernel(const int* __restrict__ argmax, int* st, int* len, int* col,
@@ -292,7 +293,7 @@ __global__ __launch_bounds__(256) void llama_session_advance_draft_kernel(const 
                                                                           int* hist, int* nstep, const int* __restrict__ tokens,
                                                                           const int* __restrict__ seq_off) {
   __shared__ int s_fin;
-  const int tid = threadIdx.x, n_eos = st[2], max_len = st[3], cap = st[4];
+  const int tid = threadIdx.x, n_eos = st[SES_N_EOS], max_len = st[SES_MAX_LEN], cap = st[SES_CAP];
   if (tid == 0) s_fin = 0;
   if (admit) {                                             // the prompts into the histories, every thread
     for (int r = 0; r < n_admit; ++r) {
@@ -322,14 +323,14 @@ __global__ __launch_bounds__(256) void llama_session_advance_draft_kernel(const 
       ++c;
       prev = tok;
       fin = c >= mn || c >= cap;
-      for (int k = 0; k < n_eos; ++k) fin = fin || tok == st[8 + k];
+      for (int k = 0; k < n_eos; ++k) fin = fin || tok == st[INTS_EOS0 + k];
     }
     col[b] = c;
     if (!admit) nstep[b] += 1;
     if (fin) { done[b] = 1; atomicAdd(&s_fin, 1); }
   }
   __syncthreads();
-  if (tid == 0 && s_fin) st[0] += s_fin;
+  if (tid == 0 && s_fin) st[SES_FINISHES] += s_fin;
 }
 
 // The proposer of a drafting session, one workgroup per slot, behind llama_session_advance_draft_kernel: the next step's g1 rows of
@@ -347,7 +348,7 @@ __global__ __launch_bounds__(256) void draft_lookup_kernel(const int* __restrict
                                                            const int* __restrict__ tab, const int* __restrict__ tabn) {
   __shared__ int s_best;
   const int s = blockIdx.x, tid = threadIdx.x, Kd = g1 - 1;
-  const int pad = st[1], max_len = st[3], cap = st[4], nmin = st[5], nmax = st[6];
+  const int pad = st[SES_PAD], max_len = st[SES_MAX_LEN], cap = st[SES_CAP], nmin = st[SES_NGRAM_MIN], nmax = st[SES_NGRAM_MAX];
   int* nx = rnext + (size_t)s * g1; int* ps = rpos + (size_t)s * g1; int* lv = rlive + (size_t)s * g1;
   if (done[s]) {                                           // uniform
     if (tid == 0) { nx[0] = pad; lv[0] = 1; dlen[s] = 0; }

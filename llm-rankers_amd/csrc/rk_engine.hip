@@ -22,6 +22,9 @@
 #include <vector>
 
 #include "../../include/rk_engine.h"
+#pragma GCC visibility push(hidden)   // (its inline functions are no exports of the library)
+#include "decode_ints.h"
+#pragma GCC visibility pop
 #include "attention.h"
 #include "attention_d128.h"
 #include "decoder_kernels.h"
@@ -204,7 +207,7 @@ struct rk_engine {
                                                                // Llama sampling head: the step's fp32 logits [rows, vocab] (logits_gen counts the moves)
   Grown<float> amax_val; Grown<int> amax_idx; int amax_gen = 0;   // greedy head: per-row block maxima / first columns
   // rk_t5_generate: self-attention K / V cache [n_dec_layers][n_seq][P][2 inner] (kv_gen counts the moves) and the per-call int
-  // block on the device (state, prefix, finished rows, output, tree arrays); decode_cached: pinned read-back of the finished step
+  // block on the device (state, prefix, finished rows, output, tree arrays); decode_loop: pinned read-back of the finished step
   Grown<half_t> kv_cache; int kv_gen = 0;
   Grown<int> gen_buf; int* gen_pin = nullptr; hipEvent_t ev_gen[2] = {nullptr, nullptr};
   size_t scores_cap = 0;
@@ -255,6 +258,7 @@ struct rk_engine {
     bool sampled = false; std::vector<unsigned long long> seeds;          // latched at open: the sampling head; every slot's seed
     int draft = 0, ngram_min = 1, ngram_max = 3;                          // rk_llama_session_open_draft: Kd extra rows per slot (0: none)
     long long steps = 0, tokens = 0;                                      // rk_llama_session_stats: steps issued, tokens they emitted
+    SessionLayout lay{0, 0, 0, 0};                                        // its int block in lints (decode_ints.h), set at the open
   } ls;
   // decoder chains as HIP graphs: key = everything the launch parameters of a chain depend on; at most RK_GRAPH_CACHE_KEYS keys
   // (run_graphed); graph_count: what run_graphed did since the engine was created (rk_debug_graph_stats)
@@ -804,25 +808,24 @@ void launch_greedy_advance(hipStream_t st, const int* argmax, int* state, const 
                            int dec_len, int max_new) {
   hipLaunchKernelGGL(greedy_advance_kernel, dim3(1), dim3(256), 0, st, argmax, state, prefix, done, out, next_ids, n_seq, dec_len, max_new);
 }
-void launch_llama_advance(hipStream_t st, const int* argmax, int* state, const int* len, int* done, int* pos, int* out, int* next_ids, int n_seq) {
-  hipLaunchKernelGGL(llama_advance_kernel, dim3(1), dim3(256), 0, st, argmax, state, len, done, pos, out, next_ids, n_seq);
+// the decoders' state machines on their int blocks (decode_ints.h: one pointer struct per block).  SessionAdmit: the admit form of
+// the session's two - row r of argmax is slot rec[r]'s (rec = slot[n] | len[n] | max_new[n]); the drafting form copies the prompts
+// tokens[seq_off[r] ..] to the histories.  The default: a step.
+struct SessionAdmit { const int* rec = nullptr; int n = 0; const int *tokens = nullptr, *seq_off = nullptr; };
+void launch_llama_advance(hipStream_t st, const int* argmax, const GenInts& d, int n_seq) {
+  hipLaunchKernelGGL(llama_advance_kernel, dim3(1), dim3(256), 0, st, argmax, d.st, d.len, d.done, d.pos, d.out, d.next, n_seq);
 }
-void launch_session_advance(hipStream_t st, const int* argmax, int* state, int* len, int* col, int* max_new, int* done, int* pos, int* out,
-                            int* next_ids, int n_slots, const int* admit, int n_admit) {
-  hipLaunchKernelGGL(llama_session_advance_kernel, dim3(1), dim3(256), 0, st, argmax, state, len, col, max_new, done, pos, out, next_ids, n_slots,
-                     admit, n_admit);
+void launch_session_advance(hipStream_t st, const int* argmax, const SessionInts& d, int n_slots, const SessionAdmit& a = {}) {
+  hipLaunchKernelGGL(llama_session_advance_kernel, dim3(1), dim3(256), 0, st, argmax, d.st, d.len, d.col, d.max_new, d.done, d.pos, d.out, d.next,
+                     n_slots, a.rec, a.n);
 }
-// a drafting session's int arrays behind the plain session's (session_draft_ints)
-struct DraftInts { int *rnext, *rpos, *rlive, *dlen, *nstep, *tabn, *tab, *hist; };
-void launch_session_advance_draft(hipStream_t st, const int* argmax, int* state, int* len, int* col, int* max_new, int* done, int* out,
-                                  int n_slots, const int* admit, int n_admit, int g1, const DraftInts& x, const int* tokens, const int* seq_off) {
-  hipLaunchKernelGGL(llama_session_advance_draft_kernel, dim3(1), dim3(256), 0, st, argmax, state, len, col, max_new, done, out, n_slots,
-                     admit, n_admit, g1, (const int*)x.rnext, (const int*)x.dlen, x.hist, x.nstep, tokens, seq_off);
+void launch_session_advance_draft(hipStream_t st, const int* argmax, const SessionInts& d, int n_slots, int g1, const SessionAdmit& a = {}) {
+  hipLaunchKernelGGL(llama_session_advance_draft_kernel, dim3(1), dim3(256), 0, st, argmax, d.st, d.len, d.col, d.max_new, d.done, d.out, n_slots,
+                     a.rec, a.n, g1, d.rnext, d.dlen, d.hist, d.nstep, a.tokens, a.seq_off);
 }
-void launch_draft_lookup(hipStream_t st, const int* state, const int* len, const int* col, const int* max_new, const int* done, int n_slots,
-                         int g1, const DraftInts& x) {
-  hipLaunchKernelGGL(draft_lookup_kernel, dim3(n_slots), dim3(256), 0, st, state, len, col, max_new, done, g1, x.rnext, x.rpos, x.rlive, x.dlen,
-                     (const int*)x.hist, (const int*)x.tab, (const int*)x.tabn);
+void launch_draft_lookup(hipStream_t st, const SessionInts& d, int n_slots, int g1) {
+  hipLaunchKernelGGL(draft_lookup_kernel, dim3(n_slots), dim3(256), 0, st, d.st, d.len, d.col, d.max_new, d.done, g1, d.rnext, d.rpos, d.rlive,
+                     d.dlen, d.hist, d.tab, d.tabn);
 }
 
 void rmsnorm(rk_engine* e, hipStream_t st, const float* x, const float* w, half_t* out, const int* row_map, int rows, float scale = 1.f) {
@@ -1795,13 +1798,14 @@ int run_graphed(rk_engine* e, hipStream_t st, std::vector<int> key, F&& body) {
   return RK_OK;
 }
 
-// The cached greedy loop of rk_t5_generate / rk_llama_generate.  `step` (one graph under `key`) decodes one position of every
-// sequence on st and leaves in *d_word the step at which the last sequence finished (0: none yet).  `forced` steps (a prefix) run
-// before the first step that yields an output column; columns below `first_col` were produced, and *d_word set, before the call
-// (the Llama prefill's).  The host reads back one word per column into a two-entry pinned ring and waits for the PREVIOUS column's
-// while the next step is queued: one step stays ahead, and a step after the last changes nothing (the advance kernels).  Returns
-// d_out's [n_seq][max_new] tokens and the final word.  Nothing is allocated here: the ring is the caller's to ensure
-// (ensure_decode_ring, with its other memory, before the chain starts).
+// The cached decoding loop of rk_t5_generate, rk_llama_generate and rk_llama_session_run.  `step` (one graph under `key`) decodes
+// one position of every sequence on st and leaves the decoder's word in *d_word: the step at which the last sequence finished (0:
+// none yet), or a session's running number of finishes.  `forced` steps (a prefix) run before the first step that yields an output
+// column; columns below `first_col` were produced, and *d_word set, before the call (the Llama prefill's).  The host reads back one
+// word per column into a two-entry pinned ring and waits for the PREVIOUS column's while the next step is queued: one step stays
+// ahead, and a step after the last changes nothing (the advance kernels).  It stops behind the word that differs from `baseline`,
+// or at column `limit`; *issued (null: not wanted) = the steps it enqueued.  Nothing is allocated here: the ring is the caller's
+// to ensure (ensure_decode_ring, with its other memory, before the chain starts).
 int ensure_decode_ring(rk_engine* e) {
   if (e->gen_pin) return RK_OK;
   HIPCHK(e, hipHostMalloc((void**)&e->gen_pin, 16 * sizeof(int), hipHostMallocDefault));
@@ -1809,25 +1813,30 @@ int ensure_decode_ring(rk_engine* e) {
   return RK_OK;
 }
 template <class F>
-int decode_cached(rk_engine* e, hipStream_t st, const std::vector<int>& key, F&& step, int forced, int first_col, int n_seq, int max_new,
-                  const int* d_word, const int* d_out, int32_t* out_tokens, int32_t* out_steps) {
+int decode_loop(rk_engine* e, hipStream_t st, const std::vector<int>& key, F&& step, int forced, int first_col, int limit, const int* d_word,
+                int baseline, int* issued = nullptr) {
   int* pin = e->gen_pin;
-  auto request = [&](int c) -> int {                                       // column c's finished-step word, read back
+  auto request = [&](int c) -> int {                                       // column c's word, read back
     HIPCHK(e, hipMemcpyAsync(pin + (c & 1), d_word, sizeof(int), hipMemcpyDeviceToHost, st));
     HIPCHK(e, hipEventRecord(e->ev_gen[c & 1], st));
     return RK_OK;
   };
-  int rc = RK_OK;
+  int rc = RK_OK, steps = 0;
   if (first_col > 0) RC(request(first_col - 1));
   bool stop = false;
-  for (int c = first_col - forced; c < max_new && !stop; ++c) {            // this step's column (< 0: a forced step)
+  for (int c = first_col - forced; c < limit && !stop; ++c, ++steps) {     // this step's column (< 0: a forced step)
     RC(run_graphed(e, st, key, step));
     if (c >= 0) RC(request(c));
     if (c >= 1) {                                                          // the previous column's word, while this step runs
       HIPCHK(e, hipEventSynchronize(e->ev_gen[(c - 1) & 1]));
-      stop = pin[(c - 1) & 1] != 0;
+      stop = pin[(c - 1) & 1] != baseline;
     }
   }
+  if (issued) *issued = steps;
+  return RK_OK;
+}
+// behind decode_loop: d_out's [n_seq][max_new] tokens and the final word; the stream is idle afterwards
+int decode_result(rk_engine* e, hipStream_t st, int n_seq, int max_new, const int* d_word, const int* d_out, int32_t* out_tokens, int32_t* out_steps) {
   std::vector<int> res((size_t)n_seq * max_new + 1);
   HIPCHK(e, hipMemcpyAsync(res.data(), d_out, (size_t)n_seq * max_new * sizeof(int), hipMemcpyDeviceToHost, st));
   HIPCHK(e, hipMemcpyAsync(res.data() + (size_t)n_seq * max_new, d_word, sizeof(int), hipMemcpyDeviceToHost, st));
@@ -2668,7 +2677,8 @@ int rk_t5_generate(rk_engine* e, const int32_t* tokens, const int32_t* seq_offse
   };
   const std::vector<int> key{GK_T5_GENERATE_STEP, 0, n_seq, (sl.maxL + 63) / 64, dec_len, max_new, e->amax_gen, e->kv_gen};
   // dec_len - 1 forced prefix steps, then one step per new column
-  if ((rc = decode_cached(e, sd, key, step, dec_len - 1, 0, n_seq, max_new, g + 1, g + o_out, out_tokens, out_steps))) return rc;
+  if ((rc = decode_loop(e, sd, key, step, dec_len - 1, 0, max_new, g + 1, 0))) return rc;
+  if ((rc = decode_result(e, sd, n_seq, max_new, g + 1, g + o_out, out_tokens, out_steps))) return rc;
   return finish_blocking(e, sl);
 }
 
@@ -3095,6 +3105,31 @@ static int llama_step_rows(rk_engine* e, hipStream_t st, int rows, int P, const 
   return RK_OK;
 }
 
+// The head behind a Llama prefill or step: `rows` final-normed rows of slots[0].dlast -> one token each in slots[0].d_argmax, by
+// arg-max, or drawn (head_sample's seed_map, pos and pos_map).  What a call or a session takes was decided before its chain started.
+struct HeadHow { bool sample = false; const int *seed_map = nullptr, *pos = nullptr, *pos_map = nullptr; };
+static int llama_head(rk_engine* e, hipStream_t st, int rows, const HeadHow& how) {
+  Slot& sl = e->slots[0];
+  return how.sample ? head_sample(e, st, sl.dlast, rows, e->ld.hidden, e->ld.vocab, e->samp, how.seed_map, how.pos, how.pos_map, sl.d_argmax)
+                    : head_argmax(e, st, sl.dlast, rows, e->ld.hidden, e->ld.vocab, sl.d_argmax);
+}
+// the key of a step graph: everything its launch arguments depend on - the kind of chain, its rows, the cache's P, a session's cap,
+// the generation of the head's buffers and of the cache's, a drafting session's Kd
+static std::vector<int> llama_step_key(const rk_engine* e, bool session, int rows, int P, int cap, bool sampled, int draft) {
+  const int kind = session ? (draft ? GK_LLAMA_SESSION_STEP_DRAFT : sampled ? GK_LLAMA_SESSION_STEP_SAMPLED : GK_LLAMA_SESSION_STEP)
+                           : (sampled ? GK_LLAMA_STEP_SAMPLED : GK_LLAMA_STEP);
+  std::vector<int> key{kind, 0, rows, P, cap, sampled ? e->logits_gen : e->amax_gen, e->lkv_gen, draft};
+  if (!draft) key.pop_back();                              // (Kd stands in a drafting session's key only, cap in a session's only)
+  if (!session) key.erase(key.begin() + 4);
+  return key;
+}
+// the stop ids of rk_llama_generate and of a session: at most INTS_MAX_EOS EOS ids and the pad id, all inside the vocabulary
+static int check_stop_ids(rk_engine* e, const int32_t* eos_ids, int n_eos, int pad_id) {
+  if (n_eos < 0 || n_eos > INTS_MAX_EOS || (n_eos > 0 && !eos_ids)) return fail(e, RK_ERR_INVALID, "n_eos must be in 0..8 (got %d)", n_eos);
+  const int rc = check_ids(e, eos_ids, n_eos, "eos");
+  return rc ? rc : check_ids(e, &pad_id, 1, "pad");
+}
+
 // Greedy continuation with a K / V cache (hf: generation/utils.py greedy loop over LlamaForCausalLM with use_cache): the prefill
 // once, keeping every layer's rotated K and its V; column 0 = the prefill's arg-max (rk_llama_greedy1's token); then ONE new row
 // per sequence and step: embedding of the fed-back token, per layer QKV (folded norm) -> attn_dec_cached_kernel -> o + residual
@@ -3111,9 +3146,8 @@ static int llama_generate(rk_engine* e, const int32_t* tokens, const int32_t* se
   if (e->ls.open) return fail(e, RK_ERR_STATE, "rk_llama_generate while a decoding session is open (it shares the cache and the step's rows): rk_llama_session_close first");
   if (!out_tokens) return fail(e, RK_ERR_INVALID, "null output");
   if (max_new <= 0) return fail(e, RK_ERR_INVALID, "max_new must be positive (got %d)", max_new);
-  if (n_eos < 0 || n_eos > 8 || (n_eos > 0 && !eos_ids)) return fail(e, RK_ERR_INVALID, "n_eos must be in 0..8 (got %d)", n_eos);
   int rc;
-  if ((rc = check_ids(e, eos_ids, n_eos, "eos")) || (rc = check_ids(e, &pad_id, 1, "pad"))) return rc;
+  if ((rc = check_stop_ids(e, eos_ids, n_eos, pad_id))) return rc;
   if ((rc = set_device(e))) return rc;
   Slot& sl = e->slots[0];
   if ((rc = check_batch(e, &sl, tokens, seq_offsets, n_seq))) return rc;
@@ -3123,44 +3157,34 @@ static int llama_generate(rk_engine* e, const int32_t* tokens, const int32_t* se
   for (int b = 0; b < n_seq; ++b)
     if (max_total > 0 && seq_offsets[b + 1] - seq_offsets[b] >= max_total)
       return fail(e, RK_ERR_INVALID, "prompt %d has %d tokens: it already reaches max_total %d", b, seq_offsets[b + 1] - seq_offsets[b], max_total);
-  const int P = sl.maxL + max_new, S = l.max_seqs;
+  const int P = sl.maxL + max_new;
+  const GenLayout lay(l.max_seqs, n_seq, max_new);         // the call's int block (decode_ints.h)
   if ((rc = ensure_amax(e, (size_t)n_seq))) return rc;
-  if ((rc = ensure_llama_gen(e, n_seq, P, 16 + 4 * (size_t)S + (size_t)n_seq * max_new))) return rc;
+  if ((rc = ensure_llama_gen(e, n_seq, P, lay.total))) return rc;
   if (seeds && (rc = ensure_sample_head(e, (size_t)n_seq))) return rc;
   hipStream_t st = sl.se;
-  // the call's int block: {n, finished step, pad, n_eos, max_new, max_total, P, 0, eos[8]} | len[S] | done[S] | pos[S] | next[S] | out[n][max_new]
-  int* g = e->lints.p;
-  int *d_len = g + 16, *d_done = d_len + S, *d_pos = d_done + S, *d_next = d_pos + S, *d_out = d_next + S;
-  std::vector<int> init(16 + 4 * (size_t)S + (size_t)n_seq * max_new, 0);
-  init[2] = pad_id; init[3] = n_eos; init[4] = max_new; init[5] = max_total; init[6] = P;
-  for (int k = 0; k < n_eos; ++k) init[8 + k] = eos_ids[k];
-  for (int b = 0; b < n_seq; ++b) init[16 + b] = seq_offsets[b + 1] - seq_offsets[b];
-  for (size_t k = 0; k < (size_t)n_seq * max_new; ++k) init[16 + 4 * (size_t)S + k] = pad_id;
+  const GenInts d = lay.bind(e->lints.p);
+  const std::vector<int> init = lay.initial(seq_offsets, max_total, P, eos_ids, n_eos, pad_id);
   HIPCHK(e, hipStreamSynchronize(st));
-  HIPCHK(e, hipMemcpy(g, init.data(), init.size() * sizeof(int), hipMemcpyHostToDevice));
+  HIPCHK(e, hipMemcpy(d.st, init.data(), init.size() * sizeof(int), hipMemcpyHostToDevice));
   if (seeds) HIPCHK(e, hipMemcpy(e->d_seeds, seeds, (size_t)n_seq * sizeof(uint64_t), hipMemcpyHostToDevice));
   const LlamaKeep keep{e->lkv.p, P};
   if ((rc = llama_prefill(e, tokens, seq_offsets, n_seq, &keep))) return rc;
   // the token index of the row's new token = the position of its last token + 1: the prefill's positions at the last rows for
   // column 0, the advance kernel's pos[] (len + column - 1) for the steps
-  auto head_and_advance = [&](bool prefill) -> int {
-    int r = !seeds ? head_argmax(e, st, sl.dlast, n_seq, l.hidden, l.vocab, sl.d_argmax)
-                   : head_sample(e, st, sl.dlast, n_seq, l.hidden, l.vocab, e->samp, nullptr, prefill ? e->d_pos : d_pos,
-                                 prefill ? sl.idx.d[IX_LAST_ROWS] : nullptr, sl.d_argmax);
-    if (r) return r;
-    Bracket br(e, st, PC_OTHER, 0, 0);
-    launch_llama_advance(st, sl.d_argmax, g, d_len, d_done, d_pos, d_out, d_next, n_seq);
+  const bool sampled = seeds != nullptr;
+  auto advance = [&]() { Bracket br(e, st, PC_OTHER, 0, 0); launch_llama_advance(st, sl.d_argmax, d, n_seq); };
+  if ((rc = llama_head(e, st, n_seq, HeadHow{sampled, nullptr, e->d_pos, sl.idx.d[IX_LAST_ROWS]}))) return rc;
+  advance();
+  auto step = [&]() -> int {
+    int r = llama_step_rows(e, st, n_seq, P, d.next, d.pos);
+    if (r || (r = llama_head(e, st, n_seq, HeadHow{sampled, nullptr, d.pos, nullptr}))) return r;
+    advance();
     return RK_OK;
   };
-  if ((rc = head_and_advance(true))) return rc;
-  auto step = [&]() -> int {
-    const int r = llama_step_rows(e, st, n_seq, P, d_next, d_pos);
-    return r ? r : head_and_advance(false);
-  };
-  const std::vector<int> key = seeds ? std::vector<int>{GK_LLAMA_STEP_SAMPLED, 0, n_seq, P, e->logits_gen, e->lkv_gen}
-                                     : std::vector<int>{GK_LLAMA_STEP, 0, n_seq, P, e->amax_gen, e->lkv_gen};
   // column 0 is the prefill's: the steps produce columns 1 .. max_new - 1
-  return decode_cached(e, st, key, step, 0, 1, n_seq, max_new, g + 1, d_out, out_tokens, out_steps);
+  if ((rc = decode_loop(e, st, llama_step_key(e, false, n_seq, P, 0, sampled, 0), step, 0, 1, max_new, d.st + GEN_FINISHED, 0))) return rc;
+  return decode_result(e, st, n_seq, max_new, d.st + GEN_FINISHED, d.out, out_tokens, out_steps);
 }
 int rk_llama_generate(rk_engine* e, const int32_t* tokens, const int32_t* seq_offsets, int n_seq, int max_new, int max_total,
                       const int32_t* eos_ids, int n_eos, int pad_id, int32_t* out_tokens, int32_t* out_steps) {
@@ -3192,27 +3216,9 @@ int rk_llama_set_sampling(rk_engine* e, float temperature, int top_k, float top_
 // goes to the next request.  The session's rows are rk_llama_generate's rows (llama_step_rows, the same launch sequence over all
 // n_slots rows, P = max_len), its prefill is llama_prefill with a slot map, and llama_session_advance_kernel keeps every slot's
 // own column counter: a prompt's tokens are bit for bit what rk_llama_generate gives for it alone.
-// int block: {finishes, pad, n_eos, max_len, cap, 0, 0, 0, eos[8]} | len[S] | col[S] | max_new[S] | done[S] | pos[S] | next[S] |
-// admit[3 S] | out[S][cap]
+// Its int block is decode_ints.h's SessionLayout (ls.lay).
 namespace {
-struct SessionInts { int *st, *len, *col, *max_new, *done, *pos, *next, *admit, *out; };
-SessionInts session_ints(rk_engine* e) {
-  const int S = e->ls.n_slots;
-  int* g = e->lints.p;
-  return SessionInts{g, g + 16, g + 16 + S, g + 16 + 2 * S, g + 16 + 3 * S, g + 16 + 4 * S, g + 16 + 5 * S, g + 16 + 6 * S, g + 16 + 9 * S};
-}
-// a drafting session's arrays behind out[S][cap] (R = S * (Kd + 1) step rows):
-// rnext[R] | rpos[R] | rlive[R] | dlen[S] | nstep[S] | tabn[S] | tab[S][cap] | hist[S][max_len]
-size_t session_n_ints(int n_slots, int cap, int max_len, int draft) {
-  const size_t S = (size_t)n_slots, plain = 16 + 9 * S + S * (size_t)cap;
-  return draft ? plain + 3 * S * (size_t)(draft + 1) + 3 * S + S * (size_t)cap + S * (size_t)max_len : plain;
-}
-DraftInts session_draft_ints(rk_engine* e) {
-  const auto& ls = e->ls;
-  const size_t S = (size_t)ls.n_slots, R = S * (size_t)(ls.draft + 1);
-  int* x = e->lints.p + 16 + 9 * S + S * (size_t)ls.cap;
-  return DraftInts{x, x + R, x + 2 * R, x + 3 * R, x + 3 * R + S, x + 3 * R + 2 * S, x + 3 * R + 3 * S, x + 3 * R + 3 * S + S * (size_t)ls.cap};
-}
+SessionInts session_ints(const rk_engine* e) { return e->ls.lay.bind(e->lints.p); }
 int session_check(rk_engine* e, const char* who) {
   if (!e) return RK_ERR_INVALID;
   if (e->family != 1) return fail(e, RK_ERR_STATE, "%s called on a T5 engine", who);
@@ -3222,15 +3228,23 @@ int session_check(rk_engine* e, const char* who) {
 // the session word, every slot's column counter and done flag -> the host mirror; the stream is idle afterwards
 int session_read_back(rk_engine* e, hipStream_t st) {
   auto& ls = e->ls;
-  const SessionInts d = session_ints(e);
-  const int S = ls.n_slots;
-  std::vector<int> buf(16 + 4 * (size_t)S);
-  HIPCHK(e, hipMemcpyAsync(buf.data(), d.st, buf.size() * sizeof(int), hipMemcpyDeviceToHost, st));   // st | len | col | max_new | done
+  const SessionLayout& lay = ls.lay;
+  std::vector<int> buf(lay.done.off + lay.done.n);         // head | len | col | max_new | done
+  HIPCHK(e, hipMemcpyAsync(buf.data(), e->lints.p, buf.size() * sizeof(int), hipMemcpyDeviceToHost, st));
   HIPCHK(e, hipStreamSynchronize(st));
   HIPCHK(e, hipGetLastError());
-  ls.seen = buf[0];
-  for (int b = 0; b < S; ++b) { ls.col[b] = buf[16 + S + b]; ls.done[b] = buf[16 + 3 * S + b]; }
+  ls.seen = buf[SES_FINISHES];
+  for (int b = 0; b < ls.n_slots; ++b) { ls.col[b] = buf[lay.col.off + b]; ls.done[b] = buf[lay.done.off + b]; }
   return RK_OK;
+}
+// behind a head: the session's state machine over the head's tokens and, for a drafting session, the proposer of the next step's
+// rows - as a step, or in the admit form
+static void session_advance(rk_engine* e, hipStream_t st, const SessionInts& d, const SessionAdmit& a = {}) {
+  const auto& ls = e->ls;
+  Bracket br(e, st, PC_OTHER, 0, 0);
+  if (!ls.draft) { launch_session_advance(st, e->slots[0].d_argmax, d, ls.n_slots, a); return; }
+  launch_session_advance_draft(st, e->slots[0].d_argmax, d, ls.n_slots, ls.draft + 1, a);
+  launch_draft_lookup(st, d, ls.n_slots, ls.draft + 1);
 }
 }  // namespace
 
@@ -3248,34 +3262,23 @@ static int session_open(rk_engine* e, int n_slots, int max_len, int max_new_cap,
   if (draft && (long)n_slots * (draft + 1) > l.max_seqs)
     return fail(e, RK_ERR_CAPACITY, "n_slots %d x (draft %d + 1) = %ld step rows > max_seqs %d (the step's activation rows)", n_slots, draft, (long)n_slots * (draft + 1), l.max_seqs);
   if (max_len > l.max_tokens) return fail(e, RK_ERR_CAPACITY, "max_len %d > max_tokens %d (the rotary tables end there)", max_len, l.max_tokens);
-  if (n_eos < 0 || n_eos > 8 || (n_eos > 0 && !eos_ids)) return fail(e, RK_ERR_INVALID, "n_eos must be in 0..8 (got %d)", n_eos);
   int rc;
-  if ((rc = check_ids(e, eos_ids, n_eos, "eos")) || (rc = check_ids(e, &pad_id, 1, "pad"))) return rc;
+  if ((rc = check_stop_ids(e, eos_ids, n_eos, pad_id))) return rc;
   if ((rc = set_device(e))) return rc;
-  const size_t S = (size_t)n_slots, G1 = (size_t)draft + 1, n_ints = session_n_ints(n_slots, max_new_cap, max_len, draft);
+  const SessionLayout lay(n_slots, max_new_cap, max_len, draft);
+  const size_t S = (size_t)n_slots, G1 = (size_t)draft + 1;
   if ((rc = ensure_amax(e, S * G1))) return rc;
-  if ((rc = ensure_llama_gen(e, n_slots, max_len, n_ints, (int)(S * G1)))) return rc;
+  if ((rc = ensure_llama_gen(e, n_slots, max_len, lay.total, (int)(S * G1)))) return rc;
   if (e->samp.on() && (rc = ensure_sample_head(e, S))) return rc;
   auto& ls = e->ls;
-  ls.n_slots = n_slots; ls.max_len = max_len; ls.cap = max_new_cap; ls.seen = 0;
+  ls.n_slots = n_slots; ls.max_len = max_len; ls.cap = max_new_cap; ls.seen = 0; ls.lay = lay;
   ls.draft = draft; ls.ngram_min = ngram_min; ls.ngram_max = ngram_max; ls.steps = 0; ls.tokens = 0;
   ls.sampled = e->samp.on(); ls.seeds.assign(S, 0);          // latched: rk_llama_set_sampling is refused until the close
   ls.busy.assign(S, 0); ls.told.assign(S, 0); ls.len.assign(S, 0); ls.max_new.assign(S, 0); ls.col.assign(S, 0); ls.done.assign(S, 1);
-  std::vector<int> init(n_ints, 0);                        // every slot idle: done, position 0, pad as its next id
-  init[1] = pad_id; init[2] = n_eos; init[3] = max_len; init[4] = max_new_cap;
-  for (int k = 0; k < n_eos; ++k) init[8 + k] = eos_ids[k];
-  for (size_t b = 0; b < S; ++b) { init[16 + 3 * S + b] = 1; init[16 + 5 * S + b] = pad_id; }
-  for (size_t k = 0; k < S * (size_t)max_new_cap; ++k) init[16 + 9 * S + k] = pad_id;
-  if (draft) {                                             // every row feeds pad at position 0; row 0 of a slot is live, no table
-    init[5] = ngram_min; init[6] = ngram_max;
-    const size_t x = 16 + 9 * S + S * (size_t)max_new_cap, R = S * G1;
-    for (size_t r = 0; r < R; ++r) { init[x + r] = pad_id; init[x + 2 * R + r] = r % G1 == 0; }
-    for (size_t b = 0; b < S; ++b) init[x + 3 * R + 2 * S + b] = -1;
-    for (size_t k = 0; k < S * (size_t)max_new_cap + S * (size_t)max_len; ++k) init[x + 3 * R + 3 * S + k] = pad_id;
-  }
+  const std::vector<int> init = lay.initial(eos_ids, n_eos, pad_id, ngram_min, ngram_max);   // every slot idle
   hipStream_t st = e->slots[0].se;
   HIPCHK(e, hipStreamSynchronize(st));
-  HIPCHK(e, hipMemcpy(e->lints.p, init.data(), n_ints * sizeof(int), hipMemcpyHostToDevice));
+  HIPCHK(e, hipMemcpy(e->lints.p, init.data(), init.size() * sizeof(int), hipMemcpyHostToDevice));
   ls.open = true;
   return RK_OK;
 }
@@ -3342,18 +3345,8 @@ static int session_admit(rk_engine* e, const int32_t* tokens, const int32_t* seq
   const LlamaKeep keep{e->lkv.p, ls.max_len, d.admit, ls.n_slots};
   if ((rc = llama_prefill(e, tokens, seq_offsets, n, &keep))) return rc;
   // (sampled: row r draws with its slot's seed, admit[r], at the index behind its prompt's last token)
-  if ((rc = !seeds ? head_argmax(e, st, sl.dlast, n, e->ld.hidden, e->ld.vocab, sl.d_argmax)
-                   : head_sample(e, st, sl.dlast, n, e->ld.hidden, e->ld.vocab, e->samp, d.admit, e->d_pos, sl.idx.d[IX_LAST_ROWS], sl.d_argmax))) return rc;
-  {
-    Bracket br(e, st, PC_OTHER, 0, 0);
-    if (!ls.draft) launch_session_advance(st, sl.d_argmax, d.st, d.len, d.col, d.max_new, d.done, d.pos, d.out, d.next, ls.n_slots, d.admit, n);
-    else {                                                 // the prompts' ids and offsets are the prefill's device copies
-      const DraftInts x = session_draft_ints(e);
-      launch_session_advance_draft(st, sl.d_argmax, d.st, d.len, d.col, d.max_new, d.done, d.out, ls.n_slots, d.admit, n, ls.draft + 1, x,
-                                   sl.d_tokens, sl.d_seq_off);
-      launch_draft_lookup(st, d.st, d.len, d.col, d.max_new, d.done, ls.n_slots, ls.draft + 1, x);
-    }
-  }
+  if ((rc = llama_head(e, st, n, HeadHow{seeds != nullptr, d.admit, e->d_pos, sl.idx.d[IX_LAST_ROWS]}))) return rc;
+  session_advance(e, st, d, SessionAdmit{d.admit, n, sl.d_tokens, sl.d_seq_off});   // the prompts' ids and offsets: the prefill's device copies
   for (int b = 0; b < n; ++b) { const int s = slots[b]; ls.busy[s] = 1; ls.told[s] = 0; ls.len[s] = adm[n + b]; ls.max_new[s] = max_new[b]; }
   return session_read_back(e, st);
 }
@@ -3381,42 +3374,19 @@ int rk_llama_session_run(rk_engine* e, int max_steps, int32_t* out_finished, int
   for (int b = 0; b < ls.n_slots; ++b) if (ls.busy[b] && !ls.done[b]) live = std::max(live, ls.max_new[b] - ls.col[b]);
   int steps = 0;
   if (!untold() && live > 0 && max_steps > 0) {
-    const int G1 = ls.draft + 1;
-    auto draft_step = [&]() -> int {                       // G1 rows per slot: step, head, accept, propose
-      const DraftInts x = session_draft_ints(e);
-      int r = llama_step_rows(e, st, ls.n_slots * G1, ls.max_len, x.rnext, x.rpos, G1, x.rlive);
-      if (r || (r = head_argmax(e, st, sl.dlast, ls.n_slots * G1, e->ld.hidden, e->ld.vocab, sl.d_argmax))) return r;
-      Bracket br(e, st, PC_OTHER, 0, 0);
-      launch_session_advance_draft(st, sl.d_argmax, d.st, d.len, d.col, d.max_new, d.done, d.out, ls.n_slots, nullptr, 0, G1, x, nullptr, nullptr);
-      launch_draft_lookup(st, d.st, d.len, d.col, d.max_new, d.done, ls.n_slots, G1, x);
-      return RK_OK;
-    };
+    // one step: a row per slot fed next[] at pos[], or G1 rows per slot - the drafting session's - fed by the proposer; the head;
+    // the state machine (and the proposer)
+    const int G1 = ls.draft + 1, rows = ls.n_slots * G1;
     auto step = [&]() -> int {
-      if (ls.draft) return draft_step();
-      int r = llama_step_rows(e, st, ls.n_slots, ls.max_len, d.next, d.pos);
-      if (r || (r = !ls.sampled ? head_argmax(e, st, sl.dlast, ls.n_slots, e->ld.hidden, e->ld.vocab, sl.d_argmax)
-                                : head_sample(e, st, sl.dlast, ls.n_slots, e->ld.hidden, e->ld.vocab, e->samp, nullptr, d.pos, nullptr, sl.d_argmax))) return r;
-      Bracket br(e, st, PC_OTHER, 0, 0);
-      launch_session_advance(st, sl.d_argmax, d.st, d.len, d.col, d.max_new, d.done, d.pos, d.out, d.next, ls.n_slots, nullptr, 0);
+      int r = llama_step_rows(e, st, rows, ls.max_len, ls.draft ? d.rnext : d.next, ls.draft ? d.rpos : d.pos, G1, d.rlive);
+      if (r || (r = llama_head(e, st, rows, HeadHow{ls.sampled, nullptr, d.pos, nullptr}))) return r;
+      session_advance(e, st, d);
       return RK_OK;
     };
-    const std::vector<int> key = ls.draft ? std::vector<int>{GK_LLAMA_SESSION_STEP_DRAFT, 0, ls.n_slots, ls.max_len, ls.cap, e->amax_gen, e->lkv_gen, ls.draft}
-                               : ls.sampled ? std::vector<int>{GK_LLAMA_SESSION_STEP_SAMPLED, 0, ls.n_slots, ls.max_len, ls.cap, e->logits_gen, e->lkv_gen}
-                                            : std::vector<int>{GK_LLAMA_SESSION_STEP, 0, ls.n_slots, ls.max_len, ls.cap, e->amax_gen, e->lkv_gen};
-    int* pin = e->gen_pin;
-    const int limit = std::min(max_steps, live);
-    bool stop = false;
-    for (int c = 0; c < limit && !stop; ++c) {             // decode_cached's loop: one word per step, one step queued ahead
-      RC(run_graphed(e, st, key, step));
-      ++steps;
-      HIPCHK(e, hipMemcpyAsync(pin + (c & 1), d.st, sizeof(int), hipMemcpyDeviceToHost, st));
-      HIPCHK(e, hipEventRecord(e->ev_gen[c & 1], st));
-      if (c >= 1) {
-        HIPCHK(e, hipEventSynchronize(e->ev_gen[(c - 1) & 1]));
-        stop = pin[(c - 1) & 1] != ls.seen;
-      }
-    }
-    sl.n_seq = ls.n_slots * G1;                            // rk_debug_read("llama_last"): the step's final rows
+    // until the session word moves (a finish), one step queued behind it; `live` bounds the loop whatever the device says
+    RC(decode_loop(e, st, llama_step_key(e, true, ls.n_slots, ls.max_len, ls.cap, ls.sampled, ls.draft), step, 0, 0, std::min(max_steps, live),
+                   d.st + SES_FINISHES, ls.seen, &steps));
+    sl.n_seq = rows;                                       // rk_debug_read("llama_last"): the step's final rows
     long long before = 0, after = 0;
     for (int b = 0; b < ls.n_slots; ++b) before += ls.col[b];
     RC(session_read_back(e, st));
@@ -3443,7 +3413,7 @@ int rk_llama_session_read(rk_engine* e, int slot, int32_t* out_tokens, int cap, 
   const SessionInts d = session_ints(e);
   HIPCHK(e, hipMemcpy(out_tokens, d.out + (size_t)slot * ls.cap, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
   const int zero = 0;                                      // idle again: one key chunk of attention per step
-  HIPCHK(e, hipMemcpy(ls.draft ? session_draft_ints(e).rpos + (size_t)slot * (ls.draft + 1) : d.pos + slot, &zero, sizeof(int), hipMemcpyHostToDevice));
+  HIPCHK(e, hipMemcpy(ls.draft ? d.rpos + (size_t)slot * (ls.draft + 1) : d.pos + slot, &zero, sizeof(int), hipMemcpyHostToDevice));
   *out_n = n;
   ls.busy[slot] = 0; ls.told[slot] = 0;
   return RK_OK;
@@ -3460,7 +3430,7 @@ int rk_llama_session_stats(rk_engine* e, int64_t* out_steps, int64_t* out_tokens
   if (out_tokens) *out_tokens = ls.tokens;
   if (out_slot_cols) for (int b = 0; b < ls.n_slots; ++b) out_slot_cols[b] = ls.busy[b] ? ls.col[b] : 0;
   if (out_slot_steps) {
-    if (ls.draft) HIPCHK(e, hipMemcpy(out_slot_steps, session_draft_ints(e).nstep, (size_t)ls.n_slots * sizeof(int), hipMemcpyDeviceToHost));
+    if (ls.draft) HIPCHK(e, hipMemcpy(out_slot_steps, session_ints(e).nstep, (size_t)ls.n_slots * sizeof(int), hipMemcpyDeviceToHost));
     for (int b = 0; b < ls.n_slots; ++b) {
       if (!ls.busy[b]) out_slot_steps[b] = 0;
       else if (!ls.draft) out_slot_steps[b] = ls.col[b] - 1;   // one token per step behind the admit's
@@ -3480,14 +3450,13 @@ int rk_debug_session_drafts(rk_engine* e, int slot, const int32_t* tokens, int n
   if (slot < 0 || slot >= ls.n_slots) return fail(e, RK_ERR_INVALID, "slot %d out of range (the session has %d)", slot, ls.n_slots);
   if (n < 0 || n > ls.cap || (n > 0 && !tokens)) return fail(e, RK_ERR_CAPACITY, "a draft table holds 0..max_new_cap = %d tokens (got %d)", ls.cap, n);
   if ((rc = check_ids(e, tokens, n, "draft"))) return rc;
-  const DraftInts x = session_draft_ints(e);
   const SessionInts d = session_ints(e);
   hipStream_t st = e->slots[0].se;
   const int tabn = tokens ? n : -1;
   HIPCHK(e, hipStreamSynchronize(st));
-  if (n > 0) HIPCHK(e, hipMemcpy(x.tab + (size_t)slot * ls.cap, tokens, (size_t)n * sizeof(int), hipMemcpyHostToDevice));
-  HIPCHK(e, hipMemcpy(x.tabn + slot, &tabn, sizeof(int), hipMemcpyHostToDevice));
-  launch_draft_lookup(st, d.st, d.len, d.col, d.max_new, d.done, ls.n_slots, ls.draft + 1, x);   // the next step's rows, by the new table
+  if (n > 0) HIPCHK(e, hipMemcpy(d.tab + (size_t)slot * ls.cap, tokens, (size_t)n * sizeof(int), hipMemcpyHostToDevice));
+  HIPCHK(e, hipMemcpy(d.tabn + slot, &tabn, sizeof(int), hipMemcpyHostToDevice));
+  launch_draft_lookup(st, d, ls.n_slots, ls.draft + 1);   // the next step's rows, by the new table
   HIPCHK(e, hipStreamSynchronize(st));
   HIPCHK(e, hipGetLastError());
   return RK_OK;
@@ -4686,13 +4655,15 @@ int rk_debug_rows(rk_engine* e, rk_debug_rows_call* q) {
         if (q->kind == 0)
           launch_greedy_advance(st, am, (int*)dout[0], (const int*)din[1], (int*)dout[1], (int*)dout[2], (int*)dout[3], rows, q->dec_len, q->max_new);
         else if (q->kind == 1)
-          launch_llama_advance(st, am, (int*)dout[0], (const int*)din[1], (int*)dout[1], (int*)dout[2], (int*)dout[3], (int*)dout[4], rows);
+          // (out 3 is the output, out 4 the next ids: the kernel's order)
+          launch_llama_advance(st, am, GenInts{(int*)dout[0], (int*)din[1], (int*)dout[1], (int*)dout[2], (int*)dout[4], (int*)dout[3]}, rows);
         else {
           const int* host_rec = din[1] ? (const int*)((const char*)q->in[1].data + q->in[1].off) + (size_t)s * rec : nullptr;
           const int n_admit = host_rec ? host_rec[0] : -1;
           const int* adm = n_admit >= 0 ? (const int*)din[1] + (size_t)s * rec + 1 : nullptr;
-          launch_session_advance(st, am, (int*)dout[0], (int*)dout[1], (int*)dout[2], (int*)dout[3], (int*)dout[4], (int*)dout[5], (int*)dout[6],
-                                 (int*)dout[7], rows, adm, n_admit >= 0 ? n_admit : 0);
+          auto o = [&](int i) { return (int*)dout[i]; };     // out 6 is the output, out 7 the next ids; no admit array, no drafting
+          const SessionInts si{o(0), o(1), o(2), o(3), o(4), o(5), o(7), nullptr, o(6)};
+          launch_session_advance(st, am, si, rows, SessionAdmit{adm, n_admit >= 0 ? n_admit : 0});
         }
       } break;
     }
@@ -4723,15 +4694,15 @@ int rk_debug_draft_steps(rk_engine* e, rk_debug_draft_steps_call* q) {
   const long A = std::max<long>((long)S * g1, MA), rec = 4 + A + 3L * MA + (MA + 1) + MT;
   if (!q->script || q->script_ints < (int64_t)n_steps * rec) return bad("script of n_steps x (4 + max(n_slots g1, max_admit) + 3 max_admit + max_admit + 1 + max_tokens) ints");
   auto state = [&](int i, long n) -> const int* { return (q->state[i].interior && n * 4 <= q->state[i].bytes) ? (const int*)q->state[i].interior : nullptr; };
-  const int* st0 = state(0, 16);
+  const int* st0 = state(0, INTS_HEAD);
   if (!st0) return bad("st of 16 ints");
-  const int n_eos = st0[2], max_len = st0[3], cap = st0[4], nmin = st0[5], nmax = st0[6];
+  const int n_eos = st0[SES_N_EOS], max_len = st0[SES_MAX_LEN], cap = st0[SES_CAP], nmin = st0[SES_NGRAM_MIN], nmax = st0[SES_NGRAM_MAX];
   if (n_eos < 0 || n_eos > 8) return bad("n_eos = st[2] in 0..8");
   if (max_len < 1 || max_len > (1 << 20) || cap < 1 || cap > (1 << 16)) return bad("max_len = st[3] in 1..2^20, cap = st[4] in 1..65536");
   if (nmin < 1 || nmin > nmax || nmax > 8) return bad("1 <= ngram_min = st[5] <= ngram_max = st[6] <= 8");
   if ((long)S * max_len * 4 > (1L << 31)) return bad("hist beyond 2^31 bytes");
   // st, len, col, max_new, done, out, rnext, rpos, rlive, dlen, nstep, tabn, tab, hist
-  const long need[RK_DEBUG_DRAFT_ARRAYS] = {16, S, S, S, S, (long)S * cap, (long)S * g1, (long)S * g1, (long)S * g1, S, S, S, (long)S * cap, (long)S * max_len};
+  const long need[RK_DEBUG_DRAFT_ARRAYS] = {INTS_HEAD, S, S, S, S, (long)S * cap, (long)S * g1, (long)S * g1, (long)S * g1, S, S, S, (long)S * cap, (long)S * max_len};
   for (int i = 0; i < RK_DEBUG_DRAFT_ARRAYS; ++i) {
     const rk_debug_rows_out& b = q->state[i];
     if (!b.interior || !b.all || b.band < 64 || b.band % 16 || b.band > (1 << 26) || need[i] * 4 != b.bytes)
@@ -4783,29 +4754,30 @@ int rk_debug_draft_steps(rk_engine* e, rk_debug_draft_steps_call* q) {
   int* dscript = (int*)alloc((size_t)n_steps * rec * 4, -1);
   if (!dscript) return done(fail(e, RK_ERR_HIP, "debug draft steps: device allocation failed"));
   DBG_HIP(hipMemcpy(dscript, q->script, (size_t)n_steps * rec * 4, hipMemcpyHostToDevice));
-  char* dall[RK_DEBUG_DRAFT_ARRAYS]; int* d[RK_DEBUG_DRAFT_ARRAYS];
+  char* dall[RK_DEBUG_DRAFT_ARRAYS]; int* da[RK_DEBUG_DRAFT_ARRAYS];
   for (int i = 0; i < RK_DEBUG_DRAFT_ARRAYS; ++i) {
     const rk_debug_rows_out& b = q->state[i];
     dall[i] = (char*)alloc((size_t)(b.bytes + 2 * b.band), RK_DEBUG_SENTINEL);
     if (!dall[i]) return done(fail(e, RK_ERR_HIP, "debug draft steps: device allocation failed"));
-    d[i] = (int*)(dall[i] + b.band);
-    DBG_HIP(hipMemcpy(d[i], b.interior, (size_t)b.bytes, hipMemcpyHostToDevice));
+    da[i] = (int*)(dall[i] + b.band);
+    DBG_HIP(hipMemcpy(da[i], b.interior, (size_t)b.bytes, hipMemcpyHostToDevice));
   }
   DBG_HIP(hipDeviceSynchronize());
   hipStream_t stream = e->slots[0].se;
-  const DraftInts x{d[6], d[7], d[8], d[9], d[10], d[11], d[12], d[13]};
+  // (no pos, next, admit: a drafting session's kernels take none of them)
+  const SessionInts d{da[0], da[1], da[2], da[3], da[4], nullptr, nullptr, nullptr, da[5], da[6], da[7], da[8], da[9], da[10], da[11], da[12], da[13]};
   for (int s = 0; s < n_steps; ++s) {
     const int* r = q->script + (size_t)s * rec;
     const int* dr = dscript + (size_t)s * rec;
     const int kind = r[0], n = r[1];
-    if (kind == 0) launch_session_advance_draft(stream, dr + 4, d[0], d[1], d[2], d[3], d[4], d[5], S, nullptr, 0, g1, x, nullptr, nullptr);
-    else if (kind == 1) launch_session_advance_draft(stream, dr + 4, d[0], d[1], d[2], d[3], d[4], d[5], S, dr + 4 + A, n, g1, x, dr + 4 + A + 3L * MA + MA + 1, dr + 4 + A + 3L * MA);
+    if (kind == 0) launch_session_advance_draft(stream, dr + 4, d, S, g1);
+    else if (kind == 1) launch_session_advance_draft(stream, dr + 4, d, S, g1, SessionAdmit{dr + 4 + A, n, dr + 4 + A + 3L * MA + MA + 1, dr + 4 + A + 3L * MA});
     else {
       const int slot = r[2];
-      if (n > 0) DBG_HIP(hipMemcpy(x.tab + (size_t)slot * cap, r + 4 + A + 3L * MA + MA + 1, (size_t)n * sizeof(int), hipMemcpyHostToDevice));
-      DBG_HIP(hipMemcpy(x.tabn + slot, &n, sizeof(int), hipMemcpyHostToDevice));
+      if (n > 0) DBG_HIP(hipMemcpy(d.tab + (size_t)slot * cap, r + 4 + A + 3L * MA + MA + 1, (size_t)n * sizeof(int), hipMemcpyHostToDevice));
+      DBG_HIP(hipMemcpy(d.tabn + slot, &n, sizeof(int), hipMemcpyHostToDevice));
     }
-    launch_draft_lookup(stream, d[0], d[1], d[2], d[3], d[4], S, g1, x);
+    launch_draft_lookup(stream, d, S, g1);
     DBG_HIP(hipStreamSynchronize(stream));
     DBG_HIP(hipGetLastError());
     for (int i = 0; i < RK_DEBUG_DRAFT_ARRAYS; ++i) {

@@ -2,6 +2,7 @@
 slots decode, one replayed step graph.  The property everything rests on: a prompt's tokens from a session equal, token for token,
 what rk_llama_generate gives for that prompt alone - whatever shares the session, whichever slot it lands in, whatever the slot held
 before.  On toy-qwen2 (7 query heads on 1 kv head, q / k / v biases) and toy-llama (2 query heads per kv head)."""
+import itertools
 import os
 import random
 
@@ -97,6 +98,63 @@ def test_session_tokens_equal_the_prompt_alone(model, which):
     eng.close()
     assert refills[4] >= 2, refills                                   # else the schedule did not test refill
     assert refills[1] == 0 and refills[16] == 0
+
+
+def test_run_step_counts_follow_the_host_model(model):
+    """The steps a plain session's run() issues, its finished set and the stats' columns and step total, after every run, against a
+    host model made from the alone-references only.  The FIFO schedule of _fifo with 4 slots and with 1, max_steps cycling through
+    1, 3 and unlimited, on the EOS set (a row that ends at its admit, one early, one late).  The model: nothing is issued while a
+    finish is unreported or nothing is active; else min(max_steps, live, f + 2) steps, live = the most columns an active slot may
+    still take, f = the steps before the first finish - one step is queued behind the finish before the host sees its word."""
+    dims, state, prompts, refs = model
+    eos, want = refs["eos"]
+    eng = _engine(dims, state)
+    branches = set()
+    for n_slots in (4, 1):
+        budgets = itertools.cycle((1, 3, 1 << 30))
+        with eng.session(n_slots, MAX_LEN, CAP, eos, PAD) as s:
+            owner, col, untold, total, nxt = {}, {}, set(), 0, 0      # per busy slot: its request, its column; finishes not yet reported
+            while nxt < len(prompts) or s.busy:
+                free = s.free_slots()
+                take = list(range(nxt, min(nxt + len(free), len(prompts))))
+                if take:
+                    slots = free[:len(take)]
+                    s.admit([prompts[r] for r in take], slots, [MAX_NEW[r] for r in take])
+                    for slot, r in zip(slots, take):
+                        owner[slot], col[slot] = r, 1                 # the admit's token is column 0
+                        if len(want[r]) == 1:
+                            untold.add(slot)
+                    nxt += len(take)
+                max_steps = next(budgets)
+                n = {b: len(want[owner[b]]) for b in col}
+                active = [b for b in col if col[b] < n[b]]
+                steps = 0
+                if active and not untold:
+                    live = max(MAX_NEW[owner[b]] - col[b] for b in active)
+                    f = min(n[b] - col[b] - 1 for b in active)
+                    steps = min(max_steps, live, f + 2)
+                    if steps == max_steps < min(live, f + 2):
+                        branches.add("limit")
+                    if steps == f + 2 < min(max_steps, live):
+                        branches.add("queued")
+                    for b in active:
+                        col[b] = min(col[b] + steps, n[b])
+                    untold = {b for b in active if col[b] == n[b]}
+                total += steps
+                finished, issued = s.run(max_steps)
+                st = s.stats()
+                print(f"{n_slots} slots, run({max_steps}): {issued} steps (model {steps}), finished {finished} (model {sorted(untold)})")
+                assert issued == steps, (n_slots, max_steps, issued, steps)
+                assert finished == sorted(untold), (n_slots, finished, untold)
+                assert [int(c) for c in st["slot_cols"]] == [col.get(b, 0) for b in range(n_slots)]
+                assert st["steps"] == total == s.steps
+                for slot in finished:
+                    assert [int(t) for t in s.read(slot)] == want[owner[slot]]
+                    del owner[slot], col[slot]
+                untold = set()
+            assert s.run() == ([], 0)
+    eng.close()
+    assert branches == {"limit", "queued"}, branches                  # else the schedule stopped exercising one of them
 
 
 def test_slot_reuse_reads_no_stale_keys(model):
