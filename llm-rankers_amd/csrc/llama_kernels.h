@@ -28,17 +28,26 @@ __device__ __forceinline__ half8 bias_v8(const half8 a, const float* __restrict_
   return o;
 }
 
-// One rotated pair of the BIAS kernels, in a FIXED form (no contraction left to the compiler): `fused` = both results as one fma
-// over a rounded product, else two rounded products and an add.  EVERY caller - the prefill's q and k, the step's new key and its
-// queries - passes fused = (element 0 of the thread's eight), so a step rounds a row exactly as a prefill does: the cached key IS
-// the prefill's key by construction.  Why element 0: that is what the compiler in use makes of the bias-free rope128_kernel
-// (one v_fma_mix, seven packed multiplies + add), so a prefill with an all-zero bias gives the bias-free bits
-// (tests/test_gpu_rankr1.py).  That equality is tied to one compiler version, not a property of the code; the bias path's own
-// guarantees do not depend on it.
+// One rotated pair, in a FIXED form (no contraction left to the compiler): `fused` = both results as one fma over a rounded
+// product, lo = fma(cos, x1, -(sin x2)) and up = fma(cos, x2, sin x1), else two rounded products and an add.  EVERY 128-wide caller,
+// with and without the bias - the prefill's q and k, the step's new key and its queries, the drafting step's append - passes
+// fused = (element 0 of the thread's eight), so a step rounds a row exactly as a prefill does: the cached key IS the prefill's key
+// by construction, and a prefill with an all-zero bias gives the bias-free bits except the sign of a zero (-0 + 0.0f = +0: the
+// bias-free kernels add nothing; tests/test_gpu_rope_forms.py asserts exactly that).  Why element 0: that is what a compiler once
+// made of the bias-free rope128_kernel's plain expression (one v_fma_mix, seven packed multiplies + add), the bits the prefill
+// always had.  The step kernels' copies of that expression had come out otherwise (up = fma(sin, x1, cos x2)), one fp16 ulp from
+// the prefill's key on about 1.3e-4 of those elements: hence one form in source.
 __device__ __forceinline__ void rope_rot(float x1, float x2, float co, float si, bool fused, float& lo, float& hi) {
 #pragma clang fp contract(off)
   if (fused) { lo = __builtin_fmaf(co, x1, -(si * x2)); hi = __builtin_fmaf(co, x2, si * x1); }
   else { lo = co * x1 - si * x2; hi = co * x2 + si * x1; }
+}
+// ONE of rope_rot's two results, for a caller that keeps one half of the head (the step's lanes): with (u, w) = (x1, -x2) it is
+// `lo`, with (x2, x1) it is `hi`, bit for bit - fl(si * -x2) = -fl(si * x2), and a - b is a + (-b) in IEEE arithmetic, zeros'
+// signs included.  Half the multiplies of rope_rot for such a lane.
+__device__ __forceinline__ float rope_rot_half(float u, float w, float co, float si, bool fused) {
+#pragma clang fp contract(off)
+  return fused ? __builtin_fmaf(co, u, si * w) : co * u + si * w;
 }
 
 // In place on the fused QKV buffer [T, ld]: the first n_rot heads of a row (all query heads, then all key heads) are
@@ -46,7 +55,7 @@ __device__ __forceinline__ void rope_rot(float x1, float x2, float co, float si,
 // One workgroup per token; a thread takes 8 consecutive pairs of one head: 16-byte accesses.
 // BIAS (Qwen2): bias [(n_rot + n_v) * 128] fp32 in q | k | v order is added to the fp16 GEMM output before the rotation - ONE
 // fp16 rounding for q and k, after bias and rotation - and to the n_v value heads behind them (touched only here).  BIAS = false
-// is the Llama kernel as it was: the same instructions, the same bits.
+// rotates the widened fp16 values by the same rope_rot calls: the bits the Llama kernel always gave, now written down.
 template <bool BIAS>
 __global__ __launch_bounds__(256) void rope128_kernel(half_t* __restrict__ qkv, const int* __restrict__ pos,
                                                       const float* __restrict__ cos_t, const float* __restrict__ sin_t,
@@ -61,25 +70,20 @@ __global__ __launch_bounds__(256) void rope128_kernel(half_t* __restrict__ qkv, 
     half_t* x = row + head * 128 + i0;
     const half8 a = *(const half8*)x, b = *(const half8*)(x + 64);
     half8 oa, ob;
+    float xa[8], xb[8];
     if constexpr (BIAS) {
-      float xa[8], xb[8];
       bias_add8(xa, a, bias + head * 128 + i0);
       bias_add8(xb, b, bias + head * 128 + 64 + i0);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        float lo, hi;
-        rope_rot(xa[j], xb[j], cr[i0 + j], sr[i0 + j], j == 0, lo, hi);
-        oa[j] = f2h_sat(lo);
-        ob[j] = f2h_sat(hi);
-      }
     } else {
 #pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const float co = cr[i0 + j], si = sr[i0 + j];
-        const float x1 = (float)a[j], x2 = (float)b[j];
-        oa[j] = f2h_sat(x1 * co - x2 * si);          // q * cos + rotate_half(q) * sin, first half: -x2
-        ob[j] = f2h_sat(x2 * co + x1 * si);          // second half: +x1
-      }
+      for (int j = 0; j < 8; ++j) { xa[j] = (float)a[j]; xb[j] = (float)b[j]; }
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {                    // q * cos + rotate_half(q) * sin: first half -x2, second half +x1
+      float lo, hi;
+      rope_rot(xa[j], xb[j], cr[i0 + j], sr[i0 + j], j == 0, lo, hi);
+      oa[j] = f2h_sat(lo);
+      ob[j] = f2h_sat(hi);
     }
     *(half8*)x = oa;
     *(half8*)(x + 64) = ob;
@@ -356,9 +360,12 @@ __device__ __forceinline__ half8 qkn_lane8(const half_t* row, const float* w, fl
 // The step's rotation of the new row, the one thing the two widths do differently: this lane's 8 dims (elements i0 .. i0 + 7 of
 // the first half of the head, or with `hi` their partners in the second) of rotated head hd (of q | k) of `row`, rounded as the
 // prefill's kernel of that width does, on the same table entries co / si.  D = 64: rope64_pairs, rope64_kernel's own form.
-// D = 128: rope128_kernel's arithmetic - bias-free the plain expression (the Llama kernel as it always was), BIAS bias_add8 and
-// the same rope_rot calls.
-template <int D, bool BIAS>
+// D = 128: rope128_kernel's arithmetic - the same rope_rot calls, on the widened fp16 values or behind bias_add8.  HALF (bias-free
+// 128 only; the cached step's body asks for it, the drafting step's kernels do not): the lane's own half by rope_rot_half, the same
+// bits from half the multiplies.  Which of the two a kernel takes is a matter of time alone: with rope_rot the plain step's R = 4
+// kernel needed 170 registers for the parent's 128 and Llama-3-8B's step at 4 slots ran 1.8 % slower; with rope_rot_half it is at
+// the parent's, while the drafting step's kernels measured faster with rope_rot ("Where roundings part").
+template <int D, bool BIAS, bool HALF = false>
 __device__ __forceinline__ half8 rope_lane8(const half_t* row, const float* bias, int hd, int i0, bool hi,
                                             const float (&co)[8], const float (&si)[8]) {
   const half_t* head = row + (size_t)hd * D;
@@ -379,13 +386,21 @@ __device__ __forceinline__ half8 rope_lane8(const half_t* row, const float* bias
         rope_rot(xa[j], xb[j], co[j], si[j], j == 0, lo, up);
         o[j] = hi ? f2h_sat(up) : f2h_sat(lo);
       }
+    } else if constexpr (HALF) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {                           // the lane's own half alone: (u, w) = (x1, -x2) or (x2, x1)
+        const float x1 = (float)a[j], x2 = (float)bb[j];
+        o[j] = f2h_sat(rope_rot_half(hi ? x2 : x1, hi ? x1 : -x2, co[j], si[j], j == 0));
+      }
     } else {
+      float xa[8], xb[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) { xa[j] = (float)a[j]; xb[j] = (float)bb[j]; }
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
-        const float x1 = (float)a[j], x2 = (float)bb[j];
-        const half_t oa = f2h_sat(x1 * co[j] - x2 * si[j]);
-        const half_t ob = f2h_sat(x2 * co[j] + x1 * si[j]);
-        o[j] = hi ? ob : oa;
+        float lo, up;
+        rope_rot(xa[j], xb[j], co[j], si[j], j == 0, lo, up);
+        o[j] = hi ? f2h_sat(up) : f2h_sat(lo);
       }
     }
     return o;
@@ -404,12 +419,14 @@ __device__ __forceinline__ half8 rope_lane8(const half_t* row, const float* bias
 //   same table entries - its key and value are used from registers and written to the cache by the workgroup that owns the
 //   position's chunk, once per kv head.  BIAS (Qwen2): the row's q / k / v get the projection bias where they are loaded -
 //   bias_add8 / bias_v8, the prefill kernel's arithmetic and rounding.  With and without it the key a step writes to the cache is
-//   bit for bit the key a prefill writes for that token.
+//   bit for bit the key a prefill writes for that token: at both widths both call one fixed source form (rope_rot), nothing is
+//   left to what a compiler contracts in one instantiation and not in another.
 // * The merge.  Each workgroup leaves one (maximum, sum, D accumulators) partial per head - its four waves merged in wave order -
 //   and attn_dec_combine_kernel merges a row's chunks in key order: nobody waits on another workgroup.
 // * Independence.  A row's context depends on its own position only, never on the batch, and a head's arithmetic does not depend
 //   on R (every per-head array is indexed by r alone, the merge is per head).
-// BIAS = false is the Llama kernel as it always was.  The sum over a key's lanes is what each width always used: row16_sum_f
+// BIAS = false is the Llama kernel (its 128-wide rotation in rope_rot's form since the step and the prefill were found to round
+// element 0's second half differently).  The sum over a key's lanes is what each width always used: row16_sum_f
 // (DPP) at 128, the three shuffles of row8_sum_f at 64.
 // (The kernel is an entry point around a body, `rotated` a lambda around rope_lane8 and the shuffles across a wave's keys are
 // written out, because that is the form the compiler in use turns into the instructions these kernels always had; the T5 step's
@@ -450,7 +467,7 @@ __device__ __forceinline__ void attn_dec_cached_body(const ARGS& p) {
   for (int j = 0; j < 8; ++j) { co[j] = p.cos_t[(size_t)pos * (D / 2) + i0 + j]; si[j] = p.sin_t[(size_t)pos * (D / 2) + i0 + j]; }
   auto rotated = [&](int hd) {
     if constexpr (QKN) return qkn_lane8(row, p.qkn, p.qkn_eps, p.n_heads, hd, i0, hi, co, si);
-    else return rope_lane8<D, BIAS>(row, p.bias, hd, i0, hi, co, si);
+    else return rope_lane8<D, BIAS, !KEYS>(row, p.bias, hd, i0, hi, co, si);
   };
   half8 knew, vnew;
   int crow = b;                                           // the row's cache row
@@ -577,33 +594,12 @@ struct LlamaDecAttnKeysArgs : LlamaDecAttnArgs {   // the drafting entries' argu
 };
 // The cache append of a drafting step, in front of each layer's attention: row b's rotated key and its value go to cache row
 // b / g1 at the row's position - formed by the helpers the step kernel forms `knew` / `vnew` with (rope_lane8 / bias_v8 / qkn_lane8,
-// on the lane mapping of attn_dec_cached_body: lane c of a key's D / 8 holds 8 dims; the bias-free 128-wide key by
-// rope_key128_fixed below, the step kernels' compiled form written out), so the bytes are those a plain step writes.
+// on the lane mapping of attn_dec_cached_body: lane c of a key's D / 8 holds 8 dims), every one of them a fixed form in source, so
+// the bytes are those a plain step writes (tests/test_gpu_rope_forms.py, tests/test_gpu_draft_attention.py: g1 plain steps leave
+// the same cache, byte for byte).
 // grid = rows; an item is (kv head, lane c).  A dead row (live[b] = 0) or a position outside the cache writes nothing.  QKN: the 8
 // lanes of an aligned group hold the items of one half of ONE head (D / 8 = 16 items per head) and the bound n_kv * 16 is a multiple
 // of 8, so a group enters and leaves the loop together and qkn_pairs' shuffles read active lanes only.
-// The bias-free 128-wide key in a FIXED form (no contraction left to the compiler): what the compiler in use makes of `knew` in every
-// bias-free attn_dec_cached_kernel<128, R> / _win_ instantiation - element 0 of the lane's eight as one fma over a rounded product,
-// lo = fma(cos, x1, -(sin x2)) and up = fma(sin, x1, cos x2), the other seven as two rounded products and an add.  Left to the
-// compiler, this kernel's copy of rope_lane8 came out with up = fma(cos, x2, sin x1) (rope128_kernel's form), one fp16 ulp away from
-// the plain step's key where the two roundings part: the cache of a drafting session was then not the plain session's
-// (tests/test_gpu_draft_attention.py: g1 plain steps leave the same cache, byte for byte).
-__device__ __forceinline__ half8 rope_key128_fixed(const half_t* row, int hd, int i0, bool hi, const float (&co)[8], const float (&si)[8]) {
-#pragma clang fp contract(off)
-  const half_t* head = row + (size_t)hd * 128;
-  const half8 a = *(const half8*)(head + i0), bb = *(const half8*)(head + 64 + i0);
-  half8 o;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const float x1 = (float)a[j], x2 = (float)bb[j];
-    float lo, up;
-    if (j == 0) { lo = __builtin_fmaf(co[j], x1, -(si[j] * x2)); up = __builtin_fmaf(si[j], x1, co[j] * x2); }
-    else { lo = x1 * co[j] - x2 * si[j]; up = x2 * co[j] + x1 * si[j]; }
-    o[j] = hi ? f2h_sat(up) : f2h_sat(lo);
-  }
-  return o;
-}
-
 template <int D, bool BIAS, bool QKN>
 __global__ __launch_bounds__(256) void kv_cache_append_kernel(LlamaDecAttnKeysArgs p) {
   constexpr int LK = D / 8, NL = D / 16;
@@ -622,7 +618,6 @@ __global__ __launch_bounds__(256) void kv_cache_append_kernel(LlamaDecAttnKeysAr
     for (int j = 0; j < 8; ++j) { co[j] = p.cos_t[(size_t)pos * (D / 2) + i0 + j]; si[j] = p.sin_t[(size_t)pos * (D / 2) + i0 + j]; }
     auto rotated = [&](int hd) {
       if constexpr (QKN) return qkn_lane8(row, p.qkn, p.qkn_eps, p.n_heads, hd, i0, hi, co, si);
-      else if constexpr (D == 128 && !BIAS) return rope_key128_fixed(row, hd, i0, hi, co, si);
       else return rope_lane8<D, BIAS>(row, p.bias, hd, i0, hi, co, si);
     };
     const half8 knew = rotated(p.n_heads + kvh);
