@@ -221,6 +221,20 @@ int rk_llama_greedy1(rk_engine* e, const int32_t* tokens, const int32_t* seq_off
 /* the same logits for a few vocabulary rows only -> out_logits[n_seq][n_out] fp32 (label scoring, tests) */
 int rk_llama_last_logits(rk_engine* e, const int32_t* tokens, const int32_t* seq_offsets, int n_seq,
                          const int32_t* out_token_ids, int n_out, float* out_logits);
+/* Query likelihood (qlm) on a decoder-only model: sequence b is its prompt followed by its labels, the last n_labels[b] tokens
+ * being the labels (p = len_b - n_labels[b] prompt tokens).  out_scores[b] = sum over j = 0 .. n_labels[b] - 1 of
+ * z[p + j - 1][tok[p + j]] - logsumexp(z[p + j - 1]), z[t] the fp32 logits of position t over the whole vocabulary, natural
+ * logarithm, summed in label order: HF's causal-LM loss (shifted labels, -100 on the prompt, reduction "none") summed and negated.
+ * The prefill is the one every other rk_llama_* call runs; behind it the final norm of the label-predicting rows, the head GEMM
+ * with the log-sum-exp fused into its epilogue and the merge kernel of rk_t5_qlm.  A sequence's score does not depend on what
+ * shares its call, bit for bit.  The number of label rows is not bounded by max_seqs.
+ * RK_ERR_INVALID for a null pointer, n_labels[b] < 1, n_labels[b] >= len_b (no prompt token in front of the first label) or a
+ * token id outside the vocabulary; RK_ERR_STATE on a T5 engine or while a decoding session is open (the session stays intact);
+ * RK_ERR_CAPACITY for a batch beyond the prefill's capacities.  A refused call launches nothing.
+ * replaces: the decoder-only branch ref: llmrankers/pointwise.py:25-26 refuses ("not supported yet for pointwise"); the T5 form is
+ * ref: llmrankers/pointwise.py:73-79 */
+int rk_llama_qlm(rk_engine* e, const int32_t* tokens, const int32_t* seq_offsets, int n_seq, const int32_t* n_labels,
+                 float* out_scores);
 /* Greedy continuation of every prompt by up to max_new tokens -> out_tokens[n_seq][max_new].  A row finishes at the
  * first token that is one of eos_ids[n_eos] (n_eos 0..8), or, when max_total > 0, once prompt_len + new == max_total;
  * finished rows emit pad_id; the call stops when every row has finished, remaining columns = pad_id;

@@ -120,9 +120,11 @@ struct Grown {
 //           those buffers is forgotten
 //   tree    rk_t5_greedy2's five arrays: written only if `sig` differs from the last tree's or anything was written since
 // The Llama family has IX_LAST_ROWS and IX_OUT_IDS only: llama_prefill writes the former through write(), rk_llama_last_logits copies
-// the latter on its stream itself (its one writer, nothing is ever skipped there).  rk_t5_generate's greedy_advance_kernel
-// writes IX_DEC_IDS on the device, behind the write() that forgot its content.
-enum DecBuf { IX_DEC_IDS, IX_OUT_IDS, IX_LAST_ROWS, IX_N_CACHED, IX_ROW_LABEL = IX_N_CACHED, IX_ROW_OFF, IX_OUT_IDX, IX_ROW_SEQ, IX_TREE_KEYS, IX_TREE_POS, IX_COUNT };
+// the latter on its stream itself (its one writer, nothing is ever skipped there).  rk_llama_qlm adds IX_ROW_MAP (the stream rows its
+// labels are predicted from), IX_ROW_LABEL and IX_ROW_OFF, allocated at its first call (ensure_llama_qlm) and written through
+// write() in front of the prefill.  rk_t5_generate's greedy_advance_kernel writes IX_DEC_IDS on the device, behind the write()
+// that forgot its content.
+enum DecBuf { IX_DEC_IDS, IX_OUT_IDS, IX_LAST_ROWS, IX_N_CACHED, IX_ROW_LABEL = IX_N_CACHED, IX_ROW_OFF, IX_OUT_IDX, IX_ROW_SEQ, IX_TREE_KEYS, IX_TREE_POS, IX_ROW_MAP, IX_COUNT };
 struct DecIndex {
   struct Src { DecBuf b; const std::vector<int>& v; };
   int* d[IX_COUNT] = {nullptr};
@@ -250,6 +252,7 @@ struct rk_engine {
   // between calls; lkv_gen counts the moves and is part of the step graph's key), and the step's activation rows (max_seqs each)
   Grown<half_t> lkv; Grown<float> lpart; Grown<int> lints; int lkv_gen = 0;
   struct LlamaStep { NormStream stream; half_t *qkv = nullptr, *ctx = nullptr, *ffh = nullptr; } lg;
+  Grown<half_t> lqlm_x;                                                           // rk_llama_qlm: the final-normed label-predicting rows [rows][hidden]
   // rk_llama_session_*: the one open decoding session.  It lives in lkv / lpart / lints (rk_llama_generate is refused meanwhile)
   // and mirrors on the host what the device's int block said at the last read-back: no step is ever in flight between two calls.
   struct LlamaSession {
@@ -2988,6 +2991,57 @@ int rk_llama_last_logits(rk_engine* e, const int32_t* tokens, const int32_t* seq
   HIPCHK(e, hipMemcpyAsync(sl.idx.d[IX_OUT_IDS], out_token_ids, n_out * sizeof(int), hipMemcpyHostToDevice, st));
   launch_head_rows(st, sl.dlast, e->lm_head, sl.idx.d[IX_OUT_IDS], sl.d_scores, n_seq, n_out, e->ld.hidden);
   return read_scores_blocking(e, sl, st, (size_t)n_seq * n_out, out_logits);
+}
+
+// rk_llama_qlm's device memory, grown between calls only: the head's block statistics and label logits (ensure_logits: the buffer
+// the sampling head shares, logits_gen counts its moves), the normed label rows, and - once, at the prefill's capacities: a label
+// row is a prompt row, so there are fewer than max_tokens of them - the three int buffers of DecIndex.
+static int ensure_llama_qlm(rk_engine* e, size_t rows) {
+  Slot& sl = e->slots[0];
+  int rc = RK_OK;
+  if (!sl.idx.d[IX_ROW_MAP]) {
+    RC(dalloc(e, &sl.idx.d[IX_ROW_MAP], (size_t)e->ld.max_tokens)); RC(dalloc(e, &sl.idx.d[IX_ROW_LABEL], (size_t)e->ld.max_tokens));
+    RC(dalloc(e, &sl.idx.d[IX_ROW_OFF], (size_t)e->ld.max_seqs + 1));
+  }
+  RC(ensure_logits(e, rows));
+  return e->lqlm_x.reserve(e, rows * (size_t)e->ld.hidden);
+}
+
+// Query likelihood on a decoder-only model: out_scores[b] = sum over the last n_labels[b] tokens of sequence b of
+// log softmax(z[t - 1])[tok[t]] (hf: modeling_llama.py LlamaForCausalLM.forward -> ForCausalLMLoss with labels = -100 on the
+// prompt, reduction "none", summed and negated: the decoder-only counterpart of ref: llmrankers/pointwise.py:73-79, which the
+// reference has for T5 only).  llama_prefill as every other entry point runs it, then rk_t5_qlm's tail on the rows that predict a
+// label: the final norm gathered through IX_ROW_MAP, the head GEMM with the log-sum-exp in its epilogue (the tiled family whatever
+// the row count; every tile shape writes the same block statistics), qlm_lse_kernel in its ragged form.  A sequence's score is a
+// function of its own tokens and label count, whatever shares the call.
+int rk_llama_qlm(rk_engine* e, const int32_t* tokens, const int32_t* seq_offsets, int n_seq, const int32_t* n_labels, float* out_scores) {
+  if (!e) return RK_ERR_INVALID;
+  if (!tokens || !seq_offsets || !n_labels || !out_scores) return fail(e, RK_ERR_INVALID, "rk_llama_qlm: tokens, seq_offsets, n_labels or out_scores missing");
+  if (e->family != 1) return fail(e, RK_ERR_STATE, "rk_llama_qlm on a T5 engine (rk_t5_qlm)");
+  if (e->ls.open) return fail(e, RK_ERR_STATE, "rk_llama_qlm while a decoding session is open (it shares the prefill's buffers): rk_llama_session_close first");
+  int rc = check_batch(e, nullptr, tokens, seq_offsets, n_seq);   // before the label counts are held against the lengths
+  if (rc) return rc;
+  std::vector<int> row_map, row_label, row_off((size_t)n_seq + 1, 0);
+  for (int b = 0; b < n_seq; ++b) {
+    const int L = seq_offsets[b + 1] - seq_offsets[b], nl = n_labels[b];
+    if (nl < 1 || nl >= L) return fail(e, RK_ERR_INVALID, "sequence %d: n_labels %d outside 1..%d (its %d tokens are a prompt of at least one token, then the labels)", b, nl, L - 1, L);
+    for (int t = seq_offsets[b + 1] - nl; t < seq_offsets[b + 1]; ++t) { row_map.push_back(t - 1); row_label.push_back(tokens[t]); }
+    row_off[b + 1] = (int)row_map.size();
+  }
+  const int rows = (int)row_map.size();
+  if ((rc = set_device(e))) return rc;
+  Slot& sl = e->slots[0];
+  hipStream_t st = sl.se;
+  RC(ensure_llama_qlm(e, (size_t)rows));
+  RC(sl.idx.write(e, st, {{IX_ROW_MAP, row_map}, {IX_ROW_LABEL, row_label}, {IX_ROW_OFF, row_off}}));
+  RC(llama_prefill(e, tokens, seq_offsets, n_seq));
+  int* const* ix = sl.idx.d;
+  const int nblk = (e->ld.vocab + 31) / 32, dm = e->ld.hidden;
+  rmsnorm(e, st, sl.enc.hidden, e->l_final_ln, e->lqlm_x.p, ix[IX_ROW_MAP], rows);
+  float* xlab = e->logits.p + (size_t)rows * nblk * 2;
+  RC(gemm(e, st, Gemm(PC_HEAD, EPI_LSE_F32, e->lqlm_x.p, dm, e->lm_head, dm, e->logits.p, nblk, rows, e->ld.vocab, dm).lse(ix[IX_ROW_LABEL], xlab)));
+  launch_qlm_lse(st, (const float2*)e->logits.p, nblk, xlab, 0, ix[IX_ROW_OFF], nullptr, sl.d_scores, n_seq);
+  return read_scores_blocking(e, sl, st, (size_t)n_seq, out_scores);
 }
 
 int rk_llama_set_rope_scaling(rk_engine* e, float factor, float low_freq_factor, float high_freq_factor, int original_max_pos) {

@@ -76,6 +76,7 @@ ABI = {
     "rk_llama_set_weight_fp8": (C.c_int, [C.c_void_p, C.c_int]),
     "rk_llama_greedy1": (C.c_int, [C.c_void_p, _i32p, _i32p, C.c_int, _i32p]),
     "rk_llama_last_logits": (C.c_int, [C.c_void_p, _i32p, _i32p, C.c_int, _i32p, C.c_int, _f32p]),
+    "rk_llama_qlm": (C.c_int, [C.c_void_p, _i32p, _i32p, C.c_int, _i32p, _f32p]),
     "rk_llama_generate": (C.c_int, [C.c_void_p, _i32p, _i32p, C.c_int, C.c_int, C.c_int, _i32p, C.c_int, C.c_int, _i32p, _i32p]),
     "rk_llama_set_sampling": (C.c_int, [C.c_void_p, C.c_float, C.c_int, C.c_float]),
     "rk_llama_generate_sampled": (C.c_int, [C.c_void_p, _i32p, _i32p, C.c_int, C.c_int, C.c_int, _i32p, C.c_int, C.c_int, _i32p, _i32p,
@@ -486,6 +487,18 @@ class RkLlamaEngine(RkEngine):
         out = np.empty((len(seqs), len(oi)), dtype=np.float32)
         self._chk(self.lib.rk_llama_last_logits(self.h, tok.ctypes.data_as(_i32p), off.ctypes.data_as(_i32p), len(seqs),
                                                 oi.ctypes.data_as(_i32p), len(oi), out.ctypes.data_as(_f32p)))
+        return out
+
+    def qlm(self, seqs: Sequence[Sequence[int]], n_labels: Sequence[int]) -> np.ndarray:
+        """rk_llama_qlm: float32 [n_seq], the log-likelihood of every sequence's last n_labels[b] tokens given the tokens in front
+        of them (natural logarithm, full-vocabulary softmax).  A sequence's score does not depend on what shares its call."""
+        if len(n_labels) != len(seqs):
+            raise ValueError(f"{len(seqs)} sequences but {len(n_labels)} label counts")
+        tok, off = pack_ragged(seqs)
+        nl = _i32(n_labels)
+        out = np.empty(len(seqs), dtype=np.float32)
+        self._chk(self.lib.rk_llama_qlm(self.h, tok.ctypes.data_as(_i32p), off.ctypes.data_as(_i32p), len(seqs),
+                                        nl.ctypes.data_as(_i32p), out.ctypes.data_as(_f32p)))
         return out
 
     def set_sampling(self, temperature: float, top_k: int, top_p: float):

@@ -708,6 +708,55 @@ class LlamaRuntime:
     def last_logits(self, seqs, out_ids) -> np.ndarray:
         return np.concatenate([self.engine.last_logits(c, out_ids) for c in self._chunks(seqs)], axis=0)
 
+    # -- the three calls PointwiseLlmRanker makes (T5Runtime's names and shapes) ---------------------------------------------------
+    def score(self, seqs, dec_prefix, out_ids) -> np.ndarray:
+        """[n, len(out_ids)] logits of the position behind every prompt: T5Runtime.score's shape.  A decoder-only model has no
+        decoder prefix - the prompt ends where the answer starts - so `dec_prefix` must be empty."""
+        if len(dec_prefix):
+            raise ValueError(f"a decoder-only model takes no decoder prefix (got {list(dec_prefix)}): the prompt carries it")
+        if not len(seqs):
+            return np.zeros((0, len(out_ids)), np.float32)
+        return self.last_logits(seqs, out_ids)
+
+    def qlm(self, seqs, labels) -> np.ndarray:
+        """float32 [n]: log P(labels | prompt) of every prompt with the same labels (RkLlamaEngine.qlm on prompt + labels)."""
+        return self.qlm_many(seqs, [labels] * len(seqs))
+
+    def qlm_many(self, seqs, labels_per_seq) -> np.ndarray:
+        """qlm scores of prompts with their OWN labels each (the passages of several queries): one engine call per capacity chunk
+        of prompt + label tokens.  Element b is bit for bit what qlm gives seqs[b] with labels_per_seq[b]; an empty label list
+        scores 0.0 without reaching the engine (the empty sum)."""
+        if len(labels_per_seq) != len(seqs):
+            raise ValueError(f"{len(seqs)} prompts but {len(labels_per_seq)} label sequences")
+        out = np.zeros(len(seqs), np.float32)
+        live = [b for b in range(len(seqs)) if len(labels_per_seq[b])]
+        full = [list(seqs[b]) + list(labels_per_seq[b]) for b in live]
+        done = 0
+        for c in self._chunks(full):
+            idx = live[done:done + len(c)]
+            out[idx] = self.engine.qlm(c, [len(labels_per_seq[b]) for b in idx])
+            done += len(c)
+        return out
+
+    def score_batches(self, batches, dec_prefix, out_ids) -> List[np.ndarray]:
+        """T5Runtime.score_batches' contract: the batches merged up to the engine's capacity (a prompt's logits do not depend on
+        what shares its call), the results cut back."""
+        batches = list(batches)
+        return self._cut(self.score([s for b in batches for s in b], dec_prefix, out_ids), batches)
+
+    def qlm_batches(self, batches, labels) -> List[np.ndarray]:
+        """T5Runtime.qlm_batches' contract, the same way."""
+        batches = list(batches)
+        return self._cut(self.qlm([s for b in batches for s in b], labels), batches)
+
+    @staticmethod
+    def _cut(rows, batches) -> List[np.ndarray]:
+        out, pos = [], 0
+        for b in batches:
+            out.append(rows[pos:pos + len(b)])
+            pos += len(b)
+        return out
+
 
 class DecodePool:
     """The scheduler between callers with many independent greedy requests and ONE decoding session (RkLlamaEngine.session, or a

@@ -4,6 +4,11 @@ Drop-in for ref: llmrankers/pointwise.py — same constructor signature, attribu
 mutation and stable descending sort.  What differs is underneath: prompts are tokenised once, batches are
 ragged (no padding, no DataLoader workers) and each batch is ONE call into the HIP engine, which returns only
 the vocabulary rows the method reads (yes/no ids) instead of materialising [B, 1, 32128] logits.
+
+Beyond the reference, which refuses them (ref: llmrankers/pointwise.py:25-26): decoder-only checkpoints (llama, mistral, qwen2, qwen3)
+are served with both methods on the Llama engine - yes_no from the logits behind the chat-templated prompt, qlm as the log-likelihood of
+the query's tokens as the prompt's continuation (hf: modeling_llama.py LlamaForCausalLM.forward with labels; rk_llama_qlm).  Candidate
+sharding and MonoT5LlmRanker stay T5 only.
 """
 from typing import List
 
@@ -15,6 +20,14 @@ from .rankers import LlmRanker, SearchResult, rerank_each
 YES_NO_PROMPT = "Passage: {text}\nQuery: {query}\nDoes the passage answer the query? Answer 'Yes' or 'No'"
 QLM_PROMPT = "Passage: {text}\nPlease write a question based on this passage."
 MONOT5_PROMPT = "Query: {query} Document: {document} Relevant:"
+
+# Decoder-only checkpoints (the reference refuses them for pointwise, ref: pointwise.py:25-26): the same two prompts as one user turn of
+# the tokenizer's chat template; yes_no reads the logits behind the prompt (rk_llama_last_logits), qlm the log-likelihood of the
+# query's tokens as the prompt's continuation (rk_llama_qlm).  POINTWISE_LLAMA_MAX_SEQS prompts per engine call.
+DECODER_ONLY_TYPES = ("llama", "mistral", "qwen2", "qwen3")
+POINTWISE_LLAMA_MAX_SEQS = 64
+DECODER_ONLY_SHARDING = ("shard_candidates=True is not supported for decoder-only checkpoints: the engine's score gather serves the T5 "
+                         "entry points; run such a model as query replicas (run.py --shard_candidates 0, its default for these models)")
 
 
 def _softmax_first(a: np.ndarray, b: np.ndarray, fp16: bool = False) -> np.ndarray:
@@ -37,15 +50,30 @@ class PointwiseLlmRanker(LlmRanker):
     # get the reference's 'cuda' score values instead: fp16 logits and fp16 probabilities, hence its exact ties.
     fp16_scores = False
     ignores_method = False      # MonoT5LlmRanker: one scoring form whatever `method` says
+    decoder_only = False        # set by _setup from the runtime's model_type (DECODER_ONLY_TYPES)
 
     def __init__(self, model_name_or_path, tokenizer_name_or_path, device, method="qlm", batch_size=1, cache_dir=None,
                  shard_candidates=False):
-        # ref: pointwise.py:13-34: tokenizer + model from the checkpoint; here the model is the HIP engine
-        from transformers import T5Tokenizer
-        from ._runtime import T5Runtime
-        tokenizer = T5Tokenizer.from_pretrained(
-            tokenizer_name_or_path if tokenizer_name_or_path is not None else model_name_or_path, cache_dir=cache_dir)
-        runtime = T5Runtime(model_name_or_path, device, cache_dir=cache_dir)   # NotImplementedError for non-T5 models
+        # ref: pointwise.py:13-34: tokenizer + model from the checkpoint; here the model is the HIP engine.  The checkpoint's
+        # model_type decides first (ref :15-26): t5 as ever; the decoder-only families, which the reference refuses for pointwise
+        # (ref :25-26), on the Llama engine; anything else is refused before a tokenizer is built.
+        from ._runtime import LlamaRuntime, T5Runtime, read_config, resolve_checkpoint
+        model_type = read_config(resolve_checkpoint(model_name_or_path, cache_dir)).get("model_type")
+        if model_type in DECODER_ONLY_TYPES and not self.ignores_method:
+            if shard_candidates:
+                raise NotImplementedError(DECODER_ONLY_SHARDING)
+            from transformers import AutoTokenizer
+            tokenizer = AutoTokenizer.from_pretrained(
+                tokenizer_name_or_path if tokenizer_name_or_path is not None else model_name_or_path, cache_dir=cache_dir)
+            runtime = LlamaRuntime(model_name_or_path, device, max_seqs=POINTWISE_LLAMA_MAX_SEQS, cache_dir=cache_dir,
+                                   accept_model_types=DECODER_ONLY_TYPES)
+        elif model_type == "t5":
+            from transformers import T5Tokenizer
+            tokenizer = T5Tokenizer.from_pretrained(
+                tokenizer_name_or_path if tokenizer_name_or_path is not None else model_name_or_path, cache_dir=cache_dir)
+            runtime = T5Runtime(model_name_or_path, device, cache_dir=cache_dir)
+        else:
+            raise NotImplementedError(f"Model type {model_type} is not supported yet by the MI355X engine")
         self._setup(runtime, tokenizer, device, method, batch_size, shard_candidates)
 
     @classmethod
@@ -60,6 +88,10 @@ class PointwiseLlmRanker(LlmRanker):
         if method == "qlm" and not self.ignores_method:
             from ._runtime import require_decoder_positions
             require_decoder_positions(runtime, "PointwiseLlmRanker(method='qlm')")
+        # a decoder-only runtime (LlamaRuntime, or a test double that says so): other prompt ids, no decoder prefix, no sharding
+        self.decoder_only = getattr(runtime, "model_type", "t5") in DECODER_ONLY_TYPES
+        if self.decoder_only and shard_candidates:
+            raise NotImplementedError(DECODER_ONLY_SHARDING)
         self.tokenizer = tokenizer
         self.llm = runtime
         self.config = getattr(runtime, "config", None)
@@ -83,6 +115,8 @@ class PointwiseLlmRanker(LlmRanker):
     def _spec(self, query: str, docs: List[SearchResult]):
         """-> (prompts, kind, arg, out_ids, dec_len, finish) or None for a method the reference ignores.
         kind 'score': arg = decoder prefix, raw = logits [n, len(out_ids)];  kind 'qlm': arg = labels, raw = [n]."""
+        if self.decoder_only:
+            return self._spec_decoder_only(query, docs)
         if self.method == "qlm":
             # ref: pointwise.py:41-82 — score = -sum_t CE(label_t), labels = "<pad> {query}" without specials
             labels = self.tokenizer.encode(f"<pad> {query}", add_special_tokens=False)
@@ -97,9 +131,36 @@ class PointwiseLlmRanker(LlmRanker):
                 lambda raw: _softmax_first(raw[:, 0], raw[:, 1], self.fp16_scores)
         return None   # any other method: the reference silently leaves the scores untouched and still sorts (ref :129)
 
+    def _spec_decoder_only(self, query: str, docs: List[SearchResult]):
+        """_spec on a decoder-only checkpoint: the T5 prompt texts; there is no decoder, so no decoder prefix and no start token."""
+        if self.method == "qlm":
+            # hf: modeling_llama.py LlamaForCausalLM.forward with labels = -100 on the prompt: score = sum_t log p(query token t |
+            # prompt, query tokens before t) - the T5 score (ref: pointwise.py:73-79) with the decoder input replaced by the prompt
+            labels = self.tokenizer.encode(query, add_special_tokens=False)
+            prompts = [QLM_PROMPT.format(text=doc.text) for doc in docs]
+            return prompts, "qlm", labels, None, len(labels), lambda raw: np.asarray(raw, dtype=np.float32).reshape(-1)
+        if self.method == "yes_no":
+            # the logits of the first generated position, as ref: pointwise.py:116-127 reads them from T5's first decoder step
+            yes_id = self.tokenizer.encode("Yes", add_special_tokens=False)[0]
+            no_id = self.tokenizer.encode("No", add_special_tokens=False)[0]
+            prompts = [YES_NO_PROMPT.format(text=doc.text, query=query) for doc in docs]
+            return prompts, "score", [], [yes_id, no_id], 0, lambda raw: _softmax_first(raw[:, 0], raw[:, 1], self.fp16_scores)
+        return None
+
+    def _prompt_ids(self, prompts: List[str]) -> List[List[int]]:
+        """Token ids of the prompts.  Decoder-only: as SetwiseLlmRanker._llama_prompt_ids builds them (ref: setwise.py:160-165) - one
+        user turn through the chat template with the generation prompt, then the tokenizer - without the " Passage:" suffix; a
+        tokenizer without a chat template (base models) takes the plain text."""
+        if not self.decoder_only:
+            return tokenize_prompts(self.tokenizer, prompts)
+        if getattr(self.tokenizer, "chat_template", None):
+            prompts = [self.tokenizer.apply_chat_template([{"role": "user", "content": p}], tokenize=False, add_generation_prompt=True)
+                       for p in prompts]
+        return [list(self.tokenizer(p)["input_ids"]) for p in prompts]
+
     def _counted_batches(self, prompts: List[str], dec_len: int):
         """Tokenise once, cut into the reference's batches and keep its counters (ref: pointwise.py:105-114)."""
-        seqs = tokenize_prompts(self.tokenizer, prompts)
+        seqs = self._prompt_ids(prompts)
         out = []
         for s, e in batches(len(seqs), self.batch_size):
             chunk = seqs[s:e]

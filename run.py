@@ -17,7 +17,8 @@ Multi-GPU (one process per GPU; the reference's only multi-GPU mode is accelerat
 ref: llmrankers/pointwise.py:20-24, README.md:357): `--num_gpus N` re-executes the command under torch.distributed.run with N
 ranks on this node (or run it under torchrun yourself).  Pointwise rankers then shard every query's CANDIDATES over the ranks
 (hits=100 over 8 GPUs -> 13,13,13,13,12,12,12,12) and the engine collects the scores with one RCCL all_gather per query
-(`--shard_candidates`, the default for pointwise under more than one rank); setwise / pairwise sorts are dependency chains, so
+(`--shard_candidates`, the default for pointwise on a T5 checkpoint under more than one rank; a decoder-only checkpoint - pointwise
+`yes_no` / `qlm` on llama, mistral, qwen2, qwen3, told from its config.json - runs as query replicas); setwise / pairwise sorts are dependency chains, so
 their QUERIES are dealt to the ranks instead (replicas) and rank 0 collects the rankings.  Rank 0 writes the run file and
 prints the averages.
 
@@ -221,11 +222,37 @@ def self_spawn(num_gpus, argv=None):
     os.execv(sys.executable, cmd)
 
 
+def decoder_only_checkpoint(model_name_or_path, cache_dir=None) -> bool:
+    """Does the checkpoint's config.json name a decoder-only family the pointwise ranker serves (llama, mistral, qwen2, qwen3)?
+    A local directory, or a hub id whose config.json is already in the local hub cache; nothing is downloaded for the question.
+    A checkpoint that is neither is not one: the ranker's constructor fetches it, and refuses --shard_candidates by name."""
+    from llmrankers.pointwise import DECODER_ONLY_TYPES
+    path = str(model_name_or_path)
+    try:
+        if os.path.isdir(path):
+            cfg = os.path.join(path, "config.json")
+        else:
+            from huggingface_hub import try_to_load_from_cache
+            cfg = try_to_load_from_cache(path, "config.json", cache_dir=cache_dir)
+        if not isinstance(cfg, str) or not os.path.exists(cfg):
+            return False
+        with open(cfg) as f:
+            return json.load(f).get("model_type") in DECODER_ONLY_TYPES
+    except Exception:
+        return False
+
+
 def candidates_sharded(args, world):
     """Pointwise under more than one rank shards the candidates of every query (one RCCL gather per query) unless
-    --shard_candidates 0 asks for query-level replicas; the sorting rankers are always replicas."""
+    --shard_candidates 0 asks for query-level replicas; the sorting rankers are always replicas.  A decoder-only checkpoint
+    (decided from its config.json) runs as query replicas unless the flag insists: candidate sharding is served for T5 only,
+    and --shard_candidates 1 then fails in the ranker's constructor."""
     flag = getattr(args.run, "shard_candidates", None)
-    return bool(args.pointwise) and world > 1 and (flag is None or int(flag) != 0)
+    if not (bool(args.pointwise) and world > 1 and (flag is None or int(flag) != 0)):
+        return False
+    if flag is None and decoder_only_checkpoint(getattr(args.run, "model_name_or_path", None), getattr(args.run, "cache_dir", None)):
+        return False
+    return True
 
 
 def build_ranker(args):
