@@ -207,6 +207,30 @@ int rk_llama_set_qk_norm(rk_engine* e, int on);
  * Call between rk_llama_create and rk_engine_finalize; RK_ERR_STATE on a T5 engine or after finalize.  Never calling it (or
  * on = 0) leaves the fp16 engine, byte for byte. */
 int rk_llama_set_weight_fp8(rk_engine* e, int on);
+/* FP8 K / V cache of the decoding step (opt-in, LOSSY: one e4m3 rounding per cached key and value element; vLLM's
+ * kv_cache_dtype="fp8" is the same option).  on != 0: the cache rk_llama_generate and rk_llama_session_* keep holds one byte per value
+ * and one exponent per vector - at most 0.52x the fp16 cache for the same (rows, positions >= 16) - and the step reads the bytes:
+ * half the step's cache stream.  Head width 128 only: rk_engine_finalize refuses (RK_ERR_STATE) a 64-wide engine.
+ * The engine-private format:
+ *   group   the 128 values of ONE key or value vector of one (cache row, kv head, position); a key as the fp16 cache holds it (behind
+ *           the Qwen2 bias, Qwen3's head norm, the rotation and the one fp16 rounding), a value behind the Qwen2 bias
+ *   e       per group one int8 exponent: the smallest integer with absmax <= 448 * 2^e, clamped to [-15, 7] (all-zero: -15)
+ *   q       per value one OCP e4m3fn byte: x * 2^-e rounded to nearest even, saturating at +-448
+ *   d       the dequantised value q * 2^e - an fp16 number by construction, as for the weights above
+ *   layout  per layer K bytes [rows][n_kv][P][128] | V bytes | K exponents [rows][n_kv][P'] | V exponents, P' = P rounded up to 32;
+ *           every region starts on a multiple of 32 bytes
+ * Every writer - the prefill's and the session admit's fill, the step, a drafting step's append - quantises through one device
+ * helper, so the key a step writes is byte for byte the key the fill writes for that token; the step's own row sees its new key and
+ * value dequantised, exactly as every later step reads them back, so a drafting session still gives the plain session's tokens.
+ * The prefill's own attention reads the un-quantised fp16 K / V of its QKV buffer: rk_llama_greedy1, rk_llama_last_logits and
+ * rk_llama_qlm are byte for byte an fp16-cache engine's.  ONLY the steps see quantised keys, so rk_llama_generate's tokens on such
+ * an engine need not equal those of a loop of rk_llama_greedy1 re-prefills (on an fp16-cache engine they do).
+ * Option llama_kv_fp8 = 0 keeps an fp16-layout cache of the dequantised values, read by the fp16 kernels: same bits in every output.
+ * Changing it is refused (RK_ERR_STATE) while a decoding session is open; the cache contents do not survive the change.
+ * Option llama_dec_r = 2 falls back to the rule on such an engine (no R = 7 instantiation), as at width 64.
+ * Call between rk_llama_create and rk_engine_finalize; RK_ERR_STATE on a T5 engine or after finalize.  Never calling it (or
+ * on = 0) leaves the fp16 cache, byte for byte.  Combines freely with rk_llama_set_weight_fp8, drafting and sampling. */
+int rk_llama_set_kv_fp8(rk_engine* e, int on);
 /* Mistral family (hf: models/mistral/modeling_mistral.py, sliding_window_causal_mask; Zephyr / RankZephyr checkpoints): attention
  * with a sliding window of `window` positions.  In the prefill query position i of a sequence sees keys max(0, i - window + 1) .. i;
  * in the cached step (rk_llama_generate, rk_llama_session_*) the row at pos sees max(0, pos - window + 1) .. pos.  The K / V cache
@@ -673,12 +697,38 @@ typedef struct rk_debug_draft_steps_call {
   rk_debug_rows_out state[RK_DEBUG_DRAFT_ARRAYS];
 } rk_debug_draft_steps_call;
 int rk_debug_draft_steps(rk_engine* e, rk_debug_draft_steps_call* call);
+/* debug: the FP8 K / V cache's quantiser (rk_llama_set_kv_fp8: the format) on n host vectors x [n][128] fp16, through the device
+ * helper every cache writer calls: q_out [n][128] bytes, exp_out [n] exponents, deq_out [n][128] the dequantised fp16 values (null:
+ * not wanted).  A finalized Llama-family engine. */
+int rk_debug_kv8_quant(rk_engine* e, const uint16_t* x, int n, uint8_t* q_out, int8_t* exp_out, uint16_t* deq_out);
+/* debug: one decoding step's attention on an FP8-cache engine (rk_llama_set_kv_fp8; RK_ERR_STATE on another) on host operands, beside
+ * rk_debug_attn kind 5 and with its operands: qkv [n_seq][ld] the step's fused rows (not rotated), pos [n_seq], cos_t / sin_t
+ * [max_pos][64], qkv_bias / qk_norm (+ qk_eps) or null, g1 / live as there (g1 > 1: the drafting step - append, then the KEYS form),
+ * the window the engine's.  cache: an fp16 cache [2][n_seq / g1][n_kv][P][128] (K then V) that the engine's quantiser converts
+ * into the layout of `mode` before the step: 0 = bytes and exponents, 1 = the fp16 layout holding the dequantised values (option
+ * llama_kv_fp8 = 0's cache).  No launch code of its own: plan_llama_dec_attn and the production launchers.
+ * Outputs, each between guard bands by rk_debug_rows_out's rule (bytes exact): ctx fp16 [n_seq][H 128]; part fp32
+ * [n_seq][H][out_nch][132], the chunk partials (132 = 128 accumulators, maximum, sum, 2 unused; a chunk no workgroup wrote keeps
+ * its pre-fill); cache_out, the cache as the step left it - mode 0: K bytes | V bytes | K exponents [..][out_pe] | V exponents
+ * (2 plane + 2 rows n_kv out_pe bytes, plane = rows n_kv P 128), mode 1: the fp16 cache (4 plane bytes).
+ * plan_only != 0: only out_R, out_nch and out_pe are filled. */
+typedef struct rk_debug_kv8_step_call {
+  int n_seq, H, n_kv, P, ld, max_pos, g1, mode, plan_only;
+  float qk_eps;
+  const uint16_t* qkv; const int32_t* pos; const float* cos_t; const float* sin_t; const float* qkv_bias; const float* qk_norm;
+  const int32_t* live; const uint16_t* cache;
+  rk_debug_rows_out ctx, part, cache_out;
+  int out_R, out_nch, out_pe;
+} rk_debug_kv8_step_call;
+int rk_debug_kv8_step(rk_engine* e, rk_debug_kv8_step_call* call);
 /* measurement: average ms per launch of the engine's GEMM kernel at one shape (epi = 0 store f16, 1 residual f32,
  * 2 GEGLU, 3 ReLU, 4 store f32), random operands, `iters` back-to-back launches timed with HIP events */
 int rk_debug_gemm_bench(rk_engine* e, int M, int N, int K, int epi, int iters, float* out_ms);
 /* debug: copy an internal activation buffer to the host as fp32. name: "enc_hidden" [T,d], "enc_out" [T,d],
  * "qkv" [T,3I], "ctx" [T,I], "dec_hidden" [B*Ld,d], "llama_last" [n_seq,hidden] (the final-normed last rows of the most recent
- * Llama call: after rk_llama_generate, the rows the last step's head read; after rk_llama_session_run, its n_slots rows). Returns number of floats written or a negative status. */
+ * Llama call: after rk_llama_generate, the rows the last step's head read; after rk_llama_session_run, its n_slots rows),
+ * "lkv" (RAW, no conversion: the bytes of the Llama K / V cache as it lies on the device, four per float slot - fp16 planes, or on
+ * an FP8-cache engine the layout at rk_llama_set_kv_fp8; rk_debug_buffers gives its capacity in 2-byte elements). Returns number of floats written or a negative status. */
 int64_t rk_debug_read(rk_engine* e, const char* name, float* out, int64_t max_floats);
 /* debug: the table of decoder graphs and what became of every decoder chain since the engine was created (csrc/rk_engine.hip:
  * run_graphed, the one function every chain of rk_t5_score / _compare / _greedy / _greedy2 / _generate, rk_llama_generate and

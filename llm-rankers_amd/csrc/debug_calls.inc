@@ -431,6 +431,7 @@ int rk_debug_attn(rk_engine* e, rk_debug_attn_call* q) {
     if (q->qk_norm && (hd != 128 || e->window > 0 || q->qkv_bias || !(q->qk_eps > 0.f)))
       return fail(e, RK_ERR_STATE, "debug attn: the step with the q / k head norm takes head_dim 128, no window, no qkv_bias and qk_eps > 0");
     lp = plan_llama_dec_attn(e, B, P, H, n_kv);
+    lp.kv8 = 0;                                               // this entry's cache is fp16 on every engine (an FP8-cache engine's: rk_debug_kv8_step)
     plan_out(lp.window > 0 ? 1 : (q->qk_norm ? 2 : 0), lp.R, lp.grid, lp.cgrid, 0);
     q->out_R = lp.R; q->out_nch = lp.nch;
     if (H % lp.R) return fail(e, RK_ERR_STATE, "debug attn: R = %d does not divide %d heads", lp.R, H);
@@ -850,8 +851,8 @@ int rk_debug_rows(rk_engine* e, rk_debug_rows_call* q) {
                            nullptr, q->n_kv, rows, (const float*)din[3], q->eps); break;
       case 9: {
         half_t* kc = (half_t*)dout[0];
-        launch_kv_fill(st, q->hd, (const half_t*)din[0], (const int*)din[1], (const int*)din[2], q->n_slots, kc,
-                       kc + (size_t)(din[2] ? q->n_slots : rows) * q->n_kv * q->P * q->hd, q->ld, q->H, q->n_kv, q->P, maxL, rows);
+        launch_kv_fill(st, q->hd, (const half_t*)din[0], (const int*)din[1], (const int*)din[2], q->n_slots,
+                       Kv8Cache{kc, kc + (size_t)(din[2] ? q->n_slots : rows) * q->n_kv * q->P * q->hd, nullptr, nullptr, 0}, q->ld, q->H, q->n_kv, q->P, maxL, rows);
       } break;
       default: {
         const int* am = (const int*)din[0] + (size_t)s * A;
@@ -1084,6 +1085,98 @@ int rk_debug_sample(rk_engine* e, rk_debug_sample_call* q) {
   return RK_OK;
 }
 
+// debug: the FP8 cache's quantiser on host vectors (include/rk_engine.h): kv8_quant16 through launch_kv8_quant
+int rk_debug_kv8_quant(rk_engine* e, const uint16_t* x, int n, uint8_t* q_out, int8_t* exp_out, uint16_t* deq_out) {
+  if (!e || !x) return RK_ERR_INVALID;
+  int rc = set_device(e);
+  if (rc) return rc;
+  if (e->family != 1 || !e->finalized) return fail(e, RK_ERR_STATE, "debug kv8 quant: a finalized Llama-family engine");
+  if (n <= 0 || n > (1 << 22)) return fail(e, RK_ERR_INVALID, "debug kv8 quant: n in 1 .. 2^22 vectors (got %d)", n);
+  hipStream_t st = e->slots[0].se;
+  DebugScratch ds(e, "debug kv8 quant");
+  const size_t N = (size_t)n * 128;
+  half_t* dX = ds.up<half_t>(x, N);
+  uint8_t* dQ = ds.alloc<uint8_t>(N, RK_DEBUG_SENTINEL);
+  int8_t* dE = ds.alloc<int8_t>((size_t)n, RK_DEBUG_SENTINEL);
+  half_t* dD = ds.alloc<half_t>(N, RK_DEBUG_SENTINEL);
+  if ((rc = ds.ready())) return rc;
+  launch_kv8_quant(st, dX, n, dQ, dE, dD);
+  DBG_HIP(ds, hipStreamSynchronize(st));
+  DBG_HIP(ds, hipGetLastError());
+  if (q_out) DBG_HIP(ds, hipMemcpy(q_out, dQ, N, hipMemcpyDeviceToHost));
+  if (exp_out) DBG_HIP(ds, hipMemcpy(exp_out, dE, (size_t)n, hipMemcpyDeviceToHost));
+  if (deq_out) DBG_HIP(ds, hipMemcpy(deq_out, dD, N * 2, hipMemcpyDeviceToHost));
+  return RK_OK;
+}
+
+// debug: one step's attention of an FP8-cache engine on host operands (include/rk_engine.h).  No launch code of its own: the
+// caller's fp16 cache goes through launch_kv8_quant into the layout of the mode, then plan_llama_dec_attn and launch_llama_dec_attn /
+// launch_llama_dec_attn_keys - llama_step_rows' branch.
+int rk_debug_kv8_step(rk_engine* e, rk_debug_kv8_step_call* q) {
+  if (!e || !q) return RK_ERR_INVALID;
+  int rc = set_device(e);
+  if (rc) return rc;
+  if (!e->finalized || e->family != 1 || !e->kv_fp8) return fail(e, RK_ERR_STATE, "debug kv8 step: a finalized Llama-family engine with an FP8 K / V cache (rk_llama_set_kv_fp8)");
+  const int B = q->n_seq, H = q->H, n_kv = q->n_kv, P = q->P, hd = 128, g1 = q->g1 > 1 ? q->g1 : 1;
+  if (B <= 0 || B > 4096 || H <= 0 || H > 1024 || n_kv <= 0 || H % n_kv || P <= 0 || P > (1 << 20) || q->mode < 0 || q->mode > 1)
+    return fail(e, RK_ERR_INVALID, "debug kv8 step: n_seq, H, n_kv (divides H), P and mode 0 / 1");
+  if (q->g1 < 0 || q->g1 > 8 || B % g1) return fail(e, RK_ERR_INVALID, "debug kv8 step: g1 in 0..8 and n_seq a multiple of it (g1 = %d, n_seq = %d)", q->g1, B);
+  if (q->ld < (H + 2 * n_kv) * hd || q->ld % 8 || q->ld > (1 << 20)) return fail(e, RK_ERR_INVALID, "debug kv8 step: ld %d >= %d, a multiple of 8", q->ld, (H + 2 * n_kv) * hd);
+  if (q->qk_norm && (e->window > 0 || q->qkv_bias || !(q->qk_eps > 0.f)))
+    return fail(e, RK_ERR_STATE, "debug kv8 step: the step with the q / k head norm takes no window, no qkv_bias and qk_eps > 0");
+  LlamaDecAttnPlan lp = plan_llama_dec_attn(e, B, P, H, n_kv);
+  lp.kv8 = q->mode ? 2 : 1;                                  // (the engine's option chooses between the two; the call names one)
+  const int rows = B / g1, pe = (P + 31) & ~31;
+  q->out_R = lp.R; q->out_nch = lp.nch; q->out_pe = pe;
+  if (H % lp.R) return fail(e, RK_ERR_STATE, "debug kv8 step: R = %d does not divide %d heads", lp.R, H);
+  if (q->plan_only) return RK_OK;
+  if (!q->qkv || !q->pos || !q->cos_t || !q->sin_t || !q->cache || (g1 > 1 && !q->live)) return fail(e, RK_ERR_INVALID, "debug kv8 step: qkv, pos, cos_t, sin_t, cache (and live with g1 > 1)");
+  for (int b = 0; b < B; ++b)
+    if (q->pos[b] < 0 || q->pos[b] >= P || q->pos[b] >= q->max_pos) return fail(e, RK_ERR_INVALID, "debug kv8 step: pos[%d] = %d outside the cache of %d / the tables of %d", b, q->pos[b], P, q->max_pos);
+  const size_t plane = (size_t)rows * n_kv * P * hd, nvec = (size_t)rows * n_kv * P, eplane = (size_t)rows * n_kv * pe;
+  const size_t cache_bytes = q->mode ? 4 * plane : 2 * plane + 2 * eplane;
+  const size_t ctx_bytes = (size_t)B * H * hd * 2, part_bytes = (size_t)B * H * lp.nch * ldc_pstr(hd) * 4;
+  if (nvec > (1u << 22) || !band_out_ok(q->ctx, (int64_t)ctx_bytes, BAND_EXACT) || !band_out_ok(q->part, (int64_t)part_bytes, BAND_EXACT) ||
+      !band_out_ok(q->cache_out, (int64_t)cache_bytes, BAND_EXACT))
+    return fail(e, RK_ERR_INVALID, "debug kv8 step: ctx (%zu bytes), part (%zu) and cache_out (%zu) as rk_debug_rows_out with bands of 64 bytes or more, multiples of 16; at most 2^22 cached vectors", ctx_bytes, part_bytes, cache_bytes);
+  hipStream_t st = e->slots[0].se;
+  DebugScratch ds(e, "debug kv8 step");
+  half_t* dQkv = ds.up<half_t>(q->qkv, (size_t)B * q->ld);
+  half_t* dC16 = ds.up<half_t>(q->cache, 2 * plane);
+  int* dPos = ds.up<int>(q->pos, (size_t)B);
+  float* dCos = ds.up<float>(q->cos_t, (size_t)q->max_pos * 64);
+  float* dSin = ds.up<float>(q->sin_t, (size_t)q->max_pos * 64);
+  float* dBias = q->qkv_bias ? ds.up<float>(q->qkv_bias, (size_t)(H + 2 * n_kv) * hd) : nullptr;
+  float* dQkn = q->qk_norm ? ds.up<float>(q->qk_norm, (size_t)2 * hd) : nullptr;
+  int* dLive = g1 > 1 ? ds.up<int>(q->live, (size_t)B) : nullptr;
+  uint8_t* dQ = ds.alloc<uint8_t>(2 * plane);                // the quantiser's dense outputs: bytes, exponents [2][nvec], dequantised
+  int8_t* dE = ds.alloc<int8_t>(2 * nvec);
+  half_t* dD = ds.alloc<half_t>(2 * plane);
+  const Banded Ctx = ds.banded(q->ctx), Part = ds.banded(q->part);
+  const Banded Cache = ds.banded(BandSpan{cache_bytes, (size_t)q->cache_out.band});   // (its interior comes from the quantiser)
+  if ((rc = ds.ready())) return rc;
+  launch_kv8_quant(st, dC16, (int)(2 * nvec), dQ, dE, dD);
+  char* ci = Cache.interior<char>();
+  Kv8Cache cc{(half_t*)ci, (half_t*)(ci + (q->mode ? 2 * plane : plane)), nullptr, nullptr, 0};
+  if (q->mode) DBG_HIP(ds, hipMemcpyAsync(ci, dD, 4 * plane, hipMemcpyDeviceToDevice, st));
+  else {
+    cc.ke = (int8_t*)(ci + 2 * plane); cc.ve = cc.ke + eplane; cc.pe = pe;
+    DBG_HIP(ds, hipMemcpyAsync(ci, dQ, 2 * plane, hipMemcpyDeviceToDevice, st));
+    DBG_HIP(ds, hipMemsetAsync(cc.ke, 0, 2 * eplane, st));   // (the pad behind P: no kernel reads it as a visible key's)
+    DBG_HIP(ds, hipMemcpy2DAsync(cc.ke, (size_t)pe, dE, (size_t)P, (size_t)P, 2 * (size_t)rows * n_kv, hipMemcpyDeviceToDevice, st));
+  }
+  const float scale_log2e = (1.0f / std::sqrt((float)hd)) * 1.4426950408889634f;
+  const LlamaDecAttnArgs aa{dQkv, cc.kc, cc.vc, dPos, dCos, dSin, Part.interior<float>(), Ctx.interior<half_t>(), q->ld, H, n_kv, P, lp.nch, scale_log2e, dBias, 0, dQkn, q->qk_eps};
+  if (g1 == 1) launch_llama_dec_attn(e, st, lp, aa, B, Kv8Ext{cc.ke, cc.ve, cc.pe});
+  else launch_llama_dec_attn_keys(e, st, lp, LlamaDecAttnKeysArgs{aa, g1, dLive}, B, Kv8Ext{cc.ke, cc.ve, cc.pe});
+  DBG_HIP(ds, hipStreamSynchronize(st));
+  DBG_HIP(ds, hipGetLastError());
+  DBG_HIP(ds, Ctx.read_back(q->ctx.all));
+  DBG_HIP(ds, Part.read_back(q->part.all));
+  DBG_HIP(ds, Cache.read_back(q->cache_out.all));
+  return RK_OK;
+}
+
 int64_t rk_debug_read(rk_engine* e, const char* name, float* out, int64_t max_floats) {
   if (!e || !name || !out) return RK_ERR_INVALID;
   if (set_device(e)) return RK_ERR_HIP;
@@ -1119,6 +1212,7 @@ int64_t rk_debug_read(rk_engine* e, const char* name, float* out, int64_t max_fl
   else if (n == "xn") { src = sl.enc.xn; cnt = (int64_t)sl.T * dm; }
   else if (n == "llama_last") { src = sl.dlast; cnt = (int64_t)sl.n_seq * dm; }   // final-normed last rows of the most recent Llama call (a session's step: n_slots rows)
   else if (n == "dec_hidden") { src = sl.dec.hidden; cnt = (int64_t)sl.n_seq * e->d.max_dec_len * dm; is_half = false; }
+  else if (n == "lkv") { src = e->lkv.p; cnt = (int64_t)(e->lkv.cap / 2); is_half = false; }   // RAW: the Llama K / V cache's bytes, four per float slot, in its layout
   else return fail(e, RK_ERR_INVALID, "unknown buffer %s", name);
   cnt = std::min(cnt, max_floats);
   if (is_half) {

@@ -307,6 +307,8 @@ __global__ __launch_bounds__(256) void attn_causal128_kernel(AttnCausalArgs p) {
 // SLOTS is the decoding session's fill (rk_llama_session_admit): the same copy, but sequence b of the call goes to cache row
 // slots[b] of a cache of n_slots rows that holds other, running rows - two 16-byte stores per thread, addresses from the slot map
 // alone.  Without SLOTS sequence b goes to row b and slots / n_slots are null / 0.
+// (An FP8-cache engine, rk_llama_set_kv_fp8, keeps bytes and exponents instead and fills them with kv8_cache_fill_kernel:
+// llama_kernels_kv8.h.)
 template <int D, bool SLOTS>
 __global__ __launch_bounds__(256) void kv_cache_fill_kernel(const half_t* __restrict__ qkv, const int* __restrict__ seq_off,
                                                             const int* __restrict__ slots, int n_slots,
@@ -356,6 +358,11 @@ __device__ __forceinline__ void rope64_pairs(const half_t* __restrict__ head, co
 
 __device__ __forceinline__ half8 qkn_lane8(const half_t* row, const float* w, float eps, int n_heads, int hd, int i0, bool hi,
                                            const float (&co)[8], const float (&si)[8]);   // llama_kernels_qknorm.h
+
+typedef unsigned kv8_u2 __attribute__((ext_vector_type(2)));   // a lane's 8 bytes of an FP8 cache vector
+typedef unsigned kv8_u4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ half8 kv8_quant16(const half8 x, kv8_u2& q, int& e);   // llama_kernels_kv8.h
+__device__ __forceinline__ half8 kv8_deq8(const kv8_u2 q, int e);
 
 // The step's rotation of the new row, the one thing the two widths do differently: this lane's 8 dims (elements i0 .. i0 + 7 of
 // the first half of the head, or with `hi` their partners in the second) of rotated head hd (of q | k) of `row`, rounded as the
@@ -444,9 +451,16 @@ __device__ __forceinline__ half8 rope_lane8(const half_t* row, const float* bias
 // (kv_cache_append_kernel ran in front): no new key is formed, none is selected and nothing is written.  The bytes the append left
 // are the bytes `knew` / `vnew` hold in the plain form, so a row's context is the plain kernel's bit for bit.  KEYS = false is the
 // kernel as it was.
-template <int D, int R, bool BIAS, bool WIN, bool QKN = false, bool KEYS = false, class ARGS = LlamaDecAttnArgs>
+// KV8 (an FP8-cache engine, rk_llama_set_kv_fp8; the entries and the format: llama_kernels_kv8.h; ARGS = LlamaDecAttnKv8Args): the
+// cache's element type.  0: fp16, the kernel as it was.  1: one e4m3fn byte per value and one exponent per vector - a lane loads 8
+// bytes of K and 8 of V, the wave its 32 keys' exponents as two 16-byte loads per plane, and kv8_deq8 turns each piece into the half8
+// the fp16 kernel loads from the dequantised cache (exact), so everything behind the loads is the same text.  2: the fp16 cache
+// holding dequantised values (option llama_kv_fp8 = 0).  1 and 2: the row's own key and value pass through kv8_quant16 before they
+// are used and before they are stored - the row sees its key as every later step reads it back.
+template <int D, int R, bool BIAS, bool WIN, bool QKN = false, bool KEYS = false, class ARGS = LlamaDecAttnArgs, int KV8 = 0>
 __device__ __forceinline__ void attn_dec_cached_body(const ARGS& p) {
   static_assert(D == 128 || D == 64, "lanes per key 16 or 8");
+  static_assert(KV8 == 0 || D == 128, "FP8 K / V cache: head_dim 128");
   constexpr int LK = D / 8, KL = 512 / D, NL = D / 16;   // lanes per key, keys per wave load, loads per wave
   __shared__ float s_m[4][R], s_l[4][R];
   __shared__ __attribute__((aligned(16))) float s_acc[4][R][D];
@@ -478,12 +492,32 @@ __device__ __forceinline__ void attn_dec_cached_body(const ARGS& p) {
     vnew = *(const half8*)(row + voff);
     if constexpr (BIAS) vnew = bias_v8(vnew, p.bias + voff);
   }
+  [[maybe_unused]] kv8_u2 kq_new, vq_new;                 // KV8: the new vectors' bytes and exponents
+  [[maybe_unused]] int ke_new = 0, ve_new = 0;
+  if constexpr (KV8 != 0 && !KEYS) {                      // every lane of the workgroup is here: a key's 16 lanes reduce together
+    knew = kv8_quant16(knew, kq_new, ke_new);
+    vnew = kv8_quant16(vnew, vq_new, ve_new);
+  }
   half_t* kbase = p.kc + ((size_t)crow * p.n_kv + kvh) * p.P * D + c * 8;
   half_t* vbase = p.vc + ((size_t)crow * p.n_kv + kvh) * p.P * D + c * 8;
+  [[maybe_unused]] uint8_t *kb8 = nullptr, *vb8 = nullptr;   // KV8 = 1: p.kc / p.vc are byte planes, p.ke / p.ve the exponents [..][pe]
+  [[maybe_unused]] int8_t *keb = nullptr, *veb = nullptr;
+  if constexpr (KV8 == 1) {
+    kb8 = (uint8_t*)p.kc + ((size_t)crow * p.n_kv + kvh) * p.P * D + c * 8;
+    vb8 = (uint8_t*)p.vc + ((size_t)crow * p.n_kv + kvh) * p.P * D + c * 8;
+    keb = p.ke + ((size_t)crow * p.n_kv + kvh) * p.pe;
+    veb = p.ve + ((size_t)crow * p.n_kv + kvh) * p.pe;
+  }
   if constexpr (!KEYS) {
     if (pos - key0 < LDC_CHUNK && h0 % G == 0 && wave == 0 && kg == 0) {   // the position's chunk, once per kv head
-      *(half8*)(kbase + (size_t)pos * D) = knew;
-      *(half8*)(vbase + (size_t)pos * D) = vnew;
+      if constexpr (KV8 == 1) {
+        *(kv8_u2*)(kb8 + (size_t)pos * D) = kq_new;
+        *(kv8_u2*)(vb8 + (size_t)pos * D) = vq_new;
+        if (c == 0) { keb[pos] = (int8_t)ke_new; veb[pos] = (int8_t)ve_new; }
+      } else {
+        *(half8*)(kbase + (size_t)pos * D) = knew;
+        *(half8*)(vbase + (size_t)pos * D) = vnew;
+      }
     }
   }
   const int wkey0 = key0 + wave * 32;
@@ -497,12 +531,37 @@ __device__ __forceinline__ void attn_dec_cached_body(const ARGS& p) {
   if (wkey0 <= pos && (!WIN || wkey0 + 31 >= lo)) {       // wave-uniform
     half8 kf[NL], vf[NL];
     const int last_old = KEYS ? pos : (pos > 0 ? pos - 1 : 0);   // keys before the new one come from the cache (KEYS: all of them)
+    if constexpr (KV8 == 1) {
+      // the wave's 32 exponents per plane (wkey0 is a multiple of 32, pe too: aligned, inside the plane), every piece requested
+      // before the first conversion.  Key wkey0 + 4 i + kg: byte kg of word i.  An exponent beyond the row's last written position
+      // belongs to a key that is masked or replaced below; whatever the byte holds is clamped to the format's range, so the
+      // masked product stays finite.
+      kv8_u2 kq[NL], vq[NL];
+      const kv8_u4 kew0 = *(const kv8_u4*)(keb + wkey0), kew1 = *(const kv8_u4*)(keb + wkey0 + 16);
+      const kv8_u4 vew0 = *(const kv8_u4*)(veb + wkey0), vew1 = *(const kv8_u4*)(veb + wkey0 + 16);
 #pragma unroll
-    for (int i = 0; i < NL; ++i) {
-      const int key = wkey0 + KL * i + kg;
-      const int idx = key < last_old ? key : last_old;
-      kf[i] = *(const half8*)(kbase + (size_t)idx * D);
-      vf[i] = *(const half8*)(vbase + (size_t)idx * D);
+      for (int i = 0; i < NL; ++i) {
+        const int key = wkey0 + KL * i + kg;
+        const int idx = key < last_old ? key : last_old;
+        kq[i] = *(const kv8_u2*)(kb8 + (size_t)idx * D);
+        vq[i] = *(const kv8_u2*)(vb8 + (size_t)idx * D);
+      }
+      const int sh = 24 - 8 * kg;
+#pragma unroll
+      for (int i = 0; i < NL; ++i) {
+        const unsigned kw = i < 4 ? kew0[i & 3] : kew1[i & 3], vw = i < 4 ? vew0[i & 3] : vew1[i & 3];
+        const int ek = (int)(kw << sh) >> 24, ev = (int)(vw << sh) >> 24;
+        kf[i] = kv8_deq8(kq[i], min(max(ek, -15), 7));
+        vf[i] = kv8_deq8(vq[i], min(max(ev, -15), 7));
+      }
+    } else {
+#pragma unroll
+      for (int i = 0; i < NL; ++i) {
+        const int key = wkey0 + KL * i + kg;
+        const int idx = key < last_old ? key : last_old;
+        kf[i] = *(const half8*)(kbase + (size_t)idx * D);
+        vf[i] = *(const half8*)(vbase + (size_t)idx * D);
+      }
     }
     if constexpr (!KEYS) {
 #pragma unroll

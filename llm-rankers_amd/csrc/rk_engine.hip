@@ -34,6 +34,7 @@
 #include "llama_kernels.h"
 #include "llama_kernels_hd64.h"
 #include "llama_kernels_qknorm.h"
+#include "llama_kernels_kv8.h"
 #include "misc_kernels.h"
 #include "sampling_kernels.h"
 
@@ -223,7 +224,7 @@ struct rk_engine {
         gemm_persistent = 1, fold_norm = 1, s64_stages = 0, dec_fold_norm = 1, greedy_spec = 160, consumer_stats = 1, xattn_mfma = 1,
         dec_ffn_tiled = 1, gemm_split = 1, dec_fuse = 1, dec_fuse_rows = 0, dec_attn_seq = 1, attn_long = 1, attn_long_nw = 0,
         llama_attn_dma = 1, attn_long_xcd = 1, llama_attn_nw = 0, dec_graph = 1, gemm_sk = 1, dec_cross_mfma = 1, dec_gemv = 1, dec_gemv_rows = 4,
-        dec_cached_attn = 1, llama_dec_r = 0, enc_serial = 0, llama_step_fp8 = 1;
+        dec_cached_attn = 1, llama_dec_r = 0, enc_serial = 0, llama_step_fp8 = 1, llama_kv_fp8 = 1;
   } opt;
   float* attn_trace = nullptr;   // measurement builds only (option attn_trace)
   int n_cu = 256;
@@ -242,6 +243,7 @@ struct rk_engine {
   bool qkv_bias = false;                                                          // Qwen2 family: q / k / v projections carry a bias
   bool qk_norm = false;                                                           // Qwen3 family: RMSNorm over head_dim on every q and k head (rk_llama_set_qk_norm)
   bool weight_fp8 = false;                                                        // rk_llama_set_weight_fp8: the step's four projections also kept as FP8 step weights
+  bool kv_fp8 = false;                                                            // rk_llama_set_kv_fp8: the decoding step's K / V cache in FP8 (llama_kernels_kv8.h)
   int window = 0;                                                                 // Mistral family: sliding window W (rk_llama_set_sliding_window), 0 = none
   std::vector<LlamaLayerW> ll; float *l_final_ln = nullptr, *rope_cos = nullptr, *rope_sin = nullptr; int* d_pos = nullptr;
   // rk_llama_set_sampling: temperature 0 = off (every entry point is greedy); d_seeds: one Philox key per row / session slot
@@ -249,7 +251,8 @@ struct rk_engine {
   struct Sampling { float T = 0.f; int k = 0; float p = 1.f; bool on() const { return T > 0.f; } } samp;
   unsigned long long* d_seeds = nullptr;
   // rk_llama_generate: K / V cache [n_layers][2][n_seq][n_kv][P][head_dim], the attention partials and the call's int block (grown
-  // between calls; lkv_gen counts the moves and is part of the step graph's key), and the step's activation rows (max_seqs each)
+  // between calls; lkv_gen counts the moves and is part of the step graph's key), and the step's activation rows (max_seqs each).
+  // An FP8-cache engine (kv_fp8) keeps bytes and exponents in lkv instead, as raw bytes: llama_kv_layer.
   Grown<half_t> lkv; Grown<float> lpart; Grown<int> lints; int lkv_gen = 0;
   struct LlamaStep { NormStream stream; half_t *qkv = nullptr, *ctx = nullptr, *ffh = nullptr; } lg;
   Grown<half_t> lqlm_x;                                                           // rk_llama_qlm: the final-normed label-predicting rows [rows][hidden]
@@ -798,14 +801,29 @@ void launch_rope(hipStream_t st, int hd, half_t* qkv, const int* pos, const floa
   else hipLaunchKernelGGL(rope128_kernel<false>, dim3(T), dim3(256), 0, st, qkv, pos, cos_t, sin_t, ld, n_rot, (const float*)nullptr, 0);
 }
 // the prompt's rotated keys and its values into the cache: sequence b to cache row b, or to row slots[b] of n_slots
-void launch_kv_fill(hipStream_t st, int hd, const half_t* qkv, const int* seq_off, const int* slots, int n_slots, half_t* kc, half_t* vc,
-                    int ld, int n_heads, int n_kv, int P, int maxL, int n_seq) {
+// cc: the layer's cache (llama_kv_layer).  kv8 (an FP8-cache engine, 128 wide): 1 = bytes and exponents into cc's four regions, 2 = the
+// dequantised fp16 values into cc.kc / cc.vc; 0: the fp16 copy
+void launch_kv_fill(hipStream_t st, int hd, const half_t* qkv, const int* seq_off, const int* slots, int n_slots, const Kv8Cache& cc,
+                    int ld, int n_heads, int n_kv, int P, int maxL, int n_seq, int kv8 = 0) {
   const dim3 g = grid_kv_fill(maxL, n_seq), b(256);
+  const int* none = nullptr;
+  if (kv8) {
+    if (hd != 128 || (kv8 == 1 && (!cc.ke || !cc.ve || cc.pe < P))) abort();   // a byte fill without its exponent planes: a host bug
+    if (kv8 == 1 && slots) hipLaunchKernelGGL((kv8_cache_fill_kernel<true, 1>), g, b, 0, st, qkv, seq_off, slots, n_slots, cc, ld, n_heads, n_kv, P);
+    else if (kv8 == 1) hipLaunchKernelGGL((kv8_cache_fill_kernel<false, 1>), g, b, 0, st, qkv, seq_off, none, 0, cc, ld, n_heads, n_kv, P);
+    else if (slots) hipLaunchKernelGGL((kv8_cache_fill_kernel<true, 2>), g, b, 0, st, qkv, seq_off, slots, n_slots, cc, ld, n_heads, n_kv, P);
+    else hipLaunchKernelGGL((kv8_cache_fill_kernel<false, 2>), g, b, 0, st, qkv, seq_off, none, 0, cc, ld, n_heads, n_kv, P);
+    return;
+  }
   with_width(hd, [&](auto W) {
     constexpr int D = decltype(W)::value;
-    if (slots) hipLaunchKernelGGL((kv_cache_fill_kernel<D, true>), g, b, 0, st, qkv, seq_off, slots, n_slots, kc, vc, ld, n_heads, n_kv, P);
-    else hipLaunchKernelGGL((kv_cache_fill_kernel<D, false>), g, b, 0, st, qkv, seq_off, (const int*)nullptr, 0, kc, vc, ld, n_heads, n_kv, P);
+    if (slots) hipLaunchKernelGGL((kv_cache_fill_kernel<D, true>), g, b, 0, st, qkv, seq_off, slots, n_slots, cc.kc, cc.vc, ld, n_heads, n_kv, P);
+    else hipLaunchKernelGGL((kv_cache_fill_kernel<D, false>), g, b, 0, st, qkv, seq_off, none, 0, cc.kc, cc.vc, ld, n_heads, n_kv, P);
   });
+}
+// n vectors of 128 through the FP8 cache's quantiser (rk_debug_kv8_quant, rk_debug_kv8_step's cache conversion)
+void launch_kv8_quant(hipStream_t st, const half_t* x, int n, uint8_t* q, int8_t* ex, half_t* deq) {
+  hipLaunchKernelGGL(kv8_quant_rows_kernel, dim3((unsigned)(((size_t)n * 16 + 255) / 256)), dim3(256), 0, st, x, n, q, ex, deq);
 }
 void launch_greedy_advance(hipStream_t st, const int* argmax, int* state, const int* prefix, int* done, int* out, int* next_ids, int n_seq,
                            int dec_len, int max_new) {
@@ -1317,14 +1335,21 @@ int refuse_window(rk_engine* e, const char* entry, int maxL) {
 // llama_dec_r = 2 falls back to the rule there.
 // On an engine with a sliding window every step runs the windowed entries (attn_dec_cached_win_kernel, attn_dec_combine_win_kernel):
 // a model constant again.  A row at pos < W skips and masks nothing there and gets the plain kernels' bits.
-struct LlamaDecAttnPlan { int R = 1, nch = 1, hd = 128, window = 0; dim3 grid, cgrid; };
+// An FP8-cache engine (rk_llama_set_kv_fp8; 128 wide): kv8 = 1, the byte kernels (attn_dec_kv8_kernel<.., 1>, attn_dec_keys_kv8_kernel,
+// kv8_cache_append_kernel) over the four regions of Kv8Ext, or kv8 = 2 (option llama_kv_fp8 = 0), the fp16 layout holding dequantised
+// values: the fp16 reader with the rounded own key (attn_dec_kv8_kernel<.., 2>), the fp16 KEYS kernels behind the rounding append.  The
+// same rule for R; it has no R = 7 instantiation, so llama_dec_r = 2 falls back to the rule, as at width 64.
+struct LlamaDecAttnPlan { int R = 1, nch = 1, hd = 128, window = 0; dim3 grid, cgrid; int kv8 = 0; };
+struct Kv8Ext { int8_t* ke = nullptr; int8_t* ve = nullptr; int pe = 0; };
+inline int kv8_mode(const rk_engine* e) { return e->kv_fp8 ? (e->opt.llama_kv_fp8 ? 1 : 2) : 0; }
 LlamaDecAttnPlan plan_llama_dec_attn(const rk_engine* e, int rows, int P, int n_heads, int n_kv) {
   LlamaDecAttnPlan p;                                        // (no CU count enters: fixed chunk length, model-constant R)
   const int G = n_heads / n_kv;
   p.hd = head_width(e);
+  p.kv8 = kv8_mode(e);
   p.R = G % 8 == 0 ? 8 : (G % 4 == 0 ? 4 : (G % 2 == 0 ? 2 : 1));
   if (e->opt.llama_dec_r == 1) p.R = 1;
-  if (e->opt.llama_dec_r == 2 && G == 7 && p.hd == 128) p.R = 7;
+  if (e->opt.llama_dec_r == 2 && G == 7 && p.hd == 128 && !p.kv8) p.R = 7;
   p.nch = (P + LDC_CHUNK - 1) / LDC_CHUNK;
   p.grid = dim3(p.nch, n_heads / p.R, rows);
   p.cgrid = dim3(n_heads, rows);
@@ -1332,9 +1357,43 @@ LlamaDecAttnPlan plan_llama_dec_attn(const rk_engine* e, int rows, int P, int n_
   return p;
 }
 
-void launch_llama_dec_attn(rk_engine* e, hipStream_t st, const LlamaDecAttnPlan& p, LlamaDecAttnArgs a, int rows) {
+// the chunk kernel of an FP8-cache engine's step, plain (keys = false, MODE = p.kv8) or the byte KEYS form
+template <bool KEYSF>
+void launch_llama_dec_attn_kv8(hipStream_t st, const LlamaDecAttnPlan& p, const LlamaDecAttnKv8Args& a) {
+  auto go = [&](auto rc) {
+    constexpr int R = decltype(rc)::value;
+    auto form = [&](auto bias, auto win, auto qkn) {
+      constexpr bool B = decltype(bias)::value, W = decltype(win)::value, Q = decltype(qkn)::value;
+      if constexpr (KEYSF) hipLaunchKernelGGL((attn_dec_keys_kv8_kernel<R, B, W, Q>), p.grid, dim3(256), 0, st, a);
+      else if (p.kv8 == 1) hipLaunchKernelGGL((attn_dec_kv8_kernel<R, B, W, Q, 1>), p.grid, dim3(256), 0, st, a);
+      else hipLaunchKernelGGL((attn_dec_kv8_kernel<R, B, W, Q, 2>), p.grid, dim3(256), 0, st, a);
+    };
+    using std::true_type; using std::false_type;
+    if (a.qkn) form(false_type{}, false_type{}, true_type{});
+    else if (p.window > 0 && a.bias) form(true_type{}, true_type{}, false_type{});
+    else if (p.window > 0) form(false_type{}, true_type{}, false_type{});
+    else if (a.bias) form(true_type{}, false_type{}, false_type{});
+    else form(false_type{}, false_type{}, false_type{});
+  };
+  using std::integral_constant;
+  switch (p.R) {
+    case 8: go(integral_constant<int, 8>{}); break;
+    case 4: go(integral_constant<int, 4>{}); break;
+    case 2: go(integral_constant<int, 2>{}); break;
+    default: go(integral_constant<int, 1>{}); break;
+  }
+}
+
+void launch_llama_dec_attn(rk_engine* e, hipStream_t st, const LlamaDecAttnPlan& p, LlamaDecAttnArgs a, int rows, const Kv8Ext& x8 = {}) {
   a.nch = p.nch; a.window = p.window;
-  Bracket br(e, st, PC_DEC_ATTN, 4.0 * rows * (double)a.P * a.n_heads * p.hd, 2.0 * rows * (double)a.P * a.n_kv * p.hd * 2.0);
+  Bracket br(e, st, PC_DEC_ATTN, 4.0 * rows * (double)a.P * a.n_heads * p.hd, 2.0 * rows * (double)a.P * a.n_kv * p.hd * (p.kv8 == 1 ? 1.0 : 2.0));
+  if (p.kv8) {                                               // (128 wide: rk_engine_finalize)
+    if (p.hd != 128 || (p.kv8 == 1 && (!x8.ke || !x8.ve || x8.pe < a.P))) abort();   // a byte plan without its exponent planes: a host bug
+    launch_llama_dec_attn_kv8<false>(st, p, LlamaDecAttnKv8Args{{a, 1, nullptr}, x8.ke, x8.ve, x8.pe});
+    if (p.window > 0) hipLaunchKernelGGL(attn_dec_combine_win_kernel<128>, p.cgrid, dim3(128), 0, st, a);
+    else hipLaunchKernelGGL(attn_dec_combine_kernel<128>, p.cgrid, dim3(128), 0, st, a);
+    return;
+  }
   with_width(p.hd, [&](auto W) {
     constexpr int D = decltype(W)::value;
     auto go = [&](auto rc) {                                 // the bias-free instantiation is the Llama kernel as it was
@@ -1368,17 +1427,45 @@ void launch_llama_dec_attn(rk_engine* e, hipStream_t st, const LlamaDecAttnPlan&
 // kv_cache_append_kernel puts every live row's key and value where a plain step would have written them, then the keys-cached
 // entries (attn_dec_keys_*_kernel: the plain body without the new-key select and the cache write) run by the SAME plan rule over
 // `rows`, and the plain merge.  One more small launch per layer than the plain step.
-void launch_llama_dec_attn_keys(rk_engine* e, hipStream_t st, const LlamaDecAttnPlan& p, LlamaDecAttnKeysArgs a, int rows) {
-  a.nch = p.nch; a.window = p.window;
-  Bracket br(e, st, PC_DEC_ATTN, 4.0 * rows * (double)a.P * a.n_heads * p.hd, 2.0 * rows * (double)a.P * a.n_kv * p.hd * 2.0);
+// the append in front of a drafting step's attention: the fp16 kernel, or on an FP8-cache engine the rounding one in the plan's layout
+static void launch_kv_append(hipStream_t st, const LlamaDecAttnPlan& p, const LlamaDecAttnKeysArgs& a, int rows, const Kv8Ext& x8) {
+  const dim3 g(rows), b(256);
+  if (p.kv8) {
+    if (p.hd != 128 || (p.kv8 == 1 && (!x8.ke || !x8.ve || x8.pe < a.P))) abort();   // a byte plan without its exponent planes: a host bug
+    const LlamaDecAttnKv8Args a8{a, x8.ke, x8.ve, x8.pe};
+    auto go = [&](auto mode) {
+      constexpr int M = decltype(mode)::value;
+      if (a.qkn) hipLaunchKernelGGL((kv8_cache_append_kernel<false, true, M>), g, b, 0, st, a8);
+      else if (a.bias) hipLaunchKernelGGL((kv8_cache_append_kernel<true, false, M>), g, b, 0, st, a8);
+      else hipLaunchKernelGGL((kv8_cache_append_kernel<false, false, M>), g, b, 0, st, a8);
+    };
+    if (p.kv8 == 1) go(std::integral_constant<int, 1>{});
+    else go(std::integral_constant<int, 2>{});
+    return;
+  }
   with_width(p.hd, [&](auto W) {
     constexpr int D = decltype(W)::value;
     if (a.qkn) {
-      if constexpr (D == 128) hipLaunchKernelGGL((kv_cache_append_kernel<D, false, true>), dim3(rows), dim3(256), 0, st, a);
+      if constexpr (D == 128) hipLaunchKernelGGL((kv_cache_append_kernel<D, false, true>), g, b, 0, st, a);
       else abort();
     }
-    else if (a.bias) hipLaunchKernelGGL((kv_cache_append_kernel<D, true, false>), dim3(rows), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((kv_cache_append_kernel<D, false, false>), dim3(rows), dim3(256), 0, st, a);
+    else if (a.bias) hipLaunchKernelGGL((kv_cache_append_kernel<D, true, false>), g, b, 0, st, a);
+    else hipLaunchKernelGGL((kv_cache_append_kernel<D, false, false>), g, b, 0, st, a);
+  });
+}
+void launch_llama_dec_attn_keys(rk_engine* e, hipStream_t st, const LlamaDecAttnPlan& p, LlamaDecAttnKeysArgs a, int rows, const Kv8Ext& x8 = {}) {
+  a.nch = p.nch; a.window = p.window;
+  Bracket br(e, st, PC_DEC_ATTN, 4.0 * rows * (double)a.P * a.n_heads * p.hd, 2.0 * rows * (double)a.P * a.n_kv * p.hd * (p.kv8 == 1 ? 1.0 : 2.0));
+  launch_kv_append(st, p, a, rows, x8);
+  if (p.kv8 == 1) {                                          // the byte KEYS kernels; kv8 = 2: the fp16 KEYS kernels below, on the dequantised values
+    launch_llama_dec_attn_kv8<true>(st, p, LlamaDecAttnKv8Args{a, x8.ke, x8.ve, x8.pe});
+    const LlamaDecAttnArgs base = a;
+    if (p.window > 0) hipLaunchKernelGGL(attn_dec_combine_win_kernel<128>, p.cgrid, dim3(128), 0, st, base);
+    else hipLaunchKernelGGL(attn_dec_combine_kernel<128>, p.cgrid, dim3(128), 0, st, base);
+    return;
+  }
+  with_width(p.hd, [&](auto W) {
+    constexpr int D = decltype(W)::value;
     auto go = [&](auto rc) {
       constexpr int R = decltype(rc)::value;
       if constexpr (R == 7 && D != 128) abort();             // no such kernel: plan_llama_dec_attn gives R = 7 at 128 alone
@@ -2815,6 +2902,8 @@ static int llama_finalize(rk_engine* e) {
   if (e->qk_norm && (hd != 128 || e->window > 0 || e->qkv_bias))
     return fail(e, RK_ERR_STATE, "the q / k head norm (rk_llama_set_qk_norm) is built for head_dim 128 without a sliding window and without q / k / v biases (got head_dim %d, window %d, biases %d): no Qwen3 checkpoint has another shape", hd, e->window, (int)e->qkv_bias);
   if (e->qk_norm && !(l.eps > 0.f)) return fail(e, RK_ERR_INVALID, "the q / k head norm needs rms_norm_eps > 0 (got %g)", (double)l.eps);
+  if (e->kv_fp8 && hd != 128)
+    return fail(e, RK_ERR_STATE, "the FP8 K / V cache (rk_llama_set_kv_fp8) is built for head_dim 128 (got %d): the 64-wide models' caches are small, and no 64-wide FP8 kernels are built", hd);
   std::string missing;
   auto N2 = [&](const std::string& n, int64_t r, int64_t c) { return need(e, n, r, c, &missing); };
   auto N1 = [&](const std::string& n, int64_t r) { return need(e, n, r, -1, &missing); };
@@ -2930,6 +3019,22 @@ static int llama_finalize(rk_engine* e) {
 // keep (rk_llama_generate only): every layer's rotated K and its V are also copied to the cache, P positions per sequence
 // slots (rk_llama_session_admit): sequence b goes to cache row slots[b] (device ints) of a cache of `rows` rows
 struct LlamaKeep { half_t* kv; int P; const int* slots = nullptr; int rows = 0; };
+// One layer's K / V cache inside lkv, for `rows` cache rows of P positions.  fp16 layout (kv8 = 0, and 2: the dequantised values):
+// K [rows][n_kv][P][hd] then V.  kv8 = 1 (llama_kernels_kv8.h): K bytes | V bytes | K exponents [rows][n_kv][pe] | V exponents,
+// pe = P rounded up to 32 - every region a multiple of 32 bytes, so each starts 32-byte aligned in hipMalloc's block.
+static size_t llama_kv_layer_halfs(const rk_engine* e, int kv8, int rows, int P) {
+  const size_t KV = (size_t)e->ld.n_kv_heads * e->ld.head_dim, pe = ((size_t)P + 31) & ~(size_t)31;
+  return kv8 == 1 ? ((size_t)rows * KV * P + (size_t)rows * e->ld.n_kv_heads * pe) : 2 * (size_t)rows * KV * P;   // (bytes / 2)
+}
+static Kv8Cache llama_kv_layer(const rk_engine* e, half_t* base, int kv8, int layer, int rows, int P) {
+  const size_t KV = (size_t)e->ld.n_kv_heads * e->ld.head_dim, plane = (size_t)rows * KV * P;
+  half_t* l0 = base + (size_t)layer * llama_kv_layer_halfs(e, kv8, rows, P);
+  if (kv8 != 1) return Kv8Cache{l0, l0 + plane, nullptr, nullptr, 0};
+  const int pe = (P + 31) & ~31;
+  uint8_t* b0 = (uint8_t*)l0;
+  int8_t* e0 = (int8_t*)(b0 + 2 * plane);
+  return Kv8Cache{(half_t*)b0, (half_t*)(b0 + plane), e0, e0 + (size_t)rows * e->ld.n_kv_heads * pe, pe};
+}
 static int llama_prefill(rk_engine* e, const int32_t* tokens, const int32_t* off, int n_seq, const LlamaKeep* keep = nullptr) {
   if (!e || e->family != 1) return fail(e, RK_ERR_STATE, "not a Llama engine");
   int rc = set_device(e);
@@ -2963,10 +3068,10 @@ static int llama_prefill(rk_engine* e, const int32_t* tokens, const int32_t* off
       launch_rope(st, hd, sl.qkv, e->d_pos, e->rope_cos, e->rope_sin, ldq, l.n_heads + l.n_kv_heads, w.qkv_bias, l.n_kv_heads, T, w.qk_norm, l.eps);
     }
     if (keep) {
-      const size_t half_layer = (size_t)(keep->slots ? keep->rows : n_seq) * KV * keep->P;
-      half_t* kc = keep->kv + (size_t)i * 2 * half_layer;
+      const int kv8 = kv8_mode(e);
+      const Kv8Cache cc = llama_kv_layer(e, keep->kv, kv8, i, keep->slots ? keep->rows : n_seq, keep->P);
       Bracket br(e, st, PC_OTHER, 0, (double)T * KV * 8.0);
-      launch_kv_fill(st, hd, sl.qkv, sl.d_seq_off, keep->slots, keep->rows, kc, kc + half_layer, ldq, l.n_heads, l.n_kv_heads, keep->P, sl.maxL, n_seq);
+      launch_kv_fill(st, hd, sl.qkv, sl.d_seq_off, keep->slots, keep->rows, cc, ldq, l.n_heads, l.n_kv_heads, keep->P, sl.maxL, n_seq, kv8);
     }
     launch_llama_attn(e, st, CausalAttnCall{sl.qkv, sl.ctx, sl.d_seq_off, ldq, Q, l.n_heads, l.n_kv_heads, sl.n_seq, sl.maxL, T}, ap);
     RC(ns.producer(e, st, Gemm(PC_ENC_GEMM_O, EPI_RESID_F32, sl.ctx, Q, w.o, Q, ns.hidden, dm, T, dm, Q)));
@@ -3087,6 +3192,14 @@ int rk_llama_set_weight_fp8(rk_engine* e, int on) {
   return RK_OK;
 }
 
+int rk_llama_set_kv_fp8(rk_engine* e, int on) {
+  if (!e) return RK_ERR_INVALID;
+  if (e->family != 1) return fail(e, RK_ERR_STATE, "the FP8 K / V cache applies to Llama-family engines (rk_llama_create)");
+  if (e->finalized) return fail(e, RK_ERR_STATE, "rk_llama_set_kv_fp8 must precede rk_engine_finalize (the head width is checked there)");
+  e->kv_fp8 = on != 0;
+  return RK_OK;
+}
+
 int rk_llama_greedy1(rk_engine* e, const int32_t* tokens, const int32_t* seq_offsets, int n_seq, int32_t* out_tokens) {
   if (!e || !out_tokens) return RK_ERR_INVALID;
   if (e->ls.open) return fail(e, RK_ERR_STATE, "rk_llama_greedy1 while a decoding session is open (it shares the prefill's buffers): rk_llama_session_close first");
@@ -3107,7 +3220,7 @@ int rk_llama_greedy1(rk_engine* e, const int32_t* tokens, const int32_t* seq_off
 static int ensure_llama_gen(rk_engine* e, int n_seq, int P, size_t ints, int step_rows = 0) {
   const rk_llama_desc& l = e->ld;
   const size_t S = (size_t)l.max_seqs, dm = l.hidden, Q = (size_t)l.n_heads * l.head_dim, KV = (size_t)l.n_kv_heads * l.head_dim, F = l.intermediate;
-  const size_t kv = (size_t)l.n_layers * 2 * n_seq * KV * P;
+  const size_t kv = (size_t)l.n_layers * llama_kv_layer_halfs(e, kv8_mode(e), n_seq, P);   // (fp16: n_layers * 2 * n_seq * KV * P)
   const size_t part = (size_t)std::max(n_seq, step_rows) * l.n_heads * ((P + LDC_CHUNK - 1) / LDC_CHUNK) * ldc_pstr(l.head_dim);
   int rc = RK_OK;
   RC(e->lkv.reserve(e, kv, &e->lkv_gen)); RC(e->lpart.reserve(e, part, &e->lkv_gen)); RC(e->lints.reserve(e, ints, &e->lkv_gen));
@@ -3131,7 +3244,6 @@ static int llama_step_rows(rk_engine* e, hipStream_t st, int rows, int P, const 
   const rk_llama_desc& l = e->ld;
   const int dm = l.hidden, Q = l.n_heads * l.head_dim, KV = l.n_kv_heads * l.head_dim, F = l.intermediate, ldq = Q + 2 * KV;
   const LlamaDecAttnPlan ap = plan_llama_dec_attn(e, rows, P, l.n_heads, l.n_kv_heads);
-  const size_t half_layer = (size_t)(rows / g1) * KV * P;
   const float scale_log2e = (1.0f / std::sqrt((float)l.head_dim)) * 1.4426950408889634f;
   const auto& lg = e->lg;
   int rc = RK_OK;
@@ -3146,11 +3258,11 @@ static int llama_step_rows(rk_engine* e, hipStream_t st, int rows, int P, const 
   for (int i = 0; i < l.n_layers; ++i) {
     const LlamaLayerW& w = e->ll[i];
     RC(gemm(e, st, normed(Gemm(PC_DEC_GEMM, EPI_STORE_F16, ns.x(), dm, w.qkv_f, dm, lg.qkv, ldq, rows, ldq, dm).w8(b8(w.qkv8)))));
-    half_t* kc = e->lkv.p + (size_t)i * 2 * half_layer;
-    const LlamaDecAttnArgs aa{lg.qkv, kc, kc + half_layer, d_pos, e->rope_cos, e->rope_sin, e->lpart.p, lg.ctx,
+    const Kv8Cache cc = llama_kv_layer(e, e->lkv.p, ap.kv8, i, rows / g1, P);
+    const LlamaDecAttnArgs aa{lg.qkv, cc.kc, cc.vc, d_pos, e->rope_cos, e->rope_sin, e->lpart.p, lg.ctx,
                               ldq, l.n_heads, l.n_kv_heads, P, ap.nch, scale_log2e, w.qkv_bias, 0, w.qk_norm, l.eps};
-    if (g1 == 1) launch_llama_dec_attn(e, st, ap, aa, rows);
-    else launch_llama_dec_attn_keys(e, st, ap, LlamaDecAttnKeysArgs{aa, g1, d_live}, rows);
+    if (g1 == 1) launch_llama_dec_attn(e, st, ap, aa, rows, Kv8Ext{cc.ke, cc.ve, cc.pe});
+    else launch_llama_dec_attn_keys(e, st, ap, LlamaDecAttnKeysArgs{aa, g1, d_live}, rows, Kv8Ext{cc.ke, cc.ve, cc.pe});
     RC(ns.producer(e, st, Gemm(PC_DEC_GEMM, EPI_RESID_F32, lg.ctx, Q, w.o, Q, ns.hidden, dm, rows, dm, Q).on(GEMM_STREAM).w8(b8(w.o8))));
     RC(gemm(e, st, normed(Gemm(PC_DEC_GEMM, EPI_SWIGLU_F16, ns.x(), dm, w.gu_f, dm, lg.ffh, F, rows, 2 * F, dm).w8(b8(w.gu8)))));
     RC(ns.producer(e, st, Gemm(PC_DEC_GEMM, EPI_RESID_F32, lg.ffh, F, w.down, F, ns.hidden, dm, rows, dm, F).on(GEMM_STREAM).w8(b8(w.down8)), i + 1 < l.n_layers));
@@ -3175,6 +3287,7 @@ static std::vector<int> llama_step_key(const rk_engine* e, bool session, int row
   std::vector<int> key{kind, 0, rows, P, cap, sampled ? e->logits_gen : e->amax_gen, e->lkv_gen, draft};
   if (!draft) key.pop_back();                              // (Kd stands in a drafting session's key only, cap in a session's only)
   if (!session) key.erase(key.begin() + 4);
+  if (e->kv_fp8) key.push_back(kv8_mode(e));               // an FP8-cache engine: which cache layout the step's kernels address
   return key;
 }
 // the stop ids of rk_llama_generate and of a session: at most INTS_MAX_EOS EOS ids and the pad id, all inside the vocabulary
@@ -3778,6 +3891,7 @@ const OptionDesc kOptions[] = {
   {"llama_dec_r", &rk_engine::Options::llama_dec_r, 0, 2, nullptr, "rk_llama_generate's attention: query heads per workgroup by plan_llama_dec_attn's rule (0), one (1), or, where a kv head has 7, all seven (2: measurement and tests; every cached K / V byte read once per step); same bits"},
   {"enc_serial", &rk_engine::Options::enc_serial, 0, 1, nullptr, "two slots: an encoder chain starts behind the other slot's (1: one encoder at a time beside the decoder before it) or as soon as it is enqueued (0: two chains interleave); same bits"},
   {"llama_step_fp8", &rk_engine::Options::llama_step_fp8, 0, 1, nullptr, "FP8 engines: the step's projections read the FP8 bytes (1, default) or the dequantised fp16 matrices through the fp16 kernel (0); same bits; no effect on an engine without FP8 weights"},
+  {"llama_kv_fp8", &rk_engine::Options::llama_kv_fp8, 0, 1, nullptr, "FP8-cache engines (rk_llama_set_kv_fp8): the step reads the cache's FP8 bytes (1, default) or keeps an fp16-layout cache of the dequantised values and reads it with the fp16 kernels (0); same bits; the cache contents do not survive a change, which is refused while a decoding session is open; no effect on an engine without an FP8 cache"},
   {"gemm_split", &rk_engine::Options::gemm_split, 0, 1, nullptr, "rows beyond the ping-pong kernel's last whole round on a fill-in tile variant (1) or one launch (0); same bits"},
 #ifdef RK_MEASURE
   {"attn_ko", &rk_engine::Options::attn_ko, 0, 1 << 20, nullptr, "timing-only knock-outs of the attention kernels (measurement builds)"},
@@ -3817,6 +3931,8 @@ int rk_engine_set_option(rk_engine* e, const char* key, int value) {
   for (const OptionDesc& o : kOptions) {
     if (strcmp(key, o.key)) continue;
     if (!strcmp(key, "gemm_skinny") && value == 1) value = 0x3F;
+    if (!strcmp(key, "llama_kv_fp8") && e->ls.open)           // the open session's cache is laid out for the current value
+      return fail(e, RK_ERR_STATE, "option llama_kv_fp8 while a decoding session is open (its cache would change layout): rk_llama_session_close first");
     if (!option_value_ok(o, value))
       return fail(e, RK_ERR_INVALID, "option %s: value %d outside %d..%d%s%s (%s)", key, value, o.lo, o.hi, o.allowed ? ", allowed: " : "", o.allowed ? o.allowed : "", o.what);
     e->opt.*(o.field) = value;

@@ -15,7 +15,7 @@ import numpy as np
 # the rk_debug_* side of the ABI: its call structs and constants (part of this module's names, as ever) and RkEngine's debug methods
 from ._engine_debug import (BUFFER_NAMES, DEBUG_BAND_ROWS, DEBUG_SENTINEL, DRAFT_ARRAYS, GEMM_OUT_DTYPE,  # noqa: F401
                             DebugCalls, RkDebugAttnCall, RkDebugBuffers, RkDebugDraftStepsCall, RkDebugGemmCall,
-                            RkDebugGemmChainCall, RkDebugGraphStats, RkDebugRowsCall, RkDebugRowsIn, RkDebugRowsOut,
+                            RkDebugGemmChainCall, RkDebugGraphStats, RkDebugKv8StepCall, RkDebugRowsCall, RkDebugRowsIn, RkDebugRowsOut,
                             RkDebugSampleCall, RkDebugXattnChainCall)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -74,6 +74,7 @@ ABI = {
     "rk_llama_set_qk_norm": (C.c_int, [C.c_void_p, C.c_int]),
     "rk_llama_set_sliding_window": (C.c_int, [C.c_void_p, C.c_int]),
     "rk_llama_set_weight_fp8": (C.c_int, [C.c_void_p, C.c_int]),
+    "rk_llama_set_kv_fp8": (C.c_int, [C.c_void_p, C.c_int]),
     "rk_llama_greedy1": (C.c_int, [C.c_void_p, _i32p, _i32p, C.c_int, _i32p]),
     "rk_llama_last_logits": (C.c_int, [C.c_void_p, _i32p, _i32p, C.c_int, _i32p, C.c_int, _f32p]),
     "rk_llama_qlm": (C.c_int, [C.c_void_p, _i32p, _i32p, C.c_int, _i32p, _f32p]),
@@ -122,6 +123,8 @@ ABI = {
     "rk_debug_xattn_chain": (C.c_int, [C.c_void_p, _P(RkDebugXattnChainCall)]),
     "rk_debug_rows": (C.c_int, [C.c_void_p, _P(RkDebugRowsCall)]),
     "rk_debug_draft_steps": (C.c_int, [C.c_void_p, _P(RkDebugDraftStepsCall)]),
+    "rk_debug_kv8_quant": (C.c_int, [C.c_void_p, _P(C.c_uint16), C.c_int, _P(C.c_uint8), _P(C.c_int8), _P(C.c_uint16)]),
+    "rk_debug_kv8_step": (C.c_int, [C.c_void_p, _P(RkDebugKv8StepCall)]),
     "rk_debug_gemm_bench": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _f32p]),
     "rk_debug_read": (C.c_int64, [C.c_void_p, C.c_char_p, _f32p, C.c_int64]),
     "rk_debug_graph_stats": (C.c_int, [C.c_void_p, _P(RkDebugGraphStats)]),
@@ -447,10 +450,12 @@ class RkLlamaEngine(RkEngine):
     """Decoder-only engine (rk_llama_*): prefill + last-position logits.  Shares weight loading, options, profiling and
     lifetime with RkEngine; the T5 entry points refuse it."""
 
-    def __init__(self, dims, device: int = 0, max_tokens: int = 16384, max_seqs: int = 16, weight_fp8: bool = False):
+    def __init__(self, dims, device: int = 0, max_tokens: int = 16384, max_seqs: int = 16, weight_fp8: bool = False,
+                 kv_fp8: bool = False):
         self.lib = load_library()
         self.dims = dims
         self.weight_fp8 = bool(weight_fp8)
+        self.kv_fp8 = bool(kv_fp8)
         self.desc = RkLlamaDesc(vocab=dims.vocab, hidden=dims.hidden, n_heads=dims.n_heads, n_kv_heads=dims.n_kv_heads,
                                 head_dim=dims.head_dim, intermediate=dims.intermediate, n_layers=dims.n_layers,
                                 tied_head=int(dims.tied_head), eps=dims.eps, rope_theta=dims.rope_theta,
@@ -464,6 +469,8 @@ class RkLlamaEngine(RkEngine):
         self.comm_rank, self.comm_world = 0, 1
         if self.weight_fp8:                                           # FP8 step weights (opt-in, lossy): before the first tensor is loaded
             self._chk(self.lib.rk_llama_set_weight_fp8(self.h, 1))
+        if self.kv_fp8:                                               # FP8 K / V cache of the decoding step (opt-in, lossy): before finalize
+            self._chk(self.lib.rk_llama_set_kv_fp8(self.h, 1))
         if getattr(dims, "rope_scaling", None) is not None:          # rope type llama3: before finalize builds the rotary tables
             f, lo, hi, orig = dims.rope_scaling
             self._chk(self.lib.rk_llama_set_rope_scaling(self.h, float(f), float(lo), float(hi), int(orig)))

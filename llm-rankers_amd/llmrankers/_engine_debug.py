@@ -83,6 +83,14 @@ class RkDebugDraftStepsCall(C.Structure):
                [("script", C.c_void_p), ("script_ints", C.c_int64), ("state", RkDebugRowsOut * 14)]
 
 
+class RkDebugKv8StepCall(C.Structure):
+    """rk_debug_kv8_step_call of include/rk_engine.h, field for field."""
+    _fields_ = [(n, C.c_int) for n in ("n_seq", "H", "n_kv", "P", "ld", "max_pos", "g1", "mode", "plan_only")] + [("qk_eps", C.c_float)] + \
+               [(n, C.c_void_p) for n in ("qkv", "pos", "cos_t", "sin_t", "qkv_bias", "qk_norm", "live", "cache")] + \
+               [("ctx", RkDebugRowsOut), ("part", RkDebugRowsOut), ("cache_out", RkDebugRowsOut)] + \
+               [(n, C.c_int) for n in ("out_R", "out_nch", "out_pe")]
+
+
 DRAFT_ARRAYS = ("st", "len", "col", "max_new", "done", "out", "rnext", "rpos", "rlive", "dlen", "nstep", "tabn", "tab", "hist")
 
 
@@ -258,6 +266,55 @@ class DebugCalls:
         self._chk(self.lib.rk_debug_quant_fp8(self.h, w16.ctypes.data_as(_P(C.c_uint16)), N, K, ld, q.ctypes.data_as(_P(C.c_uint8)),
                                               ex.ctypes.data_as(_P(C.c_int8)), deq.ctypes.data_as(_P(C.c_uint16))))
         return q, ex, deq
+
+    def debug_kv8_quant(self, x16: np.ndarray) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """The FP8 K / V cache's quantiser on host vectors (rk_debug_kv8_quant; the format: include/rk_engine.h at rk_llama_set_kv_fp8).
+        x16: fp16 [n, 128].  Returns (e4m3fn bytes [n, 128] uint8, exponents [n] int8, the dequantised fp16 vectors [n, 128])."""
+        x16 = np.ascontiguousarray(x16, dtype=np.float16)
+        assert x16.ndim == 2 and x16.shape[1] == 128
+        n = x16.shape[0]
+        q, ex, deq = np.zeros((n, 128), np.uint8), np.zeros(n, np.int8), np.zeros((n, 128), np.float16)
+        self._chk(self.lib.rk_debug_kv8_quant(self.h, x16.ctypes.data_as(_P(C.c_uint16)), n, q.ctypes.data_as(_P(C.c_uint8)),
+                                              ex.ctypes.data_as(_P(C.c_int8)), deq.ctypes.data_as(_P(C.c_uint16))))
+        return q, ex, deq
+
+    def debug_kv8_step(self, *, mode: int, qkv, pos, cos, sin, cache, H: int, n_kv: int, P: int, qkv_bias=None, qk_norm=None, qk_eps=0.0,
+                       g1=0, live=None, band=256, fill=0.0, plan_only=False) -> dict:
+        """One step's attention of an FP8-cache engine through rk_debug_kv8_step (include/rk_engine.h).  qkv fp16 [n_seq, ld]; cache
+        fp16, flat, K then V ([2][n_seq / g1][n_kv][P][128]); mode 0 = bytes, 1 = rounded fp16.  Returns R, nch, pe and, unless
+        plan_only, the whole device allocations after the call as byte arrays "ctx", "part", "cache" (band + interior + band each)
+        and "band"; the interiors of ctx and part are pre-filled with `fill`."""
+        qkv = np.ascontiguousarray(qkv, dtype=np.float16)
+        n_seq, ld = qkv.shape
+        c = RkDebugKv8StepCall()
+        c.n_seq, c.H, c.n_kv, c.P, c.ld, c.g1, c.mode, c.plan_only = n_seq, H, n_kv, P, ld, int(g1), int(mode), 1
+        self._chk(self.lib.rk_debug_kv8_step(self.h, C.byref(c)))
+        res = _out_fields(c)
+        if plan_only:
+            return res
+        c.plan_only = 0
+        keep = [qkv]
+        put = partial(_put, c, keep)
+        c.qkv = qkv.ctypes.data
+        put("pos", pos, np.int32)
+        cos, sin = put("cos_t", cos, np.float32), put("sin_t", sin, np.float32)
+        assert cos.ndim == 2 and cos.shape[1] == 64 and sin.shape == cos.shape
+        c.max_pos = cos.shape[0]
+        put("qkv_bias", qkv_bias, np.float32)
+        if qk_norm is not None:
+            put("qk_norm", qk_norm, np.float32)
+            c.qk_eps = float(qk_eps)
+        put("live", live, np.int32)
+        rows = n_seq // max(int(g1), 1)
+        plane = rows * n_kv * P * 128
+        assert put("cache", cache, np.float16).size == 2 * plane
+        cache_bytes = 4 * plane if mode else 2 * plane + 2 * rows * n_kv * res["pe"]
+        outs = [np.full((n_seq, H * 128), fill, np.float16), np.full(n_seq * H * res["nch"] * 132, fill, np.float32),
+                np.zeros(cache_bytes, np.uint8)]
+        alls = _banded_outs([c.ctx, c.part, c.cache_out], outs, None, 1, band, keep)
+        self._chk(self.lib.rk_debug_kv8_step(self.h, C.byref(c)))
+        res.update(ctx=alls[0][0], part=alls[1][0], cache=alls[2][0], band=band)
+        return res
 
     def debug_gemm_chain(self, epi: int, a16: np.ndarray, w16: np.ndarray, M: int, N: int, K: int, *, family=0, ldc=None,
                          c_in: Optional[np.ndarray] = None, accumulate=False, rowscale=None, bg: Optional[dict] = None, bg_per_fg=0,

@@ -571,6 +571,39 @@ def weight_dtype_kw(weight_dtype) -> dict:
     return {} if weight_dtype == "fp16" else {"weight_dtype": weight_dtype}
 
 
+KV_DTYPES = ("fp16", "fp8")
+
+
+def kv_dtype_kw(kv_dtype) -> dict:
+    """The keyword a ranker adds to its runtime call: none for the default (the calls of a default ranker stay what they were)."""
+    if kv_dtype not in KV_DTYPES:
+        raise ValueError(f"kv_dtype must be one of {KV_DTYPES} (got {kv_dtype!r})")
+    return {} if kv_dtype == "fp16" else {"kv_dtype": kv_dtype}
+
+
+def refuse_t5_kv_dtype(kv_dtype):
+    """The rankers' kv_dtype on a T5 checkpoint: "fp16" is what T5 runs; the FP8 K / V cache exists for the Llama family only."""
+    if kv_dtype not in KV_DTYPES:
+        raise ValueError(f"kv_dtype must be one of {KV_DTYPES} (got {kv_dtype!r})")
+    if kv_dtype != "fp16":
+        raise NotImplementedError(f"kv_dtype={kv_dtype!r} is not supported for T5 checkpoints: the FP8 K / V cache serves the Llama "
+                                  "family's decoding step (kv_dtype='fp16' is what the T5 engine runs)")
+
+
+_KV_DTYPE_CLASSES = {}          # (class, kv_dtype) -> the subclass class_with_kv_dtype hands out
+
+
+def class_with_kv_dtype(cls, kv_dtype):
+    """A ranker class whose runtime keeps an FP8 K / V cache (LlamaRuntime's kv_dtype; lossy, opt-in).  The rankers' constructors keep
+    their parameter lists, so the option is the class's, like with_weight_dtype: Cls.with_kv_dtype("fp8")(model, ...)."""
+    kv_dtype_kw(kv_dtype)                                              # ValueError for anything but "fp16" / "fp8"
+    if kv_dtype == cls.kv_dtype:
+        return cls
+    if (cls, kv_dtype) not in _KV_DTYPE_CLASSES:                       # one subclass per (class, dtype), not one per call
+        _KV_DTYPE_CLASSES[cls, kv_dtype] = type(cls.__name__, (cls,), {"kv_dtype": kv_dtype})
+    return _KV_DTYPE_CLASSES[cls, kv_dtype]
+
+
 MAX_DRAFT_TOKENS = 7
 
 
@@ -606,14 +639,18 @@ class LlamaRuntime:
     `AutoModelForCausalLM.from_pretrained(..., device_map='auto', torch_dtype=fp16)` of ref: llmrankers/setwise.py:65-69."""
 
     def __init__(self, model_name_or_path: str, device, max_tokens: int = 32768, max_seqs: int = 16, cache_dir=None,
-                 accept_model_types=("llama",), adapter_dir=None, weight_dtype="fp16"):
+                 accept_model_types=("llama",), adapter_dir=None, kv_dtype="fp16", weight_dtype="fp16"):
         """accept_model_types: the config.model_type values the caller serves - the reference's setwise / pairwise / listwise
         rankers refuse Qwen (ref: setwise.py:71), its Rank-R1 ranker runs on it.  adapter_dir: a PEFT LoRA adapter merged into
         the weights on the way in (merge_lora).  weight_dtype: "fp16", or "fp8" - FP8 step weights (RkLlamaEngine(weight_fp8=True):
-        opt-in and lossy, one e4m3 rounding per weight of the projections the decoding step streams, behind the LoRA merge)."""
+        opt-in and lossy, one e4m3 rounding per weight of the projections the decoding step streams, behind the LoRA merge).
+        kv_dtype: "fp16", or "fp8" - the decoding step's K / V cache in FP8 (RkLlamaEngine(kv_fp8=True): opt-in and lossy, one e4m3
+        rounding per cached key and value element; head_dim 128 only).  The two combine freely."""
         if weight_dtype not in WEIGHT_DTYPES:
             raise ValueError(f"weight_dtype must be one of {WEIGHT_DTYPES} (got {weight_dtype!r})")
-        self.weight_dtype = weight_dtype
+        if kv_dtype not in KV_DTYPES:
+            raise ValueError(f"kv_dtype must be one of {KV_DTYPES} (got {kv_dtype!r})")
+        self.weight_dtype, self.kv_dtype = weight_dtype, kv_dtype
         model_name_or_path = resolve_checkpoint(model_name_or_path, cache_dir)
         cfg = read_config(model_name_or_path)
         self.model_type = cfg.get("model_type")
@@ -628,7 +665,11 @@ class LlamaRuntime:
                                       "hidden <= 4096 (Llama-2/3 up to 8B, Llama-3.2-1B, TinyLlama, SmolLM2, Qwen2.5-0.5B to 7B)")
         if self.dims.qk_norm and self.dims.head_dim != 128:            # (rk_engine_finalize refuses it too; no Qwen3 checkpoint has it)
             raise NotImplementedError(f"Qwen3 with head_dim {self.dims.head_dim}: the MI355X engine's q / k head norm is built for head_dim 128")
-        self.engine = RkLlamaEngine(self.dims, parse_device(device), max_tokens, max_seqs, **({"weight_fp8": True} if weight_dtype == "fp8" else {}))
+        if kv_dtype == "fp8" and self.dims.head_dim != 128:            # (rk_engine_finalize refuses it too)
+            raise NotImplementedError(f"kv_dtype='fp8' with head_dim {self.dims.head_dim}: the MI355X engine's FP8 K / V cache is built for head_dim 128 "
+                                      "(the 64-wide models' caches are small)")
+        self.engine = RkLlamaEngine(self.dims, parse_device(device), max_tokens, max_seqs, **({"weight_fp8": True} if weight_dtype == "fp8" else {}),
+                                    **({"kv_fp8": True} if kv_dtype == "fp8" else {}))
         tensors = iter_checkpoint_tensors(model_name_or_path)
         self.engine.load_state(merge_lora(tensors, adapter_dir) if adapter_dir else tensors)
 
@@ -642,6 +683,7 @@ class LlamaRuntime:
         self.max_tokens, self.max_seqs = int(engine.desc.max_tokens), int(engine.desc.max_seqs)
         self.engine = engine
         self.weight_dtype = "fp8" if getattr(engine, "weight_fp8", False) else "fp16"
+        self.kv_dtype = "fp8" if getattr(engine, "kv_fp8", False) else "fp16"
         return self
 
     _chunks = T5Runtime._chunks
@@ -896,17 +938,16 @@ def generation_plan(runtime, prompt_lens) -> dict:
     return {"max_new": max_new, "max_total": max_total, "eos_ids": list(g["eos_token_ids"]), "pad_id": int(g["pad_token_id"])}
 
 
-def load_runtime(model_name_or_path: str, device, cache_dir=None, weight_dtype="fp16"):
+def load_runtime(model_name_or_path: str, device, cache_dir=None, weight_dtype="fp16", kv_dtype="fp16"):
     """T5Runtime or LlamaRuntime by the checkpoint's config.model_type (ref: setwise.py:40-71 dispatches the same way);
     anything else raises NotImplementedError like the reference.  weight_dtype: LlamaRuntime's; "fp8" on a T5 checkpoint raises
-    NotImplementedError."""
+    NotImplementedError.  kv_dtype: likewise."""
     path = resolve_checkpoint(model_name_or_path, cache_dir)
     mt = read_config(path).get("model_type")
     if mt == "t5":
         refuse_t5_weight_dtype(weight_dtype)
+        refuse_t5_kv_dtype(kv_dtype)
         return T5Runtime(path, device, cache_dir=cache_dir)
-    if mt == "llama":
-        if weight_dtype != "fp16":
-            return LlamaRuntime(path, device, cache_dir=cache_dir, weight_dtype=weight_dtype)
-        return LlamaRuntime(path, device, cache_dir=cache_dir)
+    if mt == "llama":                                                 # (a default call makes the call it always made)
+        return LlamaRuntime(path, device, cache_dir=cache_dir, **weight_dtype_kw(weight_dtype), **kv_dtype_kw(kv_dtype))
     raise NotImplementedError(f"Model type {mt} is not supported yet by the MI355X engine")

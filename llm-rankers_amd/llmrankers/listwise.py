@@ -17,7 +17,7 @@ import numpy as np
 
 from ._batching import tokenize_prompts
 from ._lockstep import Lockstep, drive
-from .rankers import LlmRanker, SearchResult, close_counters, tally
+from .rankers import KvDtypeOption, LlmRanker, SearchResult, close_counters, tally
 
 # the "complete" prompt of the reference (ref: listwise.py:85-104) - model input, byte for byte
 HEAD = ("This is RankGPT, an intelligent assistant that can rank passages based on their relevancy to the query.\n\n"
@@ -77,7 +77,7 @@ def permutation_order(response: str, n: int) -> List[int]:
     return order + [k for k in range(n) if k not in seen]
 
 
-class ListwiseLlmRanker(LlmRanker):
+class ListwiseLlmRanker(KvDtypeOption, LlmRanker):
     # "Passage X" / "Passage Y" tokenize into 3 tokens with the T5 vocabulary, hence 23 labels (ref: listwise.py:203-205)
     CHARACTERS = ["A", "B", "C", "D", "E", "F", "G", "H", "I", "J", "K", "L",
                   "M", "N", "O", "P", "Q", "R", "S", "T", "U", "V", "W"]
@@ -89,10 +89,10 @@ class ListwiseLlmRanker(LlmRanker):
         # greedy decoding whatever the checkpoint's generation settings say; an integer = a checkpoint that says do_sample: true
         # is sampled on the device with its own temperature / top_k / top_p, reproducibly (see _setup)
         # weight_dtype (not in the reference): "fp8" = FP8 step weights on a Llama-family checkpoint (LlamaRuntime; lossy, opt-in)
-        from ._runtime import load_runtime, resolve_checkpoint, weight_dtype_kw
+        from ._runtime import kv_dtype_kw, load_runtime, resolve_checkpoint, weight_dtype_kw
         path = resolve_checkpoint(model_name_or_path, cache_dir)
         try:
-            runtime = load_runtime(path, device, cache_dir=cache_dir, **weight_dtype_kw(weight_dtype))
+            runtime = load_runtime(path, device, cache_dir=cache_dir, **weight_dtype_kw(weight_dtype), **kv_dtype_kw(self.kv_dtype))
         except NotImplementedError as exc:   # same message shape as ref: listwise.py:247
             raise NotImplementedError(f"{exc} (listwise)") from None
         if runtime.model_type == "llama":
@@ -352,14 +352,14 @@ class R1ListwiseLlmRanker(ListwiseLlmRanker):
     def __init__(self, model_name_or_path, tokenizer_name_or_path, prompt, window_size, step_size, lora_path=None,
                  scoring='generation', num_repeat=1, cache_dir=None, device="cuda", max_new_tokens=2048):
         from transformers import AutoTokenizer
-        from ._runtime import LlamaRuntime, resolve_checkpoint, weight_dtype_kw
+        from ._runtime import LlamaRuntime, kv_dtype_kw, resolve_checkpoint, weight_dtype_kw
         from .setwise import load_prompt_file
         prompt = load_prompt_file(prompt)
         lora_path = resolve_checkpoint(lora_path, cache_dir) if lora_path is not None else None
         tokenizer = AutoTokenizer.from_pretrained(tokenizer_name_or_path if tokenizer_name_or_path is not None else model_name_or_path,
                                                   cache_dir=cache_dir)
         runtime = LlamaRuntime(model_name_or_path, device, cache_dir=cache_dir, accept_model_types=self.ACCEPT_MODEL_TYPES,
-                               adapter_dir=lora_path, **weight_dtype_kw(self.weight_dtype))
+                               adapter_dir=lora_path, **weight_dtype_kw(self.weight_dtype), **kv_dtype_kw(self.kv_dtype))
         self._setup_r1(runtime, tokenizer, prompt, lora_path, device, window_size, step_size, scoring, num_repeat, max_new_tokens)
 
     @classmethod

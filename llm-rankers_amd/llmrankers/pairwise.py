@@ -22,7 +22,7 @@ import numpy as np
 from ._batching import batches, padded_token_count, tokenize_prompts
 from ._lockstep import Lockstep, alternate, drive, heapsort_steps
 from .pointwise import _softmax_first
-from .rankers import LlmRanker, SearchResult, close_counters, rerank_each, tally, top_k_then_rest
+from .rankers import KvDtypeOption, LlmRanker, SearchResult, close_counters, rerank_each, tally, top_k_then_rest
 
 PROMPT = ('Given a query "{query}", which of the following two passages is more relevant to the query?\n\n'
           'Passage A: "{doc1}"\n\nPassage B: "{doc2}"\n\nOutput Passage A or Passage B:')
@@ -49,16 +49,16 @@ def sift(arr, n, i):
         i = largest
 
 
-class PairwiseLlmRanker(LlmRanker):
+class PairwiseLlmRanker(KvDtypeOption, LlmRanker):
     needs_decoder_positions = True            # PRP generates two tokens behind "<pad> Passage" (DuoT5LlmRanker: one position)
 
     def __init__(self, model_name_or_path, tokenizer_name_or_path, device, method="allpair", batch_size=2, k=10,
                  cache_dir=None, weight_dtype="fp16"):
         # ref: pairwise.py:30-82: T5 or Llama family by config.model_type, NotImplementedError otherwise
         # weight_dtype (not in the reference): "fp8" = FP8 step weights on a Llama-family checkpoint (LlamaRuntime; lossy, opt-in)
-        from ._runtime import load_runtime, weight_dtype_kw
+        from ._runtime import kv_dtype_kw, load_runtime, weight_dtype_kw
         try:
-            runtime = load_runtime(model_name_or_path, device, cache_dir=cache_dir, **weight_dtype_kw(weight_dtype))
+            runtime = load_runtime(model_name_or_path, device, cache_dir=cache_dir, **weight_dtype_kw(weight_dtype), **kv_dtype_kw(self.kv_dtype))
         except NotImplementedError as exc:
             raise NotImplementedError(f"{exc} (pairwise)") from None
         if runtime.model_type == "llama":
@@ -224,6 +224,12 @@ class DuoT5LlmRanker(PairwiseLlmRanker):
     FALSE_ID, TRUE_ID = 6136, 1176            # the ids of "false" / "true" in the T5 vocabulary (ref :314-315)
     fp16_scores = False                       # True: the host verdict from the returned logits, rounded as the reference's fp16 model does
     needs_decoder_positions = False
+
+    @classmethod
+    def with_kv_dtype(cls, kv_dtype):            # duoT5 serves T5 checkpoints: "fp8" is refused by name, "fp16" changes nothing
+        from ._runtime import refuse_t5_kv_dtype
+        refuse_t5_kv_dtype(kv_dtype)
+        return cls
 
     def _setup(self, runtime, tokenizer, device, method, batch_size, k):
         super()._setup(runtime, tokenizer, device, method, batch_size, k)

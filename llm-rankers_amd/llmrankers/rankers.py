@@ -54,6 +54,18 @@ def close_counters(ranker, counts):
     return counters
 
 
+class KvDtypeOption:
+    """The rankers that decode on a Llama-family checkpoint (setwise, pairwise, listwise and the two Rank-R1 rankers): an FP8 K / V
+    cache for the decoding step (LlamaRuntime's kv_dtype; lossy, opt-in).  Their constructors keep their parameter lists, so the
+    option is the class's: Cls.with_kv_dtype("fp8")(model, ...); a T5 checkpoint refuses "fp8" as it refuses weight_dtype="fp8"."""
+    kv_dtype = "fp16"
+
+    @classmethod
+    def with_kv_dtype(cls, kv_dtype):
+        from ._runtime import class_with_kv_dtype
+        return class_with_kv_dtype(cls, kv_dtype)
+
+
 class LlmRanker:
     """Interface every ranker implements: rerank a candidate list for a query; truncate text by tokens."""
 

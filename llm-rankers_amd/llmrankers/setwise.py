@@ -15,7 +15,7 @@ import numpy as np
 
 from ._batching import tokenize_prompts
 from ._lockstep import Lockstep, alternate, drive, heapsort_steps
-from .rankers import LlmRanker, SearchResult, close_counters, rerank_each, tally, top_k_then_rest
+from .rankers import KvDtypeOption, LlmRanker, SearchResult, close_counters, rerank_each, tally, top_k_then_rest
 
 random.seed(929)   # same import-time seeding as the reference (ref: setwise.py:18): permutation voting depends on it
 
@@ -52,7 +52,7 @@ def vote(refs, answers, characters, say, rng=random):
     return characters[winners[0] if len(winners) == 1 else rng.choice(winners)]
 
 
-class SetwiseLlmRanker(LlmRanker):
+class SetwiseLlmRanker(KvDtypeOption, LlmRanker):
     # "Passage X" / "Passage Y" tokenize into 3 tokens with the T5 vocabulary, hence 23 labels (ref: setwise.py:22-23)
     CHARACTERS = ["A", "B", "C", "D", "E", "F", "G", "H", "I", "J", "K", "L",
                   "M", "N", "O", "P", "Q", "R", "S", "T", "U", "V", "W"]
@@ -61,9 +61,9 @@ class SetwiseLlmRanker(LlmRanker):
                  method="heapsort", num_permutation=1, cache_dir=None, weight_dtype="fp16"):
         # ref: setwise.py:25-77: T5 or Llama family by config.model_type, NotImplementedError otherwise
         # weight_dtype (not in the reference): "fp8" = FP8 step weights on a Llama-family checkpoint (LlamaRuntime; lossy, opt-in)
-        from ._runtime import load_runtime, weight_dtype_kw
+        from ._runtime import kv_dtype_kw, load_runtime, weight_dtype_kw
         try:
-            runtime = load_runtime(model_name_or_path, device, cache_dir=cache_dir, **weight_dtype_kw(weight_dtype))
+            runtime = load_runtime(model_name_or_path, device, cache_dir=cache_dir, **weight_dtype_kw(weight_dtype), **kv_dtype_kw(self.kv_dtype))
         except NotImplementedError as exc:   # same message shape as ref: setwise.py:71
             raise NotImplementedError(f"{exc} (setwise)") from None
         if runtime.model_type == "llama":
@@ -460,13 +460,13 @@ class RankR1SetwiseLlmRanker(SetwiseLlmRanker):
         if scoring != 'generation':
             raise NotImplementedError(f"Scoring method {scoring} is not supported for RankR1SetwiseLlmRanker. RankR1SetwiseLlmRanker only supports 'generation' scoring.")
         from transformers import AutoTokenizer
-        from ._runtime import LlamaRuntime, resolve_checkpoint, weight_dtype_kw
+        from ._runtime import LlamaRuntime, kv_dtype_kw, resolve_checkpoint, weight_dtype_kw
         prompt = load_prompt_file(prompt_file)
         lora_path = resolve_checkpoint(lora_name_or_path, cache_dir) if lora_name_or_path is not None else None
         tokenizer = AutoTokenizer.from_pretrained(tokenizer_name_or_path if tokenizer_name_or_path is not None else model_name_or_path,
                                                   cache_dir=cache_dir)
         runtime = LlamaRuntime(model_name_or_path, device, cache_dir=cache_dir, accept_model_types=("qwen2", "llama", "mistral", "qwen3"),
-                               adapter_dir=lora_path, **weight_dtype_kw(self.weight_dtype))
+                               adapter_dir=lora_path, **weight_dtype_kw(self.weight_dtype), **kv_dtype_kw(self.kv_dtype))
         self._setup_r1(runtime, tokenizer, prompt, lora_path, device, num_child, k, method, num_permutation, verbose, max_new_tokens)
 
     @classmethod

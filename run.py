@@ -259,6 +259,9 @@ def build_ranker(args):
     # --weight_dtype: forwarded only when given (a run without the flag makes the calls it always made); the T5-only rankers refuse fp8
     wd = getattr(args.run, "weight_dtype", None)
     wd_kw = {} if wd is None else {"weight_dtype": wd}
+    # --kv_dtype: likewise forwarded only when given; the option is the ranker class's (with_kv_dtype), refused where weight_dtype fp8 is
+    kd = getattr(args.run, "kv_dtype", None)
+    with_kv = (lambda cls: cls) if kd is None else (lambda cls: cls.with_kv_dtype(kd))
     # --draft_tokens: the two Rank-R1 rankers (--setwise / --listwise with --prompt_file); 0, the default, changes nothing
     dt = int(getattr(args.run, "draft_tokens", 0) or 0)
     if dt and not ((args.setwise or args.listwise) and getattr(args.run, "prompt_file", None)):
@@ -267,6 +270,9 @@ def build_ranker(args):
         if wd == "fp8":
             raise NotImplementedError("--weight_dtype fp8 is not supported by the pointwise rankers: they serve T5 checkpoints, FP8 step "
                                       "weights the Llama family's decoding step")
+        if kd == "fp8":
+            raise NotImplementedError("--kv_dtype fp8 is not supported by the pointwise rankers: they score with prefills alone, the FP8 K / V "
+                                      "cache serves the Llama family's decoding step")
         from llmrankers.pointwise import MonoT5LlmRanker, PointwiseLlmRanker
         cls = MonoT5LlmRanker if "monot5" in args.run.model_name_or_path else PointwiseLlmRanker
         return cls(model_name_or_path=args.run.model_name_or_path, tokenizer_name_or_path=args.run.tokenizer_name_or_path,
@@ -279,6 +285,7 @@ def build_ranker(args):
             from llmrankers.setwise import RankR1SetwiseLlmRanker
             if wd is not None:                                   # (the two R1 constructors keep the reference's parameter lists)
                 RankR1SetwiseLlmRanker = RankR1SetwiseLlmRanker.with_weight_dtype(wd)
+            RankR1SetwiseLlmRanker = with_kv(RankR1SetwiseLlmRanker)
             if dt:
                 RankR1SetwiseLlmRanker = RankR1SetwiseLlmRanker.with_draft_tokens(dt)
             return RankR1SetwiseLlmRanker(model_name_or_path=args.run.model_name_or_path, prompt_file=args.run.prompt_file,
@@ -288,7 +295,7 @@ def build_ranker(args):
                                           method=args.setwise.method, num_permutation=args.setwise.num_permutation, k=args.setwise.k,
                                           max_new_tokens=args.run.max_new_tokens)
         from llmrankers.setwise import SetwiseLlmRanker
-        return SetwiseLlmRanker(model_name_or_path=args.run.model_name_or_path, tokenizer_name_or_path=args.run.tokenizer_name_or_path,
+        return with_kv(SetwiseLlmRanker)(model_name_or_path=args.run.model_name_or_path, tokenizer_name_or_path=args.run.tokenizer_name_or_path,
                                 device=args.run.device, cache_dir=args.run.cache_dir, num_child=args.setwise.num_child,
                                 scoring=args.run.scoring, method=args.setwise.method,
                                 num_permutation=args.setwise.num_permutation, k=args.setwise.k, **wd_kw)
@@ -302,8 +309,12 @@ def build_ranker(args):
         cls = DuoT5LlmRanker if "duot5" in args.run.model_name_or_path else PairwiseLlmRanker        # ref: run.py:99-106
         if cls is DuoT5LlmRanker and wd == "fp8":
             raise NotImplementedError("--weight_dtype fp8 is not supported by the duoT5 ranker: it serves T5 checkpoints")
+        if cls is DuoT5LlmRanker and kd == "fp8":
+            raise NotImplementedError("--kv_dtype fp8 is not supported by the duoT5 ranker: it serves T5 checkpoints")
         if cls is DuoT5LlmRanker:
             wd_kw = {}
+        else:
+            cls = with_kv(cls)
         return cls(model_name_or_path=args.run.model_name_or_path, tokenizer_name_or_path=args.run.tokenizer_name_or_path,
                                  device=args.run.device, cache_dir=args.run.cache_dir, method=args.pairwise.method,
                                  batch_size=args.pairwise.batch_size, k=args.pairwise.k, **wd_kw)
@@ -314,6 +325,7 @@ def build_ranker(args):
             from llmrankers.listwise import R1ListwiseLlmRanker
             if wd is not None:
                 R1ListwiseLlmRanker = R1ListwiseLlmRanker.with_weight_dtype(wd)
+            R1ListwiseLlmRanker = with_kv(R1ListwiseLlmRanker)
             if dt:
                 R1ListwiseLlmRanker = R1ListwiseLlmRanker.with_draft_tokens(dt)
             return R1ListwiseLlmRanker(model_name_or_path=args.run.model_name_or_path, tokenizer_name_or_path=args.run.tokenizer_name_or_path,
@@ -321,7 +333,7 @@ def build_ranker(args):
                                        lora_path=args.run.lora_name_or_path, num_repeat=args.listwise.num_repeat, cache_dir=args.run.cache_dir,
                                        device=args.run.device, max_new_tokens=args.run.max_new_tokens)
         from llmrankers.listwise import ListwiseLlmRanker
-        return ListwiseLlmRanker(model_name_or_path=args.run.model_name_or_path, tokenizer_name_or_path=args.run.tokenizer_name_or_path,
+        return with_kv(ListwiseLlmRanker)(model_name_or_path=args.run.model_name_or_path, tokenizer_name_or_path=args.run.tokenizer_name_or_path,
                                  device=args.run.device, cache_dir=args.run.cache_dir, window_size=args.listwise.window_size,
                                  step_size=args.listwise.step_size, scoring=args.run.scoring, num_repeat=args.listwise.num_repeat,
                                  **({} if getattr(args.listwise, "sample_seed", None) is None else {"sample_seed": args.listwise.sample_seed}), **wd_kw)
@@ -584,6 +596,11 @@ def build_parser():
     rp.add_argument("--weight_dtype", type=str, default=None, choices=["fp16", "fp8"],
                     help="Llama-family checkpoints: fp8 keeps the projections the decoding step streams as FP8 step weights (lossy: one "
                          "e4m3 rounding per weight; rankings can differ from fp16).  Default: fp16")
+    rp.add_argument("--kv_dtype", type=str, default=None, choices=["fp16", "fp8"],
+                    help="Llama-family checkpoints with 128-wide heads: fp8 keeps the decoding step's K / V cache in FP8 - half the cache's "
+                         "memory; it buys no time at the measured shapes (lossy: one e4m3 rounding per cached element; rankings can differ "
+                         "from fp16).  "
+                         "Combines with --weight_dtype, --draft_tokens and --sample_seed.  Default: fp16")
     rp.add_argument("--draft_tokens", type=int, default=0, choices=range(0, 8), metavar="N",
                     help="Rank-R1 rankers (--prompt_file): decode with N in 1..7 prompt-lookup draft tokens per step - the same tokens "
                          "in fewer steps where the reasoning text repeats its prompt or itself.  Default 0: off")
