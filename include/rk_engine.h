@@ -523,7 +523,7 @@ int rk_debug_gemm_chain(rk_engine* e, rk_debug_gemm_chain_call* call);
  *                        On an engine with a sliding window W every call runs the windowed entries (out_kind 1, else 0): row b reads keys
  *                        max(0, pos[b] - W + 1) .. pos[b] and the cache below them is neither read into the result nor written.
  *                        g1 / live (the LAST fields of the call, behind qk_norm / qk_eps; g1 = 0 or 1: the plain call, unchanged): a drafting
- *                        session's step, plan_llama_dec_attn over the n_seq step rows and launch_llama_dec_attn_keys as llama_step_rows calls
+ *                        session's step, plan_llama_dec_attn over the n_seq step rows and launch_llama_dec_attn (with g1 / live) as llama_step_rows calls
  *                        them.  n_seq = g1 x the cache's rows (cache = K [n_seq / g1][n_kv][P][hd] then V), step row b belongs to cache row
  *                        b / g1 at pos[b]; live[n_seq]: 1 = the row's rotated key and its value are appended at pos[b] in front of the
  *                        attention, 0 = a dead row (nothing written, its context unspecified).  Every row reads keys <= pos[b] of its cache

@@ -489,8 +489,8 @@ int rk_debug_attn(rk_engine* e, rk_debug_attn_call* q) {
     launch_dec_cached_step(e, st, AttnCachedArgs{qi, q->ldq, Cache.interior<half_t>(), P, I, dPos, oi, q->ldctx, dLut}, B, H, dTk, dTp);
   } else {
     const int g1 = q->g1 > 1 ? q->g1 : 1;                     // the drafting step: g1 step rows per cache row
-    const size_t half_layer = (size_t)(B / g1) * q->n_kv * q->P * hd;
-    Cache = ds.banded(band_rows_span(2 * half_layer, band, hd, 2), q->cache);
+    const KvLayerLayout kl = kv_layer_layout(0, B / g1, q->n_kv, hd, q->P);   // the caller's cache: one layer of the fp16 layout
+    Cache = ds.banded(band_rows_span(kl.bytes / 2, band, hd, 2), q->cache);
     int* dPos = ds.up<int>(q->pos, (size_t)B);
     float* dCos = ds.up<float>(q->cos_t, (size_t)q->max_pos * (hd / 2));
     float* dSin = ds.up<float>(q->sin_t, (size_t)q->max_pos * (hd / 2));
@@ -500,10 +500,8 @@ int rk_debug_attn(rk_engine* e, rk_debug_attn_call* q) {
     int* dLive = g1 > 1 ? ds.up<int>(q->live, (size_t)B) : nullptr;
     if ((rc = ds.ready())) return rc;
     const float scale_log2e = (1.0f / std::sqrt((float)hd)) * 1.4426950408889634f;
-    half_t* kc = Cache.interior<half_t>();
-    const LlamaDecAttnArgs aa{qi, kc, kc + half_layer, dPos, dCos, dSin, dPart, oi, q->ldq, H, q->n_kv, q->P, lp.nch, scale_log2e, dBias, 0, dQkn, q->qk_eps};
-    if (g1 == 1) launch_llama_dec_attn(e, st, lp, aa, B);
-    else launch_llama_dec_attn_keys(e, st, lp, LlamaDecAttnKeysArgs{aa, g1, dLive}, B);   // (llama_step_rows' branch)
+    const LlamaDecAttnArgs aa{qi, nullptr, nullptr /* kc, vc: the cache's, in the launch */, dPos, dCos, dSin, dPart, oi, q->ldq, H, q->n_kv, q->P, lp.nch, scale_log2e, dBias, 0, dQkn, q->qk_eps};
+    launch_llama_dec_attn(e, st, lp, aa, B, g1, dLive, kv_cache_layer(kl, Cache.interior<half_t>(), 0));   // (llama_step_rows' call)
   }
   DBG_HIP(ds, hipStreamSynchronize(st));
   DBG_HIP(ds, hipGetLastError());
@@ -849,11 +847,9 @@ int rk_debug_rows(rk_engine* e, rk_debug_rows_call* q) {
                           (const float*)din[3], q->n_kv, rows); break;
       case 11: launch_rope(st, q->hd, (half_t*)dout[0], (const int*)din[0], (const float*)din[1], (const float*)din[2], q->ld, q->H + q->n_kv,
                            nullptr, q->n_kv, rows, (const float*)din[3], q->eps); break;
-      case 9: {
-        half_t* kc = (half_t*)dout[0];
-        launch_kv_fill(st, q->hd, (const half_t*)din[0], (const int*)din[1], (const int*)din[2], q->n_slots,
-                       Kv8Cache{kc, kc + (size_t)(din[2] ? q->n_slots : rows) * q->n_kv * q->P * q->hd, nullptr, nullptr, 0}, q->ld, q->H, q->n_kv, q->P, maxL, rows);
-      } break;
+      case 9: launch_kv_fill(st, q->hd, (const half_t*)din[0], (const int*)din[1], (const int*)din[2], q->n_slots,
+                             kv_cache_layer(kv_layer_layout(0, din[2] ? q->n_slots : rows, q->n_kv, q->hd, q->P), dout[0], 0), q->ld, q->H, q->n_kv,
+                             q->P, maxL, rows); break;
       default: {
         const int* am = (const int*)din[0] + (size_t)s * A;
         if (q->kind == 0)
@@ -1110,8 +1106,8 @@ int rk_debug_kv8_quant(rk_engine* e, const uint16_t* x, int n, uint8_t* q_out, i
 }
 
 // debug: one step's attention of an FP8-cache engine on host operands (include/rk_engine.h).  No launch code of its own: the
-// caller's fp16 cache goes through launch_kv8_quant into the layout of the mode, then plan_llama_dec_attn and launch_llama_dec_attn /
-// launch_llama_dec_attn_keys - llama_step_rows' branch.
+// caller's fp16 cache goes through launch_kv8_quant into the layout of the mode (kv_layer_layout), then plan_llama_dec_attn and
+// launch_llama_dec_attn - llama_step_rows' call.
 int rk_debug_kv8_step(rk_engine* e, rk_debug_kv8_step_call* q) {
   if (!e || !q) return RK_ERR_INVALID;
   int rc = set_device(e);
@@ -1126,15 +1122,15 @@ int rk_debug_kv8_step(rk_engine* e, rk_debug_kv8_step_call* q) {
     return fail(e, RK_ERR_STATE, "debug kv8 step: the step with the q / k head norm takes no window, no qkv_bias and qk_eps > 0");
   LlamaDecAttnPlan lp = plan_llama_dec_attn(e, B, P, H, n_kv);
   lp.kv8 = q->mode ? 2 : 1;                                  // (the engine's option chooses between the two; the call names one)
-  const int rows = B / g1, pe = (P + 31) & ~31;
-  q->out_R = lp.R; q->out_nch = lp.nch; q->out_pe = pe;
+  const int rows = B / g1;
+  const KvLayerLayout kl = kv_layer_layout(lp.kv8, rows, n_kv, hd, P), k16 = kv_layer_layout(0, rows, n_kv, hd, P);   // the step's cache; the caller's
+  q->out_R = lp.R; q->out_nch = lp.nch; q->out_pe = kv_layer_layout(1, rows, n_kv, hd, P).pe;
   if (H % lp.R) return fail(e, RK_ERR_STATE, "debug kv8 step: R = %d does not divide %d heads", lp.R, H);
   if (q->plan_only) return RK_OK;
   if (!q->qkv || !q->pos || !q->cos_t || !q->sin_t || !q->cache || (g1 > 1 && !q->live)) return fail(e, RK_ERR_INVALID, "debug kv8 step: qkv, pos, cos_t, sin_t, cache (and live with g1 > 1)");
   for (int b = 0; b < B; ++b)
     if (q->pos[b] < 0 || q->pos[b] >= P || q->pos[b] >= q->max_pos) return fail(e, RK_ERR_INVALID, "debug kv8 step: pos[%d] = %d outside the cache of %d / the tables of %d", b, q->pos[b], P, q->max_pos);
-  const size_t plane = (size_t)rows * n_kv * P * hd, nvec = (size_t)rows * n_kv * P, eplane = (size_t)rows * n_kv * pe;
-  const size_t cache_bytes = q->mode ? 4 * plane : 2 * plane + 2 * eplane;
+  const size_t heads = (size_t)rows * n_kv, nvec = heads * P, cache_bytes = kl.bytes;   // nvec key vectors and as many value vectors
   const size_t ctx_bytes = (size_t)B * H * hd * 2, part_bytes = (size_t)B * H * lp.nch * ldc_pstr(hd) * 4;
   if (nvec > (1u << 22) || !band_out_ok(q->ctx, (int64_t)ctx_bytes, BAND_EXACT) || !band_out_ok(q->part, (int64_t)part_bytes, BAND_EXACT) ||
       !band_out_ok(q->cache_out, (int64_t)cache_bytes, BAND_EXACT))
@@ -1142,33 +1138,34 @@ int rk_debug_kv8_step(rk_engine* e, rk_debug_kv8_step_call* q) {
   hipStream_t st = e->slots[0].se;
   DebugScratch ds(e, "debug kv8 step");
   half_t* dQkv = ds.up<half_t>(q->qkv, (size_t)B * q->ld);
-  half_t* dC16 = ds.up<half_t>(q->cache, 2 * plane);
+  half_t* dC16 = ds.up<half_t>(q->cache, k16.bytes / 2);
   int* dPos = ds.up<int>(q->pos, (size_t)B);
   float* dCos = ds.up<float>(q->cos_t, (size_t)q->max_pos * 64);
   float* dSin = ds.up<float>(q->sin_t, (size_t)q->max_pos * 64);
   float* dBias = q->qkv_bias ? ds.up<float>(q->qkv_bias, (size_t)(H + 2 * n_kv) * hd) : nullptr;
   float* dQkn = q->qk_norm ? ds.up<float>(q->qk_norm, (size_t)2 * hd) : nullptr;
   int* dLive = g1 > 1 ? ds.up<int>(q->live, (size_t)B) : nullptr;
-  uint8_t* dQ = ds.alloc<uint8_t>(2 * plane);                // the quantiser's dense outputs: bytes, exponents [2][nvec], dequantised
+  uint8_t* dQ = ds.alloc<uint8_t>(2 * nvec * hd);            // the quantiser's dense outputs [2][nvec]: bytes, exponents, dequantised
   int8_t* dE = ds.alloc<int8_t>(2 * nvec);
-  half_t* dD = ds.alloc<half_t>(2 * plane);
+  half_t* dD = ds.alloc<half_t>(2 * nvec * hd);
   const Banded Ctx = ds.banded(q->ctx), Part = ds.banded(q->part);
   const Banded Cache = ds.banded(BandSpan{cache_bytes, (size_t)q->cache_out.band});   // (its interior comes from the quantiser)
   if ((rc = ds.ready())) return rc;
   launch_kv8_quant(st, dC16, (int)(2 * nvec), dQ, dE, dD);
-  char* ci = Cache.interior<char>();
-  Kv8Cache cc{(half_t*)ci, (half_t*)(ci + (q->mode ? 2 * plane : plane)), nullptr, nullptr, 0};
-  if (q->mode) DBG_HIP(ds, hipMemcpyAsync(ci, dD, 4 * plane, hipMemcpyDeviceToDevice, st));
+  const Kv8Cache cc = kv_cache_layer(kl, Cache.interior<char>(), 0);
+  if (q->mode) DBG_HIP(ds, hipMemcpyAsync(cc.kc, dD, k16.bytes, hipMemcpyDeviceToDevice, st));   // (dense K | V: the fp16 layout itself)
   else {
-    cc.ke = (int8_t*)(ci + 2 * plane); cc.ve = cc.ke + eplane; cc.pe = pe;
-    DBG_HIP(ds, hipMemcpyAsync(ci, dQ, 2 * plane, hipMemcpyDeviceToDevice, st));
-    DBG_HIP(ds, hipMemsetAsync(cc.ke, 0, 2 * eplane, st));   // (the pad behind P: no kernel reads it as a visible key's)
-    DBG_HIP(ds, hipMemcpy2DAsync(cc.ke, (size_t)pe, dE, (size_t)P, (size_t)P, 2 * (size_t)rows * n_kv, hipMemcpyDeviceToDevice, st));
+    uint8_t* const by[2] = {(uint8_t*)cc.kc, (uint8_t*)cc.vc};
+    int8_t* const ex[2] = {cc.ke, cc.ve};
+    for (int s = 0; s < 2; ++s) {
+      DBG_HIP(ds, hipMemcpyAsync(by[s], dQ + s * nvec * hd, nvec * hd, hipMemcpyDeviceToDevice, st));
+      DBG_HIP(ds, hipMemsetAsync(ex[s], 0, heads * cc.pe, st));   // (the pad behind P: no kernel reads it as a visible key's)
+      DBG_HIP(ds, hipMemcpy2DAsync(ex[s], (size_t)cc.pe, dE + s * nvec, (size_t)P, (size_t)P, heads, hipMemcpyDeviceToDevice, st));
+    }
   }
   const float scale_log2e = (1.0f / std::sqrt((float)hd)) * 1.4426950408889634f;
-  const LlamaDecAttnArgs aa{dQkv, cc.kc, cc.vc, dPos, dCos, dSin, Part.interior<float>(), Ctx.interior<half_t>(), q->ld, H, n_kv, P, lp.nch, scale_log2e, dBias, 0, dQkn, q->qk_eps};
-  if (g1 == 1) launch_llama_dec_attn(e, st, lp, aa, B, Kv8Ext{cc.ke, cc.ve, cc.pe});
-  else launch_llama_dec_attn_keys(e, st, lp, LlamaDecAttnKeysArgs{aa, g1, dLive}, B, Kv8Ext{cc.ke, cc.ve, cc.pe});
+  const LlamaDecAttnArgs aa{dQkv, nullptr, nullptr /* kc, vc: cc's, in the launch */, dPos, dCos, dSin, Part.interior<float>(), Ctx.interior<half_t>(), q->ld, H, n_kv, P, lp.nch, scale_log2e, dBias, 0, dQkn, q->qk_eps};
+  launch_llama_dec_attn(e, st, lp, aa, B, g1, dLive, cc);
   DBG_HIP(ds, hipStreamSynchronize(st));
   DBG_HIP(ds, hipGetLastError());
   DBG_HIP(ds, Ctx.read_back(q->ctx.all));

@@ -302,29 +302,12 @@ __global__ __launch_bounds__(256) void attn_causal128_kernel(AttnCausalArgs p) {
 // =========================== incremental decoding: one new row per sequence against a K / V cache ===========================
 // ONE kernel family for both head widths, templated on D = head_dim (128, or 64 with llama_kernels_hd64.h included).
 // rk_llama_generate keeps every layer's rotated keys and its values: per layer K [rows][n_kv][P][D] then V, fp16, the keys of one
-// kv head contiguous.  kv_cache_fill_kernel copies the prompt's rows out of the prefill's fused QKV buffer (after rope128_kernel /
-// rope64_kernel); grid = (longest prompt, n_seq), a thread moves one 16-byte piece of K and of V (D / 8 pieces per head).
-// SLOTS is the decoding session's fill (rk_llama_session_admit): the same copy, but sequence b of the call goes to cache row
-// slots[b] of a cache of n_slots rows that holds other, running rows - two 16-byte stores per thread, addresses from the slot map
-// alone.  Without SLOTS sequence b goes to row b and slots / n_slots are null / 0.
-// (An FP8-cache engine, rk_llama_set_kv_fp8, keeps bytes and exponents instead and fills them with kv8_cache_fill_kernel:
-// llama_kernels_kv8.h.)
-template <int D, bool SLOTS>
-__global__ __launch_bounds__(256) void kv_cache_fill_kernel(const half_t* __restrict__ qkv, const int* __restrict__ seq_off,
-                                                            const int* __restrict__ slots, int n_slots,
-                                                            half_t* __restrict__ kc, half_t* __restrict__ vc, int ld,
-                                                            int n_heads, int n_kv, int P) {
-  const int b = blockIdx.y, t = blockIdx.x;
-  const int tok0 = seq_off[b], crow = SLOTS ? slots[b] : b;
-  if (t >= seq_off[b + 1] - tok0 || t >= P || (SLOTS && (crow < 0 || crow >= n_slots))) return;
-  const half_t* row = qkv + (size_t)(tok0 + t) * ld + (size_t)n_heads * D;
-  for (int c = threadIdx.x; c < n_kv * (D / 8); c += 256) {
-    const int h = c / (D / 8), piece = (c % (D / 8)) * 8;
-    const size_t dst = (((size_t)crow * n_kv + h) * P + t) * D + piece;
-    *(half8*)(kc + dst) = *(const half8*)(row + h * D + piece);
-    *(half8*)(vc + dst) = *(const half8*)(row + (size_t)(n_kv + h) * D + piece);
-  }
-}
+// kv head contiguous (an FP8-cache engine, rk_llama_set_kv_fp8, keeps bytes and exponents instead: llama_kernels_kv8.h).  Who writes
+// it: the step kernel's owning workgroup, and the fill and the append further down.
+
+// the regions of one layer's cache (kv_layout.h): K and V planes - fp16, or bytes in mode 1, which adds the two exponent planes
+// [rows][n_kv][pe]; ke / ve / pe are null / 0 in the fp16 layouts (modes 0 and 2)
+struct Kv8Cache { half_t* kc; half_t* vc; int8_t* ke; int8_t* ve; int pe; };
 
 struct LlamaDecAttnArgs {
   const half_t* qkv;     // [rows, ld]: the step's fused q | k | v rows, NOT yet rotated
@@ -646,6 +629,56 @@ __global__ __launch_bounds__(256) void attn_dec_cached_kernel(LlamaDecAttnArgs p
 template <int D, int R, bool BIAS>
 __global__ __launch_bounds__(256) void attn_dec_cached_win_kernel(LlamaDecAttnArgs p) { attn_dec_cached_body<D, R, BIAS, true>(p); }
 
+// ---- the cache's fill behind a prefill (the append in front of a drafting step: further down) ----
+// How a vector enters the cache, in the cache's mode KV8: lane c (of the vector's D / 8) stores its 8 values x of the key or the
+// value of (head = cache row * n_kv + kv head, position t) into that vector's plane (and exponent plane, rows of pe).  0: fp16 as
+// it is.  1 and 2 (llama_kernels_kv8.h; the vector's 16 lanes are all here): through kv8_quant16 - 1 stores the bytes and, lane
+// 0, the exponent; 2 the dequantised fp16 values.  Called once for the key and once for the value.  (The step kernel's owning
+// workgroup and the append write the same way from vectors they hold already: their stores stay where they were - byte-identical kernels.)
+template <int D, int KV8>
+__device__ __forceinline__ void kv_cache_store8(half_t* plane, int8_t* eplane, int pe, size_t head, int P, int t, int c, half8 x) {
+  static_assert(KV8 == 0 || D == 128, "FP8 K / V cache: head_dim 128");
+  [[maybe_unused]] kv8_u2 q;
+  [[maybe_unused]] int e;
+  if constexpr (KV8 != 0) x = kv8_quant16(x, q, e);
+  const size_t dst = (head * P + t) * D + c * 8;
+  if constexpr (KV8 == 1) {
+    *(kv8_u2*)((uint8_t*)plane + dst) = q;
+    if (c == 0) eplane[head * pe + t] = (int8_t)e;
+  } else *(half8*)(plane + dst) = x;
+}
+
+// kv_cache_fill_kernel copies the prompt's rows out of the prefill's fused QKV buffer (after rope128_kernel / rope64_kernel);
+// grid = (longest prompt, n_seq), a thread moves one 16-byte piece of K and of V (D / 8 pieces per head).
+// SLOTS is the decoding session's fill (rk_llama_session_admit): the same copy, but sequence b of the call goes to cache row
+// slots[b] of a cache of n_slots rows that holds other, running rows - two 16-byte stores per thread, addresses from the slot map
+// alone.  Without SLOTS sequence b goes to row b and slots / n_slots are null / 0.
+// KV8 (the entries kv8_cache_fill_kernel: llama_kernels_kv8.h): the same grid, the same item per thread - a head's 16 pieces are
+// 16 adjacent threads and the bound n_kv * 16 is a multiple of 16, so a vector's lanes enter and leave the loop together -
+// through kv_cache_store8 in the cache's mode.
+template <int D, bool SLOTS, int KV8>
+__device__ __forceinline__ void kv_cache_fill_body(const half_t* __restrict__ qkv, const int* __restrict__ seq_off,
+                                                   const int* __restrict__ slots, int n_slots, const Kv8Cache& cc, int ld,
+                                                   int n_heads, int n_kv, int P) {
+  const int b = blockIdx.y, t = blockIdx.x;
+  const int tok0 = seq_off[b], crow = SLOTS ? slots[b] : b;
+  if (t >= seq_off[b + 1] - tok0 || t >= P || (SLOTS && (crow < 0 || crow >= n_slots))) return;
+  const half_t* row = qkv + (size_t)(tok0 + t) * ld + (size_t)n_heads * D;
+  for (int c = threadIdx.x; c < n_kv * (D / 8); c += 256) {
+    const int h = c / (D / 8), piece = (c % (D / 8)) * 8;
+    const size_t head = (size_t)crow * n_kv + h;
+    kv_cache_store8<D, KV8>(cc.kc, cc.ke, cc.pe, head, P, t, c % (D / 8), *(const half8*)(row + h * D + piece));
+    kv_cache_store8<D, KV8>(cc.vc, cc.ve, cc.pe, head, P, t, c % (D / 8), *(const half8*)(row + (size_t)(n_kv + h) * D + piece));
+  }
+}
+template <int D, bool SLOTS>
+__global__ __launch_bounds__(256) void kv_cache_fill_kernel(const half_t* __restrict__ qkv, const int* __restrict__ seq_off,
+                                                            const int* __restrict__ slots, int n_slots,
+                                                            half_t* __restrict__ kc, half_t* __restrict__ vc, int ld,
+                                                            int n_heads, int n_kv, int P) {
+  kv_cache_fill_body<D, SLOTS, 0>(qkv, seq_off, slots, n_slots, Kv8Cache{kc, vc, nullptr, nullptr, 0}, ld, n_heads, n_kv, P);
+}
+
 // ---- a drafting session's step (rk_llama_session_open_draft): G1 rows per cache row, the keys appended in front of the attention ----
 struct LlamaDecAttnKeysArgs : LlamaDecAttnArgs {   // the drafting entries' arguments; the plain kernels' struct stays what it was
   int g1;                // rows per cache row: step row b belongs to cache row b / g1
@@ -659,6 +692,9 @@ struct LlamaDecAttnKeysArgs : LlamaDecAttnArgs {   // the drafting entries' argu
 // grid = rows; an item is (kv head, lane c).  A dead row (live[b] = 0) or a position outside the cache writes nothing.  QKN: the 8
 // lanes of an aligned group hold the items of one half of ONE head (D / 8 = 16 items per head) and the bound n_kv * 16 is a multiple
 // of 8, so a group enters and leaves the loop together and qkn_pairs' shuffles read active lanes only.
+// (kv8_cache_append_kernel, llama_kernels_kv8.h, is this kernel plus the quantiser in front of the stores.  The two stay two
+// kernels: merged into one body with the cache's mode as a policy, as the fill is, the fp16 instantiations came out with another
+// schedule, and the bias one measured 2 % slower than the parent's - profiles/llama_step_dispatch_refactor.txt.)
 template <int D, bool BIAS, bool QKN>
 __global__ __launch_bounds__(256) void kv_cache_append_kernel(LlamaDecAttnKeysArgs p) {
   constexpr int LK = D / 8, NL = D / 16;

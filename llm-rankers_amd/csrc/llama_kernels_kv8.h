@@ -40,46 +40,18 @@ __device__ __forceinline__ half8 kv8_quant16(const half8 x, kv8_u2& q, int& e) {
 // fp16, every stage exact), the one SkinnyFeedFp8 takes.
 __device__ __forceinline__ half8 kv8_deq8(const kv8_u2 q, int e) { return fp8_frag(q[0], q[1], e); }
 
-// the four regions of one layer's cache; MODE 2: kc / vc alone, the fp16 layout
-struct Kv8Cache { half_t* kc; half_t* vc; int8_t* ke; int8_t* ve; int pe; };
-
 struct LlamaDecAttnKv8Args : LlamaDecAttnKeysArgs {   // kc / vc: the byte planes (MODE 1) or the fp16 planes (MODE 2)
   int8_t* ke;            // key exponents [rows][n_kv][pe]
   int8_t* ve;            // value exponents
   int pe;                // P rounded up to 32
 };
 
-// kv_cache_fill_kernel<128, SLOTS> on an FP8-cache engine: the same grid, the same item per thread - a head's 16 pieces are 16
-// adjacent threads and the bound n_kv * 16 is a multiple of 16, so a vector's lanes enter and leave the loop together.
+// kv_cache_fill_kernel<128, SLOTS> on an FP8-cache engine: the fp16 entry's body (llama_kernels.h) in the cache's MODE.
 template <bool SLOTS, int MODE>
 __global__ __launch_bounds__(256) void kv8_cache_fill_kernel(const half_t* __restrict__ qkv, const int* __restrict__ seq_off,
                                                              const int* __restrict__ slots, int n_slots, Kv8Cache cc, int ld,
                                                              int n_heads, int n_kv, int P) {
-  constexpr int D = 128;
-  const int b = blockIdx.y, t = blockIdx.x;
-  const int tok0 = seq_off[b], crow = SLOTS ? slots[b] : b;
-  if (t >= seq_off[b + 1] - tok0 || t >= P || (SLOTS && (crow < 0 || crow >= n_slots))) return;
-  const half_t* row = qkv + (size_t)(tok0 + t) * ld + (size_t)n_heads * D;
-  for (int c = threadIdx.x; c < n_kv * (D / 8); c += 256) {
-    const int h = c / (D / 8), piece = (c % (D / 8)) * 8;
-    kv8_u2 kq, vq;
-    int ek, ev;
-    const half8 kd = kv8_quant16(*(const half8*)(row + h * D + piece), kq, ek);
-    const half8 vd = kv8_quant16(*(const half8*)(row + (size_t)(n_kv + h) * D + piece), vq, ev);
-    const size_t vec = ((size_t)crow * n_kv + h) * P + t, dst = vec * D + piece;
-    if constexpr (MODE == 1) {
-      *(kv8_u2*)((uint8_t*)cc.kc + dst) = kq;
-      *(kv8_u2*)((uint8_t*)cc.vc + dst) = vq;
-      if (piece == 0) {
-        const size_t ed = ((size_t)crow * n_kv + h) * cc.pe + t;
-        cc.ke[ed] = (int8_t)ek;
-        cc.ve[ed] = (int8_t)ev;
-      }
-    } else {
-      *(half8*)(cc.kc + dst) = kd;
-      *(half8*)(cc.vc + dst) = vd;
-    }
-  }
+  kv_cache_fill_body<128, SLOTS, MODE>(qkv, seq_off, slots, n_slots, cc, ld, n_heads, n_kv, P);
 }
 
 // kv_cache_append_kernel<128, BIAS, QKN> on an FP8-cache engine: a (kv head)'s 16 items are 16 adjacent threads, the bound a

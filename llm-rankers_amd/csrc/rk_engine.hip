@@ -24,6 +24,7 @@
 #include "../../include/rk_engine.h"
 #pragma GCC visibility push(hidden)   // (its inline functions are no exports of the library)
 #include "decode_ints.h"
+#include "kv_layout.h"
 #pragma GCC visibility pop
 #include "attention.h"
 #include "attention_d128.h"
@@ -720,6 +721,12 @@ void with_width(int hd, F&& f) {
   if (hd == 64) f(std::integral_constant<int, 64>());
   else f(std::integral_constant<int, 128>());
 }
+// f(std::integral_constant<int, V>) for the V of Vs that v equals: a runtime value of a closed set to a template argument; a value
+// outside the set is a host bug
+template <int... Vs, class F>
+void with_int(int v, F&& f) {
+  if (!((v == Vs && (f(std::integral_constant<int, Vs>()), true)) || ...)) abort();
+}
 
 // Runs plan_gemm's plan of the call.  *nb (optional): the plan's statistics layout, for the GEMMs that read what this one produced.
 int gemm(rk_engine* e, hipStream_t st, const Gemm& c, int* nb = nullptr) {
@@ -800,25 +807,30 @@ void launch_rope(hipStream_t st, int hd, half_t* qkv, const int* pos, const floa
   else if (bias) hipLaunchKernelGGL(rope128_kernel<true>, dim3(T), dim3(256), 0, st, qkv, pos, cos_t, sin_t, ld, n_rot, bias, n_v);
   else hipLaunchKernelGGL(rope128_kernel<false>, dim3(T), dim3(256), 0, st, qkv, pos, cos_t, sin_t, ld, n_rot, (const float*)nullptr, 0);
 }
+// layer `layer` of a K / V cache at `base`, n_layers layers of layout L back to back (kv_layout.h): the pointers the kernels take
+Kv8Cache kv_cache_layer(const KvLayerLayout& L, void* base, int layer) {
+  char* l0 = (char*)base + (size_t)layer * L.bytes;
+  return Kv8Cache{(half_t*)(l0 + L.k), (half_t*)(l0 + L.v), L.pe ? (int8_t*)(l0 + L.ke) : nullptr, L.pe ? (int8_t*)(l0 + L.ve) : nullptr, L.pe};
+}
 // the prompt's rotated keys and its values into the cache: sequence b to cache row b, or to row slots[b] of n_slots
-// cc: the layer's cache (llama_kv_layer).  kv8 (an FP8-cache engine, 128 wide): 1 = bytes and exponents into cc's four regions, 2 = the
-// dequantised fp16 values into cc.kc / cc.vc; 0: the fp16 copy
+// cc: the layer's cache (kv_cache_layer).  kv8 (an FP8-cache engine): 1 = bytes and exponents into cc's four regions, 2 = the
+// dequantised fp16 values into cc.kc / cc.vc; 0: the fp16 copy.  Which fills exist: both widths on an fp16 cache, 128 alone on an
+// FP8 cache (dec_attn_exists' rule), each to rows or to slots.
 void launch_kv_fill(hipStream_t st, int hd, const half_t* qkv, const int* seq_off, const int* slots, int n_slots, const Kv8Cache& cc,
                     int ld, int n_heads, int n_kv, int P, int maxL, int n_seq, int kv8 = 0) {
   const dim3 g = grid_kv_fill(maxL, n_seq), b(256);
-  const int* none = nullptr;
-  if (kv8) {
-    if (hd != 128 || (kv8 == 1 && (!cc.ke || !cc.ve || cc.pe < P))) abort();   // a byte fill without its exponent planes: a host bug
-    if (kv8 == 1 && slots) hipLaunchKernelGGL((kv8_cache_fill_kernel<true, 1>), g, b, 0, st, qkv, seq_off, slots, n_slots, cc, ld, n_heads, n_kv, P);
-    else if (kv8 == 1) hipLaunchKernelGGL((kv8_cache_fill_kernel<false, 1>), g, b, 0, st, qkv, seq_off, none, 0, cc, ld, n_heads, n_kv, P);
-    else if (slots) hipLaunchKernelGGL((kv8_cache_fill_kernel<true, 2>), g, b, 0, st, qkv, seq_off, slots, n_slots, cc, ld, n_heads, n_kv, P);
-    else hipLaunchKernelGGL((kv8_cache_fill_kernel<false, 2>), g, b, 0, st, qkv, seq_off, none, 0, cc, ld, n_heads, n_kv, P);
-    return;
-  }
+  if (kv8 == 1 && (!cc.ke || !cc.ve || cc.pe < P)) abort();   // a byte fill without its exponent planes: a host bug
   with_width(hd, [&](auto W) {
-    constexpr int D = decltype(W)::value;
-    if (slots) hipLaunchKernelGGL((kv_cache_fill_kernel<D, true>), g, b, 0, st, qkv, seq_off, slots, n_slots, cc.kc, cc.vc, ld, n_heads, n_kv, P);
-    else hipLaunchKernelGGL((kv_cache_fill_kernel<D, false>), g, b, 0, st, qkv, seq_off, none, 0, cc.kc, cc.vc, ld, n_heads, n_kv, P);
+    with_int<0, 1, 2>(kv8, [&](auto mode) {
+      with_int<0, 1>(slots != nullptr, [&](auto to_slots) {
+        constexpr int D = decltype(W)::value, KV8 = decltype(mode)::value;
+        constexpr bool SLOTS = decltype(to_slots)::value != 0;
+        const int ns = SLOTS ? n_slots : 0;
+        if constexpr (KV8 != 0 && D != 128) abort();           // no such kernel
+        else if constexpr (KV8 != 0) hipLaunchKernelGGL((kv8_cache_fill_kernel<SLOTS, KV8>), g, b, 0, st, qkv, seq_off, slots, ns, cc, ld, n_heads, n_kv, P);
+        else hipLaunchKernelGGL((kv_cache_fill_kernel<D, SLOTS>), g, b, 0, st, qkv, seq_off, slots, ns, cc.kc, cc.vc, ld, n_heads, n_kv, P);
+      });
+    });
   });
 }
 // n vectors of 128 through the FP8 cache's quantiser (rk_debug_kv8_quant, rk_debug_kv8_step's cache conversion)
@@ -1336,11 +1348,10 @@ int refuse_window(rk_engine* e, const char* entry, int maxL) {
 // On an engine with a sliding window every step runs the windowed entries (attn_dec_cached_win_kernel, attn_dec_combine_win_kernel):
 // a model constant again.  A row at pos < W skips and masks nothing there and gets the plain kernels' bits.
 // An FP8-cache engine (rk_llama_set_kv_fp8; 128 wide): kv8 = 1, the byte kernels (attn_dec_kv8_kernel<.., 1>, attn_dec_keys_kv8_kernel,
-// kv8_cache_append_kernel) over the four regions of Kv8Ext, or kv8 = 2 (option llama_kv_fp8 = 0), the fp16 layout holding dequantised
+// kv8_cache_append_kernel) over the four regions of Kv8Cache, or kv8 = 2 (option llama_kv_fp8 = 0), the fp16 layout holding dequantised
 // values: the fp16 reader with the rounded own key (attn_dec_kv8_kernel<.., 2>), the fp16 KEYS kernels behind the rounding append.  The
 // same rule for R; it has no R = 7 instantiation, so llama_dec_r = 2 falls back to the rule, as at width 64.
 struct LlamaDecAttnPlan { int R = 1, nch = 1, hd = 128, window = 0; dim3 grid, cgrid; int kv8 = 0; };
-struct Kv8Ext { int8_t* ke = nullptr; int8_t* ve = nullptr; int pe = 0; };
 inline int kv8_mode(const rk_engine* e) { return e->kv_fp8 ? (e->opt.llama_kv_fp8 ? 1 : 2) : 0; }
 LlamaDecAttnPlan plan_llama_dec_attn(const rk_engine* e, int rows, int P, int n_heads, int n_kv) {
   LlamaDecAttnPlan p;                                        // (no CU count enters: fixed chunk length, model-constant R)
@@ -1357,58 +1368,57 @@ LlamaDecAttnPlan plan_llama_dec_attn(const rk_engine* e, int rows, int P, int n_
   return p;
 }
 
-// the chunk kernel of an FP8-cache engine's step, plain (keys = false, MODE = p.kv8) or the byte KEYS form
-template <bool KEYSF>
-void launch_llama_dec_attn_kv8(hipStream_t st, const LlamaDecAttnPlan& p, const LlamaDecAttnKv8Args& a) {
-  auto go = [&](auto rc) {
-    constexpr int R = decltype(rc)::value;
-    auto form = [&](auto bias, auto win, auto qkn) {
-      constexpr bool B = decltype(bias)::value, W = decltype(win)::value, Q = decltype(qkn)::value;
-      if constexpr (KEYSF) hipLaunchKernelGGL((attn_dec_keys_kv8_kernel<R, B, W, Q>), p.grid, dim3(256), 0, st, a);
-      else if (p.kv8 == 1) hipLaunchKernelGGL((attn_dec_kv8_kernel<R, B, W, Q, 1>), p.grid, dim3(256), 0, st, a);
-      else hipLaunchKernelGGL((attn_dec_kv8_kernel<R, B, W, Q, 2>), p.grid, dim3(256), 0, st, a);
-    };
-    using std::true_type; using std::false_type;
-    if (a.qkn) form(false_type{}, false_type{}, true_type{});
-    else if (p.window > 0 && a.bias) form(true_type{}, true_type{}, false_type{});
-    else if (p.window > 0) form(false_type{}, true_type{}, false_type{});
-    else if (a.bias) form(true_type{}, false_type{}, false_type{});
-    else form(false_type{}, false_type{}, false_type{});
-  };
-  using std::integral_constant;
-  switch (p.R) {
-    case 8: go(integral_constant<int, 8>{}); break;
-    case 4: go(integral_constant<int, 4>{}); break;
-    case 2: go(integral_constant<int, 2>{}); break;
-    default: go(integral_constant<int, 1>{}); break;
-  }
+// ---- which kernels the step's attention has: THE one statement (the walk, the entries and the launches below follow it) ----
+// form: what the call carries, derived in launch_llama_dec_attn alone - Qwen3's head norm (never with bias or window: rk_engine_finalize),
+// else the engine's window with or without the layer's Qwen2 bias, else the bias, else the Llama kernel as it was.
+enum DecForm { DEC_PLAIN, DEC_BIAS, DEC_WIN, DEC_WIN_BIAS, DEC_QKN };
+constexpr bool dec_form_bias(int f) { return f == DEC_BIAS || f == DEC_WIN_BIAS; }
+constexpr bool dec_form_win(int f) { return f == DEC_WIN || f == DEC_WIN_BIAS; }
+// * R = 8 / 4 / 2 / 1 everywhere; R = 7 at width 128 on an fp16 cache alone (plan_llama_dec_attn gives it nowhere else);
+// * the head norm at width 128 only; an FP8 cache (kv8 = 1 bytes, 2 dequantised fp16) at width 128 only;
+// * each of these as the plain step and as the KEYS step (a drafting session's, behind the append): KEYS constrains nothing.
+constexpr bool dec_attn_exists(int D, int R, int form, int kv8) {
+  return (D == 128 || D == 64) && (R == 8 || R == 4 || R == 2 || R == 1 || (R == 7 && D == 128 && kv8 == 0)) &&
+         form >= DEC_PLAIN && form <= DEC_QKN && (form != DEC_QKN || D == 128) && (kv8 == 0 || ((kv8 == 1 || kv8 == 2) && D == 128));
 }
-
-void launch_llama_dec_attn(rk_engine* e, hipStream_t st, const LlamaDecAttnPlan& p, LlamaDecAttnArgs a, int rows, const Kv8Ext& x8 = {}) {
-  a.nch = p.nch; a.window = p.window;
-  Bracket br(e, st, PC_DEC_ATTN, 4.0 * rows * (double)a.P * a.n_heads * p.hd, 2.0 * rows * (double)a.P * a.n_kv * p.hd * (p.kv8 == 1 ? 1.0 : 2.0));
-  if (p.kv8) {                                               // (128 wide: rk_engine_finalize)
-    if (p.hd != 128 || (p.kv8 == 1 && (!x8.ke || !x8.ve || x8.pe < a.P))) abort();   // a byte plan without its exponent planes: a host bug
-    launch_llama_dec_attn_kv8<false>(st, p, LlamaDecAttnKv8Args{{a, 1, nullptr}, x8.ke, x8.ve, x8.pe});
-    if (p.window > 0) hipLaunchKernelGGL(attn_dec_combine_win_kernel<128>, p.cgrid, dim3(128), 0, st, a);
-    else hipLaunchKernelGGL(attn_dec_combine_kernel<128>, p.cgrid, dim3(128), 0, st, a);
-    return;
-  }
-  with_width(p.hd, [&](auto W) {
-    constexpr int D = decltype(W)::value;
-    auto go = [&](auto rc) {                                 // the bias-free instantiation is the Llama kernel as it was
-      constexpr int R = decltype(rc)::value;
-      if constexpr (R == 7 && D != 128) abort();             // no such kernel: plan_llama_dec_attn gives R = 7 at 128 alone
-      else if (a.qkn) {                                      // Qwen3's head norm: 128 wide, no bias, no window (rk_engine_finalize)
-        if constexpr (D == 128) hipLaunchKernelGGL((attn_dec_cached_qkn_kernel<D, R>), p.grid, dim3(256), 0, st, a);
-        else abort();
-      }
-      else if (p.window > 0) {
-        if (a.bias) hipLaunchKernelGGL((attn_dec_cached_win_kernel<D, R, true>), p.grid, dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((attn_dec_cached_win_kernel<D, R, false>), p.grid, dim3(256), 0, st, a);
-      }
-      else if (a.bias) hipLaunchKernelGGL((attn_dec_cached_kernel<D, R, true>), p.grid, dim3(256), 0, st, a);
-      else hipLaunchKernelGGL((attn_dec_cached_kernel<D, R, false>), p.grid, dim3(256), 0, st, a);
+// The chunk kernel of a combination that exists.  kv8 = 2 with KEYS is the fp16 KEYS kernel: it forms no key, and the rounding
+// append in front of it has left dequantised values in the fp16 layout.
+template <int D, int R, int F, bool KEYS, int KV8>
+constexpr auto dec_attn_entry() {
+  static_assert(dec_attn_exists(D, R, F, KV8), "no such kernel");
+  constexpr bool B = dec_form_bias(F), W = dec_form_win(F), Q = F == DEC_QKN;
+  if constexpr (KV8 == 1 && KEYS) return &attn_dec_keys_kv8_kernel<R, B, W, Q>;
+  else if constexpr (KV8 != 0 && !KEYS) return &attn_dec_kv8_kernel<R, B, W, Q, KV8>;
+  else if constexpr (Q && KEYS) return &attn_dec_keys_qkn_kernel<D, R>;
+  else if constexpr (Q) return &attn_dec_cached_qkn_kernel<D, R>;
+  else if constexpr (W && KEYS) return &attn_dec_keys_win_kernel<D, R, B>;
+  else if constexpr (W) return &attn_dec_cached_win_kernel<D, R, B>;
+  else if constexpr (KEYS) return &attn_dec_keys_kernel<D, R, B>;
+  else return &attn_dec_cached_kernel<D, R, B>;
+}
+// ... and the append in front of a KEYS step, which knows no R and no window: the fp16 kernel, or the rounding one in the cache's mode
+template <int D, int F, int KV8>
+constexpr auto kv_append_entry() {
+  constexpr bool B = dec_form_bias(F), Q = F == DEC_QKN;
+  if constexpr (KV8 != 0) return &kv8_cache_append_kernel<B, Q, KV8>;
+  else return &kv_cache_append_kernel<D, B, Q>;
+}
+// The one walk from a plan and a call's form to the template arguments: f(D, R, form, KEYS, kv8), each an integral_constant.  A
+// combination outside dec_attn_exists is a host bug and aborts HERE.
+template <class Fn>
+void with_dec_attn(const LlamaDecAttnPlan& p, int form, bool keys, Fn&& f) {
+  with_width(p.hd, [&](auto d) {
+    auto go = [&](auto r) {
+      with_int<DEC_PLAIN, DEC_BIAS, DEC_WIN, DEC_WIN_BIAS, DEC_QKN>(form, [&](auto fm) {
+        with_int<0, 1>(keys, [&](auto k) {
+          with_int<0, 1, 2>(p.kv8, [&](auto m) {
+            constexpr bool K = decltype(k)::value != 0;
+            if constexpr (dec_attn_exists(decltype(d)::value, decltype(r)::value, decltype(fm)::value, decltype(m)::value))
+              f(d, r, fm, std::bool_constant<K>(), m);
+            else abort();
+          });
+        });
+      });
     };
     using std::integral_constant;
     switch (p.R) {
@@ -1416,81 +1426,34 @@ void launch_llama_dec_attn(rk_engine* e, hipStream_t st, const LlamaDecAttnPlan&
       case 7: go(integral_constant<int, 7>{}); break;
       case 4: go(integral_constant<int, 4>{}); break;
       case 2: go(integral_constant<int, 2>{}); break;
-      default: go(integral_constant<int, 1>{}); break;
+      case 1: go(integral_constant<int, 1>{}); break;
+      default: abort();
     }
-    if (p.window > 0) hipLaunchKernelGGL(attn_dec_combine_win_kernel<D>, p.cgrid, dim3(D), 0, st, a);
-    else hipLaunchKernelGGL(attn_dec_combine_kernel<D>, p.cgrid, dim3(D), 0, st, a);
   });
 }
 
-// A drafting session's step (rk_llama_session_open_draft): `rows` = n_slots * g1 step rows over a cache of n_slots rows.
-// kv_cache_append_kernel puts every live row's key and value where a plain step would have written them, then the keys-cached
-// entries (attn_dec_keys_*_kernel: the plain body without the new-key select and the cache write) run by the SAME plan rule over
-// `rows`, and the plain merge.  One more small launch per layer than the plain step.
-// the append in front of a drafting step's attention: the fp16 kernel, or on an FP8-cache engine the rounding one in the plan's layout
-static void launch_kv_append(hipStream_t st, const LlamaDecAttnPlan& p, const LlamaDecAttnKeysArgs& a, int rows, const Kv8Ext& x8) {
-  const dim3 g(rows), b(256);
-  if (p.kv8) {
-    if (p.hd != 128 || (p.kv8 == 1 && (!x8.ke || !x8.ve || x8.pe < a.P))) abort();   // a byte plan without its exponent planes: a host bug
-    const LlamaDecAttnKv8Args a8{a, x8.ke, x8.ve, x8.pe};
-    auto go = [&](auto mode) {
-      constexpr int M = decltype(mode)::value;
-      if (a.qkn) hipLaunchKernelGGL((kv8_cache_append_kernel<false, true, M>), g, b, 0, st, a8);
-      else if (a.bias) hipLaunchKernelGGL((kv8_cache_append_kernel<true, false, M>), g, b, 0, st, a8);
-      else hipLaunchKernelGGL((kv8_cache_append_kernel<false, false, M>), g, b, 0, st, a8);
-    };
-    if (p.kv8 == 1) go(std::integral_constant<int, 1>{});
-    else go(std::integral_constant<int, 2>{});
-    return;
-  }
-  with_width(p.hd, [&](auto W) {
-    constexpr int D = decltype(W)::value;
-    if (a.qkn) {
-      if constexpr (D == 128) hipLaunchKernelGGL((kv_cache_append_kernel<D, false, true>), g, b, 0, st, a);
-      else abort();
-    }
-    else if (a.bias) hipLaunchKernelGGL((kv_cache_append_kernel<D, true, false>), g, b, 0, st, a);
-    else hipLaunchKernelGGL((kv_cache_append_kernel<D, false, false>), g, b, 0, st, a);
-  });
-}
-void launch_llama_dec_attn_keys(rk_engine* e, hipStream_t st, const LlamaDecAttnPlan& p, LlamaDecAttnKeysArgs a, int rows, const Kv8Ext& x8 = {}) {
-  a.nch = p.nch; a.window = p.window;
+// The step's attention, the one entry of its callers (llama_step_rows, rk_debug_attn kind 5, rk_debug_kv8_step): `rows` step rows
+// over the layer's cache cc (llama_kv_layer; a.kc / a.vc come from it).  g1 == 1 (and no `live`): the plain step - the chunk kernel
+// forms, uses and writes each row's key - then the merge.  Else a drafting session's step (rk_llama_session_open_draft): rows =
+// cache rows * g1; the append puts every live row's key and value where a plain step would have written them, then the KEYS
+// entries (the plain body without the new-key select and the cache write) run by the SAME plan over `rows`, and the plain merge:
+// one more small launch per layer than the plain step.
+void launch_llama_dec_attn(rk_engine* e, hipStream_t st, const LlamaDecAttnPlan& p, LlamaDecAttnArgs a, int rows, int g1, const int* live,
+                           const Kv8Cache& cc) {
+  const bool keys = g1 != 1;
+  a.kc = cc.kc; a.vc = cc.vc; a.nch = p.nch; a.window = p.window;
+  const LlamaDecAttnKv8Args a8{{a, g1, live}, cc.ke, cc.ve, cc.pe};   // every entry takes it, or the base of it that is its own struct
+  const int form = a.qkn ? DEC_QKN : (p.window > 0 ? (a.bias ? DEC_WIN_BIAS : DEC_WIN) : (a.bias ? DEC_BIAS : DEC_PLAIN));
+  // a byte plan without its exponent planes, a KEYS step without its live flags, a head norm beside a bias or a window: host bugs
+  if ((p.kv8 == 1 && (!cc.ke || !cc.ve || cc.pe < a.P)) || (keys && (g1 < 1 || !live)) || (a.qkn && (a.bias || p.window > 0))) abort();
   Bracket br(e, st, PC_DEC_ATTN, 4.0 * rows * (double)a.P * a.n_heads * p.hd, 2.0 * rows * (double)a.P * a.n_kv * p.hd * (p.kv8 == 1 ? 1.0 : 2.0));
-  launch_kv_append(st, p, a, rows, x8);
-  if (p.kv8 == 1) {                                          // the byte KEYS kernels; kv8 = 2: the fp16 KEYS kernels below, on the dequantised values
-    launch_llama_dec_attn_kv8<true>(st, p, LlamaDecAttnKv8Args{a, x8.ke, x8.ve, x8.pe});
-    const LlamaDecAttnArgs base = a;
-    if (p.window > 0) hipLaunchKernelGGL(attn_dec_combine_win_kernel<128>, p.cgrid, dim3(128), 0, st, base);
-    else hipLaunchKernelGGL(attn_dec_combine_kernel<128>, p.cgrid, dim3(128), 0, st, base);
-    return;
-  }
-  with_width(p.hd, [&](auto W) {
-    constexpr int D = decltype(W)::value;
-    auto go = [&](auto rc) {
-      constexpr int R = decltype(rc)::value;
-      if constexpr (R == 7 && D != 128) abort();             // no such kernel: plan_llama_dec_attn gives R = 7 at 128 alone
-      else if (a.qkn) {
-        if constexpr (D == 128) hipLaunchKernelGGL((attn_dec_keys_qkn_kernel<D, R>), p.grid, dim3(256), 0, st, a);
-        else abort();
-      }
-      else if (p.window > 0) {
-        if (a.bias) hipLaunchKernelGGL((attn_dec_keys_win_kernel<D, R, true>), p.grid, dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((attn_dec_keys_win_kernel<D, R, false>), p.grid, dim3(256), 0, st, a);
-      }
-      else if (a.bias) hipLaunchKernelGGL((attn_dec_keys_kernel<D, R, true>), p.grid, dim3(256), 0, st, a);
-      else hipLaunchKernelGGL((attn_dec_keys_kernel<D, R, false>), p.grid, dim3(256), 0, st, a);
-    };
-    using std::integral_constant;
-    switch (p.R) {
-      case 8: go(integral_constant<int, 8>{}); break;
-      case 7: go(integral_constant<int, 7>{}); break;
-      case 4: go(integral_constant<int, 4>{}); break;
-      case 2: go(integral_constant<int, 2>{}); break;
-      default: go(integral_constant<int, 1>{}); break;
-    }
-    const LlamaDecAttnArgs base = a;                         // the merge is per (head, row): the plain kernels
-    if (p.window > 0) hipLaunchKernelGGL(attn_dec_combine_win_kernel<D>, p.cgrid, dim3(D), 0, st, base);
-    else hipLaunchKernelGGL(attn_dec_combine_kernel<D>, p.cgrid, dim3(D), 0, st, base);
+  with_dec_attn(p, form, keys, [&](auto d, auto r, auto f, auto k, auto m) {
+    constexpr int D = decltype(d)::value, R = decltype(r)::value, F = decltype(f)::value, KV8 = decltype(m)::value;
+    constexpr bool KEYS = decltype(k)::value;
+    if constexpr (KEYS) hipLaunchKernelGGL((kv_append_entry<D, F, KV8>()), dim3(rows), dim3(256), 0, st, a8);
+    hipLaunchKernelGGL((dec_attn_entry<D, R, F, KEYS, KV8>()), p.grid, dim3(256), 0, st, a8);
+    // the merge is per (head, row): the plain kernels for every form, mode and step
+    hipLaunchKernelGGL((dec_form_win(F) ? attn_dec_combine_win_kernel<D> : attn_dec_combine_kernel<D>), p.cgrid, dim3(D), 0, st, a8);
   });
 }
 
@@ -3019,21 +2982,13 @@ static int llama_finalize(rk_engine* e) {
 // keep (rk_llama_generate only): every layer's rotated K and its V are also copied to the cache, P positions per sequence
 // slots (rk_llama_session_admit): sequence b goes to cache row slots[b] (device ints) of a cache of `rows` rows
 struct LlamaKeep { half_t* kv; int P; const int* slots = nullptr; int rows = 0; };
-// One layer's K / V cache inside lkv, for `rows` cache rows of P positions.  fp16 layout (kv8 = 0, and 2: the dequantised values):
-// K [rows][n_kv][P][hd] then V.  kv8 = 1 (llama_kernels_kv8.h): K bytes | V bytes | K exponents [rows][n_kv][pe] | V exponents,
-// pe = P rounded up to 32 - every region a multiple of 32 bytes, so each starts 32-byte aligned in hipMalloc's block.
-static size_t llama_kv_layer_halfs(const rk_engine* e, int kv8, int rows, int P) {
-  const size_t KV = (size_t)e->ld.n_kv_heads * e->ld.head_dim, pe = ((size_t)P + 31) & ~(size_t)31;
-  return kv8 == 1 ? ((size_t)rows * KV * P + (size_t)rows * e->ld.n_kv_heads * pe) : 2 * (size_t)rows * KV * P;   // (bytes / 2)
+// One layer's K / V cache inside lkv, for `rows` cache rows of P positions, in the engine's shape: kv_layout.h's layout.
+static KvLayerLayout llama_kv_layout(const rk_engine* e, int kv8, int rows, int P) {
+  return kv_layer_layout(kv8, rows, e->ld.n_kv_heads, e->ld.head_dim, P);
 }
+static size_t llama_kv_layer_halfs(const rk_engine* e, int kv8, int rows, int P) { return llama_kv_layout(e, kv8, rows, P).bytes / 2; }
 static Kv8Cache llama_kv_layer(const rk_engine* e, half_t* base, int kv8, int layer, int rows, int P) {
-  const size_t KV = (size_t)e->ld.n_kv_heads * e->ld.head_dim, plane = (size_t)rows * KV * P;
-  half_t* l0 = base + (size_t)layer * llama_kv_layer_halfs(e, kv8, rows, P);
-  if (kv8 != 1) return Kv8Cache{l0, l0 + plane, nullptr, nullptr, 0};
-  const int pe = (P + 31) & ~31;
-  uint8_t* b0 = (uint8_t*)l0;
-  int8_t* e0 = (int8_t*)(b0 + 2 * plane);
-  return Kv8Cache{(half_t*)b0, (half_t*)(b0 + plane), e0, e0 + (size_t)rows * e->ld.n_kv_heads * pe, pe};
+  return kv_cache_layer(llama_kv_layout(e, kv8, rows, P), base, layer);
 }
 static int llama_prefill(rk_engine* e, const int32_t* tokens, const int32_t* off, int n_seq, const LlamaKeep* keep = nullptr) {
   if (!e || e->family != 1) return fail(e, RK_ERR_STATE, "not a Llama engine");
@@ -3238,7 +3193,7 @@ static int ensure_llama_gen(rk_engine* e, int n_seq, int P, size_t ints, int ste
 // rows are the engine's (ensure_llama_gen).  Nothing here depends on which rows are live: a row's bits follow from its own
 // tokens and position.
 // g1 > 1 (a drafting session): `rows` = cache rows * g1 step rows, g1 consecutive ones per cache row; live[rows] says whose key
-// and value go to the cache (kv_cache_append_kernel), and the attention reads every key from there (launch_llama_dec_attn_keys).
+// and value go to the cache (kv_cache_append_kernel), and the attention reads every key from there (launch_llama_dec_attn).
 static int llama_step_rows(rk_engine* e, hipStream_t st, int rows, int P, const int* d_next, const int* d_pos, int g1 = 1,
                            const int* d_live = nullptr) {
   const rk_llama_desc& l = e->ld;
@@ -3259,10 +3214,9 @@ static int llama_step_rows(rk_engine* e, hipStream_t st, int rows, int P, const 
     const LlamaLayerW& w = e->ll[i];
     RC(gemm(e, st, normed(Gemm(PC_DEC_GEMM, EPI_STORE_F16, ns.x(), dm, w.qkv_f, dm, lg.qkv, ldq, rows, ldq, dm).w8(b8(w.qkv8)))));
     const Kv8Cache cc = llama_kv_layer(e, e->lkv.p, ap.kv8, i, rows / g1, P);
-    const LlamaDecAttnArgs aa{lg.qkv, cc.kc, cc.vc, d_pos, e->rope_cos, e->rope_sin, e->lpart.p, lg.ctx,
+    const LlamaDecAttnArgs aa{lg.qkv, nullptr, nullptr /* kc, vc: cc's, in the launch */, d_pos, e->rope_cos, e->rope_sin, e->lpart.p, lg.ctx,
                               ldq, l.n_heads, l.n_kv_heads, P, ap.nch, scale_log2e, w.qkv_bias, 0, w.qk_norm, l.eps};
-    if (g1 == 1) launch_llama_dec_attn(e, st, ap, aa, rows, Kv8Ext{cc.ke, cc.ve, cc.pe});
-    else launch_llama_dec_attn_keys(e, st, ap, LlamaDecAttnKeysArgs{aa, g1, d_live}, rows, Kv8Ext{cc.ke, cc.ve, cc.pe});
+    launch_llama_dec_attn(e, st, ap, aa, rows, g1, d_live, cc);
     RC(ns.producer(e, st, Gemm(PC_DEC_GEMM, EPI_RESID_F32, lg.ctx, Q, w.o, Q, ns.hidden, dm, rows, dm, Q).on(GEMM_STREAM).w8(b8(w.o8))));
     RC(gemm(e, st, normed(Gemm(PC_DEC_GEMM, EPI_SWIGLU_F16, ns.x(), dm, w.gu_f, dm, lg.ffh, F, rows, 2 * F, dm).w8(b8(w.gu8)))));
     RC(ns.producer(e, st, Gemm(PC_DEC_GEMM, EPI_RESID_F32, lg.ffh, F, w.down, F, ns.hidden, dm, rows, dm, F).on(GEMM_STREAM).w8(b8(w.down8)), i + 1 < l.n_layers));

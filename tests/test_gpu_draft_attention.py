@@ -1,5 +1,5 @@
 """The attention of a drafting step alone on an MI355X: kv_cache_append_kernel and the attn_dec_keys_* entries through
-rk_debug_attn kind 5 with g1 / live - plan_llama_dec_attn over the step rows and launch_llama_dec_attn_keys, as llama_step_rows
+rk_debug_attn kind 5 with g1 / live - plan_llama_dec_attn over the step rows and launch_llama_dec_attn with g1 / live, as llama_step_rows
 calls them - against the fp64 reference of tests/_attn_ref_draft.py (tests/test_attn_ref_draft_host.py shows that it tells wrong
 kernels apart on these very problems).
 

@@ -154,22 +154,24 @@ def _check_step(eng, p, what, window=0, qk=None):
 
 
 ROWS3 = [[0, 129, 300], [1, 32, 256], [31, 127, 255], [128, 99, 100]]      # three rows with different positions: every position again
-FORMS = ["plain", "bias", "window", "qknorm"]
+FORMS = ["plain", "bias", "window", "window+bias", "qknorm"]
+WINDOWED = ("window", "window+bias")
 
 
 def _problem(form, seed, H, n_kv, pos):
     import _qwen3_ref as Q3
     if form == "qknorm":
         return Q3.build_qkn_step(seed, H, n_kv, pos, P_STEP)
-    return A.build_step(seed, H, n_kv, pos, P_STEP, "R", bias=form == "bias")
+    return A.build_step(seed, H, n_kv, pos, P_STEP, "R", bias=form in ("bias", "window+bias"))
 
 
 @pytest.mark.parametrize("heads", HEADS, ids=lambda h: f"H{h[0]}kv{h[1]}")
 @pytest.mark.parametrize("form", FORMS)
 def test_step_attention_bytes_equal_rounded_fp16_and_fp64(eng8, eng8_win, form, heads):
     """every kernel (form x R x mode is an instantiation of its own) at every position of STEP_POS as a one-row call, and in four
-    three-row calls with different positions; the window form (W = 100) so sees positions on both sides of W, 99 and 100 included"""
-    eng, window = (eng8_win, 100) if form == "window" else (eng8, 0)
+    three-row calls with different positions; the window forms (W = 100, without and with the bias) so see positions on both sides of W,
+    99 and 100 included"""
+    eng, window = (eng8_win, 100) if form in WINDOWED else (eng8, 0)
     H, n_kv = heads
     worst = 0.0
     for n, pos in enumerate([[t] for t in STEP_POS] + ROWS3):
@@ -189,7 +191,7 @@ def test_keys_form_equals_the_fp16_keys_kernel(eng8, eng8_win, form, heads):
     with two cache rows.  With every row dead (live = 0) nothing is appended: the FP8 KEYS kernel over the quantised cache against
     the unchanged fp16 KEYS kernel over the dequantised cache, bit for bit.  With every row live: the rounding append leaves numpy's
     quantisation of what the fp16 append writes, and the two forms agree."""
-    eng = eng8_win if form == "window" else eng8
+    eng = eng8_win if form in WINDOWED else eng8
     H, n_kv = heads
     for n, base in enumerate([[t] for t in STEP_POS] + [[0, 129], [31, 255], [127, 300]]):
         pos = [min(b + j, P_STEP - 1) for b in base for j in range(3)]
