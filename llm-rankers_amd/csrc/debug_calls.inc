@@ -404,8 +404,8 @@ int rk_debug_attn(rk_engine* e, rk_debug_attn_call* q) {
     if (n_kv <= 0 || H % n_kv) return fail(e, RK_ERR_INVALID, "debug attn: n_kv must divide H");
     ldq_min = (long)(H + 2 * n_kv) * hd; ldctx_min = (long)H * hd; q_rows_need = out_rows_need = T;
     cp = plan_llama_attn(e, B, maxL, H, n_kv);
-    plan_out((cp.hd64 ? 2 : (int)cp.dma) + (cp.window > 0 ? 4 : 0), cp.nw, cp.grid, dim3(0, 0, 0), cp.lds);
-    if (cp.no_win_kernel) return refuse_window(e, "debug attn", maxL);
+    plan_out((cp.hd == 64 ? 2 : (int)(cp.kind == CAUSAL_DMA)) + (cp.window > 0 ? 4 : 0), cp.nw, cp.grid, dim3(0, 0, 0), cp.lds);
+    if (!causal_attn_exists(cp)) return refuse_window(e, "debug attn", maxL);
   } else if (kind == 6) {
     const int P = q->P;
     if (P <= 0 || P > 8192) return fail(e, RK_ERR_INVALID, "debug attn: the T5 cached step takes a cache of 1..8192 positions");

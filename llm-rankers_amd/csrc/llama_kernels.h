@@ -97,27 +97,41 @@ __global__ __launch_bounds__(256) void rope128_kernel(half_t* __restrict__ qkv, 
 }
 
 struct AttnCausalArgs {
-  const half_t* qkv;     // [T, ld]: q heads at column 0, k heads at n_heads*128, v heads at (n_heads + n_kv)*128
-  half_t* ctx;           // [T, ldctx] (n_heads * 128 columns)
+  const half_t* qkv;     // [T, ld]: q heads at column 0, k heads at n_heads*D, v heads at (n_heads + n_kv)*D (D = head_dim)
+  half_t* ctx;           // [T, ldctx] (n_heads * D columns)
   const int* seq_off;    // [B+1]
   int ld, ldctx, n_heads, n_kv;
   float scale_log2e;     // head_dim**-0.5 * log2(e): the softmax runs in the log2 domain
-  int n_seq, nqb;        // attn_causal128_dma_kernel (1-D grid): sequences, query blocks of 32 NW of the longest sequence
-  int ko;                // attn_causal128_dma_kernel, measurement builds only (-DRK_MEASURE): timing knock-outs, see ATCD_KO
+  int n_seq, nqb;        // attn_causal_dma_kernel (1-D grid): sequences, query blocks of 32 NW of the longest sequence
+  int ko;                // attn_causal_dma_kernel, measurement builds only (-DRK_MEASURE): timing knock-outs, see ATCD_KO
 };
 struct AttnCausalWinArgs : AttnCausalArgs {   // the windowed entries' arguments; the plain kernels' struct stays what it was
   int window;            // Mistral's sliding window: W > 0, query i sees keys max(0, i - W + 1) .. i
 };
+// The two prefill kernels below take WIN as a template parameter: WIN = 0 is the plain kernel over AttnCausalArgs, WIN = 1 the
+// windowed entry over AttnCausalWinArgs.  The windowed form differs from the plain one in the 64-key tiles (chunks) it skips and
+// the keys it masks, nothing else: the walk starts at the first tile that holds a visible key of the block's first query, a wave
+// skips a tile that ends below its first query's bound, and a tile that starts below the bound of the wave's last query inside
+// the sequence gets the lower mask - the causal edge's -1e30.  So a sequence no longer than W runs the very tile bodies the plain
+// kernel runs and gets its bits.  (A lane whose keys of a tile are ALL below its bound - the tile is another lane's - forms
+// weights exp2(0) = 1 against its maximum of -1e30; its own first visible tile comes later, moves the maximum to a real score and
+// multiplies all of that by alpha = exp2(-1e30 - m) = 0, exactly.)
+template <bool WIN> using AttnCausalArgsOf = std::conditional_t<WIN, AttnCausalWinArgs, AttnCausalArgs>;
 
-// Flash-style causal attention, d = 128.  grid = (ceil(maxL / 128), n_heads, B); 256 threads = 4 waves x 32 queries.
-// Per 64-key tile: K rows and V TRANSPOSED are staged in LDS; S^T = K Q^T by MFMA 32x32x16 (A = K rows, B = Q^T) so a
-// lane owns ONE query column and the online-softmax state is per-lane scalars; the fp16 probabilities are already in
-// B-operand position for O^T = V^T P^T (four 32-row d fragments).  Tiles above the diagonal are skipped.
-#define ATC_KSTR 136   // sK row stride in halfs (272 B: 16-B aligned)
+// Flash-style causal attention staged through registers, D = head_dim (128 or 64): ONE kernel for every sequence length.  q heads
+// at column 0, k heads at n_heads*D, v heads at (n_heads + n_kv)*D, ctx [T, ldctx] of n_heads*D columns.
+// grid = (ceil(maxL / 128), n_heads, B); 256 threads = 4 waves x 32 queries.  Per 64-key tile: K rows and V TRANSPOSED are staged
+// in LDS (17.5 KiB at D = 64); S^T = K Q^T by MFMA 32x32x16 (D / 16 k16 steps; A = K rows, B = Q^T) so a lane owns ONE query column
+// and the online-softmax state is per-lane scalars; the fp16 probabilities are already in B-operand position for O^T = V^T P^T
+// (D / 32 32-row d fragments).  Tiles above the diagonal are skipped, the diagonal tile is masked per lane.  A row's arithmetic
+// depends on its own sequence only (its position, its keys in tiles of 64 in order): batch-independent.
+#define ATC_KPAD 8     // sK row stride in halfs is D + 8 (144 / 272 B: 16-B aligned)
 #define ATC_VSTR 68    // sVt row stride in halfs (136 B: 8-B aligned)
-__global__ __launch_bounds__(256) void attn_causal128_kernel(AttnCausalArgs p) {
-  __shared__ __attribute__((aligned(16))) half_t sK[64 * ATC_KSTR];
-  __shared__ __attribute__((aligned(16))) half_t sVt[128 * ATC_VSTR];
+template <int D, bool WIN>
+__global__ __launch_bounds__(256) void attn_causal_tile_kernel(AttnCausalArgsOf<WIN> p) {
+  constexpr int KSTR = D + ATC_KPAD, C8 = D / 8;             // C8: the 16-byte pieces of a row
+  __shared__ __attribute__((aligned(16))) half_t sK[64 * KSTR];
+  __shared__ __attribute__((aligned(16))) half_t sVt[D * ATC_VSTR];
   const int b = blockIdx.z, h = blockIdx.y, qt = blockIdx.x;
   const int tok0 = p.seq_off[b];
   const int L = p.seq_off[b + 1] - tok0;
@@ -125,38 +139,45 @@ __global__ __launch_bounds__(256) void attn_causal128_kernel(AttnCausalArgs p) {
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int hh = lane >> 5, l31 = lane & 31;
   const int kvh = h / (p.n_heads / p.n_kv);
-  const half_t* kbase = p.qkv + (size_t)(p.n_heads + kvh) * 128;
-  const half_t* vbase = p.qkv + (size_t)(p.n_heads + p.n_kv + kvh) * 128;
+  const half_t* kbase = p.qkv + (size_t)(p.n_heads + kvh) * D;
+  const half_t* vbase = p.qkv + (size_t)(p.n_heads + p.n_kv + kvh) * D;
   const int q0 = qt * 128 + wave * 32;
   const bool wave_active = q0 < L;
   const int qpos = q0 + l31;
   const int qrow = qpos < L ? qpos : L - 1;
-  half8 qf[8];
+  half8 qf[D / 16];
   {
-    const half_t* qptr = p.qkv + (size_t)(tok0 + qrow) * p.ld + h * 128 + 8 * hh;
+    const half_t* qptr = p.qkv + (size_t)(tok0 + qrow) * p.ld + h * D + 8 * hh;
 #pragma unroll
-    for (int s = 0; s < 8; ++s) qf[s] = *(const half8*)(qptr + 16 * s);
+    for (int s = 0; s < D / 16; ++s) qf[s] = *(const half8*)(qptr + 16 * s);
   }
-  f32x16 o[4];
+  f32x16 o[D / 32];
 #pragma unroll
-  for (int f = 0; f < 4; ++f)
+  for (int f = 0; f < D / 32; ++f)
 #pragma unroll
     for (int r = 0; r < 16; ++r) o[f][r] = 0.f;
   float m_run = -1e30f, l_run = 0.f;
   const int last_q = min(qt * 128 + 127, L - 1);
   const int nkt = (last_q >> 6) + 1;                 // key tiles this block of queries can see (causal)
-  for (int kt = 0; kt < nkt; ++kt) {
+  int window = 0, kt0 = 0, wlo = 0, wlo_last = 0;
+  if constexpr (WIN) {
+    window = p.window;
+    kt0 = max(qt * 128 - window + 1, 0) >> 6;        // the first tile the block's first query sees
+    wlo = q0 - window + 1;                           // lower bound of the wave's first query (its lowest)
+    wlo_last = min(q0 + 31, L - 1) - window + 1;     // ... of its last query inside the sequence (its highest)
+  }
+  for (int kt = kt0; kt < nkt; ++kt) {
     __syncthreads();                                   // the previous tile's fragments are read
     // ---- stage K (row-major) and V^T (key pairs) of keys kt*64 .. kt*64+63; rows beyond L are clamped copies (masked) ----
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int c = tid + 256 * i, row = c >> 4, cc = c & 15;
+    for (int i = 0; i < D / 32; ++i) {
+      const int c = tid + 256 * i, row = c / C8, cc = c % C8;
       const int key = min(kt * 64 + row, L - 1);
-      *(half8*)(sK + row * ATC_KSTR + cc * 8) = *(const half8*)(kbase + (size_t)(tok0 + key) * p.ld + cc * 8);
+      *(half8*)(sK + row * KSTR + cc * 8) = *(const half8*)(kbase + (size_t)(tok0 + key) * p.ld + cc * 8);
     }
 #pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int c = tid + 256 * i, kp = c >> 4, cc = c & 15;
+    for (int i = 0; i < D / 64; ++i) {
+      const int c = tid + 256 * i, kp = c / C8, cc = c % C8;
       const int k0 = min(kt * 64 + 2 * kp, L - 1), k1 = min(kt * 64 + 2 * kp + 1, L - 1);
       const half8 v0 = *(const half8*)(vbase + (size_t)(tok0 + k0) * p.ld + cc * 8);
       const half8 v1 = *(const half8*)(vbase + (size_t)(tok0 + k1) * p.ld + cc * 8);
@@ -168,13 +189,15 @@ __global__ __launch_bounds__(256) void attn_causal128_kernel(AttnCausalArgs p) {
     }
     __syncthreads();
     if (!wave_active || kt * 64 > q0 + 31) continue;    // this wave's queries see none of these keys
+    if (WIN && kt * 64 + 63 < wlo) continue;            // nor of these: the tile ends below the window of every one of them
+    const bool need_low = WIN && kt * 64 < wlo_last;    // the tile starts below the window of the wave's last query
     f32x16 s0, s1;
 #pragma unroll
     for (int r = 0; r < 16; ++r) { s0[r] = 0.f; s1[r] = 0.f; }
 #pragma unroll
-    for (int s = 0; s < 8; ++s) {
-      const half8 k0 = *(const half8*)(sK + l31 * ATC_KSTR + 16 * s + 8 * hh);
-      const half8 k1 = *(const half8*)(sK + (32 + l31) * ATC_KSTR + 16 * s + 8 * hh);
+    for (int s = 0; s < D / 16; ++s) {
+      const half8 k0 = *(const half8*)(sK + l31 * KSTR + 16 * s + 8 * hh);
+      const half8 k1 = *(const half8*)(sK + (32 + l31) * KSTR + 16 * s + 8 * hh);
       s0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(k0, qf[s], s0, 0, 0, 0);
       s1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(k1, qf[s], s1, 0, 0, 0);
     }
@@ -191,6 +214,11 @@ __global__ __launch_bounds__(256) void attn_causal128_kernel(AttnCausalArgs p) {
         s0[r] = (key0 <= qpos && key0 < L) ? s0[r] : -1e30f;
         s1[r] = (key0 + 32 <= qpos && key0 + 32 < L) ? s1[r] : -1e30f;
       }
+      if (need_low) {
+        const int key0 = key_base + (r & 3) + 8 * (r >> 2), lo = qpos - window + 1;
+        s0[r] = key0 >= lo ? s0[r] : -1e30f;
+        s1[r] = key0 + 32 >= lo ? s1[r] : -1e30f;
+      }
       tmax = fmaxf(tmax, fmaxf(s0[r], s1[r]));
     }
     tmax = fmaxf(tmax, __shfl_xor(tmax, 32));
@@ -206,7 +234,7 @@ __global__ __launch_bounds__(256) void attn_causal128_kernel(AttnCausalArgs p) {
     const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
     l_run = l_run * alpha + psum;
 #pragma unroll
-    for (int f = 0; f < 4; ++f)
+    for (int f = 0; f < D / 32; ++f)
 #pragma unroll
       for (int r = 0; r < 16; ++r) o[f][r] *= alpha;
     m_run = m_new;
@@ -220,7 +248,7 @@ __global__ __launch_bounds__(256) void attn_causal128_kernel(AttnCausalArgs p) {
         for (int i = 0; i < 8; ++i) pf[i] = (half_t)(sub == 0 ? s0[8 * sp + i] : s1[8 * sp + i]);
         const int kb = sub * 32 + 16 * sp + 4 * hh;   // keys kb..kb+3 and kb+8..kb+11 <-> regs 8sp..8sp+7
 #pragma unroll
-        for (int f = 0; f < 4; ++f) {
+        for (int f = 0; f < D / 32; ++f) {
           const half_t* vr = sVt + (f * 32 + l31) * ATC_VSTR + kb;
           const half4 v0 = *(const half4*)vr, v1 = *(const half4*)(vr + 8);
           const half8 vf = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
@@ -232,9 +260,9 @@ __global__ __launch_bounds__(256) void attn_causal128_kernel(AttnCausalArgs p) {
   if (wave_active && qpos < L) {
     // a query always sees its own key, so l_run > 0
     const float inv = 1.0f / l_run;
-    half_t* dst = p.ctx + (size_t)(tok0 + qpos) * p.ldctx + h * 128;
+    half_t* dst = p.ctx + (size_t)(tok0 + qpos) * p.ldctx + h * D;
 #pragma unroll
-    for (int f = 0; f < 4; ++f)
+    for (int f = 0; f < D / 32; ++f)
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         half4 a;
@@ -274,30 +302,285 @@ __global__ __launch_bounds__(256) void attn_causal128_kernel(AttnCausalArgs p) {
 // NW waves x 32 queries per workgroup (4 or 8): a query row's arithmetic does not depend on NW - the same chunks of 64 keys in the
 // same order, the same per-wave decisions - so the host may pick it freely (8: two waves per SIMD inside ONE workgroup, each
 // K / V chunk fetched once for 256 queries; 4: twice the workgroups, shorter critical path of the last query block)
-// The windowed form (Mistral's sliding window, AttnCausalWinArgs::window = W > 0: query i sees keys max(0, i - W + 1) .. i; the entry
-// attn_causal128_dma_win_kernel) differs from the plain one in the chunks it skips and the keys it masks, nothing else - a sequence
-// no longer than W gets the plain kernel's bits from it.  The chunk walk starts at ch0 = the first chunk that holds a visible key
-// of the block's first query: the prologue issues chunk ch0 into stage ch0 & 1 and drains it (vmcnt(0), barrier) exactly as it did
-// chunk 0, and the loop's accounting is unchanged - one chunk in flight, drained at the end of every iteration, stage = ch & 1.
-// A wave skips a chunk that ends below its first query's bound; a chunk that starts below the bound of the wave's last query
-// inside the sequence gets the lower mask (LOW), the causal edge's -1e30 - so a sequence no longer than W runs the very chunk
-// bodies the plain kernel runs.  (A lane whose keys of a chunk are ALL below its bound - the chunk is another lane's - forms
-// weights exp2(0) = 1 against its maximum of -1e30; its own first visible chunk comes later, moves the maximum to a real score and
-// multiplies all of that by alpha = exp2(-1e30 - m) = 0, exactly; alpha != 1, so the accumulators are rescaled.)
-#define ATCD_WIN 0
-#define ATCD_KERNEL attn_causal128_dma_kernel
-#define ATCD_ARGS AttnCausalArgs
-#include "attn_causal128_dma.inc"
-#undef ATCD_WIN
-#undef ATCD_KERNEL
-#undef ATCD_ARGS
-#define ATCD_WIN 1
-#define ATCD_KERNEL attn_causal128_dma_win_kernel
-#define ATCD_ARGS AttnCausalWinArgs
-#include "attn_causal128_dma.inc"
-#undef ATCD_WIN
-#undef ATCD_KERNEL
-#undef ATCD_ARGS
+// The windowed form (WIN, see AttnCausalArgsOf above): the chunk walk starts at ch0 = the first chunk that holds a visible key of
+// the block's first query: the prologue issues chunk ch0 into stage ch0 & 1 and drains it (vmcnt(0), barrier) exactly as the plain
+// kernel does chunk 0, and the loop's accounting is unchanged - one chunk in flight, drained at the end of every iteration, stage
+// = ch & 1.  The lower mask is a second compile-time flag of the chunk body (LOW), so a sequence no longer than W runs the very
+// chunk bodies the plain kernel runs.  (The lane whose chunk is ALL below its bound: alpha = 0 != 1, so the accumulators are rescaled.)
+template <int NW, bool WIN>
+__global__ __launch_bounds__(64 * NW, 2) void attn_causal_dma_kernel(AttnCausalArgsOf<WIN> p) {
+  constexpr int ATCD_QUERIES = 32 * NW;
+  extern __shared__ __attribute__((aligned(16))) unsigned char atcd_smem[];
+  half_t* const sbuf = (half_t*)atcd_smem;
+  // workgroup -> (sequence, head, query block), XCD-aware: consecutive workgroups go to the 8 XCDs in turn, each with its own
+  // L2, so workgroup i belongs to the (sequence, kv head) group 8 (i / 8 / W) + i % 8 - all W = heads-per-group x query-blocks
+  // workgroups that read one K / V pair (0.8 MB at 1.5k tokens) meet in ONE L2 instead of each XCD pulling every pair through the
+  // fabric - and walks that group's query blocks from the last (most keys) to the first, the heads of a kv head side by side
+  const int hpg = p.n_heads / p.n_kv, W = hpg * p.nqb;
+  int grp, w;
+  if (!xcd_decode((int)blockIdx.x, p.n_seq * p.n_kv, W, grp, w)) return;   // uniform for the whole block (xcd_map.h)
+  const int b = grp / p.n_kv, kvh = grp % p.n_kv, h = kvh * hpg + w % hpg, qb = p.nqb - 1 - w / hpg;
+  const int tok0 = p.seq_off[b];
+  const int L = p.seq_off[b + 1] - tok0;
+  const int Q0 = qb * ATCD_QUERIES;
+  if (Q0 >= L) return;                                       // uniform for the whole block
+  if (ATCD_KO(6)) return;
+  const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+  const int q0 = Q0 + wave * 32;
+  const bool active = q0 < L;                                // wave-uniform
+  const half_t* const kbase = p.qkv + (size_t)(p.n_heads + kvh) * 128;
+  const half_t* const vbase = p.qkv + (size_t)(p.n_heads + p.n_kv + kvh) * 128;
+  const int last_q = min(Q0 + ATCD_QUERIES - 1, L - 1);
+  const int nch = (last_q >> 6) + 1;                         // chunks this block of queries can see (causal)
+  // (all of the window's values are formed HERE and only under WIN: inside a generic lambda p.window would be looked up for
+  // WIN = 0 too, and even a dead min() outside this block moved the plain kernel's scalar prologue)
+  int window = 0, ch0 = 0, wlo = 0, wlo_last = 0;
+  if constexpr (WIN) {
+    window = p.window;
+    ch0 = max(Q0 - window + 1, 0) >> 6;                      // the first chunk the block's first query sees
+    wlo = q0 - window + 1;                                   // lower bound of the wave's first query (its lowest)
+    wlo_last = min(q0 + 31, L - 1) - window + 1;             // ... of its last query inside the sequence (its highest)
+  }
+  auto opaque_lane = [&]() {
+    int lane;
+    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane));
+    return lane;
+  };
+  struct LaneCtx { int hh, l31, qpos, kfo0, vfo0; };
+  auto lane_ctx = [&](int lane) {
+    LaneCtx c;
+    c.hh = lane >> 5; c.l31 = lane & 31; c.qpos = q0 + c.l31;
+    c.kfo0 = c.l31 * 64 + ((c.hh ^ ATTD_SWZ(c.l31)) << 3);
+    const int i16 = lane & 15, g1 = (lane >> 4) & 1;
+    c.vfo0 = (4 * c.hh + (i16 >> 2)) * 64 + (((2 * g1 + ((i16 & 3) >> 1)) ^ ((((i16 >> 3) & 1) << 2) | c.hh)) << 3) + 4 * (i16 & 1);
+    return c;
+  };
+  // chunk ch -> stage st: 32 pieces of 64 sixteen-byte slots (8 per image), 32 / NW per wave; keys beyond the sequence are
+  // clamped copies of its last row (never visible to a valid query: causal)
+  auto issue_chunk = [&](int lane, int ch, int st) {
+#pragma unroll
+    for (int k = 0; k < 32 / NW; ++k) {
+      const int pid = wave + NW * k, img = pid >> 3, sub = pid & 7;
+      const int slot = sub * 64 + lane, r = slot >> 3, c = slot & 7;
+      int key = ch * ATCD_KEYS + r;
+      key = key < L ? key : L - 1;
+      const char* hb = (const char*)((img < 2 ? kbase : vbase) + (img & 1) * 64);
+      const unsigned off = ((unsigned)(tok0 + key) * (unsigned)p.ld + ((c ^ ATTD_SWZ(r)) << 3)) * 2u;
+      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(hb + off),
+                                       (__attribute__((address_space(3))) void*)(sbuf + st * ATCD_STAGE_HALFS + img * ATCD_IMG_HALFS + sub * 512),
+                                       16, 0, 0);
+    }
+  };
+
+  // ---- prologue: this lane's Q fragments (8 k16 steps), chunk 0 ----
+  half8 qf[8];
+  {
+    const LaneCtx c = lane_ctx(opaque_lane());
+    const int qrow = c.qpos < L ? c.qpos : L - 1;
+    const half_t* qptr = p.qkv + (size_t)(tok0 + qrow) * p.ld + h * 128 + 8 * c.hh;
+#pragma unroll
+    for (int s = 0; s < 8; ++s) qf[s] = *(const half8*)(qptr + 16 * s);
+  }
+  issue_chunk(opaque_lane(), ch0, ch0 & 1);                  // (the stage of chunk ch is ch & 1 throughout)
+  // (the Q fragments are "used" here so that the compiler's wait for these tracked loads sits in front of the chunk loop and
+  // not at their first MFMA inside it, where it would drain the DMA queue of every chunk)
+  asm volatile("" :: "v"(qf[0]), "v"(qf[1]), "v"(qf[2]), "v"(qf[3]), "v"(qf[4]), "v"(qf[5]), "v"(qf[6]), "v"(qf[7]));
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (ATCD_KO(7)) return;
+
+  f32x16 o[4];
+#pragma unroll
+  for (int f = 0; f < 4; ++f)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) o[f][r] = 0.f;
+  float m_run = -1e30f, l_run = 0.f;                         // l_run: this lane's half of the row sum (the halves meet at the end)
+
+  // scores of the chunk: 8 k16 steps (4 per image) x two 32-key halves; the K fragments of step i + 1 requested before the MFMAs of step i
+  auto qk_chunk = [&](const LaneCtx& c, const half_t* kst, f32x16& s0, f32x16& s1) {
+    const half_t* kb_ = kst + c.kfo0;
+    half8 kf[2][2];
+    auto fetch = [&](int i, half8 (&d)[2]) {
+      const half_t* a = kb_ + (i >> 2) * ATCD_IMG_HALFS + ((c.kfo0 ^ ((i & 3) << 4)) - c.kfo0);
+      d[0] = *(const half8*)a;
+      d[1] = *(const half8*)(a + 32 * 64);
+    };
+    fetch(0, kf[0]);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      if (i + 1 < 8) fetch(i + 1, kf[(i + 1) & 1]);
+      __builtin_amdgcn_sched_barrier(0);
+      if (i == 0) {
+        f32x16 z;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) z[r] = 0.f;
+        s0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf[0][0], qf[0], z, 0, 0, 0);
+        s1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf[0][1], qf[0], z, 0, 0, 0);
+      } else {
+        s0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf[i & 1][0], qf[i], s0, 0, 0, 0);
+        s1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf[i & 1][1], qf[i], s1, 0, 0, 0);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  };
+  // O^T += V^T P^T for one 64-column image of the chunk's V rows (the T5 kernels' pv_tile: transposing reads a k16 step ahead
+  // of their MFMAs, counted lgkmcnt); oa / ob: output columns 0-31 / 32-63 of the image
+  auto pv_image = [&](const LaneCtx& c, const half_t* vimg, const unsigned (&pp)[16], f32x16& oa, f32x16& ob) {
+    const unsigned vb0 = (unsigned)(size_t)(const __attribute__((address_space(3))) half_t*)vimg;
+    unsigned va[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) va[i] = vb0 + 2u * (unsigned)(c.vfo0 ^ (16 * i));
+    half4 v[2][4];
+    auto step = [&](auto gc, half4 (&d)[4]) {
+      constexpr int g = decltype(gc)::value, sub = g >> 1, sp = g & 1;
+      const attd_u32x4 pu = {pp[8 * sub + 4 * sp], pp[8 * sub + 4 * sp + 1], pp[8 * sub + 4 * sp + 2], pp[8 * sub + 4 * sp + 3]};
+      const half8 pf = __builtin_bit_cast(half8, pu);
+      if constexpr (g < 3) asm volatile("s_waitcnt lgkmcnt(4)" : "+v"(d[0]), "+v"(d[1]), "+v"(d[2]), "+v"(d[3]));
+      else asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(d[0]), "+v"(d[1]), "+v"(d[2]), "+v"(d[3]));
+      __builtin_amdgcn_sched_barrier(0);
+      const half8 vf0 = {d[0][0], d[0][1], d[0][2], d[0][3], d[1][0], d[1][1], d[1][2], d[1][3]};
+      const half8 vf1 = {d[2][0], d[2][1], d[2][2], d[2][3], d[3][0], d[3][1], d[3][2], d[3][3]};
+      oa = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf0, pf, oa, 0, 0, 0);
+      ob = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf1, pf, ob, 0, 0, 0);
+    };
+    using std::integral_constant;
+    attd_issue_vt<0>(v[0], va);
+    attd_issue_vt<1>(v[1], va);
+    step(integral_constant<int, 0>{}, v[0]);
+    attd_issue_vt<2>(v[0], va);
+    step(integral_constant<int, 1>{}, v[1]);
+    attd_issue_vt<3>(v[1], va);
+    step(integral_constant<int, 2>{}, v[0]);
+    step(integral_constant<int, 3>{}, v[1]);
+  };
+
+  // one chunk of a wave that sees some of its keys.  MASK: the chunk reaches past the wave's first query (the diagonal);
+  // LOW (WIN only): the chunk starts below the window of the wave's last query
+  auto chunk_body = [&](auto maskc, auto lowc, int ch, int st) {
+    constexpr bool MASK = decltype(maskc)::value, LOW = decltype(lowc)::value;
+    const half_t* kst = sbuf + st * ATCD_STAGE_HALFS;
+    f32x16 s0, s1;
+    if (!ATCD_KO(1)) qk_chunk(lane_ctx(opaque_lane()), kst, s0, s1);
+    else {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) { s0[r] = 0.f; s1[r] = 0.f; }
+      asm volatile("" : "+v"(s0), "+v"(s1));
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    float tmax = -1e30f;
+    if (!ATCD_KO(2)) {
+      const LaneCtx c1 = lane_ctx(opaque_lane());
+      const int key_base = ch * ATCD_KEYS + 4 * c1.hh;       // register r <-> key key_base + (r & 3) + 8 (r >> 2) (+ 32 for s1)
+      const f32x2 sc = {p.scale_log2e, p.scale_log2e};
+#pragma unroll
+      for (int r = 0; r < 16; r += 2) {
+        const f32x2 t0 = f32x2{s0[r], s0[r + 1]} * sc, t1 = f32x2{s1[r], s1[r + 1]} * sc;
+        s0[r] = t0[0]; s0[r + 1] = t0[1]; s1[r] = t1[0]; s1[r + 1] = t1[1];
+        if (MASK) {
+#pragma unroll
+          for (int j = r; j < r + 2; ++j) {
+            const int key0 = key_base + (j & 3) + 8 * (j >> 2);
+            s0[j] = key0 <= c1.qpos ? s0[j] : -1e30f;
+            s1[j] = key0 + 32 <= c1.qpos ? s1[j] : -1e30f;
+          }
+        }
+        if (LOW) {
+          const int lo = c1.qpos - window + 1;
+#pragma unroll
+          for (int j = r; j < r + 2; ++j) {
+            const int key0 = key_base + (j & 3) + 8 * (j >> 2);
+            s0[j] = key0 >= lo ? s0[j] : -1e30f;
+            s1[j] = key0 + 32 >= lo ? s1[j] : -1e30f;
+          }
+        }
+        tmax = attn_max3(tmax, s0[r], s1[r]);
+        tmax = attn_max3(tmax, s0[r + 1], s1[r + 1]);
+      }
+    }
+    // (without a window the chunk's first key is visible to every query of the wave, so the row maximum is a real score)
+    const float m_c = attn_row_max(tmax);
+    const float m_new = attn_max3(m_run, m_c, m_c);
+    float psum = 0.f;
+    if (!ATCD_KO(2)) attn_tile_exp(s0, s1, m_new, psum);
+    unsigned pp[16];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const half2v a = {(half_t)s0[2 * i], (half_t)s0[2 * i + 1]};
+      const half2v b2 = {(half_t)s1[2 * i], (half_t)s1[2 * i + 1]};
+      pp[i] = __builtin_bit_cast(unsigned, a);
+      pp[8 + i] = __builtin_bit_cast(unsigned, b2);
+    }
+    // online merge (m_run starts at -1e30: alpha = 0 and the zero accumulators stay zero on the first chunk); the 64 accumulator
+    // registers are only touched when some lane's maximum moved - multiplying by 1.0f changes no bit
+    const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
+    l_run = l_run * alpha + psum;
+    m_run = m_new;
+    if (!ATCD_KO(2) && __builtin_amdgcn_ballot_w64(alpha != 1.0f)) {
+      const f32x2 a2 = {alpha, alpha};
+#pragma unroll
+      for (int f = 0; f < 4; ++f)
+#pragma unroll
+        for (int r = 0; r < 16; r += 2) {
+          const f32x2 x = f32x2{o[f][r], o[f][r + 1]} * a2;
+          o[f][r] = x[0]; o[f][r + 1] = x[1];
+        }
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    const LaneCtx c3 = lane_ctx(opaque_lane());
+    if (!ATCD_KO(3)) pv_image(c3, kst + 2 * ATCD_IMG_HALFS, pp, o[0], o[1]);
+    __builtin_amdgcn_sched_barrier(0);
+    if (!ATCD_KO(3)) pv_image(c3, kst + 3 * ATCD_IMG_HALFS, pp, o[2], o[3]);
+    __builtin_amdgcn_sched_barrier(0);
+  };
+
+  using T = std::integral_constant<bool, true>; using F = std::integral_constant<bool, false>;
+  for (int ch = ch0; ch < nch; ++ch) {
+    const int st = ch & 1;
+    // the next chunk travels while this one is computed: its stage was last read before the barrier that ended chunk ch - 1
+    if (ch + 1 < nch && !ATCD_KO(0)) issue_chunk(opaque_lane(), ch + 1, st ^ 1);
+    __builtin_amdgcn_sched_barrier(0);
+    // else: every key of the chunk lies after every query of this wave, or (WIN) before every window
+    if (active && ch * ATCD_KEYS <= q0 + 31 && (!WIN || ch * ATCD_KEYS + ATCD_KEYS - 1 >= wlo)) {
+      const bool mask = ch * ATCD_KEYS + ATCD_KEYS - 1 > q0, low = WIN && ch * ATCD_KEYS < wlo_last;
+      if (mask) { if (low) chunk_body(T{}, T{}, ch, st); else chunk_body(T{}, F{}, ch, st); }
+      else { if (low) chunk_body(F{}, T{}, ch, st); else chunk_body(F{}, F{}, ch, st); }
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // chunk ch + 1 has landed (it had this whole chunk to do so)
+    __builtin_amdgcn_s_waitcnt(0xc07f);                    // lgkmcnt(0): every LDS read of this chunk retired
+    if (!ATCD_KO(4)) __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  // ---- context rows: normalise, pack, 16-byte stores (v_permlane32_swap pairs the half-waves' quads into whole octets) ----
+  if (active) {
+    const float l_row = attn_row_sum(l_run);
+    const float inv = 1.0f / l_row;                          // a query always sees its own key: l_row > 0
+    const LaneCtx c4 = lane_ctx(opaque_lane());
+    half_t* dst = p.ctx + (size_t)(tok0 + (c4.qpos < L ? c4.qpos : L - 1)) * p.ldctx + h * 128 + 16 * c4.hh;
+#pragma unroll
+    for (int f = 0; f < 4; ++f) {
+      unsigned pk[8];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        half4 a;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) a[j] = f2h_sat(o[f][4 * q + j] * inv);
+        const auto au = __builtin_bit_cast(__attribute__((ext_vector_type(2))) unsigned, a);
+        pk[2 * q] = au[0]; pk[2 * q + 1] = au[1];
+      }
+      const auto x0 = __builtin_amdgcn_permlane32_swap(pk[0], pk[4], false, false);
+      const auto x1 = __builtin_amdgcn_permlane32_swap(pk[1], pk[5], false, false);
+      const auto y0 = __builtin_amdgcn_permlane32_swap(pk[2], pk[6], false, false);
+      const auto y1 = __builtin_amdgcn_permlane32_swap(pk[3], pk[7], false, false);
+      const attd_u32x4 lo = {x0[0], x1[0], x0[1], x1[1]};
+      const attd_u32x4 hi = {y0[0], y1[0], y0[1], y1[1]};
+      if (c4.qpos < L && !ATCD_KO(5)) {
+        *(attd_u32x4*)(dst + 32 * f) = lo;
+        *(attd_u32x4*)(dst + 32 * f + 8) = hi;
+      }
+    }
+  }
+}
 
 // =========================== incremental decoding: one new row per sequence against a K / V cache ===========================
 // ONE kernel family for both head widths, templated on D = head_dim (128, or 64 with llama_kernels_hd64.h included).

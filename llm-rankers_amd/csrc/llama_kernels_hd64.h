@@ -1,9 +1,9 @@
 // Decoder-only (Llama / Qwen2 family) kernels for gfx950 at head_dim = 64: Llama-3.2-1B, TinyLlama-1.1B, SmolLM2, Qwen2.5-0.5B.
 // The semantics are the ones quoted at the top of llama_kernels.h at this width: rotate_half pairs element i with i + 32, scaling
-// = 64**-0.5, rotary tables [max_pos][32], causal mask, fp32 softmax, repeat_kv.  Here is what is this width's own: the rotation
-// and the prefill attention.  The 128-wide kernels of llama_kernels.h are not touched by anything here; what does not see the
-// head width (bias_add8 / bias_v8 / rope_rot, AttnCausalArgs) is theirs, and so is the decode step (cache fill, cached attention,
-// combine), one family templated on the width that rotates a 64-wide row by rope64_pairs below.
+// = 64**-0.5, rotary tables [max_pos][32], causal mask, fp32 softmax, repeat_kv.  Here is what is this width's own: the rotation, and
+// the numbers of the prefill attention's LDS at this width.  What does not see the head width (bias_add8 / bias_v8 / rope_rot) is llama_kernels.h's, and so are the kernels templated on it:
+// the prefill attention (attn_causal_tile_kernel<64, .>) and the decode step (cache fill, cached attention, combine), which rotates
+// a 64-wide row by rope64_pairs below.
 #pragma once
 #include "llama_kernels.h"
 
@@ -64,34 +64,9 @@ __global__ __launch_bounds__(256) void rope64_kernel(half_t* __restrict__ qkv, c
   }
 }
 
-// Flash-style causal attention, d = 64: attn_causal128_kernel's design at half the width, ONE kernel for every sequence length.
-// AttnCausalArgs as there, with q heads at column 0, k heads at n_heads*64, v heads at (n_heads + n_kv)*64 and ctx [T, ldctx] of
-// n_heads*64 columns.  grid = (ceil(maxL / 128), n_heads, B); 256 threads = 4 waves x 32 queries.  Per 64-key tile: K rows and V
-// TRANSPOSED are staged in LDS (17.5 KiB); S^T = K Q^T by MFMA 32x32x16 (four k16 steps; A = K rows, B = Q^T) so a lane owns ONE
-// query column and the online-softmax state is per-lane scalars; the fp16 probabilities are already in B-operand position for
-// O^T = V^T P^T (two 32-row d fragments).  Tiles above the diagonal are skipped, the diagonal tile is masked per lane.  A row's
-// arithmetic depends on its own sequence only (its position, its keys in tiles of 64 in order): batch-independent.
+// The LDS of the prefill attention at this width (attn_causal_tile_kernel<64, .>, llama_kernels.h): its two row strides as
+// numbers, for the plan's report - the LDS is static, nothing is requested at launch - and for the tests, which read them here.
 #define ATC64_KSTR 72    // sK row stride in halfs (144 B: 16-B aligned)
 #define ATC64_VSTR 68    // sVt row stride in halfs (136 B: 8-B aligned)
 #define ATC64_LDS_BYTES ((64 * ATC64_KSTR + 64 * ATC64_VSTR) * 2)
-// The windowed form (Mistral's sliding window, AttnCausalWinArgs::window = W > 0: query i sees keys max(0, i - W + 1) .. i; the entry
-// attn_causal64_win_kernel) differs from the plain one in the tiles it skips and the keys it masks, nothing else: the tile loop
-// starts at the first tile that holds a visible key of the block's first query, a wave skips a tile that ends below its first
-// query's bound, and a tile that starts below the bound of the wave's last query inside the sequence gets the lower mask - the causal
-// edge's -1e30.  So a sequence no longer than W gets the plain kernel's bits from it.  (A lane whose keys of a tile are ALL below
-// its bound - the tile is another lane's - forms weights exp2(0) = 1 against its maximum of -1e30; its own first visible tile
-// comes later, moves the maximum to a real score and multiplies all of that by alpha = exp2(-1e30 - m) = 0, exactly.)
-#define ATC64_WIN 0
-#define ATC64_KERNEL attn_causal64_kernel
-#define ATC64_ARGS AttnCausalArgs
-#include "attn_causal64.inc"
-#undef ATC64_WIN
-#undef ATC64_KERNEL
-#undef ATC64_ARGS
-#define ATC64_WIN 1
-#define ATC64_KERNEL attn_causal64_win_kernel
-#define ATC64_ARGS AttnCausalWinArgs
-#include "attn_causal64.inc"
-#undef ATC64_WIN
-#undef ATC64_KERNEL
-#undef ATC64_ARGS
+static_assert(ATC64_KSTR == 64 + ATC_KPAD && ATC64_VSTR == ATC_VSTR, "the tile kernel's strides at D = 64");

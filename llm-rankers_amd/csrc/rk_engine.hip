@@ -1276,13 +1276,20 @@ int run_xattn_chain(rk_engine* e, hipStream_t st, const XAttnChain& c, const XAt
 }
 
 // Causal attention of one llama_prefill call (hf: modeling_llama.py:130-214)
+enum CausalAttnKind { CAUSAL_TILE, CAUSAL_DMA };
 struct CausalAttnPlan {
-  bool dma = false; int nw = 0, nqb = 0;   // attn_causal128_dma_kernel<nw>, query blocks of 32 nw; else attn_causal128_kernel
-  bool hd64 = false;                       // attn_causal64_kernel (llama_kernels_hd64.h), every call of a 64-wide engine
-  int window = 0;                          // > 0: the windowed entry of the kernel (attn_causal128_dma_win_kernel / attn_causal64_win_kernel)
-  bool no_win_kernel = false;              // the call needs a windowed kernel and the plan's kernel has none: refuse_window, nothing launched
+  int kind = CAUSAL_TILE, hd = 128;        // attn_causal_tile_kernel<hd, .>, or attn_causal_dma_kernel<nw, .> (128 wide)
+  int nw = 0, nqb = 0;                     // CAUSAL_DMA: waves per workgroup, query blocks of 32 nw
+  int window = 0;                          // > 0: the kernel's windowed entry (WIN = 1)
   dim3 grid; int block = 256, lds = 0, lds_opt_in = 0;
 };
+// ---- which kernels the prefill attention has: THE one statement (the walk and the launch below follow it) ----
+// the register-staged kernel at both widths, windowed at 64 only; the LDS-DMA kernel at 128, plain and windowed.  A caller whose
+// plan is outside it (a window on a 128-wide engine with llama_attn_dma = 0) refuses the call: refuse_window.
+constexpr bool causal_attn_exists(int kind, int D, bool win) {
+  return kind == CAUSAL_TILE ? (D == 64 || (D == 128 && !win)) : (kind == CAUSAL_DMA && D == 128);
+}
+inline bool causal_attn_exists(const CausalAttnPlan& p) { return causal_attn_exists(p.kind, p.hd, p.window > 0); }
 // The sliding window (rk_llama_set_sliding_window: W = e->window) enters here and nowhere else: the windowed entry is planned for a
 // call whose LONGEST sequence exceeds W, the plain kernel otherwise.  That the choice may look at the call at all rests on the
 // windowed kernels' contract (llama_kernels.h): they differ from the plain ones only in chunks they skip and keys they mask, so a
@@ -1293,11 +1300,12 @@ CausalAttnPlan plan_llama_attn(const rk_engine* e, int n_seq, int maxL, int n_he
   if (head_width(e) == 64) {
     // 64-wide heads: ONE kernel for every length, whatever llama_attn_dma / llama_attn_nw say (they choose between 128-wide
     // kernels): plan_enc_attn's D128 precedent.  Static LDS (reported, not requested at launch).
-    p.hd64 = true; p.grid = dim3((maxL + 127) / 128, n_heads, n_seq); p.lds = ATC64_LDS_BYTES;
+    p.hd = 64; p.grid = dim3((maxL + 127) / 128, n_heads, n_seq); p.lds = ATC64_LDS_BYTES;
     return p;
   }
-  p.dma = e->opt.llama_attn_dma;   // K / V chunks by LDS-DMA, V^T by transposing reads (round 5); chosen by the option alone: batch-independent
-  if (!p.dma) { p.grid = dim3((maxL + 127) / 128, n_heads, n_seq); p.no_win_kernel = p.window > 0; return p; }   // attn_causal128_kernel has no windowed form
+  // K / V chunks by LDS-DMA, V^T by transposing reads (round 5); chosen by the option alone: batch-independent
+  if (!e->opt.llama_attn_dma) { p.grid = dim3((maxL + 127) / 128, n_heads, n_seq); return p; }   // (no windowed form: causal_attn_exists)
+  p.kind = CAUSAL_DMA;
   p.nw = e->opt.llama_attn_nw == 8 ? 8 : 4;   // same bits either way
   p.nqb = (maxL + 32 * p.nw - 1) / (32 * p.nw); p.grid = dim3(xcd_grid(n_seq * n_kv, (n_heads / n_kv) * p.nqb));
   p.block = 64 * p.nw; p.lds = p.lds_opt_in = ATCD_LDS_BYTES;
@@ -1310,29 +1318,44 @@ CausalAttnPlan plan_llama_attn(const rk_engine* e, int n_seq, int maxL, int n_he
 
 // what the launcher reads of a call: llama_prefill fills it from its slot and the model, rk_debug_attn from host operands
 struct CausalAttnCall { const half_t* qkv; half_t* ctx; const int* seq_off; int ld, ldctx, n_heads, n_kv, n_seq, maxL, T; };
+// The one walk from a plan to the template arguments: f(kind, D, NW, WIN), each an integral_constant (NW = 0 for the tile kind).
+// A plan outside causal_attn_exists is a host bug and aborts HERE (the callers refuse it first).
+template <class Fn>
+void with_causal_attn(const CausalAttnPlan& p, Fn&& f) {
+  using std::integral_constant;
+  with_int<CAUSAL_TILE, CAUSAL_DMA>(p.kind, [&](auto k) {
+    with_width(p.hd, [&](auto d) {
+      with_int<0, 1>(p.window > 0, [&](auto w) {
+        auto go = [&](auto nw) {
+          constexpr bool W = decltype(w)::value != 0;
+          if constexpr (causal_attn_exists(decltype(k)::value, decltype(d)::value, W)) f(k, d, nw, std::bool_constant<W>());
+          else abort();
+        };
+        if constexpr (decltype(k)::value == CAUSAL_TILE) go(integral_constant<int, 0>{});
+        else switch (p.nw) {
+          case 8: go(integral_constant<int, 8>{}); break;
+          case 4: go(integral_constant<int, 4>{}); break;
+          default: abort();
+        }
+      });
+    });
+  });
+}
 void launch_llama_attn(rk_engine* e, hipStream_t st, const CausalAttnCall& c, const CausalAttnPlan& p) {
-  const int hd = p.hd64 ? 64 : 128;
-  const int T = c.T, Q = c.n_heads * hd, KV = c.n_kv * hd;
-  const float scale_log2e = (1.0f / std::sqrt((float)hd)) * 1.4426950408889634f;   // head_dim**-0.5 * log2(e)
+  const int T = c.T, Q = c.n_heads * p.hd, KV = c.n_kv * p.hd;
+  const float scale_log2e = (1.0f / std::sqrt((float)p.hd)) * 1.4426950408889634f;   // head_dim**-0.5 * log2(e)
   AttnCausalArgs a{c.qkv, c.ctx, c.seq_off, c.ld, c.ldctx, c.n_heads, c.n_kv, scale_log2e, 0, 0, e->opt.attn_ko};
+  if (p.kind == CAUSAL_DMA) { a.n_seq = c.n_seq; a.nqb = p.nqb; }
   Bracket br(e, st, PC_ENC_ATTN, 2.0 * (double)c.maxL * T * Q, (double)T * (2 * Q + 2 * KV) * 2.0);   // causal: half of 4 L T Q
-  if (p.no_win_kernel) abort();                              // (the callers refuse such a plan: refuse_window)
-  if (p.hd64) {
-    if (p.window > 0) hipLaunchKernelGGL(attn_causal64_win_kernel, p.grid, dim3(p.block), 0, st, AttnCausalWinArgs{a, p.window});
-    else hipLaunchKernelGGL(attn_causal64_kernel, p.grid, dim3(p.block), 0, st, a);
-    return;
-  }
-  if (!p.dma) { hipLaunchKernelGGL(attn_causal128_kernel, p.grid, dim3(p.block), 0, st, a); return; }
-  a.n_seq = c.n_seq; a.nqb = p.nqb;
-  if (p.window > 0) {
-    const AttnCausalWinArgs w{a, p.window};
-    if (p.nw == 8) launch_lds<attn_causal128_dma_win_kernel<8>>(st, p.grid, p.block, p.lds, p.lds_opt_in, w);
-    else launch_lds<attn_causal128_dma_win_kernel<4>>(st, p.grid, p.block, p.lds, p.lds_opt_in, w);
-  } else if (p.nw == 8) launch_lds<attn_causal128_dma_kernel<8>>(st, p.grid, p.block, p.lds, p.lds_opt_in, a);
-  else launch_lds<attn_causal128_dma_kernel<4>>(st, p.grid, p.block, p.lds, p.lds_opt_in, a);
+  with_causal_attn(p, [&](auto k, auto d, auto nw, auto w) {
+    constexpr bool WIN = decltype(w)::value;
+    const auto args = [&] { if constexpr (WIN) return AttnCausalWinArgs{a, p.window}; else return a; }();
+    if constexpr (decltype(k)::value == CAUSAL_DMA) launch_lds<attn_causal_dma_kernel<decltype(nw)::value, WIN>>(st, p.grid, p.block, p.lds, p.lds_opt_in, args);
+    else hipLaunchKernelGGL((attn_causal_tile_kernel<decltype(d)::value, WIN>), p.grid, dim3(p.block), 0, st, args);
+  });
 }
 int refuse_window(rk_engine* e, const char* entry, int maxL) {
-  return fail(e, RK_ERR_STATE, "%s: a sequence of %d tokens on an engine with sliding window %d needs a windowed attention kernel, and option llama_attn_dma = 0 selects attn_causal128_kernel, which has none", entry, maxL, e->window);
+  return fail(e, RK_ERR_STATE, "%s: a sequence of %d tokens on an engine with sliding window %d needs a windowed attention kernel, and option llama_attn_dma = 0 selects attn_causal_tile_kernel<128>, which has none", entry, maxL, e->window);
 }
 
 // Single-token attention of one rk_llama_generate step over the K / V cache of P positions per sequence: the chunk kernel over
@@ -2999,7 +3022,7 @@ static int llama_prefill(rk_engine* e, const int32_t* tokens, const int32_t* off
   const rk_llama_desc& l = e->ld;
   const int hd = l.head_dim, T = sl.T, dm = l.hidden, Q = l.n_heads * hd, KV = l.n_kv_heads * hd, F = l.intermediate, ldq = Q + 2 * KV;
   const CausalAttnPlan ap = plan_llama_attn(e, n_seq, sl.maxL, l.n_heads, l.n_kv_heads);
-  if (ap.no_win_kernel) return refuse_window(e, "llama prefill", sl.maxL);
+  if (!causal_attn_exists(ap)) return refuse_window(e, "llama prefill", sl.maxL);
   hipStream_t st = sl.se;
   HIPCHK(e, hipStreamSynchronize(st));
   std::vector<int> pos(T), last(n_seq);

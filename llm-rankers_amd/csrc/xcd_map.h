@@ -1,4 +1,4 @@
-// Workgroup -> (group, item) mapping of the attention kernels whose workgroups SHARE data per group (attn_causal128_dma_kernel:
+// Workgroup -> (group, item) mapping of the attention kernels whose workgroups SHARE data per group (attn_causal_dma_kernel:
 // group = (sequence, kv head), items = heads-per-kv-head x query blocks; attn_enc_long_kernel: group = (sequence, head), items =
 // query blocks).  Consecutive workgroups of a 1-D grid go to the 8 XCDs of an MI355X in turn, each XCD with its own L2: workgroup
 // i therefore takes group 8 (i / 8 / W) + i % 8, item (i / 8) % W - all W workgroups of a group run on ONE XCD, in item order,

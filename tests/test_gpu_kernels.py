@@ -1160,7 +1160,7 @@ def test_llama_3_8b_widths_one_compare_vs_oracle():
 
 
 def test_llama_attention_by_lds_dma_vs_oracle_first_kernel_and_batch_independence():
-    """attn_causal128_dma_kernel (round 5: K / V chunks of 64 keys by LDS-DMA, V^T by transposing reads; engine option
+    """attn_causal_dma_kernel (round 5: K / V chunks of 64 keys by LDS-DMA, V^T by transposing reads; engine option
     llama_attn_dma): the last-position logits of MANY PREFIXES of one 700-token sequence - the logits of many positions: every
     chunk count, the diagonal chunk at both halves, query-block boundaries, a one-token sequence - against the fp32 oracle (as
     close as the register-staged kernel), the two kernels within fp16 noise of each other, and batch independence: a prefix

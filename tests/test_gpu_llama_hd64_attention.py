@@ -26,7 +26,7 @@ pytestmark = pytest.mark.gpu
 
 BAND = 8
 ERR_HIP = -3
-KIND_HD64 = 2                       # rk_debug_attn kind 4: out_kind 0 / 1 = the 128-wide kernels, 2 = attn_causal64_kernel
+KIND_HD64 = 2                       # rk_debug_attn kind 4: out_kind 0 / 1 = the 128-wide kernels, 2 = attn_causal_tile_kernel<64>
 RATIOS = {}
 HEADS = [(4, 2), (7, 1), (3, 3)]
 

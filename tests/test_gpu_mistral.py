@@ -1,5 +1,5 @@
 """Sliding-window attention (Mistral family) on the HIP engine, end to end and at kernel level: the windowed entries of the prefill
-kernels (attn_causal128_dma_win_kernel, attn_causal64_win_kernel) and of the decode step (attn_dec_cached_win_kernel,
+kernels (attn_causal_dma_kernel<., 1>, attn_causal_tile_kernel<64, 1>) and of the decode step (attn_dec_cached_win_kernel,
 attn_dec_combine_win_kernel) behind rk_llama_set_sliding_window.  Two toys - TOY_LLAMA's shape (128-wide heads) and TOY_LLAMA_HD64's
 (64-wide) - at windows W = 1, 5, 33, 64, 100, 128, 129, 200: below a wave's 32 queries, off every 32 / 64 / 128 boundary, exactly one
 decode chunk, one key into the next chunk, spanning two chunks.
@@ -334,7 +334,7 @@ def _raw_prefill_call(eng, p):
 
 
 def test_register_staged_prefill_kernel_refuses_a_call_longer_than_the_window():
-    """llama_attn_dma = 0 selects attn_causal128_kernel, which has no windowed form: RK_ERR_STATE naming the option and the window, the
+    """llama_attn_dma = 0 selects attn_causal_tile_kernel<128>, which has no windowed form: RK_ERR_STATE naming the option and the window, the
     debug call's output all sentinel; a call that fits the window runs; the 64-wide engine has one kernel and ignores the option"""
     import _attn_ref as A
     dims = dataclasses.replace(_synth.TOY_MISTRAL, sliding_window=48)

@@ -31,7 +31,10 @@ def isa(tmp_path_factory):
 
 
 def kernel_body(lines, mangled):
-    start = next(i for i, l in enumerate(lines) if l.startswith(mangled + ":"))
+    """the body of the one kernel whose mangled name is `mangled` or, for a prefix that ends in the template arguments, begins with it"""
+    starts = [i for i, l in enumerate(lines) if re.match(re.escape(mangled) + r"\w*:", l)]
+    assert len(starts) == 1, (mangled, [lines[i] for i in starts])
+    start = starts[0]
     end = next(i for i in range(start, len(lines)) if lines[i].startswith(".Lfunc_end"))   # (a kernel may hold several s_endpgm)
     return lines[start:end + 1]
 
@@ -249,9 +252,9 @@ def test_long_sequence_attention_keeps_its_dma_in_flight(isa, nw, max_vgprs):
 
 @pytest.mark.parametrize("nw", [4, 8])
 def test_llama_dma_attention_keeps_its_dma_in_flight(isa, nw):
-    """attn_causal128_dma_kernel: the next 64-key chunk (K and V, two 64-column images each) travels by LDS-DMA while the current one
+    """attn_causal_dma_kernel<nw, 0>: the next 64-key chunk (K and V, two 64-column images each) travels by LDS-DMA while the current one
     is computed; no compiler-placed vmcnt wait between the chunk bodies, no spills, two workgroups per CU (<= 256 VGPRs, 64 KiB)."""
-    body = kernel_body(isa, f"_Z25attn_causal128_dma_kernelILi{nw}EEv14AttnCausalArgs")
+    body = kernel_body(isa, f"_Z22attn_causal_dma_kernelILi{nw}ELb0E")
     assert not any("scratch_" in l for l in body), "Llama DMA attention kernel spills"
     m = re.search(r"NumVgprs: (\d+)", "\n".join(isa[isa.index(body[-1]):isa.index(body[-1]) + 400]))
     assert m and int(m.group(1)) <= 256, m and m.group(1)

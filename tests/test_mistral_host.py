@@ -408,13 +408,15 @@ def test_windowed_kernels_isa(tmp_path_factory):
                     os.path.join(REPO, "llm-rankers_amd", "csrc", "rk_engine.hip"), "-o", str(out)], check=True, timeout=600)
     lines = out.read_text().split("\n")
 
-    def body(mangled):
-        start = next(i for i, l in enumerate(lines) if l.startswith(mangled + ":"))
+    def body(mangled):                       # (a name, or a prefix that ends in the template arguments: exactly one kernel)
+        starts = [i for i, l in enumerate(lines) if re.match(re.escape(mangled) + r"\w*:", l)]
+        assert len(starts) == 1, (mangled, [lines[i] for i in starts])
+        start = starts[0]
         end = next(i for i in range(start, len(lines)) if lines[i].startswith(".Lfunc_end"))
         return lines[start:end + 1], "\n".join(lines[end:end + 400])
 
     for nw in (4, 8):
-        code, meta = body(f"_Z29attn_causal128_dma_win_kernelILi{nw}EEv17AttnCausalWinArgs")
+        code, meta = body(f"_Z22attn_causal_dma_kernelILi{nw}ELb1E")
         assert not any("scratch_" in l for l in code) and re.search(r"ScratchSize: 0\b", meta)
         assert int(re.search(r"NumVgprs: (\d+)", meta).group(1)) <= 256
         assert sum("global_load_lds_dwordx4" in l for l in code) == 2 * 32 // nw
@@ -424,7 +426,7 @@ def test_windowed_kernels_isa(tmp_path_factory):
         for i in range(first, last):
             if "vmcnt" in code[i].split(";")[0]:
                 assert "ASMSTART" in code[i - 1], f"compiler-placed vmcnt wait between the chunk bodies: {code[i].strip()}"
-    code, meta = body("_Z24attn_causal64_win_kernel17AttnCausalWinArgs")
+    code, meta = body("_Z23attn_causal_tile_kernelILi64ELb1E")
     assert not any("scratch_" in l for l in code) and re.search(r"ScratchSize: 0\b", meta)
     for d in (128, 64):
         for r in (1, 2, 4, 8) + ((7,) if d == 128 else ()):

@@ -1,5 +1,5 @@
 """Workgroup -> (group, item) mapping of the XCD-aware attention launches (llm-rankers_amd/csrc/xcd_map.h), checked on the host:
-the header is plain integer arithmetic shared with the kernels (attn_causal128_dma_kernel, attn_enc_long_kernel), compiled here
+the header is plain integer arithmetic shared with the kernels (attn_causal_dma_kernel, attn_enc_long_kernel), compiled here
 with g++.  For every (groups, W): the grid covers every (group, item) exactly once, the padding workgroups are rejected, all
 workgroups of one group are congruent mod 8 (= run on one XCD under the round-robin dispatch) and come in item order."""
 import os

@@ -5,7 +5,7 @@
   generate    rk_llama_generate at 1 and 8 rows of 1 536 tokens: the prefill (call with 1 new token) and ms per step
               ((call with 65 new tokens - call with 1) / 64)
   attention   the prefill attention per layer from the engine's profile classes (enc_attn ms / launches of one greedy1 call):
-              attn_causal64_kernel at 32 / 8 heads of 64 next to attn_causal128_kernel (option llama_attn_dma = 0) and the LDS-DMA
+              attn_causal_tile_kernel<64> at 32 / 8 heads of 64 next to attn_causal_tile_kernel<128> (option llama_attn_dma = 0) and the LDS-DMA
               kernel (= 1) on a twin model with 16 / 4 heads of 128 - equal FLOPs, equal q width, the same prompt
 
 Appends one JSON line to profiles/llama_hd64_bench.txt.  The numbers gate nothing.  RK_LAYERS shortens the model for a quick look."""

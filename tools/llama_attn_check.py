@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Llama causal attention by LDS-DMA (llama_kernels.h: attn_causal128_dma_kernel, engine option llama_attn_dma) on the GPU:
+"""Llama causal attention by LDS-DMA (llama_kernels.h: attn_causal_dma_kernel, engine option llama_attn_dma) on the GPU:
 (1) toy Llama (2 layers, grouped-query): the last-position logits of MANY PREFIXES of one 700-token sequence - i.e. the logits
 of many positions, every chunk / diagonal / block-boundary case - with either kernel against the fp32 oracle and against each
 other; (2) batch independence: every prefix alone gives the bits it has inside the batch; (3) Llama-3-8B widths (RK_LAYERS

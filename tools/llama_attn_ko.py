@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Where the time of attn_causal128_dma_kernel goes: timing-only knock-outs of a measurement build
+"""Where the time of attn_causal_dma_kernel goes: timing-only knock-outs of a measurement build
 (hipcc ... -DRK_MEASURE -o exp/librk_engine_measure.so; RK_ENGINE_LIB=exp/librk_engine_measure.so python tools/llama_attn_ko.py).
 Llama-3-8B widths, RK_LAYERS layers (pool weights), one and four 1 536-token prompts; results of knocked-out runs are garbage."""
 import json, os, sys
