@@ -392,24 +392,22 @@ void launch_pp2(hipStream_t st, const GemmArgs& a, int max_wgs) {
 // time ~ rounds over the resident slots x the variant's time for one round of K = 1024 (us, MI355X, tools/gemm_bench.py
 // at M = 736 .. 23552, profiles/r01c_gemm_bench.txt, r01e_gemm_pingpong.txt).  All variants sum K in the same order, so
 // the choice never changes a result bit.  GEGLU pairs gate/up inside 64-row wave tiles: no 192-wide tile for it.
-// K split of the ping-pong kernel (gemm.h: SPLIT): only the fp32 residual projections (O / FFN-out, Llama o / down), only TWO ways,
-// only when the launch has at most half as many 256 x 256 tiles as the chip has CUs and K >= 6 144 (96 K tiles).  Measured
-// (profiles/r06_gemm_ksplit.txt, M = 1 536, N = 4 096): K = 14 336 281.6 -> 212.0 us, K = 8 192 155.9 -> 123.6 us, K = 4 096
-// 76.9 -> 75.1 us (not worth a different rounding); three / four ways lose (every slab is published and re-read).  Needs the
-// workspace of the launch's stream (plan_gemm).  flan-t5-large / -xl never qualify (K <= 5 120); t5-3b would and is kept off it (below).
+// K split of the ping-pong kernel (gemm.h: SPLIT): the fp32 epilogues, TWO ways - and by option only (gemm_sk = 2: the hand-off tests,
+// measurement).  The default (gemm_sk = 1) never splits.  The split rounds differently from the unsplit sum, and the one rule that
+// ever paid - at most half as many 256 x 256 tiles as the chip has CUs and K >= 6 144 (profiles/r06_gemm_ksplit.txt, M = 1 536,
+// N = 4 096: K = 14 336 281.6 -> 212.0 us, K = 8 192 155.9 -> 123.6 us; three / four ways lose) - reads the TILE COUNT of the launch,
+// i.e. how many tokens share the call: a sequence alone, in a call of 1 537 .. 4 096 tokens and in a larger one got different last
+// bits of `down`, and behind a whole ping-pong round (plan_gemm: m_pp2) even by its place in the batch - while a sequence's logits,
+// scores and tokens are promised not to depend on what shares its call (include/rk_engine.h), on T5 as on Llama.  First seen on t5-3b
+// (FFN-out N = 1 024, K = 16 384: tests/test_gpu_t5_d128.py), then at the plan lines of the Llama prefill
+// (tests/test_gpu_llama_plan_lines.py, which also sweeps this rule over the served widths); what it cost: profiles/llama_ksplit_rule.txt.
+// A rule that splits again has to read (N, K, family, options, CU count) alone, AND every kernel a call of other size may take at
+// that (N, K) - the 64x64 variant, the launches with more tiles - has to sum K in the split's order.  Needs the workspace of the
+// launch's stream (plan_gemm).
 int choose_ksplit(const rk_engine* e, int epi, int M, int N, int K) {
-  if (!e->opt.gemm_sk || !(epi == EPI_RESID_F32 || epi == EPI_STORE_F32) || K % 64) return 1;
+  if (e->opt.gemm_sk != 2 || !(epi == EPI_RESID_F32 || epi == EPI_STORE_F32) || K % 64) return 1;
   const long tiles = (long)((M + 255) / 256) * ((N + 255) / 256);
-  const int wgs = e->n_cu & ~7, nk = K / 64;
-  if (e->opt.gemm_sk == 2)                                             // tests / measurement: two ways wherever they fit
-    return (nk >= 4 && tiles * 2 <= KSPLIT_MAX_SLABS) ? 2 : 1;
-  if (epi != EPI_RESID_F32 || tiles < 1 || tiles * 2 > wgs || nk < 96) return 1;
-  // T5: never by this rule.  The split rounds differently from the unsplit sum and is decided from the TILE COUNT of the launch, i.e.
-  // from the batch - and a T5 sequence's logits are promised not to depend on what shares its call.  No T5 shape qualified until
-  // t5-3b (FFN-out: N = 1 024, K = 16 384), where 32 sequences took the split and two of them alone did not
-  // (tests/test_gpu_t5_d128.py); the Llama prefill (o / down projections), which the rule was measured on, keeps it.
-  if (e->family == 0) return 1;
-  return 2;
+  return (K / 64 >= 4 && tiles * 2 <= KSPLIT_MAX_SLABS) ? 2 : 1;    // two ways wherever they fit
 }
 
 int choose_variant(const rk_engine* e, int epi, int M, int N, int K, bool fold_producer, double* cost_out) {
@@ -427,7 +425,6 @@ int choose_variant(const rk_engine* e, int epi, int M, int N, int K, bool fold_p
     if (v.id == 5 && K < 128) continue;
     const long tiles = (long)((M + v.bm - 1) / v.bm) * ((N + v.bn - 1) / v.bn);
     double cost = (double)((tiles + v.slots - 1) / v.slots) * v.round_us;
-    if (v.id == 5 && e->opt.gemm_sk == 1 && choose_ksplit(e, epi, M, N, K) > 1) cost = 0.0;   // the K-split launch wins wherever it is eligible (measured)
     if (cost < best - 1e-9) { best = cost; bv = v.id; }
   }
   *cost_out = best;
@@ -3863,7 +3860,7 @@ const OptionDesc kOptions[] = {
   {"dec_gemv_rows", &rk_engine::Options::dec_gemv_rows, 1, GEMV_MAX_ROWS, nullptr, "largest row count of a decoder pass that takes the few-row GEMV family (default 4 = the measured cross-over; the kernel takes up to 16)"},
   {"dec_cross_mfma", &rk_engine::Options::dec_cross_mfma, 0, 1, nullptr, "long decoder prefixes (qlm), cross-attention over the materialised K / V: matrix-core kernel for sequences <= 192 keys (1) or the staged fma-chain kernels (0); differ within fp16 noise"},
   {"dec_attn_seq", &rk_engine::Options::dec_attn_seq, 0, 1, nullptr, "decoder attention at several positions: one workgroup per (head, sequence) (1) or per query row (0); same bits"},
-  {"gemm_sk", &rk_engine::Options::gemm_sk, 0, 2, nullptr, "ping-pong GEMM, fp32 residual projections with few tiles and a long K: K split over two workgroups (1: choose_ksplit), never (0), wherever it fits (2: tests)"},
+  {"gemm_sk", &rk_engine::Options::gemm_sk, 0, 2, nullptr, "ping-pong GEMM, K split of the fp32 epilogues over two workgroups: wherever it fits (2: tests, measurement), else never (0, 1 = default: choose_ksplit - a split chosen from the launch's tile count would make a sequence's bits depend on its batch)"},
   {"dec_cached_attn", &rk_engine::Options::dec_cached_attn, 0, 1, nullptr, "rk_t5_generate's self-attention: attn_dec_cached_kernel (1) or the cache append + attn_dec_kernel's tree form (0); same bits"},
   {"llama_dec_r", &rk_engine::Options::llama_dec_r, 0, 2, nullptr, "rk_llama_generate's attention: query heads per workgroup by plan_llama_dec_attn's rule (0), one (1), or, where a kv head has 7, all seven (2: measurement and tests; every cached K / V byte read once per step); same bits"},
   {"enc_serial", &rk_engine::Options::enc_serial, 0, 1, nullptr, "two slots: an encoder chain starts behind the other slot's (1: one encoder at a time beside the decoder before it) or as soon as it is enqueued (0: two chains interleave); same bits"},

@@ -202,6 +202,22 @@ class DebugCalls:
         width = -(-N // 32) if blocks else (n_split if n_split else (N // 2 if gated else N))
         lda, ldw, ldc = lda or K, ldw or K, ldc or width
         dt, per = GEMM_OUT_DTYPE[epi], (2 if epi == 7 else 1)
+        if plan_only:
+            # the plan reads shapes, strides and WHICH operands are there, never their bytes (rk_debug_gemm_ex returns in front of
+            # its extent checks): one word stands for every array, so a sweep over M costs no M-sized allocation
+            q = RkDebugGemmCall()
+            q.epi, q.family, q.M, q.N, q.K, q.lda, q.ldw, q.ldc, q.c_off = epi, family, M, N, K, lda, ldw, ldc, c_off
+            q.n_split, q.split_stride, q.batch, q.bsA, q.bsW, q.bsC = n_split, split_stride, batch, bsA, bsW, bsC
+            word = np.zeros(4, dtype=np.float32)
+            if rowscale is not None:
+                q.rowscale = word.ctypes.data
+            if ssq_in is not None:
+                q.ssq_in, q.nb_in, q.factors_kernel = word.ctypes.data, np.shape(ssq_in)[1], int(factors_kernel)
+            if producer:
+                q.xraw_out = q.ssq_out = word.ctypes.data
+            q.plan_only = 1
+            self._chk(getattr(self.lib, entry)(self.h, C.byref(q)))
+            return _out_fields(q)
         if c_in is None:
             nsb = -(-N // n_split) if n_split else 1
             c_elems = c_off + (batch - 1) * bsC + (nsb - 1) * split_stride + M * ldc
@@ -238,11 +254,8 @@ class DebugCalls:
             assert labels.size == M
             xlab = _sentinel(M, np.float32)
             q.labels, q.xlab = labels.ctypes.data, xlab.ctypes.data
-        q.plan_only = int(plan_only)
         self._chk(getattr(self.lib, entry)(self.h, C.byref(q)))
         out = _out_fields(q)
-        if plan_only:
-            return out
         out.update(C=c_out, band=band, idx=idx, xlab=xlab, ldc=ldc, c_elems=c_elems)
         if producer:
             out.update(xraw=xraw, ssq=ssq[:rows_all * q.out_nb].reshape(rows_all, q.out_nb))

@@ -250,36 +250,39 @@ def test_row_factors_with_new_data_per_launch_tier_b(eng, epi, k):
                 assert _interior(r, i, M3).tobytes() == alone[i].tobytes(), f"{what}: launch {i} differs from the call alone"
 
 
-# ---- T4: the default rule engages ------------------------------------------------------------------------------------------------
-def test_default_rule_splits_the_down_projection_and_the_chain_equals_the_calls_alone(llama):
-    """gemm_sk = 1, gemm_variant = 0 (the defaults) on a decoder-only engine: a `down`-shaped fp32 residual call plans the ping-pong
-    kernel with ksplit = 2 on the slot stream (choose_ksplit; (700, 516, 14336) does not: so few tiles go to the 64x64 kernel);
-    three launches with new data match the alone calls byte for byte."""
+# ---- T4: the `down` shape, split by option; the default rule never splits -----------------------------------------------------------
+def test_down_shape_split_chain_equals_the_calls_alone_and_the_default_rule_never_splits(llama):
+    """The defaults (gemm_sk = 1, gemm_variant = 0) on a decoder-only engine plan NO K split: not for a `down`-shaped fp32 residual
+    call on the slot stream, not for (700, 516, 14336) - the split would be decided from the launch's tile count, i.e. from the
+    batch, and a sequence's bits are promised not to depend on it (choose_ksplit; tests/test_gpu_llama_plan_lines.py).  The
+    hand-off at that shape stays covered under gemm_variant = 5, gemm_sk = 2: the ping-pong kernel with ksplit = 2, three launches
+    with new data match the alone calls byte for byte."""
     m, n, k, nl = 1536, 4096, 14336, 3
     epi = R.EPI_RESID_F32
     z = np.zeros((1, 8), np.float16)
     small = llama.debug_gemm_chain(epi, z, z, 700, 516, 14336, plan_only=True)
     assert small["ksplit"] == 1 and small["variant"] == 6, small
     plan = llama.debug_gemm_chain(epi, z, z, m, n, k, plan_only=True)
-    assert (plan["family"], plan["variant"], plan["m_pp2"], plan["ksplit"]) == (R.TILED, 5, 0, 2), plan
+    assert (plan["family"], plan["m_pp2"], plan["ksplit"]) == (R.TILED, 0, 1), plan
     rs = np.random.RandomState(4900)
     w = (rs.randint(-2048, 2049, size=(n, k), dtype=np.int16).astype(np.float32) / 1024.0).astype(np.float16)   # uniform in [-2, 2]
     a = (rs.randint(-2048, 2049, size=(nl, m, k), dtype=np.int16).astype(np.float32) / 1024.0).astype(np.float16)
     c_old = rs.standard_normal((nl, m, n)).astype(np.float32)
     rows = np.unique(np.linspace(0, m - 1, 16).round().astype(int))            # the fp64 check: a sample of rows and columns
     cols = np.unique(np.linspace(0, n - 1, 256).round().astype(int))
-    alone = []
-    for i in range(nl):
-        o = llama.debug_gemm_ex(epi, R.TILED, a[i], w, m, n, k, c_in=c_old[i])
-        assert (o["variant"], o["ksplit"]) == (5, 2)
-        got = o["C"][o["band"]:o["band"] + m * n].reshape(m, n)
-        R.check_f32(got[np.ix_(rows, cols)], R.acc64(a[i][rows], w[cols]) + c_old[i][np.ix_(rows, cols)], R.tau(a[i], w), f"down alone {i}")
-        alone.append(got)
-    r = llama.debug_gemm_chain(epi, a, w, m, n, k, c_in=c_old)
-    assert r["ksplit"] == 2
-    _bands_intact(r, "down chain")
-    for i in range(nl):
-        assert _interior(r, i, m).tobytes() == alone[i].tobytes(), f"down projection: launch {i} differs from the call alone"
+    with Options(llama, gemm_variant=5, gemm_sk=2):
+        alone = []
+        for i in range(nl):
+            o = llama.debug_gemm_ex(epi, R.TILED, a[i], w, m, n, k, c_in=c_old[i])
+            assert (o["variant"], o["ksplit"]) == (5, 2)
+            got = o["C"][o["band"]:o["band"] + m * n].reshape(m, n)
+            R.check_f32(got[np.ix_(rows, cols)], R.acc64(a[i][rows], w[cols]) + c_old[i][np.ix_(rows, cols)], R.tau(a[i], w), f"down alone {i}")
+            alone.append(got)
+        r = llama.debug_gemm_chain(epi, a, w, m, n, k, c_in=c_old)
+        assert r["ksplit"] == 2
+        _bands_intact(r, "down chain")
+        for i in range(nl):
+            assert _interior(r, i, m).tobytes() == alone[i].tobytes(), f"down projection: launch {i} differs from the call alone"
 
 
 # ---- T5: refusals ------------------------------------------------------------------------------------------------------------

@@ -103,8 +103,8 @@ def test_pingpong_gemm_random_shapes_bit_equal_to_lockstep_kernel(toy):
 def test_k_split_pingpong_gemm_vs_numpy_unsplit_kernel_and_deterministic(toy):
     """gemm_pp2_kernel<.., SPLIT> (round 6): two workgroups share an output tile, each sums a contiguous K range, the first
     arriver's fp32 partial tile travels as a write-through slab and the LAST arriver adds it to its registers.  Option gemm_sk = 2
-    forces the split wherever every half keeps two K tiles (the shipped heuristic, gemm_sk = 1, only splits the fp32 residual
-    projections of launches with few tiles and K >= 6 144).  (1) vs numpy at the fp16-input tolerance; (2) vs the unsplit kernel: equal to
+    forces the split wherever every half keeps two K tiles (the default, gemm_sk = 1, never splits: a split chosen from a launch's
+    tile count would make a row's bits depend on its batch).  (1) vs numpy at the fp16-input tolerance; (2) vs the unsplit kernel: equal to
     fp32 re-association noise; (3) each shape three times: bit-identical runs (fixed combine order, tickets reset by the last
     arriver), also right after another shape used the same slabs; (4) K too short for the split: the unsplit bits."""
     eng = toy["ckpt_gated_untied"][2]
